@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- particle-substeps/s of the SPH substep hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one DispatchCompute (ClearGrid -> BuildGrid -> SPHFluid -> OBBConstraints, the
 call of SPHFluid3D.cpp:431-522) over the whole particle set, inputs resident in HBM.
@@ -10,6 +10,11 @@ configuration the metric is quoted on.  N > 1 runs BASELINE.json configs[4]: eve
 256 x 256 x 64-cell slab with 8 388 608 particles (weak scaling along z), OBBConstraints on,
 ApplyWaveImpulse every 16th substep, one-deep halo exchange per substep -- see DESIGN.md
 "Multi-GPU".  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs is given and
+prints the line (metric, value, unit, ms_per_step, ...).  Everything else it can measure -- roofline and
+counter figures, per-kernel breakdown, the other SPH passes, the settled regime, the eager-record
+variant, the CPU baseline, the RCCL self-tests and the exchange diagnostics at N > 1 -- runs with --full.
 """
 from __future__ import annotations
 
@@ -37,16 +42,20 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="auto", help="auto (config3 at N = 1, weak5 at N > 1) | config2 | config3 | weak5 (BASELINE configs[4] slab)")
-    ap.add_argument("--settled-after", type=int, default=300, help="N = 1: after the timed run, continue the SAME run to this substep and record the settled regime (0 = skip)")
+    ap.add_argument("--settled-after", type=int, default=300, help="N = 1, --full: after the timed run, continue the SAME run to this substep and record the settled regime (0 = skip)")
     ap.add_argument("--neighbor", type=int, default=3, choices=(1, 2, 3), help="SPH pass: 3 = k_sph_walk (engine default), 2 = k_sph_list (round 2), 1 = k_sph_slow (plain per-target sweeps)")
     ap.add_argument("--aos", default="lazy", choices=["eager", "lazy"], help="lazy (engine default): the 80-byte records are materialised once per frame; eager: by every substep")
     ap.add_argument("--deadline", type=float, default=120.0, help="N > 1: seconds a rank waits for its neighbours (handshake of an exchange, drain of its streams) before it prints where it stands and exits 3")
     ap.add_argument("--frame-substeps", type=int, default=16, help="lazy, N = 1: materialise the 80-byte record array (sph_device_particles, what a renderer binds) after every this many "
                     "substeps INSIDE the timed region (Scene0p.h:48 maxSubstepsPerFrame = 16) and once more at its end")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=0, help="substeps of the CPU sample (0 = auto, about 10-30 s)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: roofline, per-kernel breakdown, settled regime, "
+                    "eager records, CPU baseline, at N > 1 the RCCL self-tests and the exchange diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                    "(float32 / float64; a fixed, seeded sample of the particle records)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-steps", type=int, default=0, help="--full: substeps of the CPU sample (0 = auto, about 10-30 s)")
     ap.add_argument("--grid-build", default="sort", choices=["sort", "ll"], help="counting sort (default) or the reference's linked lists (A/B)")
-    ap.add_argument("--no-breakdown", action="store_true", help="skip the extra untimed pass with per-kernel hipEvents")
+    ap.add_argument("--no-breakdown", action="store_true", help="--full: skip the extra untimed pass with per-kernel hipEvents")
     return ap.parse_args()
 
 
@@ -88,6 +97,41 @@ def cpu_baseline(pkg, rec, sp, cpu_steps):
         "sample": f"{k} substeps of the same {len(rec)}-particle workload (after 1 warm-up substep), oracle/sph_oracle.c with OpenMP, "
                   + ("gcc -O3 -march=native on this host" if built.returncode == 0 else "in-tree -O3 -mavx2 build (native build failed)") + f", {t:.2f} s",
     }
+
+
+DUMP_SAMPLE = 1 << 19          # particles written by --dump-outputs: about 40 MB of float32 at N = 1
+DUMP_SEED = 20250607
+
+
+def dump_outputs(out_dir, sim, multi, n_total, dist):
+    """What the timed path hands its caller after the last timed step -- the particle records -- as DIR/<field>.npy.
+    A fixed, seeded sample of DUMP_SAMPLE particles (by original index), the same for every run with the same arguments;
+    float fields as float32, the flags as float32, the sampled indices as float64.  Rank 0 writes; every rank takes part."""
+    import numpy as np
+    idx = np.arange(n_total, dtype=np.int64)
+    if n_total > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_total, DUMP_SAMPLE, replace=False))
+    if not multi:
+        rec = sim.download()[idx]
+        arrays = {"index": idx.astype(np.float64), "pos": rec["pos"], "vel": rec["vel"], "acc": rec["acc"], "density": rec["density"],
+                  "pressure": rec["pressure"], "padA": rec["padA"], "padB": rec["padB"],
+                  "isGhost": rec["isGhost"].astype(np.float32), "isActive": rec["isActive"].astype(np.float32)}
+    else:
+        own = sim.download_owned()                   # owned records of this rank, by global id (= original index)
+        mine = own[np.isin(own["id"].astype(np.int64), idx)]
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        if dist.get_rank() != 0:
+            return
+        rec = np.concatenate(parts)
+        rec = rec[np.argsort(rec["id"], kind="stable")]
+        arrays = {"index": rec["id"].astype(np.float64), "pos": rec["pos"], "vel": rec["vel"], "acc": rec["acc"], "density": rec["density"],
+                  "pressure": rec["pressure"], "padA": rec["padA"]}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if k == "index" else np.float32) for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def main():
@@ -240,7 +284,7 @@ def main():
     # to itself: the only send / receive a one-GPU box can execute; on a node it still says that RCCL moves bytes on this rank)
     selftest_gbs = None
     selftest_faces_ms = None
-    if multi and engine_rccl and isinstance(sim.exchange, halo.RcclComm):
+    if args.full and multi and engine_rccl and isinstance(sim.exchange, halo.RcclComm):
         try:
             sim.exchange.selftest_gbs(1 << 20)
             selftest_gbs = round(sim.exchange.selftest_gbs(int(sim.engine.message_bytes()[2] or sim.engine.message_bytes()[3] or (1 << 24)) & ~3), 1)
@@ -252,7 +296,7 @@ def main():
             print(f"[rank {rank}] RCCL self-test failed: {ex}", file=sys.stderr, flush=True)
     for _ in range(args.warmup):
         step()
-    sim.set_option(pkg.SPH_OPT_TIMING, 2)          # hipEvents around the dominant kernel only
+    sim.set_option(pkg.SPH_OPT_TIMING, 2)          # hipEvents around the dominant kernel only (with or without --full: the same window)
     sim.kernel_times(reset=True)
     barrier()
     materialised["n"] = 0
@@ -271,8 +315,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, multi, n_total, dist)
+
     breakdown = None
-    if not args.no_breakdown:
+    if args.full and not args.no_breakdown:
         sim.set_option(pkg.SPH_OPT_TIMING, 1)
         sim.kernel_times(reset=True)
         nb = min(args.steps, 20)
@@ -300,7 +347,7 @@ def main():
     # the headline window above is the specified lattice state; this block records, untimed for `value`, what the
     # SAME run costs once the fluid has settled into the compressed regime every long-running scene lives in.
     settled = None
-    if not multi and args.settled_after > 0 and not args.no_breakdown:
+    if args.full and not multi and args.settled_after > 0 and not args.no_breakdown:
         done = wave["n"]
         while wave["n"] < args.settled_after:
             step()
@@ -321,7 +368,7 @@ def main():
     # For the record (untimed for `value`): the same workload and window on a fresh engine with the records updated
     # by every substep (SPH_OPT_AOS_MODE 0), i.e. what the fused scattered record update costs.
     aos_eager = None
-    if not multi and args.aos == "lazy" and not args.no_breakdown and args.grid_build == "sort":
+    if args.full and not multi and args.aos == "lazy" and not args.no_breakdown and args.grid_build == "sort":
         sim2 = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream)
         sim2.set_option(pkg.SPH_OPT_NEIGHBOR_KERNEL, args.neighbor)
         sim2.set_option(pkg.SPH_OPT_AOS_MODE, 0)
@@ -344,7 +391,7 @@ def main():
     # exchange stream and on the engine's stream): pack -> transfer -> unpack, the end of the exchange and the end of the pass measured from
     # the step's start.  The transfer was hidden behind the interior iff exchange_end <= pass_end; sent bytes / transfer ms = the link's rate.
     exchange_diag = None
-    if multi and engine_rccl and isinstance(sim.exchange, halo.RcclComm) and getattr(sim, "overlap", False):
+    if args.full and multi and engine_rccl and isinstance(sim.exchange, halo.RcclComm) and getattr(sim, "overlap", False):
         sim.set_option(pkg.SPH_OPT_TIMING, 1)
         acc = [0.0] * 5
         nd = 5
@@ -398,39 +445,40 @@ def main():
             dist.destroy_process_group()
         return
 
-    g = sim.ComputeGridExtents() if not multi else sim.local_grid()
-    C_local = int(g.numCells) if not multi else int(g["numCells"])
-    sph_ms, sph_launches = kt["sph"]
-    sph_avg_s = (sph_ms / max(sph_launches, 1)) * 1e-3
-    alg_bytes = 164 * n_local + 4 * C_local          # SPHFluid pass, per launch
-    achieved = alg_bytes / sph_avg_s / 1e9 if sph_avg_s > 0 else 0.0
-    # HBM traffic, VALU instruction counts and L1 cache-line accesses are NOT measured in this run: they come from separate
-    # rocprofv3 --pmc passes over this same command (tools/profile_bench.sh), summarised for exactly the timed launches in
-    # profiles/r05_bench_counters.json.  That file carries the hash of the engine sources it was measured on; a file from
-    # other sources is refused (traffic stays null and traffic_source says why).
-    traffic = traffic_source = None
-    valu = None
-    cpath = os.path.join(ROOT, "profiles", "r05_bench_counters.json")
-    kname = "k_sph_ll" if args.grid_build == "ll" else (None, "k_sph_slow", "k_sph_list", "k_sph_walk")[args.neighbor]
-    if os.path.exists(cpath) and not multi:
-        try:
-            cj = json.load(open(cpath))
-            here = pkg.build.csrc_hash()
-            if cj.get("csrc_hash") != here:
-                traffic_source = f"profiles/r05_bench_counters.json was measured on other engine sources ({cj.get('csrc_hash')} != {here}): not used"
-            elif cj.get("workload") == wl and cj.get("kernel") == kname:
-                traffic = cj.get("hbm_bytes_per_launch")
-                traffic_source = cj.get("source")
-                if cj.get("valu_wave_insts_per_launch") and sph_avg_s > 0:
-                    # issue cost measured on gfx950 (profiles/r03_valu_rate2.txt): about 1.05 ns per wave-instruction and SIMD for the
-                    # add / mul / fma / integer add-and-or class, 1.75 ns for v_pk_*, v_cmp, v_cndmask, v_max/min and the VOP3-only forms
-                    valu = {"wave_insts_per_launch": cj["valu_wave_insts_per_launch"],
-                            "wave_insts_per_s_per_simd": cj["valu_wave_insts_per_launch"] / sph_avg_s / 1024.0,
-                            "tcp_line_accesses_per_launch": cj.get("tcp_line_accesses_per_launch"),
-                            "tcp_line_accesses_per_cycle_per_cu_at_2GHz": (cj["tcp_line_accesses_per_launch"] / 256.0 / (sph_avg_s * 2.0e9)) if cj.get("tcp_line_accesses_per_launch") else None,
-                            "source": cj.get("source")}
-        except Exception as ex:                              # noqa: BLE001
-            traffic, traffic_source = None, f"profiles/r05_bench_counters.json unreadable: {ex}"
+    if args.full:
+        g = sim.ComputeGridExtents() if not multi else sim.local_grid()
+        C_local = int(g.numCells) if not multi else int(g["numCells"])
+        sph_ms, sph_launches = kt["sph"]
+        sph_avg_s = (sph_ms / max(sph_launches, 1)) * 1e-3
+        alg_bytes = 164 * n_local + 4 * C_local          # SPHFluid pass, per launch
+        achieved = alg_bytes / sph_avg_s / 1e9 if sph_avg_s > 0 else 0.0
+        # HBM traffic, VALU instruction counts and L1 cache-line accesses are NOT measured in this run: they come from separate
+        # rocprofv3 --pmc passes over this same command (tools/profile_bench.sh), summarised for exactly the timed launches in
+        # profiles/r05_bench_counters.json.  That file carries the hash of the engine sources it was measured on; a file from
+        # other sources is refused (traffic stays null and traffic_source says why).
+        traffic = traffic_source = None
+        valu = None
+        cpath = os.path.join(ROOT, "profiles", "r05_bench_counters.json")
+        kname = "k_sph_ll" if args.grid_build == "ll" else (None, "k_sph_slow", "k_sph_list", "k_sph_walk")[args.neighbor]
+        if os.path.exists(cpath) and not multi:
+            try:
+                cj = json.load(open(cpath))
+                here = pkg.build.csrc_hash()
+                if cj.get("csrc_hash") != here:
+                    traffic_source = f"profiles/r05_bench_counters.json was measured on other engine sources ({cj.get('csrc_hash')} != {here}): not used"
+                elif cj.get("workload") == wl and cj.get("kernel") == kname:
+                    traffic = cj.get("hbm_bytes_per_launch")
+                    traffic_source = cj.get("source")
+                    if cj.get("valu_wave_insts_per_launch") and sph_avg_s > 0:
+                        # issue cost measured on gfx950 (profiles/r03_valu_rate2.txt): about 1.05 ns per wave-instruction and SIMD for the
+                        # add / mul / fma / integer add-and-or class, 1.75 ns for v_pk_*, v_cmp, v_cndmask, v_max/min and the VOP3-only forms
+                        valu = {"wave_insts_per_launch": cj["valu_wave_insts_per_launch"],
+                                "wave_insts_per_s_per_simd": cj["valu_wave_insts_per_launch"] / sph_avg_s / 1024.0,
+                                "tcp_line_accesses_per_launch": cj.get("tcp_line_accesses_per_launch"),
+                                "tcp_line_accesses_per_cycle_per_cu_at_2GHz": (cj["tcp_line_accesses_per_launch"] / 256.0 / (sph_avg_s * 2.0e9)) if cj.get("tcp_line_accesses_per_launch") else None,
+                                "source": cj.get("source")}
+            except Exception as ex:                              # noqa: BLE001
+                traffic, traffic_source = None, f"profiles/r05_bench_counters.json unreadable: {ex}"
 
     out = {
         "metric": "particle-substeps/sec", "value": n_total * args.steps / elapsed, "unit": "particle-substeps/s",
@@ -449,27 +497,30 @@ def main():
                          + (", AoS update fused)" if (args.aos == "eager" and not multi) else ") -> record write-back once per frame" if not multi else ")"))
                         + (" + halo exchange" if multi else ""),
         },
-        "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic, "traffic_source": traffic_source, "kernel": kname,
-            "window": {"kernel": kname, "first_launch": args.warmup, "launches": int(sph_launches),
-                       "note": "0-based index among this kernel's launches of the run; profiles/r05_bench_kernel_window.json holds the rocprofv3 --kernel-trace average of exactly these launches"},
-            "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": sph_avg_s * 1e6, "launches_timed": int(sph_launches),
-            # the same window with the 80-byte records updated by EVERY substep (what the 164 N figure prices; aos_eager below)
-            "frac_records_updated_every_substep": (alg_bytes / (aos_eager["sph_pass_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if aos_eager and aos_eager.get("sph_pass_us") else None,
-            "whole_substep_algorithmic_GBs": (260 * n_local + 8 * C_local) / (elapsed / args.steps) / 1e9,
-        },
-        "kernels_us_per_substep": breakdown,
         "slab_status": slab_status,
-        "exchange": exchange_diag,
-        "aos_eager": aos_eager,
-        "settled": settled,
-        "valu": valu,
     }
-    if not args.no_cpu_baseline and not multi:
-        out["cpu_baseline"] = cpu_baseline(pkg, rec, sp, args.cpu_steps)
-    elif not args.no_cpu_baseline:
-        out["cpu_baseline"] = None
+    if args.full:
+        out.update({
+            "roofline": {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic, "traffic_source": traffic_source, "kernel": kname,
+                "window": {"kernel": kname, "first_launch": args.warmup, "launches": int(sph_launches),
+                           "note": "0-based index among this kernel's launches of the run; profiles/r05_bench_kernel_window.json holds the rocprofv3 --kernel-trace average of exactly these launches"},
+                "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": sph_avg_s * 1e6, "launches_timed": int(sph_launches),
+                # the same window with the 80-byte records updated by EVERY substep (what the 164 N figure prices; aos_eager below)
+                "frac_records_updated_every_substep": (alg_bytes / (aos_eager["sph_pass_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if aos_eager and aos_eager.get("sph_pass_us") else None,
+                "whole_substep_algorithmic_GBs": (260 * n_local + 8 * C_local) / (elapsed / args.steps) / 1e9,
+            },
+            "kernels_us_per_substep": breakdown,
+            "exchange": exchange_diag,
+            "aos_eager": aos_eager,
+            "settled": settled,
+            "valu": valu,
+        })
+        if not args.no_cpu_baseline and not multi:
+            out["cpu_baseline"] = cpu_baseline(pkg, rec, sp, args.cpu_steps)
+        elif not args.no_cpu_baseline:
+            out["cpu_baseline"] = None
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

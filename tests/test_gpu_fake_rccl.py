@@ -189,7 +189,7 @@ def test_bench_two_ranks_engine_path_over_the_stand_in_transport(fake_lib):
     env = dict(os.environ, SPH_BENCH_BACKEND="gloo", SPH_RCCL_LIBRARY=fake_lib, FAKE_RCCL_TIMEOUT_S="30", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "config2", "--steps", "8",
-           "--warmup", "3", "--no-cpu-baseline", "--deadline", "60"]
+           "--warmup", "3", "--no-cpu-baseline", "--deadline", "60", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
