@@ -22,8 +22,10 @@
 #include "sph_host.h"
 #include "sph_kernels.h"
 #include "sph_walk.h"
+#include "sph_sample.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
+static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 
 namespace {
 
@@ -168,6 +170,10 @@ struct SphEngine {
     uint32_t* d_slabCnt = nullptr;          // [0] lo records, [1] hi records, [2] live count, [3] download count, [4] flags, [5] / [6] counts of the last async pack
     int debugFlags = 0;
     unsigned long long* d_stats = nullptr;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
+    // sph_sample_points (host arrays): device copies of the probes and of the results
+    float4* d_sampleIn = nullptr;
+    SphSample* d_sampleOut = nullptr;
+    size_t sampleCap = 0;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
 
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
@@ -724,6 +730,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_stencil);
     dev_free(e->d_terrain);
     dev_free(e->d_stats);
+    dev_free(e->d_sampleIn); dev_free(e->d_sampleOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (e->xstream) { (void)hipStreamSynchronize(e->xstream); (void)hipStreamDestroy(e->xstream); }
@@ -2078,6 +2085,86 @@ int sph_sync_deadline(SphEngine* e, double seconds) {
                         limit, e->stepNo, e->exchangeNo, e->intent.sendHalo[0], e->intent.sendMig[0], e->intent.sendHalo[1], e->intent.sendMig[1]);
         if (spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(100)); else std::this_thread::yield();
     }
+}
+
+// ---- field sampling (sph_sample.h) ---------------------------------------------------------------
+// The grid of the CURRENT state, built outside a substep exactly as sph_download_grid builds it.  The next dispatch builds its
+// own (dispatch_one always does), so nothing of this build reaches the simulation.
+static int sample_grid(SphEngine* e, SimK& k) {
+    if (e->slab) return fail(SPH_ERR_STATE, "sampling a z-slab engine is not supported: its halo records after a step are the step's entry state");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "sampling needs the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    int rc;
+    if ((rc = validate_params(e->params))) return rc;
+    sph::compute_grid_extents(e->params, e->grid);
+    if ((rc = ensure_grid_buffers(e))) return rc;
+    make_simk(e->params, e->grid, e->params.param_timeStep, k);
+    if ((rc = import_state(e))) return rc;
+    return build_grid(e, k);
+}
+
+int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, SphSample* devOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (m && (!devPoints4 || !devOut)) return fail(SPH_ERR_ARG, "null argument");
+    if (m > (size_t)1 << 40) return fail(SPH_ERR_ARG, "%zu probes", m);
+    SimK k;
+    int rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    if (m) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_sample_points, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, e->d_cellStart,
+                           reinterpret_cast<const float4*>(devPoints4), (void*)devOut, m);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_sample_points(SphEngine* e, const float* points4, size_t m, SphSample* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (m && (!points4 || !out)) return fail(SPH_ERR_ARG, "null argument");
+    if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
+    int rc;
+    if (m > e->sampleCap) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        dev_free(e->d_sampleIn); dev_free(e->d_sampleOut); e->sampleCap = 0;
+        if ((rc = dev_alloc(&e->d_sampleIn, m)) || (rc = dev_alloc(&e->d_sampleOut, m))) return rc;
+        e->sampleCap = m;
+    }
+    if (m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = sph_sample_points_device(e, reinterpret_cast<const float*>(e->d_sampleIn), m, e->d_sampleOut))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(out, e->d_sampleOut, m * sizeof(SphSample), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int field, void* devOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!origin || !spacing || !dims || !devOut) return fail(SPH_ERR_ARG, "null argument");
+    if (field < SPH_FIELD_DENSITY || field > SPH_FIELD_ALL) return fail(SPH_ERR_ARG, "unknown field %d", field);
+    long long total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= 1)", a, dims[a]);
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
+        total *= dims[a];
+        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
+    }
+    SimK k;
+    int rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    LatticeK L;
+    L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
+    L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
+    L.dx = dims[0]; L.dy = dims[1]; L.dz = dims[2];
+    L.nbx = (dims[0] + kBrickX - 1) / kBrickX; L.nby = (dims[1] + kBrickY - 1) / kBrickY;
+    L.nBricks = (long long)L.nbx * L.nby * ((dims[2] + kBrickZ - 1) / kBrickZ);
+    L.field = field;
+    L.stage = kSampleStage;
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_sample_lattice, dim3((unsigned)std::min<long long>(L.nBricks, 1ll << 20)), dim3(kBlock), 0, e->stream, k, L,
+                           (const float4*)e->d_sPV, e->d_cellStart, devOut);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
 }
 
 int sph_kernel_times(SphEngine* e, double msOut[SPH_K_COUNT], int64_t launchesOut[SPH_K_COUNT], int reset) {

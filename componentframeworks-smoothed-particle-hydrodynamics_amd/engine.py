@@ -106,12 +106,26 @@ ABI_SYMBOLS = (
     "sph_river_default", "sph_generate_river_terrain", "sph_spawn_river_particles", "sph_set_river", "sph_get_river",
     "sph_slab_set_verify", "sph_slab_set_deadline", "sph_slab_plan", "sph_slab_plans_agree", "sph_sync_deadline",
     "sph_slab_debug_tight_messages", "sph_comm_selftest_faces",
+    "sph_sample_points", "sph_sample_points_device", "sph_sample_lattice",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
 # left the list's slack, [7] waves with at least one fallback target
 STAMP_NAMES = ("rows_unstaged", "slow_targets", "list_entries", "rows", "lanes", "overflow_targets", "far_targets", "waves_with_fallback")
+
+
+class SphSample(C.Structure):
+    """struct SphSample of include/sph_abi.h: the fields of the fluid at one probe point (see SPHFluidGPU.sample)."""
+    _fields_ = [("density", C.c_float), ("fraction", C.c_float), ("pressure", C.c_float), ("count", C.c_uint32),
+                ("vel", C.c_float * 3), ("pad", C.c_float)]
+
+
+assert C.sizeof(SphSample) == 32
+SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("pressure", "<f4"), ("count", "<u4"),
+                         ("vel", "<f4", (3,)), ("pad", "<f4")])
+assert SAMPLE_DTYPE.itemsize == 32
+SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SPH_FIELD_ALL = 0, 1, 2, 3, 4
 
 
 class SphError(RuntimeError):
@@ -220,6 +234,9 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_sync_deadline.argtypes = [vp, C.c_double]
     L.sph_slab_debug_tight_messages.argtypes = [vp, C.c_int]
     L.sph_comm_selftest_faces.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.sph_sample_points.argtypes = [vp, vp, C.c_size_t, vp]
+    L.sph_sample_points_device.argtypes = [vp, vp, C.c_size_t, vp]
+    L.sph_sample_lattice.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default"):
@@ -303,6 +320,26 @@ def spawn_river_particles(p: SphParams, river: SphRiver, heights: np.ndarray, n_
     _check(load_library().sph_spawn_river_particles(C.byref(p), C.byref(river), h.ctypes.data_as(C.c_void_p), n_requested, seed,
                                                     buf.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(mass)))
     return buf[: n.value].copy(), float(mass.value)
+
+
+def gauge_levels(frac: np.ndarray, ys: np.ndarray, threshold: float = 0.5) -> np.ndarray:
+    """The rule of SPHFluidGPU.water_level on fraction columns frac[c, k] sampled at heights ys[k] (descending): the first sample
+    from the top with fraction >= threshold, interpolated linearly against the sample above it (that sample itself when it is the
+    topmost one); NaN where no sample reaches the threshold."""
+    frac = np.asarray(frac, np.float64)
+    ys = np.asarray(ys, np.float64)
+    out = np.full(frac.shape[0], np.nan)
+    for c in range(frac.shape[0]):
+        hit = np.nonzero(frac[c] >= threshold)[0]
+        if len(hit) == 0:
+            continue
+        k = int(hit[0])
+        if k == 0:
+            out[c] = ys[0]
+            continue
+        f0, f1 = frac[c, k - 1], frac[c, k]            # above (below threshold), at / over the threshold
+        out[c] = ys[k] + (ys[k - 1] - ys[k]) * (f1 - threshold) / (f1 - f0)
+    return out
 
 
 _PARAM_NAMES = {f[0] for f in SphParams._fields_}
@@ -504,6 +541,60 @@ class SPHFluidGPU:
         _check(self._L.sph_set_params(self._h, C.byref(self._p)))
         _check(self._L.sph_download_grid(self._h, cnt.ctypes.data_as(C.c_void_p), g.numCells, pc.ctypes.data_as(C.c_void_p), n))
         return cnt, pc[:n]
+
+    # -- field sampling (include/sph_abi.h "field sampling") ----------------------------------
+    def sample(self, points) -> np.ndarray:
+        """Fields of the current state at (m, 3) or (m, 4) probe points: a structured array of SAMPLE_DTYPE (density, fraction,
+        pressure, count, vel).  Synchronises."""
+        pts = np.asarray(points, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise SphError(f"sample: points must have shape (m, 3) or (m, 4), not {pts.shape}")
+        p4 = np.zeros((len(pts), 4), np.float32)
+        p4[:, :3] = pts[:, :3]
+        out = np.zeros(len(pts), SAMPLE_DTYPE)
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_sample_points(self._h, p4.ctypes.data_as(C.c_void_p), len(p4), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sample_device(self, dev_points: int, m: int, dev_out: int):
+        """m probes of 4 floats at device address dev_points -> m 32-byte SphSample records at dev_out (a torch tensor's
+        data_ptr(), say).  Asynchronous on the engine's stream."""
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_sample_points_device(self._h, C.c_void_p(dev_points), int(m), C.c_void_p(dev_out)))
+
+    def sample_lattice_device(self, origin, spacing, dims, dev_out: int, field: int = SPH_FIELD_DENSITY):
+        """Lattice origin + i * spacing (dims = (nx, ny, nz), x fastest) into a caller's device buffer: one float per point, or one
+        SphSample per point for SPH_FIELD_ALL.  Asynchronous on the engine's stream."""
+        d = (C.c_int * 3)(*[int(x) for x in dims])
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_sample_lattice(self._h, _f3(origin), _f3(spacing), d, int(field), C.c_void_p(dev_out)))
+
+    def sample_lattice(self, origin, spacing, dims, field: int = SPH_FIELD_DENSITY) -> np.ndarray:
+        """Host copy of sample_lattice_device: shape (nz, ny, nx), float32 or SAMPLE_DTYPE (SPH_FIELD_ALL)."""
+        import torch
+        nx, ny, nz = (int(x) for x in dims)
+        if min(nx, ny, nz) < 1:
+            raise SphError(f"sample_lattice: dims must be >= 1, not {tuple(dims)}")
+        words = 8 if field == SPH_FIELD_ALL else 1
+        buf = torch.empty(nx * ny * nz * words, dtype=torch.float32, device="cuda")
+        self.sample_lattice_device(origin, spacing, (nx, ny, nz), buf.data_ptr(), field)
+        self.sync()
+        host = buf.cpu().numpy()
+        if field == SPH_FIELD_ALL:
+            return host.view(SAMPLE_DTYPE).reshape(nz, ny, nx)
+        return host.reshape(nz, ny, nx)
+
+    def water_level(self, xz, y_lo: float, y_hi: float, dy: float, threshold: float = 0.5) -> np.ndarray:
+        """Wave gauge: per (x, z) column, the first y from the top where `fraction` >= threshold, sampled at y_hi, y_hi - dy, ...
+        down to y_lo and linearly interpolated against the sample above it; NaN where no sample reaches the threshold."""
+        cols = np.asarray(xz, dtype=np.float32).reshape(-1, 2)
+        ys = np.float32(y_hi) - np.arange(int(np.floor((y_hi - y_lo) / dy + 1e-6)) + 1, dtype=np.float32) * np.float32(dy)
+        pts = np.zeros((len(cols), len(ys), 4), np.float32)
+        pts[:, :, 0] = cols[:, None, 0]
+        pts[:, :, 1] = ys[None, :]
+        pts[:, :, 2] = cols[:, None, 1]
+        frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
+        return gauge_levels(frac, ys, threshold)
 
     def sync(self):
         _check(self._L.sph_sync(self._h))

@@ -145,6 +145,22 @@ public:
     // packed (x, y, z, w) per particle in original order into a device buffer of the renderer (w: 0 one, 1 density,
     // 2 foam, 3 speed, 4 dye): the render-side replacement of binding 0 reads (fluidDepth.vert, particleImpostor.vert)
     void PackRenderBuffer(float* devOut4, int wMode = 0) { Check(sph_pack_render_buffer(engine, devOut4, sph_num_particles(engine), wMode), "sph_pack_render_buffer"); }
+    // Field sampling (engine extension, sph_abi.h "field sampling"): the fields of the current state at probe points (host
+    // vectors; synchronises) or on a lattice origin + i * spacing, x fastest, into a device buffer (asynchronous).  Members are
+    // pushed first, as DispatchCompute does.  Returns false on error (LastError()).
+    bool SamplePoints(const std::vector<MATH::Vec4>& points, std::vector<SphSample>& out) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        out.resize(points.size());
+        return !Check(sph_sample_points(engine, points.empty() ? nullptr : &points[0].x, points.size(), out.empty() ? nullptr : out.data()),
+                      "sph_sample_points");
+    }
+    bool SampleLattice(const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], int field, void* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        return !Check(sph_sample_lattice(engine, o, s, dims, field, devOut), "sph_sample_lattice");
+    }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");

@@ -31,6 +31,7 @@ extern "C" {
 #define SPH_ABI_VERSION 4   /* 4: the PLAN of a sized exchange (SphSlabIntent) compared between neighbours before any record moves: sph_slab_step_finish_local compares the
                                neighbour engines' plans, the RCCL transport sends them across each link first (sph_slab_set_verify), waits with a deadline (SPH_ERR_TIMEOUT,
                                sph_slab_set_deadline, sph_sync_deadline); flag 32; sph_slab_plan / _plans_agree, sph_comm_selftest_faces; SPH_OPT_NEIGHBOR_KERNEL 4 retired */
+/* (still 4, additions only: SphSample, SPH_FIELD_*, sph_sample_points / sph_sample_points_device / sph_sample_lattice -- field sampling) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -262,6 +263,37 @@ int sph_sync(SphEngine* e);
  * [4] lanes (one target each), [5] targets whose list overflowed, [6] targets that left the list's slack (sweep-3
  * fallback), [7] waves with at least one fallback target.  Never used on a timed path. */
 int sph_debug_counters(SphEngine* e, uint64_t* out, int count, int reset);
+
+/* ---- field sampling at probe points and on regular lattices (no reference counterpart) ------------------------------------------
+ * The fields of the CURRENT state at arbitrary points.  A probe at x sees exactly the candidates sweep 1 of the SPH pass sees for a
+ * particle at x: the members of the <= 27 cells around x's cell (BuildGrid's formula: (x - gridMin) / cellSize with IEEE division,
+ * floorf, clamped to the grid), 9 rows in (dz, dy) order, each row one contiguous run of sorted slots, members ascending by id.  With
+ * t_j = max(h^2 - r^2, 0), r^2 the fma-based dot3 of x - x_j:
+ *   density  = mp6 * sum t_j^3, accumulated as dsum = fmaf(t*t, t, dsum) like sweep 1; NOT clamped (0 in empty space)
+ *   count    = number of candidates with r^2 < h^2
+ *   fraction = mp6 * sum invRho_j t_j^3 (Shepard sum, invRho_j = 1/rho_j of the sorted copy): ~1 inside the fluid, 0 outside
+ *   vel, pressure = sum w_j v_j / sum w_j (the same for P), w_j = invRho_j t_j^3; 0 where sum w_j = 0
+ * so fmaxf(density(x_i), rho0 / 2) at a fluid particle's position is, bit for bit, the density the next substep writes into its
+ * record.  A probe with a non-finite coordinate gives an all-zero record.  mp6 = param_mass * poly6 coefficient.
+ * Every call first builds the grid of the current state (compute_grid_extents, import, counting sort: about 150 us at 4 M particles,
+ * timed under the bin / scan / scatter classes); the sampling kernel itself is timed as SPH_K_OTHER.  The next dispatch builds its own
+ * grid: sampling never changes the simulation.  Refused with SPH_ERR_STATE: z-slab engines (their halo records after a step are the
+ * step's entry state) and SPH_OPT_GRID_BUILD 1 (no sorted copy).  With no particles every result is zero. */
+typedef struct SphSample {
+    float density, fraction, pressure;
+    uint32_t count;
+    float vel[3];
+    float pad;
+} SphSample;                       /* 32 bytes */
+enum { SPH_FIELD_DENSITY = 0, SPH_FIELD_FRACTION = 1, SPH_FIELD_PRESSURE = 2, SPH_FIELD_SPEED = 3 /* |vel| */, SPH_FIELD_ALL = 4 /* SphSample */ };
+/* m probes of 4 floats (x, y, z, unused) in HOST memory -> m records in host memory.  Synchronises. */
+int sph_sample_points(SphEngine* e, const float* points4, size_t m, SphSample* out);
+/* The same with DEVICE arrays; asynchronous on the engine's stream. */
+int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, SphSample* devOut);
+/* Lattice points origin + (float)i * spacing per axis (an fp32 multiply, then an add), i < dims, x fastest, into a DEVICE buffer:
+ * one float per point (SPH_FIELD_DENSITY / _FRACTION / _PRESSURE / _SPEED) or one SphSample per point (SPH_FIELD_ALL).  dims >= 1,
+ * at most 2^31 - 1 points; spacing finite and > 0.  Asynchronous on the engine's stream. */
+int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int field, void* devOut);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
