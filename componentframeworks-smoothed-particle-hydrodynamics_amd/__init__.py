@@ -10,6 +10,6 @@ from .engine import (  # noqa: F401
     SPH_ERR_TIMEOUT, SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_TIMING, SPHFluidGPU, SphError, SphFountain, SphGridInfo, SphParams, SphRiver, SphSlabIntent,
     compute_grid_extents, default_params, default_river, effective_half, generate_river_terrain, load_library, rotation_mat3, spawn_particles,
     spawn_river_particles, SAMPLE_DTYPE, SPH_FIELD_ALL, SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SphSample,
-    gauge_levels,
+    gauge_levels, SURFACE_VERTEX_DTYPE, SphSurface, write_ply,
 )
 from . import build, synthetic  # noqa: F401

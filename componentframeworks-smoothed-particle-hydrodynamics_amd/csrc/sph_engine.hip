@@ -23,9 +23,11 @@
 #include "sph_kernels.h"
 #include "sph_walk.h"
 #include "sph_sample.h"
+#include "sph_surface.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
+static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 
 namespace {
 
@@ -174,6 +176,18 @@ struct SphEngine {
     float4* d_sampleIn = nullptr;
     SphSample* d_sampleOut = nullptr;
     size_t sampleCap = 0;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
+    // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
+    float* d_surfVol = nullptr;
+    uint16_t* d_surfCode = nullptr;
+    uint32_t* d_surfVOff = nullptr;
+    uint2* d_surfTile = nullptr;
+    unsigned long long* d_surfTileOff = nullptr;
+    size_t surfVolCap = 0, surfCodeCap = 0, surfVOffCap = 0, surfTileCap = 0, surfTileOffCap = 0;
+    sph::SurfVertex* d_surfVerts = nullptr;
+    uint32_t* d_surfTris = nullptr;
+    size_t surfVertCap = 0, surfTriCap = 0;
+    bool surfValid = false;
+    uint32_t surfNumV = 0, surfNumT = 0;
 
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
@@ -731,6 +745,8 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_terrain);
     dev_free(e->d_stats);
     dev_free(e->d_sampleIn); dev_free(e->d_sampleOut);
+    dev_free(e->d_surfVol); dev_free(e->d_surfCode); dev_free(e->d_surfVOff); dev_free(e->d_surfTile); dev_free(e->d_surfTileOff);
+    dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (e->xstream) { (void)hipStreamSynchronize(e->xstream); (void)hipStreamDestroy(e->xstream); }
@@ -759,6 +775,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     int rc;
     if ((rc = validate_params(e->params))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
+    e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     std::vector<SphParticle> v;
     float m;
     if (e->river.riverMode && !e->terrainHeights.empty())             // :104
@@ -2164,6 +2181,119 @@ int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[
                            (const float4*)e->d_sPV, e->d_cellStart, devOut);
     }
     HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+// ---- iso-surface meshes (sph_surface.h) ----------------------------------------------------------
+static int surface_check_lattice(const float origin[3], const float spacing[3], const int dims[3], float iso) {
+    if (!origin || !spacing || !dims) return fail(SPH_ERR_ARG, "null argument");
+    long long total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 2) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= 2)", a, dims[a]);
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
+        total *= dims[a];
+        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
+    }
+    if (!std::isfinite(iso)) return fail(SPH_ERR_ARG, "iso %g is not finite", (double)iso);
+    return SPH_OK;
+}
+
+// grows an engine-owned device array to at least `need` elements (contents are not kept; the engine's stream is drained first)
+extern "C++" template <class T>
+static int surface_grow(SphEngine* e, T*& p, size_t& cap, size_t need) {
+    if (need <= cap && p) return SPH_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    dev_free(p); cap = 0;
+    int rc;
+    if ((rc = dev_alloc(&p, need))) return rc;
+    cap = need;
+    return SPH_OK;
+}
+
+// Count, scan, one synchronisation for the totals, then the vertex and triangle kernels (arguments already checked).
+static int surface_mesh(SphEngine* e, const float* vol, const float origin[3], const float spacing[3], const int dims[3], float iso, SphSurface* out) {
+    using namespace sph;
+    SurfK s;
+    s.ox = origin[0]; s.oy = origin[1]; s.oz = origin[2];
+    s.sx = spacing[0]; s.sy = spacing[1]; s.sz = spacing[2];
+    s.dx = dims[0]; s.dy = dims[1]; s.dz = dims[2];
+    s.npts = (long long)dims[0] * dims[1] * dims[2];
+    s.iso = iso;
+    s.nTiles = (int)((s.npts + kSurfTile - 1) / kSurfTile);
+    int rc;
+    if ((rc = surface_grow(e, e->d_surfCode, e->surfCodeCap, (size_t)s.npts)) || (rc = surface_grow(e, e->d_surfVOff, e->surfVOffCap, (size_t)s.npts)) ||
+        (rc = surface_grow(e, e->d_surfTile, e->surfTileCap, (size_t)s.nTiles)) ||
+        (rc = surface_grow(e, e->d_surfTileOff, e->surfTileOffCap, 2 * (size_t)s.nTiles + 2))) return rc;
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_surf_count, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, e->d_surfCode, e->d_surfTile);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_surf_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, (const uint2*)e->d_surfTile, e->d_surfTileOff, s.nTiles);
+    }
+    HIP_TRY(hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(hipMemcpyAsync(tot, e->d_surfTileOff + 2 * (size_t)s.nTiles, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull)
+        return fail(SPH_ERR_CAPACITY, "surface of %llu vertices and %llu triangles exceeds 2^32 - 1", tot[0], tot[1]);
+    if ((rc = surface_grow(e, e->d_surfVerts, e->surfVertCap, (size_t)tot[0])) ||
+        (rc = surface_grow(e, e->d_surfTris, e->surfTriCap, 3 * (size_t)tot[1]))) return rc;
+    if (tot[0]) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_surf_vertices, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, (const uint16_t*)e->d_surfCode,
+                           (const unsigned long long*)e->d_surfTileOff, e->d_surfVOff, e->d_surfVerts);
+    }
+    if (tot[1]) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_surf_triangles, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, (const uint16_t*)e->d_surfCode,
+                           (const uint32_t*)e->d_surfVOff, (const unsigned long long*)e->d_surfTileOff, e->d_surfTris);
+    }
+    HIP_TRY(hipGetLastError());
+    e->surfNumV = (uint32_t)tot[0];
+    e->surfNumT = (uint32_t)tot[1];
+    e->surfValid = true;
+    out->numVertices = e->surfNumV;
+    out->numTriangles = e->surfNumT;
+    out->vertices = e->surfNumV ? reinterpret_cast<const SphSurfaceVertex*>(e->d_surfVerts) : nullptr;
+    out->triangles = e->surfNumT ? e->d_surfTris : nullptr;
+    return SPH_OK;
+}
+
+int sph_extract_surface_volume(SphEngine* e, const float* devValues, const float origin[3], const float spacing[3], const int dims[3], float iso,
+                               SphSurface* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    e->surfValid = false;                                             // (any failure below leaves no surface: sph_abi.h)
+    if (!devValues || !out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = surface_check_lattice(origin, spacing, dims, iso))) return rc;
+    return surface_mesh(e, devValues, origin, spacing, dims, iso, out);
+}
+
+int sph_extract_surface(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int field, float iso, SphSurface* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    e->surfValid = false;
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = surface_check_lattice(origin, spacing, dims, iso))) return rc;
+    if (field < SPH_FIELD_DENSITY || field > SPH_FIELD_SPEED) return fail(SPH_ERR_ARG, "field %d is not a scalar field", field);
+    if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
+    const size_t npts = (size_t)dims[0] * dims[1] * dims[2];
+    if ((rc = surface_grow(e, e->d_surfVol, e->surfVolCap, npts))) return rc;
+    if ((rc = sph_sample_lattice(e, origin, spacing, dims, field, e->d_surfVol))) return rc;
+    return surface_mesh(e, e->d_surfVol, origin, spacing, dims, iso, out);
+}
+
+int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertexCap, uint32_t* triangles3, size_t triangleCap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->surfValid) return fail(SPH_ERR_STATE, "no surface: call sph_extract_surface or sph_extract_surface_volume first");
+    if (vertexCap < e->surfNumV || triangleCap < e->surfNumT)
+        return fail(SPH_ERR_CAPACITY, "surface has %u vertices and %u triangles (capacities %zu, %zu)", e->surfNumV, e->surfNumT, vertexCap, triangleCap);
+    if ((e->surfNumV && !vertices) || (e->surfNumT && !triangles3)) return fail(SPH_ERR_ARG, "null argument");
+    if (e->surfNumV) HIP_TRY(hipMemcpyAsync(vertices, e->d_surfVerts, (size_t)e->surfNumV * sizeof(SphSurfaceVertex), hipMemcpyDeviceToHost, e->stream));
+    if (e->surfNumT) HIP_TRY(hipMemcpyAsync(triangles3, e->d_surfTris, (size_t)e->surfNumT * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
 

@@ -107,6 +107,7 @@ ABI_SYMBOLS = (
     "sph_slab_set_verify", "sph_slab_set_deadline", "sph_slab_plan", "sph_slab_plans_agree", "sph_sync_deadline",
     "sph_slab_debug_tight_messages", "sph_comm_selftest_faces",
     "sph_sample_points", "sph_sample_points_device", "sph_sample_lattice",
+    "sph_extract_surface", "sph_extract_surface_volume", "sph_surface_download",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -126,6 +127,15 @@ SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("pressure", "
                          ("vel", "<f4", (3,)), ("pad", "<f4")])
 assert SAMPLE_DTYPE.itemsize == 32
 SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SPH_FIELD_ALL = 0, 1, 2, 3, 4
+
+
+class SphSurface(C.Structure):
+    """struct SphSurface of include/sph_abi.h: counts and borrowed device arrays of the last extracted surface."""
+    _fields_ = [("numVertices", C.c_uint32), ("numTriangles", C.c_uint32), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
+
+
+SURFACE_VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,))])     # struct SphSurfaceVertex
+assert SURFACE_VERTEX_DTYPE.itemsize == 24
 
 
 class SphError(RuntimeError):
@@ -237,6 +247,9 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_sample_points.argtypes = [vp, vp, C.c_size_t, vp]
     L.sph_sample_points_device.argtypes = [vp, vp, C.c_size_t, vp]
     L.sph_sample_lattice.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, vp]
+    L.sph_extract_surface.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, C.c_float, C.POINTER(SphSurface)]
+    L.sph_extract_surface_volume.argtypes = [vp, vp, f3, f3, C.POINTER(C.c_int), C.c_float, C.POINTER(SphSurface)]
+    L.sph_surface_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default"):
@@ -340,6 +353,23 @@ def gauge_levels(frac: np.ndarray, ys: np.ndarray, threshold: float = 0.5) -> np
         f0, f1 = frac[c, k - 1], frac[c, k]            # above (below threshold), at / over the threshold
         out[c] = ys[k] + (ys[k - 1] - ys[k]) * (f1 - threshold) / (f1 - f0)
     return out
+
+
+def write_ply(path, vertices: np.ndarray, triangles: np.ndarray) -> None:
+    """Binary little-endian PLY of a surface: x, y, z, nx, ny, nz per vertex (SURFACE_VERTEX_DTYPE), 3 uint32 indices per face."""
+    v = np.ascontiguousarray(vertices, dtype=SURFACE_VERTEX_DTYPE)
+    t = np.ascontiguousarray(triangles, dtype="<u4").reshape(-1, 3)
+    faces = np.empty(len(t), dtype=np.dtype([("n", "u1"), ("idx", "<u4", (3,))], align=False))
+    faces["n"] = 3
+    faces["idx"] = t
+    head = ("ply\nformat binary_little_endian 1.0\ncomment iso-surface (DESIGN.md section 3b)\n"
+            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            "property float nx\nproperty float ny\nproperty float nz\n"
+            f"element face {len(t)}\nproperty list uchar uint vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(head.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(faces.tobytes())
 
 
 _PARAM_NAMES = {f[0] for f in SphParams._fields_}
@@ -595,6 +625,65 @@ class SPHFluidGPU:
         pts[:, :, 2] = cols[:, None, 1]
         frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
         return gauge_levels(frac, ys, threshold)
+
+    # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
+    def default_surface_lattice(self):
+        """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
+        g = self.ComputeGridExtents()
+        h = np.float32(self._p.param_h)
+        s = np.float32(h / np.float32(2))
+        lo = np.array(g.gridMin, np.float32) - np.float32(2) * h
+        ext = np.float32(g.cellSize) * np.array(g.dims, np.float32) + np.float32(4) * h
+        dims = tuple(int(np.ceil(ext[a] / s)) + 1 for a in range(3))
+        return tuple(float(x) for x in lo), (float(s),) * 3, dims
+
+    def _download_surface(self, surf: SphSurface):
+        v = np.zeros(surf.numVertices, SURFACE_VERTEX_DTYPE)
+        t = np.zeros((surf.numTriangles, 3), np.uint32)
+        _check(self._L.sph_surface_download(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
+        return v, t
+
+    def extract_surface(self, origin, spacing, dims, iso: float = 0.5, field: int = SPH_FIELD_FRACTION) -> SphSurface:
+        """sph_extract_surface: counts and borrowed device arrays (valid until the next extract call, ResetSimulation or close)."""
+        d = (C.c_int * 3)(*[int(x) for x in dims])
+        surf = SphSurface()
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_extract_surface(self._h, _f3(origin), _f3(spacing), d, int(field), float(iso), C.byref(surf)))
+        return surf
+
+    def surface(self, origin=None, spacing=None, dims=None, iso: float = 0.5, field: int = SPH_FIELD_FRACTION):
+        """Iso-surface {field >= iso} of the current state as a closed triangle mesh: (vertices of
+        SURFACE_VERTEX_DTYPE, triangles (T, 3) uint32).  Lattice members left None come from default_surface_lattice()."""
+        do, ds, dd = self.default_surface_lattice() if origin is None or spacing is None or dims is None else (None, None, None)
+        surf = self.extract_surface(do if origin is None else origin, ds if spacing is None else spacing, dd if dims is None else dims, iso, field)
+        return self._download_surface(surf)
+
+    def extract_surface_volume(self, dev_values: int, origin, spacing, dims, iso: float = 0.5) -> SphSurface:
+        """sph_extract_surface_volume on a device address: counts and borrowed device arrays."""
+        d = (C.c_int * 3)(*[int(x) for x in dims])
+        surf = SphSurface()
+        _check(self._L.sph_extract_surface_volume(self._h, C.c_void_p(dev_values), _f3(origin), _f3(spacing), d, float(iso), C.byref(surf)))
+        return surf
+
+    def surface_from_volume(self, values, origin, spacing, dims=None, iso: float = 0.5):
+        """Iso-surface {values >= iso} of a caller's lattice of floats (x fastest): a torch CUDA float32 tensor of shape (nz, ny, nx)
+        (dims may then be omitted) or a device address with dims = (nx, ny, nz).  Returns (vertices, triangles) like surface()."""
+        if hasattr(values, "data_ptr"):
+            if not values.is_cuda or values.dtype != __import__("torch").float32 or not values.is_contiguous():
+                raise SphError("surface_from_volume: values must be a contiguous float32 CUDA tensor")
+            if dims is None:
+                if values.dim() != 3:
+                    raise SphError(f"surface_from_volume: a tensor of shape {tuple(values.shape)} needs dims")
+                dims = (values.shape[2], values.shape[1], values.shape[0])
+            if int(np.prod([int(x) for x in dims])) != values.numel():
+                raise SphError(f"surface_from_volume: dims {tuple(dims)} do not match {values.numel()} values")
+            ptr = values.data_ptr()
+        else:
+            if dims is None:
+                raise SphError("surface_from_volume: a device address needs dims")
+            ptr = int(values)
+        surf = self.extract_surface_volume(ptr, origin, spacing, dims, iso)
+        return self._download_surface(surf)
 
     def sync(self):
         _check(self._L.sph_sync(self._h))

@@ -75,6 +75,7 @@ public:
         SphParams p = ToParams();
         if (Check(sph_set_params(engine, &p), "sph_set_params")) return;
         if (PushRiver()) return;                                        // riverMode && !terrainHeights.empty() selects the spawn branch (:104)
+        surface = SphSurface{};
         if (Check(sph_reset(engine, numParticles, seed), "sph_reset")) return;
         AfterSpawn();
         std::printf("Reset: particles=%zu fluids=%zu grid=%dx%dx%d cells=%d\n", particles.size(), numFluids, gridSizeX, gridSizeY, gridSizeZ, numCells);
@@ -161,6 +162,25 @@ public:
         const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
         return !Check(sph_sample_lattice(engine, o, s, dims, field, devOut), "sph_sample_lattice");
     }
+    // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
+    // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
+    // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per
+    // triangle).  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    bool ExtractSurface(const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], int field, float iso, SphSurface& out) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        surface = SphSurface{};
+        if (Check(sph_extract_surface(engine, o, s, dims, field, iso, &out), "sph_extract_surface")) return false;
+        surface = out;
+        return true;
+    }
+    bool DownloadSurface(std::vector<SphSurfaceVertex>& vertices, std::vector<uint32_t>& triangles3) {
+        vertices.resize(surface.numVertices);
+        triangles3.resize(size_t(surface.numTriangles) * 3);
+        return !Check(sph_surface_download(engine, vertices.empty() ? nullptr : vertices.data(), vertices.size(),
+                                           triangles3.empty() ? nullptr : triangles3.data(), triangles3.size() / 3), "sph_surface_download");
+    }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");
@@ -233,6 +253,7 @@ private:
     SphEngine* engine = nullptr;
     void* stream = nullptr;
     std::string lastError;
+    SphSurface surface{};                      // counts of the last ExtractSurface (DownloadSurface sizes its vectors from them)
 
     SphRiver ToRiver() const {
         return SphRiver{riverMode ? 1 : 0, terrainW, terrainH, terrainWorldMinX, terrainWorldMinZ, terrainWorldSizeX, terrainWorldSizeZ,

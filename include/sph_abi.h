@@ -32,6 +32,7 @@ extern "C" {
                                neighbour engines' plans, the RCCL transport sends them across each link first (sph_slab_set_verify), waits with a deadline (SPH_ERR_TIMEOUT,
                                sph_slab_set_deadline, sph_sync_deadline); flag 32; sph_slab_plan / _plans_agree, sph_comm_selftest_faces; SPH_OPT_NEIGHBOR_KERNEL 4 retired */
 /* (still 4, additions only: SphSample, SPH_FIELD_*, sph_sample_points / sph_sample_points_device / sph_sample_lattice -- field sampling) */
+/* (still 4, additions only: SphSurfaceVertex, SphSurface, sph_extract_surface / sph_extract_surface_volume / sph_surface_download -- iso-surface meshes) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -294,6 +295,38 @@ int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, Sp
  * one float per point (SPH_FIELD_DENSITY / _FRACTION / _PRESSURE / _SPEED) or one SphSample per point (SPH_FIELD_ALL).  dims >= 1,
  * at most 2^31 - 1 points; spacing finite and > 0.  Asynchronous on the engine's stream. */
 int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int field, void* devOut);
+
+/* ---- iso-surface of a lattice as a closed triangle mesh (no reference counterpart) ------------------------------
+ * Marching tetrahedra on the Kuhn (Freudenthal) split of the lattice origin + (float)i * spacing (x fastest, every dims >= 2, at most
+ * 2^31 - 1 points).  A point is inside iff its value >= iso (NaN never is).  Each crossed lattice edge (from point a in one of the 7
+ * directions x, y, xy, z, xz, yz, xyz) gets exactly one vertex, ordered by a's index, then direction; position pa + t (pb - pa) with
+ * t = (iso - fa) / (fb - fa); normal -(ga + t (gb - ga)) normalised, g the central (one-sided on the lattice's first and last point)
+ * difference of the values, (0, 0, 0) where it vanishes.  Triangles are ordered by cube, then tet, then table order, and wound so that
+ * their normals point out of the inside region.  With no inside point on the lattice's outer layer the mesh is a closed, oriented
+ * 2-manifold: every undirected edge in exactly two triangles.  The bits depend only on the values, iso, origin, spacing and dims.
+ * Both extract calls synchronise once (to read the counts back), then queue the vertex and triangle kernels on the engine's stream
+ * (timed as SPH_K_OTHER).  The returned device arrays are borrowed from the engine: valid until its next extract call, sph_reset or
+ * sph_destroy; after a failed extract call the engine holds no surface.  An empty surface has counts 0 and null arrays.
+ * SPH_ERR_ARG: a null argument, dims < 2 or more than 2^31 - 1 points, a spacing that is not finite and > 0, an iso that is not finite,
+ * a field other than SPH_FIELD_DENSITY / _FRACTION / _PRESSURE / _SPEED.  SPH_ERR_CAPACITY: more than 2^32 - 1 vertices or triangles. */
+typedef struct SphSurfaceVertex {
+    float pos[3];
+    float normal[3];
+} SphSurfaceVertex;                /* 24 bytes */
+typedef struct SphSurface {
+    uint32_t numVertices, numTriangles;
+    const SphSurfaceVertex* vertices;  /* device, borrowed */
+    const uint32_t* triangles;         /* device, borrowed: 3 vertex indices per triangle */
+} SphSurface;
+/* Samples `field` of the current state on the lattice exactly as sph_sample_lattice does (into engine-owned scratch), then meshes it.
+ * Refused with SPH_ERR_STATE where sampling is: z-slab engines and SPH_OPT_GRID_BUILD 1. */
+int sph_extract_surface(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int field, float iso, SphSurface* out);
+/* Meshes the caller's DEVICE array of dims[0] * dims[1] * dims[2] floats (x fastest).  Reads no particles: works on any engine. */
+int sph_extract_surface_volume(SphEngine* e, const float* devValues, const float origin[3], const float spacing[3], const int dims[3], float iso,
+                               SphSurface* out);
+/* Copies the last extracted surface to HOST arrays (vertexCap records, triangleCap triangles of 3 indices).  Synchronises.
+ * SPH_ERR_CAPACITY (nothing written) if a capacity is below the count; SPH_ERR_STATE if the engine holds no surface. */
+int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertexCap, uint32_t* triangles3, size_t triangleCap);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
