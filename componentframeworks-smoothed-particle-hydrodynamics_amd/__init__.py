@@ -11,5 +11,7 @@ from .engine import (  # noqa: F401
     compute_grid_extents, default_params, default_river, effective_half, generate_river_terrain, load_library, rotation_mat3, spawn_particles,
     spawn_river_particles, SAMPLE_DTYPE, SPH_FIELD_ALL, SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SphSample,
     gauge_levels, SURFACE_VERTEX_DTYPE, SphSurface, write_ply,
+    SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM, SPH_STAT_MAX_SPECS,
+    SPH_STAT_MAX_BINS, SphHistogramSpec, SphStatExtremum, SphStatistics, Statistics,
 )
 from . import build, synthetic  # noqa: F401

@@ -24,10 +24,12 @@
 #include "sph_walk.h"
 #include "sph_sample.h"
 #include "sph_surface.h"
+#include "sph_stats.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
+static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
 
 namespace {
 
@@ -188,6 +190,13 @@ struct SphEngine {
     size_t surfVertCap = 0, surfTriCap = 0;
     bool surfValid = false;
     uint32_t surfNumV = 0, surfNumT = 0;
+    // sph_statistics*: per-tile sums / partial records / histogram rows, the cells kernel's rows, and the device copy of the host variant's result
+    double* d_statSums = nullptr;
+    uint32_t* d_statPart = nullptr;
+    uint32_t* d_statHist = nullptr;
+    unsigned long long* d_statCell = nullptr;
+    unsigned long long* d_statOut = nullptr;
+    size_t statSumsCap = 0, statPartCap = 0, statHistCap = 0, statCellCap = 0, statOutCap = 0;
 
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
@@ -362,7 +371,8 @@ int import_state(SphEngine* e) {
 // ClearGrid + BuildGrid as a counting sort: after this, d_cellStart/d_order describe the
 // current state buffer.
 // commitLive (z-slab dispatch only): k_rank also stores the live count as the new slots-in-use count of the exchange.
-int build_grid(SphEngine* e, const SimK& k, bool commitLive = false) {
+// orderAll (sph_statistics only): k_rank writes order[] for every slot, not only for ghosts (the exact density is gathered through it).
+int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderAll = false) {
     const int n = (int)(e->slab ? e->nSlots : e->n), C = k.numCells;
     const int nb = blocks_for(n), sb = blocks_for((size_t)C, kScanTile);
     const bool sortedCopy = e->optGridBuild == 0;     // k_rank also writes the sorted copy the SPH pass reads
@@ -389,7 +399,11 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false) {
         Timed t(e, SPH_K_SCATTER);
         hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(kBlock), 0, e->stream, e->d_binKey, e->d_cellStart, e->d_tmp, n,
                            e->slab ? e->d_slabCnt + 2 : (const uint32_t*)nullptr);
-        if (sortedCopy) {
+        if (sortedCopy && orderAll) {
+            hipLaunchKernelGGL((k_rank<true, true>), dim3(nb), dim3(kBlock), 0, e->stream, e->d_tmp, e->d_cellStart, e->d_order, n, C,
+                               e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur], e->d_foam[e->cur], e->d_sPV, e->d_sOwn, k.gx, k.gy,
+                               (uint32_t*)nullptr);
+        } else if (sortedCopy) {
             hipLaunchKernelGGL((k_rank<true>), dim3(nb), dim3(kBlock), 0, e->stream, e->d_tmp, e->d_cellStart, e->d_order, n, C,
                                e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur], e->d_foam[e->cur], e->d_sPV, e->d_sOwn, k.gx, k.gy,
                                (commitLive && e->slab) ? e->d_slabCnt + 2 : (uint32_t*)nullptr);
@@ -747,6 +761,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_sampleIn); dev_free(e->d_sampleOut);
     dev_free(e->d_surfVol); dev_free(e->d_surfCode); dev_free(e->d_surfVOff); dev_free(e->d_surfTile); dev_free(e->d_surfTileOff);
     dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
+    dev_free(e->d_statSums); dev_free(e->d_statPart); dev_free(e->d_statHist); dev_free(e->d_statCell); dev_free(e->d_statOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (e->xstream) { (void)hipStreamSynchronize(e->xstream); (void)hipStreamDestroy(e->xstream); }
@@ -2107,7 +2122,7 @@ int sph_sync_deadline(SphEngine* e, double seconds) {
 // ---- field sampling (sph_sample.h) ---------------------------------------------------------------
 // The grid of the CURRENT state, built outside a substep exactly as sph_download_grid builds it.  The next dispatch builds its
 // own (dispatch_one always does), so nothing of this build reaches the simulation.
-static int sample_grid(SphEngine* e, SimK& k) {
+static int sample_grid(SphEngine* e, SimK& k, bool orderAll = false) {
     if (e->slab) return fail(SPH_ERR_STATE, "sampling a z-slab engine is not supported: its halo records after a step are the step's entry state");
     if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "sampling needs the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     int rc;
@@ -2116,7 +2131,7 @@ static int sample_grid(SphEngine* e, SimK& k) {
     if ((rc = ensure_grid_buffers(e))) return rc;
     make_simk(e->params, e->grid, e->params.param_timeStep, k);
     if ((rc = import_state(e))) return rc;
-    return build_grid(e, k);
+    return build_grid(e, k, false, orderAll);
 }
 
 int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, SphSample* devOut) {
@@ -2293,6 +2308,106 @@ int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertex
     if ((e->surfNumV && !vertices) || (e->surfNumT && !triangles3)) return fail(SPH_ERR_ARG, "null argument");
     if (e->surfNumV) HIP_TRY(hipMemcpyAsync(vertices, e->d_surfVerts, (size_t)e->surfNumV * sizeof(SphSurfaceVertex), hipMemcpyDeviceToHost, e->stream));
     if (e->surfNumT) HIP_TRY(hipMemcpyAsync(triangles3, e->d_surfTris, (size_t)e->surfNumT * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// ---- state statistics (sph_stats.h) ------------------------------------------------------------------
+static int stats_refused(SphEngine* e) {
+    if (e->slab) return fail(SPH_ERR_STATE, "statistics of a z-slab engine are not supported: the order of the fp64 sums is defined over one engine's grid");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "statistics need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    return SPH_OK;
+}
+
+static int stats_check_specs(const SphHistogramSpec* specs, int nSpecs, const uint64_t* histOut, sph::StatK& s) {
+    if (nSpecs < 0 || nSpecs > SPH_STAT_MAX_SPECS) return fail(SPH_ERR_ARG, "%d histogram specs (0 .. %d)", nSpecs, (int)SPH_STAT_MAX_SPECS);
+    if (nSpecs && (!specs || !histOut)) return fail(SPH_ERR_ARG, "null argument");
+    s.nSpecs = nSpecs;
+    s.histWords = 0;
+    for (int i = 0; i < sph::kStatMaxSpecs; ++i) { s.field[i] = 0; s.bins[i] = 1; s.off[i] = 0; s.lo[i] = 0.0f; s.hi[i] = 1.0f; s.scale[i] = 1.0f; }
+    for (int i = 0; i < nSpecs; ++i) {
+        const SphHistogramSpec& h = specs[i];
+        if (h.field < SPH_STAT_DENSITY || h.field > SPH_STAT_FOAM) return fail(SPH_ERR_ARG, "histogram %d: unknown field %d", i, h.field);
+        if (h.bins < 1 || h.bins > SPH_STAT_MAX_BINS) return fail(SPH_ERR_ARG, "histogram %d: %u bins (1 .. %d)", i, h.bins, (int)SPH_STAT_MAX_BINS);
+        if (!std::isfinite(h.lo) || !std::isfinite(h.hi)) return fail(SPH_ERR_ARG, "histogram %d: bounds %g, %g are not finite", i, (double)h.lo, (double)h.hi);
+        if (!(h.lo < h.hi)) return fail(SPH_ERR_ARG, "histogram %d: lo %g is not below hi %g", i, (double)h.lo, (double)h.hi);
+        const float width = h.hi - h.lo;
+        const float scale = (float)h.bins / width;
+        if (!std::isfinite(width) || !std::isfinite(scale)) return fail(SPH_ERR_ARG, "histogram %d: the bin scale bins / (hi - lo) is not finite in fp32", i);
+        s.field[i] = h.field; s.bins[i] = h.bins; s.off[i] = s.histWords; s.lo[i] = h.lo; s.hi[i] = h.hi; s.scale[i] = scale;
+        s.histWords += h.bins + 2u;
+    }
+    return SPH_OK;
+}
+
+// Grid build of the current state (as sampling, with order[] for every slot), then tiles, cells, finish and the histogram sum.
+static int stats_run(SphEngine* e, const sph::StatK& specs, SphStatistics* devOut, uint64_t* devHistOut) {
+    using namespace sph;
+    SimK k;
+    int rc;
+    if ((rc = sample_grid(e, k, true))) return rc;
+    StatK s = specs;
+    s.gminx = k.gminx; s.gminy = k.gminy; s.gminz = k.gminz; s.cellSize = k.cellSize;
+    s.gx = (float)k.gx; s.gy = (float)k.gy; s.gz = (float)k.gz;
+    s.cx = (double)e->params.param_boxCenter[0]; s.cy = (double)e->params.param_boxCenter[1]; s.cz = (double)e->params.param_boxCenter[2];
+    s.n = (int)e->n;
+    s.numCells = k.numCells;
+    s.nTiles = (int)((e->n + kStatTile - 1) / kStatTile);
+    s.tilesPow2 = 1;
+    while (s.tilesPow2 < s.nTiles) s.tilesPow2 <<= 1;
+    s.nBlocks = std::min(s.nTiles, kStatGrid);
+    const int cellBlocks = std::min(blocks_for(((size_t)k.numCells + 3) / 4), kStatCellBlocks);
+    if ((rc = surface_grow(e, e->d_statSums, e->statSumsCap, (size_t)kStatSums * s.tilesPow2)) ||
+        (rc = surface_grow(e, e->d_statPart, e->statPartCap, (size_t)kStatPartWords * kStatGrid)) ||
+        (rc = surface_grow(e, e->d_statHist, e->statHistCap, (size_t)std::max(s.nBlocks, 1) * std::max(s.histWords, 1u))) ||
+        (rc = surface_grow(e, e->d_statCell, e->statCellCap, (size_t)kStatCellBlocks * kStatCellCols))) return rc;
+    if (s.nTiles) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_stats_tiles, dim3(s.nBlocks), dim3(kBlock), 0, e->stream, s, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
+                           (const uint32_t*)e->d_order, (const float2*)e->d_rp[e->cur], e->d_statSums, e->d_statPart, e->d_statHist);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_stats_cells, dim3(cellBlocks), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_cellStart, k.numCells, e->d_statCell);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_stats_finish, dim3(kStatSums + 2), dim3(kBlock), 0, e->stream, s, e->d_statSums, (const uint32_t*)e->d_statPart,
+                           (const unsigned long long*)e->d_statCell, cellBlocks, devOut);
+    }
+    if (s.histWords) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_stats_hist, dim3((s.histWords + kStatHistBins - 1u) / kStatHistBins), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_statHist, s.nBlocks, s.histWords,
+                           reinterpret_cast<unsigned long long*>(devHistOut));
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_statistics_device(SphEngine* e, SphStatistics* devOut, const SphHistogramSpec* specs, int nSpecs, uint64_t* devHistOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!devOut) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = stats_refused(e))) return rc;
+    sph::StatK s{};
+    if ((rc = stats_check_specs(specs, nSpecs, devHistOut, s))) return rc;
+    return stats_run(e, s, devOut, devHistOut);
+}
+
+int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* specs, int nSpecs, uint64_t* histOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = stats_refused(e))) return rc;
+    sph::StatK s{};
+    if ((rc = stats_check_specs(specs, nSpecs, histOut, s))) return rc;
+    const size_t headWords = sizeof(SphStatistics) / sizeof(uint64_t);
+    if ((rc = surface_grow(e, e->d_statOut, e->statOutCap, headWords + (size_t)sph::kStatHistWords))) return rc;
+    SphStatistics* devOut = reinterpret_cast<SphStatistics*>(e->d_statOut);
+    uint64_t* devHist = reinterpret_cast<uint64_t*>(e->d_statOut + headWords);
+    if ((rc = stats_run(e, s, devOut, devHist))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, devOut, sizeof(SphStatistics), hipMemcpyDeviceToHost, e->stream));
+    if (s.histWords) HIP_TRY(hipMemcpyAsync(histOut, devHist, (size_t)s.histWords * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }

@@ -210,8 +210,8 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint2* __restrict__ bi
 // this pass removes that freedom.)  order[s] = source index of the particle in sorted slot s.
 // With COPY the pass also writes the physically sorted copy of the entry state that the SPH pass
 // reads (sph_pass.h SortedIn: a 32-byte record + 16 bytes of own data per particle; 1/rho is the one correctly rounded division per
-// neighbour of the numerics contract, item 9).
-template <bool COPY>
+// neighbour of the numerics contract, item 9).  ORDER_ALL is used by the statistics path alone; the substep launches <true> and <false>.
+template <bool COPY, bool ORDER_ALL = false>
 __global__ __launch_bounds__(kBlock) void k_rank(const uint2* __restrict__ tmp, const uint32_t* __restrict__ cellStart, uint32_t* __restrict__ order, int n, int numCells,
                                                  const float4* __restrict__ pos, const float4* __restrict__ vel,
                                                  const float2* __restrict__ rp, const float* __restrict__ foam,
@@ -262,7 +262,8 @@ __global__ __launch_bounds__(kBlock) void k_rank(const uint2* __restrict__ tmp, 
         for (uint32_t q = max(s, d0 + 64u); q < e; ++q) rank += (fbits(vel[tmp[q].x].w) < myId) ? 1u : 0u;       // ... and behind its last one
     }
     if (!act) return;
-    if (!COPY || (fbits(P.w) & F_GHOST1)) order[s + rank] = me.x;                  // (read only for ghosts: special_slot passes an inactive ghost's density through)
+    if (!COPY || ORDER_ALL || (fbits(P.w) & F_GHOST1)) order[s + rank] = me.x;     // (read only for ghosts: special_slot passes an inactive ghost's density through;
+                                                                                   //  ORDER_ALL, sph_stats.h only: every slot, for the gather of the exact density)
     if (COPY) {
         pv[2u * (s + rank)] = make_float4(P.x, P.y, P.z, RP.x > 0.0f ? 1.0f / RP.x : 0.0f);
         pv[2u * (s + rank) + 1u] = make_float4(V.x, V.y, V.z, RP.y);

@@ -108,6 +108,7 @@ ABI_SYMBOLS = (
     "sph_slab_debug_tight_messages", "sph_comm_selftest_faces",
     "sph_sample_points", "sph_sample_points_device", "sph_sample_lattice",
     "sph_extract_surface", "sph_extract_surface_volume", "sph_surface_download",
+    "sph_statistics", "sph_statistics_device",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -136,6 +137,122 @@ class SphSurface(C.Structure):
 
 SURFACE_VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,))])     # struct SphSurfaceVertex
 assert SURFACE_VERTEX_DTYPE.itemsize == 24
+
+
+class SphStatExtremum(C.Structure):
+    """struct SphStatExtremum of include/sph_abi.h: an extreme value and the particle id that attains it."""
+    _fields_ = [("value", C.c_float), ("id", C.c_uint32)]
+
+
+class SphStatistics(C.Structure):
+    """struct SphStatistics of include/sph_abi.h: 832 bytes."""
+    _fields_ = [
+        ("numRecords", C.c_uint64), ("numFluid", C.c_uint64), ("numActiveGhosts", C.c_uint64), ("numInactiveGhosts", C.c_uint64),
+        ("numOther", C.c_uint64), ("numNonFinite", C.c_uint64), ("numCounted", C.c_uint64), ("numEscaped", C.c_uint64),
+        ("firstNonFiniteId", C.c_uint32), ("firstEscapedId", C.c_uint32),
+        ("minPos", SphStatExtremum * 3), ("maxPos", SphStatExtremum * 3), ("minDensity", SphStatExtremum), ("maxDensity", SphStatExtremum),
+        ("minPressure", SphStatExtremum), ("maxPressure", SphStatExtremum), ("maxFoam", SphStatExtremum), ("maxSpeed2", SphStatExtremum),
+        ("maxSpeed", C.c_float), ("reserved0", C.c_uint32),
+        ("sumPos", C.c_double * 3), ("sumVel", C.c_double * 3), ("sumSpeed2", C.c_double), ("sumDensity", C.c_double),
+        ("sumDensity2", C.c_double), ("sumPressure", C.c_double), ("sumFoam", C.c_double), ("sumInvDensity", C.c_double),
+        ("sumAngular", C.c_double * 3),
+        ("occupiedCells", C.c_uint64), ("maxCellCount", C.c_uint32), ("maxCellIndex", C.c_uint32),
+        ("occupancy", C.c_uint64 * 65),
+    ]
+
+
+assert C.sizeof(SphStatistics) == 832
+
+
+class SphHistogramSpec(C.Structure):
+    """struct SphHistogramSpec of include/sph_abi.h: field (SPH_STAT_*), bins (1 .. 1024), lo < hi."""
+    _fields_ = [("field", C.c_int32), ("bins", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM = range(7)
+SPH_STAT_MAX_SPECS, SPH_STAT_MAX_BINS = 4, 1024
+
+
+def _histogram_specs(histograms):
+    """[(field, bins, lo, hi) | SphHistogramSpec, ...] -> (ctypes array or None, count, total uint64 slots).  Checked by the library."""
+    hs = list(histograms or ())
+    if not hs:
+        return None, 0, 0
+    arr = (SphHistogramSpec * len(hs))()
+    for i, h in enumerate(hs):
+        arr[i] = h if isinstance(h, SphHistogramSpec) else SphHistogramSpec(int(h[0]), int(h[1]), float(h[2]), float(h[3]))
+    return arr, len(hs), sum(int(a.bins) + 2 for a in arr)
+
+
+class Statistics:
+    """Result of SPHFluidGPU.statistics(): `s` is the SphStatistics struct (its members are also attributes of this object),
+    `histograms` a list of uint64 arrays of bins + 2 slots (below lo, the bins, at or above hi) in spec order.  The derived numbers
+    are computed here, on the host, from the struct and the members at the time of the call."""
+
+    def __init__(self, s: SphStatistics, histograms, params: SphParams):
+        self.s = s
+        self.histograms = histograms
+        self.mass, self.h, self.dt, self.rho0 = float(params.param_mass), float(params.param_h), float(params.param_timeStep), float(params.param_restDensity)
+        self.gravity = (float(params.param_gravityX), float(params.param_gravityY), float(params.param_gravityZ))
+
+    def __getattr__(self, name):
+        return getattr(object.__getattribute__(self, "s"), name)
+
+    def tobytes(self) -> bytes:
+        return bytes(self.s) + b"".join(h.tobytes() for h in self.histograms)
+
+    @property
+    def ok(self) -> bool:
+        """No non-finite and no escaped fluid record."""
+        return self.s.numNonFinite == 0 and self.s.numEscaped == 0
+
+    @property
+    def kinetic_energy(self) -> float:
+        return 0.5 * self.mass * self.s.sumSpeed2
+
+    @property
+    def potential_energy(self) -> float:
+        return -self.mass * sum(g * p for g, p in zip(self.gravity, self.s.sumPos))
+
+    @property
+    def momentum(self):
+        return tuple(self.mass * v for v in self.s.sumVel)
+
+    @property
+    def angular_momentum(self):
+        """About param_boxCenter."""
+        return tuple(self.mass * v for v in self.s.sumAngular)
+
+    @property
+    def center_of_mass(self):
+        n = self.s.numCounted
+        return tuple(p / n for p in self.s.sumPos) if n else (0.0, 0.0, 0.0)
+
+    @property
+    def bounding_box(self):
+        return tuple(e.value for e in self.s.minPos), tuple(e.value for e in self.s.maxPos)
+
+    @property
+    def mean_density(self) -> float:
+        n = self.s.numCounted
+        return self.s.sumDensity / n if n else 0.0
+
+    @property
+    def std_density(self) -> float:
+        n = self.s.numCounted
+        if not n:
+            return 0.0
+        m = self.s.sumDensity / n
+        return max(self.s.sumDensity2 / n - m * m, 0.0) ** 0.5
+
+    @property
+    def cfl(self) -> float:
+        return self.s.maxSpeed * self.dt / self.h
+
+    @property
+    def volume(self) -> float:
+        """SPH volume sum(mass / rho_j)."""
+        return self.mass * self.s.sumInvDensity
 
 
 class SphError(RuntimeError):
@@ -250,6 +367,8 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_extract_surface.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, C.c_float, C.POINTER(SphSurface)]
     L.sph_extract_surface_volume.argtypes = [vp, vp, f3, f3, C.POINTER(C.c_int), C.c_float, C.POINTER(SphSurface)]
     L.sph_surface_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+    L.sph_statistics.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.sph_statistics_device.argtypes = [vp, vp, vp, C.c_int, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default"):
@@ -684,6 +803,28 @@ class SPHFluidGPU:
             ptr = int(values)
         surf = self.extract_surface_volume(ptr, origin, spacing, dims, iso)
         return self._download_surface(surf)
+
+    # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
+    def statistics(self, histograms=None) -> Statistics:
+        """Counts, extrema, fp64 sums, cell occupancy and up to 4 histograms ((field, bins, lo, hi) with field one of SPH_STAT_*) of the
+        current state, reduced on the GPU.  Synchronises."""
+        specs, n, words = _histogram_specs(histograms)
+        out = SphStatistics()
+        hist = np.zeros(words, np.uint64)
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_statistics(self._h, C.byref(out), specs, n, hist.ctypes.data_as(C.c_void_p) if n else None))
+        hs, at = [], 0
+        for i in range(n):
+            hs.append(hist[at:at + specs[i].bins + 2].copy())
+            at += specs[i].bins + 2
+        return Statistics(out, hs, self._p)
+
+    def statistics_device(self, dev_out: int, histograms=None, dev_hist: int = 0):
+        """The same into device memory: an 832-byte SphStatistics at dev_out and sum(bins + 2) uint64 at dev_hist (torch tensors'
+        data_ptr(), say).  Asynchronous on the engine's stream."""
+        specs, n, _ = _histogram_specs(histograms)
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_statistics_device(self._h, C.c_void_p(dev_out), specs, n, C.c_void_p(dev_hist) if dev_hist else None))
 
     def sync(self):
         _check(self._L.sph_sync(self._h))

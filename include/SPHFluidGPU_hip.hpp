@@ -16,6 +16,7 @@
 // SPH_HIP_HAVE_MATHLIB before including this header; otherwise minimal PODs are provided.
 #pragma once
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -181,6 +182,44 @@ public:
         return !Check(sph_surface_download(engine, vertices.empty() ? nullptr : vertices.data(), vertices.size(),
                                            triangles3.empty() ? nullptr : triangles3.data(), triangles3.size() / 3), "sph_surface_download");
     }
+    // State statistics (engine extension, sph_abi.h "statistics"): counts, extrema with ids, fp64 sums in a fixed
+    // order, cell occupancy and up to 4 histograms (histograms[k]: bins + 2 slots) of the current state, reduced on the device.
+    // Members are pushed first, as DispatchCompute does.  Synchronises.  Returns false on error (LastError()).
+    bool Statistics(SphStatistics& out, const std::vector<SphHistogramSpec>& specs = {}, std::vector<std::vector<uint64_t>>* histograms = nullptr) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        size_t words = 0;
+        for (const auto& h : specs) words += size_t(h.bins) + 2;
+        std::vector<uint64_t> flat(words);
+        if (Check(sph_statistics(engine, &out, specs.empty() ? nullptr : specs.data(), int(specs.size()), flat.empty() ? nullptr : flat.data()),
+                  "sph_statistics")) return false;
+        if (histograms) {
+            histograms->clear();
+            size_t at = 0;
+            for (const auto& h : specs) {
+                histograms->emplace_back(flat.begin() + at, flat.begin() + at + h.bins + 2);
+                at += size_t(h.bins) + 2;
+            }
+        }
+        return true;
+    }
+    // Derived numbers of a Statistics result with the CURRENT members (they are not part of the device contract).
+    double KineticEnergy(const SphStatistics& s) const { return 0.5 * double(param_mass) * s.sumSpeed2; }
+    double PotentialEnergy(const SphStatistics& s) const {
+        return -double(param_mass) * (double(param_gravityX) * s.sumPos[0] + double(param_gravityY) * s.sumPos[1] + double(param_gravityZ) * s.sumPos[2]);
+    }
+    MATH::Vec3 CentreOfMass(const SphStatistics& s) const {
+        const double n = s.numCounted ? double(s.numCounted) : 1.0;
+        return MATH::Vec3(float(s.sumPos[0] / n), float(s.sumPos[1] / n), float(s.sumPos[2] / n));
+    }
+    double MeanDensity(const SphStatistics& s) const { return s.numCounted ? s.sumDensity / double(s.numCounted) : 0.0; }
+    double StdDensity(const SphStatistics& s) const {
+        if (!s.numCounted) return 0.0;
+        const double m = s.sumDensity / double(s.numCounted), v = s.sumDensity2 / double(s.numCounted) - m * m;
+        return v > 0.0 ? std::sqrt(v) : 0.0;
+    }
+    double Cfl(const SphStatistics& s) const { return double(s.maxSpeed) * double(param_timeStep) / double(param_h); }
+    double SphVolume(const SphStatistics& s) const { return double(param_mass) * s.sumInvDensity; }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");

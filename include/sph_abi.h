@@ -33,6 +33,7 @@ extern "C" {
                                sph_slab_set_deadline, sph_sync_deadline); flag 32; sph_slab_plan / _plans_agree, sph_comm_selftest_faces; SPH_OPT_NEIGHBOR_KERNEL 4 retired */
 /* (still 4, additions only: SphSample, SPH_FIELD_*, sph_sample_points / sph_sample_points_device / sph_sample_lattice -- field sampling) */
 /* (still 4, additions only: SphSurfaceVertex, SphSurface, sph_extract_surface / sph_extract_surface_volume / sph_surface_download -- iso-surface meshes) */
+/* (still 4, additions only: SphStatistics, SphStatExtremum, SphHistogramSpec, SPH_STAT_*, sph_statistics / sph_statistics_device -- state statistics) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -327,6 +328,56 @@ int sph_extract_surface_volume(SphEngine* e, const float* devValues, const float
 /* Copies the last extracted surface to HOST arrays (vertexCap records, triangleCap triangles of 3 indices).  Synchronises.
  * SPH_ERR_CAPACITY (nothing written) if a capacity is below the count; SPH_ERR_STATE if the engine holds no surface. */
 int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertexCap, uint32_t* triangles3, size_t triangleCap);
+
+/* ---- statistics of the particle state (no reference counterpart) -------------------------------------------------
+ * Totals, extrema and histograms of the state the next dispatch would start from, reduced on the device.  The result is a pure function
+ * of the 80-byte records sph_download_particles would return, the current members and the grid they imply.
+ * Sets: fluid = isGhost == 0; active ghost = isGhost == 1 && isActive != 0; inactive ghost = isGhost == 1 && isActive == 0; other = the
+ * rest.  A fluid record is non-finite if any of pos.xyz, vel.xyz, density, pressure, padA is not finite.  The COUNTED set is the finite
+ * fluid records: everything except the counts is over it.  A counted record has escaped if floorf((p - gridMin) / cellSize) is < 0 or
+ * >= the grid dimension on some axis (the unclamped cell index of BuildGrid).
+ * Extrema compare with the fp32 <; of records that compare equal the lowest id wins and its stored bits are reported; an empty counted
+ * set gives min +inf, max -inf, id 0xFFFFFFFF.  speed2 = (vx*vx + vy*vy) + vz*vz in fp32 without fma; maxSpeed = sqrtf(maxSpeed2.value).
+ * Sums are fp64 (every fp32 value converted first, no fma), in a FIXED order: the slots in canonical order (cell ascending, id ascending
+ * inside a cell; records outside the counted set contribute +0.0), tiles of 2048 slots reduced by pairwise halving
+ * (x[i] += x[i + s], s = 1024 .. 1), the tile sums padded to a power of two and reduced by the same halving.  Terms: pos, vel,
+ * (vx*vx + vy*vy) + vz*vz, density, density*density, pressure, padA (foam), 1.0 / density (0 where density <= 0), and
+ * (pos - param_boxCenter) x vel (d = pos - c in fp64, then (dy*vz - dz*vy, dz*vx - dx*vz, dx*vy - dy*vx)).
+ * Cell occupancy comes from the grid: occupancy[m] = cells with exactly m members (m < 64), occupancy[64] = cells with >= 64.
+ * Histogram k of a field over the counted set has bins_k + 2 slots of uint64: v < lo -> slot 0, v >= hi -> slot bins + 1, otherwise
+ * 1 + min((int)floorf((v - lo) * ((float)bins / (hi - lo))), bins - 1), all in fp32; SPH_STAT_SPEED bins sqrtf(speed2), SPH_STAT_FOAM padA.
+ * Every call first builds the grid of the current state as sampling does (timed under the bin / scan / scatter classes); the statistics
+ * kernels are timed as SPH_K_OTHER.  The next dispatch builds its own grid: a call never changes the simulation.
+ * SPH_ERR_STATE (before any allocation): z-slab engines, SPH_OPT_GRID_BUILD 1.  SPH_ERR_ARG: a null output, nSpecs outside 0..4, null
+ * specs or histogram output with nSpecs > 0, an unknown field, bins outside 1..1024, lo or hi not finite, lo >= hi, or a bin scale
+ * (float)bins / (hi - lo) that is not finite in fp32.  With no particles: all-zero counts and sums, the empty-set extrema. */
+typedef struct SphStatExtremum {
+    float value;
+    uint32_t id;                   /* particle id (index of the record) that attains it; 0xFFFFFFFF if none */
+} SphStatExtremum;                 /* 8 bytes */
+typedef struct SphStatistics {
+    uint64_t numRecords, numFluid, numActiveGhosts, numInactiveGhosts, numOther, numNonFinite, numCounted, numEscaped;
+    uint32_t firstNonFiniteId, firstEscapedId;          /* lowest id among them, 0xFFFFFFFF if none */
+    SphStatExtremum minPos[3], maxPos[3], minDensity, maxDensity, minPressure, maxPressure, maxFoam, maxSpeed2;
+    float maxSpeed;
+    uint32_t reserved0;                                 /* 0 */
+    double sumPos[3], sumVel[3], sumSpeed2, sumDensity, sumDensity2, sumPressure, sumFoam, sumInvDensity, sumAngular[3];
+    uint64_t occupiedCells;
+    uint32_t maxCellCount, maxCellIndex;                /* the largest member count of a cell and the lowest cell index that has it */
+    uint64_t occupancy[65];
+} SphStatistics;                   /* 832 bytes */
+typedef struct SphHistogramSpec {
+    int32_t field;                 /* SPH_STAT_* */
+    uint32_t bins;                 /* 1 .. 1024 */
+    float lo, hi;                  /* finite, lo < hi */
+} SphHistogramSpec;                /* 16 bytes */
+enum { SPH_STAT_DENSITY = 0, SPH_STAT_PRESSURE = 1, SPH_STAT_SPEED = 2, SPH_STAT_POS_X = 3, SPH_STAT_POS_Y = 4, SPH_STAT_POS_Z = 5, SPH_STAT_FOAM = 6 };
+enum { SPH_STAT_MAX_SPECS = 4, SPH_STAT_MAX_BINS = 1024 };
+/* Statistics into a HOST struct and HOST histograms (histogram k: bins_k + 2 consecutive uint64_t, in spec order).  `specs` is a host
+ * array of nSpecs <= 4 entries (nSpecs == 0 with null specs / histOut is the common case).  Synchronises. */
+int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* specs, int nSpecs, uint64_t* histOut);
+/* The same into a DEVICE struct and DEVICE histograms (`specs` stays a host array); asynchronous on the engine's stream. */
+int sph_statistics_device(SphEngine* e, SphStatistics* devOut, const SphHistogramSpec* specs, int nSpecs, uint64_t* devHistOut);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
