@@ -13,5 +13,6 @@ from .engine import (  # noqa: F401
     gauge_levels, SURFACE_VERTEX_DTYPE, SphSurface, write_ply,
     SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM, SPH_STAT_MAX_SPECS,
     SPH_STAT_MAX_BINS, SphHistogramSpec, SphStatExtremum, SphStatistics, Statistics,
+    SPH_TRACER_EULER, SPH_TRACER_MIDPOINT, SphTracer, TRACER_DTYPE, write_pathlines_ply,
 )
 from . import build, synthetic  # noqa: F401

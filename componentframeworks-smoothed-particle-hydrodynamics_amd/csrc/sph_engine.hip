@@ -24,10 +24,12 @@
 #include "sph_walk.h"
 #include "sph_sample.h"
 #include "sph_surface.h"
+#include "sph_tracer.h"
 #include "sph_stats.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
+static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
 
@@ -198,6 +200,23 @@ struct SphEngine {
     unsigned long long* d_statOut = nullptr;
     size_t statSumsCap = 0, statPartCap = 0, statHistCap = 0, statCellCap = 0, statOutCap = 0;
 
+    // sph_tracers_*: M records in the caller's order (two float4 each), their processing order, the pathline ring of K x M float4, the
+    // device step counter (sph_tracer.h) and the scratch of the processing order's cell sort
+    float4* d_trRec = nullptr;
+    uint32_t* d_trPerm = nullptr;
+    float4* d_trRing = nullptr;
+    uint32_t* d_trState = nullptr;
+    uint2* d_trKey = nullptr;
+    uint32_t *d_trCellCount = nullptr, *d_trCellStart = nullptr, *d_trBlockSums = nullptr;
+    size_t trM = 0, trCap = 0, trRingCap = 0;
+    int trCells = 0;
+    int trIntegrator = 0;
+    uint32_t trK = 0, trS = 1;
+    uint64_t trSteps = 0;                // host mirror of the device step counter: non-paused substeps issued since sph_tracers_set
+    uint64_t trSorted = 0;               // trSteps at the last cell sort of the processing order
+    bool trOrdered = false;              // the processing order has been cell-sorted since sph_tracers_set
+    bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
+
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
     // timing
@@ -287,6 +306,16 @@ void free_grid_buffers(SphEngine* e) {
     e->graphs.clear();
     dev_free(e->d_cellCount); dev_free(e->d_cellStart); dev_free(e->d_blockSums);
     e->allocatedCells = 0;
+}
+
+void tracers_free(SphEngine* e) {
+    if (e->d_trRec && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(e->d_trRec); dev_free(e->d_trPerm); dev_free(e->d_trRing); dev_free(e->d_trState); dev_free(e->d_trKey);
+    dev_free(e->d_trCellCount); dev_free(e->d_trCellStart); dev_free(e->d_trBlockSums);
+    e->trM = e->trCap = e->trRingCap = 0;
+    e->trCells = 0;
+    e->trK = 0; e->trS = 1; e->trSteps = e->trSorted = 0;
+    e->trOrdered = false;
 }
 
 int alloc_particle_buffers(SphEngine* e, size_t n) {
@@ -417,6 +446,57 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
     return SPH_OK;
 }
 
+// ---- tracers (sph_tracer.h) --------------------------------------------------------------------
+// The processing order: tracers sorted by the cell they are in, re-sorted when kTracerRefresh substeps have passed since the last sort.
+// Never launched while sph_dispatch_n captures (a graph would replay the sort at every call): sph_dispatch_n sorts before it replays.
+int tracers_order(SphEngine* e, const SimK& k) {
+    if (!e->trM || e->capturing) return SPH_OK;
+    if (e->trOrdered && e->trSteps - e->trSorted < (uint64_t)kTracerRefresh) return SPH_OK;
+    const int C = k.numCells, sb = blocks_for((size_t)C, kScanTile);
+    int rc;
+    if (e->trCells != C || !e->d_trCellCount) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        dev_free(e->d_trCellCount); dev_free(e->d_trCellStart); dev_free(e->d_trBlockSums);
+        e->trCells = 0;
+        if ((rc = dev_alloc(&e->d_trCellCount, (size_t)C)) || (rc = dev_alloc(&e->d_trCellStart, (size_t)C + 1)) ||
+            (rc = dev_alloc(&e->d_trBlockSums, (size_t)sb + 1))) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_trCellCount, 0, (size_t)C * sizeof(uint32_t), e->stream));      // (k_scan_apply leaves it zero again)
+        e->trCells = C;
+    }
+    const uint32_t m = (uint32_t)e->trM;
+    const int rawSums = sb <= kScanFusedBlocks ? 1 : 0;
+    Timed t(e, SPH_K_OTHER);
+    hipLaunchKernelGGL(k_tracer_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_trRec, e->d_trKey, e->d_trCellCount, m);
+    hipLaunchKernelGGL(k_scan_reduce, dim3(sb), dim3(kBlock), 0, e->stream, e->d_trCellCount, e->d_trBlockSums, C);
+    if (!rawSums) hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(kBlock), 0, e->stream, e->d_trBlockSums, sb);
+    hipLaunchKernelGGL(k_scan_apply, dim3(sb), dim3(kBlock), 0, e->stream, e->d_trCellCount, e->d_trBlockSums, e->d_trCellStart, C, m, rawSums);
+    hipLaunchKernelGGL(k_tracer_scatter, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_trKey, e->d_trCellStart, e->d_trPerm, m);
+    HIP_TRY(hipGetLastError());
+    e->trSorted = e->trSteps;
+    e->trOrdered = true;
+    return SPH_OK;
+}
+
+// One substep's tracer work, behind build_grid of that substep: advect on the sorted copy of the entry state, then advance the device counter.
+int tracers_advect(SphEngine* e, const SimK& k, float dt) {
+    int rc;
+    if ((rc = tracers_order(e, k))) return rc;
+    const uint32_t m = (uint32_t)e->trM;
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (e->trIntegrator == SPH_TRACER_MIDPOINT)
+            hipLaunchKernelGGL((k_tracer_advect<true>), dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, e->d_cellStart, dt,
+                               (const uint32_t*)e->d_trPerm, e->d_trRec, e->d_trRing, (const uint32_t*)e->d_trState, m);
+        else
+            hipLaunchKernelGGL((k_tracer_advect<false>), dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, e->d_cellStart, dt,
+                               (const uint32_t*)e->d_trPerm, e->d_trRec, e->d_trRing, (const uint32_t*)e->d_trState, m);
+        hipLaunchKernelGGL(k_tracer_tick, dim3(1), dim3(64), 0, e->stream, e->d_trState, e->trK, e->trS);
+    }
+    HIP_TRY(hipGetLastError());
+    e->trSteps += 1;
+    return SPH_OK;
+}
+
 int writeback(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "a slab engine has no local 80-byte array: use sph_slab_download");
     if (e->aosValid) return SPH_OK;
@@ -459,6 +539,8 @@ int ensure_shape_table(SphEngine* e) {
 int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     if (e->params.param_pause) { if (boundaryFirst) HIP_TRY(hipEventRecord(e->evBoundary, e->stream)); return SPH_OK; }                               // SPHFluid3D.cpp:432
     int rc;
+    if (e->trM && e->optGridBuild == 1)
+        return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params))) return rc;
     const float dt = overrideDt > 0.0f ? overrideDt : e->params.param_timeStep;   // :434
     e->lastDt = dt;
@@ -504,6 +586,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         }
     } else {
     if ((rc = build_grid(e, k, true))) return rc;                           // :449-468
+    if (e->trM && (rc = tracers_advect(e, k, dt))) return rc;               // (reads the sorted copy and cellStart, as the SPH pass does)
     if (n) {                                                                // :470-509 (SPH + OBB fused)
         if (!e->d_sPV || e->sortedCap < (size_t)n) return fail(SPH_ERR_STATE, "sorted copy missing");
         const uint32_t* live = e->slab ? e->d_cellStart + k.numCells : nullptr;
@@ -761,6 +844,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_sampleIn); dev_free(e->d_sampleOut);
     dev_free(e->d_surfVol); dev_free(e->d_surfCode); dev_free(e->d_surfVOff); dev_free(e->d_surfTile); dev_free(e->d_surfTileOff);
     dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
+    tracers_free(e);
     dev_free(e->d_statSums); dev_free(e->d_statPart); dev_free(e->d_statHist); dev_free(e->d_statCell); dev_free(e->d_statOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -791,6 +875,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     if ((rc = validate_params(e->params))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
+    tracers_free(e);                                                  // (and the tracer set)
     std::vector<SphParticle> v;
     float m;
     if (e->river.riverMode && !e->terrainHeights.empty())             // :104
@@ -868,12 +953,17 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
                          (int)e->idBase, e->allocatedCells, 0};
     add(opts, sizeof(opts));
     const void* ptrs[20] = {e->d_aos, e->d_pos[0], e->d_pos[1], e->d_vel[0], e->d_vel[1], e->d_rp[0], e->d_rp[1], e->d_foam[0], e->d_foam[1], e->d_acc,
-                            e->d_binKey, e->d_binKey, e->d_order, e->d_tmp, e->d_cellCount, e->d_cellStart, e->d_blockSums, e->d_sPV, e->d_sPV, e->d_sOwn};
+                            e->d_binKey, e->d_intent, e->d_order, e->d_tmp, e->d_cellCount, e->d_cellStart, e->d_blockSums, e->d_sPV, e->d_sPV, e->d_sOwn};
     add(ptrs, sizeof(ptrs));
     const void* more[3] = {e->d_llNext, e->d_shapeTab, e->d_stats};
     add(more, sizeof(more));
     const size_t sz[2] = {e->n, e->cap};
     add(sz, sizeof(sz));
+    // tracers: a call with tracers is never served by a graph captured without them, with another set's buffers or another history layout
+    const void* tr[4] = {e->d_trRec, e->d_trPerm, e->d_trRing, e->d_trState};
+    add(tr, sizeof(tr));
+    const uint64_t trv[4] = {(uint64_t)e->trM, (uint64_t)e->trIntegrator, e->trK, e->trS};
+    add(trv, sizeof(trv));
     return m;
 }
 static uint64_t graph_hash(const std::vector<unsigned char>& m) {
@@ -898,6 +988,13 @@ int sph_dispatch_n(SphEngine* e, float overrideDt, int nSubsteps) {
         for (auto& g : e->graphs) if (g.key == key && g.material == material) { hit = &g; break; }
         if (hit && hit->exec) {
             sph::compute_grid_extents(e->params, e->grid);       // what an eager dispatch would have refreshed (sph_grid_info, RefreshGrid)
+            if (e->trM) {                                        // the processing order is re-sorted between calls, never inside a graph
+                int trc;
+                SimK k;
+                make_simk(e->params, e->grid, e->params.param_timeStep, k);
+                if ((trc = tracers_order(e, k))) return trc;
+                e->trSteps += (uint64_t)nSubsteps;               // (the replayed k_tracer_tick launches advance the device counter)
+            }
             HIP_TRY(hipGraphLaunch(hit->exec, e->stream));
             e->cur = hit->postCur; e->aosValid = hit->postAos; e->accValid = hit->postAcc; e->internalValid = true;
             hit->lastUse = ++e->graphClock;
@@ -906,9 +1003,19 @@ int sph_dispatch_n(SphEngine* e, float overrideDt, int nSubsteps) {
         }
     }
     const bool capture = graphable && hit;                   // seen once, run eagerly then: every buffer exists
+    if (capture && e->trM) {                                 // (as before a replay: the cell sort stays outside the graph)
+        sph::compute_grid_extents(e->params, e->grid);
+        int trc;
+        if ((trc = ensure_grid_buffers(e))) return trc;
+        SimK k;
+        make_simk(e->params, e->grid, e->params.param_timeStep, k);
+        if ((trc = tracers_order(e, k))) return trc;
+    }
     if (capture) HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    e->capturing = capture;
     int rc = SPH_OK;
     for (int i = 0; i < nSubsteps && !rc; ++i) rc = dispatch_one(e, overrideDt);
+    e->capturing = false;
     if (capture) {
         hipGraph_t graph = nullptr;
         hipError_t er = hipStreamEndCapture(e->stream, &graph);
@@ -2409,6 +2516,104 @@ int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* spe
     HIP_TRY(hipMemcpyAsync(out, devOut, sizeof(SphStatistics), hipMemcpyDeviceToHost, e->stream));
     if (s.histWords) HIP_TRY(hipMemcpyAsync(histOut, devHist, (size_t)s.histWords * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// ---- passive tracers (sph_tracer.h) ---------------------------------------------------------------
+static int tracers_check(SphEngine* e, const float* points4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "tracers on a z-slab engine are not supported: its halo records after a step are the step's entry state");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (m && !points4) return fail(SPH_ERR_ARG, "null argument");
+    if (integrator != SPH_TRACER_EULER && integrator != SPH_TRACER_MIDPOINT) return fail(SPH_ERR_ARG, "unknown integrator %d", integrator);
+    if (historyStride == 0) return fail(SPH_ERR_ARG, "historyStride must be >= 1");
+    if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu tracers exceed 2^31 - 1", m);
+    if ((unsigned long long)historyCap * (unsigned long long)m > 2147483647ull)
+        return fail(SPH_ERR_ARG, "a history of %u snapshots of %zu tracers exceeds 2^31 - 1 float4", historyCap, m);
+    return SPH_OK;
+}
+
+int sph_tracers_set_device(SphEngine* e, const float* devPoints4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride) {
+    int rc;
+    if ((rc = tracers_check(e, devPoints4, m, integrator, historyCap, historyStride))) return rc;
+    if (m == 0) { tracers_free(e); return SPH_OK; }
+    const size_t ring = (size_t)historyCap * m;
+    if (m > e->trCap || ring > e->trRingCap || !e->d_trRec) {             // (a set of the same shape reuses the buffers, and the graphs captured over them)
+        tracers_free(e);
+        if ((rc = dev_alloc(&e->d_trRec, 2 * m)) || (rc = dev_alloc(&e->d_trPerm, m)) || (rc = dev_alloc(&e->d_trKey, m)) ||
+            (rc = dev_alloc(&e->d_trRing, ring)) || (rc = dev_alloc(&e->d_trState, 4))) { tracers_free(e); return rc; }
+        e->trCap = m; e->trRingCap = ring;
+    }
+    e->trM = m; e->trIntegrator = integrator; e->trK = historyCap; e->trS = historyStride;
+    e->trSteps = e->trSorted = 0;
+    e->trOrdered = false;
+    hipLaunchKernelGGL(k_tracer_seed, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, reinterpret_cast<const float4*>(devPoints4), e->d_trRec, e->d_trPerm,
+                       e->d_trRing, e->d_trState, (uint32_t)m, historyCap, historyStride);
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_tracers_set(SphEngine* e, const float* points4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride) {
+    int rc;
+    if ((rc = tracers_check(e, points4, m, integrator, historyCap, historyStride))) return rc;
+    if (m == 0) { tracers_free(e); return SPH_OK; }
+    float4* staging = nullptr;
+    if ((rc = dev_alloc(&staging, m))) return rc;
+    hipError_t er = hipMemcpyAsync(staging, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream);
+    if (er == hipSuccess) rc = sph_tracers_set_device(e, reinterpret_cast<const float*>(staging), m, integrator, historyCap, historyStride);
+    const hipError_t es = hipStreamSynchronize(e->stream);
+    dev_free(staging);
+    if (er != hipSuccess) return fail(SPH_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(er));
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(SPH_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
+    return SPH_OK;
+}
+
+size_t sph_tracers_count(const SphEngine* e) { return e ? e->trM : 0; }
+
+int sph_tracers_info(const SphEngine* e, uint64_t* substeps, uint32_t* snapshots, uint64_t* firstSnapshot) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    const uint64_t last = e->trSteps / e->trS;                            // number of the newest snapshot
+    const uint64_t count = (e->trM && e->trK) ? std::min<uint64_t>(last + 1, e->trK) : 0;
+    if (substeps) *substeps = e->trSteps;
+    if (snapshots) *snapshots = (uint32_t)count;
+    if (firstSnapshot) *firstSnapshot = count ? last + 1 - count : 0;
+    return SPH_OK;
+}
+
+int sph_tracers_download(SphEngine* e, SphTracer* out, size_t cap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (cap < e->trM) return fail(SPH_ERR_CAPACITY, "%zu tracers (capacity %zu)", e->trM, cap);
+    if (e->trM && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (e->trM) HIP_TRY(hipMemcpyAsync(out, e->d_trRec, e->trM * sizeof(SphTracer), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_tracers_device(SphEngine* e, const SphTracer** devPtr) {
+    if (!e || !devPtr) return fail(SPH_ERR_ARG, "null argument");
+    *devPtr = e->trM ? reinterpret_cast<const SphTracer*>(e->d_trRec) : nullptr;
+    return SPH_OK;
+}
+
+int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t* snapshotsOut, uint64_t* firstSnapshotOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->trM || !e->trK) return fail(SPH_ERR_STATE, "no pathline history: call sph_tracers_set with historyCap >= 1 first");
+    uint32_t count = 0;
+    uint64_t first = 0;
+    (void)sph_tracers_info(e, nullptr, &count, &first);
+    if (snapshotCap < count) return fail(SPH_ERR_CAPACITY, "%u snapshots (capacity %zu)", count, snapshotCap);
+    if (!out4) return fail(SPH_ERR_ARG, "null argument");
+    // snapshot q lives in slot q mod K: the stored ones are at most two contiguous pieces of the ring
+    const size_t snap = e->trM * 4;                                        // floats per snapshot
+    const uint32_t s0 = (uint32_t)(first % e->trK);
+    const uint32_t n0 = std::min<uint32_t>(count, e->trK - s0);
+    HIP_TRY(hipMemcpyAsync(out4, reinterpret_cast<const float*>(e->d_trRing) + (size_t)s0 * snap, (size_t)n0 * snap * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (count > n0)
+        HIP_TRY(hipMemcpyAsync(out4 + (size_t)n0 * snap, e->d_trRing, (size_t)(count - n0) * snap * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (snapshotsOut) *snapshotsOut = count;
+    if (firstSnapshotOut) *firstSnapshotOut = first;
     return SPH_OK;
 }
 

@@ -109,6 +109,8 @@ ABI_SYMBOLS = (
     "sph_sample_points", "sph_sample_points_device", "sph_sample_lattice",
     "sph_extract_surface", "sph_extract_surface_volume", "sph_surface_download",
     "sph_statistics", "sph_statistics_device",
+    "sph_tracers_set", "sph_tracers_set_device", "sph_tracers_count", "sph_tracers_info", "sph_tracers_download", "sph_tracers_device",
+    "sph_tracers_history",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -128,6 +130,17 @@ SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("pressure", "
                          ("vel", "<f4", (3,)), ("pad", "<f4")])
 assert SAMPLE_DTYPE.itemsize == 32
 SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SPH_FIELD_ALL = 0, 1, 2, 3, 4
+
+
+class SphTracer(C.Structure):
+    """struct SphTracer of include/sph_abi.h: one passive tracer (see SPHFluidGPU.set_tracers)."""
+    _fields_ = [("pos", C.c_float * 3), ("age", C.c_float), ("vel", C.c_float * 3), ("fraction", C.c_float)]
+
+
+assert C.sizeof(SphTracer) == 32
+TRACER_DTYPE = np.dtype([("pos", "<f4", (3,)), ("age", "<f4"), ("vel", "<f4", (3,)), ("fraction", "<f4")])
+assert TRACER_DTYPE.itemsize == 32
+SPH_TRACER_EULER, SPH_TRACER_MIDPOINT = 0, 1
 
 
 class SphSurface(C.Structure):
@@ -369,9 +382,17 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_surface_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     L.sph_statistics.argtypes = [vp, vp, vp, C.c_int, vp]
     L.sph_statistics_device.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.sph_tracers_set.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
+    L.sph_tracers_set_device.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
+    L.sph_tracers_count.argtypes = [vp]
+    L.sph_tracers_count.restype = C.c_size_t
+    L.sph_tracers_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.sph_tracers_download.argtypes = [vp, vp, C.c_size_t]
+    L.sph_tracers_device.argtypes = [vp, C.POINTER(C.c_void_p)]
+    L.sph_tracers_history.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
-        if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default"):
+        if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count"):
             fn.restype = C.c_int
     _lib = L
     return L
@@ -489,6 +510,26 @@ def write_ply(path, vertices: np.ndarray, triangles: np.ndarray) -> None:
         fh.write(head.encode("ascii"))
         fh.write(v.tobytes())
         fh.write(faces.tobytes())
+
+
+def write_pathlines_ply(path, history: np.ndarray) -> None:
+    """Binary little-endian PLY of pathlines: history is (count, M, 4) as SPHFluidGPU.tracer_history returns it; one vertex
+    (x, y, z, age) per snapshot and tracer, one edge between consecutive snapshots of the same tracer."""
+    h = np.ascontiguousarray(history, dtype="<f4")
+    if h.ndim != 3 or h.shape[2] != 4:
+        raise SphError(f"write_pathlines_ply: history must have shape (count, M, 4), not {h.shape}")
+    count, m = h.shape[0], h.shape[1]
+    a = (np.arange(max(count - 1, 0), dtype=np.int64)[:, None] * m + np.arange(m, dtype=np.int64)[None, :]).reshape(-1)
+    edges = np.empty((len(a), 2), "<i4")
+    edges[:, 0] = a
+    edges[:, 1] = a + m
+    head = ("ply\nformat binary_little_endian 1.0\ncomment tracer pathlines (DESIGN.md section 3d)\n"
+            f"element vertex {count * m}\nproperty float x\nproperty float y\nproperty float z\nproperty float age\n"
+            f"element edge {len(edges)}\nproperty int vertex1\nproperty int vertex2\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(head.encode("ascii"))
+        fh.write(h.tobytes())
+        fh.write(edges.tobytes())
 
 
 _PARAM_NAMES = {f[0] for f in SphParams._fields_}
@@ -803,6 +844,55 @@ class SPHFluidGPU:
             ptr = int(values)
         surf = self.extract_surface_volume(ptr, origin, spacing, dims, iso)
         return self._download_surface(surf)
+
+    # -- passive tracers (include/sph_abi.h "passive tracers") -----------------------------------
+    def set_tracers(self, points, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
+        """(m, 3) or (m, 4) points (x, y, z[, initial age]) replace the engine's tracer set: every substep from now on advects them
+        with the fluid's Shepard velocity and keeps the `history` newest snapshots, one every `stride`
+        substeps, on the device.  Synchronises."""
+        pts = np.asarray(points, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+            raise SphError(f"set_tracers: points must have shape (m, 3) or (m, 4), not {pts.shape}")
+        p4 = np.zeros((len(pts), 4), np.float32)
+        p4[:, :pts.shape[1]] = pts
+        _check(self._L.sph_tracers_set(self._h, p4.ctypes.data_as(C.c_void_p), len(p4), int(integrator), int(history), int(stride)))
+
+    def set_tracers_device(self, dev_points: int, m: int, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
+        """The same from m points of 4 floats at device address dev_points.  Asynchronous on the engine's stream."""
+        _check(self._L.sph_tracers_set_device(self._h, C.c_void_p(dev_points), int(m), int(integrator), int(history), int(stride)))
+
+    def clear_tracers(self):
+        _check(self._L.sph_tracers_set(self._h, None, 0, SPH_TRACER_EULER, 0, 1))
+
+    def num_tracers(self) -> int:
+        return int(self._L.sph_tracers_count(self._h))
+
+    def tracer_info(self):
+        """(substeps that advected the current set, stored snapshots, number of the oldest stored snapshot)."""
+        c, n, q = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        _check(self._L.sph_tracers_info(self._h, C.byref(c), C.byref(n), C.byref(q)))
+        return int(c.value), int(n.value), int(q.value)
+
+    def tracers(self) -> np.ndarray:
+        """The tracers in the caller's order: a structured array of TRACER_DTYPE (pos, age, vel, fraction).  Synchronises."""
+        out = np.zeros(self.num_tracers(), TRACER_DTYPE)
+        _check(self._L.sph_tracers_download(self._h, out.ctypes.data_as(C.c_void_p), len(out)))
+        return out
+
+    def tracers_device(self) -> int:
+        """Borrowed device address of the 32-byte records in the caller's order (0 without tracers); valid until the next
+        dispatch, set, reset or close.  No synchronisation."""
+        p = C.c_void_p()
+        _check(self._L.sph_tracers_device(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def tracer_history(self):
+        """(first, array (count, M, 4)): the stored snapshots (x, y, z, age), oldest first, and the number of the first one.  Synchronises."""
+        _, n, _ = self.tracer_info()
+        out = np.zeros((max(n, 1), self.num_tracers(), 4), np.float32)
+        cnt, first = C.c_uint32(), C.c_uint64()
+        _check(self._L.sph_tracers_history(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(cnt), C.byref(first)))
+        return int(first.value), out[:cnt.value]
 
     # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
     def statistics(self, histograms=None) -> Statistics:

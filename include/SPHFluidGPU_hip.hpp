@@ -220,6 +220,24 @@ public:
     }
     double Cfl(const SphStatistics& s) const { return double(s.maxSpeed) * double(param_timeStep) / double(param_h); }
     double SphVolume(const SphStatistics& s) const { return double(param_mass) * s.sumInvDensity; }
+    // Passive tracers (engine extension, sph_abi.h "passive tracers"): points (x, y, z, initial age) that every substep from now on
+    // advects with the fluid's Shepard velocity, behind the substep's own grid build; `history` snapshots, one every `stride`
+    // substeps, are kept on the device.  An empty vector drops the set.  TracerHistory returns the stored snapshots oldest first
+    // (snapshot k, tracer i at out4[k * NumTracers() + i]) and the number of the first one.  Return false on error (LastError()).
+    bool SetTracers(const std::vector<MATH::Vec4>& points, int integrator = SPH_TRACER_MIDPOINT, uint32_t history = 0, uint32_t stride = 1) {
+        return !Check(sph_tracers_set(engine, points.empty() ? nullptr : &points[0].x, points.size(), integrator, history, stride), "sph_tracers_set");
+    }
+    size_t NumTracers() const { return sph_tracers_count(engine); }
+    bool DownloadTracers(std::vector<SphTracer>& out) {
+        out.resize(sph_tracers_count(engine));
+        return !Check(sph_tracers_download(engine, out.empty() ? nullptr : out.data(), out.size()), "sph_tracers_download");
+    }
+    bool TracerHistory(std::vector<MATH::Vec4>& out4, uint32_t& snapshots, uint64_t& firstSnapshot) {
+        uint32_t n = 0;
+        if (Check(sph_tracers_info(engine, nullptr, &n, nullptr), "sph_tracers_info")) return false;
+        out4.resize(size_t(n) * sph_tracers_count(engine));
+        return !Check(sph_tracers_history(engine, out4.empty() ? nullptr : &out4[0].x, n, &snapshots, &firstSnapshot), "sph_tracers_history");
+    }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");

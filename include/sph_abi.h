@@ -34,6 +34,7 @@ extern "C" {
 /* (still 4, additions only: SphSample, SPH_FIELD_*, sph_sample_points / sph_sample_points_device / sph_sample_lattice -- field sampling) */
 /* (still 4, additions only: SphSurfaceVertex, SphSurface, sph_extract_surface / sph_extract_surface_volume / sph_surface_download -- iso-surface meshes) */
 /* (still 4, additions only: SphStatistics, SphStatExtremum, SphHistogramSpec, SPH_STAT_*, sph_statistics / sph_statistics_device -- state statistics) */
+/* (still 4, additions only: SphTracer, SPH_TRACER_*, sph_tracers_set / _set_device / _count / _info / _download / _device / _history -- passive tracers) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -378,6 +379,47 @@ enum { SPH_STAT_MAX_SPECS = 4, SPH_STAT_MAX_BINS = 1024 };
 int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* specs, int nSpecs, uint64_t* histOut);
 /* The same into a DEVICE struct and DEVICE histograms (`specs` stays a host array); asynchronous on the engine's stream. */
 int sph_statistics_device(SphEngine* e, SphStatistics* devOut, const SphHistogramSpec* specs, int nSpecs, uint64_t* devHistOut);
+
+/* ---- passive tracers advected inside the substep, with pathlines (no reference counterpart) ----------------
+ * A tracer is a point that the fluid carries and that does not act on the fluid.  The engine holds M >= 0 tracers in the caller's order.
+ * Let u(x) be the `vel` of the SphSample that sph_sample_points returns for a probe at x on the state a substep STARTS from, and phi(x)
+ * its `fraction` (same candidates, same order, same fma placement, zero where sum w_j = 0, all-zero for a non-finite x).  One substep with
+ * time step dt (overrideDt if > 0, else param_timeStep) moves every tracer, per axis, in fp32, with a multiply and then an add (no fma):
+ *   SPH_TRACER_EULER     v = u(x);                                          x' = x + dt * v
+ *   SPH_TRACER_MIDPOINT  v1 = u(x); xm = x + (0.5f * dt) * v1; v = u(xm);   x' = x + dt * v     (both on the same frozen entry state)
+ * and then stores vel = v, fraction = phi(x) (at the position BEFORE the move: was the tracer in the fluid), age' = age + dt (one fp32
+ * add).  A tracer with a non-finite coordinate keeps its position bits, gets vel = 0, fraction = 0 and still ages.  A tracer outside
+ * the fluid (sum w_j = 0) does not move; one outside the grid takes the clamped cell, as a probe does.  Records whose density is <= 0
+ * (spawned or uploaded records before their first substep) have 1/rho = 0, so u = 0 and phi = 0 there: tracers do not move during
+ * the FIRST substep on such a state.
+ * Hence the tracers after n substeps are, bit for bit, what the loop  s = sample(x); dispatch(dt); x = x + dt * s.vel  gives (two
+ * samples per substep for the midpoint rule), and the particle records are byte-identical with and without tracers.
+ * Tracers see the entry state of the substep, before the fountain / river recycle of that dispatch.  param_pause: no substep, no
+ * move, no ageing.  Impulses, sph_upload_particles and sph_set_params do not touch tracers; sph_reset drops the set, sph_destroy
+ * frees it.  The advection runs behind the substep's own grid build (no second build), under sph_dispatch_n and inside its captured
+ * graphs, timed as SPH_K_OTHER.  With no tracers set a dispatch launches exactly what it launched before.
+ * Pathline history: historyCap K >= 0 snapshots, one every historyStride S >= 1 substeps.  With c the substeps that have advected the
+ * current set (0 right after a set call), snapshot q holds (x, y, z, age) of all M tracers after substep c = q S; snapshot 0 is the
+ * seed; snapshot q lives in slot q mod K of a device ring of K M float4.  min(c / S + 1, K) snapshots are stored.
+ * SPH_ERR_STATE from the set calls, before anything is allocated, on z-slab engines and under SPH_OPT_GRID_BUILD 1; setting
+ * SPH_OPT_GRID_BUILD 1 while tracers exist makes the next dispatch fail with SPH_ERR_STATE and move nothing.  SPH_ERR_ARG: null
+ * pointers with m > 0, unknown integrator, historyStride == 0, historyCap * m above 2^31 - 1 float4. */
+typedef struct SphTracer { float pos[3]; float age; float vel[3]; float fraction; } SphTracer;   /* 32 bytes */
+enum { SPH_TRACER_EULER = 0, SPH_TRACER_MIDPOINT = 1 };
+/* m points of 4 floats (x, y, z, initial age) in HOST memory replace the engine's tracer set; m == 0 drops it.  Synchronises. */
+int sph_tracers_set(SphEngine* e, const float* points4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride);
+/* The same from a DEVICE array, asynchronous on the engine's stream. */
+int sph_tracers_set_device(SphEngine* e, const float* devPoints4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride);
+size_t sph_tracers_count(const SphEngine* e);
+/* c, the number of stored snapshots and the number q of the oldest stored one (any pointer may be null). */
+int sph_tracers_info(const SphEngine* e, uint64_t* substeps, uint32_t* snapshots, uint64_t* firstSnapshot);
+/* m records in the caller's order to HOST memory (cap >= m, else SPH_ERR_CAPACITY, nothing written).  Synchronises. */
+int sph_tracers_download(SphEngine* e, SphTracer* out, size_t cap);
+/* Borrowed DEVICE pointer to the m records in the caller's order, valid until the next dispatch, set, reset or destroy; no synchronisation. */
+int sph_tracers_device(SphEngine* e, const SphTracer** devPtr);
+/* The stored snapshots, oldest first, to HOST memory: snapshotCap * m * 4 floats (snapshotCap >= the stored count, else
+ * SPH_ERR_CAPACITY).  SPH_ERR_STATE without a history (K == 0 or no tracers).  Synchronises. */
+int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t* snapshotsOut, uint64_t* firstSnapshotOut);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
