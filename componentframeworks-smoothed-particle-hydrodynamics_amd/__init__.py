@@ -14,5 +14,7 @@ from .engine import (  # noqa: F401
     SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM, SPH_STAT_MAX_SPECS,
     SPH_STAT_MAX_BINS, SphHistogramSpec, SphStatExtremum, SphStatistics, Statistics,
     SPH_TRACER_EULER, SPH_TRACER_MIDPOINT, SphTracer, TRACER_DTYPE, write_pathlines_ply,
+    SPH_MAX_OBSTACLES, SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE, SphObstacle, OBSTACLE_DTYPE, obstacle, obstacle_array,
+    obstacles_apply_host, obstacles_advance_host,
 )
 from . import build, synthetic  # noqa: F401

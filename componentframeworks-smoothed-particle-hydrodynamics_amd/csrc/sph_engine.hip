@@ -25,11 +25,13 @@
 #include "sph_sample.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
+#include "sph_obstacle.h"
 #include "sph_stats.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
+static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
 
@@ -217,6 +219,17 @@ struct SphEngine {
     bool trOrdered = false;              // the processing order has been cell-sorted since sph_tracers_set
     bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
 
+    // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
+    // and kObsSlots pinned staging slots for stream-ordered uploads, each guarded by an event recorded behind its copy
+    static constexpr int kObsSlots = 4;
+    sph::ObsRec* d_obs = nullptr;
+    sph::ObsAcc* d_obsAcc = nullptr;
+    double* d_obsPart = nullptr;
+    sph::ObsRec* h_obsStage = nullptr;   // kObsSlots x kObsMax records
+    hipEvent_t evObs[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
+    int obsSlot = 0;
+    int obsK = 0;
+
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
     // timing
@@ -316,6 +329,16 @@ void tracers_free(SphEngine* e) {
     e->trCells = 0;
     e->trK = 0; e->trS = 1; e->trSteps = e->trSorted = 0;
     e->trOrdered = false;
+}
+
+void obstacles_free(SphEngine* e) {
+    if (e->d_obs && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(e->d_obs); dev_free(e->d_obsAcc); dev_free(e->d_obsPart);
+    if (e->h_obsStage) (void)hipHostFree(e->h_obsStage);
+    e->h_obsStage = nullptr;
+    for (auto& ev : e->evObs) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    e->obsK = 0;
+    e->obsSlot = 0;
 }
 
 int alloc_particle_buffers(SphEngine* e, size_t n) {
@@ -497,6 +520,20 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
     return SPH_OK;
 }
 
+// ---- obstacles (sph_obstacle.h) -------------------------------------------------------------------
+// One substep's obstacle step on the pass's output state: k_obstacles, then the one-block finish (sums, accumulators, pose advance).
+int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
+    const int rows = n > 0 ? std::min(kObsGrid, blocks_for((size_t)n, kObsSweep)) : 0;
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, e->obsK, e->params.param_mass, pos, vel, n,
+                                     e->d_obsPart);
+        hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
 int writeback(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "a slab engine has no local 80-byte array: use sph_slab_download");
     if (e->aosValid) return SPH_OK;
@@ -563,7 +600,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     const int nx = e->cur ^ 1;
     if (k.obbDeferred && (rc = ensure_shape_table(e))) return rc;
     // the array is current: keep it current from the SPH pass (not when OBB runs as its own pass afterwards)
-    const bool fuseAos = !e->slab && e->optAos == 0 && e->aosValid && !k.obbDeferred;
+    const bool fuseAos = !e->slab && e->optAos == 0 && e->aosValid && !k.obbDeferred && !e->obsK;   // (nor when obstacles act afterwards)
     StateOut out{e->d_pos[nx], e->d_vel[nx], e->d_rp[nx], e->d_foam[nx], e->d_acc, fuseAos ? e->d_aos : nullptr, e->idBase};
     if (e->optGridBuild == 1) {
         // ---- A/B variant: the reference's atomicExchange linked lists (no sorting) ----
@@ -645,6 +682,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         hipLaunchKernelGGL(k_obb_ext, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, e->shapeTab, out.pos, out.vel, live, n,
                            (e->slab && e->optGridBuild != 1) ? (const float4*)e->d_sOwn : (const float4*)nullptr);
     }
+    if (e->obsK && (rc = obstacles_step(e, out.pos, out.vel, n, dt))) return rc;   // (after the container, before river / fountain)
     const bool riverOn = e->river.riverMode && !e->terrainHeights.empty();   // :512
     if (riverOn) {                                                           // :511-516, DispatchTerrainConstraints / ChannelConstraint / StreamEmit
         if (e->slab) return fail(SPH_ERR_STATE, "riverMode on a z-slab engine: recycled particles jump across slabs (single-GPU engines only)");
@@ -845,6 +883,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_surfVol); dev_free(e->d_surfCode); dev_free(e->d_surfVOff); dev_free(e->d_surfTile); dev_free(e->d_surfTileOff);
     dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
     tracers_free(e);
+    obstacles_free(e);
     dev_free(e->d_statSums); dev_free(e->d_statPart); dev_free(e->d_statHist); dev_free(e->d_statCell); dev_free(e->d_statOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -876,6 +915,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     tracers_free(e);                                                  // (and the tracer set)
+    if (e->d_obsAcc) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (obstacles: the set and the poses stay, the sums restart)
     std::vector<SphParticle> v;
     float m;
     if (e->river.riverMode && !e->terrainHeights.empty())             // :104
@@ -964,6 +1004,10 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     add(tr, sizeof(tr));
     const uint64_t trv[4] = {(uint64_t)e->trM, (uint64_t)e->trIntegrator, e->trK, e->trS};
     add(trv, sizeof(trv));
+    // obstacles: the buffers and the count (the kernels read the bodies from memory, so a later set / set_motion needs no new graph)
+    const void* ob[3] = {e->d_obs, e->d_obsAcc, e->d_obsPart};
+    add(ob, sizeof(ob));
+    add(&e->obsK, sizeof(e->obsK));
     return m;
 }
 static uint64_t graph_hash(const std::vector<unsigned char>& m) {
@@ -2614,6 +2658,177 @@ int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t*
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (snapshotsOut) *snapshotsOut = count;
     if (firstSnapshotOut) *firstSnapshotOut = first;
+    return SPH_OK;
+}
+
+// ---- kinematic solid obstacles (sph_obstacle.h) --------------------------------------------------
+static bool obs_all_finite(const float* v, int n) {
+    for (int i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
+    return true;
+}
+static int obstacles_check(const SphObstacle* obs, int count) {
+    if (count < 0 || count > SPH_MAX_OBSTACLES) return fail(SPH_ERR_ARG, "obstacle count %d outside 0..%d", count, SPH_MAX_OBSTACLES);
+    if (count && !obs) return fail(SPH_ERR_ARG, "null argument");
+    for (int i = 0; i < count; ++i) {
+        const SphObstacle& o = obs[i];
+        if (o.shape != SPH_OBSTACLE_SPHERE && o.shape != SPH_OBSTACLE_BOX && o.shape != SPH_OBSTACLE_CAPSULE) return fail(SPH_ERR_ARG, "obstacle %d: unknown shape %d", i, o.shape);
+        if (!obs_all_finite(o.size, 3) || !obs_all_finite(o.center, 3) || !obs_all_finite(o.rotation, 4) || !obs_all_finite(o.vel, 3) ||
+            !obs_all_finite(o.omega, 3) || !std::isfinite(o.restitution) || !std::isfinite(o.friction))
+            return fail(SPH_ERR_ARG, "obstacle %d: a field is not finite", i);
+        const int used = o.shape == SPH_OBSTACLE_SPHERE ? 1 : (o.shape == SPH_OBSTACLE_CAPSULE ? 2 : 3);
+        for (int a = 0; a < used; ++a) if (!(o.size[a] > 0.0f)) return fail(SPH_ERR_ARG, "obstacle %d: size[%d] = %g must be > 0", i, a, (double)o.size[a]);
+        const float* q = o.rotation;
+        const float n2 = std::fma(q[3], q[3], std::fma(q[2], q[2], std::fma(q[1], q[1], q[0] * q[0])));   // (the norm obs_normalize divides by)
+        if (!(n2 > 0.0f) || !std::isfinite(n2)) return fail(SPH_ERR_ARG, "obstacle %d: the quaternion is zero or cannot be normalised in fp32", i);
+        if (!(o.restitution >= 0.0f && o.restitution <= 1.0f) || !(o.friction >= 0.0f && o.friction <= 1.0f))
+            return fail(SPH_ERR_ARG, "obstacle %d: restitution and friction must lie in [0, 1]", i);
+    }
+    return SPH_OK;
+}
+// SphObstacle -> device record: the rotation normalised (the engine's set) or used as given (the host functions), M and the AABB built from it.
+static void obstacle_to_rec(const SphObstacle& o, bool normalise, sph::ObsRec& r) {
+    std::memset(&r, 0, sizeof(r));
+    r.shape = o.shape;
+    for (int a = 0; a < 3; ++a) { r.size[a] = o.size[a]; r.c[a] = o.center[a]; r.v[a] = o.vel[a]; r.w[a] = o.omega[a]; }
+    for (int a = 0; a < 4; ++a) r.q[a] = o.rotation[a];
+    r.res = o.restitution; r.fr = o.friction;
+    if (normalise) sph::obs_normalize(r.q);
+    sph::obs_matrix(r);
+    sph::obs_extent(r);
+}
+static void rec_to_obstacle(const sph::ObsRec& r, SphObstacle& o) {
+    o.shape = r.shape;
+    for (int a = 0; a < 3; ++a) { o.size[a] = r.size[a]; o.center[a] = r.c[a]; o.vel[a] = r.v[a]; o.omega[a] = r.w[a]; }
+    for (int a = 0; a < 4; ++a) o.rotation[a] = r.q[a];
+    o.restitution = r.res; o.friction = r.fr;
+}
+// The next pinned staging slot, once the copy queued from it last time has run.
+static int obstacles_slot(SphEngine* e, sph::ObsRec** slot) {
+    const int i = e->obsSlot;
+    e->obsSlot = (i + 1) % SphEngine::kObsSlots;
+    HIP_TRY(hipEventSynchronize(e->evObs[i]));
+    *slot = e->h_obsStage + (size_t)i * kObsMax;
+    return SPH_OK;
+}
+
+void sph_obstacle_default(SphObstacle* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->shape = SPH_OBSTACLE_SPHERE;
+    out->size[0] = 1.0f;
+    out->rotation[0] = 1.0f;
+    out->restitution = 0.15f;
+    out->friction = 0.02f;
+}
+
+int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (count == 0) { obstacles_free(e); return SPH_OK; }
+    if (!e->d_obs) {
+        if ((rc = dev_alloc(&e->d_obs, (size_t)kObsMax)) || (rc = dev_alloc(&e->d_obsAcc, 1)) || (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow))) {
+            obstacles_free(e); return rc;
+        }
+        hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&e->h_obsStage), sizeof(sph::ObsRec) * kObsMax * SphEngine::kObsSlots, hipHostMallocDefault);
+        for (auto& ev : e->evObs) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (er != hipSuccess) { obstacles_free(e); return fail(SPH_ERR_HIP, "obstacle staging: %s", hipGetErrorString(er)); }
+        for (auto& ev : e->evObs) HIP_TRY(hipEventRecord(ev, e->stream));
+        e->obsK = 0;
+    }
+    sph::ObsRec* slot = nullptr;
+    if ((rc = obstacles_slot(e, &slot))) return rc;
+    for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], true, slot[i]);
+    const int slotNo = (e->obsSlot + SphEngine::kObsSlots - 1) % SphEngine::kObsSlots;
+    HIP_TRY(hipMemcpyAsync(e->d_obs, slot, sizeof(sph::ObsRec) * (size_t)count, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->evObs[slotNo], e->stream));
+    if (count != e->obsK) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (another count: the sums restart)
+    e->obsK = count;
+    return SPH_OK;
+}
+
+int sph_obstacles_set_motion(SphEngine* e, int index, const float vel[3], const float omega[3]) {
+    if (!e || !vel || !omega) return fail(SPH_ERR_ARG, "null argument");
+    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    if (!obs_all_finite(vel, 3) || !obs_all_finite(omega, 3)) return fail(SPH_ERR_ARG, "obstacle %d: velocity not finite", index);
+    int rc;
+    sph::ObsRec* slot = nullptr;
+    if ((rc = obstacles_slot(e, &slot))) return rc;
+    const int slotNo = (e->obsSlot + SphEngine::kObsSlots - 1) % SphEngine::kObsSlots;
+    for (int a = 0; a < 3; ++a) { slot[0].v[a] = vel[a]; slot[0].w[a] = omega[a]; }
+    static_assert(offsetof(sph::ObsRec, w) == offsetof(sph::ObsRec, v) + 3 * sizeof(float), "v and w are adjacent");
+    HIP_TRY(hipMemcpyAsync(&e->d_obs[index].v[0], &slot[0].v[0], 6 * sizeof(float), hipMemcpyHostToDevice, e->stream));   // (the pose stays the device's)
+    HIP_TRY(hipEventRecord(e->evObs[slotNo], e->stream));
+    return SPH_OK;
+}
+
+int sph_obstacles_get(SphEngine* e, SphObstacle* out, int cap, int* countOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (cap < e->obsK) return fail(SPH_ERR_CAPACITY, "%d obstacles (capacity %d)", e->obsK, cap);
+    if (e->obsK && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (e->obsK) {
+        sph::ObsRec host[kObsMax];
+        HIP_TRY(hipMemcpyAsync(host, e->d_obs, sizeof(sph::ObsRec) * (size_t)e->obsK, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (int i = 0; i < e->obsK; ++i) rec_to_obstacle(host[i], out[i]);
+    }
+    if (countOut) *countOut = e->obsK;
+    return SPH_OK;
+}
+
+int sph_obstacles_impulses(SphEngine* e, double* out6, int cap, double* timeOut, uint64_t* substepsOut, int reset) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (cap < e->obsK) return fail(SPH_ERR_CAPACITY, "%d obstacles (capacity %d)", e->obsK, cap);
+    sph::ObsAcc a;
+    std::memset(&a, 0, sizeof(a));
+    if (e->d_obsAcc) {
+        HIP_TRY(hipMemcpyAsync(&a, e->d_obsAcc, sizeof(a), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (reset) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));
+    }
+    if (out6 && e->obsK) std::memcpy(out6, a.J, sizeof(double) * kObsTerms * (size_t)e->obsK);
+    if (timeOut) *timeOut = a.time;
+    if (substepsOut) *substepsOut = a.substeps;
+    return SPH_OK;
+}
+
+int sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMass, SphParticle* particles, size_t n, double* impulses6) {
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (n && !particles) return fail(SPH_ERR_ARG, "null particles");
+    sph::ObsRec recs[kObsMax];
+    for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], false, recs[i]);
+    double acc[kObsRow] = {0.0};
+    for (size_t i = 0; i < n; ++i) {
+        SphParticle& p = particles[i];
+        if (p.isGhost != 0) continue;
+        float px = p.pos[0], py = p.pos[1], pz = p.pos[2], vx = p.vel[0], vy = p.vel[1], vz = p.vel[2];
+        if (!std::isfinite(px) || !std::isfinite(py) || !std::isfinite(pz)) continue;
+        bool changed = false;
+        for (int b = 0; b < count; ++b) {
+            double t[kObsTerms];
+            if (!sph::obs_hit(recs[b], particleMass, px, py, pz, vx, vy, vz, t)) continue;
+            changed = true;
+            for (int c = 0; c < kObsTerms; ++c) acc[b * kObsTerms + c] += t[c];
+        }
+        if (changed) { p.pos[0] = px; p.pos[1] = py; p.pos[2] = pz; p.vel[0] = vx; p.vel[1] = vy; p.vel[2] = vz; }
+    }
+    if (impulses6) std::memcpy(impulses6, acc, sizeof(double) * kObsTerms * (size_t)count);
+    return SPH_OK;
+}
+
+int sph_obstacles_advance_host(SphObstacle* obs, int count, float dt) {
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (!std::isfinite(dt)) return fail(SPH_ERR_ARG, "dt not finite");
+    for (int i = 0; i < count; ++i) {
+        sph::ObsRec r;
+        obstacle_to_rec(obs[i], false, r);
+        sph::obs_advance(r, dt);
+        rec_to_obstacle(r, obs[i]);
+    }
     return SPH_OK;
 }
 

@@ -111,6 +111,8 @@ ABI_SYMBOLS = (
     "sph_statistics", "sph_statistics_device",
     "sph_tracers_set", "sph_tracers_set_device", "sph_tracers_count", "sph_tracers_info", "sph_tracers_download", "sph_tracers_device",
     "sph_tracers_history",
+    "sph_obstacle_default", "sph_obstacles_set", "sph_obstacles_set_motion", "sph_obstacles_get", "sph_obstacles_impulses",
+    "sph_obstacles_apply_host", "sph_obstacles_advance_host",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -141,6 +143,53 @@ assert C.sizeof(SphTracer) == 32
 TRACER_DTYPE = np.dtype([("pos", "<f4", (3,)), ("age", "<f4"), ("vel", "<f4", (3,)), ("fraction", "<f4")])
 assert TRACER_DTYPE.itemsize == 32
 SPH_TRACER_EULER, SPH_TRACER_MIDPOINT = 0, 1
+
+
+class SphObstacle(C.Structure):
+    """struct SphObstacle of include/sph_abi.h: one kinematic solid body (see obstacle() and SPHFluidGPU.set_obstacles)."""
+    _fields_ = [("shape", C.c_int32), ("size", C.c_float * 3), ("center", C.c_float * 3), ("rotation", C.c_float * 4),
+                ("vel", C.c_float * 3), ("omega", C.c_float * 3), ("restitution", C.c_float), ("friction", C.c_float)]
+
+
+assert C.sizeof(SphObstacle) == 76
+OBSTACLE_DTYPE = np.dtype([("shape", "<i4"), ("size", "<f4", (3,)), ("center", "<f4", (3,)), ("rotation", "<f4", (4,)),
+                           ("vel", "<f4", (3,)), ("omega", "<f4", (3,)), ("restitution", "<f4"), ("friction", "<f4")])
+assert OBSTACLE_DTYPE.itemsize == 76
+SPH_MAX_OBSTACLES = 16
+SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE = 0, 1, 2
+
+
+def obstacle(shape, center, size, rotation=(1.0, 0.0, 0.0, 0.0), vel=(0.0, 0.0, 0.0), omega=(0.0, 0.0, 0.0),
+             restitution: float = 0.15, friction: float = 0.02) -> SphObstacle:
+    """One body: shape SPH_OBSTACLE_*; size a number or up to 3 numbers (sphere: radius | box: half extents |
+    capsule: radius, half length of the core segment along local y; the rest 0); rotation a quaternion (w, x, y, z), local -> world."""
+    sz = [float(size)] if np.ndim(size) == 0 else [float(x) for x in size]
+    if len(sz) > 3:
+        raise SphError(f"obstacle: size has {len(sz)} components")
+    o = SphObstacle()
+    o.shape = int(shape)
+    for i, x in enumerate(sz + [0.0] * (3 - len(sz))):
+        o.size[i] = x
+    for field, val, n in (("center", center, 3), ("rotation", rotation, 4), ("vel", vel, 3), ("omega", omega, 3)):
+        arr = getattr(o, field)
+        vals = [float(x) for x in val]
+        if len(vals) != n:
+            raise SphError(f"obstacle: {field} needs {n} components, not {len(vals)}")
+        for i, x in enumerate(vals):
+            arr[i] = x
+    o.restitution = float(restitution)
+    o.friction = float(friction)
+    return o
+
+
+def obstacle_array(obstacles) -> np.ndarray:
+    """A list of SphObstacle, or a structured array, as a contiguous OBSTACLE_DTYPE array (the layout of SphObstacle)."""
+    if isinstance(obstacles, np.ndarray):
+        return np.ascontiguousarray(obstacles, OBSTACLE_DTYPE)
+    obstacles = list(obstacles)
+    if not obstacles:
+        return np.zeros(0, OBSTACLE_DTYPE)
+    return np.frombuffer(b"".join(bytes(o) for o in obstacles), OBSTACLE_DTYPE).copy()
 
 
 class SphSurface(C.Structure):
@@ -390,9 +439,18 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_tracers_download.argtypes = [vp, vp, C.c_size_t]
     L.sph_tracers_device.argtypes = [vp, C.POINTER(C.c_void_p)]
     L.sph_tracers_history.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.sph_obstacle_default.argtypes = [vp]
+    L.sph_obstacle_default.restype = None
+    L.sph_obstacles_set.argtypes = [vp, vp, C.c_int]
+    L.sph_obstacles_set_motion.argtypes = [vp, C.c_int, f3, f3]
+    L.sph_obstacles_get.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.sph_obstacles_impulses.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
+    L.sph_obstacles_apply_host.argtypes = [vp, C.c_int, C.c_float, vp, C.c_size_t, vp]
+    L.sph_obstacles_advance_host.argtypes = [vp, C.c_int, C.c_float]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
-        if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count"):
+        if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count",
+                        "sph_obstacle_default"):
             fn.restype = C.c_int
     _lib = L
     return L
@@ -894,6 +952,35 @@ class SPHFluidGPU:
         _check(self._L.sph_tracers_history(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(cnt), C.byref(first)))
         return int(first.value), out[:cnt.value]
 
+    # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
+    def set_obstacles(self, obstacles):
+        """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
+        now on keeps the fluid out of them, advances their poses and sums the fluid's impulses.  No synchronisation."""
+        arr = obstacle_array(obstacles)
+        _check(self._L.sph_obstacles_set(self._h, arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr)))
+
+    def clear_obstacles(self):
+        _check(self._L.sph_obstacles_set(self._h, None, 0))
+
+    def set_obstacle_motion(self, index: int, vel, omega):
+        """New linear / angular velocity of body `index`; the pose stays the one the device holds.  No synchronisation."""
+        _check(self._L.sph_obstacles_set_motion(self._h, int(index), _f3(vel), _f3(omega)))
+
+    def obstacles(self) -> np.ndarray:
+        """The bodies with their current (advanced) poses, an OBSTACLE_DTYPE array.  Synchronises."""
+        out = np.zeros(SPH_MAX_OBSTACLES, OBSTACLE_DTYPE)
+        k = C.c_int()
+        _check(self._L.sph_obstacles_get(self._h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(k)))
+        return out[:k.value].copy()
+
+    def obstacle_impulses(self, reset: bool = False):
+        """(J, time, substeps): J (K, 6) float64 = (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave each body since the last zeroing, the
+        simulated time and the substeps over which they were summed; reset zeroes them after the read.  Synchronises."""
+        out = np.zeros((SPH_MAX_OBSTACLES, 6), np.float64)
+        t, n = C.c_double(), C.c_uint64()
+        _check(self._L.sph_obstacles_impulses(self._h, out.ctypes.data_as(C.c_void_p), SPH_MAX_OBSTACLES, C.byref(t), C.byref(n), 1 if reset else 0))
+        return out[:len(self.obstacles())].copy(), float(t.value), int(n.value)
+
     # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
     def statistics(self, histograms=None) -> Statistics:
         """Counts, extrema, fp64 sums, cell occupancy and up to 4 histograms ((field, bins, lo, hi) with field one of SPH_STAT_*) of the
@@ -940,3 +1027,21 @@ class SPHFluidGPU:
             self.close()
         except Exception:
             pass
+
+
+def obstacles_apply_host(obstacles, particle_mass: float, particles: np.ndarray):
+    """sph_obstacles_apply_host on a copy of the records: (records, impulses (K, 6)).  No device is needed."""
+    arr = obstacle_array(obstacles)
+    rec = np.ascontiguousarray(particles, PARTICLE_DTYPE).copy()
+    imp = np.zeros((max(len(arr), 1), 6), np.float64)
+    L = load_library()
+    _check(L.sph_obstacles_apply_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(particle_mass),
+                                      rec.ctypes.data_as(C.c_void_p), len(rec), imp.ctypes.data_as(C.c_void_p)))
+    return rec, imp[:len(arr)]
+
+
+def obstacles_advance_host(obstacles, dt: float) -> np.ndarray:
+    """sph_obstacles_advance_host on a copy: the bodies one substep of dt later.  No device is needed."""
+    arr = obstacle_array(obstacles).copy()
+    _check(load_library().sph_obstacles_advance_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(dt)))
+    return arr

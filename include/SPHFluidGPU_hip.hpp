@@ -238,6 +238,33 @@ public:
         out4.resize(size_t(n) * sph_tracers_count(engine));
         return !Check(sph_tracers_history(engine, out4.empty() ? nullptr : &out4[0].x, n, &snapshots, &firstSnapshot), "sph_tracers_history");
     }
+    // Kinematic solid obstacles (engine extension, sph_abi.h "obstacles"): up to SPH_MAX_OBSTACLES bodies whose
+    // motion the caller prescribes; every substep keeps the fluid out of them, advances their poses on the device and sums, per body,
+    // the impulse (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave it.  An empty vector drops the set.  SetObstacleMotion keeps the device's pose
+    // and does not synchronise; GetObstacles and ObstacleImpulses do.  Return false on error (LastError()).
+    bool SetObstacles(const std::vector<SphObstacle>& obs) {
+        return !Check(sph_obstacles_set(engine, obs.empty() ? nullptr : obs.data(), int(obs.size())), "sph_obstacles_set");
+    }
+    bool SetObstacleMotion(int index, const MATH::Vec3& vel, const MATH::Vec3& omega) {
+        const float v[3] = {vel.x, vel.y, vel.z}, w[3] = {omega.x, omega.y, omega.z};
+        return !Check(sph_obstacles_set_motion(engine, index, v, w), "sph_obstacles_set_motion");
+    }
+    bool GetObstacles(std::vector<SphObstacle>& out) {
+        out.resize(SPH_MAX_OBSTACLES);
+        int k = 0;
+        if (Check(sph_obstacles_get(engine, out.data(), int(out.size()), &k), "sph_obstacles_get")) return false;
+        out.resize(size_t(k));
+        return true;
+    }
+    // impulses6: 6 doubles per body; time: simulated seconds and substeps they were summed over; reset zeroes them after the read.
+    bool ObstacleImpulses(std::vector<double>& impulses6, double& time, uint64_t& substeps, bool reset = false) {
+        impulses6.assign(6 * SPH_MAX_OBSTACLES, 0.0);
+        if (Check(sph_obstacles_impulses(engine, impulses6.data(), SPH_MAX_OBSTACLES, &time, &substeps, reset ? 1 : 0), "sph_obstacles_impulses")) return false;
+        std::vector<SphObstacle> cur;
+        if (!GetObstacles(cur)) return false;
+        impulses6.resize(6 * cur.size());
+        return true;
+    }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");

@@ -35,6 +35,8 @@ extern "C" {
 /* (still 4, additions only: SphSurfaceVertex, SphSurface, sph_extract_surface / sph_extract_surface_volume / sph_surface_download -- iso-surface meshes) */
 /* (still 4, additions only: SphStatistics, SphStatExtremum, SphHistogramSpec, SPH_STAT_*, sph_statistics / sph_statistics_device -- state statistics) */
 /* (still 4, additions only: SphTracer, SPH_TRACER_*, sph_tracers_set / _set_device / _count / _info / _download / _device / _history -- passive tracers) */
+/* (still 4, additions only: SphObstacle, SPH_OBSTACLE_*, SPH_MAX_OBSTACLES, sph_obstacle_default, sph_obstacles_set / _set_motion / _get / _impulses /
+    _apply_host / _advance_host -- kinematic solid obstacles) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -420,6 +422,48 @@ int sph_tracers_device(SphEngine* e, const SphTracer** devPtr);
 /* The stored snapshots, oldest first, to HOST memory: snapshotCap * m * 4 floats (snapshotCap >= the stored count, else
  * SPH_ERR_CAPACITY).  SPH_ERR_STATE without a history (K == 0 or no tracers).  Synchronises. */
 int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t* snapshotsOut, uint64_t* firstSnapshotOut);
+
+/* ---- kinematic solid obstacles with fluid force and torque feedback (no reference counterpart) ----------
+ * Up to SPH_MAX_OBSTACLES rigid bodies whose motion the caller prescribes.  Every substep, after the SPH pass and the container and
+ * before the river / fountain step, each non-ghost particle with finite coordinates meets bodies 0..K-1 in order: a particle strictly
+ * inside a body is projected onto its surface and, if it moves into the surface (u_n < 0 relative to the surface velocity
+ * V + omega x (p' - c)), gets the body's wall response.  The engine sums, per body, the linear impulse J = m (v - v') and the angular
+ * impulse (p' - c) x J in fp64 (the fluid's push on the body, about its centre), and then advances every pose by one substep on the
+ * device: c += dt V, q = normalize(q + (dt / 2) (0, omega) q) when omega != 0.  Bodies do not react to the fluid.  The sums are
+ * independent of launch shape, AoS mode, pass kernel and graph replay.  With no obstacles a dispatch launches exactly what it launched
+ * before.  SPH_ERR_ARG (the previous set stays): unknown shape, a used size component not finite or <= 0, a zero or non-finite
+ * quaternion (or one whose fp32 squared norm is not a finite positive number), any non-finite field, restitution or friction outside [0, 1], count above SPH_MAX_OBSTACLES, index out of range.
+ * SPH_ERR_STATE: z-slab engines.  param_pause: nothing moves, nothing accumulates. */
+#define SPH_MAX_OBSTACLES 16
+enum { SPH_OBSTACLE_SPHERE = 0, SPH_OBSTACLE_BOX = 1, SPH_OBSTACLE_CAPSULE = 2 };
+typedef struct SphObstacle {       /* 76 bytes */
+    int32_t  shape;
+    float    size[3];      /* sphere: x = radius | box: half extents | capsule: x = radius, y = half length of the core segment along local y */
+    float    center[3];    /* world */
+    float    rotation[4];  /* unit quaternion (w, x, y, z), local -> world; normalised by the engine on set */
+    float    vel[3];       /* world units / s */
+    float    omega[3];     /* rad / s, world frame, about center */
+    float    restitution;  /* default 0.15, param_wallRestitution's default */
+    float    friction;     /* default 0.02, param_wallFriction's default */
+} SphObstacle;
+/* A sphere of radius 1 at the origin, identity rotation, at rest, default coefficients. */
+void sph_obstacle_default(SphObstacle* out);
+/* Replaces the set (count 0 clears it and frees its buffers).  Stream-ordered, no synchronisation.  The accumulators survive a set with
+ * the same count and are zeroed by a set with another count. */
+int  sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count);
+/* New linear / angular velocity of body `index`; keeps the pose the device holds.  Stream-ordered, no synchronisation. */
+int  sph_obstacles_set_motion(SphEngine* e, int index, const float vel[3], const float omega[3]);
+/* The current (advanced) bodies to HOST memory (cap >= count, else SPH_ERR_CAPACITY); countOut may be null.  Synchronises. */
+int  sph_obstacles_get(SphEngine* e, SphObstacle* out, int cap, int* countOut);
+/* (Jx, Jy, Jz, Lx, Ly, Lz) per body (cap >= count, else SPH_ERR_CAPACITY), the simulated time (fp64 sum of dt) and the substeps summed
+ * since the last zeroing; reset != 0 zeroes them after the read.  sph_reset zeroes them too (it keeps the set and the poses).  Any
+ * output pointer may be null.  Synchronises. */
+int  sph_obstacles_impulses(SphEngine* e, double* out6, int cap, double* timeOut, uint64_t* substepsOut, int reset);
+/* Host-only, no device: the same __host__ __device__ functions the kernel runs.  The rotation is used as given (pass a pose
+ * sph_obstacles_get returned, or one normalised as section 3e does).  apply: one obstacle step on n records in index order, impulses6
+ * (count x 6, may be null) receives the sums in index order.  advance: one pose advance of every body by dt, in place. */
+int  sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMass, SphParticle* particles, size_t n, double* impulses6);
+int  sph_obstacles_advance_host(SphObstacle* obs, int count, float dt);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
