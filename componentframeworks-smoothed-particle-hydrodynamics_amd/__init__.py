@@ -16,5 +16,6 @@ from .engine import (  # noqa: F401
     SPH_TRACER_EULER, SPH_TRACER_MIDPOINT, SphTracer, TRACER_DTYPE, write_pathlines_ply,
     SPH_MAX_OBSTACLES, SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE, SphObstacle, OBSTACLE_DTYPE, obstacle, obstacle_array,
     obstacles_apply_host, obstacles_advance_host,
+    SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, SphVolumeHost, volume_sample_host, obstacles_apply_host_volumes, mesh_distance_host,
 )
 from . import build, synthetic  # noqa: F401

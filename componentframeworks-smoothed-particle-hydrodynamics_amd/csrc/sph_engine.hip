@@ -26,12 +26,14 @@
 #include "sph_surface.h"
 #include "sph_tracer.h"
 #include "sph_obstacle.h"
+#include "sph_volume.h"
 #include "sph_stats.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
+static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
 
@@ -230,6 +232,24 @@ struct SphEngine {
     int obsSlot = 0;
     int obsK = 0;
 
+    // sph_volume_* (sph_volume.h): the signed distance lattices, the device table (slots and per-body bindings) with its host mirror, pinned
+    // staging slots for stream-ordered uploads of the table, and the scratch of sph_mesh_distance (mesh copy and per-split partial results)
+    struct VolSlot { float* d = nullptr; int dims[3] = {0, 0, 0}; float spacing[3] = {0.0f, 0.0f, 0.0f}; };
+    VolSlot vols[sph::kVolMax];
+    sph::VolTable* d_volTab = nullptr;
+    sph::VolTable volTab{};              // host mirror of *d_volTab
+    sph::VolTable* h_volStage = nullptr; // kObsSlots tables
+    hipEvent_t evVol[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
+    int volSlot = 0;
+    int volBound = 0;                    // bodies bound to a volume: k_obstacles_vol is launched instead of k_obstacles while > 0
+    int obsShape[sph::kObsMax] = {0};    // shapes of the current set (a volume binds to a box only)
+    int optMeshSplit = 0;                // SPH_OPT_MESH_SPLIT
+    float* d_meshVerts = nullptr;
+    uint32_t* d_meshTris = nullptr;
+    float* d_meshD2 = nullptr;
+    double* d_meshW = nullptr;
+    size_t meshVertCap = 0, meshTriCap = 0, meshPartCap = 0;
+
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
     // timing
@@ -339,6 +359,25 @@ void obstacles_free(SphEngine* e) {
     for (auto& ev : e->evObs) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
     e->obsK = 0;
     e->obsSlot = 0;
+}
+
+// Every binding dropped (host mirror only; volumes_upload_table sends it).
+void volumes_unbind_all(SphEngine* e) {
+    for (int i = 0; i < sph::kVolBodies; ++i) e->volTab.bind[i] = -1;
+    e->volBound = 0;
+}
+void volumes_free(SphEngine* e) {
+    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    for (auto& v : e->vols) { dev_free(v.d); v = SphEngine::VolSlot{}; }
+    dev_free(e->d_volTab);
+    if (e->h_volStage) (void)hipHostFree(e->h_volStage);
+    e->h_volStage = nullptr;
+    for (auto& ev : e->evVol) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    std::memset(&e->volTab, 0, sizeof(e->volTab));
+    volumes_unbind_all(e);
+    e->volSlot = 0;
+    dev_free(e->d_meshVerts); dev_free(e->d_meshTris); dev_free(e->d_meshD2); dev_free(e->d_meshW);
+    e->meshVertCap = e->meshTriCap = e->meshPartCap = 0;
 }
 
 int alloc_particle_buffers(SphEngine* e, size_t n) {
@@ -526,7 +565,10 @@ int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
     const int rows = n > 0 ? std::min(kObsGrid, blocks_for((size_t)n, kObsSweep)) : 0;
     {
         Timed t(e, SPH_K_OTHER);
-        if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, e->obsK, e->params.param_mass, pos, vel, n,
+        if (rows && e->volBound > 0)
+            hipLaunchKernelGGL(k_obstacles_vol, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, (const VolTable*)e->d_volTab, e->obsK,
+                               e->params.param_mass, pos, vel, n, e->d_obsPart);
+        else if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, e->obsK, e->params.param_mass, pos, vel, n,
                                      e->d_obsPart);
         hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
     }
@@ -829,6 +871,7 @@ static int create_common(SphEngine** out, const SphParams* params, void* stream,
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail(SPH_ERR_HIP, "no HIP device: this engine has no CPU fallback");
     SphEngine* e = new SphEngine();
+    volumes_unbind_all(e);
     sph_fountain_default(&e->fountain);
     sph_river_default(&e->river);
     e->params = *params;
@@ -884,6 +927,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
     tracers_free(e);
     obstacles_free(e);
+    volumes_free(e);
     dev_free(e->d_statSums); dev_free(e->d_statPart); dev_free(e->d_statHist); dev_free(e->d_statCell); dev_free(e->d_statOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -949,6 +993,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_AOS_MODE: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optAos = value; break;
     case SPH_OPT_TIMING: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optTiming = value; break;
     case SPH_OPT_GRAPH: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optGraph = value; break;
+    case SPH_OPT_MESH_SPLIT: if (value < 0 || value > 64) return fail(SPH_ERR_ARG, "bad value"); e->optMeshSplit = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -969,6 +1014,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_AOS_MODE: *value = e->optAos; break;
     case SPH_OPT_TIMING: *value = e->optTiming; break;
     case SPH_OPT_GRAPH: *value = e->optGraph; break;
+    case SPH_OPT_MESH_SPLIT: *value = e->optMeshSplit; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -1008,6 +1054,11 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     const void* ob[3] = {e->d_obs, e->d_obsAcc, e->d_obsPart};
     add(ob, sizeof(ob));
     add(&e->obsK, sizeof(e->obsK));
+    // volumes: the table's address and whether any body is bound (which of the two obstacle kernels runs); the bindings and the lattices are read from memory
+    const void* vt = e->d_volTab;
+    const int anyBound = e->volBound > 0 ? 1 : 0;
+    add(&vt, sizeof(vt));
+    add(&anyBound, sizeof(anyBound));
     return m;
 }
 static uint64_t graph_hash(const std::vector<unsigned char>& m) {
@@ -2711,6 +2762,18 @@ static int obstacles_slot(SphEngine* e, sph::ObsRec** slot) {
     return SPH_OK;
 }
 
+// The host mirror of the table to the device, stream-ordered, through the next pinned staging slot.
+static int volumes_upload_table(SphEngine* e) {
+    if (!e->d_volTab) return SPH_OK;
+    const int i = e->volSlot;
+    e->volSlot = (i + 1) % SphEngine::kObsSlots;
+    HIP_TRY(hipEventSynchronize(e->evVol[i]));
+    e->h_volStage[i] = e->volTab;
+    HIP_TRY(hipMemcpyAsync(e->d_volTab, &e->h_volStage[i], sizeof(sph::VolTable), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->evVol[i], e->stream));
+    return SPH_OK;
+}
+
 void sph_obstacle_default(SphObstacle* out) {
     if (!out) return;
     std::memset(out, 0, sizeof(*out));
@@ -2726,6 +2789,10 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
     if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
     int rc;
     if ((rc = obstacles_check(obs, count))) return rc;
+    if (e->volBound > 0) {                                           // (a set replaces the set: every binding goes with it)
+        volumes_unbind_all(e);
+        if ((rc = volumes_upload_table(e))) return rc;
+    }
     if (count == 0) { obstacles_free(e); return SPH_OK; }
     if (!e->d_obs) {
         if ((rc = dev_alloc(&e->d_obs, (size_t)kObsMax)) || (rc = dev_alloc(&e->d_obsAcc, 1)) || (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow))) {
@@ -2745,6 +2812,7 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
     HIP_TRY(hipEventRecord(e->evObs[slotNo], e->stream));
     if (count != e->obsK) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (another count: the sums restart)
     e->obsK = count;
+    for (int i = 0; i < count; ++i) e->obsShape[i] = obs[i].shape;
     return SPH_OK;
 }
 
@@ -2829,6 +2897,270 @@ int sph_obstacles_advance_host(SphObstacle* obs, int count, float dt) {
         sph::obs_advance(r, dt);
         rec_to_obstacle(r, obs[i]);
     }
+    return SPH_OK;
+}
+
+// ---- volumes: signed distance lattices as bodies, mesh -> signed distance (sph_volume.h) ---------
+static int volume_check_lattice(const int dims[3], const float spacing[3], long long* totalOut, int least = 2) {
+    if (!dims || !spacing) return fail(SPH_ERR_ARG, "null argument");
+    long long total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < least) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= %d)", a, dims[a], least);
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
+        total *= dims[a];
+        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
+    }
+    if (totalOut) *totalOut = total;
+    return SPH_OK;
+}
+
+// A free slot and, on the first call, the device table with its staging.
+static int volume_free_slot(SphEngine* e, int* idOut) {
+    int rc, id = -1;
+    for (int i = 0; i < kVolMax; ++i) if (!e->vols[i].d) { id = i; break; }
+    if (id < 0) return fail(SPH_ERR_CAPACITY, "all %d volume slots are in use", kVolMax);
+    if (!e->d_volTab) {
+        if ((rc = dev_alloc(&e->d_volTab, 1))) return rc;
+        hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&e->h_volStage), sizeof(sph::VolTable) * SphEngine::kObsSlots, hipHostMallocDefault);
+        for (auto& ev : e->evVol) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (er != hipSuccess) { volumes_free(e); return fail(SPH_ERR_HIP, "volume staging: %s", hipGetErrorString(er)); }
+        for (auto& ev : e->evVol) HIP_TRY(hipEventRecord(ev, e->stream));
+    }
+    *idOut = id;
+    return SPH_OK;
+}
+// The engine takes the device array d as volume `id`.
+static int volume_adopt(SphEngine* e, int id, float* d, const int dims[3], const float spacing[3]) {
+    SphEngine::VolSlot& v = e->vols[id];
+    v.d = d;
+    for (int a = 0; a < 3; ++a) { v.dims[a] = dims[a]; v.spacing[a] = spacing[a]; }
+    sph::vol_make(d, dims, spacing, e->volTab.vol[id]);
+    return volumes_upload_table(e);
+}
+
+int sph_volume_create(SphEngine* e, const float* values, const int dims[3], const float spacing[3], int onDevice, int* idOut) {
+    if (!e || !values || !idOut) return fail(SPH_ERR_ARG, "null argument");
+    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
+    int rc, id = -1;
+    long long total = 0;
+    if ((rc = volume_check_lattice(dims, spacing, &total)) || (rc = volume_free_slot(e, &id))) return rc;
+    float* d = nullptr;
+    if ((rc = dev_alloc(&d, (size_t)total))) return rc;
+    hipError_t er = hipMemcpyAsync(d, values, (size_t)total * sizeof(float), onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream);
+    if (er == hipSuccess && !onDevice) er = hipStreamSynchronize(e->stream);      // (the caller's host array is free on return)
+    if (er != hipSuccess) { dev_free(d); return fail(SPH_ERR_HIP, "volume upload: %s", hipGetErrorString(er)); }
+    if ((rc = volume_adopt(e, id, d, dims, spacing))) return rc;
+    *idOut = id;
+    return SPH_OK;
+}
+
+static int volume_slot_check(const SphEngine* e, int id) {
+    if (id < 0 || id >= kVolMax || !e->vols[id].d) return fail(SPH_ERR_ARG, "volume %d does not exist", id);
+    return SPH_OK;
+}
+
+int sph_volume_destroy(SphEngine* e, int id) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = volume_slot_check(e, id))) return rc;
+    for (int i = 0; i < e->obsK; ++i)
+        if (e->volTab.bind[i] == id) return fail(SPH_ERR_STATE, "volume %d is bound to obstacle %d", id, i);
+    HIP_TRY(hipStreamSynchronize(e->stream));                        // (queued substeps or builds may still read it)
+    dev_free(e->vols[id].d);
+    e->vols[id] = SphEngine::VolSlot{};
+    std::memset(&e->volTab.vol[id], 0, sizeof(sph::VolRec));
+    return volumes_upload_table(e);
+}
+
+int sph_volume_info(SphEngine* e, int id, int dimsOut[3], float spacingOut[3], float halfOut[3]) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = volume_slot_check(e, id))) return rc;
+    for (int a = 0; a < 3; ++a) {
+        if (dimsOut) dimsOut[a] = e->vols[id].dims[a];
+        if (spacingOut) spacingOut[a] = e->vols[id].spacing[a];
+        if (halfOut) halfOut[a] = e->volTab.vol[id].half[a];
+    }
+    return SPH_OK;
+}
+
+int sph_obstacles_bind_volume(SphEngine* e, int index, int id) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    int rc;
+    if (id >= 0) {
+        if ((rc = volume_slot_check(e, id))) return rc;
+        if (e->obsShape[index] != SPH_OBSTACLE_BOX) return fail(SPH_ERR_ARG, "obstacle %d is not a box: a volume binds to SPH_OBSTACLE_BOX only", index);
+    } else {
+        id = -1;
+    }
+    if (e->volTab.bind[index] == id) return SPH_OK;
+    e->volBound += (id >= 0 ? 1 : 0) - (e->volTab.bind[index] >= 0 ? 1 : 0);
+    e->volTab.bind[index] = id;
+    return volumes_upload_table(e);
+}
+
+int sph_obstacles_volume(SphEngine* e, int index, int* idOut) {
+    if (!e || !idOut) return fail(SPH_ERR_ARG, "null argument");
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    *idOut = e->volTab.bind[index];
+    return SPH_OK;
+}
+
+static int volume_host_check(const SphVolumeHost& v) {
+    if (!v.values) return fail(SPH_ERR_ARG, "null lattice values");
+    return volume_check_lattice(v.dims, v.spacing, nullptr);
+}
+
+int sph_volume_sample_host(const float* values, const int dims[3], const float spacing[3], const float local[3], float* phiOut, float gradOut[3],
+                           int* insideOut) {
+    if (!values || !local || !phiOut || !gradOut || !insideOut) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = volume_check_lattice(dims, spacing, nullptr))) return rc;
+    sph::VolRec v;
+    sph::vol_make(values, dims, spacing, v);
+    float phi = std::nanf(""), g[3] = {0.0f, 0.0f, 0.0f};
+    const bool in = sph::vol_sample(v, local[0], local[1], local[2], false, phi, g);
+    if (!in) { const uint32_t q = 0x7FC00000u; std::memcpy(&phi, &q, 4); g[0] = g[1] = g[2] = 0.0f; }
+    *phiOut = phi;
+    for (int a = 0; a < 3; ++a) gradOut[a] = g[a];
+    *insideOut = in && phi < 0.0f ? 1 : 0;
+    return SPH_OK;
+}
+
+int sph_obstacles_apply_host_volumes(const SphObstacle* obs, int count, const SphVolumeHost* volumes, int volumeCount, const int* bindings,
+                                     float particleMass, SphParticle* particles, size_t n, double* impulses6) {
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (volumeCount < 0 || volumeCount > SPH_MAX_VOLUMES) return fail(SPH_ERR_ARG, "volume count %d outside 0..%d", volumeCount, SPH_MAX_VOLUMES);
+    if ((volumeCount && !volumes) || (count && !bindings)) return fail(SPH_ERR_ARG, "null argument");
+    if (n && !particles) return fail(SPH_ERR_ARG, "null particles");
+    sph::VolRec vols[kVolMax];
+    for (int i = 0; i < volumeCount; ++i) {
+        if ((rc = volume_host_check(volumes[i]))) return rc;
+        sph::vol_make(volumes[i].values, volumes[i].dims, volumes[i].spacing, vols[i]);
+    }
+    for (int i = 0; i < count; ++i) {
+        if (bindings[i] < 0) continue;
+        if (bindings[i] >= volumeCount) return fail(SPH_ERR_ARG, "obstacle %d: volume %d outside 0..%d", i, bindings[i], volumeCount - 1);
+        if (obs[i].shape != SPH_OBSTACLE_BOX) return fail(SPH_ERR_ARG, "obstacle %d is not a box: a volume binds to SPH_OBSTACLE_BOX only", i);
+    }
+    sph::ObsRec recs[kObsMax];
+    for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], false, recs[i]);
+    double acc[kObsRow] = {0.0};
+    for (size_t i = 0; i < n; ++i) {
+        SphParticle& p = particles[i];
+        if (p.isGhost != 0) continue;
+        float px = p.pos[0], py = p.pos[1], pz = p.pos[2], vx = p.vel[0], vy = p.vel[1], vz = p.vel[2];
+        if (!std::isfinite(px) || !std::isfinite(py) || !std::isfinite(pz)) continue;
+        bool changed = false;
+        for (int b = 0; b < count; ++b) {
+            double t[kObsTerms];
+            if (!sph::obs_hit_t<true>(recs[b], bindings[b] >= 0 ? &vols[bindings[b]] : nullptr, particleMass, px, py, pz, vx, vy, vz, t)) continue;
+            changed = true;
+            for (int c = 0; c < kObsTerms; ++c) acc[b * kObsTerms + c] += t[c];
+        }
+        if (changed) { p.pos[0] = px; p.pos[1] = py; p.pos[2] = pz; p.vel[0] = vx; p.vel[1] = vy; p.vel[2] = vz; }
+    }
+    if (impulses6) std::memcpy(impulses6, acc, sizeof(double) * kObsTerms * (size_t)count);
+    return SPH_OK;
+}
+
+static int mesh_check(const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3], const float spacing[3],
+                      const int dims[3], long long* totalOut) {
+    if (!vertices3 || !triangles3 || !origin) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = volume_check_lattice(dims, spacing, totalOut, 1))) return rc;                       // (a lattice of points as in sph_sample_lattice: dims >= 1)
+    if (nt == 0 || nt > 2147483647ull / 3 || nv == 0 || nv > 0xFFFFFFFFull) return fail(SPH_ERR_ARG, "a mesh of %zu vertices and %zu triangles", nv, nt);
+    if (!obs_all_finite(origin, 3)) return fail(SPH_ERR_ARG, "lattice origin not finite");
+    for (size_t i = 0; i < 3 * nv; ++i) if (!std::isfinite(vertices3[i])) return fail(SPH_ERR_ARG, "vertex %zu is not finite", i / 3);
+    for (size_t i = 0; i < 3 * nt; ++i) if (triangles3[i] >= nv) return fail(SPH_ERR_ARG, "triangle %zu names vertex %u of %zu", i / 3, triangles3[i], nv);
+    return SPH_OK;
+}
+
+int sph_mesh_distance(SphEngine* e, const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3],
+                      const float spacing[3], const int dims[3], float* devOut) {
+    if (!e || !devOut) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    long long total = 0;
+    if ((rc = mesh_check(vertices3, nv, triangles3, nt, origin, spacing, dims, &total))) return rc;
+    const long long blocks = (total + kMeshBlock - 1) / kMeshBlock;
+    // the triangles are split until about 2048 blocks exist (8 per compute unit), never below one chunk per split
+    int splits = e->optMeshSplit;
+    if (splits <= 0) splits = (int)std::min<long long>(64, std::max<long long>(1, 2048 / blocks));
+    splits = (int)std::min<size_t>((size_t)splits, (nt + kMeshChunk - 1) / kMeshChunk);
+    splits = std::max(1, std::min(splits, 64));
+    const int per = (int)((nt + (size_t)splits - 1) / (size_t)splits);
+    const size_t part = (size_t)splits * (size_t)total;
+    if (3 * nv > e->meshVertCap || 3 * nt > e->meshTriCap || part > e->meshPartCap) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (3 * nv > e->meshVertCap) { dev_free(e->d_meshVerts); e->meshVertCap = 0; if ((rc = dev_alloc(&e->d_meshVerts, 3 * nv))) return rc; e->meshVertCap = 3 * nv; }
+        if (3 * nt > e->meshTriCap) { dev_free(e->d_meshTris); e->meshTriCap = 0; if ((rc = dev_alloc(&e->d_meshTris, 3 * nt))) return rc; e->meshTriCap = 3 * nt; }
+        if (part > e->meshPartCap) {
+            dev_free(e->d_meshD2); dev_free(e->d_meshW); e->meshPartCap = 0;
+            if ((rc = dev_alloc(&e->d_meshD2, part)) || (rc = dev_alloc(&e->d_meshW, part))) return rc;
+            e->meshPartCap = part;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_meshVerts, vertices3, 3 * nv * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_meshTris, triangles3, 3 * nt * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    sph::MeshLattice L;
+    L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
+    L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
+    L.nx = dims[0]; L.ny = dims[1]; L.nz = dims[2];
+    L.total = total;
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_mesh_distance, dim3((unsigned)blocks, (unsigned)splits), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshVerts,
+                           (const uint32_t*)e->d_meshTris, (int)nt, per, L, e->d_meshD2, e->d_meshW);
+        hipLaunchKernelGGL(k_mesh_merge, dim3((unsigned)blocks), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshD2, (const double*)e->d_meshW, splits,
+                           total, devOut);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_volume_from_mesh(SphEngine* e, const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float center[3],
+                         const float spacing[3], const int dims[3], int* idOut) {
+    if (!e || !center || !idOut) return fail(SPH_ERR_ARG, "null argument");
+    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
+    int rc, id = -1;
+    long long total = 0;
+    if ((rc = volume_check_lattice(dims, spacing, &total)) || (rc = mesh_check(vertices3, nv, triangles3, nt, center, spacing, dims, &total)) ||
+        (rc = volume_free_slot(e, &id))) return rc;
+    float origin[3];
+    for (int a = 0; a < 3; ++a) origin[a] = center[a] - (0.5f * (float)(dims[a] - 1)) * spacing[a];
+    float* d = nullptr;
+    if ((rc = dev_alloc(&d, (size_t)total))) return rc;
+    if ((rc = sph_mesh_distance(e, vertices3, nv, triangles3, nt, origin, spacing, dims, d))) { dev_free(d); return rc; }
+    if ((rc = volume_adopt(e, id, d, dims, spacing))) return rc;
+    *idOut = id;
+    return SPH_OK;
+}
+
+int sph_mesh_distance_host(const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3], const float spacing[3],
+                           const int dims[3], float* out) {
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    long long total = 0;
+    if ((rc = mesh_check(vertices3, nv, triangles3, nt, origin, spacing, dims, &total))) return rc;
+    std::vector<sph::MeshTri> tris(nt);
+    for (size_t t = 0; t < nt; ++t) sph::mesh_tri_setup(vertices3, triangles3 + 3 * t, tris[t]);
+    size_t p = 0;
+    for (int k = 0; k < dims[2]; ++k)
+        for (int j = 0; j < dims[1]; ++j)
+            for (int i = 0; i < dims[0]; ++i, ++p) {
+                const float x = origin[0] + (float)i * spacing[0], y = origin[1] + (float)j * spacing[1], z = origin[2] + (float)k * spacing[2];
+                float best = INFINITY;
+                double angles = 0.0;
+                for (size_t t = 0; t < nt; ++t) {
+                    const float d2 = sph::mesh_tri_d2(tris[t], x, y, z);
+                    if (d2 < best) best = d2;
+                    angles += (double)sph::mesh_tri_angle(tris[t], x, y, z);
+                }
+                out[p] = sph::mesh_signed(best, angles);
+            }
     return SPH_OK;
 }
 

@@ -9,6 +9,8 @@
 //   k_obstacles         sweeps over the output slots with a FIXED grid (min(kObsGrid, sweeps for n)): a world-AABB cull per body and
 //                       wave, the hit, and per wave an xor butterfly of the six fp64 terms that lane 0 adds to its wave's LDS row; one
 //                       partial row per block (its waves in order).  Reads pos, reads vel only near a body, writes back only what it changed.
+//   k_obstacles_vol     k_obstacles for a set with a body bound to a volume (sph_volume.h): the binding and the volume slot are read at
+//                       wave-uniform addresses like the bodies, the eight corner loads per evaluation are the only gathers.
 //   k_obstacles_finish  one block: the partial rows summed in a fixed order (contiguous ranges, each ascending, then the ranges in order)
 //                       into the accumulators, time += dt, substeps += 1, and every pose advanced by one substep.
 // The bodies and the accumulators live in device memory, never in launch arguments, so a replayed graph sees every later
@@ -18,6 +20,7 @@
 #include <string.h>
 
 #include "sph_kernels.h"
+#include "sph_volume.h"
 
 namespace sph {
 
@@ -111,8 +114,11 @@ __host__ __device__ inline void obs_advance(ObsRec& b, float dt) {
 
 // One body against one particle.  Returns false (nothing changed) unless the particle is strictly inside; then p is
 // projected onto the surface, v gets the wall response if u_n < 0, and t receives (J, L) in fp64 (zeros when u_n >= 0).
-__host__ __device__ inline bool obs_hit(const ObsRec& b, float mass, float& px, float& py, float& pz, float& vx, float& vy, float& vz,
-                                        double (&t)[kObsTerms]) {
+// VOL: a box bound to a volume (vol != nullptr) is box, lattice extent and {phi < 0} intersected; the lattice gives
+// the projected point and the normal (vol_project), or leaves both to the box where its gradient vanishes.
+template <bool VOL>
+__host__ __device__ inline bool obs_hit_t(const ObsRec& b, const VolRec* vol, float mass, float& px, float& py, float& pz, float& vx, float& vy,
+                                          float& vz, double (&t)[kObsTerms]) {
     const float dx = px - b.c[0], dy = py - b.c[1], dz = pz - b.c[2];
     const float* M = b.M;
     float nx, ny, nz, qx, qy, qz;                                    // world normal, projected world point
@@ -134,7 +140,13 @@ __host__ __device__ inline bool obs_hit(const ObsRec& b, float mass, float& px, 
             if (!(fabsf(lx) < hx && fabsf(ly) < hy && fabsf(lz) < hz)) return false;
             const float ax = hx - fabsf(lx), ay = hy - fabsf(ly), az = hz - fabsf(lz);
             ox = lx; oy = ly; oz = lz; mx = 0.0f; my = 0.0f; mz = 0.0f;
-            if (ax <= ay && ax <= az) { const float s = lx >= 0.0f ? 1.0f : -1.0f; ox = s * hx; mx = s; }   // ties: x, then y, then z
+            int how = 2;                                             // 0: no hit, 1: the lattice projected, 2: the nearest face of the box
+            if constexpr (VOL) {
+                if (vol) how = vol_project(*vol, lx, ly, lz, ox, oy, oz, mx, my, mz);
+            }
+            if (how == 0) return false;
+            if (how == 1) {}
+            else if (ax <= ay && ax <= az) { const float s = lx >= 0.0f ? 1.0f : -1.0f; ox = s * hx; mx = s; }   // ties: x, then y, then z
             else if (ay <= az) { const float s = ly >= 0.0f ? 1.0f : -1.0f; oy = s * hy; my = s; }
             else { const float s = lz >= 0.0f ? 1.0f : -1.0f; oz = s * hz; mz = s; }
         } else {
@@ -179,6 +191,10 @@ __host__ __device__ inline bool obs_hit(const ObsRec& b, float mass, float& px, 
     }
     return true;
 }
+__host__ __device__ inline bool obs_hit(const ObsRec& b, float mass, float& px, float& py, float& pz, float& vx, float& vy, float& vz,
+                                        double (&t)[kObsTerms]) {
+    return obs_hit_t<false>(b, nullptr, mass, px, py, pz, vx, vy, vz, t);
+}
 
 // One slot against bodies 0..K-1 in order (slot s of the output state, its position already loaded): the wave's terms of every body that
 // some lane of the wave is near go through an xor butterfly, and lane 0 adds them to the wave's LDS row.
@@ -186,8 +202,10 @@ __device__ __forceinline__ bool obs_near(const ObsRec& B, float4 P) {
     return fabsf(P.x - B.c[0]) <= B.ext[0] && fabsf(P.y - B.c[1]) <= B.ext[1] && fabsf(P.z - B.c[2]) <= B.ext[2];
 }
 // The bodies are read from global memory at wave-uniform addresses (scalar loads: the cull compares against SGPRs).
-__device__ __forceinline__ void obs_slot(const ObsRec* __restrict__ bodies, int K, float mass, float4* __restrict__ pos, float4* __restrict__ vel,
-                                         int s, float4 P, bool cand, double* row, int lane) {
+// VOL: the binding of body b and the slot it names are read from the table at wave-uniform addresses as well.
+template <bool VOL>
+__device__ __forceinline__ void obs_slot(const ObsRec* __restrict__ bodies, const VolTable* __restrict__ tab, int K, float mass,
+                                         float4* __restrict__ pos, float4* __restrict__ vel, int s, float4 P, bool cand, double* row, int lane) {
     float4 V = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     bool haveV = false, changed = false;
     for (int b = 0; b < K; ++b) {
@@ -197,7 +215,12 @@ __device__ __forceinline__ void obs_slot(const ObsRec* __restrict__ bodies, int 
         double t[kObsTerms] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (near) {
             if (!haveV) { V = vel[s]; haveV = true; }
-            changed |= obs_hit(B, mass, P.x, P.y, P.z, V.x, V.y, V.z, t);
+            const VolRec* vol = nullptr;
+            if constexpr (VOL) {
+                const int id = tab->bind[b];
+                if (id >= 0) vol = &tab->vol[id];
+            }
+            changed |= obs_hit_t<VOL>(B, vol, mass, P.x, P.y, P.z, V.x, V.y, V.z, t);
         }
 #pragma unroll
         for (int c = 0; c < kObsTerms; ++c)
@@ -232,7 +255,7 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles(const ObsRec* __restric
         for (int j = 0; j < kObsUnroll; ++j) {
             const int s = base + j * kObsBlock + threadIdx.x;
             const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && obs_finite(P[j].x) && obs_finite(P[j].y) && obs_finite(P[j].z);
-            obs_slot(bodies, K, mass, pos, vel, s, P[j], cand, sacc[wave], lane);
+            obs_slot<false>(bodies, nullptr, K, mass, pos, vel, s, P[j], cand, sacc[wave], lane);
         }
     }
     __syncthreads();
@@ -242,7 +265,6 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles(const ObsRec* __restric
         part[(size_t)blockIdx.x * kObsRow + i] = r;
     }
 }
-
 // One block.  The rows are cut into chunks = min(kObsFinishBlock / (6 K), rows) contiguous ranges of ceil(rows / chunks); thread
 // (chunk, term) sums its range in ascending row order (loads issued kObsBatch at a time), then thread `term` sums the chunk sums in chunk
 // order and adds the result to the accumulator.  Then the poses advance.
@@ -277,6 +299,43 @@ __global__ __launch_bounds__(kObsFinishBlock) void k_obstacles_finish(ObsRec* __
         ObsRec B = bodies[t];
         obs_advance(B, dt);
         bodies[t] = B;
+    }
+}
+
+// The same pass for a set with at least one body bound to a volume (launched only then: DESIGN.md section 3f).  The body is written out a
+// second time on purpose: with both kernels calling one shared function template, k_obstacles no longer compiled to the instructions it
+// had before volumes existed (another register allocation), and the primitive path must not pay for this one.  It is defined after
+// k_obstacles_finish so that the finish stays next to k_obstacles in the code object: with this kernel between them the one-block finish,
+// the same instructions, ran 0.9 us slower in a kernel trace (12.9 against 11.9 us) and the pass without volumes 1-2 us slower than before.
+__global__ __launch_bounds__(kObsBlock) void k_obstacles_vol(const ObsRec* __restrict__ bodies, const VolTable* __restrict__ tab, int K, float mass,
+                                                             float4* __restrict__ pos, float4* __restrict__ vel, int n, double* __restrict__ part) {
+    __shared__ double sacc[kObsWaves][kObsRow];
+    {
+        double* z = &sacc[0][0];
+        for (int i = threadIdx.x; i < kObsWaves * kObsRow; i += kObsBlock) z[i] = 0.0;
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int base = blockIdx.x * kObsSweep; base < n; base += gridDim.x * kObsSweep) {     // (block-uniform)
+        float4 P[kObsUnroll];
+#pragma unroll
+        for (int j = 0; j < kObsUnroll; ++j) {
+            const int s = base + j * kObsBlock + threadIdx.x;
+            P[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (s < n) P[j] = pos[s];
+        }
+#pragma unroll
+        for (int j = 0; j < kObsUnroll; ++j) {
+            const int s = base + j * kObsBlock + threadIdx.x;
+            const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && obs_finite(P[j].x) && obs_finite(P[j].y) && obs_finite(P[j].z);
+            obs_slot<true>(bodies, tab, K, mass, pos, vel, s, P[j], cand, sacc[wave], lane);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < K * kObsTerms; i += kObsBlock) {
+        double r = sacc[0][i];
+        for (int w = 1; w < kObsWaves; ++w) r += sacc[w][i];
+        part[(size_t)blockIdx.x * kObsRow + i] = r;
     }
 }
 

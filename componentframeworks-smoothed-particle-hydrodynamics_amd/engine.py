@@ -15,6 +15,7 @@ raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -76,6 +77,7 @@ class SphGridInfo(C.Structure):
 # option / kernel-class constants of sph_abi.h
 SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_GRID_BUILD, SPH_OPT_AOS_MODE, SPH_OPT_TIMING, SPH_OPT_DEBUG = 1, 2, 3, 4, 100
 SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = 5, 6
+SPH_OPT_MESH_SPLIT = 7
 KERNEL_CLASSES = ("bin", "scan", "scatter", "sph", "writeback", "impulse", "other")
 
 # every symbol include/sph_abi.h declares (checked by tests/test_abi.py)
@@ -113,6 +115,8 @@ ABI_SYMBOLS = (
     "sph_tracers_history",
     "sph_obstacle_default", "sph_obstacles_set", "sph_obstacles_set_motion", "sph_obstacles_get", "sph_obstacles_impulses",
     "sph_obstacles_apply_host", "sph_obstacles_advance_host",
+    "sph_volume_create", "sph_volume_destroy", "sph_volume_info", "sph_volume_sample_host", "sph_obstacles_bind_volume", "sph_obstacles_volume",
+    "sph_obstacles_apply_host_volumes", "sph_mesh_distance", "sph_mesh_distance_host", "sph_volume_from_mesh",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -156,6 +160,7 @@ OBSTACLE_DTYPE = np.dtype([("shape", "<i4"), ("size", "<f4", (3,)), ("center", "
                            ("vel", "<f4", (3,)), ("omega", "<f4", (3,)), ("restitution", "<f4"), ("friction", "<f4")])
 assert OBSTACLE_DTYPE.itemsize == 76
 SPH_MAX_OBSTACLES = 16
+SPH_MAX_VOLUMES = 16
 SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE = 0, 1, 2
 
 
@@ -190,6 +195,26 @@ def obstacle_array(obstacles) -> np.ndarray:
     if not obstacles:
         return np.zeros(0, OBSTACLE_DTYPE)
     return np.frombuffer(b"".join(bytes(o) for o in obstacles), OBSTACLE_DTYPE).copy()
+
+
+class SphVolumeHost(C.Structure):
+    """struct SphVolumeHost of include/sph_abi.h: one lattice of signed distances in host memory (see obstacles_apply_host_volumes)."""
+    _fields_ = [("values", C.c_void_p), ("dims", C.c_int * 3), ("spacing", C.c_float * 3)]
+
+
+def _volume_lattice(values, spacing):
+    """A (nz, ny, nx) array of signed distances and its spacing -> (contiguous fp32 array, dims (nx, ny, nz), spacing[3])."""
+    v = np.ascontiguousarray(values, np.float32)
+    if v.ndim != 3:
+        raise SphError(f"a volume needs an array of shape (nz, ny, nx), not {v.shape}")
+    sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
+    return v, (C.c_int * 3)(v.shape[2], v.shape[1], v.shape[0]), sp
+
+
+def _mesh_arrays(vertices, triangles):
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    return v, t
 
 
 class SphSurface(C.Structure):
@@ -447,6 +472,17 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_obstacles_impulses.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
     L.sph_obstacles_apply_host.argtypes = [vp, C.c_int, C.c_float, vp, C.c_size_t, vp]
     L.sph_obstacles_advance_host.argtypes = [vp, C.c_int, C.c_float]
+    i3 = C.POINTER(C.c_int)
+    L.sph_volume_create.argtypes = [vp, vp, i3, f3, C.c_int, i3]
+    L.sph_volume_destroy.argtypes = [vp, C.c_int]
+    L.sph_volume_info.argtypes = [vp, C.c_int, i3, f3, f3]
+    L.sph_volume_sample_host.argtypes = [vp, i3, f3, f3, f3, f3, i3]
+    L.sph_obstacles_bind_volume.argtypes = [vp, C.c_int, C.c_int]
+    L.sph_obstacles_volume.argtypes = [vp, C.c_int, i3]
+    L.sph_obstacles_apply_host_volumes.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_float, vp, C.c_size_t, vp]
+    L.sph_mesh_distance.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
+    L.sph_volume_from_mesh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, i3]
+    L.sph_mesh_distance_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count",
@@ -982,6 +1018,70 @@ class SPHFluidGPU:
         return out[:len(self.obstacles())].copy(), float(t.value), int(n.value)
 
     # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
+    # -- triangle-mesh obstacles through signed distance lattices (include/sph_abi.h "signed distance lattices") --------
+    def create_volume(self, values, spacing) -> int:
+        """A volume from signed distances (negative inside) of shape (nz, ny, nx): a numpy array or a contiguous float32 torch CUDA tensor.
+        spacing is a scalar or (sx, sy, sz).  Returns the volume's id."""
+        vid = C.c_int(-1)
+        if hasattr(values, "data_ptr"):
+            if not values.is_cuda or values.dtype != __import__("torch").float32 or not values.is_contiguous() or values.dim() != 3:
+                raise SphError("create_volume: values must be a contiguous float32 CUDA tensor of shape (nz, ny, nx)")
+            dims = (C.c_int * 3)(values.shape[2], values.shape[1], values.shape[0])
+            sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
+            _check(self._L.sph_volume_create(self._h, C.c_void_p(values.data_ptr()), dims, _f3(sp), 1, C.byref(vid)))
+        else:
+            v, dims, sp = _volume_lattice(values, spacing)
+            _check(self._L.sph_volume_create(self._h, v.ctypes.data_as(C.c_void_p), dims, _f3(sp), 0, C.byref(vid)))
+        return int(vid.value)
+
+    def destroy_volume(self, volume_id: int):
+        _check(self._L.sph_volume_destroy(self._h, int(volume_id)))
+
+    def volume_info(self, volume_id: int):
+        """(dims (nx, ny, nz), spacing[3], half[3]) of a volume; half is the box size that covers the lattice exactly."""
+        d, sp, hf = (C.c_int * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
+        _check(self._L.sph_volume_info(self._h, int(volume_id), d, sp, hf))
+        return tuple(d), np.array(sp, np.float32), np.array(hf, np.float32)
+
+    def bind_obstacle_volume(self, index: int, volume_id: int):
+        """Body `index` (a box) takes its shape from the volume (volume_id < 0 unbinds).  set_obstacles clears every binding."""
+        _check(self._L.sph_obstacles_bind_volume(self._h, int(index), int(volume_id)))
+
+    def obstacle_volume(self, index: int) -> int:
+        vid = C.c_int(-1)
+        _check(self._L.sph_obstacles_volume(self._h, int(index), C.byref(vid)))
+        return int(vid.value)
+
+    def mesh_distance(self, vertices, triangles, origin, spacing, dims):
+        """Signed distance (negative inside) from the lattice points origin + i * spacing, dims = (nx, ny, nz), to a closed triangle mesh
+        (counter-clockwise seen from outside): a float32 torch CUDA tensor of shape (nz, ny, nx).  Asynchronous on the engine's stream."""
+        import torch
+        v, t = _mesh_arrays(vertices, triangles)
+        d = (C.c_int * 3)(*[int(x) for x in dims])
+        sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
+        if min(d) < 1 or int(d[0]) * int(d[1]) * int(d[2]) > 2 ** 31 - 1:
+            raise SphError(f"mesh_distance: bad dims {tuple(d)}")
+        out = torch.empty((int(d[2]), int(d[1]), int(d[0])), dtype=torch.float32, device="cuda")
+        _check(self._L.sph_mesh_distance(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(origin), _f3(sp), d,
+                                         C.c_void_p(out.data_ptr())))
+        self.sync()                                                      # (the tensor is handed to the caller's own stream)
+        return out
+
+    def volume_from_mesh(self, vertices, triangles, spacing: float, margin: float = 2.0):
+        """A volume around a mesh: a lattice of the given spacing about the mesh's bounding box widened by `margin` spacings on every side.
+        Returns (id, center, half): obstacle(SPH_OBSTACLE_BOX, center, half) + bind_obstacle_volume(index, id) is the whole recipe."""
+        v, t = _mesh_arrays(vertices, triangles)
+        if not len(v):
+            raise SphError("volume_from_mesh: no vertices")
+        h = np.float32(spacing)
+        lo, hi = v.min(axis=0).astype(np.float64), v.max(axis=0).astype(np.float64)
+        dims = [max(2, int(math.ceil((hi[a] - lo[a]) / float(h) + 2.0 * margin)) + 1) for a in range(3)]
+        center = (0.5 * (lo + hi)).astype(np.float32)
+        vid = C.c_int(-1)
+        _check(self._L.sph_volume_from_mesh(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(center), _f3((h, h, h)),
+                                            (C.c_int * 3)(*dims), C.byref(vid)))
+        return int(vid.value), center, self.volume_info(vid.value)[2]
+
     def statistics(self, histograms=None) -> Statistics:
         """Counts, extrema, fp64 sums, cell occupancy and up to 4 histograms ((field, bins, lo, hi) with field one of SPH_STAT_*) of the
         current state, reduced on the GPU.  Synchronises."""
@@ -1045,3 +1145,46 @@ def obstacles_advance_host(obstacles, dt: float) -> np.ndarray:
     arr = obstacle_array(obstacles).copy()
     _check(load_library().sph_obstacles_advance_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(dt)))
     return arr
+
+
+def volume_sample_host(values, spacing, local):
+    """sph_volume_sample_host at one local point of a (nz, ny, nx) lattice: (phi, gradient[3], inside).  No device is needed."""
+    v, dims, sp = _volume_lattice(values, spacing)
+    phi, inside, g = C.c_float(), C.c_int(), (C.c_float * 3)()
+    _check(load_library().sph_volume_sample_host(v.ctypes.data_as(C.c_void_p), dims, _f3(sp), _f3(local), C.byref(phi), g, C.byref(inside)))
+    return np.float32(phi.value), np.array(g, np.float32), bool(inside.value)
+
+
+def obstacles_apply_host_volumes(obstacles, volumes, bindings, particle_mass: float, particles: np.ndarray):
+    """sph_obstacles_apply_host_volumes on a copy of the records: (records, impulses (K, 6)).  volumes is a list of (values (nz, ny, nx),
+    spacing), bindings one volume index (or -1) per body.  No device is needed."""
+    arr = obstacle_array(obstacles)
+    rec = np.ascontiguousarray(particles, PARTICLE_DTYPE).copy()
+    imp = np.zeros((max(len(arr), 1), 6), np.float64)
+    keep, vols = [], (SphVolumeHost * max(len(volumes), 1))()
+    for i, (values, spacing) in enumerate(volumes):
+        v, dims, sp = _volume_lattice(values, spacing)
+        keep.append(v)
+        vols[i].values = v.ctypes.data
+        vols[i].dims[:] = list(dims)
+        vols[i].spacing[:] = [float(x) for x in sp]
+    bind = np.ascontiguousarray(bindings, np.int32)
+    if len(bind) != len(arr):
+        raise SphError(f"{len(bind)} bindings for {len(arr)} obstacles")
+    _check(load_library().sph_obstacles_apply_host_volumes(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), C.byref(vols), len(volumes),
+                                                           bind.ctypes.data_as(C.c_void_p) if len(bind) else None, float(particle_mass),
+                                                           rec.ctypes.data_as(C.c_void_p), len(rec), imp.ctypes.data_as(C.c_void_p)))
+    return rec, imp[:len(arr)]
+
+
+def mesh_distance_host(vertices, triangles, origin, spacing, dims) -> np.ndarray:
+    """sph_mesh_distance_host: the signed distances as a float32 array of shape (nz, ny, nx).  No device is needed (plain loops: small cases)."""
+    v, t = _mesh_arrays(vertices, triangles)
+    d = (C.c_int * 3)(*[int(x) for x in dims])
+    sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
+    if min(d) < 1 or int(d[0]) * int(d[1]) * int(d[2]) > 2 ** 31 - 1:
+        raise SphError(f"mesh_distance_host: bad dims {tuple(d)}")
+    out = np.empty((int(d[2]), int(d[1]), int(d[0])), np.float32)
+    _check(load_library().sph_mesh_distance_host(v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(origin), _f3(sp), d,
+                                                 out.ctypes.data_as(C.c_void_p)))
+    return out

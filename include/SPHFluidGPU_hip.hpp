@@ -265,6 +265,34 @@ public:
         impulses6.resize(6 * cur.size());
         return true;
     }
+    // Triangle-mesh obstacles through signed distance lattices (engine extension, sph_abi.h "signed distance lattices", DESIGN.md section
+    // 3f).  CreateVolume copies a lattice of signed distances (negative inside, x fastest) from host memory; VolumeFromMesh builds one on
+    // the device from a closed mesh (triangles counter-clockwise seen from outside), centred on `center`; half receives the box size
+    // that covers the lattice.  BindObstacleVolume(index, id) gives body `index` (a box) the volume's shape (id < 0 unbinds; SetObstacles
+    // clears every binding).  MeshDistance writes the signed distances of a caller's lattice into a DEVICE array.  Return false on error.
+    bool CreateVolume(const std::vector<float>& values, const int dims[3], const MATH::Vec3& spacing, int& id) {
+        const float s[3] = {spacing.x, spacing.y, spacing.z};
+        if (values.size() != size_t(dims[0]) * size_t(dims[1]) * size_t(dims[2])) { lastError = "CreateVolume: dims do not match the values"; return false; }
+        return !Check(sph_volume_create(engine, values.data(), dims, s, 0, &id), "sph_volume_create");
+    }
+    bool VolumeFromMesh(const std::vector<float>& vertices3, const std::vector<uint32_t>& triangles3, const MATH::Vec3& center, float spacing,
+                        const int dims[3], int& id, MATH::Vec3& half) {
+        const float c[3] = {center.x, center.y, center.z}, s[3] = {spacing, spacing, spacing};
+        if (Check(sph_volume_from_mesh(engine, vertices3.data(), vertices3.size() / 3, triangles3.data(), triangles3.size() / 3, c, s, dims, &id),
+                  "sph_volume_from_mesh")) return false;
+        float h[3];
+        if (Check(sph_volume_info(engine, id, nullptr, nullptr, h), "sph_volume_info")) return false;
+        half = MATH::Vec3(h[0], h[1], h[2]);
+        return true;
+    }
+    bool DestroyVolume(int id) { return !Check(sph_volume_destroy(engine, id), "sph_volume_destroy"); }
+    bool BindObstacleVolume(int index, int id) { return !Check(sph_obstacles_bind_volume(engine, index, id), "sph_obstacles_bind_volume"); }
+    bool MeshDistance(const std::vector<float>& vertices3, const std::vector<uint32_t>& triangles3, const MATH::Vec3& origin, const MATH::Vec3& spacing,
+                      const int dims[3], float* devOut) {
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        return !Check(sph_mesh_distance(engine, vertices3.data(), vertices3.size() / 3, triangles3.data(), triangles3.size() / 3, o, s, dims, devOut),
+                      "sph_mesh_distance");
+    }
     bool Download(std::vector<SPHParticle>& out) {
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");

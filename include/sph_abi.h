@@ -37,6 +37,8 @@ extern "C" {
 /* (still 4, additions only: SphTracer, SPH_TRACER_*, sph_tracers_set / _set_device / _count / _info / _download / _device / _history -- passive tracers) */
 /* (still 4, additions only: SphObstacle, SPH_OBSTACLE_*, SPH_MAX_OBSTACLES, sph_obstacle_default, sph_obstacles_set / _set_motion / _get / _impulses /
     _apply_host / _advance_host -- kinematic solid obstacles) */
+/* (still 4, additions only: SphVolumeHost, SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, sph_volume_create / _destroy / _info / _sample_host / _from_mesh,
+    sph_obstacles_bind_volume / _volume / _apply_host_volumes, sph_mesh_distance / _host -- triangle-mesh obstacles through signed distance lattices) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -138,6 +140,7 @@ enum {
     SPH_OPT_GRID_BUILD = 2,      /* 0 = counting sort (default), 1 = atomicExch linked list as BuildGrid.comp (A/B only; neighbour order then arbitrary) */
     SPH_OPT_AOS_MODE = 3,        /* 1 = lazy (default): the substep keeps its state in the engine's own arrays and the 80-byte records are brought up to date by sph_device_particles() / sph_download_particles() / sph_pack_render_buffer(), i.e. once per rendered frame instead of once per substep (the scattered 52-byte update of every record costs about 13 % of the SPH pass); 0 = eager: the SPH pass also updates the records, they are current after every dispatch. Same values either way. */
     SPH_OPT_GRAPH = 5,           /* 1 = sph_dispatch_n replays a hipGraph once the same call (same members, options, substep count) has been seen twice; default 0 */
+    SPH_OPT_MESH_SPLIT = 7,      /* sph_mesh_distance: 0 = the engine chooses into how many ranges the triangles are split (default), 1..64 = that many (capped at one per 256 triangles); same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -464,6 +467,62 @@ int  sph_obstacles_impulses(SphEngine* e, double* out6, int cap, double* timeOut
  * (count x 6, may be null) receives the sums in index order.  advance: one pose advance of every body by dt, in place. */
 int  sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMass, SphParticle* particles, size_t n, double* impulses6);
 int  sph_obstacles_advance_host(SphObstacle* obs, int count, float dt);
+
+/* ---- triangle-mesh obstacles through signed distance lattices (no reference counterpart) ---------------
+ * A VOLUME is an engine-owned lattice of fp32 signed distances in a body's local length unit, NEGATIVE INSIDE the solid, x fastest,
+ * centred on the body: local coordinate of point i on axis a is (float)i * spacing_a - half_a, half_a = 0.5f (float)(dims_a - 1)
+ * spacing_a.  Up to SPH_MAX_VOLUMES exist per engine.  Bound to a body of shape SPH_OBSTACLE_BOX (whose box stays what it is for the
+ * cull and for the host entry points of the block above), the volume makes the solid box, lattice extent and {phi < 0} intersected:
+ * a particle strictly inside the box whose lattice coordinate lies in the extent and whose trilinear phi is < 0 is projected by two
+ * steps o <- o - phi(o) grad phi(o) / |grad phi(o)| (the gradient of the same trilinear interpolant; the second evaluation at the
+ * point clamped into the extent), the local normal is the unit gradient of the second evaluation, and where a gradient has length 0
+ * or is not finite the box's nearest face decides.  Everything else (surface velocity, response, impulses, pose advance) is the
+ * block above.  Users normally give the box size = half (sph_volume_info).  Bindings and the volume table live in device memory: a
+ * replayed graph sees a later bind.  With no body bound a dispatch launches exactly the kernels it launches without volumes.
+ * SPH_ERR_ARG (nothing changes): null pointers, a dimension < 2, more than 2^31 - 1 points, a spacing not finite or <= 0, an id that
+ * names no volume, an index outside the set, a body that is not a box.  SPH_ERR_CAPACITY: all slots in use.  SPH_ERR_STATE: z-slab
+ * engines; sph_volume_destroy of a bound volume. */
+#define SPH_MAX_VOLUMES 16
+/* Copies dims[0] dims[1] dims[2] floats from host (onDevice == 0; synchronises) or device (stream-ordered) memory; *idOut is the slot. */
+int  sph_volume_create(SphEngine* e, const float* values, const int dims[3], const float spacing[3], int onDevice, int* idOut);
+/* Frees the slot.  Synchronises. */
+int  sph_volume_destroy(SphEngine* e, int id);
+/* Any output pointer may be null. */
+int  sph_volume_info(SphEngine* e, int id, int dimsOut[3], float spacingOut[3], float halfOut[3]);
+/* Binds volume `id` to body `index` (id < 0 unbinds).  sph_obstacles_set clears every binding (a set replaces the set);
+ * sph_obstacles_set_motion keeps them.  Stream-ordered, no synchronisation. */
+int  sph_obstacles_bind_volume(SphEngine* e, int index, int id);
+/* The volume bound to body `index`, -1 if none. */
+int  sph_obstacles_volume(SphEngine* e, int index, int* idOut);
+/* Host-only, no device: the same __host__ __device__ functions the kernels run.  sample: phi and the gradient of the trilinear
+ * interpolant (divided by the spacing, not normalised) at a local point; *insideOut = 1 iff the point lies in the extent and phi < 0;
+ * outside the extent (or at a NaN coordinate) phi is a quiet NaN and the gradient zero.  apply: sph_obstacles_apply_host with body b
+ * bound to volumes[bindings[b]] (bindings[b] < 0: none; bound bodies must be boxes); with every binding < 0 the result equals
+ * sph_obstacles_apply_host byte for byte. */
+typedef struct SphVolumeHost {     /* 32 bytes */
+    const float* values;
+    int          dims[3];
+    float        spacing[3];
+} SphVolumeHost;
+int  sph_volume_sample_host(const float* values, const int dims[3], const float spacing[3], const float local[3], float* phiOut, float gradOut[3],
+                            int* insideOut);
+int  sph_obstacles_apply_host_volumes(const SphObstacle* obs, int count, const SphVolumeHost* volumes, int volumeCount, const int* bindings,
+                                      float particleMass, SphParticle* particles, size_t n, double* impulses6);
+/* Signed distance from every lattice point origin + (float)i * spacing (x fastest) to a triangle mesh given in HOST memory (3 floats per
+ * vertex, 3 uint32 per triangle), one float per point into the caller's DEVICE array; asynchronous on the engine's stream after the mesh
+ * upload.  Reads no particles: works on any engine.  Magnitude: sqrtf of the minimum over the triangles of the squared distance to the
+ * closest point of the triangle (bit-exact, independent of how the work is split).  Sign: negative where the generalised winding number
+ * of the mesh is >= 0.5.  Triangles are counter-clockwise seen from outside (what sph_extract_surface emits); a closed mesh wound the
+ * other way is OUTSIDE everywhere.  Timed as SPH_K_OTHER.  SPH_ERR_ARG: null pointers, nt == 0, an index >= nv, a vertex or origin
+ * that is not finite, a dimension < 1, more than 2^31 - 1 points, a spacing not finite or <= 0.  The _host twin runs the same per-pair functions in plain loops into host memory. */
+int  sph_mesh_distance(SphEngine* e, const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3],
+                       const float spacing[3], const int dims[3], float* devOut);
+/* sph_mesh_distance straight into a new volume: the lattice of dims points is centred on `center` (origin = center - half), so a body
+ * of shape SPH_OBSTACLE_BOX at `center` with size = half (sph_volume_info) bound to *idOut is the mesh as an obstacle.  Nothing leaves the device. */
+int  sph_volume_from_mesh(SphEngine* e, const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float center[3],
+                          const float spacing[3], const int dims[3], int* idOut);
+int  sph_mesh_distance_host(const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3], const float spacing[3],
+                            const int dims[3], float* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
