@@ -17,5 +17,7 @@ from .engine import (  # noqa: F401
     SPH_MAX_OBSTACLES, SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE, SphObstacle, OBSTACLE_DTYPE, obstacle, obstacle_array,
     obstacles_apply_host, obstacles_advance_host,
     SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, SphVolumeHost, volume_sample_host, obstacles_apply_host_volumes, mesh_distance_host,
+    SPH_DYNAMICS_CONFINED, SphObstacleDynamics, DYNAMICS_DTYPE, dynamics, dynamics_sphere, dynamics_box, dynamics_capsule, dynamics_array,
+    mass_properties, obstacles_step_host, volume_moments_host,
 )
 from . import build, synthetic  # noqa: F401

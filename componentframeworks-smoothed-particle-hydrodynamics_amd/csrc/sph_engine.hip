@@ -33,6 +33,7 @@ static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
+static_assert(sizeof(SphObstacleDynamics) == 80, "SphObstacleDynamics must be 80 bytes");
 static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
@@ -243,6 +244,18 @@ struct SphEngine {
     int volSlot = 0;
     int volBound = 0;                    // bodies bound to a volume: k_obstacles_vol is launched instead of k_obstacles while > 0
     int obsShape[sph::kObsMax] = {0};    // shapes of the current set (a volume binds to a box only)
+    // dynamic bodies (sph_obstacle.h ObsDyn): one record per body beside d_obs, the records as set (host mirror),
+    // pinned staging like the bodies'; k_obstacles_finish_dyn is launched instead of k_obstacles_finish while dynCount > 0
+    sph::ObsDyn* d_dyn = nullptr;
+    sph::ObsDyn* h_dynStage = nullptr;   // kObsSlots records
+    hipEvent_t evDyn[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
+    int dynSlot = 0;
+    int dynCount = 0;
+    bool dynOn[sph::kObsMax] = {false};
+    SphObstacleDynamics dynSet[sph::kObsMax] = {};
+    // sph_volume_moments: the partial rows and the ten results
+    double* d_momPart = nullptr;
+    double* d_momOut = nullptr;
     int optMeshSplit = 0;                // SPH_OPT_MESH_SPLIT
     float* d_meshVerts = nullptr;
     uint32_t* d_meshTris = nullptr;
@@ -353,10 +366,15 @@ void tracers_free(SphEngine* e) {
 
 void obstacles_free(SphEngine* e) {
     if (e->d_obs && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(e->d_obs); dev_free(e->d_obsAcc); dev_free(e->d_obsPart);
+    dev_free(e->d_obs); dev_free(e->d_obsAcc); dev_free(e->d_obsPart); dev_free(e->d_dyn);
     if (e->h_obsStage) (void)hipHostFree(e->h_obsStage);
     e->h_obsStage = nullptr;
+    if (e->h_dynStage) (void)hipHostFree(e->h_dynStage);
+    e->h_dynStage = nullptr;
     for (auto& ev : e->evObs) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    for (auto& ev : e->evDyn) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    e->dynCount = 0; e->dynSlot = 0;
+    for (auto& on : e->dynOn) on = false;
     e->obsK = 0;
     e->obsSlot = 0;
 }
@@ -377,6 +395,7 @@ void volumes_free(SphEngine* e) {
     volumes_unbind_all(e);
     e->volSlot = 0;
     dev_free(e->d_meshVerts); dev_free(e->d_meshTris); dev_free(e->d_meshD2); dev_free(e->d_meshW);
+    dev_free(e->d_momPart); dev_free(e->d_momOut);
     e->meshVertCap = e->meshTriCap = e->meshPartCap = 0;
 }
 
@@ -560,6 +579,14 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
 }
 
 // ---- obstacles (sph_obstacle.h) -------------------------------------------------------------------
+// What obs_body_step needs of the parameters: gravity, the container's oriented box as the grid sees it, the wall restitution.
+void obstacle_world(const SphParams& p, sph::ObsWorld& W) {
+    W.g[0] = p.param_gravityX; W.g[1] = p.param_gravityY; W.g[2] = p.param_gravityZ;
+    for (int a = 0; a < 3; ++a) W.bc[a] = p.param_boxCenter[a];
+    sph::rotation_mat3(p.param_boxEulerDeg, W.A);
+    sph::effective_half(p, W.half);
+    W.rest = p.param_wallRestitution;
+}
 // One substep's obstacle step on the pass's output state: k_obstacles, then the one-block finish (sums, accumulators, pose advance).
 int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
     const int rows = n > 0 ? std::min(kObsGrid, blocks_for((size_t)n, kObsSweep)) : 0;
@@ -570,6 +597,12 @@ int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
                                e->params.param_mass, pos, vel, n, e->d_obsPart);
         else if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, e->obsK, e->params.param_mass, pos, vel, n,
                                      e->d_obsPart);
+        if (e->dynCount > 0) {                                       // (the finish that also steps the dynamic bodies)
+            ObsWorld W;
+            obstacle_world(e->params, W);
+            hipLaunchKernelGGL(k_obstacles_finish_dyn, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, (const ObsDyn*)e->d_dyn, W, e->obsK, dt,
+                               (const double*)e->d_obsPart, rows, e->d_obsAcc);
+        } else
         hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
     }
     HIP_TRY(hipGetLastError());
@@ -1059,6 +1092,11 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     const int anyBound = e->volBound > 0 ? 1 : 0;
     add(&vt, sizeof(vt));
     add(&anyBound, sizeof(anyBound));
+    // dynamic bodies: the records' address and which finish kernel runs; the records are read from memory
+    const void* dy = e->d_dyn;
+    const int anyDyn = e->dynCount > 0 ? 1 : 0;
+    add(&dy, sizeof(dy));
+    add(&anyDyn, sizeof(anyDyn));
     return m;
 }
 static uint64_t graph_hash(const std::vector<unsigned char>& m) {
@@ -2795,14 +2833,24 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
     }
     if (count == 0) { obstacles_free(e); return SPH_OK; }
     if (!e->d_obs) {
-        if ((rc = dev_alloc(&e->d_obs, (size_t)kObsMax)) || (rc = dev_alloc(&e->d_obsAcc, 1)) || (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow))) {
+        if ((rc = dev_alloc(&e->d_obs, (size_t)kObsMax)) || (rc = dev_alloc(&e->d_obsAcc, 1)) || (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow)) ||
+            (rc = dev_alloc(&e->d_dyn, (size_t)kObsMax))) {
             obstacles_free(e); return rc;
         }
         hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&e->h_obsStage), sizeof(sph::ObsRec) * kObsMax * SphEngine::kObsSlots, hipHostMallocDefault);
+        if (er == hipSuccess) er = hipHostMalloc(reinterpret_cast<void**>(&e->h_dynStage), sizeof(sph::ObsDyn) * SphEngine::kObsSlots, hipHostMallocDefault);
         for (auto& ev : e->evObs) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        for (auto& ev : e->evDyn) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
         if (er != hipSuccess) { obstacles_free(e); return fail(SPH_ERR_HIP, "obstacle staging: %s", hipGetErrorString(er)); }
         for (auto& ev : e->evObs) HIP_TRY(hipEventRecord(ev, e->stream));
+        for (auto& ev : e->evDyn) HIP_TRY(hipEventRecord(ev, e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dyn, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
         e->obsK = 0;
+    }
+    if (e->dynCount > 0) {                                           // (a set replaces the set: every dynamics record goes with it)
+        HIP_TRY(hipMemsetAsync(e->d_dyn, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
+        e->dynCount = 0;
+        for (auto& on : e->dynOn) on = false;
     }
     sph::ObsRec* slot = nullptr;
     if ((rc = obstacles_slot(e, &slot))) return rc;
@@ -2900,6 +2948,96 @@ int sph_obstacles_advance_host(SphObstacle* obs, int count, float dt) {
     return SPH_OK;
 }
 
+// ---- dynamic bodies (sph_obstacle.h obs_body_step) --------------------------
+void sph_obstacle_dynamics_default(SphObstacleDynamics* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->mass = 1.0f;
+    out->inertia[0] = out->inertia[1] = out->inertia[2] = 1.0f;
+    out->gravityScale = 1.0f;
+    out->flags = SPH_DYNAMICS_CONFINED;
+}
+// Checks a record and builds the device record: the inertia inverted in fp64 (adjugate over determinant), both stored as fp32.
+static int dynamics_to_rec(const SphObstacleDynamics& d, int index, sph::ObsDyn& r) {
+    const float* f = &d.mass;
+    static_assert(offsetof(SphObstacleDynamics, flags) == 19 * sizeof(float), "nineteen floats, then the flags");
+    if (!obs_all_finite(f, 19)) return fail(SPH_ERR_ARG, "obstacle %d: a dynamics field is not finite", index);
+    if (!(d.mass > 0.0f)) return fail(SPH_ERR_ARG, "obstacle %d: mass %g must be > 0", index, (double)d.mass);
+    if (d.linearDamping < 0.0f || d.angularDamping < 0.0f) return fail(SPH_ERR_ARG, "obstacle %d: a damping is negative", index);
+    const double xx = d.inertia[0], yy = d.inertia[1], zz = d.inertia[2], xy = d.inertia[3], xz = d.inertia[4], yz = d.inertia[5];
+    const double m2 = xx * yy - xy * xy;
+    const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;
+    const double det = xx * c00 + xy * c01 + xz * c02;
+    if (!(xx > 0.0) || !(m2 > 0.0) || !(det > 0.0) || !std::isfinite(det))                      // (Sylvester's criterion)
+        return fail(SPH_ERR_ARG, "obstacle %d: the inertia tensor is not positive definite", index);
+    const double inv[6] = {c00 / det, (xx * zz - xz * xz) / det, m2 / det, c01 / det, c02 / det, (xy * xz - xx * yz) / det};
+    std::memset(&r, 0, sizeof(r));
+    r.active = 1;
+    r.mass = d.mass;
+    for (int a = 0; a < 6; ++a) { r.I[a] = d.inertia[a]; r.Iinv[a] = (float)inv[a]; }
+    if (!obs_all_finite(r.Iinv, 6)) return fail(SPH_ERR_ARG, "obstacle %d: the inverse inertia is not finite in fp32", index);
+    for (int a = 0; a < 3; ++a) { r.com[a] = d.com[a]; r.force[a] = d.force[a]; r.torque[a] = d.torque[a]; }
+    r.gscale = d.gravityScale;
+    r.ldamp = d.linearDamping; r.adamp = d.angularDamping;
+    r.flags = d.flags;
+    return SPH_OK;
+}
+
+int sph_obstacles_set_dynamics(SphEngine* e, int index, const SphObstacleDynamics* dyn) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    int rc;
+    sph::ObsDyn rec;
+    std::memset(&rec, 0, sizeof(rec));
+    if (dyn && (rc = dynamics_to_rec(*dyn, index, rec))) return rc;
+    const int i = e->dynSlot;
+    e->dynSlot = (i + 1) % SphEngine::kObsSlots;
+    HIP_TRY(hipEventSynchronize(e->evDyn[i]));
+    e->h_dynStage[i] = rec;
+    HIP_TRY(hipMemcpyAsync(&e->d_dyn[index], &e->h_dynStage[i], sizeof(sph::ObsDyn), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->evDyn[i], e->stream));
+    const bool on = dyn != nullptr;
+    e->dynCount += (on ? 1 : 0) - (e->dynOn[index] ? 1 : 0);
+    e->dynOn[index] = on;
+    if (on) e->dynSet[index] = *dyn;
+    return SPH_OK;
+}
+
+int sph_obstacles_get_dynamics(SphEngine* e, int index, SphObstacleDynamics* out, int* dynamicOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    if (out) {
+        if (e->dynOn[index]) *out = e->dynSet[index];
+        else sph_obstacle_dynamics_default(out);
+    }
+    if (dynamicOut) *dynamicOut = e->dynOn[index] ? 1 : 0;
+    return SPH_OK;
+}
+
+int sph_obstacles_step_host(SphObstacle* obs, const SphObstacleDynamics* dyn, int count, const double* impulses6, const SphParams* params, float dt) {
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (!params || (count && !dyn)) return fail(SPH_ERR_ARG, "null argument");
+    if (!std::isfinite(dt)) return fail(SPH_ERR_ARG, "dt not finite");
+    sph::ObsDyn recs[kObsMax];
+    for (int i = 0; i < count; ++i) {
+        std::memset(&recs[i], 0, sizeof(recs[i]));
+        if (dyn[i].mass != 0.0f && (rc = dynamics_to_rec(dyn[i], i, recs[i]))) return rc;
+    }
+    sph::ObsWorld W;
+    obstacle_world(*params, W);
+    const double zero[kObsTerms] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < count; ++i) {
+        sph::ObsRec r;
+        obstacle_to_rec(obs[i], false, r);
+        if (recs[i].active) sph::obs_body_step(r, recs[i], impulses6 ? impulses6 + (size_t)i * kObsTerms : zero, W, dt);
+        else sph::obs_advance(r, dt);
+        rec_to_obstacle(r, obs[i]);
+    }
+    return SPH_OK;
+}
+
 // ---- volumes: signed distance lattices as bodies, mesh -> signed distance (sph_volume.h) ---------
 static int volume_check_lattice(const int dims[3], const float spacing[3], long long* totalOut, int least = 2) {
     if (!dims || !spacing) return fail(SPH_ERR_ARG, "null argument");
@@ -2981,6 +3119,45 @@ int sph_volume_info(SphEngine* e, int id, int dimsOut[3], float spacingOut[3], f
         if (spacingOut) spacingOut[a] = e->vols[id].spacing[a];
         if (halfOut) halfOut[a] = e->volTab.vol[id].half[a];
     }
+    return SPH_OK;
+}
+
+int sph_volume_moments(SphEngine* e, int id, double out[10]) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = volume_slot_check(e, id))) return rc;
+    if (!e->d_momPart && ((rc = dev_alloc(&e->d_momPart, (size_t)kMomGrid * kMomTerms)) || (rc = dev_alloc(&e->d_momOut, (size_t)kMomTerms)))) return rc;
+    const sph::VolRec& v = e->volTab.vol[id];
+    const long long total = (long long)v.dims[0] * v.dims[1] * v.dims[2];
+    const int rows = (int)std::min<long long>(kMomGrid, (total + kMomSweep - 1) / kMomSweep);
+    const double cell = ((double)v.spacing[0] * (double)v.spacing[1]) * (double)v.spacing[2];
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_volume_moments, dim3(rows), dim3(kMomBlock), 0, e->stream, v, sph::vol_diagonal(v.spacing), (unsigned)total, e->d_momPart);
+        hipLaunchKernelGGL(k_volume_moments_finish, dim3(1), dim3(kMomFinishBlock), 0, e->stream, (const double*)e->d_momPart, rows, cell, e->d_momOut);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, e->d_momOut, sizeof(double) * kMomTerms, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_volume_moments_host(const float* values, const int dims[3], const float spacing[3], double out[10]) {
+    if (!values || !out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = volume_check_lattice(dims, spacing, nullptr))) return rc;
+    sph::VolRec v;
+    sph::vol_make(values, dims, spacing, v);
+    const float diag = sph::vol_diagonal(v.spacing);
+    double t[kMomTerms] = {0.0};
+    size_t p = 0;
+    for (int k = 0; k < dims[2]; ++k)
+        for (int j = 0; j < dims[1]; ++j)
+            for (int i = 0; i < dims[0]; ++i, ++p)
+                sph::vol_moment_terms(values[p], diag, (float)i * v.spacing[0] - v.half[0], (float)j * v.spacing[1] - v.half[1],
+                                      (float)k * v.spacing[2] - v.half[2], t);
+    const double cell = ((double)spacing[0] * (double)spacing[1]) * (double)spacing[2];
+    for (int c = 0; c < kMomTerms; ++c) out[c] = t[c] * cell;
     return SPH_OK;
 }
 

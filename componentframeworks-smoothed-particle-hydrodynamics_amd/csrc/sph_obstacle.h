@@ -13,6 +13,8 @@
 //                       wave-uniform addresses like the bodies, the eight corner loads per evaluation are the only gathers.
 //   k_obstacles_finish  one block: the partial rows summed in a fixed order (contiguous ranges, each ascending, then the ranges in order)
 //                       into the accumulators, time += dt, substeps += 1, and every pose advanced by one substep.
+//   k_obstacles_finish_dyn  k_obstacles_finish for a set with at least one dynamic body: the same sums, and body b
+//                       stepped by thread b with this substep's own sums (obs_body_step) instead of only advanced.
 // The bodies and the accumulators live in device memory, never in launch arguments, so a replayed graph sees every later
 // sph_obstacles_set / _set_motion.  No float atomic is used: the sums depend on the slot order of the state (cell, id) only.
 #pragma once
@@ -336,6 +338,194 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles_vol(const ObsRec* __res
         double r = sacc[0][i];
         for (int w = 1; w < kObsWaves; ++w) r += sacc[w][i];
         part[(size_t)blockIdx.x * kObsRow + i] = r;
+    }
+}
+
+// ---- dynamic bodies ---------------------------------------------------------
+// A body with a dynamics record moves under the substep's own sums (J, L): k_obstacles_finish_dyn is launched instead of
+// k_obstacles_finish while at least one body has a record (k_obstacles_finish itself stays what it is for kinematic sets).  The body step
+// (obs_body_step) is __host__ __device__ and is what sph_obstacles_step_host runs.  fp32, every operation rounded on its own except
+// obs_dot3; the J and L terms are fp64.
+struct ObsDyn {                              // 128 bytes, one per body, beside ObsRec
+    int32_t active;                          // 0: kinematic
+    float mass;
+    float I[6], Iinv[6];                     // xx, yy, zz, xy, xz, yz about the centre of mass, body frame; Iinv inverted in fp64 on set
+    float com[3];
+    float gscale;
+    float force[3], torque[3];
+    float ldamp, adamp;
+    uint32_t flags;                          // bit 0: confined by the container
+    float pad[5];
+};
+static_assert(sizeof(ObsDyn) == 128, "ObsDyn must be 128 bytes");
+enum : uint32_t { OBS_DYN_CONFINED = 1u };
+
+// What the body step needs of the scene: gravity, the container's oriented box (axis j in world coordinates is A[3 j .. 3 j + 2]) and
+// the wall restitution.
+struct ObsWorld {
+    float g[3];
+    float bc[3];
+    float A[9];
+    float half[3];
+    float rest;
+};
+
+// M (S (M^T x)) for a symmetric S = (xx, yy, zz, xy, xz, yz) in the body frame: three rows of obs_dot3 each.
+__host__ __device__ inline void obs_sym_world(const float* M, const float* S, const float (&x)[3], float (&out)[3]) {
+    const float l0 = obs_dot3(x[0], x[1], x[2], M[0], M[3], M[6]);
+    const float l1 = obs_dot3(x[0], x[1], x[2], M[1], M[4], M[7]);
+    const float l2 = obs_dot3(x[0], x[1], x[2], M[2], M[5], M[8]);
+    const float s0 = obs_dot3(S[0], S[3], S[4], l0, l1, l2);
+    const float s1 = obs_dot3(S[3], S[1], S[5], l0, l1, l2);
+    const float s2 = obs_dot3(S[4], S[5], S[2], l0, l1, l2);
+    out[0] = obs_dot3(M[0], M[1], M[2], s0, s1, s2);
+    out[1] = obs_dot3(M[3], M[4], M[5], s0, s1, s2);
+    out[2] = obs_dot3(M[6], M[7], M[8], s0, s1, s2);
+}
+__host__ __device__ inline void obs_cross(const float (&a)[3], const float (&b)[3], float (&out)[3]) {
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Support points of a body in its own frame (fixed order) and their radius.
+__host__ __device__ inline int obs_support(const ObsRec& B, float (&lp)[8][3], float& rad) {
+    if (B.shape == OBS_SPHERE) { lp[0][0] = 0.0f; lp[0][1] = 0.0f; lp[0][2] = 0.0f; rad = B.size[0]; return 1; }
+    if (B.shape == OBS_CAPSULE) {
+        lp[0][0] = 0.0f; lp[0][1] = -B.size[1]; lp[0][2] = 0.0f;
+        lp[1][0] = 0.0f; lp[1][1] = B.size[1]; lp[1][2] = 0.0f;
+        rad = B.size[0];
+        return 2;
+    }
+    for (int i = 0; i < 8; ++i) {            // corner i: bit 0 -> +x, bit 1 -> +y, bit 2 -> +z
+        lp[i][0] = (i & 1) ? B.size[0] : -B.size[0];
+        lp[i][1] = (i & 2) ? B.size[1] : -B.size[1];
+        lp[i][2] = (i & 4) ? B.size[2] : -B.size[2];
+    }
+    rad = 0.0f;
+    return 8;
+}
+
+// One substep of a dynamic body: S = (J, L) of this substep about the geometric centre.
+__host__ __device__ inline void obs_body_step(ObsRec& B, const ObsDyn& D, const double* S, const ObsWorld& W, float dt) {
+    const float* M = B.M;
+    // 1. to the centre of mass
+    float o[3];
+    o[0] = obs_dot3(M[0], M[1], M[2], D.com[0], D.com[1], D.com[2]);
+    o[1] = obs_dot3(M[3], M[4], M[5], D.com[0], D.com[1], D.com[2]);
+    o[2] = obs_dot3(M[6], M[7], M[8], D.com[0], D.com[1], D.com[2]);
+    const double O0 = (double)o[0], O1 = (double)o[1], O2 = (double)o[2];
+    float Lg[3];
+    Lg[0] = (float)(S[3] - (O1 * S[2] - O2 * S[1]));
+    Lg[1] = (float)(S[4] - (O2 * S[0] - O0 * S[2]));
+    Lg[2] = (float)(S[5] - (O0 * S[1] - O1 * S[0]));
+    float w[3] = {B.w[0], B.w[1], B.w[2]};
+    float x[3], Vg[3];
+    obs_cross(w, o, x);
+    for (int a = 0; a < 3; ++a) Vg[a] = B.v[a] + x[a];
+    // 2. linear velocity
+    for (int a = 0; a < 3; ++a) {
+        const float acc = D.gscale * W.g[a] + D.force[a] / D.mass;
+        Vg[a] = (Vg[a] + (float)(S[a] / (double)D.mass)) + dt * acc;
+    }
+    // 3. angular velocity
+    {
+        float Iw[3], gy[3], rhs[3], dw[3];
+        obs_sym_world(M, D.I, w, Iw);
+        obs_cross(w, Iw, gy);
+        for (int a = 0; a < 3; ++a) rhs[a] = Lg[a] + dt * (D.torque[a] - gy[a]);
+        obs_sym_world(M, D.Iinv, rhs, dw);
+        for (int a = 0; a < 3; ++a) w[a] = w[a] + dw[a];
+    }
+    // 4. damping
+    {
+        const float fl = fmaxf(0.0f, 1.0f - D.ldamp * dt), fa = fmaxf(0.0f, 1.0f - D.adamp * dt);
+        for (int a = 0; a < 3; ++a) { Vg[a] = Vg[a] * fl; w[a] = w[a] * fa; }
+    }
+    // 5. container contact at the entry pose: faces -x, +x, -y, +y, -z, +z, support points in order
+    if (D.flags & OBS_DYN_CONFINED) {
+        float lp[8][3], rad;
+        const int np = obs_support(B, lp, rad);
+        float pen[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        const float im = 1.0f / D.mass, ope = 1.0f + W.rest;
+        for (int f = 0; f < 6; ++f) {
+            const int j = f >> 1;
+            const float sg = (f & 1) ? -1.0f : 1.0f;                 // inward normal: +axis at the low face, -axis at the high face
+            const float n[3] = {sg * W.A[3 * j], sg * W.A[3 * j + 1], sg * W.A[3 * j + 2]};
+            for (int p = 0; p < np; ++p) {
+                float s[3], r[3], d[3];
+                s[0] = obs_dot3(M[0], M[1], M[2], lp[p][0], lp[p][1], lp[p][2]);
+                s[1] = obs_dot3(M[3], M[4], M[5], lp[p][0], lp[p][1], lp[p][2]);
+                s[2] = obs_dot3(M[6], M[7], M[8], lp[p][0], lp[p][1], lp[p][2]);
+                for (int a = 0; a < 3; ++a) { r[a] = s[a] - o[a]; d[a] = (B.c[a] + s[a]) - W.bc[a]; }
+                const float dist = W.half[j] + obs_dot3(d[0], d[1], d[2], n[0], n[1], n[2]);   // distance of the point from the face, inward
+                const float depth = rad - dist;
+                if (!(depth >= 0.0f)) continue;                       // (touching counts: a body at rest on a face stays in contact)
+                if (depth > pen[f]) pen[f] = depth;
+                float wr[3], rn[3], k3[3], kr[3];
+                obs_cross(w, r, wr);
+                const float vn = obs_dot3(Vg[0] + wr[0], Vg[1] + wr[1], Vg[2] + wr[2], n[0], n[1], n[2]);
+                if (!(vn < 0.0f)) continue;
+                obs_cross(r, n, rn);
+                obs_sym_world(M, D.Iinv, rn, k3);
+                obs_cross(k3, r, kr);
+                const float den = im + obs_dot3(n[0], n[1], n[2], kr[0], kr[1], kr[2]);
+                const float jn = (-ope * vn) / den;
+                const float jm = jn * im;
+                for (int a = 0; a < 3; ++a) { Vg[a] = Vg[a] + jm * n[a]; w[a] = w[a] + jn * k3[a]; }
+            }
+        }
+        for (int f = 0; f < 6; ++f) {
+            if (!(pen[f] > 0.0f)) continue;
+            const int j = f >> 1;
+            const float sg = (f & 1) ? -1.0f : 1.0f;
+            for (int a = 0; a < 3; ++a) B.c[a] = B.c[a] + pen[f] * (sg * W.A[3 * j + a]);
+        }
+    }
+    // 6. back to the geometric centre, 7. the pose advance with the new velocities
+    obs_cross(w, o, x);
+    for (int a = 0; a < 3; ++a) { B.v[a] = Vg[a] - x[a]; B.w[a] = w[a]; }
+    obs_advance(B, dt);
+}
+
+// k_obstacles_finish for a set with at least one dynamic body (launched only then).  The sums are formed exactly as k_obstacles_finish
+// forms them; this substep's sums also go to LDS, and thread b steps body b with them (obs_body_step) or, for a kinematic body, advances it.
+__global__ __launch_bounds__(kObsFinishBlock) void k_obstacles_finish_dyn(ObsRec* __restrict__ bodies, const ObsDyn* __restrict__ dyn, ObsWorld W, int K,
+                                                                          float dt, const double* __restrict__ part, int rows, ObsAcc* __restrict__ acc) {
+    __shared__ double sums[kObsFinishBlock];
+    __shared__ double sub[kObsRow];
+    const int terms = K * kObsTerms, chunks = max(1, min(kObsFinishBlock / max(terms, 1), rows));
+    const int t = threadIdx.x, c = t % max(terms, 1), ch = t / max(terms, 1);
+    if (ch < chunks && c < terms) {
+        const int per = (rows + chunks - 1) / chunks;
+        const int r1 = min(rows, (ch + 1) * per);
+        int r = ch * per;
+        double s = 0.0;
+        for (; r + kObsBatch <= r1; r += kObsBatch) {
+            double v[kObsBatch];
+#pragma unroll
+            for (int j = 0; j < kObsBatch; ++j) v[j] = part[(size_t)(r + j) * kObsRow + c];
+#pragma unroll
+            for (int j = 0; j < kObsBatch; ++j) s += v[j];
+        }
+        for (; r < r1; ++r) s += part[(size_t)r * kObsRow + c];
+        sums[ch * terms + c] = s;
+    }
+    __syncthreads();
+    if (t < terms) {
+        double s = sums[t];
+        for (int k = 1; k < chunks; ++k) s += sums[k * terms + t];
+        sub[t] = s;
+        acc->J[t] += s;
+    }
+    if (t == 0) { acc->time += (double)dt; acc->substeps += 1ull; }
+    __syncthreads();
+    if (t < K) {
+        ObsRec B = bodies[t];
+        const ObsDyn D = dyn[t];
+        if (D.active) obs_body_step(B, D, sub + t * kObsTerms, W, dt);
+        else obs_advance(B, dt);
+        bodies[t] = B;
     }
 }
 

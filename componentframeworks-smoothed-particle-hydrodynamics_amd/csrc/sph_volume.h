@@ -248,4 +248,103 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_merge(const float* __restri
     out[p] = mesh_signed(best, angles);
 }
 
+// ---- moments of a lattice body --------------------------------------------
+// Sum over the lattice points of w {1, x, y, z, xx, yy, zz, xy, xz, yz}: x, y, z the fp32 local coordinates widened to fp64,
+// w = clamp(0.5f - phi / D, 0, 1) with D the fp32 cell diagonal (a NaN phi weighs 0), the products in fp64 from the left.
+//   k_volume_moments         a FIXED grid (min(kMomGrid, sweeps for the point count)) of sweeps of kMomSweep points: a thread takes four
+//                            consecutive points per float4 load, kMomUnroll loads in flight; ten fp64 sums per thread, an xor butterfly per
+//                            wave, the waves of a block in order, one partial row per block.
+//   k_volume_moments_finish  one block: thread (chunk, term) sums a contiguous range of rows in ascending order, thread `term` the chunks
+//                            in order, times the cell volume.
+// No float atomic: the bits depend on the lattice only.
+constexpr int kMomTerms = 10;
+constexpr int kMomBlock = 256;
+constexpr int kMomVec = 4;                   // consecutive points per thread and load (one float4)
+constexpr int kMomUnroll = 2;                // float4 loads in flight per thread
+constexpr int kMomSweep = kMomBlock * kMomUnroll * kMomVec;
+constexpr int kMomGrid = 1024;               // rows of the partial slab at most (4 blocks per compute unit)
+constexpr int kMomWaves = kMomBlock / 64;
+constexpr int kMomFinishBlock = 1024;
+constexpr int kMomChunks = kMomFinishBlock / kMomTerms;
+
+__host__ __device__ inline float vol_diagonal(const float* spacing) {
+    return sqrtf(vol_dot3(spacing[0], spacing[1], spacing[2], spacing[0], spacing[1], spacing[2]));
+}
+// The ten terms of one lattice point added to t.
+__host__ __device__ inline void vol_moment_terms(float phi, float diag, float lx, float ly, float lz, double (&t)[kMomTerms]) {
+    const float wf = fminf(fmaxf(0.5f - phi / diag, 0.0f), 1.0f);
+    const double w = (double)wf, x = (double)lx, y = (double)ly, z = (double)lz;
+    const double wx = w * x, wy = w * y, wz = w * z;
+    t[0] += w; t[1] += wx; t[2] += wy; t[3] += wz;
+    t[4] += wx * x; t[5] += wy * y; t[6] += wz * z;
+    t[7] += wx * y; t[8] += wx * z; t[9] += wy * z;
+}
+
+__global__ __launch_bounds__(kMomBlock) void k_volume_moments(VolRec v, float diag, unsigned total, double* __restrict__ part) {
+    __shared__ double sacc[kMomWaves][kMomTerms];
+    double t[kMomTerms];
+#pragma unroll
+    for (int c = 0; c < kMomTerms; ++c) t[c] = 0.0;
+    const unsigned nx = (unsigned)v.dims[0], ny = (unsigned)v.dims[1];
+    for (unsigned long long base = (unsigned long long)blockIdx.x * kMomSweep; base < total; base += (unsigned long long)gridDim.x * kMomSweep) {   // (block-uniform)
+        float phi[kMomUnroll][kMomVec];
+#pragma unroll
+        for (int j = 0; j < kMomUnroll; ++j) {
+            const unsigned long long p0 = base + (unsigned long long)(j * kMomBlock + (int)threadIdx.x) * kMomVec;
+            if (p0 + kMomVec <= total) {                             // (the lattice starts on an allocation boundary: p0 is a multiple of four)
+                const float4 q = *reinterpret_cast<const float4*>(v.values + p0);
+                phi[j][0] = q.x; phi[j][1] = q.y; phi[j][2] = q.z; phi[j][3] = q.w;
+            } else {
+#pragma unroll
+                for (int u = 0; u < kMomVec; ++u) phi[j][u] = p0 + u < total ? v.values[p0 + u] : INFINITY;   // (beyond the lattice: weight 0)
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kMomUnroll; ++j) {
+            const unsigned long long p0 = base + (unsigned long long)(j * kMomBlock + (int)threadIdx.x) * kMomVec;
+            if (p0 >= total) continue;
+            const unsigned p = (unsigned)p0, row = p / nx, k0 = row / ny;
+            unsigned i = p - row * nx, jj = row - k0 * ny, k = k0;     // one division pair per four points, then a carry
+#pragma unroll
+            for (int u = 0; u < kMomVec; ++u) {
+                if (p0 + u < total)
+                    vol_moment_terms(phi[j][u], diag, (float)i * v.spacing[0] - v.half[0], (float)jj * v.spacing[1] - v.half[1],
+                                     (float)k * v.spacing[2] - v.half[2], t);
+                if (++i == nx) { i = 0; if (++jj == ny) { jj = 0; ++k; } }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kMomTerms; ++c)
+        for (int o = 32; o >= 1; o >>= 1) t[c] += __shfl_xor(t[c], o, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0)
+        for (int c = 0; c < kMomTerms; ++c) sacc[wave][c] = t[c];
+    __syncthreads();
+    if (threadIdx.x < kMomTerms) {
+        double r = sacc[0][threadIdx.x];
+        for (int w = 1; w < kMomWaves; ++w) r += sacc[w][threadIdx.x];
+        part[(size_t)blockIdx.x * kMomTerms + threadIdx.x] = r;
+    }
+}
+
+__global__ __launch_bounds__(kMomFinishBlock) void k_volume_moments_finish(const double* __restrict__ part, int rows, double cell, double* __restrict__ out) {
+    __shared__ double sums[kMomChunks * kMomTerms];
+    const int chunks = max(1, min(kMomChunks, rows));
+    const int t = threadIdx.x, c = t % kMomTerms, ch = t / kMomTerms;
+    if (ch < chunks) {
+        const int per = (rows + chunks - 1) / chunks;
+        const int r1 = min(rows, (ch + 1) * per);
+        double s = 0.0;
+        for (int r = ch * per; r < r1; ++r) s += part[(size_t)r * kMomTerms + c];
+        sums[ch * kMomTerms + c] = s;
+    }
+    __syncthreads();
+    if (t < kMomTerms) {
+        double s = sums[t];
+        for (int k = 1; k < chunks; ++k) s += sums[k * kMomTerms + t];
+        out[t] = s * cell;
+    }
+}
+
 }  // namespace sph

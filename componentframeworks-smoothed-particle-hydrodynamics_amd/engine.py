@@ -117,6 +117,8 @@ ABI_SYMBOLS = (
     "sph_obstacles_apply_host", "sph_obstacles_advance_host",
     "sph_volume_create", "sph_volume_destroy", "sph_volume_info", "sph_volume_sample_host", "sph_obstacles_bind_volume", "sph_obstacles_volume",
     "sph_obstacles_apply_host_volumes", "sph_mesh_distance", "sph_mesh_distance_host", "sph_volume_from_mesh",
+    "sph_obstacle_dynamics_default", "sph_obstacles_set_dynamics", "sph_obstacles_get_dynamics", "sph_obstacles_step_host",
+    "sph_volume_moments", "sph_volume_moments_host",
 )
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -195,6 +197,96 @@ def obstacle_array(obstacles) -> np.ndarray:
     if not obstacles:
         return np.zeros(0, OBSTACLE_DTYPE)
     return np.frombuffer(b"".join(bytes(o) for o in obstacles), OBSTACLE_DTYPE).copy()
+
+
+class SphObstacleDynamics(C.Structure):
+    """struct SphObstacleDynamics of include/sph_abi.h: what makes a body of the obstacle set dynamic (see dynamics() and
+    SPHFluidGPU.set_obstacle_dynamics)."""
+    _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 6), ("com", C.c_float * 3), ("gravityScale", C.c_float),
+                ("force", C.c_float * 3), ("torque", C.c_float * 3), ("linearDamping", C.c_float), ("angularDamping", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+assert C.sizeof(SphObstacleDynamics) == 80
+DYNAMICS_DTYPE = np.dtype([("mass", "<f4"), ("inertia", "<f4", (6,)), ("com", "<f4", (3,)), ("gravityScale", "<f4"), ("force", "<f4", (3,)),
+                           ("torque", "<f4", (3,)), ("linearDamping", "<f4"), ("angularDamping", "<f4"), ("flags", "<u4")])
+assert DYNAMICS_DTYPE.itemsize == 80
+SPH_DYNAMICS_CONFINED = 1
+
+
+def dynamics(mass, inertia, com=(0.0, 0.0, 0.0), gravity_scale: float = 1.0, force=(0.0, 0.0, 0.0), torque=(0.0, 0.0, 0.0),
+             linear_damping: float = 0.0, angular_damping: float = 0.0, confined: bool = True) -> SphObstacleDynamics:
+    """One dynamics record.  inertia about the centre of mass in the body frame: 3 numbers (the diagonal),
+    6 (xx, yy, zz, xy, xz, yz) or a symmetric 3 x 3 array."""
+    I = np.asarray(inertia, np.float64)
+    if I.shape == (3, 3):
+        I = np.array([I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]])
+    elif I.shape == (3,):
+        I = np.concatenate([I, np.zeros(3)])
+    if I.shape != (6,):
+        raise SphError(f"dynamics: inertia of shape {np.shape(inertia)}")
+    d = SphObstacleDynamics()
+    d.mass = float(mass)
+    d.inertia[:] = [float(x) for x in I]
+    for field, val in (("com", com), ("force", force), ("torque", torque)):
+        vals = [float(x) for x in val]
+        if len(vals) != 3:
+            raise SphError(f"dynamics: {field} needs 3 components, not {len(vals)}")
+        getattr(d, field)[:] = vals
+    d.gravityScale = float(gravity_scale)
+    d.linearDamping = float(linear_damping)
+    d.angularDamping = float(angular_damping)
+    d.flags = SPH_DYNAMICS_CONFINED if confined else 0
+    return d
+
+
+def dynamics_sphere(density: float, size, **kw) -> SphObstacleDynamics:
+    """A homogeneous sphere of radius size (or size[0]): m = 4/3 pi R^3 rho, I = 2/5 m R^2."""
+    R = float(size if np.ndim(size) == 0 else size[0])
+    m = density * 4.0 / 3.0 * math.pi * R ** 3
+    return dynamics(m, [0.4 * m * R * R] * 3, **kw)
+
+
+def dynamics_box(density: float, size, **kw) -> SphObstacleDynamics:
+    """A homogeneous box of half extents size: m = 8 a b c rho, I_xx = m (b^2 + c^2) / 3 and so on."""
+    a, b, c = (float(x) for x in size)
+    m = density * 8.0 * a * b * c
+    return dynamics(m, [m * (b * b + c * c) / 3.0, m * (a * a + c * c) / 3.0, m * (a * a + b * b) / 3.0], **kw)
+
+
+def dynamics_capsule(density: float, size, **kw) -> SphObstacleDynamics:
+    """A homogeneous capsule, size = (radius r, half length L of the core segment along local y): a cylinder of length 2 L and two
+    half spheres, the half spheres' transverse moments by the parallel-axis rule from their own centroids (3 r / 8 beyond the ends)."""
+    r, L = float(size[0]), float(size[1])
+    mc = density * math.pi * r * r * 2.0 * L
+    mh = density * 2.0 / 3.0 * math.pi * r ** 3                       # one half sphere
+    iy = 0.5 * mc * r * r + 2.0 * (0.4 * mh * r * r)
+    it = mc * (3.0 * r * r + 4.0 * L * L) / 12.0 + 2.0 * (mh * (0.4 - 9.0 / 64.0) * r * r + mh * (L + 0.375 * r) ** 2)
+    return dynamics(mc + 2.0 * mh, [it, iy, it], **kw)
+
+
+def dynamics_array(records) -> np.ndarray:
+    """A list of SphObstacleDynamics (None: a kinematic body, mass 0) as a contiguous DYNAMICS_DTYPE array."""
+    if isinstance(records, np.ndarray):
+        return np.ascontiguousarray(records, DYNAMICS_DTYPE)
+    records = list(records)
+    if not records:
+        return np.zeros(0, DYNAMICS_DTYPE)
+    return np.frombuffer(b"".join(bytes(SphObstacleDynamics()) if r is None else bytes(r) for r in records), DYNAMICS_DTYPE).copy()
+
+
+def mass_properties(moments, density: float):
+    """(mass, centre of mass[3], inertia about it as (xx, yy, zz, xy, xz, yz)) from the ten moments of sph_volume_moments, by the
+    parallel-axis rule in fp64."""
+    m = np.asarray(moments, np.float64)
+    if m.shape != (10,) or not m[0] > 0:
+        raise SphError("mass_properties: ten moments with a positive volume are needed")
+    vol = m[0]
+    c = m[1:4] / vol
+    sxx, syy, szz = m[4] - vol * c[0] * c[0], m[5] - vol * c[1] * c[1], m[6] - vol * c[2] * c[2]
+    sxy, sxz, syz = m[7] - vol * c[0] * c[1], m[8] - vol * c[0] * c[2], m[9] - vol * c[1] * c[2]
+    inertia = density * np.array([syy + szz, sxx + szz, sxx + syy, -sxy, -sxz, -syz])
+    return float(density * vol), c, inertia
 
 
 class SphVolumeHost(C.Structure):
@@ -483,10 +575,17 @@ def load_library(build_if_missing: bool = True) -> C.CDLL:
     L.sph_mesh_distance.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
     L.sph_volume_from_mesh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, i3]
     L.sph_mesh_distance_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
+    L.sph_obstacle_dynamics_default.argtypes = [vp]
+    L.sph_obstacle_dynamics_default.restype = None
+    L.sph_obstacles_set_dynamics.argtypes = [vp, C.c_int, vp]
+    L.sph_obstacles_get_dynamics.argtypes = [vp, C.c_int, vp, i3]
+    L.sph_obstacles_step_host.argtypes = [vp, vp, C.c_int, vp, pp, C.c_float]
+    L.sph_volume_moments.argtypes = [vp, C.c_int, vp]
+    L.sph_volume_moments_host.argtypes = [vp, i3, f3, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count",
-                        "sph_obstacle_default"):
+                        "sph_obstacle_default", "sph_obstacle_dynamics_default"):
             fn.restype = C.c_int
     _lib = L
     return L
@@ -1047,6 +1146,29 @@ class SPHFluidGPU:
         """Body `index` (a box) takes its shape from the volume (volume_id < 0 unbinds).  set_obstacles clears every binding."""
         _check(self._L.sph_obstacles_bind_volume(self._h, int(index), int(volume_id)))
 
+    # -- dynamic rigid bodies (include/sph_abi.h "dynamic rigid bodies") -------------------------------
+    def set_obstacle_dynamics(self, index: int, record=None):
+        """Body `index` moves under the fluid's impulses, gravity and the container from the next substep on (a dynamics() record; None:
+        kinematic again).  Stream-ordered; a replayed graph sees it.  set_obstacles clears every record."""
+        _check(self._L.sph_obstacles_set_dynamics(self._h, int(index), C.byref(record) if record is not None else None))
+
+    def obstacle_dynamics(self, index: int):
+        """The record of body `index` as set, or None for a kinematic body."""
+        out, on = SphObstacleDynamics(), C.c_int()
+        _check(self._L.sph_obstacles_get_dynamics(self._h, int(index), C.byref(out), C.byref(on)))
+        return out if on.value else None
+
+    def volume_moments(self, volume_id: int) -> np.ndarray:
+        """The ten moments of the solid a volume describes (sph_volume_moments): cell volume times the weighted sums of
+        1, x, y, z, xx, yy, zz, xy, xz, yz.  Synchronises."""
+        out = np.zeros(10, np.float64)
+        _check(self._L.sph_volume_moments(self._h, int(volume_id), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def volume_mass_properties(self, volume_id: int, density: float):
+        """(mass, centre of mass in the body frame, inertia about it as xx, yy, zz, xy, xz, yz) of a homogeneous body shaped by the volume."""
+        return mass_properties(self.volume_moments(volume_id), density)
+
     def obstacle_volume(self, index: int) -> int:
         vid = C.c_int(-1)
         _check(self._L.sph_obstacles_volume(self._h, int(index), C.byref(vid)))
@@ -1145,6 +1267,28 @@ def obstacles_advance_host(obstacles, dt: float) -> np.ndarray:
     arr = obstacle_array(obstacles).copy()
     _check(load_library().sph_obstacles_advance_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(dt)))
     return arr
+
+
+def obstacles_step_host(obstacles, records, impulses, params, dt: float) -> np.ndarray:
+    """sph_obstacles_step_host on a copy: the bodies after the body step of one substep.  records: one
+    dynamics() record or None per body; impulses: the substep's (K, 6) sums or None.  No device is needed."""
+    arr = obstacle_array(obstacles).copy()
+    dyn = dynamics_array(records)
+    if len(dyn) != len(arr):
+        raise SphError(f"{len(dyn)} dynamics records for {len(arr)} obstacles")
+    imp = None if impulses is None else np.ascontiguousarray(impulses, np.float64).reshape(len(arr), 6)
+    _check(load_library().sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, dyn.ctypes.data_as(C.c_void_p) if len(arr) else None,
+                                                  len(arr), imp.ctypes.data_as(C.c_void_p) if imp is not None and len(arr) else None,
+                                                  C.byref(params), float(dt)))
+    return arr
+
+
+def volume_moments_host(values, spacing) -> np.ndarray:
+    """sph_volume_moments_host of a (nz, ny, nx) lattice: the ten moments.  No device is needed."""
+    v, dims, sp = _volume_lattice(values, spacing)
+    out = np.zeros(10, np.float64)
+    _check(load_library().sph_volume_moments_host(v.ctypes.data_as(C.c_void_p), dims, _f3(sp), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def volume_sample_host(values, spacing, local):

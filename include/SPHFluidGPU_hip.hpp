@@ -285,6 +285,20 @@ public:
         half = MATH::Vec3(h[0], h[1], h[2]);
         return true;
     }
+    // Dynamic rigid bodies (engine extension, sph_abi.h "dynamic rigid bodies"): a body with a dynamics record moves
+    // under the fluid's impulses, gravity and the container, on the device, inside the substep.  SetObstacleDynamics(index, nullptr)
+    // makes the body kinematic again; SetObstacles clears every record.  VolumeMoments returns the ten moments of the solid a volume
+    // describes (cell volume times the weighted sums of 1, x, y, z, xx, yy, zz, xy, xz, yz), for the mass properties of a mesh body.
+    bool SetObstacleDynamics(int index, const SphObstacleDynamics* dyn) {
+        return !Check(sph_obstacles_set_dynamics(engine, index, dyn), "sph_obstacles_set_dynamics");
+    }
+    bool GetObstacleDynamics(int index, SphObstacleDynamics& out, bool& dynamic) {
+        int on = 0;
+        if (Check(sph_obstacles_get_dynamics(engine, index, &out, &on), "sph_obstacles_get_dynamics")) return false;
+        dynamic = on != 0;
+        return true;
+    }
+    bool VolumeMoments(int id, double out[10]) { return !Check(sph_volume_moments(engine, id, out), "sph_volume_moments"); }
     bool DestroyVolume(int id) { return !Check(sph_volume_destroy(engine, id), "sph_volume_destroy"); }
     bool BindObstacleVolume(int index, int id) { return !Check(sph_obstacles_bind_volume(engine, index, id), "sph_obstacles_bind_volume"); }
     bool MeshDistance(const std::vector<float>& vertices3, const std::vector<uint32_t>& triangles3, const MATH::Vec3& origin, const MATH::Vec3& spacing,

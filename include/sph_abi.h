@@ -39,6 +39,8 @@ extern "C" {
     _apply_host / _advance_host -- kinematic solid obstacles) */
 /* (still 4, additions only: SphVolumeHost, SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, sph_volume_create / _destroy / _info / _sample_host / _from_mesh,
     sph_obstacles_bind_volume / _volume / _apply_host_volumes, sph_mesh_distance / _host -- triangle-mesh obstacles through signed distance lattices) */
+/* (still 4, additions only: SphObstacleDynamics, SPH_DYNAMICS_CONFINED, sph_obstacle_dynamics_default, sph_obstacles_set_dynamics / _get_dynamics /
+    _step_host, sph_volume_moments / _host -- dynamic rigid bodies) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -523,6 +525,51 @@ int  sph_volume_from_mesh(SphEngine* e, const float* vertices3, size_t nv, const
                           const float spacing[3], const int dims[3], int* idOut);
 int  sph_mesh_distance_host(const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float origin[3], const float spacing[3],
                             const int dims[3], float* out);
+
+/* ---- dynamic rigid bodies: obstacles moved by the fluid (no reference counterpart) ---------------------
+ * A body of the obstacle set with a dynamics record is DYNAMIC: at the end of every substep the engine, on the device, turns the
+ * substep's own sums (J, L) of that body into new velocities and advances the pose with them:
+ *   o = M com, L_g = L - o x J (fp64), V_g = V + omega x o;  V_g += (float)(J / mass) + dt (gravityScale g + force / mass);
+ *   omega += I_w^-1 (L_g + dt (torque - omega x (I_w omega))), I_w = M I M^T;  damping;  container contact (flag bit 0);
+ *   V = V_g - omega x o;  the pose advance of section 3e with the new V and omega.
+ * The particle pass of a substep sees the velocities the substep began with.  Container contact runs against the oriented box of
+ * param_boxCenter, param_boxEulerDeg and the effective half extents (for param_shapeType 0 the container itself, for the other
+ * shapes only their bounding box): support points (sphere: centre, radius R | capsule: the two ends of the core segment, radius r |
+ * box: the eight corners, radius 0) against faces -x, +x, -y, +y, -z, +z; a penetrating point that moves into the face gets the normal
+ * impulse j = -(1 + param_wallRestitution) v_n / (1 / mass + n . ((I_w^-1 (r x n)) x r)); no friction; afterwards the centre moves
+ * inward by each face's largest penetration.  A body without a record is kinematic, exactly as before; the accumulators keep summing
+ * what the fluid gave each body.  No body-body contact, no implicit coupling.  The exact operation order is DESIGN.md section 3g.
+ * sph_obstacles_set clears every record (a set replaces the set); sph_obstacles_set_motion on a dynamic body is a kick; sph_reset
+ * keeps the records.  SPH_ERR_ARG (the previous state stays): a non-finite field, mass <= 0, an inertia that is not positive
+ * definite, a damping < 0, an index out of range, a null pointer where a record is required.  SPH_ERR_STATE: z-slab engines. */
+#define SPH_DYNAMICS_CONFINED 1u
+typedef struct SphObstacleDynamics {   /* 80 bytes */
+    float    mass;             /* > 0 */
+    float    inertia[6];       /* xx, yy, zz, xy, xz, yz about the centre of mass, body frame; positive definite */
+    float    com[3];           /* centre of mass in the body frame, relative to center */
+    float    gravityScale;     /* times param_gravity*, default 1 */
+    float    force[3];         /* constant, world frame */
+    float    torque[3];        /* constant, world frame */
+    float    linearDamping;    /* per second: V *= max(0, 1 - linearDamping dt) */
+    float    angularDamping;
+    uint32_t flags;            /* SPH_DYNAMICS_CONFINED */
+} SphObstacleDynamics;
+/* mass 1, inertia diag(1, 1, 1), com 0, gravityScale 1, no force, torque or damping, confined by the container. */
+void sph_obstacle_dynamics_default(SphObstacleDynamics* out);
+/* Makes body `index` dynamic (dyn == NULL: kinematic again, keeping its current velocities).  Stream-ordered, no synchronisation. */
+int  sph_obstacles_set_dynamics(SphEngine* e, int index, const SphObstacleDynamics* dyn);
+/* The record of body `index` as set (*dynamicOut = 0 and a default record for a kinematic body).  Either output may be null. */
+int  sph_obstacles_get_dynamics(SphEngine* e, int index, SphObstacleDynamics* out, int* dynamicOut);
+/* Host-only, no device: the body step of one substep for `count` bodies, in place.  dyn[i].mass == 0 marks body i kinematic (it only
+ * advances); impulses6 holds the substep's (J, L) per body (null: zeros); params supplies gravity, the container box and
+ * param_wallRestitution.  The rotation is used as given, as in sph_obstacles_advance_host. */
+int  sph_obstacles_step_host(SphObstacle* obs, const SphObstacleDynamics* dyn, int count, const double* impulses6, const SphParams* params, float dt);
+/* Moments of the solid a volume describes, out = cell volume times the sum over the lattice points of w {1, x, y, z, xx, yy, zz, xy,
+ * xz, yz}: x, y, z the fp32 local coordinates of section 3f widened to fp64, w = clamp(0.5 - phi / D, 0, 1) in fp32 with D the
+ * cell diagonal.  A grid-sized reduction on the device without float atomics (the bits depend on the lattice only), timed as
+ * SPH_K_OTHER.  Synchronises.  The _host twin runs the same per-point function in plain loops, points in ascending order. */
+int  sph_volume_moments(SphEngine* e, int id, double out[10]);
+int  sph_volume_moments_host(const float* values, const int dims[3], const float spacing[3], double out[10]);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
