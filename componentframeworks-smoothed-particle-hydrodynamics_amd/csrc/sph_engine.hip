@@ -38,6 +38,8 @@ static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolB
 static_assert(sizeof(SphSurfaceVertex) == 24 && sizeof(sph::SurfVertex) == 24, "SphSurfaceVertex must be 24 bytes");
 static_assert(sizeof(SphStatistics) == 832 && alignof(SphStatistics) == 8 && sizeof(SphHistogramSpec) == 16, "SphStatistics must be 832 bytes, SphHistogramSpec 16");
 
+struct SphEngine;
+
 namespace {
 
 thread_local std::string g_err;
@@ -72,11 +74,54 @@ void dev_free(T*& p) {
     p = nullptr;
 }
 
+// An engine-owned device scratch array that only grows.  No destructor: frees stay explicit, behind the stream drains they follow.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;                                  // elements
+    int grow(SphEngine* e, size_t need);             // to at least `need` elements; contents are not kept, the engine's stream is drained first
+    void release() { dev_free(p); cap = 0; }
+};
+
+// Pinned staging for stream-ordered uploads: kObsSlots slots of `per` records, each guarded by an event recorded behind the copy queued from it.
+constexpr int kObsSlots = 4;
+template <class T>
+struct StageRing {
+    T* h = nullptr;
+    hipEvent_t ev[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
+    size_t per = 0;
+    int cur = 0;                                     // the slot handed out last
+    hipError_t create(hipStream_t stream, size_t perSlot) {
+        per = perSlot;
+        hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(T) * per * kObsSlots, hipHostMallocDefault);
+        for (auto& v : ev) if (er == hipSuccess) er = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+        for (auto& v : ev) if (er == hipSuccess) er = hipEventRecord(v, stream);      // (so that the first wait for a slot succeeds)
+        return er;
+    }
+    // The next slot, once the copy queued from it last time has run.
+    int next(T** slot) {
+        cur = (cur + 1) % kObsSlots;
+        HIP_TRY(hipEventSynchronize(ev[cur]));
+        *slot = h + (size_t)cur * per;
+        return SPH_OK;
+    }
+    // Behind the copy queued from the slot just handed out.
+    int commit(hipStream_t stream) {
+        HIP_TRY(hipEventRecord(ev[cur], stream));
+        return SPH_OK;
+    }
+    void destroy() {
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+        for (auto& v : ev) { if (v) (void)hipEventDestroy(v); v = nullptr; }
+        cur = 0;
+    }
+};
+
 inline int blocks_for(size_t n, int per = sph::kBlock) { return (int)((n + per - 1) / per); }
 
 }  // namespace
 
-struct SphEngine;
 static std::set<SphEngine*> g_engines;      // live engines of this process (sph_destroy clears what neighbours hold of a destroyed one)
 static std::mutex g_enginesMutex;           // (a host may drive its engines from one thread each)
 
@@ -182,28 +227,21 @@ struct SphEngine {
     int debugFlags = 0;
     unsigned long long* d_stats = nullptr;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
     // sph_sample_points (host arrays): device copies of the probes and of the results
-    float4* d_sampleIn = nullptr;
-    SphSample* d_sampleOut = nullptr;
-    size_t sampleCap = 0;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
+    DevBuf<float4> d_sampleIn;
+    DevBuf<SphSample> d_sampleOut;
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
-    float* d_surfVol = nullptr;
-    uint16_t* d_surfCode = nullptr;
-    uint32_t* d_surfVOff = nullptr;
-    uint2* d_surfTile = nullptr;
-    unsigned long long* d_surfTileOff = nullptr;
-    size_t surfVolCap = 0, surfCodeCap = 0, surfVOffCap = 0, surfTileCap = 0, surfTileOffCap = 0;
-    sph::SurfVertex* d_surfVerts = nullptr;
-    uint32_t* d_surfTris = nullptr;
-    size_t surfVertCap = 0, surfTriCap = 0;
+    DevBuf<float> d_surfVol;
+    DevBuf<uint16_t> d_surfCode;
+    DevBuf<uint32_t> d_surfVOff, d_surfTris;
+    DevBuf<uint2> d_surfTile;
+    DevBuf<unsigned long long> d_surfTileOff;
+    DevBuf<sph::SurfVertex> d_surfVerts;
     bool surfValid = false;
     uint32_t surfNumV = 0, surfNumT = 0;
     // sph_statistics*: per-tile sums / partial records / histogram rows, the cells kernel's rows, and the device copy of the host variant's result
-    double* d_statSums = nullptr;
-    uint32_t* d_statPart = nullptr;
-    uint32_t* d_statHist = nullptr;
-    unsigned long long* d_statCell = nullptr;
-    unsigned long long* d_statOut = nullptr;
-    size_t statSumsCap = 0, statPartCap = 0, statHistCap = 0, statCellCap = 0, statOutCap = 0;
+    DevBuf<double> d_statSums;
+    DevBuf<uint32_t> d_statPart, d_statHist;
+    DevBuf<unsigned long long> d_statCell, d_statOut;
 
     // sph_tracers_*: M records in the caller's order (two float4 each), their processing order, the pathline ring of K x M float4, the
     // device step counter (sph_tracer.h) and the scratch of the processing order's cell sort
@@ -212,9 +250,8 @@ struct SphEngine {
     float4* d_trRing = nullptr;
     uint32_t* d_trState = nullptr;
     uint2* d_trKey = nullptr;
-    uint32_t *d_trCellCount = nullptr, *d_trCellStart = nullptr, *d_trBlockSums = nullptr;
+    DevBuf<uint32_t> d_trCellCount, d_trCellStart, d_trBlockSums;
     size_t trM = 0, trCap = 0, trRingCap = 0;
-    int trCells = 0;
     int trIntegrator = 0;
     uint32_t trK = 0, trS = 1;
     uint64_t trSteps = 0;                // host mirror of the device step counter: non-paused substeps issued since sph_tracers_set
@@ -223,14 +260,11 @@ struct SphEngine {
     bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
 
     // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
-    // and kObsSlots pinned staging slots for stream-ordered uploads, each guarded by an event recorded behind its copy
-    static constexpr int kObsSlots = 4;
+    // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
     sph::ObsRec* d_obs = nullptr;
     sph::ObsAcc* d_obsAcc = nullptr;
     double* d_obsPart = nullptr;
-    sph::ObsRec* h_obsStage = nullptr;   // kObsSlots x kObsMax records
-    hipEvent_t evObs[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int obsSlot = 0;
+    StageRing<sph::ObsRec> obsStage;
     int obsK = 0;
 
     // sph_volume_* (sph_volume.h): the signed distance lattices, the device table (slots and per-body bindings) with its host mirror, pinned
@@ -239,29 +273,22 @@ struct SphEngine {
     VolSlot vols[sph::kVolMax];
     sph::VolTable* d_volTab = nullptr;
     sph::VolTable volTab{};              // host mirror of *d_volTab
-    sph::VolTable* h_volStage = nullptr; // kObsSlots tables
-    hipEvent_t evVol[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int volSlot = 0;
+    StageRing<sph::VolTable> volStage;   // one table per slot
     int volBound = 0;                    // bodies bound to a volume: k_obstacles_vol is launched instead of k_obstacles while > 0
     int obsShape[sph::kObsMax] = {0};    // shapes of the current set (a volume binds to a box only)
     // dynamic bodies (sph_obstacle.h ObsDyn): one record per body beside d_obs, the records as set (host mirror),
     // pinned staging like the bodies'; k_obstacles_finish_dyn is launched instead of k_obstacles_finish while dynCount > 0
     sph::ObsDyn* d_dyn = nullptr;
-    sph::ObsDyn* h_dynStage = nullptr;   // kObsSlots records
-    hipEvent_t evDyn[kObsSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int dynSlot = 0;
+    StageRing<sph::ObsDyn> dynStage;     // one record per slot
     int dynCount = 0;
     bool dynOn[sph::kObsMax] = {false};
     SphObstacleDynamics dynSet[sph::kObsMax] = {};
     // sph_volume_moments: the partial rows and the ten results
-    double* d_momPart = nullptr;
-    double* d_momOut = nullptr;
+    DevBuf<double> d_momPart, d_momOut;
     int optMeshSplit = 0;                // SPH_OPT_MESH_SPLIT
-    float* d_meshVerts = nullptr;
-    uint32_t* d_meshTris = nullptr;
-    float* d_meshD2 = nullptr;
-    double* d_meshW = nullptr;
-    size_t meshVertCap = 0, meshTriCap = 0, meshPartCap = 0;
+    DevBuf<float> d_meshVerts, d_meshD2;
+    DevBuf<uint32_t> d_meshTris;
+    DevBuf<double> d_meshW;
 
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
 
@@ -276,6 +303,17 @@ struct SphEngine {
 namespace {
 
 using namespace sph;
+
+template <class T>
+int DevBuf<T>::grow(SphEngine* e, size_t need) {
+    if (need <= cap && p) return SPH_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    release();
+    int rc;
+    if ((rc = dev_alloc(&p, need))) return rc;
+    cap = need;
+    return SPH_OK;
+}
 
 // Members that decide where the container walls and the grid are (for the slab exchange's reduced scan).
 void container_key(const SphParams& q, float out[15]) {
@@ -354,12 +392,19 @@ void free_grid_buffers(SphEngine* e) {
     e->allocatedCells = 0;
 }
 
+// One free function per feature (callers have drained the stream, or the function does): sph_destroy calls each.
+void sample_free(SphEngine* e) { e->d_sampleIn.release(); e->d_sampleOut.release(); }
+void surface_free(SphEngine* e) {
+    e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
+    e->d_surfVerts.release(); e->d_surfTris.release();
+}
+void stats_free(SphEngine* e) { e->d_statSums.release(); e->d_statPart.release(); e->d_statHist.release(); e->d_statCell.release(); e->d_statOut.release(); }
+
 void tracers_free(SphEngine* e) {
     if (e->d_trRec && e->stream) (void)hipStreamSynchronize(e->stream);
     dev_free(e->d_trRec); dev_free(e->d_trPerm); dev_free(e->d_trRing); dev_free(e->d_trState); dev_free(e->d_trKey);
-    dev_free(e->d_trCellCount); dev_free(e->d_trCellStart); dev_free(e->d_trBlockSums);
+    e->d_trCellCount.release(); e->d_trCellStart.release(); e->d_trBlockSums.release();
     e->trM = e->trCap = e->trRingCap = 0;
-    e->trCells = 0;
     e->trK = 0; e->trS = 1; e->trSteps = e->trSorted = 0;
     e->trOrdered = false;
 }
@@ -367,16 +412,11 @@ void tracers_free(SphEngine* e) {
 void obstacles_free(SphEngine* e) {
     if (e->d_obs && e->stream) (void)hipStreamSynchronize(e->stream);
     dev_free(e->d_obs); dev_free(e->d_obsAcc); dev_free(e->d_obsPart); dev_free(e->d_dyn);
-    if (e->h_obsStage) (void)hipHostFree(e->h_obsStage);
-    e->h_obsStage = nullptr;
-    if (e->h_dynStage) (void)hipHostFree(e->h_dynStage);
-    e->h_dynStage = nullptr;
-    for (auto& ev : e->evObs) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
-    for (auto& ev : e->evDyn) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
-    e->dynCount = 0; e->dynSlot = 0;
+    e->obsStage.destroy();
+    e->dynStage.destroy();
+    e->dynCount = 0;
     for (auto& on : e->dynOn) on = false;
     e->obsK = 0;
-    e->obsSlot = 0;
 }
 
 // Every binding dropped (host mirror only; volumes_upload_table sends it).
@@ -388,15 +428,11 @@ void volumes_free(SphEngine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto& v : e->vols) { dev_free(v.d); v = SphEngine::VolSlot{}; }
     dev_free(e->d_volTab);
-    if (e->h_volStage) (void)hipHostFree(e->h_volStage);
-    e->h_volStage = nullptr;
-    for (auto& ev : e->evVol) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    e->volStage.destroy();
     std::memset(&e->volTab, 0, sizeof(e->volTab));
     volumes_unbind_all(e);
-    e->volSlot = 0;
-    dev_free(e->d_meshVerts); dev_free(e->d_meshTris); dev_free(e->d_meshD2); dev_free(e->d_meshW);
-    dev_free(e->d_momPart); dev_free(e->d_momOut);
-    e->meshVertCap = e->meshTriCap = e->meshPartCap = 0;
+    e->d_meshVerts.release(); e->d_meshTris.release(); e->d_meshD2.release(); e->d_meshW.release();
+    e->d_momPart.release(); e->d_momOut.release();
 }
 
 int alloc_particle_buffers(SphEngine* e, size_t n) {
@@ -478,13 +514,22 @@ int import_state(SphEngine* e) {
     return SPH_OK;
 }
 
+// The counting sort's exclusive scan of `count` (C cells) into start[0..C]; k_scan_apply leaves count zero again.
+void launch_cell_scan(SphEngine* e, uint32_t* count, uint32_t* blockSums, uint32_t* start, int C, uint32_t total) {
+    const int sb = blocks_for((size_t)C, kScanTile);
+    const int rawSums = sb <= kScanFusedBlocks ? 1 : 0;
+    hipLaunchKernelGGL(k_scan_reduce, dim3(sb), dim3(kBlock), 0, e->stream, count, blockSums, C);
+    if (!rawSums) hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(kBlock), 0, e->stream, blockSums, sb);
+    hipLaunchKernelGGL(k_scan_apply, dim3(sb), dim3(kBlock), 0, e->stream, count, blockSums, start, C, total, rawSums);
+}
+
 // ClearGrid + BuildGrid as a counting sort: after this, d_cellStart/d_order describe the
 // current state buffer.
 // commitLive (z-slab dispatch only): k_rank also stores the live count as the new slots-in-use count of the exchange.
 // orderAll (sph_statistics only): k_rank writes order[] for every slot, not only for ghosts (the exact density is gathered through it).
 int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderAll = false) {
     const int n = (int)(e->slab ? e->nSlots : e->n), C = k.numCells;
-    const int nb = blocks_for(n), sb = blocks_for((size_t)C, kScanTile);
+    const int nb = blocks_for(n);
     const bool sortedCopy = e->optGridBuild == 0;     // k_rank also writes the sorted copy the SPH pass reads
     if (sortedCopy && (e->sortedCap < e->cap || !e->d_sPV)) {
         int rc;
@@ -500,10 +545,7 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
     }
     {
         Timed t(e, SPH_K_SCAN);
-        const int rawSums = sb <= kScanFusedBlocks ? 1 : 0;
-        hipLaunchKernelGGL(k_scan_reduce, dim3(sb), dim3(kBlock), 0, e->stream, e->d_cellCount, e->d_blockSums, C);
-        if (!rawSums) hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(kBlock), 0, e->stream, e->d_blockSums, sb);
-        hipLaunchKernelGGL(k_scan_apply, dim3(sb), dim3(kBlock), 0, e->stream, e->d_cellCount, e->d_blockSums, e->d_cellStart, C, (uint32_t)n, rawSums);
+        launch_cell_scan(e, e->d_cellCount, e->d_blockSums, e->d_cellStart, C, (uint32_t)n);
     }
     if (n) {
         Timed t(e, SPH_K_SCATTER);
@@ -533,25 +575,18 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
 int tracers_order(SphEngine* e, const SimK& k) {
     if (!e->trM || e->capturing) return SPH_OK;
     if (e->trOrdered && e->trSteps - e->trSorted < (uint64_t)kTracerRefresh) return SPH_OK;
-    const int C = k.numCells, sb = blocks_for((size_t)C, kScanTile);
+    const int C = k.numCells;
     int rc;
-    if (e->trCells != C || !e->d_trCellCount) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        dev_free(e->d_trCellCount); dev_free(e->d_trCellStart); dev_free(e->d_trBlockSums);
-        e->trCells = 0;
-        if ((rc = dev_alloc(&e->d_trCellCount, (size_t)C)) || (rc = dev_alloc(&e->d_trCellStart, (size_t)C + 1)) ||
-            (rc = dev_alloc(&e->d_trBlockSums, (size_t)sb + 1))) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_trCellCount, 0, (size_t)C * sizeof(uint32_t), e->stream));      // (k_scan_apply leaves it zero again)
-        e->trCells = C;
+    if (e->d_trCellStart.cap < (size_t)C + 1) {              // (grown last: a failed growth is tried again)
+        if ((rc = e->d_trCellCount.grow(e, (size_t)C)) || (rc = e->d_trBlockSums.grow(e, (size_t)blocks_for((size_t)C, kScanTile) + 1)) ||
+            (rc = e->d_trCellStart.grow(e, (size_t)C + 1))) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_trCellCount.p, 0, (size_t)C * sizeof(uint32_t), e->stream));    // (k_scan_apply leaves it zero again)
     }
     const uint32_t m = (uint32_t)e->trM;
-    const int rawSums = sb <= kScanFusedBlocks ? 1 : 0;
     Timed t(e, SPH_K_OTHER);
-    hipLaunchKernelGGL(k_tracer_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_trRec, e->d_trKey, e->d_trCellCount, m);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(sb), dim3(kBlock), 0, e->stream, e->d_trCellCount, e->d_trBlockSums, C);
-    if (!rawSums) hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(kBlock), 0, e->stream, e->d_trBlockSums, sb);
-    hipLaunchKernelGGL(k_scan_apply, dim3(sb), dim3(kBlock), 0, e->stream, e->d_trCellCount, e->d_trBlockSums, e->d_trCellStart, C, m, rawSums);
-    hipLaunchKernelGGL(k_tracer_scatter, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_trKey, e->d_trCellStart, e->d_trPerm, m);
+    hipLaunchKernelGGL(k_tracer_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_trRec, e->d_trKey, e->d_trCellCount.p, m);
+    launch_cell_scan(e, e->d_trCellCount.p, e->d_trBlockSums.p, e->d_trCellStart.p, C, m);
+    hipLaunchKernelGGL(k_tracer_scatter, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_trKey, e->d_trCellStart.p, e->d_trPerm, m);
     HIP_TRY(hipGetLastError());
     e->trSorted = e->trSteps;
     e->trOrdered = true;
@@ -654,6 +689,9 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     if (e->trM && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params))) return rc;
+    float cont[15];
+    container_key(e->params, cont);
+    const bool sameContainer = std::memcmp(cont, e->lastContainer, sizeof(cont)) == 0;   // same walls and same grid as the dispatch before
     const float dt = overrideDt > 0.0f ? overrideDt : e->params.param_timeStep;   // :434
     e->lastDt = dt;
     compute_grid_extents(e->params, e->grid);                               // :439
@@ -665,9 +703,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         k.gz = e->z1 - e->z0 + 2; k.numCells = k.gx * k.gy * k.gz; k.zoff = e->z0 - 1;
         // the pack that follows this substep may restrict itself to the ends of the slot range (same container as the substep
         // before, sorted slots): a particle that this substep carries from the middle into a face layer is then reported
-        float contNow[15];
-        container_key(e->params, contNow);
-        if (e->optGridBuild != 1 && std::memcmp(contNow, e->lastContainer, sizeof(contNow)) == 0) k.slabFlags = e->d_slabCnt + 4;
+        if (e->optGridBuild != 1 && sameContainer) k.slabFlags = e->d_slabCnt + 4;
     }
     if ((rc = import_state(e))) return rc;
     const int n = (int)(e->slab ? e->nSlots : e->n);
@@ -717,9 +753,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
             };
             // The pack of the next exchange only reads the slots of the kSlabDepth lowest / highest local cell layers (k_slab_pack,
             // under the same conditions): those two slot ranges first, the event, then everything in between.
-            float contNow[15];
-            container_key(e->params, contNow);
-            const bool split = boundaryFirst && e->slab && k.gz > 2 * kSlabDepth && !k.obbDeferred && std::memcmp(contNow, e->lastContainer, sizeof(contNow)) == 0;
+            const bool split = boundaryFirst && e->slab && k.gz > 2 * kSlabDepth && !k.obbDeferred && sameContainer;
             const bool timedStep = boundaryFirst && e->optTiming && e->evPassEnd;
             if (split) {
                 const uint32_t* endLo = e->d_cellStart + kSlabDepth * (size_t)(k.gx * k.gy);
@@ -803,9 +837,6 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         // the next k_slab_pack may restrict itself to the ends of the slot range if this substep cannot have moved a
         // particle by more than one layer: a container that did not change under the fluid (and the SPH pass reports the particle that
         // jumps from the middle into a face layer all the same, slab_check_layer_move)
-        float cont[15];
-        container_key(e->params, cont);
-        const bool sameContainer = std::memcmp(cont, e->lastContainer, sizeof(cont)) == 0;
         if (!sameContainer) slab_hold(e);                    // the walls moved under the fluid: whole faces until the counts have been seen calm again
         std::memcpy(e->lastContainer, cont, sizeof(cont));
         e->slabOrderValid = sorted && sameContainer;
@@ -955,13 +986,12 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_stencil);
     dev_free(e->d_terrain);
     dev_free(e->d_stats);
-    dev_free(e->d_sampleIn); dev_free(e->d_sampleOut);
-    dev_free(e->d_surfVol); dev_free(e->d_surfCode); dev_free(e->d_surfVOff); dev_free(e->d_surfTile); dev_free(e->d_surfTileOff);
-    dev_free(e->d_surfVerts); dev_free(e->d_surfTris);
+    sample_free(e);
+    surface_free(e);
+    stats_free(e);
     tracers_free(e);
     obstacles_free(e);
     volumes_free(e);
-    dev_free(e->d_statSums); dev_free(e->d_statPart); dev_free(e->d_statHist); dev_free(e->d_statCell); dev_free(e->d_statOut);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (e->xstream) { (void)hipStreamSynchronize(e->xstream); (void)hipStreamDestroy(e->xstream); }
@@ -1071,8 +1101,8 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     const int opts[8] = {e->optNeighbor, e->optGridBuild, e->optAos, e->cur, ((e->aosValid && e->optAos == 0) ? 1 : 0) | (e->accValid ? 2 : 0) | (e->internalValid ? 4 : 0),
                          (int)e->idBase, e->allocatedCells, 0};
     add(opts, sizeof(opts));
-    const void* ptrs[20] = {e->d_aos, e->d_pos[0], e->d_pos[1], e->d_vel[0], e->d_vel[1], e->d_rp[0], e->d_rp[1], e->d_foam[0], e->d_foam[1], e->d_acc,
-                            e->d_binKey, e->d_intent, e->d_order, e->d_tmp, e->d_cellCount, e->d_cellStart, e->d_blockSums, e->d_sPV, e->d_sPV, e->d_sOwn};
+    const void* ptrs[19] = {e->d_aos, e->d_pos[0], e->d_pos[1], e->d_vel[0], e->d_vel[1], e->d_rp[0], e->d_rp[1], e->d_foam[0], e->d_foam[1], e->d_acc,
+                            e->d_binKey, e->d_intent, e->d_order, e->d_tmp, e->d_cellCount, e->d_cellStart, e->d_blockSums, e->d_sPV, e->d_sOwn};
     add(ptrs, sizeof(ptrs));
     const void* more[3] = {e->d_llNext, e->d_shapeTab, e->d_stats};
     add(more, sizeof(more));
@@ -2374,6 +2404,20 @@ static int sample_grid(SphEngine* e, SimK& k, bool orderAll = false) {
     return build_grid(e, k, false, orderAll);
 }
 
+// A regular lattice of points as an argument: at least `least` points along every axis, a finite spacing > 0, at most 2^31 - 1 points.
+static int check_lattice(const int dims[3], const float spacing[3], int least, long long* totalOut) {
+    if (!dims || !spacing) return fail(SPH_ERR_ARG, "null argument");
+    long long total = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < least) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= %d)", a, dims[a], least);
+        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
+        total *= dims[a];
+        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
+    }
+    if (totalOut) *totalOut = total;
+    return SPH_OK;
+}
+
 int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, SphSample* devOut) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (m && (!devPoints4 || !devOut)) return fail(SPH_ERR_ARG, "null argument");
@@ -2395,15 +2439,10 @@ int sph_sample_points(SphEngine* e, const float* points4, size_t m, SphSample* o
     if (m && (!points4 || !out)) return fail(SPH_ERR_ARG, "null argument");
     if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
     int rc;
-    if (m > e->sampleCap) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        dev_free(e->d_sampleIn); dev_free(e->d_sampleOut); e->sampleCap = 0;
-        if ((rc = dev_alloc(&e->d_sampleIn, m)) || (rc = dev_alloc(&e->d_sampleOut, m))) return rc;
-        e->sampleCap = m;
-    }
-    if (m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
-    if ((rc = sph_sample_points_device(e, reinterpret_cast<const float*>(e->d_sampleIn), m, e->d_sampleOut))) return rc;
-    if (m) HIP_TRY(hipMemcpyAsync(out, e->d_sampleOut, m * sizeof(SphSample), hipMemcpyDeviceToHost, e->stream));
+    if (m && ((rc = e->d_sampleIn.grow(e, m)) || (rc = e->d_sampleOut.grow(e, m)))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = sph_sample_points_device(e, reinterpret_cast<const float*>(e->d_sampleIn.p), m, e->d_sampleOut.p))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(out, e->d_sampleOut.p, m * sizeof(SphSample), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
@@ -2412,16 +2451,9 @@ int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (!origin || !spacing || !dims || !devOut) return fail(SPH_ERR_ARG, "null argument");
     if (field < SPH_FIELD_DENSITY || field > SPH_FIELD_ALL) return fail(SPH_ERR_ARG, "unknown field %d", field);
-    long long total = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 1) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= 1)", a, dims[a]);
-        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
-        total *= dims[a];
-        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
-    }
     SimK k;
     int rc;
-    if ((rc = sample_grid(e, k))) return rc;
+    if ((rc = check_lattice(dims, spacing, 1, nullptr)) || (rc = sample_grid(e, k))) return rc;
     LatticeK L;
     L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
     L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
@@ -2441,27 +2473,10 @@ int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[
 
 // ---- iso-surface meshes (sph_surface.h) ----------------------------------------------------------
 static int surface_check_lattice(const float origin[3], const float spacing[3], const int dims[3], float iso) {
-    if (!origin || !spacing || !dims) return fail(SPH_ERR_ARG, "null argument");
-    long long total = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < 2) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= 2)", a, dims[a]);
-        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
-        total *= dims[a];
-        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
-    }
-    if (!std::isfinite(iso)) return fail(SPH_ERR_ARG, "iso %g is not finite", (double)iso);
-    return SPH_OK;
-}
-
-// grows an engine-owned device array to at least `need` elements (contents are not kept; the engine's stream is drained first)
-extern "C++" template <class T>
-static int surface_grow(SphEngine* e, T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return SPH_OK;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    dev_free(p); cap = 0;
+    if (!origin) return fail(SPH_ERR_ARG, "null argument");
     int rc;
-    if ((rc = dev_alloc(&p, need))) return rc;
-    cap = need;
+    if ((rc = check_lattice(dims, spacing, 2, nullptr))) return rc;
+    if (!std::isfinite(iso)) return fail(SPH_ERR_ARG, "iso %g is not finite", (double)iso);
     return SPH_OK;
 }
 
@@ -2476,34 +2491,34 @@ static int surface_mesh(SphEngine* e, const float* vol, const float origin[3], c
     s.iso = iso;
     s.nTiles = (int)((s.npts + kSurfTile - 1) / kSurfTile);
     int rc;
-    if ((rc = surface_grow(e, e->d_surfCode, e->surfCodeCap, (size_t)s.npts)) || (rc = surface_grow(e, e->d_surfVOff, e->surfVOffCap, (size_t)s.npts)) ||
-        (rc = surface_grow(e, e->d_surfTile, e->surfTileCap, (size_t)s.nTiles)) ||
-        (rc = surface_grow(e, e->d_surfTileOff, e->surfTileOffCap, 2 * (size_t)s.nTiles + 2))) return rc;
+    if ((rc = e->d_surfCode.grow(e, (size_t)s.npts)) || (rc = e->d_surfVOff.grow(e, (size_t)s.npts)) ||
+        (rc = e->d_surfTile.grow(e, (size_t)s.nTiles)) ||
+        (rc = e->d_surfTileOff.grow(e, 2 * (size_t)s.nTiles + 2))) return rc;
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_surf_count, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, e->d_surfCode, e->d_surfTile);
+        hipLaunchKernelGGL(k_surf_count, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, e->d_surfCode.p, e->d_surfTile.p);
     }
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_surf_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, (const uint2*)e->d_surfTile, e->d_surfTileOff, s.nTiles);
+        hipLaunchKernelGGL(k_surf_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, (const uint2*)e->d_surfTile.p, e->d_surfTileOff.p, s.nTiles);
     }
     HIP_TRY(hipGetLastError());
     unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(hipMemcpyAsync(tot, e->d_surfTileOff + 2 * (size_t)s.nTiles, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(tot, e->d_surfTileOff.p + 2 * (size_t)s.nTiles, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull)
         return fail(SPH_ERR_CAPACITY, "surface of %llu vertices and %llu triangles exceeds 2^32 - 1", tot[0], tot[1]);
-    if ((rc = surface_grow(e, e->d_surfVerts, e->surfVertCap, (size_t)tot[0])) ||
-        (rc = surface_grow(e, e->d_surfTris, e->surfTriCap, 3 * (size_t)tot[1]))) return rc;
+    if ((rc = e->d_surfVerts.grow(e, (size_t)tot[0])) ||
+        (rc = e->d_surfTris.grow(e, 3 * (size_t)tot[1]))) return rc;
     if (tot[0]) {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_surf_vertices, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, (const uint16_t*)e->d_surfCode,
-                           (const unsigned long long*)e->d_surfTileOff, e->d_surfVOff, e->d_surfVerts);
+        hipLaunchKernelGGL(k_surf_vertices, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, vol, (const uint16_t*)e->d_surfCode.p,
+                           (const unsigned long long*)e->d_surfTileOff.p, e->d_surfVOff.p, e->d_surfVerts.p);
     }
     if (tot[1]) {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_surf_triangles, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, (const uint16_t*)e->d_surfCode,
-                           (const uint32_t*)e->d_surfVOff, (const unsigned long long*)e->d_surfTileOff, e->d_surfTris);
+        hipLaunchKernelGGL(k_surf_triangles, dim3(s.nTiles), dim3(kBlock), 0, e->stream, s, (const uint16_t*)e->d_surfCode.p,
+                           (const uint32_t*)e->d_surfVOff.p, (const unsigned long long*)e->d_surfTileOff.p, e->d_surfTris.p);
     }
     HIP_TRY(hipGetLastError());
     e->surfNumV = (uint32_t)tot[0];
@@ -2511,8 +2526,8 @@ static int surface_mesh(SphEngine* e, const float* vol, const float origin[3], c
     e->surfValid = true;
     out->numVertices = e->surfNumV;
     out->numTriangles = e->surfNumT;
-    out->vertices = e->surfNumV ? reinterpret_cast<const SphSurfaceVertex*>(e->d_surfVerts) : nullptr;
-    out->triangles = e->surfNumT ? e->d_surfTris : nullptr;
+    out->vertices = e->surfNumV ? reinterpret_cast<const SphSurfaceVertex*>(e->d_surfVerts.p) : nullptr;
+    out->triangles = e->surfNumT ? e->d_surfTris.p : nullptr;
     return SPH_OK;
 }
 
@@ -2535,9 +2550,9 @@ int sph_extract_surface(SphEngine* e, const float origin[3], const float spacing
     if (field < SPH_FIELD_DENSITY || field > SPH_FIELD_SPEED) return fail(SPH_ERR_ARG, "field %d is not a scalar field", field);
     if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
     const size_t npts = (size_t)dims[0] * dims[1] * dims[2];
-    if ((rc = surface_grow(e, e->d_surfVol, e->surfVolCap, npts))) return rc;
-    if ((rc = sph_sample_lattice(e, origin, spacing, dims, field, e->d_surfVol))) return rc;
-    return surface_mesh(e, e->d_surfVol, origin, spacing, dims, iso, out);
+    if ((rc = e->d_surfVol.grow(e, npts))) return rc;
+    if ((rc = sph_sample_lattice(e, origin, spacing, dims, field, e->d_surfVol.p))) return rc;
+    return surface_mesh(e, e->d_surfVol.p, origin, spacing, dims, iso, out);
 }
 
 int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertexCap, uint32_t* triangles3, size_t triangleCap) {
@@ -2546,8 +2561,8 @@ int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertex
     if (vertexCap < e->surfNumV || triangleCap < e->surfNumT)
         return fail(SPH_ERR_CAPACITY, "surface has %u vertices and %u triangles (capacities %zu, %zu)", e->surfNumV, e->surfNumT, vertexCap, triangleCap);
     if ((e->surfNumV && !vertices) || (e->surfNumT && !triangles3)) return fail(SPH_ERR_ARG, "null argument");
-    if (e->surfNumV) HIP_TRY(hipMemcpyAsync(vertices, e->d_surfVerts, (size_t)e->surfNumV * sizeof(SphSurfaceVertex), hipMemcpyDeviceToHost, e->stream));
-    if (e->surfNumT) HIP_TRY(hipMemcpyAsync(triangles3, e->d_surfTris, (size_t)e->surfNumT * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (e->surfNumV) HIP_TRY(hipMemcpyAsync(vertices, e->d_surfVerts.p, (size_t)e->surfNumV * sizeof(SphSurfaceVertex), hipMemcpyDeviceToHost, e->stream));
+    if (e->surfNumT) HIP_TRY(hipMemcpyAsync(triangles3, e->d_surfTris.p, (size_t)e->surfNumT * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
@@ -2597,27 +2612,27 @@ static int stats_run(SphEngine* e, const sph::StatK& specs, SphStatistics* devOu
     while (s.tilesPow2 < s.nTiles) s.tilesPow2 <<= 1;
     s.nBlocks = std::min(s.nTiles, kStatGrid);
     const int cellBlocks = std::min(blocks_for(((size_t)k.numCells + 3) / 4), kStatCellBlocks);
-    if ((rc = surface_grow(e, e->d_statSums, e->statSumsCap, (size_t)kStatSums * s.tilesPow2)) ||
-        (rc = surface_grow(e, e->d_statPart, e->statPartCap, (size_t)kStatPartWords * kStatGrid)) ||
-        (rc = surface_grow(e, e->d_statHist, e->statHistCap, (size_t)std::max(s.nBlocks, 1) * std::max(s.histWords, 1u))) ||
-        (rc = surface_grow(e, e->d_statCell, e->statCellCap, (size_t)kStatCellBlocks * kStatCellCols))) return rc;
+    if ((rc = e->d_statSums.grow(e, (size_t)kStatSums * s.tilesPow2)) ||
+        (rc = e->d_statPart.grow(e, (size_t)kStatPartWords * kStatGrid)) ||
+        (rc = e->d_statHist.grow(e, (size_t)std::max(s.nBlocks, 1) * std::max(s.histWords, 1u))) ||
+        (rc = e->d_statCell.grow(e, (size_t)kStatCellBlocks * kStatCellCols))) return rc;
     if (s.nTiles) {
         Timed t(e, SPH_K_OTHER);
         hipLaunchKernelGGL(k_stats_tiles, dim3(s.nBlocks), dim3(kBlock), 0, e->stream, s, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
-                           (const uint32_t*)e->d_order, (const float2*)e->d_rp[e->cur], e->d_statSums, e->d_statPart, e->d_statHist);
+                           (const uint32_t*)e->d_order, (const float2*)e->d_rp[e->cur], e->d_statSums.p, e->d_statPart.p, e->d_statHist.p);
     }
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_stats_cells, dim3(cellBlocks), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_cellStart, k.numCells, e->d_statCell);
+        hipLaunchKernelGGL(k_stats_cells, dim3(cellBlocks), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_cellStart, k.numCells, e->d_statCell.p);
     }
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_stats_finish, dim3(kStatSums + 2), dim3(kBlock), 0, e->stream, s, e->d_statSums, (const uint32_t*)e->d_statPart,
-                           (const unsigned long long*)e->d_statCell, cellBlocks, devOut);
+        hipLaunchKernelGGL(k_stats_finish, dim3(kStatSums + 2), dim3(kBlock), 0, e->stream, s, e->d_statSums.p, (const uint32_t*)e->d_statPart.p,
+                           (const unsigned long long*)e->d_statCell.p, cellBlocks, devOut);
     }
     if (s.histWords) {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_stats_hist, dim3((s.histWords + kStatHistBins - 1u) / kStatHistBins), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_statHist, s.nBlocks, s.histWords,
+        hipLaunchKernelGGL(k_stats_hist, dim3((s.histWords + kStatHistBins - 1u) / kStatHistBins), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_statHist.p, s.nBlocks, s.histWords,
                            reinterpret_cast<unsigned long long*>(devHistOut));
     }
     HIP_TRY(hipGetLastError());
@@ -2642,9 +2657,9 @@ int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* spe
     sph::StatK s{};
     if ((rc = stats_check_specs(specs, nSpecs, histOut, s))) return rc;
     const size_t headWords = sizeof(SphStatistics) / sizeof(uint64_t);
-    if ((rc = surface_grow(e, e->d_statOut, e->statOutCap, headWords + (size_t)sph::kStatHistWords))) return rc;
-    SphStatistics* devOut = reinterpret_cast<SphStatistics*>(e->d_statOut);
-    uint64_t* devHist = reinterpret_cast<uint64_t*>(e->d_statOut + headWords);
+    if ((rc = e->d_statOut.grow(e, headWords + (size_t)sph::kStatHistWords))) return rc;
+    SphStatistics* devOut = reinterpret_cast<SphStatistics*>(e->d_statOut.p);
+    uint64_t* devHist = reinterpret_cast<uint64_t*>(e->d_statOut.p + headWords);
     if ((rc = stats_run(e, s, devOut, devHist))) return rc;
     HIP_TRY(hipMemcpyAsync(out, devOut, sizeof(SphStatistics), hipMemcpyDeviceToHost, e->stream));
     if (s.histWords) HIP_TRY(hipMemcpyAsync(histOut, devHist, (size_t)s.histWords * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
@@ -2791,25 +2806,26 @@ static void rec_to_obstacle(const sph::ObsRec& r, SphObstacle& o) {
     for (int a = 0; a < 4; ++a) o.rotation[a] = r.q[a];
     o.restitution = r.res; o.friction = r.fr;
 }
-// The next pinned staging slot, once the copy queued from it last time has run.
-static int obstacles_slot(SphEngine* e, sph::ObsRec** slot) {
-    const int i = e->obsSlot;
-    e->obsSlot = (i + 1) % SphEngine::kObsSlots;
-    HIP_TRY(hipEventSynchronize(e->evObs[i]));
-    *slot = e->h_obsStage + (size_t)i * kObsMax;
+static int obstacles_refuse_slab(const SphEngine* e) {
+    return e->slab ? fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported") : SPH_OK;
+}
+static int volumes_refuse_slab(const SphEngine* e) {
+    return e->slab ? fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported") : SPH_OK;
+}
+static int obstacle_index_check(const SphEngine* e, int index) {
+    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
     return SPH_OK;
 }
 
 // The host mirror of the table to the device, stream-ordered, through the next pinned staging slot.
 static int volumes_upload_table(SphEngine* e) {
     if (!e->d_volTab) return SPH_OK;
-    const int i = e->volSlot;
-    e->volSlot = (i + 1) % SphEngine::kObsSlots;
-    HIP_TRY(hipEventSynchronize(e->evVol[i]));
-    e->h_volStage[i] = e->volTab;
-    HIP_TRY(hipMemcpyAsync(e->d_volTab, &e->h_volStage[i], sizeof(sph::VolTable), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipEventRecord(e->evVol[i], e->stream));
-    return SPH_OK;
+    int rc;
+    sph::VolTable* slot = nullptr;
+    if ((rc = e->volStage.next(&slot))) return rc;
+    *slot = e->volTab;
+    HIP_TRY(hipMemcpyAsync(e->d_volTab, slot, sizeof(sph::VolTable), hipMemcpyHostToDevice, e->stream));
+    return e->volStage.commit(e->stream);
 }
 
 void sph_obstacle_default(SphObstacle* out) {
@@ -2824,9 +2840,8 @@ void sph_obstacle_default(SphObstacle* out) {
 
 int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
     int rc;
-    if ((rc = obstacles_check(obs, count))) return rc;
+    if ((rc = obstacles_refuse_slab(e)) || (rc = obstacles_check(obs, count))) return rc;
     if (e->volBound > 0) {                                           // (a set replaces the set: every binding goes with it)
         volumes_unbind_all(e);
         if ((rc = volumes_upload_table(e))) return rc;
@@ -2837,13 +2852,9 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
             (rc = dev_alloc(&e->d_dyn, (size_t)kObsMax))) {
             obstacles_free(e); return rc;
         }
-        hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&e->h_obsStage), sizeof(sph::ObsRec) * kObsMax * SphEngine::kObsSlots, hipHostMallocDefault);
-        if (er == hipSuccess) er = hipHostMalloc(reinterpret_cast<void**>(&e->h_dynStage), sizeof(sph::ObsDyn) * SphEngine::kObsSlots, hipHostMallocDefault);
-        for (auto& ev : e->evObs) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        for (auto& ev : e->evDyn) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        hipError_t er = e->obsStage.create(e->stream, (size_t)kObsMax);
+        if (er == hipSuccess) er = e->dynStage.create(e->stream, 1);
         if (er != hipSuccess) { obstacles_free(e); return fail(SPH_ERR_HIP, "obstacle staging: %s", hipGetErrorString(er)); }
-        for (auto& ev : e->evObs) HIP_TRY(hipEventRecord(ev, e->stream));
-        for (auto& ev : e->evDyn) HIP_TRY(hipEventRecord(ev, e->stream));
         HIP_TRY(hipMemsetAsync(e->d_dyn, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
         e->obsK = 0;
     }
@@ -2853,11 +2864,10 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
         for (auto& on : e->dynOn) on = false;
     }
     sph::ObsRec* slot = nullptr;
-    if ((rc = obstacles_slot(e, &slot))) return rc;
+    if ((rc = e->obsStage.next(&slot))) return rc;
     for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], true, slot[i]);
-    const int slotNo = (e->obsSlot + SphEngine::kObsSlots - 1) % SphEngine::kObsSlots;
     HIP_TRY(hipMemcpyAsync(e->d_obs, slot, sizeof(sph::ObsRec) * (size_t)count, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipEventRecord(e->evObs[slotNo], e->stream));
+    if ((rc = e->obsStage.commit(e->stream))) return rc;
     if (count != e->obsK) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (another count: the sums restart)
     e->obsK = count;
     for (int i = 0; i < count; ++i) e->obsShape[i] = obs[i].shape;
@@ -2866,18 +2876,15 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
 
 int sph_obstacles_set_motion(SphEngine* e, int index, const float vel[3], const float omega[3]) {
     if (!e || !vel || !omega) return fail(SPH_ERR_ARG, "null argument");
-    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
-    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
-    if (!obs_all_finite(vel, 3) || !obs_all_finite(omega, 3)) return fail(SPH_ERR_ARG, "obstacle %d: velocity not finite", index);
     int rc;
+    if ((rc = obstacles_refuse_slab(e)) || (rc = obstacle_index_check(e, index))) return rc;
+    if (!obs_all_finite(vel, 3) || !obs_all_finite(omega, 3)) return fail(SPH_ERR_ARG, "obstacle %d: velocity not finite", index);
     sph::ObsRec* slot = nullptr;
-    if ((rc = obstacles_slot(e, &slot))) return rc;
-    const int slotNo = (e->obsSlot + SphEngine::kObsSlots - 1) % SphEngine::kObsSlots;
+    if ((rc = e->obsStage.next(&slot))) return rc;
     for (int a = 0; a < 3; ++a) { slot[0].v[a] = vel[a]; slot[0].w[a] = omega[a]; }
     static_assert(offsetof(sph::ObsRec, w) == offsetof(sph::ObsRec, v) + 3 * sizeof(float), "v and w are adjacent");
     HIP_TRY(hipMemcpyAsync(&e->d_obs[index].v[0], &slot[0].v[0], 6 * sizeof(float), hipMemcpyHostToDevice, e->stream));   // (the pose stays the device's)
-    HIP_TRY(hipEventRecord(e->evObs[slotNo], e->stream));
-    return SPH_OK;
+    return e->obsStage.commit(e->stream);
 }
 
 int sph_obstacles_get(SphEngine* e, SphObstacle* out, int cap, int* countOut) {
@@ -2910,10 +2917,10 @@ int sph_obstacles_impulses(SphEngine* e, double* out6, int cap, double* timeOut,
     return SPH_OK;
 }
 
-int sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMass, SphParticle* particles, size_t n, double* impulses6) {
-    int rc;
-    if ((rc = obstacles_check(obs, count))) return rc;
-    if (n && !particles) return fail(SPH_ERR_ARG, "null particles");
+// The obstacle step on host records (arguments already checked): every live particle against bodies 0..count-1 in order, body b as the
+// lattice vols[bindings[b]] where it is bound (bindings null: no body is; obs_hit is obs_hit_t with no lattice).
+static void obstacles_apply_loop(const SphObstacle* obs, int count, const sph::VolRec* vols, const int* bindings, float particleMass,
+                                 SphParticle* particles, size_t n, double* impulses6) {
     sph::ObsRec recs[kObsMax];
     for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], false, recs[i]);
     double acc[kObsRow] = {0.0};
@@ -2925,13 +2932,21 @@ int sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMa
         bool changed = false;
         for (int b = 0; b < count; ++b) {
             double t[kObsTerms];
-            if (!sph::obs_hit(recs[b], particleMass, px, py, pz, vx, vy, vz, t)) continue;
+            const sph::VolRec* vol = (bindings && bindings[b] >= 0) ? &vols[bindings[b]] : nullptr;
+            if (!sph::obs_hit_t<true>(recs[b], vol, particleMass, px, py, pz, vx, vy, vz, t)) continue;
             changed = true;
             for (int c = 0; c < kObsTerms; ++c) acc[b * kObsTerms + c] += t[c];
         }
         if (changed) { p.pos[0] = px; p.pos[1] = py; p.pos[2] = pz; p.vel[0] = vx; p.vel[1] = vy; p.vel[2] = vz; }
     }
     if (impulses6) std::memcpy(impulses6, acc, sizeof(double) * kObsTerms * (size_t)count);
+}
+
+int sph_obstacles_apply_host(const SphObstacle* obs, int count, float particleMass, SphParticle* particles, size_t n, double* impulses6) {
+    int rc;
+    if ((rc = obstacles_check(obs, count))) return rc;
+    if (n && !particles) return fail(SPH_ERR_ARG, "null particles");
+    obstacles_apply_loop(obs, count, nullptr, nullptr, particleMass, particles, n, impulses6);
     return SPH_OK;
 }
 
@@ -2985,18 +3000,15 @@ static int dynamics_to_rec(const SphObstacleDynamics& d, int index, sph::ObsDyn&
 
 int sph_obstacles_set_dynamics(SphEngine* e, int index, const SphObstacleDynamics* dyn) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (e->slab) return fail(SPH_ERR_STATE, "obstacles on a z-slab engine are not supported");
-    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
     int rc;
-    sph::ObsDyn rec;
+    if ((rc = obstacles_refuse_slab(e)) || (rc = obstacle_index_check(e, index))) return rc;
+    sph::ObsDyn rec, *slot = nullptr;
     std::memset(&rec, 0, sizeof(rec));
     if (dyn && (rc = dynamics_to_rec(*dyn, index, rec))) return rc;
-    const int i = e->dynSlot;
-    e->dynSlot = (i + 1) % SphEngine::kObsSlots;
-    HIP_TRY(hipEventSynchronize(e->evDyn[i]));
-    e->h_dynStage[i] = rec;
-    HIP_TRY(hipMemcpyAsync(&e->d_dyn[index], &e->h_dynStage[i], sizeof(sph::ObsDyn), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipEventRecord(e->evDyn[i], e->stream));
+    if ((rc = e->dynStage.next(&slot))) return rc;
+    *slot = rec;
+    HIP_TRY(hipMemcpyAsync(&e->d_dyn[index], slot, sizeof(sph::ObsDyn), hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->dynStage.commit(e->stream))) return rc;
     const bool on = dyn != nullptr;
     e->dynCount += (on ? 1 : 0) - (e->dynOn[index] ? 1 : 0);
     e->dynOn[index] = on;
@@ -3006,7 +3018,8 @@ int sph_obstacles_set_dynamics(SphEngine* e, int index, const SphObstacleDynamic
 
 int sph_obstacles_get_dynamics(SphEngine* e, int index, SphObstacleDynamics* out, int* dynamicOut) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    int rc;
+    if ((rc = obstacle_index_check(e, index))) return rc;
     if (out) {
         if (e->dynOn[index]) *out = e->dynSet[index];
         else sph_obstacle_dynamics_default(out);
@@ -3039,19 +3052,6 @@ int sph_obstacles_step_host(SphObstacle* obs, const SphObstacleDynamics* dyn, in
 }
 
 // ---- volumes: signed distance lattices as bodies, mesh -> signed distance (sph_volume.h) ---------
-static int volume_check_lattice(const int dims[3], const float spacing[3], long long* totalOut, int least = 2) {
-    if (!dims || !spacing) return fail(SPH_ERR_ARG, "null argument");
-    long long total = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (dims[a] < least) return fail(SPH_ERR_ARG, "lattice dimension %d is %d (must be >= %d)", a, dims[a], least);
-        if (!std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) return fail(SPH_ERR_ARG, "lattice spacing %d is %g (must be finite and > 0)", a, (double)spacing[a]);
-        total *= dims[a];
-        if (total > 2147483647ll) return fail(SPH_ERR_ARG, "lattice of %d x %d x %d points exceeds 2^31 - 1 points", dims[0], dims[1], dims[2]);
-    }
-    if (totalOut) *totalOut = total;
-    return SPH_OK;
-}
-
 // A free slot and, on the first call, the device table with its staging.
 static int volume_free_slot(SphEngine* e, int* idOut) {
     int rc, id = -1;
@@ -3059,10 +3059,8 @@ static int volume_free_slot(SphEngine* e, int* idOut) {
     if (id < 0) return fail(SPH_ERR_CAPACITY, "all %d volume slots are in use", kVolMax);
     if (!e->d_volTab) {
         if ((rc = dev_alloc(&e->d_volTab, 1))) return rc;
-        hipError_t er = hipHostMalloc(reinterpret_cast<void**>(&e->h_volStage), sizeof(sph::VolTable) * SphEngine::kObsSlots, hipHostMallocDefault);
-        for (auto& ev : e->evVol) if (er == hipSuccess) er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        const hipError_t er = e->volStage.create(e->stream, 1);
         if (er != hipSuccess) { volumes_free(e); return fail(SPH_ERR_HIP, "volume staging: %s", hipGetErrorString(er)); }
-        for (auto& ev : e->evVol) HIP_TRY(hipEventRecord(ev, e->stream));
     }
     *idOut = id;
     return SPH_OK;
@@ -3078,10 +3076,9 @@ static int volume_adopt(SphEngine* e, int id, float* d, const int dims[3], const
 
 int sph_volume_create(SphEngine* e, const float* values, const int dims[3], const float spacing[3], int onDevice, int* idOut) {
     if (!e || !values || !idOut) return fail(SPH_ERR_ARG, "null argument");
-    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
     int rc, id = -1;
     long long total = 0;
-    if ((rc = volume_check_lattice(dims, spacing, &total)) || (rc = volume_free_slot(e, &id))) return rc;
+    if ((rc = volumes_refuse_slab(e)) || (rc = check_lattice(dims, spacing, 2, &total)) || (rc = volume_free_slot(e, &id))) return rc;
     float* d = nullptr;
     if ((rc = dev_alloc(&d, (size_t)total))) return rc;
     hipError_t er = hipMemcpyAsync(d, values, (size_t)total * sizeof(float), onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream);
@@ -3126,18 +3123,18 @@ int sph_volume_moments(SphEngine* e, int id, double out[10]) {
     if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
     int rc;
     if ((rc = volume_slot_check(e, id))) return rc;
-    if (!e->d_momPart && ((rc = dev_alloc(&e->d_momPart, (size_t)kMomGrid * kMomTerms)) || (rc = dev_alloc(&e->d_momOut, (size_t)kMomTerms)))) return rc;
+    if ((rc = e->d_momPart.grow(e, (size_t)kMomGrid * kMomTerms)) || (rc = e->d_momOut.grow(e, (size_t)kMomTerms))) return rc;
     const sph::VolRec& v = e->volTab.vol[id];
     const long long total = (long long)v.dims[0] * v.dims[1] * v.dims[2];
     const int rows = (int)std::min<long long>(kMomGrid, (total + kMomSweep - 1) / kMomSweep);
     const double cell = ((double)v.spacing[0] * (double)v.spacing[1]) * (double)v.spacing[2];
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_volume_moments, dim3(rows), dim3(kMomBlock), 0, e->stream, v, sph::vol_diagonal(v.spacing), (unsigned)total, e->d_momPart);
-        hipLaunchKernelGGL(k_volume_moments_finish, dim3(1), dim3(kMomFinishBlock), 0, e->stream, (const double*)e->d_momPart, rows, cell, e->d_momOut);
+        hipLaunchKernelGGL(k_volume_moments, dim3(rows), dim3(kMomBlock), 0, e->stream, v, sph::vol_diagonal(v.spacing), (unsigned)total, e->d_momPart.p);
+        hipLaunchKernelGGL(k_volume_moments_finish, dim3(1), dim3(kMomFinishBlock), 0, e->stream, (const double*)e->d_momPart.p, rows, cell, e->d_momOut.p);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, e->d_momOut, sizeof(double) * kMomTerms, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(out, e->d_momOut.p, sizeof(double) * kMomTerms, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
@@ -3145,7 +3142,7 @@ int sph_volume_moments(SphEngine* e, int id, double out[10]) {
 int sph_volume_moments_host(const float* values, const int dims[3], const float spacing[3], double out[10]) {
     if (!values || !out) return fail(SPH_ERR_ARG, "null argument");
     int rc;
-    if ((rc = volume_check_lattice(dims, spacing, nullptr))) return rc;
+    if ((rc = check_lattice(dims, spacing, 2, nullptr))) return rc;
     sph::VolRec v;
     sph::vol_make(values, dims, spacing, v);
     const float diag = sph::vol_diagonal(v.spacing);
@@ -3163,9 +3160,8 @@ int sph_volume_moments_host(const float* values, const int dims[3], const float 
 
 int sph_obstacles_bind_volume(SphEngine* e, int index, int id) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
-    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
     int rc;
+    if ((rc = volumes_refuse_slab(e)) || (rc = obstacle_index_check(e, index))) return rc;
     if (id >= 0) {
         if ((rc = volume_slot_check(e, id))) return rc;
         if (e->obsShape[index] != SPH_OBSTACLE_BOX) return fail(SPH_ERR_ARG, "obstacle %d is not a box: a volume binds to SPH_OBSTACLE_BOX only", index);
@@ -3180,21 +3176,22 @@ int sph_obstacles_bind_volume(SphEngine* e, int index, int id) {
 
 int sph_obstacles_volume(SphEngine* e, int index, int* idOut) {
     if (!e || !idOut) return fail(SPH_ERR_ARG, "null argument");
-    if (index < 0 || index >= e->obsK) return fail(SPH_ERR_ARG, "obstacle index %d outside 0..%d", index, e->obsK - 1);
+    int rc;
+    if ((rc = obstacle_index_check(e, index))) return rc;
     *idOut = e->volTab.bind[index];
     return SPH_OK;
 }
 
 static int volume_host_check(const SphVolumeHost& v) {
     if (!v.values) return fail(SPH_ERR_ARG, "null lattice values");
-    return volume_check_lattice(v.dims, v.spacing, nullptr);
+    return check_lattice(v.dims, v.spacing, 2, nullptr);
 }
 
 int sph_volume_sample_host(const float* values, const int dims[3], const float spacing[3], const float local[3], float* phiOut, float gradOut[3],
                            int* insideOut) {
     if (!values || !local || !phiOut || !gradOut || !insideOut) return fail(SPH_ERR_ARG, "null argument");
     int rc;
-    if ((rc = volume_check_lattice(dims, spacing, nullptr))) return rc;
+    if ((rc = check_lattice(dims, spacing, 2, nullptr))) return rc;
     sph::VolRec v;
     sph::vol_make(values, dims, spacing, v);
     float phi = std::nanf(""), g[3] = {0.0f, 0.0f, 0.0f};
@@ -3223,24 +3220,7 @@ int sph_obstacles_apply_host_volumes(const SphObstacle* obs, int count, const Sp
         if (bindings[i] >= volumeCount) return fail(SPH_ERR_ARG, "obstacle %d: volume %d outside 0..%d", i, bindings[i], volumeCount - 1);
         if (obs[i].shape != SPH_OBSTACLE_BOX) return fail(SPH_ERR_ARG, "obstacle %d is not a box: a volume binds to SPH_OBSTACLE_BOX only", i);
     }
-    sph::ObsRec recs[kObsMax];
-    for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], false, recs[i]);
-    double acc[kObsRow] = {0.0};
-    for (size_t i = 0; i < n; ++i) {
-        SphParticle& p = particles[i];
-        if (p.isGhost != 0) continue;
-        float px = p.pos[0], py = p.pos[1], pz = p.pos[2], vx = p.vel[0], vy = p.vel[1], vz = p.vel[2];
-        if (!std::isfinite(px) || !std::isfinite(py) || !std::isfinite(pz)) continue;
-        bool changed = false;
-        for (int b = 0; b < count; ++b) {
-            double t[kObsTerms];
-            if (!sph::obs_hit_t<true>(recs[b], bindings[b] >= 0 ? &vols[bindings[b]] : nullptr, particleMass, px, py, pz, vx, vy, vz, t)) continue;
-            changed = true;
-            for (int c = 0; c < kObsTerms; ++c) acc[b * kObsTerms + c] += t[c];
-        }
-        if (changed) { p.pos[0] = px; p.pos[1] = py; p.pos[2] = pz; p.vel[0] = vx; p.vel[1] = vy; p.vel[2] = vz; }
-    }
-    if (impulses6) std::memcpy(impulses6, acc, sizeof(double) * kObsTerms * (size_t)count);
+    obstacles_apply_loop(obs, count, vols, bindings, particleMass, particles, n, impulses6);
     return SPH_OK;
 }
 
@@ -3248,7 +3228,7 @@ static int mesh_check(const float* vertices3, size_t nv, const uint32_t* triangl
                       const int dims[3], long long* totalOut) {
     if (!vertices3 || !triangles3 || !origin) return fail(SPH_ERR_ARG, "null argument");
     int rc;
-    if ((rc = volume_check_lattice(dims, spacing, totalOut, 1))) return rc;                       // (a lattice of points as in sph_sample_lattice: dims >= 1)
+    if ((rc = check_lattice(dims, spacing, 1, totalOut))) return rc;                       // (a lattice of points as in sph_sample_lattice: dims >= 1)
     if (nt == 0 || nt > 2147483647ull / 3 || nv == 0 || nv > 0xFFFFFFFFull) return fail(SPH_ERR_ARG, "a mesh of %zu vertices and %zu triangles", nv, nt);
     if (!obs_all_finite(origin, 3)) return fail(SPH_ERR_ARG, "lattice origin not finite");
     for (size_t i = 0; i < 3 * nv; ++i) if (!std::isfinite(vertices3[i])) return fail(SPH_ERR_ARG, "vertex %zu is not finite", i / 3);
@@ -3270,18 +3250,9 @@ int sph_mesh_distance(SphEngine* e, const float* vertices3, size_t nv, const uin
     splits = std::max(1, std::min(splits, 64));
     const int per = (int)((nt + (size_t)splits - 1) / (size_t)splits);
     const size_t part = (size_t)splits * (size_t)total;
-    if (3 * nv > e->meshVertCap || 3 * nt > e->meshTriCap || part > e->meshPartCap) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (3 * nv > e->meshVertCap) { dev_free(e->d_meshVerts); e->meshVertCap = 0; if ((rc = dev_alloc(&e->d_meshVerts, 3 * nv))) return rc; e->meshVertCap = 3 * nv; }
-        if (3 * nt > e->meshTriCap) { dev_free(e->d_meshTris); e->meshTriCap = 0; if ((rc = dev_alloc(&e->d_meshTris, 3 * nt))) return rc; e->meshTriCap = 3 * nt; }
-        if (part > e->meshPartCap) {
-            dev_free(e->d_meshD2); dev_free(e->d_meshW); e->meshPartCap = 0;
-            if ((rc = dev_alloc(&e->d_meshD2, part)) || (rc = dev_alloc(&e->d_meshW, part))) return rc;
-            e->meshPartCap = part;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(e->d_meshVerts, vertices3, 3 * nv * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_meshTris, triangles3, 3 * nt * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->d_meshVerts.grow(e, 3 * nv)) || (rc = e->d_meshTris.grow(e, 3 * nt)) || (rc = e->d_meshD2.grow(e, part)) || (rc = e->d_meshW.grow(e, part))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_meshVerts.p, vertices3, 3 * nv * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_meshTris.p, triangles3, 3 * nt * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     sph::MeshLattice L;
     L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
     L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
@@ -3289,9 +3260,9 @@ int sph_mesh_distance(SphEngine* e, const float* vertices3, size_t nv, const uin
     L.total = total;
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_mesh_distance, dim3((unsigned)blocks, (unsigned)splits), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshVerts,
-                           (const uint32_t*)e->d_meshTris, (int)nt, per, L, e->d_meshD2, e->d_meshW);
-        hipLaunchKernelGGL(k_mesh_merge, dim3((unsigned)blocks), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshD2, (const double*)e->d_meshW, splits,
+        hipLaunchKernelGGL(k_mesh_distance, dim3((unsigned)blocks, (unsigned)splits), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshVerts.p,
+                           (const uint32_t*)e->d_meshTris.p, (int)nt, per, L, e->d_meshD2.p, e->d_meshW.p);
+        hipLaunchKernelGGL(k_mesh_merge, dim3((unsigned)blocks), dim3(kMeshBlock), 0, e->stream, (const float*)e->d_meshD2.p, (const double*)e->d_meshW.p, splits,
                            total, devOut);
     }
     HIP_TRY(hipGetLastError());
@@ -3301,10 +3272,9 @@ int sph_mesh_distance(SphEngine* e, const float* vertices3, size_t nv, const uin
 int sph_volume_from_mesh(SphEngine* e, const float* vertices3, size_t nv, const uint32_t* triangles3, size_t nt, const float center[3],
                          const float spacing[3], const int dims[3], int* idOut) {
     if (!e || !center || !idOut) return fail(SPH_ERR_ARG, "null argument");
-    if (e->slab) return fail(SPH_ERR_STATE, "volumes on a z-slab engine are not supported");
     int rc, id = -1;
     long long total = 0;
-    if ((rc = volume_check_lattice(dims, spacing, &total)) || (rc = mesh_check(vertices3, nv, triangles3, nt, center, spacing, dims, &total)) ||
+    if ((rc = volumes_refuse_slab(e)) || (rc = check_lattice(dims, spacing, 2, &total)) || (rc = mesh_check(vertices3, nv, triangles3, nt, center, spacing, dims, &total)) ||
         (rc = volume_free_slot(e, &id))) return rc;
     float origin[3];
     for (int a = 0; a < 3; ++a) origin[a] = center[a] - (0.5f * (float)(dims[a] - 1)) * spacing[a];
