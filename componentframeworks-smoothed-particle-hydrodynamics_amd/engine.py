@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's `SPHFluidGPU` class over the C-ABI (include/sph_abi.h).
 
 The reference boundary is the C++ class SPHFluidGPU
-(/root/reference/ComponentFramework/SPHFluid3D.h:26-210): public methods plus public
+(ComponentFramework/SPHFluid3D.h:26-210): public methods plus public
 `param_*` data members that the caller pokes directly (Scene0p.cpp:936-1056) and that are
 re-read at every DispatchCompute (SPHFluid3D.cpp:458-506).  This module keeps those names:
 `DispatchCompute`, `ResetSimulation`, `ApplyWaveImpulse`, `EffectiveHalf`, `GetNumFluids`,
@@ -22,7 +22,9 @@ import numpy as np
 
 from . import build as _build
 
+# ---- constants and structs, in the order of include/sph_abi.h ---------------------------------------------------------
 FLT_MAX = 3.4028234663852886e38
+SPH_ERR_TIMEOUT = -5
 
 # 80-byte record, SPHFluid3D.h:12-24
 PARTICLE_DTYPE = np.dtype(
@@ -54,6 +56,10 @@ class SphParams(C.Structure):
     ]
 
 
+class SphGridInfo(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("numCells", C.c_int32), ("gridMin", C.c_float * 3), ("cellSize", C.c_float)]
+
+
 class SphFountain(C.Structure):
     """fountain* members of the reference class (SPHFluid3D.h:161-168), same names."""
     _fields_ = [("fountainMode", C.c_int32), ("fountainOffset", C.c_float * 3), ("fountainRadius", C.c_float),
@@ -70,56 +76,10 @@ class SphRiver(C.Structure):
                 ("riverPhase", C.c_float), ("riverChannelWidth", C.c_float), ("riverChannelDepth", C.c_float), ("riverSlopeDrop", C.c_float)]
 
 
-class SphGridInfo(C.Structure):
-    _fields_ = [("dims", C.c_int32 * 3), ("numCells", C.c_int32), ("gridMin", C.c_float * 3), ("cellSize", C.c_float)]
-
-
-# option / kernel-class constants of sph_abi.h
+# option constants of sph_abi.h
 SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_GRID_BUILD, SPH_OPT_AOS_MODE, SPH_OPT_TIMING, SPH_OPT_DEBUG = 1, 2, 3, 4, 100
 SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = 5, 6
 SPH_OPT_MESH_SPLIT = 7
-KERNEL_CLASSES = ("bin", "scan", "scatter", "sph", "writeback", "impulse", "other")
-
-# every symbol include/sph_abi.h declares (checked by tests/test_abi.py)
-class SphSlabIntent(C.Structure):
-    """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
-    _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
-                ("sendHalo", C.c_uint32 * 2), ("sendMig", C.c_uint32 * 2), ("recvHalo", C.c_uint32 * 2), ("recvMig", C.c_uint32 * 2),
-                ("holdEvents", C.c_uint32), ("paramsHash", C.c_uint32), ("flags", C.c_uint32), ("zRange", C.c_uint32)]
-
-
-assert C.sizeof(SphSlabIntent) == 64
-SPH_ERR_TIMEOUT = -5
-
-
-ABI_SYMBOLS = (
-    "sph_abi_version", "sph_params_default", "sph_rotation_mat3", "sph_effective_half",
-    "sph_compute_grid_extents", "sph_spawn_particles", "sph_last_error", "sph_create",
-    "sph_create_from_particles", "sph_destroy", "sph_reset", "sph_set_params", "sph_get_params",
-    "sph_set_option", "sph_get_option", "sph_dispatch", "sph_dispatch_n", "sph_apply_wave_impulse",
-    "sph_num_particles", "sph_grid_info", "sph_upload_particles", "sph_download_particles",
-    "sph_device_particles", "sph_pack_render_buffer", "sph_initial_particles", "sph_download_grid", "sph_sync", "sph_kernel_times",
-    "sph_debug_counters", "sph_apply_vortex_impulse", "sph_apply_attractor_impulse", "sph_set_stencil_targets",
-    "sph_apply_stencil_attract", "sph_apply_curl_flow", "sph_fountain_default", "sph_set_fountain", "sph_get_fountain", "sph_create_slab", "sph_slab_pack", "sph_slab_unpack", "sph_slab_download",
-    "sph_slab_alloc_faces", "sph_slab_face_buffer", "sph_slab_pack_async", "sph_slab_unpack_async", "sph_slab_status",
-    "sph_comm_unique_id", "sph_comm_create", "sph_comm_destroy", "sph_comm_selftest", "sph_comm_selftest_timed", "sph_slab_exchange",
-    "sph_slab_step_begin", "sph_slab_step_finish", "sph_slab_step_finish_local",
-    "sph_slab_face_bytes", "sph_slab_clear_flags", "sph_slab_message_bytes", "sph_slab_message_records", "sph_slab_step_times",
-    "sph_river_default", "sph_generate_river_terrain", "sph_spawn_river_particles", "sph_set_river", "sph_get_river",
-    "sph_slab_set_verify", "sph_slab_set_deadline", "sph_slab_plan", "sph_slab_plans_agree", "sph_sync_deadline",
-    "sph_slab_debug_tight_messages", "sph_comm_selftest_faces",
-    "sph_sample_points", "sph_sample_points_device", "sph_sample_lattice",
-    "sph_extract_surface", "sph_extract_surface_volume", "sph_surface_download",
-    "sph_statistics", "sph_statistics_device",
-    "sph_tracers_set", "sph_tracers_set_device", "sph_tracers_count", "sph_tracers_info", "sph_tracers_download", "sph_tracers_device",
-    "sph_tracers_history",
-    "sph_obstacle_default", "sph_obstacles_set", "sph_obstacles_set_motion", "sph_obstacles_get", "sph_obstacles_impulses",
-    "sph_obstacles_apply_host", "sph_obstacles_advance_host",
-    "sph_volume_create", "sph_volume_destroy", "sph_volume_info", "sph_volume_sample_host", "sph_obstacles_bind_volume", "sph_obstacles_volume",
-    "sph_obstacles_apply_host_volumes", "sph_mesh_distance", "sph_mesh_distance_host", "sph_volume_from_mesh",
-    "sph_obstacle_dynamics_default", "sph_obstacles_set_dynamics", "sph_obstacles_get_dynamics", "sph_obstacles_step_host",
-    "sph_volume_moments", "sph_volume_moments_host",
-)
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -134,10 +94,52 @@ class SphSample(C.Structure):
 
 
 assert C.sizeof(SphSample) == 32
-SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("pressure", "<f4"), ("count", "<u4"),
-                         ("vel", "<f4", (3,)), ("pad", "<f4")])
+SAMPLE_DTYPE = np.dtype(SphSample)
 assert SAMPLE_DTYPE.itemsize == 32
 SPH_FIELD_DENSITY, SPH_FIELD_FRACTION, SPH_FIELD_PRESSURE, SPH_FIELD_SPEED, SPH_FIELD_ALL = 0, 1, 2, 3, 4
+
+
+SURFACE_VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,))])     # struct SphSurfaceVertex
+assert SURFACE_VERTEX_DTYPE.itemsize == 24
+
+
+class SphSurface(C.Structure):
+    """struct SphSurface of include/sph_abi.h: counts and borrowed device arrays of the last extracted surface."""
+    _fields_ = [("numVertices", C.c_uint32), ("numTriangles", C.c_uint32), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
+
+
+class SphStatExtremum(C.Structure):
+    """struct SphStatExtremum of include/sph_abi.h: an extreme value and the particle id that attains it."""
+    _fields_ = [("value", C.c_float), ("id", C.c_uint32)]
+
+
+class SphStatistics(C.Structure):
+    """struct SphStatistics of include/sph_abi.h (DESIGN.md section 3c): 832 bytes."""
+    _fields_ = [
+        ("numRecords", C.c_uint64), ("numFluid", C.c_uint64), ("numActiveGhosts", C.c_uint64), ("numInactiveGhosts", C.c_uint64),
+        ("numOther", C.c_uint64), ("numNonFinite", C.c_uint64), ("numCounted", C.c_uint64), ("numEscaped", C.c_uint64),
+        ("firstNonFiniteId", C.c_uint32), ("firstEscapedId", C.c_uint32),
+        ("minPos", SphStatExtremum * 3), ("maxPos", SphStatExtremum * 3), ("minDensity", SphStatExtremum), ("maxDensity", SphStatExtremum),
+        ("minPressure", SphStatExtremum), ("maxPressure", SphStatExtremum), ("maxFoam", SphStatExtremum), ("maxSpeed2", SphStatExtremum),
+        ("maxSpeed", C.c_float), ("reserved0", C.c_uint32),
+        ("sumPos", C.c_double * 3), ("sumVel", C.c_double * 3), ("sumSpeed2", C.c_double), ("sumDensity", C.c_double),
+        ("sumDensity2", C.c_double), ("sumPressure", C.c_double), ("sumFoam", C.c_double), ("sumInvDensity", C.c_double),
+        ("sumAngular", C.c_double * 3),
+        ("occupiedCells", C.c_uint64), ("maxCellCount", C.c_uint32), ("maxCellIndex", C.c_uint32),
+        ("occupancy", C.c_uint64 * 65),
+    ]
+
+
+assert C.sizeof(SphStatistics) == 832
+
+
+class SphHistogramSpec(C.Structure):
+    """struct SphHistogramSpec of include/sph_abi.h: field (SPH_STAT_*), bins (1 .. 1024), lo < hi."""
+    _fields_ = [("field", C.c_int32), ("bins", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM = range(7)
+SPH_STAT_MAX_SPECS, SPH_STAT_MAX_BINS = 4, 1024
 
 
 class SphTracer(C.Structure):
@@ -146,7 +148,7 @@ class SphTracer(C.Structure):
 
 
 assert C.sizeof(SphTracer) == 32
-TRACER_DTYPE = np.dtype([("pos", "<f4", (3,)), ("age", "<f4"), ("vel", "<f4", (3,)), ("fraction", "<f4")])
+TRACER_DTYPE = np.dtype(SphTracer)
 assert TRACER_DTYPE.itemsize == 32
 SPH_TRACER_EULER, SPH_TRACER_MIDPOINT = 0, 1
 
@@ -158,12 +160,376 @@ class SphObstacle(C.Structure):
 
 
 assert C.sizeof(SphObstacle) == 76
-OBSTACLE_DTYPE = np.dtype([("shape", "<i4"), ("size", "<f4", (3,)), ("center", "<f4", (3,)), ("rotation", "<f4", (4,)),
-                           ("vel", "<f4", (3,)), ("omega", "<f4", (3,)), ("restitution", "<f4"), ("friction", "<f4")])
+OBSTACLE_DTYPE = np.dtype(SphObstacle)
 assert OBSTACLE_DTYPE.itemsize == 76
 SPH_MAX_OBSTACLES = 16
-SPH_MAX_VOLUMES = 16
 SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE = 0, 1, 2
+
+
+class SphVolumeHost(C.Structure):
+    """struct SphVolumeHost of include/sph_abi.h: one lattice of signed distances in host memory (see obstacles_apply_host_volumes)."""
+    _fields_ = [("values", C.c_void_p), ("dims", C.c_int * 3), ("spacing", C.c_float * 3)]
+
+
+SPH_MAX_VOLUMES = 16
+
+
+class SphObstacleDynamics(C.Structure):
+    """struct SphObstacleDynamics of include/sph_abi.h: what makes a body of the obstacle set dynamic (see dynamics() and
+    SPHFluidGPU.set_obstacle_dynamics)."""
+    _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 6), ("com", C.c_float * 3), ("gravityScale", C.c_float),
+                ("force", C.c_float * 3), ("torque", C.c_float * 3), ("linearDamping", C.c_float), ("angularDamping", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+assert C.sizeof(SphObstacleDynamics) == 80
+DYNAMICS_DTYPE = np.dtype(SphObstacleDynamics)
+assert DYNAMICS_DTYPE.itemsize == 80
+SPH_DYNAMICS_CONFINED = 1
+
+
+class SphSlabIntent(C.Structure):
+    """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
+    _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
+                ("sendHalo", C.c_uint32 * 2), ("sendMig", C.c_uint32 * 2), ("recvHalo", C.c_uint32 * 2), ("recvMig", C.c_uint32 * 2),
+                ("holdEvents", C.c_uint32), ("paramsHash", C.c_uint32), ("flags", C.c_uint32), ("zRange", C.c_uint32)]
+
+
+assert C.sizeof(SphSlabIntent) == 64
+KERNEL_CLASSES = ("bin", "scan", "scatter", "sph", "writeback", "impulse", "other")     # SPH_K_* of "measurement"
+
+
+# ---- the C-ABI: every function include/sph_abi.h declares, in its order, as name -> (restype, argtypes) -------------------
+# The one statement of the binding: ABI_SYMBOLS and load_library() derive from it, tests/test_abi.py holds it against the header's
+# prototypes.  A record that only passes through (particles, samples, tracers, obstacles ...) crosses as c_void_p.
+_int, _f, _d, _sz, _u32, _u64, _vp = C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32, C.c_uint64, C.c_void_p
+_P = C.POINTER
+_pf, _pi, _pp, _gp = _P(_f), _P(_int), _P(SphParams), _P(SphGridInfo)
+_ABI = {
+    # host-only helpers (no device needed)
+    "sph_abi_version": (_int, []),
+    "sph_params_default": (_int, [_pp]),
+    "sph_rotation_mat3": (_int, [_pf, _pf]),
+    "sph_effective_half": (_int, [_pp, _pf]),
+    "sph_compute_grid_extents": (_int, [_pp, _gp]),
+    "sph_spawn_particles": (_int, [_pp, _sz, _u32, _vp, _P(_sz), _pf]),
+    "sph_last_error": (C.c_char_p, []),
+    # lifetime
+    "sph_create": (_int, [_P(_vp), _sz, _pp, _u32, _vp]),
+    "sph_create_from_particles": (_int, [_P(_vp), _vp, _sz, _pp, _vp]),
+    "sph_destroy": (_int, [_vp]),
+    "sph_reset": (_int, [_vp, _sz, _u32]),
+    # parameters
+    "sph_set_params": (_int, [_vp, _pp]),
+    "sph_get_params": (_int, [_vp, _pp]),
+    "sph_set_option": (_int, [_vp, _int, _int]),
+    "sph_get_option": (_int, [_vp, _int, _pi]),
+    # the hot path
+    "sph_dispatch": (_int, [_vp, _f]),
+    "sph_dispatch_n": (_int, [_vp, _f, _int]),
+    "sph_apply_wave_impulse": (_int, [_vp, _f, _f, _f, _pf, _f, _f]),
+    "sph_apply_vortex_impulse": (_int, [_vp, _f, _f]),
+    "sph_apply_attractor_impulse": (_int, [_vp, _pf, _f, _f]),
+    "sph_set_stencil_targets": (_int, [_vp, _vp, _sz]),
+    "sph_apply_stencil_attract": (_int, [_vp, _f, _f]),
+    "sph_apply_curl_flow": (_int, [_vp, _f, _f, _f]),
+    "sph_fountain_default": (None, [_P(SphFountain)]),
+    "sph_set_fountain": (_int, [_vp, _P(SphFountain)]),
+    "sph_get_fountain": (_int, [_vp, _P(SphFountain)]),
+    "sph_river_default": (None, [_P(SphRiver)]),
+    "sph_generate_river_terrain": (_int, [_pp, _int, _P(SphRiver), _vp]),
+    "sph_spawn_river_particles": (_int, [_pp, _P(SphRiver), _vp, _sz, _u32, _vp, _P(_sz), _pf]),
+    "sph_set_river": (_int, [_vp, _P(SphRiver), _vp]),
+    "sph_get_river": (_int, [_vp, _P(SphRiver)]),
+    # data
+    "sph_num_particles": (_sz, [_vp]),
+    "sph_grid_info": (_int, [_vp, _gp]),
+    "sph_upload_particles": (_int, [_vp, _vp, _sz]),
+    "sph_download_particles": (_int, [_vp, _vp, _sz]),
+    "sph_device_particles": (_int, [_vp, _P(_vp)]),
+    "sph_pack_render_buffer": (_int, [_vp, _vp, _sz, _int]),
+    "sph_initial_particles": (_int, [_vp, _vp, _sz]),
+    "sph_download_grid": (_int, [_vp, _vp, _sz, _vp, _sz]),
+    "sph_sync": (_int, [_vp]),
+    "sph_debug_counters": (_int, [_vp, _P(_u64), _int, _int]),
+    # field sampling
+    "sph_sample_points": (_int, [_vp, _vp, _sz, _vp]),
+    "sph_sample_points_device": (_int, [_vp, _vp, _sz, _vp]),
+    "sph_sample_lattice": (_int, [_vp, _pf, _pf, _pi, _int, _vp]),
+    # iso-surface
+    "sph_extract_surface": (_int, [_vp, _pf, _pf, _pi, _int, _f, _P(SphSurface)]),
+    "sph_extract_surface_volume": (_int, [_vp, _vp, _pf, _pf, _pi, _f, _P(SphSurface)]),
+    "sph_surface_download": (_int, [_vp, _vp, _sz, _vp, _sz]),
+    # statistics
+    "sph_statistics": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "sph_statistics_device": (_int, [_vp, _vp, _vp, _int, _vp]),
+    # passive tracers
+    "sph_tracers_set": (_int, [_vp, _vp, _sz, _int, _u32, _u32]),
+    "sph_tracers_set_device": (_int, [_vp, _vp, _sz, _int, _u32, _u32]),
+    "sph_tracers_count": (_sz, [_vp]),
+    "sph_tracers_info": (_int, [_vp, _P(_u64), _P(_u32), _P(_u64)]),
+    "sph_tracers_download": (_int, [_vp, _vp, _sz]),
+    "sph_tracers_device": (_int, [_vp, _P(_vp)]),
+    "sph_tracers_history": (_int, [_vp, _vp, _sz, _P(_u32), _P(_u64)]),
+    # kinematic solid obstacles
+    "sph_obstacle_default": (None, [_vp]),
+    "sph_obstacles_set": (_int, [_vp, _vp, _int]),
+    "sph_obstacles_set_motion": (_int, [_vp, _int, _pf, _pf]),
+    "sph_obstacles_get": (_int, [_vp, _vp, _int, _pi]),
+    "sph_obstacles_impulses": (_int, [_vp, _vp, _int, _P(_d), _P(_u64), _int]),
+    "sph_obstacles_apply_host": (_int, [_vp, _int, _f, _vp, _sz, _vp]),
+    "sph_obstacles_advance_host": (_int, [_vp, _int, _f]),
+    # triangle-mesh obstacles through signed distance lattices
+    "sph_volume_create": (_int, [_vp, _vp, _pi, _pf, _int, _pi]),
+    "sph_volume_destroy": (_int, [_vp, _int]),
+    "sph_volume_info": (_int, [_vp, _int, _pi, _pf, _pf]),
+    "sph_obstacles_bind_volume": (_int, [_vp, _int, _int]),
+    "sph_obstacles_volume": (_int, [_vp, _int, _pi]),
+    "sph_volume_sample_host": (_int, [_vp, _pi, _pf, _pf, _pf, _pf, _pi]),
+    "sph_obstacles_apply_host_volumes": (_int, [_vp, _int, _vp, _int, _vp, _f, _vp, _sz, _vp]),
+    "sph_mesh_distance": (_int, [_vp, _vp, _sz, _vp, _sz, _pf, _pf, _pi, _vp]),
+    "sph_volume_from_mesh": (_int, [_vp, _vp, _sz, _vp, _sz, _pf, _pf, _pi, _pi]),
+    "sph_mesh_distance_host": (_int, [_vp, _sz, _vp, _sz, _pf, _pf, _pi, _vp]),
+    # dynamic rigid bodies
+    "sph_obstacle_dynamics_default": (None, [_vp]),
+    "sph_obstacles_set_dynamics": (_int, [_vp, _int, _vp]),
+    "sph_obstacles_get_dynamics": (_int, [_vp, _int, _vp, _pi]),
+    "sph_obstacles_step_host": (_int, [_vp, _vp, _int, _vp, _pp, _f]),
+    "sph_volume_moments": (_int, [_vp, _int, _vp]),
+    "sph_volume_moments_host": (_int, [_vp, _pi, _pf, _vp]),
+    # multi-GPU: z-slab decomposition
+    "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
+    "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
+    "sph_slab_unpack": (_int, [_vp, _vp, _u32, _vp, _u32]),
+    "sph_slab_download": (_int, [_vp, _vp, _sz, _P(_sz)]),
+    # the same exchange without host round trips, and its RCCL transport
+    "sph_slab_alloc_faces": (_int, [_vp, _u32]),
+    "sph_slab_face_buffer": (_int, [_vp, _int, _P(_vp)]),
+    "sph_slab_face_bytes": (_int, [_vp, _P(_u64)]),
+    "sph_slab_pack_async": (_int, [_vp]),
+    "sph_slab_unpack_async": (_int, [_vp, _vp, _vp, _u32]),
+    "sph_slab_status": (_int, [_vp, _P(_u32)]),
+    "sph_slab_clear_flags": (_int, [_vp, _u32]),
+    "sph_slab_message_bytes": (_int, [_vp, _P(_u64)]),
+    "sph_slab_message_records": (_int, [_u32, _u32, _u32]),
+    "sph_comm_unique_id": (_int, [_vp]),
+    "sph_comm_create": (_int, [_P(_vp), _vp, _int, _int]),
+    "sph_comm_destroy": (_int, [_vp]),
+    "sph_comm_selftest": (_int, [_vp, _u64]),
+    "sph_comm_selftest_timed": (_int, [_vp, _u64, _pf]),
+    "sph_slab_exchange": (_int, [_vp, _vp]),
+    # agreement of the two ends of a link
+    "sph_slab_set_verify": (_int, [_vp, _int]),
+    "sph_slab_set_deadline": (_int, [_vp, _d]),
+    "sph_slab_plan": (_int, [_vp, _P(SphSlabIntent), _pf]),
+    "sph_slab_plans_agree": (_int, [_P(SphSlabIntent), _P(SphSlabIntent), _int, C.c_char_p, _sz]),
+    "sph_sync_deadline": (_int, [_vp, _d]),
+    "sph_slab_debug_tight_messages": (_int, [_vp, _int]),
+    "sph_comm_selftest_faces": (_int, [_vp, _u32, _P(_u32), _pf]),
+    # boundary-first substep
+    "sph_slab_step_begin": (_int, [_vp, _f]),
+    "sph_slab_step_finish": (_int, [_vp, _vp]),
+    "sph_slab_step_finish_local": (_int, [_vp, _vp, _vp]),
+    "sph_slab_step_times": (_int, [_vp, _pf]),
+    # measurement
+    "sph_kernel_times": (_int, [_vp, _P(_d), _P(C.c_int64), _int]),
+}
+ABI_SYMBOLS = tuple(_ABI)
+
+
+# ---- the loader -----------------------------------------------------------------------------------------------------------
+class SphError(RuntimeError):
+    pass
+
+
+_lib = None
+
+
+def lib_path() -> str:
+    return _build.LIB_PATH
+
+
+def load_library(build_if_missing: bool = True) -> C.CDLL:
+    """Load libsph_hip.so (building it in-tree first if asked and needed)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if build_if_missing:
+        _build.build()
+    if not os.path.exists(_build.LIB_PATH):
+        raise SphError(f"{_build.LIB_PATH} is missing: run __graft_entry__.build(); there is no CPU fallback")
+    # One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64 (same soname as the
+    # system one).  Whichever loads first wins, and torch cannot see the GPU behind the system
+    # runtime, so let torch load first when it is installed (it is only plumbing here: halo
+    # buffers, streams, torch.distributed).
+    if os.environ.get("SPH_NO_TORCH_PRELOAD", "0") != "1":
+        try:
+            import torch  # noqa: F401
+        except Exception:
+            pass
+    # developer A/B of kernel variants: SPH_HIP_LIB names another build of the same sources
+    L = C.CDLL(os.environ.get("SPH_HIP_LIB") or _build.LIB_PATH)
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib = L
+    return L
+
+
+# ---- free helpers: errors and marshalling ---------------------------------------------------------------------------------
+def _check(rc: int):
+    if rc != 0:
+        msg = load_library().sph_last_error()
+        raise SphError(f"sph C-ABI error {rc}: {msg.decode() if msg else '?'}")
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _ptr(arr):
+    """The data pointer of a numpy array (the caller keeps the array alive across the call)."""
+    return arr.ctypes.data_as(C.c_void_p)
+
+
+def _ptr_or_none(arr):
+    return _ptr(arr) if len(arr) else None
+
+
+def _dims3(dims, who=None):
+    """(nx, ny, nz) as int[3]; with `who`, every dimension >= 1 and at most 2^31 - 1 points, or SphError in who's name."""
+    d = (C.c_int * 3)(*[int(x) for x in dims])
+    if who and (min(d) < 1 or int(d[0]) * int(d[1]) * int(d[2]) > 2 ** 31 - 1):
+        raise SphError(f"{who}: bad dims {tuple(d)}")
+    return d
+
+
+def _spacing3(spacing):
+    """A scalar or (sx, sy, sz) as 3 float32."""
+    return np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
+
+
+def _points4(points, who, keep_w):
+    """(m, 3) or (m, 4) points as a fresh (m, 4) float32 array; the fourth column is the caller's (keep_w) or 0."""
+    pts = np.asarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+        raise SphError(f"{who}: points must have shape (m, 3) or (m, 4), not {pts.shape}")
+    p4 = np.zeros((len(pts), 4), np.float32)
+    k = pts.shape[1] if keep_w else 3
+    p4[:, :k] = pts[:, :k]
+    return p4
+
+
+def _is_cuda_f32(t) -> bool:
+    """A contiguous float32 torch CUDA tensor?"""
+    return t.is_cuda and t.dtype == __import__("torch").float32 and t.is_contiguous()
+
+
+def _assign(struct, name, value):
+    """struct.name = value, element by element where the field is an array."""
+    cur = getattr(struct, name)
+    if hasattr(cur, "__len__"):
+        for i, x in enumerate(value):
+            cur[i] = x
+    else:
+        setattr(struct, name, value)
+
+
+def _volume_lattice(values, spacing):
+    """A (nz, ny, nx) array of signed distances and its spacing -> (contiguous fp32 array, dims (nx, ny, nz), spacing[3])."""
+    v = np.ascontiguousarray(values, np.float32)
+    if v.ndim != 3:
+        raise SphError(f"a volume needs an array of shape (nz, ny, nx), not {v.shape}")
+    return v, _dims3(v.shape[::-1]), _spacing3(spacing)
+
+
+def _mesh_arrays(vertices, triangles):
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    return v, t
+
+
+def _histogram_specs(histograms):
+    """[(field, bins, lo, hi) | SphHistogramSpec, ...] -> (ctypes array or None, count, total uint64 slots).  Checked by the library."""
+    hs = list(histograms or ())
+    if not hs:
+        return None, 0, 0
+    arr = (SphHistogramSpec * len(hs))()
+    for i, h in enumerate(hs):
+        arr[i] = h if isinstance(h, SphHistogramSpec) else SphHistogramSpec(int(h[0]), int(h[1]), float(h[2]), float(h[3]))
+    return arr, len(hs), sum(int(a.bins) + 2 for a in arr)
+
+
+# ---- free helpers: records and results ------------------------------------------------------------------------------------
+class Statistics:
+    """Result of SPHFluidGPU.statistics(): `s` is the SphStatistics struct (its members are also attributes of this object),
+    `histograms` a list of uint64 arrays of bins + 2 slots (below lo, the bins, at or above hi) in spec order.  The derived numbers
+    are computed here, on the host, from the struct and the members at the time of the call (DESIGN.md section 3c)."""
+
+    def __init__(self, s: SphStatistics, histograms, params: SphParams):
+        self.s = s
+        self.histograms = histograms
+        self.mass, self.h, self.dt, self.rho0 = float(params.param_mass), float(params.param_h), float(params.param_timeStep), float(params.param_restDensity)
+        self.gravity = (float(params.param_gravityX), float(params.param_gravityY), float(params.param_gravityZ))
+
+    def __getattr__(self, name):
+        return getattr(object.__getattribute__(self, "s"), name)
+
+    def tobytes(self) -> bytes:
+        return bytes(self.s) + b"".join(h.tobytes() for h in self.histograms)
+
+    @property
+    def ok(self) -> bool:
+        """No non-finite and no escaped fluid record."""
+        return self.s.numNonFinite == 0 and self.s.numEscaped == 0
+
+    @property
+    def kinetic_energy(self) -> float:
+        return 0.5 * self.mass * self.s.sumSpeed2
+
+    @property
+    def potential_energy(self) -> float:
+        return -self.mass * sum(g * p for g, p in zip(self.gravity, self.s.sumPos))
+
+    @property
+    def momentum(self):
+        return tuple(self.mass * v for v in self.s.sumVel)
+
+    @property
+    def angular_momentum(self):
+        """About param_boxCenter."""
+        return tuple(self.mass * v for v in self.s.sumAngular)
+
+    @property
+    def center_of_mass(self):
+        n = self.s.numCounted
+        return tuple(p / n for p in self.s.sumPos) if n else (0.0, 0.0, 0.0)
+
+    @property
+    def bounding_box(self):
+        return tuple(e.value for e in self.s.minPos), tuple(e.value for e in self.s.maxPos)
+
+    @property
+    def mean_density(self) -> float:
+        n = self.s.numCounted
+        return self.s.sumDensity / n if n else 0.0
+
+    @property
+    def std_density(self) -> float:
+        n = self.s.numCounted
+        if not n:
+            return 0.0
+        m = self.s.sumDensity / n
+        return max(self.s.sumDensity2 / n - m * m, 0.0) ** 0.5
+
+    @property
+    def cfl(self) -> float:
+        return self.s.maxSpeed * self.dt / self.h
+
+    @property
+    def volume(self) -> float:
+        """SPH volume sum(mass / rho_j)."""
+        return self.mass * self.s.sumInvDensity
 
 
 def obstacle(shape, center, size, rotation=(1.0, 0.0, 0.0, 0.0), vel=(0.0, 0.0, 0.0), omega=(0.0, 0.0, 0.0),
@@ -197,21 +563,6 @@ def obstacle_array(obstacles) -> np.ndarray:
     if not obstacles:
         return np.zeros(0, OBSTACLE_DTYPE)
     return np.frombuffer(b"".join(bytes(o) for o in obstacles), OBSTACLE_DTYPE).copy()
-
-
-class SphObstacleDynamics(C.Structure):
-    """struct SphObstacleDynamics of include/sph_abi.h: what makes a body of the obstacle set dynamic (see dynamics() and
-    SPHFluidGPU.set_obstacle_dynamics)."""
-    _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 6), ("com", C.c_float * 3), ("gravityScale", C.c_float),
-                ("force", C.c_float * 3), ("torque", C.c_float * 3), ("linearDamping", C.c_float), ("angularDamping", C.c_float),
-                ("flags", C.c_uint32)]
-
-
-assert C.sizeof(SphObstacleDynamics) == 80
-DYNAMICS_DTYPE = np.dtype([("mass", "<f4"), ("inertia", "<f4", (6,)), ("com", "<f4", (3,)), ("gravityScale", "<f4"), ("force", "<f4", (3,)),
-                           ("torque", "<f4", (3,)), ("linearDamping", "<f4"), ("angularDamping", "<f4"), ("flags", "<u4")])
-assert DYNAMICS_DTYPE.itemsize == 80
-SPH_DYNAMICS_CONFINED = 1
 
 
 def dynamics(mass, inertia, com=(0.0, 0.0, 0.0), gravity_scale: float = 1.0, force=(0.0, 0.0, 0.0), torque=(0.0, 0.0, 0.0),
@@ -289,328 +640,520 @@ def mass_properties(moments, density: float):
     return float(density * vol), c, inertia
 
 
-class SphVolumeHost(C.Structure):
-    """struct SphVolumeHost of include/sph_abi.h: one lattice of signed distances in host memory (see obstacles_apply_host_volumes)."""
-    _fields_ = [("values", C.c_void_p), ("dims", C.c_int * 3), ("spacing", C.c_float * 3)]
+_PARAM_NAMES = {f[0] for f in SphParams._fields_}
+_RIVER_NAMES = {f[0] for f in SphRiver._fields_}
+_FOUNTAIN_NAMES = {f[0] for f in SphFountain._fields_}
 
 
-def _volume_lattice(values, spacing):
-    """A (nz, ny, nx) array of signed distances and its spacing -> (contiguous fp32 array, dims (nx, ny, nz), spacing[3])."""
-    v = np.ascontiguousarray(values, np.float32)
-    if v.ndim != 3:
-        raise SphError(f"a volume needs an array of shape (nz, ny, nx), not {v.shape}")
-    sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
-    return v, (C.c_int * 3)(v.shape[2], v.shape[1], v.shape[0]), sp
+class SPHFluidGPU:
+    """Drop-in for the reference class of the same name (SPHFluid3D.h:26).
 
+    SPHFluidGPU(numParticles)                    -> spawn as InitializeParticles does (seeded)
+    SPHFluidGPU.from_particles(records, params)  -> caller-provided 80-byte records
+    """
 
-def _mesh_arrays(vertices, triangles):
-    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
-    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
-    return v, t
+    def __init__(self, numParticles_: int = 50000, params: SphParams | None = None, seed: int = 1, stream: int | None = None,
+                 _particles: np.ndarray | None = None):
+        L = load_library()
+        self._L = L
+        self._p = params if params is not None else default_params()
+        self._h = C.c_void_p()
+        self._f = SphFountain()
+        L.sph_fountain_default(C.byref(self._f))
+        self._r = SphRiver()
+        L.sph_river_default(C.byref(self._r))
+        self.terrainHeights = np.zeros(0, np.float32)   # SPHFluid3D.h:175
+        self._terrain_sent = None
+        self.numParticles = int(numParticles_)
+        self.seed = int(seed)
+        if _particles is not None:
+            arr = np.ascontiguousarray(_particles, dtype=PARTICLE_DTYPE)
+            _check(L.sph_create_from_particles(C.byref(self._h), _ptr(arr), len(arr), C.byref(self._p), stream))
+        else:
+            _check(L.sph_create(C.byref(self._h), self.numParticles, C.byref(self._p), self.seed, stream))
+        _check(L.sph_get_params(self._h, C.byref(self._p)))   # spawn overwrote param_mass (SPHFluid3D.cpp:92)
 
+    @classmethod
+    def from_particles(cls, particles: np.ndarray, params: SphParams, stream: int | None = None) -> "SPHFluidGPU":
+        return cls(len(particles), params=params, stream=stream, _particles=particles)
 
-class SphSurface(C.Structure):
-    """struct SphSurface of include/sph_abi.h: counts and borrowed device arrays of the last extracted surface."""
-    _fields_ = [("numVertices", C.c_uint32), ("numTriangles", C.c_uint32), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
-
-
-SURFACE_VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,))])     # struct SphSurfaceVertex
-assert SURFACE_VERTEX_DTYPE.itemsize == 24
-
-
-class SphStatExtremum(C.Structure):
-    """struct SphStatExtremum of include/sph_abi.h: an extreme value and the particle id that attains it."""
-    _fields_ = [("value", C.c_float), ("id", C.c_uint32)]
-
-
-class SphStatistics(C.Structure):
-    """struct SphStatistics of include/sph_abi.h (DESIGN.md section 3c): 832 bytes."""
-    _fields_ = [
-        ("numRecords", C.c_uint64), ("numFluid", C.c_uint64), ("numActiveGhosts", C.c_uint64), ("numInactiveGhosts", C.c_uint64),
-        ("numOther", C.c_uint64), ("numNonFinite", C.c_uint64), ("numCounted", C.c_uint64), ("numEscaped", C.c_uint64),
-        ("firstNonFiniteId", C.c_uint32), ("firstEscapedId", C.c_uint32),
-        ("minPos", SphStatExtremum * 3), ("maxPos", SphStatExtremum * 3), ("minDensity", SphStatExtremum), ("maxDensity", SphStatExtremum),
-        ("minPressure", SphStatExtremum), ("maxPressure", SphStatExtremum), ("maxFoam", SphStatExtremum), ("maxSpeed2", SphStatExtremum),
-        ("maxSpeed", C.c_float), ("reserved0", C.c_uint32),
-        ("sumPos", C.c_double * 3), ("sumVel", C.c_double * 3), ("sumSpeed2", C.c_double), ("sumDensity", C.c_double),
-        ("sumDensity2", C.c_double), ("sumPressure", C.c_double), ("sumFoam", C.c_double), ("sumInvDensity", C.c_double),
-        ("sumAngular", C.c_double * 3),
-        ("occupiedCells", C.c_uint64), ("maxCellCount", C.c_uint32), ("maxCellIndex", C.c_uint32),
-        ("occupancy", C.c_uint64 * 65),
-    ]
-
-
-assert C.sizeof(SphStatistics) == 832
-
-
-class SphHistogramSpec(C.Structure):
-    """struct SphHistogramSpec of include/sph_abi.h: field (SPH_STAT_*), bins (1 .. 1024), lo < hi."""
-    _fields_ = [("field", C.c_int32), ("bins", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
-
-
-SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y, SPH_STAT_POS_Z, SPH_STAT_FOAM = range(7)
-SPH_STAT_MAX_SPECS, SPH_STAT_MAX_BINS = 4, 1024
-
-
-def _histogram_specs(histograms):
-    """[(field, bins, lo, hi) | SphHistogramSpec, ...] -> (ctypes array or None, count, total uint64 slots).  Checked by the library."""
-    hs = list(histograms or ())
-    if not hs:
-        return None, 0, 0
-    arr = (SphHistogramSpec * len(hs))()
-    for i, h in enumerate(hs):
-        arr[i] = h if isinstance(h, SphHistogramSpec) else SphHistogramSpec(int(h[0]), int(h[1]), float(h[2]), float(h[3]))
-    return arr, len(hs), sum(int(a.bins) + 2 for a in arr)
-
-
-class Statistics:
-    """Result of SPHFluidGPU.statistics(): `s` is the SphStatistics struct (its members are also attributes of this object),
-    `histograms` a list of uint64 arrays of bins + 2 slots (below lo, the bins, at or above hi) in spec order.  The derived numbers
-    are computed here, on the host, from the struct and the members at the time of the call (DESIGN.md section 3c)."""
-
-    def __init__(self, s: SphStatistics, histograms, params: SphParams):
-        self.s = s
-        self.histograms = histograms
-        self.mass, self.h, self.dt, self.rho0 = float(params.param_mass), float(params.param_h), float(params.param_timeStep), float(params.param_restDensity)
-        self.gravity = (float(params.param_gravityX), float(params.param_gravityY), float(params.param_gravityZ))
-
+    # -- public param_* members ----------------------------------------------------------
     def __getattr__(self, name):
-        return getattr(object.__getattribute__(self, "s"), name)
+        if name in _PARAM_NAMES or name in _FOUNTAIN_NAMES or name in _RIVER_NAMES:
+            v = getattr(object.__getattribute__(self, "_p" if name in _PARAM_NAMES else ("_f" if name in _FOUNTAIN_NAMES else "_r")), name)
+            return list(v) if hasattr(v, "__len__") else v
+        raise AttributeError(name)
 
-    def tobytes(self) -> bytes:
-        return bytes(self.s) + b"".join(h.tobytes() for h in self.histograms)
-
-    @property
-    def ok(self) -> bool:
-        """No non-finite and no escaped fluid record."""
-        return self.s.numNonFinite == 0 and self.s.numEscaped == 0
-
-    @property
-    def kinetic_energy(self) -> float:
-        return 0.5 * self.mass * self.s.sumSpeed2
+    def __setattr__(self, name, value):
+        if name in _PARAM_NAMES or name in _FOUNTAIN_NAMES or name in _RIVER_NAMES:
+            st = self._p if name in _PARAM_NAMES else (self._f if name in _FOUNTAIN_NAMES else self._r)
+            _assign(st, name, value)
+        else:
+            object.__setattr__(self, name, value)
 
     @property
-    def potential_energy(self) -> float:
-        return -self.mass * sum(g * p for g, p in zip(self.gravity, self.s.sumPos))
+    def params(self) -> SphParams:
+        return self._p
 
+    # -- reference methods ---------------------------------------------------------------
+    def _push_params(self):
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
+
+    def _push_members(self):
+        _check(self._L.sph_set_params(self._h, C.byref(self._p)))  # members are re-read every dispatch (:458-506); spelled out: no extra frame in the timed loop
+        _check(self._L.sph_set_fountain(self._h, C.byref(self._f)))  # fountain* members (:519-541)
+        self._push_river()
+
+    def _push_river(self):                                           # river members (:511-516); the heightfield only when it changed
+        th = self.terrainHeights
+        fresh = th is not self._terrain_sent and len(th) > 0
+        ptr = None
+        if fresh:
+            th = np.ascontiguousarray(th, np.float32)
+            if len(th) != self._r.terrainW * self._r.terrainH:
+                raise SphError(f"terrainHeights has {len(th)} samples, terrainW x terrainH = {self._r.terrainW * self._r.terrainH}")
+            ptr = _ptr(th)
+        _check(self._L.sph_set_river(self._h, C.byref(self._r), ptr))
+        if fresh:
+            self._terrain_sent = self.terrainHeights
+
+    def set_river(self, river: SphRiver, heights):                   # all river members + terrainHeights in one go
+        C.memmove(C.byref(self._r), C.byref(river), C.sizeof(SphRiver))
+        self.terrainHeights = np.ascontiguousarray(heights, np.float32).copy()
+        self._push_river()
+
+    def GenerateRiverTerrain(self, seed: int):                       # SPHFluid3D.cpp:772-878
+        heights = np.zeros(self._r.terrainW * self._r.terrainH, np.float32)
+        _check(self._L.sph_generate_river_terrain(C.byref(self._p), int(seed), C.byref(self._r), _ptr(heights)))
+        self.terrainHeights = heights
+        self._push_river()
+
+    def DispatchCompute(self, overrideDt: float = -1.0):            # SPHFluid3D.cpp:431
+        self._push_members()
+        _check(self._L.sph_dispatch(self._h, overrideDt))
+        _check(self._L.sph_get_fountain(self._h, C.byref(self._f)))  # fountainSeed++ (:541)
+
+    SimulateSubstep = DispatchCompute   # BASELINE.json's name for the same entry point
+
+    def DispatchN(self, n: int, overrideDt: float = -1.0):           # Scene0p.cpp:3720-3739 loop
+        self._push_members()
+        _check(self._L.sph_dispatch_n(self._h, overrideDt, int(n)))
+        _check(self._L.sph_get_fountain(self._h, C.byref(self._f)))
+
+    def ResetSimulation(self, seed: int | None = None):             # SPHFluid3D.cpp:713
+        if seed is not None:
+            self.seed = int(seed)
+        self._push_params()
+        self._push_river()                                           # riverMode && !terrainHeights.empty() picks the spawn branch (:104)
+        _check(self._L.sph_reset(self._h, self.numParticles, self.seed))
+        _check(self._L.sph_get_params(self._h, C.byref(self._p)))
+
+    def ApplyWaveImpulse(self, amplitude, wavelength, phase, dir, yMin=-FLT_MAX, yMax=FLT_MAX):   # SPHFluid3D.cpp:604
+        _check(self._L.sph_apply_wave_impulse(self._h, amplitude, wavelength, phase, _f3(dir), yMin, yMax))
+
+    def ApplyVortexImpulse(self, tangentKick, inwardKick):          # SPHFluid3D.cpp:627
+        self._push_params()   # reads param_boxCenter / EulerDeg / half
+        _check(self._L.sph_apply_vortex_impulse(self._h, tangentKick, inwardKick))
+
+    def ApplyAttractorImpulse(self, point, pullKick, radius):        # SPHFluid3D.cpp:650
+        _check(self._L.sph_apply_attractor_impulse(self._h, _f3(point), pullKick, radius))
+
+    def SetStencilTargets(self, points):                             # SPHFluid3D.cpp:684
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        _check(self._L.sph_set_stencil_targets(self._h, _ptr(pts), len(pts)))
+        self.stencilCount = len(pts)
+
+    def ApplyStencilAttract(self, pullKick, dampKick):               # SPHFluid3D.cpp:695
+        _check(self._L.sph_apply_stencil_attract(self._h, pullKick, dampKick))
+
+    def ApplyCurlFlow(self, kick, scale, time):                      # SPHFluid3D.cpp:668
+        _check(self._L.sph_apply_curl_flow(self._h, kick, scale, time))
+
+    def EffectiveHalf(self):                                         # SPHFluid3D.h:127
+        return effective_half(self._p)
+
+    def ComputeGridExtents(self):                                    # SPHFluid3D.cpp:354
+        return compute_grid_extents(self._p)
+
+    def GetNumFluids(self) -> int:                                   # SPHFluid3D.cpp:601
+        return int(self._L.sph_num_particles(self._h))
+
+    # -- reference data members ----------------------------------------------------------
     @property
-    def momentum(self):
-        return tuple(self.mass * v for v in self.s.sumVel)
+    def particles(self) -> np.ndarray:
+        """Host copy of the INITIAL records (never refreshed, as in the reference)."""
+        n = self.GetNumFluids()
+        out = np.zeros(n, PARTICLE_DTYPE)
+        _check(self._L.sph_initial_particles(self._h, _ptr(out), n))
+        return out
 
-    @property
-    def angular_momentum(self):
-        """About param_boxCenter."""
-        return tuple(self.mass * v for v in self.s.sumAngular)
+    def _grid(self) -> SphGridInfo:
+        g = SphGridInfo()
+        _check(self._L.sph_grid_info(self._h, C.byref(g)))
+        return g
 
-    @property
-    def center_of_mass(self):
-        n = self.s.numCounted
-        return tuple(p / n for p in self.s.sumPos) if n else (0.0, 0.0, 0.0)
+    gridSizeX = property(lambda self: self._grid().dims[0])
+    gridSizeY = property(lambda self: self._grid().dims[1])
+    gridSizeZ = property(lambda self: self._grid().dims[2])
+    numCells = property(lambda self: self._grid().numCells)
+    gridMinV = property(lambda self: list(self._grid().gridMin))
+    cellSize = property(lambda self: self._grid().cellSize)
 
-    @property
-    def bounding_box(self):
-        return tuple(e.value for e in self.s.minPos), tuple(e.value for e in self.s.maxPos)
+    # -- engine extras -------------------------------------------------------------------
+    def set_option(self, option: int, value: int):
+        _check(self._L.sph_set_option(self._h, option, value))
 
-    @property
-    def mean_density(self) -> float:
-        n = self.s.numCounted
-        return self.s.sumDensity / n if n else 0.0
+    def get_option(self, option: int) -> int:
+        v = C.c_int(0)
+        _check(self._L.sph_get_option(self._h, option, C.byref(v)))
+        return v.value
 
-    @property
-    def std_density(self) -> float:
-        n = self.s.numCounted
-        if not n:
-            return 0.0
-        m = self.s.sumDensity / n
-        return max(self.s.sumDensity2 / n - m * m, 0.0) ** 0.5
+    def upload(self, particles: np.ndarray):
+        arr = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+        _check(self._L.sph_upload_particles(self._h, _ptr(arr), len(arr)))
 
-    @property
-    def cfl(self) -> float:
-        return self.s.maxSpeed * self.dt / self.h
+    def download(self) -> np.ndarray:
+        n = self.GetNumFluids()
+        out = np.zeros(n, PARTICLE_DTYPE)
+        _check(self._L.sph_download_particles(self._h, _ptr(out), n))
+        return out
 
-    @property
-    def volume(self) -> float:
-        """SPH volume sum(mass / rho_j)."""
-        return self.mass * self.s.sumInvDensity
+    def device_particles(self) -> int:
+        """Device address of the 80-byte AoS (the `ssbo` renderers bind, Scene0p.cpp:1625)."""
+        p = C.c_void_p()
+        _check(self._L.sph_device_particles(self._h, C.byref(p)))
+        return int(p.value)
 
+    def pack_render_buffer(self, dev_ptr: int, w_mode: int = 0):
+        """(x, y, z, w) per particle in original order into a caller-owned device buffer (a mapped vertex
+        buffer in a renderer; a torch tensor's data_ptr() in the tests)."""
+        _check(self._L.sph_pack_render_buffer(self._h, C.c_void_p(dev_ptr), self.GetNumFluids(), int(w_mode)))
 
-class SphError(RuntimeError):
-    pass
+    def download_grid(self):
+        g = compute_grid_extents(self._p)
+        n = self.GetNumFluids()
+        cnt = np.zeros(g.numCells, np.int32)
+        pc = np.zeros(max(n, 1), np.int32)
+        self._push_params()
+        _check(self._L.sph_download_grid(self._h, _ptr(cnt), g.numCells, _ptr(pc), n))
+        return cnt, pc[:n]
 
+    def sync(self):
+        _check(self._L.sph_sync(self._h))
 
-_lib = None
+    def debug_counters(self, reset: bool = False) -> dict:
+        buf = (C.c_uint64 * len(STAMP_NAMES))()
+        _check(self._L.sph_debug_counters(self._h, buf, len(STAMP_NAMES), 1 if reset else 0))
+        return {k: int(buf[i]) for i, k in enumerate(STAMP_NAMES)}
 
+    # -- field sampling (include/sph_abi.h "field sampling") ----------------------------------
+    def sample(self, points) -> np.ndarray:
+        """Fields of the current state at (m, 3) or (m, 4) probe points: a structured array of SAMPLE_DTYPE (density, fraction,
+        pressure, count, vel).  Synchronises."""
+        p4 = _points4(points, "sample", keep_w=False)
+        out = np.zeros(len(p4), SAMPLE_DTYPE)
+        self._push_params()
+        _check(self._L.sph_sample_points(self._h, _ptr(p4), len(p4), _ptr(out)))
+        return out
 
-def lib_path() -> str:
-    return _build.LIB_PATH
+    def sample_device(self, dev_points: int, m: int, dev_out: int):
+        """m probes of 4 floats at device address dev_points -> m 32-byte SphSample records at dev_out (a torch tensor's
+        data_ptr(), say).  Asynchronous on the engine's stream."""
+        self._push_params()
+        _check(self._L.sph_sample_points_device(self._h, C.c_void_p(dev_points), int(m), C.c_void_p(dev_out)))
 
+    def sample_lattice_device(self, origin, spacing, dims, dev_out: int, field: int = SPH_FIELD_DENSITY):
+        """Lattice origin + i * spacing (dims = (nx, ny, nz), x fastest) into a caller's device buffer: one float per point, or one
+        SphSample per point for SPH_FIELD_ALL.  Asynchronous on the engine's stream."""
+        self._push_params()
+        _check(self._L.sph_sample_lattice(self._h, _f3(origin), _f3(spacing), _dims3(dims), int(field), C.c_void_p(dev_out)))
 
-def load_library(build_if_missing: bool = True) -> C.CDLL:
-    """Load libsph_hip.so (building it in-tree first if asked and needed)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if build_if_missing:
-        _build.build()
-    if not os.path.exists(_build.LIB_PATH):
-        raise SphError(f"{_build.LIB_PATH} is missing: run __graft_entry__.build(); there is no CPU fallback")
-    # One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64 (same soname as the
-    # system one).  Whichever loads first wins, and torch cannot see the GPU behind the system
-    # runtime, so let torch load first when it is installed (it is only plumbing here: halo
-    # buffers, streams, torch.distributed).
-    if os.environ.get("SPH_NO_TORCH_PRELOAD", "0") != "1":
+    def sample_lattice(self, origin, spacing, dims, field: int = SPH_FIELD_DENSITY) -> np.ndarray:
+        """Host copy of sample_lattice_device: shape (nz, ny, nx), float32 or SAMPLE_DTYPE (SPH_FIELD_ALL)."""
+        import torch
+        nx, ny, nz = (int(x) for x in dims)
+        if min(nx, ny, nz) < 1:
+            raise SphError(f"sample_lattice: dims must be >= 1, not {tuple(dims)}")
+        words = 8 if field == SPH_FIELD_ALL else 1
+        buf = torch.empty(nx * ny * nz * words, dtype=torch.float32, device="cuda")
+        self.sample_lattice_device(origin, spacing, (nx, ny, nz), buf.data_ptr(), field)
+        self.sync()
+        host = buf.cpu().numpy()
+        if field == SPH_FIELD_ALL:
+            return host.view(SAMPLE_DTYPE).reshape(nz, ny, nx)
+        return host.reshape(nz, ny, nx)
+
+    def water_level(self, xz, y_lo: float, y_hi: float, dy: float, threshold: float = 0.5) -> np.ndarray:
+        """Wave gauge: per (x, z) column, the first y from the top where `fraction` >= threshold, sampled at y_hi, y_hi - dy, ...
+        down to y_lo and linearly interpolated against the sample above it; NaN where no sample reaches the threshold."""
+        cols = np.asarray(xz, dtype=np.float32).reshape(-1, 2)
+        ys = np.float32(y_hi) - np.arange(int(np.floor((y_hi - y_lo) / dy + 1e-6)) + 1, dtype=np.float32) * np.float32(dy)
+        pts = np.zeros((len(cols), len(ys), 4), np.float32)
+        pts[:, :, 0] = cols[:, None, 0]
+        pts[:, :, 1] = ys[None, :]
+        pts[:, :, 2] = cols[:, None, 1]
+        frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
+        return gauge_levels(frac, ys, threshold)
+
+    # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
+    def default_surface_lattice(self):
+        """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
+        g = self.ComputeGridExtents()
+        h = np.float32(self._p.param_h)
+        s = np.float32(h / np.float32(2))
+        lo = np.array(g.gridMin, np.float32) - np.float32(2) * h
+        ext = np.float32(g.cellSize) * np.array(g.dims, np.float32) + np.float32(4) * h
+        dims = tuple(int(np.ceil(ext[a] / s)) + 1 for a in range(3))
+        return tuple(float(x) for x in lo), (float(s),) * 3, dims
+
+    def _download_surface(self, surf: SphSurface):
+        v = np.zeros(surf.numVertices, SURFACE_VERTEX_DTYPE)
+        t = np.zeros((surf.numTriangles, 3), np.uint32)
+        _check(self._L.sph_surface_download(self._h, _ptr(v), len(v), _ptr(t), len(t)))
+        return v, t
+
+    def extract_surface(self, origin, spacing, dims, iso: float = 0.5, field: int = SPH_FIELD_FRACTION) -> SphSurface:
+        """sph_extract_surface: counts and borrowed device arrays (valid until the next extract call, ResetSimulation or close)."""
+        surf = SphSurface()
+        self._push_params()
+        _check(self._L.sph_extract_surface(self._h, _f3(origin), _f3(spacing), _dims3(dims), int(field), float(iso), C.byref(surf)))
+        return surf
+
+    def surface(self, origin=None, spacing=None, dims=None, iso: float = 0.5, field: int = SPH_FIELD_FRACTION):
+        """Iso-surface {field >= iso} of the current state as a closed triangle mesh (DESIGN.md section 3b): (vertices of
+        SURFACE_VERTEX_DTYPE, triangles (T, 3) uint32).  Lattice members left None come from default_surface_lattice()."""
+        do, ds, dd = self.default_surface_lattice() if origin is None or spacing is None or dims is None else (None, None, None)
+        surf = self.extract_surface(do if origin is None else origin, ds if spacing is None else spacing, dd if dims is None else dims, iso, field)
+        return self._download_surface(surf)
+
+    def extract_surface_volume(self, dev_values: int, origin, spacing, dims, iso: float = 0.5) -> SphSurface:
+        """sph_extract_surface_volume on a device address: counts and borrowed device arrays."""
+        surf = SphSurface()
+        _check(self._L.sph_extract_surface_volume(self._h, C.c_void_p(dev_values), _f3(origin), _f3(spacing), _dims3(dims), float(iso), C.byref(surf)))
+        return surf
+
+    def surface_from_volume(self, values, origin, spacing, dims=None, iso: float = 0.5):
+        """Iso-surface {values >= iso} of a caller's lattice of floats (x fastest): a torch CUDA float32 tensor of shape (nz, ny, nx)
+        (dims may then be omitted) or a device address with dims = (nx, ny, nz).  Returns (vertices, triangles) like surface()."""
+        if hasattr(values, "data_ptr"):
+            if not _is_cuda_f32(values):
+                raise SphError("surface_from_volume: values must be a contiguous float32 CUDA tensor")
+            if dims is None:
+                if values.dim() != 3:
+                    raise SphError(f"surface_from_volume: a tensor of shape {tuple(values.shape)} needs dims")
+                dims = (values.shape[2], values.shape[1], values.shape[0])
+            if int(np.prod([int(x) for x in dims])) != values.numel():
+                raise SphError(f"surface_from_volume: dims {tuple(dims)} do not match {values.numel()} values")
+            ptr = values.data_ptr()
+        else:
+            if dims is None:
+                raise SphError("surface_from_volume: a device address needs dims")
+            ptr = int(values)
+        surf = self.extract_surface_volume(ptr, origin, spacing, dims, iso)
+        return self._download_surface(surf)
+
+    # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
+    def statistics(self, histograms=None) -> Statistics:
+        """Counts, extrema, fp64 sums, cell occupancy and up to 4 histograms ((field, bins, lo, hi) with field one of SPH_STAT_*) of the
+        current state, reduced on the GPU (DESIGN.md section 3c).  Synchronises."""
+        specs, n, words = _histogram_specs(histograms)
+        out = SphStatistics()
+        hist = np.zeros(words, np.uint64)
+        self._push_params()
+        _check(self._L.sph_statistics(self._h, C.byref(out), specs, n, _ptr(hist) if n else None))
+        hs, at = [], 0
+        for i in range(n):
+            hs.append(hist[at:at + specs[i].bins + 2].copy())
+            at += specs[i].bins + 2
+        return Statistics(out, hs, self._p)
+
+    def statistics_device(self, dev_out: int, histograms=None, dev_hist: int = 0):
+        """The same into device memory: an 832-byte SphStatistics at dev_out and sum(bins + 2) uint64 at dev_hist (torch tensors'
+        data_ptr(), say).  Asynchronous on the engine's stream."""
+        specs, n, _ = _histogram_specs(histograms)
+        self._push_params()
+        _check(self._L.sph_statistics_device(self._h, C.c_void_p(dev_out), specs, n, C.c_void_p(dev_hist) if dev_hist else None))
+
+    # -- passive tracers (include/sph_abi.h "passive tracers") -----------------------------------
+    def set_tracers(self, points, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
+        """(m, 3) or (m, 4) points (x, y, z[, initial age]) replace the engine's tracer set: every substep from now on advects them
+        with the fluid's Shepard velocity (DESIGN.md section 3d) and keeps the `history` newest snapshots, one every `stride`
+        substeps, on the device.  Synchronises."""
+        p4 = _points4(points, "set_tracers", keep_w=True)
+        _check(self._L.sph_tracers_set(self._h, _ptr(p4), len(p4), int(integrator), int(history), int(stride)))
+
+    def set_tracers_device(self, dev_points: int, m: int, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
+        """The same from m points of 4 floats at device address dev_points.  Asynchronous on the engine's stream."""
+        _check(self._L.sph_tracers_set_device(self._h, C.c_void_p(dev_points), int(m), int(integrator), int(history), int(stride)))
+
+    def clear_tracers(self):
+        _check(self._L.sph_tracers_set(self._h, None, 0, SPH_TRACER_EULER, 0, 1))
+
+    def num_tracers(self) -> int:
+        return int(self._L.sph_tracers_count(self._h))
+
+    def tracer_info(self):
+        """(substeps that advected the current set, stored snapshots, number of the oldest stored snapshot)."""
+        c, n, q = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        _check(self._L.sph_tracers_info(self._h, C.byref(c), C.byref(n), C.byref(q)))
+        return int(c.value), int(n.value), int(q.value)
+
+    def tracers(self) -> np.ndarray:
+        """The tracers in the caller's order: a structured array of TRACER_DTYPE (pos, age, vel, fraction).  Synchronises."""
+        out = np.zeros(self.num_tracers(), TRACER_DTYPE)
+        _check(self._L.sph_tracers_download(self._h, _ptr(out), len(out)))
+        return out
+
+    def tracers_device(self) -> int:
+        """Borrowed device address of the 32-byte records in the caller's order (0 without tracers); valid until the next
+        dispatch, set, reset or close.  No synchronisation."""
+        p = C.c_void_p()
+        _check(self._L.sph_tracers_device(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def tracer_history(self):
+        """(first, array (count, M, 4)): the stored snapshots (x, y, z, age), oldest first, and the number of the first one.  Synchronises."""
+        _, n, _ = self.tracer_info()
+        out = np.zeros((max(n, 1), self.num_tracers(), 4), np.float32)
+        cnt, first = C.c_uint32(), C.c_uint64()
+        _check(self._L.sph_tracers_history(self._h, _ptr(out), out.shape[0], C.byref(cnt), C.byref(first)))
+        return int(first.value), out[:cnt.value]
+
+    # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
+    def set_obstacles(self, obstacles):
+        """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
+        now on keeps the fluid out of them, advances their poses and sums the fluid's impulses (DESIGN.md section 3e).  No synchronisation."""
+        arr = obstacle_array(obstacles)
+        _check(self._L.sph_obstacles_set(self._h, _ptr_or_none(arr), len(arr)))
+
+    def clear_obstacles(self):
+        _check(self._L.sph_obstacles_set(self._h, None, 0))
+
+    def set_obstacle_motion(self, index: int, vel, omega):
+        """New linear / angular velocity of body `index`; the pose stays the one the device holds.  No synchronisation."""
+        _check(self._L.sph_obstacles_set_motion(self._h, int(index), _f3(vel), _f3(omega)))
+
+    def obstacles(self) -> np.ndarray:
+        """The bodies with their current (advanced) poses, an OBSTACLE_DTYPE array.  Synchronises."""
+        out = np.zeros(SPH_MAX_OBSTACLES, OBSTACLE_DTYPE)
+        k = C.c_int()
+        _check(self._L.sph_obstacles_get(self._h, _ptr(out), len(out), C.byref(k)))
+        return out[:k.value].copy()
+
+    def obstacle_impulses(self, reset: bool = False):
+        """(J, time, substeps): J (K, 6) float64 = (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave each body since the last zeroing, the
+        simulated time and the substeps over which they were summed; reset zeroes them after the read.  Synchronises."""
+        out = np.zeros((SPH_MAX_OBSTACLES, 6), np.float64)
+        t, n = C.c_double(), C.c_uint64()
+        _check(self._L.sph_obstacles_impulses(self._h, _ptr(out), SPH_MAX_OBSTACLES, C.byref(t), C.byref(n), 1 if reset else 0))
+        return out[:len(self.obstacles())].copy(), float(t.value), int(n.value)
+
+    # -- triangle-mesh obstacles through signed distance lattices (include/sph_abi.h "signed distance lattices") --------
+    def create_volume(self, values, spacing) -> int:
+        """A volume from signed distances (negative inside) of shape (nz, ny, nx): a numpy array or a contiguous float32 torch CUDA tensor.
+        spacing is a scalar or (sx, sy, sz).  Returns the volume's id."""
+        vid = C.c_int(-1)
+        if hasattr(values, "data_ptr"):
+            if not _is_cuda_f32(values) or values.dim() != 3:
+                raise SphError("create_volume: values must be a contiguous float32 CUDA tensor of shape (nz, ny, nx)")
+            _check(self._L.sph_volume_create(self._h, C.c_void_p(values.data_ptr()), _dims3(values.shape[::-1]), _f3(_spacing3(spacing)), 1, C.byref(vid)))
+        else:
+            v, dims, sp = _volume_lattice(values, spacing)
+            _check(self._L.sph_volume_create(self._h, _ptr(v), dims, _f3(sp), 0, C.byref(vid)))
+        return int(vid.value)
+
+    def destroy_volume(self, volume_id: int):
+        _check(self._L.sph_volume_destroy(self._h, int(volume_id)))
+
+    def volume_info(self, volume_id: int):
+        """(dims (nx, ny, nz), spacing[3], half[3]) of a volume; half is the box size that covers the lattice exactly."""
+        d, sp, hf = (C.c_int * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
+        _check(self._L.sph_volume_info(self._h, int(volume_id), d, sp, hf))
+        return tuple(d), np.array(sp, np.float32), np.array(hf, np.float32)
+
+    def bind_obstacle_volume(self, index: int, volume_id: int):
+        """Body `index` (a box) takes its shape from the volume (volume_id < 0 unbinds).  set_obstacles clears every binding."""
+        _check(self._L.sph_obstacles_bind_volume(self._h, int(index), int(volume_id)))
+
+    def obstacle_volume(self, index: int) -> int:
+        vid = C.c_int(-1)
+        _check(self._L.sph_obstacles_volume(self._h, int(index), C.byref(vid)))
+        return int(vid.value)
+
+    def mesh_distance(self, vertices, triangles, origin, spacing, dims):
+        """Signed distance (negative inside) from the lattice points origin + i * spacing, dims = (nx, ny, nz), to a closed triangle mesh
+        (counter-clockwise seen from outside): a float32 torch CUDA tensor of shape (nz, ny, nx).  Asynchronous on the engine's stream."""
+        import torch
+        v, t = _mesh_arrays(vertices, triangles)
+        d = _dims3(dims, "mesh_distance")
+        sp = _spacing3(spacing)
+        out = torch.empty((int(d[2]), int(d[1]), int(d[0])), dtype=torch.float32, device="cuda")
+        _check(self._L.sph_mesh_distance(self._h, _ptr(v), len(v), _ptr(t), len(t), _f3(origin), _f3(sp), d, C.c_void_p(out.data_ptr())))
+        self.sync()                                                      # (the tensor is handed to the caller's own stream)
+        return out
+
+    def volume_from_mesh(self, vertices, triangles, spacing: float, margin: float = 2.0):
+        """A volume around a mesh: a lattice of the given spacing about the mesh's bounding box widened by `margin` spacings on every side.
+        Returns (id, center, half): obstacle(SPH_OBSTACLE_BOX, center, half) + bind_obstacle_volume(index, id) is the whole recipe."""
+        v, t = _mesh_arrays(vertices, triangles)
+        if not len(v):
+            raise SphError("volume_from_mesh: no vertices")
+        h = np.float32(spacing)
+        lo, hi = v.min(axis=0).astype(np.float64), v.max(axis=0).astype(np.float64)
+        dims = [max(2, int(math.ceil((hi[a] - lo[a]) / float(h) + 2.0 * margin)) + 1) for a in range(3)]
+        center = (0.5 * (lo + hi)).astype(np.float32)
+        vid = C.c_int(-1)
+        _check(self._L.sph_volume_from_mesh(self._h, _ptr(v), len(v), _ptr(t), len(t), _f3(center), _f3((h, h, h)), _dims3(dims), C.byref(vid)))
+        return int(vid.value), center, self.volume_info(vid.value)[2]
+
+    # -- dynamic rigid bodies (include/sph_abi.h "dynamic rigid bodies") -------------------------------
+    def set_obstacle_dynamics(self, index: int, record=None):
+        """Body `index` moves under the fluid's impulses, gravity and the container from the next substep on (a dynamics() record; None:
+        kinematic again).  Stream-ordered; a replayed graph sees it.  set_obstacles clears every record."""
+        _check(self._L.sph_obstacles_set_dynamics(self._h, int(index), C.byref(record) if record is not None else None))
+
+    def obstacle_dynamics(self, index: int):
+        """The record of body `index` as set, or None for a kinematic body."""
+        out, on = SphObstacleDynamics(), C.c_int()
+        _check(self._L.sph_obstacles_get_dynamics(self._h, int(index), C.byref(out), C.byref(on)))
+        return out if on.value else None
+
+    def volume_moments(self, volume_id: int) -> np.ndarray:
+        """The ten moments of the solid a volume describes (sph_volume_moments): cell volume times the weighted sums of
+        1, x, y, z, xx, yy, zz, xy, xz, yz.  Synchronises."""
+        out = np.zeros(10, np.float64)
+        _check(self._L.sph_volume_moments(self._h, int(volume_id), _ptr(out)))
+        return out
+
+    def volume_mass_properties(self, volume_id: int, density: float):
+        """(mass, centre of mass in the body frame, inertia about it as xx, yy, zz, xy, xz, yz) of a homogeneous body shaped by the volume."""
+        return mass_properties(self.volume_moments(volume_id), density)
+
+    # -- measurement (include/sph_abi.h "measurement") and the end of the engine's life ---------------------------
+    def kernel_times(self, reset: bool = False):
+        ms = (C.c_double * len(KERNEL_CLASSES))()
+        cnt = (C.c_int64 * len(KERNEL_CLASSES))()
+        _check(self._L.sph_kernel_times(self._h, ms, cnt, 1 if reset else 0))
+        return {k: (ms[i], cnt[i]) for i, k in enumerate(KERNEL_CLASSES)}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._L.sph_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
         try:
-            import torch  # noqa: F401
+            self.close()
         except Exception:
             pass
-    # developer A/B of kernel variants: SPH_HIP_LIB names another build of the same sources
-    L = C.CDLL(os.environ.get("SPH_HIP_LIB") or _build.LIB_PATH)
-    vp, pp, gp = C.c_void_p, C.POINTER(SphParams), C.POINTER(SphGridInfo)
-    f3 = C.POINTER(C.c_float)
-    L.sph_abi_version.restype = C.c_int
-    L.sph_last_error.restype = C.c_char_p
-    L.sph_params_default.argtypes = [pp]
-    L.sph_rotation_mat3.argtypes = [f3, f3]
-    L.sph_effective_half.argtypes = [pp, f3]
-    L.sph_compute_grid_extents.argtypes = [pp, gp]
-    L.sph_spawn_particles.argtypes = [pp, C.c_size_t, C.c_uint32, vp, C.POINTER(C.c_size_t), f3]
-    L.sph_create.argtypes = [C.POINTER(vp), C.c_size_t, pp, C.c_uint32, vp]
-    L.sph_create_from_particles.argtypes = [C.POINTER(vp), vp, C.c_size_t, pp, vp]
-    L.sph_destroy.argtypes = [vp]
-    L.sph_reset.argtypes = [vp, C.c_size_t, C.c_uint32]
-    L.sph_set_params.argtypes = [vp, pp]
-    L.sph_get_params.argtypes = [vp, pp]
-    L.sph_set_option.argtypes = [vp, C.c_int, C.c_int]
-    L.sph_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.sph_dispatch.argtypes = [vp, C.c_float]
-    L.sph_dispatch_n.argtypes = [vp, C.c_float, C.c_int]
-    L.sph_apply_wave_impulse.argtypes = [vp, C.c_float, C.c_float, C.c_float, f3, C.c_float, C.c_float]
-    L.sph_num_particles.argtypes = [vp]
-    L.sph_num_particles.restype = C.c_size_t
-    L.sph_grid_info.argtypes = [vp, gp]
-    L.sph_upload_particles.argtypes = [vp, vp, C.c_size_t]
-    L.sph_download_particles.argtypes = [vp, vp, C.c_size_t]
-    L.sph_device_particles.argtypes = [vp, C.POINTER(vp)]
-    L.sph_pack_render_buffer.argtypes = [vp, vp, C.c_size_t, C.c_int]
-    L.sph_initial_particles.argtypes = [vp, vp, C.c_size_t]
-    L.sph_download_grid.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
-    L.sph_sync.argtypes = [vp]
-    L.sph_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
-    L.sph_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.c_int]
-    L.sph_apply_vortex_impulse.argtypes = [vp, C.c_float, C.c_float]
-    L.sph_apply_attractor_impulse.argtypes = [vp, f3, C.c_float, C.c_float]
-    L.sph_set_stencil_targets.argtypes = [vp, vp, C.c_size_t]
-    L.sph_apply_stencil_attract.argtypes = [vp, C.c_float, C.c_float]
-    L.sph_apply_curl_flow.argtypes = [vp, C.c_float, C.c_float, C.c_float]
-    L.sph_fountain_default.argtypes = [C.POINTER(SphFountain)]
-    L.sph_set_fountain.argtypes = [vp, C.POINTER(SphFountain)]
-    L.sph_get_fountain.argtypes = [vp, C.POINTER(SphFountain)]
-    L.sph_create_slab.argtypes = [C.POINTER(vp), vp, vp, C.c_size_t, pp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
-    L.sph_slab_pack.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
-    L.sph_slab_unpack.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32]
-    L.sph_slab_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.sph_slab_alloc_faces.argtypes = [vp, C.c_uint32]
-    L.sph_slab_face_buffer.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.sph_slab_pack_async.argtypes = [vp]
-    L.sph_slab_unpack_async.argtypes = [vp, vp, vp, C.c_uint32]
-    L.sph_slab_status.argtypes = [vp, C.POINTER(C.c_uint32)]
-    L.sph_comm_unique_id.argtypes = [vp]
-    L.sph_comm_create.argtypes = [C.POINTER(vp), vp, C.c_int, C.c_int]
-    L.sph_comm_destroy.argtypes = [vp]
-    L.sph_comm_selftest.argtypes = [vp, C.c_uint64]
-    L.sph_comm_selftest_timed.argtypes = [vp, C.c_uint64, C.POINTER(C.c_float)]
-    L.sph_slab_exchange.argtypes = [vp, vp]
-    L.sph_slab_step_begin.argtypes = [vp, C.c_float]
-    L.sph_slab_step_finish.argtypes = [vp, vp]
-    L.sph_slab_step_finish_local.argtypes = [vp, vp, vp]
-    L.sph_slab_face_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.sph_slab_clear_flags.argtypes = [vp, C.c_uint32]
-    L.sph_slab_message_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.sph_slab_step_times.argtypes = [vp, C.POINTER(C.c_float)]
-    L.sph_slab_message_records.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
-    L.sph_river_default.argtypes = [C.POINTER(SphRiver)]
-    L.sph_generate_river_terrain.argtypes = [pp, C.c_int, C.POINTER(SphRiver), vp]
-    L.sph_spawn_river_particles.argtypes = [pp, C.POINTER(SphRiver), vp, C.c_size_t, C.c_uint32, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]
-    L.sph_set_river.argtypes = [vp, C.POINTER(SphRiver), vp]
-    L.sph_get_river.argtypes = [vp, C.POINTER(SphRiver)]
-    L.sph_slab_set_verify.argtypes = [vp, C.c_int]
-    L.sph_slab_set_deadline.argtypes = [vp, C.c_double]
-    L.sph_slab_plan.argtypes = [vp, C.POINTER(SphSlabIntent), C.POINTER(C.c_float)]
-    L.sph_slab_plans_agree.argtypes = [C.POINTER(SphSlabIntent), C.POINTER(SphSlabIntent), C.c_int, C.c_char_p, C.c_size_t]
-    L.sph_sync_deadline.argtypes = [vp, C.c_double]
-    L.sph_slab_debug_tight_messages.argtypes = [vp, C.c_int]
-    L.sph_comm_selftest_faces.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
-    L.sph_sample_points.argtypes = [vp, vp, C.c_size_t, vp]
-    L.sph_sample_points_device.argtypes = [vp, vp, C.c_size_t, vp]
-    L.sph_sample_lattice.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, vp]
-    L.sph_extract_surface.argtypes = [vp, f3, f3, C.POINTER(C.c_int), C.c_int, C.c_float, C.POINTER(SphSurface)]
-    L.sph_extract_surface_volume.argtypes = [vp, vp, f3, f3, C.POINTER(C.c_int), C.c_float, C.POINTER(SphSurface)]
-    L.sph_surface_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
-    L.sph_statistics.argtypes = [vp, vp, vp, C.c_int, vp]
-    L.sph_statistics_device.argtypes = [vp, vp, vp, C.c_int, vp]
-    L.sph_tracers_set.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
-    L.sph_tracers_set_device.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
-    L.sph_tracers_count.argtypes = [vp]
-    L.sph_tracers_count.restype = C.c_size_t
-    L.sph_tracers_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.sph_tracers_download.argtypes = [vp, vp, C.c_size_t]
-    L.sph_tracers_device.argtypes = [vp, C.POINTER(C.c_void_p)]
-    L.sph_tracers_history.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.sph_obstacle_default.argtypes = [vp]
-    L.sph_obstacle_default.restype = None
-    L.sph_obstacles_set.argtypes = [vp, vp, C.c_int]
-    L.sph_obstacles_set_motion.argtypes = [vp, C.c_int, f3, f3]
-    L.sph_obstacles_get.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
-    L.sph_obstacles_impulses.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
-    L.sph_obstacles_apply_host.argtypes = [vp, C.c_int, C.c_float, vp, C.c_size_t, vp]
-    L.sph_obstacles_advance_host.argtypes = [vp, C.c_int, C.c_float]
-    i3 = C.POINTER(C.c_int)
-    L.sph_volume_create.argtypes = [vp, vp, i3, f3, C.c_int, i3]
-    L.sph_volume_destroy.argtypes = [vp, C.c_int]
-    L.sph_volume_info.argtypes = [vp, C.c_int, i3, f3, f3]
-    L.sph_volume_sample_host.argtypes = [vp, i3, f3, f3, f3, f3, i3]
-    L.sph_obstacles_bind_volume.argtypes = [vp, C.c_int, C.c_int]
-    L.sph_obstacles_volume.argtypes = [vp, C.c_int, i3]
-    L.sph_obstacles_apply_host_volumes.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_float, vp, C.c_size_t, vp]
-    L.sph_mesh_distance.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
-    L.sph_volume_from_mesh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, i3]
-    L.sph_mesh_distance_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, f3, f3, i3, vp]
-    L.sph_obstacle_dynamics_default.argtypes = [vp]
-    L.sph_obstacle_dynamics_default.restype = None
-    L.sph_obstacles_set_dynamics.argtypes = [vp, C.c_int, vp]
-    L.sph_obstacles_get_dynamics.argtypes = [vp, C.c_int, vp, i3]
-    L.sph_obstacles_step_host.argtypes = [vp, vp, C.c_int, vp, pp, C.c_float]
-    L.sph_volume_moments.argtypes = [vp, C.c_int, vp]
-    L.sph_volume_moments_host.argtypes = [vp, i3, f3, vp]
-    for name in ABI_SYMBOLS:
-        fn = getattr(L, name)
-        if name not in ("sph_last_error", "sph_num_particles", "sph_abi_version", "sph_fountain_default", "sph_river_default", "sph_tracers_count",
-                        "sph_obstacle_default", "sph_obstacle_dynamics_default"):
-            fn.restype = C.c_int
-    _lib = L
-    return L
 
 
-def _check(rc: int):
-    if rc != 0:
-        msg = load_library().sph_last_error()
-        raise SphError(f"sph C-ABI error {rc}: {msg.decode() if msg else '?'}")
-
-
-def _f3(v):
-    return (C.c_float * 3)(*[float(x) for x in v])
-
-
+# ---- host-only functions (no device is needed), in the order of include/sph_abi.h ------------------------------------------
 def default_params(**overrides) -> SphParams:
     p = SphParams()
     _check(load_library().sph_params_default(C.byref(p)))
     for k, v in overrides.items():
-        cur = getattr(p, k)
-        if hasattr(cur, "__len__"):
-            for i, x in enumerate(v):
-                cur[i] = x
-        else:
-            setattr(p, k, v)
+        _assign(p, k, v)
     return p
 
 
@@ -636,7 +1179,7 @@ def spawn_particles(p: SphParams, n_requested: int, seed: int):
     buf = np.zeros(max(n_requested, 1), PARTICLE_DTYPE)
     n = C.c_size_t()
     mass = C.c_float()
-    _check(load_library().sph_spawn_particles(C.byref(p), n_requested, seed, buf.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(mass)))
+    _check(load_library().sph_spawn_particles(C.byref(p), n_requested, seed, _ptr(buf), C.byref(n), C.byref(mass)))
     return buf[: n.value].copy(), float(mass.value)
 
 
@@ -644,7 +1187,7 @@ def default_river(**kw) -> SphRiver:
     r = SphRiver()
     load_library().sph_river_default(C.byref(r))
     for k, v in kw.items():
-        setattr(r, k, v)
+        _assign(r, k, v)
     return r
 
 
@@ -653,7 +1196,7 @@ def generate_river_terrain(p: SphParams, seed: int, river: SphRiver | None = Non
     writes param_gravityY / Z of `p` like the reference."""
     r = river if river is not None else default_river()
     heights = np.zeros(r.terrainW * r.terrainH, np.float32)
-    _check(load_library().sph_generate_river_terrain(C.byref(p), int(seed), C.byref(r), heights.ctypes.data_as(C.c_void_p)))
+    _check(load_library().sph_generate_river_terrain(C.byref(p), int(seed), C.byref(r), _ptr(heights)))
     return r, heights
 
 
@@ -663,8 +1206,7 @@ def spawn_river_particles(p: SphParams, river: SphRiver, heights: np.ndarray, n_
     buf = np.zeros(max(n_requested, 1), PARTICLE_DTYPE)
     n = C.c_size_t()
     mass = C.c_float()
-    _check(load_library().sph_spawn_river_particles(C.byref(p), C.byref(river), h.ctypes.data_as(C.c_void_p), n_requested, seed,
-                                                    buf.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(mass)))
+    _check(load_library().sph_spawn_river_particles(C.byref(p), C.byref(river), _ptr(h), n_requested, seed, _ptr(buf), C.byref(n), C.byref(mass)))
     return buf[: n.value].copy(), float(mass.value)
 
 
@@ -725,577 +1267,28 @@ def write_pathlines_ply(path, history: np.ndarray) -> None:
         fh.write(edges.tobytes())
 
 
-_PARAM_NAMES = {f[0] for f in SphParams._fields_}
-_RIVER_NAMES = {f[0] for f in SphRiver._fields_}
-_FOUNTAIN_NAMES = {f[0] for f in SphFountain._fields_}
-
-
-class SPHFluidGPU:
-    """Drop-in for the reference class of the same name (SPHFluid3D.h:26).
-
-    SPHFluidGPU(numParticles)                    -> spawn as InitializeParticles does (seeded)
-    SPHFluidGPU.from_particles(records, params)  -> caller-provided 80-byte records
-    """
-
-    def __init__(self, numParticles_: int = 50000, params: SphParams | None = None, seed: int = 1, stream: int | None = None,
-                 _particles: np.ndarray | None = None):
-        L = load_library()
-        object.__setattr__(self, "_L", L)
-        object.__setattr__(self, "_p", params if params is not None else default_params())
-        object.__setattr__(self, "_h", C.c_void_p())
-        object.__setattr__(self, "_f", SphFountain())
-        L.sph_fountain_default(C.byref(self._f))
-        object.__setattr__(self, "_r", SphRiver())
-        L.sph_river_default(C.byref(self._r))
-        object.__setattr__(self, "terrainHeights", np.zeros(0, np.float32))   # SPHFluid3D.h:175
-        object.__setattr__(self, "_terrain_sent", None)
-        object.__setattr__(self, "numParticles", int(numParticles_))
-        object.__setattr__(self, "seed", int(seed))
-        if _particles is not None:
-            arr = np.ascontiguousarray(_particles, dtype=PARTICLE_DTYPE)
-            _check(L.sph_create_from_particles(C.byref(self._h), arr.ctypes.data_as(C.c_void_p), len(arr), C.byref(self._p), stream))
-        else:
-            _check(L.sph_create(C.byref(self._h), self.numParticles, C.byref(self._p), self.seed, stream))
-        _check(L.sph_get_params(self._h, C.byref(self._p)))   # spawn overwrote param_mass (SPHFluid3D.cpp:92)
-
-    @classmethod
-    def from_particles(cls, particles: np.ndarray, params: SphParams, stream: int | None = None) -> "SPHFluidGPU":
-        return cls(len(particles), params=params, stream=stream, _particles=particles)
-
-    # -- public param_* members ----------------------------------------------------------
-    def __getattr__(self, name):
-        if name in _PARAM_NAMES or name in _FOUNTAIN_NAMES or name in _RIVER_NAMES:
-            v = getattr(object.__getattribute__(self, "_p" if name in _PARAM_NAMES else ("_f" if name in _FOUNTAIN_NAMES else "_r")), name)
-            return list(v) if hasattr(v, "__len__") else v
-        raise AttributeError(name)
-
-    def __setattr__(self, name, value):
-        if name in _PARAM_NAMES or name in _FOUNTAIN_NAMES or name in _RIVER_NAMES:
-            st = self._p if name in _PARAM_NAMES else (self._f if name in _FOUNTAIN_NAMES else self._r)
-            cur = getattr(st, name)
-            if hasattr(cur, "__len__"):
-                for i, x in enumerate(value):
-                    cur[i] = x
-            else:
-                setattr(st, name, value)
-        else:
-            object.__setattr__(self, name, value)
-
-    @property
-    def params(self) -> SphParams:
-        return self._p
-
-    # -- reference methods ---------------------------------------------------------------
-    def _push_members(self):
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))  # members are re-read every dispatch (:458-506)
-        _check(self._L.sph_set_fountain(self._h, C.byref(self._f)))  # fountain* members (:519-541)
-        self._push_river()
-
-    def _push_river(self):                                           # river members (:511-516); the heightfield only when it changed
-        th = self.terrainHeights
-        fresh = th is not self._terrain_sent and len(th) > 0
-        ptr = None
-        if fresh:
-            th = np.ascontiguousarray(th, np.float32)
-            if len(th) != self._r.terrainW * self._r.terrainH:
-                raise SphError(f"terrainHeights has {len(th)} samples, terrainW x terrainH = {self._r.terrainW * self._r.terrainH}")
-            ptr = th.ctypes.data_as(C.c_void_p)
-        _check(self._L.sph_set_river(self._h, C.byref(self._r), ptr))
-        if fresh:
-            object.__setattr__(self, "_terrain_sent", self.terrainHeights)
-
-    def set_river(self, river: SphRiver, heights):                   # all river members + terrainHeights in one go
-        C.memmove(C.byref(self._r), C.byref(river), C.sizeof(SphRiver))
-        object.__setattr__(self, "terrainHeights", np.ascontiguousarray(heights, np.float32).copy())
-        self._push_river()
-
-    def GenerateRiverTerrain(self, seed: int):                       # SPHFluid3D.cpp:772-878
-        heights = np.zeros(self._r.terrainW * self._r.terrainH, np.float32)
-        _check(self._L.sph_generate_river_terrain(C.byref(self._p), int(seed), C.byref(self._r), heights.ctypes.data_as(C.c_void_p)))
-        object.__setattr__(self, "terrainHeights", heights)
-        self._push_river()
-
-    def DispatchCompute(self, overrideDt: float = -1.0):            # SPHFluid3D.cpp:431
-        self._push_members()
-        _check(self._L.sph_dispatch(self._h, overrideDt))
-        _check(self._L.sph_get_fountain(self._h, C.byref(self._f)))  # fountainSeed++ (:541)
-
-    SimulateSubstep = DispatchCompute   # BASELINE.json's name for the same entry point
-
-    def DispatchN(self, n: int, overrideDt: float = -1.0):           # Scene0p.cpp:3720-3739 loop
-        self._push_members()
-        _check(self._L.sph_dispatch_n(self._h, overrideDt, int(n)))
-        _check(self._L.sph_get_fountain(self._h, C.byref(self._f)))
-
-    def ResetSimulation(self, seed: int | None = None):             # SPHFluid3D.cpp:713
-        if seed is not None:
-            self.seed = int(seed)
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        self._push_river()                                           # riverMode && !terrainHeights.empty() picks the spawn branch (:104)
-        _check(self._L.sph_reset(self._h, self.numParticles, self.seed))
-        _check(self._L.sph_get_params(self._h, C.byref(self._p)))
-
-    def ApplyWaveImpulse(self, amplitude, wavelength, phase, dir, yMin=-FLT_MAX, yMax=FLT_MAX):   # SPHFluid3D.cpp:604
-        _check(self._L.sph_apply_wave_impulse(self._h, amplitude, wavelength, phase, _f3(dir), yMin, yMax))
-
-    def ApplyVortexImpulse(self, tangentKick, inwardKick):          # SPHFluid3D.cpp:627
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))   # reads param_boxCenter / EulerDeg / half
-        _check(self._L.sph_apply_vortex_impulse(self._h, tangentKick, inwardKick))
-
-    def ApplyAttractorImpulse(self, point, pullKick, radius):        # SPHFluid3D.cpp:650
-        _check(self._L.sph_apply_attractor_impulse(self._h, _f3(point), pullKick, radius))
-
-    def SetStencilTargets(self, points):                             # SPHFluid3D.cpp:684
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
-        _check(self._L.sph_set_stencil_targets(self._h, pts.ctypes.data_as(C.c_void_p), len(pts)))
-        object.__setattr__(self, "stencilCount", len(pts))
-
-    def ApplyStencilAttract(self, pullKick, dampKick):               # SPHFluid3D.cpp:695
-        _check(self._L.sph_apply_stencil_attract(self._h, pullKick, dampKick))
-
-    def ApplyCurlFlow(self, kick, scale, time):                      # SPHFluid3D.cpp:668
-        _check(self._L.sph_apply_curl_flow(self._h, kick, scale, time))
-
-    def EffectiveHalf(self):                                         # SPHFluid3D.h:127
-        return effective_half(self._p)
-
-    def ComputeGridExtents(self):                                    # SPHFluid3D.cpp:354
-        return compute_grid_extents(self._p)
-
-    def GetNumFluids(self) -> int:                                   # SPHFluid3D.cpp:601
-        return int(self._L.sph_num_particles(self._h))
-
-    # -- reference data members ----------------------------------------------------------
-    @property
-    def particles(self) -> np.ndarray:
-        """Host copy of the INITIAL records (never refreshed, as in the reference)."""
-        n = self.GetNumFluids()
-        out = np.zeros(n, PARTICLE_DTYPE)
-        _check(self._L.sph_initial_particles(self._h, out.ctypes.data_as(C.c_void_p), n))
-        return out
-
-    def _grid(self) -> SphGridInfo:
-        g = SphGridInfo()
-        _check(self._L.sph_grid_info(self._h, C.byref(g)))
-        return g
-
-    gridSizeX = property(lambda self: self._grid().dims[0])
-    gridSizeY = property(lambda self: self._grid().dims[1])
-    gridSizeZ = property(lambda self: self._grid().dims[2])
-    numCells = property(lambda self: self._grid().numCells)
-    gridMinV = property(lambda self: list(self._grid().gridMin))
-    cellSize = property(lambda self: self._grid().cellSize)
-
-    # -- engine extras -------------------------------------------------------------------
-    def set_option(self, option: int, value: int):
-        _check(self._L.sph_set_option(self._h, option, value))
-
-    def get_option(self, option: int) -> int:
-        v = C.c_int(0)
-        _check(self._L.sph_get_option(self._h, option, C.byref(v)))
-        return v.value
-
-    def upload(self, particles: np.ndarray):
-        arr = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
-        _check(self._L.sph_upload_particles(self._h, arr.ctypes.data_as(C.c_void_p), len(arr)))
-
-    def download(self) -> np.ndarray:
-        n = self.GetNumFluids()
-        out = np.zeros(n, PARTICLE_DTYPE)
-        _check(self._L.sph_download_particles(self._h, out.ctypes.data_as(C.c_void_p), n))
-        return out
-
-    def device_particles(self) -> int:
-        """Device address of the 80-byte AoS (the `ssbo` renderers bind, Scene0p.cpp:1625)."""
-        p = C.c_void_p()
-        _check(self._L.sph_device_particles(self._h, C.byref(p)))
-        return int(p.value)
-
-    def pack_render_buffer(self, dev_ptr: int, w_mode: int = 0):
-        """(x, y, z, w) per particle in original order into a caller-owned device buffer (a mapped vertex
-        buffer in a renderer; a torch tensor's data_ptr() in the tests)."""
-        _check(self._L.sph_pack_render_buffer(self._h, C.c_void_p(dev_ptr), self.GetNumFluids(), int(w_mode)))
-
-    def download_grid(self):
-        g = compute_grid_extents(self._p)
-        n = self.GetNumFluids()
-        cnt = np.zeros(g.numCells, np.int32)
-        pc = np.zeros(max(n, 1), np.int32)
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_download_grid(self._h, cnt.ctypes.data_as(C.c_void_p), g.numCells, pc.ctypes.data_as(C.c_void_p), n))
-        return cnt, pc[:n]
-
-    # -- field sampling (include/sph_abi.h "field sampling") ----------------------------------
-    def sample(self, points) -> np.ndarray:
-        """Fields of the current state at (m, 3) or (m, 4) probe points: a structured array of SAMPLE_DTYPE (density, fraction,
-        pressure, count, vel).  Synchronises."""
-        pts = np.asarray(points, dtype=np.float32)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise SphError(f"sample: points must have shape (m, 3) or (m, 4), not {pts.shape}")
-        p4 = np.zeros((len(pts), 4), np.float32)
-        p4[:, :3] = pts[:, :3]
-        out = np.zeros(len(pts), SAMPLE_DTYPE)
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_sample_points(self._h, p4.ctypes.data_as(C.c_void_p), len(p4), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def sample_device(self, dev_points: int, m: int, dev_out: int):
-        """m probes of 4 floats at device address dev_points -> m 32-byte SphSample records at dev_out (a torch tensor's
-        data_ptr(), say).  Asynchronous on the engine's stream."""
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_sample_points_device(self._h, C.c_void_p(dev_points), int(m), C.c_void_p(dev_out)))
-
-    def sample_lattice_device(self, origin, spacing, dims, dev_out: int, field: int = SPH_FIELD_DENSITY):
-        """Lattice origin + i * spacing (dims = (nx, ny, nz), x fastest) into a caller's device buffer: one float per point, or one
-        SphSample per point for SPH_FIELD_ALL.  Asynchronous on the engine's stream."""
-        d = (C.c_int * 3)(*[int(x) for x in dims])
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_sample_lattice(self._h, _f3(origin), _f3(spacing), d, int(field), C.c_void_p(dev_out)))
-
-    def sample_lattice(self, origin, spacing, dims, field: int = SPH_FIELD_DENSITY) -> np.ndarray:
-        """Host copy of sample_lattice_device: shape (nz, ny, nx), float32 or SAMPLE_DTYPE (SPH_FIELD_ALL)."""
-        import torch
-        nx, ny, nz = (int(x) for x in dims)
-        if min(nx, ny, nz) < 1:
-            raise SphError(f"sample_lattice: dims must be >= 1, not {tuple(dims)}")
-        words = 8 if field == SPH_FIELD_ALL else 1
-        buf = torch.empty(nx * ny * nz * words, dtype=torch.float32, device="cuda")
-        self.sample_lattice_device(origin, spacing, (nx, ny, nz), buf.data_ptr(), field)
-        self.sync()
-        host = buf.cpu().numpy()
-        if field == SPH_FIELD_ALL:
-            return host.view(SAMPLE_DTYPE).reshape(nz, ny, nx)
-        return host.reshape(nz, ny, nx)
-
-    def water_level(self, xz, y_lo: float, y_hi: float, dy: float, threshold: float = 0.5) -> np.ndarray:
-        """Wave gauge: per (x, z) column, the first y from the top where `fraction` >= threshold, sampled at y_hi, y_hi - dy, ...
-        down to y_lo and linearly interpolated against the sample above it; NaN where no sample reaches the threshold."""
-        cols = np.asarray(xz, dtype=np.float32).reshape(-1, 2)
-        ys = np.float32(y_hi) - np.arange(int(np.floor((y_hi - y_lo) / dy + 1e-6)) + 1, dtype=np.float32) * np.float32(dy)
-        pts = np.zeros((len(cols), len(ys), 4), np.float32)
-        pts[:, :, 0] = cols[:, None, 0]
-        pts[:, :, 1] = ys[None, :]
-        pts[:, :, 2] = cols[:, None, 1]
-        frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
-        return gauge_levels(frac, ys, threshold)
-
-    # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
-    def default_surface_lattice(self):
-        """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
-        g = self.ComputeGridExtents()
-        h = np.float32(self._p.param_h)
-        s = np.float32(h / np.float32(2))
-        lo = np.array(g.gridMin, np.float32) - np.float32(2) * h
-        ext = np.float32(g.cellSize) * np.array(g.dims, np.float32) + np.float32(4) * h
-        dims = tuple(int(np.ceil(ext[a] / s)) + 1 for a in range(3))
-        return tuple(float(x) for x in lo), (float(s),) * 3, dims
-
-    def _download_surface(self, surf: SphSurface):
-        v = np.zeros(surf.numVertices, SURFACE_VERTEX_DTYPE)
-        t = np.zeros((surf.numTriangles, 3), np.uint32)
-        _check(self._L.sph_surface_download(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
-        return v, t
-
-    def extract_surface(self, origin, spacing, dims, iso: float = 0.5, field: int = SPH_FIELD_FRACTION) -> SphSurface:
-        """sph_extract_surface: counts and borrowed device arrays (valid until the next extract call, ResetSimulation or close)."""
-        d = (C.c_int * 3)(*[int(x) for x in dims])
-        surf = SphSurface()
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_extract_surface(self._h, _f3(origin), _f3(spacing), d, int(field), float(iso), C.byref(surf)))
-        return surf
-
-    def surface(self, origin=None, spacing=None, dims=None, iso: float = 0.5, field: int = SPH_FIELD_FRACTION):
-        """Iso-surface {field >= iso} of the current state as a closed triangle mesh (DESIGN.md section 3b): (vertices of
-        SURFACE_VERTEX_DTYPE, triangles (T, 3) uint32).  Lattice members left None come from default_surface_lattice()."""
-        do, ds, dd = self.default_surface_lattice() if origin is None or spacing is None or dims is None else (None, None, None)
-        surf = self.extract_surface(do if origin is None else origin, ds if spacing is None else spacing, dd if dims is None else dims, iso, field)
-        return self._download_surface(surf)
-
-    def extract_surface_volume(self, dev_values: int, origin, spacing, dims, iso: float = 0.5) -> SphSurface:
-        """sph_extract_surface_volume on a device address: counts and borrowed device arrays."""
-        d = (C.c_int * 3)(*[int(x) for x in dims])
-        surf = SphSurface()
-        _check(self._L.sph_extract_surface_volume(self._h, C.c_void_p(dev_values), _f3(origin), _f3(spacing), d, float(iso), C.byref(surf)))
-        return surf
-
-    def surface_from_volume(self, values, origin, spacing, dims=None, iso: float = 0.5):
-        """Iso-surface {values >= iso} of a caller's lattice of floats (x fastest): a torch CUDA float32 tensor of shape (nz, ny, nx)
-        (dims may then be omitted) or a device address with dims = (nx, ny, nz).  Returns (vertices, triangles) like surface()."""
-        if hasattr(values, "data_ptr"):
-            if not values.is_cuda or values.dtype != __import__("torch").float32 or not values.is_contiguous():
-                raise SphError("surface_from_volume: values must be a contiguous float32 CUDA tensor")
-            if dims is None:
-                if values.dim() != 3:
-                    raise SphError(f"surface_from_volume: a tensor of shape {tuple(values.shape)} needs dims")
-                dims = (values.shape[2], values.shape[1], values.shape[0])
-            if int(np.prod([int(x) for x in dims])) != values.numel():
-                raise SphError(f"surface_from_volume: dims {tuple(dims)} do not match {values.numel()} values")
-            ptr = values.data_ptr()
-        else:
-            if dims is None:
-                raise SphError("surface_from_volume: a device address needs dims")
-            ptr = int(values)
-        surf = self.extract_surface_volume(ptr, origin, spacing, dims, iso)
-        return self._download_surface(surf)
-
-    # -- passive tracers (include/sph_abi.h "passive tracers") -----------------------------------
-    def set_tracers(self, points, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
-        """(m, 3) or (m, 4) points (x, y, z[, initial age]) replace the engine's tracer set: every substep from now on advects them
-        with the fluid's Shepard velocity (DESIGN.md section 3d) and keeps the `history` newest snapshots, one every `stride`
-        substeps, on the device.  Synchronises."""
-        pts = np.asarray(points, dtype=np.float32)
-        if pts.ndim != 2 or pts.shape[1] not in (3, 4):
-            raise SphError(f"set_tracers: points must have shape (m, 3) or (m, 4), not {pts.shape}")
-        p4 = np.zeros((len(pts), 4), np.float32)
-        p4[:, :pts.shape[1]] = pts
-        _check(self._L.sph_tracers_set(self._h, p4.ctypes.data_as(C.c_void_p), len(p4), int(integrator), int(history), int(stride)))
-
-    def set_tracers_device(self, dev_points: int, m: int, integrator: int = SPH_TRACER_MIDPOINT, history: int = 0, stride: int = 1):
-        """The same from m points of 4 floats at device address dev_points.  Asynchronous on the engine's stream."""
-        _check(self._L.sph_tracers_set_device(self._h, C.c_void_p(dev_points), int(m), int(integrator), int(history), int(stride)))
-
-    def clear_tracers(self):
-        _check(self._L.sph_tracers_set(self._h, None, 0, SPH_TRACER_EULER, 0, 1))
-
-    def num_tracers(self) -> int:
-        return int(self._L.sph_tracers_count(self._h))
-
-    def tracer_info(self):
-        """(substeps that advected the current set, stored snapshots, number of the oldest stored snapshot)."""
-        c, n, q = C.c_uint64(), C.c_uint32(), C.c_uint64()
-        _check(self._L.sph_tracers_info(self._h, C.byref(c), C.byref(n), C.byref(q)))
-        return int(c.value), int(n.value), int(q.value)
-
-    def tracers(self) -> np.ndarray:
-        """The tracers in the caller's order: a structured array of TRACER_DTYPE (pos, age, vel, fraction).  Synchronises."""
-        out = np.zeros(self.num_tracers(), TRACER_DTYPE)
-        _check(self._L.sph_tracers_download(self._h, out.ctypes.data_as(C.c_void_p), len(out)))
-        return out
-
-    def tracers_device(self) -> int:
-        """Borrowed device address of the 32-byte records in the caller's order (0 without tracers); valid until the next
-        dispatch, set, reset or close.  No synchronisation."""
-        p = C.c_void_p()
-        _check(self._L.sph_tracers_device(self._h, C.byref(p)))
-        return int(p.value or 0)
-
-    def tracer_history(self):
-        """(first, array (count, M, 4)): the stored snapshots (x, y, z, age), oldest first, and the number of the first one.  Synchronises."""
-        _, n, _ = self.tracer_info()
-        out = np.zeros((max(n, 1), self.num_tracers(), 4), np.float32)
-        cnt, first = C.c_uint32(), C.c_uint64()
-        _check(self._L.sph_tracers_history(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(cnt), C.byref(first)))
-        return int(first.value), out[:cnt.value]
-
-    # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
-    def set_obstacles(self, obstacles):
-        """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
-        now on keeps the fluid out of them, advances their poses and sums the fluid's impulses (DESIGN.md section 3e).  No synchronisation."""
-        arr = obstacle_array(obstacles)
-        _check(self._L.sph_obstacles_set(self._h, arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr)))
-
-    def clear_obstacles(self):
-        _check(self._L.sph_obstacles_set(self._h, None, 0))
-
-    def set_obstacle_motion(self, index: int, vel, omega):
-        """New linear / angular velocity of body `index`; the pose stays the one the device holds.  No synchronisation."""
-        _check(self._L.sph_obstacles_set_motion(self._h, int(index), _f3(vel), _f3(omega)))
-
-    def obstacles(self) -> np.ndarray:
-        """The bodies with their current (advanced) poses, an OBSTACLE_DTYPE array.  Synchronises."""
-        out = np.zeros(SPH_MAX_OBSTACLES, OBSTACLE_DTYPE)
-        k = C.c_int()
-        _check(self._L.sph_obstacles_get(self._h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(k)))
-        return out[:k.value].copy()
-
-    def obstacle_impulses(self, reset: bool = False):
-        """(J, time, substeps): J (K, 6) float64 = (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave each body since the last zeroing, the
-        simulated time and the substeps over which they were summed; reset zeroes them after the read.  Synchronises."""
-        out = np.zeros((SPH_MAX_OBSTACLES, 6), np.float64)
-        t, n = C.c_double(), C.c_uint64()
-        _check(self._L.sph_obstacles_impulses(self._h, out.ctypes.data_as(C.c_void_p), SPH_MAX_OBSTACLES, C.byref(t), C.byref(n), 1 if reset else 0))
-        return out[:len(self.obstacles())].copy(), float(t.value), int(n.value)
-
-    # -- state statistics (include/sph_abi.h "statistics") ----------------------------------------
-    # -- triangle-mesh obstacles through signed distance lattices (include/sph_abi.h "signed distance lattices") --------
-    def create_volume(self, values, spacing) -> int:
-        """A volume from signed distances (negative inside) of shape (nz, ny, nx): a numpy array or a contiguous float32 torch CUDA tensor.
-        spacing is a scalar or (sx, sy, sz).  Returns the volume's id."""
-        vid = C.c_int(-1)
-        if hasattr(values, "data_ptr"):
-            if not values.is_cuda or values.dtype != __import__("torch").float32 or not values.is_contiguous() or values.dim() != 3:
-                raise SphError("create_volume: values must be a contiguous float32 CUDA tensor of shape (nz, ny, nx)")
-            dims = (C.c_int * 3)(values.shape[2], values.shape[1], values.shape[0])
-            sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
-            _check(self._L.sph_volume_create(self._h, C.c_void_p(values.data_ptr()), dims, _f3(sp), 1, C.byref(vid)))
-        else:
-            v, dims, sp = _volume_lattice(values, spacing)
-            _check(self._L.sph_volume_create(self._h, v.ctypes.data_as(C.c_void_p), dims, _f3(sp), 0, C.byref(vid)))
-        return int(vid.value)
-
-    def destroy_volume(self, volume_id: int):
-        _check(self._L.sph_volume_destroy(self._h, int(volume_id)))
-
-    def volume_info(self, volume_id: int):
-        """(dims (nx, ny, nz), spacing[3], half[3]) of a volume; half is the box size that covers the lattice exactly."""
-        d, sp, hf = (C.c_int * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
-        _check(self._L.sph_volume_info(self._h, int(volume_id), d, sp, hf))
-        return tuple(d), np.array(sp, np.float32), np.array(hf, np.float32)
-
-    def bind_obstacle_volume(self, index: int, volume_id: int):
-        """Body `index` (a box) takes its shape from the volume (volume_id < 0 unbinds).  set_obstacles clears every binding."""
-        _check(self._L.sph_obstacles_bind_volume(self._h, int(index), int(volume_id)))
-
-    # -- dynamic rigid bodies (include/sph_abi.h "dynamic rigid bodies") -------------------------------
-    def set_obstacle_dynamics(self, index: int, record=None):
-        """Body `index` moves under the fluid's impulses, gravity and the container from the next substep on (a dynamics() record; None:
-        kinematic again).  Stream-ordered; a replayed graph sees it.  set_obstacles clears every record."""
-        _check(self._L.sph_obstacles_set_dynamics(self._h, int(index), C.byref(record) if record is not None else None))
-
-    def obstacle_dynamics(self, index: int):
-        """The record of body `index` as set, or None for a kinematic body."""
-        out, on = SphObstacleDynamics(), C.c_int()
-        _check(self._L.sph_obstacles_get_dynamics(self._h, int(index), C.byref(out), C.byref(on)))
-        return out if on.value else None
-
-    def volume_moments(self, volume_id: int) -> np.ndarray:
-        """The ten moments of the solid a volume describes (sph_volume_moments): cell volume times the weighted sums of
-        1, x, y, z, xx, yy, zz, xy, xz, yz.  Synchronises."""
-        out = np.zeros(10, np.float64)
-        _check(self._L.sph_volume_moments(self._h, int(volume_id), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def volume_mass_properties(self, volume_id: int, density: float):
-        """(mass, centre of mass in the body frame, inertia about it as xx, yy, zz, xy, xz, yz) of a homogeneous body shaped by the volume."""
-        return mass_properties(self.volume_moments(volume_id), density)
-
-    def obstacle_volume(self, index: int) -> int:
-        vid = C.c_int(-1)
-        _check(self._L.sph_obstacles_volume(self._h, int(index), C.byref(vid)))
-        return int(vid.value)
-
-    def mesh_distance(self, vertices, triangles, origin, spacing, dims):
-        """Signed distance (negative inside) from the lattice points origin + i * spacing, dims = (nx, ny, nz), to a closed triangle mesh
-        (counter-clockwise seen from outside): a float32 torch CUDA tensor of shape (nz, ny, nx).  Asynchronous on the engine's stream."""
-        import torch
-        v, t = _mesh_arrays(vertices, triangles)
-        d = (C.c_int * 3)(*[int(x) for x in dims])
-        sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
-        if min(d) < 1 or int(d[0]) * int(d[1]) * int(d[2]) > 2 ** 31 - 1:
-            raise SphError(f"mesh_distance: bad dims {tuple(d)}")
-        out = torch.empty((int(d[2]), int(d[1]), int(d[0])), dtype=torch.float32, device="cuda")
-        _check(self._L.sph_mesh_distance(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(origin), _f3(sp), d,
-                                         C.c_void_p(out.data_ptr())))
-        self.sync()                                                      # (the tensor is handed to the caller's own stream)
-        return out
-
-    def volume_from_mesh(self, vertices, triangles, spacing: float, margin: float = 2.0):
-        """A volume around a mesh: a lattice of the given spacing about the mesh's bounding box widened by `margin` spacings on every side.
-        Returns (id, center, half): obstacle(SPH_OBSTACLE_BOX, center, half) + bind_obstacle_volume(index, id) is the whole recipe."""
-        v, t = _mesh_arrays(vertices, triangles)
-        if not len(v):
-            raise SphError("volume_from_mesh: no vertices")
-        h = np.float32(spacing)
-        lo, hi = v.min(axis=0).astype(np.float64), v.max(axis=0).astype(np.float64)
-        dims = [max(2, int(math.ceil((hi[a] - lo[a]) / float(h) + 2.0 * margin)) + 1) for a in range(3)]
-        center = (0.5 * (lo + hi)).astype(np.float32)
-        vid = C.c_int(-1)
-        _check(self._L.sph_volume_from_mesh(self._h, v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(center), _f3((h, h, h)),
-                                            (C.c_int * 3)(*dims), C.byref(vid)))
-        return int(vid.value), center, self.volume_info(vid.value)[2]
-
-    def statistics(self, histograms=None) -> Statistics:
-        """Counts, extrema, fp64 sums, cell occupancy and up to 4 histograms ((field, bins, lo, hi) with field one of SPH_STAT_*) of the
-        current state, reduced on the GPU (DESIGN.md section 3c).  Synchronises."""
-        specs, n, words = _histogram_specs(histograms)
-        out = SphStatistics()
-        hist = np.zeros(words, np.uint64)
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_statistics(self._h, C.byref(out), specs, n, hist.ctypes.data_as(C.c_void_p) if n else None))
-        hs, at = [], 0
-        for i in range(n):
-            hs.append(hist[at:at + specs[i].bins + 2].copy())
-            at += specs[i].bins + 2
-        return Statistics(out, hs, self._p)
-
-    def statistics_device(self, dev_out: int, histograms=None, dev_hist: int = 0):
-        """The same into device memory: an 832-byte SphStatistics at dev_out and sum(bins + 2) uint64 at dev_hist (torch tensors'
-        data_ptr(), say).  Asynchronous on the engine's stream."""
-        specs, n, _ = _histogram_specs(histograms)
-        _check(self._L.sph_set_params(self._h, C.byref(self._p)))
-        _check(self._L.sph_statistics_device(self._h, C.c_void_p(dev_out), specs, n, C.c_void_p(dev_hist) if dev_hist else None))
-
-    def sync(self):
-        _check(self._L.sph_sync(self._h))
-
-    def kernel_times(self, reset: bool = False):
-        ms = (C.c_double * len(KERNEL_CLASSES))()
-        cnt = (C.c_int64 * len(KERNEL_CLASSES))()
-        _check(self._L.sph_kernel_times(self._h, ms, cnt, 1 if reset else 0))
-        return {k: (ms[i], cnt[i]) for i, k in enumerate(KERNEL_CLASSES)}
-
-    def debug_counters(self, reset: bool = False) -> dict:
-        buf = (C.c_uint64 * len(STAMP_NAMES))()
-        _check(self._L.sph_debug_counters(self._h, buf, len(STAMP_NAMES), 1 if reset else 0))
-        return {k: int(buf[i]) for i, k in enumerate(STAMP_NAMES)}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._L.sph_destroy(self._h)
-            object.__setattr__(self, "_h", C.c_void_p())
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def obstacles_apply_host(obstacles, particle_mass: float, particles: np.ndarray):
     """sph_obstacles_apply_host on a copy of the records: (records, impulses (K, 6)).  No device is needed."""
     arr = obstacle_array(obstacles)
     rec = np.ascontiguousarray(particles, PARTICLE_DTYPE).copy()
     imp = np.zeros((max(len(arr), 1), 6), np.float64)
     L = load_library()
-    _check(L.sph_obstacles_apply_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(particle_mass),
-                                      rec.ctypes.data_as(C.c_void_p), len(rec), imp.ctypes.data_as(C.c_void_p)))
+    _check(L.sph_obstacles_apply_host(_ptr_or_none(arr), len(arr), float(particle_mass), _ptr(rec), len(rec), _ptr(imp)))
     return rec, imp[:len(arr)]
 
 
 def obstacles_advance_host(obstacles, dt: float) -> np.ndarray:
     """sph_obstacles_advance_host on a copy: the bodies one substep of dt later.  No device is needed."""
     arr = obstacle_array(obstacles).copy()
-    _check(load_library().sph_obstacles_advance_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), float(dt)))
+    _check(load_library().sph_obstacles_advance_host(_ptr_or_none(arr), len(arr), float(dt)))
     return arr
-
-
-def obstacles_step_host(obstacles, records, impulses, params, dt: float) -> np.ndarray:
-    """sph_obstacles_step_host on a copy: the bodies after the body step of one substep (DESIGN.md section 3g).  records: one
-    dynamics() record or None per body; impulses: the substep's (K, 6) sums or None.  No device is needed."""
-    arr = obstacle_array(obstacles).copy()
-    dyn = dynamics_array(records)
-    if len(dyn) != len(arr):
-        raise SphError(f"{len(dyn)} dynamics records for {len(arr)} obstacles")
-    imp = None if impulses is None else np.ascontiguousarray(impulses, np.float64).reshape(len(arr), 6)
-    _check(load_library().sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, dyn.ctypes.data_as(C.c_void_p) if len(arr) else None,
-                                                  len(arr), imp.ctypes.data_as(C.c_void_p) if imp is not None and len(arr) else None,
-                                                  C.byref(params), float(dt)))
-    return arr
-
-
-def volume_moments_host(values, spacing) -> np.ndarray:
-    """sph_volume_moments_host of a (nz, ny, nx) lattice: the ten moments.  No device is needed."""
-    v, dims, sp = _volume_lattice(values, spacing)
-    out = np.zeros(10, np.float64)
-    _check(load_library().sph_volume_moments_host(v.ctypes.data_as(C.c_void_p), dims, _f3(sp), out.ctypes.data_as(C.c_void_p)))
-    return out
 
 
 def volume_sample_host(values, spacing, local):
     """sph_volume_sample_host at one local point of a (nz, ny, nx) lattice: (phi, gradient[3], inside).  No device is needed."""
     v, dims, sp = _volume_lattice(values, spacing)
     phi, inside, g = C.c_float(), C.c_int(), (C.c_float * 3)()
-    _check(load_library().sph_volume_sample_host(v.ctypes.data_as(C.c_void_p), dims, _f3(sp), _f3(local), C.byref(phi), g, C.byref(inside)))
+    _check(load_library().sph_volume_sample_host(_ptr(v), dims, _f3(sp), _f3(local), C.byref(phi), g, C.byref(inside)))
     return np.float32(phi.value), np.array(g, np.float32), bool(inside.value)
 
 
@@ -1315,20 +1308,37 @@ def obstacles_apply_host_volumes(obstacles, volumes, bindings, particle_mass: fl
     bind = np.ascontiguousarray(bindings, np.int32)
     if len(bind) != len(arr):
         raise SphError(f"{len(bind)} bindings for {len(arr)} obstacles")
-    _check(load_library().sph_obstacles_apply_host_volumes(arr.ctypes.data_as(C.c_void_p) if len(arr) else None, len(arr), C.byref(vols), len(volumes),
-                                                           bind.ctypes.data_as(C.c_void_p) if len(bind) else None, float(particle_mass),
-                                                           rec.ctypes.data_as(C.c_void_p), len(rec), imp.ctypes.data_as(C.c_void_p)))
+    _check(load_library().sph_obstacles_apply_host_volumes(_ptr_or_none(arr), len(arr), C.byref(vols), len(volumes),
+                                                           _ptr_or_none(bind), float(particle_mass), _ptr(rec), len(rec), _ptr(imp)))
     return rec, imp[:len(arr)]
 
 
 def mesh_distance_host(vertices, triangles, origin, spacing, dims) -> np.ndarray:
     """sph_mesh_distance_host: the signed distances as a float32 array of shape (nz, ny, nx).  No device is needed (plain loops: small cases)."""
     v, t = _mesh_arrays(vertices, triangles)
-    d = (C.c_int * 3)(*[int(x) for x in dims])
-    sp = np.broadcast_to(np.asarray(spacing, np.float32), (3,)).copy()
-    if min(d) < 1 or int(d[0]) * int(d[1]) * int(d[2]) > 2 ** 31 - 1:
-        raise SphError(f"mesh_distance_host: bad dims {tuple(d)}")
+    d = _dims3(dims, "mesh_distance_host")
+    sp = _spacing3(spacing)
     out = np.empty((int(d[2]), int(d[1]), int(d[0])), np.float32)
-    _check(load_library().sph_mesh_distance_host(v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t), _f3(origin), _f3(sp), d,
-                                                 out.ctypes.data_as(C.c_void_p)))
+    _check(load_library().sph_mesh_distance_host(_ptr(v), len(v), _ptr(t), len(t), _f3(origin), _f3(sp), d, _ptr(out)))
+    return out
+
+
+def obstacles_step_host(obstacles, records, impulses, params, dt: float) -> np.ndarray:
+    """sph_obstacles_step_host on a copy: the bodies after the body step of one substep (DESIGN.md section 3g).  records: one
+    dynamics() record or None per body; impulses: the substep's (K, 6) sums or None.  No device is needed."""
+    arr = obstacle_array(obstacles).copy()
+    dyn = dynamics_array(records)
+    if len(dyn) != len(arr):
+        raise SphError(f"{len(dyn)} dynamics records for {len(arr)} obstacles")
+    imp = None if impulses is None else np.ascontiguousarray(impulses, np.float64).reshape(len(arr), 6)
+    _check(load_library().sph_obstacles_step_host(_ptr_or_none(arr), _ptr_or_none(dyn), len(arr), None if imp is None else _ptr_or_none(imp),
+                                                  C.byref(params), float(dt)))
+    return arr
+
+
+def volume_moments_host(values, spacing) -> np.ndarray:
+    """sph_volume_moments_host of a (nz, ny, nx) lattice: the ten moments.  No device is needed."""
+    v, dims, sp = _volume_lattice(values, spacing)
+    out = np.zeros(10, np.float64)
+    _check(load_library().sph_volume_moments_host(_ptr(v), dims, _f3(sp), _ptr(out)))
     return out

@@ -64,11 +64,15 @@ class HipSlabEngine:
         rec = np.ascontiguousarray(particles, dtype=_eng.PARTICLE_DTYPE)
         idv = np.ascontiguousarray(ids, dtype=np.uint32)
         assert len(rec) == len(idv)
-        _eng._check(self._L.sph_create_slab(C.byref(self._h), rec.ctypes.data_as(C.c_void_p), idv.ctypes.data_as(C.c_void_p), len(rec),
+        _eng._check(self._L.sph_create_slab(C.byref(self._h), _eng._ptr(rec), _eng._ptr(idv), len(rec),
                                             C.byref(params), z0, z1, int(has_lo), int(has_hi), int(capacity), stream))
         self.capacity = int(capacity)
 
     device = "cuda"
+
+    def push_params(self):
+        """The members into the engine (sph_set_params): what exchange(), step_begin() and dispatch() do first."""
+        _eng._check(self._L.sph_set_params(self._h, C.byref(self._p)))
 
     def pack(self, send_lo, send_hi):
         counts = (C.c_uint32 * 2)()
@@ -103,12 +107,12 @@ class HipSlabEngine:
     def exchange(self, comm: "RcclComm"):
         """pack -> grouped ncclSend/ncclRecv with the z-neighbours -> unpack, on the engine's stream (sph_slab_exchange).  The engine gets the
         members first, as dispatch() and step_begin() do: the exchange cuts its records for the grid the NEXT dispatch will use."""
-        _eng._check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        self.push_params()
         _eng._check(self._L.sph_slab_exchange(self._h, comm._h))
 
     # -- boundary-first substep: the exchange of the next substep beside the interior of the SPH pass ----------
     def step_begin(self, dt=-1.0):
-        _eng._check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        self.push_params()
         _eng._check(self._L.sph_slab_step_begin(self._h, dt))
 
     def step_finish(self, comm: "RcclComm"):
@@ -164,7 +168,7 @@ class HipSlabEngine:
         return [float(x) for x in out]
 
     def dispatch(self, dt=-1.0):
-        _eng._check(self._L.sph_set_params(self._h, C.byref(self._p)))
+        self.push_params()
         _eng._check(self._L.sph_dispatch(self._h, dt))
 
     def apply_wave_impulse(self, amplitude, wavelength, phase, direction, y_min, y_max):
@@ -182,7 +186,7 @@ class HipSlabEngine:
     def download_owned(self) -> np.ndarray:
         out = np.zeros(self.capacity, OUT_DTYPE)
         n = C.c_size_t()
-        _eng._check(self._L.sph_slab_download(self._h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        _eng._check(self._L.sph_slab_download(self._h, _eng._ptr(out), len(out), C.byref(n)))
         return out[: n.value].copy()
 
     def close(self):
@@ -381,7 +385,7 @@ class SlabSimulation:
                 key = _grid_key(self.engine._p)
                 if not getattr(self, "_primed", False) or key != getattr(self, "_grid_key", None):
                     if not self.engine._p.param_pause:
-                        _eng._check(self.engine._L.sph_set_params(self.engine._h, C.byref(self.engine._p)))
+                        self.engine.push_params()
                         self.engine.exchange(self.exchange)
                         self._primed = True
                         self._grid_key = key
@@ -486,7 +490,7 @@ class SlabGroup:
             paused = bool(self.sims[0].engine._p.param_pause)
             if (not self._primed or key != getattr(self, "_grid_key", None)) and not paused:
                 for s in self.sims:               # (a grid that moved between two steps: the halo records in place were cut for the old one)
-                    _eng._check(s.engine._L.sph_set_params(s.engine._h, C.byref(s.engine._p)))
+                    s.engine.push_params()
                 self._exchange_async()
                 self._primed = True
                 self._grid_key = key

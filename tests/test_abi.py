@@ -10,10 +10,31 @@ import pytest
 from conftest import ROOT, to_oracle_params
 
 
-def _declared_functions():
+def _header():
     src = open(os.path.join(ROOT, "include", "sph_abi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sph_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared_functions():
+    return sorted(set(re.findall(r"\b(sph_[a-z0-9_]+)\s*\(", _header())))
+
+
+def _prototypes():
+    """[(name, return type, [parameter text, ...]), ...] of every function include/sph_abi.h declares, in its order."""
+    out = []
+    for ret, name, params in re.findall(r"\b(const\s+char\s*\*|int|void|size_t)\s+(sph_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header()):
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        out.append((name, re.sub(r"\s+", "", ret), params))
+    return out
+
+
+RETURN_TYPES = {"int": (C.c_int, C.c_int32), "void": (None,), "size_t": (C.c_size_t,), "constchar*": (C.c_char_p,)}
+SCALAR_TYPES = {"int": (C.c_int, C.c_int32), "float": (C.c_float,), "double": (C.c_double,), "size_t": (C.c_size_t,),
+                "uint32_t": (C.c_uint32,), "uint64_t": (C.c_uint64,)}
+
+
+def _is_pointer_type(t):
+    return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
 
 
 def test_exports_match_header(pkg):
@@ -23,6 +44,21 @@ def test_exports_match_header(pkg):
     for name in declared:
         assert hasattr(L, name), name
     assert L.sph_abi_version() == 4
+    # every prototype of the header against the restype / argtypes the binding gives the function: no declaration may be skipped
+    protos = _prototypes()
+    assert [p[0] for p in protos] == list(pkg.ABI_SYMBOLS), "the parser must find every declaration, in the header's order"
+    assert len(protos) == len(pkg.ABI_SYMBOLS) == len(declared)
+    for name, ret, params in protos:
+        fn = getattr(L, name)
+        assert fn.restype in RETURN_TYPES[ret], f"{name}: restype {fn.restype} for '{ret}'"
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), f"{name}: {len(fn.argtypes or ())} argtypes for {len(params)} parameters"
+        for i, (text, t) in enumerate(zip(params, fn.argtypes)):
+            if "*" in text or "[" in text:
+                assert _is_pointer_type(t), f"{name}: parameter {i} '{text}' is a pointer, argtypes has {t}"
+            else:
+                kind = text.split()[-2] if len(text.split()) > 1 else text
+                assert kind in SCALAR_TYPES, f"{name}: parameter {i} '{text}' has a type the check does not know"
+                assert t in SCALAR_TYPES[kind], f"{name}: parameter {i} '{text}' is a {kind}, argtypes has {t}"
 
 
 def test_struct_layouts(pkg):
