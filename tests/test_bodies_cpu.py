@@ -14,7 +14,6 @@ import ctypes as C
 import math
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,16 +23,13 @@ import body_ref as B
 import body_scenes as S
 import obstacle_ref as R
 import volume_ref as VR
+from support import build_example, c_layout, check_shim_syntax, same_bits
 
 F = np.float32
 U = 2.0 ** -24
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 BODY_SYMBOLS = ("sph_obstacle_dynamics_default", "sph_obstacles_set_dynamics", "sph_obstacles_get_dynamics", "sph_obstacles_step_host",
                 "sph_volume_moments", "sph_volume_moments_host")
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), f"{what}:\n{a}\nvs\n{b}"
 
 
 def _rotated_params(pkg, **kw):
@@ -78,36 +74,19 @@ def test_library_exports_the_dynamics_interface(pkg):
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
 def test_dynamics_mirror_matches_the_header(pkg, tmp_path):
     """sizeof and every offsetof of SphObstacleDynamics (and sizeof SphObstacle), printed by C99 compiled against the header."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sph_abi.h"', 'int main(void) {',
-             '    printf("sizeof %zu %zu\\n", sizeof(SphObstacleDynamics), sizeof(SphObstacle));']
-    for fname, _ in pkg.SphObstacleDynamics._fields_:
-        lines.append(f'    printf("{fname} %zu\\n", offsetof(SphObstacleDynamics, {fname}));')
-    lines.append('    printf("flag %u\\n", SPH_DYNAMICS_CONFINED);')
-    lines += ['    return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True, capture_output=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert out[0] == "sizeof 80 76"
-    for ln, (fname, _) in zip(out[1:-1], pkg.SphObstacleDynamics._fields_):
-        name, val = ln.split()
-        assert name == fname and int(val) == getattr(pkg.SphObstacleDynamics, fname).offset == pkg.DYNAMICS_DTYPE.fields[fname][1], ln
-    assert len(out) == len(pkg.SphObstacleDynamics._fields_) + 2 and out[-1] == f"flag {pkg.SPH_DYNAMICS_CONFINED}"
+    size, offsets, extra = c_layout("SphObstacleDynamics", pkg.SphObstacleDynamics, [
+        'printf("SphObstacle %zu\\n", sizeof(SphObstacle));', 'printf("flag %u\\n", SPH_DYNAMICS_CONFINED);'], tmp_path)
+    assert size == 80
+    assert len(offsets) == len(pkg.SphObstacleDynamics._fields_)
+    for (name, val), (fname, _) in zip(offsets, pkg.SphObstacleDynamics._fields_):
+        assert name == fname and val == getattr(pkg.SphObstacleDynamics, fname).offset == pkg.DYNAMICS_DTYPE.fields[fname][1], (name, val)
+    assert extra == ["SphObstacle 76", f"flag {pkg.SPH_DYNAMICS_CONFINED}"]
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_floating_bodies_compiles_and_links_against_the_c_abi(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.join(ROOT, PKG_NAME)
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-x", "c++", "-fsyntax-only",
-                    os.path.join(ROOT, "include", "SPHFluidGPU_hip.hpp")], check=True, capture_output=True)
-    exe = str(tmp_path / "floating_bodies")
-    res = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "floating_bodies.cpp"),
-                          "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    assert os.path.exists(exe)
+    check_shim_syntax()
+    assert os.path.exists(build_example(pkg, "floating_bodies", tmp_path, werror=True))
 
 
 # ---- 2. the host step against the restatement -------------------------------------------------------
@@ -147,14 +126,14 @@ def test_host_step_matches_the_restatement(pkg):
         darr = pkg.dynamics_array(recs)
         infos = []
         want = R.to_array(B.step_all(R.bodies(arr, normalise=False), [B.record(x) for x in darr], imp, W, dt, infos))
-        _same_bits(got, want, f"bodies {i0}..{i0 + 7}")
+        same_bits(got, want, f"bodies {i0}..{i0 + 7}")
         for info in infos:
             seen[len(info["faces"])] = seen.get(len(info["faces"]), 0) + 1
     print(f"bodies by the number of faces they penetrate: {seen}")
     assert all(seen[k] >= 10 for k in (0, 1, 2, 3)), seen
     # null sums are zero sums
     arr = pkg.obstacle_array([c[0] for c in cases[:4]])
-    _same_bits(pkg.obstacles_step_host(arr, [c[1] for c in cases[:4]], None, sp, dt),
+    same_bits(pkg.obstacles_step_host(arr, [c[1] for c in cases[:4]], None, sp, dt),
                pkg.obstacles_step_host(arr, [c[1] for c in cases[:4]], np.zeros((4, 6)), sp, dt), "null sums")
 
 
@@ -173,7 +152,7 @@ def test_free_fall_without_fluid(pkg):
         ref[0]["v"] = np.array([F(1.0), vy, F(-2.0)], F)
         ref = R.advance(ref, dt)                                          # center follows obs_advance with the new velocity
         assert arr["vel"][0][1] == vy, (n, arr["vel"][0], vy)
-        _same_bits(arr, R.to_array(ref), f"free fall, step {n}")
+        same_bits(arr, R.to_array(ref), f"free fall, step {n}")
     assert vy < -30 * abs(float(push))
 
 
@@ -188,7 +167,7 @@ def test_a_body_nothing_acts_on_keeps_every_bit_of_its_pose(pkg):
     cur = arr
     for _ in range(25):
         cur = pkg.obstacles_step_host(cur, recs, np.zeros((3, 6)), sp, F(sp.param_timeStep))
-    _same_bits(cur, arr, "zero sums, no gravity, omega = 0")
+    same_bits(cur, arr, "zero sums, no gravity, omega = 0")
 
 
 @pytest.mark.parametrize("e", [0.0, 0.15, 0.5, 1.0])
@@ -202,7 +181,7 @@ def test_a_sphere_dropped_on_the_floor_leaves_with_minus_e_times_its_speed(pkg, 
     dt = F(sp.param_timeStep)
     got = pkg.obstacles_step_host(arr, [d], None, sp, dt)
     want = R.to_array(B.step_all(R.bodies(arr, normalise=False), [B.record(pkg.dynamics_array([d])[0])], None, S.world_of(pkg, sp), dt))
-    _same_bits(got, want, f"bounce, e = {e}")
+    same_bits(got, want, f"bounce, e = {e}")
     vy = float(got["vel"][0][1])
     print(f"e = {e}: V_y -3 -> {vy!r}")
     assert abs(vy - 3.0 * float(F(e))) <= 8 * U * (1 + e) * 3.0
@@ -446,14 +425,14 @@ def test_refusals_of_the_host_step(pkg):
         dyn = pkg.dynamics_array([good, d])
         rc = L.sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p), dyn.ctypes.data_as(C.c_void_p), 2, None, C.byref(sp), F(1e-3))
         assert rc == -1, what
-        _same_bits(arr, before, what + ": the bodies stay")
+        same_bits(arr, before, what + ": the bodies stay")
     dyn = pkg.dynamics_array([good, good])
     before = arr.copy()
     assert L.sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p), None, 2, None, C.byref(sp), F(1e-3)) == -1
     assert L.sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p), dyn.ctypes.data_as(C.c_void_p), 2, None, None, F(1e-3)) == -1
     assert L.sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p), dyn.ctypes.data_as(C.c_void_p), 17, None, C.byref(sp), F(1e-3)) == -1
     assert L.sph_obstacles_step_host(arr.ctypes.data_as(C.c_void_p), dyn.ctypes.data_as(C.c_void_p), 2, None, C.byref(sp), F(np.nan)) == -1
-    _same_bits(arr, before, "refused calls")
+    same_bits(arr, before, "refused calls")
     out = np.full(10, 7.0)
     v = np.zeros((3, 3, 3), F)
     d3, s3 = (C.c_int * 3)(3, 3, 3), (C.c_float * 3)(0.1, 0.1, 0.1)

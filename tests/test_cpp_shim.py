@@ -1,29 +1,17 @@
 """The header-only C++ twin of the reference class (include/SPHFluidGPU_hip.hpp)."""
 import os
 import shutil
-import subprocess
 
 import pytest
 
-from conftest import PKG_NAME, ROOT
-
-PKG_DIR = os.path.join(ROOT, PKG_NAME)
-EXE = os.path.join(ROOT, "examples", "headless_scene")
-
-
-def _build_example():
-    cmd = ["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "headless_scene.cpp"),
-           "-L", PKG_DIR, "-lsph_hip", "-Wl,-rpath," + PKG_DIR, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", EXE]
-    subprocess.run(cmd, check=True, capture_output=True)
+from conftest import ROOT
+from support import build_example, check_shim_syntax, run_example
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_shim_compiles_and_links_against_the_c_abi(pkg):
-    pkg.load_library()
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "include"), "-x", "c++",
-                    os.path.join(ROOT, "include", "SPHFluidGPU_hip.hpp")], check=True, capture_output=True)
-    _build_example()
-    assert os.path.exists(EXE)
+def test_shim_compiles_and_links_against_the_c_abi(pkg, tmp_path):
+    check_shim_syntax()
+    assert os.path.exists(build_example(pkg, "headless_scene", tmp_path))
     src = open(os.path.join(ROOT, "include", "SPHFluidGPU_hip.hpp")).read()
     for name in ("DispatchCompute", "ResetSimulation", "ApplyWaveImpulse", "EffectiveHalf", "ComputeGridExtents", "GetNumFluids",
                  "param_h", "param_mass", "param_restDensity", "param_gasConstant", "param_viscosity", "param_gravityY",
@@ -35,41 +23,22 @@ def test_shim_compiles_and_links_against_the_c_abi(pkg):
 
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_headless_scene_runs_on_the_gpu(pkg):
+def test_headless_scene_runs_on_the_gpu(pkg, tmp_path):
     """Scene0p's call pattern (ctor, per-frame impulse, 16-substep frames, param edits, reset)
     through the C++ shim."""
-    pkg.load_library()
-    _build_example()
-    env = dict(os.environ, LD_LIBRARY_PATH=PKG_DIR + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([EXE, "50000"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "headless_scene", tmp_path), ["50000"], timeout=300)
     assert res.returncode == 0 and "headless_scene OK" in res.stdout
 
 
-SLAB_EXE = os.path.join(ROOT, "examples", "slab_pair")
-
-
-def _build_slab_example():
-    cmd = ["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "slab_pair.cpp"),
-           "-L", PKG_DIR, "-lsph_hip", "-Wl,-rpath," + PKG_DIR, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", SLAB_EXE]
-    subprocess.run(cmd, check=True, capture_output=True)
-
-
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_slab_example_links_against_the_c_abi(pkg):
-    pkg.load_library()
-    _build_slab_example()
-    assert os.path.exists(SLAB_EXE)
+def test_slab_example_links_against_the_c_abi(pkg, tmp_path):
+    assert os.path.exists(build_example(pkg, "slab_pair", tmp_path))
 
 
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_slab_pair_through_the_c_abi_only(pkg):
+def test_slab_pair_through_the_c_abi_only(pkg, tmp_path):
     """A C++ host drives two z-slab engines through include/sph_abi.h alone (device-side counts, no host round trip in
     the exchange) and gets the single-engine result bit for bit."""
-    pkg.load_library()
-    _build_slab_example()
-    env = dict(os.environ, LD_LIBRARY_PATH=PKG_DIR + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([SLAB_EXE, "60000", "24"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "slab_pair", tmp_path), ["60000", "24"], timeout=300)
     assert res.returncode == 0 and "slab_pair OK" in res.stdout

@@ -7,16 +7,16 @@ last-bit difference in a sum legitimately changes them; they are compared by wha
 those of tests/test_bodies_cpu.py, where they are derived."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, assert_records_equal, small_scene, to_oracle_params
+from conftest import assert_records_equal, small_scene, to_oracle_params
 import body_ref as B
 import body_scenes as S
 import obstacle_ref as R
 import volume_ref as VR
+from support import build_example, engine, fluid_block, run_example, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -24,24 +24,10 @@ F = np.float32
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _engine(pkg, rec, sp, kern=3, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_NEIGHBOR_KERNEL, kern)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    return f
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), f"{what}:\n{a}\nvs\n{b}"
-
-
 def _scene4096(pkg):
     rec = np.load(os.path.join(G, "scene4096.npz"))["after_10"]
     _, sp = small_scene(pkg, n=4096, grid=16, seed=7)
-    p = rec["pos"][rec["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = p.min(axis=0), p.max(axis=0)
-    return rec, sp, (0.5 * (lo + hi)).astype(F), float((hi - lo).max())
+    return (rec, sp, *fluid_block(rec))
 
 
 def _four_bodies(pkg, sp, c, E, confined=True):
@@ -86,7 +72,7 @@ def test_one_step_ahead(pkg, oracle):
     rv = [VR.volume(v, h) for v, h in vols]
     n_fluid = int((rec0["isGhost"] == 0).sum())
     for kern, aos in ((3, 1), (2, 0)):
-        f = _engine(pkg, rec0, sp, kern, aos)
+        f = engine(pkg, rec0, sp, kern, aos)
         _set_all(f, arr, dyn, vols, bindings)
         for i, d in enumerate(dyn):
             got = f.obstacle_dynamics(i)
@@ -103,7 +89,7 @@ def test_one_step_ahead(pkg, oracle):
             assert_records_equal(f.download(), want_rec, what)
             bound = R.impulse_bound(info)
             assert (np.abs(J - want_imp) <= bound).all(), f"{what}: |engine - reference| {np.abs(J - want_imp)} above {bound}"
-            _same_bits(f.obstacles(), R.to_array(B.step_all(bs, ds, J, W, dt)), f"{what}: poses and velocities")
+            same_bits(f.obstacles(), R.to_array(B.step_all(bs, ds, J, W, dt)), f"{what}: poses and velocities")
             touched += int(info["touched"].sum())
         print(f"pass {kern} aos {aos}: the reference touches {touched / 30:.1f} of {n_fluid} fluid particles per substep")
         assert touched >= 30 * 0.005 * n_fluid
@@ -116,7 +102,7 @@ def test_replay_equals_single_dispatches(pkg):
     rho = float(sp.param_restDensity)
     runs = []
     for mode in ("graph", "dispatch_n", "single"):
-        f = _engine(pkg, rec0, sp, 3, 1, 1 if mode == "graph" else 0)
+        f = engine(pkg, rec0, sp, 3, 1, 1 if mode == "graph" else 0)
         _set_all(f, arr, dyn, vols, bindings)
         seen = []
         for call in range(4):
@@ -142,16 +128,16 @@ def test_replay_equals_single_dispatches(pkg):
     for other, name in ((runs[0], "graph"), (runs[1], "dispatch_n")):
         for k, ((ra, oa, ja), (rb, ob, jb)) in enumerate(zip(other, runs[2])):
             assert_records_equal(ra, rb, f"{name}, call {k}: records")
-            _same_bits(oa, ob, f"{name}, call {k}: poses")
-            _same_bits(ja[0], jb[0], f"{name}, call {k}: accumulators")
+            same_bits(oa, ob, f"{name}, call {k}: poses")
+            same_bits(ja[0], jb[0], f"{name}, call {k}: accumulators")
             assert ja[1:] == jb[1:]
     # the changes took effect: another mass sinks, the kick is visible, the kinematic body keeps its velocity
-    plain = _engine(pkg, rec0, sp, 3, 1, 0)
+    plain = engine(pkg, rec0, sp, 3, 1, 0)
     _set_all(plain, arr, dyn, vols, bindings)
     plain.DispatchN(128)
     assert not np.array_equal(plain.obstacles()["center"][0], runs[2][1][1]["center"][0])
     plain.close()
-    _same_bits(runs[2][3][1]["vel"][1], runs[2][2][1]["vel"][1], "a body made kinematic keeps its velocity")
+    same_bits(runs[2][3][1]["vel"][1], runs[2][2][1]["vel"][1], "a body made kinematic keeps its velocity")
     assert all(np.isfinite(o[f]).all() for _, o, _ in runs[2] for f in ("center", "rotation", "vel", "omega"))
 
 
@@ -162,7 +148,7 @@ def test_momentum_ledger_on_the_device(pkg):
     rho = float(sp.param_restDensity)
     dyn[1] = pkg.dynamics_sphere(0.8 * rho, 0.14 * E, confined=False)
     dyn[2] = pkg.dynamics_capsule(2.0 * rho, (0.08 * E, 0.1 * E), confined=False)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     _set_all(f, arr, dyn, vols, bindings)
     dt = F(sp.param_timeStep)
     push = np.array([float(F(dt * F(x))) for x in (sp.param_gravityX, sp.param_gravityY, sp.param_gravityZ)])
@@ -182,7 +168,7 @@ def test_momentum_ledger_on_the_device(pkg):
         assert (res <= bound).all(), f"substep {k}: residual {res} above {bound}"
         worst = max(worst, float((res / bound).max()))
         pushed += int((J != 0).any(axis=1).sum())
-        _same_bits(new["vel"][3], cur["vel"][3], "the kinematic body keeps its velocity")
+        same_bits(new["vel"][3], cur["vel"][3], "the kinematic body keeps its velocity")
         cur = new
     print(f"largest residual / bound over 200 substeps: {worst:.3g}; body-substeps with a fluid impulse: {pushed} of 600")
     assert pushed >= 100
@@ -193,7 +179,7 @@ def test_floating_on_the_device(pkg, oracle):
     """The floating scene of tests/test_bodies_cpu.py::test_floating on the device, with the same assertions (derived there)."""
     rec0, sp, arr, dyn = S.floating_scene(pkg)
     dt = F(sp.param_timeStep)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     f.set_obstacles(arr)
     for i, d in enumerate(dyn):
         f.set_obstacle_dynamics(i, d)
@@ -240,7 +226,7 @@ def test_kinematic_behaviour_is_unchanged(pkg):
     arr["vel"][0] = (0.5, -0.2, 0.1)
     out = []
     for with_dynamics in (True, False):
-        f = _engine(pkg, rec0, sp, 3, 1, 1)
+        f = engine(pkg, rec0, sp, 3, 1, 1)
         f.set_obstacles(arr)
         if with_dynamics:
             for i in (0, 2):
@@ -252,8 +238,8 @@ def test_kinematic_behaviour_is_unchanged(pkg):
         out.append((f.download(), f.obstacles(), f.obstacle_impulses()))
         f.close()
     assert_records_equal(out[0][0], out[1][0], "records")
-    _same_bits(out[0][1], out[1][1], "poses")
-    _same_bits(out[0][2][0], out[1][2][0], "accumulators")
+    same_bits(out[0][1], out[1][1], "poses")
+    same_bits(out[0][2][0], out[1][2][0], "accumulators")
     assert out[0][2][1:] == out[1][2][1:]
 
 
@@ -261,7 +247,7 @@ def test_moments_on_the_device(pkg):
     """Against the host twin within the order bound 2 (n - 1) 2^-53 sum |t| cell, on lattices that split differently over the kernel's fixed
     grid: one below a single sweep of a block, one of a few blocks, one larger than the whole grid's first sweep (the grid-stride loop)."""
     rec0, sp = small_scene(pkg, n=4096, grid=16)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     for name, values, h in (("9^3", VR.sphere_lattice(0.1, 0.1, margin=3), 0.1), ("41^3", VR.sphere_lattice(0.85, 0.05), 0.05),
                             ("box 61 x 41 x 51", VR.box_lattice((0.5, 0.3, 0.4), 0.02, margin=5), 0.02), ("141^3", VR.sphere_lattice(0.67, 0.01), 0.01)):
         vid = f.create_volume(values, h)
@@ -270,7 +256,7 @@ def test_moments_on_the_device(pkg):
         host = pkg.volume_moments_host(values, h)
         want, bound = B.moments(values, h)
         print(f"{name}: {values.size} points, volume {got[0]:.6g}; max |device - host| / bound = {(np.abs(got - host) / np.maximum(bound, 1e-300)).max():.3g}")
-        _same_bits(got, again, f"{name}: two runs")
+        same_bits(got, again, f"{name}: two runs")
         assert (np.abs(got - host) <= bound).all() and (np.abs(got - want) <= bound).all(), f"{name}: {np.abs(got - host)} above {bound}"
         assert got[0] > 0
         mass, com, inertia = f.volume_mass_properties(vid, 2.0)
@@ -294,7 +280,7 @@ def test_refusals_and_state_changes(pkg):
     slab = halo.HipSlabEngine(rec0, np.arange(len(rec0), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec0) * 1.2) + 8192)
     assert L.sph_obstacles_set_dynamics(slab._h, 0, C.byref(dyn[0])) == -3 and b"slab" in L.sph_last_error()
     slab.close()
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     _set_all(f, arr, dyn, vols, bindings)
     good = dyn[0]
 
@@ -308,7 +294,7 @@ def test_refusals_and_state_changes(pkg):
                 setattr(d, k, v)
         return d
     f.DispatchN(2)
-    ref = _engine(pkg, rec0, sp)
+    ref = engine(pkg, rec0, sp)
     _set_all(ref, arr, dyn, vols, bindings)
     ref.DispatchN(2)
     for what, (idx, d) in {"mass 0": (0, bad(mass=0.0)), "negative mass": (0, bad(mass=-2.0)), "nan field": (0, bad(gravityScale=float("nan"))),
@@ -324,7 +310,7 @@ def test_refusals_and_state_changes(pkg):
         assert (got is None) == (d is None) and (d is None or bytes(got) == bytes(d)), f"a refused record replaced that of body {i}"
     f.DispatchN(3)
     ref.DispatchN(3)
-    _same_bits(f.obstacles(), ref.obstacles(), "refused records change nothing on the device")
+    same_bits(f.obstacles(), ref.obstacles(), "refused records change nothing on the device")
     # sph_reset keeps the records, param_pause moves nothing, a set clears the records
     f.ResetSimulation()
     assert f.obstacle_dynamics(0) is not None
@@ -334,25 +320,17 @@ def test_refusals_and_state_changes(pkg):
     assert not np.array_equal(before["vel"][0], after["vel"][0])          # still dynamic: gravity acts
     f.param_pause = 1
     f.DispatchN(4)
-    _same_bits(f.obstacles(), after, "pause")
+    same_bits(f.obstacles(), after, "pause")
     f.param_pause = 0
     f.set_obstacles(after)
     assert all(f.obstacle_dynamics(i) is None for i in range(4))
     f.DispatchCompute()
-    _same_bits(f.obstacles()["vel"], after["vel"], "a set clears the dynamics: every body is kinematic")
+    same_bits(f.obstacles()["vel"], after["vel"], "a set clears the dynamics: every body is kinematic")
     f.close()
     ref.close()
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_floating_bodies_example(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.join(ROOT, PKG_NAME)
-    exe = str(tmp_path / "floating_bodies")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "floating_bodies.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, "20", "50000"], capture_output=True, text=True, env=env, timeout=600)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "floating_bodies", tmp_path), ["20", "50000"], timeout=600)
     assert res.returncode == 0 and "floating_bodies OK" in res.stdout

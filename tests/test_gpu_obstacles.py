@@ -5,16 +5,15 @@ are exactly defined terms whose fp64 sum order is the engine's choice: the engin
 by at most 2 (n_terms - 1) 2^-53 sum |t_i| per component, the worst case of two sums of the same terms in different orders.
 Every parity substep must touch at least 0.5 % of the fluid particles on the reference side, with at least one particle on the u_n < 0
 branch, so a body that misses the fluid cannot pass."""
-import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, assert_records_equal, small_scene, to_oracle_params
+from conftest import assert_records_equal, small_scene, to_oracle_params
 import obstacle_ref as R
+from support import build_example, check_impulses, engine, fluid_block, run_example, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -23,17 +22,10 @@ SCENES = ((4096, 16), (32768, 32))
 MOTIONS = ("static", "moving", "spinning")
 
 
-def _block(rec):
-    """Centre and largest extent of the fluid block."""
-    p = rec["pos"][rec["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = p.min(axis=0), p.max(axis=0)
-    return (0.5 * (lo + hi)).astype(F), float((hi - lo).max())
-
-
 def _body(pkg, shape, motion, rec, dt, offset=(0.0, 0.0, 0.0)):
     """One body inside the fluid block: sized from the block's extent E, moving by at most 0.04 E over 8 substeps, or turning by
     about 0.2 rad over 8 substeps."""
-    c, E = _block(rec)
+    c, E = fluid_block(rec)
     c = (c + F(E) * np.asarray(offset, F)).astype(F)
     if shape == R.SPHERE:
         size, rot = (0.2 * E,), (1.0, 0.0, 0.0, 0.0)
@@ -50,18 +42,6 @@ def _body(pkg, shape, motion, rec, dt, offset=(0.0, 0.0, 0.0)):
     return pkg.obstacle(shape, c, size, rotation=rot, vel=vel, omega=omega)
 
 
-def _engine(pkg, rec, sp, kern=3, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_NEIGHBOR_KERNEL, kern)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    return f
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), f"{what}:\n{a}\nvs\n{b}"
-
-
 def _reference(oracle, rec, sp, arr, steps, fountain=None):
     """Per substep: (records, bodies as OBSTACLE_DTYPE, impulses, info) of oracle + restatement."""
     op = to_oracle_params(oracle, sp)
@@ -71,12 +51,6 @@ def _reference(oracle, rec, sp, arr, steps, fountain=None):
         rec, bs, imp, info = R.step(oracle, rec, op, bs, fountain=fountain)
         out.append((rec, R.to_array(bs), imp, info))
     return out
-
-
-def _check_impulses(got, want, info, what):
-    bound = R.impulse_bound(info)
-    err = np.abs(got - want)
-    assert (err <= bound).all(), f"{what}: |engine - reference| {err} above {bound}"
 
 
 def _cap(info, n_fluid, what):
@@ -101,15 +75,15 @@ def test_parity_with_oracle_and_reference(pkg, oracle, n, grid):
             for kern in (1, 2, 3):
                 for aos in (0, 1):
                     what = f"{n}: shape {shape} {motion} pass {kern} aos {aos}"
-                    f = _engine(pkg, rec0, sp, kern, aos)
+                    f = engine(pkg, rec0, sp, kern, aos)
                     f.set_obstacles(arr)
                     for k, (want_rec, want_bodies, want_imp, info) in enumerate(ref):
                         f.DispatchCompute()
                         assert_records_equal(f.download(), want_rec, f"{what} substep {k}")
-                        _same_bits(f.obstacles(), want_bodies, f"{what} substep {k}: poses")
+                        same_bits(f.obstacles(), want_bodies, f"{what} substep {k}: poses")
                         J, t, steps = f.obstacle_impulses(reset=True)
                         assert steps == 1 and t == np.float64(F(dt)), (steps, t)
-                        _check_impulses(J, want_imp, info, f"{what} substep {k}")
+                        check_impulses(J, want_imp, info, f"{what} substep {k}")
                     f.close()
 
 
@@ -122,7 +96,7 @@ def test_bodies_outside_the_container_change_nothing(pkg, oracle):
                               pkg.obstacle(R.CAPSULE, far + F(5), (1, 2), rotation=(0.5, 0.5, 0.5, 0.5))])
     bs = R.bodies(arr)
     for aos in (0, 1):
-        a, b = _engine(pkg, rec0, sp, 3, aos), _engine(pkg, rec0, sp, 3, aos)
+        a, b = engine(pkg, rec0, sp, 3, aos), engine(pkg, rec0, sp, 3, aos)
         a.set_obstacles(arr)
         for k in range(8):
             a.DispatchCompute()
@@ -131,7 +105,7 @@ def test_bodies_outside_the_container_change_nothing(pkg, oracle):
         bs_k = bs
         for _ in range(8):
             bs_k = R.advance(bs_k, dt)
-        _same_bits(a.obstacles(), R.to_array(bs_k), f"aos {aos}: poses")
+        same_bits(a.obstacles(), R.to_array(bs_k), f"aos {aos}: poses")
         J, t, steps = a.obstacle_impulses()
         assert steps == 8 and (J == 0).all() and not np.signbit(J).any()
         a.close()
@@ -139,7 +113,7 @@ def test_bodies_outside_the_container_change_nothing(pkg, oracle):
 
 
 def _impulse_series(pkg, rec, sp, arr, kern, aos, steps=8):
-    f = _engine(pkg, rec, sp, kern, aos)
+    f = engine(pkg, rec, sp, kern, aos)
     f.set_obstacles(arr)
     out = []
     for _ in range(steps):
@@ -161,7 +135,7 @@ def test_impulse_bits_do_not_depend_on_pass_aos_mode_or_run(pkg):
         for aos in (0, 1):
             for run in range(2 if (kern, aos) == (3, 1) else 1):
                 got, r = _impulse_series(pkg, rec0, sp, arr, kern, aos)
-                _same_bits(got, first, f"impulses, pass {kern} aos {aos} run {run}")
+                same_bits(got, first, f"impulses, pass {kern} aos {aos} run {run}")
                 assert_records_equal(r, recs, f"pass {kern} aos {aos}")
 
 
@@ -173,7 +147,7 @@ def test_graph_replay_sees_set_motion(pkg):
                ((-1.5, 0.0, 1.0), (0.0, -4.0, 1.0)), ((0.5, 0.5, 0.5), (1.0, 1.0, 1.0))]
     runs = []
     for graph in (1, 0):
-        f = _engine(pkg, rec0, sp, 3, 1, graph)
+        f = engine(pkg, rec0, sp, 3, 1, graph)
         f.set_obstacles(arr)
         seen = []
         for i, (v, w) in enumerate(motions):
@@ -189,8 +163,8 @@ def test_graph_replay_sees_set_motion(pkg):
             assert launches > 0
     for k, ((ra, oa, ja), (rb, ob, jb)) in enumerate(zip(*runs)):
         assert_records_equal(ra, rb, f"call {k}: records")
-        _same_bits(oa, ob, f"call {k}: poses")
-        _same_bits(ja[0], jb[0], f"call {k}: impulses")
+        same_bits(oa, ob, f"call {k}: poses")
+        same_bits(ja[0], jb[0], f"call {k}: impulses")
         assert ja[1:] == jb[1:]
     assert (runs[0][-1][1]["vel"][0] == F(0.5)).all() and runs[0][-1][1]["omega"][1][1] == F(-4.0)   # the last set_motion of each body
     assert not np.array_equal(runs[0][1][1]["center"], runs[0][2][1]["center"])
@@ -212,7 +186,7 @@ def test_refusals_resets_pause_and_fountain(pkg, oracle):
     # SPH_ERR_ARG keeps the previous set
     a = _body(pkg, R.BOX, "moving", rec0, dt)
     b = _body(pkg, R.CAPSULE, "spinning", rec0, dt)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     f.set_obstacles([a, b])
     before = f.obstacles()
     bad = pkg.obstacle(R.SPHERE, (0, 0, 0), -1.0)
@@ -220,7 +194,7 @@ def test_refusals_resets_pause_and_fountain(pkg, oracle):
                 [pkg.obstacle(R.SPHERE, (0, 0, 0), 1.0, restitution=2.0)], [pkg.obstacle(R.SPHERE, (0, float("nan"), 0), 1.0)]):
         with pytest.raises(pkg.SphError, match="-1"):
             f.set_obstacles(obs)
-        _same_bits(f.obstacles(), before, "a refused set keeps the previous one")
+        same_bits(f.obstacles(), before, "a refused set keeps the previous one")
     for idx in (-1, 2):
         with pytest.raises(pkg.SphError, match="-1"):
             f.set_obstacle_motion(idx, (0, 0, 0), (0, 0, 0))
@@ -248,15 +222,15 @@ def test_refusals_resets_pause_and_fountain(pkg, oracle):
     assert f.obstacle_impulses()[2] == 2
     f.ResetSimulation()
     assert f.obstacle_impulses()[1:] == (0.0, 0)
-    _same_bits(f.obstacles(), poses, "sph_reset keeps the set and the current poses")
+    same_bits(f.obstacles(), poses, "sph_reset keeps the set and the current poses")
     # param_pause: nothing moves, nothing accumulates
     f.DispatchN(2)
     r, o, i = f.download(), f.obstacles(), f.obstacle_impulses()
     f.param_pause = 1
     f.DispatchCompute()
     f.DispatchN(4)
-    _same_bits(f.download(), r, "pause: records")
-    _same_bits(f.obstacles(), o, "pause: poses")
+    same_bits(f.download(), r, "pause: records")
+    same_bits(f.obstacles(), o, "pause: poses")
     assert f.obstacle_impulses()[1:] == i[1:] and f.obstacle_impulses()[0].tobytes() == i[0].tobytes()
     f.param_pause = 0
     f.clear_obstacles()
@@ -264,7 +238,7 @@ def test_refusals_resets_pause_and_fountain(pkg, oracle):
     f.DispatchCompute()
     f.close()
     # fountain + obstacles against the oracle in the engine's order: SPH pass, container, obstacles, fountain recycle
-    e = _engine(pkg, rec0, sp, 3, 0)
+    e = engine(pkg, rec0, sp, 3, 0)
     e.fountainMode = 1
     e.fountainOffset = (0.0, -1.0, 0.0)
     e.fountainDrainPerSec = 200.0
@@ -279,18 +253,18 @@ def test_refusals_resets_pause_and_fountain(pkg, oracle):
     for k, (want_rec, want_bodies, want_imp, info) in enumerate(ref):
         e.DispatchCompute()
         assert_records_equal(e.download(), want_rec, f"fountain substep {k}")
-        _same_bits(e.obstacles(), want_bodies, f"fountain substep {k}: poses")
-        _check_impulses(e.obstacle_impulses(reset=True)[0], want_imp, info, f"fountain substep {k}")
+        same_bits(e.obstacles(), want_bodies, f"fountain substep {k}: poses")
+        check_impulses(e.obstacle_impulses(reset=True)[0], want_imp, info, f"fountain substep {k}")
     assert e.fountainSeed == 6
     e.close()
 
 
 def test_drag_opposes_the_motion_of_a_sphere(pkg):
     rec0, sp = small_scene(pkg, n=32768, grid=32)
-    c, E = _block(rec0)
+    c, E = fluid_block(rec0)
     dt = float(sp.param_timeStep)
     V = 0.05 * E / (16 * dt)                                             # 5 % of the block over the run: the sphere stays inside the fluid
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     f.DispatchN(4)                                                       # densities first
     f.set_obstacles([pkg.obstacle(R.SPHERE, c, 0.2 * E, vel=(V, 0.0, 0.0))])
     f.DispatchN(16)
@@ -302,15 +276,7 @@ def test_drag_opposes_the_motion_of_a_sphere(pkg):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_stirred_tank_torque_opposes_the_spin(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.join(ROOT, PKG_NAME)
-    exe = str(tmp_path / "stirred_tank")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "stirred_tank.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, "10", "50000", "4.0"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "stirred_tank", tmp_path), ["10", "50000", "4.0"], timeout=300)
     assert res.returncode == 0 and "stirred_tank OK" in res.stdout
     torques = [float(x) for x in re.findall(r"torque_y=(\S+)", res.stdout)]
     assert len(torques) == 10 and all(t * 4.0 < 0 for t in torques), torques

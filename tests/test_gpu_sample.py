@@ -11,36 +11,22 @@ reference's fraction is >= 0.05: both sums are then within ~2.5e-3 relative of f
 import ctypes as C
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import assert_records_equal, small_scene, to_oracle_params
+from conftest import ROOT, assert_records_equal, small_scene, to_oracle_params
 import sample_ref
+from support import build_example, identity_states, run_example, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 F = np.float32
 
 
-def _identity_states(pkg):
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=7)
-    yield "scene4096", np.load(os.path.join(G, "scene4096.npz"))["after_10"], sp
-    z = np.load(os.path.join(G, "cylinder2000.npz"))
-    sp = pkg.default_params(param_shapeType=2, param_boxHalf=(2.2, 1.6, 0.9), param_boxEulerDeg=(10.0, -25.0, 40.0),
-                            param_boxCenter=(0.2, -0.1, 0.3), param_mass=float(z["mass"]))
-    yield "cylinder2000", z["after"], sp
-    fx = np.load(os.path.join(G, "settled_pool.npz"))
-    yield "settled_pool", fx["settled"], pkg.default_params(param_mass=float(fx["mass"]))
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
-    yield "small_scene", rec, sp
-
-
 def test_density_at_the_particles_is_the_next_substeps_density(pkg, oracle):
-    for name, rec, sp in _identity_states(pkg):
+    for name, rec, sp in identity_states(pkg):
         op = to_oracle_params(oracle, sp)
         fluid = rec["isGhost"] == 0
         want_oracle = oracle.substep(rec, op)["density"]
@@ -184,51 +170,19 @@ def test_mass_of_the_density_field(pkg):
     assert abs(total / (len(rec) * float(sp.param_mass)) - 1.0) < 0.005
 
 
-def _run(pkg, rec, sp, sample, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    g = f.ComputeGridExtents()
+def test_sampling_does_not_change_the_simulation(pkg):
+    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
     h = sp.param_h
     pts = rec["pos"][::7, :3]
 
-    def probe():
-        if sample:
-            f.sample(pts)
-            f.sample_lattice(g.gridMin, (h / 2, h / 2, h / 2), (24, 24, 24), pkg.SPH_FIELD_ALL)
-            f.sample_lattice(g.gridMin, (h, h, h), (16, 16, 16), pkg.SPH_FIELD_DENSITY)
-    probe()
-    if graph:
-        for _ in range(4):
-            f.DispatchN(3)
-            probe()
-    else:
-        for _ in range(3):
-            f.DispatchCompute()
-            probe()
-        f.DispatchN(4)
-        probe()
-        f.ApplyWaveImpulse(1.5, 3.0, 0.25, (0.0, 1.0, 0.0))
-        probe()
-        f.DispatchN(3)
-    mid = f.download()
-    probe()
-    f.upload(mid)
-    probe()
-    after_upload = f.download()
-    probe()
-    f.DispatchN(2)
-    out = f.download()
-    launches = f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES)
-    f.close()
-    return after_upload, out, launches
-
-
-def test_sampling_does_not_change_the_simulation(pkg):
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
+    def probe(f):
+        g = f.ComputeGridExtents()
+        f.sample(pts)
+        f.sample_lattice(g.gridMin, (h / 2, h / 2, h / 2), (24, 24, 24), pkg.SPH_FIELD_ALL)
+        f.sample_lattice(g.gridMin, (h, h, h), (16, 16, 16), pkg.SPH_FIELD_DENSITY)
     for aos, graph in ((1, 0), (0, 0), (1, 1), (0, 1)):
-        a_up, a, la = _run(pkg, rec, sp, True, aos, graph)
-        b_up, b, lb = _run(pkg, rec, sp, False, aos, graph)
+        a_up, a, la = undisturbed_run(pkg, rec, sp, probe, aos, graph)
+        b_up, b, lb = undisturbed_run(pkg, rec, sp, None, aos, graph)
         assert_records_equal(a_up, b_up, f"upload / download, aos {aos} graph {graph}")
         assert_records_equal(a, b, f"aos {aos} graph {graph}")
         if graph:
@@ -343,15 +297,7 @@ def test_water_level_on_the_settled_pool(pkg):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_wave_gauge_example(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.dirname(pkg.build.LIB_PATH)
-    exe = str(tmp_path / "wave_gauge")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "wave_gauge.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, "50000", "12"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "wave_gauge", tmp_path), ["50000", "12"], timeout=300)
     assert res.returncode == 0 and "wave_gauge OK" in res.stdout
     frames = [ln for ln in res.stdout.splitlines() if ln.startswith("frame ")]
     assert len(frames) == 12

@@ -9,17 +9,16 @@ import ctypes as C
 import math
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import assert_records_equal, small_scene
+from conftest import ROOT, assert_records_equal, small_scene
 import stats_ref
+from support import build_example, run_example
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 F = np.float32
 SPECS = [(stats_ref.DENSITY, 256, 0.0, 8000.0), (stats_ref.SPEED, 1024, 0.0, 40.0), (stats_ref.POS_Y, 100, -2.5, 2.5), (stats_ref.FOAM, 1, 0.0, 1.0)]
@@ -348,21 +347,13 @@ def test_device_variant_equals_the_host_variant(pkg):
 # ---- 9. the C++ example -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_run_monitor_example(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.dirname(pkg.build.LIB_PATH)
-    exe = str(tmp_path / "run_monitor")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "run_monitor.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, "20", "50000"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    exe = build_example(pkg, "run_monitor", tmp_path)
+    res = run_example(exe, ["20", "50000"], timeout=300)
     assert res.returncode == 0 and "run_monitor OK" in res.stdout
     frames = [ln for ln in res.stdout.splitlines() if ln.startswith("frame ")]
     assert len(frames) == 20
     for ln in frames:
         vals = dict(tok.split("=") for tok in ln.split()[2:])
         assert int(vals["counted"]) == 50000 and all(np.isfinite(float(v)) for v in vals.values()), ln
-    res = subprocess.run([exe, "20", "50000", "1234"], capture_output=True, text=True, env=env, timeout=300)   # poisons id 1234 after frame 3
-    print(res.stdout, res.stderr)
+    res = run_example(exe, ["20", "50000", "1234"], timeout=300)          # poisons id 1234 after frame 3
     assert res.returncode != 0 and "id 1234" in res.stdout and "run_monitor OK" not in res.stdout

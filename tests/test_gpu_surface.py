@@ -4,17 +4,16 @@ simulation, repeatability, refusals, the C++ example and one full-size case."""
 import ctypes as C
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import assert_records_equal, small_scene
+from conftest import ROOT, assert_records_equal, small_scene
 import surface_ref as sr
+from support import build_example, run_example, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 F = np.float32
 
@@ -143,49 +142,16 @@ def test_settled_pool_default_lattice(pkg):
     assert abs(vol / want - 1.0) < 0.10
 
 
-def _run(pkg, rec, sp, extract, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    g = f.ComputeGridExtents()
-    h = sp.param_h
-
-    def probe():
-        if extract:
-            f.surface()
-            f.surface(g.gridMin, (h, h, h), (16, 16, 16), 500.0, pkg.SPH_FIELD_DENSITY)
-    probe()
-    if graph:
-        for _ in range(4):
-            f.DispatchN(3)
-            probe()
-    else:
-        for _ in range(3):
-            f.DispatchCompute()
-            probe()
-        f.DispatchN(4)
-        probe()
-        f.ApplyWaveImpulse(1.5, 3.0, 0.25, (0.0, 1.0, 0.0))
-        probe()
-        f.DispatchN(3)
-    mid = f.download()
-    probe()
-    f.upload(mid)
-    probe()
-    after_upload = f.download()
-    probe()
-    f.DispatchN(2)
-    out = f.download()
-    launches = f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES)
-    f.close()
-    return after_upload, out, launches
-
-
 def test_extraction_does_not_change_the_simulation(pkg):
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
+    h = sp.param_h
+
+    def probe(f):
+        f.surface()
+        f.surface(f.ComputeGridExtents().gridMin, (h, h, h), (16, 16, 16), 500.0, pkg.SPH_FIELD_DENSITY)
     for aos, graph in ((1, 0), (0, 0), (1, 1), (0, 1)):
-        a_up, a, la = _run(pkg, rec, sp, True, aos, graph)
-        b_up, b, lb = _run(pkg, rec, sp, False, aos, graph)
+        a_up, a, la = undisturbed_run(pkg, rec, sp, probe, aos, graph)
+        b_up, b, lb = undisturbed_run(pkg, rec, sp, None, aos, graph)
         assert_records_equal(a_up, b_up, f"upload / download, aos {aos} graph {graph}")
         assert_records_equal(a, b, f"aos {aos} graph {graph}")
         if graph:
@@ -316,17 +282,9 @@ def _parse_ply(path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_surface_mesh_example(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.dirname(pkg.build.LIB_PATH)
-    exe = str(tmp_path / "surface_mesh")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "surface_mesh.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
     out = tmp_path / "frames"
     out.mkdir()
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, str(out), "3"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "surface_mesh", tmp_path), [out, "3"], timeout=300)
     assert res.returncode == 0 and "surface_mesh OK" in res.stdout
     frames = [ln for ln in res.stdout.splitlines() if ln.startswith("frame ")]
     assert len(frames) == 3

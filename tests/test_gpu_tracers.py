@@ -7,14 +7,13 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, assert_records_equal, small_scene, to_oracle_params
 import tracer_ref as T
-from test_gpu_sample import _identity_states
+from support import build_example, engine, identity_states, run_example
 
 pytestmark = pytest.mark.gpu
 
@@ -47,14 +46,6 @@ def _seeds(pkg, rec, sp, rng, n_fluid=160, n_box=160, n_out=40):
     p4[:, 3] = rng.random(len(xyz)).astype(F)
     p4[-1, 3] = p4[-2, 3]                                                # (the duplicate pair: same point, same age)
     return p4, len(xyz) - 3, (len(xyz) - 2, len(xyz) - 1)               # index of the NaN tracer, indices of the duplicate pair
-
-
-def _engine(pkg, rec, sp, kern=3, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_NEIGHBOR_KERNEL, kern)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    return f
 
 
 def _host_step(f, tr, dt, integ, dispatch_dt=-1.0):
@@ -101,7 +92,7 @@ def _same(a, b, what):
 
 def test_tracers_equal_the_host_loop_and_the_reference(pkg, oracle):
     n = 10
-    for name, rec, sp in _identity_states(pkg):
+    for name, rec, sp in identity_states(pkg):
         op = to_oracle_params(oracle, sp)
         p4, i_nan, (d0, d1) = _seeds(pkg, rec, sp, np.random.default_rng(17))
         dt = F(sp.param_timeStep)
@@ -112,7 +103,7 @@ def test_tracers_equal_the_host_loop_and_the_reference(pkg, oracle):
             for kern in (1, 2, 3):
                 for aos in (0, 1):
                     what = f"{name} integrator {integ} pass {kern} aos {aos}"
-                    f = _engine(pkg, rec, sp, kern, aos)
+                    f = engine(pkg, rec, sp, kern, aos)
                     f.set_tracers(p4, integ)
                     assert f.num_tracers() == len(p4)
                     for _ in range(n):
@@ -120,11 +111,11 @@ def test_tracers_equal_the_host_loop_and_the_reference(pkg, oracle):
                     got, got_rec = f.tracers(), f.download()
                     assert f.tracer_info()[0] == n
                     f.close()
-                    h = _engine(pkg, rec, sp, kern, aos)
+                    h = engine(pkg, rec, sp, kern, aos)
                     loop = _host_loop(h, p4, n, dt, integ)
                     loop_rec = h.download()
                     h.close()
-                    p = _engine(pkg, rec, sp, kern, aos)                 # no tracers, no sampling
+                    p = engine(pkg, rec, sp, kern, aos)                  # no tracers, no sampling
                     for _ in range(n):
                         p.DispatchCompute()
                     plain_rec = p.download()
@@ -145,7 +136,7 @@ def test_first_substep_on_records_without_a_density_moves_nothing(pkg):
     rec["vel"][:, :3] = F(1.5)
     p4 = np.zeros((256, 4), F)
     p4[:, :3] = rec["pos"][::16, :3]
-    f = _engine(pkg, rec, sp)
+    f = engine(pkg, rec, sp)
     f.set_tracers(p4, T.MIDPOINT)
     f.DispatchCompute()
     a = f.tracers()
@@ -163,8 +154,8 @@ def test_graph_replay_equals_eager_dispatch(pkg):
     p4, _, _ = _seeds(pkg, rec, sp, np.random.default_rng(23))
     for integ in (T.EULER, T.MIDPOINT):
         for aos in (0, 1):
-            g = _engine(pkg, rec, sp, 3, aos, graph=1)
-            e = _engine(pkg, rec, sp, 3, aos, graph=0)
+            g = engine(pkg, rec, sp, 3, aos, graph=1)
+            e = engine(pkg, rec, sp, 3, aos, graph=0)
             for f in (g, e):
                 f.set_tracers(p4, integ, history=4, stride=3)
             for _ in range(5):
@@ -209,7 +200,7 @@ def test_history_ring(pkg):
     _, sp = small_scene(pkg, n=4096, grid=16, seed=7)
     p4, _, _ = _seeds(pkg, rec, sp, np.random.default_rng(29))
     n = 8
-    step = _engine(pkg, rec, sp)                                         # the stepwise run: a download after every substep
+    step = engine(pkg, rec, sp)                                          # the stepwise run: a download after every substep
     step.set_tracers(p4, T.MIDPOINT)
     snaps = [T.snapshot_of(step.tracers())]
     for _ in range(n):
@@ -218,7 +209,7 @@ def test_history_ring(pkg):
     step.close()
     assert snaps[0].tobytes() == p4.tobytes()                            # snapshot 0 is the seed
     for K, S in ((3, 1), (2, 3), (16, 1), (1, 1), (5, 3)):
-        f = _engine(pkg, rec, sp)
+        f = engine(pkg, rec, sp)
         f.set_tracers(p4, T.MIDPOINT, history=K, stride=S)
         first, hist = f.tracer_history()
         assert first == 0 and hist.shape == (1, len(p4), 4) and hist[0].tobytes() == p4.tobytes()
@@ -243,9 +234,9 @@ def test_order_independence_across_a_refresh_of_the_processing_order(pkg):
     p4, _, (d0, d1) = _seeds(pkg, rec, sp, rng, 600, 300, 60)
     perm = rng.permutation(len(p4))
     for integ in (T.EULER, T.MIDPOINT):
-        a = _engine(pkg, rec, sp)
+        a = engine(pkg, rec, sp)
         a.set_tracers(p4, integ, history=3, stride=R // 2)
-        b = _engine(pkg, rec, sp)
+        b = engine(pkg, rec, sp)
         b.set_tracers(p4[perm], integ, history=3, stride=R // 2)
         a.DispatchN(n)                                                   # one call ...
         for _ in range(n):                                               # ... and single dispatches
@@ -258,7 +249,7 @@ def test_order_independence_across_a_refresh_of_the_processing_order(pkg):
         _same(ta[perm], tb, f"permuted seeds, integrator {integ}")
         assert fa == fb and ha[:, perm].tobytes() == hb.tobytes()
         assert ta[d0].tobytes() == ta[d1].tobytes()
-        h = _engine(pkg, rec, sp)                                        # the host loop has no processing order at all
+        h = engine(pkg, rec, sp)                                         # the host loop has no processing order at all
         loop = _host_loop(h, p4, n, F(sp.param_timeStep), integ)
         h.close()
         _same(ta, loop, f"{n} substeps against the host loop, integrator {integ}")
@@ -270,7 +261,7 @@ def test_fountain_river_pause_and_override_dt(pkg, oracle):
     p4, _, _ = _seeds(pkg, rec, sp, np.random.default_rng(37))
     dt = F(sp.param_timeStep)
     # fountain mode: tracers see the entry state, before the recycle of the same dispatch
-    pair = [_engine(pkg, rec, sp), _engine(pkg, rec, sp)]
+    pair = [engine(pkg, rec, sp), engine(pkg, rec, sp)]
     for f in pair:
         f.fountainMode = 1
         f.fountainOffset = (0.0, -1.0, 0.0)
@@ -290,7 +281,7 @@ def test_fountain_river_pause_and_override_dt(pkg, oracle):
     P, rsp, _, river, _, heights = test_gpu_river._scene(pkg, oracle)
     P = oracle.substep_river(P, to_oracle_params(oracle, rsp), oracle.ORiver.from_buffer_copy(bytes(river)), heights, steps=2)   # densities
     r4, _, _ = _seeds(pkg, P, rsp, np.random.default_rng(41))
-    pair = [_engine(pkg, P, rsp), _engine(pkg, P, rsp)]
+    pair = [engine(pkg, P, rsp), engine(pkg, P, rsp)]
     for f in pair:
         f.set_river(river, heights)
     pair[0].set_tracers(r4, T.EULER)
@@ -304,7 +295,7 @@ def test_fountain_river_pause_and_override_dt(pkg, oracle):
     for f in pair:
         f.close()
     # param_pause: no substep, no move, no ageing, c unchanged
-    f = _engine(pkg, rec, sp)
+    f = engine(pkg, rec, sp)
     f.set_tracers(p4, T.MIDPOINT, history=4)
     f.DispatchN(3)
     a = f.tracers()
@@ -318,7 +309,7 @@ def test_fountain_river_pause_and_override_dt(pkg, oracle):
     f.close()
     # overrideDt: the step and the age use it
     odt = F(0.6) * dt
-    f, h = _engine(pkg, rec, sp), _engine(pkg, rec, sp)
+    f, h = engine(pkg, rec, sp), engine(pkg, rec, sp)
     f.set_tracers(p4, T.MIDPOINT)
     for _ in range(5):
         f.DispatchCompute(float(odt))
@@ -353,7 +344,7 @@ def test_refusals_and_lifetimes(pkg):
     assert L.sph_tracers_set(slab._h, ptr, m, 1, 0, 1) == -3 and b"slab" in L.sph_last_error()
     assert L.sph_tracers_count(slab._h) == 0
     slab.close()
-    f = _engine(pkg, rec, sp)
+    f = engine(pkg, rec, sp)
     h = f._h
     # SPH_OPT_GRID_BUILD 1: at set ...
     f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
@@ -401,7 +392,7 @@ def test_refusals_and_lifetimes(pkg):
     hip.hipMemcpy.argtypes = [vp, vp, C.c_size_t, C.c_int]
     assert hip.hipMemcpy(view.ctypes.data_as(vp), vp(f.tracers_device()), 32 * m, 2) == 0          # hipMemcpyDeviceToHost
     assert view.tobytes() == got.tobytes()
-    g2 = _engine(pkg, rec, sp)                                           # the host variant on a fresh engine with the same history of calls
+    g2 = engine(pkg, rec, sp)                                            # the host variant on a fresh engine with the same history of calls
     g2.DispatchCompute()
     g2.set_tracers(p4, T.EULER, history=2)
     g2.DispatchCompute()
@@ -438,7 +429,7 @@ def test_refusals_and_lifetimes(pkg):
     f.DispatchCompute()
     f.close()
     # N = 0 particles: nothing to carry the tracers
-    z = _engine(pkg, rec[:0], sp)
+    z = engine(pkg, rec[:0], sp)
     z.set_tracers(p4, T.MIDPOINT, history=2)
     z.DispatchN(3)
     t = z.tracers()
@@ -495,17 +486,9 @@ def _parse_pathlines(path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_pathlines_example(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.dirname(pkg.build.LIB_PATH)
-    exe = str(tmp_path / "pathlines")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "pathlines.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     ply = tmp_path / "pathlines.ply"
     frames = 4
-    res = subprocess.run([exe, str(ply), str(frames)], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout, res.stderr)
+    res = run_example(build_example(pkg, "pathlines", tmp_path), [ply, frames], timeout=300)
     assert res.returncode == 0 and "pathlines OK" in res.stdout
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("frame ")]
     assert len(lines) == frames

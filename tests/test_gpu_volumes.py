@@ -3,46 +3,21 @@
 sph_mesh_distance is compared byte for byte with its host twin and the numpy restatement tests/volume_ref.py; records and poses after
 substeps with bound bodies are compared bit for bit with the oracle's substep followed by the restatement, impulses within the bound of
 section 3e for a re-ordered fp64 sum (tests/obstacle_ref.py impulse_bound)."""
-import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, assert_records_equal, small_scene, to_oracle_params
+from conftest import assert_records_equal, small_scene, to_oracle_params
 import obstacle_ref as R
 import surface_ref as sr
 import volume_ref as VR
+from support import build_example, check_impulses, engine, fluid_block, run_example, same_bits
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-
-
-def _block(rec):
-    p = rec["pos"][rec["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = p.min(axis=0), p.max(axis=0)
-    return (0.5 * (lo + hi)).astype(F), float((hi - lo).max())
-
-
-def _engine(pkg, rec, sp, kern=3, aos=1, graph=0):
-    f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_NEIGHBOR_KERNEL, kern)
-    f.set_option(pkg.SPH_OPT_AOS_MODE, aos)
-    f.set_option(pkg.SPH_OPT_GRAPH, graph)
-    return f
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), f"{what}:\n{a}\nvs\n{b}"
-
-
-def _check_impulses(got, want, info, what):
-    bound = R.impulse_bound(info)
-    err = np.abs(got - want)
-    assert (err <= bound).all(), f"{what}: |engine - reference| {err} above {bound}"
 
 
 def mesh_fixtures():
@@ -62,7 +37,7 @@ def mesh_fixtures():
 
 def _scene_bodies(pkg, rec, dt):
     """Volumes and bodies sized from the fluid block: a sphere lattice and a box lattice with a flat core."""
-    c, E = _block(rec)
+    c, E = fluid_block(rec)
     Rs = 0.2 * E
     hs = Rs / 6.0
     sphere = VR.sphere_lattice(Rs, hs)
@@ -113,24 +88,24 @@ def _bind_all(f, vols, bindings):
 
 def test_mesh_distance_equals_the_host_twin_and_the_restatement(pkg):
     rec0, sp = small_scene(pkg, n=4096, grid=16)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     for name, v, t, origin, h, dims in mesh_fixtures():
         want, w = VR.mesh_distance(v, t, origin, h, dims)
         dev = np.abs(w - np.round(w)).max()
         print(f"{name}: {len(t)} triangles, {want.size} points, max |w - round(w)| = {dev:.3g}, {int((want < 0).sum())} inside")
         assert dev < 0.01 and (want < 0).any() and (want > 0).any()
         host = pkg.mesh_distance_host(v, t, origin, h, dims)
-        _same_bits(host, want, f"{name}: host twin against the restatement")
+        same_bits(host, want, f"{name}: host twin against the restatement")
         for split in (0, 1, 2, 5):
             f.set_option(pkg.SPH_OPT_MESH_SPLIT, split)
             got = f.mesh_distance(v, t, origin, h, dims).cpu().numpy()
-            _same_bits(got, want, f"{name}: split {split}")
+            same_bits(got, want, f"{name}: split {split}")
     f.close()
 
 
 def test_mesh_distance_large_case_does_not_depend_on_the_split(pkg):
     rec0, sp = small_scene(pkg, n=4096, grid=16)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     RADIUS = 0.27                                                       # about six spacings: the near-surface set stays a few thousand points
     v, t = VR.icosphere(5, RADIUS)
     assert len(t) == 20480
@@ -140,8 +115,8 @@ def test_mesh_distance_large_case_does_not_depend_on_the_split(pkg):
     for split in (3, 16, 0):
         f.set_option(pkg.SPH_OPT_MESH_SPLIT, split)
         outs.append(f.mesh_distance(v, t, origin, h, (n, n, n)).cpu().numpy())
-    _same_bits(outs[0], outs[1], "split 3 against split 16")
-    _same_bits(outs[0], outs[2], "split 3 against the engine's choice")
+    same_bits(outs[0], outs[1], "split 3 against split 16")
+    same_bits(outs[0], outs[2], "split 3 against the engine's choice")
     got = outs[0]
     pts = VR.lattice_points(origin, h, (n, n, n)).astype(np.float64)
     r = np.linalg.norm(pts, axis=1)
@@ -168,7 +143,7 @@ def test_mesh_distance_large_case_does_not_depend_on_the_split(pkg):
 def test_round_trip_through_the_mesher(pkg):
     import torch
     rec0, sp = small_scene(pkg, n=4096, grid=16)
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     name, v, t, origin, h, dims = mesh_fixtures()[0]
     phi = f.mesh_distance(v, t, origin, h, dims)
     mv, mt = f.surface_from_volume((-phi).contiguous(), origin, (h, h, h), None, 0.0)
@@ -198,16 +173,16 @@ def test_parity_with_oracle_and_reference(pkg, oracle, n, grid):
         print(f"{n} {name}: reference touches {[int(i['touched'].sum()) for _, _, _, i in ref]} of {n_fluid}")
         for kern, aos in ((3, 1), (3, 0), (2, 1), (1, 0)) if n > 4096 else [(k, a) for k in (1, 2, 3) for a in (0, 1)]:
             what = f"{n}: {name} pass {kern} aos {aos}"
-            f = _engine(pkg, rec0, sp, kern, aos)
+            f = engine(pkg, rec0, sp, kern, aos)
             f.set_obstacles(arr)
             _bind_all(f, vols, bindings)
             for k, (want_rec, want_bodies, want_imp, info) in enumerate(ref):
                 f.DispatchCompute()
                 assert_records_equal(f.download(), want_rec, f"{what} substep {k}")
-                _same_bits(f.obstacles(), want_bodies, f"{what} substep {k}: poses")
+                same_bits(f.obstacles(), want_bodies, f"{what} substep {k}: poses")
                 J, t, s = f.obstacle_impulses(reset=True)
                 assert s == 1
-                _check_impulses(J, want_imp, info, f"{what} substep {k}")
+                check_impulses(J, want_imp, info, f"{what} substep {k}")
             f.close()
 
 
@@ -220,7 +195,7 @@ def test_graph_replay_sees_bind_and_set_motion(pkg):
     motions = [((1.0, 0.0, 0.0), (0.0, 2.0, 0.0)), ((0.0, -2.0, 0.5), (3.0, 0.0, 0.0)), ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)), ((-1.5, 0.0, 1.0), (0.0, -4.0, 1.0))]
     runs = []
     for graph in (1, 0):
-        f = _engine(pkg, rec0, sp, 3, 1, graph)
+        f = engine(pkg, rec0, sp, 3, 1, graph)
         f.set_obstacles(arr)
         ids = [f.create_volume(*sph), f.create_volume(*box)]
         f.bind_obstacle_volume(0, ids[0])
@@ -243,8 +218,8 @@ def test_graph_replay_sees_bind_and_set_motion(pkg):
             assert launches > 0
     for k, ((ra, oa, ja), (rb, ob, jb)) in enumerate(zip(*runs)):
         assert_records_equal(ra, rb, f"call {k}: records")
-        _same_bits(oa, ob, f"call {k}: poses")
-        _same_bits(ja[0], jb[0], f"call {k}: impulses")
+        same_bits(oa, ob, f"call {k}: poses")
+        same_bits(ja[0], jb[0], f"call {k}: impulses")
         assert ja[1:] == jb[1:]
     # a bind changes the result: the same calls without the second bind differ
     assert (runs[0][-1][2][0] != 0).any()
@@ -266,7 +241,7 @@ def test_sphere_lattice_against_the_analytic_sphere(pkg, oracle):
     rel_cpu = np.linalg.norm(Jv - Js) / np.linalg.norm(Js)
     out = []
     for arr, bind in ((body_v, True), (body_s, False)):
-        f = _engine(pkg, rec0, sp)
+        f = engine(pkg, rec0, sp)
         f.set_obstacles(arr)
         if bind:
             f.bind_obstacle_volume(0, f.create_volume(*sph))
@@ -287,7 +262,7 @@ def test_without_a_binding_nothing_changes(pkg):
                               pkg.obstacle(R.SPHERE, c + F(0.25 * E), 0.1 * E)])
     runs = []
     for mode in ("plain", "unbound", "bound"):
-        f = _engine(pkg, rec0, sp)
+        f = engine(pkg, rec0, sp)
         f.set_option(pkg.SPH_OPT_TIMING, 1)
         f.set_obstacles(arr)
         if mode != "plain":
@@ -303,8 +278,8 @@ def test_without_a_binding_nothing_changes(pkg):
         runs.append((f.download(), f.obstacles(), f.obstacle_impulses()[0], {k: v[1] for k, v in f.kernel_times().items()}))
         f.close()
     assert_records_equal(runs[0][0], runs[1][0], "unbound against plain")
-    _same_bits(runs[0][1], runs[1][1], "poses")
-    _same_bits(runs[0][2], runs[1][2], "impulses")
+    same_bits(runs[0][1], runs[1][1], "poses")
+    same_bits(runs[0][2], runs[1][2], "impulses")
     assert runs[0][3] == runs[1][3], (runs[0][3], runs[1][3])
     assert runs[0][3] == runs[2][3], "a bound body launches as many kernels per class"
     assert runs[2][0].tobytes() != runs[0][0].tobytes()
@@ -327,7 +302,7 @@ def test_refusals_on_the_device_path(pkg):
     assert L.sph_volume_create(slab._h, vals.ctypes.data_as(C.c_void_p), dims, sp3, 0, C.byref(vid)) == -3 and b"slab" in L.sph_last_error()
     assert L.sph_obstacles_bind_volume(slab._h, 0, 0) == -3 and vid.value == -7
     slab.close()
-    f = _engine(pkg, rec0, sp)
+    f = engine(pkg, rec0, sp)
     f.set_obstacles([pkg.obstacle(R.BOX, c, _half(sph)), pkg.obstacle(R.SPHERE, c, 0.1 * E)])
     a = f.create_volume(*sph)
     f.bind_obstacle_volume(0, a)
@@ -365,14 +340,6 @@ def test_refusals_on_the_device_path(pkg):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_mesh_obstacle_example_keeps_the_fluid_outside(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.join(ROOT, PKG_NAME)
-    exe = str(tmp_path / "mesh_obstacle")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "mesh_obstacle.cpp"),
-                    "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                   check=True, capture_output=True)
-    env = dict(os.environ, LD_LIBRARY_PATH=pkg_dir + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    res = subprocess.run([exe, "200"], capture_output=True, text=True, env=env, timeout=300)
-    print(res.stdout[-3000:], res.stderr[-2000:])
+    res = run_example(build_example(pkg, "mesh_obstacle", tmp_path), ["200"], timeout=300)
     assert res.returncode == 0 and "mesh_obstacle OK" in res.stdout
     assert len(re.findall(r"torque=", res.stdout)) >= 10

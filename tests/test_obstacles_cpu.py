@@ -12,13 +12,13 @@ Bounds used below and where they come from:
 import ctypes as C
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import PKG_NAME, ROOT
 import obstacle_ref as R
+from support import build_example, c_layout, check_impulses, check_shim_syntax, records, same_bits
 
 F = np.float32
 U = 2.0 ** -24
@@ -46,29 +46,6 @@ def _bodies(pkg, rng, shapes, centers, scale=1.0, spin=True):
     return pkg.obstacle_array(out)
 
 
-def _records(pkg, pos, vel, ghost=None):
-    rec = np.zeros(len(pos), pkg.PARTICLE_DTYPE)
-    rec["pos"][:, :3] = pos
-    rec["pos"][:, 3] = 1.0
-    rec["vel"][:, :3] = vel
-    rec["density"] = 1000.0
-    if ghost is not None:
-        rec["isGhost"] = ghost
-    return rec
-
-
-def _same_bits(a, b, what):
-    x, y = np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)
-    assert a.shape == b.shape and np.array_equal(x, y), what
-
-
-def _check_impulses(got, want, info, what):
-    bound = R.impulse_bound(info)
-    err = np.abs(got - want)
-    print(f"{what}: touched {info['touched'].tolist()} u_n<0 {info['negative'].tolist()} max err {err.max():.3g} max bound {bound.max():.3g}")
-    assert (err <= bound).all(), f"{what}: {err} > {bound}"
-
-
 def test_library_exports_the_obstacle_interface(pkg):
     L = pkg.load_library()
     for name in OBSTACLE_SYMBOLS:
@@ -90,37 +67,19 @@ def test_library_exports_the_obstacle_interface(pkg):
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
 def test_ctypes_mirror_matches_the_header(pkg, tmp_path):
     """sizeof and every offsetof of SphObstacle, printed by C99 compiled against the header."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sph_abi.h"', 'int main(void) {',
-             '    printf("sizeof %zu\\n", sizeof(SphObstacle));']
-    for fname, _ in pkg.SphObstacle._fields_:
-        lines.append(f'    printf("{fname} %zu\\n", offsetof(SphObstacle, {fname}));')
-    lines.append('    printf("enum %d %d %d %d\\n", SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE, SPH_MAX_OBSTACLES);')
-    lines += ['    return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True, capture_output=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert out[0] == "sizeof 76"
-    for ln, (fname, _) in zip(out[1:-1], pkg.SphObstacle._fields_):
-        name, val = ln.split()
-        assert name == fname and int(val) == getattr(pkg.SphObstacle, fname).offset == pkg.OBSTACLE_DTYPE.fields[fname][1], ln
-    assert len(out) == len(pkg.SphObstacle._fields_) + 2
-    assert out[-1].split()[1:] == ["0", "1", "2", "16"]
+    size, offsets, extra = c_layout("SphObstacle", pkg.SphObstacle, [
+        'printf("enum %d %d %d %d\\n", SPH_OBSTACLE_SPHERE, SPH_OBSTACLE_BOX, SPH_OBSTACLE_CAPSULE, SPH_MAX_OBSTACLES);'], tmp_path)
+    assert size == 76
+    assert len(offsets) == len(pkg.SphObstacle._fields_)
+    for (name, val), (fname, _) in zip(offsets, pkg.SphObstacle._fields_):
+        assert name == fname and val == getattr(pkg.SphObstacle, fname).offset == pkg.OBSTACLE_DTYPE.fields[fname][1], (name, val)
+    assert len(extra) == 1 and extra[0].split() == ["enum", "0", "1", "2", "16"]
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_stirred_tank_compiles_and_links_against_the_c_abi(pkg, tmp_path):
-    pkg.load_library()
-    pkg_dir = os.path.join(ROOT, PKG_NAME)
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-x", "c++", "-fsyntax-only",
-                    os.path.join(ROOT, "include", "SPHFluidGPU_hip.hpp")], check=True, capture_output=True)
-    exe = str(tmp_path / "stirred_tank")
-    res = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "stirred_tank.cpp"),
-                          "-L", pkg_dir, "-lsph_hip", "-Wl,-rpath," + pkg_dir, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    assert os.path.exists(exe)
+    check_shim_syntax()
+    assert os.path.exists(build_example(pkg, "stirred_tank", tmp_path, werror=True))
 
 
 def _degenerate_cases(pkg):
@@ -158,18 +117,18 @@ def _degenerate_cases(pkg):
 
 def test_degenerate_cases_follow_the_contract(pkg):
     bodies, pos, vel, ghost, exp = _degenerate_cases(pkg)
-    rec = _records(pkg, pos, vel, ghost)
+    rec = records(pkg, pos, vel, ghost)
     got, imp = pkg.obstacles_apply_host(bodies, 0.02, rec)
     want, want_imp, info = R.apply(R.bodies(bodies, normalise=False), F(0.02), rec)
-    _same_bits(got, want, "host vs reference")
+    same_bits(got, want, "host vs reference")
     for i, p, v in exp:
         if p is not None:
             assert np.array_equal(got["pos"][i, :3], p), (i, got["pos"][i, :3], p)
         if v == "keep":
-            _same_bits(got[i:i + 1], rec[i:i + 1], f"record {i} must keep its bits")
+            same_bits(got[i:i + 1], rec[i:i + 1], f"record {i} must keep its bits")
     assert (got["vel"][3] == rec["vel"][3]).all() and not np.array_equal(got["pos"][3], rec["pos"][3])   # u_n >= 0: projected, velocity kept
     assert got["vel"][0, 1] > rec["vel"][0, 1]                                            # the u_n < 0 branch
-    _check_impulses(imp, want_imp, info, "degenerate cases")
+    check_impulses(imp, want_imp, info, "degenerate cases")
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -183,13 +142,13 @@ def test_host_apply_matches_the_reference(pkg, seed):
     vel = (rng.standard_normal((n, 3)) * 2).astype(F)
     ghost = (rng.random(n) < 0.03).astype(np.int32)
     pos[rng.choice(n, 20, replace=False), rng.integers(0, 3, 20)] = np.nan
-    rec = _records(pkg, pos, vel, ghost)
+    rec = records(pkg, pos, vel, ghost)
     mass = F(rng.uniform(0.01, 2))
     got, imp = pkg.obstacles_apply_host(bodies, mass, rec)
     want, want_imp, info = R.apply(R.bodies(bodies, normalise=False), mass, rec)
-    _same_bits(got, want, f"seed {seed}: host vs reference")
+    same_bits(got, want, f"seed {seed}: host vs reference")
     assert (info["touched"] > 50).all() and (info["negative"] > 10).all() and (info["touched"] > info["negative"]).all(), info["touched"]
-    _check_impulses(imp, want_imp, info, f"seed {seed}")
+    check_impulses(imp, want_imp, info, f"seed {seed}")
     # particles that no body touches keep their bits
     moved = (got.view(np.uint8).reshape(n, 80) != rec.view(np.uint8).reshape(n, 80)).any(axis=1)
     touched = np.zeros(n, bool)
@@ -226,7 +185,7 @@ def test_no_particle_is_inside_after_one_application(pkg):
     n = 40000
     pos = np.concatenate([centers[i] + rng.uniform(-1.2, 1.2, (n // 6, 3)) for i in range(6)]).astype(F)
     vel = rng.standard_normal(pos.shape).astype(F)
-    rec = _records(pkg, pos, vel)
+    rec = records(pkg, pos, vel)
     got, _ = pkg.obstacles_apply_host(bodies, F(0.1), rec)
     bs = R.bodies(bodies, normalise=False)
     p = got["pos"][:, :3]
@@ -254,10 +213,10 @@ def test_host_advance_matches_the_reference(pkg):
         cur = pkg.obstacles_advance_host(cur, dt)
         bs = R.advance(bs, dt)
         want = R.to_array(bs)
-        _same_bits(cur, want, f"advance {k}")
-    _same_bits(cur["rotation"][1], arr["rotation"][1], "omega = 0 keeps the rotation bits")
-    _same_bits(cur["rotation"][2], arr["rotation"][2], "omega = -0 keeps the rotation bits")
-    _same_bits(cur["center"][2], arr["center"][2], "V = 0 keeps the centre bits")
+        same_bits(cur, want, f"advance {k}")
+    same_bits(cur["rotation"][1], arr["rotation"][1], "omega = 0 keeps the rotation bits")
+    same_bits(cur["rotation"][2], arr["rotation"][2], "omega = -0 keeps the rotation bits")
+    same_bits(cur["center"][2], arr["center"][2], "V = 0 keeps the centre bits")
     assert not np.array_equal(cur["rotation"][0], arr["rotation"][0])
     q = cur["rotation"].astype(np.float64)
     assert np.abs((q * q).sum(axis=1) - 1).max() < 8 * U
@@ -266,7 +225,7 @@ def test_host_advance_matches_the_reference(pkg):
 def test_refusals_of_the_host_entry_points(pkg):
     L = pkg.load_library()
     good = pkg.obstacle(R.BOX, (0, 0, 0), (1, 1, 1))
-    rec = _records(pkg, np.zeros((4, 3), F), np.zeros((4, 3), F))
+    rec = records(pkg, np.zeros((4, 3), F), np.zeros((4, 3), F))
     cases = []
     for field, val in (("shape", 3), ("shape", -1)):
         o = pkg.obstacle(R.BOX, (0, 0, 0), (1, 1, 1))
@@ -285,7 +244,7 @@ def test_refusals_of_the_host_entry_points(pkg):
         before = rec.copy()
         assert L.sph_obstacles_apply_host(arr.ctypes.data_as(C.c_void_p), 2, 1.0, rec.ctypes.data_as(C.c_void_p), len(rec), None) == -1
         assert L.sph_obstacles_advance_host(arr.ctypes.data_as(C.c_void_p), 2, 1e-3) == -1
-        _same_bits(rec, before, "a refused call writes nothing")
+        same_bits(rec, before, "a refused call writes nothing")
     # sizes a shape does not use are not checked for positivity; 17 bodies are too many
     sph = pkg.obstacle(R.SPHERE, (0, 0, 0), 1.0)
     arr = pkg.obstacle_array([sph])

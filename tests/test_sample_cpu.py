@@ -3,15 +3,14 @@ the CPU oracle, the calibration of the bounds tests/test_gpu_sample.py relies on
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import small_scene, to_oracle_params
+from conftest import ROOT, small_scene, to_oracle_params
 import sample_ref
+from support import check_shim_syntax
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 HEADER = os.path.join(ROOT, "include", "sph_abi.h")
 
@@ -149,4 +148,4 @@ def test_cpp_twin_compiles_with_sampling(tmp_path):
                    '    const int dims[3] = {4, 4, 4};\n'
                    '    return f.SamplePoints(pts, out) && f.SampleLattice(MATH::Vec3(0, 0, 0), MATH::Vec3(0.1f, 0.1f, 0.1f), dims, SPH_FIELD_ALL, dev);\n'
                    '}\n')
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "include"), str(src)], check=True)
+    check_shim_syntax(src)

@@ -12,13 +12,13 @@ import math
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, small_scene
 import stats_ref
+from support import c_layout
 
 G = os.path.join(ROOT, "tests", "golden")
 F = np.float32
@@ -214,29 +214,21 @@ def test_histogram_edge_cases():
 def test_ctypes_mirror_matches_the_header(pkg, tmp_path):
     """sizeof and every offsetof of SphStatistics / SphStatExtremum / SphHistogramSpec, printed by C99 compiled against the header."""
     structs = {"SphStatistics": pkg.SphStatistics, "SphStatExtremum": pkg.SphStatExtremum, "SphHistogramSpec": pkg.SphHistogramSpec}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sph_abi.h"', 'int main(void) {']
-    for sname, st in structs.items():
-        lines.append(f'    printf("{sname} sizeof %zu\\n", sizeof({sname}));')
-        for fname, _ in st._fields_:
-            lines.append(f'    printf("{sname} {fname} %zu\\n", offsetof({sname}, {fname}));')
-    lines.append('    printf("enum %d %d %d %d %d %d %d %d %d\\n", SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y,'
-                 ' SPH_STAT_POS_Z, SPH_STAT_FOAM, SPH_STAT_MAX_SPECS, SPH_STAT_MAX_BINS);')
-    lines += ['    return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True, capture_output=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    enum = ('printf("enum %d %d %d %d %d %d %d %d %d\\n", SPH_STAT_DENSITY, SPH_STAT_PRESSURE, SPH_STAT_SPEED, SPH_STAT_POS_X, SPH_STAT_POS_Y,'
+            ' SPH_STAT_POS_Z, SPH_STAT_FOAM, SPH_STAT_MAX_SPECS, SPH_STAT_MAX_BINS);')
     seen = 0
-    for ln in out[:-1]:
-        sname, fname, val = ln.split()
-        st = structs[sname]
-        assert int(val) == (C.sizeof(st) if fname == "sizeof" else getattr(st, fname).offset), ln
-        seen += 1
+    for sname, st in structs.items():
+        size, offsets, extra = c_layout(sname, st, [enum], tmp_path)
+        assert size == C.sizeof(st), sname
+        assert [f for f, _ in offsets] == [f for f, _ in st._fields_], sname
+        for fname, val in offsets:
+            assert val == getattr(st, fname).offset, (sname, fname, val)
+        seen += 1 + len(offsets)
+        assert len(extra) == 1
     assert seen == sum(len(st._fields_) + 1 for st in structs.values())
     assert C.sizeof(pkg.SphStatistics) == 832 and C.sizeof(pkg.SphStatistics) % 8 == 0 and C.alignment(pkg.SphStatistics) == 8
     assert C.sizeof(pkg.SphHistogramSpec) == 16
-    assert out[-1].split()[1:] == [str(v) for v in (pkg.SPH_STAT_DENSITY, pkg.SPH_STAT_PRESSURE, pkg.SPH_STAT_SPEED, pkg.SPH_STAT_POS_X, pkg.SPH_STAT_POS_Y,
+    assert extra[0].split()[1:] == [str(v) for v in (pkg.SPH_STAT_DENSITY, pkg.SPH_STAT_PRESSURE, pkg.SPH_STAT_SPEED, pkg.SPH_STAT_POS_X, pkg.SPH_STAT_POS_Y,
                                                      pkg.SPH_STAT_POS_Z, pkg.SPH_STAT_FOAM, pkg.SPH_STAT_MAX_SPECS, pkg.SPH_STAT_MAX_BINS)]
     assert (stats_ref.DENSITY, stats_ref.PRESSURE, stats_ref.SPEED, stats_ref.POS_X, stats_ref.POS_Y, stats_ref.POS_Z, stats_ref.FOAM) == tuple(range(7))
     # the header names every member the mirror has, in the same order

@@ -22,34 +22,12 @@ import numpy as np
 import obstacle_ref as R
 import surface_ref as sr
 import volume_ref as VR
+from support import check_impulses, records, same_bits
 
 F = np.float32
 U = 2.0 ** -24
 VOLUME_SYMBOLS = ("sph_volume_create", "sph_volume_destroy", "sph_volume_info", "sph_volume_sample_host", "sph_volume_from_mesh",
                   "sph_obstacles_bind_volume", "sph_obstacles_volume", "sph_obstacles_apply_host_volumes", "sph_mesh_distance", "sph_mesh_distance_host")
-
-
-def _same_bits(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.tobytes() == b.tobytes(), what
-
-
-def _records(pkg, pos, vel, ghost=None):
-    rec = np.zeros(len(pos), pkg.PARTICLE_DTYPE)
-    rec["pos"][:, :3] = pos
-    rec["pos"][:, 3] = 1.0
-    rec["vel"][:, :3] = vel
-    rec["density"] = 1000.0
-    if ghost is not None:
-        rec["isGhost"] = ghost
-    return rec
-
-
-def _check_impulses(got, want, info, what):
-    bound = R.impulse_bound(info)
-    err = np.abs(got - want)
-    print(f"{what}: touched {info['touched'].tolist()} u_n<0 {info['negative'].tolist()} max err {err.max():.3g} max bound {bound.max():.3g}")
-    assert (err <= bound).all(), f"{what}: {err} > {bound}"
 
 
 def _sample_all(pkg, values, spacing, pts):
@@ -90,7 +68,7 @@ def test_sample_equals_the_restatement(pkg):
         want = VR.sample_host_result(vol, allp)
         got = _sample_all(pkg, values, spacing, allp)
         for g, w, name in zip(got, want, ("phi", "gradient", "inside")):
-            _same_bits(g, w, f"{shape}: {name}")
+            same_bits(g, w, f"{shape}: {name}")
         assert want[2].any() and (~np.isnan(want[0])).sum() > 300 and np.isnan(want[0]).sum() > 50
         # NaN corners: every compare is false
         holed = values.copy()
@@ -99,7 +77,7 @@ def test_sample_equals_the_restatement(pkg):
         want = VR.sample_host_result(vh, pts)
         got = _sample_all(pkg, holed, spacing, pts)
         for g, w, name in zip(got, want, ("phi", "gradient", "inside")):
-            _same_bits(g, w, f"{shape} with a NaN corner: {name}")
+            same_bits(g, w, f"{shape} with a NaN corner: {name}")
         assert np.isnan(want[0][want[1][:, 0] != want[1][:, 0]]).all() and not want[2][np.isnan(want[0])].any()
 
 
@@ -128,7 +106,7 @@ def _lattice_scene(pkg, rng, bodies, n=6000, spread=1.6):
     vel = (rng.standard_normal((n, 3)) * 2.0).astype(F)
     ghost = (rng.uniform(size=n) < 0.05).astype(np.int32)
     pos[:5, 0] = np.nan
-    return _records(pkg, pos, vel, ghost)
+    return records(pkg, pos, vel, ghost)
 
 
 def test_apply_equals_the_restatement(pkg):
@@ -152,14 +130,14 @@ def test_apply_equals_the_restatement(pkg):
         bs = R.bodies(arr, normalise=False)
         want, imp, info = VR.apply(bs, [VR.volume(*v) for v in vols], bindings, F(0.02), rec)
         got, J = pkg.obstacles_apply_host_volumes(arr, vols, bindings, 0.02, rec)
-        _same_bits(got, want, f"{name}: records")
-        _check_impulses(J, imp, info, name)
+        same_bits(got, want, f"{name}: records")
+        check_impulses(J, imp, info, name)
         assert info["touched"].min() >= 50 and info["negative"].min() >= 10, (name, info["touched"], info["negative"])
         plain, Jp = pkg.obstacles_apply_host(arr, 0.02, rec)
         assert plain.tobytes() != got.tobytes(), f"{name}: the volume changes nothing"
         none, Jn = pkg.obstacles_apply_host_volumes(arr, vols, [-1] * len(arr), 0.02, rec)
-        _same_bits(none, plain, f"{name}: without bindings")
-        _same_bits(Jn, Jp, f"{name}: impulses without bindings")
+        same_bits(none, plain, f"{name}: without bindings")
+        same_bits(Jn, Jp, f"{name}: impulses without bindings")
     # the flat core of the box lattice sends particles to the box's own faces: the fallback must have been taken
     vol = VR.volume(*box)
     how, _, _ = VR.project(vol, (rng.uniform(-0.3, 0.3, (2000, 3))).astype(F))
@@ -173,7 +151,7 @@ def test_projection_residual_and_agreement_with_the_analytic_sphere(pkg):
     vol = VR.volume(values, h)
     rng = np.random.default_rng(11)
     pos = rng.uniform(-10.0, 10.0, (200000, 3)).astype(F)
-    rec = _records(pkg, pos, np.zeros_like(pos))
+    rec = records(pkg, pos, np.zeros_like(pos))
     body_v = R.bodies(pkg.obstacle_array([pkg.obstacle(R.BOX, (0, 0, 0), vol["half"])]), normalise=False)
     body_s = R.bodies(pkg.obstacle_array([pkg.obstacle(R.SPHERE, (0, 0, 0), Rs)]), normalise=False)
     out_v, _, info_v = VR.apply(body_v, [vol], [0], F(0.02), rec)
@@ -221,7 +199,7 @@ def test_mesh_distance_equals_the_restatement(pkg):
         print(f"{name}: {len(t)} triangles, {want.size} points, max |w - round(w)| = {dev:.3g}, {int((want < 0).sum())} inside")
         assert dev < 0.01, f"{name}: a lattice point lies on the surface"
         got = pkg.mesh_distance_host(v, t, origin, h, dims)
-        _same_bits(got, want, name)                                      # every point
+        same_bits(got, want, name)                                       # every point
         assert (want < 0).sum() > 100 and (want > 0).sum() > 100
         assert np.array_equal(want < 0, (np.round(w) == 1).reshape(want.shape))
         pts = VR.lattice_points(origin, h, dims)
@@ -271,7 +249,7 @@ def test_refusals_write_nothing(pkg):
     half = VR.volume(values, 0.25)["half"]
     rng = np.random.default_rng(2)
     box = pkg.obstacle(R.BOX, (0, 0, 0), half)
-    rec = _records(pkg, rng.uniform(-1.5, 1.5, (500, 3)).astype(F), rng.standard_normal((500, 3)).astype(F))
+    rec = records(pkg, rng.uniform(-1.5, 1.5, (500, 3)).astype(F), rng.standard_normal((500, 3)).astype(F))
     ok, _ = pkg.obstacles_apply_host_volumes([box], [(values, 0.25)], [0], 0.02, rec)
     assert ok.tobytes() != rec.tobytes()
     arr = pkg.obstacle_array([box])

@@ -13,11 +13,12 @@ obstacle pass and its finish), 25 substeps after 3 warm-ups, median [p10, p90].
                 kinematic and dynamic sets and one moments call) are copied into the result: the one-block finish kernels are too short
                 for the bracket to tell apart.
   python tools/time_bodies.py [out.json] [--parent-tree DIR] [--trace CSV]
+Without an out.json the result goes to time_bodies.json in the current directory; profiles/r11_time_bodies.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
 import csv
-import importlib
 import json
 import os
 import subprocess
@@ -25,48 +26,23 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ROOT = os.environ.get("SPH_TREE", HERE)                                  # the tree the package is imported from (child processes)
-sys.path.insert(0, ROOT)
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
+import timing
+from timing import HERE, REPS, ROOT, pkg, stats                         # ROOT: the tree SPH_TREE names (child processes), else HERE
 
 F = np.float32
-REPS = 25
 ROUNDS = 3
 COPY_BYTES_PER_S = 6.29e12
 KERNELS = ("k_obstacles_finish_dyn", "k_obstacles_finish", "k_obstacles", "k_volume_moments_finish", "k_volume_moments")
 
 
-def stats(us):
-    us = np.asarray(us, np.float64)
-    return {"median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()),
-            "p10_us": float(np.percentile(us, 10)), "p90_us": float(np.percentile(us, 90)), "calls": int(len(us))}
-
-
 def bodies(state, dt, K=4):
-    fluid = state["pos"][state["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = fluid.min(axis=0), fluid.max(axis=0)
-    cell = (hi - lo) / 2
-    r = 0.3 * float(cell.min())
+    centres, r = timing.body_grid(state, K)
     out = []
-    for k in range(K):
-        c = lo + cell * (np.array([k % 2, (k // 2) % 2, 0]) + 0.5)
+    for k, c in enumerate(centres):
         shape = k % 3
         size = (r,) if shape == 0 else ((r, 0.8 * r, 0.6 * r) if shape == 1 else (0.6 * r, 0.7 * r))
         out.append(pkg.obstacle(shape, c, size, rotation=(0.9, 0.1, 0.3, 0.2), vel=(0.02 * r / dt, 0.0, 0.0), omega=(0.0, 0.5 / (16 * dt), 0.1 / (16 * dt))))
     return out, r
-
-
-def other_us(f):
-    ms, launches = f.kernel_times(reset=True)["other"]
-    return ms * 1000.0, int(launches)
-
-
-def scene():
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    return cfg, rec, pkg.default_params(**syn.params_fields(cfg))
 
 
 def obstacle_step(rec, sp, stream, dynamic):
@@ -78,16 +54,7 @@ def obstacle_step(rec, sp, stream, dynamic):
         for k, o in enumerate(obs):
             make = (pkg.dynamics_sphere, pkg.dynamics_box, pkg.dynamics_capsule)[o.shape]
             f.set_obstacle_dynamics(k, make(0.6 * rho, list(o.size)[:3] if o.shape else o.size[0]))
-    f.set_option(pkg.SPH_OPT_TIMING, 1)
-    for _ in range(3):
-        f.DispatchCompute()
-    other_us(f)
-    us = []
-    for _ in range(REPS):
-        f.DispatchCompute()
-        t, launches = other_us(f)
-        assert launches == 1, launches
-        us.append(t)
+    us = timing.other_per_dispatch(f)
     f.close()
     return stats(us)
 
@@ -95,7 +62,7 @@ def obstacle_step(rec, sp, stream, dynamic):
 def kinematic_child(out_path):
     """Child process: the kinematic obstacle step from the tree SPH_TREE names (only what the parent commit has is used)."""
     import torch
-    _, rec, sp = scene()
+    _, rec, sp = timing.config3()
     res = obstacle_step(rec, sp, torch.cuda.Stream(), False)
     res["tree"] = ROOT
     res["csrc_hash"] = pkg.build.csrc_hash()
@@ -128,7 +95,7 @@ def moments(f, n):
 def trace_run():
     """A short run for a kernel trace: 40 substeps kinematic, 40 dynamic, moments of a 256^3 lattice."""
     import torch
-    _, rec, sp = scene()
+    _, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
     for dynamic in (False, True):
         f = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream.cuda_stream)
@@ -170,11 +137,10 @@ def main() -> None:
     parent = args[args.index("--parent-tree") + 1] if "--parent-tree" in args else None
     trace = args[args.index("--trace") + 1] if "--trace" in args else None
     plain = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] not in ("--parent-tree", "--trace"))]
-    out_path = plain[0] if plain else os.path.join(ROOT, "profiles", "r11_time_bodies.json")
-    cfg, rec, sp = scene()
+    out_path = timing.out_path(plain, "bodies")
+    cfg, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
-    res = {"tool": "tools/time_bodies.py", "csrc_hash": pkg.build.csrc_hash(), "config": cfg.name, "particles": int(len(rec)),
-           "device": torch.cuda.get_device_name(0), "samples_per_case": REPS, "bodies": 4}
+    res = timing.header("tools/time_bodies.py", cfg, rec, samples_per_case=REPS, bodies=4)
     res["kinematic"] = obstacle_step(rec, sp, stream, False)
     res["dynamic"] = obstacle_step(rec, sp, stream, True)
     res["dynamic_minus_kinematic_us"] = res["dynamic"]["median_us"] - res["kinematic"]["median_us"]
@@ -203,10 +169,7 @@ def main() -> None:
     if trace:
         res["kernel_trace"] = read_trace(trace)
         print("trace", json.dumps(res["kernel_trace"]), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path)
+    timing.write_json(res, out_path)
 
 
 if __name__ == "__main__":

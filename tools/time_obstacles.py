@@ -11,81 +11,34 @@ For K = 1, 4 and 16 spinning, slowly moving bodies (spheres, boxes and capsules 
 
 touched_fraction is the share of records whose position differs after one substep with the bodies from one without them.
   python tools/time_obstacles.py [out.json]          (SPH_HIP_LIB selects a variant library, tools/build_variant.sh)
+Without an argument the result goes to time_obstacles.json in the current directory; profiles/r09_time_obstacles.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
-import importlib
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
-F = np.float32
-REPS = 25
-
-
-def stats(us):
-    us = np.asarray(us, np.float64)
-    return {"median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()),
-            "p10_us": float(np.percentile(us, 10)), "p90_us": float(np.percentile(us, 90)), "calls": int(len(us))}
+import timing
+from timing import REPS, pkg, stats
 
 
 def bodies(state, K, dt):
-    fluid = state["pos"][state["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = fluid.min(axis=0), fluid.max(axis=0)
-    side = int(np.ceil(K ** (1.0 / 3.0) - 1e-9))
-    cell = (hi - lo) / side
-    r = 0.3 * float(cell.min())
+    centres, r = timing.body_grid(state, K)
     out = []
-    for k in range(K):
-        i, j, l = k % side, (k // side) % side, k // (side * side)
-        c = lo + cell * (np.array([i, j, l]) + 0.5)
+    for k, c in enumerate(centres):
         shape = k % 3
         size = (r,) if shape == 0 else ((r, 0.8 * r, 0.6 * r) if shape == 1 else (0.6 * r, 0.7 * r))
         out.append(pkg.obstacle(shape, c, size, rotation=(0.9, 0.1, 0.3, 0.2), vel=(0.02 * r / dt, 0.0, 0.0), omega=(0.0, 0.5 / (16 * dt), 0.1 / (16 * dt))))
     return out
 
 
-def other_us(f):
-    ms, launches = f.kernel_times(reset=True)["other"]
-    return ms * 1000.0, int(launches)
-
-
-def copy_yardstick(n, stream):
-    import torch
-    src = [torch.ones((n, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-    dst = [torch.empty((n, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    us = []
-    with torch.cuda.stream(stream):
-        for k in range(3 + REPS):
-            a.record(stream)
-            dst[0].copy_(src[0])
-            dst[1].copy_(src[1])
-            b.record(stream)
-            b.synchronize()
-            if k >= 3:
-                us.append(a.elapsed_time(b) * 1000.0)
-    return stats(us)
-
-
 def obstacle_pass(state, sp, stream, K):
     f = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)
     f.set_obstacles(bodies(state, K, float(sp.param_timeStep)))
-    f.set_option(pkg.SPH_OPT_TIMING, 1)
-    for _ in range(3):
-        f.DispatchCompute()
-    other_us(f)
-    us = []
-    for _ in range(REPS):
-        f.DispatchCompute()
-        t, launches = other_us(f)
-        assert launches == 1, launches                                  # one bracket: the two obstacle launches, nothing else
-        us.append(t)
+    us = timing.other_per_dispatch(f)                                    # one bracket: the two obstacle launches, nothing else
     f.set_option(pkg.SPH_OPT_TIMING, 0)
     J, t, n = f.obstacle_impulses()
     f.close()
@@ -94,33 +47,19 @@ def obstacle_pass(state, sp, stream, K):
 
 def touched_fraction(state, sp, stream, K):
     a = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)
-    b = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)
     a.set_obstacles(bodies(state, K, float(sp.param_timeStep)))
-    a.DispatchCompute()
-    b.DispatchCompute()
-    ra, rb = a.download(), b.download()
-    a.close()
-    b.close()
-    return float((ra["pos"] != rb["pos"]).any(axis=1).mean())
+    return timing.moved_fraction(state, sp, stream, a)
 
 
 def main() -> None:
     import torch
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r09_time_obstacles.json")
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    sp = pkg.default_params(**syn.params_fields(cfg))
+    out_path = timing.out_path(sys.argv[1:], "obstacles")
+    cfg, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
-    res = {"tool": "tools/time_obstacles.py", "csrc_hash": pkg.build.csrc_hash(), "library": os.path.basename(os.environ.get("SPH_HIP_LIB") or "libsph_hip.so"),
-           "config": cfg.name, "particles": int(len(rec)), "device": torch.cuda.get_device_name(0), "samples_per_case": REPS, "regimes": {}}
+    res = timing.header("tools/time_obstacles.py", cfg, rec, variant_library=True, samples_per_case=REPS, regimes={})
     f = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream.cuda_stream)
-    done = 0
-    for label, substep in (("lattice_state", 1), ("compressed", 300)):
-        f.DispatchN(substep - done) if substep - done > 1 else f.DispatchCompute()
-        done = substep
-        state = f.download()
-        yard = copy_yardstick(len(state), stream)
+    for label, substep, state in timing.regimes(f, single_step_compute=True):
+        yard = timing.copy_yardstick(len(state), stream)
         r = {"substep": substep, "yardstick": yard}
         for K in (1, 4, 16):
             s, info = obstacle_pass(state, sp, stream, K)
@@ -131,10 +70,7 @@ def main() -> None:
     f.close()
     res["goal"] = "K = 1 and K = 4: obstacle_pass <= 1.25 x yardstick"
     res["goal_met"] = all(res["regimes"][g][f"K{K}"]["ratio"] <= 1.25 for g in res["regimes"] for K in (1, 4))
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path, "goal met" if res["goal_met"] else "goal NOT met")
+    timing.write_json(res, out_path, "goal met" if res["goal_met"] else "goal NOT met")
 
 
 if __name__ == "__main__":

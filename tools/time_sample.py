@@ -9,28 +9,24 @@ lattice state (substep 0) and after 300 substeps (the compressed regime, DESIGN.
 
 Device events on the engine's stream around each call, 3 warm-up calls, median and spread of 25.
   python tools/time_sample.py [out.json]
+Without an argument the result goes to time_sample.json in the current directory; profiles/r06_time_sample.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
-import importlib
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
+import timing
+from timing import pkg
 
 
 def main() -> None:
     import torch
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r06_time_sample.json")
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    sp = pkg.default_params(**syn.params_fields(cfg))
+    out_path = timing.out_path(sys.argv[1:], "sample")
+    cfg, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
     f = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream.cuda_stream)
     g = f.ComputeGridExtents()
@@ -55,30 +51,12 @@ def main() -> None:
     out_pts = torch.empty((npts, 8), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
 
-    def timed(fn, reps=25, warm=3):
-        for _ in range(warm):
-            fn()
-        ms = []
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            ms.append(a.elapsed_time(b) * 1000.0)
-        ms = np.array(ms)
-        return {"median_us": float(np.median(ms)), "min_us": float(ms.min()), "max_us": float(ms.max()),
-                "p10_us": float(np.percentile(ms, 10)), "p90_us": float(np.percentile(ms, 90)), "calls": int(reps)}
+    def timed(fn):
+        return timing.events(fn, stream)
 
-    res = {"tool": "tools/time_sample.py", "csrc_hash": pkg.build.csrc_hash(), "config": cfg.name, "particles": int(len(rec)),
-           "grid": list(g.dims), "lattice": list(dims), "lattice_points": int(npts), "spacing": "h/2", "random_probes": 1 << 20,
-           "device": torch.cuda.get_device_name(0), "regimes": {}}
-    done = 0
-    for label, substep in (("lattice_state", 0), ("compressed", 300)):
-        if substep > done:
-            f.DispatchN(substep - done)
-            done = substep
-        f.sync()
+    res = timing.header("tools/time_sample.py", cfg, rec, grid=list(g.dims), lattice=list(dims), lattice_points=int(npts), spacing="h/2",
+                        random_probes=1 << 20, regimes={})
+    for label, substep, _ in timing.regimes(f, (("lattice_state", 0), ("compressed", 300)), download=False):
         r = {}
         r["a_lattice_density"] = timed(lambda: f.sample_lattice_device(origin, spacing, dims, out_f.data_ptr(), pkg.SPH_FIELD_DENSITY))
         r["b_lattice_all"] = timed(lambda: f.sample_lattice_device(origin, spacing, dims, out_all.data_ptr(), pkg.SPH_FIELD_ALL))
@@ -100,10 +78,7 @@ def main() -> None:
         res["regimes"][label] = dict(substep=substep, **r)
         print(label, json.dumps({k: (v["median_us"] if isinstance(v, dict) else v) for k, v in r.items()}), flush=True)
     f.close()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path)
+    timing.write_json(res, out_path)
 
 
 if __name__ == "__main__":

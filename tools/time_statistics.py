@@ -10,26 +10,19 @@
 
 5 warm-up calls, median and p10-p90 of 25.
   python tools/time_statistics.py [out.json]
+Without an argument the result goes to time_statistics.json in the current directory; profiles/r07_time_statistics.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
-import importlib
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
-
-
-def _stats(us):
-    us = np.array(us)
-    return {"median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()),
-            "p10_us": float(np.percentile(us, 10)), "p90_us": float(np.percentile(us, 90)), "calls": int(len(us))}
+import timing
+from timing import pkg, stats
 
 
 def numpy_reductions(rec, g):
@@ -56,16 +49,12 @@ def numpy_reductions(rec, g):
 
 
 def main() -> None:
-    import torch
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r07_time_statistics.json")
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    sp = pkg.default_params(**syn.params_fields(cfg))
+    out_path = timing.out_path(sys.argv[1:], "statistics")
+    cfg, rec, sp = timing.config3()
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    n = len(rec)
-    del rec
     g = f.ComputeGridExtents()
+    head = timing.header("tools/time_statistics.py", cfg, rec, grid=list(g.dims))
+    del rec
     rho0, half = float(sp.param_restDensity), float(sp.param_boxHalf[1])
     specs = [(pkg.SPH_STAT_DENSITY, 256, 0.0, 16 * rho0), (pkg.SPH_STAT_PRESSURE, 256, 0.0, 4.0e7), (pkg.SPH_STAT_SPEED, 256, 0.0, 120.0),
              (pkg.SPH_STAT_POS_Y, 256, -half, half)]
@@ -80,7 +69,7 @@ def main() -> None:
             t0 = time.perf_counter()
             fn()
             us.append((time.perf_counter() - t0) * 1e6)
-        return _stats(us)
+        return stats(us)
 
     def classes(hist):
         """Device time per call of the grid build classes and of class "other" (SPH_OPT_TIMING)."""
@@ -96,16 +85,10 @@ def main() -> None:
             other.append(kt["other"][0] * 1000.0)
             launches.append(int(kt["other"][1]))
         f.set_option(pkg.SPH_OPT_TIMING, 0)
-        return _stats(build), dict(_stats(other), launches_per_call=int(np.median(launches)))
+        return stats(build), dict(stats(other), launches_per_call=int(np.median(launches)))
 
-    res = {"tool": "tools/time_statistics.py", "csrc_hash": pkg.build.csrc_hash(), "config": cfg.name, "particles": int(n), "grid": list(g.dims),
-           "histograms": [list(s) for s in specs], "device": torch.cuda.get_device_name(0), "regimes": {}}
-    done = 0
-    for label, substep in (("lattice_state", 1), ("compressed", 300)):
-        f.DispatchN(substep - done)
-        done = substep
-        f.sync()
-        f.download()                                                     # lazy AoS mode: the records are written back once, outside the timings
+    res = dict(head, histograms=[list(s) for s in specs], regimes={})
+    for label, substep, _ in timing.regimes(f):                          # (downloads: lazy AoS mode writes the records back once, outside the timings)
         r = {}
         r["a_grid_build"], r["b_statistics_kernels"] = classes(None)
         _, r["b_statistics_kernels_4x256_bins"] = classes(specs)
@@ -125,10 +108,7 @@ def main() -> None:
         res["regimes"][label] = dict(substep=substep, **r)
         print(label, json.dumps({k: (x["median_us"] if isinstance(x, dict) and "median_us" in x else x) for k, x in r.items()}), flush=True)
     f.close()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path)
+    timing.write_json(res, out_path)
 
 
 if __name__ == "__main__":

@@ -15,10 +15,11 @@ interface (sample, host update, dispatch per substep).
 
 Device events on the engine's stream, warm-up, median and p10-p90 of the samples.
   python tools/time_tracers.py [out.json]          (SPH_HIP_LIB selects a variant library, tools/build_variant.sh)
+Without an argument the result goes to time_tracers.json in the current directory; profiles/r08_time_tracers.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
-import importlib
 import json
 import os
 import re
@@ -27,16 +28,10 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
+import timing
+from timing import ROOT, other_us, pkg, stats
+
 F = np.float32
-
-
-def stats(us):
-    us = np.asarray(us, np.float64)
-    return {"median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()),
-            "p10_us": float(np.percentile(us, 10)), "p90_us": float(np.percentile(us, 90)), "calls": int(len(us))}
 
 
 def refresh_interval() -> int:
@@ -50,11 +45,6 @@ def seeds(state, m, rng):
     p4 = np.zeros((m, 4), F)
     p4[:, :3] = (lo + (hi - lo) * rng.random((m, 3))).astype(F)
     return p4
-
-
-def other_us(f):
-    ms, launches = f.kernel_times(reset=True)["other"]
-    return ms * 1000.0, int(launches)
 
 
 def tracer_work(f, p4, integ, R, reps):
@@ -109,37 +99,25 @@ def host_loop(f, p4, n, dt, integ):
 
 def main() -> None:
     import torch
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r08_time_tracers.json")
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    sp = pkg.default_params(**syn.params_fields(cfg))
+    out_path = timing.out_path(sys.argv[1:], "tracers")
+    cfg, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
     f = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream.cuda_stream)
     R = refresh_interval()
     reps = 2 * R + 8
-    res = {"tool": "tools/time_tracers.py", "csrc_hash": pkg.build.csrc_hash(), "library": os.path.basename(os.environ.get("SPH_HIP_LIB") or "libsph_hip.so"),
-           "config": cfg.name, "particles": int(len(rec)), "device": torch.cuda.get_device_name(0), "refresh_interval": R,
-           "samples_per_case": reps, "regimes": {}}
+    res = timing.header("tools/time_tracers.py", cfg, rec, variant_library=True, refresh_interval=R, samples_per_case=reps, regimes={})
     rng = np.random.default_rng(7)
-    done = 0
-    state = rec
-    for label, substep in (("lattice_state", 1), ("compressed", 300)):
-        f.DispatchN(substep - done)
-        done = substep
-        state = f.download()
-        f.close()
+    for label, substep, state in timing.regimes(f):
         r = {}
         for m in (1 << 16, 1 << 20):
             p4 = seeds(state, m, rng)
             for name, integ in (("euler", pkg.SPH_TRACER_EULER), ("midpoint", pkg.SPH_TRACER_MIDPOINT)):
-                f = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)        # every case starts from the same state
-                r[f"{name}_{m}"] = tracer_work(f, p4, integ, R, reps)
-                f.close()
+                e = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)        # every case starts from the same state
+                r[f"{name}_{m}"] = tracer_work(e, p4, integ, R, reps)
+                e.close()
                 print(label, name, m, json.dumps({k: (v["median_us"] if isinstance(v, dict) and "median_us" in v else v)
                                                    for k, v in r[f"{name}_{m}"].items()}), flush=True)
         res["regimes"][label] = dict(substep=substep, **r)
-        f = pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)
     f.close()
     # end to end: 100 substeps with 1 M tracers, one sph_dispatch_n call against the host loop over the sampling interface
     p4 = seeds(state, 1 << 20, rng)
@@ -176,10 +154,7 @@ def main() -> None:
                      "dispatch_n_without_tracers_ms": t_plain * 1e3, "host_loop_over_engine": t_host / t_engine}
         print("end_to_end", name, json.dumps(e2e[name]), flush=True)
     res["end_to_end"] = e2e
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path)
+    timing.write_json(res, out_path)
 
 
 if __name__ == "__main__":

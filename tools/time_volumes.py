@@ -13,10 +13,11 @@ No ratio is gated.
 sph_mesh_distance on an icosphere: 128^3 points x 20 480 triangles and 64^3 x 1 280: wall time of the call up to the end of the stream,
 device time of its two kernels, pairs per second.
   python tools/time_volumes.py [out.json]          (SPH_HIP_LIB selects a variant library, tools/build_variant.sh)
+Without an argument the result goes to time_volumes.json in the current directory; profiles/r10_time_volumes.json is the committed
+record of the first measurement.
 """
 from __future__ import annotations
 
-import importlib
 import json
 import os
 import sys
@@ -24,11 +25,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-pkg = importlib.import_module("componentframeworks-smoothed-particle-hydrodynamics_amd")
-from time_obstacles import REPS, copy_yardstick, other_us, stats  # noqa: E402
+import timing
+from timing import REPS, ROOT, pkg, stats
 
 F = np.float32
 LATTICE = 33                                                            # points per axis of the sphere's lattice
@@ -42,17 +40,11 @@ def sphere_lattice(radius):
 
 
 def boxes(state, K, dt):
-    fluid = state["pos"][state["isGhost"] == 0][:, :3].astype(np.float64)
-    lo, hi = fluid.min(axis=0), fluid.max(axis=0)
-    side = int(np.ceil(K ** (1.0 / 3.0) - 1e-9))
-    cell = (hi - lo) / side
-    r = 0.3 * float(cell.min())
+    centres, r = timing.body_grid(state, K)
     values, h = sphere_lattice(r)
     half = F(0.5) * F(LATTICE - 1) * h
     out = []
-    for k in range(K):
-        i, j, l = k % side, (k // side) % side, k // (side * side)
-        c = lo + cell * (np.array([i, j, l]) + 0.5)
+    for c in centres:
         out.append(pkg.obstacle(pkg.SPH_OBSTACLE_BOX, c, (half, half, half), rotation=(0.9, 0.1, 0.3, 0.2), vel=(0.02 * r / dt, 0.0, 0.0),
                                 omega=(0.0, 0.5 / (16 * dt), 0.1 / (16 * dt))))
     return out, values, h
@@ -71,28 +63,13 @@ def engine(state, sp, stream, K, bound):
 
 def obstacle_pass(state, sp, stream, K, bound):
     f = engine(state, sp, stream, K, bound)
-    f.set_option(pkg.SPH_OPT_TIMING, 1)
-    for _ in range(3):
-        f.DispatchCompute()
-    other_us(f)
-    us = []
-    for _ in range(REPS):
-        f.DispatchCompute()
-        t, launches = other_us(f)
-        assert launches == 1, launches
-        us.append(t)
+    us = timing.other_per_dispatch(f)
     f.close()
     return stats(us)
 
 
 def moved_fraction(state, sp, stream, K, bound):
-    a, b = engine(state, sp, stream, K, bound), pkg.SPHFluidGPU.from_particles(state, sp, stream=stream.cuda_stream)
-    a.DispatchCompute()
-    b.DispatchCompute()
-    ra, rb = a.download(), b.download()
-    a.close()
-    b.close()
-    return float((ra["pos"] != rb["pos"]).any(axis=1).mean())
+    return timing.moved_fraction(state, sp, stream, engine(state, sp, stream, K, bound))
 
 
 def icosphere(subdivisions):
@@ -122,27 +99,19 @@ def mesh_build(f, n, subdivisions):
 
 def main() -> None:
     import torch
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r10_time_volumes.json")
-    syn = pkg.synthetic
-    cfg = syn.CONFIGS[3]
-    rec, _ = syn.make_particles(cfg)
-    sp = pkg.default_params(**syn.params_fields(cfg))
+    out_path = timing.out_path(sys.argv[1:], "volumes")
+    cfg, rec, sp = timing.config3()
     stream = torch.cuda.Stream()
-    res = {"tool": "tools/time_volumes.py", "csrc_hash": pkg.build.csrc_hash(), "library": os.path.basename(os.environ.get("SPH_HIP_LIB") or "libsph_hip.so"),
-           "config": cfg.name, "particles": int(len(rec)), "device": torch.cuda.get_device_name(0), "samples_per_case": REPS,
-           "volume_lattice": [LATTICE] * 3, "regimes": {}, "mesh_distance": {}}
+    res = timing.header("tools/time_volumes.py", cfg, rec, variant_library=True, samples_per_case=REPS, volume_lattice=[LATTICE] * 3,
+                        regimes={}, mesh_distance={})
     f = pkg.SPHFluidGPU.from_particles(rec, sp, stream=stream.cuda_stream)
     f.set_option(pkg.SPH_OPT_TIMING, 1)
     for label, n, sub in (("128^3 x 20480", 128, 5), ("64^3 x 1280", 64, 3)):
         res["mesh_distance"][label] = mesh_build(f, n, sub)
         print(label, json.dumps(res["mesh_distance"][label]), flush=True)
     f.set_option(pkg.SPH_OPT_TIMING, 0)
-    done = 0
-    for label, substep in (("lattice_state", 1), ("compressed", 300)):
-        f.DispatchN(substep - done) if substep - done > 1 else f.DispatchCompute()
-        done = substep
-        state = f.download()
-        yard = copy_yardstick(len(state), stream)
+    for label, substep, state in timing.regimes(f, single_step_compute=True):
+        yard = timing.copy_yardstick(len(state), stream)
         r = {"substep": substep, "yardstick": yard}
         for K in (1, 4):
             box, vol = obstacle_pass(state, sp, stream, K, False), obstacle_pass(state, sp, stream, K, True)
@@ -152,10 +121,7 @@ def main() -> None:
             print(label, K, json.dumps({k: (v["median_us"] if isinstance(v, dict) else v) for k, v in r[f"K{K}"].items()}), "copy_us", yard["median_us"], flush=True)
         res["regimes"][label] = r
     f.close()
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print("wrote", out_path)
+    timing.write_json(res, out_path)
 
 
 if __name__ == "__main__":
