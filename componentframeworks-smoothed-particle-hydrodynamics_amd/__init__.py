@@ -19,5 +19,6 @@ from .engine import (  # noqa: F401
     SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, SphVolumeHost, volume_sample_host, obstacles_apply_host_volumes, mesh_distance_host,
     SPH_DYNAMICS_CONFINED, SphObstacleDynamics, DYNAMICS_DTYPE, dynamics, dynamics_sphere, dynamics_box, dynamics_capsule, dynamics_array,
     mass_properties, obstacles_step_host, volume_moments_host,
+    SPH_MAX_SCALAR_CHANNELS, SPH_OPT_SCALAR_SWEEP, SPH_SCALAR_ADD, SPH_SCALAR_SET, ScalarMoments, SphScalarMoments, mixing_index, scalars_step_host,
 )
 from . import build, synthetic  # noqa: F401

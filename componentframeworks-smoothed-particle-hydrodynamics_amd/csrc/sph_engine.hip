@@ -25,6 +25,7 @@
 #include "sph_sample.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
+#include "sph_scalar.h"
 #include "sph_obstacle.h"
 #include "sph_volume.h"
 #include "sph_stats.h"
@@ -32,6 +33,8 @@
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
+static_assert(sizeof(SphScalarMoments) == 40, "SphScalarMoments must be 40 bytes");
+static_assert(SPH_MAX_SCALAR_CHANNELS == sph::kScalarMax && SPH_SCALAR_SET == sph::kScalarSet && SPH_SCALAR_ADD == sph::kScalarAdd, "scalar constants of sph_abi.h and sph_scalar.h");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
 static_assert(sizeof(SphObstacleDynamics) == 80, "SphObstacleDynamics must be 80 bytes");
 static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
@@ -259,6 +262,23 @@ struct SphEngine {
     bool trOrdered = false;              // the processing order has been cell-sorted since sph_tracers_set
     bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
 
+    // sph_scalars_* (sph_scalar.h): K channels per particle in the caller's order, their gathered copy in slot order
+    // (K values + the ghost weight per slot), the coefficients as the kernels read them (device memory: a replayed graph sees a later
+    // change) with their pinned staging, and the device word of the last substep's diffusion number
+    float* d_scVal = nullptr;
+    float* d_scSorted = nullptr;
+    sph::ScalarCoef* d_scCoef = nullptr;
+    uint32_t* d_scState = nullptr;
+    StageRing<sph::ScalarCoef> scStage;
+    int scK = 0;
+    size_t scN = 0;                      // particles the buffers were allocated for
+    float scCoeffs[2 * sph::kScalarMax] = {0};   // D_0 .. D_{K-1}, lambda_0 .. lambda_{K-1} as set
+    uint64_t scSteps = 0;                // non-paused substeps issued since sph_scalars_set
+    int optScalarSweep = 0;              // SPH_OPT_SCALAR_SWEEP: 0 = plain walk, 1 = LDS-staged
+    DevBuf<float4> d_scView;             // sph_scalars_moments: a channel laid out as the statistics kernels' input (3 float4 per slot)
+    DevBuf<float2> d_scViewRp;
+    DevBuf<float> d_scSampleOut;         // sph_scalars_sample_points (host arrays): device copy of the results
+
     // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
     // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
     sph::ObsRec* d_obs = nullptr;
@@ -407,6 +427,14 @@ void tracers_free(SphEngine* e) {
     e->trM = e->trCap = e->trRingCap = 0;
     e->trK = 0; e->trS = 1; e->trSteps = e->trSorted = 0;
     e->trOrdered = false;
+}
+
+void scalars_free(SphEngine* e) {
+    if (e->d_scVal && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(e->d_scVal); dev_free(e->d_scSorted); dev_free(e->d_scCoef); dev_free(e->d_scState);
+    e->scStage.destroy();
+    e->d_scView.release(); e->d_scViewRp.release(); e->d_scSampleOut.release();
+    e->scK = 0; e->scN = 0; e->scSteps = 0;
 }
 
 void obstacles_free(SphEngine* e) {
@@ -613,6 +641,109 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
     return SPH_OK;
 }
 
+// ---- diffusing scalars (sph_scalar.h) -------------------------------------------------------------
+// One substep's scalar work, behind build_grid of that substep: gather the values into slot order, then the neighbour sweep on the sorted copy.
+template <int K>
+void scalars_launch(SphEngine* e, const SimK& k, float dt, uint32_t n) {
+    hipLaunchKernelGGL((k_scalar_gather<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, (const float*)e->d_scVal, e->d_scSorted,
+                       e->d_scState, e->idBase, n);
+    const float kLap = scalar_klap(e->params.param_mass, e->params.param_h);
+    if (e->optScalarSweep == 1)
+        hipLaunchKernelGGL((k_scalar_sweep_staged<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
+                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef, kLap, dt, e->d_scVal, e->d_scState,
+                           e->idBase, n);
+    else
+        hipLaunchKernelGGL((k_scalar_sweep<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
+                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef, kLap, dt, e->d_scVal, e->d_scState,
+                           e->idBase, n);
+}
+// The gather alone, outside a substep (sampling, on the grid of the current state): the diffusion number is left alone.
+template <int K>
+void scalars_gather_launch(SphEngine* e, uint32_t n) {
+    hipLaunchKernelGGL((k_scalar_gather<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, (const float*)e->d_scVal, e->d_scSorted,
+                       (uint32_t*)nullptr, e->idBase, n);
+}
+void scalars_gather_now(SphEngine* e, uint32_t n) {
+    switch (e->scK) {
+    case 1: scalars_gather_launch<1>(e, n); break;
+    case 2: scalars_gather_launch<2>(e, n); break;
+    case 3: scalars_gather_launch<3>(e, n); break;
+    default: scalars_gather_launch<4>(e, n); break;
+    }
+}
+int scalars_step(SphEngine* e, const SimK& k, float dt) {
+    const uint32_t n = (uint32_t)e->n;
+    if (n) {
+        Timed t(e, SPH_K_OTHER);
+        switch (e->scK) {
+        case 1: scalars_launch<1>(e, k, dt, n); break;
+        case 2: scalars_launch<2>(e, k, dt, n); break;
+        case 3: scalars_launch<3>(e, k, dt, n); break;
+        default: scalars_launch<4>(e, k, dt, n); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    e->scSteps += 1;
+    return SPH_OK;
+}
+
+// The substep's scalar work on the CPU: the grid as the counting sort leaves it (cells ascending, members ascending by index), the
+// gathered copy, then scalar_pair / scalar_finish per target in slot order.
+template <int K>
+float scalars_step_loop(const SimK& k, float kLap, float dt, const sph::ScalarCoef& co, const SphParticle* P, size_t n, float* values) {
+    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int cx = sph::scalar_cell_axis(P[i].pos[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(P[i].pos[1], k.gminy, k.cellSize, k.gy),
+                  cz = sph::scalar_cell_axis(P[i].pos[2], k.gminz, k.cellSize, k.gz);
+        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+        start[cell[i] + 1] += 1u;
+    }
+    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) order[fill[cell[i]]++] = (uint32_t)i;
+    }
+    std::vector<float> pv(4 * n), sC((size_t)(K + 1) * n);
+    for (size_t q = 0; q < n; ++q) {
+        const SphParticle& p = P[order[q]];
+        pv[4 * q] = p.pos[0]; pv[4 * q + 1] = p.pos[1]; pv[4 * q + 2] = p.pos[2];
+        pv[4 * q + 3] = p.density > 0.0f ? 1.0f / p.density : 0.0f;
+        for (int c = 0; c < K; ++c) sC[q * (K + 1) + c] = values[(size_t)order[q] * K + c];
+        sC[q * (K + 1) + K] = p.isGhost != 0 ? 0.0f : 1.0f;
+    }
+    uint32_t best = 0u;
+    for (size_t q = 0; q < n; ++q) {
+        const float* X = &pv[4 * q];
+        const float* ci = &sC[q * (K + 1)];
+        if (!(ci[K] > 0.0f) || !sph::scalar_finite(X[0]) || !sph::scalar_finite(X[1]) || !sph::scalar_finite(X[2]) || !(X[3] > 0.0f)) continue;
+        float a[K], W = 0.0f;
+        for (int c = 0; c < K; ++c) a[c] = 0.0f;
+        const int cx = sph::scalar_cell_axis(X[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(X[1], k.gminy, k.cellSize, k.gy),
+                  cz = sph::scalar_cell_axis(X[2], k.gminz, k.cellSize, k.gz);
+        const int xlo = std::max(cx - 1, 0), xhi = std::min(cx + 1, k.gx - 1);
+        for (int r = 0; r < 9; ++r) {
+            const int nz = cz + r / 3 - 1, ny = cy + r % 3 - 1;
+            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
+            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
+            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+                if (j == q) continue;
+                const float* Y = &pv[4 * (size_t)j];
+                const float* cj = &sC[(size_t)j * (K + 1)];
+                sph::scalar_pair<K>(k.h, k.h2, X[0], X[1], X[2], X[3], ci, Y[0], Y[1], Y[2], cj[K] > 0.0f ? Y[3] : 0.0f, cj, a, W);
+            }
+        }
+        float out[K];
+        const float s = sph::scalar_finish<K>(co, kLap, dt, ci, a, W, out);
+        for (int c = 0; c < K; ++c) values[(size_t)order[q] * K + c] = out[c];
+        uint32_t bits;
+        std::memcpy(&bits, &s, 4);
+        best = std::max(best, bits);
+    }
+    float mx;
+    std::memcpy(&mx, &best, 4);
+    return mx;
+}
+
 // ---- obstacles (sph_obstacle.h) -------------------------------------------------------------------
 // What obs_body_step needs of the parameters: gravity, the container's oriented box as the grid sees it, the wall restitution.
 void obstacle_world(const SphParams& p, sph::ObsWorld& W) {
@@ -688,6 +819,8 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     int rc;
     if (e->trM && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (e->scK && e->optGridBuild == 1)
+        return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params))) return rc;
     float cont[15];
     container_key(e->params, cont);
@@ -735,6 +868,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     } else {
     if ((rc = build_grid(e, k, true))) return rc;                           // :449-468
     if (e->trM && (rc = tracers_advect(e, k, dt))) return rc;               // (reads the sorted copy and cellStart, as the SPH pass does)
+    if (e->scK && (rc = scalars_step(e, k, dt))) return rc;                 // (the same two, and the sorted own data)
     if (n) {                                                                // :470-509 (SPH + OBB fused)
         if (!e->d_sPV || e->sortedCap < (size_t)n) return fail(SPH_ERR_STATE, "sorted copy missing");
         const uint32_t* live = e->slab ? e->d_cellStart + k.numCells : nullptr;
@@ -990,6 +1124,7 @@ int sph_destroy(SphEngine* e) {
     surface_free(e);
     stats_free(e);
     tracers_free(e);
+    scalars_free(e);
     obstacles_free(e);
     volumes_free(e);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -1022,6 +1157,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     tracers_free(e);                                                  // (and the tracer set)
+    scalars_free(e);                                                  // (and the scalar channels)
     if (e->d_obsAcc) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (obstacles: the set and the poses stay, the sums restart)
     std::vector<SphParticle> v;
     float m;
@@ -1057,6 +1193,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_TIMING: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optTiming = value; break;
     case SPH_OPT_GRAPH: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optGraph = value; break;
     case SPH_OPT_MESH_SPLIT: if (value < 0 || value > 64) return fail(SPH_ERR_ARG, "bad value"); e->optMeshSplit = value; break;
+    case SPH_OPT_SCALAR_SWEEP: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optScalarSweep = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1078,6 +1215,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_TIMING: *value = e->optTiming; break;
     case SPH_OPT_GRAPH: *value = e->optGraph; break;
     case SPH_OPT_MESH_SPLIT: *value = e->optMeshSplit; break;
+    case SPH_OPT_SCALAR_SWEEP: *value = e->optScalarSweep; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -1113,6 +1251,11 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     add(tr, sizeof(tr));
     const uint64_t trv[4] = {(uint64_t)e->trM, (uint64_t)e->trIntegrator, e->trK, e->trS};
     add(trv, sizeof(trv));
+    // scalars: a call with scalars is never served by a graph captured without them or with another channel count; the coefficients are read from memory
+    const void* sc[4] = {e->d_scVal, e->d_scSorted, e->d_scCoef, e->d_scState};
+    add(sc, sizeof(sc));
+    add(&e->scK, sizeof(e->scK));
+    add(&e->optScalarSweep, sizeof(e->optScalarSweep));
     // obstacles: the buffers and the count (the kernels read the bodies from memory, so a later set / set_motion needs no new graph)
     const void* ob[3] = {e->d_obs, e->d_obsAcc, e->d_obsPart};
     add(ob, sizeof(ob));
@@ -1158,6 +1301,7 @@ int sph_dispatch_n(SphEngine* e, float overrideDt, int nSubsteps) {
                 if ((trc = tracers_order(e, k))) return trc;
                 e->trSteps += (uint64_t)nSubsteps;               // (the replayed k_tracer_tick launches advance the device counter)
             }
+            if (e->scK) e->scSteps += (uint64_t)nSubsteps;
             HIP_TRY(hipGraphLaunch(hit->exec, e->stream));
             e->cur = hit->postCur; e->aosValid = hit->postAos; e->accValid = hit->postAcc; e->internalValid = true;
             hit->lastUse = ++e->graphClock;
@@ -2596,11 +2740,20 @@ static int stats_check_specs(const SphHistogramSpec* specs, int nSpecs, const ui
 }
 
 // Grid build of the current state (as sampling, with order[] for every slot), then tiles, cells, finish and the histogram sum.
+static int stats_reduce(SphEngine* e, const sph::StatK& specs, const sph::SimK& k, const float4* pv, const float4* own, const uint32_t* order,
+                        const float2* rp, SphStatistics* devOut, uint64_t* devHistOut);
 static int stats_run(SphEngine* e, const sph::StatK& specs, SphStatistics* devOut, uint64_t* devHistOut) {
-    using namespace sph;
-    SimK k;
+    sph::SimK k;
     int rc;
     if ((rc = sample_grid(e, k, true))) return rc;
+    return stats_reduce(e, specs, k, e->d_sPV, e->d_sOwn, e->d_order, e->d_rp[e->cur], devOut, devHistOut);
+}
+// The reduction over a sorted copy (pv, own), the exact densities rp[order[slot]] and the grid's cellStart (sph_scalars_moments hands it a
+// channel laid out as such a copy).
+static int stats_reduce(SphEngine* e, const sph::StatK& specs, const sph::SimK& k, const float4* pv, const float4* own, const uint32_t* order,
+                        const float2* rp, SphStatistics* devOut, uint64_t* devHistOut) {
+    using namespace sph;
+    int rc;
     StatK s = specs;
     s.gminx = k.gminx; s.gminy = k.gminy; s.gminz = k.gminz; s.cellSize = k.cellSize;
     s.gx = (float)k.gx; s.gy = (float)k.gy; s.gz = (float)k.gz;
@@ -2618,8 +2771,7 @@ static int stats_run(SphEngine* e, const sph::StatK& specs, SphStatistics* devOu
         (rc = e->d_statCell.grow(e, (size_t)kStatCellBlocks * kStatCellCols))) return rc;
     if (s.nTiles) {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_stats_tiles, dim3(s.nBlocks), dim3(kBlock), 0, e->stream, s, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
-                           (const uint32_t*)e->d_order, (const float2*)e->d_rp[e->cur], e->d_statSums.p, e->d_statPart.p, e->d_statHist.p);
+        hipLaunchKernelGGL(k_stats_tiles, dim3(s.nBlocks), dim3(kBlock), 0, e->stream, s, pv, own, order, rp, e->d_statSums.p, e->d_statPart.p, e->d_statHist.p);
     }
     {
         Timed t(e, SPH_K_OTHER);
@@ -2762,6 +2914,284 @@ int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t*
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (snapshotsOut) *snapshotsOut = count;
     if (firstSnapshotOut) *firstSnapshotOut = first;
+    return SPH_OK;
+}
+
+// ---- diffusing scalars (sph_scalar.h) -------------------------------------------------------------
+static int scalars_refused(SphEngine* e) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "scalars on a z-slab engine are not supported: halo records would have to carry them");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    return SPH_OK;
+}
+static int scalars_check_coeffs(const float* coeffs, int K) {
+    if (!coeffs) return fail(SPH_ERR_ARG, "null argument");
+    for (int i = 0; i < 2 * K; ++i)
+        if (!std::isfinite(coeffs[i]) || coeffs[i] < 0.0f)
+            return fail(SPH_ERR_ARG, "%s %d is %g (must be finite and >= 0)", i < K ? "diffusivity" : "decay rate", i % K, (double)coeffs[i]);
+    return SPH_OK;
+}
+// The coefficients as set, through a pinned slot, to the device record the kernels read: stream-ordered.
+static int scalars_upload_coef(SphEngine* e) {
+    sph::ScalarCoef* slot = nullptr;
+    int rc;
+    if ((rc = e->scStage.next(&slot))) return rc;
+    sph::scalar_make_coef(e->scK, e->scCoeffs, *slot);
+    HIP_TRY(hipMemcpyAsync(e->d_scCoef, slot, sizeof(sph::ScalarCoef), hipMemcpyHostToDevice, e->stream));
+    return e->scStage.commit(e->stream);
+}
+static int scalars_check_set(SphEngine* e, size_t n, int channels, const float* coeffs) {
+    int rc;
+    if ((rc = scalars_refused(e))) return rc;
+    if (channels == 0) return SPH_OK;
+    if (channels < 1 || channels > SPH_MAX_SCALAR_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (1 .. %d)", channels, SPH_MAX_SCALAR_CHANNELS);
+    if (n != e->n) return fail(SPH_ERR_ARG, "%zu values per channel for an engine of %zu particles", n, e->n);
+    return scalars_check_coeffs(coeffs, channels);
+}
+
+int sph_scalars_set_device(SphEngine* e, const float* devValues, size_t n, int channels, const float* coeffs) {
+    int rc;
+    if ((rc = scalars_check_set(e, n, channels, coeffs))) return rc;
+    if (channels == 0) { scalars_free(e); return SPH_OK; }
+    if (channels != e->scK || n != e->scN || !e->d_scVal) {              // (a set of the same shape reuses the buffers, and the graphs captured over them)
+        scalars_free(e);
+        hipError_t er = hipSuccess;
+        if ((rc = dev_alloc(&e->d_scVal, n * (size_t)channels)) || (rc = dev_alloc(&e->d_scSorted, n * (size_t)(channels + 1))) ||
+            (rc = dev_alloc(&e->d_scCoef, 1)) || (rc = dev_alloc(&e->d_scState, 4)) ||
+            (er = e->scStage.create(e->stream, 1)) != hipSuccess) {
+            scalars_free(e);
+            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the scalar coefficients: %s", hipGetErrorString(er));
+        }
+        e->scN = n;
+    }
+    e->scK = channels;
+    e->scSteps = 0;
+    std::memcpy(e->scCoeffs, coeffs, sizeof(float) * 2 * (size_t)channels);
+    if ((rc = scalars_upload_coef(e))) return rc;
+    if (devValues) {
+        if (n) HIP_TRY(hipMemcpyAsync(e->d_scVal, devValues, n * (size_t)channels * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+        hipLaunchKernelGGL(k_scalar_clear_state, dim3(1), dim3(64), 0, e->stream, e->d_scState);
+    } else {
+        // channel 0 = padB of the records (never rewritten by a substep, so the 80-byte array holds it whether or not it is current)
+        hipLaunchKernelGGL(k_scalar_seed, dim3(std::max(1, blocks_for(n))), dim3(kBlock), 0, e->stream, (const SphParticle*)e->d_aos, e->d_scVal, e->d_scState,
+                           channels, (uint32_t)n);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_scalars_set(SphEngine* e, const float* values, size_t n, int channels, const float* coeffs) {
+    int rc;
+    if ((rc = scalars_check_set(e, n, channels, coeffs))) return rc;
+    if (channels == 0) { scalars_free(e); return SPH_OK; }
+    float* staging = nullptr;
+    hipError_t er = hipSuccess;
+    if (values) {
+        if ((rc = dev_alloc(&staging, n * (size_t)channels))) return rc;
+        if (n) er = hipMemcpyAsync(staging, values, n * (size_t)channels * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    }
+    if (er == hipSuccess) rc = sph_scalars_set_device(e, staging, n, channels, coeffs);
+    const hipError_t es = hipStreamSynchronize(e->stream);
+    dev_free(staging);
+    if (er != hipSuccess) return fail(SPH_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(er));
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(SPH_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
+    return SPH_OK;
+}
+
+int sph_scalars_set_coefficients(SphEngine* e, const float* coeffs) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    int rc;
+    if ((rc = scalars_check_coeffs(coeffs, e->scK))) return rc;
+    std::memcpy(e->scCoeffs, coeffs, sizeof(float) * 2 * (size_t)e->scK);
+    return scalars_upload_coef(e);
+}
+
+int sph_scalars_channels(const SphEngine* e) { return e ? e->scK : 0; }
+
+int sph_scalars_download(SphEngine* e, float* out, size_t cap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    const size_t total = e->scK ? e->scN * (size_t)e->scK : 0;
+    if (cap < total) return fail(SPH_ERR_CAPACITY, "%zu values (capacity %zu)", total, cap);
+    if (total && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (total) HIP_TRY(hipMemcpyAsync(out, e->d_scVal, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_scalars_device(SphEngine* e, const float** devPtr) {
+    if (!e || !devPtr) return fail(SPH_ERR_ARG, "null argument");
+    *devPtr = e->scK ? e->d_scVal : nullptr;
+    return SPH_OK;
+}
+
+int sph_scalars_paint(SphEngine* e, const float center[3], float radius, int channel, float value, int mode) {
+    if (!e || !center) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    if (channel < 0 || channel >= e->scK) return fail(SPH_ERR_ARG, "channel %d of %d", channel, e->scK);
+    if (mode != SPH_SCALAR_SET && mode != SPH_SCALAR_ADD) return fail(SPH_ERR_ARG, "unknown mode %d", mode);
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(SPH_ERR_ARG, "radius %g (must be finite and > 0)", (double)radius);
+    if (!e->internalValid && !e->aosValid) return fail(SPH_ERR_STATE, "no valid particle state");
+    if (e->n) {
+        // the engine's own state arrays while they hold the state, else the 80-byte records (after an upload): nothing is materialised
+        const bool own = e->internalValid;
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_scalar_paint, dim3(blocks_for(e->n)), dim3(kBlock), 0, e->stream, own ? (const float4*)e->d_pos[e->cur] : (const float4*)nullptr,
+                           (const float4*)e->d_vel[e->cur], (const SphParticle*)e->d_aos, e->d_scVal, e->scK, channel, center[0], center[1], center[2],
+                           radius * radius, value, mode, e->idBase, (uint32_t)e->n);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_scalars_info(SphEngine* e, uint64_t* substepsOut, float* maxNumberOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (substepsOut) *substepsOut = e->scK ? e->scSteps : 0;
+    if (maxNumberOut) {
+        *maxNumberOut = 0.0f;
+        if (e->scK) {
+            HIP_TRY(hipMemcpyAsync(maxNumberOut, e->d_scState, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+    }
+    return SPH_OK;
+}
+
+// Grid of the CURRENT state (as sampling builds it) and the values gathered into its slot order; the diffusion number is left alone.
+static int scalars_sample_grid(SphEngine* e, int channel, SimK& k, bool orderAll = false) {
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    if (channel < 0 || channel >= e->scK) return fail(SPH_ERR_ARG, "channel %d of %d", channel, e->scK);
+    int rc;
+    if ((rc = sample_grid(e, k, orderAll))) return rc;
+    const uint32_t n = (uint32_t)e->n;
+    if (n) {
+        Timed t(e, SPH_K_OTHER);
+        scalars_gather_now(e, n);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_scalars_moments(SphEngine* e, SphScalarMoments* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    int rc;
+    if ((rc = stats_refused(e))) return rc;
+    SimK k;
+    if ((rc = sample_grid(e, k, true))) return rc;
+    const size_t n = e->n, headWords = sizeof(SphStatistics) / sizeof(uint64_t);
+    if ((rc = e->d_scView.grow(e, 3 * n)) || (rc = e->d_scViewRp.grow(e, n)) || (rc = e->d_statOut.grow(e, headWords * (size_t)sph::kScalarMax + (size_t)sph::kStatHistWords)))
+        return rc;
+    sph::StatK s{};
+    if ((rc = stats_check_specs(nullptr, 0, nullptr, s))) return rc;
+    float4* vPv = e->d_scView.p;
+    float4* vOwn = e->d_scView.p + 2 * n;
+    for (int c = 0; c < e->scK; ++c) {
+        if (n) {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_scalar_stat_view, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
+                               (const uint32_t*)e->d_order, (const float*)e->d_scVal, e->scK, c, vPv, vOwn, e->d_scViewRp.p, e->idBase, (uint32_t)n);
+        }
+        if ((rc = stats_reduce(e, s, k, vPv, vOwn, e->d_order, e->d_scViewRp.p, reinterpret_cast<SphStatistics*>(e->d_statOut.p + headWords * (size_t)c), nullptr)))
+            return rc;
+    }
+    std::vector<SphStatistics> st((size_t)e->scK);
+    HIP_TRY(hipMemcpyAsync(st.data(), e->d_statOut.p, sizeof(SphStatistics) * (size_t)e->scK, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int c = 0; c < e->scK; ++c) {
+        out[c].count = st[c].numCounted;
+        out[c].sum = st[c].sumPos[0];
+        out[c].sumSquares = st[c].sumDensity2;
+        out[c].min = st[c].minPos[0];
+        out[c].max = st[c].maxPos[0];
+    }
+    return SPH_OK;
+}
+
+int sph_scalars_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, int channel, float* devOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (m && (!devPoints4 || !devOut)) return fail(SPH_ERR_ARG, "null argument");
+    if (m > (size_t)1 << 40) return fail(SPH_ERR_ARG, "%zu probes", m);
+    SimK k;
+    int rc;
+    if ((rc = scalars_sample_grid(e, channel, k))) return rc;
+    if (m) {
+        Timed t(e, SPH_K_OTHER);
+        const float4* pts = reinterpret_cast<const float4*>(devPoints4);
+        const dim3 grid(blocks_for(m)), block(kBlock);
+        switch (e->scK) {
+        case 1: hipLaunchKernelGGL((k_scalar_sample_points<1>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, pts, devOut, m); break;
+        case 2: hipLaunchKernelGGL((k_scalar_sample_points<2>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, pts, devOut, m); break;
+        case 3: hipLaunchKernelGGL((k_scalar_sample_points<3>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, pts, devOut, m); break;
+        default: hipLaunchKernelGGL((k_scalar_sample_points<4>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, pts, devOut, m); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_scalars_sample_points(SphEngine* e, const float* points4, size_t m, int channel, float* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (m && (!points4 || !out)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = scalars_refused(e))) return rc;
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    if (channel < 0 || channel >= e->scK) return fail(SPH_ERR_ARG, "channel %d of %d", channel, e->scK);
+    if (m && ((rc = e->d_sampleIn.grow(e, m)) || (rc = e->d_scSampleOut.grow(e, m)))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = sph_scalars_sample_points_device(e, reinterpret_cast<const float*>(e->d_sampleIn.p), m, channel, e->d_scSampleOut.p))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(out, e->d_scSampleOut.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_scalars_sample_lattice(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int channel, float* devOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!origin || !spacing || !dims || !devOut) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    int rc;
+    long long total = 0;
+    if ((rc = check_lattice(dims, spacing, 1, &total)) || (rc = scalars_sample_grid(e, channel, k))) return rc;
+    {
+        Timed t(e, SPH_K_OTHER);
+        const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 1ll << 20)), block(kBlock);
+        switch (e->scK) {
+        case 1: hipLaunchKernelGGL((k_scalar_sample_lattice<1>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, origin[0], origin[1], origin[2], spacing[0], spacing[1], spacing[2], dims[0], dims[1], total, devOut); break;
+        case 2: hipLaunchKernelGGL((k_scalar_sample_lattice<2>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, origin[0], origin[1], origin[2], spacing[0], spacing[1], spacing[2], dims[0], dims[1], total, devOut); break;
+        case 3: hipLaunchKernelGGL((k_scalar_sample_lattice<3>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, origin[0], origin[1], origin[2], spacing[0], spacing[1], spacing[2], dims[0], dims[1], total, devOut); break;
+        default: hipLaunchKernelGGL((k_scalar_sample_lattice<4>), grid, block, 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, channel, origin[0], origin[1], origin[2], spacing[0], spacing[1], spacing[2], dims[0], dims[1], total, devOut); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_scalars_step_host(const SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels, const float* coeffs,
+                          float* maxNumberOut) {
+    if (!params || (n && (!particles || !values))) return fail(SPH_ERR_ARG, "null argument");
+    if (channels < 1 || channels > SPH_MAX_SCALAR_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (1 .. %d)", channels, SPH_MAX_SCALAR_CHANNELS);
+    int rc;
+    if ((rc = scalars_check_coeffs(coeffs, channels)) || (rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    const float step = dt > 0.0f ? dt : params->param_timeStep;
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, step, k);
+    sph::ScalarCoef co;
+    sph::scalar_make_coef(channels, coeffs, co);
+    const float kLap = sph::scalar_klap(params->param_mass, params->param_h);
+    float mx = 0.0f;
+    if (!params->param_pause) {
+        switch (channels) {
+        case 1: mx = scalars_step_loop<1>(k, kLap, step, co, particles, n, values); break;
+        case 2: mx = scalars_step_loop<2>(k, kLap, step, co, particles, n, values); break;
+        case 3: mx = scalars_step_loop<3>(k, kLap, step, co, particles, n, values); break;
+        default: mx = scalars_step_loop<4>(k, kLap, step, co, particles, n, values); break;
+        }
+    }
+    if (maxNumberOut) *maxNumberOut = mx;
     return SPH_OK;
 }
 

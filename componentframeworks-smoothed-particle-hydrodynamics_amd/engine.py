@@ -80,6 +80,7 @@ class SphRiver(C.Structure):
 SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_GRID_BUILD, SPH_OPT_AOS_MODE, SPH_OPT_TIMING, SPH_OPT_DEBUG = 1, 2, 3, 4, 100
 SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = 5, 6
 SPH_OPT_MESH_SPLIT = 7
+SPH_OPT_SCALAR_SWEEP = 8
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -151,6 +152,18 @@ assert C.sizeof(SphTracer) == 32
 TRACER_DTYPE = np.dtype(SphTracer)
 assert TRACER_DTYPE.itemsize == 32
 SPH_TRACER_EULER, SPH_TRACER_MIDPOINT = 0, 1
+
+
+SPH_MAX_SCALAR_CHANNELS = 4
+SPH_SCALAR_SET, SPH_SCALAR_ADD = 0, 1
+
+
+class SphScalarMoments(C.Structure):
+    """struct SphScalarMoments of include/sph_abi.h: count, fp64 sum and sum of squares, extrema of one scalar channel."""
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_double), ("sumSquares", C.c_double), ("min", SphStatExtremum), ("max", SphStatExtremum)]
+
+
+assert C.sizeof(SphScalarMoments) == 40
 
 
 class SphObstacle(C.Structure):
@@ -271,6 +284,20 @@ _ABI = {
     "sph_tracers_download": (_int, [_vp, _vp, _sz]),
     "sph_tracers_device": (_int, [_vp, _P(_vp)]),
     "sph_tracers_history": (_int, [_vp, _vp, _sz, _P(_u32), _P(_u64)]),
+    # diffusing scalar fields
+    "sph_scalars_set": (_int, [_vp, _vp, _sz, _int, _pf]),
+    "sph_scalars_set_device": (_int, [_vp, _vp, _sz, _int, _pf]),
+    "sph_scalars_set_coefficients": (_int, [_vp, _pf]),
+    "sph_scalars_channels": (_int, [_vp]),
+    "sph_scalars_download": (_int, [_vp, _vp, _sz]),
+    "sph_scalars_device": (_int, [_vp, _P(_vp)]),
+    "sph_scalars_paint": (_int, [_vp, _pf, _f, _int, _f, _int]),
+    "sph_scalars_info": (_int, [_vp, _P(_u64), _pf]),
+    "sph_scalars_moments": (_int, [_vp, _vp]),
+    "sph_scalars_sample_points": (_int, [_vp, _vp, _sz, _int, _vp]),
+    "sph_scalars_sample_points_device": (_int, [_vp, _vp, _sz, _int, _vp]),
+    "sph_scalars_sample_lattice": (_int, [_vp, _pf, _pf, _pi, _int, _vp]),
+    "sph_scalars_step_host": (_int, [_vp, _sz, _pp, _f, _vp, _int, _pf, _pf]),
     # kinematic solid obstacles
     "sph_obstacle_default": (None, [_vp]),
     "sph_obstacles_set": (_int, [_vp, _vp, _int]),
@@ -461,6 +488,49 @@ def _histogram_specs(histograms):
 
 
 # ---- free helpers: records and results ------------------------------------------------------------------------------------
+def _scalar_coeffs(channels: int, diffusivity, decay):
+    """2 K float32: D_0 .. D_{K-1}, lambda_0 .. lambda_{K-1} (a scalar is every channel's value)."""
+    k = int(channels)
+    return np.concatenate([np.broadcast_to(np.asarray(diffusivity, np.float32), (k,)), np.broadcast_to(np.asarray(decay, np.float32), (k,))]).astype(np.float32)
+
+
+def _scalar_values(values, n=None):
+    """(n, K) float32 from (n,) or (n, K) values."""
+    v = np.ascontiguousarray(values, np.float32)
+    if v.ndim == 1:
+        v = v.reshape(-1, 1)
+    if v.ndim != 2 or (n is not None and len(v) != n):
+        raise SphError(f"scalar values must have shape (n,) or (n, K){'' if n is None else f' with n = {n}'}, not {v.shape}")
+    return v
+
+
+class ScalarMoments:
+    """sph_scalars_moments of one channel plus what follows from it.  Attributes: count, sum, sum_squares, min, max (value, id)."""
+
+    def __init__(self, m: SphScalarMoments):
+        self.count, self.sum, self.sum_squares = int(m.count), float(m.sum), float(m.sumSquares)
+        self.min, self.max = (np.float32(m.min.value), int(m.min.id)), (np.float32(m.max.value), int(m.max.id))
+
+    @property
+    def mean(self) -> float:
+        return self.sum / self.count if self.count else 0.0
+
+    @property
+    def variance(self) -> float:
+        """sum_squares / count - mean^2, not below 0."""
+        return max(self.sum_squares / self.count - self.mean ** 2, 0.0) if self.count else 0.0
+
+    def mixing_index(self, initial_variance: float) -> float:
+        """1 - variance / initial_variance: 0 for the unmixed state the variance was taken from, 1 when uniform."""
+        return mixing_index(self.variance, initial_variance)
+
+
+def mixing_index(variance: float, initial_variance: float) -> float:
+    if not initial_variance > 0.0:
+        raise SphError(f"mixing_index: the initial variance must be > 0, not {initial_variance}")
+    return 1.0 - float(variance) / float(initial_variance)
+
+
 class Statistics:
     """Result of SPHFluidGPU.statistics(): `s` is the SphStatistics struct (its members are also attributes of this object),
     `histograms` a list of uint64 arrays of bins + 2 slots (below lo, the bins, at or above hi) in spec order.  The derived numbers
@@ -1019,6 +1089,94 @@ class SPHFluidGPU:
         _check(self._L.sph_tracers_history(self._h, _ptr(out), out.shape[0], C.byref(cnt), C.byref(first)))
         return int(first.value), out[:cnt.value]
 
+    # -- diffusing scalar fields (include/sph_abi.h "diffusing scalar fields") --
+    def set_scalars(self, values=None, diffusivity=0.0, decay=0.0, channels: int | None = None):
+        """(n,) or (n, K) values replace the engine's scalar channels; values=None seeds channel 0 from padB of the records (the
+        reference's dye) and the others with 0 (`channels`, default 1).  diffusivity / decay: one number or K of them.  Synchronises."""
+        if values is None:
+            k = 1 if channels is None else int(channels)
+            co = _scalar_coeffs(max(k, 1), diffusivity, decay)
+            _check(self._L.sph_scalars_set(self._h, None, self.numParticles, k, co.ctypes.data_as(_pf)))
+            return
+        v = _scalar_values(values)
+        co = _scalar_coeffs(max(v.shape[1], 1), diffusivity, decay)
+        _check(self._L.sph_scalars_set(self._h, _ptr(v), len(v), v.shape[1], co.ctypes.data_as(_pf)))
+
+    def set_scalars_device(self, dev_values: int, n: int, channels: int, diffusivity=0.0, decay=0.0):
+        """The same from a device address of n * channels floats, asynchronous on the engine's stream."""
+        co = _scalar_coeffs(max(int(channels), 1), diffusivity, decay)
+        _check(self._L.sph_scalars_set_device(self._h, C.c_void_p(dev_values), int(n), int(channels), co.ctypes.data_as(_pf)))
+
+    def set_scalar_coefficients(self, diffusivity=0.0, decay=0.0):
+        """New D_k and lambda_k for the current channels, stream-ordered (replayed graphs see them)."""
+        co = _scalar_coeffs(max(self.num_scalar_channels(), 1), diffusivity, decay)
+        _check(self._L.sph_scalars_set_coefficients(self._h, co.ctypes.data_as(_pf)))
+
+    def clear_scalars(self):
+        _check(self._L.sph_scalars_set(self._h, None, 0, 0, None))
+
+    def num_scalar_channels(self) -> int:
+        return int(self._L.sph_scalars_channels(self._h))
+
+    def scalars(self) -> np.ndarray:
+        """The values in the caller's order, shape (n, K) float32.  Synchronises."""
+        k = self.num_scalar_channels()
+        out = np.zeros((self.numParticles if k else 0, k), np.float32)
+        _check(self._L.sph_scalars_download(self._h, _ptr(out), out.size))
+        return out
+
+    def scalars_device(self) -> int:
+        """Borrowed device address of the n * K floats (0 without scalars); valid until the next dispatch, set, reset or close."""
+        p = C.c_void_p()
+        _check(self._L.sph_scalars_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def paint_scalar(self, center, radius: float, value: float, channel: int = 0, mode: int = SPH_SCALAR_SET):
+        """channel = value (SPH_SCALAR_SET) or += value (SPH_SCALAR_ADD) for every non-ghost particle strictly inside the sphere."""
+        _check(self._L.sph_scalars_paint(self._h, _f3(center), float(radius), int(channel), float(value), int(mode)))
+
+    def scalar_info(self):
+        """(substeps stepped since set_scalars, diffusion number of the last one).  Synchronises."""
+        c, s = C.c_uint64(), C.c_float()
+        _check(self._L.sph_scalars_info(self._h, C.byref(c), C.byref(s)))
+        return int(c.value), np.float32(s.value)
+
+    def scalar_moments(self):
+        """One ScalarMoments per channel (count, fp64 sums in the statistics' fixed order, extrema with ids).  Synchronises."""
+        out = (SphScalarMoments * SPH_MAX_SCALAR_CHANNELS)()
+        self._push_params()
+        _check(self._L.sph_scalars_moments(self._h, C.byref(out)))
+        return [ScalarMoments(out[k]) for k in range(self.num_scalar_channels())]
+
+    def sample_scalar(self, points, channel: int = 0) -> np.ndarray:
+        """Shepard value of a channel at (m, 3) or (m, 4) probe points: (m,) float32.  Synchronises."""
+        p4 = _points4(points, "sample_scalar", keep_w=False)
+        out = np.zeros(len(p4), np.float32)
+        self._push_params()
+        _check(self._L.sph_scalars_sample_points(self._h, _ptr(p4), len(p4), int(channel), _ptr(out)))
+        return out
+
+    def sample_scalar_device(self, dev_points: int, m: int, dev_out: int, channel: int = 0):
+        self._push_params()
+        _check(self._L.sph_scalars_sample_points_device(self._h, C.c_void_p(dev_points), int(m), int(channel), C.c_void_p(dev_out)))
+
+    def scalar_lattice_device(self, origin, spacing, dims, dev_out: int, channel: int = 0):
+        """Shepard value of a channel on the lattice origin + i * spacing (x fastest) into a device buffer of one float per point; it
+        feeds extract_surface_volume / surface_from_volume unchanged.  Asynchronous on the engine's stream."""
+        self._push_params()
+        _check(self._L.sph_scalars_sample_lattice(self._h, _f3(origin), _f3(_spacing3(spacing)), _dims3(dims, "scalar_lattice"), int(channel),
+                                                  C.c_void_p(dev_out)))
+
+    def scalar_lattice(self, origin, spacing, dims, channel: int = 0, device: bool = False):
+        """scalar_lattice_device into a fresh torch CUDA tensor of shape (nz, ny, nx); device=False returns its host copy (numpy)."""
+        import torch
+        nx, ny, nz = (int(x) for x in dims)
+        _dims3(dims, "scalar_lattice")
+        buf = torch.empty((nz, ny, nx), dtype=torch.float32, device="cuda")
+        self.scalar_lattice_device(origin, spacing, (nx, ny, nz), buf.data_ptr(), channel)
+        self.sync()
+        return buf if device else buf.cpu().numpy()
+
     # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
     def set_obstacles(self, obstacles):
         """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
@@ -1334,6 +1492,16 @@ def obstacles_step_host(obstacles, records, impulses, params, dt: float) -> np.n
     _check(load_library().sph_obstacles_step_host(_ptr_or_none(arr), _ptr_or_none(dyn), len(arr), None if imp is None else _ptr_or_none(imp),
                                                   C.byref(params), float(dt)))
     return arr
+
+
+def scalars_step_host(particles: np.ndarray, params: SphParams, values, diffusivity=0.0, decay=0.0, dt: float = -1.0):
+    """sph_scalars_step_host on a copy of the values: ((n, K) values one substep later, the diffusion number).  No device is needed."""
+    rec = np.ascontiguousarray(particles, PARTICLE_DTYPE)
+    v = _scalar_values(values, len(rec)).copy()
+    co = _scalar_coeffs(max(v.shape[1], 1), diffusivity, decay)
+    s = C.c_float()
+    _check(load_library().sph_scalars_step_host(_ptr(rec), len(rec), C.byref(params), float(dt), _ptr(v), v.shape[1], co.ctypes.data_as(_pf), C.byref(s)))
+    return v, np.float32(s.value)
 
 
 def volume_moments_host(values, spacing) -> np.ndarray:

@@ -238,6 +238,50 @@ public:
         out4.resize(size_t(n) * sph_tracers_count(engine));
         return !Check(sph_tracers_history(engine, out4.empty() ? nullptr : &out4[0].x, n, &snapshots, &firstSnapshot), "sph_tracers_history");
     }
+    // Diffusing scalar channels (engine extension, sph_abi.h "diffusing scalar fields"): K <= SPH_MAX_SCALAR_CHANNELS
+    // floats per particle, particle-major in the caller's order, that move with their particles and diffuse between neighbours inside
+    // every substep from now on.  values empty: channel 0 is seeded from padB (the dye), the others with 0; channels == 0 drops the set.
+    // coeffs: D_0 .. D_{K-1}, then lambda_0 .. lambda_{K-1}.  ScalarMoments and SampleScalarLattice push the members first, as
+    // DispatchCompute does.  Return false on error (LastError()).
+    bool SetScalars(const std::vector<float>& values, int channels, const std::vector<float>& coeffs) {
+        if (channels > 0 && coeffs.size() != size_t(2 * channels)) { lastError = "SetScalars: coeffs must hold 2 * channels floats"; return false; }
+        if (!values.empty() && values.size() != sph_num_particles(engine) * size_t(channels)) { lastError = "SetScalars: values must hold numParticles * channels floats"; return false; }
+        return !Check(sph_scalars_set(engine, values.empty() ? nullptr : values.data(), sph_num_particles(engine), channels, coeffs.empty() ? nullptr : coeffs.data()),
+                      "sph_scalars_set");
+    }
+    bool SetScalarCoefficients(const std::vector<float>& coeffs) {
+        if (coeffs.size() != size_t(2 * sph_scalars_channels(engine))) { lastError = "SetScalarCoefficients: coeffs must hold 2 * channels floats"; return false; }
+        return !Check(sph_scalars_set_coefficients(engine, coeffs.data()), "sph_scalars_set_coefficients");
+    }
+    int NumScalarChannels() const { return sph_scalars_channels(engine); }
+    bool DownloadScalars(std::vector<float>& out) {
+        out.resize(sph_num_particles(engine) * size_t(sph_scalars_channels(engine)));
+        return !Check(sph_scalars_download(engine, out.empty() ? nullptr : out.data(), out.size()), "sph_scalars_download");
+    }
+    bool PaintScalar(const MATH::Vec3& center, float radius, int channel, float value, int mode = SPH_SCALAR_SET) {
+        const float c[3] = {center.x, center.y, center.z};
+        return !Check(sph_scalars_paint(engine, c, radius, channel, value, mode), "sph_scalars_paint");
+    }
+    bool ScalarMoments(std::vector<SphScalarMoments>& out) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        out.assign(SPH_MAX_SCALAR_CHANNELS, SphScalarMoments{});
+        if (Check(sph_scalars_moments(engine, out.data()), "sph_scalars_moments")) return false;
+        out.resize(size_t(sph_scalars_channels(engine)));
+        return true;
+    }
+    static double ScalarVariance(const SphScalarMoments& m) {
+        if (!m.count) return 0.0;
+        const double mean = m.sum / double(m.count), v = m.sumSquares / double(m.count) - mean * mean;
+        return v > 0.0 ? v : 0.0;
+    }
+    bool ScalarInfo(uint64_t& substeps, float& maxNumber) { return !Check(sph_scalars_info(engine, &substeps, &maxNumber), "sph_scalars_info"); }
+    bool SampleScalarLattice(const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], int channel, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        return !Check(sph_scalars_sample_lattice(engine, o, s, dims, channel, devOut), "sph_scalars_sample_lattice");
+    }
     // Kinematic solid obstacles (engine extension, sph_abi.h "obstacles"): up to SPH_MAX_OBSTACLES bodies whose
     // motion the caller prescribes; every substep keeps the fluid out of them, advances their poses on the device and sums, per body,
     // the impulse (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave it.  An empty vector drops the set.  SetObstacleMotion keeps the device's pose

@@ -35,6 +35,8 @@ extern "C" {
 /* (still 4, additions only: SphSurfaceVertex, SphSurface, sph_extract_surface / sph_extract_surface_volume / sph_surface_download -- iso-surface meshes) */
 /* (still 4, additions only: SphStatistics, SphStatExtremum, SphHistogramSpec, SPH_STAT_*, sph_statistics / sph_statistics_device -- state statistics) */
 /* (still 4, additions only: SphTracer, SPH_TRACER_*, sph_tracers_set / _set_device / _count / _info / _download / _device / _history -- passive tracers) */
+/* (still 4, additions only: SPH_MAX_SCALAR_CHANNELS, SPH_SCALAR_*, sph_scalars_set / _set_device / _set_coefficients / _channels / _download / _device /
+    _paint / _info / _moments / _sample_points / _sample_points_device / _sample_lattice / _step_host, SphScalarMoments, SPH_OPT_SCALAR_SWEEP -- diffusing scalar fields carried by the particles) */
 /* (still 4, additions only: SphObstacle, SPH_OBSTACLE_*, SPH_MAX_OBSTACLES, sph_obstacle_default, sph_obstacles_set / _set_motion / _get / _impulses /
     _apply_host / _advance_host -- kinematic solid obstacles) */
 /* (still 4, additions only: SphVolumeHost, SPH_MAX_VOLUMES, SPH_OPT_MESH_SPLIT, sph_volume_create / _destroy / _info / _sample_host / _from_mesh,
@@ -143,6 +145,7 @@ enum {
     SPH_OPT_AOS_MODE = 3,        /* 1 = lazy (default): the substep keeps its state in the engine's own arrays and the 80-byte records are brought up to date by sph_device_particles() / sph_download_particles() / sph_pack_render_buffer(), i.e. once per rendered frame instead of once per substep (the scattered 52-byte update of every record costs about 13 % of the SPH pass); 0 = eager: the SPH pass also updates the records, they are current after every dispatch. Same values either way. */
     SPH_OPT_GRAPH = 5,           /* 1 = sph_dispatch_n replays a hipGraph once the same call (same members, options, substep count) has been seen twice; default 0 */
     SPH_OPT_MESH_SPLIT = 7,      /* sph_mesh_distance: 0 = the engine chooses into how many ranges the triangles are split (default), 1..64 = that many (capped at one per 256 triangles); same bits */
+    SPH_OPT_SCALAR_SWEEP = 8,    /* scalar channels (sph_scalars_*): 0 = the sweep walks global memory (default, the bit-level yardstick), 1 = a block of 256 consecutive slots stages its candidate rows in LDS first; same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -427,6 +430,86 @@ int sph_tracers_device(SphEngine* e, const SphTracer** devPtr);
 /* The stored snapshots, oldest first, to HOST memory: snapshotCap * m * 4 floats (snapshotCap >= the stored count, else
  * SPH_ERR_CAPACITY).  SPH_ERR_STATE without a history (K == 0 or no tracers).  Synchronises. */
 int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t* snapshotsOut, uint64_t* firstSnapshotOut);
+
+/* ---- diffusing scalar fields carried by the particles: dye, heat (no reference counterpart) ----------------
+ * The engine holds K channels, 1 <= K <= SPH_MAX_SCALAR_CHANNELS, one fp32 each per particle, stored particle-major (c[i * K + k])
+ * in the caller's order: index i is the same particle forever, like the records.  A value moves with its particle for free and
+ * exchanges with the particle's neighbours through an SPH Laplacian (Brookshaw / Cleary-Monaghan with the spiky gradient the force
+ * sweep uses).  Channel k has a diffusivity D_k >= 0 and a decay rate lambda_k >= 0; `coeffs` is always 2 K floats,
+ * D_0 .. D_{K-1} and then lambda_0 .. lambda_{K-1}.
+ * One non-paused substep with time step dt (overrideDt if > 0, else param_timeStep) updates every target i from the state the
+ * substep STARTS from -- the sorted copy (x, y, z, 1/rho) the tracers and the SPH pass read; 1/rho = 0 for a record with density <= 0:
+ *   targets      records with isGhost == 0, finite position and 1/rho_i > 0; every other record keeps its values bit for bit.  Ghost
+ *                records are neither targets nor candidates (the gather step gives them the weight 0), so the exchange is conservative.
+ *   candidates   those of a probe of sph_sample_points at x_i: the clamped cell of x_i, 9 rows in (dz, dy) order, slots ascending
+ *                (members of a cell ascending by index); particle i itself is skipped.
+ *   pairs        those with 0 < r2 < h2 and 1/rho_j > 0, r2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) of d = x_i - x_j, h2 = h * h.
+ *   weight       r = sqrtf(r2); u = h - r; G = ((u * u) * r) / (r2 + 0.01f * h2); w = ((1/rho_i) * (1/rho_j)) * G   (bitwise symmetric in i, j)
+ *   sums         a_k = fmaf(w, c_jk - c_ik, a_k); W = W + w          (both start at +0, candidates in the order above)
+ *   finish       kLap = (float)(90 m / (pi ((h^2 h^2) h^2))) with m = param_mass, h = param_h, in double;
+ *                c_ik' = c_ik + dt * (((D_k * kLap) * a_k) - (lambda_k * c_ik))      (fp32 multiplies and adds, no fma)
+ *   number       s_i = (dt * (Dmax * kLap)) * W with Dmax = max_k D_k.  The engine keeps the maximum of s_i over the targets of the last
+ *                substep, taken on the float's bits (non-negative floats order as unsigned integers), so it does not depend on launch
+ *                shape.  Explicit Euler keeps a maximum principle only while s_i + dt lambda_k <= 1; the engine reports, it does not clamp.
+ * Records whose density is <= 0 (before their first substep) have 1/rho = 0: nothing diffuses during the FIRST substep on such a
+ * state, as tracers do not move then.  D is the operator's nominal coefficient.  The weight carries 1 / (rho_i rho_j), so D is rho times
+ * a diffusivity (Cleary-Monaghan's conductivity over heat capacity): a long mode of wave number k decays at f (D / rho) k^2, and the
+ * factor f depends on the neighbours per support (0.92 on a cubic lattice of spacing h / 2, 0.30 at 0.85 h).
+ * Recycled particles (fountain, river) keep their values.  param_pause: no step.  sph_upload_particles, impulses and sph_set_params do
+ * not touch scalars (kLap follows param_mass and param_h of the dispatch); sph_reset drops them, sph_destroy frees them.  The particle
+ * records are byte-identical with and without scalars, padB included; with no scalars set a dispatch launches exactly what it launched
+ * before.  The step runs behind the substep's own grid build as two launches (gather, sweep), under sph_dispatch_n and inside its
+ * captured graphs, timed as SPH_K_OTHER.  Set, drop and the channel count enter a graph's key; the coefficients live in device memory,
+ * so a replayed graph sees a later sph_scalars_set_coefficients.
+ * SPH_ERR_STATE from the set calls, before anything is allocated, on z-slab engines and under SPH_OPT_GRID_BUILD 1; setting
+ * SPH_OPT_GRID_BUILD 1 while scalars exist makes the next dispatch fail with SPH_ERR_STATE and change nothing.  SPH_ERR_ARG (the
+ * previous state stays): a null pointer where data is required, n != sph_num_particles, K outside 1 .. 4, a non-finite or negative
+ * coefficient, a channel out of range, an unknown mode, a radius that is not finite and > 0. */
+#define SPH_MAX_SCALAR_CHANNELS 4
+enum { SPH_SCALAR_SET = 0, SPH_SCALAR_ADD = 1 };
+/* n * channels floats in HOST memory replace the engine's scalar set; channels == 0 drops it (values, coeffs ignored).  values == NULL
+ * seeds channel 0 from padB of the current records (the reference's dye) and the other channels with 0.  Synchronises. */
+int sph_scalars_set(SphEngine* e, const float* values, size_t n, int channels, const float* coeffs);
+/* The same from a DEVICE array (`coeffs` stays a host array), asynchronous on the engine's stream. */
+int sph_scalars_set_device(SphEngine* e, const float* devValues, size_t n, int channels, const float* coeffs);
+/* New D_k and lambda_k for the current channels, stream-ordered: substeps enqueued later, replayed graphs included, use them. */
+int sph_scalars_set_coefficients(SphEngine* e, const float* coeffs);
+int sph_scalars_channels(const SphEngine* e);
+/* n * K floats in the caller's order to HOST memory (cap >= n * K floats, else SPH_ERR_CAPACITY, nothing written).  Synchronises. */
+int sph_scalars_download(SphEngine* e, float* out, size_t cap);
+/* Borrowed DEVICE pointer to the n * K floats (NULL without scalars), valid until the next dispatch, set, reset or destroy; no synchronisation. */
+int sph_scalars_device(SphEngine* e, const float** devPtr);
+/* The dye injector and the heat source: channel = value (SPH_SCALAR_SET) or channel += value (SPH_SCALAR_ADD, one fp32 add) for every
+ * non-ghost record whose CURRENT position lies strictly inside the sphere: fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < radius * radius with
+ * d = x - center (a particle exactly on the sphere is not inside, nor is one with a non-finite coordinate).  One per-particle kernel on
+ * the engine's own state arrays, stream-ordered; no record is materialised. */
+int sph_scalars_paint(SphEngine* e, const float center[3], float radius, int channel, float value, int mode);
+/* The substeps stepped since the set call and the diffusion number of the last one (0 before the first); either pointer may be null.
+ * Synchronises when the number is asked for. */
+int sph_scalars_info(SphEngine* e, uint64_t* substepsOut, float* maxNumberOut);
+/* Per channel over the targets of the state the next dispatch would start from (non-ghost, finite position, density > 0) whose value is
+ * finite: count, fp64 sum and sum of squares (each value converted to fp64 first, the square one exact fp64 product) in the FIXED order
+ * of sph_statistics (slots in canonical order, tiles of 2048 by pairwise halving, the tile sums by the same halving), and the extrema
+ * with the lowest id among equals (empty set: +inf, -inf, id 0xFFFFFFFF).  It is the statistics reduction run over each channel, behind a
+ * grid build of the current state; K records to HOST memory.  Synchronises. */
+typedef struct SphScalarMoments {
+    uint64_t count;
+    double sum, sumSquares;
+    SphStatExtremum min, max;
+} SphScalarMoments;                /* 40 bytes */
+int sph_scalars_moments(SphEngine* e, SphScalarMoments* out);
+/* Shepard value of one channel, sum w_j c_jk / sum w_j, with the w_j = ((t t) t) (1/rho_j), the candidates and the order of
+ * sph_sample_points (num = fmaf(w_j, c_jk, num), wsum = wsum + w_j, one IEEE division): 0 where sum w_j = 0 and for a non-finite point.
+ * m points of 4 floats (x, y, z, unused) -> m floats.  Host arrays: synchronises.  Device arrays: asynchronous on the engine's stream. */
+int sph_scalars_sample_points(SphEngine* e, const float* points4, size_t m, int channel, float* out);
+int sph_scalars_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, int channel, float* devOut);
+/* The same on the lattice origin + (float)i * spacing of sph_sample_lattice (x fastest) into a DEVICE array of one float per point: it
+ * feeds sph_extract_surface_volume unchanged (concentration iso-surfaces).  Asynchronous on the engine's stream. */
+int sph_scalars_sample_lattice(SphEngine* e, const float origin[3], const float spacing[3], const int dims[3], int channel, float* devOut);
+/* Host-only bit-level yardstick: one substep's scalar update of `values` (n * channels floats, in place) on the state `particles`, with
+ * the same pair and finish functions in plain loops over a grid built as the counting sort builds it.  dt <= 0: param_timeStep. */
+int sph_scalars_step_host(const SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels,
+                          const float* coeffs, float* maxNumberOut);
 
 /* ---- kinematic solid obstacles with fluid force and torque feedback (no reference counterpart) ----------
  * Up to SPH_MAX_OBSTACLES rigid bodies whose motion the caller prescribes.  Every substep, after the SPH pass and the container and
