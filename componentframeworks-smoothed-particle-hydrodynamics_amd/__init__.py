@@ -20,5 +20,7 @@ from .engine import (  # noqa: F401
     SPH_DYNAMICS_CONFINED, SphObstacleDynamics, DYNAMICS_DTYPE, dynamics, dynamics_sphere, dynamics_box, dynamics_capsule, dynamics_array,
     mass_properties, obstacles_step_host, volume_moments_host,
     SPH_MAX_SCALAR_CHANNELS, SPH_OPT_SCALAR_SWEEP, SPH_SCALAR_ADD, SPH_SCALAR_SET, ScalarMoments, SphScalarMoments, mixing_index, scalars_step_host,
+    SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_SPHERE, SPH_SOURCE_BOX, SPH_SOURCE_RATE, SPH_SOURCE_RELAX, SphScalarSource, SOURCE_DTYPE, scalar_source,
+    source_array, scalars_couple_host,
 )
 from . import build, synthetic  # noqa: F401

@@ -29,12 +29,15 @@
 #include "sph_obstacle.h"
 #include "sph_volume.h"
 #include "sph_stats.h"
+#include "sph_couple.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
 static_assert(sizeof(SphScalarMoments) == 40, "SphScalarMoments must be 40 bytes");
 static_assert(SPH_MAX_SCALAR_CHANNELS == sph::kScalarMax && SPH_SCALAR_SET == sph::kScalarSet && SPH_SCALAR_ADD == sph::kScalarAdd, "scalar constants of sph_abi.h and sph_scalar.h");
+static_assert(sizeof(SphScalarSource) == sizeof(sph::CoupleSrc) && SPH_MAX_SCALAR_SOURCES == sph::kCoupleMax && SPH_SOURCE_SPHERE == sph::COUPLE_SPHERE &&
+              SPH_SOURCE_BOX == sph::COUPLE_BOX && SPH_SOURCE_RATE == sph::COUPLE_RATE && SPH_SOURCE_RELAX == sph::COUPLE_RELAX, "SphScalarSource must be 64 bytes");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
 static_assert(sizeof(SphObstacleDynamics) == 80, "SphObstacleDynamics must be 80 bytes");
 static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
@@ -278,6 +281,15 @@ struct SphEngine {
     DevBuf<float4> d_scView;             // sph_scalars_moments: a channel laid out as the statistics kernels' input (3 float4 per slot)
     DevBuf<float2> d_scViewRp;
     DevBuf<float> d_scSampleOut;         // sph_scalars_sample_points (host arrays): device copy of the results
+    // sph_scalars_set_buoyancy / _set_sources (sph_couple.h): the table the kernel reads (device memory: a replayed
+    // graph sees a later change) with its host mirror and pinned staging, the books, and the per-block partial rows.  They belong to the
+    // scalar set: allocated by the first call that switches something on, freed with the channels.
+    sph::CoupleTab* d_cpTab = nullptr;
+    sph::CoupleAcc* d_cpAcc = nullptr;
+    double* d_cpPart = nullptr;
+    StageRing<sph::CoupleTab> cpStage;   // one table per slot
+    sph::CoupleTab cpTab{};              // host mirror of *d_cpTab
+    bool cpBuoy = false;                 // a beta is non-zero: the kick runs, and the pass does not keep the 80-byte array current
 
     // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
     // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
@@ -433,6 +445,10 @@ void scalars_free(SphEngine* e) {
     if (e->d_scVal && e->stream) (void)hipStreamSynchronize(e->stream);
     dev_free(e->d_scVal); dev_free(e->d_scSorted); dev_free(e->d_scCoef); dev_free(e->d_scState);
     e->scStage.destroy();
+    dev_free(e->d_cpTab); dev_free(e->d_cpAcc); dev_free(e->d_cpPart);
+    e->cpStage.destroy();
+    e->cpTab = sph::CoupleTab{};
+    e->cpBuoy = false;
     e->d_scView.release(); e->d_scViewRp.release(); e->d_scSampleOut.release();
     e->scK = 0; e->scN = 0; e->scSteps = 0;
 }
@@ -744,6 +760,33 @@ float scalars_step_loop(const SimK& k, float kLap, float dt, const sph::ScalarCo
     return mx;
 }
 
+// The coupling step on host records (arguments already checked): sources in order, then the kick, record by record in index order.
+template <int K>
+void couple_host_loop(const sph::CoupleTab& tab, bool buoy, const sph::ObsRec* recs, float dt, float gx, float gy, float gz, SphParticle* P, size_t n,
+                             float* values, double* sums, uint64_t* hits) {
+    for (size_t i = 0; i < n; ++i) {
+        SphParticle& p = P[i];
+        if (p.isGhost != 0 || !std::isfinite(p.pos[0]) || !std::isfinite(p.pos[1]) || !std::isfinite(p.pos[2])) continue;
+        float cv[K];
+        for (int k = 0; k < K; ++k) cv[k] = values[i * K + k];
+        for (int s = 0; s < tab.nSrc; ++s) {
+            const sph::CoupleSrc& S = tab.src[s];
+            if (!sph::couple_inside(S, S.body >= 0 ? recs + S.body : nullptr, p.pos[0], p.pos[1], p.pos[2])) continue;
+            const float old = cv[S.channel];
+            if (!std::isfinite(old)) continue;
+            const float now = sph::couple_apply(S, dt, old);
+            cv[S.channel] = now;
+            values[i * K + S.channel] = now;
+            sums[s] += (double)now - (double)old;
+            hits[s] += 1u;
+        }
+        if (buoy) {
+            float vx = p.vel[0], vy = p.vel[1], vz = p.vel[2];
+            if (sph::couple_kick<K>(tab.beta, tab.ref, cv, dt, gx, gy, gz, vx, vy, vz)) { p.vel[0] = vx; p.vel[1] = vy; p.vel[2] = vz; }
+        }
+    }
+}
+
 // ---- obstacles (sph_obstacle.h) -------------------------------------------------------------------
 // What obs_body_step needs of the parameters: gravity, the container's oriented box as the grid sees it, the wall restitution.
 void obstacle_world(const SphParams& p, sph::ObsWorld& W) {
@@ -770,6 +813,50 @@ int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
                                (const double*)e->d_obsPart, rows, e->d_obsAcc);
         } else
         hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+// ---- active scalars (sph_couple.h) -------------------------------------------------------------------
+// A source bound to a body the obstacle set does not have: the dispatch is refused before anything is enqueued.
+int couple_refused(const SphEngine* e) {
+    for (int i = 0; i < e->cpTab.nSrc; ++i)
+        if (e->cpTab.src[i].body >= e->obsK)
+            return fail(SPH_ERR_STATE, "scalar source %d rides on obstacle %d, the set has %d", i, e->cpTab.src[i].body, e->obsK);
+    return SPH_OK;
+}
+template <int K>
+void couple_launch(SphEngine* e, int rows, bool src, float4* pos, float4* vel, int n, float dt) {
+    const SphParams& p = e->params;
+    const dim3 grid(rows), block(kObsBlock);
+    const CoupleTab* tab = e->d_cpTab;
+    const ObsRec* bodies = e->d_obs;
+    if (src && e->cpBuoy)
+        hipLaunchKernelGGL((k_scalar_couple<K, true, true>), grid, block, 0, e->stream, tab, bodies, e->obsK, dt, p.param_gravityX, p.param_gravityY, p.param_gravityZ,
+                           (const float4*)pos, vel, e->d_scVal, e->idBase, n, e->d_cpPart);
+    else if (src)
+        hipLaunchKernelGGL((k_scalar_couple<K, true, false>), grid, block, 0, e->stream, tab, bodies, e->obsK, dt, p.param_gravityX, p.param_gravityY, p.param_gravityZ,
+                           (const float4*)pos, vel, e->d_scVal, e->idBase, n, e->d_cpPart);
+    else
+        hipLaunchKernelGGL((k_scalar_couple<K, false, true>), grid, block, 0, e->stream, tab, bodies, e->obsK, dt, p.param_gravityX, p.param_gravityY, p.param_gravityZ,
+                           (const float4*)pos, vel, e->d_scVal, e->idBase, n, e->d_cpPart);
+}
+// One substep's coupling step on the pass's output state: k_scalar_couple, then (with sources) the one-block finish of the books.
+int couple_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
+    const bool src = e->cpTab.nSrc > 0;
+    const int rows = n > 0 ? std::min(kObsGrid, blocks_for((size_t)n, kObsSweep)) : 0;
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (rows) {
+            switch (e->scK) {
+            case 1: couple_launch<1>(e, rows, src, pos, vel, n, dt); break;
+            case 2: couple_launch<2>(e, rows, src, pos, vel, n, dt); break;
+            case 3: couple_launch<3>(e, rows, src, pos, vel, n, dt); break;
+            default: couple_launch<4>(e, rows, src, pos, vel, n, dt); break;
+            }
+        }
+        if (src) hipLaunchKernelGGL(k_scalar_couple_finish, dim3(1), dim3(kCoupleFinishBlock), 0, e->stream, dt, (const double*)e->d_cpPart, rows, e->d_cpAcc);
     }
     HIP_TRY(hipGetLastError());
     return SPH_OK;
@@ -821,7 +908,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if (e->scK && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if ((rc = validate_params(e->params))) return rc;
+    if ((rc = validate_params(e->params)) || (rc = couple_refused(e))) return rc;
     float cont[15];
     container_key(e->params, cont);
     const bool sameContainer = std::memcmp(cont, e->lastContainer, sizeof(cont)) == 0;   // same walls and same grid as the dispatch before
@@ -844,7 +931,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     const int nx = e->cur ^ 1;
     if (k.obbDeferred && (rc = ensure_shape_table(e))) return rc;
     // the array is current: keep it current from the SPH pass (not when OBB runs as its own pass afterwards)
-    const bool fuseAos = !e->slab && e->optAos == 0 && e->aosValid && !k.obbDeferred && !e->obsK;   // (nor when obstacles act afterwards)
+    const bool fuseAos = !e->slab && e->optAos == 0 && e->aosValid && !k.obbDeferred && !e->obsK && !e->cpBuoy;   // (nor when obstacles or the buoyancy kick act afterwards)
     StateOut out{e->d_pos[nx], e->d_vel[nx], e->d_rp[nx], e->d_foam[nx], e->d_acc, fuseAos ? e->d_aos : nullptr, e->idBase};
     if (e->optGridBuild == 1) {
         // ---- A/B variant: the reference's atomicExchange linked lists (no sorting) ----
@@ -926,6 +1013,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
                            (e->slab && e->optGridBuild != 1) ? (const float4*)e->d_sOwn : (const float4*)nullptr);
     }
     if (e->obsK && (rc = obstacles_step(e, out.pos, out.vel, n, dt))) return rc;   // (after the container, before river / fountain)
+    if (e->scK && (e->cpBuoy || e->cpTab.nSrc) && (rc = couple_step(e, out.pos, out.vel, n, dt))) return rc;   // (sources, then buoyancy)
     const bool riverOn = e->river.riverMode && !e->terrainHeights.empty();   // :512
     if (riverOn) {                                                           // :511-516, DispatchTerrainConstraints / ChannelConstraint / StreamEmit
         if (e->slab) return fail(SPH_ERR_STATE, "riverMode on a z-slab engine: recycled particles jump across slabs (single-GPU engines only)");
@@ -1256,6 +1344,11 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     add(sc, sizeof(sc));
     add(&e->scK, sizeof(e->scK));
     add(&e->optScalarSweep, sizeof(e->optScalarSweep));
+    // active scalars: the buffers and which of the coupling kernels run; coefficients, sources and their count are read from memory
+    const void* cp[3] = {e->d_cpTab, e->d_cpAcc, e->d_cpPart};
+    add(cp, sizeof(cp));
+    const int cpWhat = (e->cpBuoy ? 1 : 0) | (e->cpTab.nSrc > 0 ? 2 : 0);
+    add(&cpWhat, sizeof(cpWhat));
     // obstacles: the buffers and the count (the kernels read the bodies from memory, so a later set / set_motion needs no new graph)
     const void* ob[3] = {e->d_obs, e->d_obsAcc, e->d_obsPart};
     add(ob, sizeof(ob));
@@ -1293,6 +1386,8 @@ int sph_dispatch_n(SphEngine* e, float overrideDt, int nSubsteps) {
         key = graph_hash(material);
         for (auto& g : e->graphs) if (g.key == key && g.material == material) { hit = &g; break; }
         if (hit && hit->exec) {
+            int crc;
+            if ((crc = couple_refused(e))) return crc;           // (a replay changes nothing either)
             sph::compute_grid_extents(e->params, e->grid);       // what an eager dispatch would have refreshed (sph_grid_info, RefreshGrid)
             if (e->trM) {                                        // the processing order is re-sorted between calls, never inside a graph
                 int trc;
@@ -2949,6 +3044,8 @@ static int scalars_check_set(SphEngine* e, size_t n, int channels, const float* 
     return scalars_check_coeffs(coeffs, channels);
 }
 
+static int couple_clear(SphEngine* e);
+
 int sph_scalars_set_device(SphEngine* e, const float* devValues, size_t n, int channels, const float* coeffs) {
     int rc;
     if ((rc = scalars_check_set(e, n, channels, coeffs))) return rc;
@@ -2967,7 +3064,7 @@ int sph_scalars_set_device(SphEngine* e, const float* devValues, size_t n, int c
     e->scK = channels;
     e->scSteps = 0;
     std::memcpy(e->scCoeffs, coeffs, sizeof(float) * 2 * (size_t)channels);
-    if ((rc = scalars_upload_coef(e))) return rc;
+    if ((rc = scalars_upload_coef(e)) || (rc = couple_clear(e))) return rc;   // (a new set starts without buoyancy and without sources)
     if (devValues) {
         if (n) HIP_TRY(hipMemcpyAsync(e->d_scVal, devValues, n * (size_t)channels * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
         hipLaunchKernelGGL(k_scalar_clear_state, dim3(1), dim3(64), 0, e->stream, e->d_scState);
@@ -3389,6 +3486,187 @@ int sph_obstacles_advance_host(SphObstacle* obs, int count, float dt) {
         obstacle_to_rec(obs[i], false, r);
         sph::obs_advance(r, dt);
         rec_to_obstacle(r, obs[i]);
+    }
+    return SPH_OK;
+}
+
+// ---- active scalars: buoyancy and continuous sources (sph_couple.h) ---------
+static int couple_precheck(SphEngine* e) {
+    int rc;
+    if ((rc = scalars_refused(e))) return rc;
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    return SPH_OK;
+}
+// The buffers, at the first call that switches something on.
+static int couple_ensure(SphEngine* e) {
+    if (e->d_cpTab) return SPH_OK;
+    int rc;
+    hipError_t er = hipSuccess;
+    if ((rc = dev_alloc(&e->d_cpTab, 1)) || (rc = dev_alloc(&e->d_cpAcc, 1)) || (rc = dev_alloc(&e->d_cpPart, (size_t)kObsGrid * kCoupleTerms)) ||
+        (er = e->cpStage.create(e->stream, 1)) != hipSuccess) {
+        dev_free(e->d_cpTab); dev_free(e->d_cpAcc); dev_free(e->d_cpPart);
+        e->cpStage.destroy();
+        return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the coupling table: %s", hipGetErrorString(er));
+    }
+    HIP_TRY(hipMemsetAsync(e->d_cpAcc, 0, sizeof(sph::CoupleAcc), e->stream));
+    return SPH_OK;
+}
+// The host mirror to the device, stream-ordered, through the next pinned staging slot.
+static int couple_upload(SphEngine* e) {
+    if (!e->d_cpTab) return SPH_OK;
+    int rc;
+    sph::CoupleTab* slot = nullptr;
+    if ((rc = e->cpStage.next(&slot))) return rc;
+    *slot = e->cpTab;
+    HIP_TRY(hipMemcpyAsync(e->d_cpTab, slot, sizeof(sph::CoupleTab), hipMemcpyHostToDevice, e->stream));
+    return e->cpStage.commit(e->stream);
+}
+static int couple_clear(SphEngine* e) {
+    e->cpTab = sph::CoupleTab{};
+    e->cpBuoy = false;
+    if (e->d_cpAcc) HIP_TRY(hipMemsetAsync(e->d_cpAcc, 0, sizeof(sph::CoupleAcc), e->stream));
+    return couple_upload(e);
+}
+static int couple_check_sources(const SphScalarSource* src, int count, int K) {
+    if (count < 0 || count > SPH_MAX_SCALAR_SOURCES) return fail(SPH_ERR_ARG, "source count %d outside 0..%d", count, SPH_MAX_SCALAR_SOURCES);
+    if (count && !src) return fail(SPH_ERR_ARG, "null argument");
+    for (int i = 0; i < count; ++i) {
+        const SphScalarSource& s = src[i];
+        if (s.shape != SPH_SOURCE_SPHERE && s.shape != SPH_SOURCE_BOX) return fail(SPH_ERR_ARG, "source %d: unknown shape %d", i, s.shape);
+        if (s.mode != SPH_SOURCE_RATE && s.mode != SPH_SOURCE_RELAX) return fail(SPH_ERR_ARG, "source %d: unknown mode %d", i, s.mode);
+        if (s.channel < 0 || s.channel >= K) return fail(SPH_ERR_ARG, "source %d: channel %d of %d", i, s.channel, K);
+        if (s.body < -1 || s.body >= SPH_MAX_OBSTACLES) return fail(SPH_ERR_ARG, "source %d: body %d outside -1..%d", i, s.body, SPH_MAX_OBSTACLES - 1);
+        if (!obs_all_finite(s.center, 3) || !obs_all_finite(s.size, 3) || !std::isfinite(s.rate) || !std::isfinite(s.target))
+            return fail(SPH_ERR_ARG, "source %d: a field is not finite", i);
+        const int used = s.shape == SPH_SOURCE_SPHERE ? 1 : 3;
+        for (int a = 0; a < used; ++a) if (!(s.size[a] > 0.0f)) return fail(SPH_ERR_ARG, "source %d: size[%d] = %g must be > 0", i, a, (double)s.size[a]);
+        if (s.rate < 0.0f) return fail(SPH_ERR_ARG, "source %d: rate %g must be >= 0", i, (double)s.rate);
+    }
+    return SPH_OK;
+}
+static int couple_check_buoyancy(const float* beta, const float* ref, int K) {
+    if ((beta == nullptr) != (ref == nullptr)) return fail(SPH_ERR_ARG, "null argument");
+    if (beta && (!obs_all_finite(beta, K) || !obs_all_finite(ref, K))) return fail(SPH_ERR_ARG, "a buoyancy coefficient or reference value is not finite");
+    return SPH_OK;
+}
+static void source_to_rec(const SphScalarSource& s, sph::CoupleSrc& r) {
+    std::memset(&r, 0, sizeof(r));
+    r.shape = s.shape; r.channel = s.channel; r.mode = s.mode; r.body = s.body;
+    for (int a = 0; a < 3; ++a) { r.center[a] = s.center[a]; r.size[a] = s.size[a]; }
+    r.rate = s.rate; r.target = s.target;
+}
+
+int sph_scalars_set_buoyancy(SphEngine* e, const float* beta, const float* ref) {
+    int rc;
+    if ((rc = couple_precheck(e)) || (rc = couple_check_buoyancy(beta, ref, e->scK))) return rc;
+    bool on = false;
+    for (int k = 0; beta && k < e->scK; ++k) on = on || beta[k] != 0.0f;
+    if (on && (rc = couple_ensure(e))) return rc;
+    for (int k = 0; k < sph::kScalarMax; ++k) {
+        e->cpTab.beta[k] = (beta && k < e->scK) ? beta[k] : 0.0f;
+        e->cpTab.ref[k] = (ref && k < e->scK) ? ref[k] : 0.0f;
+    }
+    e->cpBuoy = on;
+    return couple_upload(e);
+}
+
+int sph_scalars_get_buoyancy(SphEngine* e, float* beta, float* ref) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    for (int k = 0; k < e->scK; ++k) {
+        if (beta) beta[k] = e->cpTab.beta[k];
+        if (ref) ref[k] = e->cpTab.ref[k];
+    }
+    return SPH_OK;
+}
+
+void sph_scalar_source_default(SphScalarSource* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->shape = SPH_SOURCE_SPHERE;
+    out->mode = SPH_SOURCE_RATE;
+    out->body = -1;
+    out->size[0] = out->size[1] = out->size[2] = 1.0f;
+}
+
+int sph_scalars_set_sources(SphEngine* e, const SphScalarSource* sources, int count) {
+    int rc;
+    if ((rc = couple_precheck(e)) || (rc = couple_check_sources(sources, count, e->scK))) return rc;
+    if (count && (rc = couple_ensure(e))) return rc;
+    if (count != e->cpTab.nSrc && e->d_cpAcc) HIP_TRY(hipMemsetAsync(e->d_cpAcc, 0, sizeof(sph::CoupleAcc), e->stream));   // (another count: the books restart)
+    for (int i = 0; i < sph::kCoupleMax; ++i) {
+        if (i < count) source_to_rec(sources[i], e->cpTab.src[i]);
+        else std::memset(&e->cpTab.src[i], 0, sizeof(sph::CoupleSrc));
+    }
+    e->cpTab.nSrc = count;
+    return couple_upload(e);
+}
+
+int sph_scalars_get_sources(SphEngine* e, SphScalarSource* out, int cap, int* countOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    const int count = e->cpTab.nSrc;
+    if (cap < count) return fail(SPH_ERR_CAPACITY, "%d sources (capacity %d)", count, cap);
+    if (count && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (count) std::memcpy(out, e->cpTab.src, sizeof(SphScalarSource) * (size_t)count);
+    if (countOut) *countOut = count;
+    return SPH_OK;
+}
+
+int sph_scalars_injected(SphEngine* e, double* sums, uint64_t* hits, int cap, double* timeOut, uint64_t* substepsOut, int reset) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->scK) return fail(SPH_ERR_STATE, "no scalars: call sph_scalars_set first");
+    const int count = e->cpTab.nSrc;
+    if (cap < count) return fail(SPH_ERR_CAPACITY, "%d sources (capacity %d)", count, cap);
+    sph::CoupleAcc a;
+    std::memset(&a, 0, sizeof(a));
+    if (e->d_cpAcc) {
+        HIP_TRY(hipMemcpyAsync(&a, e->d_cpAcc, sizeof(a), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (reset) HIP_TRY(hipMemsetAsync(e->d_cpAcc, 0, sizeof(sph::CoupleAcc), e->stream));
+    }
+    for (int i = 0; i < count; ++i) {
+        if (sums) sums[i] = a.sum[i];
+        if (hits) hits[i] = a.hits[i];
+    }
+    if (timeOut) *timeOut = a.time;
+    if (substepsOut) *substepsOut = a.substeps;
+    return SPH_OK;
+}
+
+int sph_scalars_couple_host(SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels, const float* beta,
+                            const float* ref, const SphScalarSource* sources, int nSources, const SphObstacle* obstacles, int nObstacles,
+                            double* sumsOut, uint64_t* hitsOut) {
+    if (!params || (n && (!particles || !values))) return fail(SPH_ERR_ARG, "null argument");
+    if (channels < 1 || channels > SPH_MAX_SCALAR_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (1 .. %d)", channels, SPH_MAX_SCALAR_CHANNELS);
+    int rc;
+    if ((rc = couple_check_buoyancy(beta, ref, channels)) || (rc = couple_check_sources(sources, nSources, channels)) || (rc = obstacles_check(obstacles, nObstacles)))
+        return rc;
+    sph::CoupleTab tab{};
+    for (int k = 0; k < channels && beta; ++k) { tab.beta[k] = beta[k]; tab.ref[k] = ref[k]; }
+    tab.nSrc = nSources;
+    for (int i = 0; i < nSources; ++i) {
+        source_to_rec(sources[i], tab.src[i]);
+        if (sources[i].body >= nObstacles) return fail(SPH_ERR_STATE, "scalar source %d rides on obstacle %d, the set has %d", i, sources[i].body, nObstacles);
+    }
+    sph::ObsRec recs[kObsMax];
+    for (int i = 0; i < nObstacles; ++i) obstacle_to_rec(obstacles[i], false, recs[i]);
+    const float step = dt > 0.0f ? dt : params->param_timeStep;
+    double sums[sph::kCoupleMax] = {0.0};
+    uint64_t hits[sph::kCoupleMax] = {0};
+    if (!params->param_pause) {
+        const float gx = params->param_gravityX, gy = params->param_gravityY, gz = params->param_gravityZ;
+        const bool buoy = beta != nullptr;
+        switch (channels) {
+        case 1: couple_host_loop<1>(tab, buoy, recs, step, gx, gy, gz, particles, n, values, sums, hits); break;
+        case 2: couple_host_loop<2>(tab, buoy, recs, step, gx, gy, gz, particles, n, values, sums, hits); break;
+        case 3: couple_host_loop<3>(tab, buoy, recs, step, gx, gy, gz, particles, n, values, sums, hits); break;
+        default: couple_host_loop<4>(tab, buoy, recs, step, gx, gy, gz, particles, n, values, sums, hits); break;
+        }
+    }
+    for (int i = 0; i < nSources; ++i) {
+        if (sumsOut) sumsOut[i] = sums[i];
+        if (hitsOut) hitsOut[i] = hits[i];
     }
     return SPH_OK;
 }

@@ -201,6 +201,21 @@ assert DYNAMICS_DTYPE.itemsize == 80
 SPH_DYNAMICS_CONFINED = 1
 
 
+class SphScalarSource(C.Structure):
+    """struct SphScalarSource of include/sph_abi.h: one continuous source or sink of a scalar channel (see scalar_source() and
+    SPHFluidGPU.set_scalar_sources)."""
+    _fields_ = [("shape", C.c_int32), ("channel", C.c_int32), ("mode", C.c_int32), ("body", C.c_int32), ("center", C.c_float * 3),
+                ("size", C.c_float * 3), ("rate", C.c_float), ("target", C.c_float), ("pad", C.c_float * 4)]
+
+
+assert C.sizeof(SphScalarSource) == 64
+SOURCE_DTYPE = np.dtype(SphScalarSource)
+assert SOURCE_DTYPE.itemsize == 64
+SPH_MAX_SCALAR_SOURCES = 8
+SPH_SOURCE_SPHERE, SPH_SOURCE_BOX = 0, 1
+SPH_SOURCE_RATE, SPH_SOURCE_RELAX = 0, 1
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -324,6 +339,14 @@ _ABI = {
     "sph_obstacles_step_host": (_int, [_vp, _vp, _int, _vp, _pp, _f]),
     "sph_volume_moments": (_int, [_vp, _int, _vp]),
     "sph_volume_moments_host": (_int, [_vp, _pi, _pf, _vp]),
+    # active scalars: buoyancy and continuous sources
+    "sph_scalars_set_buoyancy": (_int, [_vp, _pf, _pf]),
+    "sph_scalars_get_buoyancy": (_int, [_vp, _pf, _pf]),
+    "sph_scalar_source_default": (None, [_vp]),
+    "sph_scalars_set_sources": (_int, [_vp, _vp, _int]),
+    "sph_scalars_get_sources": (_int, [_vp, _vp, _int, _pi]),
+    "sph_scalars_injected": (_int, [_vp, _vp, _vp, _int, _P(_d), _P(_u64), _int]),
+    "sph_scalars_couple_host": (_int, [_vp, _sz, _pp, _f, _vp, _int, _pf, _pf, _vp, _int, _vp, _int, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -600,6 +623,42 @@ class Statistics:
     def volume(self) -> float:
         """SPH volume sum(mass / rho_j)."""
         return self.mass * self.s.sumInvDensity
+
+
+def scalar_source(shape, center, size, channel: int = 0, mode: int = SPH_SOURCE_RATE, rate: float = 0.0, target: float = 0.0,
+                  body: int = -1) -> SphScalarSource:
+    """One source: shape SPH_SOURCE_SPHERE (size = radius) or SPH_SOURCE_BOX (size = 3 half extents); centre in
+    the world frame (body -1) or in the local frame of obstacle `body`; SPH_SOURCE_RATE adds rate per second, SPH_SOURCE_RELAX
+    relaxes towards target at rate per second."""
+    s = SphScalarSource()
+    load_library().sph_scalar_source_default(C.byref(s))
+    sz = [float(size)] * 3 if np.ndim(size) == 0 else [float(x) for x in size]
+    ce = [float(x) for x in center]
+    if len(sz) != 3 or len(ce) != 3:
+        raise SphError("scalar_source: center and size need 3 components (size may be one number)")
+    s.shape, s.channel, s.mode, s.body = int(shape), int(channel), int(mode), int(body)
+    for i in range(3):
+        s.center[i], s.size[i] = ce[i], sz[i]
+    s.rate, s.target = float(rate), float(target)
+    return s
+
+
+def source_array(sources) -> np.ndarray:
+    """A list of SphScalarSource, or a structured array, as a contiguous SOURCE_DTYPE array (the layout of SphScalarSource)."""
+    if isinstance(sources, np.ndarray):
+        return np.ascontiguousarray(sources, SOURCE_DTYPE)
+    sources = list(sources or ())
+    if not sources:
+        return np.zeros(0, SOURCE_DTYPE)
+    return np.frombuffer(b"".join(bytes(o) for o in sources), SOURCE_DTYPE).copy()
+
+
+def _buoyancy(channels: int, beta, ref):
+    """(beta, ref) as two float32 arrays of K values (a scalar is every channel's value), or (None, None) for beta None."""
+    if beta is None:
+        return None, None
+    k = int(channels)
+    return (np.broadcast_to(np.asarray(beta, np.float32), (k,)).copy(), np.broadcast_to(np.asarray(0.0 if ref is None else ref, np.float32), (k,)).copy())
 
 
 def obstacle(shape, center, size, rotation=(1.0, 0.0, 0.0, 0.0), vel=(0.0, 0.0, 0.0), omega=(0.0, 0.0, 0.0),
@@ -1177,6 +1236,41 @@ class SPHFluidGPU:
         self.sync()
         return buf if device else buf.cpu().numpy()
 
+    # -- active scalars: buoyancy and continuous sources (include/sph_abi.h "active scalars") --
+    def set_scalar_buoyancy(self, beta=None, ref=0.0):
+        """beta_k and ref_k per channel (a scalar is every channel's value); beta=None switches the kick off.  Every substep from now
+        on adds -(dt sum_k beta_k (c_k - ref_k)) g to the velocity of every fluid particle.  No synchronisation."""
+        b, r = _buoyancy(max(self.num_scalar_channels(), 1), beta, ref)
+        _check(self._L.sph_scalars_set_buoyancy(self._h, None if b is None else b.ctypes.data_as(_pf), None if r is None else r.ctypes.data_as(_pf)))
+
+    def scalar_buoyancy(self):
+        """(beta, ref): two float32 arrays of K values as set (zeros while off)."""
+        k = self.num_scalar_channels()
+        b, r = np.zeros(max(k, 1), np.float32), np.zeros(max(k, 1), np.float32)
+        _check(self._L.sph_scalars_get_buoyancy(self._h, b.ctypes.data_as(_pf), r.ctypes.data_as(_pf)))
+        return b[:k], r[:k]
+
+    def set_scalar_sources(self, sources=()):
+        """Replace the source table (a list of scalar_source() results or a SOURCE_DTYPE array; empty clears it).  No synchronisation."""
+        arr = source_array(sources)
+        _check(self._L.sph_scalars_set_sources(self._h, _ptr_or_none(arr), len(arr)))
+
+    def scalar_sources(self) -> np.ndarray:
+        """The sources as set, a SOURCE_DTYPE array."""
+        out = np.zeros(SPH_MAX_SCALAR_SOURCES, SOURCE_DTYPE)
+        k = C.c_int()
+        _check(self._L.sph_scalars_get_sources(self._h, _ptr(out), len(out), C.byref(k)))
+        return out[:k.value].copy()
+
+    def scalar_injected(self, reset: bool = False):
+        """(sums, hits, time, substeps): per source the fp64 sum of c' - c and the (particle, substep) hits since the last zeroing, the
+        simulated time and the substeps over which they were summed; reset zeroes them after the read.  Synchronises."""
+        sums, hits = np.zeros(SPH_MAX_SCALAR_SOURCES, np.float64), np.zeros(SPH_MAX_SCALAR_SOURCES, np.uint64)
+        t, n = C.c_double(), C.c_uint64()
+        _check(self._L.sph_scalars_injected(self._h, _ptr(sums), _ptr(hits), SPH_MAX_SCALAR_SOURCES, C.byref(t), C.byref(n), 1 if reset else 0))
+        k = len(self.scalar_sources())
+        return sums[:k].copy(), hits[:k].copy(), float(t.value), int(n.value)
+
     # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
     def set_obstacles(self, obstacles):
         """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
@@ -1510,3 +1604,17 @@ def volume_moments_host(values, spacing) -> np.ndarray:
     out = np.zeros(10, np.float64)
     _check(load_library().sph_volume_moments_host(_ptr(v), dims, _f3(sp), _ptr(out)))
     return out
+
+
+def scalars_couple_host(particles: np.ndarray, params: SphParams, values, beta=None, ref=0.0, sources=(), obstacles=(), dt: float = -1.0):
+    """sph_scalars_couple_host on copies: (records, (n, K) values, sums, hits) after the coupling step of one substep (DESIGN.md
+    section 3i).  obstacles: the poses body-bound sources ride on (what SPHFluidGPU.obstacles() returns).  No device is needed."""
+    rec = np.ascontiguousarray(particles, PARTICLE_DTYPE).copy()
+    v = _scalar_values(values, len(rec)).copy()
+    b, r = _buoyancy(max(v.shape[1], 1), beta, ref)
+    src, obs = source_array(sources), obstacle_array(obstacles)
+    sums, hits = np.zeros(max(len(src), 1), np.float64), np.zeros(max(len(src), 1), np.uint64)
+    _check(load_library().sph_scalars_couple_host(_ptr(rec), len(rec), C.byref(params), float(dt), _ptr(v), v.shape[1],
+                                                  None if b is None else b.ctypes.data_as(_pf), None if r is None else r.ctypes.data_as(_pf),
+                                                  _ptr_or_none(src), len(src), _ptr_or_none(obs), len(obs), _ptr(sums), _ptr(hits)))
+    return rec, v, sums[:len(src)], hits[:len(src)]

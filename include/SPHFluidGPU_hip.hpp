@@ -282,6 +282,29 @@ public:
         const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
         return !Check(sph_scalars_sample_lattice(engine, o, s, dims, channel, devOut), "sph_scalars_sample_lattice");
     }
+    // Active scalars (engine extension, sph_abi.h "active scalars"): SetScalarBuoyancy gives every channel a
+    // beta and a reference value (empty vectors switch the kick off), SetScalarSources replaces the table of continuous sources (up to
+    // SPH_MAX_SCALAR_SOURCES, an empty vector clears it); both act inside every substep and do not synchronise.  ScalarInjected reads
+    // the books per source (fp64 sum of c' - c and the hits) and synchronises.  Return false on error (LastError()).
+    bool SetScalarBuoyancy(const std::vector<float>& beta, const std::vector<float>& ref) {
+        const size_t k = size_t(sph_scalars_channels(engine));
+        if (beta.size() != ref.size() || (!beta.empty() && beta.size() != k)) { lastError = "SetScalarBuoyancy: beta and ref must hold one float per channel"; return false; }
+        return !Check(sph_scalars_set_buoyancy(engine, beta.empty() ? nullptr : beta.data(), ref.empty() ? nullptr : ref.data()), "sph_scalars_set_buoyancy");
+    }
+    bool SetScalarSources(const std::vector<SphScalarSource>& sources) {
+        return !Check(sph_scalars_set_sources(engine, sources.empty() ? nullptr : sources.data(), int(sources.size())), "sph_scalars_set_sources");
+    }
+    bool ScalarInjected(std::vector<double>& sums, std::vector<uint64_t>& hits, double& time, uint64_t& substeps, bool reset = false) {
+        sums.assign(SPH_MAX_SCALAR_SOURCES, 0.0);
+        hits.assign(SPH_MAX_SCALAR_SOURCES, 0);
+        int count = 0;
+        SphScalarSource cur[SPH_MAX_SCALAR_SOURCES];
+        if (Check(sph_scalars_get_sources(engine, cur, SPH_MAX_SCALAR_SOURCES, &count), "sph_scalars_get_sources")) return false;
+        if (Check(sph_scalars_injected(engine, sums.data(), hits.data(), SPH_MAX_SCALAR_SOURCES, &time, &substeps, reset ? 1 : 0), "sph_scalars_injected")) return false;
+        sums.resize(size_t(count));
+        hits.resize(size_t(count));
+        return true;
+    }
     // Kinematic solid obstacles (engine extension, sph_abi.h "obstacles"): up to SPH_MAX_OBSTACLES bodies whose
     // motion the caller prescribes; every substep keeps the fluid out of them, advances their poses on the device and sums, per body,
     // the impulse (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave it.  An empty vector drops the set.  SetObstacleMotion keeps the device's pose

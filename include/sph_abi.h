@@ -43,6 +43,8 @@ extern "C" {
     sph_obstacles_bind_volume / _volume / _apply_host_volumes, sph_mesh_distance / _host -- triangle-mesh obstacles through signed distance lattices) */
 /* (still 4, additions only: SphObstacleDynamics, SPH_DYNAMICS_CONFINED, sph_obstacle_dynamics_default, sph_obstacles_set_dynamics / _get_dynamics /
     _step_host, sph_volume_moments / _host -- dynamic rigid bodies) */
+/* (still 4, additions only: SphScalarSource, SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_*, sph_scalar_source_default, sph_scalars_set_buoyancy / _get_buoyancy /
+    _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -653,6 +655,72 @@ int  sph_obstacles_step_host(SphObstacle* obs, const SphObstacleDynamics* dyn, i
  * SPH_K_OTHER.  Synchronises.  The _host twin runs the same per-point function in plain loops, points in ascending order. */
 int  sph_volume_moments(SphEngine* e, int id, double out[10]);
 int  sph_volume_moments_host(const float* values, const int dims[3], const float spacing[3], double out[10]);
+
+/* ---- active scalars: buoyancy from heat or salt, and continuous sources (no reference counterpart) ----------
+ * The scalar channels act back on the fluid, and regions in the world or riding on an obstacle feed them every substep on the device.
+ * Both are off by default and belong to the scalar set: sph_scalars_set / _set_device reset them to none (and zero the books), sph_reset
+ * drops them, sph_destroy frees them.  With neither set a dispatch launches exactly what it launched before.
+ * One non-paused substep with time step dt (the dt the dispatch steps with) runs, on the substep's OUTPUT state, after the SPH pass, the
+ * container and the obstacle step, and before river / fountain: the sources 0 .. S-1 in order, then the buoyancy kick.  Targets are
+ * the records with isGhost == 0 and finite position; every other record keeps its bits and its values.
+ *   frame      body == -1: d = p - center (world axes).  body == b: the local frame of obstacle b as the device holds it AFTER this
+ *              substep's obstacle step (kinematic, volume-bound and dynamic bodies alike): q = p - c_b, l_a = fmaf(q_z, M_za, fmaf(q_y, M_ya,
+ *              q_x * M_xa)) (l = M^T q, the dot3 of section 3e), d = l - center.
+ *   inside     strict: sphere fmaf(d_z, d_z, fmaf(d_y, d_y, d_x * d_x)) < size[0] * size[0]; box |d_a| < size[a] on all three axes.
+ *   hit        a target inside whose value c in the source's channel is finite.  Each source sees the result of the ones before it.
+ *   arithmetic fp32, a multiply and then an add, no fma:  SPH_SOURCE_RATE  c' = c + dt * rate;
+ *              SPH_SOURCE_RELAX  a = fminf(dt * rate, 1.0f); r = c + a * (target - c);
+ *              c' = fminf(fmaxf(r, fminf(c, target)), fmaxf(c, target))   (the clamp only acts where a rounding of target - c would carry r
+ *              past the target: c' never leaves the closed interval between c and target, so no stability number is needed)
+ *   books      per source the number of (particle, substep) hits and the fp64 sum of (double)c' - (double)c (one fp64 subtraction per
+ *              hit), cumulative since the last zeroing; with them the simulated time (fp64 sum of dt) and the substeps, which advance
+ *              while at least one source is set, graph replays included.  No float atomic: the sums depend on the slot order of the
+ *              state only.  A set call with another source count zeroes the books, one with the same count keeps them.
+ *   buoyancy   s = 0; for k = 0 .. K-1: s = fmaf(beta_k, c_k - ref_k, s), on the values the sources just wrote.  Where s is finite and
+ *              != 0: v_a' = v_a - (dt * s) * g_a per axis with g = (param_gravityX, Y, Z) of this dispatch (a multiply, a multiply and a
+ *              subtract, no fma); otherwise the record is not written.  beta > 0 with c > ref accelerates against gravity (heat);
+ *              salt takes beta < 0.  Positions are not touched and the velocity is not capped: the next pass's own cap applies.
+ * The coefficients, the source table and the source count live in device memory: a replayed graph sees a later set call.  Whether the
+ * kernels run, and their buffers, enter a graph's key.  While a beta is non-zero the SPH pass does not keep the 80-byte array current
+ * by itself (SPH_OPT_AOS_MODE 0 writes it back after the substep, as with obstacles); sources alone never change a record.
+ * SPH_ERR_STATE: no scalars; z-slab engines and SPH_OPT_GRID_BUILD 1 (as the block above); a dispatch while a source's body is >= the
+ * obstacle count (the dispatch fails and changes nothing).  SPH_ERR_ARG (the previous state stays): a count above
+ * SPH_MAX_SCALAR_SOURCES, a null pointer where data is needed (beta without ref), an unknown shape or mode, a channel outside [0, K), a
+ * non-finite field, a used size component that is not > 0, rate < 0, body < -1 or >= SPH_MAX_OBSTACLES. */
+#define SPH_MAX_SCALAR_SOURCES 8
+enum { SPH_SOURCE_SPHERE = 0, SPH_SOURCE_BOX = 1 };
+enum { SPH_SOURCE_RATE = 0, SPH_SOURCE_RELAX = 1 };
+typedef struct SphScalarSource {   /* 64 bytes */
+    int32_t  shape;        /* SPH_SOURCE_SPHERE | SPH_SOURCE_BOX */
+    int32_t  channel;
+    int32_t  mode;         /* SPH_SOURCE_RATE | SPH_SOURCE_RELAX */
+    int32_t  body;         /* -1: world frame | b: local frame of obstacle b */
+    float    center[3];
+    float    size[3];      /* sphere: x = radius | box: half extents */
+    float    rate;         /* RATE: value per second | RELAX: 1 / s */
+    float    target;       /* RELAX only */
+    float    pad[4];
+} SphScalarSource;
+/* K floats each (beta_k, ref_k), all finite; NULL, NULL switches buoyancy off.  Stream-ordered, no synchronisation. */
+int  sph_scalars_set_buoyancy(SphEngine* e, const float* beta, const float* ref);
+/* The coefficients as set (zeros while off); either pointer may be null. */
+int  sph_scalars_get_buoyancy(SphEngine* e, float* beta, float* ref);
+/* A unit sphere at the world origin on channel 0, SPH_SOURCE_RATE with rate 0. */
+void sph_scalar_source_default(SphScalarSource* out);
+/* Replaces the source table; count 0 clears it.  Stream-ordered, no synchronisation. */
+int  sph_scalars_set_sources(SphEngine* e, const SphScalarSource* sources, int count);
+/* The sources as set (cap >= count, else SPH_ERR_CAPACITY); countOut may be null. */
+int  sph_scalars_get_sources(SphEngine* e, SphScalarSource* out, int cap, int* countOut);
+/* The books: per source the fp64 sum and the hits (cap >= count, else SPH_ERR_CAPACITY), the simulated time and the substeps summed
+ * since the last zeroing; reset != 0 zeroes them after the read.  Any output pointer may be null.  Synchronises. */
+int  sph_scalars_injected(SphEngine* e, double* sums, uint64_t* hits, int cap, double* timeOut, uint64_t* substepsOut, int reset);
+/* Host-only, no device: the same __host__ __device__ functions the kernel runs, on n records and n * channels values in place, in
+ * index order (record i owns values[i * channels ..]).  beta, ref: NULL, NULL for no buoyancy.  obstacles: the poses a body-bound source
+ * rides on, rotation used as given (pass what sph_obstacles_get returned).  sumsOut / hitsOut (nSources each, may be null) receive this
+ * step's books, the sums added in index order.  dt <= 0: param_timeStep.  param_pause: nothing happens. */
+int  sph_scalars_couple_host(SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels,
+                             const float* beta, const float* ref, const SphScalarSource* sources, int nSources,
+                             const SphObstacle* obstacles, int nObstacles, double* sumsOut, uint64_t* hitsOut);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
