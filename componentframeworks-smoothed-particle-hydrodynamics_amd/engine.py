@@ -1155,7 +1155,7 @@ class SPHFluidGPU:
         if values is None:
             k = 1 if channels is None else int(channels)
             co = _scalar_coeffs(max(k, 1), diffusivity, decay)
-            _check(self._L.sph_scalars_set(self._h, None, self.numParticles, k, co.ctypes.data_as(_pf)))
+            _check(self._L.sph_scalars_set(self._h, None, self.GetNumFluids(), k, co.ctypes.data_as(_pf)))   # (the engine's count: a reset may spawn fewer than numParticles)
             return
         v = _scalar_values(values)
         co = _scalar_coeffs(max(v.shape[1], 1), diffusivity, decay)
@@ -1180,7 +1180,7 @@ class SPHFluidGPU:
     def scalars(self) -> np.ndarray:
         """The values in the caller's order, shape (n, K) float32.  Synchronises."""
         k = self.num_scalar_channels()
-        out = np.zeros((self.numParticles if k else 0, k), np.float32)
+        out = np.zeros((self.GetNumFluids() if k else 0, k), np.float32)
         _check(self._L.sph_scalars_download(self._h, _ptr(out), out.size))
         return out
 

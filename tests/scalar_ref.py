@@ -188,6 +188,21 @@ def cubic_lattice(pkg, oracle, m, spacing_over_h, h=0.28, rho0=1000.0):
     return rec, sp
 
 
+def paint(rec, values, center, radius, channel, value, mode):
+    """sph_scalars_paint: channel = value (mode 0, SPH_SCALAR_SET) or channel += value (mode 1, one fp32 add) for every record with
+    isGhost == 0 whose position lies strictly inside the sphere, fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < radius * radius with d = x - center
+    (a non-finite coordinate is never inside).  A new (n, K) array."""
+    c = np.ascontiguousarray(values, F).reshape(len(rec), -1).copy()
+    pos = rec["pos"][:, :3].astype(F)
+    ce = np.asarray(center, F)
+    with np.errstate(all="ignore"):
+        d = [(pos[:, a] - ce[a]).astype(F) for a in range(3)]
+        inside = (rec["isGhost"] == 0) & (dot3(d[0], d[1], d[2], d[0], d[1], d[2]) < F(F(radius) * F(radius)))
+        new = np.full(len(rec), F(value), F) if mode == 0 else (c[:, channel] + F(value)).astype(F)
+    c[:, channel] = np.where(inside, new, c[:, channel])
+    return c
+
+
 def moments(values, tgt, particle_cell):
     """Per channel over the targets with a finite value, as sph_scalars_moments forms them: count, the statistics' fixed-order fp64
     sum and sum of squares (slots in canonical order, +0.0 outside the set), (min, id), (max, id)."""

@@ -104,6 +104,54 @@ def fluid_block(rec):
     return (0.5 * (lo + hi)).astype(F), float((hi - lo).max())
 
 
+def random_scene(pkg, seed):
+    """A seeded random scene for the fuzz tests: (records, params, substeps, what).  It varies the kernel length h (h^2 > 1 selects the
+    walk's other template instance), non-cubic grids down to three cells, 0.3 .. 20 particles per cell, speeds up to the velocity cap,
+    clumps, ghosts, particles outside the grid, rotated containers of every shape and the time step."""
+    rng = np.random.default_rng(1000 + seed)
+    h = float(rng.choice([0.1, 0.28, 0.28, 0.6, 1.25, 2.0]))
+    dims = [int(rng.integers(3, 22)) for _ in range(3)]
+    half = [(g / 2.0 - 1.0) * h - 0.01 * h for g in dims]
+    lam = float(rng.choice([0.3, 1.0, 2.0, 2.0, 6.0, 20.0]))
+    fill = float(rng.uniform(0.3, 1.0))                       # fraction of the box height that holds particles
+    cells = max(1, (dims[0] - 2) * (dims[2] - 2) * max(1, int((dims[1] - 2) * fill)))
+    n = int(min(14000, max(1, lam * cells)))
+    dt = float(rng.choice([1e-3, 5e-4, 2e-3]))
+    s = 0.8 * h
+    sp = pkg.default_params(
+        param_h=h, param_mass=float(np.float32(1000.0 * s ** 3)), param_restDensity=1000.0, param_gasConstant=2000.0,
+        param_viscosity=3.5, param_gravityX=0.0, param_gravityY=-980.0 * h / 0.28, param_gravityZ=0.0, param_surfaceTension=0.0728,
+        param_timeStep=dt, param_foamGen=1.0, param_foamVelRef=8.0, param_boxCenter=(0.0, 0.0, 0.0), param_boxHalf=tuple(half),
+        param_boxEulerDeg=(0.0, 0.0, 0.0), param_shapeType=0, param_wallRestitution=0.15, param_wallFriction=0.02, grid_cap=160)
+    if rng.random() < 0.5:
+        sp.param_shapeType = int(rng.integers(0, 15))
+        for a in range(3):
+            sp.param_shapeAux[a] = float(rng.uniform(0.2, 1.0))
+    if rng.random() < 0.4:
+        for a in range(3):
+            sp.param_boxEulerDeg[a] = float(rng.uniform(-40, 40))
+    rec = np.zeros(n, pkg.PARTICLE_DTYPE)
+    lo = np.array([-half[0], -half[1], -half[2]], np.float32)
+    ext = np.array([2 * half[0], 2 * half[1] * fill, 2 * half[2]], np.float32)
+    rec["pos"][:, :3] = lo + rng.random((n, 3)).astype(np.float32) * ext
+    rec["pos"][:, 3] = 1.0
+    vcap = 0.4 * h / dt
+    sigma = float(rng.choice([0.0, 0.02, 0.1, 0.5])) * vcap
+    rec["vel"][:, :3] = rng.normal(0, 1, (n, 3)).astype(np.float32) * np.float32(sigma)
+    rec["isActive"][:] = 1
+    if n > 200 and rng.random() < 0.4:                         # a clump: hundreds of particles inside one cell
+        k = int(rng.integers(50, min(n, 1500)))
+        rec["pos"][:k, :3] = rec["pos"][0, :3] + rng.normal(0, 0.2 * h, (k, 3)).astype(np.float32)
+    if n > 100 and rng.random() < 0.4:                         # ghosts of every kind, some inactive particles
+        g = rng.choice(n, size=n // 20, replace=False)
+        rec["isGhost"][g] = rng.choice([1, 1, 3], size=len(g))
+        rec["isActive"][g[: len(g) // 2]] = 0
+    if n > 100 and rng.random() < 0.3:                         # particles outside the grid
+        rec["pos"][rng.choice(n, size=n // 50 + 1, replace=False), 0] += np.float32(4.0 * half[0] + 3 * h)
+    steps = int(rng.integers(1, 4))
+    return rec, sp, steps, dict(h=h, dims=dims, n=n, per_cell=lam, sigma_over_cap=sigma / vcap, dt=dt, steps=steps, shape=int(sp.param_shapeType))
+
+
 def identity_states(pkg):
     """(name, records, params) of the states the sampling identities are checked on."""
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=7)
