@@ -22,5 +22,7 @@ from .engine import (  # noqa: F401
     SPH_MAX_SCALAR_CHANNELS, SPH_OPT_SCALAR_SWEEP, SPH_SCALAR_ADD, SPH_SCALAR_SET, ScalarMoments, SphScalarMoments, mixing_index, scalars_step_host,
     SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_SPHERE, SPH_SOURCE_BOX, SPH_SOURCE_RATE, SPH_SOURCE_RELAX, SphScalarSource, SOURCE_DTYPE, scalar_source,
     source_array, scalars_couple_host,
+    SPH_OPT_DIFFUSE_TIMED, SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE, SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, DIFFUSE_DTYPE, diffuse_config,
+    diffuse_step_host, write_points_ply,
 )
 from . import build, synthetic  # noqa: F401

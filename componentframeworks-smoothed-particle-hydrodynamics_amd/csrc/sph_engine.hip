@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -25,6 +26,7 @@
 #include "sph_sample.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
+#include "sph_diffuse.h"
 #include "sph_scalar.h"
 #include "sph_obstacle.h"
 #include "sph_volume.h"
@@ -34,6 +36,8 @@
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
 static_assert(sizeof(SphTracer) == 32, "SphTracer must be 32 bytes");
+static_assert(sizeof(SphDiffuse) == 48 && sizeof(sph::DiffuseRec) == 48 && sizeof(SphDiffuseConfig) == 64 && sizeof(SphDiffuseInfo) == 88, "SphDiffuse must be 48 bytes, SphDiffuseConfig 64, SphDiffuseInfo 88");
+static_assert(SPH_DIFFUSE_SPRAY == sph::DF_SPRAY && SPH_DIFFUSE_FOAM == sph::DF_FOAM && SPH_DIFFUSE_BUBBLE == sph::DF_BUBBLE, "diffuse classes of sph_abi.h and sph_diffuse.h");
 static_assert(sizeof(SphScalarMoments) == 40, "SphScalarMoments must be 40 bytes");
 static_assert(SPH_MAX_SCALAR_CHANNELS == sph::kScalarMax && SPH_SCALAR_SET == sph::kScalarSet && SPH_SCALAR_ADD == sph::kScalarAdd, "scalar constants of sph_abi.h and sph_scalar.h");
 static_assert(sizeof(SphScalarSource) == sizeof(sph::CoupleSrc) && SPH_MAX_SCALAR_SOURCES == sph::kCoupleMax && SPH_SOURCE_SPHERE == sph::COUPLE_SPHERE &&
@@ -265,6 +269,21 @@ struct SphEngine {
     bool trOrdered = false;              // the processing order has been cell-sorted since sph_tracers_set
     bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
 
+    // sph_diffuse_* (sph_diffuse.h): the pool of C records (three float4 each) and the scratch pool a substep advances
+    // into, the device state words (alive count, substep counter, totals), the coefficients as the kernels read them (device memory: a
+    // replayed graph sees a later change) with their pinned staging, the survivor flags with their scan, the per-block counts, and the
+    // child counts in id order with their scan
+    float4* d_dfPool = nullptr;
+    float4* d_dfScratch = nullptr;
+    uint32_t* d_dfState = nullptr;
+    sph::DiffuseCoef* d_dfCoef = nullptr;
+    StageRing<sph::DiffuseCoef> dfStage;
+    uint32_t *d_dfFlag = nullptr, *d_dfFlagStart = nullptr, *d_dfFlagSums = nullptr, *d_dfPart = nullptr;
+    DevBuf<uint32_t> d_dfCnt, d_dfCntStart, d_dfCntSums;
+    uint32_t dfC = 0;                    // capacity of the pool (0: none)
+    int optDiffuseTimed = 0;             // SPH_OPT_DIFFUSE_TIMED: which launches of the substep the timing bracket covers (0 all, 1 advance, 2 the rest)
+    SphDiffuseConfig dfCfg{};            // the config in force
+
     // sph_scalars_* (sph_scalar.h): K channels per particle in the caller's order, their gathered copy in slot order
     // (K values + the ghost weight per slot), the coefficients as the kernels read them (device memory: a replayed graph sees a later
     // change) with their pinned staging, and the device word of the last substep's diffusion number
@@ -439,6 +458,16 @@ void tracers_free(SphEngine* e) {
     e->trM = e->trCap = e->trRingCap = 0;
     e->trK = 0; e->trS = 1; e->trSteps = e->trSorted = 0;
     e->trOrdered = false;
+}
+
+void diffuse_free(SphEngine* e) {
+    if (e->d_dfPool && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(e->d_dfPool); dev_free(e->d_dfScratch); dev_free(e->d_dfState); dev_free(e->d_dfCoef);
+    e->dfStage.destroy();
+    dev_free(e->d_dfFlag); dev_free(e->d_dfFlagStart); dev_free(e->d_dfFlagSums); dev_free(e->d_dfPart);
+    e->d_dfCnt.release(); e->d_dfCntStart.release(); e->d_dfCntSums.release();
+    e->dfC = 0;
+    e->dfCfg = SphDiffuseConfig{};
 }
 
 void scalars_free(SphEngine* e) {
@@ -654,6 +683,45 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
     }
     HIP_TRY(hipGetLastError());
     e->trSteps += 1;
+    return SPH_OK;
+}
+
+// ---- spray, foam and bubbles (sph_diffuse.h) -----------------------------------------------------
+// One substep's work on the pool, behind build_grid of that substep: advance into the scratch pool, count the children, scan both,
+// compact the survivors back, emit the newborn behind them, tick.  Sized by C and N alone.
+int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
+    const uint32_t C = e->dfC;
+    int rc;
+    if (e->d_dfCntStart.cap < (size_t)n + 1) {               // (grown last: a failed growth is tried again; never while capturing: the eager run before has grown them)
+        if (e->capturing) return fail(SPH_ERR_STATE, "diffuse scratch missing during a graph capture");
+        if ((rc = e->d_dfCnt.grow(e, (size_t)n + 8)) || (rc = e->d_dfCntSums.grow(e, (size_t)blocks_for((size_t)n, kScanTile) + 1)) ||
+            (rc = e->d_dfCntStart.grow(e, (size_t)n + 1))) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_dfCnt.p, 0, e->d_dfCnt.cap * sizeof(uint32_t), e->stream));     // (k_scan_apply leaves it zero again)
+    }
+    // one bracket per substep: around everything, or (SPH_OPT_DIFFUSE_TIMED, measurements) around the advance or around the rest
+    std::unique_ptr<Timed> t;
+    if (e->optDiffuseTimed != 2) t.reset(new Timed(e, SPH_K_OTHER));
+    const int cb = blocks_for(C), nb = blocks_for(n);
+    hipLaunchKernelGGL(k_diffuse_advance, dim3(cb), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, dt,
+                       (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const float4*)e->d_dfPool, e->d_dfScratch, e->d_dfFlag, e->d_dfPart, C);
+    if (e->optDiffuseTimed == 1) t.reset();
+    if (e->optDiffuseTimed == 2) t.reset(new Timed(e, SPH_K_OTHER));
+    if (n)
+        hipLaunchKernelGGL(k_diffuse_count, dim3(nb), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn, dt,
+                           (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, e->d_dfCnt.p, e->idBase, n);
+    launch_cell_scan(e, e->d_dfFlag, e->d_dfFlagSums, e->d_dfFlagStart, (int)C, C);
+    if (n) launch_cell_scan(e, e->d_dfCnt.p, e->d_dfCntSums.p, e->d_dfCntStart.p, (int)n, n);
+    else HIP_TRY(hipMemsetAsync(e->d_dfCntStart.p, 0, sizeof(uint32_t), e->stream));
+    hipLaunchKernelGGL(k_diffuse_compact, dim3(cb), dim3(kBlock), 0, e->stream, (const float4*)e->d_dfScratch, (const uint32_t*)e->d_dfFlagStart,
+                       (const uint32_t*)e->d_dfState, e->d_dfPool, C);
+    if (n)
+        hipLaunchKernelGGL(k_diffuse_emit, dim3(nb), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
+                           (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const uint32_t*)e->d_dfCntStart.p,
+                           (const uint32_t*)e->d_dfFlagStart, e->d_dfPool, e->idBase, n, C);
+    hipLaunchKernelGGL(k_diffuse_tick, dim3(1), dim3(kBlock), 0, e->stream, e->d_dfState, (const uint32_t*)e->d_dfPart, (uint32_t)cb,
+                       (const uint32_t*)e->d_dfFlagStart, (const uint32_t*)e->d_dfCntStart.p, n, C);
+    t.reset();
+    HIP_TRY(hipGetLastError());
     return SPH_OK;
 }
 
@@ -908,6 +976,8 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if (e->scK && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (e->dfC && e->optGridBuild == 1)
+        return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params)) || (rc = couple_refused(e))) return rc;
     float cont[15];
     container_key(e->params, cont);
@@ -955,6 +1025,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     } else {
     if ((rc = build_grid(e, k, true))) return rc;                           // :449-468
     if (e->trM && (rc = tracers_advect(e, k, dt))) return rc;               // (reads the sorted copy and cellStart, as the SPH pass does)
+    if (e->dfC && (rc = diffuse_step(e, k, dt, (uint32_t)n))) return rc;    // (the same two, and the sorted own data)
     if (e->scK && (rc = scalars_step(e, k, dt))) return rc;                 // (the same two, and the sorted own data)
     if (n) {                                                                // :470-509 (SPH + OBB fused)
         if (!e->d_sPV || e->sortedCap < (size_t)n) return fail(SPH_ERR_STATE, "sorted copy missing");
@@ -1212,6 +1283,7 @@ int sph_destroy(SphEngine* e) {
     surface_free(e);
     stats_free(e);
     tracers_free(e);
+    diffuse_free(e);
     scalars_free(e);
     obstacles_free(e);
     volumes_free(e);
@@ -1245,6 +1317,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     tracers_free(e);                                                  // (and the tracer set)
+    diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
     if (e->d_obsAcc) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (obstacles: the set and the poses stay, the sums restart)
     std::vector<SphParticle> v;
@@ -1282,6 +1355,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_GRAPH: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optGraph = value; break;
     case SPH_OPT_MESH_SPLIT: if (value < 0 || value > 64) return fail(SPH_ERR_ARG, "bad value"); e->optMeshSplit = value; break;
     case SPH_OPT_SCALAR_SWEEP: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optScalarSweep = value; break;
+    case SPH_OPT_DIFFUSE_TIMED: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optDiffuseTimed = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1304,6 +1378,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_GRAPH: *value = e->optGraph; break;
     case SPH_OPT_MESH_SPLIT: *value = e->optMeshSplit; break;
     case SPH_OPT_SCALAR_SWEEP: *value = e->optScalarSweep; break;
+    case SPH_OPT_DIFFUSE_TIMED: *value = e->optDiffuseTimed; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -1339,6 +1414,11 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     add(tr, sizeof(tr));
     const uint64_t trv[4] = {(uint64_t)e->trM, (uint64_t)e->trIntegrator, e->trK, e->trS};
     add(trv, sizeof(trv));
+    // diffuse particles: pool set, its capacity and every buffer the substep's kernels get; the coefficients and all counts are read from memory
+    const void* df[11] = {e->d_dfPool, e->d_dfScratch, e->d_dfState, e->d_dfCoef, e->d_dfFlag, e->d_dfFlagStart, e->d_dfFlagSums, e->d_dfPart,
+                          e->d_dfCnt.p, e->d_dfCntStart.p, e->d_dfCntSums.p};
+    add(df, sizeof(df));
+    add(&e->dfC, sizeof(e->dfC));
     // scalars: a call with scalars is never served by a graph captured without them or with another channel count; the coefficients are read from memory
     const void* sc[4] = {e->d_scVal, e->d_scSorted, e->d_scCoef, e->d_scState};
     add(sc, sizeof(sc));
@@ -3009,6 +3089,200 @@ int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t*
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (snapshotsOut) *snapshotsOut = count;
     if (firstSnapshotOut) *firstSnapshotOut = first;
+    return SPH_OK;
+}
+
+// ---- spray, foam and bubbles (sph_diffuse.h) ------------------------------------------------------
+static bool diffuse_nonneg(float v) { return std::isfinite(v) && v >= 0.0f; }
+static int diffuse_check_config(const SphDiffuseConfig& c) {
+    if (!diffuse_nonneg(c.rate) || !diffuse_nonneg(c.lifeMin) || !diffuse_nonneg(c.lifeMax) || !diffuse_nonneg(c.spread))
+        return fail(SPH_ERR_ARG, "diffuse rate, lifeMin, lifeMax and spread must be finite and >= 0");
+    if (c.lifeMax < c.lifeMin) return fail(SPH_ERR_ARG, "diffuse lifeMax %g < lifeMin %g", (double)c.lifeMax, (double)c.lifeMin);
+    if (c.maxPerParent < 1u || c.maxPerParent > 8u) return fail(SPH_ERR_ARG, "diffuse maxPerParent %u (1 .. 8)", c.maxPerParent);
+    if (c.sprayBelow > c.bubbleAbove) return fail(SPH_ERR_ARG, "diffuse sprayBelow %u > bubbleAbove %u", c.sprayBelow, c.bubbleAbove);
+    if (!(c.kd >= 0.0f && c.kd <= 1.0f)) return fail(SPH_ERR_ARG, "diffuse kd %g outside [0, 1]", (double)c.kd);
+    if (!std::isfinite(c.threshold) || !std::isfinite(c.kb)) return fail(SPH_ERR_ARG, "diffuse threshold and kb must be finite");
+    if (!(c.maxAge >= 0.0f)) return fail(SPH_ERR_ARG, "diffuse maxAge must be >= 0");
+    if (c.capacity > 2147483647u) return fail(SPH_ERR_ARG, "a diffuse capacity of %u exceeds 2^31 - 1", c.capacity);
+    return SPH_OK;
+}
+static sph::DiffuseCoef diffuse_coef_of(const SphDiffuseConfig& c) {
+    return sph::DiffuseCoef{c.threshold, c.rate, c.lifeMin, c.lifeMax, c.spread, c.kb, c.kd, c.maxAge, c.sprayBelow, c.bubbleAbove, c.maxPerParent, c.seed};
+}
+void sph_diffuse_default(SphDiffuseConfig* out) {
+    if (!out) return;
+    SphDiffuseConfig c{};
+    c.capacity = 65536u; c.seed = 1u;
+    c.threshold = 0.02f; c.rate = 5000.0f;
+    c.lifeMin = 0.2f; c.lifeMax = 1.0f;
+    c.spread = 0.5f; c.maxAge = 4.0f;
+    c.sprayBelow = 6u; c.bubbleAbove = 20u;
+    c.kb = 2.0f; c.kd = 0.5f;
+    c.maxPerParent = 4u;
+    *out = c;
+}
+int sph_diffuse_set(SphEngine* e, const SphDiffuseConfig* cfg) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "diffuse particles on a z-slab engine are not supported: a record would have to migrate with the fluid around it");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (!cfg || cfg->capacity == 0u) { diffuse_free(e); return SPH_OK; }
+    int rc;
+    if ((rc = diffuse_check_config(*cfg))) return rc;
+    const uint32_t C = cfg->capacity;
+    if (C != e->dfC || !e->d_dfPool) {
+        diffuse_free(e);
+        hipError_t er = hipSuccess;
+        const size_t cb = (size_t)blocks_for((size_t)C);
+        if ((rc = dev_alloc(&e->d_dfPool, (size_t)3 * C)) || (rc = dev_alloc(&e->d_dfScratch, (size_t)3 * C)) || (rc = dev_alloc(&e->d_dfState, (size_t)DF_WORDS)) ||
+            (rc = dev_alloc(&e->d_dfCoef, 1)) || (rc = dev_alloc(&e->d_dfFlag, (size_t)C + 8)) || (rc = dev_alloc(&e->d_dfFlagStart, (size_t)C + 1)) ||
+            (rc = dev_alloc(&e->d_dfFlagSums, (size_t)blocks_for((size_t)C, kScanTile) + 1)) || (rc = dev_alloc(&e->d_dfPart, cb * DF_PART_WORDS)) ||
+            (er = e->dfStage.create(e->stream, 1)) != hipSuccess) {
+            diffuse_free(e);
+            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the diffuse coefficients: %s", hipGetErrorString(er));
+        }
+        hipError_t m1 = hipMemsetAsync(e->d_dfState, 0, DF_WORDS * sizeof(uint32_t), e->stream);
+        hipError_t m2 = hipMemsetAsync(e->d_dfFlag, 0, ((size_t)C + 8) * sizeof(uint32_t), e->stream);    // (k_scan_apply leaves it zero again)
+        if (m1 != hipSuccess || m2 != hipSuccess) { diffuse_free(e); return fail(SPH_ERR_HIP, "hipMemsetAsync of the diffuse pool failed"); }
+        e->dfC = C;
+    }
+    sph::DiffuseCoef* slot = nullptr;
+    if ((rc = e->dfStage.next(&slot))) return rc;
+    *slot = diffuse_coef_of(*cfg);
+    HIP_TRY(hipMemcpyAsync(e->d_dfCoef, slot, sizeof(sph::DiffuseCoef), hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->dfStage.commit(e->stream))) return rc;
+    e->dfCfg = *cfg;
+    return SPH_OK;
+}
+int sph_diffuse_get(SphEngine* e, SphDiffuseConfig* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    *out = e->dfCfg;
+    return SPH_OK;
+}
+static void diffuse_info_of(const uint32_t* w, uint32_t C, SphDiffuseInfo& o) {
+    auto u64 = [&](int i) { return ((uint64_t)w[i + 1] << 32) | w[i]; };
+    o = SphDiffuseInfo{};
+    o.substeps = u64(DF_STEP_LO);
+    o.spawned = u64(DF_TOTALS); o.dropped = u64(DF_TOTALS + 2); o.diedLife = u64(DF_TOTALS + 4); o.diedAge = u64(DF_TOTALS + 6);
+    o.leftBox = u64(DF_TOTALS + 8); o.nonFinite = u64(DF_TOTALS + 10); o.seeded = u64(DF_TOTALS + 12);
+    o.alive = std::min(w[DF_ALIVE], C); o.capacity = C;
+    for (int q = 0; q < 3; ++q) o.aliveByKind[q] = w[DF_CLASS + q];
+}
+int sph_diffuse_info(SphEngine* e, SphDiffuseInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    *out = SphDiffuseInfo{};
+    if (!e->dfC) return SPH_OK;
+    uint32_t w[DF_WORDS];
+    HIP_TRY(hipMemcpyAsync(w, e->d_dfState, sizeof(w), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    diffuse_info_of(w, e->dfC, *out);
+    return SPH_OK;
+}
+int sph_diffuse_download(SphEngine* e, SphDiffuse* out, size_t cap, size_t* countOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    SphDiffuseInfo info;
+    int rc;
+    if ((rc = sph_diffuse_info(e, &info))) return rc;
+    if (cap < info.alive) return fail(SPH_ERR_CAPACITY, "%u diffuse particles (capacity %zu)", info.alive, cap);
+    if (info.alive && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (info.alive) {
+        HIP_TRY(hipMemcpyAsync(out, e->d_dfPool, (size_t)info.alive * sizeof(SphDiffuse), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    if (countOut) *countOut = info.alive;
+    return SPH_OK;
+}
+int sph_diffuse_device(SphEngine* e, const SphDiffuse** records, const uint32_t** aliveCountWord) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (records) *records = e->dfC ? reinterpret_cast<const SphDiffuse*>(e->d_dfPool) : nullptr;
+    if (aliveCountWord) *aliveCountWord = e->dfC ? e->d_dfState + DF_ALIVE : nullptr;
+    return SPH_OK;
+}
+int sph_diffuse_seed(SphEngine* e, const SphDiffuse* records, size_t m) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->dfC) return fail(SPH_ERR_STATE, "no diffuse pool: call sph_diffuse_set first");
+    if (m == 0) return SPH_OK;
+    if (!records) return fail(SPH_ERR_ARG, "null argument");
+    uint32_t w[DF_WORDS];
+    HIP_TRY(hipMemcpyAsync(w, e->d_dfState, sizeof(w), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const uint32_t alive = std::min(w[DF_ALIVE], e->dfC);
+    if (m > (size_t)(e->dfC - alive)) return fail(SPH_ERR_CAPACITY, "%zu diffuse records behind %u living ones exceed the capacity of %u", m, alive, e->dfC);
+    for (size_t i = 0; i < m; ++i) if (records[i].kind <= 2u) w[DF_CLASS + records[i].kind] += 1u;
+    w[DF_ALIVE] = alive + (uint32_t)m;
+    const uint64_t seeded = (((uint64_t)w[DF_TOTALS + 13] << 32) | w[DF_TOTALS + 12]) + m;
+    w[DF_TOTALS + 12] = (uint32_t)seeded; w[DF_TOTALS + 13] = (uint32_t)(seeded >> 32);
+    HIP_TRY(hipMemcpy(e->d_dfPool + (size_t)3 * alive, records, m * sizeof(SphDiffuse), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_dfState, w, sizeof(w), hipMemcpyHostToDevice));
+    return SPH_OK;
+}
+int sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
+                          const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals) {
+    if (!cfg || !params || !countOut || (m && (!pool || !samples)) || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = diffuse_check_config(*cfg)) || (rc = validate_params(*params))) return rc;
+    const size_t C = cfg->capacity;
+    if (m > C) return fail(SPH_ERR_CAPACITY, "%zu diffuse records exceed the capacity of %zu", m, C);
+    if (C && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (params->param_pause) {
+        if (out != pool && m) std::memmove(out, pool, m * sizeof(SphDiffuse));
+        *countOut = m;
+        return SPH_OK;
+    }
+    const float step = dt > 0.0f ? dt : params->param_timeStep;
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, step, k);
+    const float gmin[3] = {k.gminx, k.gminy, k.gminz};
+    const int dims[3] = {k.gx, k.gy, k.gz};
+    const sph::DiffuseBox box = sph::diffuse_box(gmin, k.cellSize, dims, k.gravx, k.gravy, k.gravz);
+    const sph::DiffuseCoef co = diffuse_coef_of(*cfg);
+    const uint32_t lo = (uint32_t)substep, hi = (uint32_t)(substep >> 32);
+    uint64_t died[5] = {0, 0, 0, 0, 0};
+    uint32_t kinds[3] = {0, 0, 0};
+    std::vector<SphDiffuse> next;
+    next.reserve(m);
+    for (size_t i = 0; i < m; ++i) {                                   // 1. advance, 3. the survivors in their order
+        sph::DiffuseRec r;
+        std::memcpy(&r, &pool[i], sizeof(r));
+        const SphSample& s = samples[i];
+        const int fate = sph::diffuse_move(co, box, step, s.vel[0], s.vel[1], s.vel[2], s.count, r);
+        died[fate] += 1;
+        if (fate != sph::DF_LIVES) continue;
+        SphDiffuse o;
+        std::memcpy(&o, &r, sizeof(o));
+        next.push_back(o);
+        kinds[r.kind] += 1u;
+    }
+    const size_t survivors = next.size();
+    uint64_t spawned = 0;
+    for (size_t i = 0; i < n; ++i) {                                   // 2. spawn, in id order
+        const SphParticle& p = particles[i];
+        const uint32_t flags = (p.isGhost == 1 ? F_GHOST1 : 0u) | (p.isGhost != 0 ? F_GHOSTNZ : 0u) | (p.isActive == 0 ? F_INACTIVE : 0u);
+        const float invRho = p.density > 0.0f ? 1.0f / p.density : 0.0f;
+        const uint32_t children = sph::diffuse_children(co, step, p.padA, flags, invRho, (uint32_t)i, lo, hi);
+        for (uint32_t q = 0; q < children; ++q) {
+            if (next.size() < C) {
+                const sph::DiffuseRec r = sph::diffuse_child(co, k.h, p.pos[0], p.pos[1], p.pos[2], p.vel[0], p.vel[1], p.vel[2], (uint32_t)i, lo, hi, q);
+                SphDiffuse o;
+                std::memcpy(&o, &r, sizeof(o));
+                next.push_back(o);
+            }
+        }
+        spawned += children;
+    }
+    const uint64_t born = next.size() - survivors;
+    if (!next.empty()) std::memcpy(out, next.data(), next.size() * sizeof(SphDiffuse));
+    *countOut = next.size();
+    if (totals) {
+        totals->substeps += 1;
+        totals->spawned += spawned; totals->dropped += spawned - born;
+        totals->diedLife += died[sph::DF_DIED_LIFE]; totals->diedAge += died[sph::DF_DIED_AGE];
+        totals->leftBox += died[sph::DF_DIED_BOX]; totals->nonFinite += died[sph::DF_DIED_NONFINITE];
+        totals->alive = (uint32_t)next.size(); totals->capacity = (uint32_t)C;
+        totals->aliveByKind[0] = kinds[0]; totals->aliveByKind[1] = kinds[1] + (uint32_t)born; totals->aliveByKind[2] = kinds[2];
+    }
     return SPH_OK;
 }
 

@@ -81,6 +81,7 @@ SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_GRID_BUILD, SPH_OPT_AOS_MODE, SPH_OPT_TIMING, S
 SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = 5, 6
 SPH_OPT_MESH_SPLIT = 7
 SPH_OPT_SCALAR_SWEEP = 8
+SPH_OPT_DIFFUSE_TIMED = 9
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -152,6 +153,32 @@ assert C.sizeof(SphTracer) == 32
 TRACER_DTYPE = np.dtype(SphTracer)
 assert TRACER_DTYPE.itemsize == 32
 SPH_TRACER_EULER, SPH_TRACER_MIDPOINT = 0, 1
+
+
+class SphDiffuse(C.Structure):
+    """struct SphDiffuse of include/sph_abi.h: one spray, foam or bubble particle (see SPHFluidGPU.set_diffuse)."""
+    _fields_ = [("pos", C.c_float * 3), ("life", C.c_float), ("vel", C.c_float * 3), ("age", C.c_float),
+                ("parent", C.c_uint32), ("birth", C.c_uint32), ("kind", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SphDiffuseConfig(C.Structure):
+    """struct SphDiffuseConfig of include/sph_abi.h; diffuse_config() fills one."""
+    _fields_ = [("capacity", C.c_uint32), ("seed", C.c_uint32), ("threshold", C.c_float), ("rate", C.c_float), ("lifeMin", C.c_float),
+                ("lifeMax", C.c_float), ("spread", C.c_float), ("maxAge", C.c_float), ("sprayBelow", C.c_uint32), ("bubbleAbove", C.c_uint32),
+                ("kb", C.c_float), ("kd", C.c_float), ("maxPerParent", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+class SphDiffuseInfo(C.Structure):
+    """struct SphDiffuseInfo of include/sph_abi.h: the device counter, the alive count and the running totals of the pool."""
+    _fields_ = [("substeps", C.c_uint64), ("spawned", C.c_uint64), ("dropped", C.c_uint64), ("diedLife", C.c_uint64), ("diedAge", C.c_uint64),
+                ("leftBox", C.c_uint64), ("nonFinite", C.c_uint64), ("seeded", C.c_uint64), ("alive", C.c_uint32), ("capacity", C.c_uint32),
+                ("aliveByKind", C.c_uint32 * 3), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(SphDiffuse) == 48 and C.sizeof(SphDiffuseConfig) == 64 and C.sizeof(SphDiffuseInfo) == 88
+DIFFUSE_DTYPE = np.dtype(SphDiffuse)
+assert DIFFUSE_DTYPE.itemsize == 48
+SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE = 0, 1, 2
 
 
 SPH_MAX_SCALAR_CHANNELS = 4
@@ -347,6 +374,15 @@ _ABI = {
     "sph_scalars_get_sources": (_int, [_vp, _vp, _int, _pi]),
     "sph_scalars_injected": (_int, [_vp, _vp, _vp, _int, _P(_d), _P(_u64), _int]),
     "sph_scalars_couple_host": (_int, [_vp, _sz, _pp, _f, _vp, _int, _pf, _pf, _vp, _int, _vp, _int, _vp, _vp]),
+    # spray, foam and bubbles
+    "sph_diffuse_default": (None, [_P(SphDiffuseConfig)]),
+    "sph_diffuse_set": (_int, [_vp, _P(SphDiffuseConfig)]),
+    "sph_diffuse_get": (_int, [_vp, _P(SphDiffuseConfig)]),
+    "sph_diffuse_info": (_int, [_vp, _P(SphDiffuseInfo)]),
+    "sph_diffuse_download": (_int, [_vp, _vp, _sz, _P(_sz)]),
+    "sph_diffuse_device": (_int, [_vp, _P(_vp), _P(_vp)]),
+    "sph_diffuse_seed": (_int, [_vp, _vp, _sz]),
+    "sph_diffuse_step_host": (_int, [_P(SphDiffuseConfig), _pp, _f, _u64, _vp, _sz, _vp, _vp, _sz, _vp, _P(_sz), _P(SphDiffuseInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -1140,6 +1176,46 @@ class SPHFluidGPU:
         _check(self._L.sph_tracers_device(self._h, C.byref(p)))
         return int(p.value or 0)
 
+    # -- spray, foam and bubbles (include/sph_abi.h "spray, foam and bubbles") --------------------
+    def set_diffuse(self, config=None, **overrides):
+        """Switch secondary particles on: config is a SphDiffuseConfig (diffuse_config()) or None for the
+        defaults, overrides name its fields.  The capacity of the pool in place keeps the pool and replaces the coefficients."""
+        cfg = diffuse_config(**overrides) if config is None else _copy_config(config, overrides)
+        _check(self._L.sph_diffuse_set(self._h, C.byref(cfg)))
+
+    def clear_diffuse(self):
+        _check(self._L.sph_diffuse_set(self._h, None))
+
+    def diffuse_config(self) -> "SphDiffuseConfig":
+        """The config in force (capacity 0 without a pool)."""
+        cfg = SphDiffuseConfig()
+        _check(self._L.sph_diffuse_get(self._h, C.byref(cfg)))
+        return cfg
+
+    def diffuse_info(self) -> dict:
+        """Counter, alive count and running totals of the pool as a dict of ints (aliveByKind: a list).  Synchronises."""
+        info = SphDiffuseInfo()
+        _check(self._L.sph_diffuse_info(self._h, C.byref(info)))
+        return _info_dict(info)
+
+    def diffuse(self) -> np.ndarray:
+        """The living records in pool order: a structured array of DIFFUSE_DTYPE.  Synchronises."""
+        out = np.zeros(max(int(self.diffuse_config().capacity), 1), DIFFUSE_DTYPE)
+        n = C.c_size_t()
+        _check(self._L.sph_diffuse_download(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def diffuse_device(self):
+        """(records, aliveCountWord): borrowed device addresses of the 48-byte records and of the alive count (0, 0 without a pool)."""
+        r, a = C.c_void_p(), C.c_void_p()
+        _check(self._L.sph_diffuse_device(self._h, C.byref(r), C.byref(a)))
+        return int(r.value or 0), int(a.value or 0)
+
+    def seed_diffuse(self, records):
+        """Caller-made DIFFUSE_DTYPE records behind the living ones, taken as they are.  Synchronises."""
+        rec = np.ascontiguousarray(records, DIFFUSE_DTYPE)
+        _check(self._L.sph_diffuse_seed(self._h, _ptr_or_none(rec), len(rec)))
+
     def tracer_history(self):
         """(first, array (count, M, 4)): the stored snapshots (x, y, z, age), oldest first, and the number of the first one.  Synchronises."""
         _, n, _ = self.tracer_info()
@@ -1517,6 +1593,63 @@ def write_pathlines_ply(path, history: np.ndarray) -> None:
         fh.write(head.encode("ascii"))
         fh.write(h.tobytes())
         fh.write(edges.tobytes())
+
+
+def write_points_ply(path, records: np.ndarray) -> None:
+    """Binary little-endian PLY of diffuse particles: one vertex (x, y, z, kind) per DIFFUSE_DTYPE record."""
+    r = np.ascontiguousarray(records, DIFFUSE_DTYPE)
+    v = np.empty(len(r), np.dtype([("pos", "<f4", (3,)), ("kind", "u1")], align=False))
+    v["pos"] = r["pos"]
+    v["kind"] = r["kind"]
+    head = ("ply\nformat binary_little_endian 1.0\ncomment spray 0, foam 1, bubbles 2 (DESIGN.md section 3j)\n"
+            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\nproperty uchar kind\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(head.encode("ascii"))
+        fh.write(v.tobytes())
+
+
+def _copy_config(config, overrides):
+    cfg = SphDiffuseConfig.from_buffer_copy(config)
+    for name, value in overrides.items():
+        if name not in dict(SphDiffuseConfig._fields_) or name == "pad":
+            raise SphError(f"SphDiffuseConfig has no field {name}")
+        setattr(cfg, name, value)
+    return cfg
+
+
+def diffuse_config(**overrides) -> SphDiffuseConfig:
+    """sph_diffuse_default with the named fields replaced.  No device is needed."""
+    cfg = SphDiffuseConfig()
+    load_library().sph_diffuse_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def _info_dict(info) -> dict:
+    out = {name: int(getattr(info, name)) for name, _ in SphDiffuseInfo._fields_ if name not in ("aliveByKind", "pad")}
+    out["aliveByKind"] = [int(x) for x in info.aliveByKind]
+    return out
+
+
+def diffuse_step_host(config, params, pool, samples, particles, substep: int, dt: float = -1.0, totals=None):
+    """sph_diffuse_step_host: (pool one substep later, totals dict).  pool: DIFFUSE_DTYPE records, samples: the SAMPLE_DTYPE records at
+    their positions, particles: the state the substep starts from, substep: the counter before the step, totals: the dict a previous
+    call returned (or None for zeros).  No device is needed."""
+    src = np.ascontiguousarray(pool, DIFFUSE_DTYPE)
+    smp = np.ascontiguousarray(samples, SAMPLE_DTYPE)
+    if len(smp) != len(src):
+        raise SphError(f"{len(smp)} samples for {len(src)} diffuse records")
+    rec = np.ascontiguousarray(particles, PARTICLE_DTYPE)
+    out = np.zeros(max(min(int(config.capacity), len(src) + 8 * len(rec)), 1), DIFFUSE_DTYPE)
+    info = SphDiffuseInfo()
+    for name, value in (totals or {}).items():
+        if name == "aliveByKind":
+            info.aliveByKind[:] = list(value)
+        else:
+            setattr(info, name, value)
+    n = C.c_size_t()
+    _check(load_library().sph_diffuse_step_host(C.byref(config), C.byref(params), float(dt), int(substep), _ptr_or_none(src), len(src),
+                                                _ptr_or_none(smp), _ptr_or_none(rec), len(rec), _ptr(out), C.byref(n), C.byref(info)))
+    return out[:n.value].copy(), _info_dict(info)
 
 
 def obstacles_apply_host(obstacles, particle_mass: float, particles: np.ndarray):

@@ -238,6 +238,21 @@ public:
         out4.resize(size_t(n) * sph_tracers_count(engine));
         return !Check(sph_tracers_history(engine, out4.empty() ? nullptr : &out4[0].x, n, &snapshots, &firstSnapshot), "sph_tracers_history");
     }
+    // Spray, foam and bubbles (engine extension, sph_abi.h "spray, foam and bubbles"): secondary particles that
+    // every substep from now on spawns where the fluid foams, classes, moves, ages and removes on the device.  A config with capacity 0
+    // drops the pool; DiffuseConfig() returns the defaults to edit.  Return false on error (LastError()).
+    static SphDiffuseConfig DiffuseConfig() { SphDiffuseConfig c; sph_diffuse_default(&c); return c; }
+    bool SetDiffuse(const SphDiffuseConfig& config) { return !Check(sph_diffuse_set(engine, &config), "sph_diffuse_set"); }
+    bool DownloadDiffuse(std::vector<SphDiffuse>& out) {
+        SphDiffuseInfo info;
+        if (Check(sph_diffuse_info(engine, &info), "sph_diffuse_info")) return false;
+        out.resize(info.alive);
+        size_t n = 0;
+        if (Check(sph_diffuse_download(engine, out.empty() ? nullptr : out.data(), out.size(), &n), "sph_diffuse_download")) return false;
+        out.resize(n);
+        return true;
+    }
+    bool DiffuseInfo(SphDiffuseInfo& out) { return !Check(sph_diffuse_info(engine, &out), "sph_diffuse_info"); }
     // Diffusing scalar channels (engine extension, sph_abi.h "diffusing scalar fields"): K <= SPH_MAX_SCALAR_CHANNELS
     // floats per particle, particle-major in the caller's order, that move with their particles and diffuse between neighbours inside
     // every substep from now on.  values empty: channel 0 is seeded from padB (the dye), the others with 0; channels == 0 drops the set.

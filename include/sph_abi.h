@@ -45,6 +45,8 @@ extern "C" {
     _step_host, sph_volume_moments / _host -- dynamic rigid bodies) */
 /* (still 4, additions only: SphScalarSource, SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_*, sph_scalar_source_default, sph_scalars_set_buoyancy / _get_buoyancy /
     _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
+/* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
+    _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -148,6 +150,7 @@ enum {
     SPH_OPT_GRAPH = 5,           /* 1 = sph_dispatch_n replays a hipGraph once the same call (same members, options, substep count) has been seen twice; default 0 */
     SPH_OPT_MESH_SPLIT = 7,      /* sph_mesh_distance: 0 = the engine chooses into how many ranges the triangles are split (default), 1..64 = that many (capped at one per 256 triangles); same bits */
     SPH_OPT_SCALAR_SWEEP = 8,    /* scalar channels (sph_scalars_*): 0 = the sweep walks global memory (default, the bit-level yardstick), 1 = a block of 256 consecutive slots stages its candidate rows in LDS first; same bits */
+    SPH_OPT_DIFFUSE_TIMED = 9,   /* diffuse particles (sph_diffuse_*), measurements only: which launches of a substep the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = the advance kernel, 2 = the spawn side (count, scans, compaction, emit, tick); the launches themselves are the same */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -721,6 +724,87 @@ int  sph_scalars_injected(SphEngine* e, double* sums, uint64_t* hits, int cap, d
 int  sph_scalars_couple_host(SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels,
                              const float* beta, const float* ref, const SphScalarSource* sources, int nSources,
                              const SphObstacle* obstacles, int nObstacles, double* sumsOut, uint64_t* hitsOut);
+
+/* ---- spray, foam and bubbles: secondary particles spawned by the fluid (no reference counterpart) -----------
+ * Secondary ("diffuse") particles in the sense of Ihmsen et al. 2012, reduced to what the engine's state supports: points that do not
+ * act on the fluid, born where the fluid foams (padA, the foam factor every substep computes), classed every substep by how much fluid
+ * surrounds them, moved by class, aged and removed.  Off by default; with no pool set a dispatch launches exactly what it launched before.
+ * The pool is a SEQUENCE of at most `capacity` records.  One substep, on the state the substep STARTS from (behind the grid build, in
+ * front of the SPH pass and of the fountain / river recycle), with u = vel and n = count of the SphSample that sph_sample_points gives at
+ * the record's position, g the params' gravity, every fp32 expression a multiply and then an add (no fma), in the order written:
+ *   1. advance  n < sprayBelow: spray   v' = v + dt g;                                  x' = x + dt v'
+ *               n > bubbleAbove: bubble v' = (v - (dt kb) g) + kd (u - v);              x' = x + dt v'
+ *               otherwise: foam         v' = u;  x' = x + dt u;  life' = life - dt
+ *               age' = age + dt for every class; kind = the class.  The record dies, counted under the FIRST cause that holds, if a
+ *               coordinate of x' is not finite, x' lies outside the grid's box [gridMin, gridMin + (float)dims * cellSize] (bounds
+ *               included), not life' > 0, age' > maxAge.
+ *   2. spawn    a fluid particle (isGhost == 0; isActive says something about ghosts only, the spawners write 0) with density > 0 (read as
+ *               the sorted copy's 1/rho > 0) and a finite padA > threshold has min(floor((rate dt) (padA - threshold) + U_0), maxPerParent)
+ *               children; child k is born at pos + (spread h) (2 U - 1) per axis (U_{1+4k}, U_{2+4k}, U_{3+4k}) with the parent's velocity,
+ *               life = lifeMin + U_{4+4k} (lifeMax - lifeMin), age 0, parent = the particle's id, birth = the low word of the substep
+ *               counter, kind = SPH_DIFFUSE_FOAM until its first substep classes it.  U_d = (hash >> 8) 2^-24 with hash =
+ *               mix(mix(mix(mix(mix(seed + 0x9e3779b9) ^ id) ^ counterLow) ^ counterHigh) ^ d), mix(x): x ^= x >> 16; x *= 0x7feb352d;
+ *               x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 -- no state is carried.
+ *   3. order    the survivors keep their relative order; the newborn follow in (parent id ascending, k ascending); newborn that would
+ *               exceed the capacity are dropped from the END of that order and counted.
+ *   4. the 64-bit substep counter and the running totals advance (device memory).
+ * Hence the pool after n substeps equals, bit for bit and order included, the host loop
+ *   s = sph_sample_points(pool positions); P = sph_download_particles; sph_dispatch(dt); pool = sph_diffuse_step_host(pool, s, P, ...)
+ * also through sph_dispatch_n and captured graphs, and the particle records are byte-identical with and without a pool.
+ * param_pause: nothing happens.  Impulses, uploads and sph_set_params do not touch the pool; sph_reset drops it.  Timed as SPH_K_OTHER.
+ * SPH_ERR_STATE from sph_diffuse_set, before anything is allocated, on z-slab engines and under SPH_OPT_GRID_BUILD 1; setting
+ * SPH_OPT_GRID_BUILD 1 while a pool exists makes the next dispatch fail with SPH_ERR_STATE and change nothing.  SPH_ERR_ARG (the previous
+ * config stays in force): a rate, lifeMin, lifeMax or spread that is not finite or negative, lifeMax < lifeMin, maxPerParent outside
+ * 1 .. 8, sprayBelow > bubbleAbove, kd outside [0, 1], a threshold or kb that is not finite, a maxAge that is NaN or negative, a capacity
+ * above 2^31 - 1. */
+typedef struct SphDiffuse { float pos[3]; float life; float vel[3]; float age; uint32_t parent; uint32_t birth; uint32_t kind; uint32_t pad; } SphDiffuse;   /* 48 bytes */
+enum { SPH_DIFFUSE_SPRAY = 0, SPH_DIFFUSE_FOAM = 1, SPH_DIFFUSE_BUBBLE = 2 };
+typedef struct SphDiffuseConfig {
+    uint32_t capacity;       /* C: records the pool can hold (0: no pool) */
+    uint32_t seed;           /* of the hash */
+    float    threshold;      /* padA above which a particle spawns */
+    float    rate;           /* children per second and unit of padA above the threshold */
+    float    lifeMin, lifeMax;   /* seconds; only foam loses life */
+    float    spread;         /* half width of the birth cube in units of h */
+    float    maxAge;         /* seconds; bounds every class */
+    uint32_t sprayBelow;     /* n below this: spray */
+    uint32_t bubbleAbove;    /* n above this: bubble */
+    float    kb;             /* buoyancy of a bubble in units of gravity */
+    float    kd;             /* drag of a bubble towards the fluid's velocity per substep, 0 .. 1 */
+    uint32_t maxPerParent;   /* 1 .. 8 */
+    uint32_t pad[3];
+} SphDiffuseConfig;          /* 64 bytes */
+typedef struct SphDiffuseInfo {
+    uint64_t substeps;       /* the device counter: substeps that stepped this pool */
+    uint64_t spawned, dropped, diedLife, diedAge, leftBox, nonFinite;   /* running totals since the pool was made */
+    uint64_t seeded;         /* records sph_diffuse_seed put in: alive == seeded + spawned - dropped - the four deaths */
+    uint32_t alive, capacity;
+    uint32_t aliveByKind[3]; /* by the records' kind after the last substep */
+    uint32_t pad;
+} SphDiffuseInfo;            /* 88 bytes */
+/* The defaults DESIGN.md section 3j argues for (capacity 65536). */
+void sph_diffuse_default(SphDiffuseConfig* out);
+/* NULL or capacity 0 drops the pool.  The capacity of the pool in place: the pool stays and the coefficients are replaced (stream-ordered,
+ * no re-capture of a graph); another capacity: a new, empty pool with counters at zero. */
+int  sph_diffuse_set(SphEngine* e, const SphDiffuseConfig* cfg);
+/* The config in force (capacity 0 without a pool). */
+int  sph_diffuse_get(SphEngine* e, SphDiffuseConfig* out);
+/* Counter, alive count and totals (zeros without a pool).  Synchronises. */
+int  sph_diffuse_info(SphEngine* e, SphDiffuseInfo* out);
+/* The living records in pool order to HOST memory (cap >= alive, else SPH_ERR_CAPACITY, nothing written).  Synchronises. */
+int  sph_diffuse_download(SphEngine* e, SphDiffuse* out, size_t cap, size_t* countOut);
+/* Borrowed device addresses of the records and of the word that holds the alive count (null without a pool); valid until the pool is
+ * dropped or re-made.  A kernel of the host's on the engine's stream sees the pool after the last enqueued substep. */
+int  sph_diffuse_device(SphEngine* e, const SphDiffuse** records, const uint32_t** aliveCountWord);
+/* m caller-made records behind the living ones, for tests and for emitters of the host's own (alive + m <= capacity, else
+ * SPH_ERR_CAPACITY, nothing written; SPH_ERR_STATE without a pool).  The records are taken as they are.  Synchronises. */
+int  sph_diffuse_seed(SphEngine* e, const SphDiffuse* records, size_t m);
+/* Host-only, no device: the same __host__ __device__ functions the kernels run, in plain loops.  pool[0 .. m) with samples[i] the SphSample
+ * at pool[i].pos, particles[0 .. n) the state the substep starts from (id = index), substep = the counter before the step; out needs room
+ * for cfg->capacity records.  totals (may be null) is advanced like the device's, `substeps` included.  dt <= 0: param_timeStep.
+ * param_pause: out = pool. */
+int  sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
+                           const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
