@@ -24,6 +24,7 @@
 #include "sph_kernels.h"
 #include "sph_walk.h"
 #include "sph_sample.h"
+#include "sph_neighbors.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
 #include "sph_diffuse.h"
@@ -239,6 +240,13 @@ struct SphEngine {
     // sph_sample_points (host arrays): device copies of the probes and of the results
     DevBuf<float4> d_sampleIn;
     DevBuf<SphSample> d_sampleOut;
+    // sph_neighbors_*: ids of the sorted slots, counts, tile sums / maxima / totals of the scan, and the lists themselves (CSR)
+    DevBuf<int32_t> d_nbIds, d_nbIndices;
+    DevBuf<uint32_t> d_nbCnt, d_nbTileMax;
+    DevBuf<unsigned long long> d_nbTileSums;
+    DevBuf<long long> d_nbOffsets;
+    SphNeighborInfo nbInfo{};               // kind 0: no lists
+    bool nbIndexed = false;                 // d_nbIndices holds nbInfo.total entries
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
     DevBuf<uint16_t> d_surfCode;
@@ -281,6 +289,7 @@ struct SphEngine {
     uint32_t *d_dfFlag = nullptr, *d_dfFlagStart = nullptr, *d_dfFlagSums = nullptr, *d_dfPart = nullptr;
     DevBuf<uint32_t> d_dfCnt, d_dfCntStart, d_dfCntSums;
     uint32_t dfC = 0;                    // capacity of the pool (0: none)
+    int optNbFill = 0;                   // SPH_OPT_NEIGHBORS_FILL: 0 = lane-owned stores (k_neighbors_fill), 1 = the wave-cooperative row write (same bits)
     int optDiffuseTimed = 0;             // SPH_OPT_DIFFUSE_TIMED: which launches of the substep the timing bracket covers (0 all, 1 advance, 2 the rest)
     SphDiffuseConfig dfCfg{};            // the config in force
 
@@ -445,6 +454,11 @@ void free_grid_buffers(SphEngine* e) {
 
 // One free function per feature (callers have drained the stream, or the function does): sph_destroy calls each.
 void sample_free(SphEngine* e) { e->d_sampleIn.release(); e->d_sampleOut.release(); }
+void neighbors_free(SphEngine* e) {
+    e->d_nbIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbTileMax.release(); e->d_nbTileSums.release(); e->d_nbOffsets.release();
+    e->nbInfo = SphNeighborInfo{};
+    e->nbIndexed = false;
+}
 void surface_free(SphEngine* e) {
     e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
     e->d_surfVerts.release(); e->d_surfTris.release();
@@ -1280,6 +1294,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_terrain);
     dev_free(e->d_stats);
     sample_free(e);
+    neighbors_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1316,6 +1331,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     if ((rc = validate_params(e->params))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
+    neighbors_free(e);                                                // (and the neighbour lists)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1356,6 +1372,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_MESH_SPLIT: if (value < 0 || value > 64) return fail(SPH_ERR_ARG, "bad value"); e->optMeshSplit = value; break;
     case SPH_OPT_SCALAR_SWEEP: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optScalarSweep = value; break;
     case SPH_OPT_DIFFUSE_TIMED: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optDiffuseTimed = value; break;
+    case SPH_OPT_NEIGHBORS_FILL: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optNbFill = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1379,6 +1396,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_MESH_SPLIT: *value = e->optMeshSplit; break;
     case SPH_OPT_SCALAR_SWEEP: *value = e->optScalarSweep; break;
     case SPH_OPT_DIFFUSE_TIMED: *value = e->optDiffuseTimed; break;
+    case SPH_OPT_NEIGHBORS_FILL: *value = e->optNbFill; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -2787,6 +2805,214 @@ int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[
                            (const float4*)e->d_sPV, e->d_cellStart, devOut);
     }
     HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+// ---- neighbour lists (sph_neighbors.h) -----------------------------------------------------------
+static_assert(sizeof(SphNeighborInfo) == 40, "SphNeighborInfo must be 40 bytes");
+static_assert(sizeof(long long) == sizeof(int64_t), "offsets are int64");
+
+// Radius and flags as arguments: the stencil half-width through *stencil.
+static int neighbors_check(float radius, float cellSize, int flags, bool query, int* stencil) {
+    if (flags & ~(SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF | SPH_NEIGHBORS_COUNT_ONLY)) return fail(SPH_ERR_ARG, "unknown neighbour flags %d", flags);
+    if ((flags & SPH_NEIGHBORS_SELF) && (flags & SPH_NEIGHBORS_HALF)) return fail(SPH_ERR_ARG, "SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF: a half list has no diagonal");
+    if (query && (flags & (SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF))) return fail(SPH_ERR_ARG, "SPH_NEIGHBORS_SELF / _HALF apply to particle lists only");
+    *stencil = sph::neighbor_stencil(radius, cellSize);
+    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
+    return SPH_OK;
+}
+
+// Grid of the current state, ids, count, scan, one synchronisation for the total, then the fill (arguments already checked for null).
+static int neighbors_run(SphEngine* e, const float4* devPoints, size_t m, float radius, int flags, uint64_t maxPairs, SphNeighborInfo* out) {
+    using namespace sph;
+    const bool query = devPoints != nullptr || m != 0;
+    SimK k;
+    int rc, stencil = 0;
+    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
+    if ((rc = validate_params(e->params))) return rc;
+    {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        if ((rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
+    }
+    const size_t n = e->n, rows = query ? m : n;
+    const int tiles = blocks_for(rows, kScanTile);
+    e->nbInfo = SphNeighborInfo{};                                                  // (the lists held so far end here)
+    e->nbIndexed = false;
+    if ((rc = e->d_nbIds.grow(e, n)) || (rc = e->d_nbCnt.grow(e, rows)) || (rc = e->d_nbOffsets.grow(e, rows + 1)) ||
+        (rc = e->d_nbTileSums.grow(e, (size_t)tiles + 2)) || (rc = e->d_nbTileMax.grow(e, (size_t)tiles))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    NbK nb;
+    nb.R2 = radius * radius;
+    nb.s = stencil;
+    nb.flags = flags;
+    nb.idBase = e->idBase;
+    nb.n = (uint32_t)n;
+    unsigned long long* totals = e->d_nbTileSums.p + tiles;                         // (sum, largest count) behind the tile sums
+    const dim3 grid(blocks_for(rows)), block(kBlock);
+    auto walk = [&](bool fill) {
+        Timed t(e, SPH_K_OTHER);
+        if (query && fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (query && fill) hipLaunchKernelGGL((k_neighbors_fill<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (query) hipLaunchKernelGGL((k_neighbors_count<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, e->d_nbCnt.p);
+        else if (fill) hipLaunchKernelGGL((k_neighbors_fill<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else hipLaunchKernelGGL((k_neighbors_count<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, e->d_nbCnt.p);
+    };
+    unsigned long long host[2] = {0ull, 0ull};
+    if (rows) {
+        if (n) {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(n)), block, 0, e->stream, (const float4*)e->d_sOwn, e->d_nbIds.p, e->idBase, (uint32_t)n);
+        }
+        walk(false);                                                                // (writes cnt[row] of every row)
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_nbCnt.p, rows, e->d_nbTileSums.p, e->d_nbTileMax.p);
+            hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, e->d_nbTileSums.p, (const uint32_t*)e->d_nbTileMax.p, tiles, totals);
+            hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_nbCnt.p, rows, (const unsigned long long*)e->d_nbTileSums.p,
+                               (const unsigned long long*)totals, e->d_nbOffsets.p);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(e->d_nbOffsets.p, 0, sizeof(long long), e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphNeighborInfo info{};
+    info.rows = rows; info.total = host[0]; info.radius = radius; info.stencil = stencil; info.flags = flags; info.kind = query ? 2 : 1;
+    info.maxCount = (uint32_t)host[1];
+    e->nbInfo = info;
+    if (out) *out = info;
+    if (maxPairs && info.total > maxPairs)
+        return fail(SPH_ERR_CAPACITY, "%llu neighbour pairs exceed maxPairs %llu (offsets are valid, no indices were written)", (unsigned long long)info.total, (unsigned long long)maxPairs);
+    if (flags & SPH_NEIGHBORS_COUNT_ONLY) return SPH_OK;
+    if ((rc = e->d_nbIndices.grow(e, (size_t)info.total))) return rc;
+    if (rows && info.total) walk(true);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->nbIndexed = true;
+    return SPH_OK;
+}
+
+int sph_neighbors_build(SphEngine* e, float radius, int flags, uint64_t maxPairs, SphNeighborInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    return neighbors_run(e, nullptr, 0, radius, flags, maxPairs, out);
+}
+
+int sph_neighbors_query(SphEngine* e, const float* devPoints4, size_t m, float radius, int flags, uint64_t maxPairs, SphNeighborInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || !devPoints4) return fail(SPH_ERR_ARG, "null argument");
+    if (m == 0 || m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (1 .. 2^31 - 1)", m);
+    return neighbors_run(e, reinterpret_cast<const float4*>(devPoints4), m, radius, flags, maxPairs, out);
+}
+
+int sph_neighbors_info(const SphEngine* e, SphNeighborInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    *out = e->nbInfo;
+    return SPH_OK;
+}
+
+int sph_neighbors_device(SphEngine* e, const int64_t** offsets, const int32_t** indices) {
+    if (!e || !offsets || !indices) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->nbInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no neighbour lists");
+    *offsets = reinterpret_cast<const int64_t*>(e->d_nbOffsets.p);
+    *indices = e->nbIndexed ? e->d_nbIndices.p : nullptr;
+    return SPH_OK;
+}
+
+static int neighbors_copy(SphEngine* e, int64_t* offsets, int32_t* indices, uint64_t indexCap, hipMemcpyKind kind) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!offsets || (e->nbIndexed && e->nbInfo.total && !indices)) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->nbInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no neighbour lists");
+    if (e->nbIndexed && indexCap < e->nbInfo.total)
+        return fail(SPH_ERR_CAPACITY, "room for %llu indices, the lists hold %llu", (unsigned long long)indexCap, (unsigned long long)e->nbInfo.total);
+    HIP_TRY(hipMemcpyAsync(offsets, e->d_nbOffsets.p, ((size_t)e->nbInfo.rows + 1) * sizeof(int64_t), kind, e->stream));
+    if (e->nbIndexed && e->nbInfo.total) HIP_TRY(hipMemcpyAsync(indices, e->d_nbIndices.p, (size_t)e->nbInfo.total * sizeof(int32_t), kind, e->stream));
+    return SPH_OK;
+}
+int sph_neighbors_export(SphEngine* e, int64_t* devOffsets, int32_t* devIndices, uint64_t indexCap) {
+    return neighbors_copy(e, devOffsets, devIndices, indexCap, hipMemcpyDeviceToDevice);
+}
+int sph_neighbors_download(SphEngine* e, int64_t* offsets, int32_t* indices, uint64_t indexCap) {
+    int rc;
+    if ((rc = neighbors_copy(e, offsets, indices, indexCap, hipMemcpyDeviceToHost))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m,
+                       float radius, int flags, int64_t* offsets, int32_t* indices, uint64_t indexCap, SphNeighborInfo* out) {
+    if (!params || !offsets || !out || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    int rc, stencil = 0;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
+    const float R2 = radius * radius;
+    // the grid as the counting sort leaves it: cells ascending, members ascending by index
+    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
+    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
+        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
+        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        int cx, cy, cz;
+        cellOf(particles[i].pos, cx, cy, cz);
+        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+        start[cell[i] + 1] += 1u;
+    }
+    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
+    }
+    const size_t rows = query ? m : n;
+    // f(id) per kept entry of row r, in order
+    auto walk = [&](size_t r, auto&& f) {
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        if (query && !(sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2]))) return;
+        int cx, cy, cz;
+        cellOf(x, cx, cy, cz);
+        const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
+        for (int rr = 0; rr < w * w; ++rr) {
+            const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
+            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
+            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
+            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+                const float* y = particles[order[j]].pos;
+                const bool acc = sph::neighbor_accept(x[0], x[1], x[2], y[0], y[1], y[2], R2);
+                if (query ? acc : sph::neighbor_keep(flags, j == slotOf[r], acc, (uint32_t)r, order[j])) f(order[j]);
+            }
+        }
+    };
+    uint64_t total = 0;
+    uint32_t maxCount = 0;
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t c = 0;
+        offsets[r] = (int64_t)total;
+        walk(r, [&](uint32_t) { c += 1u; });
+        total += c;
+        maxCount = std::max(maxCount, c);
+    }
+    offsets[rows] = (int64_t)total;
+    SphNeighborInfo info{};
+    info.rows = rows; info.total = total; info.radius = radius; info.stencil = stencil; info.flags = flags; info.kind = query ? 2 : 1;
+    info.maxCount = maxCount;
+    *out = info;
+    if (flags & SPH_NEIGHBORS_COUNT_ONLY) return SPH_OK;
+    if (total > indexCap) return fail(SPH_ERR_CAPACITY, "room for %llu indices, the lists hold %llu", (unsigned long long)indexCap, (unsigned long long)total);
+    if (total && !indices) return fail(SPH_ERR_ARG, "null argument");
+    for (size_t r = 0; r < rows; ++r) {
+        int64_t w = offsets[r];
+        walk(r, [&](uint32_t id) { indices[w++] = (int32_t)id; });
+    }
     return SPH_OK;
 }
 

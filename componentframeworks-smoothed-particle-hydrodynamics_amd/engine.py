@@ -82,6 +82,7 @@ SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = 5, 6
 SPH_OPT_MESH_SPLIT = 7
 SPH_OPT_SCALAR_SWEEP = 8
 SPH_OPT_DIFFUSE_TIMED = 9
+SPH_OPT_NEIGHBORS_FILL = 10
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -243,6 +244,16 @@ SPH_SOURCE_SPHERE, SPH_SOURCE_BOX = 0, 1
 SPH_SOURCE_RATE, SPH_SOURCE_RELAX = 0, 1
 
 
+class SphNeighborInfo(C.Structure):
+    """struct SphNeighborInfo of include/sph_abi.h: what the engine's neighbour lists hold (see SPHFluidGPU.neighbors)."""
+    _fields_ = [("rows", C.c_uint64), ("total", C.c_uint64), ("radius", C.c_float), ("stencil", C.c_int32), ("flags", C.c_int32),
+                ("kind", C.c_int32), ("maxCount", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(SphNeighborInfo) == 40
+SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY = 1, 2, 4
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -383,6 +394,14 @@ _ABI = {
     "sph_diffuse_device": (_int, [_vp, _P(_vp), _P(_vp)]),
     "sph_diffuse_seed": (_int, [_vp, _vp, _sz]),
     "sph_diffuse_step_host": (_int, [_P(SphDiffuseConfig), _pp, _f, _u64, _vp, _sz, _vp, _vp, _sz, _vp, _P(_sz), _P(SphDiffuseInfo)]),
+    # neighbour lists
+    "sph_neighbors_build": (_int, [_vp, _f, _int, _u64, _P(SphNeighborInfo)]),
+    "sph_neighbors_query": (_int, [_vp, _vp, _sz, _f, _int, _u64, _P(SphNeighborInfo)]),
+    "sph_neighbors_info": (_int, [_vp, _P(SphNeighborInfo)]),
+    "sph_neighbors_device": (_int, [_vp, _P(_vp), _P(_vp)]),
+    "sph_neighbors_export": (_int, [_vp, _vp, _vp, _u64]),
+    "sph_neighbors_download": (_int, [_vp, _vp, _vp, _u64]),
+    "sph_neighbors_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _vp, _u64, _P(SphNeighborInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -504,6 +523,10 @@ def _points4(points, who, keep_w):
     k = pts.shape[1] if keep_w else 3
     p4[:, :k] = pts[:, :k]
     return p4
+
+
+def _neighbor_flags(self_, half, count_only) -> int:
+    return (SPH_NEIGHBORS_SELF if self_ else 0) | (SPH_NEIGHBORS_HALF if half else 0) | (SPH_NEIGHBORS_COUNT_ONLY if count_only else 0)
 
 
 def _is_cuda_f32(t) -> bool:
@@ -1059,6 +1082,65 @@ class SPHFluidGPU:
         pts[:, :, 2] = cols[:, None, 1]
         frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
         return gauge_levels(frac, ys, threshold)
+
+    # -- neighbour lists (include/sph_abi.h "fixed-radius neighbour lists") ------------------------
+    def neighbors(self, radius=None, self_=False, half=False, count_only=False, max_pairs: int = 0, device: bool = False):
+        """CSR neighbour lists of every particle within `radius` (None: param_h; at most three cells): (offsets int64[n + 1], indices
+        int32[total]) in the engine's order, ascending (cell index, particle id) per row; rows are numbered by particle id.  self_ keeps
+        the particle itself, half keeps only id_j > id_i, count_only returns indices None.  numpy arrays, or with device=True fresh
+        torch device tensors.  A total above max_pairs (> 0) raises SphError; neighbor_lists() then still gives the offsets."""
+        self._push_params()
+        info = SphNeighborInfo()
+        r = self._p.param_h if radius is None else radius
+        _check(self._L.sph_neighbors_build(self._h, float(r), _neighbor_flags(self_, half, count_only), int(max_pairs), C.byref(info)))
+        return self.neighbor_lists(device)
+
+    def query_neighbors(self, points, radius, count_only=False, max_pairs: int = 0, device: bool = False):
+        """The same for (m, 3) or (m, 4) query points: row i lists the particles within `radius` of points[i] (a torch device tensor of
+        (m, 4) float32 is used in place).  A point with a non-finite coordinate has an empty row."""
+        import torch
+        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
+            dev = points
+        else:
+            dev = torch.from_numpy(_points4(points, "query_neighbors", keep_w=False)).cuda()
+        self._push_params()
+        info = SphNeighborInfo()
+        _check(self._L.sph_neighbors_query(self._h, C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), _neighbor_flags(False, False, count_only),
+                                           int(max_pairs), C.byref(info)))
+        return self.neighbor_lists(device)
+
+    def neighbor_info(self) -> SphNeighborInfo:
+        """What the engine's lists hold: rows, total, radius, stencil, flags, kind (0 none, 1 particles, 2 query), maxCount."""
+        info = SphNeighborInfo()
+        _check(self._L.sph_neighbors_info(self._h, C.byref(info)))
+        return info
+
+    def neighbor_lists(self, device: bool = False):
+        """(offsets, indices) of the lists the engine holds; indices is None for count-only lists and after a max_pairs refusal."""
+        info = self.neighbor_info()
+        dp_off, dp_idx = C.c_void_p(), C.c_void_p()
+        _check(self._L.sph_neighbors_device(self._h, C.byref(dp_off), C.byref(dp_idx)))
+        rows, total = int(info.rows), int(info.total)
+        indexed = not (info.flags & SPH_NEIGHBORS_COUNT_ONLY) and bool(dp_idx.value)      # (a refused build lends no indices)
+        if device:
+            import torch
+            off = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
+            idx = torch.empty(total, dtype=torch.int32, device="cuda") if indexed else None
+            _check(self._L.sph_neighbors_export(self._h, C.c_void_p(off.data_ptr()), C.c_void_p(idx.data_ptr()) if total and indexed else None, total))
+            self.sync()
+            return off, idx
+        off = np.zeros(rows + 1, np.int64)
+        idx = np.zeros(total, np.int32) if indexed else None
+        _check(self._L.sph_neighbors_download(self._h, _ptr(off), _ptr(idx) if idx is not None else None, total))
+        return off, idx
+
+    def radius_graph(self, radius=None, half: bool = False):
+        """The neighbour relation as a (2, E) int64 torch device tensor [receiver, sender] (E = total; half: every undirected edge once,
+        receiver < sender), derived from the CSR lists on the device.  Edges stand in CSR order."""
+        import torch
+        off, idx = self.neighbors(radius, half=half, device=True)
+        recv = torch.repeat_interleave(torch.arange(off.numel() - 1, device=off.device), off[1:] - off[:-1])
+        return torch.stack((recv, idx.to(torch.int64)))
 
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
@@ -1650,6 +1732,29 @@ def diffuse_step_host(config, params, pool, samples, particles, substep: int, dt
     _check(load_library().sph_diffuse_step_host(C.byref(config), C.byref(params), float(dt), int(substep), _ptr_or_none(src), len(src),
                                                 _ptr_or_none(smp), _ptr_or_none(rec), len(rec), _ptr(out), C.byref(n), C.byref(info)))
     return out[:n.value].copy(), _info_dict(info)
+
+
+def neighbors_host(records, params, radius, points=None, self_=False, half=False, count_only=False):
+    """sph_neighbors_host: (offsets, indices) of SPHFluidGPU.neighbors (points None) or query_neighbors on host records, computed on the
+    CPU by the same accept function over a counting sort of its own.  No device is needed."""
+    L = load_library()
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    p4 = None if points is None else _points4(points, "neighbors_host", keep_w=False)
+    flags = _neighbor_flags(self_, half, count_only)
+    rows = len(rec) if p4 is None else len(p4)
+    off = np.zeros(rows + 1, np.int64)
+    info = SphNeighborInfo()
+    pp = _ptr(p4) if p4 is not None else None
+
+    def call(fl, idx, cap):
+        return L.sph_neighbors_host(_ptr(rec) if len(rec) else None, len(rec), C.byref(params), pp, rows if p4 is not None else 0, float(radius), fl,
+                                    _ptr(off), _ptr(idx) if idx is not None else None, cap, C.byref(info))
+    _check(call(flags | SPH_NEIGHBORS_COUNT_ONLY, None, 0))
+    if count_only:
+        return off, None
+    idx = np.zeros(int(info.total), np.int32)
+    _check(call(flags, idx, len(idx)))
+    return off, idx
 
 
 def obstacles_apply_host(obstacles, particle_mass: float, particles: np.ndarray):

@@ -163,6 +163,35 @@ public:
         const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
         return !Check(sph_sample_lattice(engine, o, s, dims, field, devOut), "sph_sample_lattice");
     }
+    // Neighbour lists (engine extension, sph_abi.h "fixed-radius neighbour lists"): CSR lists of the particles within
+    // `radius` (<= 0: param_h; at most three cells) of every particle (rows numbered by particle id) or of query points in DEVICE memory
+    // (4 floats each), in the engine's order.  flags: SPH_NEIGHBORS_SELF / _HALF / _COUNT_ONLY; maxPairs > 0 refuses larger lists.  The
+    // lists stay in the engine until the next call, ResetSimulation or the destructor; DownloadNeighbors copies them to the host
+    // (indices stays empty for count-only lists).  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    bool Neighbors(SphNeighborInfo& out, float radius = 0.0f, int flags = 0, uint64_t maxPairs = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_neighbors_build(engine, radius > 0.0f ? radius : param_h, flags, maxPairs, &out), "sph_neighbors_build");
+    }
+    bool QueryNeighbors(const float* devPoints4, size_t m, float radius, SphNeighborInfo& out, int flags = 0, uint64_t maxPairs = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_neighbors_query(engine, devPoints4, m, radius, flags, maxPairs, &out), "sph_neighbors_query");
+    }
+    SphNeighborInfo NeighborInfo() {
+        SphNeighborInfo info{};
+        Check(sph_neighbors_info(engine, &info), "sph_neighbors_info");
+        return info;
+    }
+    bool DownloadNeighbors(std::vector<int64_t>& offsets, std::vector<int32_t>& indices) {
+        const SphNeighborInfo info = NeighborInfo();
+        const int64_t* dOff = nullptr;
+        const int32_t* dIdx = nullptr;
+        if (Check(sph_neighbors_device(engine, &dOff, &dIdx), "sph_neighbors_device")) return false;
+        offsets.assign(size_t(info.rows) + 1, 0);
+        indices.assign(dIdx ? size_t(info.total) : 0, 0);
+        return !Check(sph_neighbors_download(engine, offsets.data(), dIdx ? indices.data() : nullptr, indices.size()), "sph_neighbors_download");
+    }
     // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
     // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
     // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per

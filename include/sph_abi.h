@@ -47,6 +47,7 @@ extern "C" {
     _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
 /* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
+/* (still 4, additions only: SphNeighborInfo, SPH_NEIGHBORS_*, sph_neighbors_build / _query / _info / _device / _export / _download / _host, SPH_OPT_NEIGHBORS_FILL -- neighbour lists) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -151,6 +152,7 @@ enum {
     SPH_OPT_MESH_SPLIT = 7,      /* sph_mesh_distance: 0 = the engine chooses into how many ranges the triangles are split (default), 1..64 = that many (capped at one per 256 triangles); same bits */
     SPH_OPT_SCALAR_SWEEP = 8,    /* scalar channels (sph_scalars_*): 0 = the sweep walks global memory (default, the bit-level yardstick), 1 = a block of 256 consecutive slots stages its candidate rows in LDS first; same bits */
     SPH_OPT_DIFFUSE_TIMED = 9,   /* diffuse particles (sph_diffuse_*), measurements only: which launches of a substep the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = the advance kernel, 2 = the spawn side (count, scans, compaction, emit, tick); the launches themselves are the same */
+    SPH_OPT_NEIGHBORS_FILL = 10, /* neighbour lists (sph_neighbors_*), an A/B of the fill kernel: 0 = every lane writes the entries of its own row (default), 1 = a wave writes one row at a time with consecutive lanes; the same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -805,6 +807,49 @@ int  sph_diffuse_seed(SphEngine* e, const SphDiffuse* records, size_t m);
  * param_pause: out = pool. */
 int  sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
                            const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals);
+
+/* ---- fixed-radius neighbour lists in CSR form (no reference counterpart) --------------------------------------
+ * The engine's neighbour relation as an output: for every particle, or for arbitrary query points, the particles within a radius R,
+ * on the device, in the engine's fixed order.  The grid is that of the CURRENT state, built exactly as sph_sample_points builds it
+ * (cells from BuildGrid's formula: (x - gridMin) / cellSize with IEEE division, floorf, clamp).  For 0 < R <= 3 * cellSize:
+ *   R2 = R * R in fp32; the stencil half-width s is the smallest of 1, 2, 3 with R <= (float)s * cellSize;
+ *   the candidates of a target in cell (cx, cy, cz) are the members of the cells [c - s, c + s] per axis that lie inside the grid;
+ *   candidate j is accepted when r2 < R2, r2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with d = x_target - x_j (at R = h: sweep 1's test
+ *   and the `count` of SphSample);
+ *   the accepted candidates stand in ascending sorted slot, i.e. ascending (cell index, particle id) -- for s = 1 the order the SPH
+ *   pass visits them; entries are particle ids (the index into the 80-byte array) as int32; rows are numbered by particle id
+ *   (particle lists) or by query point (query lists); offsets is int64[rows + 1] and offsets[rows] the total.
+ * Particle lists: the target's own slot is left out by default; SPH_NEIGHBORS_SELF keeps it (by slot identity, not by distance);
+ * SPH_NEIGHBORS_HALF keeps only id_j > id_i (an undirected edge list); SELF | HALF is SPH_ERR_ARG.  Every record has a row, ghosts and
+ * inactive records included.  Query lists: SELF and HALF are SPH_ERR_ARG; a point with a non-finite coordinate has an empty row.  A
+ * particle with a non-finite position is accepted by nobody (r2 is NaN).  SPH_NEIGHBORS_COUNT_ONLY builds offsets and maxCount only.
+ * Bit for bit: the relation is symmetric (j in N(i) <=> i in N(j)), and at R = h with SELF the length of row i equals the `count` of
+ * sph_sample_points at particle i's position.
+ * The lists are engine-owned and stay valid until the next sph_neighbors_build / _query, sph_reset or sph_destroy; a dispatch does not
+ * touch them (they describe the state they were built from) and a build never changes the simulation.  maxPairs > 0 and a total above
+ * it: SPH_ERR_CAPACITY after the count pass, *out filled, offsets valid, no index buffer.  Timed as SPH_K_OTHER (the grid build under
+ * bin / scan / scatter).  SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1, as sampling.  SPH_ERR_ARG: a null argument, an R that
+ * is not finite, <= 0 or above 3 * cellSize, unknown flag bits, more than 2^31 - 1 query points. */
+enum { SPH_NEIGHBORS_SELF = 1, SPH_NEIGHBORS_HALF = 2, SPH_NEIGHBORS_COUNT_ONLY = 4 };
+typedef struct SphNeighborInfo { uint64_t rows, total; float radius; int32_t stencil, flags, kind /*0 none, 1 particles, 2 query*/; uint32_t maxCount, pad; } SphNeighborInfo;   /* 40 bytes */
+/* Lists of every particle.  Synchronises. */
+int sph_neighbors_build(SphEngine* e, float radius, int flags, uint64_t maxPairs, SphNeighborInfo* out);
+/* Lists of m query points of 4 floats (x, y, z, unused) in DEVICE memory.  Synchronises. */
+int sph_neighbors_query(SphEngine* e, const float* devPoints4, size_t m, float radius, int flags, uint64_t maxPairs, SphNeighborInfo* out);
+/* What the engine holds (kind 0 before any build). */
+int sph_neighbors_info(const SphEngine* e, SphNeighborInfo* out);
+/* Borrowed device addresses: offsets[rows + 1], indices[total] (null for count-only or refused lists).  SPH_ERR_STATE without lists. */
+int sph_neighbors_device(SphEngine* e, const int64_t** offsets, const int32_t** indices);
+/* Device-to-device copies into the caller's memory on the engine's stream (asynchronous), and copies to HOST memory (synchronises).
+ * SPH_ERR_STATE without lists; SPH_ERR_CAPACITY (nothing written) if indexCap is below the total; SPH_ERR_ARG for a null offsets, or a
+ * null indices while the engine holds at least one (count-only, refused and empty lists hold none: indices is then ignored). */
+int sph_neighbors_export(SphEngine* e, int64_t* devOffsets, int32_t* devIndices, uint64_t indexCap);
+int sph_neighbors_download(SphEngine* e, int64_t* offsets, int32_t* indices, uint64_t indexCap);
+/* Host-only, no device: the same neighbor_accept over a counting sort of its own (cells ascending, members ascending by index).
+ * points4 NULL: particle lists of particles[0 .. n) (m ignored); else query lists of m points.  offsets needs rows + 1 entries;
+ * a total above indexCap: SPH_ERR_CAPACITY with *out filled and offsets valid (so a COUNT_ONLY call sizes the second one). */
+int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m,
+                       float radius, int flags, int64_t* offsets, int32_t* indices, uint64_t indexCap, SphNeighborInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
