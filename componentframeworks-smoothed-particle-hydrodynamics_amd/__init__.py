@@ -25,5 +25,7 @@ from .engine import (  # noqa: F401
     SPH_OPT_DIFFUSE_TIMED, SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE, SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, DIFFUSE_DTYPE, diffuse_config,
     diffuse_step_host, write_points_ply,
     SPH_OPT_NEIGHBORS_FILL, SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY, SphNeighborInfo, neighbors_host,
+    SPH_OPT_COMPONENTS_VARIANT, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, SphComponent, SphComponentInfo, COMPONENT_DTYPE, components_host,
+    component_centers,
 )
 from . import build, synthetic  # noqa: F401

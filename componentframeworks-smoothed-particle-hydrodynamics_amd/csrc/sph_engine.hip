@@ -25,6 +25,7 @@
 #include "sph_walk.h"
 #include "sph_sample.h"
 #include "sph_neighbors.h"
+#include "sph_components.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
 #include "sph_diffuse.h"
@@ -247,6 +248,16 @@ struct SphEngine {
     DevBuf<long long> d_nbOffsets;
     SphNeighborInfo nbInfo{};               // kind 0: no lists
     bool nbIndexed = false;                 // d_nbIndices holds nbInfo.total entries
+    // sph_components_*: per sorted slot the particle id, the union-find parent and the tree's smallest id; per particle id labels, roots and the
+    // root flags with their scan (offsets, tile sums / maxima); the table; the words of the launches (changed / more) and the table's reduction
+    DevBuf<int32_t> d_ccIds, d_ccLabels, d_ccRoots;
+    DevBuf<uint32_t> d_ccParent, d_ccMinId, d_ccFlag, d_ccTileMax, d_ccWords;
+    DevBuf<unsigned long long> d_ccTileSums, d_ccStats;
+    DevBuf<long long> d_ccOffsets;
+    DevBuf<sph::CcRow> d_ccTable;
+    SphComponentInfo ccInfo{};
+    bool ccValid = false;                   // the buffers hold the result ccInfo describes
+    int optCcVariant = 0;                   // SPH_OPT_COMPONENTS_VARIANT
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
     DevBuf<uint16_t> d_surfCode;
@@ -458,6 +469,12 @@ void neighbors_free(SphEngine* e) {
     e->d_nbIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbTileMax.release(); e->d_nbTileSums.release(); e->d_nbOffsets.release();
     e->nbInfo = SphNeighborInfo{};
     e->nbIndexed = false;
+}
+void components_free(SphEngine* e) {
+    e->d_ccIds.release(); e->d_ccLabels.release(); e->d_ccRoots.release(); e->d_ccParent.release(); e->d_ccMinId.release(); e->d_ccFlag.release();
+    e->d_ccTileMax.release(); e->d_ccWords.release(); e->d_ccTileSums.release(); e->d_ccStats.release(); e->d_ccOffsets.release(); e->d_ccTable.release();
+    e->ccInfo = SphComponentInfo{};
+    e->ccValid = false;
 }
 void surface_free(SphEngine* e) {
     e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
@@ -1295,6 +1312,7 @@ int sph_destroy(SphEngine* e) {
     dev_free(e->d_stats);
     sample_free(e);
     neighbors_free(e);
+    components_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1332,6 +1350,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     neighbors_free(e);                                                // (and the neighbour lists)
+    components_free(e);                                               // (and the components)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1373,6 +1392,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_SCALAR_SWEEP: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optScalarSweep = value; break;
     case SPH_OPT_DIFFUSE_TIMED: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optDiffuseTimed = value; break;
     case SPH_OPT_NEIGHBORS_FILL: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optNbFill = value; break;
+    case SPH_OPT_COMPONENTS_VARIANT: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optCcVariant = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1397,6 +1417,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_SCALAR_SWEEP: *value = e->optScalarSweep; break;
     case SPH_OPT_DIFFUSE_TIMED: *value = e->optDiffuseTimed; break;
     case SPH_OPT_NEIGHBORS_FILL: *value = e->optNbFill; break;
+    case SPH_OPT_COMPONENTS_VARIANT: *value = e->optCcVariant; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -3013,6 +3034,288 @@ int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* 
         int64_t w = offsets[r];
         walk(r, [&](uint32_t id) { indices[w++] = (int32_t)id; });
     }
+    return SPH_OK;
+}
+
+// ---- connected components (sph_components.h) -----------------------------------------------------
+static_assert(sizeof(SphComponent) == 64 && sizeof(SphComponent) == sizeof(sph::CcRow), "SphComponent must be 64 bytes");
+static_assert(offsetof(SphComponent, bbMin) == offsetof(sph::CcRow, bbMin) && offsetof(SphComponent, sumQ) == offsetof(sph::CcRow, sumQ) &&
+              offsetof(SphComponent, flags) == offsetof(sph::CcRow, flags), "CcRow is the device view of SphComponent");
+static_assert(sizeof(SphComponentInfo) == 56, "SphComponentInfo must be 56 bytes");
+
+static int components_check(float radius, float cellSize, int flags, int* stencil) {
+    if (flags & ~SPH_COMPONENTS_FLUID_ONLY) return fail(SPH_ERR_ARG, "unknown component flags %d", flags);
+    *stencil = sph::neighbor_stencil(radius, cellSize);
+    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
+    return SPH_OK;
+}
+
+int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo* out) {
+    using namespace sph;
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    int rc, stencil = 0;
+    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
+    if ((rc = validate_params(e->params))) return rc;
+    SphGridInfo g;
+    sph::compute_grid_extents(e->params, g);
+    if ((rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
+    const size_t n = e->n;
+    const int tiles = blocks_for(n, kScanTile);
+    e->ccInfo = SphComponentInfo{};                                                 // (the result held so far ends here)
+    e->ccValid = false;
+    if ((rc = e->d_ccIds.grow(e, n)) || (rc = e->d_ccLabels.grow(e, n)) || (rc = e->d_ccRoots.grow(e, n)) || (rc = e->d_ccParent.grow(e, n)) ||
+        (rc = e->d_ccMinId.grow(e, n)) || (rc = e->d_ccFlag.grow(e, n)) || (rc = e->d_ccOffsets.grow(e, n + 1)) || (rc = e->d_ccTileSums.grow(e, (size_t)tiles + 2)) ||
+        (rc = e->d_ccTileMax.grow(e, (size_t)tiles)) || (rc = e->d_ccWords.grow(e, (size_t)kCcWords)) || (rc = e->d_ccStats.grow(e, 3))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    SphComponentInfo info{};
+    info.rows = n; info.radius = radius; info.stencil = stencil; info.flags = flags;
+    uint64_t C = 0;
+    if (n) {
+        NbK nb;
+        nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)n;
+        const dim3 grid(blocks_for(n)), block(kBlock);
+        const float4* pv = (const float4*)e->d_sPV;
+        const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
+        const int32_t* ids = e->d_ccIds.p;
+        uint32_t* parent = e->d_ccParent.p;
+        uint32_t* words = e->d_ccWords.p;
+        HIP_TRY(hipMemsetAsync(words, 0, (size_t)kCcWords * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_ccStats.p, 0, 3 * sizeof(unsigned long long), e->stream));
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_components_init, grid, block, 0, e->stream, (const float4*)e->d_sOwn, e->d_ccIds.p, parent, e->d_ccMinId.p, e->idBase, (uint32_t)n, flags);
+        }
+        // hook + compress until a whole hook launch finds every edge inside one tree; every launch has a word of its own
+        int word = 0;
+        auto compress = [&]() {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_components_compress, grid, block, 0, e->stream, parent, (uint32_t)n, words + word);
+            return word++;
+        };
+        bool done = false;
+        uint32_t rounds = 0;
+        while (!done && rounds < (uint32_t)kCcMaxRounds) {
+            const int hookWord = word++;
+            {
+                Timed t(e, SPH_K_OTHER);
+                if (e->optCcVariant & kCcFullWalk) hipLaunchKernelGGL((k_components_hook<false>), grid, block, 0, e->stream, k, nb, pv, cellStart, ids, parent, words + hookWord);
+                else hipLaunchKernelGGL((k_components_hook<true>), grid, block, 0, e->stream, k, nb, pv, cellStart, ids, parent, words + hookWord);
+            }
+            rounds += 1;
+            int jumpWord = compress();                                              // (queued before the hook's word is known: one round trip per round)
+            uint32_t got[2] = {0u, 0u};                                             // the hook's "changed", the compress launch's "more"
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(got, words + hookWord, sizeof(got), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            if (!got[0]) { done = true; break; }
+            for (int jumps = 1; got[1]; ++jumps) {
+                if (jumps >= kCcMaxJumps) return fail(SPH_ERR_STATE, "components: the trees were not flat after %d compress launches in round %u", jumps, rounds);
+                jumpWord = compress();
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(got + 1, words + jumpWord, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+                HIP_TRY(hipStreamSynchronize(e->stream));
+            }
+        }
+        if (!done) return fail(SPH_ERR_STATE, "components: no hook launch found every edge inside one tree within %u rounds", rounds);
+        info.rounds = rounds;
+        unsigned long long* totals = e->d_ccTileSums.p + tiles;
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_components_minid, grid, block, 0, e->stream, ids, (const uint32_t*)parent, e->d_ccMinId.p, (uint32_t)n);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_components_roots, grid, block, 0, e->stream, ids, (const uint32_t*)parent, (const uint32_t*)e->d_ccMinId.p, e->d_ccRoots.p, e->d_ccFlag.p, (uint32_t)n);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_ccFlag.p, n, e->d_ccTileSums.p, e->d_ccTileMax.p);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, e->d_ccTileSums.p, (const uint32_t*)e->d_ccTileMax.p, tiles, totals);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_ccFlag.p, n, (const unsigned long long*)e->d_ccTileSums.p,
+                               (const unsigned long long*)totals, e->d_ccOffsets.p);
+        }
+        unsigned long long host[2] = {0ull, 0ull};
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        C = host[0];
+        if (C > n) return fail(SPH_ERR_STATE, "components: %llu bodies of %zu records", (unsigned long long)C, n);
+        if ((rc = e->d_ccTable.grow(e, (size_t)C))) return rc;
+        const double S = 65536.0 / (double)k.cellSize;
+        if (C) {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_components_table_init, dim3(blocks_for((size_t)C)), block, 0, e->stream, e->d_ccTable.p, (uint32_t)C);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);                                                // (with C == 0 it still writes the labels: all -1)
+            if (e->optCcVariant & kCcLaneAtomics) hipLaunchKernelGGL((k_components_label<false>), grid, block, 0, e->stream, k, S, pv, ids, (const int32_t*)e->d_ccRoots.p, (const long long*)e->d_ccOffsets.p, e->d_ccLabels.p, e->d_ccTable.p, (uint32_t)n, (uint32_t)C);
+            else hipLaunchKernelGGL((k_components_label<true>), grid, block, 0, e->stream, k, S, pv, ids, (const int32_t*)e->d_ccRoots.p, (const long long*)e->d_ccOffsets.p, e->d_ccLabels.p, e->d_ccTable.p, (uint32_t)n, (uint32_t)C);
+        }
+        unsigned long long stats[3] = {0ull, 0ull, 0ull};
+        if (C) {
+            {
+                Timed t(e, SPH_K_OTHER);
+                hipLaunchKernelGGL(k_components_finish, dim3(blocks_for((size_t)C)), block, 0, e->stream, e->d_ccTable.p, (uint32_t)C, e->d_ccStats.p);
+            }
+            HIP_TRY(hipMemcpyAsync(stats, e->d_ccStats.p, sizeof(stats), hipMemcpyDeviceToHost, e->stream));
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        info.numComponents = C;
+        info.numExcluded = n - stats[2];
+        if (C) {
+            info.largestCount = stats[0] >> 32;
+            info.largestRoot = ~(uint32_t)(stats[0] & 0xffffffffull);
+            info.numSingletons = (uint32_t)stats[1];
+        }
+    }
+    e->ccInfo = info;
+    e->ccValid = true;
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_components_info(const SphEngine* e, SphComponentInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->ccValid) return fail(SPH_ERR_STATE, "the engine holds no components");
+    *out = e->ccInfo;
+    return SPH_OK;
+}
+
+int sph_components_device(SphEngine* e, const int32_t** labels, const int32_t** roots, const SphComponent** table) {
+    if (!e || !labels || !roots || !table) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->ccValid) return fail(SPH_ERR_STATE, "the engine holds no components");
+    *labels = e->d_ccLabels.p;
+    *roots = e->d_ccRoots.p;
+    *table = reinterpret_cast<const SphComponent*>(e->d_ccTable.p);
+    return SPH_OK;
+}
+
+int sph_components_download(SphEngine* e, int32_t* labels, int32_t* roots, SphComponent* table, uint64_t tableCap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->ccValid) return fail(SPH_ERR_STATE, "the engine holds no components");
+    const size_t n = (size_t)e->ccInfo.rows, C = (size_t)e->ccInfo.numComponents;
+    if (table && tableCap < C) return fail(SPH_ERR_CAPACITY, "room for %llu table rows, the engine holds %zu components", (unsigned long long)tableCap, C);
+    if (labels && n) HIP_TRY(hipMemcpyAsync(labels, e->d_ccLabels.p, n * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    if (roots && n) HIP_TRY(hipMemcpyAsync(roots, e->d_ccRoots.p, n * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    if (table && C) HIP_TRY(hipMemcpyAsync(table, e->d_ccTable.p, C * sizeof(SphComponent), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_components_host(const SphParticle* particles, size_t n, const SphParams* params, float radius, int flags,
+                        int32_t* labels, int32_t* roots, SphComponent* table, uint64_t tableCap, SphComponentInfo* out) {
+    if (!params || !out || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    int rc, stencil = 0;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
+    const float R2 = radius * radius;
+    const bool fluidOnly = (flags & SPH_COMPONENTS_FLUID_ONLY) != 0;
+    // the grid as the counting sort leaves it: cells ascending, members ascending by index (as sph_neighbors_host)
+    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
+    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
+        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
+        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        int cx, cy, cz;
+        cellOf(particles[i].pos, cx, cy, cz);
+        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+        start[cell[i] + 1] += 1u;
+    }
+    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
+    }
+    // a plain sequential union-find over particle ids: the smaller root wins, so a root is the smallest id of its tree
+    std::vector<uint32_t> parent(n);
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    auto find = [&](uint32_t x) {
+        uint32_t r = x;
+        while (parent[r] != r) r = parent[r];
+        while (parent[x] != r) { const uint32_t nx = parent[x]; parent[x] = r; x = nx; }
+        return r;
+    };
+    auto takesPart = [&](size_t i) { return !(fluidOnly && particles[i].isGhost != 0); };
+    for (size_t i = 0; i < n; ++i) {
+        if (!takesPart(i)) continue;
+        const float* x = particles[i].pos;
+        int cx, cy, cz;
+        cellOf(x, cx, cy, cz);
+        const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
+        for (int rr = 0; rr < w * w; ++rr) {
+            const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
+            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
+            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
+            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1] && j < slotOf[i]; ++j) {      // an edge is seen from its larger slot
+                const uint32_t o = order[j];
+                const float* y = particles[o].pos;
+                if (!takesPart(o) || !sph::neighbor_accept(x[0], x[1], x[2], y[0], y[1], y[2], R2)) continue;
+                const uint32_t a = find((uint32_t)i), b = find(o);
+                if (a != b) parent[std::max(a, b)] = std::min(a, b);
+            }
+        }
+    }
+    std::vector<int32_t> lab(n, -1), root(n, -1);
+    std::vector<sph::CcRow> rows;
+    uint64_t excluded = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!takesPart(i)) { excluded += 1; continue; }
+        const uint32_t r = find((uint32_t)i);                                       // r <= i: its row exists already
+        root[i] = (int32_t)r;
+        if (r == i) {
+            sph::CcRow row{};
+            row.root = r;
+            for (int a = 0; a < 3; ++a) { row.bbMin[a] = 0xffffffffu; row.bbMax[a] = 0u; }
+            lab[i] = (int32_t)rows.size();
+            rows.push_back(row);
+        } else {
+            lab[i] = lab[r];
+        }
+        sph::CcRow& row = rows[(size_t)lab[i]];
+        row.count += 1u;
+        const float* x = particles[i].pos;
+        if (!sph::cc_finite3(x[0], x[1], x[2])) { row.flags |= sph::kCcNonFinite; continue; }
+        const float gmin[3] = {k.gminx, k.gminy, k.gminz};
+        const double S = 65536.0 / (double)k.cellSize;
+        for (int a = 0; a < 3; ++a) {
+            row.sumQ[a] += (unsigned long long)sph::cc_fixed(x[a], gmin[a], S);
+            row.bbMin[a] = std::min(row.bbMin[a], sph::cc_ordered(x[a]));
+            row.bbMax[a] = std::max(row.bbMax[a], sph::cc_ordered(x[a]));
+        }
+    }
+    SphComponentInfo info{};
+    info.rows = n; info.numComponents = rows.size(); info.numExcluded = excluded; info.radius = radius; info.stencil = stencil; info.flags = flags;
+    for (sph::CcRow& row : rows) {
+        const bool empty = (row.flags & sph::kCcNonFinite) != 0u;
+        for (int a = 0; a < 3; ++a) {
+            const float mn = empty ? 0.0f : sph::cc_unordered(row.bbMin[a]), mx = empty ? 0.0f : sph::cc_unordered(row.bbMax[a]);
+            memcpy(&row.bbMin[a], &mn, 4);
+            memcpy(&row.bbMax[a], &mx, 4);
+        }
+        if (row.count > info.largestCount) { info.largestCount = row.count; info.largestRoot = row.root; }     // (rows ascend by root: ties keep the smaller)
+        if (row.count == 1u) info.numSingletons += 1u;
+    }
+    *out = info;
+    if (table && tableCap < rows.size())
+        return fail(SPH_ERR_CAPACITY, "room for %llu table rows, the state has %zu components", (unsigned long long)tableCap, rows.size());
+    if (labels && n) memcpy(labels, lab.data(), n * sizeof(int32_t));
+    if (roots && n) memcpy(roots, root.data(), n * sizeof(int32_t));
+    if (table && !rows.empty()) memcpy(table, rows.data(), rows.size() * sizeof(SphComponent));
     return SPH_OK;
 }
 

@@ -83,6 +83,7 @@ SPH_OPT_MESH_SPLIT = 7
 SPH_OPT_SCALAR_SWEEP = 8
 SPH_OPT_DIFFUSE_TIMED = 9
 SPH_OPT_NEIGHBORS_FILL = 10
+SPH_OPT_COMPONENTS_VARIANT = 11
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -254,6 +255,26 @@ assert C.sizeof(SphNeighborInfo) == 40
 SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY = 1, 2, 4
 
 
+class SphComponent(C.Structure):
+    """struct SphComponent of include/sph_abi.h: one row of the table of connected bodies (see SPHFluidGPU.components)."""
+    _fields_ = [("root", C.c_uint32), ("count", C.c_uint32), ("bbMin", C.c_float * 3), ("bbMax", C.c_float * 3), ("sumQ", C.c_int64 * 3),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SphComponentInfo(C.Structure):
+    """struct SphComponentInfo of include/sph_abi.h: what the engine's components hold."""
+    _fields_ = [("rows", C.c_uint64), ("numComponents", C.c_uint64), ("numExcluded", C.c_uint64), ("largestCount", C.c_uint64),
+                ("largestRoot", C.c_uint32), ("numSingletons", C.c_uint32), ("radius", C.c_float), ("stencil", C.c_int32), ("flags", C.c_int32),
+                ("rounds", C.c_uint32)]
+
+
+assert C.sizeof(SphComponent) == 64 and C.sizeof(SphComponentInfo) == 56
+COMPONENT_DTYPE = np.dtype(SphComponent)
+assert COMPONENT_DTYPE.itemsize == 64
+SPH_COMPONENTS_FLUID_ONLY = 1
+SPH_COMPONENT_NONFINITE = 1
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -402,6 +423,12 @@ _ABI = {
     "sph_neighbors_export": (_int, [_vp, _vp, _vp, _u64]),
     "sph_neighbors_download": (_int, [_vp, _vp, _vp, _u64]),
     "sph_neighbors_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _vp, _u64, _P(SphNeighborInfo)]),
+    # connected components
+    "sph_components_build": (_int, [_vp, _f, _int, _P(SphComponentInfo)]),
+    "sph_components_info": (_int, [_vp, _P(SphComponentInfo)]),
+    "sph_components_device": (_int, [_vp, _P(_vp), _P(_vp), _P(_vp)]),
+    "sph_components_download": (_int, [_vp, _vp, _vp, _vp, _u64]),
+    "sph_components_host": (_int, [_vp, _sz, _pp, _f, _int, _vp, _vp, _vp, _u64, _P(SphComponentInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -1142,6 +1169,37 @@ class SPHFluidGPU:
         recv = torch.repeat_interleave(torch.arange(off.numel() - 1, device=off.device), off[1:] - off[:-1])
         return torch.stack((recv, idx.to(torch.int64)))
 
+    # -- connected components (include/sph_abi.h "connected components") --------------------------
+    def components(self, radius=None, fluid_only: bool = False, device: bool = False):
+        """Connected bodies of the neighbour relation at `radius` (None: param_h; at most three cells): (labels int32[n], roots int32[n],
+        table COMPONENT_DTYPE[C]).  roots[i] is the smallest particle id of i's body, bodies are numbered in ascending order of it and
+        labels[i] is that number; fluid_only leaves out the records with isGhost != 0 (label and root -1).  numpy arrays; with device=True
+        labels and roots are fresh torch int32 device tensors (the table stays a numpy array)."""
+        self._push_params()
+        info = SphComponentInfo()
+        r = self._p.param_h if radius is None else radius
+        _check(self._L.sph_components_build(self._h, float(r), SPH_COMPONENTS_FLUID_ONLY if fluid_only else 0, C.byref(info)))
+        n, c = int(info.rows), int(info.numComponents)
+        table = np.zeros(c, COMPONENT_DTYPE)
+        if device:
+            import torch
+            labels = torch.empty(n, dtype=torch.int32, device="cuda")
+            roots = torch.empty(n, dtype=torch.int32, device="cuda")
+            _check(self._L.sph_components_download(self._h, C.c_void_p(labels.data_ptr()) if n else None, C.c_void_p(roots.data_ptr()) if n else None,
+                                                   _ptr(table) if c else None, c))
+            return labels, roots, table
+        labels = np.zeros(n, np.int32)
+        roots = np.zeros(n, np.int32)
+        _check(self._L.sph_components_download(self._h, _ptr(labels) if n else None, _ptr(roots) if n else None, _ptr(table) if c else None, c))
+        return labels, roots, table
+
+    def component_info(self) -> SphComponentInfo:
+        """What the engine's components hold: rows, numComponents, numExcluded, largestCount, largestRoot, numSingletons, radius, stencil,
+        flags, rounds.  SphError before any components() call."""
+        info = SphComponentInfo()
+        _check(self._L.sph_components_info(self._h, C.byref(info)))
+        return info
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -1755,6 +1813,30 @@ def neighbors_host(records, params, radius, points=None, self_=False, half=False
     idx = np.zeros(int(info.total), np.int32)
     _check(call(flags, idx, len(idx)))
     return off, idx
+
+
+def components_host(records, params, radius, fluid_only: bool = False):
+    """sph_components_host: (labels, roots, table, info) of SPHFluidGPU.components on host records, computed on the CPU by a sequential
+    union-find with the same accept function.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    n = len(rec)
+    labels, roots, table = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, COMPONENT_DTYPE)
+    info = SphComponentInfo()
+    _check(load_library().sph_components_host(_ptr_or_none(rec), n, C.byref(params), float(radius), SPH_COMPONENTS_FLUID_ONLY if fluid_only else 0,
+                                              _ptr_or_none(labels), _ptr_or_none(roots), _ptr_or_none(table), n, C.byref(info)))
+    return labels, roots, table[:int(info.numComponents)].copy(), info
+
+
+def component_centers(table, grid) -> np.ndarray:
+    """(C, 3) float64 centres of the bodies of a component table: gridMin + cellSize * sumQ / (65536 * count), `grid` the SphGridInfo of
+    the state (compute_grid_extents).  A body flagged SPH_COMPONENT_NONFINITE has no centre (NaN)."""
+    t = np.asarray(table)
+    gmin = np.array(list(grid.gridMin), np.float64)
+    cnt = t["count"].astype(np.float64)[:, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ctr = gmin + float(grid.cellSize) * t["sumQ"].astype(np.float64) / (65536.0 * cnt)
+    ctr[(t["flags"] & SPH_COMPONENT_NONFINITE) != 0] = np.nan
+    return ctr
 
 
 def obstacles_apply_host(obstacles, particle_mass: float, particles: np.ndarray):

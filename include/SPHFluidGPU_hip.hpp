@@ -192,6 +192,29 @@ public:
         indices.assign(dIdx ? size_t(info.total) : 0, 0);
         return !Check(sph_neighbors_download(engine, offsets.data(), dIdx ? indices.data() : nullptr, indices.size()), "sph_neighbors_download");
     }
+    // Connected components (engine extension, sph_abi.h "connected components"): which particles hang together under
+    // the neighbour relation at `radius` (<= 0: param_h; at most three cells).  flags: SPH_COMPONENTS_FLUID_ONLY.  The result stays in the
+    // engine until the next call, ResetSimulation or the destructor; DownloadComponents copies labels[n], roots[n] and the table of one
+    // row per body to the host.  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    bool Components(SphComponentInfo& out, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_components_build(engine, radius > 0.0f ? radius : param_h, flags, &out), "sph_components_build");
+    }
+    SphComponentInfo ComponentInfo() {
+        SphComponentInfo info{};
+        Check(sph_components_info(engine, &info), "sph_components_info");
+        return info;
+    }
+    bool DownloadComponents(std::vector<int32_t>& labels, std::vector<int32_t>& roots, std::vector<SphComponent>& table) {
+        SphComponentInfo info{};
+        if (Check(sph_components_info(engine, &info), "sph_components_info")) return false;
+        labels.assign(size_t(info.rows), 0);
+        roots.assign(size_t(info.rows), 0);
+        table.assign(size_t(info.numComponents), SphComponent{});
+        return !Check(sph_components_download(engine, labels.empty() ? nullptr : labels.data(), roots.empty() ? nullptr : roots.data(),
+                                              table.empty() ? nullptr : table.data(), table.size()), "sph_components_download");
+    }
     // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
     // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
     // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per

@@ -48,6 +48,7 @@ extern "C" {
 /* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
 /* (still 4, additions only: SphNeighborInfo, SPH_NEIGHBORS_*, sph_neighbors_build / _query / _info / _device / _export / _download / _host, SPH_OPT_NEIGHBORS_FILL -- neighbour lists) */
+/* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -153,6 +154,7 @@ enum {
     SPH_OPT_SCALAR_SWEEP = 8,    /* scalar channels (sph_scalars_*): 0 = the sweep walks global memory (default, the bit-level yardstick), 1 = a block of 256 consecutive slots stages its candidate rows in LDS first; same bits */
     SPH_OPT_DIFFUSE_TIMED = 9,   /* diffuse particles (sph_diffuse_*), measurements only: which launches of a substep the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = the advance kernel, 2 = the spawn side (count, scans, compaction, emit, tick); the launches themselves are the same */
     SPH_OPT_NEIGHBORS_FILL = 10, /* neighbour lists (sph_neighbors_*), an A/B of the fill kernel: 0 = every lane writes the entries of its own row (default), 1 = a wave writes one row at a time with consecutive lanes; the same bits */
+    SPH_OPT_COMPONENTS_VARIANT = 11, /* connected components (sph_components_*), A/Bs for measurements: bit 0 = the hook walks every candidate, not only those in front of the target's slot; bit 1 = the table kernel issues its atomics per lane, not once per wave and label; default 0; the same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -850,6 +852,46 @@ int sph_neighbors_download(SphEngine* e, int64_t* offsets, int32_t* indices, uin
  * a total above indexCap: SPH_ERR_CAPACITY with *out filled and offsets valid (so a COUNT_ONLY call sizes the second one). */
 int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m,
                        float radius, int flags, int64_t* offsets, int32_t* indices, uint64_t indexCap, SphNeighborInfo* out);
+
+/* ---- connected components: which particles hang together (no reference counterpart) --------------------------
+ * The graph of the neighbour relation above (same grid of the CURRENT state, radius rules 0 < R <= 3 * cellSize, stencil half-width and
+ * accept test): records i != j are joined when j is a candidate of i and r2 < R2.  A component is a connected component of that graph;
+ * every participating record is in exactly one, a record with no edge is a component of one.  A record with a non-finite coordinate is
+ * accepted by nobody: a component of one with SPH_COMPONENT_NONFINITE in its row's flags.  By default every record takes part;
+ * SPH_COMPONENTS_FLUID_ONLY leaves out the records with isGhost != 0: they join nothing, bridge nothing, and get label and root -1.
+ *   roots[i]  = the smallest particle id in i's component; components are numbered 0 .. C-1 in ascending order of that id and
+ *   labels[i] = that number; both int32[n], indexed by particle id.  Row c of the table describes component c: its root, the number of
+ *   members, the fp32 minimum and maximum of their positions, and sumQ, the sum over the members of the fixed-point position
+ *   q = llrint(clamp(((double)x - (double)gridMin) * S, -2^36, 2^36)) per axis, S = 65536.0 / (double)cellSize (subtract, then multiply,
+ *   each rounded in fp64; round to nearest even).  The centre of a body is gridMin + cellSize * sumQ / (65536 * count).  A non-finite
+ *   component has a zero box and zero sums.  Everything is integer from the accept test on: the same bytes on every run.
+ * The buffers are engine-owned and stay valid until the next sph_components_build, sph_reset or sph_destroy; a dispatch does not touch
+ * them and a build never changes the simulation.  Timed as SPH_K_OTHER.  SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as
+ * sampling); _info / _device / _download before any build; a build that needed more than 64 rounds (no result is left).  SPH_ERR_ARG: a
+ * null argument, a bad R, unknown flag bits.  n = 0: everything zero or empty, the call succeeds. */
+enum { SPH_COMPONENTS_FLUID_ONLY = 1 };
+enum { SPH_COMPONENT_NONFINITE = 1 };
+typedef struct SphComponent { uint32_t root, count; float bbMin[3], bbMax[3]; int64_t sumQ[3]; uint32_t flags, pad; } SphComponent;   /* 64 bytes */
+typedef struct SphComponentInfo {
+    uint64_t rows, numComponents, numExcluded, largestCount;
+    uint32_t largestRoot /* ties go to the smaller root */, numSingletons;
+    float radius;
+    int32_t stencil, flags;
+    uint32_t rounds /* hook launches used (0 from sph_components_host) */;
+} SphComponentInfo;   /* 56 bytes */
+/* Labels, roots and table of the current state.  Synchronises. */
+int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo* out);
+int sph_components_info(const SphEngine* e, SphComponentInfo* out);
+/* Borrowed device addresses: labels[rows], roots[rows], table[numComponents]. */
+int sph_components_device(SphEngine* e, const int32_t** labels, const int32_t** roots, const SphComponent** table);
+/* Copies into the caller's memory, host or device (the kind of each copy follows from the address); synchronises; any pointer may be
+ * null.  SPH_ERR_CAPACITY (nothing written) if table is given and tableCap is
+ * below numComponents. */
+int sph_components_download(SphEngine* e, int32_t* labels, int32_t* roots, SphComponent* table, uint64_t tableCap);
+/* Host-only, no device: a sequential union-find over the counting sort of sph_neighbors_host with the same accept function; the same
+ * bytes (rounds = 0).  labels, roots and table may be null; *out is filled before a tableCap refusal (nothing else is written then). */
+int sph_components_host(const SphParticle* particles, size_t n, const SphParams* params, float radius, int flags,
+                        int32_t* labels, int32_t* roots, SphComponent* table, uint64_t tableCap, SphComponentInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
