@@ -27,5 +27,6 @@ from .engine import (  # noqa: F401
     SPH_OPT_NEIGHBORS_FILL, SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY, SphNeighborInfo, neighbors_host,
     SPH_OPT_COMPONENTS_VARIANT, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, SphComponent, SphComponentInfo, COMPONENT_DTYPE, components_host,
     component_centers,
+    SPH_OPT_KNN_VARIANT, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, SphKnnInfo, knn_host,
 )
 from . import build, synthetic  # noqa: F401

@@ -26,6 +26,7 @@
 #include "sph_sample.h"
 #include "sph_neighbors.h"
 #include "sph_components.h"
+#include "sph_knn.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
 #include "sph_diffuse.h"
@@ -258,6 +259,13 @@ struct SphEngine {
     SphComponentInfo ccInfo{};
     bool ccValid = false;                   // the buffers hold the result ccInfo describes
     int optCcVariant = 0;                   // SPH_OPT_COMPONENTS_VARIANT
+    // sph_knn_*: ids of the sorted slots, the dense rows (indices, dist2: rows * k each), the counts and the two words of the reduction
+    DevBuf<int32_t> d_knnIds, d_knnIndices;
+    DevBuf<float> d_knnDist2;
+    DevBuf<uint32_t> d_knnCounts;
+    DevBuf<unsigned long long> d_knnStats;
+    SphKnnInfo knnInfo{};                   // kind 0: no rows
+    int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
     DevBuf<uint16_t> d_surfCode;
@@ -475,6 +483,10 @@ void components_free(SphEngine* e) {
     e->d_ccTileMax.release(); e->d_ccWords.release(); e->d_ccTileSums.release(); e->d_ccStats.release(); e->d_ccOffsets.release(); e->d_ccTable.release();
     e->ccInfo = SphComponentInfo{};
     e->ccValid = false;
+}
+void knn_free(SphEngine* e) {
+    e->d_knnIds.release(); e->d_knnIndices.release(); e->d_knnDist2.release(); e->d_knnCounts.release(); e->d_knnStats.release();
+    e->knnInfo = SphKnnInfo{};
 }
 void surface_free(SphEngine* e) {
     e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
@@ -1313,6 +1325,7 @@ int sph_destroy(SphEngine* e) {
     sample_free(e);
     neighbors_free(e);
     components_free(e);
+    knn_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1351,6 +1364,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     e->surfValid = false;                                             // (the borrowed surface arrays end here: sph_abi.h)
     neighbors_free(e);                                                // (and the neighbour lists)
     components_free(e);                                               // (and the components)
+    knn_free(e);                                                      // (and the k nearest neighbours)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1393,6 +1407,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_DIFFUSE_TIMED: if (value < 0 || value > 2) return fail(SPH_ERR_ARG, "bad value"); e->optDiffuseTimed = value; break;
     case SPH_OPT_NEIGHBORS_FILL: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optNbFill = value; break;
     case SPH_OPT_COMPONENTS_VARIANT: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optCcVariant = value; break;
+    case SPH_OPT_KNN_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optKnnVariant = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1418,6 +1433,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_DIFFUSE_TIMED: *value = e->optDiffuseTimed; break;
     case SPH_OPT_NEIGHBORS_FILL: *value = e->optNbFill; break;
     case SPH_OPT_COMPONENTS_VARIANT: *value = e->optCcVariant; break;
+    case SPH_OPT_KNN_VARIANT: *value = e->optKnnVariant; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -3316,6 +3332,192 @@ int sph_components_host(const SphParticle* particles, size_t n, const SphParams*
     if (labels && n) memcpy(labels, lab.data(), n * sizeof(int32_t));
     if (roots && n) memcpy(roots, root.data(), n * sizeof(int32_t));
     if (table && !rows.empty()) memcpy(table, rows.data(), rows.size() * sizeof(SphComponent));
+    return SPH_OK;
+}
+
+// ---- k nearest neighbours (sph_knn.h) --------------------------------------------------------------
+static_assert(sizeof(SphKnnInfo) == 48, "SphKnnInfo must be 48 bytes");
+static_assert(SPH_KNN_SELF == sph::kKnnSelf && SPH_KNN_FLUID_ONLY == sph::kKnnFluidOnly && SPH_KNN_MAX_K == sph::kKnnMaxK, "sph_knn.h mirrors SPH_KNN_*");
+
+static int knn_check(int k, float radius, float cellSize, int flags, bool query, int* stencil) {
+    if (flags & ~(SPH_KNN_SELF | SPH_KNN_FLUID_ONLY)) return fail(SPH_ERR_ARG, "unknown kNN flags %d", flags);
+    if (query && (flags & SPH_KNN_SELF)) return fail(SPH_ERR_ARG, "SPH_KNN_SELF applies to particle rows only");
+    if (k < 1 || k > SPH_KNN_MAX_K) return fail(SPH_ERR_ARG, "k = %d (1 .. %d)", k, (int)SPH_KNN_MAX_K);
+    *stencil = sph::neighbor_stencil(radius, cellSize);
+    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
+    return SPH_OK;
+}
+
+// One launch of the variant and class in force (arguments already checked).
+static void knn_launch(SphEngine* e, bool query, const sph::SimK& k, const sph::NbK& nb, int kk, const float4* devPoints, size_t rows) {
+    using namespace sph;
+    using Kernel = void (*)(SimK, NbK, int, const float4*, const uint32_t*, const int32_t*, const float4*, const float4*, size_t, int32_t*, float*, uint32_t*,
+                            unsigned long long*);
+    auto go = [&](Kernel kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(rows, threads)), dim3(threads), 0, e->stream, k, nb, kk, (const float4*)e->d_sPV,
+                           (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_knnIds.p, (const float4*)e->d_sOwn, devPoints, rows, e->d_knnIndices.p,
+                           e->d_knnDist2.p, e->d_knnCounts.p, e->d_knnStats.p);
+    };
+    if (e->optKnnVariant == 1) return go(query ? k_knn_select<false> : k_knn_select<true>, kBlock);
+    switch (knn_class(kk)) {
+    case 8: return go(query ? k_knn<false, 8> : k_knn<true, 8>, knn_threads(8));
+    case 16: return go(query ? k_knn<false, 16> : k_knn<true, 16>, knn_threads(16));
+    case 32: return go(query ? k_knn<false, 32> : k_knn<true, 32>, knn_threads(32));
+    default: return go(query ? k_knn<false, 64> : k_knn<true, 64>, knn_threads(64));
+    }
+}
+
+// Grid of the current state, ids, the selection, one synchronisation for the two totals.
+static int knn_run(SphEngine* e, bool query, const float4* devPoints, size_t m, int kk, float radius, int flags, SphKnnInfo* out) {
+    using namespace sph;
+    SimK k;
+    int rc, stencil = 0;
+    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
+    if ((rc = validate_params(e->params))) return rc;
+    {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        if ((rc = knn_check(kk, radius, g.cellSize, flags, query, &stencil))) return rc;
+    }
+    const size_t n = e->n, rows = query ? m : n;
+    e->knnInfo = SphKnnInfo{};                                                      // (the rows held so far end here)
+    if ((rc = e->d_knnIds.grow(e, n)) || (rc = e->d_knnIndices.grow(e, rows * (size_t)kk)) || (rc = e->d_knnDist2.grow(e, rows * (size_t)kk)) ||
+        (rc = e->d_knnCounts.grow(e, rows)) || (rc = e->d_knnStats.grow(e, 2))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    NbK nb;
+    nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)n;
+    unsigned long long host[2] = {0ull, 0ull};
+    if (rows) {
+        HIP_TRY(hipMemsetAsync(e->d_knnStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
+        if (n) {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, e->d_knnIds.p, e->idBase, (uint32_t)n);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            knn_launch(e, query, k, nb, kk, devPoints, rows);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, e->d_knnStats.p, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphKnnInfo info{};
+    info.rows = rows; info.total = host[0]; info.rowsFull = host[1]; info.radius = radius; info.k = kk; info.stencil = stencil; info.flags = flags;
+    info.kind = query ? 2 : 1;
+    e->knnInfo = info;
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_knn_build(SphEngine* e, int k, float radius, int flags, SphKnnInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    return knn_run(e, false, nullptr, 0, k, radius, flags, out);
+}
+
+int sph_knn_query(SphEngine* e, const float* devPoints4, size_t m, int k, float radius, int flags, SphKnnInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || (m && !devPoints4)) return fail(SPH_ERR_ARG, "null argument");
+    if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    return knn_run(e, true, reinterpret_cast<const float4*>(devPoints4), m, k, radius, flags, out);
+}
+
+int sph_knn_info(const SphEngine* e, SphKnnInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->knnInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no k nearest neighbours");
+    *out = e->knnInfo;
+    return SPH_OK;
+}
+
+int sph_knn_device(SphEngine* e, const int32_t** indices, const float** dist2, const uint32_t** counts) {
+    if (!e || !indices || !dist2 || !counts) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->knnInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no k nearest neighbours");
+    *indices = e->d_knnIndices.p;
+    *dist2 = e->d_knnDist2.p;
+    *counts = e->d_knnCounts.p;
+    return SPH_OK;
+}
+
+int sph_knn_download(SphEngine* e, int32_t* indices, float* dist2, uint32_t* counts) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->knnInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no k nearest neighbours");
+    const size_t rows = (size_t)e->knnInfo.rows, cells = rows * (size_t)e->knnInfo.k;
+    if (indices && cells) HIP_TRY(hipMemcpyAsync(indices, e->d_knnIndices.p, cells * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    if (dist2 && cells) HIP_TRY(hipMemcpyAsync(dist2, e->d_knnDist2.p, cells * sizeof(float), hipMemcpyDefault, e->stream));
+    if (counts && rows) HIP_TRY(hipMemcpyAsync(counts, e->d_knnCounts.p, rows * sizeof(uint32_t), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, int kk, float radius, int flags,
+                 int32_t* indices, float* dist2, uint32_t* counts, SphKnnInfo* out) {
+    if (!params || !out || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    int rc, stencil = 0;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = knn_check(kk, radius, g.cellSize, flags, query, &stencil))) return rc;
+    const float R2 = radius * radius;
+    const bool self = (flags & SPH_KNN_SELF) != 0, fluidOnly = (flags & SPH_KNN_FLUID_ONLY) != 0;
+    // the grid as the counting sort leaves it: cells ascending, members ascending by index (as sph_neighbors_host)
+    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
+    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
+        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
+        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        int cx, cy, cz;
+        cellOf(particles[i].pos, cx, cy, cz);
+        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+        start[cell[i] + 1] += 1u;
+    }
+    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
+    }
+    const size_t rows = query ? m : n;
+    SphKnnInfo info{};
+    info.rows = rows; info.radius = radius; info.k = kk; info.stencil = stencil; info.flags = flags; info.kind = query ? 2 : 1;
+    std::vector<unsigned long long> keys;
+    for (size_t r = 0; r < rows; ++r) {
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        keys.clear();
+        const bool walk = query ? (sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+        if (walk) {
+            int cx, cy, cz;
+            cellOf(x, cx, cy, cz);
+            const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
+            for (int rr = 0; rr < w * w; ++rr) {
+                const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
+                if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
+                const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
+                for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+                    if (!query && !self && j == slotOf[r]) continue;
+                    const uint32_t o = order[j];
+                    const float* y = particles[o].pos;
+                    const float r2 = sph::knn_r2(x[0], x[1], x[2], y[0], y[1], y[2]);
+                    if (!(r2 < R2) || (fluidOnly && particles[o].isGhost != 0)) continue;
+                    keys.push_back(sph::knn_key(r2, o));
+                }
+            }
+        }
+        std::sort(keys.begin(), keys.end());
+        const size_t c = std::min(keys.size(), (size_t)kk);
+        for (size_t s = 0; s < (size_t)kk; ++s) {
+            if (indices) indices[r * (size_t)kk + s] = s < c ? (int32_t)(uint32_t)(keys[s] & 0xffffffffull) : -1;
+            if (dist2) dist2[r * (size_t)kk + s] = s < c ? sph::knn_key_r2(keys[s]) : INFINITY;
+        }
+        if (counts) counts[r] = (uint32_t)c;
+        info.total += c;
+        info.rowsFull += c == (size_t)kk ? 1u : 0u;
+    }
+    *out = info;
     return SPH_OK;
 }
 

@@ -84,6 +84,7 @@ SPH_OPT_SCALAR_SWEEP = 8
 SPH_OPT_DIFFUSE_TIMED = 9
 SPH_OPT_NEIGHBORS_FILL = 10
 SPH_OPT_COMPONENTS_VARIANT = 11
+SPH_OPT_KNN_VARIANT = 12
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -275,6 +276,16 @@ SPH_COMPONENTS_FLUID_ONLY = 1
 SPH_COMPONENT_NONFINITE = 1
 
 
+class SphKnnInfo(C.Structure):
+    """struct SphKnnInfo of include/sph_abi.h: what the engine's k-nearest-neighbour rows hold (see SPHFluidGPU.knn)."""
+    _fields_ = [("rows", C.c_uint64), ("total", C.c_uint64), ("rowsFull", C.c_uint64), ("radius", C.c_float), ("k", C.c_int32),
+                ("stencil", C.c_int32), ("flags", C.c_int32), ("kind", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(SphKnnInfo) == 48
+SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K = 1, 2, 64
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -429,6 +440,13 @@ _ABI = {
     "sph_components_device": (_int, [_vp, _P(_vp), _P(_vp), _P(_vp)]),
     "sph_components_download": (_int, [_vp, _vp, _vp, _vp, _u64]),
     "sph_components_host": (_int, [_vp, _sz, _pp, _f, _int, _vp, _vp, _vp, _u64, _P(SphComponentInfo)]),
+    # k nearest neighbours
+    "sph_knn_build": (_int, [_vp, _int, _f, _int, _P(SphKnnInfo)]),
+    "sph_knn_query": (_int, [_vp, _vp, _sz, _int, _f, _int, _P(SphKnnInfo)]),
+    "sph_knn_info": (_int, [_vp, _P(SphKnnInfo)]),
+    "sph_knn_device": (_int, [_vp, _P(_vp), _P(_vp), _P(_vp)]),
+    "sph_knn_download": (_int, [_vp, _vp, _vp, _vp]),
+    "sph_knn_host": (_int, [_vp, _sz, _pp, _vp, _sz, _int, _f, _int, _vp, _vp, _vp, _P(SphKnnInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -554,6 +572,10 @@ def _points4(points, who, keep_w):
 
 def _neighbor_flags(self_, half, count_only) -> int:
     return (SPH_NEIGHBORS_SELF if self_ else 0) | (SPH_NEIGHBORS_HALF if half else 0) | (SPH_NEIGHBORS_COUNT_ONLY if count_only else 0)
+
+
+def _knn_flags(self_, fluid_only) -> int:
+    return (SPH_KNN_SELF if self_ else 0) | (SPH_KNN_FLUID_ONLY if fluid_only else 0)
 
 
 def _is_cuda_f32(t) -> bool:
@@ -1200,6 +1222,67 @@ class SPHFluidGPU:
         _check(self._L.sph_components_info(self._h, C.byref(info)))
         return info
 
+    # -- k nearest neighbours (include/sph_abi.h "k nearest neighbours") ---------------------------
+    def knn(self, k: int, radius=None, self_=False, fluid_only: bool = False, device: bool = False):
+        """The k nearest particles of every particle within `radius` (None: param_h; at most three cells), nearest first, ties to the
+        smaller id: (idx (n, k) int32 padded with -1, d2 (n, k) float32 padded with +inf, counts (n,) uint32); rows are numbered by
+        particle id.  self_ makes the particle an ordinary candidate of its own row (distance 0), fluid_only leaves the records with
+        isGhost != 0 out of every row and gives them empty rows.  numpy arrays, or with device=True fresh torch device tensors."""
+        self._push_params()
+        info = SphKnnInfo()
+        r = self._p.param_h if radius is None else radius
+        _check(self._L.sph_knn_build(self._h, int(k), float(r), _knn_flags(self_, fluid_only), C.byref(info)))
+        return self.knn_rows(device)
+
+    def query_knn(self, points, k: int, radius, fluid_only: bool = False, device: bool = False):
+        """The same around (m, 3) or (m, 4) query points: row i holds the k nearest particles within `radius` of points[i] (a torch
+        device tensor of (m, 4) float32 is used in place).  A point with a non-finite coordinate has an empty row."""
+        import torch
+        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
+            dev = points
+        else:
+            dev = torch.from_numpy(_points4(points, "query_knn", keep_w=False)).cuda()
+        self._push_params()
+        info = SphKnnInfo()
+        m = int(dev.shape[0])
+        _check(self._L.sph_knn_query(self._h, C.c_void_p(dev.data_ptr()) if m else None, m, int(k), float(radius), _knn_flags(False, fluid_only),
+                                     C.byref(info)))
+        return self.knn_rows(device)
+
+    def knn_info(self) -> SphKnnInfo:
+        """What the engine's rows hold: rows, total (sum of counts), rowsFull (rows with count == k), k, radius, stencil, flags, kind
+        (1 particles, 2 query).  SphError before any knn() / query_knn() call."""
+        info = SphKnnInfo()
+        _check(self._L.sph_knn_info(self._h, C.byref(info)))
+        return info
+
+    def knn_rows(self, device: bool = False):
+        """(idx, d2, counts) of the rows the engine holds."""
+        info = self.knn_info()
+        rows, k = int(info.rows), int(info.k)
+        if device:
+            import torch
+            idx = torch.empty((rows, k), dtype=torch.int32, device="cuda")
+            d2 = torch.empty((rows, k), dtype=torch.float32, device="cuda")
+            cnt = torch.empty(rows, dtype=torch.int32, device="cuda")                # (uint32 counts <= 64 in an int32 tensor: the same bits)
+            _check(self._L.sph_knn_download(self._h, C.c_void_p(idx.data_ptr()) if rows else None, C.c_void_p(d2.data_ptr()) if rows else None,
+                                            C.c_void_p(cnt.data_ptr()) if rows else None))
+            return idx, d2, cnt
+        idx = np.zeros((rows, k), np.int32)
+        d2 = np.zeros((rows, k), np.float32)
+        cnt = np.zeros(rows, np.uint32)
+        _check(self._L.sph_knn_download(self._h, _ptr(idx) if rows else None, _ptr(d2) if rows else None, _ptr(cnt) if rows else None))
+        return idx, d2, cnt
+
+    def knn_graph(self, k: int, radius=None, self_=False):
+        """The k-nearest-neighbour relation as a (2, E) int64 torch device tensor [receiver, sender], E = knn_info().total: the padded
+        entries are removed; edges stand in row order, then rank order."""
+        import torch
+        idx, _, _ = self.knn(k, radius, self_=self_, device=True)
+        recv = torch.arange(idx.shape[0], device=idx.device).unsqueeze(1).expand(-1, idx.shape[1])
+        keep = idx >= 0
+        return torch.stack((recv[keep], idx[keep].to(torch.int64)))
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -1825,6 +1908,23 @@ def components_host(records, params, radius, fluid_only: bool = False):
     _check(load_library().sph_components_host(_ptr_or_none(rec), n, C.byref(params), float(radius), SPH_COMPONENTS_FLUID_ONLY if fluid_only else 0,
                                               _ptr_or_none(labels), _ptr_or_none(roots), _ptr_or_none(table), n, C.byref(info)))
     return labels, roots, table[:int(info.numComponents)].copy(), info
+
+
+def knn_host(records, params, k, radius, points=None, self_=False, fluid_only=False):
+    """sph_knn_host: (idx, d2, counts, info) of SPHFluidGPU.knn (points None) or query_knn on host records, computed on the CPU: the
+    counting sort of neighbors_host, the same r2, per row the accepted keys sorted and cut at k.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    p4 = None if points is None else _points4(points, "knn_host", keep_w=False)
+    rows = len(rec) if p4 is None else len(p4)
+    kk = int(k)
+    width = kk if 1 <= kk <= SPH_KNN_MAX_K else 1                                    # (a refused k writes nothing)
+    idx, d2, cnt = np.zeros((rows, width), np.int32), np.zeros((rows, width), np.float32), np.zeros(rows, np.uint32)
+    info = SphKnnInfo()
+    pp = None if p4 is None else _ptr(p4 if len(p4) else np.zeros((1, 4), np.float32))   # (non-null: query rows, also for m = 0)
+    _check(load_library().sph_knn_host(_ptr_or_none(rec), len(rec), C.byref(params), pp, rows if p4 is not None else 0, kk, float(radius),
+                                       _knn_flags(self_, fluid_only), _ptr(idx) if rows else None, _ptr(d2) if rows else None,
+                                       _ptr(cnt) if rows else None, C.byref(info)))
+    return idx, d2, cnt, info
 
 
 def component_centers(table, grid) -> np.ndarray:

@@ -215,6 +215,36 @@ public:
         return !Check(sph_components_download(engine, labels.empty() ? nullptr : labels.data(), roots.empty() ? nullptr : roots.data(),
                                               table.empty() ? nullptr : table.data(), table.size()), "sph_components_download");
     }
+    // k nearest neighbours (engine extension, sph_abi.h "k nearest neighbours"): per particle (rows numbered by
+    // particle id) or per query point in DEVICE memory (4 floats each) the k nearest particles within `radius` (<= 0: param_h; at most
+    // three cells), nearest first, ties to the smaller id.  flags: SPH_KNN_SELF / _FLUID_ONLY; 1 <= k <= SPH_KNN_MAX_K.  The rows stay in
+    // the engine until the next call, ResetSimulation or the destructor; DownloadKnn copies indices[rows * k] (padded with -1),
+    // dist2[rows * k] (padded with +inf) and counts[rows] to the host.  Members are pushed first, as DispatchCompute does.  Return false
+    // on error (LastError()).
+    bool Knn(SphKnnInfo& out, int k, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_knn_build(engine, k, radius > 0.0f ? radius : param_h, flags, &out), "sph_knn_build");
+    }
+    bool QueryKnn(const float* devPoints4, size_t m, int k, float radius, SphKnnInfo& out, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_knn_query(engine, devPoints4, m, k, radius, flags, &out), "sph_knn_query");
+    }
+    SphKnnInfo KnnInfo() {
+        SphKnnInfo info{};
+        Check(sph_knn_info(engine, &info), "sph_knn_info");
+        return info;
+    }
+    bool DownloadKnn(std::vector<int32_t>& indices, std::vector<float>& dist2, std::vector<uint32_t>& counts) {
+        SphKnnInfo info{};
+        if (Check(sph_knn_info(engine, &info), "sph_knn_info")) return false;
+        indices.assign(size_t(info.rows) * size_t(info.k), 0);
+        dist2.assign(indices.size(), 0.0f);
+        counts.assign(size_t(info.rows), 0u);
+        return !Check(sph_knn_download(engine, indices.empty() ? nullptr : indices.data(), dist2.empty() ? nullptr : dist2.data(),
+                                       counts.empty() ? nullptr : counts.data()), "sph_knn_download");
+    }
     // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
     // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
     // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per

@@ -49,6 +49,7 @@ extern "C" {
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
 /* (still 4, additions only: SphNeighborInfo, SPH_NEIGHBORS_*, sph_neighbors_build / _query / _info / _device / _export / _download / _host, SPH_OPT_NEIGHBORS_FILL -- neighbour lists) */
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
+/* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -155,6 +156,7 @@ enum {
     SPH_OPT_DIFFUSE_TIMED = 9,   /* diffuse particles (sph_diffuse_*), measurements only: which launches of a substep the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = the advance kernel, 2 = the spawn side (count, scans, compaction, emit, tick); the launches themselves are the same */
     SPH_OPT_NEIGHBORS_FILL = 10, /* neighbour lists (sph_neighbors_*), an A/B of the fill kernel: 0 = every lane writes the entries of its own row (default), 1 = a wave writes one row at a time with consecutive lanes; the same bits */
     SPH_OPT_COMPONENTS_VARIANT = 11, /* connected components (sph_components_*), A/Bs for measurements: bit 0 = the hook walks every candidate, not only those in front of the target's slot; bit 1 = the table kernel issues its atomics per lane, not once per wave and label; default 0; the same bits */
+    SPH_OPT_KNN_VARIANT = 12,    /* k nearest neighbours (sph_knn_*), an A/B for measurements: 0 = one target per lane keeps its k best keys in LDS (default), 1 = k selection passes over the candidates without any storage (slow); the same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -892,6 +894,48 @@ int sph_components_download(SphEngine* e, int32_t* labels, int32_t* roots, SphCo
  * bytes (rounds = 0).  labels, roots and table may be null; *out is filled before a tableCap refusal (nothing else is written then). */
 int sph_components_host(const SphParticle* particles, size_t n, const SphParams* params, float radius, int flags,
                         int32_t* labels, int32_t* roots, SphComponent* table, uint64_t tableCap, SphComponentInfo* out);
+
+/* ---- k nearest neighbours within a radius (no reference counterpart) ------------------------------------------
+ * For every particle, or for arbitrary query points, the k nearest particles within a radius R, nearest first, on the device.  Grid
+ * (of the CURRENT state), radius rules 0 < R <= 3 * cellSize, R2 = R * R in fp32, stencil half-width and candidates are those of the
+ * neighbour lists above.  Candidate j is accepted when r2 < R2 with the same r2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), d = x_target -
+ * x_j, and has the key ((uint64)bits(r2) << 32) | id_j: r2 is >= +0, so keys compared as uint64 order by ascending r2 and, among equal
+ * r2, by ascending particle id.  The row of a target is its min(k, accepted) smallest keys, ascending -- one answer whatever the order
+ * in which candidates are met, also on lattices and for coincident particles, and the same bytes on every run.  1 <= k <= SPH_KNN_MAX_K.
+ * Particle rows are numbered by particle id and every record has a row; the target's own slot is left out by slot identity.
+ * NOTE, SPH_KNN_SELF is not SPH_NEIGHBORS_SELF: with it the own slot is an ORDINARY candidate (r2 = 0, placed by id among coincident
+ * particles), so a target with a non-finite position still has an empty row (the neighbour lists keep such a target by identity).
+ * SPH_KNN_FLUID_ONLY: records with isGhost != 0 are never candidates and their own rows are empty.  Query rows are numbered by query
+ * point: SELF is SPH_ERR_ARG, FLUID_ONLY is allowed, a point with a non-finite coordinate has an empty row.
+ * Outputs, engine-owned, dense and row-major: indices int32[rows * k] (particle ids, padded with -1), dist2 float[rows * k] (the fp32 r2
+ * of each entry bit for bit, padded with +inf), counts uint32[rows].  SphKnnInfo: total = the sum of the counts, rowsFull = the rows with
+ * count == k (integer reductions).  Bit for bit: the row for k1 is a prefix of the row for k2 > k1; counts[i] = min(k, degree_i) with the
+ * degree of sph_neighbors_build at the same R (SELF for SELF), and for k >= degree_i the row holds exactly that list's ids; dist2
+ * ascends along a row and equal dist2 have ascending ids.
+ * The buffers stay valid until the next sph_knn_build / _query, sph_reset or sph_destroy; the neighbour lists and the components have
+ * buffers of their own (neither kind of call invalidates the other); a dispatch does not touch them and a build never changes the
+ * simulation.  Timed as SPH_K_OTHER.  SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as sampling); _info / _device / _download
+ * before any build.  SPH_ERR_ARG: a null argument, a bad R, k outside 1 .. 64, unknown flag bits, more than 2^31 - 1 query points.
+ * n = 0 or m = 0: empty results, the call succeeds. */
+enum { SPH_KNN_SELF = 1, SPH_KNN_FLUID_ONLY = 2 };
+enum { SPH_KNN_MAX_K = 64 };
+typedef struct SphKnnInfo { uint64_t rows, total, rowsFull; float radius; int32_t k, stencil, flags, kind /*0 none, 1 particles, 2 query*/, pad; } SphKnnInfo;   /* 48 bytes */
+/* Rows of every particle.  Synchronises. */
+int sph_knn_build(SphEngine* e, int k, float radius, int flags, SphKnnInfo* out);
+/* Rows of m query points of 4 floats (x, y, z, unused) in DEVICE memory (may be null when m is 0).  Synchronises. */
+int sph_knn_query(SphEngine* e, const float* devPoints4, size_t m, int k, float radius, int flags, SphKnnInfo* out);
+/* What the engine holds. */
+int sph_knn_info(const SphEngine* e, SphKnnInfo* out);
+/* Borrowed device addresses: indices[rows * k], dist2[rows * k], counts[rows]. */
+int sph_knn_device(SphEngine* e, const int32_t** indices, const float** dist2, const uint32_t** counts);
+/* Copies into the caller's memory, host or device (the kind of each copy follows from the address); synchronises; any pointer may be
+ * null. */
+int sph_knn_download(SphEngine* e, int32_t* indices, float* dist2, uint32_t* counts);
+/* Host-only, no device: the counting sort of sph_neighbors_host and the same r2; per row the accepted keys are collected, sorted and
+ * cut at k; the same bytes.  points4 NULL: particle rows of particles[0 .. n) (m ignored); else query rows of m points.  indices,
+ * dist2 and counts may be null. */
+int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, int k, float radius, int flags,
+                 int32_t* indices, float* dist2, uint32_t* counts, SphKnnInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
