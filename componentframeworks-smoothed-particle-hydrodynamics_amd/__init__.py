@@ -28,5 +28,6 @@ from .engine import (  # noqa: F401
     SPH_OPT_COMPONENTS_VARIANT, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, SphComponent, SphComponentInfo, COMPONENT_DTYPE, components_host,
     component_centers,
     SPH_OPT_KNN_VARIANT, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, SphKnnInfo, knn_host,
+    SPH_OPT_RAYS_VARIANT, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, SphRayHit, SphRaysInfo, RAY_HIT_DTYPE, rays_host, camera_rays, parallel_rays,
 )
 from . import build, synthetic  # noqa: F401

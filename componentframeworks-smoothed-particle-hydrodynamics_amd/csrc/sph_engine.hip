@@ -27,6 +27,7 @@
 #include "sph_neighbors.h"
 #include "sph_components.h"
 #include "sph_knn.h"
+#include "sph_rays.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
 #include "sph_diffuse.h"
@@ -265,6 +266,14 @@ struct SphEngine {
     DevBuf<uint32_t> d_knnCounts;
     DevBuf<unsigned long long> d_knnStats;
     SphKnnInfo knnInfo{};                   // kind 0: no rows
+    // sph_rays_*: the staged rays of sph_rays_cast (two float4 each), the hits (two float4 each) and the two words of the reduction
+    DevBuf<float4> d_rayIn, d_rayHits;
+    DevBuf<unsigned long long> d_rayStats;
+    DevBuf<uint2> d_rayBin;                 // the ordering of the rays by their cell of entry: (cell, arrival number) per ray, the histogram over
+    DevBuf<uint32_t> d_rayCount, d_rayStart, d_rayBlockSums, d_rayOrder;   // numCells + 1 bins, its scan, the tile sums, the order
+    int optRaysVariant = 0;                 // SPH_OPT_RAYS_VARIANT: 0 = rays cast in the caller's order, 1 = in the order of their cell of entry (same bits)
+    SphRaysInfo raysInfo{};
+    bool raysValid = false;
     int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
@@ -487,6 +496,12 @@ void components_free(SphEngine* e) {
 void knn_free(SphEngine* e) {
     e->d_knnIds.release(); e->d_knnIndices.release(); e->d_knnDist2.release(); e->d_knnCounts.release(); e->d_knnStats.release();
     e->knnInfo = SphKnnInfo{};
+}
+void rays_free(SphEngine* e) {
+    e->d_rayIn.release(); e->d_rayHits.release(); e->d_rayStats.release();
+    e->d_rayBin.release(); e->d_rayCount.release(); e->d_rayStart.release(); e->d_rayBlockSums.release(); e->d_rayOrder.release();
+    e->raysInfo = SphRaysInfo{};
+    e->raysValid = false;
 }
 void surface_free(SphEngine* e) {
     e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
@@ -1326,6 +1341,7 @@ int sph_destroy(SphEngine* e) {
     neighbors_free(e);
     components_free(e);
     knn_free(e);
+    rays_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1365,6 +1381,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     neighbors_free(e);                                                // (and the neighbour lists)
     components_free(e);                                               // (and the components)
     knn_free(e);                                                      // (and the k nearest neighbours)
+    rays_free(e);                                                     // (and the ray hits)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1408,6 +1425,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_NEIGHBORS_FILL: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optNbFill = value; break;
     case SPH_OPT_COMPONENTS_VARIANT: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optCcVariant = value; break;
     case SPH_OPT_KNN_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optKnnVariant = value; break;
+    case SPH_OPT_RAYS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaysVariant = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1434,6 +1452,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_NEIGHBORS_FILL: *value = e->optNbFill; break;
     case SPH_OPT_COMPONENTS_VARIANT: *value = e->optCcVariant; break;
     case SPH_OPT_KNN_VARIANT: *value = e->optKnnVariant; break;
+    case SPH_OPT_RAYS_VARIANT: *value = e->optRaysVariant; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -3516,6 +3535,208 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
         if (counts) counts[r] = (uint32_t)c;
         info.total += c;
         info.rowsFull += c == (size_t)kk ? 1u : 0u;
+    }
+    *out = info;
+    return SPH_OK;
+}
+
+// ---- ray casts (sph_rays.h) ------------------------------------------------------------------------
+static_assert(sizeof(SphRayHit) == 32 && sizeof(SphRaysInfo) == 32, "SphRayHit and SphRaysInfo must be 32 bytes");
+static_assert(SPH_RAYS_FLUID_ONLY == sph::kRaysFluidOnly && SPH_RAYS_ANY_HIT == sph::kRaysAnyHit, "sph_rays.h mirrors SPH_RAYS_*");
+
+static int rays_check(float radius, float cellSize, int flags, size_t m) {
+    if (flags & ~(SPH_RAYS_FLUID_ONLY | SPH_RAYS_ANY_HIT)) return fail(SPH_ERR_ARG, "unknown ray flags %d", flags);
+    if (!std::isfinite(radius) || !(radius > 0.0f) || !(radius <= 0.5f * cellSize))
+        return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above half a cell (%g)", (double)radius, (double)(0.5f * cellSize));
+    if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu rays (at most 2^31 - 1)", m);
+    return SPH_OK;
+}
+static sph::RayK rays_consts(float radius, int flags, uint32_t idBase, size_t n) {
+    sph::RayK rk;
+    rk.r2 = radius * radius; rk.invr = 1.0f / radius; rk.flags = flags; rk.idBase = idBase; rk.n = (uint32_t)n;
+    return rk;
+}
+
+int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float radius, int flags, SphRaysInfo* out) {
+    using namespace sph;
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || (m && !devRays8)) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    int rc;
+    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
+    if ((rc = validate_params(e->params))) return rc;
+    {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;
+    }
+    e->raysValid = false;                                                           // (the hits held so far end here)
+    if ((rc = e->d_rayHits.grow(e, 2 * m)) || (rc = e->d_rayStats.grow(e, 2))) return rc;
+    const bool ordered = e->optRaysVariant == 1 && m && e->n;
+    {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        const size_t bins = (size_t)g.numCells + 1;
+        if (ordered) {
+            if ((rc = e->d_rayBin.grow(e, m)) || (rc = e->d_rayOrder.grow(e, m)) || (rc = e->d_rayCount.grow(e, bins)) || (rc = e->d_rayStart.grow(e, bins + 1)) ||
+                (rc = e->d_rayBlockSums.grow(e, (size_t)blocks_for(bins, kScanTile) + 1))) return rc;
+        }
+    }
+    if ((rc = sample_grid(e, k))) return rc;
+    const RayK rk = rays_consts(radius, flags, e->idBase, e->n);
+    const float4* rays = reinterpret_cast<const float4*>(devRays8);
+    unsigned long long host[2] = {0ull, 0ull};
+    if (m) {
+        HIP_TRY(hipMemsetAsync(e->d_rayStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
+        if (ordered) {
+            HIP_TRY(hipMemsetAsync(e->d_rayCount.p, 0, ((size_t)k.numCells + 1) * sizeof(uint32_t), e->stream));
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_rays_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rays, m, e->d_rayBin.p, e->d_rayCount.p);
+            launch_cell_scan(e, e->d_rayCount.p, e->d_rayBlockSums.p, e->d_rayStart.p, k.numCells + 1, (uint32_t)m);
+            hipLaunchKernelGGL(k_rays_order, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_rayBin.p, (const uint32_t*)e->d_rayStart.p, m, e->d_rayOrder.p);
+        }
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_rays, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rk, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                               (const float4*)e->d_sOwn, rays, ordered ? (const uint32_t*)e->d_rayOrder.p : (const uint32_t*)nullptr, m, e->d_rayHits.p, e->d_rayStats.p);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, e->d_rayStats.p, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphRaysInfo info{};
+    info.rays = m; info.hits = host[0]; info.voidRays = host[1]; info.radius = radius; info.flags = flags;
+    e->raysInfo = info;
+    e->raysValid = true;
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_rays_cast(SphEngine* e, const float* rays8, size_t m, float radius, int flags, SphRaysInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
+    if (e->slab || e->optGridBuild == 1) { sph::SimK k; return sample_grid(e, k); }   // (the refusal, before any allocation)
+    int rc;
+    if ((rc = validate_params(e->params))) return rc;
+    {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;                // (nothing is staged for a call that will be refused)
+    }
+    if (m && (rc = e->d_rayIn.grow(e, 2 * m))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(e->d_rayIn.p, rays8, m * 2 * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    return sph_rays_cast_device(e, reinterpret_cast<const float*>(e->d_rayIn.p), m, radius, flags, out);
+}
+
+int sph_rays_info(const SphEngine* e, SphRaysInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->raysValid) return fail(SPH_ERR_STATE, "the engine holds no ray hits");
+    *out = e->raysInfo;
+    return SPH_OK;
+}
+
+int sph_rays_device(SphEngine* e, const SphRayHit** hits) {
+    if (!e || !hits) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->raysValid) return fail(SPH_ERR_STATE, "the engine holds no ray hits");
+    *hits = reinterpret_cast<const SphRayHit*>(e->d_rayHits.p);
+    return SPH_OK;
+}
+
+int sph_rays_download(SphEngine* e, SphRayHit* hits) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->raysValid) return fail(SPH_ERR_STATE, "the engine holds no ray hits");
+    const size_t m = (size_t)e->raysInfo.rays;
+    if (m && !hits) return fail(SPH_ERR_ARG, "null argument");
+    if (m) HIP_TRY(hipMemcpyAsync(hits, e->d_rayHits.p, m * sizeof(SphRayHit), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// The definition: every ray against every participating record, no grid.  walk: sph_rays_walk_host, the device's ray_walk over the grid
+// as the counting sort leaves it.
+static int rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                     SphRayHit* hits, SphRaysInfo* out, bool walk);
+int sph_rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                  SphRayHit* hits, SphRaysInfo* out) {
+    return rays_host(particles, n, params, rays8, m, radius, flags, hits, out, false);
+}
+int sph_rays_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                       SphRayHit* hits, SphRaysInfo* out) {
+    return rays_host(particles, n, params, rays8, m, radius, flags, hits, out, true);
+}
+static int rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                     SphRayHit* hits, SphRaysInfo* out, bool walk) {
+    if (!params || !out || (n && !particles) || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;
+    const sph::RayK rk = rays_consts(radius, flags, 0u, n);
+    const bool fluidOnly = (flags & SPH_RAYS_FLUID_ONLY) != 0;
+    std::vector<uint8_t> takesPart(n);
+    for (size_t j = 0; j < n; ++j)
+        takesPart[j] = !(fluidOnly && particles[j].isGhost != 0) && sph::ray_in_grid(k, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2]);
+    // for the walk: the grid as the counting sort leaves it (cells ascending, members ascending by index), positions in slot order
+    std::vector<uint32_t> start, order;
+    std::vector<float4> spos;
+    if (walk) {
+        std::vector<uint32_t> cell(n);
+        start.assign((size_t)k.numCells + 1, 0u);
+        order.resize(n);
+        spos.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const float* x = particles[i].pos;
+            const int cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy),
+                      cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
+            cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+            start[cell[i] + 1] += 1u;
+        }
+        for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t slot = fill[cell[i]]++;
+            order[slot] = (uint32_t)i;
+            spos[slot] = make_float4(particles[i].pos[0], particles[i].pos[1], particles[i].pos[2], 0.0f);
+        }
+    }
+    auto rows = [&](int cx, int cy, int cz, auto&& f) {                                   // neighbor_rows at s = 1
+        const int xlo = std::max(cx - 1, 0), xhi = std::min(cx + 1, k.gx - 1);
+        for (int r = 0; r < 9; ++r) {
+            const int nz = cz + r / 3 - 1, ny = cy + r % 3 - 1;
+            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
+            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
+            f(start[rowBase + xlo], std::min(start[rowBase + xhi + 1], (uint32_t)n));
+        }
+    };
+    SphRaysInfo info{};
+    info.rays = m; info.radius = radius; info.flags = flags;
+    for (size_t i = 0; i < m; ++i) {
+        sph::Ray R;
+        unsigned long long best = sph::kRayNoKey;
+        if (!sph::ray_setup(rays8 + 8 * i, R)) {
+            info.voidRays += 1;
+        } else if (walk) {
+            uint32_t slot = 0u;
+            best = sph::ray_walk(k, rk, R, rows, [&](uint32_t j) { return spos[j]; }, [&](uint32_t j) { return order[j]; },
+                                 [&](uint32_t j) { return particles[order[j]].isGhost != 0; }, slot);
+        } else {
+            for (size_t j = 0; j < n; ++j) {
+                float t;
+                if (!takesPart[j] || !sph::ray_hit(R, rk.r2, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2], t)) continue;
+                best = std::min(best, sph::ray_key(t, (uint32_t)j));
+            }
+        }
+        if (best != sph::kRayNoKey) info.hits += 1;
+        if (hits) {
+            const float* x = best != sph::kRayNoKey ? particles[(size_t)(best & 0xffffffffull)].pos : nullptr;
+            float o8[8];
+            sph::ray_write(R, rk, best, x ? x[0] : 0.0f, x ? x[1] : 0.0f, x ? x[2] : 0.0f, o8);
+            memcpy(&hits[i], o8, sizeof(o8));
+        }
     }
     *out = info;
     return SPH_OK;

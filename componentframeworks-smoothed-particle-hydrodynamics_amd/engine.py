@@ -85,6 +85,7 @@ SPH_OPT_DIFFUSE_TIMED = 9
 SPH_OPT_NEIGHBORS_FILL = 10
 SPH_OPT_COMPONENTS_VARIANT = 11
 SPH_OPT_KNN_VARIANT = 12
+SPH_OPT_RAYS_VARIANT = 13
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -286,6 +287,22 @@ assert C.sizeof(SphKnnInfo) == 48
 SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K = 1, 2, 64
 
 
+class SphRayHit(C.Structure):
+    """struct SphRayHit of include/sph_abi.h: what one ray met first (see SPHFluidGPU.raycast); a miss is (+inf, -1, zeros)."""
+    _fields_ = [("t", C.c_float), ("id", C.c_int32), ("pos", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class SphRaysInfo(C.Structure):
+    """struct SphRaysInfo of include/sph_abi.h: what the engine's ray hits hold."""
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("voidRays", C.c_uint64), ("radius", C.c_float), ("flags", C.c_int32)]
+
+
+assert C.sizeof(SphRayHit) == 32 and C.sizeof(SphRaysInfo) == 32
+RAY_HIT_DTYPE = np.dtype(SphRayHit)
+assert RAY_HIT_DTYPE.itemsize == 32
+SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT = 1, 2
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -447,6 +464,13 @@ _ABI = {
     "sph_knn_device": (_int, [_vp, _P(_vp), _P(_vp), _P(_vp)]),
     "sph_knn_download": (_int, [_vp, _vp, _vp, _vp]),
     "sph_knn_host": (_int, [_vp, _sz, _pp, _vp, _sz, _int, _f, _int, _vp, _vp, _vp, _P(SphKnnInfo)]),
+    "sph_rays_cast": (_int, [_vp, _vp, _sz, _f, _int, _P(SphRaysInfo)]),
+    "sph_rays_cast_device": (_int, [_vp, _vp, _sz, _f, _int, _P(SphRaysInfo)]),
+    "sph_rays_info": (_int, [_vp, _P(SphRaysInfo)]),
+    "sph_rays_device": (_int, [_vp, _P(_vp)]),
+    "sph_rays_download": (_int, [_vp, _vp]),
+    "sph_rays_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
+    "sph_rays_walk_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -576,6 +600,23 @@ def _neighbor_flags(self_, half, count_only) -> int:
 
 def _knn_flags(self_, fluid_only) -> int:
     return (SPH_KNN_SELF if self_ else 0) | (SPH_KNN_FLUID_ONLY if fluid_only else 0)
+
+
+def _rays_flags(fluid_only, any_hit) -> int:
+    return (SPH_RAYS_FLUID_ONLY if fluid_only else 0) | (SPH_RAYS_ANY_HIT if any_hit else 0)
+
+
+def _rays8(rays, who):
+    """(m, 8) rays (ox, oy, oz, tmin, dx, dy, dz, tmax) as a contiguous float32 array."""
+    r = np.ascontiguousarray(rays, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise SphError(f"{who}: rays must have shape (m, 8), not {r.shape}")
+    return r
+
+
+def _split_hits(hits):
+    """A RAY_HIT_DTYPE array as (t, ids, pos, normal)."""
+    return hits["t"].copy(), hits["id"].copy(), hits["pos"].copy(), hits["normal"].copy()
 
 
 def _is_cuda_f32(t) -> bool:
@@ -1283,6 +1324,46 @@ class SPHFluidGPU:
         keep = idx >= 0
         return torch.stack((recv[keep], idx[keep].to(torch.int64)))
 
+    # -- ray casts (include/sph_abi.h "ray casts") ------------------------------------------------
+    def raycast(self, rays, radius=None, fluid_only: bool = False, any_hit: bool = False, device: bool = False):
+        """The first particle every ray enters, each particle a solid sphere of `radius` (None: 0.25 * param_h; at most half a cell).
+        rays: (m, 8) float32 rows (ox, oy, oz, tmin, dx, dy, dz, tmax), numpy or a torch device tensor (used in place); t is in units of
+        the given direction.  Returns (t (m,), ids (m,) int32, pos (m, 3), normal (m, 3)); a miss is (+inf, -1, zeros).  fluid_only
+        leaves out the records with isGhost != 0; any_hit only says whether anything is met (ids 0 / -1, t 0 / +inf).  numpy arrays, or
+        with device=True fresh torch device tensors (views of one copy of the engine's hits, as knn's rows)."""
+        import torch
+        self._push_params()
+        info = SphRaysInfo()
+        r = 0.25 * self._p.param_h if radius is None else radius
+        flags = _rays_flags(fluid_only, any_hit)
+        if isinstance(rays, torch.Tensor):
+            if not (_is_cuda_f32(rays) and rays.dim() == 2 and rays.shape[1] == 8):
+                raise SphError(f"raycast: a torch tensor of rays must be a contiguous float32 device tensor of shape (m, 8), not {tuple(rays.shape)}")
+            m = int(rays.shape[0])
+            _check(self._L.sph_rays_cast_device(self._h, C.c_void_p(rays.data_ptr()) if m else None, m, float(r), flags, C.byref(info)))
+        else:
+            r8 = _rays8(rays, "raycast")
+            _check(self._L.sph_rays_cast(self._h, _ptr(r8) if len(r8) else None, len(r8), float(r), flags, C.byref(info)))
+        return self.ray_hits(device)
+
+    def rays_info(self) -> SphRaysInfo:
+        """What the engine's hits hold: rays, hits, voidRays, radius, flags.  SphError before any raycast() call."""
+        info = SphRaysInfo()
+        _check(self._L.sph_rays_info(self._h, C.byref(info)))
+        return info
+
+    def ray_hits(self, device: bool = False):
+        """(t, ids, pos, normal) of the hits the engine holds."""
+        m = int(self.rays_info().rays)
+        if device:
+            import torch
+            z = torch.empty((m, 8), dtype=torch.float32, device="cuda")             # (one device copy of the 32-byte hits, split into views)
+            _check(self._L.sph_rays_download(self._h, C.c_void_p(z.data_ptr()) if m else None))
+            return z[:, 0], z[:, 1].view(torch.int32), z[:, 2:5], z[:, 5:8]
+        hits = np.zeros(m, RAY_HIT_DTYPE)
+        _check(self._L.sph_rays_download(self._h, _ptr(hits) if m else None))
+        return _split_hits(hits)
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -1925,6 +2006,58 @@ def knn_host(records, params, k, radius, points=None, self_=False, fluid_only=Fa
                                        _knn_flags(self_, fluid_only), _ptr(idx) if rows else None, _ptr(d2) if rows else None,
                                        _ptr(cnt) if rows else None, C.byref(info)))
     return idx, d2, cnt, info
+
+
+def rays_host(records, params, rays, radius, fluid_only=False, any_hit=False, with_info=False, walk=False):
+    """sph_rays_host: (t, ids, pos, normal) of SPHFluidGPU.raycast on host records, computed on the CPU by brute force over all
+    participating records with the same hit arithmetic: the definition of a cast.  with_info adds the SphRaysInfo.  walk=True runs
+    sph_rays_walk_host in its place: the device's grid walk, on the host.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    r8 = _rays8(rays, "rays_host")
+    hits = np.zeros(len(r8), RAY_HIT_DTYPE)
+    info = SphRaysInfo()
+    L = load_library()
+    _check((L.sph_rays_walk_host if walk else L.sph_rays_host)(_ptr_or_none(rec), len(rec), C.byref(params), _ptr_or_none(r8), len(r8),
+                                                                   float(radius), _rays_flags(fluid_only, any_hit), _ptr_or_none(hits), C.byref(info)))
+    out = _split_hits(hits)
+    return out + (info,) if with_info else out
+
+
+def camera_rays(eye, target, up, fov_y, width, height, tmin=0.0, tmax=np.inf) -> np.ndarray:
+    """(width * height, 8) rays of a pinhole camera at `eye` looking at `target`: row y * width + x goes through the centre of pixel
+    (x, y), y downwards, of an image plane at distance 1 with a vertical field of view of fov_y radians.  Directions are not normalised
+    (the one through the image centre has length 1).  Only an array of rays: no image is written anywhere."""
+    eye, target, up = (np.asarray(v, np.float64) for v in (eye, target, up))
+    f = target - eye
+    f /= np.linalg.norm(f)
+    s = np.cross(f, up)
+    s /= np.linalg.norm(s)
+    u = np.cross(s, f)
+    th = np.tan(0.5 * float(fov_y))
+    px = ((np.arange(width) + 0.5) / width * 2.0 - 1.0) * th * (width / height)
+    py = (1.0 - (np.arange(height) + 0.5) / height * 2.0) * th
+    d = f[None, None, :] + px[None, :, None] * s[None, None, :] + py[:, None, None] * u[None, None, :]
+    r = np.zeros((height * width, 8), np.float32)
+    r[:, 0:3] = eye
+    r[:, 3] = tmin
+    r[:, 4:7] = d.reshape(-1, 3)
+    r[:, 7] = tmax
+    return r
+
+
+def parallel_rays(origin, u, v, direction, nu, nv, tmin=0.0, tmax=np.inf) -> np.ndarray:
+    """(nu * nv, 8) parallel rays: row j * nu + i starts at origin + (i + 0.5) / nu * u + (j + 0.5) / nv * v, the centres of an nu x nv
+    sheet spanned by the vectors u and v, and every ray has the given direction (not normalised)."""
+    origin, u, v, direction = (np.asarray(x, np.float64) for x in (origin, u, v, direction))
+    a = (np.arange(nu) + 0.5) / nu
+    b = (np.arange(nv) + 0.5) / nv
+    o = origin[None, None, :] + a[None, :, None] * u[None, None, :] + b[:, None, None] * v[None, None, :]
+    r = np.zeros((nu * nv, 8), np.float32)
+    r[:, 0:3] = o.reshape(-1, 3)
+    r[:, 3] = tmin
+    r[:, 4:7] = direction
+    r[:, 7] = tmax
+    return r
 
 
 def component_centers(table, grid) -> np.ndarray:

@@ -245,6 +245,33 @@ public:
         return !Check(sph_knn_download(engine, indices.empty() ? nullptr : indices.data(), dist2.empty() ? nullptr : dist2.data(),
                                        counts.empty() ? nullptr : counts.data()), "sph_knn_download");
     }
+    // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
+    // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
+    // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE
+    // memory.  The hits stay in the engine until the next call, ResetSimulation or the destructor; DownloadRayHits copies them to the host
+    // (a miss is t = +inf, id = -1, the rest 0).  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    bool CastRays(const std::vector<float>& rays8, SphRaysInfo& out, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_rays_cast(engine, rays8.empty() ? nullptr : rays8.data(), rays8.size() / 8, radius > 0.0f ? radius : 0.25f * param_h, flags, &out),
+                      "sph_rays_cast");
+    }
+    bool CastRaysDevice(const float* devRays8, size_t m, SphRaysInfo& out, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_rays_cast_device(engine, devRays8, m, radius > 0.0f ? radius : 0.25f * param_h, flags, &out), "sph_rays_cast_device");
+    }
+    SphRaysInfo RaysInfo() {
+        SphRaysInfo info{};
+        Check(sph_rays_info(engine, &info), "sph_rays_info");
+        return info;
+    }
+    bool DownloadRayHits(std::vector<SphRayHit>& hits) {
+        SphRaysInfo info{};
+        if (Check(sph_rays_info(engine, &info), "sph_rays_info")) return false;
+        hits.assign(size_t(info.rays), SphRayHit{});
+        return !Check(sph_rays_download(engine, hits.empty() ? nullptr : hits.data()), "sph_rays_download");
+    }
     // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
     // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
     // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per

@@ -50,6 +50,7 @@ extern "C" {
 /* (still 4, additions only: SphNeighborInfo, SPH_NEIGHBORS_*, sph_neighbors_build / _query / _info / _device / _export / _download / _host, SPH_OPT_NEIGHBORS_FILL -- neighbour lists) */
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
+/* (still 4, additions only: SphRayHit, SphRaysInfo, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, sph_rays_cast / _cast_device / _info / _device / _download / _host / _walk_host, SPH_OPT_RAYS_VARIANT -- ray casts against the particles) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -157,6 +158,7 @@ enum {
     SPH_OPT_NEIGHBORS_FILL = 10, /* neighbour lists (sph_neighbors_*), an A/B of the fill kernel: 0 = every lane writes the entries of its own row (default), 1 = a wave writes one row at a time with consecutive lanes; the same bits */
     SPH_OPT_COMPONENTS_VARIANT = 11, /* connected components (sph_components_*), A/Bs for measurements: bit 0 = the hook walks every candidate, not only those in front of the target's slot; bit 1 = the table kernel issues its atomics per lane, not once per wave and label; default 0; the same bits */
     SPH_OPT_KNN_VARIANT = 12,    /* k nearest neighbours (sph_knn_*), an A/B for measurements: 0 = one target per lane keeps its k best keys in LDS (default), 1 = k selection passes over the candidates without any storage (slow); the same bits */
+    SPH_OPT_RAYS_VARIANT = 13,   /* ray casts (sph_rays_*), an A/B for measurements: 0 = the rays are cast in the caller's order (default), 1 = in the order of the grid cell they enter first (a counting sort of the rays in front of the walk: faster for incoherent rays, slower for sheets and fans); the same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -936,6 +938,51 @@ int sph_knn_download(SphEngine* e, int32_t* indices, float* dist2, uint32_t* cou
  * dist2 and counts may be null. */
 int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, int k, float radius, int flags,
                  int32_t* indices, float* dist2, uint32_t* counts, SphKnnInfo* out);
+
+/* ---- ray casts against the particles (no reference counterpart) ----------------------------------------------
+ * Every participating record is a solid sphere of radius r around its position; for each of m rays the call gives the first sphere the
+ * ray ENTERS, on the device.  A ray is 8 floats, (ox, oy, oz, tmin), (dx, dy, dz, tmax); t is in units of the given direction (nothing
+ * is normalised) and tmax = +inf is allowed.  A ray is void, and a miss, when any of o, d, tmin is not finite, tmax is NaN,
+ * a = dot3(d, d) is 0 or not finite, or tmin > tmax.  0 < r <= 0.5f * cellSize (tested in fp32), r2 = r * r in fp32.
+ * A record takes part when floorf((x - gridMin) / cellSize) lies in [0, dims) on every axis BEFORE the clamp of the grid build (records
+ * outside the grid's box neither hit nor block; a NaN fails the compares); ghosts and inactive records take part like any other, and
+ * SPH_RAYS_FLUID_ONLY leaves out records with isGhost != 0.
+ * Per candidate, every operation rounded on its own except the fmaf()s: L = x_j - o, tca = dot3(L, d) * (1 / a), q = fmaf(-tca, d, L)
+ * per axis, s = r2 - dot3(q, q); s < 0 is a miss; t = tca - sqrtf(s * (1 / a)) (IEEE division and square root on both sides); accepted
+ * when tmin <= t <= tmax.  Only entries count: a sphere that contains the ray's start has t < tmin and is not hit.
+ * key(j) = ((uint64)ordered(t) << 32) | id_j, ordered() the sign-flip map from float bits to unsigned order; the result of a ray is
+ * the smallest key over all accepted participating records -- one answer whatever the order in which candidates are met, also on
+ * lattices and for coincident particles, and the same bytes on every run.  The result does not name the grid.
+ * Output: one SphRayHit per ray, in ray order: pos = fmaf(t, d, o) per axis, normal = (pos - x_id) * (1 / r); a miss is t = +inf,
+ * id = -1, the rest 0.  SPH_RAYS_ANY_HIT: only whether anything is accepted -- id 0 and t 0 on a hit, id -1 and t +inf on a miss, the
+ * rest 0; by definition it equals (first-hit id >= 0).  SphRaysInfo: hits and voidRays are integer reductions.
+ * The hits stay valid until the next sph_rays_cast / _cast_device, sph_reset or sph_destroy; a cast changes no record, a dispatch does
+ * not touch the hits, and neighbour lists, components and kNN rows have buffers of their own (no call of one kind invalidates
+ * another's).  Timed as SPH_K_OTHER.  SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as sampling); _info / _device / _download
+ * before any cast.  SPH_ERR_ARG: a null argument, a bad r, unknown flag bits, m > 2^31 - 1.  m = 0: no hits; n = 0: every ray a miss;
+ * the call succeeds. */
+enum { SPH_RAYS_FLUID_ONLY = 1, SPH_RAYS_ANY_HIT = 2 };
+typedef struct SphRayHit { float t; int32_t id; float pos[3]; float normal[3]; } SphRayHit;   /* 32 bytes */
+typedef struct SphRaysInfo { uint64_t rays, hits, voidRays; float radius; int32_t flags; } SphRaysInfo;   /* 32 bytes */
+/* m rays of 8 floats in HOST memory (may be null when m is 0): staged upload, then as _cast_device.  Synchronises. */
+int sph_rays_cast(SphEngine* e, const float* rays8, size_t m, float radius, int flags, SphRaysInfo* out);
+/* m rays of 8 floats in DEVICE memory (may be null when m is 0).  One synchronisation, for the two counts. */
+int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float radius, int flags, SphRaysInfo* out);
+/* What the engine holds. */
+int sph_rays_info(const SphEngine* e, SphRaysInfo* out);
+/* Borrowed device address: hits[rays]. */
+int sph_rays_device(SphEngine* e, const SphRayHit** hits);
+/* Copies the hits into the caller's memory, host or device (the kind of the copy follows from the address); synchronises. */
+int sph_rays_download(SphEngine* e, SphRayHit* hits);
+/* Host-only, no device, THE DEFINITION: brute force over all participating records, no grid, the same ray_hit; the same bytes.
+ * hits may be null. */
+int sph_rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                  SphRayHit* hits, SphRaysInfo* out);
+/* TEST HOOK, not part of what an application needs.  Host-only, no device: the DEVICE's walk (the same ray_walk function) over the grid
+ * as the counting sort leaves it.  Same bytes as sph_rays_host while the walk is complete; it is there so that the walk can be tested
+ * against the definition without a device. */
+int sph_rays_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                       SphRayHit* hits, SphRaysInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
