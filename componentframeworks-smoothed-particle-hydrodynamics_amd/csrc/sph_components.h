@@ -71,11 +71,7 @@ __host__ __device__ inline long long cc_fixed(float x, float gmin, double S) {
     const double d = ((double)x - (double)gmin) * S;
     return llrint(fmin(fmax(d, -68719476736.0), 68719476736.0));
 }
-__host__ __device__ inline bool cc_finite(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x7F800000u) != 0x7F800000u;
-}
+__host__ __device__ inline bool cc_finite(float f) { return float_finite(f); }
 __host__ __device__ inline bool cc_finite3(float x, float y, float z) { return cc_finite(x) && cc_finite(y) && cc_finite(z); }
 
 __device__ __forceinline__ uint32_t cc_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace sph {
 
@@ -49,6 +50,12 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ __forceinline__ float signf(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
+// Neither an infinity nor a NaN: a test on the bits, the same on both sides (scalar_, cc_, vol_, obs_ and ray_finite are this).
+__host__ __device__ inline bool float_finite(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return (u & 0x7F800000u) != 0x7F800000u;
+}
 
 // BuildGrid.comp:25-26 / SPHFluid.comp:86-87: cell coordinate along one axis.
 __device__ __forceinline__ int cell_axis(float p, float gmin, float cellSize, int dim) {

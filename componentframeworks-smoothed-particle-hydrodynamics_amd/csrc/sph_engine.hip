@@ -243,8 +243,10 @@ struct SphEngine {
     // sph_sample_points (host arrays): device copies of the probes and of the results
     DevBuf<float4> d_sampleIn;
     DevBuf<SphSample> d_sampleOut;
-    // sph_neighbors_*: ids of the sorted slots, counts, tile sums / maxima / totals of the scan, and the lists themselves (CSR)
-    DevBuf<int32_t> d_nbIds, d_nbIndices;
+    // the queries that walk the grid by particle id (neighbour lists, kNN): ids of the sorted slots, refilled by every run (slot_ids_fill)
+    DevBuf<int32_t> d_slotIds;
+    // sph_neighbors_*: counts, tile sums / maxima / totals of the scan, and the lists themselves (CSR)
+    DevBuf<int32_t> d_nbIndices;
     DevBuf<uint32_t> d_nbCnt, d_nbTileMax;
     DevBuf<unsigned long long> d_nbTileSums;
     DevBuf<long long> d_nbOffsets;
@@ -260,8 +262,8 @@ struct SphEngine {
     SphComponentInfo ccInfo{};
     bool ccValid = false;                   // the buffers hold the result ccInfo describes
     int optCcVariant = 0;                   // SPH_OPT_COMPONENTS_VARIANT
-    // sph_knn_*: ids of the sorted slots, the dense rows (indices, dist2: rows * k each), the counts and the two words of the reduction
-    DevBuf<int32_t> d_knnIds, d_knnIndices;
+    // sph_knn_*: the dense rows (indices, dist2: rows * k each), the counts and the two words of the reduction
+    DevBuf<int32_t> d_knnIndices;
     DevBuf<float> d_knnDist2;
     DevBuf<uint32_t> d_knnCounts;
     DevBuf<unsigned long long> d_knnStats;
@@ -483,7 +485,7 @@ void free_grid_buffers(SphEngine* e) {
 // One free function per feature (callers have drained the stream, or the function does): sph_destroy calls each.
 void sample_free(SphEngine* e) { e->d_sampleIn.release(); e->d_sampleOut.release(); }
 void neighbors_free(SphEngine* e) {
-    e->d_nbIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbTileMax.release(); e->d_nbTileSums.release(); e->d_nbOffsets.release();
+    e->d_slotIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbTileMax.release(); e->d_nbTileSums.release(); e->d_nbOffsets.release();
     e->nbInfo = SphNeighborInfo{};
     e->nbIndexed = false;
 }
@@ -494,7 +496,7 @@ void components_free(SphEngine* e) {
     e->ccValid = false;
 }
 void knn_free(SphEngine* e) {
-    e->d_knnIds.release(); e->d_knnIndices.release(); e->d_knnDist2.release(); e->d_knnCounts.release(); e->d_knnStats.release();
+    e->d_slotIds.release(); e->d_knnIndices.release(); e->d_knnDist2.release(); e->d_knnCounts.release(); e->d_knnStats.release();
     e->knnInfo = SphKnnInfo{};
 }
 void rays_free(SphEngine* e) {
@@ -833,18 +835,8 @@ int scalars_step(SphEngine* e, const SimK& k, float dt) {
 // gathered copy, then scalar_pair / scalar_finish per target in slot order.
 template <int K>
 float scalars_step_loop(const SimK& k, float kLap, float dt, const sph::ScalarCoef& co, const SphParticle* P, size_t n, float* values) {
-    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int cx = sph::scalar_cell_axis(P[i].pos[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(P[i].pos[1], k.gminy, k.cellSize, k.gy),
-                  cz = sph::scalar_cell_axis(P[i].pos[2], k.gminz, k.cellSize, k.gz);
-        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-        start[cell[i] + 1] += 1u;
-    }
-    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-    {
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) order[fill[cell[i]]++] = (uint32_t)i;
-    }
+    const sph::HostGrid grid(k, P, n);
+    const std::vector<uint32_t>& order = grid.order;
     std::vector<float> pv(4 * n), sC((size_t)(K + 1) * n);
     for (size_t q = 0; q < n; ++q) {
         const SphParticle& p = P[order[q]];
@@ -860,20 +852,16 @@ float scalars_step_loop(const SimK& k, float kLap, float dt, const sph::ScalarCo
         if (!(ci[K] > 0.0f) || !sph::scalar_finite(X[0]) || !sph::scalar_finite(X[1]) || !sph::scalar_finite(X[2]) || !(X[3] > 0.0f)) continue;
         float a[K], W = 0.0f;
         for (int c = 0; c < K; ++c) a[c] = 0.0f;
-        const int cx = sph::scalar_cell_axis(X[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(X[1], k.gminy, k.cellSize, k.gy),
-                  cz = sph::scalar_cell_axis(X[2], k.gminz, k.cellSize, k.gz);
-        const int xlo = std::max(cx - 1, 0), xhi = std::min(cx + 1, k.gx - 1);
-        for (int r = 0; r < 9; ++r) {
-            const int nz = cz + r / 3 - 1, ny = cy + r % 3 - 1;
-            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
-            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
-            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+        int cx, cy, cz;
+        grid.cell(X, cx, cy, cz);
+        grid.rows(1, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
                 if (j == q) continue;
                 const float* Y = &pv[4 * (size_t)j];
                 const float* cj = &sC[(size_t)j * (K + 1)];
                 sph::scalar_pair<K>(k.h, k.h2, X[0], X[1], X[2], X[3], ci, Y[0], Y[1], Y[2], cj[K] > 0.0f ? Y[3] : 0.0f, cj, a, W);
             }
-        }
+        });
         float out[K];
         const float s = sph::scalar_finish<K>(co, kLap, dt, ci, a, W, out);
         for (int c = 0; c < K; ++c) values[(size_t)order[q] * K + c] = out[c];
@@ -2783,18 +2771,68 @@ int sph_sync_deadline(SphEngine* e, double seconds) {
 }
 
 // ---- field sampling (sph_sample.h) ---------------------------------------------------------------
+// What no query of the current state supports: a z-slab engine, the linked-list grid.  Entry points that allocate state this first.
+static int query_refused(const SphEngine* e) {
+    if (e->slab) return fail(SPH_ERR_STATE, "sampling a z-slab engine is not supported: its halo records after a step are the step's entry state");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "sampling needs the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    return SPH_OK;
+}
 // The grid of the CURRENT state, built outside a substep exactly as sph_download_grid builds it.  The next dispatch builds its
 // own (dispatch_one always does), so nothing of this build reaches the simulation.
 static int sample_grid(SphEngine* e, SimK& k, bool orderAll = false) {
-    if (e->slab) return fail(SPH_ERR_STATE, "sampling a z-slab engine is not supported: its halo records after a step are the step's entry state");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "sampling needs the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     int rc;
-    if ((rc = validate_params(e->params))) return rc;
+    if ((rc = query_refused(e)) || (rc = validate_params(e->params))) return rc;
     sph::compute_grid_extents(e->params, e->grid);
     if ((rc = ensure_grid_buffers(e))) return rc;
     make_simk(e->params, e->grid, e->params.param_timeStep, k);
     if ((rc = import_state(e))) return rc;
     return build_grid(e, k, false, orderAll);
+}
+
+// How every query that checks arguments against the grid opens: the refusal, then the params, then the grid they give (for the cell
+// size and the cell count).  Nothing is allocated and nothing of the engine changes; the caller's order from here on is argument
+// check, allocation, sample_grid.
+static int query_grid(const SphEngine* e, SphGridInfo& g) {
+    int rc;
+    if ((rc = query_refused(e)) || (rc = validate_params(e->params))) return rc;
+    sph::compute_grid_extents(e->params, g);
+    return SPH_OK;
+}
+
+// A search radius as an argument: the stencil half-width through *stencil.
+static int radius_stencil(float radius, float cellSize, int* stencil) {
+    *stencil = sph::neighbor_stencil(radius, cellSize);
+    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
+    return SPH_OK;
+}
+static sph::NbK make_nbk(const SphEngine* e, float radius, int stencil, int flags) {
+    sph::NbK nb;
+    nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)e->n;
+    return nb;
+}
+// ids[slot] of the grid sample_grid has just built, into d_slotIds (grown by the caller).
+static void slot_ids_fill(SphEngine* e) {
+    if (!e->n) return;
+    Timed t(e, SPH_K_OTHER);
+    hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(e->n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, e->d_slotIds.p, e->idBase, (uint32_t)e->n);
+}
+// The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0: tileSums holds blocks_for(rows, kScanTile) + 2 words
+// (the totals, sum and largest count, lie behind the tile sums), tileMax one per tile.  One synchronisation: hostTotals[0 .. 2).
+static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets,
+                         unsigned long long hostTotals[2]) {
+    const int tiles = blocks_for(rows, kScanTile);
+    unsigned long long* totals = tileSums + tiles;
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
+        hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
+        hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
+                           (const unsigned long long*)totals, offsets);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hostTotals, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
 }
 
 // A regular lattice of points as an argument: at least `least` points along every axis, a finite spacing > 0, at most 2^31 - 1 points.
@@ -2830,8 +2868,8 @@ int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, Sp
 int sph_sample_points(SphEngine* e, const float* points4, size_t m, SphSample* out) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (m && (!points4 || !out)) return fail(SPH_ERR_ARG, "null argument");
-    if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
     int rc;
+    if ((rc = query_refused(e))) return rc;                                         // (the refusal, before any allocation)
     if (m && ((rc = e->d_sampleIn.grow(e, m)) || (rc = e->d_sampleOut.grow(e, m)))) return rc;
     if (m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
     if ((rc = sph_sample_points_device(e, reinterpret_cast<const float*>(e->d_sampleIn.p), m, e->d_sampleOut.p))) return rc;
@@ -2873,9 +2911,7 @@ static int neighbors_check(float radius, float cellSize, int flags, bool query, 
     if (flags & ~(SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF | SPH_NEIGHBORS_COUNT_ONLY)) return fail(SPH_ERR_ARG, "unknown neighbour flags %d", flags);
     if ((flags & SPH_NEIGHBORS_SELF) && (flags & SPH_NEIGHBORS_HALF)) return fail(SPH_ERR_ARG, "SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF: a half list has no diagonal");
     if (query && (flags & (SPH_NEIGHBORS_SELF | SPH_NEIGHBORS_HALF))) return fail(SPH_ERR_ARG, "SPH_NEIGHBORS_SELF / _HALF apply to particle lists only");
-    *stencil = sph::neighbor_stencil(radius, cellSize);
-    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
-    return SPH_OK;
+    return radius_stencil(radius, cellSize, stencil);
 }
 
 // Grid of the current state, ids, count, scan, one synchronisation for the total, then the fill (arguments already checked for null).
@@ -2883,58 +2919,36 @@ static int neighbors_run(SphEngine* e, const float4* devPoints, size_t m, float 
     using namespace sph;
     const bool query = devPoints != nullptr || m != 0;
     SimK k;
+    SphGridInfo g;
     int rc, stencil = 0;
-    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
-    if ((rc = validate_params(e->params))) return rc;
-    {
-        SphGridInfo g;
-        sph::compute_grid_extents(e->params, g);
-        if ((rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
-    }
+    if ((rc = query_grid(e, g)) || (rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
     const size_t n = e->n, rows = query ? m : n;
     const int tiles = blocks_for(rows, kScanTile);
     e->nbInfo = SphNeighborInfo{};                                                  // (the lists held so far end here)
     e->nbIndexed = false;
-    if ((rc = e->d_nbIds.grow(e, n)) || (rc = e->d_nbCnt.grow(e, rows)) || (rc = e->d_nbOffsets.grow(e, rows + 1)) ||
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_nbCnt.grow(e, rows)) || (rc = e->d_nbOffsets.grow(e, rows + 1)) ||
         (rc = e->d_nbTileSums.grow(e, (size_t)tiles + 2)) || (rc = e->d_nbTileMax.grow(e, (size_t)tiles))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    NbK nb;
-    nb.R2 = radius * radius;
-    nb.s = stencil;
-    nb.flags = flags;
-    nb.idBase = e->idBase;
-    nb.n = (uint32_t)n;
-    unsigned long long* totals = e->d_nbTileSums.p + tiles;                         // (sum, largest count) behind the tile sums
+    const NbK nb = make_nbk(e, radius, stencil, flags);
     const dim3 grid(blocks_for(rows)), block(kBlock);
     auto walk = [&](bool fill) {
         Timed t(e, SPH_K_OTHER);
-        if (query && fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (query && fill) hipLaunchKernelGGL((k_neighbors_fill<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (query) hipLaunchKernelGGL((k_neighbors_count<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, e->d_nbCnt.p);
-        else if (fill) hipLaunchKernelGGL((k_neighbors_fill<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else hipLaunchKernelGGL((k_neighbors_count<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_nbIds.p, devPoints, rows, e->d_nbCnt.p);
+        if (query && fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (query && fill) hipLaunchKernelGGL((k_neighbors_fill<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else if (query) hipLaunchKernelGGL((k_neighbors_count<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, e->d_nbCnt.p);
+        else if (fill) hipLaunchKernelGGL((k_neighbors_fill<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
+        else hipLaunchKernelGGL((k_neighbors_count<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, e->d_nbCnt.p);
     };
     unsigned long long host[2] = {0ull, 0ull};
     if (rows) {
-        if (n) {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(n)), block, 0, e->stream, (const float4*)e->d_sOwn, e->d_nbIds.p, e->idBase, (uint32_t)n);
-        }
+        slot_ids_fill(e);
         walk(false);                                                                // (writes cnt[row] of every row)
-        {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_nbCnt.p, rows, e->d_nbTileSums.p, e->d_nbTileMax.p);
-            hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, e->d_nbTileSums.p, (const uint32_t*)e->d_nbTileMax.p, tiles, totals);
-            hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_nbCnt.p, rows, (const unsigned long long*)e->d_nbTileSums.p,
-                               (const unsigned long long*)totals, e->d_nbOffsets.p);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+        if ((rc = scan_counts64(e, e->d_nbCnt.p, rows, e->d_nbTileSums.p, e->d_nbTileMax.p, e->d_nbOffsets.p, host))) return rc;
     } else {
         HIP_TRY(hipMemsetAsync(e->d_nbOffsets.p, 0, sizeof(long long), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
     SphNeighborInfo info{};
     info.rows = rows; info.total = host[0]; info.radius = radius; info.stencil = stencil; info.flags = flags; info.kind = query ? 2 : 1;
     info.maxCount = (uint32_t)host[1];
@@ -3012,41 +3026,23 @@ int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* 
     sph::make_simk(*params, g, params->param_timeStep, k);
     if ((rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
     const float R2 = radius * radius;
-    // the grid as the counting sort leaves it: cells ascending, members ascending by index
-    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
-    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
-        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
-        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
-    };
-    for (size_t i = 0; i < n; ++i) {
-        int cx, cy, cz;
-        cellOf(particles[i].pos, cx, cy, cz);
-        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-        start[cell[i] + 1] += 1u;
-    }
-    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-    {
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
-    }
+    const sph::HostGrid grid(k, particles, n);
+    const std::vector<uint32_t>& order = grid.order;
+    const std::vector<uint32_t>& slotOf = grid.slotOf;
     const size_t rows = query ? m : n;
     // f(id) per kept entry of row r, in order
     auto walk = [&](size_t r, auto&& f) {
         const float* x = query ? points4 + 4 * r : particles[r].pos;
         if (query && !(sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2]))) return;
         int cx, cy, cz;
-        cellOf(x, cx, cy, cz);
-        const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
-        for (int rr = 0; rr < w * w; ++rr) {
-            const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
-            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
-            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
-            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+        grid.cell(x, cx, cy, cz);
+        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
                 const float* y = particles[order[j]].pos;
                 const bool acc = sph::neighbor_accept(x[0], x[1], x[2], y[0], y[1], y[2], R2);
                 if (query ? acc : sph::neighbor_keep(flags, j == slotOf[r], acc, (uint32_t)r, order[j])) f(order[j]);
             }
-        }
+        });
     };
     uint64_t total = 0;
     uint32_t maxCount = 0;
@@ -3080,9 +3076,7 @@ static_assert(sizeof(SphComponentInfo) == 56, "SphComponentInfo must be 56 bytes
 
 static int components_check(float radius, float cellSize, int flags, int* stencil) {
     if (flags & ~SPH_COMPONENTS_FLUID_ONLY) return fail(SPH_ERR_ARG, "unknown component flags %d", flags);
-    *stencil = sph::neighbor_stencil(radius, cellSize);
-    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
-    return SPH_OK;
+    return radius_stencil(radius, cellSize, stencil);
 }
 
 int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo* out) {
@@ -3090,12 +3084,9 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (!out) return fail(SPH_ERR_ARG, "null argument");
     SimK k;
-    int rc, stencil = 0;
-    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
-    if ((rc = validate_params(e->params))) return rc;
     SphGridInfo g;
-    sph::compute_grid_extents(e->params, g);
-    if ((rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
     const size_t n = e->n;
     const int tiles = blocks_for(n, kScanTile);
     e->ccInfo = SphComponentInfo{};                                                 // (the result held so far ends here)
@@ -3108,8 +3099,7 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
     info.rows = n; info.radius = radius; info.stencil = stencil; info.flags = flags;
     uint64_t C = 0;
     if (n) {
-        NbK nb;
-        nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)n;
+        const NbK nb = make_nbk(e, radius, stencil, flags);
         const dim3 grid(blocks_for(n)), block(kBlock);
         const float4* pv = (const float4*)e->d_sPV;
         const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
@@ -3155,7 +3145,6 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
         }
         if (!done) return fail(SPH_ERR_STATE, "components: no hook launch found every edge inside one tree within %u rounds", rounds);
         info.rounds = rounds;
-        unsigned long long* totals = e->d_ccTileSums.p + tiles;
         {
             Timed t(e, SPH_K_OTHER);
             hipLaunchKernelGGL(k_components_minid, grid, block, 0, e->stream, ids, (const uint32_t*)parent, e->d_ccMinId.p, (uint32_t)n);
@@ -3164,23 +3153,8 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
             Timed t(e, SPH_K_OTHER);
             hipLaunchKernelGGL(k_components_roots, grid, block, 0, e->stream, ids, (const uint32_t*)parent, (const uint32_t*)e->d_ccMinId.p, e->d_ccRoots.p, e->d_ccFlag.p, (uint32_t)n);
         }
-        {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_ccFlag.p, n, e->d_ccTileSums.p, e->d_ccTileMax.p);
-        }
-        {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, e->d_ccTileSums.p, (const uint32_t*)e->d_ccTileMax.p, tiles, totals);
-        }
-        {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), block, 0, e->stream, (const uint32_t*)e->d_ccFlag.p, n, (const unsigned long long*)e->d_ccTileSums.p,
-                               (const unsigned long long*)totals, e->d_ccOffsets.p);
-        }
         unsigned long long host[2] = {0ull, 0ull};
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        if ((rc = scan_counts64(e, e->d_ccFlag.p, n, e->d_ccTileSums.p, e->d_ccTileMax.p, e->d_ccOffsets.p, host))) return rc;
         C = host[0];
         if (C > n) return fail(SPH_ERR_STATE, "components: %llu bodies of %zu records", (unsigned long long)C, n);
         if ((rc = e->d_ccTable.grow(e, (size_t)C))) return rc;
@@ -3259,23 +3233,9 @@ int sph_components_host(const SphParticle* particles, size_t n, const SphParams*
     if ((rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
     const float R2 = radius * radius;
     const bool fluidOnly = (flags & SPH_COMPONENTS_FLUID_ONLY) != 0;
-    // the grid as the counting sort leaves it: cells ascending, members ascending by index (as sph_neighbors_host)
-    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
-    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
-        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
-        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
-    };
-    for (size_t i = 0; i < n; ++i) {
-        int cx, cy, cz;
-        cellOf(particles[i].pos, cx, cy, cz);
-        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-        start[cell[i] + 1] += 1u;
-    }
-    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-    {
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
-    }
+    const sph::HostGrid grid(k, particles, n);
+    const std::vector<uint32_t>& order = grid.order;
+    const std::vector<uint32_t>& slotOf = grid.slotOf;
     // a plain sequential union-find over particle ids: the smaller root wins, so a root is the smallest id of its tree
     std::vector<uint32_t> parent(n);
     for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
@@ -3290,20 +3250,16 @@ int sph_components_host(const SphParticle* particles, size_t n, const SphParams*
         if (!takesPart(i)) continue;
         const float* x = particles[i].pos;
         int cx, cy, cz;
-        cellOf(x, cx, cy, cz);
-        const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
-        for (int rr = 0; rr < w * w; ++rr) {
-            const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
-            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
-            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
-            for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1] && j < slotOf[i]; ++j) {      // an edge is seen from its larger slot
+        grid.cell(x, cx, cy, cz);
+        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe && j < slotOf[i]; ++j) {                   // an edge is seen from its larger slot
                 const uint32_t o = order[j];
                 const float* y = particles[o].pos;
                 if (!takesPart(o) || !sph::neighbor_accept(x[0], x[1], x[2], y[0], y[1], y[2], R2)) continue;
                 const uint32_t a = find((uint32_t)i), b = find(o);
                 if (a != b) parent[std::max(a, b)] = std::min(a, b);
             }
-        }
+        });
     }
     std::vector<int32_t> lab(n, -1), root(n, -1);
     std::vector<sph::CcRow> rows;
@@ -3362,9 +3318,7 @@ static int knn_check(int k, float radius, float cellSize, int flags, bool query,
     if (flags & ~(SPH_KNN_SELF | SPH_KNN_FLUID_ONLY)) return fail(SPH_ERR_ARG, "unknown kNN flags %d", flags);
     if (query && (flags & SPH_KNN_SELF)) return fail(SPH_ERR_ARG, "SPH_KNN_SELF applies to particle rows only");
     if (k < 1 || k > SPH_KNN_MAX_K) return fail(SPH_ERR_ARG, "k = %d (1 .. %d)", k, (int)SPH_KNN_MAX_K);
-    *stencil = sph::neighbor_stencil(radius, cellSize);
-    if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
-    return SPH_OK;
+    return radius_stencil(radius, cellSize, stencil);
 }
 
 // One launch of the variant and class in force (arguments already checked).
@@ -3374,7 +3328,7 @@ static void knn_launch(SphEngine* e, bool query, const sph::SimK& k, const sph::
                             unsigned long long*);
     auto go = [&](Kernel kernel, int threads) {
         hipLaunchKernelGGL(kernel, dim3(blocks_for(rows, threads)), dim3(threads), 0, e->stream, k, nb, kk, (const float4*)e->d_sPV,
-                           (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_knnIds.p, (const float4*)e->d_sOwn, devPoints, rows, e->d_knnIndices.p,
+                           (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn, devPoints, rows, e->d_knnIndices.p,
                            e->d_knnDist2.p, e->d_knnCounts.p, e->d_knnStats.p);
     };
     if (e->optKnnVariant == 1) return go(query ? k_knn_select<false> : k_knn_select<true>, kBlock);
@@ -3390,28 +3344,19 @@ static void knn_launch(SphEngine* e, bool query, const sph::SimK& k, const sph::
 static int knn_run(SphEngine* e, bool query, const float4* devPoints, size_t m, int kk, float radius, int flags, SphKnnInfo* out) {
     using namespace sph;
     SimK k;
+    SphGridInfo g;
     int rc, stencil = 0;
-    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
-    if ((rc = validate_params(e->params))) return rc;
-    {
-        SphGridInfo g;
-        sph::compute_grid_extents(e->params, g);
-        if ((rc = knn_check(kk, radius, g.cellSize, flags, query, &stencil))) return rc;
-    }
+    if ((rc = query_grid(e, g)) || (rc = knn_check(kk, radius, g.cellSize, flags, query, &stencil))) return rc;
     const size_t n = e->n, rows = query ? m : n;
     e->knnInfo = SphKnnInfo{};                                                      // (the rows held so far end here)
-    if ((rc = e->d_knnIds.grow(e, n)) || (rc = e->d_knnIndices.grow(e, rows * (size_t)kk)) || (rc = e->d_knnDist2.grow(e, rows * (size_t)kk)) ||
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_knnIndices.grow(e, rows * (size_t)kk)) || (rc = e->d_knnDist2.grow(e, rows * (size_t)kk)) ||
         (rc = e->d_knnCounts.grow(e, rows)) || (rc = e->d_knnStats.grow(e, 2))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    NbK nb;
-    nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)n;
+    const NbK nb = make_nbk(e, radius, stencil, flags);
     unsigned long long host[2] = {0ull, 0ull};
     if (rows) {
         HIP_TRY(hipMemsetAsync(e->d_knnStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
-        if (n) {
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, e->d_knnIds.p, e->idBase, (uint32_t)n);
-        }
+        slot_ids_fill(e);
         {
             Timed t(e, SPH_K_OTHER);
             knn_launch(e, query, k, nb, kk, devPoints, rows);
@@ -3483,23 +3428,9 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
     if ((rc = knn_check(kk, radius, g.cellSize, flags, query, &stencil))) return rc;
     const float R2 = radius * radius;
     const bool self = (flags & SPH_KNN_SELF) != 0, fluidOnly = (flags & SPH_KNN_FLUID_ONLY) != 0;
-    // the grid as the counting sort leaves it: cells ascending, members ascending by index (as sph_neighbors_host)
-    std::vector<uint32_t> cell(n), start((size_t)k.numCells + 1, 0u), order(n), slotOf(n);
-    auto cellOf = [&](const float* x, int& cx, int& cy, int& cz) {
-        cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
-        cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
-    };
-    for (size_t i = 0; i < n; ++i) {
-        int cx, cy, cz;
-        cellOf(particles[i].pos, cx, cy, cz);
-        cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-        start[cell[i] + 1] += 1u;
-    }
-    for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-    {
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cell[i]]++; order[slotOf[i]] = (uint32_t)i; }
-    }
+    const sph::HostGrid grid(k, particles, n);
+    const std::vector<uint32_t>& order = grid.order;
+    const std::vector<uint32_t>& slotOf = grid.slotOf;
     const size_t rows = query ? m : n;
     SphKnnInfo info{};
     info.rows = rows; info.radius = radius; info.k = kk; info.stencil = stencil; info.flags = flags; info.kind = query ? 2 : 1;
@@ -3510,13 +3441,9 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
         const bool walk = query ? (sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
         if (walk) {
             int cx, cy, cz;
-            cellOf(x, cx, cy, cz);
-            const int xlo = std::max(cx - stencil, 0), xhi = std::min(cx + stencil, k.gx - 1), w = 2 * stencil + 1;
-            for (int rr = 0; rr < w * w; ++rr) {
-                const int nz = cz + rr / w - stencil, ny = cy + rr % w - stencil;
-                if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
-                const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
-                for (uint32_t j = start[rowBase + xlo]; j < start[rowBase + xhi + 1]; ++j) {
+            grid.cell(x, cx, cy, cz);
+            grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
                     if (!query && !self && j == slotOf[r]) continue;
                     const uint32_t o = order[j];
                     const float* y = particles[o].pos;
@@ -3524,7 +3451,7 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
                     if (!(r2 < R2) || (fluidOnly && particles[o].isGhost != 0)) continue;
                     keys.push_back(sph::knn_key(r2, o));
                 }
-            }
+            });
         }
         std::sort(keys.begin(), keys.end());
         const size_t c = std::min(keys.size(), (size_t)kk);
@@ -3562,26 +3489,15 @@ int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float ra
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (!out || (m && !devRays8)) return fail(SPH_ERR_ARG, "null argument");
     SimK k;
+    SphGridInfo g;
     int rc;
-    if (e->slab || e->optGridBuild == 1) return sample_grid(e, k);                  // (the refusal, before any allocation)
-    if ((rc = validate_params(e->params))) return rc;
-    {
-        SphGridInfo g;
-        sph::compute_grid_extents(e->params, g);
-        if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;
-    }
+    if ((rc = query_grid(e, g)) || (rc = rays_check(radius, g.cellSize, flags, m))) return rc;
     e->raysValid = false;                                                           // (the hits held so far end here)
     if ((rc = e->d_rayHits.grow(e, 2 * m)) || (rc = e->d_rayStats.grow(e, 2))) return rc;
     const bool ordered = e->optRaysVariant == 1 && m && e->n;
-    {
-        SphGridInfo g;
-        sph::compute_grid_extents(e->params, g);
-        const size_t bins = (size_t)g.numCells + 1;
-        if (ordered) {
-            if ((rc = e->d_rayBin.grow(e, m)) || (rc = e->d_rayOrder.grow(e, m)) || (rc = e->d_rayCount.grow(e, bins)) || (rc = e->d_rayStart.grow(e, bins + 1)) ||
-                (rc = e->d_rayBlockSums.grow(e, (size_t)blocks_for(bins, kScanTile) + 1))) return rc;
-        }
-    }
+    const size_t bins = (size_t)g.numCells + 1;
+    if (ordered && ((rc = e->d_rayBin.grow(e, m)) || (rc = e->d_rayOrder.grow(e, m)) || (rc = e->d_rayCount.grow(e, bins)) || (rc = e->d_rayStart.grow(e, bins + 1)) ||
+                    (rc = e->d_rayBlockSums.grow(e, (size_t)blocks_for(bins, kScanTile) + 1)))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
     const RayK rk = rays_consts(radius, flags, e->idBase, e->n);
     const float4* rays = reinterpret_cast<const float4*>(devRays8);
@@ -3615,14 +3531,9 @@ int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float ra
 int sph_rays_cast(SphEngine* e, const float* rays8, size_t m, float radius, int flags, SphRaysInfo* out) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (!out || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
-    if (e->slab || e->optGridBuild == 1) { sph::SimK k; return sample_grid(e, k); }   // (the refusal, before any allocation)
+    SphGridInfo g;
     int rc;
-    if ((rc = validate_params(e->params))) return rc;
-    {
-        SphGridInfo g;
-        sph::compute_grid_extents(e->params, g);
-        if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;                // (nothing is staged for a call that will be refused)
-    }
+    if ((rc = query_grid(e, g)) || (rc = rays_check(radius, g.cellSize, flags, m))) return rc;   // (nothing is staged for a call that will be refused)
     if (m && (rc = e->d_rayIn.grow(e, 2 * m))) return rc;
     if (m) HIP_TRY(hipMemcpyAsync(e->d_rayIn.p, rays8, m * 2 * sizeof(float4), hipMemcpyHostToDevice, e->stream));
     return sph_rays_cast_device(e, reinterpret_cast<const float*>(e->d_rayIn.p), m, radius, flags, out);
@@ -3680,38 +3591,12 @@ static int rays_host(const SphParticle* particles, size_t n, const SphParams* pa
     std::vector<uint8_t> takesPart(n);
     for (size_t j = 0; j < n; ++j)
         takesPart[j] = !(fluidOnly && particles[j].isGhost != 0) && sph::ray_in_grid(k, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2]);
-    // for the walk: the grid as the counting sort leaves it (cells ascending, members ascending by index), positions in slot order
-    std::vector<uint32_t> start, order;
-    std::vector<float4> spos;
-    if (walk) {
-        std::vector<uint32_t> cell(n);
-        start.assign((size_t)k.numCells + 1, 0u);
-        order.resize(n);
-        spos.resize(n);
-        for (size_t i = 0; i < n; ++i) {
-            const float* x = particles[i].pos;
-            const int cx = sph::scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx), cy = sph::scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy),
-                      cz = sph::scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
-            cell[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-            start[cell[i] + 1] += 1u;
-        }
-        for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t slot = fill[cell[i]]++;
-            order[slot] = (uint32_t)i;
-            spos[slot] = make_float4(particles[i].pos[0], particles[i].pos[1], particles[i].pos[2], 0.0f);
-        }
-    }
-    auto rows = [&](int cx, int cy, int cz, auto&& f) {                                   // neighbor_rows at s = 1
-        const int xlo = std::max(cx - 1, 0), xhi = std::min(cx + 1, k.gx - 1);
-        for (int r = 0; r < 9; ++r) {
-            const int nz = cz + r / 3 - 1, ny = cy + r % 3 - 1;
-            if (nz < 0 || nz >= k.gz || ny < 0 || ny >= k.gy) continue;
-            const size_t rowBase = ((size_t)nz * k.gy + ny) * k.gx;
-            f(start[rowBase + xlo], std::min(start[rowBase + xhi + 1], (uint32_t)n));
-        }
-    };
+    // for the walk: the grid of the records, and their positions in slot order
+    const sph::HostGrid grid(k, particles, walk ? n : 0);
+    const std::vector<uint32_t>& order = grid.order;
+    std::vector<float4> spos(order.size());
+    for (size_t j = 0; j < order.size(); ++j) spos[j] = make_float4(particles[order[j]].pos[0], particles[order[j]].pos[1], particles[order[j]].pos[2], 0.0f);
+    auto rows = [&](int cx, int cy, int cz, auto&& f) { grid.rows(1, cx, cy, cz, f); };
     SphRaysInfo info{};
     info.rays = m; info.radius = radius; info.flags = flags;
     for (size_t i = 0; i < m; ++i) {
@@ -3819,7 +3704,7 @@ int sph_extract_surface(SphEngine* e, const float origin[3], const float spacing
     int rc;
     if ((rc = surface_check_lattice(origin, spacing, dims, iso))) return rc;
     if (field < SPH_FIELD_DENSITY || field > SPH_FIELD_SPEED) return fail(SPH_ERR_ARG, "field %d is not a scalar field", field);
-    if (e->slab || e->optGridBuild == 1) { SimK k; return sample_grid(e, k); }     // (the refusal, before any allocation)
+    if ((rc = query_refused(e))) return rc;
     const size_t npts = (size_t)dims[0] * dims[1] * dims[2];
     if ((rc = e->d_surfVol.grow(e, npts))) return rc;
     if ((rc = sph_sample_lattice(e, origin, spacing, dims, field, e->d_surfVol.p))) return rc;

@@ -50,9 +50,10 @@ struct NbK {
     uint32_t idBase, n;
 };
 
-// sample_rows at half-width s: f(first slot, end slot) per row that lies inside the grid, in ascending slot order.
+// sample_rows at half-width s: f(first slot, end slot) per row that lies inside the grid, in ascending slot order.  __host__ too: the
+// *_host references walk their grid (HostGrid of sph_scalar.h) with this very function.
 template <class F>
-__device__ __forceinline__ void neighbor_rows(const SimK& k, const uint32_t* __restrict__ cellStart, int s, uint32_t n, int cx, int cy, int cz, F&& f) {
+__host__ __device__ __forceinline__ void neighbor_rows(const SimK& k, const uint32_t* __restrict__ cellStart, int s, uint32_t n, int cx, int cy, int cz, F&& f) {
     const int xlo = max(cx - s, 0), xhi = min(cx + s, k.gx - 1), w = 2 * s + 1;
     for (int r = 0; r < w * w; ++r) {
         const int nz = cz + r / w - s, ny = cy + r % w - s;

@@ -64,11 +64,7 @@ struct ObsAcc {
 __host__ __device__ inline float obs_dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return fmaf(az, bz, fmaf(ay, by, ax * bx));
 }
-__host__ __device__ inline bool obs_finite(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x7F800000u) != 0x7F800000u;
-}
+__host__ __device__ inline bool obs_finite(float f) { return float_finite(f); }
 
 // q / |q|, |q| = sqrtf(fmaf(z, z, fmaf(y, y, fmaf(x, x, w * w)))), four IEEE divisions.
 __host__ __device__ inline void obs_normalize(float (&q)[4]) {

@@ -72,7 +72,7 @@ __host__ __device__ inline uint32_t ray_bits(float f) {
     memcpy(&u, &f, 4);
     return u;
 }
-__host__ __device__ inline bool ray_finite(float f) { return (ray_bits(f) & 0x7F800000u) != 0x7F800000u; }
+__host__ __device__ inline bool ray_finite(float f) { return float_finite(f); }
 // dot3 of sph_device.h for both sides.
 __host__ __device__ inline float ray_dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(az, bz, fmaf(ay, by, ax * bx)); }
 // float bits -> unsigned order (negative t below positive t), and back.

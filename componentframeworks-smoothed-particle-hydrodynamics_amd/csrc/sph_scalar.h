@@ -24,7 +24,9 @@
 #include <math.h>
 #include <string.h>
 
-#include "sph_sample.h"
+#include <vector>
+
+#include "sph_neighbors.h"   // neighbor_rows; sph_sample.h
 
 namespace sph {
 
@@ -44,11 +46,7 @@ static_assert(sizeof(ScalarCoef) == 48, "ScalarCoef is 48 bytes");
 __host__ __device__ inline float scalar_dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return fmaf(az, bz, fmaf(ay, by, ax * bx));
 }
-__host__ __device__ inline bool scalar_finite(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x7F800000u) != 0x7F800000u;
-}
+__host__ __device__ inline bool scalar_finite(float f) { return float_finite(f); }
 // cell_axis of sph_device.h for both sides (the same four IEEE operations).
 __host__ __device__ inline int scalar_cell_axis(float p, float gmin, float cellSize, int dim) {
     const float q = (p - gmin) / cellSize;
@@ -56,6 +54,34 @@ __host__ __device__ inline int scalar_cell_axis(float p, float gmin, float cellS
     f = fminf(fmaxf(f, 0.0f), (float)(dim - 1));
     return (int)f;
 }
+
+// The grid of host records as the counting sort leaves it: cells ascending, members ascending by index.  start[c] is the first sorted
+// slot of cell c, order[slot] the record in that slot, slotOf[i] the slot of record i.  Every *_host reference builds this one and
+// walks it with the device's own neighbor_rows.
+struct HostGrid {
+    const SimK& k;
+    std::vector<uint32_t> start, order, slotOf;
+    HostGrid(const SimK& k_, const SphParticle* particles, size_t n) : k(k_), start((size_t)k_.numCells + 1, 0u), order(n), slotOf(n) {
+        std::vector<uint32_t> cellOf(n);
+        for (size_t i = 0; i < n; ++i) {
+            int cx, cy, cz;
+            cell(particles[i].pos, cx, cy, cz);
+            cellOf[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+            start[cellOf[i] + 1] += 1u;
+        }
+        for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cellOf[i]]++; order[slotOf[i]] = (uint32_t)i; }
+    }
+    // The clamped cell of a point.
+    void cell(const float* x, int& cx, int& cy, int& cz) const {
+        cx = scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
+        cz = scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
+    }
+    // f(first slot, end slot) per in-grid row of the (2s + 1)^2 around a cell, in ascending slot order.
+    template <class F>
+    void rows(int s, int cx, int cy, int cz, F&& f) const { neighbor_rows(k, start.data(), s, (uint32_t)order.size(), cx, cy, cz, f); }
+};
 
 // kLap = (float)(2 m 45 / (pi h^6)) = (float)((90 m) / (pi ((h^2 h^2) h^2))), in double on the host.
 inline float scalar_klap(float mass, float h) {

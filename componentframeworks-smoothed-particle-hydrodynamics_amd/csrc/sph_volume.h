@@ -22,6 +22,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "sph_device.h"   // float_finite
+
 namespace sph {
 
 constexpr int kVolMax = 16;                  // SPH_MAX_VOLUMES
@@ -49,11 +51,7 @@ struct VolTable {
 __host__ __device__ inline float vol_dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return fmaf(az, bz, fmaf(ay, by, ax * bx));
 }
-__host__ __device__ inline bool vol_finite(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x7F800000u) != 0x7F800000u;
-}
+__host__ __device__ inline bool vol_finite(float f) { return float_finite(f); }
 __host__ __device__ inline float vol_lerp(float a, float b, float f) { return a + f * (b - a); }   // subtract, multiply, add
 
 // half_a = (0.5f (float)(dims_a - 1)) spacing_a, inv_a = 1.0f / spacing_a.

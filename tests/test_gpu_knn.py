@@ -365,6 +365,7 @@ def test_refusals_and_states(pkg):
     # null pointers are skipped by the download; device memory is told from host memory by the address
     assert L.sph_knn_download(f._h, None, None, cnt.ctypes.data_as(vp)) == 0 and np.array_equal(cnt, want[2]) and (idx == 9).all()
     d_idx = torch.zeros((n, 8), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()                                                       # (the fill runs on torch's stream, the copy on the engine's own)
     assert L.sph_knn_download(f._h, vp(d_idx.data_ptr()), d2.ctypes.data_as(vp), None) == 0
     assert np.array_equal(d_idx.cpu().numpy(), want[0]) and d2.view(np.uint32).tobytes() == want[1].view(np.uint32).tobytes()
     # the option

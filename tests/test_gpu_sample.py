@@ -260,6 +260,7 @@ def test_refusals_and_edge_cases(pkg):
     p4 = torch.zeros((len(state), 4), dtype=torch.float32, device="cuda")
     p4[:, :3] = torch.from_numpy(state["pos"][:, :3].copy()).cuda()
     o = torch.zeros((len(state), 8), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()                      # the fills run on torch's stream, the kernel on the engine's own
     f.sample_device(p4.data_ptr(), len(state), o.data_ptr())
     f.sync()
     assert o.cpu().numpy().tobytes() == f.sample(state["pos"][:, :3]).tobytes()
