@@ -29,5 +29,7 @@ from .engine import (  # noqa: F401
     component_centers,
     SPH_OPT_KNN_VARIANT, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, SphKnnInfo, knn_host,
     SPH_OPT_RAYS_VARIANT, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, SphRayHit, SphRaysInfo, RAY_HIT_DTYPE, rays_host, camera_rays, parallel_rays,
+    SPH_OPT_SHELL_TIMED, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, SphShell, SphShellConfig, SphShellInfo, SHELL_DTYPE, shell_host,
+    shell_config,
 )
 from . import build, synthetic  # noqa: F401

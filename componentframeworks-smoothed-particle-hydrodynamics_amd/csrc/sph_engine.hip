@@ -27,6 +27,7 @@
 #include "sph_neighbors.h"
 #include "sph_components.h"
 #include "sph_knn.h"
+#include "sph_shell.h"
 #include "sph_rays.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
@@ -277,6 +278,16 @@ struct SphEngine {
     SphRaysInfo raysInfo{};
     bool raysValid = false;
     int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
+    // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
+    // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets, tile sums / maxima); the two words of the reduction
+    DevBuf<sph::ShellRow> d_shRows;
+    DevBuf<int32_t> d_shIds, d_shSlots;
+    DevBuf<float4> d_shNrm;
+    DevBuf<uint32_t> d_shFlagRow, d_shFlagSlot, d_shTileMax;
+    DevBuf<unsigned long long> d_shTileSums, d_shStats;
+    DevBuf<long long> d_shOffsets;
+    SphShellInfo shellInfo{};               // kind 0: no rows
+    int optShellTimed = 0;                  // SPH_OPT_SHELL_TIMED: which launches of a build the timing bracket covers (0 all, 1 pass 1, 2 pass 2, 3 scans and compactions)
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
     DevBuf<uint16_t> d_surfCode;
@@ -498,6 +509,11 @@ void components_free(SphEngine* e) {
 void knn_free(SphEngine* e) {
     e->d_slotIds.release(); e->d_knnIndices.release(); e->d_knnDist2.release(); e->d_knnCounts.release(); e->d_knnStats.release();
     e->knnInfo = SphKnnInfo{};
+}
+void shell_free(SphEngine* e) {
+    e->d_shRows.release(); e->d_shIds.release(); e->d_shSlots.release(); e->d_shNrm.release(); e->d_shFlagRow.release(); e->d_shFlagSlot.release();
+    e->d_shTileMax.release(); e->d_shTileSums.release(); e->d_shStats.release(); e->d_shOffsets.release();
+    e->shellInfo = SphShellInfo{};
 }
 void rays_free(SphEngine* e) {
     e->d_rayIn.release(); e->d_rayHits.release(); e->d_rayStats.release();
@@ -1330,6 +1346,7 @@ int sph_destroy(SphEngine* e) {
     components_free(e);
     knn_free(e);
     rays_free(e);
+    shell_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1370,6 +1387,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     components_free(e);                                               // (and the components)
     knn_free(e);                                                      // (and the k nearest neighbours)
     rays_free(e);                                                     // (and the ray hits)
+    shell_free(e);                                                    // (and the free-surface rows)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1414,6 +1432,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_COMPONENTS_VARIANT: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optCcVariant = value; break;
     case SPH_OPT_KNN_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optKnnVariant = value; break;
     case SPH_OPT_RAYS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaysVariant = value; break;
+    case SPH_OPT_SHELL_TIMED: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optShellTimed = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
         if ((value & 8) && !e->d_stats) {
@@ -1441,6 +1460,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_COMPONENTS_VARIANT: *value = e->optCcVariant; break;
     case SPH_OPT_KNN_VARIANT: *value = e->optKnnVariant; break;
     case SPH_OPT_RAYS_VARIANT: *value = e->optRaysVariant; break;
+    case SPH_OPT_SHELL_TIMED: *value = e->optShellTimed; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
     default: return fail(SPH_ERR_ARG, "unknown option %d", option);
@@ -2818,16 +2838,22 @@ static void slot_ids_fill(SphEngine* e) {
 }
 // The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0: tileSums holds blocks_for(rows, kScanTile) + 2 words
 // (the totals, sum and largest count, lie behind the tile sums), tileMax one per tile.  One synchronisation: hostTotals[0 .. 2).
-static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets,
-                         unsigned long long hostTotals[2]) {
+// scan_counts64_launch: the three launches alone (no bracket, no synchronisation); the totals lie at tileSums + tiles.
+static unsigned long long* scan_counts64_launch(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets) {
     const int tiles = blocks_for(rows, kScanTile);
     unsigned long long* totals = tileSums + tiles;
+    hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
+    hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
+    hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
+                       (const unsigned long long*)totals, offsets);
+    return totals;
+}
+static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets,
+                         unsigned long long hostTotals[2]) {
+    unsigned long long* totals;
     {
         Timed t(e, SPH_K_OTHER);
-        hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
-        hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
-        hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
-                           (const unsigned long long*)totals, offsets);
+        totals = scan_counts64_launch(e, cnt, rows, tileSums, tileMax, offsets);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hostTotals, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -3463,6 +3489,212 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
         info.total += c;
         info.rowsFull += c == (size_t)kk ? 1u : 0u;
     }
+    *out = info;
+    return SPH_OK;
+}
+
+// ---- free-surface particles (sph_shell.h) ------------------------------------------------------------
+static_assert(sizeof(SphShell) == 32 && sizeof(SphShellConfig) == 16 && sizeof(SphShellInfo) == 48, "SphShell is 32 bytes, SphShellConfig 16, SphShellInfo 48");
+static_assert(sizeof(sph::ShellRow) == sizeof(SphShell) && offsetof(sph::ShellRow, crest) == offsetof(SphShell, crest) &&
+              offsetof(sph::ShellRow, flags) == offsetof(SphShell, flags), "sph_shell.h mirrors SphShell");
+static_assert(SPH_SHELL_FLUID_ONLY == sph::kShellFluidOnly && SPH_SHELL_MEMBER == sph::kShellMember && SPH_SHELL_ISOLATED == sph::kShellIsolated,
+              "sph_shell.h mirrors SPH_SHELL_*");
+
+void sph_shell_default(SphShellConfig* cfg) {
+    if (!cfg) return;
+    cfg->radius = 0.0f; cfg->offset = 0.10f; cfg->minCount = 0u; cfg->flags = 0;
+}
+
+// The config as an argument: *radius is the radius in force (cfg.radius <= 0: h), the stencil half-width through *stencil.
+static int shell_check(const SphShellConfig& cfg, float h, float cellSize, float* radius, int* stencil) {
+    if (cfg.flags & ~SPH_SHELL_FLUID_ONLY) return fail(SPH_ERR_ARG, "unknown shell flags %d", cfg.flags);
+    if (!std::isfinite(cfg.offset) || cfg.offset < 0.0f) return fail(SPH_ERR_ARG, "offset %g is not finite or < 0", (double)cfg.offset);
+    *radius = cfg.radius <= 0.0f ? h : cfg.radius;
+    return radius_stencil(*radius, cellSize, stencil);
+}
+static sph::ShellK shell_consts(const SphShellConfig& cfg, float radius) {
+    sph::ShellK sk;
+    sk.R = radius; sk.R2 = radius * radius; sk.offset = cfg.offset; sk.minCount = cfg.minCount;
+    return sk;
+}
+
+// Grid of the current state, ids, pass 1, the scan of the flags by row (ids) and -- particle rows -- by slot (the targets of pass 2), pass 2.
+// One synchronisation in the middle, for numShell (it sizes pass 2) and the two words of the reduction, and the one that ends the call.
+static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m, const SphShellConfig& cfg, SphShellInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    float radius = 0.0f;
+    if ((rc = query_grid(e, g)) || (rc = shell_check(cfg, e->params.param_h, g.cellSize, &radius, &stencil))) return rc;
+    const size_t n = e->n, rows = query ? m : n, tiles = (size_t)blocks_for(rows, kScanTile);
+    e->shellInfo = SphShellInfo{};                                                  // (the rows held so far end here)
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_shRows.grow(e, rows)) || (rc = e->d_shIds.grow(e, rows)) || (rc = e->d_shFlagRow.grow(e, rows)) ||
+        (rc = e->d_shOffsets.grow(e, rows + 1)) || (rc = e->d_shTileSums.grow(e, tiles + 2)) || (rc = e->d_shTileMax.grow(e, tiles)) ||
+        (rc = e->d_shStats.grow(e, 2))) return rc;
+    if (!query && ((rc = e->d_shNrm.grow(e, n)) || (rc = e->d_shFlagSlot.grow(e, n)) || (rc = e->d_shSlots.grow(e, n)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, radius, stencil, cfg.flags);
+    const ShellK sk = shell_consts(cfg, radius);
+    const int timed = e->optShellTimed;
+    unsigned long long stats[2] = {0ull, 0ull}, totals[2] = {0ull, 0ull};
+    if (rows) {
+        const dim3 grid(blocks_for(rows)), block(kBlock);
+        const float4* pv = (const float4*)e->d_sPV;
+        const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
+        HIP_TRY(hipMemsetAsync(e->d_shStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
+        std::unique_ptr<Timed> t;
+        auto bracket = [&](int part) { t.reset(); if (timed == 0 || timed == part) t.reset(new Timed(e, SPH_K_OTHER)); };
+        if (timed == 0 || timed == 1) slot_ids_fill(e);
+        else if (n) hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(n)), block, 0, e->stream, (const float4*)e->d_sOwn, e->d_slotIds.p, e->idBase, (uint32_t)n);
+        bracket(1);
+        if (query) hipLaunchKernelGGL((k_shell_gather<false>), grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn,
+                                      devPoints, rows, e->d_shRows.p, e->d_shFlagRow.p, (float4*)nullptr, (uint32_t*)nullptr, e->d_shStats.p);
+        else hipLaunchKernelGGL((k_shell_gather<true>), grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn,
+                                devPoints, rows, e->d_shRows.p, e->d_shFlagRow.p, e->d_shNrm.p, e->d_shFlagSlot.p, e->d_shStats.p);
+        bracket(3);                                                                 // ids[]: the flags by row, scanned and compacted
+        unsigned long long* devTotals = scan_counts64_launch(e, e->d_shFlagRow.p, rows, e->d_shTileSums.p, e->d_shTileMax.p, e->d_shOffsets.p);
+        hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagRow.p, (const long long*)e->d_shOffsets.p, rows, e->d_shIds.p);
+        t.reset();
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(totals, devTotals, sizeof(totals), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(stats, e->d_shStats.p, sizeof(stats), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const size_t numShell = (size_t)totals[0];
+        if (numShell > rows) return fail(SPH_ERR_STATE, "shell: %zu shell rows of %zu", numShell, rows);
+        if (!query && numShell) {                                                   // the same scan by slot: pass 2's targets in ascending slot order
+            bracket(3);
+            (void)scan_counts64_launch(e, e->d_shFlagSlot.p, n, e->d_shTileSums.p, e->d_shTileMax.p, e->d_shOffsets.p);
+            hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagSlot.p, (const long long*)e->d_shOffsets.p, n, e->d_shSlots.p);
+            bracket(2);
+            hipLaunchKernelGGL(k_shell_crest, dim3(blocks_for(numShell)), block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p,
+                               (const float4*)e->d_shNrm.p, (const int32_t*)e->d_shSlots.p, numShell, rows, e->d_shRows.p);
+            t.reset();
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphShellInfo info{};
+    info.rows = rows; info.numShell = totals[0]; info.numIsolated = stats[0]; info.maxCount = (uint32_t)stats[1]; info.radius = radius;
+    info.stencil = stencil; info.kind = query ? 2 : 1; info.flags = cfg.flags;
+    e->shellInfo = info;
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_shell_build(SphEngine* e, const SphShellConfig* cfg, SphShellInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !out) return fail(SPH_ERR_ARG, "null argument");
+    return shell_run(e, false, nullptr, 0, *cfg, out);
+}
+
+int sph_shell_query(SphEngine* e, const float* devPoints4, size_t m, const SphShellConfig* cfg, SphShellInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !out || (m && !devPoints4)) return fail(SPH_ERR_ARG, "null argument");
+    if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    return shell_run(e, true, reinterpret_cast<const float4*>(devPoints4), m, *cfg, out);
+}
+
+int sph_shell_info(const SphEngine* e, SphShellInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->shellInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no free-surface rows");
+    *out = e->shellInfo;
+    return SPH_OK;
+}
+
+int sph_shell_device(SphEngine* e, const SphShell** rows, const int32_t** ids) {
+    if (!e || !rows || !ids) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->shellInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no free-surface rows");
+    *rows = reinterpret_cast<const SphShell*>(e->d_shRows.p);
+    *ids = e->d_shIds.p;
+    return SPH_OK;
+}
+
+int sph_shell_download(SphEngine* e, SphShell* rows, int32_t* ids) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->shellInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no free-surface rows");
+    const size_t r = (size_t)e->shellInfo.rows, s = (size_t)e->shellInfo.numShell;
+    if (rows && r) HIP_TRY(hipMemcpyAsync(rows, e->d_shRows.p, r * sizeof(SphShell), hipMemcpyDefault, e->stream));
+    if (ids && s) HIP_TRY(hipMemcpyAsync(ids, e->d_shIds.p, s * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, const SphShellConfig* cfg,
+                   SphShell* rowsOut, int32_t* ids, float* sums4, SphShellInfo* out) {
+    if (!params || !cfg || !out || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    int rc, stencil = 0;
+    float radius = 0.0f;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = shell_check(*cfg, params->param_h, g.cellSize, &radius, &stencil))) return rc;
+    const sph::ShellK sk = shell_consts(*cfg, radius);
+    const bool fluidOnly = (cfg->flags & SPH_SHELL_FLUID_ONLY) != 0;
+    const sph::HostGrid grid(k, particles, n);
+    const std::vector<uint32_t>& order = grid.order;
+    const std::vector<uint32_t>& slotOf = grid.slotOf;
+    const size_t rows = query ? m : n;
+    std::vector<sph::ShellRow> res(rows);
+    SphShellInfo info{};
+    info.rows = rows; info.radius = radius; info.stencil = stencil; info.kind = query ? 2 : 1; info.flags = cfg->flags;
+    for (size_t r = 0; r < rows; ++r) {                                             // pass 1
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        sph::shell_zero(res[r]);
+        if (sums4) sums4[4 * r] = sums4[4 * r + 1] = sums4[4 * r + 2] = sums4[4 * r + 3] = 0.0f;
+        bool walk = sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2]);
+        if (!query && fluidOnly && particles[r].isGhost != 0) walk = false;
+        if (!walk) continue;
+        sph::ShellAcc a;
+        sph::shell_reset(a);
+        int cx, cy, cz;
+        grid.cell(x, cx, cy, cz);
+        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                if (!query && j == slotOf[r]) continue;
+                const uint32_t o = order[j];
+                const float* y = particles[o].pos;
+                float dx, dy, dz, r2;
+                if (!sph::shell_accept(x[0], x[1], x[2], y[0], y[1], y[2], sk.R2, dx, dy, dz, r2)) continue;
+                if (fluidOnly && particles[o].isGhost != 0) continue;
+                sph::shell_add(a, dx, dy, dz, r2, sk.R2);
+            }
+        });
+        sph::shell_finish(a, sk, res[r]);
+        if (sums4) { sums4[4 * r] = a.Sx; sums4[4 * r + 1] = a.Sy; sums4[4 * r + 2] = a.Sz; sums4[4 * r + 3] = a.W; }
+        if (res[r].flags & sph::kShellIsolated) info.numIsolated += 1u;
+        info.maxCount = std::max(info.maxCount, res[r].count);
+    }
+    for (size_t r = 0; r < rows && !query; ++r) {                                   // pass 2: shell targets, shell candidates
+        if (!(res[r].flags & sph::kShellMember)) continue;
+        const float* x = particles[r].pos;
+        const float* nrm = res[r].normal;
+        long long crest = 0ll;
+        int cx, cy, cz;
+        grid.cell(x, cx, cy, cz);
+        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                const uint32_t o = order[j];
+                if (!(res[o].flags & sph::kShellMember) || j == slotOf[r]) continue;
+                const float* y = particles[o].pos;
+                float dx, dy, dz, r2;
+                if (!sph::shell_accept(x[0], x[1], x[2], y[0], y[1], y[2], sk.R2, dx, dy, dz, r2)) continue;
+                crest += sph::shell_crest_term(nrm[0], nrm[1], nrm[2], res[o].normal[0], res[o].normal[1], res[o].normal[2], dx, dy, dz, r2, sk.R);
+            }
+        });
+        res[r].crest = sph::shell_crest_value(crest);
+    }
+    for (size_t r = 0; r < rows; ++r) {
+        if (!(res[r].flags & sph::kShellMember)) continue;
+        if (ids) ids[info.numShell] = (int32_t)r;
+        info.numShell += 1u;
+    }
+    if (rowsOut && rows) memcpy(rowsOut, res.data(), rows * sizeof(SphShell));
     *out = info;
     return SPH_OK;
 }

@@ -86,6 +86,7 @@ SPH_OPT_NEIGHBORS_FILL = 10
 SPH_OPT_COMPONENTS_VARIANT = 11
 SPH_OPT_KNN_VARIANT = 12
 SPH_OPT_RAYS_VARIANT = 13
+SPH_OPT_SHELL_TIMED = 14
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -303,6 +304,30 @@ assert RAY_HIT_DTYPE.itemsize == 32
 SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT = 1, 2
 
 
+class SphShell(C.Structure):
+    """struct SphShell of include/sph_abi.h: the free-surface record of one particle or query point (see SPHFluidGPU.shell)."""
+    _fields_ = [("normal", C.c_float * 3), ("offsetRatio", C.c_float), ("crest", C.c_float), ("count", C.c_uint32), ("flags", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class SphShellConfig(C.Structure):
+    """struct SphShellConfig of include/sph_abi.h: radius (<= 0: param_h), offset threshold, minCount, flags (see shell_config())."""
+    _fields_ = [("radius", C.c_float), ("offset", C.c_float), ("minCount", C.c_uint32), ("flags", C.c_int32)]
+
+
+class SphShellInfo(C.Structure):
+    """struct SphShellInfo of include/sph_abi.h: what the engine's free-surface rows hold."""
+    _fields_ = [("rows", C.c_uint64), ("numShell", C.c_uint64), ("numIsolated", C.c_uint64), ("maxCount", C.c_uint32), ("radius", C.c_float),
+                ("stencil", C.c_int32), ("kind", C.c_int32), ("flags", C.c_int32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(SphShell) == 32 and C.sizeof(SphShellConfig) == 16 and C.sizeof(SphShellInfo) == 48
+SHELL_DTYPE = np.dtype(SphShell)
+assert SHELL_DTYPE.itemsize == 32
+SPH_SHELL_FLUID_ONLY = 1
+SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED = 1, 2
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -471,6 +496,14 @@ _ABI = {
     "sph_rays_download": (_int, [_vp, _vp]),
     "sph_rays_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
     "sph_rays_walk_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
+    # free-surface particles
+    "sph_shell_default": (None, [_P(SphShellConfig)]),
+    "sph_shell_build": (_int, [_vp, _P(SphShellConfig), _P(SphShellInfo)]),
+    "sph_shell_query": (_int, [_vp, _vp, _sz, _P(SphShellConfig), _P(SphShellInfo)]),
+    "sph_shell_info": (_int, [_vp, _P(SphShellInfo)]),
+    "sph_shell_device": (_int, [_vp, _P(_vp), _P(_vp)]),
+    "sph_shell_download": (_int, [_vp, _vp, _vp]),
+    "sph_shell_host": (_int, [_vp, _sz, _pp, _vp, _sz, _P(SphShellConfig), _vp, _vp, _vp, _P(SphShellInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -1364,6 +1397,59 @@ class SPHFluidGPU:
         _check(self._L.sph_rays_download(self._h, _ptr(hits) if m else None))
         return _split_hits(hits)
 
+    # -- free-surface particles (include/sph_abi.h "free-surface particles") ----------------------
+    def shell(self, radius=None, offset: float = 0.10, min_count: int = 0, fluid_only: bool = False, device: bool = False):
+        """The free-surface shell of the particles from their positions alone: (rows, ids).  rows is a SHELL_DTYPE array numbered by
+        particle id (normal, offsetRatio, crest, count, flags: SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED), ids the int32 particle ids of the
+        shell in ascending order.  A particle is in the shell when the weighted centroid of its neighbours within `radius` (None:
+        param_h; at most three cells) lies further than offset * radius from it, when it has fewer than min_count neighbours, or none;
+        normal points out of the fluid, crest measures how sharply convex the shell is there.  fluid_only leaves the records with
+        isGhost != 0 out of every sum and gives them all-zero rows.  With device=True torch device tensors: ((n, 8) float32 rows --
+        columns 0:3 normal, 3 offsetRatio, 4 crest, 5 / 6 count / flags as bits (view(torch.int32)) -- and ids (numShell,) int32)."""
+        self._push_params()
+        info = SphShellInfo()
+        cfg = shell_config(radius=0.0 if radius is None else radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+        _check(self._L.sph_shell_build(self._h, C.byref(cfg), C.byref(info)))
+        return self.shell_rows(device)
+
+    def query_shell(self, points, radius, offset: float = 0.10, min_count: int = 0, fluid_only: bool = False, device: bool = False):
+        """The same first pass around (m, 3) or (m, 4) query points (a torch device tensor of (m, 4) float32 is used in place): row i is
+        the record of points[i] (no own slot is left out, crest is 0), ids lists the flagged points.  A smooth surface normal at a ray
+        hit or a mesh vertex.  A point with a non-finite coordinate has an all-zero row."""
+        import torch
+        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
+            dev = points
+        else:
+            dev = torch.from_numpy(_points4(points, "query_shell", keep_w=False)).cuda()
+        self._push_params()
+        info = SphShellInfo()
+        cfg = shell_config(radius=radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+        m = int(dev.shape[0])
+        _check(self._L.sph_shell_query(self._h, C.c_void_p(dev.data_ptr()) if m else None, m, C.byref(cfg), C.byref(info)))
+        return self.shell_rows(device)
+
+    def shell_info(self) -> SphShellInfo:
+        """What the engine's free-surface rows hold: rows, numShell, numIsolated, maxCount, radius, stencil, kind (1 particles, 2 query),
+        flags.  SphError before any shell() / query_shell() call."""
+        info = SphShellInfo()
+        _check(self._L.sph_shell_info(self._h, C.byref(info)))
+        return info
+
+    def shell_rows(self, device: bool = False):
+        """(rows, ids) of the free-surface rows the engine holds."""
+        info = self.shell_info()
+        rows, ns = int(info.rows), int(info.numShell)
+        if device:
+            import torch
+            z = torch.empty((rows, 8), dtype=torch.float32, device="cuda")          # (one device copy of the 32-byte rows)
+            ids = torch.empty(ns, dtype=torch.int32, device="cuda")
+            _check(self._L.sph_shell_download(self._h, C.c_void_p(z.data_ptr()) if rows else None, C.c_void_p(ids.data_ptr()) if ns else None))
+            return z, ids
+        out = np.zeros(rows, SHELL_DTYPE)
+        ids = np.zeros(ns, np.int32)
+        _check(self._L.sph_shell_download(self._h, _ptr(out) if rows else None, _ptr(ids) if ns else None))
+        return out, ids
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -1913,10 +1999,11 @@ def write_points_ply(path, records: np.ndarray) -> None:
 
 
 def _copy_config(config, overrides):
-    cfg = SphDiffuseConfig.from_buffer_copy(config)
+    kind = type(config)
+    cfg = kind.from_buffer_copy(config)
     for name, value in overrides.items():
-        if name not in dict(SphDiffuseConfig._fields_) or name == "pad":
-            raise SphError(f"SphDiffuseConfig has no field {name}")
+        if name not in dict(kind._fields_) or name == "pad":
+            raise SphError(f"{kind.__name__} has no field {name}")
         setattr(cfg, name, value)
     return cfg
 
@@ -2006,6 +2093,31 @@ def knn_host(records, params, k, radius, points=None, self_=False, fluid_only=Fa
                                        _knn_flags(self_, fluid_only), _ptr(idx) if rows else None, _ptr(d2) if rows else None,
                                        _ptr(cnt) if rows else None, C.byref(info)))
     return idx, d2, cnt, info
+
+
+def shell_config(**overrides) -> SphShellConfig:
+    """sph_shell_default with the named fields replaced.  No device is needed."""
+    cfg = SphShellConfig()
+    load_library().sph_shell_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def shell_host(records, params, radius=None, offset=0.10, min_count=0, fluid_only=False, points=None, sums=False):
+    """sph_shell_host: (rows, ids, info) of SPHFluidGPU.shell (points None) or query_shell on host records, computed on the CPU by the
+    device's own per-candidate, finish and crest functions over the counting sort of neighbors_host, in the same order: the same bytes.
+    sums=True adds the (rows, 4) float32 sums of pass 1 (Sx, Sy, Sz, W) the rows were finished from.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    p4 = None if points is None else _points4(points, "shell_host", keep_w=False)
+    rows = len(rec) if p4 is None else len(p4)
+    out, ids, acc = np.zeros(rows, SHELL_DTYPE), np.zeros(rows, np.int32), np.zeros((rows, 4), np.float32)
+    info = SphShellInfo()
+    cfg = shell_config(radius=0.0 if radius is None else radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+    pp = None if p4 is None else _ptr(p4 if len(p4) else np.zeros((1, 4), np.float32))   # (non-null: query rows, also for m = 0)
+    _check(load_library().sph_shell_host(_ptr_or_none(rec), len(rec), C.byref(params), pp, rows if p4 is not None else 0, C.byref(cfg),
+                                         _ptr(out) if rows else None, _ptr(ids) if rows else None, _ptr(acc) if sums and rows else None,
+                                         C.byref(info)))
+    res = (out, ids[:int(info.numShell)].copy(), info)
+    return res + (acc,) if sums else res
 
 
 def rays_host(records, params, rays, radius, fluid_only=False, any_hit=False, with_info=False, walk=False):

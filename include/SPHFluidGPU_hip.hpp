@@ -245,6 +245,39 @@ public:
         return !Check(sph_knn_download(engine, indices.empty() ? nullptr : indices.data(), dist2.empty() ? nullptr : dist2.data(),
                                        counts.empty() ? nullptr : counts.data()), "sph_knn_download");
     }
+    // Free-surface particles (engine extension, sph_abi.h "free-surface particles"): per particle (rows numbered by
+    // particle id) or per query point in DEVICE memory (4 floats each) whether it lies in the outer shell of the fluid, the outward normal
+    // there, the offset of the neighbours' weighted centroid in units of the radius, and -- particle rows -- the crest measure of the shell's
+    // convexity; from the positions alone.  cfg: sph_shell_default's fields (radius <= 0: param_h; at most three cells).  The rows stay in
+    // the engine until the next call, ResetSimulation or the destructor; DownloadShell copies rows[rows] and ids[numShell] (the shell's
+    // rows, ascending) to the host.  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    static SphShellConfig ShellConfig() {
+        SphShellConfig cfg;
+        sph_shell_default(&cfg);
+        return cfg;
+    }
+    bool Shell(SphShellInfo& out, const SphShellConfig& cfg) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_shell_build(engine, &cfg, &out), "sph_shell_build");
+    }
+    bool QueryShell(const float* devPoints4, size_t m, const SphShellConfig& cfg, SphShellInfo& out) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_shell_query(engine, devPoints4, m, &cfg, &out), "sph_shell_query");
+    }
+    SphShellInfo ShellInfo() {
+        SphShellInfo info{};
+        Check(sph_shell_info(engine, &info), "sph_shell_info");
+        return info;
+    }
+    bool DownloadShell(std::vector<SphShell>& rows, std::vector<int32_t>& ids) {
+        SphShellInfo info{};
+        if (Check(sph_shell_info(engine, &info), "sph_shell_info")) return false;
+        rows.assign(size_t(info.rows), SphShell{});
+        ids.assign(size_t(info.numShell), 0);
+        return !Check(sph_shell_download(engine, rows.empty() ? nullptr : rows.data(), ids.empty() ? nullptr : ids.data()), "sph_shell_download");
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

@@ -51,6 +51,7 @@ extern "C" {
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
 /* (still 4, additions only: SphRayHit, SphRaysInfo, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, sph_rays_cast / _cast_device / _info / _device / _download / _host / _walk_host, SPH_OPT_RAYS_VARIANT -- ray casts against the particles) */
+/* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -159,6 +160,7 @@ enum {
     SPH_OPT_COMPONENTS_VARIANT = 11, /* connected components (sph_components_*), A/Bs for measurements: bit 0 = the hook walks every candidate, not only those in front of the target's slot; bit 1 = the table kernel issues its atomics per lane, not once per wave and label; default 0; the same bits */
     SPH_OPT_KNN_VARIANT = 12,    /* k nearest neighbours (sph_knn_*), an A/B for measurements: 0 = one target per lane keeps its k best keys in LDS (default), 1 = k selection passes over the candidates without any storage (slow); the same bits */
     SPH_OPT_RAYS_VARIANT = 13,   /* ray casts (sph_rays_*), an A/B for measurements: 0 = the rays are cast in the caller's order (default), 1 = in the order of the grid cell they enter first (a counting sort of the rays in front of the walk: faster for incoherent rays, slower for sheets and fans); the same bits */
+    SPH_OPT_SHELL_TIMED = 14,    /* free-surface particles (sph_shell_*), measurements only: which launches of a build the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = pass 1 (ids and the gather), 2 = pass 2 (the crest kernel), 3 = the two scans and compactions; the launches themselves are the same */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -983,6 +985,55 @@ int sph_rays_host(const SphParticle* particles, size_t n, const SphParams* param
  * against the definition without a device. */
 int sph_rays_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
                        SphRayHit* hits, SphRaysInfo* out);
+
+/* ---- free-surface particles (no reference counterpart) ---------------------------------------------------------
+ * Which particles lie in the outer shell of the fluid, which way the surface faces there, and how sharply convex it is -- from the
+ * positions alone, on the device.  Grid, radius rules (0 < R <= 3 cells), stencil, candidate order and r2 are those of the neighbour
+ * lists above.  SphShellConfig: radius (<= 0: param_h), offset (the threshold, finite and >= 0, default 0.10), minCount (default 0 =
+ * off), flags (SPH_SHELL_FLUID_ONLY: records with isGhost != 0 are never candidates and their own rows are all zero).
+ * Pass 1, for a target at x: every accepted candidate j (r2 < R2; the target's own slot is left out by identity on particle rows), in
+ * the order of the (2s + 1)^2 candidate rows, with d = x_j - x, t = R2 - r2, w = t * t:  count += 1, W += w, S = fmaf(w, d, S) per
+ * axis.  Then s2 = dot3(S, S), lim = (offset * R) * W; the target is IN THE SHELL iff count == 0 or count < minCount or s2 > lim * lim;
+ * normal = -S / sqrtf(s2) (zero where s2 == 0); offsetRatio = sqrtf(s2) / (R * W) (zero where W == 0); count == 0 also sets
+ * SPH_SHELL_ISOLATED.  A target with a non-finite coordinate has an all-zero row.
+ * Pass 2, particle rows only, for a shell particle i with normal n_i: every accepted shell candidate j != i in the same order with
+ * dot3(d, n_i) < 0 (it lies behind i's tangent plane: the surface is convex there) adds the term (1 - dot3(n_i, n_j)) *
+ * (1 - sqrtf(r2) / R), rounded once to fp32, to the crest sum -- the wave-crest sum of Ihmsen et al. 2012 over the shell.  The sum is
+ * kept in fixed point (every term truncated to a multiple of 2^-32, int64 additions, one conversion to fp32 at the end), so crest does
+ * not depend on the order of the candidates.  crest is 0 for rows that are not in the shell, for isolated rows and for query rows.  IEEE division and square root on both sides, every other operation rounded on its own
+ * except the fmaf()s; no floating-point atomics: the same bytes on every run, and the bytes of sph_shell_host.
+ * Outputs, engine-owned: rows SphShell[rows], numbered by particle id (or by query point), and ids int32[numShell], the rows in the
+ * shell in ascending order (what a renderer gathers by).  SphShellInfo: numShell, numIsolated and maxCount (the largest count) are
+ * integer reductions.  Query rows: pass 1 only, no own slot.
+ * The buffers stay valid until the next sph_shell_build / _query, sph_reset or sph_destroy; neighbour lists, components, kNN rows and
+ * ray hits have buffers of their own (no call of one kind invalidates another's); a dispatch does not touch them and a build never
+ * changes the simulation.  Timed as SPH_K_OTHER.  SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as sampling); _info /
+ * _device / _download before any build.  SPH_ERR_ARG: a null argument, a bad R, an offset that is not finite or < 0, unknown flag
+ * bits, more than 2^31 - 1 query points.  n = 0 or m = 0: empty results, the call succeeds. */
+enum { SPH_SHELL_FLUID_ONLY = 1 };                    /* SphShellConfig.flags */
+enum { SPH_SHELL_MEMBER = 1, SPH_SHELL_ISOLATED = 2 };   /* SphShell.flags */
+typedef struct SphShell { float normal[3]; float offsetRatio; float crest; uint32_t count; uint32_t flags; uint32_t pad; } SphShell;   /* 32 bytes */
+typedef struct SphShellConfig { float radius; float offset; uint32_t minCount; int32_t flags; } SphShellConfig;   /* 16 bytes */
+typedef struct SphShellInfo { uint64_t rows, numShell, numIsolated; uint32_t maxCount; float radius; int32_t stencil, kind /*0 none, 1 particles, 2 query*/, flags; uint32_t pad; } SphShellInfo;   /* 48 bytes */
+/* radius 0 (param_h), offset 0.10, minCount 0, flags 0. */
+void sph_shell_default(SphShellConfig* cfg);
+/* Rows of every particle, both passes.  Synchronises. */
+int sph_shell_build(SphEngine* e, const SphShellConfig* cfg, SphShellInfo* out);
+/* Rows of m query points of 4 floats (x, y, z, unused) in DEVICE memory (may be null when m is 0), pass 1 only.  Synchronises. */
+int sph_shell_query(SphEngine* e, const float* devPoints4, size_t m, const SphShellConfig* cfg, SphShellInfo* out);
+/* What the engine holds. */
+int sph_shell_info(const SphEngine* e, SphShellInfo* out);
+/* Borrowed device addresses: rows[rows], ids[numShell]. */
+int sph_shell_device(SphEngine* e, const SphShell** rows, const int32_t** ids);
+/* Copies into the caller's memory, host or device (the kind of each copy follows from the address); synchronises; either pointer may
+ * be null. */
+int sph_shell_download(SphEngine* e, SphShell* rows, int32_t* ids);
+/* Host-only, no device: the counting sort of sph_neighbors_host and the same per-candidate, finish and crest functions in the same
+ * order; the same bytes.  points4 NULL: particle rows of particles[0 .. n) (m ignored); else query rows of m points.  rows and ids
+ * (room for one entry per row) may be null; so may sums4, which receives the sums of pass 1 the rows were finished from, 4 floats per
+ * row (Sx, Sy, Sz, W) -- what the tests hold against a float64 restatement. */
+int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, const SphShellConfig* cfg,
+                   SphShell* rows, int32_t* ids, float* sums4, SphShellInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
