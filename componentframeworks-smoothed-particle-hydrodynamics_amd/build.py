@@ -13,7 +13,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libsph_hip.so")
 SOURCES = ["sph_engine.hip"]
-HEADERS = ["sph_device.h", "sph_host.h", "sph_kernels.h", "sph_pass.h", "sph_walk.h", "sph_shapes_ext.h", "sph_sample.h", "sph_neighbors.h", "sph_components.h", "sph_knn.h", "sph_shell.h", "sph_rays.h", "sph_surface.h", "sph_stats.h", "sph_tracer.h", "sph_scalar.h", "sph_obstacle.h", "sph_volume.h", "sph_couple.h", os.path.join("..", "..", "include", "sph_abi.h")]
+# Every header of csrc/ (a new one needs no entry here) and the ABI header: what needs_build() watches and csrc_hash() covers.
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "sph_abi.h")]
 
 # -ffp-contract=off: the arithmetic contract (DESIGN.md "Numerics") fixes where fmaf() is
 # used; the compiler must not fuse anything else.  Division / sqrt stay at hipcc's

@@ -1,7 +1,7 @@
 // sph_components.h -- connected components of the neighbour relation (bodies of fluid, droplets) with a table per body (no reference
 // counterpart).
 //
-// The graph: records i != j are joined when j is a candidate of i (sph_neighbors.h: the cells [c - s, c + s] per axis) and
+// The graph: records i != j are joined when j is a candidate of i (sph_query.h: the cells [c - s, c + s] per axis) and
 // neighbor_accept holds.  The relation is symmetric bit for bit, so its components are a well-defined result; they are named by the
 // smallest particle id they hold, which makes the output independent of the order in which anything below happens.
 //
@@ -32,7 +32,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "sph_neighbors.h"
+#include "sph_query.h"
 
 namespace sph {
 
@@ -71,8 +71,7 @@ __host__ __device__ inline long long cc_fixed(float x, float gmin, double S) {
     const double d = ((double)x - (double)gmin) * S;
     return llrint(fmin(fmax(d, -68719476736.0), 68719476736.0));
 }
-__host__ __device__ inline bool cc_finite(float f) { return float_finite(f); }
-__host__ __device__ inline bool cc_finite3(float x, float y, float z) { return cc_finite(x) && cc_finite(y) && cc_finite(z); }
+__host__ __device__ inline bool cc_finite3(float x, float y, float z) { return float_finite(x) && float_finite(y) && float_finite(z); }
 
 __device__ __forceinline__ uint32_t cc_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -105,18 +104,6 @@ __device__ __forceinline__ void cc_for_each_key(uint32_t key, bool active, F&& f
         todo &= ~__ballot(mine);
     }
 }
-__device__ __forceinline__ uint32_t cc_wave_min(uint32_t v) {
-    for (int sh = 32; sh >= 1; sh >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, sh, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t cc_wave_max(uint32_t v) {
-    for (int sh = 32; sh >= 1; sh >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, sh, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long cc_wave_sum64(unsigned long long v) {
-    for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kBlock) void k_components_init(const float4* __restrict__ own, int32_t* __restrict__ ids, uint32_t* __restrict__ parent,
                                                             uint32_t* __restrict__ minId, uint32_t idBase, uint32_t n, int flags) {
@@ -141,9 +128,9 @@ __global__ __launch_bounds__(kBlock) void k_components_hook(SimK k, NbK nb, cons
     bool hooked = false;
     if (act) {
         const float4 P = pv[2u * q];
-        const int cx = cell_axis(P.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(P.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(P.z, k.gminz, k.cellSize, k.gz);
+        const int3 cell = cell_of(k, P.x, P.y, P.z);
         uint32_t rq = kCcNone;                                                      // an ancestor of q (or q), read on the first accepted candidate
-        neighbor_rows(k, cellStart, nb.s, nb.n, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
             const uint32_t end = HALF ? min(qe, q) : qe;
             for (uint32_t j = qs; j < end; ++j) {
                 if (!HALF && j == q) continue;
@@ -191,7 +178,7 @@ __global__ __launch_bounds__(kBlock) void k_components_minid(const int32_t* __re
     const uint32_t root = act ? min(parent[q], n - 1u) : 0u;
     const int lane = threadIdx.x & 63;
     cc_for_each_key(root, act, [&](uint32_t slot, bool mine, int leader) {
-        const uint32_t m = cc_wave_min(mine ? (uint32_t)v : kCcNone);
+        const uint32_t m = wave_min(mine ? (uint32_t)v : kCcNone);
         if (lane == leader) atomicMin(minId + slot, m);
     });
 }
@@ -263,9 +250,9 @@ __global__ __launch_bounds__(kBlock) void k_components_label(SimK k, double S, c
             uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
             if (any) {
                 for (int a = 0; a < 3; ++a) {
-                    s[a] = cc_wave_sum64(mine ? sq[a] : 0ull);
-                    mn[a] = cc_wave_min(mine ? lo[a] : 0xffffffffu);
-                    mx[a] = cc_wave_max(mine ? hi[a] : 0u);
+                    s[a] = wave_sum(mine ? sq[a] : 0ull);
+                    mn[a] = wave_min(mine ? lo[a] : 0xffffffffu);
+                    mx[a] = wave_max(mine ? hi[a] : 0u);
                 }
             }
             if (lane == leader) {
@@ -311,12 +298,9 @@ __global__ __launch_bounds__(kBlock) void k_components_finish(CcRow* __restrict_
         ones = r.count == 1u ? 1ull : 0ull;
         total = r.count;
     }
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const unsigned long long o = __shfl_xor(key, sh, 64);
-        key = o > key ? o : key;
-    }
-    ones = cc_wave_sum64(ones);
-    total = cc_wave_sum64(total);
+    key = wave_max(key);
+    ones = wave_sum(ones);
+    total = wave_sum(total);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = key; sm[1][w] = ones; sm[2][w] = total; }
     __syncthreads();

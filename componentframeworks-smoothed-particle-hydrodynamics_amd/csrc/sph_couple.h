@@ -26,8 +26,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "sph_obstacle.h"
-#include "sph_scalar.h"
+#include "sph_obstacle.h"   // built on it: a source may sit in a body's frame (ObsRec), and the sweep has k_obstacles' shape (kObs*)
+#include "sph_scalar.h"     // built on it: the channels it acts on (kScalarMax)
 
 namespace sph {
 
@@ -70,13 +70,13 @@ __host__ __device__ inline bool couple_inside(const CoupleSrc& S, const ObsRec* 
     if (B) {
         const float qx = px - B->c[0], qy = py - B->c[1], qz = pz - B->c[2];
         const float* M = B->M;
-        dx = obs_dot3(qx, qy, qz, M[0], M[3], M[6]) - S.center[0];   // l = M^T (p - c_b), d = l - center
-        dy = obs_dot3(qx, qy, qz, M[1], M[4], M[7]) - S.center[1];
-        dz = obs_dot3(qx, qy, qz, M[2], M[5], M[8]) - S.center[2];
+        dx = dot3(qx, qy, qz, M[0], M[3], M[6]) - S.center[0];   // l = M^T (p - c_b), d = l - center
+        dy = dot3(qx, qy, qz, M[1], M[4], M[7]) - S.center[1];
+        dz = dot3(qx, qy, qz, M[2], M[5], M[8]) - S.center[2];
     } else {
         dx = px - S.center[0]; dy = py - S.center[1]; dz = pz - S.center[2];
     }
-    if (S.shape == COUPLE_SPHERE) return obs_dot3(dx, dy, dz, dx, dy, dz) < S.size[0] * S.size[0];
+    if (S.shape == COUPLE_SPHERE) return dot3(dx, dy, dz, dx, dy, dz) < S.size[0] * S.size[0];
     return fabsf(dx) < S.size[0] && fabsf(dy) < S.size[1] && fabsf(dz) < S.size[2];
 }
 
@@ -97,7 +97,7 @@ __host__ __device__ inline bool couple_kick(const float* beta, const float* ref,
     float s = 0.0f;
 #pragma unroll
     for (int k = 0; k < K; ++k) s = fmaf(beta[k], c[k] - ref[k], s);
-    if (!scalar_finite(s) || s == 0.0f) return false;
+    if (!float_finite(s) || s == 0.0f) return false;
     const float f = dt * s;
     vx = vx - f * gx; vy = vy - f * gy; vz = vz - f * gz;
     return true;
@@ -125,7 +125,7 @@ __host__ __device__ inline void couple_box(const CoupleSrc& S, const ObsRec* B, 
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         X.e[a] = X.e[a] * 1.001f + 1e-6f + 1e-5f * mag;
-        if (!(X.e[a] >= 0.0f) || !scalar_finite(X.c[a])) X.e[a] = INFINITY;   // (a box that cannot be formed culls nothing)
+        if (!(X.e[a] >= 0.0f) || !float_finite(X.c[a])) X.e[a] = INFINITY;   // (a box that cannot be formed culls nothing)
     }
 }
 
@@ -160,7 +160,7 @@ __device__ __forceinline__ void couple_slot(const CoupleTab* __restrict__ tab, c
                 float old = 0.0f;
 #pragma unroll
                 for (int k = 0; k < K; ++k) if (k == ch) old = cv[k];
-                if (scalar_finite(old) && ch >= 0 && ch < K) {
+                if (float_finite(old) && ch >= 0 && ch < K) {
                     const float now = couple_apply(S, dt, old);
 #pragma unroll
                     for (int k = 0; k < K; ++k) if (k == ch) cv[k] = now;
@@ -171,7 +171,7 @@ __device__ __forceinline__ void couple_slot(const CoupleTab* __restrict__ tab, c
             }
             const unsigned long long h = (unsigned long long)__popcll(__ballot(hit));
             if (h == 0ull) continue;                                  // (wave-uniform: every term is +0.0)
-            for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o, 64);
+            t = wave_sum(t);
             if (lane == 0) { rowSum[i] += t; rowHits[i] += h; }
         }
         if (wrote) {
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(kObsBlock) void k_scalar_couple(const CoupleTab* __
         for (int j = 0; j < kObsUnroll; ++j) {
             const int s = base + j * kObsBlock + threadIdx.x;
             const uint32_t id = fbits(V[j].w) - idBase;
-            const bool cand = s < n && id < (uint32_t)n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && obs_finite(P[j].x) && obs_finite(P[j].y) &&
-                              obs_finite(P[j].z);
+            const bool cand = s < n && id < (uint32_t)n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && float_finite(P[j].x) && float_finite(P[j].y) &&
+                              float_finite(P[j].z);
             couple_slot<K, SRC, BUOY>(tab, bodies, nBodies, nSrc, boxes, dt, gx, gy, gz, vel, c, s, P[j], V[j], id, cand, ssum[wave], shits[wave], lane);
         }
     }

@@ -9,6 +9,7 @@
 // GPUs (DESIGN.md "Numerics").
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -45,20 +46,23 @@ enum : uint32_t {
     F_DEAD = 16u      // z-slab mode: slot no longer part of this rank's set (left or stale ghost); skipped by the sort
 };
 
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+// The dot product of the whole engine, on both sides: the *_host twins run this very function.
+__host__ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return fmaf(az, bz, fmaf(ay, by, ax * bx));
 }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ __forceinline__ float signf(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
-// Neither an infinity nor a NaN: a test on the bits, the same on both sides (scalar_, cc_, vol_, obs_ and ray_finite are this).
+// Neither an infinity nor a NaN: a test on the bits, the same on both sides.
 __host__ __device__ inline bool float_finite(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);
     return (u & 0x7F800000u) != 0x7F800000u;
 }
+// A point a kernel may walk from (probes, query points, targets).
+__device__ __forceinline__ bool sample_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
-// BuildGrid.comp:25-26 / SPHFluid.comp:86-87: cell coordinate along one axis.
-__device__ __forceinline__ int cell_axis(float p, float gmin, float cellSize, int dim) {
+// BuildGrid.comp:25-26 / SPHFluid.comp:86-87: cell coordinate along one axis.  On both sides: four IEEE operations.
+__host__ __device__ __forceinline__ int cell_axis(float p, float gmin, float cellSize, int dim) {
     float q = (p - gmin) / cellSize;
     float f = floorf(q);
     f = fminf(fmaxf(f, 0.0f), (float)(dim - 1));
@@ -70,6 +74,10 @@ __device__ __forceinline__ int cell_axis(float p, float gmin, float cellSize, in
 __device__ __forceinline__ int cell_z_global(const SimK& k, float pz) { return cell_axis(pz, k.gminz, k.cellSize, k.gzGlobal); }
 __device__ __forceinline__ int cell_z_local(const SimK& k, float pz) {
     return min(max(cell_z_global(k, pz) - k.zoff, 0), k.gz - 1);
+}
+// The clamped cell of a point, no z offset (every query, sampler and *_host twin; the substep's kernels take z through cell_z_local).
+__host__ __device__ __forceinline__ int3 cell_of(const SimK& k, float x, float y, float z) {
+    return make_int3(cell_axis(x, k.gminx, k.cellSize, k.gx), cell_axis(y, k.gminy, k.cellSize, k.gy), cell_axis(z, k.gminz, k.cellSize, k.gz));
 }
 // z-slab engines.  Round 4: the exchange FOLLOWS a particle across up to kSlabJump cell layers in z per substep (halo copies are one layer
 // deep and migrants go to the adjacent rank -- which a jump of up to kSlabJump layers still reaches while every slab is thicker than

@@ -17,7 +17,7 @@
 // to C.  Every fp32 expression is a multiply, then an add (-ffp-contract=off: no fma); diffuse_move / diffuse_children / diffuse_child are
 // __host__ __device__ so that sph_diffuse_step_host runs the same statements.
 #pragma once
-#include "sph_tracer.h"
+#include "sph_tracer.h"   // built on the tracer's field sample: tracer_field
 
 namespace sph {
 

@@ -246,18 +246,20 @@ struct SphEngine {
     DevBuf<SphSample> d_sampleOut;
     // the queries that walk the grid by particle id (neighbour lists, kNN): ids of the sorted slots, refilled by every run (slot_ids_fill)
     DevBuf<int32_t> d_slotIds;
-    // sph_neighbors_*: counts, tile sums / maxima / totals of the scan, and the lists themselves (CSR)
+    // the scratch of the 64-bit scan of neighbour lists, components and shell (scan_scratch_grow): dead once a scan's totals have been read
+    DevBuf<unsigned long long> d_scanTileSums;   // (the two totals lie behind the tile sums)
+    DevBuf<uint32_t> d_scanTileMax;
+    // sph_neighbors_*: counts, the offsets of their scan, and the lists themselves (CSR)
     DevBuf<int32_t> d_nbIndices;
-    DevBuf<uint32_t> d_nbCnt, d_nbTileMax;
-    DevBuf<unsigned long long> d_nbTileSums;
+    DevBuf<uint32_t> d_nbCnt;
     DevBuf<long long> d_nbOffsets;
     SphNeighborInfo nbInfo{};               // kind 0: no lists
     bool nbIndexed = false;                 // d_nbIndices holds nbInfo.total entries
     // sph_components_*: per sorted slot the particle id, the union-find parent and the tree's smallest id; per particle id labels, roots and the
-    // root flags with their scan (offsets, tile sums / maxima); the table; the words of the launches (changed / more) and the table's reduction
+    // root flags with their scan (offsets); the table; the words of the launches (changed / more) and the table's reduction
     DevBuf<int32_t> d_ccIds, d_ccLabels, d_ccRoots;
-    DevBuf<uint32_t> d_ccParent, d_ccMinId, d_ccFlag, d_ccTileMax, d_ccWords;
-    DevBuf<unsigned long long> d_ccTileSums, d_ccStats;
+    DevBuf<uint32_t> d_ccParent, d_ccMinId, d_ccFlag, d_ccWords;
+    DevBuf<unsigned long long> d_ccStats;
     DevBuf<long long> d_ccOffsets;
     DevBuf<sph::CcRow> d_ccTable;
     SphComponentInfo ccInfo{};
@@ -279,12 +281,12 @@ struct SphEngine {
     bool raysValid = false;
     int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
     // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
-    // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets, tile sums / maxima); the two words of the reduction
+    // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets); the two words of the reduction
     DevBuf<sph::ShellRow> d_shRows;
     DevBuf<int32_t> d_shIds, d_shSlots;
     DevBuf<float4> d_shNrm;
-    DevBuf<uint32_t> d_shFlagRow, d_shFlagSlot, d_shTileMax;
-    DevBuf<unsigned long long> d_shTileSums, d_shStats;
+    DevBuf<uint32_t> d_shFlagRow, d_shFlagSlot;
+    DevBuf<unsigned long long> d_shStats;
     DevBuf<long long> d_shOffsets;
     SphShellInfo shellInfo{};               // kind 0: no rows
     int optShellTimed = 0;                  // SPH_OPT_SHELL_TIMED: which launches of a build the timing bracket covers (0 all, 1 pass 1, 2 pass 2, 3 scans and compactions)
@@ -496,13 +498,14 @@ void free_grid_buffers(SphEngine* e) {
 // One free function per feature (callers have drained the stream, or the function does): sph_destroy calls each.
 void sample_free(SphEngine* e) { e->d_sampleIn.release(); e->d_sampleOut.release(); }
 void neighbors_free(SphEngine* e) {
-    e->d_slotIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbTileMax.release(); e->d_nbTileSums.release(); e->d_nbOffsets.release();
+    e->d_slotIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbOffsets.release();
+    e->d_scanTileSums.release(); e->d_scanTileMax.release();        // (the scan scratch of components and shell too: the three are freed together)
     e->nbInfo = SphNeighborInfo{};
     e->nbIndexed = false;
 }
 void components_free(SphEngine* e) {
     e->d_ccIds.release(); e->d_ccLabels.release(); e->d_ccRoots.release(); e->d_ccParent.release(); e->d_ccMinId.release(); e->d_ccFlag.release();
-    e->d_ccTileMax.release(); e->d_ccWords.release(); e->d_ccTileSums.release(); e->d_ccStats.release(); e->d_ccOffsets.release(); e->d_ccTable.release();
+    e->d_ccWords.release(); e->d_ccStats.release(); e->d_ccOffsets.release(); e->d_ccTable.release();
     e->ccInfo = SphComponentInfo{};
     e->ccValid = false;
 }
@@ -512,7 +515,7 @@ void knn_free(SphEngine* e) {
 }
 void shell_free(SphEngine* e) {
     e->d_shRows.release(); e->d_shIds.release(); e->d_shSlots.release(); e->d_shNrm.release(); e->d_shFlagRow.release(); e->d_shFlagSlot.release();
-    e->d_shTileMax.release(); e->d_shTileSums.release(); e->d_shStats.release(); e->d_shOffsets.release();
+    e->d_shStats.release(); e->d_shOffsets.release();
     e->shellInfo = SphShellInfo{};
 }
 void rays_free(SphEngine* e) {
@@ -865,12 +868,10 @@ float scalars_step_loop(const SimK& k, float kLap, float dt, const sph::ScalarCo
     for (size_t q = 0; q < n; ++q) {
         const float* X = &pv[4 * q];
         const float* ci = &sC[q * (K + 1)];
-        if (!(ci[K] > 0.0f) || !sph::scalar_finite(X[0]) || !sph::scalar_finite(X[1]) || !sph::scalar_finite(X[2]) || !(X[3] > 0.0f)) continue;
+        if (!(ci[K] > 0.0f) || !sph::float_finite(X[0]) || !sph::float_finite(X[1]) || !sph::float_finite(X[2]) || !(X[3] > 0.0f)) continue;
         float a[K], W = 0.0f;
         for (int c = 0; c < K; ++c) a[c] = 0.0f;
-        int cx, cy, cz;
-        grid.cell(X, cx, cy, cz);
-        grid.rows(1, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        grid.rows(1, X, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe; ++j) {
                 if (j == q) continue;
                 const float* Y = &pv[4 * (size_t)j];
@@ -2836,24 +2837,30 @@ static void slot_ids_fill(SphEngine* e) {
     Timed t(e, SPH_K_OTHER);
     hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(e->n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, e->d_slotIds.p, e->idBase, (uint32_t)e->n);
 }
-// The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0: tileSums holds blocks_for(rows, kScanTile) + 2 words
-// (the totals, sum and largest count, lie behind the tile sums), tileMax one per tile.  One synchronisation: hostTotals[0 .. 2).
-// scan_counts64_launch: the three launches alone (no bracket, no synchronisation); the totals lie at tileSums + tiles.
-static unsigned long long* scan_counts64_launch(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets) {
+// The scratch of scan_counts64 for `rows` counts, one pair for every family: blocks_for(rows, kScanTile) + 2 words of tile sums (the
+// totals, sum and largest count, lie behind them) and one maximum per tile.  Dead once a scan's totals have been read.
+static int scan_scratch_grow(SphEngine* e, size_t rows) {
+    const size_t tiles = (size_t)blocks_for(rows, kScanTile);
+    const int rc = e->d_scanTileSums.grow(e, tiles + 2);
+    return rc ? rc : e->d_scanTileMax.grow(e, tiles);
+}
+// The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0 (scan_scratch_grow first).  One synchronisation: hostTotals[0 .. 2).
+// scan_counts64_launch: the three launches alone (no bracket, no synchronisation); returns where the totals lie on the device.
+static unsigned long long* scan_counts64_launch(SphEngine* e, const uint32_t* cnt, size_t rows, long long* offsets) {
     const int tiles = blocks_for(rows, kScanTile);
-    unsigned long long* totals = tileSums + tiles;
+    unsigned long long *tileSums = e->d_scanTileSums.p, *totals = tileSums + tiles;
+    uint32_t* tileMax = e->d_scanTileMax.p;
     hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
     hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
     hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
                        (const unsigned long long*)totals, offsets);
     return totals;
 }
-static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, unsigned long long* tileSums, uint32_t* tileMax, long long* offsets,
-                         unsigned long long hostTotals[2]) {
+static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, long long* offsets, unsigned long long hostTotals[2]) {
     unsigned long long* totals;
     {
         Timed t(e, SPH_K_OTHER);
-        totals = scan_counts64_launch(e, cnt, rows, tileSums, tileMax, offsets);
+        totals = scan_counts64_launch(e, cnt, rows, offsets);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hostTotals, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -2949,28 +2956,29 @@ static int neighbors_run(SphEngine* e, const float4* devPoints, size_t m, float 
     int rc, stencil = 0;
     if ((rc = query_grid(e, g)) || (rc = neighbors_check(radius, g.cellSize, flags, query, &stencil))) return rc;
     const size_t n = e->n, rows = query ? m : n;
-    const int tiles = blocks_for(rows, kScanTile);
     e->nbInfo = SphNeighborInfo{};                                                  // (the lists held so far end here)
     e->nbIndexed = false;
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_nbCnt.grow(e, rows)) || (rc = e->d_nbOffsets.grow(e, rows + 1)) ||
-        (rc = e->d_nbTileSums.grow(e, (size_t)tiles + 2)) || (rc = e->d_nbTileMax.grow(e, (size_t)tiles))) return rc;
+        (rc = scan_scratch_grow(e, rows))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
     const NbK nb = make_nbk(e, radius, stencil, flags);
     const dim3 grid(blocks_for(rows)), block(kBlock);
+    using Count = void (*)(SimK, NbK, const float4*, const uint32_t*, const int32_t*, const float4*, size_t, uint32_t*);
+    using Fill = void (*)(SimK, NbK, const float4*, const uint32_t*, const int32_t*, const float4*, size_t, const long long*, int32_t*);
     auto walk = [&](bool fill) {
         Timed t(e, SPH_K_OTHER);
-        if (query && fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (fill && e->optNbFill) hipLaunchKernelGGL((k_neighbors_fill_wave<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (query && fill) hipLaunchKernelGGL((k_neighbors_fill<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else if (query) hipLaunchKernelGGL((k_neighbors_count<false>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, e->d_nbCnt.p);
-        else if (fill) hipLaunchKernelGGL((k_neighbors_fill<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
-        else hipLaunchKernelGGL((k_neighbors_count<true>), grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, e->d_nbCnt.p);
+        auto go = [&](auto kernel, auto... own) {                                   // the arguments every walk shares, then the kernel's own
+            hipLaunchKernelGGL(kernel, grid, block, 0, e->stream, k, nb, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const int32_t*)e->d_slotIds.p, devPoints, rows, own...);
+        };
+        if (!fill) return go(query ? (Count)k_neighbors_count<false> : (Count)k_neighbors_count<true>, e->d_nbCnt.p);
+        const Fill plain = query ? (Fill)k_neighbors_fill<false> : (Fill)k_neighbors_fill<true>, wave = query ? (Fill)k_neighbors_fill_wave<false> : (Fill)k_neighbors_fill_wave<true>;
+        go(e->optNbFill ? wave : plain, (const long long*)e->d_nbOffsets.p, e->d_nbIndices.p);
     };
     unsigned long long host[2] = {0ull, 0ull};
     if (rows) {
         slot_ids_fill(e);
         walk(false);                                                                // (writes cnt[row] of every row)
-        if ((rc = scan_counts64(e, e->d_nbCnt.p, rows, e->d_nbTileSums.p, e->d_nbTileMax.p, e->d_nbOffsets.p, host))) return rc;
+        if ((rc = scan_counts64(e, e->d_nbCnt.p, rows, e->d_nbOffsets.p, host))) return rc;
     } else {
         HIP_TRY(hipMemsetAsync(e->d_nbOffsets.p, 0, sizeof(long long), e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3059,10 +3067,8 @@ int sph_neighbors_host(const SphParticle* particles, size_t n, const SphParams* 
     // f(id) per kept entry of row r, in order
     auto walk = [&](size_t r, auto&& f) {
         const float* x = query ? points4 + 4 * r : particles[r].pos;
-        if (query && !(sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2]))) return;
-        int cx, cy, cz;
-        grid.cell(x, cx, cy, cz);
-        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        if (query && !(sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2]))) return;
+        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe; ++j) {
                 const float* y = particles[order[j]].pos;
                 const bool acc = sph::neighbor_accept(x[0], x[1], x[2], y[0], y[1], y[2], R2);
@@ -3114,12 +3120,11 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
     int rc, stencil = 0;
     if ((rc = query_grid(e, g)) || (rc = components_check(radius, g.cellSize, flags, &stencil))) return rc;
     const size_t n = e->n;
-    const int tiles = blocks_for(n, kScanTile);
     e->ccInfo = SphComponentInfo{};                                                 // (the result held so far ends here)
     e->ccValid = false;
     if ((rc = e->d_ccIds.grow(e, n)) || (rc = e->d_ccLabels.grow(e, n)) || (rc = e->d_ccRoots.grow(e, n)) || (rc = e->d_ccParent.grow(e, n)) ||
-        (rc = e->d_ccMinId.grow(e, n)) || (rc = e->d_ccFlag.grow(e, n)) || (rc = e->d_ccOffsets.grow(e, n + 1)) || (rc = e->d_ccTileSums.grow(e, (size_t)tiles + 2)) ||
-        (rc = e->d_ccTileMax.grow(e, (size_t)tiles)) || (rc = e->d_ccWords.grow(e, (size_t)kCcWords)) || (rc = e->d_ccStats.grow(e, 3))) return rc;
+        (rc = e->d_ccMinId.grow(e, n)) || (rc = e->d_ccFlag.grow(e, n)) || (rc = e->d_ccOffsets.grow(e, n + 1)) || (rc = scan_scratch_grow(e, n)) ||
+        (rc = e->d_ccWords.grow(e, (size_t)kCcWords)) || (rc = e->d_ccStats.grow(e, 3))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
     SphComponentInfo info{};
     info.rows = n; info.radius = radius; info.stencil = stencil; info.flags = flags;
@@ -3180,7 +3185,7 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
             hipLaunchKernelGGL(k_components_roots, grid, block, 0, e->stream, ids, (const uint32_t*)parent, (const uint32_t*)e->d_ccMinId.p, e->d_ccRoots.p, e->d_ccFlag.p, (uint32_t)n);
         }
         unsigned long long host[2] = {0ull, 0ull};
-        if ((rc = scan_counts64(e, e->d_ccFlag.p, n, e->d_ccTileSums.p, e->d_ccTileMax.p, e->d_ccOffsets.p, host))) return rc;
+        if ((rc = scan_counts64(e, e->d_ccFlag.p, n, e->d_ccOffsets.p, host))) return rc;
         C = host[0];
         if (C > n) return fail(SPH_ERR_STATE, "components: %llu bodies of %zu records", (unsigned long long)C, n);
         if ((rc = e->d_ccTable.grow(e, (size_t)C))) return rc;
@@ -3275,9 +3280,7 @@ int sph_components_host(const SphParticle* particles, size_t n, const SphParams*
     for (size_t i = 0; i < n; ++i) {
         if (!takesPart(i)) continue;
         const float* x = particles[i].pos;
-        int cx, cy, cz;
-        grid.cell(x, cx, cy, cz);
-        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe && j < slotOf[i]; ++j) {                   // an edge is seen from its larger slot
                 const uint32_t o = order[j];
                 const float* y = particles[o].pos;
@@ -3464,11 +3467,9 @@ int sph_knn_host(const SphParticle* particles, size_t n, const SphParams* params
     for (size_t r = 0; r < rows; ++r) {
         const float* x = query ? points4 + 4 * r : particles[r].pos;
         keys.clear();
-        const bool walk = query ? (sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+        const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
         if (walk) {
-            int cx, cy, cz;
-            grid.cell(x, cx, cy, cz);
-            grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
                 for (uint32_t j = qs; j < qe; ++j) {
                     if (!query && !self && j == slotOf[r]) continue;
                     const uint32_t o = order[j];
@@ -3527,10 +3528,10 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
     int rc, stencil = 0;
     float radius = 0.0f;
     if ((rc = query_grid(e, g)) || (rc = shell_check(cfg, e->params.param_h, g.cellSize, &radius, &stencil))) return rc;
-    const size_t n = e->n, rows = query ? m : n, tiles = (size_t)blocks_for(rows, kScanTile);
+    const size_t n = e->n, rows = query ? m : n;
     e->shellInfo = SphShellInfo{};                                                  // (the rows held so far end here)
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_shRows.grow(e, rows)) || (rc = e->d_shIds.grow(e, rows)) || (rc = e->d_shFlagRow.grow(e, rows)) ||
-        (rc = e->d_shOffsets.grow(e, rows + 1)) || (rc = e->d_shTileSums.grow(e, tiles + 2)) || (rc = e->d_shTileMax.grow(e, tiles)) ||
+        (rc = e->d_shOffsets.grow(e, rows + 1)) || (rc = scan_scratch_grow(e, rows)) ||
         (rc = e->d_shStats.grow(e, 2))) return rc;
     if (!query && ((rc = e->d_shNrm.grow(e, n)) || (rc = e->d_shFlagSlot.grow(e, n)) || (rc = e->d_shSlots.grow(e, n)))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
@@ -3553,7 +3554,7 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
         else hipLaunchKernelGGL((k_shell_gather<true>), grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn,
                                 devPoints, rows, e->d_shRows.p, e->d_shFlagRow.p, e->d_shNrm.p, e->d_shFlagSlot.p, e->d_shStats.p);
         bracket(3);                                                                 // ids[]: the flags by row, scanned and compacted
-        unsigned long long* devTotals = scan_counts64_launch(e, e->d_shFlagRow.p, rows, e->d_shTileSums.p, e->d_shTileMax.p, e->d_shOffsets.p);
+        unsigned long long* devTotals = scan_counts64_launch(e, e->d_shFlagRow.p, rows, e->d_shOffsets.p);
         hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagRow.p, (const long long*)e->d_shOffsets.p, rows, e->d_shIds.p);
         t.reset();
         HIP_TRY(hipGetLastError());
@@ -3564,7 +3565,7 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
         if (numShell > rows) return fail(SPH_ERR_STATE, "shell: %zu shell rows of %zu", numShell, rows);
         if (!query && numShell) {                                                   // the same scan by slot: pass 2's targets in ascending slot order
             bracket(3);
-            (void)scan_counts64_launch(e, e->d_shFlagSlot.p, n, e->d_shTileSums.p, e->d_shTileMax.p, e->d_shOffsets.p);
+            (void)scan_counts64_launch(e, e->d_shFlagSlot.p, n, e->d_shOffsets.p);
             hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagSlot.p, (const long long*)e->d_shOffsets.p, n, e->d_shSlots.p);
             bracket(2);
             hipLaunchKernelGGL(k_shell_crest, dim3(blocks_for(numShell)), block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p,
@@ -3647,14 +3648,12 @@ int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* para
         const float* x = query ? points4 + 4 * r : particles[r].pos;
         sph::shell_zero(res[r]);
         if (sums4) sums4[4 * r] = sums4[4 * r + 1] = sums4[4 * r + 2] = sums4[4 * r + 3] = 0.0f;
-        bool walk = sph::scalar_finite(x[0]) && sph::scalar_finite(x[1]) && sph::scalar_finite(x[2]);
+        bool walk = sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2]);
         if (!query && fluidOnly && particles[r].isGhost != 0) walk = false;
         if (!walk) continue;
         sph::ShellAcc a;
         sph::shell_reset(a);
-        int cx, cy, cz;
-        grid.cell(x, cx, cy, cz);
-        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe; ++j) {
                 if (!query && j == slotOf[r]) continue;
                 const uint32_t o = order[j];
@@ -3675,9 +3674,7 @@ int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* para
         const float* x = particles[r].pos;
         const float* nrm = res[r].normal;
         long long crest = 0ll;
-        int cx, cy, cz;
-        grid.cell(x, cx, cy, cz);
-        grid.rows(stencil, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe; ++j) {
                 const uint32_t o = order[j];
                 if (!(res[o].flags & sph::kShellMember) || j == slotOf[r]) continue;

@@ -16,6 +16,7 @@
 //   rp[s]  = (density, pressure)    foam[s] = padA           acc[s] = (ax, ay, az, 0)
 #pragma once
 #include "sph_device.h"
+#include "sph_wave.h"   // wave_incl_scan, block_excl_scan, wave_max
 
 namespace sph {
 
@@ -86,30 +87,6 @@ __global__ __launch_bounds__(kBlock) void k_bin(SimK k, const float4* __restrict
     if (head && valid) base = atomicAdd(&cellCount[cell], (uint32_t)(endLane - lane));
     base = (uint32_t)__shfl((int)base, startLane, 64);
     if (inRange) binKey[i] = make_uint2(cell, base + (uint32_t)(lane - startLane));
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread (256 threads = 4 waves); returns the
-// exclusive prefix and, through total, the block sum.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sm, uint32_t& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = wave_incl_scan(v);
-    if (lane == 63) sm[w] = inc;
-    __syncthreads();
-    uint32_t w0 = sm[0], w1 = sm[1], w2 = sm[2], w3 = sm[3];
-    uint32_t base = (w > 0 ? w0 : 0u) + (w > 1 ? w1 : 0u) + (w > 2 ? w2 : 0u);
-    total = w0 + w1 + w2 + w3;
-    __syncthreads();
-    return base + inc - v;
 }
 
 // Each thread owns kScanItems CONSECUTIVE cells (16-byte loads), so a tile of 256 x kScanItems cells needs one block-wide scan.
@@ -242,8 +219,7 @@ __global__ __launch_bounds__(kBlock) void k_rank(const uint2* __restrict__ tmp, 
     // straddles the wave's edge, a crowded cell of compressed fluid) are gathered from memory.
     const uint32_t d0 = (uint32_t)d - (uint32_t)(threadIdx.x & 63);                // slot of lane 0
     const uint32_t m = e - s;
-    uint32_t mWave = m;
-    for (int sh = 32; sh >= 1; sh >>= 1) mWave = max(mWave, (uint32_t)__shfl_xor((int)mWave, sh, 64));
+    const uint32_t mWave = wave_max(m);
     if (mWave > 1u) {                                                              // wave-uniform
         if (mWave <= 64u) {
             for (uint32_t j = 0; j < mWave; ++j) {                                 // wave-uniform trip count: the shuffle needs every lane

@@ -1,9 +1,9 @@
 // sph_knn.h -- the k nearest neighbours within a radius, of the particles or of query points (no reference counterpart; DESIGN.md
 // section 3m).
 //
-// Grid, radius rules, stencil and candidates are those of sph_neighbors.h (neighbor_stencil, neighbor_rows, neighbor_target).  A
-// candidate j is accepted when r2 < R2, r2 = knn_r2 (the arithmetic of neighbor_accept), and gets the key (bits(r2) << 32) | id_j:
-// r2 is a sum of squares, >= +0 and never -0, so keys compared as uint64 order by ascending r2, ties to the smaller particle id.  The
+// Grid, radius rules, stencil, candidates and the target of a lane are those of sph_query.h (neighbor_stencil, neighbor_rows,
+// query_target).  A candidate j is accepted when r2 < R2, r2 = knn_r2 (the arithmetic of neighbor_accept), and gets the key
+// (bits(r2) << 32) | id_j: r2 is a sum of squares, >= +0 and never -0, so keys compared as uint64 order by ascending r2, ties to the smaller particle id.  The
 // row of a target is its min(k, accepted) smallest keys, ascending: one answer whatever the order in which the candidates are met.
 // Flags differ from the neighbour lists': without SPH_KNN_SELF the target's own slot is left out by slot identity; WITH it the own
 // slot is an ordinary candidate (r2 = 0, ordered by id among coincident particles), so a target with a NaN position keeps an empty
@@ -28,7 +28,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "sph_neighbors.h"
+#include "sph_query.h"
 
 namespace sph {
 
@@ -39,7 +39,7 @@ constexpr unsigned long long kKnnNoKey = ~0ull;     // above every key: the high
 // The squared distance of neighbor_accept, returned: dot3 of sph_device.h; NaN on either side gives NaN (accepted by no radius).
 __host__ __device__ inline float knn_r2(float xi, float yi, float zi, float xj, float yj, float zj) {
     const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+    return dot3(dx, dy, dz, dx, dy, dz);
 }
 __host__ __device__ inline uint32_t knn_bits(float r2) {
     uint32_t u;
@@ -61,9 +61,9 @@ constexpr int knn_threads(int kcap) { return kcap <= 16 ? 256 : kcap == 32 ? 128
 template <bool PARTICLES, class F>
 __device__ __forceinline__ void knn_walk(const SimK& k, const NbK& nb, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
                                          float px, float py, float pz, uint32_t q, F&& f) {
-    const int cx = cell_axis(px, k.gminx, k.cellSize, k.gx), cy = cell_axis(py, k.gminy, k.cellSize, k.gy), cz = cell_axis(pz, k.gminz, k.cellSize, k.gz);
+    const int3 cell = cell_of(k, px, py, pz);
     const bool skipOwn = PARTICLES && !(nb.flags & kKnnSelf);
-    neighbor_rows(k, cellStart, nb.s, nb.n, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
         for (uint32_t j = qs; j < qe; ++j) {
             if (skipOwn && j == q) continue;
             const float4 J = pv[2u * j];
@@ -73,24 +73,17 @@ __device__ __forceinline__ void knn_walk(const SimK& k, const NbK& nb, const flo
     });
 }
 
-// Is the record of sorted slot j a ghost (isGhost != 0)?  One word of its own data.
-__device__ __forceinline__ bool knn_ghost(const float4* __restrict__ own, uint32_t j) {
-    return (fbits(reinterpret_cast<const float*>(own)[(size_t)j * 4u + 2u]) & F_GHOSTNZ) != 0u;
-}
-
-// Target of a lane (neighbor_target) and whether it walks: a ghost's particle row is empty under FLUID_ONLY.
+// Target of a lane (query_target) and whether it walks: a ghost's particle row is empty under FLUID_ONLY.
 template <bool PARTICLES>
 __device__ __forceinline__ bool knn_target(const NbK& nb, const float4* __restrict__ pv, const int32_t* __restrict__ ids, const float4* __restrict__ own,
                                            const float4* __restrict__ points, size_t rows, size_t i, float4& P, size_t& row, bool& walk) {
-    if (!neighbor_target<PARTICLES>(nb, pv, ids, points, rows, i, P, row, walk)) return false;
-    if (PARTICLES && walk && (nb.flags & kKnnFluidOnly)) walk = !knn_ghost(own, (uint32_t)i);
+    if (!query_target<PARTICLES>(pv, ids, points, rows, i, P, row, walk)) return false;
+    if (PARTICLES && walk && (nb.flags & kKnnFluidOnly)) walk = !slot_ghost(own, (uint32_t)i);
     return true;
 }
-
 // (sum of counts, full rows) of the wave into stats[0], stats[1]: every lane of the wave must arrive.
 __device__ __forceinline__ void knn_reduce(uint32_t cnt, bool full, unsigned long long* __restrict__ stats) {
-    uint32_t s = cnt;
-    for (int sh = 32; sh >= 1; sh >>= 1) s += (uint32_t)__shfl_xor((int)s, sh, 64);
+    const uint32_t s = wave_sum(cnt);
     const unsigned long long nf = (unsigned long long)__popcll(__ballot(full));
     if ((threadIdx.x & 63) == 0) {
         if (s) atomicAdd(stats + 0, (unsigned long long)s);
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(knn_threads(KCAP)) void k_knn(SimK k, NbK nb, int k
     if (act && walk) {
         knn_walk<PARTICLES>(k, nb, pv, cellStart, P.x, P.y, P.z, (uint32_t)i, [&](uint32_t j, float r2) {
             if (knn_bits(r2) > (uint32_t)(worst >> 32)) return;                 // a full row: the one further compare
-            if (fluidOnly && knn_ghost(own, j)) return;
+            if (fluidOnly && slot_ghost(own, j)) return;
             const unsigned long long key = knn_key(r2, (uint32_t)ids[j]);
             if (key >= worst) return;                                           // (equal r2 bits, a larger id)
             if (cnt == K) {                                                     // a full row drops its worst: the root
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void k_knn_select(SimK k, NbK nb, int kk, c
             unsigned long long found = kKnnNoKey;
             if (walk) {
                 knn_walk<PARTICLES>(k, nb, pv, cellStart, P.x, P.y, P.z, (uint32_t)i, [&](uint32_t j, float r2) {
-                    if (fluidOnly && knn_ghost(own, j)) return;
+                    if (fluidOnly && slot_ghost(own, j)) return;
                     const unsigned long long key = knn_key(r2, (uint32_t)ids[j]);
                     if ((cnt == 0 || key > last) && key < found) found = key;
                 });

@@ -4,7 +4,7 @@
 // non-ghost particle with finite coordinates meets bodies 0..K-1 in order; one strictly inside is projected onto the surface and, if it
 // moves into the surface relative to the surface velocity, gets the body's wall response.  The per-particle arithmetic (obs_hit) and the
 // pose advance (obs_advance) are __host__ __device__: sph_obstacles_apply_host / _advance_host run the same functions on the CPU.
-// -ffp-contract=off: the only fused operations are the explicit fmaf() of obs_dot3.
+// -ffp-contract=off: the only fused operations are the explicit fmaf() of dot3 (sph_device.h).
 //
 //   k_obstacles         sweeps over the output slots with a FIXED grid (min(kObsGrid, sweeps for n)): a world-AABB cull per body and
 //                       wave, the hit, and per wave an xor butterfly of the six fp64 terms that lane 0 adds to its wave's LDS row; one
@@ -22,7 +22,7 @@
 #include <string.h>
 
 #include "sph_kernels.h"
-#include "sph_volume.h"
+#include "sph_volume.h"   // built on it: a body may be bound to a volume (k_obstacles_vol)
 
 namespace sph {
 
@@ -60,11 +60,6 @@ struct ObsAcc {
     double time;                             // fp64 sum of dt
     unsigned long long substeps;
 };
-
-__host__ __device__ inline float obs_dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-__host__ __device__ inline bool obs_finite(float f) { return float_finite(f); }
 
 // q / |q|, |q| = sqrtf(fmaf(z, z, fmaf(y, y, fmaf(x, x, w * w)))), four IEEE divisions.
 __host__ __device__ inline void obs_normalize(float (&q)[4]) {
@@ -122,16 +117,16 @@ __host__ __device__ inline bool obs_hit_t(const ObsRec& b, const VolRec* vol, fl
     float nx, ny, nz, qx, qy, qz;                                    // world normal, projected world point
     if (b.shape == OBS_SPHERE) {
         const float R = b.size[0];
-        const float r2 = obs_dot3(dx, dy, dz, dx, dy, dz);
+        const float r2 = dot3(dx, dy, dz, dx, dy, dz);
         if (!(r2 < R * R)) return false;
         const float len = sqrtf(r2);
         if (len == 0.0f) { nx = M[1]; ny = M[4]; nz = M[7]; }       // the exact centre: local +y
         else { nx = dx / len; ny = dy / len; nz = dz / len; }
         qx = b.c[0] + R * nx; qy = b.c[1] + R * ny; qz = b.c[2] + R * nz;
     } else {
-        const float lx = obs_dot3(dx, dy, dz, M[0], M[3], M[6]);      // l = M^T (p - c)
-        const float ly = obs_dot3(dx, dy, dz, M[1], M[4], M[7]);
-        const float lz = obs_dot3(dx, dy, dz, M[2], M[5], M[8]);
+        const float lx = dot3(dx, dy, dz, M[0], M[3], M[6]);      // l = M^T (p - c)
+        const float ly = dot3(dx, dy, dz, M[1], M[4], M[7]);
+        const float lz = dot3(dx, dy, dz, M[2], M[5], M[8]);
         float ox, oy, oz, mx, my, mz;                                // local projected point, local normal
         if (b.shape == OBS_BOX) {
             const float hx = b.size[0], hy = b.size[1], hz = b.size[2];
@@ -151,26 +146,26 @@ __host__ __device__ inline bool obs_hit_t(const ObsRec& b, const VolRec* vol, fl
             const float r = b.size[0], L = b.size[1];
             const float sy = fminf(fmaxf(ly, -L), L);
             const float ex = lx, ey = ly - sy, ez = lz;
-            const float e2 = obs_dot3(ex, ey, ez, ex, ey, ez);
+            const float e2 = dot3(ex, ey, ez, ex, ey, ez);
             if (!(e2 < r * r)) return false;
             const float len = sqrtf(e2);
             if (len == 0.0f) { mx = 1.0f; my = 0.0f; mz = 0.0f; }   // on the core segment: local +x
             else { mx = ex / len; my = ey / len; mz = ez / len; }
             ox = r * mx; oy = sy + r * my; oz = r * mz;
         }
-        nx = obs_dot3(M[0], M[1], M[2], mx, my, mz);
-        ny = obs_dot3(M[3], M[4], M[5], mx, my, mz);
-        nz = obs_dot3(M[6], M[7], M[8], mx, my, mz);
-        qx = b.c[0] + obs_dot3(M[0], M[1], M[2], ox, oy, oz);
-        qy = b.c[1] + obs_dot3(M[3], M[4], M[5], ox, oy, oz);
-        qz = b.c[2] + obs_dot3(M[6], M[7], M[8], ox, oy, oz);
+        nx = dot3(M[0], M[1], M[2], mx, my, mz);
+        ny = dot3(M[3], M[4], M[5], mx, my, mz);
+        nz = dot3(M[6], M[7], M[8], mx, my, mz);
+        qx = b.c[0] + dot3(M[0], M[1], M[2], ox, oy, oz);
+        qy = b.c[1] + dot3(M[3], M[4], M[5], ox, oy, oz);
+        qz = b.c[2] + dot3(M[6], M[7], M[8], ox, oy, oz);
     }
     const float rx = qx - b.c[0], ry = qy - b.c[1], rz = qz - b.c[2];
     const float sx = b.v[0] + (b.w[1] * rz - b.w[2] * ry);           // surface velocity V + omega x r
     const float sy = b.v[1] + (b.w[2] * rx - b.w[0] * rz);
     const float sz = b.v[2] + (b.w[0] * ry - b.w[1] * rx);
     const float ux = vx - sx, uy = vy - sy, uz = vz - sz;
-    const float un = obs_dot3(ux, uy, uz, nx, ny, nz);
+    const float un = dot3(ux, uy, uz, nx, ny, nz);
     px = qx; py = qy; pz = qz;
     for (int i = 0; i < kObsTerms; ++i) t[i] = 0.0;
     if (un < 0.0f) {
@@ -222,7 +217,7 @@ __device__ __forceinline__ void obs_slot(const ObsRec* __restrict__ bodies, cons
         }
 #pragma unroll
         for (int c = 0; c < kObsTerms; ++c)
-            for (int o = 32; o >= 1; o >>= 1) t[c] += __shfl_xor(t[c], o, 64);
+            for (int o = 32; o >= 1; o >>= 1) t[c] += __shfl_xor(t[c], o, 64);   // (open-coded: wave_sum per term reorders the independent chains; profiles/r20_header_refactor_ab.json)
         if (lane == 0)
             for (int c = 0; c < kObsTerms; ++c) row[b * kObsTerms + c] += t[c];
     }
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles(const ObsRec* __restric
 #pragma unroll
         for (int j = 0; j < kObsUnroll; ++j) {
             const int s = base + j * kObsBlock + threadIdx.x;
-            const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && obs_finite(P[j].x) && obs_finite(P[j].y) && obs_finite(P[j].z);
+            const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && float_finite(P[j].x) && float_finite(P[j].y) && float_finite(P[j].z);
             obs_slot<false>(bodies, nullptr, K, mass, pos, vel, s, P[j], cand, sacc[wave], lane);
         }
     }
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles_vol(const ObsRec* __res
 #pragma unroll
         for (int j = 0; j < kObsUnroll; ++j) {
             const int s = base + j * kObsBlock + threadIdx.x;
-            const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && obs_finite(P[j].x) && obs_finite(P[j].y) && obs_finite(P[j].z);
+            const bool cand = s < n && !(fbits(P[j].w) & (F_GHOSTNZ | F_HALO)) && float_finite(P[j].x) && float_finite(P[j].y) && float_finite(P[j].z);
             obs_slot<true>(bodies, tab, K, mass, pos, vel, s, P[j], cand, sacc[wave], lane);
         }
     }
@@ -341,7 +336,7 @@ __global__ __launch_bounds__(kObsBlock) void k_obstacles_vol(const ObsRec* __res
 // A body with a dynamics record moves under the substep's own sums (J, L): k_obstacles_finish_dyn is launched instead of
 // k_obstacles_finish while at least one body has a record (k_obstacles_finish itself stays what it is for kinematic sets).  The body step
 // (obs_body_step) is __host__ __device__ and is what sph_obstacles_step_host runs.  fp32, every operation rounded on its own except
-// obs_dot3; the J and L terms are fp64.
+// dot3; the J and L terms are fp64.
 struct ObsDyn {                              // 128 bytes, one per body, beside ObsRec
     int32_t active;                          // 0: kinematic
     float mass;
@@ -366,17 +361,17 @@ struct ObsWorld {
     float rest;
 };
 
-// M (S (M^T x)) for a symmetric S = (xx, yy, zz, xy, xz, yz) in the body frame: three rows of obs_dot3 each.
+// M (S (M^T x)) for a symmetric S = (xx, yy, zz, xy, xz, yz) in the body frame: three rows of dot3 each.
 __host__ __device__ inline void obs_sym_world(const float* M, const float* S, const float (&x)[3], float (&out)[3]) {
-    const float l0 = obs_dot3(x[0], x[1], x[2], M[0], M[3], M[6]);
-    const float l1 = obs_dot3(x[0], x[1], x[2], M[1], M[4], M[7]);
-    const float l2 = obs_dot3(x[0], x[1], x[2], M[2], M[5], M[8]);
-    const float s0 = obs_dot3(S[0], S[3], S[4], l0, l1, l2);
-    const float s1 = obs_dot3(S[3], S[1], S[5], l0, l1, l2);
-    const float s2 = obs_dot3(S[4], S[5], S[2], l0, l1, l2);
-    out[0] = obs_dot3(M[0], M[1], M[2], s0, s1, s2);
-    out[1] = obs_dot3(M[3], M[4], M[5], s0, s1, s2);
-    out[2] = obs_dot3(M[6], M[7], M[8], s0, s1, s2);
+    const float l0 = dot3(x[0], x[1], x[2], M[0], M[3], M[6]);
+    const float l1 = dot3(x[0], x[1], x[2], M[1], M[4], M[7]);
+    const float l2 = dot3(x[0], x[1], x[2], M[2], M[5], M[8]);
+    const float s0 = dot3(S[0], S[3], S[4], l0, l1, l2);
+    const float s1 = dot3(S[3], S[1], S[5], l0, l1, l2);
+    const float s2 = dot3(S[4], S[5], S[2], l0, l1, l2);
+    out[0] = dot3(M[0], M[1], M[2], s0, s1, s2);
+    out[1] = dot3(M[3], M[4], M[5], s0, s1, s2);
+    out[2] = dot3(M[6], M[7], M[8], s0, s1, s2);
 }
 __host__ __device__ inline void obs_cross(const float (&a)[3], const float (&b)[3], float (&out)[3]) {
     out[0] = a[1] * b[2] - a[2] * b[1];
@@ -407,9 +402,9 @@ __host__ __device__ inline void obs_body_step(ObsRec& B, const ObsDyn& D, const 
     const float* M = B.M;
     // 1. to the centre of mass
     float o[3];
-    o[0] = obs_dot3(M[0], M[1], M[2], D.com[0], D.com[1], D.com[2]);
-    o[1] = obs_dot3(M[3], M[4], M[5], D.com[0], D.com[1], D.com[2]);
-    o[2] = obs_dot3(M[6], M[7], M[8], D.com[0], D.com[1], D.com[2]);
+    o[0] = dot3(M[0], M[1], M[2], D.com[0], D.com[1], D.com[2]);
+    o[1] = dot3(M[3], M[4], M[5], D.com[0], D.com[1], D.com[2]);
+    o[2] = dot3(M[6], M[7], M[8], D.com[0], D.com[1], D.com[2]);
     const double O0 = (double)o[0], O1 = (double)o[1], O2 = (double)o[2];
     float Lg[3];
     Lg[0] = (float)(S[3] - (O1 * S[2] - O2 * S[1]));
@@ -450,22 +445,22 @@ __host__ __device__ inline void obs_body_step(ObsRec& B, const ObsDyn& D, const 
             const float n[3] = {sg * W.A[3 * j], sg * W.A[3 * j + 1], sg * W.A[3 * j + 2]};
             for (int p = 0; p < np; ++p) {
                 float s[3], r[3], d[3];
-                s[0] = obs_dot3(M[0], M[1], M[2], lp[p][0], lp[p][1], lp[p][2]);
-                s[1] = obs_dot3(M[3], M[4], M[5], lp[p][0], lp[p][1], lp[p][2]);
-                s[2] = obs_dot3(M[6], M[7], M[8], lp[p][0], lp[p][1], lp[p][2]);
+                s[0] = dot3(M[0], M[1], M[2], lp[p][0], lp[p][1], lp[p][2]);
+                s[1] = dot3(M[3], M[4], M[5], lp[p][0], lp[p][1], lp[p][2]);
+                s[2] = dot3(M[6], M[7], M[8], lp[p][0], lp[p][1], lp[p][2]);
                 for (int a = 0; a < 3; ++a) { r[a] = s[a] - o[a]; d[a] = (B.c[a] + s[a]) - W.bc[a]; }
-                const float dist = W.half[j] + obs_dot3(d[0], d[1], d[2], n[0], n[1], n[2]);   // distance of the point from the face, inward
+                const float dist = W.half[j] + dot3(d[0], d[1], d[2], n[0], n[1], n[2]);   // distance of the point from the face, inward
                 const float depth = rad - dist;
                 if (!(depth >= 0.0f)) continue;                       // (touching counts: a body at rest on a face stays in contact)
                 if (depth > pen[f]) pen[f] = depth;
                 float wr[3], rn[3], k3[3], kr[3];
                 obs_cross(w, r, wr);
-                const float vn = obs_dot3(Vg[0] + wr[0], Vg[1] + wr[1], Vg[2] + wr[2], n[0], n[1], n[2]);
+                const float vn = dot3(Vg[0] + wr[0], Vg[1] + wr[1], Vg[2] + wr[2], n[0], n[1], n[2]);
                 if (!(vn < 0.0f)) continue;
                 obs_cross(r, n, rn);
                 obs_sym_world(M, D.Iinv, rn, k3);
                 obs_cross(k3, r, kr);
-                const float den = im + obs_dot3(n[0], n[1], n[2], kr[0], kr[1], kr[2]);
+                const float den = im + dot3(n[0], n[1], n[2], kr[0], kr[1], kr[2]);
                 const float jn = (-ope * vn) / den;
                 const float jm = jn * im;
                 for (int a = 0; a < 3; ++a) { Vg[a] = Vg[a] + jm * n[a]; w[a] = w[a] + jn * k3[a]; }

@@ -1,9 +1,10 @@
 // sph_pass.h -- the SPH pass (SPHFluid.comp:66-221 + fused OBBConstraints.comp) of the engine.
 //
-//   k_sph_list  (default)  one target per lane over the physically sorted copy: wave-cooperative LDS windows for the
-//               candidate scan (density + neighbour list), sweeps 2 / 3 over the listed neighbours only.
-//   k_sph_slow  one target per thread, three full candidate sweeps straight from global memory: the plain statement
-//               of the same arithmetic (A/B variant SPH_OPT_NEIGHBOR_KERNEL = 1).
+// The default pass is k_sph_walk (sph_walk.h, SPH_OPT_NEIGHBOR_KERNEL = 3); the two kernels here are its A/B variants:
+//   k_sph_list  (= 2, round 2's pass)  one target per lane over the physically sorted copy: wave-cooperative LDS windows
+//               for the candidate scan (density + neighbour list), sweeps 2 / 3 over the listed neighbours only.
+//   k_sph_slow  (= 1)  one target per thread, three full candidate sweeps straight from global memory: the plain
+//               statement of the same arithmetic.
 // Same functions (sph_device.h), same candidate order, therefore the same bits.
 #pragma once
 #include <type_traits>

@@ -49,7 +49,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "sph_knn.h"   // knn_ghost; neighbor_rows of sph_neighbors.h
+#include "sph_query.h"   // neighbor_rows, slot_ghost
 
 namespace sph {
 
@@ -72,9 +72,6 @@ __host__ __device__ inline uint32_t ray_bits(float f) {
     memcpy(&u, &f, 4);
     return u;
 }
-__host__ __device__ inline bool ray_finite(float f) { return float_finite(f); }
-// dot3 of sph_device.h for both sides.
-__host__ __device__ inline float ray_dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(az, bz, fmaf(ay, by, ax * bx)); }
 // float bits -> unsigned order (negative t below positive t), and back.
 __host__ __device__ inline uint32_t ray_ordered(float f) {
     const uint32_t u = ray_bits(f);
@@ -94,10 +91,10 @@ __host__ __device__ inline bool ray_setup(const float* a8, Ray& R) {
     R.ox = a8[0]; R.oy = a8[1]; R.oz = a8[2]; R.tmin = a8[3];
     R.dx = a8[4]; R.dy = a8[5]; R.dz = a8[6]; R.tmax = a8[7];
     R.inva = 0.0f;
-    if (!(ray_finite(R.ox) && ray_finite(R.oy) && ray_finite(R.oz) && ray_finite(R.dx) && ray_finite(R.dy) && ray_finite(R.dz) && ray_finite(R.tmin))) return false;
+    if (!(float_finite(R.ox) && float_finite(R.oy) && float_finite(R.oz) && float_finite(R.dx) && float_finite(R.dy) && float_finite(R.dz) && float_finite(R.tmin))) return false;
     if (R.tmax != R.tmax) return false;
-    const float a = ray_dot3(R.dx, R.dy, R.dz, R.dx, R.dy, R.dz);
-    if (!(a > 0.0f) || !ray_finite(a)) return false;
+    const float a = dot3(R.dx, R.dy, R.dz, R.dx, R.dy, R.dz);
+    if (!(a > 0.0f) || !float_finite(a)) return false;
     if (R.tmin > R.tmax) return false;
     R.inva = 1.0f / a;
     return true;
@@ -108,9 +105,9 @@ __host__ __device__ inline bool ray_setup(const float* a8, Ray& R) {
 // sphere that contains the ray's start has t < tmin and is not hit.  A NaN anywhere fails the compares.
 __host__ __device__ inline bool ray_hit(const Ray& R, float r2, float x, float y, float z, float& t) {
     const float Lx = x - R.ox, Ly = y - R.oy, Lz = z - R.oz;
-    const float tca = ray_dot3(Lx, Ly, Lz, R.dx, R.dy, R.dz) * R.inva;
+    const float tca = dot3(Lx, Ly, Lz, R.dx, R.dy, R.dz) * R.inva;
     const float qx = fmaf(-tca, R.dx, Lx), qy = fmaf(-tca, R.dy, Ly), qz = fmaf(-tca, R.dz, Lz);
-    const float d2 = ray_dot3(qx, qy, qz, qx, qy, qz);
+    const float d2 = dot3(qx, qy, qz, qx, qy, qz);
     const float s = r2 - d2;
     if (s < 0.0f) return false;
     const float thc = sqrtf(s * R.inva);
@@ -173,7 +170,7 @@ __host__ __device__ inline bool ray_enter(const SimK& k, const Ray& R, float& t0
     t0 = R.tmin; t1 = R.tmax;
     if (!(ray_clip_axis(R.ox, R.dx, k.gminx - cs, fmaf((float)(k.gx + 1), cs, k.gminx), t0, t1) &&
           ray_clip_axis(R.oy, R.dy, k.gminy - cs, fmaf((float)(k.gy + 1), cs, k.gminy), t0, t1) &&
-          ray_clip_axis(R.oz, R.dz, k.gminz - cs, fmaf((float)(k.gz + 1), cs, k.gminz), t0, t1) && t0 <= t1 && ray_finite(t0))) return false;
+          ray_clip_axis(R.oz, R.dz, k.gminz - cs, fmaf((float)(k.gz + 1), cs, k.gminz), t0, t1) && t0 <= t1 && float_finite(t0))) return false;
     gX = (fmaf(t0, R.dx, R.ox) - k.gminx) / cs; gY = (fmaf(t0, R.dy, R.oy) - k.gminy) / cs; gZ = (fmaf(t0, R.dz, R.oz) - k.gminz) / cs;
     return true;
 }
@@ -282,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void k_rays(SimK k, RayK rk, const float4* 
     if (live)
         best = ray_walk(
             k, rk, R, [&](int cx, int cy, int cz, auto&& f) { neighbor_rows(k, cellStart, 1, rk.n, cx, cy, cz, f); }, [&](uint32_t j) { return pv[2u * j]; },
-            [&](uint32_t j) { const uint32_t id = fbits(own[j].w) - rk.idBase; return id < rk.n ? id : 0u; }, [&](uint32_t j) { return knn_ghost(own, j); }, bestSlot);
+            [&](uint32_t j) { const uint32_t id = fbits(own[j].w) - rk.idBase; return id < rk.n ? id : 0u; }, [&](uint32_t j) { return slot_ghost(own, j); }, bestSlot);
     if (act) {
         float x = 0.0f, y = 0.0f, z = 0.0f;
         if (best != kRayNoKey && !(rk.flags & kRaysAnyHit)) {

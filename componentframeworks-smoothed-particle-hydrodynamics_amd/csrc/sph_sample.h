@@ -70,8 +70,6 @@ __device__ __forceinline__ SampleOut sample_finish(const SimK& k, const SampleAc
     return o;
 }
 
-__device__ __forceinline__ bool sample_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 // The 9 candidate rows of x's cell, in canonical order: f(row, nz, ny, first slot, end slot).
 template <class F>
 __device__ __forceinline__ void sample_rows(const SimK& k, const uint32_t* __restrict__ cellStart, int cx, int cy, int cz, F&& f) {
@@ -89,8 +87,8 @@ __device__ __forceinline__ SampleAcc sample_global(const SimK& k, const float4* 
                                                    float px, float py, float pz) {
     SampleAcc a;
     sample_reset(a);
-    const int cx = cell_axis(px, k.gminx, k.cellSize, k.gx), cy = cell_axis(py, k.gminy, k.cellSize, k.gy), cz = cell_axis(pz, k.gminz, k.cellSize, k.gz);
-    sample_rows(k, cellStart, cx, cy, cz, [&](int, int, uint32_t qs, uint32_t qe) {
+    const int3 cell = cell_of(k, px, py, pz);
+    sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
         for (uint32_t q = qs; q < qe; ++q) {
             const float4 J = pv[2u * q];
             const float4 JV = VEL ? pv[2u * q + 1u] : J;
@@ -212,8 +210,8 @@ __device__ __forceinline__ void lattice_brick(const SimK& k, const LatticeK& L, 
             if (staged) {
                 sample_reset(a);
                 const int rows = meta[1], cylo = meta[2], nyS = meta[3], czlo = meta[4];
-                const int cx = cell_axis(px, k.gminx, k.cellSize, k.gx), cy = cell_axis(py, k.gminy, k.cellSize, k.gy), cz = cell_axis(pz, k.gminz, k.cellSize, k.gz);
-                sample_rows(k, cellStart, cx, cy, cz, [&](int nz, int ny, uint32_t qs, uint32_t qe) {
+                const int3 cell = cell_of(k, px, py, pz);
+                sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int nz, int ny, uint32_t qs, uint32_t qe) {
                     const int sr = (nz - czlo) * nyS + (ny - cylo);
                     const bool inRows = ny >= cylo && ny < cylo + nyS && sr >= 0 && sr < rows;
                     const uint32_t base = inRows ? rowOff[sr] : 0u, first = inRows ? rowQs[sr] : 0u, len = inRows ? rowOff[sr + 1] - base : 0u;

@@ -26,7 +26,8 @@
 
 #include <vector>
 
-#include "sph_neighbors.h"   // neighbor_rows; sph_sample.h
+#include "sph_query.h"    // HostGrid of the *_host twin
+#include "sph_sample.h"   // sample_rows
 
 namespace sph {
 
@@ -42,46 +43,6 @@ struct ScalarCoef {
     float pad[3];
 };
 static_assert(sizeof(ScalarCoef) == 48, "ScalarCoef is 48 bytes");
-
-__host__ __device__ inline float scalar_dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-__host__ __device__ inline bool scalar_finite(float f) { return float_finite(f); }
-// cell_axis of sph_device.h for both sides (the same four IEEE operations).
-__host__ __device__ inline int scalar_cell_axis(float p, float gmin, float cellSize, int dim) {
-    const float q = (p - gmin) / cellSize;
-    float f = floorf(q);
-    f = fminf(fmaxf(f, 0.0f), (float)(dim - 1));
-    return (int)f;
-}
-
-// The grid of host records as the counting sort leaves it: cells ascending, members ascending by index.  start[c] is the first sorted
-// slot of cell c, order[slot] the record in that slot, slotOf[i] the slot of record i.  Every *_host reference builds this one and
-// walks it with the device's own neighbor_rows.
-struct HostGrid {
-    const SimK& k;
-    std::vector<uint32_t> start, order, slotOf;
-    HostGrid(const SimK& k_, const SphParticle* particles, size_t n) : k(k_), start((size_t)k_.numCells + 1, 0u), order(n), slotOf(n) {
-        std::vector<uint32_t> cellOf(n);
-        for (size_t i = 0; i < n; ++i) {
-            int cx, cy, cz;
-            cell(particles[i].pos, cx, cy, cz);
-            cellOf[i] = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
-            start[cellOf[i] + 1] += 1u;
-        }
-        for (size_t c = 0; c < (size_t)k.numCells; ++c) start[c + 1] += start[c];
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < n; ++i) { slotOf[i] = fill[cellOf[i]]++; order[slotOf[i]] = (uint32_t)i; }
-    }
-    // The clamped cell of a point.
-    void cell(const float* x, int& cx, int& cy, int& cz) const {
-        cx = scalar_cell_axis(x[0], k.gminx, k.cellSize, k.gx); cy = scalar_cell_axis(x[1], k.gminy, k.cellSize, k.gy);
-        cz = scalar_cell_axis(x[2], k.gminz, k.cellSize, k.gz);
-    }
-    // f(first slot, end slot) per in-grid row of the (2s + 1)^2 around a cell, in ascending slot order.
-    template <class F>
-    void rows(int s, int cx, int cy, int cz, F&& f) const { neighbor_rows(k, start.data(), s, (uint32_t)order.size(), cx, cy, cz, f); }
-};
 
 // kLap = (float)(2 m 45 / (pi h^6)) = (float)((90 m) / (pi ((h^2 h^2) h^2))), in double on the host.
 inline float scalar_klap(float mass, float h) {
@@ -105,7 +66,7 @@ template <int K>
 __host__ __device__ inline void scalar_pair(float h, float h2, float xi, float yi, float zi, float wi, const float* ci,
                                             float xj, float yj, float zj, float wj, const float* cj, float (&a)[K], float& W) {
     const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    const float r2 = scalar_dot3(dx, dy, dz, dx, dy, dz);
+    const float r2 = dot3(dx, dy, dz, dx, dy, dz);
     if (!(r2 > 0.0f && r2 < h2 && wj > 0.0f)) return;
     const float r = sqrtf(r2);
     const float u = h - r;
@@ -179,8 +140,7 @@ __device__ __forceinline__ void scalar_store(bool target, const ScalarCoef* __re
         for (int j = 0; j < K; ++j) c[(size_t)id * K + j] = out[j];
         sBits = fbits(s);
     }
-    // non-negative floats order as their bits: one atomic per wave
-    for (int sh = 32; sh >= 1; sh >>= 1) sBits = max(sBits, (uint32_t)__shfl_xor((int)sBits, sh, 64));
+    sBits = wave_max(sBits);                                           // non-negative floats order as their bits: one atomic per wave
     if ((threadIdx.x & 63) == 0 && sBits) atomicMax(&state[0], sBits);
 }
 
@@ -198,8 +158,8 @@ __global__ __launch_bounds__(kBlock) void k_scalar_sweep(SimK k, const float4* _
     for (int j = 0; j < K; ++j) { ci[j] = 0.0f; a[j] = 0.0f; }
     const bool target = scalar_target<K>(pv, own, sC, idBase, n, q, P, id, ci);
     if (target) {
-        const int cx = cell_axis(P.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(P.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(P.z, k.gminz, k.cellSize, k.gz);
-        sample_rows(k, cellStart, cx, cy, cz, [&](int, int, uint32_t qs, uint32_t qe) {
+        const int3 cell = cell_of(k, P.x, P.y, P.z);
+        sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
             qe = min(qe, n);                                           // (cellStart never exceeds n; kept so that no load leaves the arrays)
             for (uint32_t j = qs; j < qe; ++j)
                 if (j != q) scalar_candidate_global<K>(k, pv, sC, P, ci, j, a, W);
@@ -283,8 +243,8 @@ __global__ __launch_bounds__(kBlock) void k_scalar_sweep_staged(SimK k, const fl
     const bool target = scalar_target<K>(pv, own, sC, idBase, n, q, P, id, ci);
     if (target) {
         const int rows = meta[1], cylo = meta[2], nyS = meta[3], czlo = meta[4];
-        const int cx = cell_axis(P.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(P.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(P.z, k.gminz, k.cellSize, k.gz);
-        sample_rows(k, cellStart, cx, cy, cz, [&](int nz, int ny, uint32_t qs, uint32_t qe) {
+        const int3 cell = cell_of(k, P.x, P.y, P.z);
+        sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int nz, int ny, uint32_t qs, uint32_t qe) {
             qe = min(qe, n);
             const int sr = (nz - czlo) * nyS + (ny - cylo);
             const bool inRows = staged && nz >= czlo && ny >= cylo && ny < cylo + nyS && sr >= 0 && sr < rows;
@@ -315,8 +275,8 @@ __device__ __forceinline__ float scalar_shepard(const SimK& k, const float4* __r
                                                 const float* __restrict__ sC, int channel, float px, float py, float pz) {
     if (!sample_finite(px, py, pz)) return 0.0f;
     float num = 0.0f, wsum = 0.0f;
-    const int cx = cell_axis(px, k.gminx, k.cellSize, k.gx), cy = cell_axis(py, k.gminy, k.cellSize, k.gy), cz = cell_axis(pz, k.gminz, k.cellSize, k.gz);
-    sample_rows(k, cellStart, cx, cy, cz, [&](int, int, uint32_t qs, uint32_t qe) {
+    const int3 cell = cell_of(k, px, py, pz);
+    sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
         for (uint32_t j = qs; j < qe; ++j) {
             const float4 J = pv[2u * j];
             const float dx = px - J.x, dy = py - J.y, dz = pz - J.z;

@@ -1,7 +1,8 @@
 // sph_shell.h -- free-surface particles: which particles (or query points) lie in the outer shell of the fluid, which way the surface
 // faces there, and how sharply convex it is (no reference counterpart).
 //
-// Grid, radius rules, stencil and candidates are those of sph_neighbors.h (neighbor_stencil, neighbor_rows; r2 is neighbor_accept's).
+// Grid, radius rules, stencil, candidates and the target of a lane are those of sph_query.h (neighbor_stencil, neighbor_rows,
+// query_target; r2 is neighbor_accept's).
 // Only positions enter.  Pass 1 sums, over the accepted candidates j of a target at x in row order, with d = x_j - x, t = R2 - r2 and
 // w = t * t:  cnt += 1, W += w, S = fma(w, d, S).  The finish turns (cnt, W, S) into the record: s2 = dot3(S, S), lim = (offset R) W,
 // in the shell iff cnt == 0 or cnt < minCount or s2 > lim^2; normal = -S / sqrt(s2) (zero where s2 == 0); offsetRatio = sqrt(s2) /
@@ -17,7 +18,8 @@
 //                             positions straight from global memory (16 B each), every sum lane-owned.  Writes the 32-byte row, the
 //                             by-row flag word for the scan of ids[], and for particles the by-slot float4 (normal, shell ? 1 : 0) and the
 //                             by-slot flag word; adds (isolated rows, largest count) to stats with one integer atomic per wave and word.
-//   k_shell_compact           out[offsets[i]] = i where flag[i]: the scan's second half, used twice (ids[] by row, shell slots by slot).
+//   k_shell_compact           (sph_query.h) out[offsets[i]] = i where flag[i]: the scan's second half, used twice (ids[] by row, shell
+//                             slots by slot).
 //   k_shell_crest             pass 2 over the compacted shell slots in ascending slot order (full waves whose lanes still share rows): a
 //                             candidate that is not in the shell costs the one 16-byte load of its by-slot float4.
 // ids[] is k_neighbors_ids' (a permutation of [0, n)); the range guards (row < rows, j < end <= n, offsets < rows) stay so that no load
@@ -25,7 +27,7 @@
 #pragma once
 #include <math.h>
 
-#include "sph_knn.h"   // knn_ghost
+#include "sph_query.h"
 
 namespace sph {
 
@@ -53,7 +55,7 @@ struct ShellK {
 // d = x_j - x and r2 = dot3(d, d): the bits of neighbor_accept's r2 (its d is the exact negative, the squares are the same floats).
 __host__ __device__ inline bool shell_accept(float xi, float yi, float zi, float xj, float yj, float zj, float R2, float& dx, float& dy, float& dz, float& r2) {
     dx = xj - xi; dy = yj - yi; dz = zj - zi;
-    r2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+    r2 = dot3(dx, dy, dz, dx, dy, dz);
     return r2 < R2;
 }
 // One accepted candidate of pass 1.
@@ -66,7 +68,7 @@ __host__ __device__ inline void shell_add(ShellAcc& a, float dx, float dy, float
 }
 // The record of a target that walked (crest stays 0).
 __host__ __device__ inline void shell_finish(const ShellAcc& a, const ShellK& sk, ShellRow& out) {
-    const float s2 = fmaf(a.Sz, a.Sz, fmaf(a.Sy, a.Sy, a.Sx * a.Sx));
+    const float s2 = dot3(a.Sx, a.Sy, a.Sz, a.Sx, a.Sy, a.Sz);
     const float lim = (sk.offset * sk.R) * a.W;
     const bool in = a.cnt == 0u || a.cnt < sk.minCount || s2 > lim * lim;
     const float len = sqrtf(s2);
@@ -92,8 +94,8 @@ __host__ __device__ inline void shell_zero(ShellRow& out) {
 constexpr float kShellCrestScale = 4294967296.0f;     // 2^32
 __host__ __device__ inline long long shell_crest_term(float nx, float ny, float nz, float mx, float my, float mz, float dx, float dy, float dz,
                                                       float r2, float R) {
-    if (!(fmaf(dz, nz, fmaf(dy, ny, dx * nx)) < 0.0f)) return 0ll;
-    const float turn = 1.0f - fmaf(nz, mz, fmaf(ny, my, nx * mx));
+    if (!(dot3(dx, dy, dz, nx, ny, nz) < 0.0f)) return 0ll;
+    const float turn = 1.0f - dot3(nx, ny, nz, mx, my, mz);
     const float close = 1.0f - sqrtf(r2) / R;
     const float term = turn * close;
     if (!(fabsf(term) <= 4.0f)) return 0ll;                                      // (never met with unit normals: keeps the conversion defined)
@@ -104,8 +106,7 @@ __host__ __device__ inline float shell_crest_value(long long sum) { return (floa
 
 // (isolated rows, largest count) of the wave into stats[0], stats[1]: every lane of the wave must arrive.
 __device__ __forceinline__ void shell_reduce(bool isolated, uint32_t cnt, unsigned long long* __restrict__ stats) {
-    uint32_t m = cnt;
-    for (int sh = 32; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
+    const uint32_t m = wave_max(cnt);
     const unsigned long long ni = (unsigned long long)__popcll(__ballot(isolated));
     if ((threadIdx.x & 63) == 0) {
         if (ni) atomicAdd(stats + 0, ni);
@@ -123,33 +124,24 @@ __global__ __launch_bounds__(kBlock) void k_shell_gather(SimK k, NbK nb, ShellK 
     const bool fluidOnly = (nb.flags & kShellFluidOnly) != 0;
     float4 P = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     size_t row = 0;
-    bool act = i < rows;
-    if (act) {
-        if (PARTICLES) {
-            P = pv[2u * (uint32_t)i];
-            row = (size_t)(uint32_t)ids[i];
-            act = row < rows;
-        } else {
-            P = points[i];
-            row = i;
-        }
-    }
-    bool walk = act && sample_finite(P.x, P.y, P.z);
-    if (PARTICLES && walk && fluidOnly) walk = !knn_ghost(own, (uint32_t)i);
+    bool walk = false;
+    const bool act = query_target<PARTICLES>(pv, ids, points, rows, i, P, row, walk);
+    walk = act && sample_finite(P.x, P.y, P.z);                               // (a non-finite particle has an all-zero row here)
+    if (PARTICLES && walk && fluidOnly) walk = !slot_ghost(own, (uint32_t)i);
     ShellRow r;
     shell_zero(r);
     if (walk) {
         ShellAcc a;
         shell_reset(a);
         const uint32_t q = (uint32_t)i;
-        const int cx = cell_axis(P.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(P.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(P.z, k.gminz, k.cellSize, k.gz);
-        neighbor_rows(k, cellStart, nb.s, nb.n, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+        const int3 cell = cell_of(k, P.x, P.y, P.z);
+        neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
             for (uint32_t j = qs; j < qe; ++j) {
                 if (PARTICLES && j == q) continue;
                 const float4 J = pv[2u * j];
                 float dx, dy, dz, r2;
                 if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
-                if (fluidOnly && knn_ghost(own, j)) continue;
+                if (fluidOnly && slot_ghost(own, j)) continue;
                 shell_add(a, dx, dy, dz, r2, nb.R2);
             }
         });
@@ -169,15 +161,6 @@ __global__ __launch_bounds__(kBlock) void k_shell_gather(SimK k, NbK nb, ShellK 
     shell_reduce(walk && (r.flags & kShellIsolated), r.count, stats);
 }
 
-// The second half of a compaction: out[offsets[i]] = i where flag[i] (offsets: the exclusive scan of flag).
-__global__ __launch_bounds__(kBlock) void k_shell_compact(const uint32_t* __restrict__ flag, const long long* __restrict__ offsets, size_t rows,
-                                                          int32_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= rows || !flag[i]) return;
-    const long long at = offsets[i];
-    if (at >= 0 && (size_t)at < rows) out[at] = (int32_t)i;
-}
-
 __global__ __launch_bounds__(kBlock) void k_shell_crest(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
                                                         const int32_t* __restrict__ ids, const float4* __restrict__ nrmSlot,
                                                         const int32_t* __restrict__ shellSlots, size_t numShell, size_t rows, ShellRow* __restrict__ out) {
@@ -190,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void k_shell_crest(SimK k, NbK nb, ShellK s
     const float4 P = pv[2u * q];
     const float4 N = nrmSlot[q];
     long long crest = 0ll;
-    const int cx = cell_axis(P.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(P.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(P.z, k.gminz, k.cellSize, k.gz);
-    neighbor_rows(k, cellStart, nb.s, nb.n, cx, cy, cz, [&](uint32_t qs, uint32_t qe) {
+    const int3 cell = cell_of(k, P.x, P.y, P.z);
+    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
         for (uint32_t j = qs; j < qe; ++j) {
             const float4 M = nrmSlot[j];
             if (M.w == 0.0f || j == q) continue;                              // not in the shell: nothing else is read

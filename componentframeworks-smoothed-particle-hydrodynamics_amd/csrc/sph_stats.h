@@ -72,7 +72,6 @@ __device__ __forceinline__ void stat_wave_ext(float (&ev)[kStatExt], uint32_t (&
             stat_take(stat_is_min(k), ev[k], eid[k], v2, id2);
         }
 }
-__device__ __forceinline__ bool stat_finite(float f) { return (fbits(f) & 0x7F800000u) != 0x7F800000u; }
 
 __device__ __forceinline__ uint32_t stat_bin(float v, float lo, float hi, float scale, uint32_t bins) {
     if (v < lo) return 0u;
@@ -92,8 +91,8 @@ __device__ __forceinline__ void stat_slot(const StatK& k, bool in, float4 a, flo
     const float foam = o.y, prs = b.w;
     const bool fluid = in && !(flags & F_GHOSTNZ);
     const bool g1 = in && (flags & F_GHOST1);
-    const bool finite = stat_finite(a.x) && stat_finite(a.y) && stat_finite(a.z) && stat_finite(b.x) && stat_finite(b.y) && stat_finite(b.z) &&
-                        stat_finite(rho) && stat_finite(prs) && stat_finite(foam);
+    const bool finite = float_finite(a.x) && float_finite(a.y) && float_finite(a.z) && float_finite(b.x) && float_finite(b.y) && float_finite(b.z) &&
+                        float_finite(rho) && float_finite(prs) && float_finite(foam);
     const bool counted = fluid && finite;
     const bool bad = fluid && !finite;
     const float qx = floorf((a.x - k.gminx) / k.cellSize), qy = floorf((a.y - k.gminy) / k.cellSize), qz = floorf((a.z - k.gminz) / k.cellSize);
@@ -220,9 +219,9 @@ __global__ __launch_bounds__(kBlock) void k_stats_tiles(StatK k, const float4* _
     }
     // extrema, counts, first ids: any tree gives the same bits
     stat_wave_ext(ev, eid);
-    for (int s = 32; s >= 1; s >>= 1) {
-        first[0] = min(first[0], (uint32_t)__shfl_xor((int)first[0], s, 64));
-        first[1] = min(first[1], (uint32_t)__shfl_xor((int)first[1], s, 64));
+    for (int s = 32; s >= 1; s >>= 1) {                                                 // (open-coded, like the loops below: the calls of sph_wave.h
+        first[0] = min(first[0], (uint32_t)__shfl_xor((int)first[0], s, 64));           // reorder the interleaved chains, and the statistics kernels
+        first[1] = min(first[1], (uint32_t)__shfl_xor((int)first[1], s, 64));           // missed the A/B rule with them: profiles/r20_header_refactor_ab.json)
     }
     if (lane == 0) {
 #pragma unroll

@@ -156,16 +156,6 @@ __global__ __launch_bounds__(kBlock) void k_surf_count(SurfK s, const float* __r
     if (threadIdx.x == 0) tileSums[blockIdx.x] = make_uint2(totV, totT);
 }
 
-__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
 // One block.  Thread t sums a contiguous run of tiles, the 256 run sums are scanned in 64 bits, then each thread writes its run's
 // exclusive offsets: tileOff[2 t] vertices, tileOff[2 t + 1] triangles; tileOff[2 nTiles], [2 nTiles + 1] the totals.
 __global__ __launch_bounds__(kBlock) void k_surf_scan_tiles(const uint2* __restrict__ tileSums, unsigned long long* __restrict__ tileOff, int nTiles) {

@@ -50,10 +50,10 @@ __device__ __forceinline__ SampleOut tracer_field(const SimK& k, const float4* _
     if (!sample_finite(x, y, z)) return o;
     SampleAcc a;
     sample_reset(a);
-    const int cx = cell_axis(x, k.gminx, k.cellSize, k.gx), cy = cell_axis(y, k.gminy, k.cellSize, k.gy), cz = cell_axis(z, k.gminz, k.cellSize, k.gz);
+    const int3 cell = cell_of(k, x, y, z);
     // sample_global's walk with the loads of kTracerAhead candidates issued together: a lane's walk is a chain of dependent cache
     // misses otherwise.  The candidates are accumulated in the same order, so the bits are sample_global's.
-    sample_rows(k, cellStart, cx, cy, cz, [&](int, int, uint32_t qs, uint32_t qe) {
+    sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
         uint32_t q = qs;
         for (; q + (uint32_t)kTracerAhead <= qe; q += (uint32_t)kTracerAhead) {
             float4 J[kTracerAhead], V[kTracerAhead];
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(kBlock) void k_tracer_bin(SimK k, const float4* __r
     if (i >= m) return;
     const float4 p = rec[2u * i];
     // (cell_axis clamps: a tracer outside the grid or with a non-finite coordinate still lands in [0, numCells))
-    const int cx = cell_axis(p.x, k.gminx, k.cellSize, k.gx), cy = cell_axis(p.y, k.gminy, k.cellSize, k.gy), cz = cell_axis(p.z, k.gminz, k.cellSize, k.gz);
-    const uint32_t cell = (uint32_t)((cz * k.gy + cy) * k.gx + cx);
+    const int3 c = cell_of(k, p.x, p.y, p.z);
+    const uint32_t cell = (uint32_t)((c.z * k.gy + c.y) * k.gx + c.x);
     key[i] = make_uint2(cell, atomicAdd(&cellCount[cell], 1u));
 }
 

@@ -5,7 +5,7 @@
 // axis a is (float)i * spacing_a - half_a.  vol_sample is the trilinear interpolant and the gradient of the same interpolant, vol_project
 // the two-step projection of a point inside the solid onto the zero level set; both are __host__ __device__ and are what k_obstacles_vol
 // (sph_obstacle.h) and sph_volume_sample_host / sph_obstacles_apply_host_volumes run.  -ffp-contract=off: the only fused operations are
-// the explicit fmaf() of vol_dot3.
+// the explicit fmaf() of dot3 (sph_device.h).
 //
 //   k_mesh_distance   all pairs (lattice point, triangle), tiled like an n-body kernel: a lane owns one lattice point, a block stages
 //                     kMeshChunk triangles with their edges into LDS (one triangle per thread, once per chunk) and every lane reads the
@@ -22,7 +22,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "sph_device.h"   // float_finite
+#include "sph_device.h"   // dot3, float_finite
 
 namespace sph {
 
@@ -48,10 +48,6 @@ struct VolTable {
     int32_t bind[kVolBodies];
 };
 
-__host__ __device__ inline float vol_dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-__host__ __device__ inline bool vol_finite(float f) { return float_finite(f); }
 __host__ __device__ inline float vol_lerp(float a, float b, float f) { return a + f * (b - a); }   // subtract, multiply, add
 
 // half_a = (0.5f (float)(dims_a - 1)) spacing_a, inv_a = 1.0f / spacing_a.
@@ -101,16 +97,16 @@ __host__ __device__ inline int vol_project(const VolRec& v, float lx, float ly, 
     float phi, g[3];
     if (!vol_sample(v, lx, ly, lz, false, phi, g)) return 0;
     if (!(phi < 0.0f)) return 0;
-    float len = sqrtf(vol_dot3(g[0], g[1], g[2], g[0], g[1], g[2]));
-    if (len == 0.0f || !vol_finite(len)) return 2;
+    float len = sqrtf(dot3(g[0], g[1], g[2], g[0], g[1], g[2]));
+    if (len == 0.0f || !float_finite(len)) return 2;
     const float ax = g[0] / len, ay = g[1] / len, az = g[2] / len;
     const float px = lx - phi * ax, py = ly - phi * ay, pz = lz - phi * az;
     vol_sample(v, px, py, pz, true, phi, g);
-    len = sqrtf(vol_dot3(g[0], g[1], g[2], g[0], g[1], g[2]));
-    if (len == 0.0f || !vol_finite(len)) return 2;
+    len = sqrtf(dot3(g[0], g[1], g[2], g[0], g[1], g[2]));
+    if (len == 0.0f || !float_finite(len)) return 2;
     const float bx = g[0] / len, by = g[1] / len, bz = g[2] / len;
     const float qx = px - phi * bx, qy = py - phi * by, qz = pz - phi * bz;
-    if (!vol_finite(qx) || !vol_finite(qy) || !vol_finite(qz)) return 0;
+    if (!float_finite(qx) || !float_finite(qy) || !float_finite(qz)) return 0;
     ox = qx; oy = qy; oz = qz; mx = bx; my = by; mz = bz;
     return 1;
 }
@@ -144,14 +140,14 @@ __host__ __device__ inline void mesh_tri_setup(const float* __restrict__ verts, 
 // face, in this order), then dot3(p - q, p - q).  Every operation but the fmaf of dot3 is rounded on its own; the divisions are IEEE.
 __host__ __device__ inline float mesh_tri_d2(const MeshTri& T, float px, float py, float pz) {
     const float apx = px - T.a[0], apy = py - T.a[1], apz = pz - T.a[2];
-    const float d1 = vol_dot3(T.ab[0], T.ab[1], T.ab[2], apx, apy, apz);
-    const float d2 = vol_dot3(T.ac[0], T.ac[1], T.ac[2], apx, apy, apz);
+    const float d1 = dot3(T.ab[0], T.ab[1], T.ab[2], apx, apy, apz);
+    const float d2 = dot3(T.ac[0], T.ac[1], T.ac[2], apx, apy, apz);
     float qx, qy, qz;
     do {
         if (d1 <= 0.0f && d2 <= 0.0f) { qx = T.a[0]; qy = T.a[1]; qz = T.a[2]; break; }
         const float bpx = px - T.b[0], bpy = py - T.b[1], bpz = pz - T.b[2];
-        const float d3 = vol_dot3(T.ab[0], T.ab[1], T.ab[2], bpx, bpy, bpz);
-        const float d4 = vol_dot3(T.ac[0], T.ac[1], T.ac[2], bpx, bpy, bpz);
+        const float d3 = dot3(T.ab[0], T.ab[1], T.ab[2], bpx, bpy, bpz);
+        const float d4 = dot3(T.ac[0], T.ac[1], T.ac[2], bpx, bpy, bpz);
         if (d3 >= 0.0f && d4 <= d3) { qx = T.b[0]; qy = T.b[1]; qz = T.b[2]; break; }
         const float vc = d1 * d4 - d3 * d2;
         if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
@@ -160,8 +156,8 @@ __host__ __device__ inline float mesh_tri_d2(const MeshTri& T, float px, float p
             break;
         }
         const float cpx = px - T.c[0], cpy = py - T.c[1], cpz = pz - T.c[2];
-        const float d5 = vol_dot3(T.ab[0], T.ab[1], T.ab[2], cpx, cpy, cpz);
-        const float d6 = vol_dot3(T.ac[0], T.ac[1], T.ac[2], cpx, cpy, cpz);
+        const float d5 = dot3(T.ab[0], T.ab[1], T.ab[2], cpx, cpy, cpz);
+        const float d6 = dot3(T.ac[0], T.ac[1], T.ac[2], cpx, cpy, cpz);
         if (d6 >= 0.0f && d5 <= d6) { qx = T.c[0]; qy = T.c[1]; qz = T.c[2]; break; }
         const float vb = d5 * d2 - d1 * d6;
         if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
@@ -181,7 +177,7 @@ __host__ __device__ inline float mesh_tri_d2(const MeshTri& T, float px, float p
         qx = (T.a[0] + T.ab[0] * v) + T.ac[0] * w; qy = (T.a[1] + T.ab[1] * v) + T.ac[1] * w; qz = (T.a[2] + T.ab[2] * v) + T.ac[2] * w;
     } while (false);
     const float ex = px - qx, ey = py - qy, ez = pz - qz;
-    return vol_dot3(ex, ey, ez, ex, ey, ez);
+    return dot3(ex, ey, ez, ex, ey, ez);
 }
 
 // Half the solid angle of the triangle seen from p (Van Oosterom and Strackee): atan2f(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|).
@@ -190,9 +186,9 @@ __host__ __device__ inline float mesh_tri_angle(const MeshTri& T, float px, floa
     const float ax = T.a[0] - px, ay = T.a[1] - py, az = T.a[2] - pz;
     const float bx = T.b[0] - px, by = T.b[1] - py, bz = T.b[2] - pz;
     const float cx = T.c[0] - px, cy = T.c[1] - py, cz = T.c[2] - pz;
-    const float la = sqrtf(vol_dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(vol_dot3(bx, by, bz, bx, by, bz)), lc = sqrtf(vol_dot3(cx, cy, cz, cx, cy, cz));
-    const float det = vol_dot3(ax, ay, az, by * cz - bz * cy, bz * cx - bx * cz, bx * cy - by * cx);
-    const float den = (((la * lb) * lc + vol_dot3(ax, ay, az, bx, by, bz) * lc) + vol_dot3(bx, by, bz, cx, cy, cz) * la) + vol_dot3(cx, cy, cz, ax, ay, az) * lb;
+    const float la = sqrtf(dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(dot3(bx, by, bz, bx, by, bz)), lc = sqrtf(dot3(cx, cy, cz, cx, cy, cz));
+    const float det = dot3(ax, ay, az, by * cz - bz * cy, bz * cx - bx * cz, bx * cy - by * cx);
+    const float den = (((la * lb) * lc + dot3(ax, ay, az, bx, by, bz) * lc) + dot3(bx, by, bz, cx, cy, cz) * la) + dot3(cx, cy, cz, ax, ay, az) * lb;
     return atan2f(det, den);
 }
 
@@ -266,7 +262,7 @@ constexpr int kMomFinishBlock = 1024;
 constexpr int kMomChunks = kMomFinishBlock / kMomTerms;
 
 __host__ __device__ inline float vol_diagonal(const float* spacing) {
-    return sqrtf(vol_dot3(spacing[0], spacing[1], spacing[2], spacing[0], spacing[1], spacing[2]));
+    return sqrtf(dot3(spacing[0], spacing[1], spacing[2], spacing[0], spacing[1], spacing[2]));
 }
 // The ten terms of one lattice point added to t.
 __host__ __device__ inline void vol_moment_terms(float phi, float diag, float lx, float ly, float lz, double (&t)[kMomTerms]) {
@@ -314,7 +310,7 @@ __global__ __launch_bounds__(kMomBlock) void k_volume_moments(VolRec v, float di
     }
 #pragma unroll
     for (int c = 0; c < kMomTerms; ++c)
-        for (int o = 32; o >= 1; o >>= 1) t[c] += __shfl_xor(t[c], o, 64);
+        for (int o = 32; o >= 1; o >>= 1) t[c] += __shfl_xor(t[c], o, 64);   // (open-coded: wave_sum per term reorders the independent chains; profiles/r20_header_refactor_ab.json)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0)
         for (int c = 0; c < kMomTerms; ++c) sacc[wave][c] = t[c];

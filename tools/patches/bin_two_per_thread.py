@@ -5,7 +5,7 @@ d = sys.argv[1]
 p = os.path.join(d, "sph_kernels.h")
 s = open(p).read()
 a = s.index("__global__ __launch_bounds__(kBlock) void k_bin(")
-b = s.index("__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {")
+b = s.index("// Each thread owns kScanItems CONSECUTIVE cells")             # what follows k_bin (the scans are sph_wave.h's)
 new = r'''constexpr int kBinPerThread = BINPT;
 __global__ __launch_bounds__(kBlock) void k_bin(SimK k, const float4* __restrict__ pos, uint2* __restrict__ binKey,
                                                 uint32_t* __restrict__ cellCount, int n, const uint32_t* __restrict__ slotsInUse) {
