@@ -657,6 +657,34 @@ def _is_cuda_f32(t) -> bool:
     return t.is_cuda and t.dtype == __import__("torch").float32 and t.is_contiguous()
 
 
+def _device_points4(points, who):
+    """Query points as a (m, 4) float32 torch device tensor: such a tensor is used in place, anything else is uploaded (_points4)."""
+    import torch
+    if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
+        return points
+    return torch.from_numpy(_points4(points, who, keep_w=False)).cuda()
+
+
+def _fetch(call, device, specs, null_empty=True):
+    """The results of a query, one fresh array per spec (shape, numpy dtype, name of the torch dtype), filled by one call(*pointers):
+    numpy zeros, or with `device` torch.empty on the device (a spec without a torch dtype stays a numpy array).  A spec of None is no
+    array: None and a null pointer; an empty array goes as a null pointer too, unless null_empty is False."""
+    out, ptrs = [], []
+    for spec in specs:
+        arr = ptr = None
+        if spec is not None and device and spec[2]:
+            import torch
+            arr = torch.empty(spec[0], dtype=getattr(torch, spec[2]), device="cuda")
+            ptr = C.c_void_p(arr.data_ptr()) if arr.numel() or not null_empty else None
+        elif spec is not None:
+            arr = np.zeros(spec[0], spec[1])
+            ptr = _ptr(arr) if arr.size or not null_empty else None
+        out.append(arr)
+        ptrs.append(ptr)
+    _check(call(*ptrs))
+    return tuple(out)
+
+
 def _assign(struct, name, value):
     """struct.name = value, element by element where the field is an array."""
     cur = getattr(struct, name)
@@ -1206,6 +1234,17 @@ class SPHFluidGPU:
         frac = self.sample(pts.reshape(-1, 4))["fraction"].reshape(len(cols), len(ys))
         return gauge_levels(frac, ys, threshold)
 
+    # -- spatial queries: what the five families below share ---------------------------------------
+    def _radius(self, radius, default: float = 1.0):
+        """A query's radius: the caller's, or for None `default` times param_h."""
+        return default * self._p.param_h if radius is None else radius
+
+    def _info(self, kind, getter):
+        """A fresh info struct of `kind`, filled by the library's getter."""
+        info = kind()
+        _check(getter(self._h, C.byref(info)))
+        return info
+
     # -- neighbour lists (include/sph_abi.h "fixed-radius neighbour lists") ------------------------
     def neighbors(self, radius=None, self_=False, half=False, count_only=False, max_pairs: int = 0, device: bool = False):
         """CSR neighbour lists of every particle within `radius` (None: param_h; at most three cells): (offsets int64[n + 1], indices
@@ -1214,18 +1253,13 @@ class SPHFluidGPU:
         torch device tensors.  A total above max_pairs (> 0) raises SphError; neighbor_lists() then still gives the offsets."""
         self._push_params()
         info = SphNeighborInfo()
-        r = self._p.param_h if radius is None else radius
-        _check(self._L.sph_neighbors_build(self._h, float(r), _neighbor_flags(self_, half, count_only), int(max_pairs), C.byref(info)))
+        _check(self._L.sph_neighbors_build(self._h, float(self._radius(radius)), _neighbor_flags(self_, half, count_only), int(max_pairs), C.byref(info)))
         return self.neighbor_lists(device)
 
     def query_neighbors(self, points, radius, count_only=False, max_pairs: int = 0, device: bool = False):
         """The same for (m, 3) or (m, 4) query points: row i lists the particles within `radius` of points[i] (a torch device tensor of
         (m, 4) float32 is used in place).  A point with a non-finite coordinate has an empty row."""
-        import torch
-        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
-            dev = points
-        else:
-            dev = torch.from_numpy(_points4(points, "query_neighbors", keep_w=False)).cuda()
+        dev = _device_points4(points, "query_neighbors")
         self._push_params()
         info = SphNeighborInfo()
         _check(self._L.sph_neighbors_query(self._h, C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), _neighbor_flags(False, False, count_only),
@@ -1234,9 +1268,7 @@ class SPHFluidGPU:
 
     def neighbor_info(self) -> SphNeighborInfo:
         """What the engine's lists hold: rows, total, radius, stencil, flags, kind (0 none, 1 particles, 2 query), maxCount."""
-        info = SphNeighborInfo()
-        _check(self._L.sph_neighbors_info(self._h, C.byref(info)))
-        return info
+        return self._info(SphNeighborInfo, self._L.sph_neighbors_info)
 
     def neighbor_lists(self, device: bool = False):
         """(offsets, indices) of the lists the engine holds; indices is None for count-only lists and after a max_pairs refusal."""
@@ -1245,16 +1277,11 @@ class SPHFluidGPU:
         _check(self._L.sph_neighbors_device(self._h, C.byref(dp_off), C.byref(dp_idx)))
         rows, total = int(info.rows), int(info.total)
         indexed = not (info.flags & SPH_NEIGHBORS_COUNT_ONLY) and bool(dp_idx.value)      # (a refused build lends no indices)
+        copy = self._L.sph_neighbors_export if device else self._L.sph_neighbors_download
+        specs = ((rows + 1, np.int64, "int64"), (total, np.int32, "int32") if indexed else None)
+        off, idx = _fetch(lambda p_off, p_idx: copy(self._h, p_off, p_idx, total), device, specs, null_empty=device)   # (the host copy is given an empty idx as it is)
         if device:
-            import torch
-            off = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
-            idx = torch.empty(total, dtype=torch.int32, device="cuda") if indexed else None
-            _check(self._L.sph_neighbors_export(self._h, C.c_void_p(off.data_ptr()), C.c_void_p(idx.data_ptr()) if total and indexed else None, total))
             self.sync()
-            return off, idx
-        off = np.zeros(rows + 1, np.int64)
-        idx = np.zeros(total, np.int32) if indexed else None
-        _check(self._L.sph_neighbors_download(self._h, _ptr(off), _ptr(idx) if idx is not None else None, total))
         return off, idx
 
     def radius_graph(self, radius=None, half: bool = False):
@@ -1273,28 +1300,15 @@ class SPHFluidGPU:
         labels and roots are fresh torch int32 device tensors (the table stays a numpy array)."""
         self._push_params()
         info = SphComponentInfo()
-        r = self._p.param_h if radius is None else radius
-        _check(self._L.sph_components_build(self._h, float(r), SPH_COMPONENTS_FLUID_ONLY if fluid_only else 0, C.byref(info)))
+        _check(self._L.sph_components_build(self._h, float(self._radius(radius)), SPH_COMPONENTS_FLUID_ONLY if fluid_only else 0, C.byref(info)))
         n, c = int(info.rows), int(info.numComponents)
-        table = np.zeros(c, COMPONENT_DTYPE)
-        if device:
-            import torch
-            labels = torch.empty(n, dtype=torch.int32, device="cuda")
-            roots = torch.empty(n, dtype=torch.int32, device="cuda")
-            _check(self._L.sph_components_download(self._h, C.c_void_p(labels.data_ptr()) if n else None, C.c_void_p(roots.data_ptr()) if n else None,
-                                                   _ptr(table) if c else None, c))
-            return labels, roots, table
-        labels = np.zeros(n, np.int32)
-        roots = np.zeros(n, np.int32)
-        _check(self._L.sph_components_download(self._h, _ptr(labels) if n else None, _ptr(roots) if n else None, _ptr(table) if c else None, c))
-        return labels, roots, table
+        specs = ((n, np.int32, "int32"), (n, np.int32, "int32"), (c, COMPONENT_DTYPE, None))
+        return _fetch(lambda p_labels, p_roots, p_table: self._L.sph_components_download(self._h, p_labels, p_roots, p_table, c), device, specs)
 
     def component_info(self) -> SphComponentInfo:
         """What the engine's components hold: rows, numComponents, numExcluded, largestCount, largestRoot, numSingletons, radius, stencil,
         flags, rounds.  SphError before any components() call."""
-        info = SphComponentInfo()
-        _check(self._L.sph_components_info(self._h, C.byref(info)))
-        return info
+        return self._info(SphComponentInfo, self._L.sph_components_info)
 
     # -- k nearest neighbours (include/sph_abi.h "k nearest neighbours") ---------------------------
     def knn(self, k: int, radius=None, self_=False, fluid_only: bool = False, device: bool = False):
@@ -1304,18 +1318,13 @@ class SPHFluidGPU:
         isGhost != 0 out of every row and gives them empty rows.  numpy arrays, or with device=True fresh torch device tensors."""
         self._push_params()
         info = SphKnnInfo()
-        r = self._p.param_h if radius is None else radius
-        _check(self._L.sph_knn_build(self._h, int(k), float(r), _knn_flags(self_, fluid_only), C.byref(info)))
+        _check(self._L.sph_knn_build(self._h, int(k), float(self._radius(radius)), _knn_flags(self_, fluid_only), C.byref(info)))
         return self.knn_rows(device)
 
     def query_knn(self, points, k: int, radius, fluid_only: bool = False, device: bool = False):
         """The same around (m, 3) or (m, 4) query points: row i holds the k nearest particles within `radius` of points[i] (a torch
         device tensor of (m, 4) float32 is used in place).  A point with a non-finite coordinate has an empty row."""
-        import torch
-        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
-            dev = points
-        else:
-            dev = torch.from_numpy(_points4(points, "query_knn", keep_w=False)).cuda()
+        dev = _device_points4(points, "query_knn")
         self._push_params()
         info = SphKnnInfo()
         m = int(dev.shape[0])
@@ -1326,27 +1335,15 @@ class SPHFluidGPU:
     def knn_info(self) -> SphKnnInfo:
         """What the engine's rows hold: rows, total (sum of counts), rowsFull (rows with count == k), k, radius, stencil, flags, kind
         (1 particles, 2 query).  SphError before any knn() / query_knn() call."""
-        info = SphKnnInfo()
-        _check(self._L.sph_knn_info(self._h, C.byref(info)))
-        return info
+        return self._info(SphKnnInfo, self._L.sph_knn_info)
 
     def knn_rows(self, device: bool = False):
         """(idx, d2, counts) of the rows the engine holds."""
         info = self.knn_info()
         rows, k = int(info.rows), int(info.k)
-        if device:
-            import torch
-            idx = torch.empty((rows, k), dtype=torch.int32, device="cuda")
-            d2 = torch.empty((rows, k), dtype=torch.float32, device="cuda")
-            cnt = torch.empty(rows, dtype=torch.int32, device="cuda")                # (uint32 counts <= 64 in an int32 tensor: the same bits)
-            _check(self._L.sph_knn_download(self._h, C.c_void_p(idx.data_ptr()) if rows else None, C.c_void_p(d2.data_ptr()) if rows else None,
-                                            C.c_void_p(cnt.data_ptr()) if rows else None))
-            return idx, d2, cnt
-        idx = np.zeros((rows, k), np.int32)
-        d2 = np.zeros((rows, k), np.float32)
-        cnt = np.zeros(rows, np.uint32)
-        _check(self._L.sph_knn_download(self._h, _ptr(idx) if rows else None, _ptr(d2) if rows else None, _ptr(cnt) if rows else None))
-        return idx, d2, cnt
+        specs = (((rows, k), np.int32, "int32"), ((rows, k), np.float32, "float32"),
+                 (rows, np.uint32, "int32"))                                             # (uint32 counts <= 64 in an int32 tensor: the same bits)
+        return _fetch(lambda p_idx, p_d2, p_cnt: self._L.sph_knn_download(self._h, p_idx, p_d2, p_cnt), device, specs)
 
     def knn_graph(self, k: int, radius=None, self_=False):
         """The k-nearest-neighbour relation as a (2, E) int64 torch device tensor [receiver, sender], E = knn_info().total: the padded
@@ -1367,7 +1364,7 @@ class SPHFluidGPU:
         import torch
         self._push_params()
         info = SphRaysInfo()
-        r = 0.25 * self._p.param_h if radius is None else radius
+        r = self._radius(radius, 0.25)
         flags = _rays_flags(fluid_only, any_hit)
         if isinstance(rays, torch.Tensor):
             if not (_is_cuda_f32(rays) and rays.dim() == 2 and rays.shape[1] == 8):
@@ -1381,21 +1378,17 @@ class SPHFluidGPU:
 
     def rays_info(self) -> SphRaysInfo:
         """What the engine's hits hold: rays, hits, voidRays, radius, flags.  SphError before any raycast() call."""
-        info = SphRaysInfo()
-        _check(self._L.sph_rays_info(self._h, C.byref(info)))
-        return info
+        return self._info(SphRaysInfo, self._L.sph_rays_info)
 
     def ray_hits(self, device: bool = False):
         """(t, ids, pos, normal) of the hits the engine holds."""
         m = int(self.rays_info().rays)
+        spec = ((m, 8), None, "float32") if device else (m, RAY_HIT_DTYPE, None)        # (one device copy of the 32-byte hits, split into views)
+        (z,) = _fetch(lambda p_hits: self._L.sph_rays_download(self._h, p_hits), device, (spec,))
         if device:
             import torch
-            z = torch.empty((m, 8), dtype=torch.float32, device="cuda")             # (one device copy of the 32-byte hits, split into views)
-            _check(self._L.sph_rays_download(self._h, C.c_void_p(z.data_ptr()) if m else None))
             return z[:, 0], z[:, 1].view(torch.int32), z[:, 2:5], z[:, 5:8]
-        hits = np.zeros(m, RAY_HIT_DTYPE)
-        _check(self._L.sph_rays_download(self._h, _ptr(hits) if m else None))
-        return _split_hits(hits)
+        return _split_hits(z)
 
     # -- free-surface particles (include/sph_abi.h "free-surface particles") ----------------------
     def shell(self, radius=None, offset: float = 0.10, min_count: int = 0, fluid_only: bool = False, device: bool = False):
@@ -1408,7 +1401,7 @@ class SPHFluidGPU:
         columns 0:3 normal, 3 offsetRatio, 4 crest, 5 / 6 count / flags as bits (view(torch.int32)) -- and ids (numShell,) int32)."""
         self._push_params()
         info = SphShellInfo()
-        cfg = shell_config(radius=0.0 if radius is None else radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+        cfg = _shell_cfg(radius, offset, min_count, fluid_only)
         _check(self._L.sph_shell_build(self._h, C.byref(cfg), C.byref(info)))
         return self.shell_rows(device)
 
@@ -1416,14 +1409,10 @@ class SPHFluidGPU:
         """The same first pass around (m, 3) or (m, 4) query points (a torch device tensor of (m, 4) float32 is used in place): row i is
         the record of points[i] (no own slot is left out, crest is 0), ids lists the flagged points.  A smooth surface normal at a ray
         hit or a mesh vertex.  A point with a non-finite coordinate has an all-zero row."""
-        import torch
-        if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
-            dev = points
-        else:
-            dev = torch.from_numpy(_points4(points, "query_shell", keep_w=False)).cuda()
+        dev = _device_points4(points, "query_shell")
         self._push_params()
         info = SphShellInfo()
-        cfg = shell_config(radius=radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+        cfg = _shell_cfg(float(radius), offset, min_count, fluid_only)                   # (no default radius for a query: None is a TypeError)
         m = int(dev.shape[0])
         _check(self._L.sph_shell_query(self._h, C.c_void_p(dev.data_ptr()) if m else None, m, C.byref(cfg), C.byref(info)))
         return self.shell_rows(device)
@@ -1431,24 +1420,14 @@ class SPHFluidGPU:
     def shell_info(self) -> SphShellInfo:
         """What the engine's free-surface rows hold: rows, numShell, numIsolated, maxCount, radius, stencil, kind (1 particles, 2 query),
         flags.  SphError before any shell() / query_shell() call."""
-        info = SphShellInfo()
-        _check(self._L.sph_shell_info(self._h, C.byref(info)))
-        return info
+        return self._info(SphShellInfo, self._L.sph_shell_info)
 
     def shell_rows(self, device: bool = False):
         """(rows, ids) of the free-surface rows the engine holds."""
         info = self.shell_info()
         rows, ns = int(info.rows), int(info.numShell)
-        if device:
-            import torch
-            z = torch.empty((rows, 8), dtype=torch.float32, device="cuda")          # (one device copy of the 32-byte rows)
-            ids = torch.empty(ns, dtype=torch.int32, device="cuda")
-            _check(self._L.sph_shell_download(self._h, C.c_void_p(z.data_ptr()) if rows else None, C.c_void_p(ids.data_ptr()) if ns else None))
-            return z, ids
-        out = np.zeros(rows, SHELL_DTYPE)
-        ids = np.zeros(ns, np.int32)
-        _check(self._L.sph_shell_download(self._h, _ptr(out) if rows else None, _ptr(ids) if ns else None))
-        return out, ids
+        spec = ((rows, 8), None, "float32") if device else (rows, SHELL_DTYPE, None)    # (one device copy of the 32-byte rows)
+        return _fetch(lambda p_rows, p_ids: self._L.sph_shell_download(self._h, p_rows, p_ids), device, (spec, (ns, np.int32, "int32")))
 
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
@@ -2043,21 +2022,32 @@ def diffuse_step_host(config, params, pool, samples, particles, substep: int, dt
     return out[:n.value].copy(), _info_dict(info)
 
 
+_NO_POINT = np.zeros((1, 4), np.float32)                                            # somewhere for the pointer of an empty query to point
+
+
+def _host_args(records, params, query, if_empty=None):
+    """What the host twins of the queries begin with: (number of result rows, (records, n, params, query, m)).  query: the (m, 4)
+    points or (m, 8) rays, or None for one row per record (a null pointer, m = 0); the pointer of an empty query is that of `if_empty`
+    (None: null).  The pointers keep their arrays alive."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    if query is None:
+        return len(rec), (_ptr_or_none(rec), len(rec), C.byref(params), None, 0)
+    at = query if len(query) else if_empty
+    return len(query), (_ptr_or_none(rec), len(rec), C.byref(params), None if at is None else _ptr(at), len(query))
+
+
 def neighbors_host(records, params, radius, points=None, self_=False, half=False, count_only=False):
     """sph_neighbors_host: (offsets, indices) of SPHFluidGPU.neighbors (points None) or query_neighbors on host records, computed on the
     CPU by the same accept function over a counting sort of its own.  No device is needed."""
     L = load_library()
-    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
     p4 = None if points is None else _points4(points, "neighbors_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=p4)                           # (null means "no query points": an empty array stays one)
     flags = _neighbor_flags(self_, half, count_only)
-    rows = len(rec) if p4 is None else len(p4)
     off = np.zeros(rows + 1, np.int64)
     info = SphNeighborInfo()
-    pp = _ptr(p4) if p4 is not None else None
 
     def call(fl, idx, cap):
-        return L.sph_neighbors_host(_ptr(rec) if len(rec) else None, len(rec), C.byref(params), pp, rows if p4 is not None else 0, float(radius), fl,
-                                    _ptr(off), _ptr(idx) if idx is not None else None, cap, C.byref(info))
+        return L.sph_neighbors_host(*head, float(radius), fl, _ptr(off), _ptr(idx) if idx is not None else None, cap, C.byref(info))
     _check(call(flags | SPH_NEIGHBORS_COUNT_ONLY, None, 0))
     if count_only:
         return off, None
@@ -2081,17 +2071,14 @@ def components_host(records, params, radius, fluid_only: bool = False):
 def knn_host(records, params, k, radius, points=None, self_=False, fluid_only=False):
     """sph_knn_host: (idx, d2, counts, info) of SPHFluidGPU.knn (points None) or query_knn on host records, computed on the CPU: the
     counting sort of neighbors_host, the same r2, per row the accepted keys sorted and cut at k.  No device is needed."""
-    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
     p4 = None if points is None else _points4(points, "knn_host", keep_w=False)
-    rows = len(rec) if p4 is None else len(p4)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)                    # (non-null: query rows, also for m = 0)
     kk = int(k)
     width = kk if 1 <= kk <= SPH_KNN_MAX_K else 1                                    # (a refused k writes nothing)
     idx, d2, cnt = np.zeros((rows, width), np.int32), np.zeros((rows, width), np.float32), np.zeros(rows, np.uint32)
     info = SphKnnInfo()
-    pp = None if p4 is None else _ptr(p4 if len(p4) else np.zeros((1, 4), np.float32))   # (non-null: query rows, also for m = 0)
-    _check(load_library().sph_knn_host(_ptr_or_none(rec), len(rec), C.byref(params), pp, rows if p4 is not None else 0, kk, float(radius),
-                                       _knn_flags(self_, fluid_only), _ptr(idx) if rows else None, _ptr(d2) if rows else None,
-                                       _ptr(cnt) if rows else None, C.byref(info)))
+    _check(load_library().sph_knn_host(*head, kk, float(radius), _knn_flags(self_, fluid_only), _ptr_or_none(idx), _ptr_or_none(d2), _ptr_or_none(cnt),
+                                       C.byref(info)))
     return idx, d2, cnt, info
 
 
@@ -2102,20 +2089,21 @@ def shell_config(**overrides) -> SphShellConfig:
     return _copy_config(cfg, overrides)
 
 
+def _shell_cfg(radius, offset, min_count, fluid_only) -> SphShellConfig:
+    """The config of shell(), query_shell() and shell_host(); radius None goes as 0: the library's default, param_h."""
+    return shell_config(radius=0.0 if radius is None else radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
+
+
 def shell_host(records, params, radius=None, offset=0.10, min_count=0, fluid_only=False, points=None, sums=False):
     """sph_shell_host: (rows, ids, info) of SPHFluidGPU.shell (points None) or query_shell on host records, computed on the CPU by the
     device's own per-candidate, finish and crest functions over the counting sort of neighbors_host, in the same order: the same bytes.
     sums=True adds the (rows, 4) float32 sums of pass 1 (Sx, Sy, Sz, W) the rows were finished from.  No device is needed."""
-    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
     p4 = None if points is None else _points4(points, "shell_host", keep_w=False)
-    rows = len(rec) if p4 is None else len(p4)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)                    # (non-null: query rows, also for m = 0)
     out, ids, acc = np.zeros(rows, SHELL_DTYPE), np.zeros(rows, np.int32), np.zeros((rows, 4), np.float32)
     info = SphShellInfo()
-    cfg = shell_config(radius=0.0 if radius is None else radius, offset=offset, minCount=min_count, flags=SPH_SHELL_FLUID_ONLY if fluid_only else 0)
-    pp = None if p4 is None else _ptr(p4 if len(p4) else np.zeros((1, 4), np.float32))   # (non-null: query rows, also for m = 0)
-    _check(load_library().sph_shell_host(_ptr_or_none(rec), len(rec), C.byref(params), pp, rows if p4 is not None else 0, C.byref(cfg),
-                                         _ptr(out) if rows else None, _ptr(ids) if rows else None, _ptr(acc) if sums and rows else None,
-                                         C.byref(info)))
+    cfg = _shell_cfg(radius, offset, min_count, fluid_only)
+    _check(load_library().sph_shell_host(*head, C.byref(cfg), _ptr_or_none(out), _ptr_or_none(ids), _ptr_or_none(acc) if sums else None, C.byref(info)))
     res = (out, ids[:int(info.numShell)].copy(), info)
     return res + (acc,) if sums else res
 
@@ -2124,13 +2112,11 @@ def rays_host(records, params, rays, radius, fluid_only=False, any_hit=False, wi
     """sph_rays_host: (t, ids, pos, normal) of SPHFluidGPU.raycast on host records, computed on the CPU by brute force over all
     participating records with the same hit arithmetic: the definition of a cast.  with_info adds the SphRaysInfo.  walk=True runs
     sph_rays_walk_host in its place: the device's grid walk, on the host.  No device is needed."""
-    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
-    r8 = _rays8(rays, "rays_host")
-    hits = np.zeros(len(r8), RAY_HIT_DTYPE)
+    rows, head = _host_args(records, params, _rays8(rays, "rays_host"))
+    hits = np.zeros(rows, RAY_HIT_DTYPE)
     info = SphRaysInfo()
     L = load_library()
-    _check((L.sph_rays_walk_host if walk else L.sph_rays_host)(_ptr_or_none(rec), len(rec), C.byref(params), _ptr_or_none(r8), len(r8),
-                                                                   float(radius), _rays_flags(fluid_only, any_hit), _ptr_or_none(hits), C.byref(info)))
+    _check((L.sph_rays_walk_host if walk else L.sph_rays_host)(*head, float(radius), _rays_flags(fluid_only, any_hit), _ptr_or_none(hits), C.byref(info)))
     out = _split_hits(hits)
     return out + (info,) if with_info else out
 

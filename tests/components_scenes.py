@@ -2,18 +2,10 @@
 walk can go wrong.  scenes(pkg) yields (name, records, params, radius, expected number of bodies or None)."""
 import numpy as np
 
+from query_scenes import grid, params  # noqa: F401  (the box of 4 x 3 x 3.5 at h = 0.5; CS.params is what the test files call)
 from support import records
 
 F = np.float32
-
-
-def params(pkg, h=0.5, cap=160):
-    return pkg.default_params(param_h=h, param_boxHalf=(2.0, 1.5, 1.75), param_boxCenter=(0.25, -0.5, 0.125), grid_cap=cap)
-
-
-def grid(pkg, sp):
-    g = pkg.compute_grid_extents(sp)
-    return np.array(list(g.gridMin), F), np.array(list(g.dims), np.int64), F(g.cellSize)
 
 
 def rec_of(pkg, pos, ghost=None):

@@ -1,7 +1,9 @@
-"""Scenes shared by the k-nearest-neighbour tests (test_knn_cpu.py, test_gpu_knn.py): a box of 4 x 3 x 3.5 at h = 0.5 as the neighbour
-list tests use it, uniform clouds, the exact lattice, coincident particles and ghosts of every kind."""
+"""Scenes shared by the tests of the spatial queries (neighbour lists, components, k nearest neighbours, ray casts, free-surface shell,
+on the CPU and on the device): a box of 4 x 3 x 3.5 at h = 0.5, uniform clouds, the exact lattice, coincident particles, ghosts of every
+kind, the crowded cell and the query cloud with its three non-finite rows."""
 import numpy as np
 
+import neighbors_ref as NR
 from support import records
 
 F = np.float32
@@ -63,3 +65,35 @@ def with_ghosts(pkg, n=1200, seed=13):
     rec["isGhost"] = np.where(i % 3 == 0, np.where(i % 2 == 0, 1, 3), 0)
     rec["isActive"] = (i % 4 != 0)
     return rec, sp
+
+
+def crowded_cell(pkg, crowd):
+    """`crowd` particles inside cell (3, 2, 4) behind 400 uniform ones: (records, params, start, members), the cell's run of sorted
+    slots (its first slot and its length, the background's share included).  The generator is seeded with `crowd`."""
+    rng = np.random.default_rng(crowd)
+    sp = params(pkg)
+    lo, dims, cs = grid(pkg, sp)
+    cell = np.array([3, 2, 4])
+    assert (cell + 1 < dims).all()
+    inside = lo + (cell.astype(F) + F(0.05) + F(0.9) * rng.random((crowd, 3)).astype(F)) * cs
+    pos = np.concatenate([grid_cloud(rng, (lo, dims, cs), 400), inside])
+    rec = records(pkg, pos, np.zeros_like(pos))
+    c = NR.cells(pkg, rec["pos"], sp)
+    mine = (cell[2] * dims[1] + cell[1]) * dims[0] + cell[0]
+    start, members = int((c < mine).sum()), int((c == mine).sum())
+    return rec, sp, start, members
+
+
+def query_cloud(pkg, m=701):
+    """1500 particles up to a tenth of the grid's extent beyond its faces and m query points up to 0.3 of it beyond them (701 is no
+    multiple of 64), with NaN, +inf and -inf in rows 5, 256 and m - 1: (records, params, points)."""
+    rng = np.random.default_rng(8)
+    sp = params(pkg)
+    g = grid(pkg, sp)
+    pos = grid_cloud(rng, g, 1500, beyond=0.1)
+    rec = records(pkg, pos, np.zeros_like(pos))
+    pts = grid_cloud(rng, g, m, beyond=0.3)
+    pts[5, 0] = np.nan
+    pts[256, 1] = np.inf
+    pts[m - 1, 2] = -np.inf
+    return rec, sp, pts

@@ -1,12 +1,12 @@
-"""Scenes and rays shared by the ray-cast tests (test_rays_cpu.py, test_gpu_rays.py, test_gpu_fuzz_rays.py): the kNN tests' box of
-4 x 3 x 3.5 at h = 0.5 with its uniform clouds, exact lattice, coincident eight and ghost mix, plus a lattice that fills the whole grid
-and the families of rays that can go wrong in a grid walk."""
+"""Scenes and rays shared by the ray-cast tests (test_rays_cpu.py, test_gpu_rays.py, test_gpu_fuzz_rays.py): the box of 4 x 3 x 3.5
+at h = 0.5 of query_scenes.py with its uniform clouds, exact lattice, coincident eight and ghost mix, plus a lattice that fills the
+whole grid and the families of rays that can go wrong in a grid walk."""
 from importlib import import_module
 
 import numpy as np
 
 from conftest import PKG_NAME
-from knn_scenes import box_cloud, coincident, grid, grid_cloud, lattice, params, uniform, with_ghosts  # noqa: F401
+from query_scenes import box_cloud, coincident, grid, grid_cloud, lattice, params, uniform, with_ghosts  # noqa: F401
 from support import records
 
 F = np.float32

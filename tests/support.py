@@ -1,7 +1,10 @@
 """Helpers shared by the test modules (imported like the *_ref.py modules): building and running the C++ examples, the C99 layout
-program behind the ctypes mirrors, the bitwise and impulse comparisons, and the engine set-ups several GPU test files use."""
+program behind the ctypes mirrors, the bitwise and impulse comparisons, the engine set-ups several GPU test files use, and what the
+GPU tests of every spatial query repeat (same_info, after_dispatches, the two refusing engines)."""
 import os
 import subprocess
+from contextlib import contextmanager
+from importlib import import_module
 
 import numpy as np
 
@@ -202,3 +205,49 @@ def undisturbed_run(pkg, rec, sp, probe, aos=1, graph=0):
     launches = f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES)
     f.close()
     return after_upload, out, launches
+
+
+# ---- the spatial queries: what every family's GPU tests repeat --------------------------------------
+def same_info(info, want, fields, what):
+    """The named fields of two info structs are equal."""
+    assert [getattr(info, a) for a in fields] == [getattr(want, a) for a in fields], what
+
+
+def after_dispatches(pkg, kern, aos, graph, check, unchanged, scene=None):
+    """The "a query on a state the engine produced" scenario: an engine for (kern, aos, graph) on `scene` (records, params; None: the
+    small scene of 4096), four DispatchN(3) (a graph is captured once a call repeats, then replayed), the download, the family's
+    check(engine, records now, params, what), one more DispatchN(3) and the family's unchanged(engine, what check returned): a result
+    describes the state it was built from."""
+    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3) if scene is None else scene
+    f = engine(pkg, rec, sp, kern, aos, graph)
+    for _ in range(4):
+        f.DispatchN(3)
+    if graph:
+        assert f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES) >= 1
+    now = f.download()
+    held = check(f, now, sp, f"kernel {kern} aos {aos} graph {graph}")
+    f.DispatchN(3)
+    unchanged(f, held)
+    f.close()
+
+
+@contextmanager
+def slab_engine(pkg, rec, sp):
+    """The first of the two engines every query refuses with -3: a slab engine (here one slab over the whole grid), closed on exit."""
+    halo = import_module(pkg.__name__ + ".halo")
+    g = pkg.compute_grid_extents(sp)
+    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
+    try:
+        yield slab
+    finally:
+        slab.close()
+
+
+@contextmanager
+def linked_list_grid(pkg, f):
+    """The second: the caller's engine while its grid is built as linked lists (SPH_OPT_GRID_BUILD 1), the option put back on exit."""
+    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
+    try:
+        yield f
+    finally:
+        f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)

@@ -2,7 +2,6 @@
 rounds) on the scenes of components_scenes.py, against the restatement where the margin allows, against the engine's own neighbour
 lists, on states the engine produced, and the interface around them."""
 import ctypes as C
-from importlib import import_module
 
 import numpy as np
 import pytest
@@ -10,7 +9,7 @@ import pytest
 from conftest import assert_records_equal, small_scene
 import components_ref as CR
 import components_scenes as CS
-from support import build_example, engine, run_example, undisturbed_run
+from support import after_dispatches, build_example, linked_list_grid, run_example, same_info, slab_engine, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -29,7 +28,7 @@ def _same(pkg, f, rec, sp, R, fluid_only=False, what=""):
     assert labels.tobytes() == wl.tobytes(), f"{what}: labels differ"
     assert roots.tobytes() == wr.tobytes(), f"{what}: roots differ"
     assert table.tobytes() == wt.tobytes(), f"{what}: tables differ"
-    assert [getattr(info, k) for k in INFO_FIELDS] == [getattr(winfo, k) for k in INFO_FIELDS], what
+    same_info(info, winfo, INFO_FIELDS, what)
     assert (1 <= info.rounds < ROUND_CAP) if len(rec) else info.rounds == 0
     return labels, roots, table, info
 
@@ -102,22 +101,23 @@ def test_after_dispatches(pkg, kern, aos, graph):
     """On a state the engine produced: the components of the downloaded records, twice the same bytes, still there after a dispatch."""
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
     rec["isGhost"][::37] = 1
-    f = engine(pkg, rec, sp, kern, aos, graph)
-    for _ in range(4):
-        f.DispatchN(3)
-    now = f.download()
-    for fac, fluid_only in ((0.6, False), (1.0, True), (2.0, False)):
-        R = float(F(fac) * F(sp.param_h))
-        first = _same(pkg, f, now, sp, R, fluid_only=fluid_only, what=f"kernel {kern} aos {aos} graph {graph} R {fac} h")
-        again = f.components(R, fluid_only=fluid_only)
-        assert all(a.tobytes() == b.tobytes() for a, b in zip(first[:3], again))
-    f.DispatchN(3)                                                                 # the result describes the state it was built from
-    info = f.component_info()
-    assert info.numComponents == first[3].numComponents
-    L = pkg.load_library()
-    lab = np.zeros(len(rec), np.int32)
-    assert L.sph_components_download(f._h, lab.ctypes.data_as(vp), None, None, 0) == 0 and lab.tobytes() == first[0].tobytes()
-    f.close()
+
+    def check(f, now, sp, what):
+        for fac, fluid_only in ((0.6, False), (1.0, True), (2.0, False)):
+            R = float(F(fac) * F(sp.param_h))
+            first = _same(pkg, f, now, sp, R, fluid_only=fluid_only, what=f"{what} R {fac} h")
+            again = f.components(R, fluid_only=fluid_only)
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(first[:3], again))
+        return first
+
+    def unchanged(f, first):                                                       # the result describes the state it was built from
+        info = f.component_info()
+        assert info.numComponents == first[3].numComponents
+        L = pkg.load_library()
+        lab = np.zeros(len(rec), np.int32)
+        assert L.sph_components_download(f._h, lab.ctypes.data_as(vp), None, None, 0) == 0 and lab.tobytes() == first[0].tobytes()
+
+    after_dispatches(pkg, kern, aos, graph, check, unchanged, scene=(rec, sp))
 
 
 def test_components_do_not_change_the_simulation(pkg):
@@ -140,11 +140,8 @@ def test_refusals_and_states(pkg):
     L = pkg.load_library()
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
     info = pkg.SphComponentInfo()
-    halo = import_module(pkg.__name__ + ".halo")
-    g = pkg.compute_grid_extents(sp)
-    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
-    assert L.sph_components_build(slab._h, sp.param_h, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
-    slab.close()
+    with slab_engine(pkg, rec, sp) as slab:
+        assert L.sph_components_build(slab._h, sp.param_h, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     n = len(rec)
     labels, roots, table = np.full(n, 9, np.int32), np.full(n, 9, np.int32), np.zeros(n, pkg.COMPONENT_DTYPE)
@@ -157,10 +154,9 @@ def test_refusals_and_states(pkg):
         with pytest.raises(pkg.SphError, match="-3"):
             f.component_info()
     nothing_held()                                                                 # before any build
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.components()
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)
+    with linked_list_grid(pkg, f):
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.components()
     nothing_held()
     for R in (0.0, -1.0, float("nan"), float("inf"), 3.01 * sp.param_h):
         assert L.sph_components_build(f._h, R, 0, C.byref(info)) == -1

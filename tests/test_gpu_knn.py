@@ -2,15 +2,14 @@
 for the default kernel (LDS rows) AND the selection kernel (SPH_OPT_KNN_VARIANT 1), on the smallest shapes where they can go wrong; the
 interface around them; and the proof that a build changes neither the simulation nor the other query results."""
 import ctypes as C
-from importlib import import_module
 
 import numpy as np
 import pytest
 
 from conftest import assert_records_equal, small_scene
-import knn_scenes as KS
 import neighbors_ref as NR
-from support import build_example, engine, records, run_example, undisturbed_run
+import query_scenes as QS
+from support import after_dispatches, build_example, linked_list_grid, records, run_example, same_info, slab_engine, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -37,8 +36,7 @@ def _same(pkg, f, rec, sp, k, R, points=None, dev_points=None, what="", **kw):
         else:
             got = f.query_knn(points if dev_points is None else dev_points, k, R, **kw)
         _equal(got, want, f"{what} k {k} R {R} {kw} variant {variant}")
-        info = f.knn_info()
-        assert [getattr(info, a) for a in INFO_FIELDS] == [getattr(want[3], a) for a in INFO_FIELDS], f"{what} k {k} R {R} variant {variant}"
+        same_info(f.knn_info(), want[3], INFO_FIELDS, f"{what} k {k} R {R} variant {variant}")
     f.set_option(pkg.SPH_OPT_KNN_VARIANT, 0)
     return want
 
@@ -51,17 +49,7 @@ def _h(sp, fac):
 def test_crowded_cell(pkg, crowd):
     """A cell with 63 / 64 / 65 / 300 members among 400 others: far more accepted candidates than any row keeps, in one run of sorted
     slots (300: a run that crosses a block boundary of every class), so a full row is overwritten many times."""
-    rng = np.random.default_rng(crowd)
-    sp = KS.params(pkg)
-    lo, dims, cs = KS.grid(pkg, sp)
-    cell = np.array([3, 2, 4])
-    assert (cell + 1 < dims).all()
-    inside = lo + (cell.astype(F) + F(0.05) + F(0.9) * rng.random((crowd, 3)).astype(F)) * cs
-    pos = np.concatenate([KS.grid_cloud(rng, (lo, dims, cs), 400), inside])
-    rec = records(pkg, pos, np.zeros_like(pos))
-    c = NR.cells(pkg, rec["pos"], sp)
-    mine = (cell[2] * dims[1] + cell[1]) * dims[0] + cell[0]
-    start, members = int((c < mine).sum()), int((c == mine).sum())
+    rec, sp, start, members = QS.crowded_cell(pkg, crowd)
     assert members >= crowd
     if crowd == 300:
         assert start // 256 != (start + members - 1) // 256, "the cell's run must cross a block boundary of sorted slots"
@@ -77,7 +65,7 @@ def test_crowded_cell(pkg, crowd):
 
 @pytest.mark.parametrize("fac", [1.0, 2.0, 3.0, 1.3])
 def test_every_class_edge_and_radius_class(pkg, fac):
-    rec, sp = KS.uniform(pkg, 1200, seed=31)
+    rec, sp = QS.uniform(pkg, 1200, seed=31)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     R = _h(sp, fac)
     res = {}
@@ -103,11 +91,11 @@ def test_edge_corner_and_clamped_cells(pkg):
     """Members of every corner cell and particles up to 30 % of the box beyond every face (clamped cells): the stencil is cut at the
     grid's faces, and far-away particles share a clamped cell."""
     rng = np.random.default_rng(2)
-    sp = KS.params(pkg)
-    lo, dims, cs = KS.grid(pkg, sp)
+    sp = QS.params(pkg)
+    lo, dims, cs = QS.grid(pkg, sp)
     corners = np.array([[x, y, z] for x in (0, dims[0] - 1) for y in (0, dims[1] - 1) for z in (0, dims[2] - 1)])
     corner_pos = lo + (np.repeat(corners, 6, axis=0).astype(F) + rng.random((48, 3)).astype(F)) * cs
-    pos = np.concatenate([KS.grid_cloud(rng, (lo, dims, cs), 1500, beyond=0.3), corner_pos])
+    pos = np.concatenate([QS.grid_cloud(rng, (lo, dims, cs), 1500, beyond=0.3), corner_pos])
     rec = records(pkg, pos, np.zeros_like(pos))
     assert not NR.inside_grid(pkg, rec["pos"], sp)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
@@ -115,9 +103,9 @@ def test_edge_corner_and_clamped_cells(pkg):
         _same(pkg, f, rec, sp, k, _h(sp, fac), what="clamped")
     _same(pkg, f, rec, sp, 16, _h(sp, 2.0), self_=True, what="clamped")
     # a grid of 4 x 4 x 4 cells around a much larger box: s = 3 covers the whole grid from the middle cells, most particles are clamped
-    small = KS.params(pkg, cap=4)
+    small = QS.params(pkg, cap=4)
     assert list(pkg.compute_grid_extents(small).dims) == [4, 4, 4]
-    pos = KS.grid_cloud(rng, (lo, dims, cs), 700)
+    pos = QS.grid_cloud(rng, (lo, dims, cs), 700)
     rec = records(pkg, pos, np.zeros_like(pos))
     g = pkg.SPHFluidGPU.from_particles(rec, small)
     for k, fac in ((8, 1.0), (64, 3.0)):
@@ -128,14 +116,14 @@ def test_edge_corner_and_clamped_cells(pkg):
 
 def test_tie_order_on_the_device(pkg):
     """The exact lattice (whole shells tie) and eight coincident particles (runs of r2 = 0): ties resolve by id on the device too."""
-    rec, sp = KS.lattice(pkg)
+    rec, sp = QS.lattice(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for k, R in ((6, 0.5), (7, 0.5), (19, 1.0), (64, 1.0)):
         idx, d2, cnt, _ = _same(pkg, f, rec, sp, k, R, what="lattice")
         tied = (d2[:, 1:] == d2[:, :-1]) & np.isfinite(d2[:, 1:])
         assert tied.any() and (idx[:, 1:][tied] > idx[:, :-1][tied]).all()
     f.close()
-    rec, sp, same = KS.coincident(pkg)
+    rec, sp, same = QS.coincident(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for k in (4, 8, 16):
         idx, d2, _, _ = _same(pkg, f, rec, sp, k, 1.0, self_=True, what="coincident")
@@ -147,19 +135,19 @@ def test_tie_order_on_the_device(pkg):
 
 def test_short_rows_ghosts_and_non_finite_particles(pkg):
     # a sparse background: most rows shorter than k, padded; k > n
-    rec, sp = KS.uniform(pkg, 150, seed=32)
+    rec, sp = QS.uniform(pkg, 150, seed=32)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for k, fac in ((8, 1.0), (16, 2.0), (64, 3.0)):
         idx, d2, cnt, info = _same(pkg, f, rec, sp, k, _h(sp, fac), what="sparse")
         assert (cnt < k).any() and (idx[np.arange(k)[None, :] >= cnt[:, None]] == -1).all()
     f.close()
-    rec, sp = KS.uniform(pkg, 20, seed=25)
+    rec, sp = QS.uniform(pkg, 20, seed=25)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     want = _same(pkg, f, rec, sp, 64, 1.5, what="k > n")
     assert want[3].rowsFull == 0 and want[3].total > 0
     f.close()
     # ghosts of every kind, inactive records: candidates like any other, unless FLUID_ONLY
-    rec, sp = KS.with_ghosts(pkg)
+    rec, sp = QS.with_ghosts(pkg)
     ghost = rec["isGhost"] != 0
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for kw in (dict(), dict(fluid_only=True), dict(fluid_only=True, self_=True)):
@@ -170,7 +158,7 @@ def test_short_rows_ghosts_and_non_finite_particles(pkg):
     _same(pkg, f, rec, sp, 8, 1.0, points=rec["pos"][:333, :3], fluid_only=True, what="ghosts, query")
     f.close()
     # non-finite positions: accepted by nobody, an empty row also under SELF
-    rec, sp = KS.uniform(pkg, 1000, seed=23)
+    rec, sp = QS.uniform(pkg, 1000, seed=23)
     rec["pos"][7, 0] = np.nan
     rec["pos"][300, 2] = np.inf
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
@@ -181,7 +169,7 @@ def test_short_rows_ghosts_and_non_finite_particles(pkg):
 
 
 def test_degenerate_engines(pkg):
-    sp = KS.params(pkg)
+    sp = QS.params(pkg)
     none = np.zeros(0, pkg.PARTICLE_DTYPE)
     f = pkg.SPHFluidGPU.from_particles(none, sp)
     want = _same(pkg, f, none, sp, 8, 1.0, what="n = 0")
@@ -200,7 +188,7 @@ def test_degenerate_engines(pkg):
     f.close()
     # all particles in one cell
     rng = np.random.default_rng(33)
-    lo, dims, cs = KS.grid(pkg, sp)
+    lo, dims, cs = QS.grid(pkg, sp)
     pos = lo + (np.array([4, 3, 3], F) + F(0.02) + F(0.96) * rng.random((300, 3)).astype(F)) * cs
     rec = records(pkg, pos, np.zeros_like(pos))
     assert len(np.unique(NR.cells(pkg, rec["pos"], sp))) == 1
@@ -212,15 +200,7 @@ def test_degenerate_engines(pkg):
 
 def test_query_rows(pkg):
     import torch
-    rng = np.random.default_rng(8)
-    sp = KS.params(pkg)
-    grid = KS.grid(pkg, sp)
-    pos = KS.grid_cloud(rng, grid, 1500, beyond=0.1)
-    rec = records(pkg, pos, np.zeros_like(pos))
-    pts = KS.grid_cloud(rng, grid, 701, beyond=0.3)                               # inside and outside the grid; 701 is no multiple of 64
-    pts[5, 0] = np.nan
-    pts[256, 1] = np.inf
-    pts[700, 2] = -np.inf
+    rec, sp, pts = QS.query_cloud(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for k, fac in ((8, 1.0), (17, 2.0), (64, 3.0)):
         idx, d2, cnt, info = _same(pkg, f, rec, sp, k, _h(sp, fac), points=pts, what="query")
@@ -236,18 +216,14 @@ def test_query_rows(pkg):
 @pytest.mark.parametrize("kern,aos,graph", [(3, 1, 0), (1, 1, 0), (3, 0, 0), (3, 1, 1)])
 def test_after_dispatches(pkg, kern, aos, graph):
     """On a state the engine produced: the rows are those of the downloaded records, and a later dispatch does not touch them."""
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
-    f = engine(pkg, rec, sp, kern, aos, graph)
-    for _ in range(4):
-        f.DispatchN(3)
-    if graph:
-        assert f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES) >= 1
-    now = f.download()
-    _same(pkg, f, now, sp, 8, _h(sp, 1.0), what=f"kernel {kern} aos {aos} graph {graph}")
-    want = _same(pkg, f, now, sp, 33, _h(sp, 2.0), what=f"kernel {kern} aos {aos} graph {graph}")
-    f.DispatchN(3)
-    _equal(f.knn_rows(), want, "after a dispatch")
-    f.close()
+    def check(f, now, sp, what):
+        _same(pkg, f, now, sp, 8, _h(sp, 1.0), what=what)
+        return _same(pkg, f, now, sp, 33, _h(sp, 2.0), what=what)
+
+    def unchanged(f, want):
+        _equal(f.knn_rows(), want, "after a dispatch")
+
+    after_dispatches(pkg, kern, aos, graph, check, unchanged)
 
 
 def test_device_tensors_and_knn_graph(pkg):
@@ -320,12 +296,9 @@ def test_refusals_and_states(pkg):
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
     info = pkg.SphKnnInfo()
     pts = torch.zeros(16, dtype=torch.float32, device="cuda")
-    halo = import_module(pkg.__name__ + ".halo")
-    g = pkg.compute_grid_extents(sp)
-    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
-    assert L.sph_knn_build(slab._h, 8, sp.param_h, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
-    assert L.sph_knn_query(slab._h, vp(pts.data_ptr()), 4, 8, sp.param_h, 0, C.byref(info)) == -3
-    slab.close()
+    with slab_engine(pkg, rec, sp) as slab:
+        assert L.sph_knn_build(slab._h, 8, sp.param_h, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
+        assert L.sph_knn_query(slab._h, vp(pts.data_ptr()), 4, 8, sp.param_h, 0, C.byref(info)) == -3
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     n = len(rec)
     idx, d2, cnt = np.full((n, 8), 9, np.int32), np.zeros((n, 8), F), np.zeros(n, np.uint32)
@@ -339,12 +312,11 @@ def test_refusals_and_states(pkg):
             f.knn_info()
         assert (idx == 9).all()
     nothing_held()                                                                 # before any build
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.knn(8)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.query_knn(rec["pos"][:4, :3], 8, sp.param_h)
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)
+    with linked_list_grid(pkg, f):
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.knn(8)
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.query_knn(rec["pos"][:4, :3], 8, sp.param_h)
     nothing_held()
     for R in (0.0, -1.0, float("nan"), float("inf"), 3.01 * sp.param_h):
         assert L.sph_knn_build(f._h, 8, R, 0, C.byref(info)) == -1

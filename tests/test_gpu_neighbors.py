@@ -1,28 +1,19 @@
 """Neighbour lists on the device (sph_neighbors.h) against sph_neighbors_host, bit for bit in offsets and indices, on the smallest
 shapes where the kernels can go wrong; the interface around them; and the proof that building lists never changes the simulation."""
 import ctypes as C
-from importlib import import_module
 
 import numpy as np
 import pytest
 
 from conftest import assert_records_equal, small_scene
 import neighbors_ref as NR
-from support import build_example, engine, records, run_example, undisturbed_run
+import query_scenes as QS
+from support import after_dispatches, build_example, linked_list_grid, records, run_example, slab_engine, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 vp = C.c_void_p
 FLAG_SETS = (dict(), dict(self_=True), dict(half=True), dict(count_only=True), dict(self_=True, count_only=True))
-
-
-def _params(pkg, h=0.5, half=(2.0, 1.5, 1.75), cap=160):
-    return pkg.default_params(param_h=h, param_boxHalf=half, param_boxCenter=(0.25, -0.5, 0.125), grid_cap=cap)
-
-
-def _grid(pkg, sp):
-    g = pkg.compute_grid_extents(sp)
-    return np.array(list(g.gridMin), F), np.array(list(g.dims), np.int64), F(g.cellSize)
 
 
 def _same(got, want, what):
@@ -56,27 +47,11 @@ def _check(pkg, rec, sp, **kw):
     f.close()
 
 
-def _background(rng, sp_grid, n, beyond=0.0):
-    lo, dims, cs = sp_grid
-    ext = dims.astype(F) * cs
-    return lo + (rng.random((n, 3)).astype(F) * F(1.0 + 2.0 * beyond) - F(beyond)) * ext
-
-
 @pytest.mark.parametrize("crowd", [63, 64, 65, 200, 300])
 def test_crowded_cell(pkg, crowd):
     """A cell with more members than a wave (63 / 64 / 65) and than a block (300: its run of sorted slots crosses a block boundary),
     among a few hundred others: rows longer than a wave and than a block, targets of one block in many cells."""
-    rng = np.random.default_rng(crowd)
-    sp = _params(pkg)
-    lo, dims, cs = _grid(pkg, sp)
-    cell = np.array([3, 2, 4])
-    assert (cell + 1 < dims).all()
-    inside = lo + (cell.astype(F) + F(0.05) + F(0.9) * rng.random((crowd, 3)).astype(F)) * cs
-    pos = np.concatenate([_background(rng, (lo, dims, cs), 400), inside])
-    rec = records(pkg, pos, np.zeros_like(pos))
-    c = NR.cells(pkg, rec["pos"], sp)
-    mine = (cell[2] * dims[1] + cell[1]) * dims[0] + cell[0]
-    start, members = int((c < mine).sum()), int((c == mine).sum())
+    rec, sp, start, members = QS.crowded_cell(pkg, crowd)
     assert members >= crowd
     if crowd == 300:
         assert start // 256 != (start + members - 1) // 256, "the cell's run must cross a block boundary of sorted slots"
@@ -87,11 +62,11 @@ def test_edge_corner_and_clamped_cells(pkg):
     """Members of every corner and edge cell, and particles up to 30 % of the box beyond every face (clamped cells): the stencil is cut
     at the grid's faces and the relation stays symmetric."""
     rng = np.random.default_rng(2)
-    sp = _params(pkg)
-    lo, dims, cs = _grid(pkg, sp)
+    sp = QS.params(pkg)
+    lo, dims, cs = QS.grid(pkg, sp)
     corners = np.array([[x, y, z] for x in (0, dims[0] - 1) for y in (0, dims[1] - 1) for z in (0, dims[2] - 1)])
     corner_pos = lo + (np.repeat(corners, 6, axis=0).astype(F) + rng.random((48, 3)).astype(F)) * cs
-    pos = np.concatenate([_background(rng, (lo, dims, cs), 1500, beyond=0.3), corner_pos])
+    pos = np.concatenate([QS.grid_cloud(rng, (lo, dims, cs), 1500, beyond=0.3), corner_pos])
     rec = records(pkg, pos, np.zeros_like(pos))
     assert not NR.inside_grid(pkg, rec["pos"], sp)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
@@ -104,8 +79,8 @@ def test_edge_corner_and_clamped_cells(pkg):
 
 def test_degenerate_engines(pkg):
     rng = np.random.default_rng(4)
-    sp = _params(pkg)
-    grid = _grid(pkg, sp)
+    sp = QS.params(pkg)
+    grid = QS.grid(pkg, sp)
     # one particle
     one = records(pkg, np.array([[0.2, -0.4, 0.1]], F), np.zeros((1, 3), F))
     _check(pkg, one, sp, what="n = 1")
@@ -116,7 +91,7 @@ def test_degenerate_engines(pkg):
     assert f.neighbors(count_only=True, device=True)[1] is None
     f.close()
     # ghosts and inactive records only: binned like any other record
-    pos = _background(rng, grid, 500)
+    pos = QS.grid_cloud(rng, grid, 500)
     ghosts = records(pkg, pos, np.zeros_like(pos), ghost=np.where(np.arange(500) % 3 == 0, 3, 1).astype(np.int32))
     ghosts["isActive"] = np.arange(500) % 2
     _check(pkg, ghosts, sp, what="ghosts")
@@ -133,16 +108,16 @@ def test_degenerate_engines(pkg):
     assert idx[off[7]:off[8]].tolist() == [7] and idx[off[300]:off[301]].tolist() == [300]
     f.close()
     # a grid of 4 x 4 x 4 cells around a much larger box: s = 3 covers the whole grid from the middle cells, most particles are clamped
-    small = _params(pkg, cap=4)
+    small = QS.params(pkg, cap=4)
     assert list(pkg.compute_grid_extents(small).dims) == [4, 4, 4]
-    pos = _background(rng, grid, 700)
+    pos = QS.grid_cloud(rng, grid, 700)
     _check(pkg, records(pkg, pos, np.zeros_like(pos)), small, what="grid_cap 4")
 
 
 def test_radius_classes_between_the_cell_multiples(pkg):
     rng = np.random.default_rng(6)
-    sp = _params(pkg)
-    pos = _background(rng, _grid(pkg, sp), 1200)
+    sp = QS.params(pkg)
+    pos = QS.grid_cloud(rng, QS.grid(pkg, sp), 1200)
     rec = records(pkg, pos, np.zeros_like(pos))
     up = float(np.nextafter(F(sp.param_h), F(np.inf))) / sp.param_h              # the first radius of class s = 2
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
@@ -158,32 +133,21 @@ def test_radius_classes_between_the_cell_multiples(pkg):
 def test_after_dispatches(pkg, kern, aos, graph):
     """On a state the engine produced (every SPH pass variant, lazy and eager records, a replayed graph): the lists are those of the
     downloaded records, and at R = h with SELF the degrees are the sampler's counts."""
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
-    f = engine(pkg, rec, sp, kern, aos, graph)
-    for _ in range(4):                                                             # (a graph is captured once a call repeats, then replayed)
-        f.DispatchN(3)
-    if graph:
-        assert f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES) >= 1
-    now = f.download()
-    _check_engine(pkg, f, now, sp, factors=(1.0, 2.0), flag_sets=(dict(), dict(half=True)), what=f"kernel {kern} aos {aos} graph {graph}")
-    off, idx = f.neighbors(self_=True)
-    assert np.array_equal(np.diff(off), f.sample(now["pos"][:, :3])["count"].astype(np.int64))
-    f.DispatchN(3)                                                                 # the lists describe the state they were built from
-    _same(f.neighbor_lists(), (off, idx), "after a dispatch")
-    f.close()
+    def check(f, now, sp, what):
+        _check_engine(pkg, f, now, sp, factors=(1.0, 2.0), flag_sets=(dict(), dict(half=True)), what=what)
+        off, idx = f.neighbors(self_=True)
+        assert np.array_equal(np.diff(off), f.sample(now["pos"][:, :3])["count"].astype(np.int64))
+        return off, idx
+
+    def unchanged(f, held):                                                        # the lists describe the state they were built from
+        _same(f.neighbor_lists(), held, "after a dispatch")
+
+    after_dispatches(pkg, kern, aos, graph, check, unchanged)
 
 
 def test_query_lists(pkg):
     import torch
-    rng = np.random.default_rng(8)
-    sp = _params(pkg)
-    grid = _grid(pkg, sp)
-    pos = _background(rng, grid, 1500, beyond=0.1)
-    rec = records(pkg, pos, np.zeros_like(pos))
-    pts = _background(rng, grid, 700, beyond=0.3)
-    pts[5, 0] = np.nan
-    pts[256, 1] = np.inf
-    pts[699, 2] = -np.inf
+    rec, sp, pts = QS.query_cloud(pkg, 700)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for fac in (1.0, 2.0, 3.0):
         R = float(F(fac) * F(sp.param_h))
@@ -312,20 +276,16 @@ def test_refused_on_slab_engines_and_linked_list_grid(pkg):
     rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
     info = pkg.SphNeighborInfo()
     pts = torch.zeros(16, dtype=torch.float32, device="cuda")
-    halo = import_module(pkg.__name__ + ".halo")
-    g = pkg.compute_grid_extents(sp)
-    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
-    assert L.sph_neighbors_build(slab._h, sp.param_h, 0, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
-    assert L.sph_neighbors_query(slab._h, vp(pts.data_ptr()), 4, sp.param_h, 0, 0, C.byref(info)) == -3
-    slab.close()
+    with slab_engine(pkg, rec, sp) as slab:
+        assert L.sph_neighbors_build(slab._h, sp.param_h, 0, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
+        assert L.sph_neighbors_query(slab._h, vp(pts.data_ptr()), 4, sp.param_h, 0, 0, C.byref(info)) == -3
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.neighbors()
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.query_neighbors(rec["pos"][:4, :3], sp.param_h)
-    assert f.neighbor_info().kind == 0
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)
+    with linked_list_grid(pkg, f):
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.neighbors()
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.query_neighbors(rec["pos"][:4, :3], sp.param_h)
+        assert f.neighbor_info().kind == 0
     _same(f.neighbors(), pkg.neighbors_host(rec, sp, sp.param_h), "grid build 0 again")
     f.close()
 

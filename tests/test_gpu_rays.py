@@ -3,18 +3,18 @@ the counts, on the smallest shapes where a grid walk can go wrong (rays_scenes.s
 corners, zero direction components, starts outside the box, spheres that stick out of it, clamped records, r = half a cell exactly, a
 dense lattice, ties); the interface around it; and the proof that a cast changes neither the simulation nor the other query results."""
 import ctypes as C
-from importlib import import_module
 
 import numpy as np
 import pytest
 
 from conftest import assert_records_equal, small_scene
 import rays_scenes as RS
-from support import build_example, run_example, undisturbed_run
+from support import build_example, linked_list_grid, run_example, same_info, slab_engine, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 vp = C.c_void_p
+INFO_FIELDS = ("rays", "hits", "voidRays", "radius", "flags")
 
 
 def _same(pkg, f, rec, sp, r, radius, what, dev=False, **kw):
@@ -29,8 +29,7 @@ def _same(pkg, f, rec, sp, r, radius, what, dev=False, **kw):
         else:
             got = f.raycast(r, radius, **kw)
         RS.same_hits(got, want, f"{what} variant {variant}")
-        info, w = f.rays_info(), want[4]
-        assert (info.rays, info.hits, info.voidRays, info.radius, info.flags) == (w.rays, w.hits, w.voidRays, w.radius, w.flags), what
+        same_info(f.rays_info(), want[4], INFO_FIELDS, what)
     f.set_option(pkg.SPH_OPT_RAYS_VARIANT, 0)
     return want
 
@@ -155,12 +154,9 @@ def test_refusals_and_states(pkg):
     dr = torch.from_numpy(r).cuda()
     rad = float(F(0.25) * F(sp.param_h))
     cs = float(pkg.compute_grid_extents(sp).cellSize)
-    halo = import_module(pkg.__name__ + ".halo")
-    g = pkg.compute_grid_extents(sp)
-    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
-    assert L.sph_rays_cast(slab._h, r.ctypes.data_as(vp), 16, rad, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
-    assert L.sph_rays_cast_device(slab._h, vp(dr.data_ptr()), 16, rad, 0, C.byref(info)) == -3
-    slab.close()
+    with slab_engine(pkg, rec, sp) as slab:
+        assert L.sph_rays_cast(slab._h, r.ctypes.data_as(vp), 16, rad, 0, C.byref(info)) == -3 and b"slab" in L.sph_last_error()
+        assert L.sph_rays_cast_device(slab._h, vp(dr.data_ptr()), 16, rad, 0, C.byref(info)) == -3
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     hits = np.full(16, 9, np.int32).repeat(8).view(pkg.RAY_HIT_DTYPE)
     p = vp()
@@ -172,12 +168,11 @@ def test_refusals_and_states(pkg):
             f.rays_info()
         assert (hits["id"] == 9).all()
     nothing_held()                                                                 # before any cast
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.raycast(r)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.raycast(dr)
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)
+    with linked_list_grid(pkg, f):
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.raycast(r)
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.raycast(dr)
     nothing_held()
     for bad in (0.0, -1.0, float("nan"), float("inf"), float(np.nextafter(F(0.5) * F(cs), F(9)))):
         assert L.sph_rays_cast(f._h, r.ctypes.data_as(vp), 16, bad, 0, C.byref(info)) == -1

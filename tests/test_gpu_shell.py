@@ -4,17 +4,16 @@ neither the simulation nor the other query results."""
 import ctypes as C
 import os
 import re
-from importlib import import_module
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, PKG_NAME, assert_records_equal, small_scene
-import knn_scenes as KS
 import neighbors_ref as NR
+import query_scenes as QS
 import rays_scenes as RS
 import shell_scenes as SS
-from support import build_example, engine, records, run_example, undisturbed_run
+from support import after_dispatches, build_example, linked_list_grid, records, run_example, same_info, slab_engine, undisturbed_run
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -47,8 +46,7 @@ def _same(pkg, f, rec, sp, R=None, points=None, dev_points=None, what="", **kw):
     else:
         got = f.query_shell(points if dev_points is None else dev_points, R, **kw)
     _equal(got, want, f"{what} R {R} {kw}")
-    info = f.shell_info()
-    assert [getattr(info, a) for a in INFO_FIELDS] == [getattr(want[2], a) for a in INFO_FIELDS], f"{what} R {R} {kw}"
+    same_info(f.shell_info(), want[2], INFO_FIELDS, f"{what} R {R} {kw}")
     return want
 
 
@@ -60,17 +58,17 @@ def _h(sp, fac):
 def test_edges_of_the_grid(pkg, fac):
     """The uniform box and a cloud up to a quarter of the grid's extent beyond every face (edge, corner and clamped cells), at every
     radius class."""
-    rec, sp = KS.uniform(pkg, 3000, seed=31)
+    rec, sp = QS.uniform(pkg, 3000, seed=31)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     want = _same(pkg, f, rec, sp, _h(sp, fac), what="uniform")
     assert want[2].stencil == int(np.ceil(fac)) and 0 < want[2].numShell < len(rec) and (want[0]["crest"] > 0).any()
     f.close()
     rng = np.random.default_rng(2)
-    grid = KS.grid(pkg, sp)
+    grid = QS.grid(pkg, sp)
     lo, dims, cs = grid
     corners = np.array([[x, y, z] for x in (0, dims[0] - 1) for y in (0, dims[1] - 1) for z in (0, dims[2] - 1)])
     corner_pos = lo + (np.repeat(corners, 6, axis=0).astype(F) + rng.random((48, 3)).astype(F)) * cs
-    pos = np.concatenate([KS.grid_cloud(rng, grid, 2500, beyond=0.25), corner_pos])
+    pos = np.concatenate([QS.grid_cloud(rng, grid, 2500, beyond=0.25), corner_pos])
     rec = records(pkg, pos, np.zeros_like(pos))
     assert not NR.inside_grid(pkg, rec["pos"], sp)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
@@ -80,13 +78,7 @@ def test_edges_of_the_grid(pkg, fac):
 
 def test_crowded_cell(pkg):
     """One cell of 300 members among 400 others: long runs of one lane, a run of sorted slots that crosses a block boundary."""
-    rng = np.random.default_rng(300)
-    sp = KS.params(pkg)
-    lo, dims, cs = KS.grid(pkg, sp)
-    cell = np.array([3, 2, 4])
-    inside = lo + (cell.astype(F) + F(0.05) + F(0.9) * rng.random((300, 3)).astype(F)) * cs
-    pos = np.concatenate([KS.grid_cloud(rng, (lo, dims, cs), 400), inside])
-    rec = records(pkg, pos, np.zeros_like(pos))
+    rec, sp, _, _ = QS.crowded_cell(pkg, 300)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for fac in (1.0, 2.0):
         want = _same(pkg, f, rec, sp, _h(sp, fac), what="crowd")
@@ -96,7 +88,7 @@ def test_crowded_cell(pkg):
 
 
 def test_special_records(pkg):
-    rec, sp = KS.with_ghosts(pkg)
+    rec, sp = QS.with_ghosts(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for kw in (dict(), dict(fluid_only=True)):
         for fac in (2.0, 3.0):
@@ -106,14 +98,14 @@ def test_special_records(pkg):
                 assert (want[0][ghost].view(np.uint8) == 0).all() and not np.isin(want[1], np.flatnonzero(ghost)).any()
     _same(pkg, f, rec, sp, 1.0, points=rec["pos"][:333, :3], fluid_only=True, what="ghosts, query")
     f.close()
-    rec, sp = KS.uniform(pkg, 1000, seed=23)
+    rec, sp = QS.uniform(pkg, 1000, seed=23)
     rec["pos"][7, 0] = np.nan
     rec["pos"][300, 2] = np.inf
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     want = _same(pkg, f, rec, sp, 1.0, what="non-finite")
     assert (want[0][[7, 300]].view(np.uint8) == 0).all()
     f.close()
-    rec, sp, same = KS.coincident(pkg)
+    rec, sp, same = QS.coincident(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     want = _same(pkg, f, rec, sp, 1.0, what="coincident")
     assert len({want[0][i].tobytes() for i in same}) == 1
@@ -123,8 +115,8 @@ def test_special_records(pkg):
 
 @pytest.mark.parametrize("n", [0, 1, 65])
 def test_tiny_engines(pkg, n):
-    sp = KS.params(pkg)
-    rec = KS.uniform(pkg, max(n, 1), seed=5)[0][:n]
+    sp = QS.params(pkg)
+    rec = QS.uniform(pkg, max(n, 1), seed=5)[0][:n]
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     want = _same(pkg, f, rec, sp, 1.0, what=f"n = {n}")
     assert want[2].kind == 1 and want[2].rows == n
@@ -143,7 +135,7 @@ def test_scan_tile_seams(pkg):
     the shell slots cross tile seams; a scene with no shell at all (the threshold out of reach) and one that is all shell."""
     tile = _scan_tile()
     for n in (tile - 1, tile, tile + 1, 2 * tile + 1):
-        rec, sp = KS.uniform(pkg, n, seed=n)
+        rec, sp = QS.uniform(pkg, n, seed=n)
         f = pkg.SPHFluidGPU.from_particles(rec, sp)
         want = _same(pkg, f, rec, sp, 1.0, what=f"n = {n}")
         assert 0 < want[2].numShell < n
@@ -167,15 +159,7 @@ def test_ball_crest(pkg):
 
 def test_query_rows(pkg):
     import torch
-    rng = np.random.default_rng(8)
-    sp = KS.params(pkg)
-    grid = KS.grid(pkg, sp)
-    pos = KS.grid_cloud(rng, grid, 1500, beyond=0.1)
-    rec = records(pkg, pos, np.zeros_like(pos))
-    pts = KS.grid_cloud(rng, grid, 701, beyond=0.3)                               # inside and outside the grid; 701 is no multiple of 64
-    pts[5, 0] = np.nan
-    pts[256, 1] = np.inf
-    pts[700, 2] = -np.inf
+    rec, sp, pts = QS.query_cloud(pkg)
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     for fac in (1.0, 2.0, 3.0):
         rows, ids, info = _same(pkg, f, rec, sp, _h(sp, fac), points=pts, what="query")
@@ -191,18 +175,14 @@ def test_query_rows(pkg):
 @pytest.mark.parametrize("kern,aos,graph", [(3, 1, 0), (1, 1, 0), (3, 0, 0), (3, 1, 1)])
 def test_after_dispatches(pkg, kern, aos, graph):
     """On a state the engine produced: the rows are those of the downloaded records, and a later dispatch does not touch them."""
-    rec, sp = small_scene(pkg, n=4096, grid=16, seed=3)
-    f = engine(pkg, rec, sp, kern, aos, graph)
-    for _ in range(4):
-        f.DispatchN(3)
-    if graph:
-        assert f.get_option(pkg.SPH_OPT_GRAPH_LAUNCHES) >= 1
-    now = f.download()
-    _same(pkg, f, now, sp, what=f"kernel {kern} aos {aos} graph {graph}")
-    want = _same(pkg, f, now, sp, _h(sp, 2.0), offset=0.15, what=f"kernel {kern} aos {aos} graph {graph}")
-    f.DispatchN(3)
-    _equal(f.shell_rows(), want, "after a dispatch")
-    f.close()
+    def check(f, now, sp, what):
+        _same(pkg, f, now, sp, what=what)
+        return _same(pkg, f, now, sp, _h(sp, 2.0), offset=0.15, what=what)
+
+    def unchanged(f, want):
+        _equal(f.shell_rows(), want, "after a dispatch")
+
+    after_dispatches(pkg, kern, aos, graph, check, unchanged)
 
 
 def test_shell_does_not_change_the_simulation(pkg):
@@ -286,12 +266,9 @@ def test_refusals_and_states(pkg):
     info = pkg.SphShellInfo()
     cfg = pkg.shell_config()
     pts = torch.zeros(16, dtype=torch.float32, device="cuda")
-    halo = import_module(pkg.__name__ + ".halo")
-    g = pkg.compute_grid_extents(sp)
-    slab = halo.HipSlabEngine(rec, np.arange(len(rec), dtype=np.uint32), sp, 0, g.dims[2], False, False, int(len(rec) * 1.2) + 8192)
-    assert L.sph_shell_build(slab._h, C.byref(cfg), C.byref(info)) == -3 and b"slab" in L.sph_last_error()
-    assert L.sph_shell_query(slab._h, vp(pts.data_ptr()), 4, C.byref(cfg), C.byref(info)) == -3
-    slab.close()
+    with slab_engine(pkg, rec, sp) as slab:
+        assert L.sph_shell_build(slab._h, C.byref(cfg), C.byref(info)) == -3 and b"slab" in L.sph_last_error()
+        assert L.sph_shell_query(slab._h, vp(pts.data_ptr()), 4, C.byref(cfg), C.byref(info)) == -3
     f = pkg.SPHFluidGPU.from_particles(rec, sp)
     n = len(rec)
     rows, ids = np.full(n, 9, np.uint8).repeat(32).view(pkg.SHELL_DTYPE), np.full(n, 9, np.int32)
@@ -305,12 +282,11 @@ def test_refusals_and_states(pkg):
             f.shell_info()
         assert (ids == 9).all() and (rows.view(np.uint8) == 9).all()
     nothing_held()                                                                 # before any build
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 1)
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.shell()
-    with pytest.raises(pkg.SphError, match="-3"):
-        f.query_shell(rec["pos"][:4, :3], sp.param_h)
-    f.set_option(pkg.SPH_OPT_GRID_BUILD, 0)
+    with linked_list_grid(pkg, f):
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.shell()
+        with pytest.raises(pkg.SphError, match="-3"):
+            f.query_shell(rec["pos"][:4, :3], sp.param_h)
     nothing_held()
     for bad in (dict(radius=float("nan")), dict(radius=float("inf")), dict(radius=3.01 * sp.param_h), dict(offset=-0.1), dict(offset=float("nan")),
                 dict(offset=float("inf")), dict(flags=2), dict(flags=-1)):

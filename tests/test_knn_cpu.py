@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import knn_ref as KR
-import knn_scenes as KS
 import neighbors_ref as NR
+import query_scenes as QS
 import support
 
 F = np.float32
@@ -42,7 +42,7 @@ def test_host_equals_the_float64_restatement(pkg, n, k, R):
     """Near-tie rows at 1e-6 R^2 (the threshold the comparison uses), measured on these seeded scenes: 2000 / k 16 / R 1.0: 0.15 %;
     2000 / k 8 / R 0.5: 0 %; 4000 / k 32 / R 1.5: 1.00 %; 2000 / k 64 / R 1.0: 0.40 % (printed below; the bound of 5 % is a condition on
     the inputs, checked on the restatement alone before anything is compared)."""
-    rec, sp = KS.uniform(pkg, n, seed=n + k)
+    rec, sp = QS.uniform(pkg, n, seed=n + k)
     assert NR.inside_grid(pkg, rec["pos"], sp)
     w_idx, w_d2, w_cnt, near, edge = KR.knn(rec["pos"], k, R)
     share = near.mean()
@@ -62,7 +62,7 @@ def test_host_equals_the_float64_restatement(pkg, n, k, R):
 
 
 def test_prefix_property(pkg):
-    rec, sp = KS.uniform(pkg, 2000, seed=21)
+    rec, sp = QS.uniform(pkg, 2000, seed=21)
     ks = (1, 7, 8, 9, 16, 33, 64)
     res = {k: pkg.knn_host(rec, sp, k, 1.0) for k in ks}
     i64, d64, c64, _ = res[64]
@@ -77,7 +77,7 @@ def test_prefix_property(pkg):
 
 @pytest.mark.parametrize("self_", [False, True])
 def test_rows_are_the_neighbour_lists_when_k_covers_them(pkg, self_):
-    rec, sp = KS.uniform(pkg, 2000, seed=22)
+    rec, sp = QS.uniform(pkg, 2000, seed=22)
     n = len(rec)
     for R, k in ((0.5, 64), (1.0, 8), (1.3, 17)):
         off, nidx = pkg.neighbors_host(rec, sp, R, self_=self_)
@@ -98,7 +98,7 @@ def test_rows_are_the_neighbour_lists_when_k_covers_them(pkg, self_):
 def test_exact_ties_on_a_lattice_resolve_by_id(pkg):
     """Spacing h / 2 with exactly representable coordinates: every r2 is exact in fp32 and in float64, whole shells tie, and the order
     inside a shell is the id order -- the restatement's rows, entry for entry, although every row is a (near-)tie row."""
-    rec, sp = KS.lattice(pkg)
+    rec, sp = QS.lattice(pkg)
     for k, R in ((6, 0.5), (7, 0.5), (19, 1.0), (64, 1.0)):
         w_idx, w_d2, w_cnt, near, edge = KR.knn(rec["pos"], k, R)
         idx, d2, cnt, _ = pkg.knn_host(rec, sp, k, R)
@@ -109,7 +109,7 @@ def test_exact_ties_on_a_lattice_resolve_by_id(pkg):
 
 
 def test_coincident_particles_are_ordered_by_id(pkg):
-    rec, sp, same = KS.coincident(pkg)
+    rec, sp, same = QS.coincident(pkg)
     for k in (4, 8, 16):
         idx, d2, cnt, _ = pkg.knn_host(rec, sp, k, 1.0, self_=True)
         for i in same:
@@ -126,7 +126,7 @@ def test_coincident_particles_are_ordered_by_id(pkg):
 
 
 def test_fluid_only_with_ghosts_of_every_kind(pkg):
-    rec, sp = KS.with_ghosts(pkg)
+    rec, sp = QS.with_ghosts(pkg)
     ghost = rec["isGhost"] != 0
     assert set(np.unique(rec["isGhost"])) == {0, 1, 3} and (rec["isActive"] == 0).any()
     for k, R in ((8, 1.0), (33, 1.5)):
@@ -144,7 +144,7 @@ def test_fluid_only_with_ghosts_of_every_kind(pkg):
 
 
 def test_non_finite_particles_and_query_points(pkg):
-    rec, sp = KS.uniform(pkg, 1000, seed=23)
+    rec, sp = QS.uniform(pkg, 1000, seed=23)
     rec["pos"][7, 0] = np.nan
     rec["pos"][300, 2] = np.inf
     for self_ in (False, True):
@@ -158,7 +158,7 @@ def test_non_finite_particles_and_query_points(pkg):
 
 
 def test_argument_refusals(pkg):
-    rec, sp = KS.uniform(pkg, 200, seed=24)
+    rec, sp = QS.uniform(pkg, 200, seed=24)
     L = pkg.load_library()
     h = sp.param_h
     cs = pkg.compute_grid_extents(sp).cellSize
@@ -186,7 +186,7 @@ def test_argument_refusals(pkg):
 
 
 def test_tiny_inputs(pkg):
-    sp = KS.params(pkg)
+    sp = QS.params(pkg)
     none = np.zeros(0, pkg.PARTICLE_DTYPE)
     idx, d2, cnt, info = pkg.knn_host(none, sp, 8, 1.0)
     assert idx.shape == (0, 8) and cnt.shape == (0,) and (info.rows, info.total, info.rowsFull, info.kind) == (0, 0, 0, 1)
@@ -200,7 +200,7 @@ def test_tiny_inputs(pkg):
     idx, d2, cnt, info = pkg.knn_host(one, sp, 4, 1.0, points=np.zeros((0, 3), F))
     assert idx.shape == (0, 4) and (info.rows, info.kind) == (0, 2)
     # k > n: every row shorter than k
-    rec, sp = KS.uniform(pkg, 20, seed=25)
+    rec, sp = QS.uniform(pkg, 20, seed=25)
     idx, d2, cnt, info = pkg.knn_host(rec, sp, 64, 1.5)
     _well_formed(idx, d2, cnt, 64, 20)
     assert (cnt < 20).all() and info.rowsFull == 0 and cnt.sum() == info.total > 0

@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import knn_scenes as KS
 import neighbors_ref as NR
+import query_scenes as QS
 import shell_ref as SR
 import shell_scenes as SS
 from support import records
@@ -23,7 +23,7 @@ def _scene(pkg, name):
     """(records, params, nominal or None, radius, reference, (rows, ids, info) of the twin), computed once per session."""
     if name not in _CACHE:
         if name == "uniform":
-            rec, sp = KS.uniform(pkg, 2000, seed=41)
+            rec, sp = QS.uniform(pkg, 2000, seed=41)
             nominal = None
         else:
             rec, sp, nominal = dict(block=lambda: SS.block(pkg), ball10=lambda: SS.ball(pkg, 10.0), ball5=lambda: SS.ball(pkg, 5.0),
@@ -174,8 +174,8 @@ def _back(rows, ids, perm):
 
 
 def _lattice_runs(pkg, R):
-    """The twin on knn_scenes.lattice and on four permutations of its ids, the permuted runs mapped back."""
-    rec, sp = KS.lattice(pkg)
+    """The twin on query_scenes.lattice and on four permutations of its ids, the permuted runs mapped back."""
+    rec, sp = QS.lattice(pkg)
     base = pkg.shell_host(rec, sp, R)
     runs = []
     for seed in range(4):
@@ -187,7 +187,7 @@ def _lattice_runs(pkg, R):
 
 @pytest.mark.parametrize("R", [0.5, 1.0])
 def test_order_on_the_exact_lattice(pkg, R):
-    """knn_scenes.lattice: coordinates are multiples of 1/4 and R^2 is one too, so every d, r2, t, w, every product w d and every
+    """query_scenes.lattice: coordinates are multiples of 1/4 and R^2 is one too, so every d, r2, t, w, every product w d and every
     partial sum of pass 1 is exactly representable: symmetric sums cancel to exactly zero in the interior, and no order of the
     candidates can change a bit of S or W.  The order of the candidates inside a cell follows the particle ids, so this is the scene on
     which pass 1's bytes -- normal, offsetRatio, count, flags -- and ids are the same under every permutation of the ids, once the rows
@@ -219,7 +219,7 @@ def test_crest_order_on_the_exact_lattice(pkg, R):
 
 
 def test_coincident_ghosts_and_special_records(pkg):
-    rec, sp, same = KS.coincident(pkg)
+    rec, sp, same = QS.coincident(pkg)
     R = 1.0
     rows, ids, info = pkg.shell_host(rec, sp, R)
     _well_formed(rows, ids, info, len(rec))
@@ -233,7 +233,7 @@ def test_coincident_ghosts_and_special_records(pkg):
     ref = SR.shell(rec["pos"], R)
     assert np.array_equal(rows["count"].astype(np.int64)[~ref["edge"]], ref["count"][~ref["edge"]])
     # ghosts: candidates like any other, unless FLUID_ONLY
-    rec, sp = KS.with_ghosts(pkg)
+    rec, sp = QS.with_ghosts(pkg)
     ghost = rec["isGhost"] != 0
     a, aids, ainfo = pkg.shell_host(rec, sp, R)
     b, bids, binfo = pkg.shell_host(rec, sp, R, fluid_only=True)
@@ -249,7 +249,7 @@ def test_coincident_ghosts_and_special_records(pkg):
     q = pkg.shell_host(rec, sp, R, fluid_only=True, points=rec["pos"][:50, :3] + F(0.01))
     assert q[2].kind == 2 and (q[0]["crest"] == 0).all() and q[2].rows == 50
     # a non-finite particle: an all-zero row, a candidate of nobody
-    rec, sp = KS.uniform(pkg, 1000, seed=23)
+    rec, sp = QS.uniform(pkg, 1000, seed=23)
     base = pkg.shell_host(np.delete(rec, [7, 300]), sp, R)[0]
     rec["pos"][7, 0] = np.nan
     rec["pos"][300, 2] = np.inf
@@ -262,7 +262,7 @@ def test_coincident_ghosts_and_special_records(pkg):
 
 
 def test_lone_particle_empty_engine_min_count_and_radius_classes(pkg):
-    sp = KS.params(pkg)
+    sp = QS.params(pkg)
     one = records(pkg, np.array([[0.2, -0.4, 0.1]], F), np.zeros((1, 3), F))
     rows, ids, info = pkg.shell_host(one, sp, 1.0)
     assert rows["flags"].tolist() == [3] and ids.tolist() == [0] and (info.numShell, info.numIsolated, info.maxCount, info.kind) == (1, 1, 0, 1)
@@ -273,7 +273,7 @@ def test_lone_particle_empty_engine_min_count_and_radius_classes(pkg):
     q = pkg.shell_host(none, sp, 1.0, points=np.zeros((3, 3), F))
     assert q[0]["flags"].tolist() == [3, 3, 3] and q[1].tolist() == [0, 1, 2] and q[2].numIsolated == 3
     # minCount alone: the offset never flags
-    rec, sp = KS.uniform(pkg, 1200, seed=31)
+    rec, sp = QS.uniform(pkg, 1200, seed=31)
     rows, ids, info = pkg.shell_host(rec, sp, 1.0, offset=1e30, min_count=0)
     assert ((rows["flags"] & 1) == (rows["count"] == 0)).all()
     mid = int(np.median(rows["count"]))
@@ -300,7 +300,7 @@ def test_lone_particle_empty_engine_min_count_and_radius_classes(pkg):
 
 def test_argument_errors_and_layout(pkg, tmp_path):
     from support import c_layout
-    rec, sp = KS.uniform(pkg, 50, seed=1)
+    rec, sp = QS.uniform(pkg, 50, seed=1)
     for kw in (dict(radius=float("nan")), dict(radius=float("inf")), dict(radius=3.01 * sp.param_h), dict(offset=-0.1), dict(offset=float("nan")),
                dict(offset=float("inf"))):
         with pytest.raises(pkg.SphError, match="-1"):

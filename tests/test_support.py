@@ -6,7 +6,7 @@ import pytest
 
 from conftest import small_scene, to_oracle_params
 import obstacle_ref as R
-from support import build_example, check_impulses, fluid_block, same_bits
+from support import after_dispatches, build_example, check_impulses, fluid_block, same_bits, same_info
 
 F = np.float32
 
@@ -57,6 +57,60 @@ def test_check_impulses_holds_at_the_bound_and_fails_one_ulp_above(pkg, oracle):
     above[0, 1] = np.nextafter(want[0, 1] + bound[0, 1], np.inf)
     with pytest.raises(AssertionError, match="one ulp above"):
         check_impulses(above, want, info, "one ulp above")
+
+
+def test_same_info_compares_the_named_fields_only(pkg):
+    a, b = pkg.SphKnnInfo(rows=5, total=7, k=8), pkg.SphKnnInfo(rows=5, total=9, k=8)
+    same_info(a, b, ("rows", "k"), "rows and k")
+    with pytest.raises(AssertionError, match="the total"):
+        same_info(a, b, ("rows", "total", "k"), "the total")
+
+
+class _NoDevice:
+    """Stands in for the package and for its engine in after_dispatches: it notes what is called and replays no graph."""
+    SPH_OPT_NEIGHBOR_KERNEL, SPH_OPT_AOS_MODE, SPH_OPT_GRAPH, SPH_OPT_GRAPH_LAUNCHES = "kern", "aos", "graph", "launches"
+
+    def __init__(self, launches):
+        self.SPHFluidGPU, self.options, self.seen = self, {"launches": launches}, []
+
+    def from_particles(self, rec, sp):
+        self.seen.append(("engine", rec, sp))
+        return self
+
+    def set_option(self, option, value):
+        self.options[option] = value
+
+    def get_option(self, option):
+        return self.options[option]
+
+    def DispatchN(self, n):
+        self.seen.append(("dispatch", n))
+
+    def download(self):
+        return "now"
+
+    def close(self):
+        self.seen.append("close")
+
+
+def test_after_dispatches_runs_the_scenario_in_order_and_wants_the_graph_replayed():
+    def check(f, now, sp, what):
+        f.seen.append(("check", now, sp, what))
+        return "held"
+
+    def unchanged(f, held):
+        f.seen.append(("unchanged", held))
+
+    fake = _NoDevice(launches=2)
+    after_dispatches(fake, 1, 0, 1, check, unchanged, scene=("rec", "sp"))
+    assert fake.options == {"kern": 1, "aos": 0, "graph": 1, "launches": 2}
+    assert fake.seen == [("engine", "rec", "sp")] + [("dispatch", 3)] * 4 + [("check", "now", "sp", "kernel 1 aos 0 graph 1"), ("dispatch", 3),
+                                                                              ("unchanged", "held"), "close"]
+    with pytest.raises(AssertionError):
+        after_dispatches(_NoDevice(launches=0), 3, 1, 1, check, unchanged, scene=("rec", "sp"))
+    eager = _NoDevice(launches=0)                                                   # without a graph no launch is asked for
+    after_dispatches(eager, 3, 1, 0, check, unchanged, scene=("rec", "sp"))
+    assert eager.seen[-1] == "close"
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")

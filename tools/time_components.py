@@ -19,40 +19,15 @@ Without an argument the result goes to time_components.json in the current direc
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 import json
 import sys
 
 import timing
-from timing import pkg
+from timing import components_build as components, pkg
 
 REPS = 10
-
-
-def series(f, fn, reps=REPS, warm=2):
-    for _ in range(warm):
-        fn()
-    f.kernel_times(reset=True)
-    other, build, launches = [], [], []
-    for _ in range(reps):
-        fn()
-        t = f.kernel_times(reset=True)
-        other.append(t["other"][0] * 1000.0)
-        launches.append(int(t["other"][1]))
-        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
-    return timing.stats(other), timing.stats(build), launches
-
-
-def components(f, R):
-    info = pkg.SphComponentInfo()
-    pkg.engine._check(f._L.sph_components_build(f._h, float(R), pkg.SPH_COMPONENTS_FLUID_ONLY, C.byref(info)))
-    return info
-
-
-def count_only(f, R):
-    info = pkg.SphNeighborInfo()
-    pkg.engine._check(f._L.sph_neighbors_build(f._h, float(R), pkg.SPH_NEIGHBORS_COUNT_ONLY, 0, C.byref(info)))
-    return info
+series = functools.partial(timing.series, reps=REPS, warm=2)
 
 
 def main() -> None:
@@ -75,8 +50,9 @@ def main() -> None:
         r = {}
         for name, R in (("R=h", h), ("R=2h", 2.0 * h)):
             v = {}
-            cnt, grid_us, _ = series(f, lambda: count_only(f, R))
-            full, _, launches = series(f, lambda: components(f, R))
+            cnt, grid_us = series(f, lambda: timing.neighbors_build(f, R, pkg.SPH_NEIGHBORS_COUNT_ONLY))
+            launches = []
+            full, _ = series(f, lambda: components(f, R), launches=launches)
             info = f.component_info()
             v["count_only"], v["grid_build"], v["components"] = cnt, grid_us, full
             v.update(rounds=int(info.rounds), launches=launches[-1], bodies=int(info.numComponents), largest=int(info.largestCount),
@@ -84,10 +60,10 @@ def main() -> None:
             v["per_round_over_count"] = full["median_us"] / info.rounds / cnt["median_us"]
             v["whole_over_count"] = full["median_us"] / cnt["median_us"]
             f.set_option(pkg.SPH_OPT_COMPONENTS_VARIANT, 1)
-            v["full_walk"], _, _ = series(f, lambda: components(f, R), reps=5, warm=1)
+            v["full_walk"], _ = series(f, lambda: components(f, R), reps=5, warm=1)
             v["full_walk_rounds"] = int(f.component_info().rounds)
             f.set_option(pkg.SPH_OPT_COMPONENTS_VARIANT, 2)
-            v["lane_atomics"], _, _ = series(f, lambda: components(f, R), reps=2, warm=0)
+            v["lane_atomics"], _ = series(f, lambda: components(f, R), reps=2, warm=0)
             f.set_option(pkg.SPH_OPT_COMPONENTS_VARIANT, 0)
             r[name] = v
             print(label, name, json.dumps({k: (x["median_us"] if isinstance(x, dict) else x) for k, x in v.items()}), flush=True)

@@ -20,42 +20,14 @@ the kernel in the tree (profiles/r17_time_knn_sorted_rows.json: an earlier versi
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import sys
 
 import timing
-from timing import pkg
+from timing import knn_build as knn, neighbors_build as lists, pkg, series
 
 KS = (8, 16, 32, 64)
 SLOW_REPS = 3                                                                    # calls of the selection kernel per case (seconds each at k = 64)
-
-
-def series(f, fn, reps=timing.REPS, warm=3):
-    """Class `other` (and the grid build's classes) of each of `reps` calls of fn."""
-    for _ in range(warm):
-        fn()
-    f.kernel_times(reset=True)
-    other, build = [], []
-    for _ in range(reps):
-        fn()
-        t = f.kernel_times(reset=True)
-        other.append(t["other"][0] * 1000.0)
-        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
-    return timing.stats(other), timing.stats(build)
-
-
-def knn(f, k, R):
-    """sph_knn_build without the copy of the rows that SPHFluidGPU.knn makes."""
-    info = pkg.SphKnnInfo()
-    pkg.engine._check(f._L.sph_knn_build(f._h, int(k), float(R), 0, C.byref(info)))
-    return info
-
-
-def lists(f, R):
-    info = pkg.SphNeighborInfo()
-    pkg.engine._check(f._L.sph_neighbors_build(f._h, float(R), 0, 0, C.byref(info)))
-    return info
 
 
 def torch_route(f, pos, R, k):
@@ -111,19 +83,13 @@ def main() -> None:
                 print(label, name, "k", k, json.dumps({vv: v["knn"][vv][str(k)]["median_us"] for vv in ("0", "1")}),
                       "neighbors_build", nb["median_us"], flush=True)
             # the torch route once per radius (k = 16); checked against the engine's rows where the distances do not tie
-            try:
-                with torch.cuda.stream(stream):
-                    route = timing.events(lambda: torch_route(f, pos, R, 16), stream, reps=SLOW_REPS, warm=1)
-                    t_idx, _ = torch_route(f, pos, R, 16)
-                    e_idx = f.knn(16, R, device=True)[0]
-                    stream.synchronize()
-                    share = float((t_idx == e_idx.to(torch.int64)).all(dim=1).float().mean())
-                v["torch_route_k16"] = dict(route, rows_equal_share=share)
+            def rows_equal(routed):
+                e_idx = f.knn(16, R, device=True)[0]
+                stream.synchronize()
+                return dict(rows_equal_share=float((routed[0] == e_idx.to(torch.int64)).all(dim=1).float().mean()))
+            v["torch_route_k16"] = route = timing.torch_route(lambda: torch_route(f, pos, R, 16), rows_equal, stream, SLOW_REPS)
+            if "not_measured" not in route:
                 v["torch_route_over_knn_k16"] = route["median_us"] / v["knn"]["0"]["16"]["median_us"]
-                del t_idx, e_idx
-            except RuntimeError as err:                                          # (torch.sort takes at most INT_MAX elements; or out of device memory)
-                v["torch_route_k16"] = {"not_measured": str(err).splitlines()[0][:200]}
-            torch.cuda.empty_cache()
             print(label, name, "torch route", json.dumps(v["torch_route_k16"]), flush=True)
             r[name] = v
         res["regimes"][label] = dict(substep=substep, **r)

@@ -22,41 +22,13 @@ record of the first measurement.
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import sys
 
 import numpy as np
 
 import timing
-from timing import pkg
-
-
-def series(f, fn, reps=timing.REPS, warm=3):
-    """Class `other` (and the grid build's classes) of each of `reps` calls of fn."""
-    for _ in range(warm):
-        fn()
-    f.kernel_times(reset=True)
-    other, build = [], []
-    for _ in range(reps):
-        fn()
-        t = f.kernel_times(reset=True)
-        other.append(t["other"][0] * 1000.0)
-        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
-    return timing.stats(other), timing.stats(build)
-
-
-def build(f, R, flags=0):
-    """sph_neighbors_build without the copy of the lists that SPHFluidGPU.neighbors makes."""
-    info = pkg.SphNeighborInfo()
-    pkg.engine._check(f._L.sph_neighbors_build(f._h, float(R), int(flags), 0, C.byref(info)))
-    return info
-
-
-def query_count(f, pts, R):
-    info = pkg.SphNeighborInfo()
-    pkg.engine._check(f._L.sph_neighbors_query(f._h, C.c_void_p(pts.data_ptr()), int(pts.shape[0]), float(R), pkg.SPH_NEIGHBORS_COUNT_ONLY, 0, C.byref(info)))
-    return info
+from timing import neighbors_build as build, neighbors_query_count as query_count, pkg, series
 
 
 def main() -> None:

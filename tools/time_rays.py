@@ -18,36 +18,16 @@ Without an argument the result goes to time_rays.json in the current directory; 
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 import json
 import sys
 
 import timing
-from timing import pkg
+from timing import pkg, rays_cast as cast
 
 REPS = 10
 SIDE = 1024
-
-
-def series(f, fn, reps=REPS, warm=2):
-    """Class `other` (and the grid build's classes) of each of `reps` calls of fn."""
-    for _ in range(warm):
-        fn()
-    f.kernel_times(reset=True)
-    other, build = [], []
-    for _ in range(reps):
-        fn()
-        t = f.kernel_times(reset=True)
-        other.append(t["other"][0] * 1000.0)
-        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
-    return timing.stats(other), timing.stats(build)
-
-
-def cast(f, dev, radius, flags):
-    """sph_rays_cast_device without the copy of the hits that SPHFluidGPU.raycast makes."""
-    info = pkg.SphRaysInfo()
-    pkg.engine._check(f._L.sph_rays_cast_device(f._h, C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), int(flags), C.byref(info)))
-    return info
+series = functools.partial(timing.series, reps=REPS, warm=2)
 
 
 def main() -> None:
@@ -91,9 +71,8 @@ def main() -> None:
                       "grid build", v["first_hit"]["grid_build"]["median_us"], flush=True)
             del dev
         pts = torch.from_numpy(np.ascontiguousarray(np.concatenate([seg[:, 0:3], np.zeros((len(seg), 1), np.float32)], axis=1))).cuda()
-        info = pkg.SphKnnInfo()
-        knn, build = series(f, lambda: pkg.engine._check(f._L.sph_knn_query(f._h, C.c_void_p(pts.data_ptr()), len(seg), 8, h, 0, C.byref(info))))
-        r["knn_query_k8_R=h"] = dict(knn, total=int(info.total), grid_build=build)
+        knn, build = series(f, lambda: timing.knn_query(f, pts, 8, h))
+        r["knn_query_k8_R=h"] = dict(knn, total=int(f.knn_info().total), grid_build=build)
         print(label, "knn query", knn["median_us"], flush=True)
         res["regimes"][label] = dict(substep=substep, **r)
     res["copy"] = timing.copy_yardstick(len(rec), stream)

@@ -22,42 +22,13 @@ Without an argument the result goes to time_shell.json in the current directory;
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import sys
 
 import timing
-from timing import pkg
+from timing import pkg, series, shell_build as shell
 
 SLOW_REPS = 3                                                                    # runs of the torch route
-
-
-def series(f, fn, reps=timing.REPS, warm=3):
-    """Class `other` (and the grid build's classes) of each of `reps` calls of fn."""
-    for _ in range(warm):
-        fn()
-    f.kernel_times(reset=True)
-    other, build = [], []
-    for _ in range(reps):
-        fn()
-        t = f.kernel_times(reset=True)
-        other.append(t["other"][0] * 1000.0)
-        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
-    return timing.stats(other), timing.stats(build)
-
-
-def shell(f, R):
-    """sph_shell_build without the copy of the rows that SPHFluidGPU.shell makes."""
-    info = pkg.SphShellInfo()
-    cfg = pkg.shell_config(radius=float(R))
-    pkg.engine._check(f._L.sph_shell_build(f._h, C.byref(cfg), C.byref(info)))
-    return info
-
-
-def counts(f, R):
-    info = pkg.SphNeighborInfo()
-    pkg.engine._check(f._L.sph_neighbors_build(f._h, float(R), pkg.SPH_NEIGHBORS_COUNT_ONLY, 0, C.byref(info)))
-    return info
 
 
 def torch_route(f, pos, R):
@@ -90,7 +61,7 @@ def main() -> None:
         r = {}
         for name, R in (("R=h", h), ("R=2h", 2.0 * h)):
             v = {}
-            walk, grid_us = series(f, lambda: counts(f, R))
+            walk, grid_us = series(f, lambda: timing.neighbors_build(f, R, pkg.SPH_NEIGHBORS_COUNT_ONLY))
             ni = f.neighbor_info()
             v["count_walk"] = dict(walk, total=int(ni.total), mean_degree=ni.total / n, max_count=int(ni.maxCount))
             v["grid_build"] = grid_us
@@ -111,20 +82,15 @@ def main() -> None:
                   "shell", si.numShell, flush=True)
             if name == "R=h":
                 # the torch route once (pass 1 only); checked against the engine's rows through the offset ratio where W > 0
-                try:
-                    with torch.cuda.stream(stream):
-                        route = timing.events(lambda: torch_route(f, pos, float(np.float32(R))), stream, reps=SLOW_REPS, warm=1)
-                        W, S = torch_route(f, pos, float(np.float32(R)))
-                        z = f.shell(R, device=True)[0]
-                        stream.synchronize()
-                        ratio = torch.where(W > 0, S.norm(dim=1) / (float(R) * W.clamp_min(1e-30)), torch.zeros_like(W))
-                        err = float((ratio - z[:, 3]).abs().max())
-                    v["torch_route_pass1"] = dict(route, edges=int(ni.total), max_offset_ratio_difference=err)
+                def offset_ratios(routed):
+                    W, S = routed
+                    z = f.shell(R, device=True)[0]
+                    stream.synchronize()
+                    ratio = torch.where(W > 0, S.norm(dim=1) / (float(R) * W.clamp_min(1e-30)), torch.zeros_like(W))
+                    return dict(edges=int(ni.total), max_offset_ratio_difference=float((ratio - z[:, 3]).abs().max()))
+                v["torch_route_pass1"] = route = timing.torch_route(lambda: torch_route(f, pos, float(np.float32(R))), offset_ratios, stream, SLOW_REPS)
+                if "not_measured" not in route:
                     v["torch_route_over_pass1"] = route["median_us"] / sh["pass1"]["median_us"]
-                    del W, S, z, ratio
-                except RuntimeError as err:                                      # (out of device memory, or a tensor above a size limit)
-                    v["torch_route_pass1"] = {"not_measured": str(err).splitlines()[0][:200]}
-                torch.cuda.empty_cache()
                 print(label, name, "torch route", json.dumps(v["torch_route_pass1"]), flush=True)
             r[name] = v
         res["regimes"][label] = dict(substep=substep, **r)

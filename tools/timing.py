@@ -1,7 +1,10 @@
 """What the tools/time_*.py scripts share: the package import, the config 3 scene and its two regimes, the sample statistics, the
-device-event brackets, the copy yardstick, the body grid of the obstacle tools, and the head and tail of a result file."""
+device-event brackets, the copy yardstick, the body grid of the obstacle tools, the head and tail of a result file, and for the tools
+of the spatial queries (time_neighbors, time_components, time_knn, time_rays, time_shell) the series of the engine's own brackets,
+the queries through the C ABI alone, and the torch route a query is compared with."""
 from __future__ import annotations
 
+import ctypes as C
 import importlib
 import json
 import os
@@ -81,6 +84,74 @@ def events(fn, stream, reps=REPS, warm=3):
         b.synchronize()
         us.append(a.elapsed_time(b) * 1000.0)
     return stats(us)
+
+
+def series(f, fn, reps=REPS, warm=3, launches=None):
+    """The engine's own brackets (SPH_OPT_TIMING) of each of `reps` calls of fn after `warm` warm-ups: (stats of class `other`, stats of
+    the grid build's classes bin + scan + scatter).  A list given as `launches` receives the number of `other` brackets of each call."""
+    for _ in range(warm):
+        fn()
+    f.kernel_times(reset=True)
+    other, build = [], []
+    for _ in range(reps):
+        fn()
+        t = f.kernel_times(reset=True)
+        other.append(t["other"][0] * 1000.0)
+        build.append(sum(t[c][0] for c in ("bin", "scan", "scatter")) * 1000.0)
+        if launches is not None:
+            launches.append(int(t["other"][1]))
+    return stats(other), stats(build)
+
+
+def _bare(f, fn, info, *args):
+    """A query through the C ABI alone, without the copy of the result that the binding's method makes; returns the filled info."""
+    pkg.engine._check(fn(f._h, *args, C.byref(info)))
+    return info
+
+
+def neighbors_build(f, R, flags=0):
+    return _bare(f, f._L.sph_neighbors_build, pkg.SphNeighborInfo(), float(R), int(flags), 0)
+
+
+def neighbors_query_count(f, pts, R):
+    return _bare(f, f._L.sph_neighbors_query, pkg.SphNeighborInfo(), C.c_void_p(pts.data_ptr()), int(pts.shape[0]), float(R), pkg.SPH_NEIGHBORS_COUNT_ONLY, 0)
+
+
+def components_build(f, R):
+    return _bare(f, f._L.sph_components_build, pkg.SphComponentInfo(), float(R), pkg.SPH_COMPONENTS_FLUID_ONLY)
+
+
+def knn_build(f, k, R):
+    return _bare(f, f._L.sph_knn_build, pkg.SphKnnInfo(), int(k), float(R), 0)
+
+
+def knn_query(f, pts, k, R):
+    return _bare(f, f._L.sph_knn_query, pkg.SphKnnInfo(), C.c_void_p(pts.data_ptr()), int(pts.shape[0]), int(k), float(R), 0)
+
+
+def rays_cast(f, dev, radius, flags):
+    return _bare(f, f._L.sph_rays_cast_device, pkg.SphRaysInfo(), C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), int(flags))
+
+
+def shell_build(f, R):
+    cfg = pkg.shell_config(radius=float(R))
+    return _bare(f, f._L.sph_shell_build, pkg.SphShellInfo(), C.byref(cfg))
+
+
+def torch_route(route, compare, stream, reps):
+    """What a query replaces, written in torch: device events on the torch stream around `reps` runs of route() after one warm-up, then
+    compare(route()), a dict of what the comparison with the engine's result found.  Returns the stats with that dict, or, where the
+    route does not fit (out of device memory, a tensor above a size limit such as torch.sort's INT_MAX elements), {"not_measured": the
+    error's first line}; the cache is emptied either way."""
+    import torch
+    try:
+        with torch.cuda.stream(stream):
+            t = events(route, stream, reps=reps, warm=1)
+            out = dict(t, **compare(route()))
+    except RuntimeError as err:
+        out = {"not_measured": str(err).splitlines()[0][:200]}
+    torch.cuda.empty_cache()
+    return out
 
 
 def copy_yardstick(n, stream):
