@@ -28,6 +28,7 @@
 #include "sph_components.h"
 #include "sph_knn.h"
 #include "sph_shell.h"
+#include "sph_aniso.h"
 #include "sph_rays.h"
 #include "sph_surface.h"
 #include "sph_tracer.h"
@@ -289,6 +290,11 @@ struct SphEngine {
     DevBuf<unsigned long long> d_shStats;
     DevBuf<long long> d_shOffsets;
     SphShellInfo shellInfo{};               // kind 0: no rows
+    // sph_aniso_*: the rows by particle id, per sorted slot the three float4 a lattice node reads, the four words of the reduction
+    DevBuf<sph::AnisoRow> d_anRows;
+    DevBuf<float4> d_anSlots;
+    DevBuf<unsigned long long> d_anStats;
+    SphAnisoInfo anisoInfo{};               // kind 0: no rows
     int optShellTimed = 0;                  // SPH_OPT_SHELL_TIMED: which launches of a build the timing bracket covers (0 all, 1 pass 1, 2 pass 2, 3 scans and compactions)
     // sph_extract_surface*: scratch per lattice point (sampled volume, codes, vertex offsets) and per tile, and the borrowed outputs
     DevBuf<float> d_surfVol;
@@ -517,6 +523,10 @@ void shell_free(SphEngine* e) {
     e->d_shRows.release(); e->d_shIds.release(); e->d_shSlots.release(); e->d_shNrm.release(); e->d_shFlagRow.release(); e->d_shFlagSlot.release();
     e->d_shStats.release(); e->d_shOffsets.release();
     e->shellInfo = SphShellInfo{};
+}
+void aniso_free(SphEngine* e) {
+    e->d_anRows.release(); e->d_anSlots.release(); e->d_anStats.release();
+    e->anisoInfo = SphAnisoInfo{};
 }
 void rays_free(SphEngine* e) {
     e->d_rayIn.release(); e->d_rayHits.release(); e->d_rayStats.release();
@@ -1348,6 +1358,7 @@ int sph_destroy(SphEngine* e) {
     knn_free(e);
     rays_free(e);
     shell_free(e);
+    aniso_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1389,6 +1400,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     knn_free(e);                                                      // (and the k nearest neighbours)
     rays_free(e);                                                     // (and the ray hits)
     shell_free(e);                                                    // (and the free-surface rows)
+    aniso_free(e);                                                    // (and the anisotropy rows)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -2882,6 +2894,20 @@ static int check_lattice(const int dims[3], const float spacing[3], int least, l
     return SPH_OK;
 }
 
+// The constants of a lattice kernel (arguments already checked): the 8 x 8 x 4 bricks of k_sample_lattice and k_aniso_lattice.
+static sph::LatticeK lattice_consts(const float origin[3], const float spacing[3], const int dims[3], int field, int stage) {
+    using namespace sph;
+    LatticeK L;
+    L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
+    L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
+    L.dx = dims[0]; L.dy = dims[1]; L.dz = dims[2];
+    L.nbx = (dims[0] + kBrickX - 1) / kBrickX; L.nby = (dims[1] + kBrickY - 1) / kBrickY;
+    L.nBricks = (long long)L.nbx * L.nby * ((dims[2] + kBrickZ - 1) / kBrickZ);
+    L.field = field;
+    L.stage = stage;
+    return L;
+}
+
 int sph_sample_points_device(SphEngine* e, const float* devPoints4, size_t m, SphSample* devOut) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (m && (!devPoints4 || !devOut)) return fail(SPH_ERR_ARG, "null argument");
@@ -2918,14 +2944,7 @@ int sph_sample_lattice(SphEngine* e, const float origin[3], const float spacing[
     SimK k;
     int rc;
     if ((rc = check_lattice(dims, spacing, 1, nullptr)) || (rc = sample_grid(e, k))) return rc;
-    LatticeK L;
-    L.ox = origin[0]; L.oy = origin[1]; L.oz = origin[2];
-    L.sx = spacing[0]; L.sy = spacing[1]; L.sz = spacing[2];
-    L.dx = dims[0]; L.dy = dims[1]; L.dz = dims[2];
-    L.nbx = (dims[0] + kBrickX - 1) / kBrickX; L.nby = (dims[1] + kBrickY - 1) / kBrickY;
-    L.nBricks = (long long)L.nbx * L.nby * ((dims[2] + kBrickZ - 1) / kBrickZ);
-    L.field = field;
-    L.stage = kSampleStage;
+    const LatticeK L = lattice_consts(origin, spacing, dims, field, kSampleStage);
     {
         Timed t(e, SPH_K_OTHER);
         hipLaunchKernelGGL(k_sample_lattice, dim3((unsigned)std::min<long long>(L.nBricks, 1ll << 20)), dim3(kBlock), 0, e->stream, k, L,
@@ -3949,6 +3968,269 @@ int sph_surface_download(SphEngine* e, SphSurfaceVertex* vertices, size_t vertex
     if (e->surfNumV) HIP_TRY(hipMemcpyAsync(vertices, e->d_surfVerts.p, (size_t)e->surfNumV * sizeof(SphSurfaceVertex), hipMemcpyDeviceToHost, e->stream));
     if (e->surfNumT) HIP_TRY(hipMemcpyAsync(triangles3, e->d_surfTris.p, (size_t)e->surfNumT * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// ---- anisotropic kernels (sph_aniso.h; behind the surface section: sph_aniso_surface ends in its mesher) ------
+static_assert(sizeof(SphAniso) == 64 && sizeof(SphAnisoConfig) == 32 && sizeof(SphAnisoInfo) == 56, "SphAniso is 64 bytes, SphAnisoConfig 32, SphAnisoInfo 56");
+static_assert(sizeof(sph::AnisoRow) == sizeof(SphAniso) && offsetof(sph::AnisoRow, count) == offsetof(SphAniso, count) &&
+              offsetof(sph::AnisoRow, flags) == offsetof(SphAniso, flags) && offsetof(sph::AnisoRow, reach) == offsetof(SphAniso, reach) &&
+              offsetof(sph::AnisoRow, amplitude) == offsetof(SphAniso, amplitude), "sph_aniso.h mirrors SphAniso");
+static_assert(SPH_ANISO_FLUID_ONLY == sph::kAnisoFluidOnly && SPH_ANISO_VALID == sph::kAnisoValid && SPH_ANISO_SPARSE == sph::kAnisoSparse &&
+              SPH_ANISO_CLAMPED == sph::kAnisoClamped, "sph_aniso.h mirrors SPH_ANISO_*");
+
+void sph_aniso_default(SphAnisoConfig* cfg) {
+    if (!cfg) return;
+    cfg->radius = 0.0f; cfg->support = 0.0f; cfg->smoothing = 0.9f; cfg->maxRatio = 4.0f; cfg->maxStretch = 1.5f; cfg->sparseScale = 0.5f;
+    cfg->minCount = 25u; cfg->flags = 0;
+}
+
+// The config as an argument: the constants of a build (radius and support in force), the stencil half-width through *stencil.
+static int aniso_check(const SphAnisoConfig& cfg, float h, float cellSize, sph::AnisoK* ak, float* radius, int* stencil) {
+    if (cfg.flags & ~SPH_ANISO_FLUID_ONLY) return fail(SPH_ERR_ARG, "unknown anisotropy flags %d", cfg.flags);
+    if (!std::isfinite(cfg.support)) return fail(SPH_ERR_ARG, "support %g is not finite", (double)cfg.support);
+    if (!(cfg.smoothing >= 0.0f && cfg.smoothing <= 1.0f)) return fail(SPH_ERR_ARG, "smoothing %g is not in [0, 1]", (double)cfg.smoothing);
+    if (!std::isfinite(cfg.maxRatio) || !(cfg.maxRatio >= 1.0f)) return fail(SPH_ERR_ARG, "maxRatio %g is not finite or < 1", (double)cfg.maxRatio);
+    if (!std::isfinite(cfg.maxStretch) || !(cfg.maxStretch > 0.0f)) return fail(SPH_ERR_ARG, "maxStretch %g is not finite or <= 0", (double)cfg.maxStretch);
+    if (!std::isfinite(cfg.sparseScale) || !(cfg.sparseScale > 0.0f)) return fail(SPH_ERR_ARG, "sparseScale %g is not finite or <= 0", (double)cfg.sparseScale);
+    *radius = cfg.radius <= 0.0f ? 2.0f * h : cfg.radius;
+    int rc;
+    if ((rc = radius_stencil(*radius, cellSize, stencil))) return rc;
+    ak->R2 = *radius * *radius;
+    ak->scale = 11.0f / ak->R2;
+    ak->support = cfg.support <= 0.0f ? h : cfg.support;
+    ak->lambda = cfg.smoothing; ak->maxRatio = cfg.maxRatio; ak->maxStretch = cfg.maxStretch; ak->sparseScale = cfg.sparseScale;
+    ak->minCount = cfg.minCount;
+    return SPH_OK;
+}
+// A lattice of nodes as an argument of the anisotropic field: check_lattice with dimensions >= 0 (a 0 is an empty lattice: *total 0).
+static int aniso_check_lattice(const float origin[3], const float spacing[3], const int dims[3], long long* total) {
+    if (!origin) return fail(SPH_ERR_ARG, "null argument");
+    return check_lattice(dims, spacing, 0, total);
+}
+static void aniso_fill_info(SphAnisoInfo& info, size_t rows, float radius, float support, int stencil, float cellSize, int flags) {
+    info.rows = rows; info.radius = radius; info.support = support; info.stencil = stencil; info.kind = 1; info.flags = flags;
+    info.reachStencil = sph::neighbor_stencil(info.maxReach, cellSize);
+}
+// The field needs every ellipsoid inside the widest stencil.
+static int aniso_check_reach(const SphAnisoInfo& info, float cellSize) {
+    if (!(info.maxReach <= 3.0f * cellSize))
+        return fail(SPH_ERR_ARG, "maxReach %g is above three cells (%g): lower support, maxStretch or smoothing", (double)info.maxReach, (double)(3.0f * cellSize));
+    return SPH_OK;
+}
+
+// Grid of the current state, ids, the gather, one synchronisation for the four words of the reduction.  *kOut / *cellSize: the grid it ran on.
+static int aniso_run(SphEngine* e, const SphAnisoConfig& cfg, SphAnisoInfo* out, SimK* kOut, float* cellSize) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    AnisoK ak;
+    int rc, stencil = 0;
+    float radius = 0.0f;
+    if ((rc = query_grid(e, g)) || (rc = aniso_check(cfg, e->params.param_h, g.cellSize, &ak, &radius, &stencil))) return rc;
+    const size_t n = e->n;
+    e->anisoInfo = SphAnisoInfo{};                                                  // (the rows held so far end here)
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_anRows.grow(e, n)) || (rc = e->d_anSlots.grow(e, 3 * n)) || (rc = e->d_anStats.grow(e, 4))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, radius, stencil, cfg.flags);
+    unsigned long long stats[4] = {0ull, 0ull, 0ull, 0ull};
+    if (n) {
+        HIP_TRY(hipMemsetAsync(e->d_anStats.p, 0, sizeof(stats), e->stream));
+        slot_ids_fill(e);
+        {
+            Timed t(e, SPH_K_OTHER);
+            hipLaunchKernelGGL(k_aniso_gather, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, nb, ak, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                               (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn, n, e->d_anRows.p, e->d_anSlots.p, e->d_anStats.p);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(stats, e->d_anStats.p, sizeof(stats), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphAnisoInfo info{};
+    info.numSparse = stats[0]; info.numClamped = stats[1]; info.maxCount = (uint32_t)stats[2];
+    const uint32_t reachBits = (uint32_t)stats[3];
+    memcpy(&info.maxReach, &reachBits, 4);
+    aniso_fill_info(info, n, radius, ak.support, stencil, g.cellSize, cfg.flags);
+    e->anisoInfo = info;
+    *out = info;
+    if (kOut) *kOut = k;
+    if (cellSize) *cellSize = g.cellSize;
+    return SPH_OK;
+}
+
+int sph_aniso_build(SphEngine* e, const SphAnisoConfig* cfg, SphAnisoInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !out) return fail(SPH_ERR_ARG, "null argument");
+    return aniso_run(e, *cfg, out, nullptr, nullptr);
+}
+
+int sph_aniso_info(const SphEngine* e, SphAnisoInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->anisoInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no anisotropy rows");
+    *out = e->anisoInfo;
+    return SPH_OK;
+}
+
+int sph_aniso_device(SphEngine* e, const SphAniso** rows) {
+    if (!e || !rows) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->anisoInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no anisotropy rows");
+    *rows = reinterpret_cast<const SphAniso*>(e->d_anRows.p);
+    return SPH_OK;
+}
+
+int sph_aniso_download(SphEngine* e, SphAniso* rows) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->anisoInfo.kind) return fail(SPH_ERR_STATE, "the engine holds no anisotropy rows");
+    const size_t r = (size_t)e->anisoInfo.rows;
+    if (rows && r) HIP_TRY(hipMemcpyAsync(rows, e->d_anRows.p, r * sizeof(SphAniso), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// The rows, then the lattice kernel behind them (arguments already checked; total > 0 nodes or none).
+static int aniso_lattice_run(SphEngine* e, const SphAnisoConfig& cfg, const float origin[3], const float spacing[3], const int dims[3], long long total,
+                             float* devOut, SphAnisoInfo* out) {
+    using namespace sph;
+    SimK k;
+    float cellSize = 0.0f;
+    int rc;
+    if ((rc = aniso_run(e, cfg, out, &k, &cellSize)) || (rc = aniso_check_reach(*out, cellSize))) return rc;
+    if (!total) return SPH_OK;
+    const LatticeK L = lattice_consts(origin, spacing, dims, kFieldFraction, 0);      // (field and stage are not read)
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_aniso_lattice, dim3((unsigned)std::min<long long>(L.nBricks, 1ll << 20)), dim3(kBlock), 0, e->stream, k, L, out->reachStencil,
+                           (uint32_t)e->n, e->params.param_mass, (const float4*)e->d_anSlots.p, (const uint32_t*)e->d_cellStart, devOut);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aniso_lattice(SphEngine* e, const SphAnisoConfig* cfg, const float origin[3], const float spacing[3], const int dims[3], float* devOut, SphAnisoInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !out) return fail(SPH_ERR_ARG, "null argument");
+    long long total = 0;
+    int rc;
+    if ((rc = aniso_check_lattice(origin, spacing, dims, &total))) return rc;
+    if (total && !devOut) return fail(SPH_ERR_ARG, "null argument");
+    return aniso_lattice_run(e, *cfg, origin, spacing, dims, total, devOut, out);
+}
+
+int sph_aniso_surface(SphEngine* e, const SphAnisoConfig* cfg, const float origin[3], const float spacing[3], const int dims[3], float iso, SphSurface* out,
+                      SphAnisoInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    e->surfValid = false;                                             // (any failure below leaves no surface: sph_abi.h)
+    if (!cfg || !out || !info) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = surface_check_lattice(origin, spacing, dims, iso)) || (rc = query_refused(e))) return rc;
+    const size_t npts = (size_t)dims[0] * dims[1] * dims[2];
+    if ((rc = e->d_surfVol.grow(e, npts))) return rc;
+    if ((rc = aniso_lattice_run(e, *cfg, origin, spacing, dims, (long long)npts, e->d_surfVol.p, info))) return rc;
+    return surface_mesh(e, e->d_surfVol.p, origin, spacing, dims, iso, out);
+}
+
+// The rows and the slot records (by sorted slot of `grid`) of host records: what both twins start from.
+static void aniso_rows_host(const SphParticle* particles, size_t n, const sph::HostGrid& grid, int stencil, const sph::AnisoK& ak, bool fluidOnly,
+                            std::vector<sph::AnisoRow>& res, std::vector<sph::AnisoSlot>& slots, SphAnisoInfo& info) {
+    const std::vector<uint32_t>& order = grid.order;
+    res.resize(n);
+    slots.resize(n);
+    for (size_t r = 0; r < n; ++r) {
+        const float* x = particles[r].pos;
+        sph::AnisoSlot& slot = slots[grid.slotOf[r]];
+        sph::aniso_zero(res[r], slot);
+        bool walk = sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2]);
+        if (fluidOnly && particles[r].isGhost != 0) walk = false;
+        if (!walk) continue;
+        sph::AnisoAcc a;
+        sph::aniso_reset(a);
+        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                const uint32_t o = order[j];
+                const float* y = particles[o].pos;
+                float dx, dy, dz, r2;
+                if (!sph::aniso_accept(x[0], x[1], x[2], y[0], y[1], y[2], ak.R2, dx, dy, dz, r2)) continue;
+                if (fluidOnly && particles[o].isGhost != 0) continue;
+                sph::aniso_add(a, dx, dy, dz, r2, ak.R2);
+            }
+        });
+        const float invRho = particles[r].density > 0.0f ? 1.0f / particles[r].density : 0.0f;
+        if (a.cnt) sph::aniso_finish(a, ak, x[0], x[1], x[2], invRho, res[r], slot);
+        if (res[r].flags & sph::kAnisoSparse) info.numSparse += 1u;
+        if (res[r].flags & sph::kAnisoClamped) info.numClamped += 1u;
+        info.maxCount = std::max(info.maxCount, res[r].count);
+        if (res[r].reach > info.maxReach) info.maxReach = res[r].reach;
+    }
+}
+
+// What both twins open with: the params, the grid they give, the config; then the rows.
+static int aniso_host_open(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, SimK& k, SphGridInfo& g,
+                           sph::AnisoK& ak, float* radius, int* stencil) {
+    if (!params || !cfg || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    sph::compute_grid_extents(*params, g);
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    return aniso_check(*cfg, params->param_h, g.cellSize, &ak, radius, stencil);
+}
+
+int sph_aniso_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, SphAniso* rowsOut, SphAnisoInfo* out) {
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    SphGridInfo g;
+    sph::AnisoK ak;
+    int rc, stencil = 0;
+    float radius = 0.0f;
+    if ((rc = aniso_host_open(particles, n, params, cfg, k, g, ak, &radius, &stencil))) return rc;
+    const sph::HostGrid grid(k, particles, n);
+    std::vector<sph::AnisoRow> res;
+    std::vector<sph::AnisoSlot> slots;
+    SphAnisoInfo info{};
+    aniso_rows_host(particles, n, grid, stencil, ak, (cfg->flags & SPH_ANISO_FLUID_ONLY) != 0, res, slots, info);
+    aniso_fill_info(info, n, radius, ak.support, stencil, g.cellSize, cfg->flags);
+    if (rowsOut && n) memcpy(rowsOut, res.data(), n * sizeof(SphAniso));
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_aniso_lattice_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, const float origin[3],
+                           const float spacing[3], const int dims[3], float* values, SphAnisoInfo* out) {
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    long long total = 0;
+    int rc, stencil = 0;
+    if ((rc = aniso_check_lattice(origin, spacing, dims, &total))) return rc;
+    if (total && !values) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    SphGridInfo g;
+    sph::AnisoK ak;
+    float radius = 0.0f;
+    if ((rc = aniso_host_open(particles, n, params, cfg, k, g, ak, &radius, &stencil))) return rc;
+    const sph::HostGrid grid(k, particles, n);
+    std::vector<sph::AnisoRow> res;
+    std::vector<sph::AnisoSlot> slots;
+    SphAnisoInfo info{};
+    aniso_rows_host(particles, n, grid, stencil, ak, (cfg->flags & SPH_ANISO_FLUID_ONLY) != 0, res, slots, info);
+    aniso_fill_info(info, n, radius, ak.support, stencil, g.cellSize, cfg->flags);
+    *out = info;
+    if ((rc = aniso_check_reach(info, g.cellSize))) return rc;
+    for (long long p = 0; p < total; ++p) {
+        const int i = (int)(p % dims[0]), j = (int)((p / dims[0]) % dims[1]), l = (int)(p / ((long long)dims[0] * dims[1]));
+        const float x[3] = {sph::aniso_coord(origin[0], i, spacing[0]), sph::aniso_coord(origin[1], j, spacing[1]), sph::aniso_coord(origin[2], l, spacing[2])};
+        float acc = 0.0f;
+        const bool finite = sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2]);
+        if (finite) {
+            grid.rows(info.reachStencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t q = qs; q < qe; ++q) {
+                    const sph::AnisoSlot& s = slots[q];
+                    float rx, ry, rz;
+                    if (!sph::aniso_node_near(x[0], x[1], x[2], s.cx, s.cy, s.cz, s.rho2, rx, ry, rz)) continue;
+                    acc = sph::aniso_node_term(rx, ry, rz, s.qxx, s.qyy, s.qzz, s.qxy, s.qxz, s.qyz, s.amp, acc);
+                }
+            });
+        }
+        values[p] = finite ? sph::aniso_node_value(params->param_mass, acc) : 0.0f;
+    }
     return SPH_OK;
 }
 

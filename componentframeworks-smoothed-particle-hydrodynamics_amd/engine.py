@@ -328,6 +328,33 @@ SPH_SHELL_FLUID_ONLY = 1
 SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED = 1, 2
 
 
+class SphAniso(C.Structure):
+    """struct SphAniso of include/sph_abi.h: the smoothed centre and the ellipsoid of one particle (see SPHFluidGPU.anisotropy)."""
+    _fields_ = [("center", C.c_float * 3), ("count", C.c_uint32), ("axis0", C.c_float * 3), ("flags", C.c_uint32), ("axis1", C.c_float * 3),
+                ("reach", C.c_float), ("axis2", C.c_float * 3), ("amplitude", C.c_float)]
+
+
+class SphAnisoConfig(C.Structure):
+    """struct SphAnisoConfig of include/sph_abi.h: radius (<= 0: 2 param_h), support (<= 0: param_h), smoothing, maxRatio, maxStretch,
+    sparseScale, minCount, flags (see aniso_config())."""
+    _fields_ = [("radius", C.c_float), ("support", C.c_float), ("smoothing", C.c_float), ("maxRatio", C.c_float), ("maxStretch", C.c_float),
+                ("sparseScale", C.c_float), ("minCount", C.c_uint32), ("flags", C.c_int32)]
+
+
+class SphAnisoInfo(C.Structure):
+    """struct SphAnisoInfo of include/sph_abi.h: what the engine's anisotropy rows hold."""
+    _fields_ = [("rows", C.c_uint64), ("numSparse", C.c_uint64), ("numClamped", C.c_uint64), ("maxCount", C.c_uint32), ("radius", C.c_float),
+                ("support", C.c_float), ("stencil", C.c_int32), ("maxReach", C.c_float), ("reachStencil", C.c_int32), ("kind", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+assert C.sizeof(SphAniso) == 64 and C.sizeof(SphAnisoConfig) == 32 and C.sizeof(SphAnisoInfo) == 56
+ANISO_DTYPE = np.dtype(SphAniso)
+assert ANISO_DTYPE.itemsize == 64
+SPH_ANISO_FLUID_ONLY = 1
+SPH_ANISO_VALID, SPH_ANISO_SPARSE, SPH_ANISO_CLAMPED = 1, 2, 4
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -504,6 +531,16 @@ _ABI = {
     "sph_shell_device": (_int, [_vp, _P(_vp), _P(_vp)]),
     "sph_shell_download": (_int, [_vp, _vp, _vp]),
     "sph_shell_host": (_int, [_vp, _sz, _pp, _vp, _sz, _P(SphShellConfig), _vp, _vp, _vp, _P(SphShellInfo)]),
+    # anisotropic kernels
+    "sph_aniso_default": (None, [_P(SphAnisoConfig)]),
+    "sph_aniso_build": (_int, [_vp, _P(SphAnisoConfig), _P(SphAnisoInfo)]),
+    "sph_aniso_info": (_int, [_vp, _P(SphAnisoInfo)]),
+    "sph_aniso_device": (_int, [_vp, _P(_vp)]),
+    "sph_aniso_download": (_int, [_vp, _vp]),
+    "sph_aniso_lattice": (_int, [_vp, _P(SphAnisoConfig), _pf, _pf, _pi, _vp, _P(SphAnisoInfo)]),
+    "sph_aniso_surface": (_int, [_vp, _P(SphAnisoConfig), _pf, _pf, _pi, _f, _P(SphSurface), _P(SphAnisoInfo)]),
+    "sph_aniso_host": (_int, [_vp, _sz, _pp, _P(SphAnisoConfig), _vp, _P(SphAnisoInfo)]),
+    "sph_aniso_lattice_host": (_int, [_vp, _sz, _pp, _P(SphAnisoConfig), _pf, _pf, _pi, _vp, _P(SphAnisoInfo)]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -1429,6 +1466,60 @@ class SPHFluidGPU:
         spec = ((rows, 8), None, "float32") if device else (rows, SHELL_DTYPE, None)    # (one device copy of the 32-byte rows)
         return _fetch(lambda p_rows, p_ids: self._L.sph_shell_download(self._h, p_rows, p_ids), device, (spec, (ns, np.int32, "int32")))
 
+    # -- anisotropic kernels (include/sph_abi.h "anisotropic kernels") ------------------------------
+    def anisotropy(self, radius=None, support=None, smoothing: float = 0.9, max_ratio: float = 4.0, max_stretch: float = 1.5, min_count: int = 25,
+                   sparse_scale: float = 0.5, fluid_only: bool = False, device: bool = False):
+        """Per particle the smoothed centre and the ellipsoid of the anisotropic kernel (Yu & Turk 2013): an
+        ANISO_DTYPE array numbered by particle id (center, count, axis0 / axis1 / axis2: the semi-axis vectors in world units, longest
+        first, flags: SPH_ANISO_VALID / _SPARSE / _CLAMPED, reach, amplitude).  radius (None: 2 param_h; at most three cells) bounds
+        the neighbourhood whose weighted covariance shapes the ellipsoid, support (None: param_h) scales it, smoothing pulls the centre
+        towards the neighbourhood's mean, max_ratio bounds longest / shortest axis, max_stretch the longest axis in units of support;
+        a particle with fewer than min_count neighbours gets a sphere of sparse_scale * support.  fluid_only leaves the records with
+        isGhost != 0 out of every sum and gives them all-zero rows.  With device=True an (n, 16) float32 torch device tensor (columns
+        0:3 center, 4:7 axis0, 8:11 axis1, 11 reach, 12:15 axis2, 15 amplitude; 3 / 7 count / flags as bits)."""
+        self._push_params()
+        info = SphAnisoInfo()
+        cfg = _aniso_cfg(radius, support, smoothing, max_ratio, max_stretch, min_count, sparse_scale, fluid_only)
+        _check(self._L.sph_aniso_build(self._h, C.byref(cfg), C.byref(info)))
+        return self.aniso_rows(device)
+
+    def aniso_info(self) -> SphAnisoInfo:
+        """What the engine's anisotropy rows hold: rows, numSparse, numClamped, maxCount, radius, support, stencil, maxReach,
+        reachStencil, kind, flags.  SphError before any anisotropy() / aniso_lattice() / aniso_surface() call."""
+        return self._info(SphAnisoInfo, self._L.sph_aniso_info)
+
+    def aniso_rows(self, device: bool = False):
+        """The anisotropy rows the engine holds."""
+        rows = int(self.aniso_info().rows)
+        spec = ((rows, 16), None, "float32") if device else (rows, ANISO_DTYPE, None)   # (one device copy of the 64-byte rows)
+        return _fetch(lambda p_rows: self._L.sph_aniso_download(self._h, p_rows), device, (spec,))[0]
+
+    def aniso_lattice(self, origin, spacing, dims, device: bool = False, **cfg):
+        """The anisotropic fraction on the lattice origin + i * spacing (dims = (nx, ny, nz), x fastest), summed from the ellipsoids of
+        a fresh anisotropy(**cfg) build: float32 of shape (nz, ny, nx), a numpy array or with device=True a torch device tensor.
+        SphError where the largest reach exceeds three cells (aniso_info() then still describes the rows)."""
+        import torch
+        nx, ny, nz = (int(x) for x in dims)
+        buf = torch.empty((max(nz, 0), max(ny, 0), max(nx, 0)), dtype=torch.float32, device="cuda")
+        self._push_params()
+        info = SphAnisoInfo()
+        _check(self._L.sph_aniso_lattice(self._h, C.byref(_aniso_cfg(**cfg)), _f3(origin), _f3(_spacing3(spacing)), _dims3((nx, ny, nz)),
+                                         C.c_void_p(buf.data_ptr()) if buf.numel() else None, C.byref(info)))
+        self.sync()
+        return buf if device else buf.cpu().numpy()
+
+    def aniso_surface(self, origin=None, spacing=None, dims=None, iso: float = 0.5, **cfg):
+        """Iso-surface {anisotropic fraction >= iso} as a closed triangle mesh, flatter on flat water and thinner on sheets than
+        surface(): (vertices of SURFACE_VERTEX_DTYPE, triangles (T, 3) uint32).  Lattice members left None come from
+        default_surface_lattice(); cfg: the arguments of anisotropy()."""
+        do, ds, dd = self.default_surface_lattice() if origin is None or spacing is None or dims is None else (None, None, None)
+        surf, info = SphSurface(), SphAnisoInfo()
+        self._push_params()
+        _check(self._L.sph_aniso_surface(self._h, C.byref(_aniso_cfg(**cfg)), _f3(do if origin is None else origin),
+                                         _f3(_spacing3(ds if spacing is None else spacing)), _dims3(dd if dims is None else dims), float(iso),
+                                         C.byref(surf), C.byref(info)))
+        return self._download_surface(surf)
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -2106,6 +2197,42 @@ def shell_host(records, params, radius=None, offset=0.10, min_count=0, fluid_onl
     _check(load_library().sph_shell_host(*head, C.byref(cfg), _ptr_or_none(out), _ptr_or_none(ids), _ptr_or_none(acc) if sums else None, C.byref(info)))
     res = (out, ids[:int(info.numShell)].copy(), info)
     return res + (acc,) if sums else res
+
+
+def aniso_config(**overrides) -> SphAnisoConfig:
+    """sph_aniso_default with the named fields replaced.  No device is needed."""
+    cfg = SphAnisoConfig()
+    load_library().sph_aniso_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def _aniso_cfg(radius=None, support=None, smoothing=0.9, max_ratio=4.0, max_stretch=1.5, min_count=25, sparse_scale=0.5, fluid_only=False) -> SphAnisoConfig:
+    """The config of anisotropy(), aniso_lattice(), aniso_surface() and the two twins; radius / support None go as 0: the library's
+    defaults, 2 param_h and param_h."""
+    return aniso_config(radius=0.0 if radius is None else radius, support=0.0 if support is None else support, smoothing=smoothing, maxRatio=max_ratio,
+                        maxStretch=max_stretch, sparseScale=sparse_scale, minCount=min_count, flags=SPH_ANISO_FLUID_ONLY if fluid_only else 0)
+
+
+def aniso_host(records, params, **cfg):
+    """sph_aniso_host: (rows, info) of SPHFluidGPU.anisotropy(**cfg) on host records, computed on the CPU by the device's own sum and
+    finish functions over the counting sort of neighbors_host, in the same order: the same bytes.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    out = np.zeros(len(rec), ANISO_DTYPE)
+    info = SphAnisoInfo()
+    _check(load_library().sph_aniso_host(_ptr_or_none(rec), len(rec), C.byref(params), C.byref(_aniso_cfg(**cfg)), _ptr_or_none(out), C.byref(info)))
+    return out, info
+
+
+def aniso_lattice_host(records, params, origin, spacing, dims, **cfg):
+    """sph_aniso_lattice_host: (values of shape (nz, ny, nx), info) of SPHFluidGPU.aniso_lattice on host records, computed on the CPU
+    in the same order: the same bytes.  No device is needed."""
+    rec = np.ascontiguousarray(records, PARTICLE_DTYPE)
+    nx, ny, nz = (int(x) for x in dims)
+    out = np.zeros((max(nz, 0), max(ny, 0), max(nx, 0)), np.float32)
+    info = SphAnisoInfo()
+    _check(load_library().sph_aniso_lattice_host(_ptr_or_none(rec), len(rec), C.byref(params), C.byref(_aniso_cfg(**cfg)), _f3(origin),
+                                                 _f3(_spacing3(spacing)), _dims3((nx, ny, nz)), _ptr(out) if out.size else None, C.byref(info)))
+    return out, info
 
 
 def rays_host(records, params, rays, radius, fluid_only=False, any_hit=False, with_info=False, walk=False):

@@ -278,6 +278,51 @@ public:
         ids.assign(size_t(info.numShell), 0);
         return !Check(sph_shell_download(engine, rows.empty() ? nullptr : rows.data(), ids.empty() ? nullptr : ids.data()), "sph_shell_download");
     }
+    // Anisotropic kernels (engine extension, sph_abi.h "anisotropic kernels"): per particle (rows numbered by
+    // particle id) a smoothed centre and the three semi-axis vectors of an ellipsoid shaped by the neighbourhood, and the lattice of the
+    // anisotropic fraction summed from those ellipsoids with its iso-surface.  cfg: sph_aniso_default's fields (radius <= 0: 2 param_h,
+    // support <= 0: param_h).  The rows stay in the engine until the next of these calls, ResetSimulation or the destructor;
+    // DownloadAniso copies them to the host.  AnisoLattice writes dims[0] * dims[1] * dims[2] floats (x fastest) to DEVICE memory;
+    // ExtractAnisoSurface meshes that lattice as ExtractSurface meshes a field (DownloadSurface copies the result).  Members are pushed
+    // first, as DispatchCompute does.  Return false on error (LastError()).
+    static SphAnisoConfig AnisoConfig() {
+        SphAnisoConfig cfg;
+        sph_aniso_default(&cfg);
+        return cfg;
+    }
+    bool Anisotropy(SphAnisoInfo& out, const SphAnisoConfig& cfg) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aniso_build(engine, &cfg, &out), "sph_aniso_build");
+    }
+    SphAnisoInfo AnisoInfo() {
+        SphAnisoInfo info{};
+        Check(sph_aniso_info(engine, &info), "sph_aniso_info");
+        return info;
+    }
+    bool DownloadAniso(std::vector<SphAniso>& rows) {
+        SphAnisoInfo info{};
+        if (Check(sph_aniso_info(engine, &info), "sph_aniso_info")) return false;
+        rows.assign(size_t(info.rows), SphAniso{});
+        return !Check(sph_aniso_download(engine, rows.empty() ? nullptr : rows.data()), "sph_aniso_download");
+    }
+    bool AnisoLattice(const SphAnisoConfig& cfg, const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        SphAnisoInfo info{};
+        return !Check(sph_aniso_lattice(engine, &cfg, o, s, dims, devOut, &info), "sph_aniso_lattice");
+    }
+    bool ExtractAnisoSurface(const SphAnisoConfig& cfg, const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], float iso, SphSurface& out) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        SphAnisoInfo info{};
+        surface = SphSurface{};
+        if (Check(sph_aniso_surface(engine, &cfg, o, s, dims, iso, &out, &info), "sph_aniso_surface")) return false;
+        surface = out;
+        return true;
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

@@ -51,6 +51,7 @@ extern "C" {
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
 /* (still 4, additions only: SphRayHit, SphRaysInfo, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, sph_rays_cast / _cast_device / _info / _device / _download / _host / _walk_host, SPH_OPT_RAYS_VARIANT -- ray casts against the particles) */
+/* (still 4, additions only: SphAniso, SphAnisoConfig, SphAnisoInfo, SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID / _SPARSE / _CLAMPED, sph_aniso_default / _build / _info / _device / _download / _lattice / _surface / _host / _lattice_host -- anisotropic kernels) */
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
@@ -1034,6 +1035,71 @@ int sph_shell_download(SphEngine* e, SphShell* rows, int32_t* ids);
  * row (Sx, Sy, Sz, W) -- what the tests hold against a float64 restatement. */
 int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* params, const float* points4, size_t m, const SphShellConfig* cfg,
                    SphShell* rows, int32_t* ids, float* sums4, SphShellInfo* out);
+
+/* ---- anisotropic kernels (no reference counterpart) -------------------------------------------------------------
+ * Per particle a smoothed centre and an ellipsoid from the weighted covariance of its neighbourhood (Yu & Turk 2013), and the lattice
+ * of the anisotropic fraction summed from those ellipsoids, whose iso-surface is flatter on flat water and thinner on sheets than the
+ * surface of SPH_FIELD_FRACTION.  Grid, radius rules (0 < R <= 3 cells), stencil, candidate order and r2 are those of the neighbour
+ * lists above.  SphAnisoConfig: radius R (<= 0: 2 * param_h), support a (<= 0: param_h; finite), smoothing lambda (0 .. 1), maxRatio kr
+ * (finite, >= 1), maxStretch (finite, > 0), sparseScale kn (finite, > 0), minCount, flags (SPH_ANISO_FLUID_ONLY: records with
+ * isGhost != 0 are never candidates and their own rows are all zero).
+ * Sums, for a particle at x over every accepted candidate j (r2 < R2; the particle's own slot is one of them: d = 0) in the order of
+ * the (2s + 1)^2 candidate rows, with d = x_j - x, t = R2 - r2, w = (t * t) * t:  count += 1, W += w, S_a = fmaf(w, d_a, S_a),
+ * M_ab = fmaf(w * d_a, d_b, M_ab) for ab in xx, yy, zz, xy, xz, yz.
+ * Finish: m_a = S_a / W; C_ab = (M_ab / W - m_a * m_b) * (11.0f / R2) (the identity for a full, uniformly filled neighbourhood); C is
+ * eigen-decomposed by five sweeps of cyclic Jacobi over the pairs (0,1), (0,2), (1,2) (a step is skipped when a_pq == 0; th = (a_qq -
+ * a_pp) / (2 a_pq), t = 1 / (|th| + sqrtf(th * th + 1)) negated when th < 0, c = 1 / sqrtf(t * t + 1), s = t * c, a_pp -= t a_pq,
+ * a_qq += t a_pq, a_pq = 0, the remaining pair and the columns of V rotated as (x, y) -> (fmaf(-s, y, c * x), fmaf(s, x, c * y))); the
+ * eigenvalues are sorted in descending order by the exchanges (0,1), (1,2), (0,1) with a strict compare, columns with them;
+ * s_k = sqrtf(max(l_k, 0)).  The row is SPARSE if count < minCount or !(s_0 > 0): then s = (kn, kn, kn) and the axes are the coordinate
+ * axes.  Otherwise s_0 = min(s_0, maxStretch), s_k = min(max(s_k, s_0 / kr), maxStretch), and the row is CLAMPED if any s_k changed.
+ * Row (SphAniso, 64 bytes, numbered by particle id): center = fmaf(lambda, m, x); axisK = (a * s_k) * v_k, the ellipsoid's semi-axis
+ * vectors in world units, longest first (their handedness is not fixed); reach = a * s_0 + |center - x|: how far from the particle's
+ * own position its ellipsoid can be met; amplitude = invRho * ((i_0 * i_1) * i_2), i_k = 1 / (a * s_k), invRho the word the fraction
+ * sampler reads (density > 0 ? 1.0f / density : 0.0f).  A particle with a non-finite position has an all-zero row (no SPH_ANISO_VALID)
+ * and is never a candidate; under SPH_ANISO_FLUID_ONLY so has a ghost.
+ * Field: a lattice node at x = origin + (float)i * spacing (x fastest, the coordinates of sph_sample_lattice) walks the candidate rows
+ * at reachStencil = the stencil of the largest reach around its cell; per candidate r = x - center_j, skipped unless dot3(r, r) <
+ * (a * s_0)^2; q2 = r' Q r with Q = sum_k (i_k * i_k) v_k v_k'; u = max(1 - q2, 0); acc = fmaf(amplitude_j, (u * u) * u, acc); the
+ * node's value is (param_mass * 1.5666815f) * acc (315 / (64 pi)); a node with a non-finite coordinate gets 0.  With every s_k = 1 and
+ * a = h this is SPH_FIELD_FRACTION up to rounding.  If the largest reach exceeds three cells, sph_aniso_lattice and sph_aniso_surface
+ * refuse with SPH_ERR_ARG ("maxReach ..."): the rows of that build are still held (sph_aniso_info says how large it was); lower
+ * support, maxStretch or smoothing.
+ * IEEE division and square root on both sides, every other operation rounded on its own except the fmaf()s (csrc/sph_aniso.h lists
+ * them); no floating-point atomics: the same bytes on every run, and the bytes of sph_aniso_host / sph_aniso_lattice_host.
+ * The rows are the engine's own and stay valid until the next sph_aniso_build / _lattice / _surface, sph_reset or sph_destroy; no
+ * other family invalidates them, a dispatch does not touch them and a build never changes the simulation.  Timed as SPH_K_OTHER.
+ * SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as sampling); _info / _device / _download before any build.  SPH_ERR_ARG: a
+ * null argument, a config value outside its range, unknown flag bits, a negative lattice dimension, a spacing that is not finite or
+ * <= 0, more than 2^31 - 1 nodes.  n = 0 and a lattice with a dimension of 0: empty results, the call succeeds. */
+enum { SPH_ANISO_FLUID_ONLY = 1 };                    /* SphAnisoConfig.flags */
+enum { SPH_ANISO_VALID = 1, SPH_ANISO_SPARSE = 2, SPH_ANISO_CLAMPED = 4 };   /* SphAniso.flags */
+typedef struct SphAniso { float center[3]; uint32_t count; float axis0[3]; uint32_t flags; float axis1[3]; float reach; float axis2[3]; float amplitude; } SphAniso;   /* 64 bytes */
+typedef struct SphAnisoConfig { float radius, support, smoothing, maxRatio, maxStretch, sparseScale; uint32_t minCount; int32_t flags; } SphAnisoConfig;   /* 32 bytes */
+typedef struct SphAnisoInfo { uint64_t rows, numSparse, numClamped; uint32_t maxCount; float radius, support; int32_t stencil; float maxReach; int32_t reachStencil /*0: no reach, or above three cells*/, kind /*0 none, 1 particles*/, flags; } SphAnisoInfo;   /* 56 bytes */
+/* radius 0 (2 * param_h), support 0 (param_h), smoothing 0.9, maxRatio 4, maxStretch 1.5, sparseScale 0.5, minCount 25, flags 0. */
+void sph_aniso_default(SphAnisoConfig* cfg);
+/* Rows of every particle.  Synchronises. */
+int sph_aniso_build(SphEngine* e, const SphAnisoConfig* cfg, SphAnisoInfo* out);
+/* What the engine holds. */
+int sph_aniso_info(const SphEngine* e, SphAnisoInfo* out);
+/* Borrowed device address: rows[rows] (what a splat renderer binds). */
+int sph_aniso_device(SphEngine* e, const SphAniso** rows);
+/* Copies into the caller's memory, host or device (the kind of the copy follows from the address); synchronises. */
+int sph_aniso_download(SphEngine* e, SphAniso* rows);
+/* Builds the rows (as sph_aniso_build, one read-back of the info), then writes dims[0] * dims[1] * dims[2] floats to devOut in DEVICE
+ * memory, asynchronously on the engine's stream. */
+int sph_aniso_lattice(SphEngine* e, const SphAnisoConfig* cfg, const float origin[3], const float spacing[3], const int dims[3], float* devOut, SphAnisoInfo* out);
+/* The lattice into engine scratch, then the mesher of sph_extract_surface_volume: {value >= iso} as a closed triangle mesh (dims >= 2
+ * per axis).  `out` borrows from the engine under the rules of sph_extract_surface; sph_surface_download copies it. */
+int sph_aniso_surface(SphEngine* e, const SphAnisoConfig* cfg, const float origin[3], const float spacing[3], const int dims[3], float iso, SphSurface* out,
+                      SphAnisoInfo* info);
+/* Host-only, no device: the counting sort of sph_neighbors_host and the same sum, finish and node functions in the same order; the
+ * same bytes.  rows (n records) may be null. */
+int sph_aniso_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, SphAniso* rows, SphAnisoInfo* out);
+/* The twin of sph_aniso_lattice: values (dims[0] * dims[1] * dims[2] floats, x fastest) in host memory. */
+int sph_aniso_lattice_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, const float origin[3],
+                           const float spacing[3], const int dims[3], float* values, SphAnisoInfo* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one

@@ -1,6 +1,6 @@
 """What the tools/time_*.py scripts share: the package import, the config 3 scene and its two regimes, the sample statistics, the
 device-event brackets, the copy yardstick, the body grid of the obstacle tools, the head and tail of a result file, and for the tools
-of the spatial queries (time_neighbors, time_components, time_knn, time_rays, time_shell) the series of the engine's own brackets,
+of the spatial queries (time_neighbors, time_components, time_knn, time_rays, time_shell, time_aniso) the series of the engine's own brackets,
 the queries through the C ABI alone, and the torch route a query is compared with."""
 from __future__ import annotations
 
@@ -136,6 +136,11 @@ def rays_cast(f, dev, radius, flags):
 def shell_build(f, R):
     cfg = pkg.shell_config(radius=float(R))
     return _bare(f, f._L.sph_shell_build, pkg.SphShellInfo(), C.byref(cfg))
+
+
+def aniso_build(f, R):
+    cfg = pkg.aniso_config(radius=float(R))
+    return _bare(f, f._L.sph_aniso_build, pkg.SphAnisoInfo(), C.byref(cfg))
 
 
 def torch_route(route, compare, stream, reps):
