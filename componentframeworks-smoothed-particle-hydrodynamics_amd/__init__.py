@@ -23,7 +23,7 @@ from .engine import (  # noqa: F401
     SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_SPHERE, SPH_SOURCE_BOX, SPH_SOURCE_RATE, SPH_SOURCE_RELAX, SphScalarSource, SOURCE_DTYPE, scalar_source,
     source_array, scalars_couple_host,
     SPH_OPT_DIFFUSE_TIMED, SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE, SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, DIFFUSE_DTYPE, diffuse_config,
-    diffuse_step_host, write_points_ply,
+    diffuse_step_host, write_points_ply, SphDiffuseCrest, SphDiffuseCrestInfo, diffuse_crest_config,
     SPH_OPT_NEIGHBORS_FILL, SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY, SphNeighborInfo, neighbors_host,
     SPH_OPT_COMPONENTS_VARIANT, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, SphComponent, SphComponentInfo, COMPONENT_DTYPE, components_host,
     component_centers,

@@ -16,6 +16,14 @@
 // No float atomics, no integer atomics either; every launch is sized by C or N; every index derived from a device-side count is clamped
 // to C.  Every fp32 expression is a multiply, then an add (-ffp-contract=off: no fma); diffuse_move / diffuse_children / diffuse_child are
 // __host__ __device__ so that sph_diffuse_step_host runs the same statements.
+//
+// Crest births (the optional second birth term, sph_abi.h SphDiffuseCrest): the engine runs a free-surface pass by slot over the same
+// grid (sph_shell.h; this header does not include it) and hands its plain arrays to
+//   k_diffuse_count_crest  k_diffuse_count plus diffuse_crest_children from the slot's normal, crest sum and sorted velocity on an acting
+//                          substep; the block's crest children go to its row of crestPart[]
+//   k_diffuse_crest_tick   one block in front of k_diffuse_tick (which advances the counter): adds up crestPart[], then its thread 0
+//                          advances the crest books
+// diffuse_crest_children takes plain scalars and is __host__ __device__: sph_diffuse_step_host_crest runs it on SphShell rows.
 #pragma once
 #include "sph_tracer.h"   // built on the tracer's field sample: tracer_field
 
@@ -102,6 +110,44 @@ __host__ __device__ inline uint32_t diffuse_children(const DiffuseCoef& c, float
     return f > 0.0f ? (uint32_t)f : 0u;
 }
 
+// ---- crest births ----
+// The coefficients of the crest term as the kernels read them (device memory, beside DiffuseCoef: a replayed graph sees a later change).
+struct DiffuseCrestCoef {
+    float rate, crestMin, crestMax, speedMin, speedMax, align;
+    uint32_t every, pad;
+};
+// crest[] words (uint32): the books of the crest term
+enum : int { DFC_ACTING = 0 /* (lo, hi) */, DFC_SPAWNED = 2 /* (lo, hi) */, DFC_SHELL = 4, DFC_WORDS = 8 };
+
+// Does the term act on the substep whose counter, before the step, is (lo, hi)?
+__host__ __device__ inline bool diffuse_crest_acts(uint32_t lo, uint32_t hi, uint32_t every) {
+    return every != 0u && (((unsigned long long)hi << 32) | lo) % every == 0ull;
+}
+__host__ __device__ inline float diffuse_window(float x, float lo, float hi) { return fminf(fmaxf((x - lo) / (hi - lo), 0.0f), 1.0f); }
+
+// Children of the crest term of a fluid particle on an acting substep, before the cap on the sum with the foam term's.  (nx, ny, nz),
+// crest, member, isolated: the particle's free-surface row; (vx, vy, vz): its velocity.  Draw 33: the first draw diffuse_child leaves.
+__host__ __device__ inline uint32_t diffuse_crest_children(const DiffuseCoef& c, const DiffuseCrestCoef& cc, float dt, uint32_t flags, float invRho,
+                                                           bool member, bool isolated, float nx, float ny, float nz, float crest,
+                                                           float vx, float vy, float vz, uint32_t id, uint32_t stepLo, uint32_t stepHi) {
+    if (flags & F_GHOSTNZ) return 0u;
+    if (!(invRho > 0.0f)) return 0u;
+    if (!member || isolated) return 0u;
+    const float sp2 = dot3(vx, vy, vz, vx, vy, vz);
+    if (!diffuse_isfinite(sp2)) return 0u;
+    const float sp = sqrtf(sp2);
+    if (!(sp > 0.0f)) return 0u;
+    if (!(dot3(vx, vy, vz, nx, ny, nz) >= cc.align * sp)) return 0u;
+    const float pc = diffuse_window(crest, cc.crestMin, cc.crestMax);
+    const float pk = diffuse_window(sp, cc.speedMin, cc.speedMax);
+    const float p = pc * pk;
+    if (!(p > 0.0f)) return 0u;
+    const float lam = ((cc.rate * dt) * (float)cc.every) * p;
+    const float f = floorf(lam + diffuse_uniform(c.seed, id, stepLo, stepHi, 33u));
+    if (!(f < (float)c.maxPerParent)) return c.maxPerParent;
+    return f > 0.0f ? (uint32_t)f : 0u;
+}
+
 // Child k of parent id: draws 1 + 4 k .. 4 + 4 k.
 __host__ __device__ inline DiffuseRec diffuse_child(const DiffuseCoef& c, float h, float px, float py, float pz, float vx, float vy, float vz,
                                                     uint32_t id, uint32_t stepLo, uint32_t stepHi, uint32_t k) {
@@ -181,6 +227,40 @@ __global__ __launch_bounds__(kBlock) void k_diffuse_count(const float4* __restri
     cnt[idx] = diffuse_children(*coef, dt, o.y, fbits(o.z), pv[2u * s].w, fbits(o.w), state[DF_STEP_LO], state[DF_STEP_HI]);
 }
 
+// ---- child counts with the crest term: nrmSlot (normal, 0 outside the shell | 1 member | 2 isolated member) and crestSlot are by slot ----
+__global__ __launch_bounds__(kBlock) void k_diffuse_count_crest(const float4* __restrict__ pv, const float4* __restrict__ own, float dt,
+                                                                const DiffuseCoef* __restrict__ coef, const DiffuseCrestCoef* __restrict__ crestCoef,
+                                                                const uint32_t* __restrict__ state, const float4* __restrict__ nrmSlot,
+                                                                const float* __restrict__ crestSlot, uint32_t* __restrict__ cnt,
+                                                                uint32_t* __restrict__ crestPart, uint32_t idBase, uint32_t n) {
+    __shared__ uint32_t sm[4];
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t extra = 0u;
+    if (s < n) {
+        const float4 o = own[s];                                        // (cell, foam, flags, id)
+        const uint32_t idx = fbits(o.w) - idBase;
+        if (idx < n) {                                                  // (always: ids are idBase + [0, n))
+            const DiffuseCoef c = *coef;
+            const DiffuseCrestCoef cc = *crestCoef;
+            const uint32_t lo = state[DF_STEP_LO], hi = state[DF_STEP_HI];
+            const float invRho = pv[2u * s].w;
+            const uint32_t f = diffuse_children(c, dt, o.y, fbits(o.z), invRho, fbits(o.w), lo, hi);
+            uint32_t all = f;
+            if (f < c.maxPerParent && diffuse_crest_acts(lo, hi, cc.every)) {   // (a full parent has no room for a crest child: nothing is read)
+                const float4 N = nrmSlot[s], V = pv[2u * s + 1u];
+                const uint32_t born = diffuse_crest_children(c, cc, dt, fbits(o.z), invRho, N.w != 0.0f, N.w == 2.0f, N.x, N.y, N.z, crestSlot[s],
+                                                             V.x, V.y, V.z, fbits(o.w), lo, hi);
+                all = min(f + born, c.maxPerParent);
+            }
+            extra = all - f;
+            cnt[idx] = all;
+        }
+    }
+    uint32_t total;
+    (void)block_excl_scan(extra, sm, total);
+    if (threadIdx.x == 0) crestPart[blockIdx.x] = total;
+}
+
 // ---- stable compaction of the survivors: scratch -> pool ----
 __global__ __launch_bounds__(kBlock) void k_diffuse_compact(const float4* __restrict__ scratch, const uint32_t* __restrict__ flagStart,
                                                             const uint32_t* __restrict__ state, float4* __restrict__ pool, uint32_t C) {
@@ -256,6 +336,24 @@ __global__ __launch_bounds__(kBlock) void k_diffuse_tick(uint32_t* __restrict__ 
     diffuse_add64(state + DF_TOTALS + 8, tot[DF_PART_BOX]);
     diffuse_add64(state + DF_TOTALS + 10, tot[DF_PART_NONFINITE]);
     diffuse_add64(state + DF_STEP_LO, 1ull);
+}
+
+// ---- one block in front of k_diffuse_tick: the rows of crestPart[] added up, then thread 0 alone writes the crest books ----
+// shellTotal: the word behind the scan of the shell flags by slot (the number of shell members), clamped to n.
+__global__ __launch_bounds__(kBlock) void k_diffuse_crest_tick(const uint32_t* __restrict__ state, const DiffuseCrestCoef* __restrict__ crestCoef,
+                                                               const uint32_t* __restrict__ crestPart, uint32_t rows,
+                                                               const long long* __restrict__ shellTotal, uint32_t n, uint32_t* __restrict__ crest) {
+    __shared__ uint32_t sm[4];
+    uint32_t acc = 0u;
+    for (uint32_t r = threadIdx.x; r < rows; r += kBlock) acc += crestPart[r];
+    uint32_t total;
+    (void)block_excl_scan(acc, sm, total);
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    if (!diffuse_crest_acts(state[DF_STEP_LO], state[DF_STEP_HI], crestCoef->every)) return;
+    const long long t = n ? *shellTotal : 0ll;
+    diffuse_add64(crest + DFC_ACTING, 1ull);
+    diffuse_add64(crest + DFC_SPAWNED, total);
+    crest[DFC_SHELL] = t < 0ll ? 0u : (t > (long long)n ? n : (uint32_t)t);
 }
 
 }  // namespace sph

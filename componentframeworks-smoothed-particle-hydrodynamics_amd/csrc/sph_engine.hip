@@ -341,6 +341,21 @@ struct SphEngine {
     int optNbFill = 0;                   // SPH_OPT_NEIGHBORS_FILL: 0 = lane-owned stores (k_neighbors_fill), 1 = the wave-cooperative row write (same bits)
     int optDiffuseTimed = 0;             // SPH_OPT_DIFFUSE_TIMED: which launches of the substep the timing bracket covers (0 all, 1 advance, 2 the rest)
     SphDiffuseConfig dfCfg{};            // the config in force
+    // crest births of the pool (sph_diffuse_set_crest): the coefficients and the books in device memory (made by the first set, kept as
+    // long as the pool) with their pinned staging, and the scratch of the shell pass by slot, all its own (a captured graph bakes the
+    // addresses in, and the scratch of sph_shell_* may be re-made by any query): normal and member word, 0 / 1 flag, its scan with the
+    // tile scratch, the compacted shell slots, the crest per slot, the per-block rows of crest children
+    sph::DiffuseCrestCoef* d_dfCrCoef = nullptr;
+    uint32_t* d_dfCrState = nullptr;
+    StageRing<sph::DiffuseCrestCoef> dfCrStage;
+    DevBuf<float4> d_dfCrNrm;
+    DevBuf<uint32_t> d_dfCrFlag, d_dfCrTileMax, d_dfCrPart;
+    DevBuf<long long> d_dfCrOffsets;
+    DevBuf<unsigned long long> d_dfCrTileSums;
+    DevBuf<int32_t> d_dfCrSlots;
+    DevBuf<float> d_dfCrCrest;
+    bool dfCrOn = false;
+    SphDiffuseCrest dfCrCfg{};           // the crest config in force (all zero while off)
 
     // sph_scalars_* (sph_scalar.h): K channels per particle in the caller's order, their gathered copy in slot order
     // (K values + the ghost weight per slot), the coefficients as the kernels read them (device memory: a replayed graph sees a later
@@ -557,6 +572,12 @@ void diffuse_free(SphEngine* e) {
     e->d_dfCnt.release(); e->d_dfCntStart.release(); e->d_dfCntSums.release();
     e->dfC = 0;
     e->dfCfg = SphDiffuseConfig{};
+    dev_free(e->d_dfCrCoef); dev_free(e->d_dfCrState);               // (the crest term goes with the pool)
+    e->dfCrStage.destroy();
+    e->d_dfCrNrm.release(); e->d_dfCrFlag.release(); e->d_dfCrTileMax.release(); e->d_dfCrPart.release(); e->d_dfCrOffsets.release();
+    e->d_dfCrTileSums.release(); e->d_dfCrSlots.release(); e->d_dfCrCrest.release();
+    e->dfCrOn = false;
+    e->dfCrCfg = SphDiffuseCrest{};
 }
 
 void scalars_free(SphEngine* e) {
@@ -776,8 +797,65 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
 }
 
 // ---- spray, foam and bubbles (sph_diffuse.h) -----------------------------------------------------
-// One substep's work on the pool, behind build_grid of that substep: advance into the scratch pool, count the children, scan both,
-// compact the survivors back, emit the newborn behind them, tick.  Sized by C and N alone.
+// The launch arguments of the crest term's shell pass at the current params (radius <= 0: h); false: no radius of this grid.
+bool diffuse_crest_args(const SphEngine* e, float cellSize, float* radius, int* stencil) {
+    *radius = e->dfCrCfg.radius <= 0.0f ? e->params.param_h : e->dfCrCfg.radius;
+    *stencil = sph::neighbor_stencil(*radius, cellSize);
+    return *stencil != 0;
+}
+
+// The scratch of the crest term's shell pass for n slots, grown in the eager run in front of the substep's timed bracket.
+int diffuse_crest_scratch(SphEngine* e, uint32_t n) {
+    const size_t tiles = (size_t)blocks_for((size_t)n, kScanTile);
+    int rc;
+    if (e->d_dfCrOffsets.cap < (size_t)n + 1) {              // (grown last: a failed growth is tried again; never while capturing)
+        if (e->capturing) return fail(SPH_ERR_STATE, "diffuse crest scratch missing during a graph capture");
+        if ((rc = e->d_dfCrNrm.grow(e, n)) || (rc = e->d_dfCrFlag.grow(e, n)) || (rc = e->d_dfCrSlots.grow(e, n)) || (rc = e->d_dfCrCrest.grow(e, n)) ||
+            (rc = e->d_dfCrTileSums.grow(e, tiles + 2)) || (rc = e->d_dfCrTileMax.grow(e, tiles)) || (rc = e->d_dfCrPart.grow(e, (size_t)blocks_for(n))) ||
+            (rc = e->d_dfCrOffsets.grow(e, (size_t)n + 1))) return rc;
+        // (a first substep that does not act leaves the passes idle: the scan and the count must still read defined words)
+        HIP_TRY(hipMemsetAsync(e->d_dfCrNrm.p, 0, e->d_dfCrNrm.cap * sizeof(float4), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dfCrFlag.p, 0, e->d_dfCrFlag.cap * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dfCrSlots.p, 0, e->d_dfCrSlots.cap * sizeof(int32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dfCrCrest.p, 0, e->d_dfCrCrest.cap * sizeof(float), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dfCrOffsets.p, 0, e->d_dfCrOffsets.cap * sizeof(long long), e->stream));
+    }
+    return SPH_OK;
+}
+// The crest term's launches in front of the count: pass 1 by slot, the scan of the shell flags (its total stays behind the offsets),
+// the compaction of the shell slots, pass 2 over them.  All sized by n; on a substep that does not act the two passes return at once.
+// sph_shell.h and sph_diffuse.h meet here, through plain arrays.
+int diffuse_crest_shell(SphEngine* e, const SimK& k, uint32_t n) {
+    float radius = 0.0f;
+    int stencil = 0;
+    if (!diffuse_crest_args(e, k.cellSize, &radius, &stencil))
+        return fail(SPH_ERR_STATE, "diffuse crest radius %g is above three cells (%g) of this grid", (double)radius, (double)(3.0f * k.cellSize));
+    if (!n) return SPH_OK;
+    const size_t tiles = (size_t)blocks_for((size_t)n, kScanTile);
+    NbK nb;
+    nb.R2 = radius * radius; nb.s = stencil; nb.flags = e->dfCrCfg.flags; nb.idBase = e->idBase; nb.n = n;
+    ShellK sk;
+    sk.R = radius; sk.R2 = radius * radius; sk.offset = e->dfCrCfg.offset; sk.minCount = e->dfCrCfg.minCount;
+    const dim3 grid(blocks_for(n)), block(kBlock), scan((unsigned)tiles);
+    const float4* pv = (const float4*)e->d_sPV;
+    const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
+    const uint32_t* counter = (const uint32_t*)e->d_dfState + DF_STEP_LO;
+    const uint32_t* period = &e->d_dfCrCoef->every;          // (an address, not a load: device memory)
+    unsigned long long *tileSums = e->d_dfCrTileSums.p, *totals = tileSums + tiles;
+    hipLaunchKernelGGL(k_shell_slot_gather, grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const float4*)e->d_sOwn, counter, period, e->d_dfCrNrm.p,
+                       e->d_dfCrFlag.p);
+    hipLaunchKernelGGL(k_neighbors_scan_reduce, scan, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, tileSums, e->d_dfCrTileMax.p);
+    hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, tileSums, (const uint32_t*)e->d_dfCrTileMax.p, (int)tiles, totals);
+    hipLaunchKernelGGL(k_neighbors_scan_apply, scan, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, (const unsigned long long*)tileSums,
+                       (const unsigned long long*)totals, e->d_dfCrOffsets.p);
+    hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (const long long*)e->d_dfCrOffsets.p, (size_t)n, e->d_dfCrSlots.p);
+    hipLaunchKernelGGL(k_shell_slot_crest, grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const float4*)e->d_dfCrNrm.p, (const int32_t*)e->d_dfCrSlots.p,
+                       (const long long*)e->d_dfCrOffsets.p + n, counter, period, e->d_dfCrCrest.p);
+    return SPH_OK;
+}
+
+// One substep's work on the pool, behind build_grid of that substep: advance into the scratch pool, count the children (with the crest
+// term on: behind its shell pass), scan both, compact the survivors back, emit the newborn behind them, tick.  Sized by C and N alone.
 int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
     const uint32_t C = e->dfC;
     int rc;
@@ -787,6 +865,8 @@ int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
             (rc = e->d_dfCntStart.grow(e, (size_t)n + 1))) return rc;
         HIP_TRY(hipMemsetAsync(e->d_dfCnt.p, 0, e->d_dfCnt.cap * sizeof(uint32_t), e->stream));     // (k_scan_apply leaves it zero again)
     }
+    const bool crest = e->dfCrOn;
+    if (crest && (rc = diffuse_crest_scratch(e, n))) return rc;
     // one bracket per substep: around everything, or (SPH_OPT_DIFFUSE_TIMED, measurements) around the advance or around the rest
     std::unique_ptr<Timed> t;
     if (e->optDiffuseTimed != 2) t.reset(new Timed(e, SPH_K_OTHER));
@@ -795,7 +875,12 @@ int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
                        (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const float4*)e->d_dfPool, e->d_dfScratch, e->d_dfFlag, e->d_dfPart, C);
     if (e->optDiffuseTimed == 1) t.reset();
     if (e->optDiffuseTimed == 2) t.reset(new Timed(e, SPH_K_OTHER));
-    if (n)
+    if (crest && (rc = diffuse_crest_shell(e, k, n))) return rc;
+    if (n && crest)
+        hipLaunchKernelGGL(k_diffuse_count_crest, dim3(nb), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn, dt,
+                           (const DiffuseCoef*)e->d_dfCoef, (const DiffuseCrestCoef*)e->d_dfCrCoef, (const uint32_t*)e->d_dfState,
+                           (const float4*)e->d_dfCrNrm.p, (const float*)e->d_dfCrCrest.p, e->d_dfCnt.p, e->d_dfCrPart.p, e->idBase, n);
+    else if (n)
         hipLaunchKernelGGL(k_diffuse_count, dim3(nb), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn, dt,
                            (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, e->d_dfCnt.p, e->idBase, n);
     launch_cell_scan(e, e->d_dfFlag, e->d_dfFlagSums, e->d_dfFlagStart, (int)C, C);
@@ -807,6 +892,9 @@ int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
         hipLaunchKernelGGL(k_diffuse_emit, dim3(nb), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
                            (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const uint32_t*)e->d_dfCntStart.p,
                            (const uint32_t*)e->d_dfFlagStart, e->d_dfPool, e->idBase, n, C);
+    if (crest)                                                          // (in front of the tick: it reads the counter the tick advances)
+        hipLaunchKernelGGL(k_diffuse_crest_tick, dim3(1), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_dfState, (const DiffuseCrestCoef*)e->d_dfCrCoef,
+                           (const uint32_t*)e->d_dfCrPart.p, (uint32_t)(n ? nb : 0), (const long long*)e->d_dfCrOffsets.p + n, n, e->d_dfCrState);
     hipLaunchKernelGGL(k_diffuse_tick, dim3(1), dim3(kBlock), 0, e->stream, e->d_dfState, (const uint32_t*)e->d_dfPart, (uint32_t)cb,
                        (const uint32_t*)e->d_dfFlagStart, (const uint32_t*)e->d_dfCntStart.p, n, C);
     t.reset();
@@ -1061,6 +1149,12 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     if ((rc = ensure_grid_buffers(e))) return rc;                           // :440-447
     SimK k;
     make_simk(e->params, e->grid, dt, k);
+    if (e->dfC && e->dfCrOn) {                                              // (refused before anything is launched)
+        float radius = 0.0f;
+        int stencil = 0;
+        if (!diffuse_crest_args(e, k.cellSize, &radius, &stencil))
+            return fail(SPH_ERR_STATE, "diffuse crest radius %g is above three cells (%g) of this grid", (double)radius, (double)(3.0f * k.cellSize));
+    }
     if (e->slab) {
         if (e->z1 > e->grid.dims[2] || e->z0 < 0) return fail(SPH_ERR_STATE, "slab [%d,%d) outside the %d-layer grid", e->z0, e->z1, e->grid.dims[2]);
         k.gz = e->z1 - e->z0 + 2; k.numCells = k.gx * k.gy * k.gz; k.zoff = e->z0 - 1;
@@ -1538,6 +1632,15 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     const int anyDyn = e->dynCount > 0 ? 1 : 0;
     add(&dy, sizeof(dy));
     add(&anyDyn, sizeof(anyDyn));
+    // crest births of the pool, only while the term is on (off: the material of before): every buffer its launches get and the shell pass's
+    // launch arguments (radius, hence the stencil, offset, minCount, flags); rate, windows, align and every are read from memory
+    if (e->dfC && e->dfCrOn) {
+        const void* cr[10] = {e->d_dfCrCoef, e->d_dfCrState, e->d_dfCrNrm.p, e->d_dfCrFlag.p, e->d_dfCrTileMax.p, e->d_dfCrPart.p, e->d_dfCrOffsets.p,
+                              e->d_dfCrTileSums.p, e->d_dfCrSlots.p, e->d_dfCrCrest.p};
+        add(cr, sizeof(cr));
+        add(&e->dfCrCfg.radius, sizeof(float));                       // (with the params above it fixes the radius in force and the stencil)
+        add(&e->dfCrCfg.offset, sizeof(float)); add(&e->dfCrCfg.minCount, sizeof(uint32_t)); add(&e->dfCrCfg.flags, sizeof(int32_t));
+    }
     return m;
 }
 static uint64_t graph_hash(const std::vector<unsigned char>& m) {
@@ -4563,11 +4666,105 @@ int sph_diffuse_seed(SphEngine* e, const SphDiffuse* records, size_t m) {
     HIP_TRY(hipMemcpy(e->d_dfState, w, sizeof(w), hipMemcpyHostToDevice));
     return SPH_OK;
 }
-int sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
-                          const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals) {
+// ---- crest births of the pool ----
+static_assert(sizeof(SphDiffuseCrest) == 48 && sizeof(SphDiffuseCrestInfo) == 32 && sizeof(sph::DiffuseCrestCoef) == 32, "SphDiffuseCrest is 48 bytes, SphDiffuseCrestInfo 32");
+static bool crest_window(float lo, float hi) { return std::isfinite(lo) && std::isfinite(hi) && lo < hi; }
+// The crest config as an argument (h and cellSize: of the params the shell pass would run with).
+static int diffuse_check_crest(const SphDiffuseCrest& c, float h, float cellSize) {
+    if (!diffuse_nonneg(c.rate)) return fail(SPH_ERR_ARG, "diffuse crest rate must be finite and >= 0");
+    const SphShellConfig sc{c.radius, c.offset, c.minCount, c.flags};
+    float radius = 0.0f;
+    int stencil = 0, rc;
+    if (!std::isfinite(c.radius)) return fail(SPH_ERR_ARG, "diffuse crest radius %g is not finite", (double)c.radius);
+    if ((rc = shell_check(sc, h, cellSize, &radius, &stencil))) return rc;
+    if (!crest_window(c.crestMin, c.crestMax)) return fail(SPH_ERR_ARG, "diffuse crest window [%g, %g] is empty or not finite", (double)c.crestMin, (double)c.crestMax);
+    if (!crest_window(c.speedMin, c.speedMax)) return fail(SPH_ERR_ARG, "diffuse crest speed window [%g, %g] is empty or not finite", (double)c.speedMin, (double)c.speedMax);
+    if (!(c.align >= 0.0f && c.align <= 1.0f)) return fail(SPH_ERR_ARG, "diffuse crest align %g outside [0, 1]", (double)c.align);
+    if (c.every == 0u) return fail(SPH_ERR_ARG, "diffuse crest every must be >= 1");
+    return SPH_OK;
+}
+static sph::DiffuseCrestCoef diffuse_crest_coef_of(const SphDiffuseCrest& c) {
+    return sph::DiffuseCrestCoef{c.rate, c.crestMin, c.crestMax, c.speedMin, c.speedMax, c.align, c.every, 0u};
+}
+void sph_diffuse_crest_default(SphDiffuseCrest* out) {
+    if (!out) return;
+    SphDiffuseCrest c{};
+    c.rate = 300.0f; c.radius = 0.0f; c.offset = 0.10f; c.minCount = 0u; c.flags = 0;
+    c.crestMin = 0.5f; c.crestMax = 2.0f;
+    c.speedMin = 20.0f; c.speedMax = 60.0f;
+    c.align = 0.6f; c.every = 1u;
+    *out = c;
+}
+int sph_diffuse_set_crest(SphEngine* e, const SphDiffuseCrest* crest) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->dfC) return fail(SPH_ERR_STATE, "no diffuse pool: call sph_diffuse_set first");
+    if (!crest || crest->rate == 0.0f) {                                // off: the launches of before; the books stay
+        e->dfCrOn = false;
+        e->dfCrCfg = SphDiffuseCrest{};
+        return SPH_OK;
+    }
+    int rc;
+    if ((rc = validate_params(e->params))) return rc;
+    SphGridInfo g;
+    sph::compute_grid_extents(e->params, g);
+    if ((rc = diffuse_check_crest(*crest, e->params.param_h, g.cellSize))) return rc;
+    if (!e->d_dfCrCoef) {
+        hipError_t er = hipSuccess;
+        if ((rc = dev_alloc(&e->d_dfCrCoef, 1)) || (rc = dev_alloc(&e->d_dfCrState, (size_t)DFC_WORDS)) ||
+            (er = e->dfCrStage.create(e->stream, 1)) != hipSuccess ||
+            (er = hipMemsetAsync(e->d_dfCrState, 0, DFC_WORDS * sizeof(uint32_t), e->stream)) != hipSuccess) {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            dev_free(e->d_dfCrCoef); dev_free(e->d_dfCrState);
+            e->dfCrStage.destroy();
+            return rc ? rc : fail(SPH_ERR_HIP, "staging of the diffuse crest coefficients: %s", hipGetErrorString(er));
+        }
+    }
+    sph::DiffuseCrestCoef* slot = nullptr;
+    if ((rc = e->dfCrStage.next(&slot))) return rc;
+    *slot = diffuse_crest_coef_of(*crest);
+    HIP_TRY(hipMemcpyAsync(e->d_dfCrCoef, slot, sizeof(sph::DiffuseCrestCoef), hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->dfCrStage.commit(e->stream))) return rc;
+    e->dfCrCfg = *crest;
+    e->dfCrCfg.pad = 0u;
+    e->dfCrOn = true;
+    return SPH_OK;
+}
+int sph_diffuse_get_crest(SphEngine* e, SphDiffuseCrest* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    *out = e->dfCrCfg;
+    return SPH_OK;
+}
+int sph_diffuse_crest_info(SphEngine* e, SphDiffuseCrestInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    *out = SphDiffuseCrestInfo{};
+    if (!e->dfC || !e->d_dfCrState) return SPH_OK;
+    uint32_t w[DFC_WORDS];
+    HIP_TRY(hipMemcpyAsync(w, e->d_dfCrState, sizeof(w), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    out->acting = ((uint64_t)w[DFC_ACTING + 1] << 32) | w[DFC_ACTING];
+    out->crestSpawned = ((uint64_t)w[DFC_SPAWNED + 1] << 32) | w[DFC_SPAWNED];
+    out->shellSize = w[DFC_SHELL];
+    out->on = e->dfCrOn ? 1 : 0;
+    if (e->dfCrOn && validate_params(e->params) == SPH_OK) {
+        SphGridInfo g;
+        sph::compute_grid_extents(e->params, g);
+        (void)diffuse_crest_args(e, g.cellSize, &out->radius, &out->stencil);
+    }
+    return SPH_OK;
+}
+
+static int diffuse_step_host_run(const SphDiffuseConfig* cfg, const SphDiffuseCrest* crest, const SphParams* params, float dt, uint64_t substep,
+                                 const SphDiffuse* pool, size_t m, const SphSample* samples, const SphParticle* particles, size_t n,
+                                 const SphShell* shellRows, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals, SphDiffuseCrestInfo* crestTotals) {
     if (!cfg || !params || !countOut || (m && (!pool || !samples)) || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
     int rc;
     if ((rc = diffuse_check_config(*cfg)) || (rc = validate_params(*params))) return rc;
+    if (crest) {
+        SphGridInfo cg;
+        sph::compute_grid_extents(*params, cg);
+        if ((rc = diffuse_check_crest(*crest, params->param_h, cg.cellSize))) return rc;
+        if (n && !shellRows) return fail(SPH_ERR_ARG, "null argument");
+    }
     const size_t C = cfg->capacity;
     if (m > C) return fail(SPH_ERR_CAPACITY, "%zu diffuse records exceed the capacity of %zu", m, C);
     if (C && !out) return fail(SPH_ERR_ARG, "null argument");
@@ -4604,12 +4801,25 @@ int sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, 
         kinds[r.kind] += 1u;
     }
     const size_t survivors = next.size();
-    uint64_t spawned = 0;
+    uint64_t spawned = 0, crestSpawned = 0;
+    uint32_t shellSize = 0;
+    const sph::DiffuseCrestCoef cc = crest ? diffuse_crest_coef_of(*crest) : sph::DiffuseCrestCoef{};
+    const bool acts = crest && sph::diffuse_crest_acts(lo, hi, cc.every);
     for (size_t i = 0; i < n; ++i) {                                   // 2. spawn, in id order
         const SphParticle& p = particles[i];
         const uint32_t flags = (p.isGhost == 1 ? F_GHOST1 : 0u) | (p.isGhost != 0 ? F_GHOSTNZ : 0u) | (p.isActive == 0 ? F_INACTIVE : 0u);
         const float invRho = p.density > 0.0f ? 1.0f / p.density : 0.0f;
-        const uint32_t children = sph::diffuse_children(co, step, p.padA, flags, invRho, (uint32_t)i, lo, hi);
+        uint32_t children = sph::diffuse_children(co, step, p.padA, flags, invRho, (uint32_t)i, lo, hi);
+        if (acts) {                                                    // the crest term's children behind the foam term's
+            const SphShell& s = shellRows[i];
+            const bool member = (s.flags & SPH_SHELL_MEMBER) != 0;
+            if (member) shellSize += 1u;
+            const uint32_t born = sph::diffuse_crest_children(co, cc, step, flags, invRho, member, (s.flags & SPH_SHELL_ISOLATED) != 0, s.normal[0],
+                                                              s.normal[1], s.normal[2], s.crest, p.vel[0], p.vel[1], p.vel[2], (uint32_t)i, lo, hi);
+            const uint32_t all = std::min(children + born, co.maxPerParent);
+            crestSpawned += all - children;
+            children = all;
+        }
         for (uint32_t q = 0; q < children; ++q) {
             if (next.size() < C) {
                 const sph::DiffuseRec r = sph::diffuse_child(co, k.h, p.pos[0], p.pos[1], p.pos[2], p.vel[0], p.vel[1], p.vel[2], (uint32_t)i, lo, hi, q);
@@ -4631,7 +4841,23 @@ int sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, 
         totals->alive = (uint32_t)next.size(); totals->capacity = (uint32_t)C;
         totals->aliveByKind[0] = kinds[0]; totals->aliveByKind[1] = kinds[1] + (uint32_t)born; totals->aliveByKind[2] = kinds[2];
     }
+    if (crestTotals && acts) {
+        crestTotals->acting += 1;
+        crestTotals->crestSpawned += crestSpawned;
+        crestTotals->shellSize = shellSize;
+    }
     return SPH_OK;
+}
+int sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
+                          const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals) {
+    return diffuse_step_host_run(cfg, nullptr, params, dt, substep, pool, m, samples, particles, n, nullptr, out, countOut, totals, nullptr);
+}
+int sph_diffuse_step_host_crest(const SphDiffuseConfig* cfg, const SphDiffuseCrest* crest, const SphParams* params, float dt, uint64_t substep,
+                                const SphDiffuse* pool, size_t m, const SphSample* samples, const SphParticle* particles, size_t n,
+                                const SphShell* shellRows, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals, SphDiffuseCrestInfo* crestTotals) {
+    const bool on = crest && crest->rate != 0.0f;                      // (NULL or rate == 0: sph_diffuse_step_host)
+    return diffuse_step_host_run(cfg, on ? crest : nullptr, params, dt, substep, pool, m, samples, particles, n, shellRows, out, countOut, totals,
+                                 on ? crestTotals : nullptr);
 }
 
 // ---- diffusing scalars (sph_scalar.h) -------------------------------------------------------------

@@ -22,6 +22,9 @@
 //                             slots by slot).
 //   k_shell_crest             pass 2 over the compacted shell slots in ascending slot order (full waves whose lanes still share rows): a
 //                             candidate that is not in the shell costs the one 16-byte load of its by-slot float4.
+//   k_shell_slot_gather /     the same two passes by slot for a substep that reads them itself (the diffuse pool's crest births): 20 bytes
+//   k_shell_slot_crest        per target instead of 56, one float per slot, no rows by id, no atomics, both sized by n and gated by a
+//                             counter in device memory (shell_gate)
 // ids[] is k_neighbors_ids' (a permutation of [0, n)); the range guards (row < rows, j < end <= n, offsets < rows) stay so that no load
 // or store can leave its array.
 #pragma once
@@ -185,6 +188,81 @@ __global__ __launch_bounds__(kBlock) void k_shell_crest(SimK k, NbK nb, ShellK s
         }
     });
     out[row].crest = shell_crest_value(crest);
+}
+
+// ---- the two passes by slot, for a substep that reads normals and crests itself (the crest births of the diffuse pool) ----
+// Nothing by id, no reduction, no host-side count: both launches are sized by n.  A launch is gated by a 64-bit counter (two words) and a
+// period, both in device memory: it works when the counter is a multiple of the period and returns at once otherwise, since a captured
+// graph has a fixed launch list.
+__device__ __forceinline__ bool shell_gate(const uint32_t* __restrict__ counter, const uint32_t* __restrict__ period) {
+    const uint32_t p = *period;
+    return p != 0u && (((unsigned long long)counter[1] << 32) | counter[0]) % p == 0ull;
+}
+
+// Pass 1 by slot: k_shell_gather<true>'s walk; writes only the by-slot float4 (normal, 0 outside the shell | 1 member | 2 isolated
+// member) and the by-slot 0 / 1 flag word for the scan.
+__global__ __launch_bounds__(kBlock) void k_shell_slot_gather(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                              const float4* __restrict__ own, const uint32_t* __restrict__ counter,
+                                                              const uint32_t* __restrict__ period, float4* __restrict__ nrmSlot,
+                                                              uint32_t* __restrict__ flagSlot) {
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nb.n || !shell_gate(counter, period)) return;
+    const bool fluidOnly = (nb.flags & kShellFluidOnly) != 0;
+    const float4 P = pv[2u * q];
+    bool walk = sample_finite(P.x, P.y, P.z);                                 // (a non-finite particle has an all-zero row)
+    if (walk && fluidOnly) walk = !slot_ghost(own, q);
+    ShellRow r;
+    shell_zero(r);
+    if (walk) {
+        ShellAcc a;
+        shell_reset(a);
+        const int3 cell = cell_of(k, P.x, P.y, P.z);
+        neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                if (j == q) continue;
+                const float4 J = pv[2u * j];
+                float dx, dy, dz, r2;
+                if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
+                if (fluidOnly && slot_ghost(own, j)) continue;
+                shell_add(a, dx, dy, dz, r2, nb.R2);
+            }
+        });
+        shell_finish(a, sk, r);
+    }
+    const uint32_t in = r.flags & kShellMember;
+    nrmSlot[q] = make_float4(r.normal[0], r.normal[1], r.normal[2], in ? ((r.flags & kShellIsolated) ? 2.0f : 1.0f) : 0.0f);
+    flagSlot[q] = in;
+}
+
+// Pass 2 by slot: k_shell_crest's walk over the compacted shell slots.  The launch is sized by n; the number of targets is the word behind
+// the scan (numShell, device memory), clamped to n.  One float per slot: lane t clears the slot t where it is no shell member, and writes
+// the crest of the t-th shell slot where there is one -- the two sets of slots are disjoint.
+__global__ __launch_bounds__(kBlock) void k_shell_slot_crest(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                             const float4* __restrict__ nrmSlot, const int32_t* __restrict__ shellSlots,
+                                                             const long long* __restrict__ numShell, const uint32_t* __restrict__ counter,
+                                                             const uint32_t* __restrict__ period, float* __restrict__ crestSlot) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= nb.n || !shell_gate(counter, period)) return;
+    if (nrmSlot[t].w == 0.0f) crestSlot[t] = 0.0f;
+    const long long total = *numShell;
+    if (total <= 0ll || (long long)t >= total) return;                        // (t < nb.n already: the count is clamped to n)
+    const uint32_t q = (uint32_t)shellSlots[t];
+    if (q >= nb.n) return;
+    const float4 P = pv[2u * q];
+    const float4 N = nrmSlot[q];
+    long long crest = 0ll;
+    const int3 cell = cell_of(k, P.x, P.y, P.z);
+    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
+        for (uint32_t j = qs; j < qe; ++j) {
+            const float4 M = nrmSlot[j];
+            if (M.w == 0.0f || j == q) continue;                              // not in the shell: nothing else is read
+            const float4 J = pv[2u * j];
+            float dx, dy, dz, r2;
+            if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
+            crest += shell_crest_term(N.x, N.y, N.z, M.x, M.y, M.z, dx, dy, dz, r2, sk.R);
+        }
+    });
+    crestSlot[q] = shell_crest_value(crest);
 }
 
 }  // namespace sph

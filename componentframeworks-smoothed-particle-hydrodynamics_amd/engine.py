@@ -180,7 +180,22 @@ class SphDiffuseInfo(C.Structure):
                 ("aliveByKind", C.c_uint32 * 3), ("pad", C.c_uint32)]
 
 
+class SphDiffuseCrest(C.Structure):
+    """struct SphDiffuseCrest of include/sph_abi.h: the pool's second birth term, at wave crests (DESIGN.md section 3j);
+    diffuse_crest_config() fills one."""
+    _fields_ = [("rate", C.c_float), ("radius", C.c_float), ("offset", C.c_float), ("minCount", C.c_uint32), ("flags", C.c_int32),
+                ("crestMin", C.c_float), ("crestMax", C.c_float), ("speedMin", C.c_float), ("speedMax", C.c_float), ("align", C.c_float),
+                ("every", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SphDiffuseCrestInfo(C.Structure):
+    """struct SphDiffuseCrestInfo of include/sph_abi.h: the books of the crest term."""
+    _fields_ = [("acting", C.c_uint64), ("crestSpawned", C.c_uint64), ("shellSize", C.c_uint32), ("on", C.c_int32), ("radius", C.c_float),
+                ("stencil", C.c_int32)]
+
+
 assert C.sizeof(SphDiffuse) == 48 and C.sizeof(SphDiffuseConfig) == 64 and C.sizeof(SphDiffuseInfo) == 88
+assert C.sizeof(SphDiffuseCrest) == 48 and C.sizeof(SphDiffuseCrestInfo) == 32
 DIFFUSE_DTYPE = np.dtype(SphDiffuse)
 assert DIFFUSE_DTYPE.itemsize == 48
 SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE = 0, 1, 2
@@ -495,6 +510,12 @@ _ABI = {
     "sph_diffuse_device": (_int, [_vp, _P(_vp), _P(_vp)]),
     "sph_diffuse_seed": (_int, [_vp, _vp, _sz]),
     "sph_diffuse_step_host": (_int, [_P(SphDiffuseConfig), _pp, _f, _u64, _vp, _sz, _vp, _vp, _sz, _vp, _P(_sz), _P(SphDiffuseInfo)]),
+    "sph_diffuse_crest_default": (None, [_P(SphDiffuseCrest)]),
+    "sph_diffuse_set_crest": (_int, [_vp, _P(SphDiffuseCrest)]),
+    "sph_diffuse_get_crest": (_int, [_vp, _P(SphDiffuseCrest)]),
+    "sph_diffuse_crest_info": (_int, [_vp, _P(SphDiffuseCrestInfo)]),
+    "sph_diffuse_step_host_crest": (_int, [_P(SphDiffuseConfig), _P(SphDiffuseCrest), _pp, _f, _u64, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _P(_sz),
+                                           _P(SphDiffuseInfo), _P(SphDiffuseCrestInfo)]),
     # neighbour lists
     "sph_neighbors_build": (_int, [_vp, _f, _int, _u64, _P(SphNeighborInfo)]),
     "sph_neighbors_query": (_int, [_vp, _vp, _sz, _f, _int, _u64, _P(SphNeighborInfo)]),
@@ -1676,6 +1697,29 @@ class SPHFluidGPU:
         rec = np.ascontiguousarray(records, DIFFUSE_DTYPE)
         _check(self._L.sph_diffuse_seed(self._h, _ptr_or_none(rec), len(rec)))
 
+    def set_diffuse_crest(self, config=None, **overrides):
+        """Switch the pool's crest births on: config is a SphDiffuseCrest (diffuse_crest_config()) or None for
+        the defaults, overrides name its fields.  rate 0 switches the term off.  Needs a pool (set_diffuse)."""
+        cfg = diffuse_crest_config(**overrides) if config is None else _copy_config(config, overrides)
+        self._push_params()                                                             # (the radius is checked against their grid)
+        _check(self._L.sph_diffuse_set_crest(self._h, C.byref(cfg)))
+
+    def clear_diffuse_crest(self):
+        _check(self._L.sph_diffuse_set_crest(self._h, None))
+
+    def diffuse_crest(self) -> "SphDiffuseCrest":
+        """The crest config in force (all zero while the term is off)."""
+        cfg = SphDiffuseCrest()
+        _check(self._L.sph_diffuse_get_crest(self._h, C.byref(cfg)))
+        return cfg
+
+    def diffuse_crest_info(self) -> dict:
+        """The books of the crest term: acting substeps, crest children, the shell size of the last acting substep, whether the term
+        is on, the radius and stencil in force.  Synchronises."""
+        info = SphDiffuseCrestInfo()
+        _check(self._L.sph_diffuse_crest_info(self._h, C.byref(info)))
+        return _crest_info_dict(info)
+
     def tracer_history(self):
         """(first, array (count, M, 4)): the stored snapshots (x, y, z, age), oldest first, and the number of the first one.  Synchronises."""
         _, n, _ = self.tracer_info()
@@ -2091,26 +2135,55 @@ def _info_dict(info) -> dict:
     return out
 
 
-def diffuse_step_host(config, params, pool, samples, particles, substep: int, dt: float = -1.0, totals=None):
+def diffuse_crest_config(**overrides) -> SphDiffuseCrest:
+    """sph_diffuse_crest_default with the named fields replaced.  No device is needed."""
+    cfg = SphDiffuseCrest()
+    load_library().sph_diffuse_crest_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+_CREST_BOOKS = ("acting", "crestSpawned", "shellSize")
+
+
+def _crest_info_dict(info) -> dict:
+    out = {name: int(getattr(info, name)) for name in _CREST_BOOKS + ("on", "stencil")}
+    out["radius"] = float(info.radius)
+    return out
+
+
+def diffuse_step_host(config, params, pool, samples, particles, substep: int, dt: float = -1.0, totals=None, crest=None, shell_rows=None):
     """sph_diffuse_step_host: (pool one substep later, totals dict).  pool: DIFFUSE_DTYPE records, samples: the SAMPLE_DTYPE records at
     their positions, particles: the state the substep starts from, substep: the counter before the step, totals: the dict a previous
-    call returned (or None for zeros).  No device is needed."""
+    call returned (or None for zeros).  crest: a SphDiffuseCrest -- then sph_diffuse_step_host_crest with shell_rows, the SHELL_DTYPE
+    rows by id of `particles` (shell_host with the crest config's radius, offset, minCount and flags); the totals dict then carries the
+    crest books (acting, crestSpawned, shellSize) too.  No device is needed."""
     src = np.ascontiguousarray(pool, DIFFUSE_DTYPE)
     smp = np.ascontiguousarray(samples, SAMPLE_DTYPE)
     if len(smp) != len(src):
         raise SphError(f"{len(smp)} samples for {len(src)} diffuse records")
     rec = np.ascontiguousarray(particles, PARTICLE_DTYPE)
     out = np.zeros(max(min(int(config.capacity), len(src) + 8 * len(rec)), 1), DIFFUSE_DTYPE)
-    info = SphDiffuseInfo()
+    info, books = SphDiffuseInfo(), SphDiffuseCrestInfo()
     for name, value in (totals or {}).items():
         if name == "aliveByKind":
             info.aliveByKind[:] = list(value)
+        elif name in _CREST_BOOKS:
+            setattr(books, name, value)
         else:
             setattr(info, name, value)
     n = C.c_size_t()
-    _check(load_library().sph_diffuse_step_host(C.byref(config), C.byref(params), float(dt), int(substep), _ptr_or_none(src), len(src),
-                                                _ptr_or_none(smp), _ptr_or_none(rec), len(rec), _ptr(out), C.byref(n), C.byref(info)))
-    return out[:n.value].copy(), _info_dict(info)
+    if crest is None:
+        _check(load_library().sph_diffuse_step_host(C.byref(config), C.byref(params), float(dt), int(substep), _ptr_or_none(src), len(src),
+                                                    _ptr_or_none(smp), _ptr_or_none(rec), len(rec), _ptr(out), C.byref(n), C.byref(info)))
+        return out[:n.value].copy(), dict(_info_dict(info), **{k: v for k, v in (totals or {}).items() if k in _CREST_BOOKS})
+    rows = None if shell_rows is None else np.ascontiguousarray(shell_rows, SHELL_DTYPE)
+    if rows is not None and len(rows) != len(rec):
+        raise SphError(f"{len(rows)} shell rows for {len(rec)} particles")
+    _check(load_library().sph_diffuse_step_host_crest(C.byref(config), C.byref(crest), C.byref(params), float(dt), int(substep), _ptr_or_none(src),
+                                                      len(src), _ptr_or_none(smp), _ptr_or_none(rec), len(rec),
+                                                      None if rows is None else _ptr_or_none(rows), _ptr(out), C.byref(n), C.byref(info),
+                                                      C.byref(books)))
+    return out[:n.value].copy(), dict(_info_dict(info), **{k: int(getattr(books, k)) for k in _CREST_BOOKS})
 
 
 _NO_POINT = np.zeros((1, 4), np.float32)                                            # somewhere for the pointer of an empty query to point

@@ -440,6 +440,17 @@ public:
         return true;
     }
     bool DiffuseInfo(SphDiffuseInfo& out) { return !Check(sph_diffuse_info(engine, &out), "sph_diffuse_info"); }
+    // Births at wave crests (sph_abi.h "births at wave crests"): the pool's optional second birth term, from a free-surface pass inside
+    // the substep.  Needs a pool; a config with rate 0 switches the term off; DiffuseCrest() returns the defaults to edit.  The members
+    // are pushed first (the radius is checked against their grid).
+    static SphDiffuseCrest DiffuseCrest() { SphDiffuseCrest c; sph_diffuse_crest_default(&c); return c; }
+    bool SetDiffuseCrest(const SphDiffuseCrest& crest) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_diffuse_set_crest(engine, &crest), "sph_diffuse_set_crest");
+    }
+    bool GetDiffuseCrest(SphDiffuseCrest& out) { return !Check(sph_diffuse_get_crest(engine, &out), "sph_diffuse_get_crest"); }
+    bool DiffuseCrestInfo(SphDiffuseCrestInfo& out) { return !Check(sph_diffuse_crest_info(engine, &out), "sph_diffuse_crest_info"); }
     // Diffusing scalar channels (engine extension, sph_abi.h "diffusing scalar fields"): K <= SPH_MAX_SCALAR_CHANNELS
     // floats per particle, particle-major in the caller's order, that move with their particles and diffuse between neighbours inside
     // every substep from now on.  values empty: channel 0 is seeded from padB (the dye), the others with 0; channels == 0 drops the set.

@@ -47,6 +47,8 @@ extern "C" {
     _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
 /* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
+/* (still 4, additions only: SphDiffuseCrest, SphDiffuseCrestInfo, sph_diffuse_crest_default / _crest_info, sph_diffuse_set_crest / _get_crest,
+ * sph_diffuse_step_host_crest -- spray and foam born at wave crests) */
 /* (still 4, additions only: SphNeighborInfo, SPH_NEIGHBORS_*, sph_neighbors_build / _query / _info / _device / _export / _download / _host, SPH_OPT_NEIGHBORS_FILL -- neighbour lists) */
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
@@ -816,6 +818,74 @@ int  sph_diffuse_seed(SphEngine* e, const SphDiffuse* records, size_t m);
  * param_pause: out = pool. */
 int  sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params, float dt, uint64_t substep, const SphDiffuse* pool, size_t m,
                            const SphSample* samples, const SphParticle* particles, size_t n, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals);
+
+/* ---- births at wave crests: a second, optional birth term of the pool ("crest births") ---------------------
+ * Ihmsen et al.'s wave-crest potential, from the free-surface rows of section 3o: a fluid particle of the shell whose surface is sharply
+ * convex (crest) and which moves along its own outward normal bears children, wherever padA stands.  Off by default; with the term off a
+ * substep launches what it launched before and the pool, the records and the graph keys are the same bytes.  The config belongs to the
+ * pool.  Everything is fp32, every operation rounded on its own (no fma but those of shell_add), dot3 as elsewhere, sqrtf and / correctly
+ * rounded, in the order written:
+ *   acting   a substep ACTS when the pool's 64-bit substep counter before the step is a multiple of `every`; on other substeps the term
+ *            bears nobody (its kernels are launched and return at once: a captured graph has a fixed launch list).
+ *   shell    on an acting substep the SphShell rows (normal, crest, flags) of sph_shell_build with (radius, offset, minCount, flags) on the
+ *            substep's ENTRY state: the same shell_accept / shell_add / shell_finish / shell_crest_term / shell_crest_value over the sorted
+ *            copy the substep has just built, whose slot order is HostGrid's (cell, id) order; hence the bytes of sph_shell_host.
+ *   who      a particle QUALIFIES when isGhost == 0, the sorted copy's 1/rho > 0, its row has SPH_SHELL_MEMBER and not
+ *            SPH_SHELL_ISOLATED, sp2 = dot3(v, v) is finite, sp = sqrtf(sp2) > 0 and dot3(v, normal) >= align * sp.
+ *   how many pc = fminf(fmaxf((crest - crestMin) / (crestMax - crestMin), 0), 1); pk = fminf(fmaxf((sp - speedMin) / (speedMax - speedMin), 0), 1);
+ *            p = pc * pk; nobody where not p > 0; lam = ((rate * dt) * (float)every) * p; c = floorf(lam + U_33), taken as maxPerParent
+ *            where not c < (float)maxPerParent (U_33: draw 33 of the hash above, the first draw the eight children of a parent do not use).
+ *            With f the children of the foam term (step 2 above, exactly as it is, draw 0 included) the parent has min(f + c, maxPerParent)
+ *            children: k = 0 .. f - 1 are the foam term's, the crest term's follow them.  Placement, life, order, dropping from the end
+ *            and the books' identity are those of steps 2 to 4; crest children are counted in `spawned` too.
+ *   books    SphDiffuseCrestInfo: acting substeps, crest children before dropping, the number of shell members of the last acting substep
+ *            (device memory, no atomics: per-block rows added up behind the count).  They live as long as the pool.
+ * Hence the pool and the books equal, bit for bit and order included, the host loop of the block above with
+ *   rows = sph_shell_host(P, (radius, offset, minCount, flags)) (or sph_shell_build + download, the same bytes) in front of the dispatch
+ * and sph_diffuse_step_host_crest in place of sph_diffuse_step_host, also through sph_dispatch_n and captured graphs.  rate, the two
+ * windows, align and every are read from device memory: a replayed graph sees a change without a new capture; radius, offset, minCount
+ * and flags are launch arguments (a change captures anew).
+ * sph_diffuse_set with the capacity in place keeps the crest config; another capacity, NULL, sph_reset and sph_destroy drop it.
+ * SPH_ERR_STATE from sph_diffuse_set_crest without a pool (and the pool's own refusals hold); SPH_ERR_STATE from a dispatch whose grid
+ * makes the radius exceed three cells.  SPH_ERR_ARG (the previous state stays in force): a rate that is not finite or negative, a radius
+ * that is not finite or above three cells of the current params' grid, an offset that is not finite or negative, a window that is empty
+ * (min >= max) or not finite, align outside [0, 1], every == 0, unknown flag bits. */
+typedef struct SphDiffuseCrest {
+    float    rate;           /* children per second at full potential (pc = pk = 1); 0: the term is off */
+    float    radius;         /* of the shell pass; <= 0: param_h; at most three cells (SphShellConfig's rule) */
+    float    offset;         /* SphShellConfig.offset */
+    uint32_t minCount;       /* SphShellConfig.minCount */
+    int32_t  flags;          /* SphShellConfig.flags (SPH_SHELL_FLUID_ONLY) */
+    float    crestMin, crestMax;   /* the clamp window of the crest sum, crestMin < crestMax */
+    float    speedMin, speedMax;   /* the clamp window of the speed, speedMin < speedMax */
+    float    align;          /* 0 .. 1: the cosine between velocity and normal a parent needs at least (the paper's 0.6) */
+    uint32_t every;          /* >= 1: the term acts on substeps whose counter is a multiple of it */
+    uint32_t pad;
+} SphDiffuseCrest;           /* 48 bytes */
+typedef struct SphDiffuseCrestInfo {
+    uint64_t acting;         /* substeps on which the term acted */
+    uint64_t crestSpawned;   /* children of the crest term before dropping (part of SphDiffuseInfo.spawned) */
+    uint32_t shellSize;      /* shell members of the last acting substep */
+    int32_t  on;             /* 1 while the term is switched on */
+    float    radius;         /* the radius in force at the current params (0 while off) */
+    int32_t  stencil;        /* its half-width in cells (0 while off) */
+} SphDiffuseCrestInfo;       /* 32 bytes */
+/* The defaults DESIGN.md section 3j argues for (a starting point, chosen on the default scene). */
+void sph_diffuse_crest_default(SphDiffuseCrest* out);
+/* NULL or rate == 0 switches the term off (the books stay).  Stream-ordered; no re-capture of a graph unless a launch argument changes. */
+int  sph_diffuse_set_crest(SphEngine* e, const SphDiffuseCrest* crest);
+/* The config in force (all zero while off or without a pool). */
+int  sph_diffuse_get_crest(SphEngine* e, SphDiffuseCrest* out);
+/* The books (zeros without a pool).  Synchronises. */
+int  sph_diffuse_crest_info(SphEngine* e, SphDiffuseCrestInfo* out);
+/* sph_diffuse_step_host with the crest term: crest (NULL or rate == 0: exactly sph_diffuse_step_host) and shellRows[0 .. n), the SphShell
+ * rows by id of the state the substep starts from (sph_shell_host or sph_shell_build with the crest config's radius, offset, minCount and
+ * flags; needed when crest is on and n > 0).  crestTotals (may be null) is advanced like the device's books. */
+struct SphShell;             /* (defined with the free-surface particles below) */
+int  sph_diffuse_step_host_crest(const SphDiffuseConfig* cfg, const SphDiffuseCrest* crest, const SphParams* params, float dt, uint64_t substep,
+                                 const SphDiffuse* pool, size_t m, const SphSample* samples, const SphParticle* particles, size_t n,
+                                 const struct SphShell* shellRows, SphDiffuse* out, size_t* countOut, SphDiffuseInfo* totals,
+                                 SphDiffuseCrestInfo* crestTotals);
 
 /* ---- fixed-radius neighbour lists in CSR form (no reference counterpart) --------------------------------------
  * The engine's neighbour relation as an output: for every particle, or for arbitrary query points, the particles within a radius R,
