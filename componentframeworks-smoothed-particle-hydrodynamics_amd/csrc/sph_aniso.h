@@ -3,10 +3,10 @@
 // section 3q).
 //
 // Grid, radius rules, stencil, candidates and the target of a lane are those of sph_query.h (neighbor_stencil, neighbor_rows,
-// query_target; d = x_j - x and r2 = dot3(d, d) are the neighbour lists').  Only positions enter the ellipsoid; 1/rho of the sorted
+// query_target; the candidate walk is neighbor_gather, the own slot included).  Only positions enter the ellipsoid; 1/rho of the sorted
 // copy enters the amplitude.
 //
-//   aniso_accept / aniso_add / aniso_finish / aniso_node_term / aniso_node_value / aniso_coord   __host__ __device__: sph_aniso_host and
+//   aniso_add / aniso_finish / aniso_node_term / aniso_node_value / aniso_coord   __host__ __device__: sph_aniso_host and
 //                             sph_aniso_lattice_host run the same functions over HostGrid in the same row order, so the device gives the
 //                             twins' bytes.  sqrtf and the divisions are correctly rounded on both sides (hipcc's defaults); every other
 //                             operation is rounded on its own (-ffp-contract=off) except the fmaf()s written out below.  WHERE fmaf IS
@@ -18,7 +18,7 @@
 //                             a NaN value gives the bound, the second operand, and so does a tie), so that the sign of a zero is the
 //                             same on both sides.
 //                             No cbrtf, no trigonometry, no floating-point atomics.
-//   k_aniso_gather            one particle per lane in sorted-slot order (built like k_shell_gather<true>): 16 bytes per candidate, the
+//   k_aniso_gather            one particle per lane in sorted-slot order (neighbor_gather<false>): 16 bytes per candidate, the
 //                             eleven sums lane-owned, the Jacobi fully unrolled (p, q compile-time), the 64-byte row as four 16-byte
 //                             stores by particle id and the 48-byte slot record as three by sorted slot; (sparse rows, clamped rows,
 //                             largest count, largest reach as bits) go to stats with one integer atomic per wave and word.
@@ -74,12 +74,6 @@ struct AnisoK {
 __host__ __device__ __forceinline__ float aniso_min(float a, float b) { return a < b ? a : b; }
 __host__ __device__ __forceinline__ float aniso_max(float a, float b) { return a > b ? a : b; }
 
-// d = x_j - x and r2 = dot3(d, d): the bits of neighbor_accept's r2.
-__host__ __device__ inline bool aniso_accept(float xi, float yi, float zi, float xj, float yj, float zj, float R2, float& dx, float& dy, float& dz, float& r2) {
-    dx = xj - xi; dy = yj - yi; dz = zj - zi;
-    r2 = dot3(dx, dy, dz, dx, dy, dz);
-    return r2 < R2;
-}
 // One accepted candidate (the particle's own slot is one: d = 0, w = R2^3).
 __host__ __device__ inline void aniso_add(AnisoAcc& a, float dx, float dy, float dz, float r2, float R2) {
     const float t = R2 - r2;
@@ -264,16 +258,7 @@ __global__ __launch_bounds__(kBlock) void k_aniso_gather(SimK k, NbK nb, AnisoK 
     if (walk) {
         AnisoAcc a;
         aniso_reset(a);
-        const int3 cell = cell_of(k, P.x, P.y, P.z);
-        neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
-            for (uint32_t j = qs; j < qe; ++j) {
-                const float4 J = pv[2u * j];
-                float dx, dy, dz, r2;
-                if (!aniso_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
-                if (fluidOnly && slot_ghost(own, j)) continue;
-                aniso_add(a, dx, dy, dz, r2, nb.R2);
-            }
-        });
+        neighbor_gather<false>(k, nb, pv, cellStart, own, fluidOnly, P, 0u, [&](float dx, float dy, float dz, float r2) { aniso_add(a, dx, dy, dz, r2, nb.R2); });
         if (a.cnt) aniso_finish(a, ak, P.x, P.y, P.z, P.w, r, s);                // (always: the particle's own slot is a candidate)
     }
     if (act) {

@@ -136,6 +136,19 @@ struct StageRing {
 
 inline int blocks_for(size_t n, int per = sph::kBlock) { return (int)((n + per - 1) / per); }
 
+// The scratch of one 64-bit scan (scan_counts64_launch) of `rows` counts: blocks_for(rows, kScanTile) + 2 words of tile sums (the totals,
+// sum and largest count, lie behind them) and one maximum per tile.  Dead once a scan's totals have been read.
+struct ScanScratch {
+    DevBuf<unsigned long long> tileSums;
+    DevBuf<uint32_t> tileMax;
+    int grow(SphEngine* e, size_t rows) {
+        const size_t tiles = (size_t)blocks_for(rows, sph::kScanTile);
+        const int rc = tileSums.grow(e, tiles + 2);
+        return rc ? rc : tileMax.grow(e, tiles);
+    }
+    void release() { tileSums.release(); tileMax.release(); }
+};
+
 }  // namespace
 
 static std::set<SphEngine*> g_engines;      // live engines of this process (sph_destroy clears what neighbours hold of a destroyed one)
@@ -247,9 +260,8 @@ struct SphEngine {
     DevBuf<SphSample> d_sampleOut;
     // the queries that walk the grid by particle id (neighbour lists, kNN): ids of the sorted slots, refilled by every run (slot_ids_fill)
     DevBuf<int32_t> d_slotIds;
-    // the scratch of the 64-bit scan of neighbour lists, components and shell (scan_scratch_grow): dead once a scan's totals have been read
-    DevBuf<unsigned long long> d_scanTileSums;   // (the two totals lie behind the tile sums)
-    DevBuf<uint32_t> d_scanTileMax;
+    // the scratch of the 64-bit scan of neighbour lists, components and shell
+    ScanScratch scanScratch;
     // sph_neighbors_*: counts, the offsets of their scan, and the lists themselves (CSR)
     DevBuf<int32_t> d_nbIndices;
     DevBuf<uint32_t> d_nbCnt;
@@ -349,9 +361,9 @@ struct SphEngine {
     uint32_t* d_dfCrState = nullptr;
     StageRing<sph::DiffuseCrestCoef> dfCrStage;
     DevBuf<float4> d_dfCrNrm;
-    DevBuf<uint32_t> d_dfCrFlag, d_dfCrTileMax, d_dfCrPart;
+    DevBuf<uint32_t> d_dfCrFlag, d_dfCrPart;
     DevBuf<long long> d_dfCrOffsets;
-    DevBuf<unsigned long long> d_dfCrTileSums;
+    ScanScratch dfCrScan;
     DevBuf<int32_t> d_dfCrSlots;
     DevBuf<float> d_dfCrCrest;
     bool dfCrOn = false;
@@ -520,7 +532,7 @@ void free_grid_buffers(SphEngine* e) {
 void sample_free(SphEngine* e) { e->d_sampleIn.release(); e->d_sampleOut.release(); }
 void neighbors_free(SphEngine* e) {
     e->d_slotIds.release(); e->d_nbIndices.release(); e->d_nbCnt.release(); e->d_nbOffsets.release();
-    e->d_scanTileSums.release(); e->d_scanTileMax.release();        // (the scan scratch of components and shell too: the three are freed together)
+    e->scanScratch.release();                                       // (the scan scratch of components and shell too: the three are freed together)
     e->nbInfo = SphNeighborInfo{};
     e->nbIndexed = false;
 }
@@ -574,8 +586,8 @@ void diffuse_free(SphEngine* e) {
     e->dfCfg = SphDiffuseConfig{};
     dev_free(e->d_dfCrCoef); dev_free(e->d_dfCrState);               // (the crest term goes with the pool)
     e->dfCrStage.destroy();
-    e->d_dfCrNrm.release(); e->d_dfCrFlag.release(); e->d_dfCrTileMax.release(); e->d_dfCrPart.release(); e->d_dfCrOffsets.release();
-    e->d_dfCrTileSums.release(); e->d_dfCrSlots.release(); e->d_dfCrCrest.release();
+    e->d_dfCrNrm.release(); e->d_dfCrFlag.release(); e->dfCrScan.release(); e->d_dfCrPart.release(); e->d_dfCrOffsets.release();
+    e->d_dfCrSlots.release(); e->d_dfCrCrest.release();
     e->dfCrOn = false;
     e->dfCrCfg = SphDiffuseCrest{};
 }
@@ -796,22 +808,41 @@ int tracers_advect(SphEngine* e, const SimK& k, float dt) {
     return SPH_OK;
 }
 
+// ---- what the shell pass inside the substep shares with the queries (sph_query.h, sph_shell.h) ----
+NbK make_nbk(const SphEngine* e, float radius, int stencil, int flags, size_t n) { return NbK{radius * radius, stencil, flags, e->idBase, (uint32_t)n}; }
+// The three launches of the 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0, on scratch grown for `rows`
+// (no bracket, no synchronisation); returns where the totals lie on the device.
+unsigned long long* scan_counts64_launch(SphEngine* e, const ScanScratch& scratch, const uint32_t* cnt, size_t rows, long long* offsets) {
+    const int tiles = blocks_for(rows, kScanTile);
+    unsigned long long *tileSums = scratch.tileSums.p, *totals = tileSums + tiles;
+    uint32_t* tileMax = scratch.tileMax.p;
+    hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
+    hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
+    hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
+                       (const unsigned long long*)totals, offsets);
+    return totals;
+}
+// The radius in force of a shell config (radius <= 0: h) and the constants of its kernels.
+float shell_radius(const SphShellConfig& cfg, float h) { return cfg.radius <= 0.0f ? h : cfg.radius; }
+ShellK shell_consts(const SphShellConfig& cfg, float radius) { return ShellK{radius, radius * radius, cfg.offset, cfg.minCount}; }
+
 // ---- spray, foam and bubbles (sph_diffuse.h) -----------------------------------------------------
-// The launch arguments of the crest term's shell pass at the current params (radius <= 0: h); false: no radius of this grid.
+// The crest term's shell pass as a shell config.
+SphShellConfig diffuse_crest_shell_config(const SphDiffuseCrest& c) { return SphShellConfig{c.radius, c.offset, c.minCount, c.flags}; }
+// The launch arguments of the crest term's shell pass at the current params; false: no radius of this grid.
 bool diffuse_crest_args(const SphEngine* e, float cellSize, float* radius, int* stencil) {
-    *radius = e->dfCrCfg.radius <= 0.0f ? e->params.param_h : e->dfCrCfg.radius;
+    *radius = shell_radius(diffuse_crest_shell_config(e->dfCrCfg), e->params.param_h);
     *stencil = sph::neighbor_stencil(*radius, cellSize);
     return *stencil != 0;
 }
 
 // The scratch of the crest term's shell pass for n slots, grown in the eager run in front of the substep's timed bracket.
 int diffuse_crest_scratch(SphEngine* e, uint32_t n) {
-    const size_t tiles = (size_t)blocks_for((size_t)n, kScanTile);
     int rc;
     if (e->d_dfCrOffsets.cap < (size_t)n + 1) {              // (grown last: a failed growth is tried again; never while capturing)
         if (e->capturing) return fail(SPH_ERR_STATE, "diffuse crest scratch missing during a graph capture");
         if ((rc = e->d_dfCrNrm.grow(e, n)) || (rc = e->d_dfCrFlag.grow(e, n)) || (rc = e->d_dfCrSlots.grow(e, n)) || (rc = e->d_dfCrCrest.grow(e, n)) ||
-            (rc = e->d_dfCrTileSums.grow(e, tiles + 2)) || (rc = e->d_dfCrTileMax.grow(e, tiles)) || (rc = e->d_dfCrPart.grow(e, (size_t)blocks_for(n))) ||
+            (rc = e->dfCrScan.grow(e, n)) || (rc = e->d_dfCrPart.grow(e, (size_t)blocks_for(n))) ||
             (rc = e->d_dfCrOffsets.grow(e, (size_t)n + 1))) return rc;
         // (a first substep that does not act leaves the passes idle: the scan and the count must still read defined words)
         HIP_TRY(hipMemsetAsync(e->d_dfCrNrm.p, 0, e->d_dfCrNrm.cap * sizeof(float4), e->stream));
@@ -831,23 +862,17 @@ int diffuse_crest_shell(SphEngine* e, const SimK& k, uint32_t n) {
     if (!diffuse_crest_args(e, k.cellSize, &radius, &stencil))
         return fail(SPH_ERR_STATE, "diffuse crest radius %g is above three cells (%g) of this grid", (double)radius, (double)(3.0f * k.cellSize));
     if (!n) return SPH_OK;
-    const size_t tiles = (size_t)blocks_for((size_t)n, kScanTile);
-    NbK nb;
-    nb.R2 = radius * radius; nb.s = stencil; nb.flags = e->dfCrCfg.flags; nb.idBase = e->idBase; nb.n = n;
-    ShellK sk;
-    sk.R = radius; sk.R2 = radius * radius; sk.offset = e->dfCrCfg.offset; sk.minCount = e->dfCrCfg.minCount;
-    const dim3 grid(blocks_for(n)), block(kBlock), scan((unsigned)tiles);
+    const SphShellConfig cfg = diffuse_crest_shell_config(e->dfCrCfg);
+    const NbK nb = make_nbk(e, radius, stencil, cfg.flags, n);
+    const ShellK sk = shell_consts(cfg, radius);
+    const dim3 grid(blocks_for(n)), block(kBlock);
     const float4* pv = (const float4*)e->d_sPV;
     const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
     const uint32_t* counter = (const uint32_t*)e->d_dfState + DF_STEP_LO;
     const uint32_t* period = &e->d_dfCrCoef->every;          // (an address, not a load: device memory)
-    unsigned long long *tileSums = e->d_dfCrTileSums.p, *totals = tileSums + tiles;
     hipLaunchKernelGGL(k_shell_slot_gather, grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const float4*)e->d_sOwn, counter, period, e->d_dfCrNrm.p,
                        e->d_dfCrFlag.p);
-    hipLaunchKernelGGL(k_neighbors_scan_reduce, scan, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, tileSums, e->d_dfCrTileMax.p);
-    hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), block, 0, e->stream, tileSums, (const uint32_t*)e->d_dfCrTileMax.p, (int)tiles, totals);
-    hipLaunchKernelGGL(k_neighbors_scan_apply, scan, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, (const unsigned long long*)tileSums,
-                       (const unsigned long long*)totals, e->d_dfCrOffsets.p);
+    (void)scan_counts64_launch(e, e->dfCrScan, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, e->d_dfCrOffsets.p);
     hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_dfCrFlag.p, (const long long*)e->d_dfCrOffsets.p, (size_t)n, e->d_dfCrSlots.p);
     hipLaunchKernelGGL(k_shell_slot_crest, grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const float4*)e->d_dfCrNrm.p, (const int32_t*)e->d_dfCrSlots.p,
                        (const long long*)e->d_dfCrOffsets.p + n, counter, period, e->d_dfCrCrest.p);
@@ -1635,8 +1660,8 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     // crest births of the pool, only while the term is on (off: the material of before): every buffer its launches get and the shell pass's
     // launch arguments (radius, hence the stencil, offset, minCount, flags); rate, windows, align and every are read from memory
     if (e->dfC && e->dfCrOn) {
-        const void* cr[10] = {e->d_dfCrCoef, e->d_dfCrState, e->d_dfCrNrm.p, e->d_dfCrFlag.p, e->d_dfCrTileMax.p, e->d_dfCrPart.p, e->d_dfCrOffsets.p,
-                              e->d_dfCrTileSums.p, e->d_dfCrSlots.p, e->d_dfCrCrest.p};
+        const void* cr[10] = {e->d_dfCrCoef, e->d_dfCrState, e->d_dfCrNrm.p, e->d_dfCrFlag.p, e->dfCrScan.tileMax.p, e->d_dfCrPart.p, e->d_dfCrOffsets.p,
+                              e->dfCrScan.tileSums.p, e->d_dfCrSlots.p, e->d_dfCrCrest.p};
         add(cr, sizeof(cr));
         add(&e->dfCrCfg.radius, sizeof(float));                       // (with the params above it fixes the radius in force and the stencil)
         add(&e->dfCrCfg.offset, sizeof(float)); add(&e->dfCrCfg.minCount, sizeof(uint32_t)); add(&e->dfCrCfg.flags, sizeof(int32_t));
@@ -2941,41 +2966,19 @@ static int radius_stencil(float radius, float cellSize, int* stencil) {
     if (!*stencil) return fail(SPH_ERR_ARG, "radius %g is not finite, not > 0 or above three cells (%g)", (double)radius, (double)(3.0f * cellSize));
     return SPH_OK;
 }
-static sph::NbK make_nbk(const SphEngine* e, float radius, int stencil, int flags) {
-    sph::NbK nb;
-    nb.R2 = radius * radius; nb.s = stencil; nb.flags = flags; nb.idBase = e->idBase; nb.n = (uint32_t)e->n;
-    return nb;
-}
 // ids[slot] of the grid sample_grid has just built, into d_slotIds (grown by the caller).
 static void slot_ids_fill(SphEngine* e) {
     if (!e->n) return;
     Timed t(e, SPH_K_OTHER);
     hipLaunchKernelGGL(k_neighbors_ids, dim3(blocks_for(e->n)), dim3(kBlock), 0, e->stream, (const float4*)e->d_sOwn, e->d_slotIds.p, e->idBase, (uint32_t)e->n);
 }
-// The scratch of scan_counts64 for `rows` counts, one pair for every family: blocks_for(rows, kScanTile) + 2 words of tile sums (the
-// totals, sum and largest count, lie behind them) and one maximum per tile.  Dead once a scan's totals have been read.
-static int scan_scratch_grow(SphEngine* e, size_t rows) {
-    const size_t tiles = (size_t)blocks_for(rows, kScanTile);
-    const int rc = e->d_scanTileSums.grow(e, tiles + 2);
-    return rc ? rc : e->d_scanTileMax.grow(e, tiles);
-}
-// The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0 (scan_scratch_grow first).  One synchronisation: hostTotals[0 .. 2).
-// scan_counts64_launch: the three launches alone (no bracket, no synchronisation); returns where the totals lie on the device.
-static unsigned long long* scan_counts64_launch(SphEngine* e, const uint32_t* cnt, size_t rows, long long* offsets) {
-    const int tiles = blocks_for(rows, kScanTile);
-    unsigned long long *tileSums = e->d_scanTileSums.p, *totals = tileSums + tiles;
-    uint32_t* tileMax = e->d_scanTileMax.p;
-    hipLaunchKernelGGL(k_neighbors_scan_reduce, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, tileSums, tileMax);
-    hipLaunchKernelGGL(k_neighbors_scan_tiles, dim3(1), dim3(kBlock), 0, e->stream, tileSums, (const uint32_t*)tileMax, tiles, totals);
-    hipLaunchKernelGGL(k_neighbors_scan_apply, dim3(tiles), dim3(kBlock), 0, e->stream, cnt, rows, (const unsigned long long*)tileSums,
-                       (const unsigned long long*)totals, offsets);
-    return totals;
-}
+// The 64-bit exclusive scan of cnt[0 .. rows) into offsets[0 .. rows], rows > 0, on the queries' scratch (scanScratch.grow first): the
+// three launches in one bracket.  One synchronisation: hostTotals[0 .. 2).
 static int scan_counts64(SphEngine* e, const uint32_t* cnt, size_t rows, long long* offsets, unsigned long long hostTotals[2]) {
     unsigned long long* totals;
     {
         Timed t(e, SPH_K_OTHER);
-        totals = scan_counts64_launch(e, cnt, rows, offsets);
+        totals = scan_counts64_launch(e, e->scanScratch, cnt, rows, offsets);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hostTotals, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -3081,9 +3084,9 @@ static int neighbors_run(SphEngine* e, const float4* devPoints, size_t m, float 
     e->nbInfo = SphNeighborInfo{};                                                  // (the lists held so far end here)
     e->nbIndexed = false;
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_nbCnt.grow(e, rows)) || (rc = e->d_nbOffsets.grow(e, rows + 1)) ||
-        (rc = scan_scratch_grow(e, rows))) return rc;
+        (rc = e->scanScratch.grow(e, rows))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    const NbK nb = make_nbk(e, radius, stencil, flags);
+    const NbK nb = make_nbk(e, radius, stencil, flags, e->n);
     const dim3 grid(blocks_for(rows)), block(kBlock);
     using Count = void (*)(SimK, NbK, const float4*, const uint32_t*, const int32_t*, const float4*, size_t, uint32_t*);
     using Fill = void (*)(SimK, NbK, const float4*, const uint32_t*, const int32_t*, const float4*, size_t, const long long*, int32_t*);
@@ -3245,14 +3248,14 @@ int sph_components_build(SphEngine* e, float radius, int flags, SphComponentInfo
     e->ccInfo = SphComponentInfo{};                                                 // (the result held so far ends here)
     e->ccValid = false;
     if ((rc = e->d_ccIds.grow(e, n)) || (rc = e->d_ccLabels.grow(e, n)) || (rc = e->d_ccRoots.grow(e, n)) || (rc = e->d_ccParent.grow(e, n)) ||
-        (rc = e->d_ccMinId.grow(e, n)) || (rc = e->d_ccFlag.grow(e, n)) || (rc = e->d_ccOffsets.grow(e, n + 1)) || (rc = scan_scratch_grow(e, n)) ||
+        (rc = e->d_ccMinId.grow(e, n)) || (rc = e->d_ccFlag.grow(e, n)) || (rc = e->d_ccOffsets.grow(e, n + 1)) || (rc = e->scanScratch.grow(e, n)) ||
         (rc = e->d_ccWords.grow(e, (size_t)kCcWords)) || (rc = e->d_ccStats.grow(e, 3))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
     SphComponentInfo info{};
     info.rows = n; info.radius = radius; info.stencil = stencil; info.flags = flags;
     uint64_t C = 0;
     if (n) {
-        const NbK nb = make_nbk(e, radius, stencil, flags);
+        const NbK nb = make_nbk(e, radius, stencil, flags, e->n);
         const dim3 grid(blocks_for(n)), block(kBlock);
         const float4* pv = (const float4*)e->d_sPV;
         const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
@@ -3503,7 +3506,7 @@ static int knn_run(SphEngine* e, bool query, const float4* devPoints, size_t m, 
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_knnIndices.grow(e, rows * (size_t)kk)) || (rc = e->d_knnDist2.grow(e, rows * (size_t)kk)) ||
         (rc = e->d_knnCounts.grow(e, rows)) || (rc = e->d_knnStats.grow(e, 2))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    const NbK nb = make_nbk(e, radius, stencil, flags);
+    const NbK nb = make_nbk(e, radius, stencil, flags, e->n);
     unsigned long long host[2] = {0ull, 0ull};
     if (rows) {
         HIP_TRY(hipMemsetAsync(e->d_knnStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
@@ -3632,13 +3635,8 @@ void sph_shell_default(SphShellConfig* cfg) {
 static int shell_check(const SphShellConfig& cfg, float h, float cellSize, float* radius, int* stencil) {
     if (cfg.flags & ~SPH_SHELL_FLUID_ONLY) return fail(SPH_ERR_ARG, "unknown shell flags %d", cfg.flags);
     if (!std::isfinite(cfg.offset) || cfg.offset < 0.0f) return fail(SPH_ERR_ARG, "offset %g is not finite or < 0", (double)cfg.offset);
-    *radius = cfg.radius <= 0.0f ? h : cfg.radius;
+    *radius = shell_radius(cfg, h);
     return radius_stencil(*radius, cellSize, stencil);
-}
-static sph::ShellK shell_consts(const SphShellConfig& cfg, float radius) {
-    sph::ShellK sk;
-    sk.R = radius; sk.R2 = radius * radius; sk.offset = cfg.offset; sk.minCount = cfg.minCount;
-    return sk;
 }
 
 // Grid of the current state, ids, pass 1, the scan of the flags by row (ids) and -- particle rows -- by slot (the targets of pass 2), pass 2.
@@ -3653,11 +3651,11 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
     const size_t n = e->n, rows = query ? m : n;
     e->shellInfo = SphShellInfo{};                                                  // (the rows held so far end here)
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_shRows.grow(e, rows)) || (rc = e->d_shIds.grow(e, rows)) || (rc = e->d_shFlagRow.grow(e, rows)) ||
-        (rc = e->d_shOffsets.grow(e, rows + 1)) || (rc = scan_scratch_grow(e, rows)) ||
+        (rc = e->d_shOffsets.grow(e, rows + 1)) || (rc = e->scanScratch.grow(e, rows)) ||
         (rc = e->d_shStats.grow(e, 2))) return rc;
     if (!query && ((rc = e->d_shNrm.grow(e, n)) || (rc = e->d_shFlagSlot.grow(e, n)) || (rc = e->d_shSlots.grow(e, n)))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    const NbK nb = make_nbk(e, radius, stencil, cfg.flags);
+    const NbK nb = make_nbk(e, radius, stencil, cfg.flags, e->n);
     const ShellK sk = shell_consts(cfg, radius);
     const int timed = e->optShellTimed;
     unsigned long long stats[2] = {0ull, 0ull}, totals[2] = {0ull, 0ull};
@@ -3676,7 +3674,7 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
         else hipLaunchKernelGGL((k_shell_gather<true>), grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn,
                                 devPoints, rows, e->d_shRows.p, e->d_shFlagRow.p, e->d_shNrm.p, e->d_shFlagSlot.p, e->d_shStats.p);
         bracket(3);                                                                 // ids[]: the flags by row, scanned and compacted
-        unsigned long long* devTotals = scan_counts64_launch(e, e->d_shFlagRow.p, rows, e->d_shOffsets.p);
+        unsigned long long* devTotals = scan_counts64_launch(e, e->scanScratch, e->d_shFlagRow.p, rows, e->d_shOffsets.p);
         hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagRow.p, (const long long*)e->d_shOffsets.p, rows, e->d_shIds.p);
         t.reset();
         HIP_TRY(hipGetLastError());
@@ -3687,7 +3685,7 @@ static int shell_run(SphEngine* e, bool query, const float4* devPoints, size_t m
         if (numShell > rows) return fail(SPH_ERR_STATE, "shell: %zu shell rows of %zu", numShell, rows);
         if (!query && numShell) {                                                   // the same scan by slot: pass 2's targets in ascending slot order
             bracket(3);
-            (void)scan_counts64_launch(e, e->d_shFlagSlot.p, n, e->d_shOffsets.p);
+            (void)scan_counts64_launch(e, e->scanScratch, e->d_shFlagSlot.p, n, e->d_shOffsets.p);
             hipLaunchKernelGGL(k_shell_compact, grid, block, 0, e->stream, (const uint32_t*)e->d_shFlagSlot.p, (const long long*)e->d_shOffsets.p, n, e->d_shSlots.p);
             bracket(2);
             hipLaunchKernelGGL(k_shell_crest, dim3(blocks_for(numShell)), block, 0, e->stream, k, nb, sk, pv, cellStart, (const int32_t*)e->d_slotIds.p,
@@ -3775,17 +3773,8 @@ int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* para
         if (!walk) continue;
         sph::ShellAcc a;
         sph::shell_reset(a);
-        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
-            for (uint32_t j = qs; j < qe; ++j) {
-                if (!query && j == slotOf[r]) continue;
-                const uint32_t o = order[j];
-                const float* y = particles[o].pos;
-                float dx, dy, dz, r2;
-                if (!sph::shell_accept(x[0], x[1], x[2], y[0], y[1], y[2], sk.R2, dx, dy, dz, r2)) continue;
-                if (fluidOnly && particles[o].isGhost != 0) continue;
-                sph::shell_add(a, dx, dy, dz, r2, sk.R2);
-            }
-        });
+        grid.gather(stencil, x, sk.R2, particles, fluidOnly, query ? sph::HostGrid::kNoSlot : slotOf[r],
+                    [&](float dx, float dy, float dz, float r2) { sph::shell_add(a, dx, dy, dz, r2, sk.R2); });
         sph::shell_finish(a, sk, res[r]);
         if (sums4) { sums4[4 * r] = a.Sx; sums4[4 * r + 1] = a.Sy; sums4[4 * r + 2] = a.Sz; sums4[4 * r + 3] = a.W; }
         if (res[r].flags & sph::kShellIsolated) info.numIsolated += 1u;
@@ -3802,7 +3791,7 @@ int sph_shell_host(const SphParticle* particles, size_t n, const SphParams* para
                 if (!(res[o].flags & sph::kShellMember) || j == slotOf[r]) continue;
                 const float* y = particles[o].pos;
                 float dx, dy, dz, r2;
-                if (!sph::shell_accept(x[0], x[1], x[2], y[0], y[1], y[2], sk.R2, dx, dy, dz, r2)) continue;
+                if (!sph::neighbor_offset(x[0], x[1], x[2], y[0], y[1], y[2], sk.R2, dx, dy, dz, r2)) continue;
                 crest += sph::shell_crest_term(nrm[0], nrm[1], nrm[2], res[o].normal[0], res[o].normal[1], res[o].normal[2], dx, dy, dz, r2, sk.R);
             }
         });
@@ -4135,7 +4124,7 @@ static int aniso_run(SphEngine* e, const SphAnisoConfig& cfg, SphAnisoInfo* out,
     e->anisoInfo = SphAnisoInfo{};                                                  // (the rows held so far end here)
     if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_anRows.grow(e, n)) || (rc = e->d_anSlots.grow(e, 3 * n)) || (rc = e->d_anStats.grow(e, 4))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
-    const NbK nb = make_nbk(e, radius, stencil, cfg.flags);
+    const NbK nb = make_nbk(e, radius, stencil, cfg.flags, e->n);
     unsigned long long stats[4] = {0ull, 0ull, 0ull, 0ull};
     if (n) {
         HIP_TRY(hipMemsetAsync(e->d_anStats.p, 0, sizeof(stats), e->stream));
@@ -4235,7 +4224,6 @@ int sph_aniso_surface(SphEngine* e, const SphAnisoConfig* cfg, const float origi
 // The rows and the slot records (by sorted slot of `grid`) of host records: what both twins start from.
 static void aniso_rows_host(const SphParticle* particles, size_t n, const sph::HostGrid& grid, int stencil, const sph::AnisoK& ak, bool fluidOnly,
                             std::vector<sph::AnisoRow>& res, std::vector<sph::AnisoSlot>& slots, SphAnisoInfo& info) {
-    const std::vector<uint32_t>& order = grid.order;
     res.resize(n);
     slots.resize(n);
     for (size_t r = 0; r < n; ++r) {
@@ -4247,16 +4235,8 @@ static void aniso_rows_host(const SphParticle* particles, size_t n, const sph::H
         if (!walk) continue;
         sph::AnisoAcc a;
         sph::aniso_reset(a);
-        grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
-            for (uint32_t j = qs; j < qe; ++j) {
-                const uint32_t o = order[j];
-                const float* y = particles[o].pos;
-                float dx, dy, dz, r2;
-                if (!sph::aniso_accept(x[0], x[1], x[2], y[0], y[1], y[2], ak.R2, dx, dy, dz, r2)) continue;
-                if (fluidOnly && particles[o].isGhost != 0) continue;
-                sph::aniso_add(a, dx, dy, dz, r2, ak.R2);
-            }
-        });
+        grid.gather(stencil, x, ak.R2, particles, fluidOnly, sph::HostGrid::kNoSlot,
+                    [&](float dx, float dy, float dz, float r2) { sph::aniso_add(a, dx, dy, dz, r2, ak.R2); });
         const float invRho = particles[r].density > 0.0f ? 1.0f / particles[r].density : 0.0f;
         if (a.cnt) sph::aniso_finish(a, ak, x[0], x[1], x[2], invRho, res[r], slot);
         if (res[r].flags & sph::kAnisoSparse) info.numSparse += 1u;
@@ -4672,11 +4652,10 @@ static bool crest_window(float lo, float hi) { return std::isfinite(lo) && std::
 // The crest config as an argument (h and cellSize: of the params the shell pass would run with).
 static int diffuse_check_crest(const SphDiffuseCrest& c, float h, float cellSize) {
     if (!diffuse_nonneg(c.rate)) return fail(SPH_ERR_ARG, "diffuse crest rate must be finite and >= 0");
-    const SphShellConfig sc{c.radius, c.offset, c.minCount, c.flags};
     float radius = 0.0f;
     int stencil = 0, rc;
     if (!std::isfinite(c.radius)) return fail(SPH_ERR_ARG, "diffuse crest radius %g is not finite", (double)c.radius);
-    if ((rc = shell_check(sc, h, cellSize, &radius, &stencil))) return rc;
+    if ((rc = shell_check(diffuse_crest_shell_config(c), h, cellSize, &radius, &stencil))) return rc;
     if (!crest_window(c.crestMin, c.crestMax)) return fail(SPH_ERR_ARG, "diffuse crest window [%g, %g] is empty or not finite", (double)c.crestMin, (double)c.crestMax);
     if (!crest_window(c.speedMin, c.speedMax)) return fail(SPH_ERR_ARG, "diffuse crest speed window [%g, %g] is empty or not finite", (double)c.speedMin, (double)c.speedMax);
     if (!(c.align >= 0.0f && c.align <= 1.0f)) return fail(SPH_ERR_ARG, "diffuse crest align %g outside [0, 1]", (double)c.align);

@@ -1,12 +1,16 @@
-// sph_query.h -- what the spatial queries share (neighbour lists, components, kNN, shell, rays; the *_host twins): the stencil and its
-// row walk, the target of a lane, the CPU grid of the twins, and the kernels every family launches.  Shared layer (with sph_sample.h):
-// it stands on the base and substep headers only, and every feature header may include it.
+// sph_query.h -- what the spatial queries share (neighbour lists, components, kNN, shell, aniso, rays; the *_host twins): the stencil
+// and its row walk, the candidate walk of the families that sum over positions alone (shell, aniso), the target of a lane, the CPU grid
+// of the twins, and the kernels every family launches.  Shared layer (with sph_sample.h): it stands on the base and substep headers
+// only, and every feature header may include it.
 //
 // A target at x in cell (cx, cy, cz) (cell_of, clamped) sees the members of the cells [c - s, c + s] per axis that lie in the grid,
 // s = 1, 2, 3 the smallest half-width with R <= (float)s * cellSize: (2s + 1)^2 rows in (dz, dy) order, each row one contiguous run of
 // sorted slots, i.e. ascending sorted slot = ascending (cell index, particle id).
 //
-//   neighbor_stencil / neighbor_rows / neighbor_accept: __host__ __device__ (the twins walk HostGrid with them); slot_ghost / query_target: device
+//   neighbor_stencil / neighbor_rows / neighbor_accept / neighbor_offset: __host__ __device__ (the twins walk HostGrid with them);
+//   slot_ghost / query_target: device
+//   neighbor_gather<SKIP> / HostGrid::gather: the candidate walk of the shell's pass 1 and the aniso gather, device and twin.  The other
+//                          families keep their loops: they read other data before the distance test, keep j, or stage rows in LDS.
 // The kernels keep the names of their first users (tools and committed profiles match kernels by name); all of them are shared:
 //   k_neighbors_ids        ids[slot] = particle id of the sorted slot (neighbour lists, kNN, shell)
 //   k_neighbors_scan_*     64-bit exclusive scan of cnt into offsets[0 .. rows], and the largest count; tiles, no atomics (neighbour
@@ -34,6 +38,13 @@ __host__ __device__ inline bool neighbor_accept(float xi, float yi, float zi, fl
     const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
     return dot3(dx, dy, dz, dx, dy, dz) < R2;
 }
+// The same test for a family that sums over d = x_j - x: r2 = dot3(d, d) has the bits of neighbor_accept's r2 (its d is the exact
+// negative, the squares are the same floats).
+__host__ __device__ inline bool neighbor_offset(float xi, float yi, float zi, float xj, float yj, float zj, float R2, float& dx, float& dy, float& dz, float& r2) {
+    dx = xj - xi; dy = yj - yi; dz = zj - zi;
+    r2 = dot3(dx, dy, dz, dx, dy, dz);
+    return r2 < R2;
+}
 
 struct NbK {
     float R2;
@@ -52,6 +63,29 @@ __host__ __device__ __forceinline__ void neighbor_rows(const SimK& k, const uint
         const int rowBase = (nz * k.gy + ny) * k.gx;
         f(cellStart[rowBase + xlo], min(cellStart[rowBase + xhi + 1], n));
     }
+}
+
+// Is the record of sorted slot j a ghost (isGhost != 0)?  One word of its own data.
+__device__ __forceinline__ bool slot_ghost(const float4* __restrict__ own, uint32_t j) {
+    return (fbits(reinterpret_cast<const float*>(own)[(size_t)j * 4u + 2u]) & F_GHOSTNZ) != 0u;
+}
+
+// The candidate walk of a target at P: f(dx, dy, dz, r2) per accepted candidate j of the rows of cell_of(P), j ascending, without
+// j == self where SKIP; under fluidOnly without ghosts.  The position is loaded first, the own data second and for accepted candidates only.
+template <bool SKIP, class F>
+__device__ __forceinline__ void neighbor_gather(const SimK& k, const NbK& nb, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                const float4* __restrict__ own, bool fluidOnly, const float4& P, uint32_t self, F&& f) {
+    const int3 cell = cell_of(k, P.x, P.y, P.z);
+    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
+        for (uint32_t j = qs; j < qe; ++j) {
+            if (SKIP && j == self) continue;
+            const float4 J = pv[2u * j];
+            float dx, dy, dz, r2;
+            if (!neighbor_offset(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
+            if (fluidOnly && slot_ghost(own, j)) continue;
+            f(dx, dy, dz, r2);
+        }
+    });
 }
 
 // The grid of host records as the counting sort leaves it: cells ascending, members ascending by index.  start[c] is the first sorted
@@ -76,12 +110,22 @@ struct HostGrid {
     void rows(int s, int cx, int cy, int cz, F&& f) const { neighbor_rows(k, start.data(), s, (uint32_t)order.size(), cx, cy, cz, f); }
     template <class F>
     void rows(int s, const float* x, F&& f) const { const int3 c = cell_of(k, x[0], x[1], x[2]); rows(s, c.x, c.y, c.z, f); }
+    // neighbor_gather's twin for a target at x: the same visits in the same order over order[]; skipSlot is kNoSlot where nothing is skipped.
+    static constexpr uint32_t kNoSlot = 0xffffffffu;
+    template <class F>
+    void gather(int s, const float* x, float R2, const SphParticle* particles, bool fluidOnly, uint32_t skipSlot, F&& f) const {
+        rows(s, x, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                if (j == skipSlot) continue;
+                const SphParticle& c = particles[order[j]];
+                float dx, dy, dz, r2;
+                if (!neighbor_offset(x[0], x[1], x[2], c.pos[0], c.pos[1], c.pos[2], R2, dx, dy, dz, r2)) continue;
+                if (fluidOnly && c.isGhost != 0) continue;
+                f(dx, dy, dz, r2);
+            }
+        });
+    }
 };
-
-// Is the record of sorted slot j a ghost (isGhost != 0)?  One word of its own data.
-__device__ __forceinline__ bool slot_ghost(const float4* __restrict__ own, uint32_t j) {
-    return (fbits(reinterpret_cast<const float*>(own)[(size_t)j * 4u + 2u]) & F_GHOSTNZ) != 0u;
-}
 
 // Target of a lane: particle rows, slot i -> (position, row = id); query rows, point i -> (position, row = i).  false: the lane has no
 // row.  walk: a query point walks when it is finite; a particle always does.  A family's FLUID_ONLY rule for a ghost target stays with

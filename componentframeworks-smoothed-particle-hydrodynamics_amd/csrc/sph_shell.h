@@ -2,7 +2,7 @@
 // faces there, and how sharply convex it is (no reference counterpart).
 //
 // Grid, radius rules, stencil, candidates and the target of a lane are those of sph_query.h (neighbor_stencil, neighbor_rows,
-// query_target; r2 is neighbor_accept's).
+// query_target, neighbor_offset, neighbor_gather).
 // Only positions enter.  Pass 1 sums, over the accepted candidates j of a target at x in row order, with d = x_j - x, t = R2 - r2 and
 // w = t * t:  cnt += 1, W += w, S = fma(w, d, S).  The finish turns (cnt, W, S) into the record: s2 = dot3(S, S), lim = (offset R) W,
 // in the shell iff cnt == 0 or cnt < minCount or s2 > lim^2; normal = -S / sqrt(s2) (zero where s2 == 0); offsetRatio = sqrt(s2) /
@@ -10,21 +10,27 @@
 // candidate lies behind the target's tangent plane), the term (1 - dot(n_i, n_j)) (1 - sqrt(r2) / R) joins the crest sum, which is
 // kept in fixed point (units of 2^-32) so that it is the same whatever the order of the candidates.
 //
-//   shell_accept / shell_add / shell_finish / shell_crest_term / shell_crest_value   __host__ __device__: sph_shell_host runs the same functions over
+//   shell_add / shell_finish / shell_crest_term / shell_crest_value   __host__ __device__: sph_shell_host runs the same functions over
 //                             HostGrid in the same row order, so the device's rows equal the twin's bytes.  sqrtf and the divisions
 //                             are correctly rounded on both sides (hipcc's defaults, as sph_rays.h relies on them); everything else is
 //                             the explicit fmaf()s and single operations (-ffp-contract=off).
-//   k_shell_gather<P>         pass 1: one target per lane (P: sorted-slot order, rows numbered by id; else the caller's points), candidate
-//                             positions straight from global memory (16 B each), every sum lane-owned.  Writes the 32-byte row, the
-//                             by-row flag word for the scan of ids[], and for particles the by-slot float4 (normal, shell ? 1 : 0) and the
-//                             by-slot flag word; adds (isolated rows, largest count) to stats with one integer atomic per wave and word.
-//   k_shell_compact           (sph_query.h) out[offsets[i]] = i where flag[i]: the scan's second half, used twice (ids[] by row, shell
-//                             slots by slot).
-//   k_shell_crest             pass 2 over the compacted shell slots in ascending slot order (full waves whose lanes still share rows): a
-//                             candidate that is not in the shell costs the one 16-byte load of its by-slot float4.
-//   k_shell_slot_gather /     the same two passes by slot for a substep that reads them itself (the diffuse pool's crest births): 20 bytes
+// Two bodies, four kernels:
+//   shell_row<SKIP>           pass 1 of one target: the zero row, or neighbor_gather (candidate positions straight from global memory,
+//                             16 B each) into lane-owned sums and shell_finish.
+//   shell_crest_sum           pass 2 of one shell slot; a candidate that is not in the shell costs the one 16-byte load of its by-slot
+//                             float4 (read before the position: the loop is its own).
+//   k_shell_gather<P>         pass 1 per lane (P: sorted-slot order, rows numbered by id, own slot skipped; else the caller's points) with
+//                             shell_row's text written out: through shell_row it measured 2.2 to 2.5 % slower, with two more scalar
+//                             instructions in front of an unchanged loop (profiles/r23_shell_walk_ab.json).  Writes the 32-byte row, the by-row flag word for the scan of ids[], and for particles the by-slot float4
+//                             (normal, shell ? 1 : 0) and the by-slot flag word; adds (isolated rows, largest count) to stats with one
+//                             integer atomic per wave and word.
+//   k_shell_crest             shell_crest_sum over the compacted shell slots in ascending slot order (full waves whose lanes still share
+//                             rows); writes the crest of the row by id.
+//   k_shell_slot_gather /     the same bodies by slot for a substep that reads them itself (the diffuse pool's crest births): 20 bytes
 //   k_shell_slot_crest        per target instead of 56, one float per slot, no rows by id, no atomics, both sized by n and gated by a
 //                             counter in device memory (shell_gate)
+//   k_shell_compact           (sph_query.h) out[offsets[i]] = i where flag[i]: the scan's second half, used twice (ids[] by row, shell
+//                             slots by slot).
 // ids[] is k_neighbors_ids' (a permutation of [0, n)); the range guards (row < rows, j < end <= n, offsets < rows) stay so that no load
 // or store can leave its array.
 #pragma once
@@ -55,12 +61,6 @@ struct ShellK {
     uint32_t minCount;
 };
 
-// d = x_j - x and r2 = dot3(d, d): the bits of neighbor_accept's r2 (its d is the exact negative, the squares are the same floats).
-__host__ __device__ inline bool shell_accept(float xi, float yi, float zi, float xj, float yj, float zj, float R2, float& dx, float& dy, float& dz, float& r2) {
-    dx = xj - xi; dy = yj - yi; dz = zj - zi;
-    r2 = dot3(dx, dy, dz, dx, dy, dz);
-    return r2 < R2;
-}
 // One accepted candidate of pass 1.
 __host__ __device__ inline void shell_add(ShellAcc& a, float dx, float dy, float dz, float r2, float R2) {
     const float t = R2 - r2;
@@ -117,6 +117,39 @@ __device__ __forceinline__ void shell_reduce(bool isolated, uint32_t cnt, unsign
     }
 }
 
+// Pass 1 of a target at P (sorted slot `self`, left out where SKIP): the zero row where it does not walk.
+template <bool SKIP>
+__device__ __forceinline__ ShellRow shell_row(const SimK& k, const NbK& nb, const ShellK& sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                              const float4* __restrict__ own, bool fluidOnly, const float4& P, uint32_t self, bool walk) {
+    ShellRow r;
+    shell_zero(r);
+    if (walk) {
+        ShellAcc a;
+        shell_reset(a);
+        neighbor_gather<SKIP>(k, nb, pv, cellStart, own, fluidOnly, P, self, [&](float dx, float dy, float dz, float r2) { shell_add(a, dx, dy, dz, r2, nb.R2); });
+        shell_finish(a, sk, r);
+    }
+    return r;
+}
+
+// Pass 2 of the shell slot q at P with normal N: the crest sum over its shell candidates (nrmSlot[j].w != 0), in fixed point.
+__device__ __forceinline__ long long shell_crest_sum(const SimK& k, const NbK& nb, const ShellK& sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                     const float4* __restrict__ nrmSlot, uint32_t q, const float4& P, const float4& N) {
+    long long crest = 0ll;
+    const int3 cell = cell_of(k, P.x, P.y, P.z);
+    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
+        for (uint32_t j = qs; j < qe; ++j) {
+            const float4 M = nrmSlot[j];
+            if (M.w == 0.0f || j == q) continue;                              // not in the shell: nothing else is read
+            const float4 J = pv[2u * j];
+            float dx, dy, dz, r2;
+            if (!neighbor_offset(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
+            crest += shell_crest_term(N.x, N.y, N.z, M.x, M.y, M.z, dx, dy, dz, r2, sk.R);
+        }
+    });
+    return crest;
+}
+
 template <bool PARTICLES>
 __global__ __launch_bounds__(kBlock) void k_shell_gather(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
                                                          const int32_t* __restrict__ ids, const float4* __restrict__ own,
@@ -133,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_shell_gather(SimK k, NbK nb, ShellK 
     if (PARTICLES && walk && fluidOnly) walk = !slot_ghost(own, (uint32_t)i);
     ShellRow r;
     shell_zero(r);
-    if (walk) {
+    if (walk) {                                                               // (shell_row's text, see the file comment)
         ShellAcc a;
         shell_reset(a);
         const uint32_t q = (uint32_t)i;
@@ -143,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_shell_gather(SimK k, NbK nb, ShellK 
                 if (PARTICLES && j == q) continue;
                 const float4 J = pv[2u * j];
                 float dx, dy, dz, r2;
-                if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
+                if (!neighbor_offset(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
                 if (fluidOnly && slot_ghost(own, j)) continue;
                 shell_add(a, dx, dy, dz, r2, nb.R2);
             }
@@ -175,19 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_shell_crest(SimK k, NbK nb, ShellK s
     if (row >= rows) return;
     const float4 P = pv[2u * q];
     const float4 N = nrmSlot[q];
-    long long crest = 0ll;
-    const int3 cell = cell_of(k, P.x, P.y, P.z);
-    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
-        for (uint32_t j = qs; j < qe; ++j) {
-            const float4 M = nrmSlot[j];
-            if (M.w == 0.0f || j == q) continue;                              // not in the shell: nothing else is read
-            const float4 J = pv[2u * j];
-            float dx, dy, dz, r2;
-            if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
-            crest += shell_crest_term(N.x, N.y, N.z, M.x, M.y, M.z, dx, dy, dz, r2, sk.R);
-        }
-    });
-    out[row].crest = shell_crest_value(crest);
+    out[row].crest = shell_crest_value(shell_crest_sum(k, nb, sk, pv, cellStart, nrmSlot, q, P, N));
 }
 
 // ---- the two passes by slot, for a substep that reads normals and crests itself (the crest births of the diffuse pool) ----
@@ -199,7 +220,7 @@ __device__ __forceinline__ bool shell_gate(const uint32_t* __restrict__ counter,
     return p != 0u && (((unsigned long long)counter[1] << 32) | counter[0]) % p == 0ull;
 }
 
-// Pass 1 by slot: k_shell_gather<true>'s walk; writes only the by-slot float4 (normal, 0 outside the shell | 1 member | 2 isolated
+// Pass 1 by slot (shell_row<true>): writes only the by-slot float4 (normal, 0 outside the shell | 1 member | 2 isolated
 // member) and the by-slot 0 / 1 flag word for the scan.
 __global__ __launch_bounds__(kBlock) void k_shell_slot_gather(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
                                                               const float4* __restrict__ own, const uint32_t* __restrict__ counter,
@@ -211,30 +232,13 @@ __global__ __launch_bounds__(kBlock) void k_shell_slot_gather(SimK k, NbK nb, Sh
     const float4 P = pv[2u * q];
     bool walk = sample_finite(P.x, P.y, P.z);                                 // (a non-finite particle has an all-zero row)
     if (walk && fluidOnly) walk = !slot_ghost(own, q);
-    ShellRow r;
-    shell_zero(r);
-    if (walk) {
-        ShellAcc a;
-        shell_reset(a);
-        const int3 cell = cell_of(k, P.x, P.y, P.z);
-        neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
-            for (uint32_t j = qs; j < qe; ++j) {
-                if (j == q) continue;
-                const float4 J = pv[2u * j];
-                float dx, dy, dz, r2;
-                if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
-                if (fluidOnly && slot_ghost(own, j)) continue;
-                shell_add(a, dx, dy, dz, r2, nb.R2);
-            }
-        });
-        shell_finish(a, sk, r);
-    }
+    const ShellRow r = shell_row<true>(k, nb, sk, pv, cellStart, own, fluidOnly, P, q, walk);
     const uint32_t in = r.flags & kShellMember;
     nrmSlot[q] = make_float4(r.normal[0], r.normal[1], r.normal[2], in ? ((r.flags & kShellIsolated) ? 2.0f : 1.0f) : 0.0f);
     flagSlot[q] = in;
 }
 
-// Pass 2 by slot: k_shell_crest's walk over the compacted shell slots.  The launch is sized by n; the number of targets is the word behind
+// Pass 2 by slot (shell_crest_sum) over the compacted shell slots.  The launch is sized by n; the number of targets is the word behind
 // the scan (numShell, device memory), clamped to n.  One float per slot: lane t clears the slot t where it is no shell member, and writes
 // the crest of the t-th shell slot where there is one -- the two sets of slots are disjoint.
 __global__ __launch_bounds__(kBlock) void k_shell_slot_crest(SimK k, NbK nb, ShellK sk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
@@ -250,19 +254,7 @@ __global__ __launch_bounds__(kBlock) void k_shell_slot_crest(SimK k, NbK nb, She
     if (q >= nb.n) return;
     const float4 P = pv[2u * q];
     const float4 N = nrmSlot[q];
-    long long crest = 0ll;
-    const int3 cell = cell_of(k, P.x, P.y, P.z);
-    neighbor_rows(k, cellStart, nb.s, nb.n, cell.x, cell.y, cell.z, [&](uint32_t qs, uint32_t qe) {
-        for (uint32_t j = qs; j < qe; ++j) {
-            const float4 M = nrmSlot[j];
-            if (M.w == 0.0f || j == q) continue;                              // not in the shell: nothing else is read
-            const float4 J = pv[2u * j];
-            float dx, dy, dz, r2;
-            if (!shell_accept(P.x, P.y, P.z, J.x, J.y, J.z, nb.R2, dx, dy, dz, r2)) continue;
-            crest += shell_crest_term(N.x, N.y, N.z, M.x, M.y, M.z, dx, dy, dz, r2, sk.R);
-        }
-    });
-    crestSlot[q] = shell_crest_value(crest);
+    crestSlot[q] = shell_crest_value(shell_crest_sum(k, nb, sk, pv, cellStart, nrmSlot, q, P, N));
 }
 
 }  // namespace sph

@@ -828,7 +828,7 @@ int  sph_diffuse_step_host(const SphDiffuseConfig* cfg, const SphParams* params,
  *   acting   a substep ACTS when the pool's 64-bit substep counter before the step is a multiple of `every`; on other substeps the term
  *            bears nobody (its kernels are launched and return at once: a captured graph has a fixed launch list).
  *   shell    on an acting substep the SphShell rows (normal, crest, flags) of sph_shell_build with (radius, offset, minCount, flags) on the
- *            substep's ENTRY state: the same shell_accept / shell_add / shell_finish / shell_crest_term / shell_crest_value over the sorted
+ *            substep's ENTRY state: the same neighbor_offset / shell_add / shell_finish / shell_crest_term / shell_crest_value over the sorted
  *            copy the substep has just built, whose slot order is HostGrid's (cell, id) order; hence the bytes of sph_shell_host.
  *   who      a particle QUALIFIES when isGhost == 0, the sorted copy's 1/rho > 0, its row has SPH_SHELL_MEMBER and not
  *            SPH_SHELL_ISOLATED, sp2 = dot3(v, v) is finite, sp = sqrtf(sp2) > 0 and dot3(v, normal) >= align * sp.
