@@ -29,6 +29,7 @@ from .engine import (  # noqa: F401
     component_centers,
     SPH_OPT_KNN_VARIANT, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, SphKnnInfo, knn_host,
     SPH_OPT_RAYS_VARIANT, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, SphRayHit, SphRaysInfo, RAY_HIT_DTYPE, rays_host, camera_rays, parallel_rays,
+    SPH_OPT_RAY_SPANS_VARIANT, SphRaySpan, SphRaySpansInfo, RAY_SPAN_DTYPE, ray_spans_host, ray_spans_walk_host, ray_thickness,
     SPH_OPT_SHELL_TIMED, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, SphShell, SphShellConfig, SphShellInfo, SHELL_DTYPE, shell_host,
     shell_config,
     SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID, SPH_ANISO_SPARSE, SPH_ANISO_CLAMPED, SphAniso, SphAnisoConfig, SphAnisoInfo, ANISO_DTYPE, aniso_config,

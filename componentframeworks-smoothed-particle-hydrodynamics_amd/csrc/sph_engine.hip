@@ -292,6 +292,12 @@ struct SphEngine {
     int optRaysVariant = 0;                 // SPH_OPT_RAYS_VARIANT: 0 = rays cast in the caller's order, 1 = in the order of their cell of entry (same bits)
     SphRaysInfo raysInfo{};
     bool raysValid = false;
+    // sph_rays_span*: the spans (two uint4 each) and the four words of their reduction; the staged rays and the ordering are the cast's scratch
+    DevBuf<uint4> d_spanRows;
+    DevBuf<unsigned long long> d_spanStats;
+    int optRaySpansVariant = 0;             // SPH_OPT_RAY_SPANS_VARIANT: 0 = the layer walk, 1 = the block walk (same bits)
+    SphRaySpansInfo spansInfo{};
+    bool spansValid = false;
     int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
     // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
     // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets); the two words of the reduction
@@ -560,6 +566,9 @@ void rays_free(SphEngine* e) {
     e->d_rayBin.release(); e->d_rayCount.release(); e->d_rayStart.release(); e->d_rayBlockSums.release(); e->d_rayOrder.release();
     e->raysInfo = SphRaysInfo{};
     e->raysValid = false;
+    e->d_spanRows.release(); e->d_spanStats.release();
+    e->spansInfo = SphRaySpansInfo{};
+    e->spansValid = false;
 }
 void surface_free(SphEngine* e) {
     e->d_surfVol.release(); e->d_surfCode.release(); e->d_surfVOff.release(); e->d_surfTile.release(); e->d_surfTileOff.release();
@@ -1517,7 +1526,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     neighbors_free(e);                                                // (and the neighbour lists)
     components_free(e);                                               // (and the components)
     knn_free(e);                                                      // (and the k nearest neighbours)
-    rays_free(e);                                                     // (and the ray hits)
+    rays_free(e);                                                     // (and the ray hits and spans)
     shell_free(e);                                                    // (and the free-surface rows)
     aniso_free(e);                                                    // (and the anisotropy rows)
     tracers_free(e);                                                  // (and the tracer set)
@@ -1564,6 +1573,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_COMPONENTS_VARIANT: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optCcVariant = value; break;
     case SPH_OPT_KNN_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optKnnVariant = value; break;
     case SPH_OPT_RAYS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaysVariant = value; break;
+    case SPH_OPT_RAY_SPANS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaySpansVariant = value; break;
     case SPH_OPT_SHELL_TIMED: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optShellTimed = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
@@ -1592,6 +1602,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_COMPONENTS_VARIANT: *value = e->optCcVariant; break;
     case SPH_OPT_KNN_VARIANT: *value = e->optKnnVariant; break;
     case SPH_OPT_RAYS_VARIANT: *value = e->optRaysVariant; break;
+    case SPH_OPT_RAY_SPANS_VARIANT: *value = e->optRaySpansVariant; break;
     case SPH_OPT_SHELL_TIMED: *value = e->optShellTimed; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
@@ -3818,10 +3829,33 @@ static int rays_check(float radius, float cellSize, int flags, size_t m) {
     if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu rays (at most 2^31 - 1)", m);
     return SPH_OK;
 }
+static int spans_check(float radius, float cellSize, int flags, size_t m) {
+    if (flags & SPH_RAYS_ANY_HIT) return fail(SPH_ERR_ARG, "SPH_RAYS_ANY_HIT has no meaning for spans");
+    return rays_check(radius, cellSize, flags, m);
+}
 static sph::RayK rays_consts(float radius, int flags, uint32_t idBase, size_t n) {
     sph::RayK rk;
     rk.r2 = radius * radius; rk.invr = 1.0f / radius; rk.flags = flags; rk.idBase = idBase; rk.n = (uint32_t)n;
     return rk;
+}
+
+// SPH_OPT_RAYS_VARIANT 1, for casts and spans: the scratch of the counting sort of m rays by their cell of entry, and its launches
+// (d_rayOrder then holds the order).
+static int rays_order_grow(SphEngine* e, size_t m, const SphGridInfo& g) {
+    const size_t bins = (size_t)g.numCells + 1;
+    int rc;
+    if ((rc = e->d_rayBin.grow(e, m)) || (rc = e->d_rayOrder.grow(e, m)) || (rc = e->d_rayCount.grow(e, bins)) || (rc = e->d_rayStart.grow(e, bins + 1)) ||
+        (rc = e->d_rayBlockSums.grow(e, (size_t)blocks_for(bins, kScanTile) + 1))) return rc;
+    return SPH_OK;
+}
+static int rays_order_launch(SphEngine* e, const SimK& k, const float4* rays, size_t m) {
+    using namespace sph;
+    HIP_TRY(hipMemsetAsync(e->d_rayCount.p, 0, ((size_t)k.numCells + 1) * sizeof(uint32_t), e->stream));
+    Timed t(e, SPH_K_OTHER);
+    hipLaunchKernelGGL(k_rays_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rays, m, e->d_rayBin.p, e->d_rayCount.p);
+    launch_cell_scan(e, e->d_rayCount.p, e->d_rayBlockSums.p, e->d_rayStart.p, k.numCells + 1, (uint32_t)m);
+    hipLaunchKernelGGL(k_rays_order, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_rayBin.p, (const uint32_t*)e->d_rayStart.p, m, e->d_rayOrder.p);
+    return SPH_OK;
 }
 
 int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float radius, int flags, SphRaysInfo* out) {
@@ -3835,22 +3869,14 @@ int sph_rays_cast_device(SphEngine* e, const float* devRays8, size_t m, float ra
     e->raysValid = false;                                                           // (the hits held so far end here)
     if ((rc = e->d_rayHits.grow(e, 2 * m)) || (rc = e->d_rayStats.grow(e, 2))) return rc;
     const bool ordered = e->optRaysVariant == 1 && m && e->n;
-    const size_t bins = (size_t)g.numCells + 1;
-    if (ordered && ((rc = e->d_rayBin.grow(e, m)) || (rc = e->d_rayOrder.grow(e, m)) || (rc = e->d_rayCount.grow(e, bins)) || (rc = e->d_rayStart.grow(e, bins + 1)) ||
-                    (rc = e->d_rayBlockSums.grow(e, (size_t)blocks_for(bins, kScanTile) + 1)))) return rc;
+    if (ordered && (rc = rays_order_grow(e, m, g))) return rc;
     if ((rc = sample_grid(e, k))) return rc;
     const RayK rk = rays_consts(radius, flags, e->idBase, e->n);
     const float4* rays = reinterpret_cast<const float4*>(devRays8);
     unsigned long long host[2] = {0ull, 0ull};
     if (m) {
         HIP_TRY(hipMemsetAsync(e->d_rayStats.p, 0, 2 * sizeof(unsigned long long), e->stream));
-        if (ordered) {
-            HIP_TRY(hipMemsetAsync(e->d_rayCount.p, 0, ((size_t)k.numCells + 1) * sizeof(uint32_t), e->stream));
-            Timed t(e, SPH_K_OTHER);
-            hipLaunchKernelGGL(k_rays_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rays, m, e->d_rayBin.p, e->d_rayCount.p);
-            launch_cell_scan(e, e->d_rayCount.p, e->d_rayBlockSums.p, e->d_rayStart.p, k.numCells + 1, (uint32_t)m);
-            hipLaunchKernelGGL(k_rays_order, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_rayBin.p, (const uint32_t*)e->d_rayStart.p, m, e->d_rayOrder.p);
-        }
+        if (ordered && (rc = rays_order_launch(e, k, rays, m))) return rc;
         {
             Timed t(e, SPH_K_OTHER);
             hipLaunchKernelGGL(k_rays, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rk, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
@@ -3903,6 +3929,25 @@ int sph_rays_download(SphEngine* e, SphRayHit* hits) {
     return SPH_OK;
 }
 
+// What the host twins of casts and spans begin with: the checks (check: rays_check or spans_check), the grid's constants and who takes part.
+static int rays_host_setup(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                           int (*check)(float, float, int, size_t), SimK& k, sph::RayK& rk, std::vector<uint8_t>& takesPart) {
+    if (!params || (n && !particles) || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = check(radius, g.cellSize, flags, m))) return rc;
+    rk = rays_consts(radius, flags, 0u, n);
+    const bool fluidOnly = (flags & SPH_RAYS_FLUID_ONLY) != 0;
+    takesPart.resize(n);
+    for (size_t j = 0; j < n; ++j)
+        takesPart[j] = !(fluidOnly && particles[j].isGhost != 0) && sph::ray_in_grid(k, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2]);
+    return SPH_OK;
+}
+
 // The definition: every ray against every participating record, no grid.  walk: sph_rays_walk_host, the device's ray_walk over the grid
 // as the counting sort leaves it.
 static int rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
@@ -3917,20 +3962,12 @@ int sph_rays_walk_host(const SphParticle* particles, size_t n, const SphParams* 
 }
 static int rays_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
                      SphRayHit* hits, SphRaysInfo* out, bool walk) {
-    if (!params || !out || (n && !particles) || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
-    int rc;
-    if ((rc = validate_params(*params))) return rc;
-    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
-    SphGridInfo g;
-    sph::compute_grid_extents(*params, g);
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
     SimK k;
-    sph::make_simk(*params, g, params->param_timeStep, k);
-    if ((rc = rays_check(radius, g.cellSize, flags, m))) return rc;
-    const sph::RayK rk = rays_consts(radius, flags, 0u, n);
-    const bool fluidOnly = (flags & SPH_RAYS_FLUID_ONLY) != 0;
-    std::vector<uint8_t> takesPart(n);
-    for (size_t j = 0; j < n; ++j)
-        takesPart[j] = !(fluidOnly && particles[j].isGhost != 0) && sph::ray_in_grid(k, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2]);
+    sph::RayK rk;
+    std::vector<uint8_t> takesPart;
+    int rc;
+    if ((rc = rays_host_setup(particles, n, params, rays8, m, radius, flags, rays_check, k, rk, takesPart))) return rc;
     // for the walk: the grid of the records, and their positions in slot order
     const sph::HostGrid grid(k, particles, walk ? n : 0);
     const std::vector<uint32_t>& order = grid.order;
@@ -3965,6 +4002,141 @@ static int rays_host(const SphParticle* particles, size_t n, const SphParams* pa
     }
     *out = info;
     return SPH_OK;
+}
+
+// ---- ray spans (sph_rays.h "spans"): state of their own beside the hits; the staged rays and the ordering scratch are shared -----
+static_assert(sizeof(SphRaySpan) == 32 && sizeof(SphRaySpansInfo) == 48, "SphRaySpan must be 32 bytes, SphRaySpansInfo 48");
+
+int sph_rays_span_device(SphEngine* e, const float* devRays8, size_t m, float radius, int flags, SphRaySpansInfo* out) {
+    using namespace sph;
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || (m && !devRays8)) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    SphGridInfo g;
+    int rc;
+    if ((rc = query_grid(e, g)) || (rc = spans_check(radius, g.cellSize, flags, m))) return rc;
+    e->spansValid = false;                                                          // (the spans held so far end here)
+    if ((rc = e->d_spanRows.grow(e, 2 * m)) || (rc = e->d_spanStats.grow(e, 4))) return rc;
+    const bool ordered = e->optRaysVariant == 1 && m && e->n;
+    if (ordered && (rc = rays_order_grow(e, m, g))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const RayK rk = rays_consts(radius, flags, e->idBase, e->n);
+    const float4* rays = reinterpret_cast<const float4*>(devRays8);
+    unsigned long long host[4] = {0ull, 0ull, 0ull, 0ull};
+    if (m) {
+        HIP_TRY(hipMemsetAsync(e->d_spanStats.p, 0, sizeof(host), e->stream));
+        if (ordered && (rc = rays_order_launch(e, k, rays, m))) return rc;
+        {
+            Timed t(e, SPH_K_OTHER);
+            auto kern = e->optRaySpansVariant == 1 ? k_ray_spans<true> : k_ray_spans<false>;
+            hipLaunchKernelGGL(kern, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, rk, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                               (const float4*)e->d_sOwn, rays, ordered ? (const uint32_t*)e->d_rayOrder.p : (const uint32_t*)nullptr, m, e->d_spanRows.p, e->d_spanStats.p);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, e->d_spanStats.p, sizeof(host), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SphRaySpansInfo info{};
+    info.rays = m; info.crossed = host[0]; info.voidRays = host[1]; info.total = host[2]; info.maxCount = (uint32_t)host[3]; info.radius = radius; info.flags = flags;
+    e->spansInfo = info;
+    e->spansValid = true;
+    *out = info;
+    return SPH_OK;
+}
+
+int sph_rays_span(SphEngine* e, const float* rays8, size_t m, float radius, int flags, SphRaySpansInfo* out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!out || (m && !rays8)) return fail(SPH_ERR_ARG, "null argument");
+    SphGridInfo g;
+    int rc;
+    if ((rc = query_grid(e, g)) || (rc = spans_check(radius, g.cellSize, flags, m))) return rc;  // (nothing is staged for a call that will be refused)
+    if (m && (rc = e->d_rayIn.grow(e, 2 * m))) return rc;
+    if (m) HIP_TRY(hipMemcpyAsync(e->d_rayIn.p, rays8, m * 2 * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    return sph_rays_span_device(e, reinterpret_cast<const float*>(e->d_rayIn.p), m, radius, flags, out);
+}
+
+int sph_rays_span_info(const SphEngine* e, SphRaySpansInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->spansValid) return fail(SPH_ERR_STATE, "the engine holds no ray spans");
+    *out = e->spansInfo;
+    return SPH_OK;
+}
+
+int sph_rays_span_rows(SphEngine* e, const SphRaySpan** rows) {
+    if (!e || !rows) return fail(SPH_ERR_ARG, "null argument");
+    if (!e->spansValid) return fail(SPH_ERR_STATE, "the engine holds no ray spans");
+    *rows = reinterpret_cast<const SphRaySpan*>(e->d_spanRows.p);
+    return SPH_OK;
+}
+
+int sph_rays_span_download(SphEngine* e, SphRaySpan* rows) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!e->spansValid) return fail(SPH_ERR_STATE, "the engine holds no ray spans");
+    const size_t m = (size_t)e->spansInfo.rays;
+    if (m && !rows) return fail(SPH_ERR_ARG, "null argument");
+    if (m) HIP_TRY(hipMemcpyAsync(rows, e->d_spanRows.p, m * sizeof(SphRaySpan), hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// The definition (walk < 0): every ray against every participating record, no grid.  walk 0 / 1: ray_span_walk, layer / block, over
+// the grid as the counting sort leaves it.
+static int spans_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                      SphRaySpan* rowsOut, SphRaySpansInfo* out, int walk) {
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    SimK k;
+    sph::RayK rk;
+    std::vector<uint8_t> takesPart;
+    int rc;
+    if ((rc = rays_host_setup(particles, n, params, rays8, m, radius, flags, spans_check, k, rk, takesPart))) return rc;
+    const sph::HostGrid grid(k, particles, walk >= 0 ? n : 0);
+    const std::vector<uint32_t>& order = grid.order;
+    std::vector<float4> spos(order.size());
+    for (size_t j = 0; j < order.size(); ++j) spos[j] = make_float4(particles[order[j]].pos[0], particles[order[j]].pos[1], particles[order[j]].pos[2], 0.0f);
+    auto rows = [&](int x0, int x1, int y0, int y1, int z0, int z1, auto&& f) { sph::cell_box_rows(k, grid.start.data(), (uint32_t)order.size(), x0, x1, y0, y1, z0, z1, f); };
+    auto pos = [&](uint32_t j) { return spos[j]; };
+    auto id = [&](uint32_t j) { return order[j]; };
+    auto ghost = [&](uint32_t j) { return particles[order[j]].isGhost != 0; };
+    SphRaySpansInfo info{};
+    info.rays = m; info.radius = radius; info.flags = flags;
+    for (size_t i = 0; i < m; ++i) {
+        sph::Ray R;
+        sph::RaySpanAcc acc;
+        const bool live = sph::ray_setup(rays8 + 8 * i, R);
+        if (!live) {
+            info.voidRays += 1;
+        } else if (walk == 0) {
+            sph::ray_span_walk<false>(k, rk, R, rows, pos, id, ghost, acc);
+        } else if (walk == 1) {
+            sph::ray_span_walk<true>(k, rk, R, rows, pos, id, ghost, acc);
+        } else {
+            for (size_t j = 0; j < n; ++j) {
+                float tin, tout;
+                uint32_t q;
+                if (!takesPart[j] || !sph::ray_span(R, rk.r2, particles[j].pos[0], particles[j].pos[1], particles[j].pos[2], tin, tout, q)) continue;
+                sph::ray_span_add(acc, tin, tout, q, (uint32_t)j);
+            }
+        }
+        if (acc.count) info.crossed += 1;
+        info.total += acc.count;
+        info.maxCount = std::max(info.maxCount, acc.count);
+        if (rowsOut) {
+            uint32_t o8[8];
+            sph::ray_span_write(acc, !live, o8);
+            memcpy(&rowsOut[i], o8, sizeof(o8));
+        }
+    }
+    *out = info;
+    return SPH_OK;
+}
+int sph_rays_span_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                       SphRaySpan* rows, SphRaySpansInfo* out) {
+    return spans_host(particles, n, params, rays8, m, radius, flags, rows, out, -1);
+}
+int sph_rays_span_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                            int variant, SphRaySpan* rows, SphRaySpansInfo* out) {
+    if (variant < 0 || variant > 1) return fail(SPH_ERR_ARG, "span walk variant %d (0 = layer walk, 1 = block walk)", variant);
+    return spans_host(particles, n, params, rays8, m, radius, flags, rows, out, variant);
 }
 
 // ---- iso-surface meshes (sph_surface.h) ----------------------------------------------------------

@@ -20,6 +20,8 @@
 //                             (to t0 .. t1), and a 3-D DDA walks the cells with indices in [-1, dims] along it; at each step the members
 //                             of the 3 x 3 x 3 block around the current cell (neighbor_rows with s = 1, which clamps the block to the
 //                             cells that exist) are tested with ray_hit and the smallest key stays in registers.  No LDS, no scratch.
+//   ray_span / ray_span_walk / k_ray_spans    spans, at the end of this file: what a ray crosses in all (count, first entry, last exit,
+//                             summed chord share), from a walk that cannot stop early and meets every sphere exactly once
 //
 // Completeness.  A sphere the ray enters at t has its centre within r <= cellSize / 2 of the point P(t) of the ray.  If P(t) lies in
 // cell c, the centre lies in [c - 1/2, c + 3/2) cells on every axis, inside the block of c, and it is still inside the block of any cell
@@ -292,6 +294,175 @@ __global__ __launch_bounds__(kBlock) void k_rays(SimK k, RayK rk, const float4* 
         hits[2 * i + 1] = make_float4(o8[4], o8[5], o8[6], o8[7]);
     }
     rays_reduce(act && best != kRayNoKey, act && !live, stats);
+}
+
+// ---- spans: what a ray crosses in all (DESIGN.md section 3n "Spans") ------------------------------------------------------------
+// Per ray the number of spheres whose chord inside [tmin, tmax] has positive length, the smallest tin and the largest tout with the ids
+// that hold them, and the summed chord length in units of 2^-24 of a diameter.  Every field is a min, a max or an integer sum of
+// per-sphere values (ray_span) that do not depend on how the sphere was found: sph_rays_span_host (brute force, no grid) is the
+// definition and a walk gives its bytes as long as it hands every participating sphere to ray_span exactly once.
+//
+// Completeness is the cast's: the part of a chord inside the window has positive length and lies in the widened box (centres are
+// inside the grid, r is at most half a cell), hence in [t0, t1]; each of its points is within r of the centre, so the centre is in the
+// block of the cell that holds the point.  The walk has no termination test: it ends with the segment or outside [-1, dims].
+// Once only.  The DDA's path is monotone per axis, and cell X lies in block(c) iff |X - c| <= 1 on every axis: a box of cells, which a
+// monotone path meets in ONE contiguous run.  X is therefore new exactly at the step that enters the run.
+//   layer walk   the first cell tests its whole block; after a step of s = +-1 along axis a only the cells with coordinate c_a + s of
+//                the new block are tested: that layer is block(c_new) \ block(c_prev), so nothing is tested twice, and the step that
+//                enters X's run has X_a = c_a + s, so nothing is left out.  A third of the candidates.
+//   block walk   every step tests the whole block (as k_rays), and a crossed candidate is dropped when its own cell (the floor of
+//                ray_axis_in, which participation computes anyway; for a participant it is the cell the grid holds it in) lies within
+//                Chebyshev distance 1 of the PREVIOUS cell of the path: "in the previous block" is "seen before" by the run argument.
+//                Integers only.
+
+struct RaySpanAcc {
+    unsigned long long enter = kRayNoKey;    // smallest (ordered(tin) << 32) | id
+    unsigned long long exit = 0ull;          // largest (ordered(tout) << 32) | ~id: ties go to the smaller id; below every real key
+    unsigned long long length = 0ull;
+    uint32_t count = 0u;
+};
+
+// Is the sphere crossed?  tca, thc as ray_hit forms them; the chord clipped to the window; q its share of the diameter in 2^-24.
+__host__ __device__ inline bool ray_span(const Ray& R, float r2, float x, float y, float z, float& tin, float& tout, uint32_t& q) {
+    const float Lx = x - R.ox, Ly = y - R.oy, Lz = z - R.oz;
+    const float tca = dot3(Lx, Ly, Lz, R.dx, R.dy, R.dz) * R.inva;
+    const float qx = fmaf(-tca, R.dx, Lx), qy = fmaf(-tca, R.dy, Ly), qz = fmaf(-tca, R.dz, Lz);
+    const float d2 = dot3(qx, qy, qz, qx, qy, qz);
+    const float s = r2 - d2;
+    if (!(s >= 0.0f)) return false;
+    const float thc = sqrtf(s * R.inva);
+    tin = fmaxf(tca - thc, R.tmin);
+    tout = fminf(tca + thc, R.tmax);
+    if (!(tin < tout)) return false;
+    const float f = fminf((tout - tin) / (2.0f * thc), 1.0f);
+    q = (uint32_t)fmaf(f, 16777216.0f, 0.5f);
+    return true;
+}
+__host__ __device__ inline void ray_span_add(RaySpanAcc& a, float tin, float tout, uint32_t q, uint32_t id) {
+    const unsigned long long ke = ray_key(tin, id), kx = ((unsigned long long)ray_ordered(tout) << 32) | (unsigned long long)(~id);
+    a.enter = ke < a.enter ? ke : a.enter;
+    a.exit = kx > a.exit ? kx : a.exit;
+    a.length += q;
+    a.count += 1u;
+}
+// ray_in_grid with the integer cell its floors give; the cell is meaningful where the result is true.
+__host__ __device__ inline bool ray_cell_in(const SimK& k, float x, float y, float z, int& X, int& Y, int& Z) {
+    const float fx = floorf((x - k.gminx) / k.cellSize), fy = floorf((y - k.gminy) / k.cellSize), fz = floorf((z - k.gminz) / k.cellSize);
+    if (!(fx >= 0.0f && fx < (float)k.gx && fy >= 0.0f && fy < (float)k.gy && fz >= 0.0f && fz < (float)k.gz)) return false;
+    X = (int)fx; Y = (int)fy; Z = (int)fz;
+    return true;
+}
+
+// The 8 words of a SphRaySpan: (tEnter, tExit, idEnter, idExit, count, flags, length lo, length hi).
+__host__ __device__ inline void ray_span_write(const RaySpanAcc& a, bool isVoid, uint32_t* out8) {
+    out8[0] = 0x7F800000u; out8[1] = 0xFF800000u; out8[2] = 0xFFFFFFFFu; out8[3] = 0xFFFFFFFFu;
+    out8[4] = a.count; out8[5] = isVoid ? 1u : 0u;
+    out8[6] = (uint32_t)(a.length & 0xffffffffull); out8[7] = (uint32_t)(a.length >> 32);
+    if (!a.count) return;
+    out8[0] = ray_bits(ray_unordered((uint32_t)(a.enter >> 32)));
+    out8[1] = ray_bits(ray_unordered((uint32_t)(a.exit >> 32)));
+    out8[2] = (uint32_t)(a.enter & 0xffffffffull);
+    out8[3] = ~(uint32_t)(a.exit & 0xffffffffull);
+}
+
+// neighbor_rows for an arbitrary box of cells [x0, x1] x [y0, y1] x [z0, z1], clamped to the cells that exist: f(first slot, end slot)
+// per row, ascending.
+template <class F>
+__host__ __device__ __forceinline__ void cell_box_rows(const SimK& k, const uint32_t* __restrict__ cellStart, uint32_t n, int x0, int x1, int y0, int y1, int z0, int z1,
+                                                       F&& f) {
+    x0 = max(x0, 0); x1 = min(x1, k.gx - 1);
+    y0 = max(y0, 0); y1 = min(y1, k.gy - 1);
+    z0 = max(z0, 0); z1 = min(z1, k.gz - 1);
+    if (x0 > x1) return;
+    for (int nz = z0; nz <= z1; ++nz)
+        for (int ny = y0; ny <= y1; ++ny) {
+            const int rowBase = (nz * k.gy + ny) * k.gx;
+            f(cellStart[rowBase + x0], min(cellStart[rowBase + x1 + 1], n));
+        }
+}
+
+// The span walk of one ray that ray_setup passed.  BLOCK: the block walk, else the layer walk.  The grid through callables as in
+// ray_walk, with rows(x0, x1, y0, y1, z0, z1, f) the rows of a box of cells (cell_box_rows).
+template <bool BLOCK, class Rows, class Pos, class Id, class Ghost>
+__host__ __device__ inline void ray_span_walk(const SimK& k, const RayK& rk, const Ray& R, Rows&& rows, Pos&& pos, Id&& id, Ghost&& ghost, RaySpanAcc& acc) {
+    const bool fluidOnly = (rk.flags & kRaysFluidOnly) != 0;
+    if (!rk.n) return;
+    const float cs = k.cellSize;
+    float t0, t1, gX, gY, gZ;
+    if (!ray_enter(k, R, t0, t1, gX, gY, gZ)) return;
+    int cx = ray_cell(gX, k.gx), cy = ray_cell(gY, k.gy), cz = ray_cell(gZ, k.gz);
+    const float cdx = cs / R.dx, cdy = cs / R.dy, cdz = cs / R.dz;
+    const int sx = R.dx > 0.0f ? 1 : -1, sy = R.dy > 0.0f ? 1 : -1, sz = R.dz > 0.0f ? 1 : -1;
+    const float uEnd = t1 - t0;
+    int px = -4, py = -4, pz = -4;                                                          // the previous cell of the path: none yet (no cell of the grid is near -4)
+    int x0 = cx - 1, x1 = cx + 1, y0 = cy - 1, y1 = cy + 1, z0 = cz - 1, z1 = cz + 1;       // the box of cells to test at this step
+    const int maxSteps = k.gx + k.gy + k.gz + 6;
+    for (int step = 0; step <= maxSteps; ++step) {
+        rows(x0, x1, y0, y1, z0, z1, [&](uint32_t qs, uint32_t qe) {
+            for (uint32_t j = qs; j < qe; ++j) {
+                const float4 J = pos(j);
+                float tin, tout;
+                uint32_t q;
+                if (!ray_span(R, rk.r2, J.x, J.y, J.z, tin, tout, q)) continue;
+                if (fluidOnly && ghost(j)) continue;
+                int X, Y, Z;
+                if (!ray_cell_in(k, J.x, J.y, J.z, X, Y, Z)) continue;
+                if (BLOCK && abs(X - px) <= 1 && abs(Y - py) <= 1 && abs(Z - pz) <= 1) continue;
+                ray_span_add(acc, tin, tout, q, id(j));
+            }
+        });
+        const float ux = ray_cross(cx, gX, R.dx, cdx), uy = ray_cross(cy, gY, R.dy, cdy), uz = ray_cross(cz, gZ, R.dz, cdz);
+        const float un = fminf(fminf(ux, uy), uz);
+        if (!(un <= uEnd)) break;                                                           // the segment ends inside this cell (or never leaves it)
+        px = cx; py = cy; pz = cz;
+        if (ux <= uy && ux <= uz) { cx += sx; if (cx < -1 || cx > k.gx) break; }
+        else if (uy <= uz) { cy += sy; if (cy < -1 || cy > k.gy) break; }
+        else { cz += sz; if (cz < -1 || cz > k.gz) break; }
+        x0 = cx - 1; x1 = cx + 1; y0 = cy - 1; y1 = cy + 1; z0 = cz - 1; z1 = cz + 1;
+        if (!BLOCK) {                                                                       // the new layer only
+            if (cx != px) x0 = x1 = cx + sx;
+            else if (cy != py) y0 = y1 = cy + sy;
+            else z0 = z1 = cz + sz;
+        }
+    }
+}
+
+// One ray per lane, order as in k_rays.  The two keys, the length and the count stay in registers; spans[2 i], spans[2 i + 1]: the
+// 32 bytes of ray i.  stats: crossed rays, void rays, the sum of the counts (added), the largest count (max), reduced per wave first.
+template <bool BLOCK>
+__global__ __launch_bounds__(kBlock) void k_ray_spans(SimK k, RayK rk, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                      const float4* __restrict__ own, const float4* __restrict__ rays, const uint32_t* __restrict__ order, size_t m,
+                                                      uint4* __restrict__ spans, unsigned long long* __restrict__ stats) {
+    const size_t lane = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const size_t i = (order && lane < m) ? (size_t)order[lane] : lane;
+    const bool act = lane < m && i < m;
+    Ray R;
+    bool live = false;
+    if (act) {
+        const float4 A = rays[2 * i], B = rays[2 * i + 1];
+        const float a8[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
+        live = ray_setup(a8, R);
+    }
+    RaySpanAcc acc;
+    if (live)
+        ray_span_walk<BLOCK>(
+            k, rk, R, [&](int x0, int x1, int y0, int y1, int z0, int z1, auto&& f) { cell_box_rows(k, cellStart, rk.n, x0, x1, y0, y1, z0, z1, f); },
+            [&](uint32_t j) { return pv[2u * j]; }, [&](uint32_t j) { const uint32_t id = fbits(own[j].w) - rk.idBase; return id < rk.n ? id : 0u; },
+            [&](uint32_t j) { return slot_ghost(own, j); }, acc);
+    if (act) {
+        uint32_t o8[8];
+        ray_span_write(acc, !live, o8);
+        spans[2 * i] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
+        spans[2 * i + 1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
+    }
+    const uint32_t cnt = act ? acc.count : 0u;
+    const unsigned long long nc = (unsigned long long)__popcll(__ballot(cnt != 0u)), nv = (unsigned long long)__popcll(__ballot(act && !live));
+    const unsigned long long total = wave_sum((unsigned long long)cnt), mx = (unsigned long long)wave_max(cnt);
+    if ((threadIdx.x & 63) == 0) {
+        if (nc) atomicAdd(stats + 0, nc);
+        if (nv) atomicAdd(stats + 1, nv);
+        if (total) { atomicAdd(stats + 2, total); atomicMax(stats + 3, mx); }
+    }
 }
 
 }  // namespace sph

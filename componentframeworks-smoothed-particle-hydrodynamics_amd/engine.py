@@ -86,6 +86,7 @@ SPH_OPT_NEIGHBORS_FILL = 10
 SPH_OPT_COMPONENTS_VARIANT = 11
 SPH_OPT_KNN_VARIANT = 12
 SPH_OPT_RAYS_VARIANT = 13
+SPH_OPT_RAY_SPANS_VARIANT = 15
 SPH_OPT_SHELL_TIMED = 14
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
@@ -319,6 +320,24 @@ assert RAY_HIT_DTYPE.itemsize == 32
 SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT = 1, 2
 
 
+class SphRaySpan(C.Structure):
+    """struct SphRaySpan of include/sph_abi.h: what one ray crosses in all (see SPHFluidGPU.ray_spans); nothing crossed is
+    (+inf, -inf, -1, -1, 0)."""
+    _fields_ = [("tEnter", C.c_float), ("tExit", C.c_float), ("idEnter", C.c_int32), ("idExit", C.c_int32), ("count", C.c_uint32),
+                ("flags", C.c_uint32), ("length", C.c_uint64)]
+
+
+class SphRaySpansInfo(C.Structure):
+    """struct SphRaySpansInfo of include/sph_abi.h: what the engine's ray spans hold."""
+    _fields_ = [("rays", C.c_uint64), ("crossed", C.c_uint64), ("voidRays", C.c_uint64), ("total", C.c_uint64), ("maxCount", C.c_uint32),
+                ("radius", C.c_float), ("flags", C.c_int32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(SphRaySpan) == 32 and C.sizeof(SphRaySpansInfo) == 48
+RAY_SPAN_DTYPE = np.dtype(SphRaySpan)
+assert RAY_SPAN_DTYPE.itemsize == 32
+
+
 class SphShell(C.Structure):
     """struct SphShell of include/sph_abi.h: the free-surface record of one particle or query point (see SPHFluidGPU.shell)."""
     _fields_ = [("normal", C.c_float * 3), ("offsetRatio", C.c_float), ("crest", C.c_float), ("count", C.c_uint32), ("flags", C.c_uint32),
@@ -544,6 +563,13 @@ _ABI = {
     "sph_rays_download": (_int, [_vp, _vp]),
     "sph_rays_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
     "sph_rays_walk_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaysInfo)]),
+    "sph_rays_span": (_int, [_vp, _vp, _sz, _f, _int, _P(SphRaySpansInfo)]),
+    "sph_rays_span_device": (_int, [_vp, _vp, _sz, _f, _int, _P(SphRaySpansInfo)]),
+    "sph_rays_span_info": (_int, [_vp, _P(SphRaySpansInfo)]),
+    "sph_rays_span_rows": (_int, [_vp, _P(_vp)]),
+    "sph_rays_span_download": (_int, [_vp, _vp]),
+    "sph_rays_span_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _vp, _P(SphRaySpansInfo)]),
+    "sph_rays_span_walk_host": (_int, [_vp, _sz, _pp, _vp, _sz, _f, _int, _int, _vp, _P(SphRaySpansInfo)]),
     # free-surface particles
     "sph_shell_default": (None, [_P(SphShellConfig)]),
     "sph_shell_build": (_int, [_vp, _P(SphShellConfig), _P(SphShellInfo)]),
@@ -1448,6 +1474,39 @@ class SPHFluidGPU:
             return z[:, 0], z[:, 1].view(torch.int32), z[:, 2:5], z[:, 5:8]
         return _split_hits(z)
 
+    # -- ray spans (include/sph_abi.h "ray spans") ------------------------------------------------
+    def ray_spans(self, rays, radius=None, fluid_only: bool = False, device: bool = False):
+        """What every ray crosses in all, each particle a solid sphere of `radius` (None: 0.25 * param_h; at most half a cell): a
+        RAY_SPAN_DTYPE array (tEnter, tExit, idEnter, idExit, count, flags, length), one row per ray; ray_thickness() turns length into
+        world units.  rays as for raycast(): (m, 8) float32, numpy or a torch device tensor (used in place).  A sphere that contains the
+        ray's start counts; nothing crossed is (+inf, -inf, -1, -1, 0); flags bit 0 marks a void ray.  With device=True a fresh (m, 8)
+        int32 torch device tensor of the same 32-byte rows.  The held hits of raycast() are not touched."""
+        import torch
+        self._push_params()
+        info = SphRaySpansInfo()
+        r = self._radius(radius, 0.25)
+        flags = _rays_flags(fluid_only, False)
+        if isinstance(rays, torch.Tensor):
+            if not (_is_cuda_f32(rays) and rays.dim() == 2 and rays.shape[1] == 8):
+                raise SphError(f"ray_spans: a torch tensor of rays must be a contiguous float32 device tensor of shape (m, 8), not {tuple(rays.shape)}")
+            m = int(rays.shape[0])
+            _check(self._L.sph_rays_span_device(self._h, C.c_void_p(rays.data_ptr()) if m else None, m, float(r), flags, C.byref(info)))
+        else:
+            r8 = _rays8(rays, "ray_spans")
+            _check(self._L.sph_rays_span(self._h, _ptr(r8) if len(r8) else None, len(r8), float(r), flags, C.byref(info)))
+        return self.ray_span_rows(device)
+
+    def ray_spans_info(self) -> SphRaySpansInfo:
+        """What the engine's spans hold: rays, crossed, voidRays, total, maxCount, radius, flags.  SphError before any ray_spans() call."""
+        return self._info(SphRaySpansInfo, self._L.sph_rays_span_info)
+
+    def ray_span_rows(self, device: bool = False):
+        """The spans the engine holds: a RAY_SPAN_DTYPE array, or with device=True an (m, 8) int32 torch device tensor of the same bytes."""
+        m = int(self.ray_spans_info().rays)
+        spec = ((m, 8), None, "int32") if device else (m, RAY_SPAN_DTYPE, None)
+        (z,) = _fetch(lambda p_rows: self._L.sph_rays_span_download(self._h, p_rows), device, (spec,))
+        return z
+
     # -- free-surface particles (include/sph_abi.h "free-surface particles") ----------------------
     def shell(self, radius=None, offset: float = 0.10, min_count: int = 0, fluid_only: bool = False, device: bool = False):
         """The free-surface shell of the particles from their positions alone: (rows, ids).  rows is a SHELL_DTYPE array numbered by
@@ -2319,6 +2378,31 @@ def rays_host(records, params, rays, radius, fluid_only=False, any_hit=False, wi
     _check((L.sph_rays_walk_host if walk else L.sph_rays_host)(*head, float(radius), _rays_flags(fluid_only, any_hit), _ptr_or_none(hits), C.byref(info)))
     out = _split_hits(hits)
     return out + (info,) if with_info else out
+
+
+def _spans_host(who, fn, records, params, rays, radius, fluid_only, with_info, *variant):
+    rows, head = _host_args(records, params, _rays8(rays, who))
+    out = np.zeros(rows, RAY_SPAN_DTYPE)
+    info = SphRaySpansInfo()
+    _check(fn(*head, float(radius), _rays_flags(fluid_only, False), *variant, _ptr_or_none(out), C.byref(info)))
+    return (out, info) if with_info else out
+
+
+def ray_spans_host(records, params, rays, radius, fluid_only=False, with_info=False):
+    """sph_rays_span_host: the RAY_SPAN_DTYPE rows of SPHFluidGPU.ray_spans on host records, computed on the CPU by brute force over all
+    participating records: the definition of a span.  with_info adds the SphRaySpansInfo.  No device is needed."""
+    return _spans_host("ray_spans_host", load_library().sph_rays_span_host, records, params, rays, radius, fluid_only, with_info)
+
+
+def ray_spans_walk_host(records, params, rays, radius, fluid_only=False, with_info=False, variant=0):
+    """sph_rays_span_walk_host: the same rows by the device's span walk over a grid built on the host; variant 0 = the layer walk,
+    1 = the block walk (SPH_OPT_RAY_SPANS_VARIANT).  No device is needed."""
+    return _spans_host("ray_spans_walk_host", load_library().sph_rays_span_walk_host, records, params, rays, radius, fluid_only, with_info, int(variant))
+
+
+def ray_thickness(rows, radius) -> np.ndarray:
+    """The summed chord length of RAY_SPAN_DTYPE rows in world units, float64: length * 2 r * 2^-24.  Overlapping spheres add."""
+    return np.asarray(rows)["length"].astype(np.float64) * (2.0 * float(radius) * 2.0 ** -24)
 
 
 def camera_rays(eye, target, up, fov_y, width, height, tmin=0.0, tmax=np.inf) -> np.ndarray:

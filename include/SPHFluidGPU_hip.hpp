@@ -350,6 +350,33 @@ public:
         hits.assign(size_t(info.rays), SphRayHit{});
         return !Check(sph_rays_download(engine, hits.empty() ? nullptr : hits.data()), "sph_rays_download");
     }
+    // Ray spans (engine extension, sph_abi.h "ray spans"): for each of m rays what it crosses in all -- the number
+    // of spheres with a chord of positive length inside [tmin, tmax] (a sphere around the ray's start counts), the first entry and the
+    // last exit with their particle ids, and the summed share of the chords in units of 2^-24 of a diameter (thickness = length * 2 r *
+    // 2^-24).  radius and flags as CastRays (SPH_RAYS_ANY_HIT is refused).  The spans stay in the engine, beside the hits of CastRays,
+    // until the next call, ResetSimulation or the destructor; nothing crossed is (+inf, -inf, -1, -1, 0).  Return false on error.
+    bool SpanRays(const std::vector<float>& rays8, SphRaySpansInfo& out, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_rays_span(engine, rays8.empty() ? nullptr : rays8.data(), rays8.size() / 8, radius > 0.0f ? radius : 0.25f * param_h, flags, &out),
+                      "sph_rays_span");
+    }
+    bool SpanRaysDevice(const float* devRays8, size_t m, SphRaySpansInfo& out, float radius = 0.0f, int flags = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_rays_span_device(engine, devRays8, m, radius > 0.0f ? radius : 0.25f * param_h, flags, &out), "sph_rays_span_device");
+    }
+    SphRaySpansInfo RaySpansInfo() {
+        SphRaySpansInfo info{};
+        Check(sph_rays_span_info(engine, &info), "sph_rays_span_info");
+        return info;
+    }
+    bool DownloadRaySpans(std::vector<SphRaySpan>& rows) {
+        SphRaySpansInfo info{};
+        if (Check(sph_rays_span_info(engine, &info), "sph_rays_span_info")) return false;
+        rows.assign(size_t(info.rays), SphRaySpan{});
+        return !Check(sph_rays_span_download(engine, rows.empty() ? nullptr : rows.data()), "sph_rays_span_download");
+    }
     // Iso-surface (engine extension, sph_abi.h "iso-surface"): the closed triangle mesh of {field >= iso} on the lattice
     // origin + i * spacing (dims >= 2 per axis).  `out` holds counts and device arrays borrowed from the engine, valid until the next
     // ExtractSurface, ResetSimulation or the destructor.  DownloadSurface copies the last surface to the host (3 indices per

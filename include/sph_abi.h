@@ -53,6 +53,7 @@ extern "C" {
 /* (still 4, additions only: SphComponent, SphComponentInfo, SPH_COMPONENTS_FLUID_ONLY, SPH_COMPONENT_NONFINITE, sph_components_build / _info / _device / _download / _host, SPH_OPT_COMPONENTS_VARIANT -- connected bodies of fluid) */
 /* (still 4, additions only: SphKnnInfo, SPH_KNN_SELF, SPH_KNN_FLUID_ONLY, SPH_KNN_MAX_K, sph_knn_build / _query / _info / _device / _download / _host, SPH_OPT_KNN_VARIANT -- k nearest neighbours) */
 /* (still 4, additions only: SphRayHit, SphRaysInfo, SPH_RAYS_FLUID_ONLY, SPH_RAYS_ANY_HIT, sph_rays_cast / _cast_device / _info / _device / _download / _host / _walk_host, SPH_OPT_RAYS_VARIANT -- ray casts against the particles) */
+/* (still 4, additions only: SphRaySpan, SphRaySpansInfo, sph_rays_span / _span_device / _span_info / _span_rows / _span_download / _span_host / _span_walk_host, SPH_OPT_RAY_SPANS_VARIANT -- ray spans: what each ray crosses in all) */
 /* (still 4, additions only: SphAniso, SphAnisoConfig, SphAnisoInfo, SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID / _SPARSE / _CLAMPED, sph_aniso_default / _build / _info / _device / _download / _lattice / _surface / _host / _lattice_host -- anisotropic kernels) */
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
@@ -164,6 +165,7 @@ enum {
     SPH_OPT_KNN_VARIANT = 12,    /* k nearest neighbours (sph_knn_*), an A/B for measurements: 0 = one target per lane keeps its k best keys in LDS (default), 1 = k selection passes over the candidates without any storage (slow); the same bits */
     SPH_OPT_RAYS_VARIANT = 13,   /* ray casts (sph_rays_*), an A/B for measurements: 0 = the rays are cast in the caller's order (default), 1 = in the order of the grid cell they enter first (a counting sort of the rays in front of the walk: faster for incoherent rays, slower for sheets and fans); the same bits */
     SPH_OPT_SHELL_TIMED = 14,    /* free-surface particles (sph_shell_*), measurements only: which launches of a build the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = pass 1 (ids and the gather), 2 = pass 2 (the crest kernel), 3 = the two scans and compactions; the launches themselves are the same */
+    SPH_OPT_RAY_SPANS_VARIANT = 15, /* ray spans (sph_rays_span*), an A/B for measurements: 0 = the layer walk (default: after the first cell only the new 3 x 3 layer of the block is tested), 1 = the block walk (every step tests the whole block and drops what the previous cell's block held); the same bits.  SPH_OPT_RAYS_VARIANT orders the rays of spans as it does those of casts */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -1056,6 +1058,45 @@ int sph_rays_host(const SphParticle* particles, size_t n, const SphParams* param
  * against the definition without a device. */
 int sph_rays_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
                        SphRayHit* hits, SphRaysInfo* out);
+
+/* ---- ray spans: what each ray crosses in all (no reference counterpart; DESIGN.md section 3n "Spans") -------------------------------
+ * The other half of a cast: how much of the fluid lies along the ray and where the ray leaves it.  Rays, void rays, the radius bound,
+ * participation and SPH_RAYS_FLUID_ONLY are those of the cast; SPH_RAYS_ANY_HIT is SPH_ERR_ARG here.
+ * With tca and thc = sqrtf(s * (1 / a)) exactly as above, tin = fmaxf(tca - thc, tmin), tout = fminf(tca + thc, tmax): a sphere is
+ * CROSSED iff s >= 0 && tin < tout (a chord of positive length inside the window).  Unlike the cast, a sphere that contains the ray's
+ * start counts, with tin = tmin.  Its share of a diameter is f = fminf((tout - tin) / (2 * thc), 1), q = (uint32)fmaf(f, 16777216, 0.5f).
+ * Per ray one SphRaySpan: tEnter the smallest tin (+inf if nothing is crossed), tExit the largest tout (-inf), idEnter the id of the
+ * smallest key (ordered(tin), id) (the cast's key rule; -1), idExit the id of the largest ordered(tout), ties to the smaller id (-1),
+ * count the number of crossed spheres, flags bit 0 = the ray is void, length the sum of q.  The thickness in world units is
+ * length * 2 r * 2^-24 whatever the length of d; overlapping spheres add.  f is the share of the sphere's OWN chord that lies inside the
+ * window, so a sphere crossed whole counts as one diameter whatever the impact parameter (a disc splat, as a splatted thickness buffer
+ * has it): through spheres of number density n the thickness per unit path is n pi r^2 * 2 r, three halves of the packing fraction
+ * n 4 pi r^3 / 3.  Every field is a min, a max or an integer sum of per-sphere
+ * values: the result does not depend on the order in which the spheres are met, is the same on every run, and sph_rays_span_host (brute
+ * force) is its definition.  On rays that start outside every sphere, tEnter / idEnter are the cast's t / id.
+ * SphRaySpansInfo: crossed (rays with count > 0), voidRays, total (the sum of count), maxCount: integer reductions.
+ * Spans and hits are separate state: a span call does not end the held hits nor a cast the held spans; the spans stay valid until the
+ * next sph_rays_span / _span_device, sph_reset or sph_destroy.  A span call changes no record.  Timed as SPH_K_OTHER.  Refusals, m = 0
+ * and n = 0 as for the cast. */
+typedef struct SphRaySpan { float tEnter, tExit; int32_t idEnter, idExit; uint32_t count, flags; uint64_t length; } SphRaySpan;   /* 32 bytes */
+typedef struct SphRaySpansInfo { uint64_t rays, crossed, voidRays, total; uint32_t maxCount; float radius; int32_t flags; uint32_t pad; } SphRaySpansInfo;   /* 48 bytes */
+/* m rays of 8 floats in HOST memory (may be null when m is 0): staged upload, then as _span_device.  Synchronises. */
+int sph_rays_span(SphEngine* e, const float* rays8, size_t m, float radius, int flags, SphRaySpansInfo* out);
+/* m rays of 8 floats in DEVICE memory (may be null when m is 0).  One synchronisation, for the four counts. */
+int sph_rays_span_device(SphEngine* e, const float* devRays8, size_t m, float radius, int flags, SphRaySpansInfo* out);
+/* What the engine holds. */
+int sph_rays_span_info(const SphEngine* e, SphRaySpansInfo* out);
+/* Borrowed device address: rows[rays]. */
+int sph_rays_span_rows(SphEngine* e, const SphRaySpan** rows);
+/* Copies the spans into the caller's memory, host or device (the kind of the copy follows from the address); synchronises. */
+int sph_rays_span_download(SphEngine* e, SphRaySpan* rows);
+/* Host-only, no device, THE DEFINITION: brute force over all participating records, no grid, the same ray_span.  rows may be null. */
+int sph_rays_span_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                       SphRaySpan* rows, SphRaySpansInfo* out);
+/* TEST HOOK.  Host-only, no device: the DEVICE's span walk (the same ray_span_walk function) over the grid as the counting sort leaves
+ * it; variant 0 = the layer walk, 1 = the block walk.  Same bytes as sph_rays_span_host while the walk meets every sphere once. */
+int sph_rays_span_walk_host(const SphParticle* particles, size_t n, const SphParams* params, const float* rays8, size_t m, float radius, int flags,
+                            int variant, SphRaySpan* rows, SphRaySpansInfo* out);
 
 /* ---- free-surface particles (no reference counterpart) ---------------------------------------------------------
  * Which particles lie in the outer shell of the fluid, which way the surface faces there, and how sharply convex it is -- from the

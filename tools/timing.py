@@ -1,6 +1,6 @@
 """What the tools/time_*.py scripts share: the package import, the config 3 scene and its two regimes, the sample statistics, the
 device-event brackets, the copy yardstick, the body grid of the obstacle tools, the head and tail of a result file, and for the tools
-of the spatial queries (time_neighbors, time_components, time_knn, time_rays, time_shell, time_aniso) the series of the engine's own brackets,
+of the spatial queries (time_neighbors, time_components, time_knn, time_rays, time_ray_spans, time_shell, time_aniso) the series of the engine's own brackets,
 the queries through the C ABI alone, and the torch route a query is compared with."""
 from __future__ import annotations
 
@@ -131,6 +131,10 @@ def knn_query(f, pts, k, R):
 
 def rays_cast(f, dev, radius, flags):
     return _bare(f, f._L.sph_rays_cast_device, pkg.SphRaysInfo(), C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), int(flags))
+
+
+def rays_span(f, dev, radius, flags=0):
+    return _bare(f, f._L.sph_rays_span_device, pkg.SphRaySpansInfo(), C.c_void_p(dev.data_ptr()), int(dev.shape[0]), float(radius), int(flags))
 
 
 def shell_build(f, R):
