@@ -22,6 +22,8 @@ from .engine import (  # noqa: F401
     SPH_MAX_SCALAR_CHANNELS, SPH_OPT_SCALAR_SWEEP, SPH_SCALAR_ADD, SPH_SCALAR_SET, ScalarMoments, SphScalarMoments, mixing_index, scalars_step_host,
     SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_SPHERE, SPH_SOURCE_BOX, SPH_SOURCE_RATE, SPH_SOURCE_RELAX, SphScalarSource, SOURCE_DTYPE, scalar_source,
     source_array, scalars_couple_host,
+    SPH_MAX_GATES, SPH_MAX_GATE_HISTORY, SPH_GATE_RECT, SPH_GATE_ELLIPSE, SPH_GATE_UNBOUNDED, SphGate, SphGateBooks, GATE_DTYPE, GATE_BOOKS_DTYPE,
+    gate, gate_box, gate_array, gate_discharge, gates_step_host,
     SPH_OPT_DIFFUSE_TIMED, SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE, SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, DIFFUSE_DTYPE, diffuse_config,
     diffuse_step_host, write_points_ply, SphDiffuseCrest, SphDiffuseCrestInfo, diffuse_crest_config,
     SPH_OPT_NEIGHBORS_FILL, SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY, SphNeighborInfo, neighbors_host,

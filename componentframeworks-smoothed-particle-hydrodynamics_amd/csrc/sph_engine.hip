@@ -38,6 +38,7 @@
 #include "sph_volume.h"
 #include "sph_stats.h"
 #include "sph_couple.h"
+#include "sph_gate.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
@@ -48,6 +49,9 @@ static_assert(sizeof(SphScalarMoments) == 40, "SphScalarMoments must be 40 bytes
 static_assert(SPH_MAX_SCALAR_CHANNELS == sph::kScalarMax && SPH_SCALAR_SET == sph::kScalarSet && SPH_SCALAR_ADD == sph::kScalarAdd, "scalar constants of sph_abi.h and sph_scalar.h");
 static_assert(sizeof(SphScalarSource) == sizeof(sph::CoupleSrc) && SPH_MAX_SCALAR_SOURCES == sph::kCoupleMax && SPH_SOURCE_SPHERE == sph::COUPLE_SPHERE &&
               SPH_SOURCE_BOX == sph::COUPLE_BOX && SPH_SOURCE_RATE == sph::COUPLE_RATE && SPH_SOURCE_RELAX == sph::COUPLE_RELAX, "SphScalarSource must be 64 bytes");
+static_assert(sizeof(SphGate) == sizeof(sph::GateRec) && sizeof(SphGateBooks) == 8 * sph::kGateWords && SPH_MAX_GATES == sph::kGateMax &&
+              SPH_MAX_GATE_HISTORY == sph::kGateHistoryMax && SPH_GATE_RECT == sph::GATE_RECT && SPH_GATE_ELLIPSE == sph::GATE_ELLIPSE &&
+              SPH_GATE_UNBOUNDED == sph::GATE_UNBOUNDED && SPH_MAX_SCALAR_CHANNELS == sph::kGateChannels, "SphGate must be 64 bytes, SphGateBooks 72");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
 static_assert(sizeof(SphObstacleDynamics) == 80, "SphObstacleDynamics must be 80 bytes");
 static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
@@ -401,6 +405,16 @@ struct SphEngine {
     sph::CoupleTab cpTab{};              // host mirror of *d_cpTab
     bool cpBuoy = false;                 // a beta is non-zero: the kick runs, and the pass does not keep the 80-byte array current
 
+    // sph_gates_* (sph_gate.h): the table the kernels read (device memory: a replayed graph sees a later set) with
+    // its host mirror and pinned staging, the gates as set, the books, the per-block partial rows and the history ring (gtRingCap rows)
+    sph::GateTab* d_gtTab = nullptr;
+    sph::GateAcc* d_gtAcc = nullptr;
+    DevBuf<unsigned long long> d_gtPart, d_gtRing;
+    StageRing<sph::GateTab> gtStage;     // one table per slot
+    sph::GateTab gtTab{};                // host mirror of *d_gtTab (count 0: no gates, nothing is launched)
+    SphGate gtSet[sph::kGateMax] = {};
+    uint32_t gtRingCap = 0;
+
     // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
     // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
     sph::ObsRec* d_obs = nullptr;
@@ -611,6 +625,15 @@ void scalars_free(SphEngine* e) {
     e->cpBuoy = false;
     e->d_scView.release(); e->d_scViewRp.release(); e->d_scSampleOut.release();
     e->scK = 0; e->scN = 0; e->scSteps = 0;
+}
+
+void gates_free(SphEngine* e) {
+    if (e->d_gtTab && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(e->d_gtTab); dev_free(e->d_gtAcc);
+    e->d_gtPart.release(); e->d_gtRing.release();
+    e->gtStage.destroy();
+    e->gtTab = sph::GateTab{};
+    e->gtRingCap = 0;
 }
 
 void obstacles_free(SphEngine* e) {
@@ -1125,6 +1148,34 @@ int couple_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
     return SPH_OK;
 }
 
+// ---- flow gates (sph_gate.h) -------------------------------------------------------------------------
+template <int K>
+void gates_launch(SphEngine* e, int rows, const float4* pos, const float4* vel, int n) {
+    hipLaunchKernelGGL((k_gates<K>), dim3(rows), dim3(kGateBlock), 0, e->stream, (const GateTab*)e->d_gtTab, pos, vel, (const float4*)e->d_sPV,
+                       (const float*)e->d_scVal, e->idBase, n, e->d_gtPart.p);
+}
+// One substep's gate step on the pass's output state and the sorted copy of its entry state: k_gates, then the one-block finish of the
+// books and of the ring.  It writes no particle state.
+int gates_step(SphEngine* e, const float4* pos, const float4* vel, int n, float dt) {
+    const int rows = n > 0 ? std::min(kGateGrid, blocks_for((size_t)n, kGateSweep)) : 0;
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (rows) {
+            switch (e->scK) {
+            case 0: gates_launch<0>(e, rows, pos, vel, n); break;
+            case 1: gates_launch<1>(e, rows, pos, vel, n); break;
+            case 2: gates_launch<2>(e, rows, pos, vel, n); break;
+            case 3: gates_launch<3>(e, rows, pos, vel, n); break;
+            default: gates_launch<4>(e, rows, pos, vel, n); break;
+            }
+        }
+        hipLaunchKernelGGL(k_gates_finish, dim3(1), dim3(kGateFinishBlock), 0, e->stream, dt, (const unsigned long long*)e->d_gtPart.p, rows,
+                           (const GateTab*)e->d_gtTab, e->d_gtAcc, e->d_gtRing.p, e->gtRingCap);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
 int writeback(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "a slab engine has no local 80-byte array: use sph_slab_download");
     if (e->aosValid) return SPH_OK;
@@ -1173,6 +1224,8 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if (e->dfC && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (e->gtTab.count && e->optGridBuild == 1)
+        return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params)) || (rc = couple_refused(e))) return rc;
     float cont[15];
     container_key(e->params, cont);
@@ -1286,6 +1339,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     }
     if (e->obsK && (rc = obstacles_step(e, out.pos, out.vel, n, dt))) return rc;   // (after the container, before river / fountain)
     if (e->scK && (e->cpBuoy || e->cpTab.nSrc) && (rc = couple_step(e, out.pos, out.vel, n, dt))) return rc;   // (sources, then buoyancy)
+    if (e->gtTab.count && (rc = gates_step(e, out.pos, out.vel, n, dt))) return rc;   // (sees the kick's velocity and the sources' values)
     const bool riverOn = e->river.riverMode && !e->terrainHeights.empty();   // :512
     if (riverOn) {                                                           // :511-516, DispatchTerrainConstraints / ChannelConstraint / StreamEmit
         if (e->slab) return fail(SPH_ERR_STATE, "riverMode on a z-slab engine: recycled particles jump across slabs (single-GPU engines only)");
@@ -1492,6 +1546,7 @@ int sph_destroy(SphEngine* e) {
     tracers_free(e);
     diffuse_free(e);
     scalars_free(e);
+    gates_free(e);
     obstacles_free(e);
     volumes_free(e);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -1532,6 +1587,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
+    gates_free(e);                                                    // (and the flow gates)
     if (e->d_obsAcc) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (obstacles: the set and the poses stay, the sums restart)
     std::vector<SphParticle> v;
     float m;
@@ -1676,6 +1732,12 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
         add(cr, sizeof(cr));
         add(&e->dfCrCfg.radius, sizeof(float));                       // (with the params above it fixes the radius in force and the stencil)
         add(&e->dfCrCfg.offset, sizeof(float)); add(&e->dfCrCfg.minCount, sizeof(uint32_t)); add(&e->dfCrCfg.flags, sizeof(int32_t));
+    }
+    // flow gates, only while gates are set (off: the material of before): the buffers of the two launches; table, count, history and stride are read from memory
+    if (e->gtTab.count) {
+        const void* gt[4] = {e->d_gtTab, e->d_gtAcc, e->d_gtPart.p, e->d_gtRing.p};
+        add(gt, sizeof(gt));
+        add(&e->gtRingCap, sizeof(e->gtRingCap));
     }
     return m;
 }
@@ -5666,6 +5728,161 @@ int sph_scalars_couple_host(SphParticle* particles, size_t n, const SphParams* p
     for (int i = 0; i < nSources; ++i) {
         if (sumsOut) sumsOut[i] = sums[i];
         if (hitsOut) hitsOut[i] = hits[i];
+    }
+    return SPH_OK;
+}
+
+// ---- flow gates (sph_gate.h) ------------------------------------------------
+static int gates_check(const SphGate* gates, int count) {
+    if (count < 0 || count > SPH_MAX_GATES) return fail(SPH_ERR_ARG, "gate count %d outside 0..%d", count, SPH_MAX_GATES);
+    if (count && !gates) return fail(SPH_ERR_ARG, "null argument");
+    for (int i = 0; i < count; ++i) {
+        const SphGate& g = gates[i];
+        if (g.shape != SPH_GATE_RECT && g.shape != SPH_GATE_ELLIPSE) return fail(SPH_ERR_ARG, "gate %d: unknown shape %d", i, g.shape);
+        if (g.flags & ~SPH_GATE_UNBOUNDED) return fail(SPH_ERR_ARG, "gate %d: unknown flag bits %d", i, g.flags);
+        if (!obs_all_finite(g.center, 3) || !obs_all_finite(g.u, 3) || !obs_all_finite(g.v, 3)) return fail(SPH_ERR_ARG, "gate %d: a field is not finite", i);
+        double uu = 0.0, vv = 0.0, uv = 0.0;
+        for (int a = 0; a < 3; ++a) { uu += (double)g.u[a] * g.u[a]; vv += (double)g.v[a] * g.v[a]; uv += (double)g.u[a] * g.v[a]; }
+        if (!(uu > 0.0) || !(vv > 0.0)) return fail(SPH_ERR_ARG, "gate %d: u and v must not have zero length", i);
+        if (std::fabs(uv) > 1e-4 * std::sqrt(uu) * std::sqrt(vv)) return fail(SPH_ERR_ARG, "gate %d: u and v are not orthogonal (u.v = %g)", i, uv);
+    }
+    return SPH_OK;
+}
+static void gate_to_rec(const SphGate& g, sph::GateRec& r) {
+    std::memset(&r, 0, sizeof(r));
+    r.shape = g.shape; r.flags = g.flags;
+    for (int a = 0; a < 3; ++a) { r.c[a] = g.center[a]; r.u[a] = g.u[a]; r.v[a] = g.v[a]; }
+    sph::gate_derive(r);
+}
+// The host mirror to the device, stream-ordered, through the next pinned staging slot.
+static int gates_upload(SphEngine* e) {
+    int rc;
+    sph::GateTab* slot = nullptr;
+    if ((rc = e->gtStage.next(&slot))) return rc;
+    *slot = e->gtTab;
+    HIP_TRY(hipMemcpyAsync(e->d_gtTab, slot, sizeof(sph::GateTab), hipMemcpyHostToDevice, e->stream));
+    return e->gtStage.commit(e->stream);
+}
+// The buffers, at the first call that sets a gate; the ring grows with the history asked for.
+static int gates_ensure(SphEngine* e, uint32_t history) {
+    int rc;
+    if (!e->d_gtTab) {
+        hipError_t er = hipSuccess;
+        if ((rc = dev_alloc(&e->d_gtTab, 1)) || (rc = dev_alloc(&e->d_gtAcc, 1)) || (er = e->gtStage.create(e->stream, 1)) != hipSuccess ||
+            (rc = e->d_gtPart.grow(e, (size_t)kGateGrid * kGateTerms))) {
+            dev_free(e->d_gtTab); dev_free(e->d_gtAcc);
+            e->gtStage.destroy();
+            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the gate table: %s", hipGetErrorString(er));
+        }
+        HIP_TRY(hipMemsetAsync(e->d_gtAcc, 0, sizeof(sph::GateAcc), e->stream));
+    }
+    if (history > e->gtRingCap || !e->d_gtRing.p) {
+        if ((rc = e->d_gtRing.grow(e, (size_t)std::max(history, 1u) * kGateRingRow))) return rc;
+        e->gtRingCap = std::max(history, 1u);
+    }
+    return SPH_OK;
+}
+
+int sph_gates_set(SphEngine* e, const SphGate* gates, int count, uint32_t history, uint32_t stride) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "gates on a z-slab engine are not supported: a crossing needs the entry and the exit state at one slot");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    int rc;
+    if ((rc = gates_check(gates, count))) return rc;
+    if (history > SPH_MAX_GATE_HISTORY) return fail(SPH_ERR_ARG, "history %u above %d", history, SPH_MAX_GATE_HISTORY);
+    if (stride == 0) return fail(SPH_ERR_ARG, "stride must be >= 1");
+    if (!count && !e->d_gtTab) return SPH_OK;                         // (never set: nothing to clear)
+    if ((rc = gates_ensure(e, history))) return rc;
+    if (count != e->gtTab.count || history != e->gtTab.history || stride != e->gtTab.stride) {   // (another count, history or stride: books and ring restart)
+        HIP_TRY(hipMemsetAsync(e->d_gtAcc, 0, sizeof(sph::GateAcc), e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_gtRing.p, 0, sizeof(unsigned long long) * (size_t)e->gtRingCap * kGateRingRow, e->stream));
+    }
+    for (int i = 0; i < sph::kGateMax; ++i) {
+        if (i < count) { gate_to_rec(gates[i], e->gtTab.g[i]); e->gtSet[i] = gates[i]; }
+        else { std::memset(&e->gtTab.g[i], 0, sizeof(sph::GateRec)); std::memset(&e->gtSet[i], 0, sizeof(SphGate)); }
+    }
+    e->gtTab.count = count; e->gtTab.history = history; e->gtTab.stride = stride;
+    return gates_upload(e);
+}
+
+int sph_gates_get(SphEngine* e, SphGate* out, int cap, int* countOut, uint32_t* historyOut, uint32_t* strideOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    const int count = e->gtTab.count;
+    if (out && cap < count) return fail(SPH_ERR_CAPACITY, "%d gates (capacity %d)", count, cap);
+    if (out && count) std::memcpy(out, e->gtSet, sizeof(SphGate) * (size_t)count);
+    if (countOut) *countOut = count;
+    if (historyOut) *historyOut = e->gtTab.history;
+    if (strideOut) *strideOut = count ? e->gtTab.stride : 1u;
+    return SPH_OK;
+}
+
+int sph_gates_books(SphEngine* e, SphGateBooks* books, double* timeOut, uint64_t* substepsOut, int reset) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    std::unique_ptr<sph::GateAcc> a(new sph::GateAcc());
+    std::memset(a.get(), 0, sizeof(sph::GateAcc));
+    if (e->d_gtAcc) {
+        HIP_TRY(hipMemcpyAsync(a.get(), e->d_gtAcc, sizeof(sph::GateAcc), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (reset) HIP_TRY(hipMemsetAsync(e->d_gtAcc, 0, offsetof(sph::GateAcc, ringSteps), e->stream));   // (the ring keeps counting)
+    }
+    if (books && e->gtTab.count) std::memcpy(books, a->words, sizeof(SphGateBooks) * (size_t)e->gtTab.count);
+    if (timeOut) *timeOut = a->time;
+    if (substepsOut) *substepsOut = a->substeps;
+    return SPH_OK;
+}
+
+int sph_gates_history(SphEngine* e, uint64_t* firstOut, uint32_t* countOut, SphGateBooks* rows, double* times) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    const uint32_t H = e->gtTab.count ? e->gtTab.history : 0u, S = std::max(e->gtTab.stride, 1u);
+    uint64_t taken = 0;
+    std::vector<unsigned long long> ring;
+    if (H && e->d_gtAcc) {
+        unsigned long long steps = 0;
+        ring.resize((size_t)H * kGateRingRow);
+        HIP_TRY(hipMemcpyAsync(&steps, &e->d_gtAcc->ringSteps, sizeof(steps), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(ring.data(), e->d_gtRing.p, sizeof(unsigned long long) * ring.size(), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        taken = steps / S;
+    }
+    const uint32_t have = (uint32_t)std::min<uint64_t>(taken, H);
+    const uint64_t first = taken - have;
+    for (uint32_t i = 0; i < have; ++i) {
+        const unsigned long long* row = ring.data() + (size_t)((first + i) % H) * kGateRingRow;
+        if (rows) std::memcpy(rows + (size_t)i * e->gtTab.count, row, sizeof(SphGateBooks) * (size_t)e->gtTab.count);
+        if (times) std::memcpy(times + i, row + kGateTerms, sizeof(double));
+    }
+    if (firstOut) *firstOut = first;
+    if (countOut) *countOut = have;
+    return SPH_OK;
+}
+
+int sph_gates_step_host(const SphParticle* entry, const SphParticle* exitRecords, size_t n, const SphGate* gates, int count, const float* values,
+                        int channels, SphGateBooks* books) {
+    if (n && (!entry || !exitRecords)) return fail(SPH_ERR_ARG, "null argument");
+    if (channels < 0 || channels > SPH_MAX_SCALAR_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (0 .. %d)", channels, SPH_MAX_SCALAR_CHANNELS);
+    if ((channels && n && !values) || (count && !books)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = gates_check(gates, count))) return rc;
+    sph::GateRec recs[sph::kGateMax];
+    for (int g = 0; g < count; ++g) gate_to_rec(gates[g], recs[g]);
+    for (size_t i = 0; i < n; ++i) {
+        const SphParticle& a = entry[i];
+        const SphParticle& b = exitRecords[i];
+        if (b.isGhost != 0 || !obs_all_finite(b.pos, 3) || !obs_all_finite(a.pos, 3)) continue;
+        for (int g = 0; g < count; ++g) {
+            const sph::GateRec& G = recs[g];
+            const float s0 = sph::gate_side(G, a.pos[0], a.pos[1], a.pos[2]), s1 = sph::gate_side(G, b.pos[0], b.pos[1], b.pos[2]);
+            const int dir = sph::gate_crossing(s0, s1);
+            if (!dir || !sph::gate_counts(G, a.pos[0], a.pos[1], a.pos[2], b.pos[0], b.pos[1], b.pos[2], s0, s1)) continue;
+            const double sg = dir > 0 ? 1.0 : -1.0;
+            SphGateBooks& B = books[g];
+            if (dir > 0) B.forward += 1; else B.backward += 1;
+            for (int c = 0; c < 3; ++c) B.vel[c] += sg * (double)b.vel[c];
+            for (int k = 0; k < channels; ++k) {
+                const float cv = values[i * (size_t)channels + k];
+                B.scalar[k] += sph::float_finite(cv) ? sg * (double)cv : 0.0;
+            }
+        }
     }
     return SPH_OK;
 }

@@ -264,6 +264,28 @@ SPH_SOURCE_SPHERE, SPH_SOURCE_BOX = 0, 1
 SPH_SOURCE_RATE, SPH_SOURCE_RELAX = 0, 1
 
 
+class SphGate(C.Structure):
+    """struct SphGate of include/sph_abi.h: one flow gate, an oriented planar patch fixed in the world (see gate() and
+    SPHFluidGPU.set_gates)."""
+    _fields_ = [("shape", C.c_int32), ("flags", C.c_int32), ("center", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3),
+                ("pad", C.c_float * 5)]
+
+
+class SphGateBooks(C.Structure):
+    """struct SphGateBooks: the cumulative books of one gate."""
+    _fields_ = [("forward", C.c_uint64), ("backward", C.c_uint64), ("vel", C.c_double * 3), ("scalar", C.c_double * 4)]
+
+
+assert C.sizeof(SphGate) == 64 and C.sizeof(SphGateBooks) == 72
+GATE_DTYPE = np.dtype(SphGate)
+GATE_BOOKS_DTYPE = np.dtype(SphGateBooks)
+assert GATE_DTYPE.itemsize == 64 and GATE_BOOKS_DTYPE.itemsize == 72
+SPH_MAX_GATES = 8
+SPH_MAX_GATE_HISTORY = 4096
+SPH_GATE_RECT, SPH_GATE_ELLIPSE = 0, 1
+SPH_GATE_UNBOUNDED = 1
+
+
 class SphNeighborInfo(C.Structure):
     """struct SphNeighborInfo of include/sph_abi.h: what the engine's neighbour lists hold (see SPHFluidGPU.neighbors)."""
     _fields_ = [("rows", C.c_uint64), ("total", C.c_uint64), ("radius", C.c_float), ("stencil", C.c_int32), ("flags", C.c_int32),
@@ -520,6 +542,12 @@ _ABI = {
     "sph_scalars_get_sources": (_int, [_vp, _vp, _int, _pi]),
     "sph_scalars_injected": (_int, [_vp, _vp, _vp, _int, _P(_d), _P(_u64), _int]),
     "sph_scalars_couple_host": (_int, [_vp, _sz, _pp, _f, _vp, _int, _pf, _pf, _vp, _int, _vp, _int, _vp, _vp]),
+    # flow gates
+    "sph_gates_set": (_int, [_vp, _vp, _int, _u32, _u32]),
+    "sph_gates_get": (_int, [_vp, _vp, _int, _pi, _P(_u32), _P(_u32)]),
+    "sph_gates_books": (_int, [_vp, _vp, _P(_d), _P(_u64), _int]),
+    "sph_gates_history": (_int, [_vp, _P(_u64), _P(_u32), _vp, _vp]),
+    "sph_gates_step_host": (_int, [_vp, _vp, _sz, _vp, _int, _vp, _int, _vp]),
     # spray, foam and bubbles
     "sph_diffuse_default": (None, [_P(SphDiffuseConfig)]),
     "sph_diffuse_set": (_int, [_vp, _P(SphDiffuseConfig)]),
@@ -945,6 +973,53 @@ def source_array(sources) -> np.ndarray:
     if not sources:
         return np.zeros(0, SOURCE_DTYPE)
     return np.frombuffer(b"".join(bytes(o) for o in sources), SOURCE_DTYPE).copy()
+
+
+def gate(shape, center, u, v, unbounded: bool = False) -> SphGate:
+    """One flow gate: SPH_GATE_RECT or SPH_GATE_ELLIPSE with centre `center` and the orthogonal half-extent
+    vectors u and v; forward is cross(u, v).  unbounded: the whole plane counts, not only the patch."""
+    g = SphGate()
+    ce, uu, vv = ([float(x) for x in a] for a in (center, u, v))
+    if len(ce) != 3 or len(uu) != 3 or len(vv) != 3:
+        raise SphError("gate: center, u and v need 3 components")
+    g.shape, g.flags = int(shape), SPH_GATE_UNBOUNDED if unbounded else 0
+    for i in range(3):
+        g.center[i], g.u[i], g.v[i] = ce[i], uu[i], vv[i]
+    return g
+
+
+def gate_box(center, half) -> list:
+    """Six rectangles with outward normals around the axis-aligned box centre +- half: a control volume.  Order -x, +x, -y, +y, -z, +z;
+    forward - backward summed over the six is the net outflow."""
+    c = [float(x) for x in center]
+    h = [float(half)] * 3 if np.ndim(half) == 0 else [float(x) for x in half]
+    out = []
+    for a in range(3):
+        b, d = (a + 1) % 3, (a + 2) % 3
+        for sign in (-1.0, 1.0):
+            ce, u, v = list(c), [0.0] * 3, [0.0] * 3
+            ce[a] += sign * h[a]
+            u[b], v[d] = h[b], sign * h[d]                            # cross(e_b, e_d) = e_a
+            out.append(gate(SPH_GATE_RECT, ce, u, v))
+    return out
+
+
+def gate_array(gates) -> np.ndarray:
+    """A list of SphGate, or a structured array, as a contiguous GATE_DTYPE array (the layout of SphGate)."""
+    if isinstance(gates, np.ndarray):
+        return np.ascontiguousarray(gates, GATE_DTYPE)
+    gates = list(gates or ())
+    if not gates:
+        return np.zeros(0, GATE_DTYPE)
+    return np.frombuffer(b"".join(bytes(o) for o in gates), GATE_DTYPE).copy()
+
+
+def gate_discharge(rows, time: float, params: SphParams) -> np.ndarray:
+    """Net volume per unit time through each gate: (forward - backward) * param_mass / param_restDensity / time, from the rows of
+    gate_books() or of one history row."""
+    rows = np.asarray(rows)
+    net = rows["forward"].astype(np.float64) - rows["backward"].astype(np.float64)
+    return net * float(params.param_mass) / float(params.param_restDensity) / float(time)
 
 
 def _buoyancy(channels: int, beta, ref):
@@ -1910,6 +1985,46 @@ class SPHFluidGPU:
         k = len(self.scalar_sources())
         return sums[:k].copy(), hits[:k].copy(), float(t.value), int(n.value)
 
+    # -- flow gates (include/sph_abi.h "flow gates") ----------------------
+    def set_gates(self, gates, history: int = 0, stride: int = 1):
+        """Replace the gate table (a list of gate() results or a GATE_DTYPE array; empty clears it).  Every substep from now on books
+        what crosses each gate; with history > 0 the cumulative books go into a ring row on the device every `stride` substeps.
+        Another count, history or stride zeroes books and ring.  No synchronisation."""
+        arr = gate_array(gates)
+        _check(self._L.sph_gates_set(self._h, _ptr_or_none(arr), len(arr), int(history), int(stride)))
+
+    def clear_gates(self):
+        _check(self._L.sph_gates_set(self._h, None, 0, 0, 1))
+
+    def _gates_info(self):
+        k, h, s = C.c_int(), C.c_uint32(), C.c_uint32()
+        _check(self._L.sph_gates_get(self._h, None, 0, C.byref(k), C.byref(h), C.byref(s)))
+        return k.value, h.value, s.value
+
+    def gates(self) -> np.ndarray:
+        """The gates as set, a GATE_DTYPE array."""
+        out = np.zeros(SPH_MAX_GATES, GATE_DTYPE)
+        k = C.c_int()
+        _check(self._L.sph_gates_get(self._h, _ptr(out), len(out), C.byref(k), None, None))
+        return out[:k.value].copy()
+
+    def gate_books(self, reset: bool = False):
+        """(rows, time, substeps): per gate the books (GATE_BOOKS_DTYPE: forward, backward, vel, scalar) since the last zeroing, the
+        simulated time and the substeps over which they were summed; reset zeroes them after the read.  Synchronises."""
+        rows = np.zeros(SPH_MAX_GATES, GATE_BOOKS_DTYPE)
+        t, n = C.c_double(), C.c_uint64()
+        _check(self._L.sph_gates_books(self._h, _ptr(rows), C.byref(t), C.byref(n), 1 if reset else 0))
+        return rows[:self._gates_info()[0]].copy(), float(t.value), int(n.value)
+
+    def gate_history(self):
+        """(first, rows (count, gates) GATE_BOOKS_DTYPE, times (count,)): the stored ring rows, oldest first, and the index of the first
+        one (row i was taken after (first + i + 1) * stride substeps).  Synchronises."""
+        k, h, _ = self._gates_info()
+        rows, times = np.zeros((max(h, 1), max(k, 1)), GATE_BOOKS_DTYPE), np.zeros(max(h, 1), np.float64)
+        first, cnt = C.c_uint64(), C.c_uint32()
+        _check(self._L.sph_gates_history(self._h, C.byref(first), C.byref(cnt), _ptr(rows.reshape(-1)), _ptr(times)))
+        return int(first.value), rows.reshape(-1)[:cnt.value * k].reshape(cnt.value, k).copy(), times[:cnt.value].copy()
+
     # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
     def set_obstacles(self, obstacles):
         """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
@@ -2553,3 +2668,20 @@ def scalars_couple_host(particles: np.ndarray, params: SphParams, values, beta=N
                                                   None if b is None else b.ctypes.data_as(_pf), None if r is None else r.ctypes.data_as(_pf),
                                                   _ptr_or_none(src), len(src), _ptr_or_none(obs), len(obs), _ptr(sums), _ptr(hits)))
     return rec, v, sums[:len(src)], hits[:len(src)]
+
+
+def gates_step_host(entry: np.ndarray, exit_records: np.ndarray, gates, values=None, books=None) -> np.ndarray:
+    """sph_gates_step_host: the books (GATE_BOOKS_DTYPE, one row per gate) after one substep whose entry and exit records are given
+    (record i of both is the same particle), added in index order to a copy of `books` (None: zeros).  values: (n,) or (n, K) scalar
+    values after the substep, or None.  No device is needed."""
+    a, b = np.ascontiguousarray(entry, PARTICLE_DTYPE), np.ascontiguousarray(exit_records, PARTICLE_DTYPE)
+    if len(a) != len(b):
+        raise SphError("gates_step_host: entry and exit records differ in length")
+    arr = gate_array(gates)
+    v = None if values is None else _scalar_values(values, len(b))
+    k = 0 if v is None else v.shape[1]
+    out = np.zeros(max(len(arr), 1), GATE_BOOKS_DTYPE) if books is None else np.ascontiguousarray(books, GATE_BOOKS_DTYPE).copy()
+    if len(out) < len(arr):
+        raise SphError("gates_step_host: fewer book rows than gates")
+    _check(load_library().sph_gates_step_host(_ptr(a), _ptr(b), len(b), _ptr_or_none(arr), len(arr), None if not k else _ptr(v), k, _ptr(out)))
+    return out[:len(arr)] if books is None else out

@@ -545,6 +545,58 @@ public:
         hits.resize(size_t(count));
         return true;
     }
+    // Flow gates (engine extension, sph_abi.h "flow gates"): up to SPH_MAX_GATES oriented planar patches fixed in the
+    // world; every substep from now on books, on the device, what crosses each of them (counts, fp64 sums of velocity and scalar values),
+    // and with history > 0 stores the cumulative books every `stride` substeps in a ring.  An empty vector clears the table.  Gate() and
+    // GateBox() build the records (GateBox: six rectangles with outward normals, -x +x -y +y -z +z).  SetGates does not synchronise;
+    // GateBooks and GateHistory (rows oldest first, row k, gate i at rows[k * gates + i]) do.  Return false on error (LastError()).
+    static SphGate Gate(int shape, const float center[3], const float u[3], const float v[3], bool unbounded = false) {
+        SphGate g = SphGate();
+        g.shape = shape; g.flags = unbounded ? SPH_GATE_UNBOUNDED : 0;
+        for (int a = 0; a < 3; ++a) { g.center[a] = center[a]; g.u[a] = u[a]; g.v[a] = v[a]; }
+        return g;
+    }
+    static std::vector<SphGate> GateBox(const float center[3], const float half[3]) {
+        std::vector<SphGate> out;
+        for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, d = (a + 2) % 3;
+            for (int side = 0; side < 2; ++side) {
+                const float sign = side ? 1.0f : -1.0f;
+                float ce[3] = {center[0], center[1], center[2]}, u[3] = {0.0f, 0.0f, 0.0f}, v[3] = {0.0f, 0.0f, 0.0f};
+                ce[a] += sign * half[a];
+                u[b] = half[b]; v[d] = sign * half[d];                       // cross(e_b, e_d) = e_a
+                out.push_back(Gate(SPH_GATE_RECT, ce, u, v));
+            }
+        }
+        return out;
+    }
+    bool SetGates(const std::vector<SphGate>& gates, uint32_t history = 0, uint32_t stride = 1) {
+        return !Check(sph_gates_set(engine, gates.empty() ? nullptr : gates.data(), int(gates.size()), history, stride), "sph_gates_set");
+    }
+    bool GetGates(std::vector<SphGate>& out) {
+        int count = 0;
+        out.resize(SPH_MAX_GATES);
+        if (Check(sph_gates_get(engine, out.data(), SPH_MAX_GATES, &count, nullptr, nullptr), "sph_gates_get")) return false;
+        out.resize(size_t(count));
+        return true;
+    }
+    bool GateBooks(std::vector<SphGateBooks>& books, double& time, uint64_t& substeps, bool reset = false) {
+        int count = 0;
+        if (Check(sph_gates_get(engine, nullptr, 0, &count, nullptr, nullptr), "sph_gates_get")) return false;
+        books.assign(size_t(count), SphGateBooks());
+        return !Check(sph_gates_books(engine, books.empty() ? nullptr : books.data(), &time, &substeps, reset ? 1 : 0), "sph_gates_books");
+    }
+    bool GateHistory(std::vector<SphGateBooks>& rows, std::vector<double>& times, uint32_t& stored, uint64_t& firstRow) {
+        int count = 0;
+        uint32_t history = 0;
+        if (Check(sph_gates_get(engine, nullptr, 0, &count, &history, nullptr), "sph_gates_get")) return false;
+        rows.assign(size_t(history) * size_t(count), SphGateBooks());
+        times.assign(history, 0.0);
+        if (Check(sph_gates_history(engine, &firstRow, &stored, rows.empty() ? nullptr : rows.data(), times.empty() ? nullptr : times.data()), "sph_gates_history")) return false;
+        rows.resize(size_t(stored) * size_t(count));
+        times.resize(stored);
+        return true;
+    }
     // Kinematic solid obstacles (engine extension, sph_abi.h "obstacles"): up to SPH_MAX_OBSTACLES bodies whose
     // motion the caller prescribes; every substep keeps the fluid out of them, advances their poses on the device and sums, per body,
     // the impulse (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave it.  An empty vector drops the set.  SetObstacleMotion keeps the device's pose

@@ -45,6 +45,7 @@ extern "C" {
     _step_host, sph_volume_moments / _host -- dynamic rigid bodies) */
 /* (still 4, additions only: SphScalarSource, SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_*, sph_scalar_source_default, sph_scalars_set_buoyancy / _get_buoyancy /
     _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
+/* (still 4, additions only: SphGate, SphGateBooks, SPH_MAX_GATES, SPH_MAX_GATE_HISTORY, SPH_GATE_*, sph_gates_set / _get / _books / _history / _step_host -- flow gates) */
 /* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
 /* (still 4, additions only: SphDiffuseCrest, SphDiffuseCrestInfo, sph_diffuse_crest_default / _crest_info, sph_diffuse_set_crest / _get_crest,
@@ -739,6 +740,63 @@ int  sph_scalars_injected(SphEngine* e, double* sums, uint64_t* hits, int cap, d
 int  sph_scalars_couple_host(SphParticle* particles, size_t n, const SphParams* params, float dt, float* values, int channels,
                              const float* beta, const float* ref, const SphScalarSource* sources, int nSources,
                              const SphObstacle* obstacles, int nObstacles, double* sumsOut, uint64_t* hitsOut);
+
+/* ---- flow gates: what crosses a plane, counted inside the substep (no reference counterpart) ----------------
+ * A gate is an oriented planar patch fixed in the world: a rectangle or an ellipse with centre `center` and the half-extent vectors u
+ * and v (orthogonal, any length), or with SPH_GATE_UNBOUNDED its whole plane.  The forward normal is N = cross(u, v), per component a
+ * multiply, a multiply and a subtract, not normalised.  Off by default; with no gates set a dispatch launches exactly what it launched
+ * before.  One non-paused substep books, on its OUTPUT state, after the container, the obstacle step and the coupling step and before
+ * river / fountain (a recycled particle's jump is never a crossing), for every record with isGhost == 0 whose position is finite at the
+ * entry and at the exit of the substep (p0, p1), per gate, in fp32 with dot3(a, b) = fmaf(a_z, b_z, fmaf(a_y, b_y, a_x * b_x)):
+ *   side     s0 = dot3(p0 - center, N), s1 = dot3(p1 - center, N); forward: s0 < 0 && s1 >= 0; backward: s0 >= 0 && s1 < 0; else nothing
+ *   where    t = s0 / (s0 - s1); x_a = fmaf(t, p1_a - p0_a, p0_a); d = x - center; a = dot3(d, u); b = dot3(d, v);
+ *            rectangle: |a| < dot3(u, u) && |b| < dot3(v, v); ellipse: fa = a / dot3(u, u), fb = b / dot3(v, v), fmaf(fa, fa, fb * fb) < 1;
+ *            SPH_GATE_UNBOUNDED: always
+ *   books    per gate the forward and backward counts, the fp64 sums of +(double)v_a (forward) / -(double)v_a (backward) of the output
+ *            velocity, and of +-(double)c_k of the scalar channels after this substep's sources (a non-finite value adds 0, channels the
+ *            engine does not carry stay 0); with them the simulated time (fp64 sum of dt) and the substeps since the last zeroing.  No
+ *            float atomic: the sums depend on the slot order of the state only, the counts are exact.
+ *   history  every `stride` substeps (counted since the ring was last zeroed) the cumulative books of every gate and the time go into row
+ *            (substeps / stride - 1) mod history of a ring on the device: a long sph_dispatch_n or a replayed graph leaves a hydrograph.
+ * The step writes no particle state.  The table, the count, history and stride live in device memory: a replayed graph sees a later
+ * sph_gates_set; whether the step runs, and its buffers, enter a graph's key only while gates are set.  A set call with another count,
+ * history or stride zeroes books and ring, one with the same three keeps them.  sph_reset drops the gates, sph_destroy frees them.
+ * SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (no sorted copy); setting that option while gates exist makes the next dispatch
+ * fail and change nothing.  SPH_ERR_ARG (the previous state stays): a count above SPH_MAX_GATES, a null table with count > 0, an unknown
+ * shape or flag, a non-finite field, u or v of zero length, |u.v| > 1e-4 |u| |v| (in double), history above 4096, stride 0. */
+#define SPH_MAX_GATES 8
+#define SPH_MAX_GATE_HISTORY 4096
+enum { SPH_GATE_RECT = 0, SPH_GATE_ELLIPSE = 1 };
+enum { SPH_GATE_UNBOUNDED = 1 };
+typedef struct SphGate {   /* 64 bytes */
+    int32_t  shape;        /* SPH_GATE_RECT | SPH_GATE_ELLIPSE */
+    int32_t  flags;        /* SPH_GATE_UNBOUNDED */
+    float    center[3];
+    float    u[3];         /* half-extent vectors; forward is cross(u, v) */
+    float    v[3];
+    float    pad[5];
+} SphGate;
+typedef struct SphGateBooks {   /* 72 bytes */
+    uint64_t forward, backward;
+    double   vel[3];
+    double   scalar[4];    /* SPH_MAX_SCALAR_CHANNELS */
+} SphGateBooks;
+/* Replaces the gate table; count 0 clears it.  history: rows of the ring (0: none); stride >= 1.  Stream-ordered. */
+int  sph_gates_set(SphEngine* e, const SphGate* gates, int count, uint32_t history, uint32_t stride);
+/* The gates as set (cap >= count, else SPH_ERR_CAPACITY); any output pointer may be null. */
+int  sph_gates_get(SphEngine* e, SphGate* out, int cap, int* countOut, uint32_t* historyOut, uint32_t* strideOut);
+/* The books of the `count` gates, the simulated time and the substeps summed since the last zeroing; reset != 0 zeroes these (not the
+ * ring) after the read.  Any output pointer may be null.  Synchronises. */
+int  sph_gates_books(SphEngine* e, SphGateBooks* books, double* timeOut, uint64_t* substepsOut, int reset);
+/* The stored ring rows in chronological order: *countOut <= history rows of `count` books each (rows: room for history * count records)
+ * with their times (room for history), and the index of the first one (row i was taken after (first + i + 1) * stride substeps).
+ * Any output pointer may be null.  Synchronises. */
+int  sph_gates_history(SphEngine* e, uint64_t* firstOut, uint32_t* countOut, SphGateBooks* rows, double* times);
+/* Host-only, no device: the same __host__ __device__ functions the kernel runs on n records at the entry and at the exit of one substep
+ * (record i of both is the same particle), in index order, the sums added in index order INTO books[0 .. count-1].  values: n * channels
+ * floats (record i owns values[i * channels ..]) or NULL with channels 0. */
+int  sph_gates_step_host(const SphParticle* entry, const SphParticle* exitRecords, size_t n, const SphGate* gates, int count,
+                         const float* values, int channels, SphGateBooks* books);
 
 /* ---- spray, foam and bubbles: secondary particles spawned by the fluid (no reference counterpart) -----------
  * Secondary ("diffuse") particles in the sense of Ihmsen et al. 2012, reduced to what the engine's state supports: points that do not
