@@ -24,6 +24,11 @@ from .engine import (  # noqa: F401
     source_array, scalars_couple_host,
     SPH_MAX_GATES, SPH_MAX_GATE_HISTORY, SPH_GATE_RECT, SPH_GATE_ELLIPSE, SPH_GATE_UNBOUNDED, SphGate, SphGateBooks, GATE_DTYPE, GATE_BOOKS_DTYPE,
     gate, gate_box, gate_array, gate_discharge, gates_step_host,
+    SPH_MAX_MONITORS, SPH_MAX_MONITOR_POINTS, SPH_MAX_MONITOR_HISTORY, SPH_MONITOR_NONE, SPH_MONITOR_POINTS, SPH_MONITOR_LATTICE, SPH_MONITOR_FIELDS,
+    SPH_MONITOR_WET_SHARE, SPH_MONITOR_MEAN_FRACTION, SPH_MONITOR_VAR_FRACTION, SPH_MONITOR_MEAN_DENSITY, SPH_MONITOR_MEAN_PRESSURE,
+    SPH_MONITOR_VAR_PRESSURE, SPH_MONITOR_MEAN_VEL_X, SPH_MONITOR_MEAN_VEL_Y, SPH_MONITOR_MEAN_VEL_Z, SPH_MONITOR_TKE,
+    SphMonitorConfig, SphMonitorRow, SphMonitorInfo, MONITOR_ROW_DTYPE, monitor_config, monitor_accumulate_host, monitor_field_host,
+    monitor_schedule_host, monitor_means,
     SPH_OPT_DIFFUSE_TIMED, SPH_DIFFUSE_SPRAY, SPH_DIFFUSE_FOAM, SPH_DIFFUSE_BUBBLE, SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, DIFFUSE_DTYPE, diffuse_config,
     diffuse_step_host, write_points_ply, SphDiffuseCrest, SphDiffuseCrestInfo, diffuse_crest_config,
     SPH_OPT_NEIGHBORS_FILL, SPH_NEIGHBORS_SELF, SPH_NEIGHBORS_HALF, SPH_NEIGHBORS_COUNT_ONLY, SphNeighborInfo, neighbors_host,

@@ -39,6 +39,7 @@
 #include "sph_stats.h"
 #include "sph_couple.h"
 #include "sph_gate.h"
+#include "sph_monitor.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
@@ -52,6 +53,9 @@ static_assert(sizeof(SphScalarSource) == sizeof(sph::CoupleSrc) && SPH_MAX_SCALA
 static_assert(sizeof(SphGate) == sizeof(sph::GateRec) && sizeof(SphGateBooks) == 8 * sph::kGateWords && SPH_MAX_GATES == sph::kGateMax &&
               SPH_MAX_GATE_HISTORY == sph::kGateHistoryMax && SPH_GATE_RECT == sph::GATE_RECT && SPH_GATE_ELLIPSE == sph::GATE_ELLIPSE &&
               SPH_GATE_UNBOUNDED == sph::GATE_UNBOUNDED && SPH_MAX_SCALAR_CHANNELS == sph::kGateChannels, "SphGate must be 64 bytes, SphGateBooks 72");
+static_assert(sizeof(SphMonitorRow) == sizeof(sph::MonitorRow) && offsetof(SphMonitorRow, sumVelVel) == offsetof(sph::MonitorRow, sumVelVel) &&
+              sizeof(SphMonitorConfig) == 24 && sizeof(SphMonitorInfo) == 112 && SPH_MAX_MONITORS == sph::kMonitorMax && SPH_MONITOR_TKE == sph::kMonTke &&
+              SPH_MONITOR_WET_SHARE == sph::kMonWetShare && SPH_MONITOR_VAR_PRESSURE == sph::kMonVarPressure, "SphMonitorRow must be 128 bytes");
 static_assert(sizeof(SphObstacle) == 76 && SPH_MAX_OBSTACLES == sph::kObsMax, "SphObstacle must be 76 bytes");
 static_assert(sizeof(SphObstacleDynamics) == 80, "SphObstacleDynamics must be 80 bytes");
 static_assert(SPH_MAX_VOLUMES == sph::kVolMax && SPH_MAX_OBSTACLES == sph::kVolBodies && sizeof(SphVolumeHost) == 32, "SphVolumeHost must be 32 bytes");
@@ -151,6 +155,24 @@ struct ScanScratch {
         return rc ? rc : tileMax.grow(e, tiles);
     }
     void release() { tileSums.release(); tileMax.release(); }
+};
+
+// One field monitor (sph_monitor.h): the table the kernels read (device memory: a replayed graph sees a later set or
+// reset) with the table as uploaded last and its pinned staging, the points and their processing order (explicit points only), the rows,
+// the ring of history x ringPoints samples (two float4 each) and its history times.  Buffers only grow while the slot lives.
+struct MonitorSlot {
+    int kind = SPH_MONITOR_NONE;
+    size_t m = 0;
+    int dims[3] = {0, 0, 0};
+    float origin[3] = {0.0f, 0.0f, 0.0f}, spacing[3] = {0.0f, 0.0f, 0.0f};
+    SphMonitorConfig cfg{};
+    sph::MonitorTab* d_tab = nullptr;
+    sph::MonitorTab tab{};
+    StageRing<sph::MonitorTab> stage;
+    DevBuf<float4> d_points, d_ring;
+    DevBuf<uint32_t> d_perm;
+    DevBuf<sph::MonitorRow> d_rows;
+    DevBuf<double> d_times;
 };
 
 }  // namespace
@@ -415,6 +437,10 @@ struct SphEngine {
     SphGate gtSet[sph::kGateMax] = {};
     uint32_t gtRingCap = 0;
 
+    // sph_monitor_*: the slots, and how many of them hold a monitor (0: nothing is launched, nothing enters a graph's key)
+    MonitorSlot mon[sph::kMonitorMax];
+    int monCount = 0;
+
     // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
     // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
     sph::ObsRec* d_obs = nullptr;
@@ -634,6 +660,22 @@ void gates_free(SphEngine* e) {
     e->gtStage.destroy();
     e->gtTab = sph::GateTab{};
     e->gtRingCap = 0;
+}
+
+void monitor_free(SphEngine* e, int slot) {
+    MonitorSlot& s = e->mon[slot];
+    if (s.d_tab && e->stream) (void)hipStreamSynchronize(e->stream);
+    dev_free(s.d_tab);
+    s.stage.destroy();
+    s.d_points.release(); s.d_ring.release(); s.d_perm.release(); s.d_rows.release(); s.d_times.release();
+    if (s.kind != SPH_MONITOR_NONE) e->monCount -= 1;
+    s.kind = SPH_MONITOR_NONE; s.m = 0;
+    s.dims[0] = s.dims[1] = s.dims[2] = 0;
+    s.cfg = SphMonitorConfig{};
+    s.tab = sph::MonitorTab{};
+}
+void monitors_free(SphEngine* e) {
+    for (int i = 0; i < sph::kMonitorMax; ++i) monitor_free(e, i);
 }
 
 void obstacles_free(SphEngine* e) {
@@ -1176,6 +1218,26 @@ int gates_step(SphEngine* e, const float4* pos, const float4* vel, int n, float 
     return SPH_OK;
 }
 
+// ---- field monitors (sph_monitor.h) ---------------------------------------------------------------------
+// One substep's monitor work, behind build_grid of that substep: per slot the sampling launch (it returns at once in a non-acting
+// substep: the decision is in device memory) and the one-thread tick.  It writes no particle state.
+int monitors_step(SphEngine* e, const SimK& k, float dt) {
+    for (int i = 0; i < kMonitorMax; ++i) {
+        MonitorSlot& s = e->mon[i];
+        if (s.kind == SPH_MONITOR_NONE) continue;
+        Timed t(e, SPH_K_OTHER);
+        if (s.kind == SPH_MONITOR_POINTS)
+            hipLaunchKernelGGL(k_monitor_points, dim3(blocks_for(s.m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                               (const MonitorTab*)s.d_tab, (const float4*)s.d_points.p, (const uint32_t*)s.d_perm.p, s.d_rows.p, s.d_ring.p, (uint32_t)s.m);
+        else
+            hipLaunchKernelGGL(k_monitor_lattice, dim3((unsigned)std::min<long long>(s.tab.L.nBricks, 1ll << 20)), dim3(kBlock), 0, e->stream, k,
+                               (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const MonitorTab*)s.d_tab, s.d_rows.p, s.d_ring.p);
+        hipLaunchKernelGGL(k_monitor_tick, dim3(1), dim3(64), 0, e->stream, s.d_tab, s.d_times.p, dt);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
 int writeback(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "a slab engine has no local 80-byte array: use sph_slab_download");
     if (e->aosValid) return SPH_OK;
@@ -1226,6 +1288,8 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if (e->gtTab.count && e->optGridBuild == 1)
         return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (e->monCount && e->optGridBuild == 1)
+        return fail(SPH_ERR_STATE, "monitors need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     if ((rc = validate_params(e->params)) || (rc = couple_refused(e))) return rc;
     float cont[15];
     container_key(e->params, cont);
@@ -1279,6 +1343,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     } else {
     if ((rc = build_grid(e, k, true))) return rc;                           // :449-468
     if (e->trM && (rc = tracers_advect(e, k, dt))) return rc;               // (reads the sorted copy and cellStart, as the SPH pass does)
+    if (e->monCount && (rc = monitors_step(e, k, dt))) return rc;           // (the same two; DESIGN.md section 3s: a probe of the entry state)
     if (e->dfC && (rc = diffuse_step(e, k, dt, (uint32_t)n))) return rc;    // (the same two, and the sorted own data)
     if (e->scK && (rc = scalars_step(e, k, dt))) return rc;                 // (the same two, and the sorted own data)
     if (n) {                                                                // :470-509 (SPH + OBB fused)
@@ -1547,6 +1612,7 @@ int sph_destroy(SphEngine* e) {
     diffuse_free(e);
     scalars_free(e);
     gates_free(e);
+    monitors_free(e);
     obstacles_free(e);
     volumes_free(e);
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -1588,6 +1654,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
     gates_free(e);                                                    // (and the flow gates)
+    monitors_free(e);                                                 // (and every field monitor)
     if (e->d_obsAcc) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (obstacles: the set and the poses stay, the sums restart)
     std::vector<SphParticle> v;
     float m;
@@ -1738,6 +1805,16 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
         const void* gt[4] = {e->d_gtTab, e->d_gtAcc, e->d_gtPart.p, e->d_gtRing.p};
         add(gt, sizeof(gt));
         add(&e->gtRingCap, sizeof(e->gtRingCap));
+    }
+    // field monitors, only while one is set (off: the material of before): per slot the kind, M, a lattice's dims (the launch grid), the
+    // buffers and the ring layout; every, stride, the counters, wetFraction, a lattice's origin and spacing are read from memory
+    if (e->monCount) {
+        for (const MonitorSlot& s : e->mon) {
+            const void* mo[6] = {s.d_tab, s.d_points.p, s.d_perm.p, s.d_rows.p, s.d_ring.p, s.d_times.p};
+            add(mo, sizeof(mo));
+            const uint64_t mv[7] = {(uint64_t)s.kind, (uint64_t)s.m, (uint64_t)s.dims[0], (uint64_t)s.dims[1], (uint64_t)s.dims[2], s.tab.history, s.tab.ringPoints};
+            add(mv, sizeof(mv));
+        }
     }
     return m;
 }
@@ -5883,6 +5960,286 @@ int sph_gates_step_host(const SphParticle* entry, const SphParticle* exitRecords
                 B.scalar[k] += sph::float_finite(cv) ? sg * (double)cv : 0.0;
             }
         }
+    }
+    return SPH_OK;
+}
+
+// ---- field monitors (sph_monitor.h) ----------------------------------------
+void sph_monitor_config_default(SphMonitorConfig* out) {
+    if (!out) return;
+    *out = SphMonitorConfig{};
+    out->every = 1u; out->wetFraction = 0.5f; out->history = 0u; out->stride = 1u; out->ringPoints = 0u;
+}
+static constexpr size_t kMonitorRingBytes = (size_t)256 << 20;
+// The refusals every set call opens with, in the order of the gates: the engine's state before anything else, then the arguments.
+static int monitor_refused(const SphEngine* e) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "monitors on a z-slab engine are not supported: its halo records after a step are the step's entry state");
+    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "monitors need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    return SPH_OK;
+}
+static int monitor_slot_check(int slot) {
+    if (slot < 0 || slot >= SPH_MAX_MONITORS) return fail(SPH_ERR_ARG, "monitor slot %d outside 0..%d", slot, SPH_MAX_MONITORS - 1);
+    return SPH_OK;
+}
+// The config against M points: *cfg is the config in force (NULL: the defaults; ringPoints 0 with a history: min(M, 64)).
+static int monitor_config_check(const SphMonitorConfig* in, size_t m, SphMonitorConfig* cfg) {
+    if (in) *cfg = *in; else sph_monitor_config_default(cfg);
+    cfg->pad = 0u;
+    if (cfg->every == 0u || cfg->stride == 0u) return fail(SPH_ERR_ARG, "every and stride must be >= 1");
+    if (cfg->history > SPH_MAX_MONITOR_HISTORY) return fail(SPH_ERR_ARG, "history %u above %d", cfg->history, SPH_MAX_MONITOR_HISTORY);
+    if (cfg->ringPoints > m) return fail(SPH_ERR_ARG, "ringPoints %u above the %zu points", cfg->ringPoints, m);
+    if (!std::isfinite(cfg->wetFraction)) return fail(SPH_ERR_ARG, "wetFraction is not finite");
+    if (cfg->history && !cfg->ringPoints) cfg->ringPoints = (uint32_t)std::min<size_t>(m, 64);
+    if (!cfg->history) cfg->ringPoints = 0u;
+    if ((size_t)cfg->history * cfg->ringPoints * sizeof(SphSample) > kMonitorRingBytes)
+        return fail(SPH_ERR_ARG, "a ring of %u rows of %u samples exceeds 256 MiB", cfg->history, cfg->ringPoints);
+    return SPH_OK;
+}
+// The table a set or a reset uploads: counters at zero, the first substep acts.
+static sph::MonitorTab monitor_fresh_tab(const SphMonitorConfig& cfg, const sph::LatticeK& L) {
+    sph::MonitorTab t{};
+    t.every = cfg.every; t.stride = cfg.stride; t.history = cfg.history; t.ringPoints = cfg.ringPoints;
+    t.wetFraction = cfg.wetFraction;
+    t.act = 1u;
+    t.row = sph::monitor_row_of(0ull, cfg.history, cfg.stride);
+    t.L = L;
+    return t;
+}
+// Rows, ring and times to zero and the fresh table to the device, stream-ordered (the table through the next pinned staging slot).
+static int monitor_restart(SphEngine* e, MonitorSlot& s) {
+    int rc;
+    HIP_TRY(hipMemsetAsync(s.d_rows.p, 0, s.m * sizeof(sph::MonitorRow), e->stream));
+    if (s.tab.history) {
+        HIP_TRY(hipMemsetAsync(s.d_ring.p, 0, (size_t)s.tab.history * s.tab.ringPoints * 2 * sizeof(float4), e->stream));
+        HIP_TRY(hipMemsetAsync(s.d_times.p, 0, (size_t)s.tab.history * sizeof(double), e->stream));
+    }
+    sph::MonitorTab* slot = nullptr;
+    if ((rc = s.stage.next(&slot))) return rc;
+    *slot = s.tab;
+    HIP_TRY(hipMemcpyAsync(s.d_tab, slot, sizeof(sph::MonitorTab), hipMemcpyHostToDevice, e->stream));
+    return s.stage.commit(e->stream);
+}
+// The buffers of a slot about to hold `m` points of `kind` under cfg (arguments already checked).  A slot that keeps kind, M and ring
+// layout keeps every buffer, and the graphs captured over them.
+static int monitor_ensure(SphEngine* e, int slot, int kind, size_t m, const SphMonitorConfig& cfg) {
+    MonitorSlot& s = e->mon[slot];
+    int rc;
+    if (!s.d_tab) {
+        hipError_t er = hipSuccess;
+        if ((rc = dev_alloc(&s.d_tab, 1)) || (er = s.stage.create(e->stream, 1)) != hipSuccess) {
+            monitor_free(e, slot);
+            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the monitor table: %s", hipGetErrorString(er));
+        }
+    }
+    const size_t ring = std::max<size_t>((size_t)cfg.history * cfg.ringPoints * 2, 1);
+    if ((rc = s.d_rows.grow(e, m)) || (rc = s.d_ring.grow(e, ring)) || (rc = s.d_times.grow(e, std::max<size_t>(cfg.history, 1))) ||
+        (kind == SPH_MONITOR_POINTS && ((rc = s.d_points.grow(e, m)) || (rc = s.d_perm.grow(e, m))))) {
+        monitor_free(e, slot);
+        return rc;
+    }
+    return SPH_OK;
+}
+// The slot's host record after a successful set, then the restart.
+static int monitor_commit(SphEngine* e, int slot, int kind, size_t m, const int dims[3], const float origin[3], const float spacing[3],
+                          const SphMonitorConfig& cfg, const sph::LatticeK& L) {
+    MonitorSlot& s = e->mon[slot];
+    if (s.kind == SPH_MONITOR_NONE) e->monCount += 1;
+    s.kind = kind; s.m = m; s.cfg = cfg;
+    for (int a = 0; a < 3; ++a) { s.dims[a] = dims[a]; s.origin[a] = origin[a]; s.spacing[a] = spacing[a]; }
+    s.tab = monitor_fresh_tab(cfg, L);
+    return monitor_restart(e, s);
+}
+// The processing order of explicit points: sorted by the cell of the grid in force at set time (speed only; the points never move).
+static void monitor_order(const SphEngine* e, const float4* pts, size_t m, std::vector<uint32_t>& perm) {
+    SphGridInfo g{};
+    sph::compute_grid_extents(e->params, g);
+    perm.resize(m);
+    for (size_t i = 0; i < m; ++i) perm[i] = (uint32_t)i;
+    if (!(g.cellSize > 0.0f) || !std::isfinite(g.cellSize)) return;
+    std::vector<uint32_t> cell(m);
+    for (size_t i = 0; i < m; ++i) {
+        const float p[3] = {pts[i].x, pts[i].y, pts[i].z};
+        int c[3];
+        for (int a = 0; a < 3; ++a) {
+            const float f = std::floor((p[a] - g.gridMin[a]) / g.cellSize);
+            c[a] = !(f >= 0.0f) ? 0 : (f >= (float)(g.dims[a] - 1) ? std::max(g.dims[a] - 1, 0) : (int)f);
+        }
+        cell[i] = (uint32_t)((c[2] * g.dims[1] + c[1]) * g.dims[0] + c[0]);
+    }
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return cell[a] < cell[b]; });
+}
+static int monitor_set_points(SphEngine* e, int slot, const float* points4, size_t m, const SphMonitorConfig* config, bool onDevice) {
+    int rc;
+    SphMonitorConfig cfg;
+    if ((rc = monitor_refused(e)) || (rc = monitor_slot_check(slot))) return rc;
+    if (m && !points4) return fail(SPH_ERR_ARG, "null argument");
+    if (m > (size_t)SPH_MAX_MONITOR_POINTS) return fail(SPH_ERR_ARG, "%zu monitor points exceed %d", m, SPH_MAX_MONITOR_POINTS);
+    if ((rc = monitor_config_check(config, m ? m : 1, &cfg))) return rc;
+    if (m == 0) { monitor_free(e, slot); return SPH_OK; }
+    std::vector<float4> host(m);
+    if (onDevice) {                                                    // (the order is made on the host: a set call is rare)
+        HIP_TRY(hipMemcpyAsync(host.data(), points4, m * sizeof(float4), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+        std::memcpy(host.data(), points4, m * sizeof(float4));
+    }
+    std::vector<uint32_t> perm;
+    monitor_order(e, host.data(), m, perm);
+    if ((rc = monitor_ensure(e, slot, SPH_MONITOR_POINTS, m, cfg))) return rc;
+    MonitorSlot& s = e->mon[slot];
+    HIP_TRY(hipMemcpyAsync(s.d_points.p, host.data(), m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s.d_perm.p, perm.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    const int dims[3] = {(int)m, 1, 1};
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    rc = monitor_commit(e, slot, SPH_MONITOR_POINTS, m, dims, zero, zero, cfg, sph::LatticeK{});
+    HIP_TRY(hipStreamSynchronize(e->stream));                          // (the two vectors are pageable memory)
+    return rc;
+}
+int sph_monitor_set(SphEngine* e, int slot, const float* points4, size_t m, const SphMonitorConfig* config) {
+    return monitor_set_points(e, slot, points4, m, config, false);
+}
+int sph_monitor_set_device(SphEngine* e, int slot, const float* devPoints4, size_t m, const SphMonitorConfig* config) {
+    return monitor_set_points(e, slot, devPoints4, m, config, true);
+}
+int sph_monitor_set_lattice(SphEngine* e, int slot, const float origin[3], const float spacing[3], const int dims[3], const SphMonitorConfig* config) {
+    int rc;
+    SphMonitorConfig cfg;
+    long long total = 0;
+    if ((rc = monitor_refused(e)) || (rc = monitor_slot_check(slot))) return rc;
+    if (!origin || !spacing || !dims) return fail(SPH_ERR_ARG, "null argument");
+    if ((rc = check_lattice(dims, spacing, 1, &total))) return rc;
+    if (total > (long long)SPH_MAX_MONITOR_POINTS) return fail(SPH_ERR_ARG, "a lattice of %lld monitor points exceeds %d", total, SPH_MAX_MONITOR_POINTS);
+    if (!obs_all_finite(origin, 3)) return fail(SPH_ERR_ARG, "the lattice origin is not finite");
+    if ((rc = monitor_config_check(config, (size_t)total, &cfg))) return rc;
+    if ((rc = monitor_ensure(e, slot, SPH_MONITOR_LATTICE, (size_t)total, cfg))) return rc;
+    return monitor_commit(e, slot, SPH_MONITOR_LATTICE, (size_t)total, dims, origin, spacing, cfg, lattice_consts(origin, spacing, dims, SPH_FIELD_ALL, kSampleStage));
+}
+// The device's counters of a slot that holds a monitor.  Synchronises.
+static int monitor_counters(SphEngine* e, const MonitorSlot& s, sph::MonitorTab* out) {
+    HIP_TRY(hipMemcpyAsync(out, s.d_tab, sizeof(sph::MonitorTab), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+// Ring rows written by `a` acting substeps, and how many of them the ring still holds.
+static void monitor_ring_span(const sph::MonitorTab& t, uint64_t* first, uint32_t* have) {
+    const uint64_t taken = t.history ? (t.a + t.stride - 1) / t.stride : 0;
+    *have = (uint32_t)std::min<uint64_t>(taken, t.history);
+    *first = taken - *have;
+}
+int sph_monitor_info(SphEngine* e, int slot, SphMonitorInfo* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    std::memset(out, 0, sizeof(*out));
+    const MonitorSlot& s = e->mon[slot];
+    if (s.kind == SPH_MONITOR_NONE) return SPH_OK;
+    sph::MonitorTab t;
+    if ((rc = monitor_counters(e, s, &t))) return rc;
+    out->kind = s.kind; out->points = s.m; out->config = s.cfg;
+    for (int a = 0; a < 3; ++a) { out->dims[a] = s.dims[a]; out->origin[a] = s.origin[a]; out->spacing[a] = s.spacing[a]; }
+    out->substeps = t.c; out->acting = t.a; out->time = t.time;
+    uint64_t first; uint32_t have;
+    monitor_ring_span(t, &first, &have);
+    out->firstRow = first; out->ringRows = have;
+    return SPH_OK;
+}
+int sph_monitor_download(SphEngine* e, int slot, SphMonitorRow* out, size_t cap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    const MonitorSlot& s = e->mon[slot];
+    if (cap < s.m) return fail(SPH_ERR_CAPACITY, "%zu monitor rows (capacity %zu)", s.m, cap);
+    if (s.m && !out) return fail(SPH_ERR_ARG, "null argument");
+    if (s.m) HIP_TRY(hipMemcpyAsync(out, s.d_rows.p, s.m * sizeof(SphMonitorRow), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+int sph_monitor_device(SphEngine* e, int slot, const SphMonitorRow** devPtr) {
+    if (!e || !devPtr) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    *devPtr = e->mon[slot].kind != SPH_MONITOR_NONE ? reinterpret_cast<const SphMonitorRow*>(e->mon[slot].d_rows.p) : nullptr;
+    return SPH_OK;
+}
+int sph_monitor_history(SphEngine* e, int slot, uint64_t* firstOut, uint32_t* countOut, SphSample* samples, double* times, size_t rowCap) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    const MonitorSlot& s = e->mon[slot];
+    uint64_t first = 0; uint32_t have = 0;
+    if (s.kind != SPH_MONITOR_NONE && s.tab.history) {
+        sph::MonitorTab t;
+        if ((rc = monitor_counters(e, s, &t))) return rc;
+        monitor_ring_span(t, &first, &have);
+        if ((samples || times) && rowCap < have) return fail(SPH_ERR_CAPACITY, "%u ring rows (capacity %zu)", have, rowCap);
+        const size_t rowBytes = (size_t)t.ringPoints * sizeof(SphSample);
+        for (uint32_t i = 0; i < have; ++i) {                          // (oldest first: the ring's rows in chronological order)
+            const size_t r = (size_t)((first + i) % t.history);
+            if (samples) HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(samples) + i * rowBytes, reinterpret_cast<const char*>(s.d_ring.p) + r * rowBytes, rowBytes, hipMemcpyDeviceToHost, e->stream));
+            if (times) HIP_TRY(hipMemcpyAsync(times + i, s.d_times.p + r, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    if (firstOut) *firstOut = first;
+    if (countOut) *countOut = have;
+    return SPH_OK;
+}
+int sph_monitor_field(SphEngine* e, int slot, int field, float* devOut) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    if (field < 0 || field >= sph::kMonFields) return fail(SPH_ERR_ARG, "unknown monitor field %d", field);
+    const MonitorSlot& s = e->mon[slot];
+    if (s.kind == SPH_MONITOR_NONE) return fail(SPH_ERR_STATE, "no monitor in slot %d", slot);
+    if (!devOut) return fail(SPH_ERR_ARG, "null argument");
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_monitor_field, dim3(blocks_for(s.m)), dim3(kBlock), 0, e->stream, (const sph::MonitorRow*)s.d_rows.p, field, devOut, s.m);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+int sph_monitor_reset(SphEngine* e, int slot) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = monitor_slot_check(slot))) return rc;
+    MonitorSlot& s = e->mon[slot];
+    if (s.kind == SPH_MONITOR_NONE) return fail(SPH_ERR_STATE, "no monitor in slot %d", slot);
+    return monitor_restart(e, s);                                      // (s.tab is the table of the last set: counters at zero)
+}
+int sph_monitor_clear(SphEngine* e, int slot) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (slot >= SPH_MAX_MONITORS) return monitor_slot_check(slot);
+    if (slot < 0) monitors_free(e); else monitor_free(e, slot);
+    return SPH_OK;
+}
+int sph_monitor_accumulate_host(SphMonitorRow* rows, const SphSample* samples, size_t m, float wetFraction) {
+    if (m && (!rows || !samples)) return fail(SPH_ERR_ARG, "null argument");
+    if (!std::isfinite(wetFraction)) return fail(SPH_ERR_ARG, "wetFraction is not finite");
+    for (size_t i = 0; i < m; ++i) {
+        const SphSample& q = samples[i];
+        (void)sph::monitor_update(*reinterpret_cast<sph::MonitorRow*>(rows + i), q.density, q.fraction, q.pressure, q.vel[0], q.vel[1], q.vel[2], wetFraction);
+    }
+    return SPH_OK;
+}
+int sph_monitor_field_host(const SphMonitorRow* rows, size_t m, int field, float* out) {
+    if (m && (!rows || !out)) return fail(SPH_ERR_ARG, "null argument");
+    if (field < 0 || field >= sph::kMonFields) return fail(SPH_ERR_ARG, "unknown monitor field %d", field);
+    for (size_t i = 0; i < m; ++i) out[i] = sph::monitor_field_value(*reinterpret_cast<const sph::MonitorRow*>(rows + i), field);
+    return SPH_OK;
+}
+int sph_monitor_schedule_host(uint32_t every, uint32_t stride, uint32_t history, size_t substeps, uint32_t* actsOut, uint32_t* rowsOut) {
+    if (substeps && (!actsOut || !rowsOut)) return fail(SPH_ERR_ARG, "null argument");
+    if (every == 0u || stride == 0u) return fail(SPH_ERR_ARG, "every and stride must be >= 1");
+    if (history > SPH_MAX_MONITOR_HISTORY) return fail(SPH_ERR_ARG, "history %u above %d", history, SPH_MAX_MONITOR_HISTORY);
+    SphMonitorConfig cfg{};
+    cfg.every = every; cfg.stride = stride; cfg.history = history; cfg.ringPoints = history ? 1u : 0u;
+    sph::MonitorTab t = monitor_fresh_tab(cfg, sph::LatticeK{});
+    for (size_t i = 0; i < substeps; ++i) {
+        bool acted;
+        rowsOut[i] = sph::monitor_tick(t, 0.0, &acted);
+        actsOut[i] = acted ? 1u : 0u;
     }
     return SPH_OK;
 }

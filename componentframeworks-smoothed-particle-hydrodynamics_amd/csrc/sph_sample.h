@@ -16,6 +16,8 @@
 //                     stages the row runs of the brick's cell range +-1 into LDS once (16 bytes per record, 32 when
 //                     velocity or pressure is asked for) and walks them from there; a brick whose rows do not fit
 //                     walks global memory instead.  Same candidate function, same order, therefore the same bits.
+//                     The brick walk hands each point's sample to a sink: this kernel stores it, k_monitor_lattice
+//                     (sph_monitor.h) accumulates it.
 #pragma once
 #include "sph_kernels.h"
 
@@ -98,6 +100,28 @@ __device__ __forceinline__ SampleAcc sample_global(const SimK& k, const float4* 
     return a;
 }
 
+// sample_global's walk with the loads of AHEAD candidates issued together: a lane's walk is a chain of dependent cache misses
+// otherwise.  The candidates are accumulated in the same order, so the bits are sample_global's (tracers, monitors).
+template <int AHEAD>
+__device__ __forceinline__ SampleAcc sample_ahead(const SimK& k, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
+                                                  float x, float y, float z) {
+    SampleAcc a;
+    sample_reset(a);
+    const int3 cell = cell_of(k, x, y, z);
+    sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
+        uint32_t q = qs;
+        for (; q + (uint32_t)AHEAD <= qe; q += (uint32_t)AHEAD) {
+            float4 J[AHEAD], V[AHEAD];
+#pragma unroll
+            for (int u = 0; u < AHEAD; ++u) { J[u] = pv[2u * (q + (uint32_t)u)]; V[u] = pv[2u * (q + (uint32_t)u) + 1u]; }
+#pragma unroll
+            for (int u = 0; u < AHEAD; ++u) sample_candidate<true>(k, x, y, z, J[u], V[u], a);
+        }
+        for (; q < qe; ++q) sample_candidate<true>(k, x, y, z, pv[2u * q], pv[2u * q + 1u], a);
+    });
+    return a;
+}
+
 __device__ __forceinline__ void sample_store(void* out, size_t idx, int field, const SampleOut& o) {
     if (field == kFieldAll) {
         float4* d = reinterpret_cast<float4*>(out) + 2 * idx;
@@ -144,9 +168,10 @@ struct LatticeK {
 
 __device__ __forceinline__ float lattice_coord(float o, int i, float s) { return o + (float)i * s; }   // a multiply, then an add (no fma: -ffp-contract=off)
 
-template <bool VEL>
+// sink(point index (x fastest), SampleOut): what becomes of a point's sample (k_sample_lattice stores it, a monitor accumulates it).
+template <bool VEL, class SINK>
 __device__ __forceinline__ void lattice_brick(const SimK& k, const LatticeK& L, const float4* __restrict__ pv, const uint32_t* __restrict__ cellStart,
-                                              void* __restrict__ out, long long b, float4* st, uint32_t* rowQs, uint32_t* rowOff, int* meta) {
+                                              SINK&& sink, long long b, float4* st, uint32_t* rowQs, uint32_t* rowOff, int* meta) {
     constexpr int recF4 = VEL ? 2 : 1;
     const int tid = threadIdx.x;
     const int bx = (int)(b % L.nbx), by = (int)((b / L.nbx) % L.nby), bz = (int)(b / ((long long)L.nbx * L.nby));
@@ -235,7 +260,7 @@ __device__ __forceinline__ void lattice_brick(const SimK& k, const LatticeK& L, 
             }
             o = sample_finish(k, a);
         }
-        sample_store(out, ((size_t)l * (size_t)L.dy + (size_t)j) * (size_t)L.dx + (size_t)i, L.field, o);
+        sink(((size_t)l * (size_t)L.dy + (size_t)j) * (size_t)L.dx + (size_t)i, o);
     }
     __syncthreads();                                                   // LDS is reused by the next brick
 }
@@ -246,9 +271,10 @@ __global__ __launch_bounds__(kBlock) void k_sample_lattice(SimK k, LatticeK L, c
     __shared__ uint32_t rowQs[kStageRows], rowOff[kStageRows + 1];
     __shared__ int meta[8];
     const bool vel = L.field != kFieldDensity && L.field != kFieldFraction;
+    auto store = [&](size_t idx, const SampleOut& o) { sample_store(out, idx, L.field, o); };
     for (long long b = blockIdx.x; b < L.nBricks; b += gridDim.x) {
-        if (vel) lattice_brick<true>(k, L, pv, cellStart, out, b, st, rowQs, rowOff, meta);
-        else lattice_brick<false>(k, L, pv, cellStart, out, b, st, rowQs, rowOff, meta);
+        if (vel) lattice_brick<true>(k, L, pv, cellStart, store, b, st, rowQs, rowOff, meta);
+        else lattice_brick<false>(k, L, pv, cellStart, store, b, st, rowQs, rowOff, meta);
     }
 }
 

@@ -48,23 +48,8 @@ __device__ __forceinline__ SampleOut tracer_field(const SimK& k, const float4* _
                                                   float x, float y, float z) {
     SampleOut o{};
     if (!sample_finite(x, y, z)) return o;
-    SampleAcc a;
-    sample_reset(a);
-    const int3 cell = cell_of(k, x, y, z);
-    // sample_global's walk with the loads of kTracerAhead candidates issued together: a lane's walk is a chain of dependent cache
-    // misses otherwise.  The candidates are accumulated in the same order, so the bits are sample_global's.
-    sample_rows(k, cellStart, cell.x, cell.y, cell.z, [&](int, int, uint32_t qs, uint32_t qe) {
-        uint32_t q = qs;
-        for (; q + (uint32_t)kTracerAhead <= qe; q += (uint32_t)kTracerAhead) {
-            float4 J[kTracerAhead], V[kTracerAhead];
-#pragma unroll
-            for (int u = 0; u < kTracerAhead; ++u) { J[u] = pv[2u * (q + (uint32_t)u)]; V[u] = pv[2u * (q + (uint32_t)u) + 1u]; }
-#pragma unroll
-            for (int u = 0; u < kTracerAhead; ++u) sample_candidate<true>(k, x, y, z, J[u], V[u], a);
-        }
-        for (; q < qe; ++q) sample_candidate<true>(k, x, y, z, pv[2u * q], pv[2u * q + 1u], a);
-    });
-    return sample_finish(k, a);
+    // (sample_ahead of sph_sample.h: the loads of kTracerAhead candidates in flight at once, the bits of sample_global)
+    return sample_finish(k, sample_ahead<kTracerAhead>(k, pv, cellStart, x, y, z));
 }
 
 template <bool MIDPOINT>

@@ -286,6 +286,37 @@ SPH_GATE_RECT, SPH_GATE_ELLIPSE = 0, 1
 SPH_GATE_UNBOUNDED = 1
 
 
+class SphMonitorConfig(C.Structure):
+    """struct SphMonitorConfig of include/sph_abi.h: how a field monitor samples (monitor_config() fills one)."""
+    _fields_ = [("every", C.c_uint32), ("wetFraction", C.c_float), ("history", C.c_uint32), ("stride", C.c_uint32), ("ringPoints", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class SphMonitorRow(C.Structure):
+    """struct SphMonitorRow: the running sums of one monitor point."""
+    _fields_ = [("samples", C.c_uint64), ("wet", C.c_uint64), ("sumFraction", C.c_double), ("sumFraction2", C.c_double), ("sumDensity", C.c_double),
+                ("sumPressure", C.c_double), ("sumPressure2", C.c_double), ("sumVel", C.c_double * 3), ("sumVelVel", C.c_double * 6)]
+
+
+class SphMonitorInfo(C.Structure):
+    """struct SphMonitorInfo: what a monitor slot holds, with the device's counters (see SPHFluidGPU.monitor_info)."""
+    _fields_ = [("kind", C.c_int32), ("dims", C.c_int32 * 3), ("points", C.c_uint64), ("config", SphMonitorConfig), ("substeps", C.c_uint64),
+                ("acting", C.c_uint64), ("time", C.c_double), ("firstRow", C.c_uint64), ("ringRows", C.c_uint32), ("pad", C.c_uint32),
+                ("origin", C.c_float * 3), ("spacing", C.c_float * 3)]
+
+
+assert C.sizeof(SphMonitorConfig) == 24 and C.sizeof(SphMonitorRow) == 128 and C.sizeof(SphMonitorInfo) == 112
+MONITOR_ROW_DTYPE = np.dtype(SphMonitorRow)
+assert MONITOR_ROW_DTYPE.itemsize == 128
+SPH_MAX_MONITORS = 4
+SPH_MAX_MONITOR_POINTS = 4194304
+SPH_MAX_MONITOR_HISTORY = 4096
+SPH_MONITOR_NONE, SPH_MONITOR_POINTS, SPH_MONITOR_LATTICE = 0, 1, 2
+(SPH_MONITOR_WET_SHARE, SPH_MONITOR_MEAN_FRACTION, SPH_MONITOR_VAR_FRACTION, SPH_MONITOR_MEAN_DENSITY, SPH_MONITOR_MEAN_PRESSURE,
+ SPH_MONITOR_VAR_PRESSURE, SPH_MONITOR_MEAN_VEL_X, SPH_MONITOR_MEAN_VEL_Y, SPH_MONITOR_MEAN_VEL_Z, SPH_MONITOR_TKE) = range(10)
+SPH_MONITOR_FIELDS = 10
+
+
 class SphNeighborInfo(C.Structure):
     """struct SphNeighborInfo of include/sph_abi.h: what the engine's neighbour lists hold (see SPHFluidGPU.neighbors)."""
     _fields_ = [("rows", C.c_uint64), ("total", C.c_uint64), ("radius", C.c_float), ("stencil", C.c_int32), ("flags", C.c_int32),
@@ -548,6 +579,21 @@ _ABI = {
     "sph_gates_books": (_int, [_vp, _vp, _P(_d), _P(_u64), _int]),
     "sph_gates_history": (_int, [_vp, _P(_u64), _P(_u32), _vp, _vp]),
     "sph_gates_step_host": (_int, [_vp, _vp, _sz, _vp, _int, _vp, _int, _vp]),
+    # field monitors
+    "sph_monitor_config_default": (None, [_P(SphMonitorConfig)]),
+    "sph_monitor_set": (_int, [_vp, _int, _vp, _sz, _P(SphMonitorConfig)]),
+    "sph_monitor_set_device": (_int, [_vp, _int, _vp, _sz, _P(SphMonitorConfig)]),
+    "sph_monitor_set_lattice": (_int, [_vp, _int, _pf, _pf, _pi, _P(SphMonitorConfig)]),
+    "sph_monitor_info": (_int, [_vp, _int, _P(SphMonitorInfo)]),
+    "sph_monitor_download": (_int, [_vp, _int, _vp, _sz]),
+    "sph_monitor_device": (_int, [_vp, _int, _P(_vp)]),
+    "sph_monitor_history": (_int, [_vp, _int, _P(_u64), _P(_u32), _vp, _vp, _sz]),
+    "sph_monitor_field": (_int, [_vp, _int, _int, _vp]),
+    "sph_monitor_reset": (_int, [_vp, _int]),
+    "sph_monitor_clear": (_int, [_vp, _int]),
+    "sph_monitor_accumulate_host": (_int, [_vp, _vp, _sz, _f]),
+    "sph_monitor_field_host": (_int, [_vp, _sz, _int, _vp]),
+    "sph_monitor_schedule_host": (_int, [_u32, _u32, _u32, _sz, _vp, _vp]),
     # spray, foam and bubbles
     "sph_diffuse_default": (None, [_P(SphDiffuseConfig)]),
     "sph_diffuse_set": (_int, [_vp, _P(SphDiffuseConfig)]),
@@ -2025,6 +2071,83 @@ class SPHFluidGPU:
         _check(self._L.sph_gates_history(self._h, C.byref(first), C.byref(cnt), _ptr(rows.reshape(-1)), _ptr(times)))
         return int(first.value), rows.reshape(-1)[:cnt.value * k].reshape(cnt.value, k).copy(), times[:cnt.value].copy()
 
+    # -- field monitors (include/sph_abi.h "field monitors") ----------------
+    def set_monitor(self, points=None, *, lattice=None, slot: int = 0, every: int = 1, wet_fraction: float = 0.5, history: int = 0,
+                    stride: int = 1, ring_points=None):
+        """Set monitor `slot` to explicit points ((m, 3) or (m, 4), numpy or a (m, 4) float32 torch device tensor) or to
+        lattice=(origin, spacing, dims) with dims = (nx, ny, nz).  From now on every `every`-th substep adds, inside the substep, the
+        sample() of each point to the point's running sums; with history > 0 every `stride`-th of them also stores the raw samples of
+        the first ring_points points (None: min(M, 64)) in a ring on the device.  A set call restarts the slot."""
+        if (points is None) == (lattice is None):
+            raise SphError("set_monitor: give either points or lattice=(origin, spacing, dims)")
+        cfg = monitor_config(every=int(every), wetFraction=float(wet_fraction), history=int(history), stride=int(stride),
+                             ringPoints=0 if ring_points is None else int(ring_points))
+        self._push_params()
+        if lattice is not None:
+            origin, spacing, dims = lattice
+            _check(self._L.sph_monitor_set_lattice(self._h, int(slot), _f3(origin), _f3(_spacing3(spacing)), _dims3(dims), C.byref(cfg)))
+            return
+        if type(points).__module__.startswith("torch"):
+            dev = _device_points4(points, "set_monitor")
+            _check(self._L.sph_monitor_set_device(self._h, int(slot), C.c_void_p(dev.data_ptr()), len(dev), C.byref(cfg)))
+            return
+        p4 = _points4(points, "set_monitor", keep_w=False)
+        _check(self._L.sph_monitor_set(self._h, int(slot), _ptr_or_none(p4), len(p4), C.byref(cfg)))
+
+    def monitor_info(self, slot: int = 0) -> dict:
+        """What the slot holds as a dict: kind (SPH_MONITOR_NONE for an empty slot), dims, points, the config as set (every,
+        wetFraction, history, stride, ringPoints), substeps, acting, time, ringRows, firstRow, origin, spacing.  Synchronises."""
+        info = SphMonitorInfo()
+        _check(self._L.sph_monitor_info(self._h, int(slot), C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("kind", "points", "substeps", "acting", "firstRow", "ringRows")}
+        out.update({name: int(getattr(info.config, name)) for name in ("every", "history", "stride", "ringPoints")})
+        out.update(wetFraction=float(info.config.wetFraction), time=float(info.time), dims=tuple(int(x) for x in info.dims),
+                   origin=tuple(float(x) for x in info.origin), spacing=tuple(float(x) for x in info.spacing))
+        return out
+
+    def monitor_rows(self, slot: int = 0, device: bool = False):
+        """The rows of the slot in the caller's order: a MONITOR_ROW_DTYPE array, of shape (nz, ny, nx) for a lattice; with
+        device=True the borrowed device address of the 128-byte rows (no synchronisation, no copy)."""
+        if device:
+            p = C.c_void_p()
+            _check(self._L.sph_monitor_device(self._h, int(slot), C.byref(p)))
+            return int(p.value or 0)
+        info = self.monitor_info(slot)
+        out = np.zeros(info["points"], MONITOR_ROW_DTYPE)
+        _check(self._L.sph_monitor_download(self._h, int(slot), _ptr_or_none(out), len(out)))
+        return out.reshape(info["dims"][::-1]) if info["kind"] == SPH_MONITOR_LATTICE else out
+
+    def monitor_history(self, slot: int = 0):
+        """(first, samples (rows, ringPoints) SAMPLE_DTYPE, times (rows,)): the ring rows held, oldest first, the fp64 time of the state
+        each was sampled on, and the index of the first one (ring row r was written by acting substep r * stride).  Synchronises."""
+        info = self.monitor_info(slot)
+        cap, rp = max(info["history"], 1), info["ringPoints"]
+        samples, times = np.zeros((cap, max(rp, 1)), SAMPLE_DTYPE), np.zeros(cap, np.float64)
+        first, cnt = C.c_uint64(), C.c_uint32()
+        _check(self._L.sph_monitor_history(self._h, int(slot), C.byref(first), C.byref(cnt), _ptr(samples.reshape(-1)), _ptr(times), cap))
+        return int(first.value), samples.reshape(-1)[:cnt.value * rp].reshape(cnt.value, rp).copy(), times[:cnt.value].copy()
+
+    def monitor_field(self, field: int, slot: int = 0, device: bool = False):
+        """A derived field (SPH_MONITOR_*) of the slot: M float32, of shape (nz, ny, nx) for a lattice (surface_from_volume takes it as
+        it is); a numpy array, or with device=True a torch device tensor (asynchronous on the engine's stream)."""
+        import torch
+        info = self.monitor_info(slot)
+        shape = info["dims"][::-1] if info["kind"] == SPH_MONITOR_LATTICE else (info["points"],)
+        buf = torch.empty(shape, dtype=torch.float32, device="cuda")
+        _check(self._L.sph_monitor_field(self._h, int(slot), int(field), C.c_void_p(buf.data_ptr())))
+        if device:
+            return buf
+        self.sync()
+        return buf.cpu().numpy()
+
+    def reset_monitor(self, slot: int = 0):
+        """Zero rows, counters and ring of the slot on the stream and keep its buffers: averaging begins anew (after a spin-up, say)."""
+        _check(self._L.sph_monitor_reset(self._h, int(slot)))
+
+    def clear_monitor(self, slot=None):
+        """Drop the monitor of one slot, or (None) of every slot."""
+        _check(self._L.sph_monitor_clear(self._h, -1 if slot is None else int(slot)))
+
     # -- kinematic solid obstacles (include/sph_abi.h "obstacles") -------------------------------
     def set_obstacles(self, obstacles):
         """Replace the set of bodies (a list of obstacle() results or an OBSTACLE_DTYPE array; empty clears it).  Every substep from
@@ -2685,3 +2808,53 @@ def gates_step_host(entry: np.ndarray, exit_records: np.ndarray, gates, values=N
         raise SphError("gates_step_host: fewer book rows than gates")
     _check(load_library().sph_gates_step_host(_ptr(a), _ptr(b), len(b), _ptr_or_none(arr), len(arr), None if not k else _ptr(v), k, _ptr(out)))
     return out[:len(arr)] if books is None else out
+
+
+def monitor_config(**overrides) -> SphMonitorConfig:
+    """sph_monitor_config_default with the named fields replaced.  No device is needed."""
+    cfg = SphMonitorConfig()
+    load_library().sph_monitor_config_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def monitor_accumulate_host(rows, samples, wet_fraction: float = 0.5) -> np.ndarray:
+    """sph_monitor_accumulate_host: the rows (MONITOR_ROW_DTYPE, any shape) after one acting substep whose samples (SAMPLE_DTYPE, the
+    same number) are given, added to a copy of `rows` (None: zeros).  No device is needed."""
+    smp = np.ascontiguousarray(samples, SAMPLE_DTYPE)
+    out = np.zeros(smp.shape, MONITOR_ROW_DTYPE) if rows is None else np.ascontiguousarray(rows, MONITOR_ROW_DTYPE).copy()
+    if out.size != smp.size:
+        raise SphError("monitor_accumulate_host: rows and samples differ in length")
+    _check(load_library().sph_monitor_accumulate_host(_ptr(out.reshape(-1)), _ptr(smp.reshape(-1)), smp.size, float(wet_fraction)))
+    return out
+
+
+def monitor_field_host(rows, field: int) -> np.ndarray:
+    """sph_monitor_field_host: the derived field (SPH_MONITOR_*) of MONITOR_ROW_DTYPE rows, float32 of the rows' shape."""
+    r = np.ascontiguousarray(rows, MONITOR_ROW_DTYPE)
+    out = np.zeros(r.shape, np.float32)
+    _check(load_library().sph_monitor_field_host(_ptr(r.reshape(-1)), r.size, int(field), _ptr(out.reshape(-1))))
+    return out
+
+
+def monitor_schedule_host(every: int, stride: int, history: int, substeps: int):
+    """sph_monitor_schedule_host: (acts, rows) of the first `substeps` substeps after a set: acts[s] is 1 where substep s acts, rows[s]
+    the ring row it writes or 0xFFFFFFFF."""
+    acts, rows = np.zeros(substeps, np.uint32), np.zeros(substeps, np.uint32)
+    _check(load_library().sph_monitor_schedule_host(int(every), int(stride), int(history), int(substeps), _ptr(acts), _ptr(rows)))
+    return acts, rows
+
+
+def monitor_means(rows) -> dict:
+    """A numpy convenience over MONITOR_ROW_DTYPE rows, not byte-checked (plain float64 numpy, nan where the dividing count is 0):
+    wet_share, fraction, density (over all samples), pressure, vel (..., 3) (over wet samples) and reynolds (..., 3, 3), the
+    covariance <u_a u_b> - <u_a><u_b> of the wet samples."""
+    r = np.asarray(rows)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n, w = r["samples"].astype(np.float64), r["wet"].astype(np.float64)
+        n, w = np.where(n > 0, n, np.nan), np.where(w > 0, w, np.nan)
+        vel = r["sumVel"] / w[..., None]
+        second = np.zeros(r.shape + (3, 3))
+        for k, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            second[..., a, b] = second[..., b, a] = r["sumVelVel"][..., k] / w
+        return dict(wet_share=r["wet"] / n, fraction=r["sumFraction"] / n, density=r["sumDensity"] / n, pressure=r["sumPressure"] / w, vel=vel,
+                    reynolds=second - vel[..., :, None] * vel[..., None, :])

@@ -597,6 +597,57 @@ public:
         times.resize(stored);
         return true;
     }
+    // Field monitors (engine extension, sph_abi.h "field monitors"): up to SPH_MAX_MONITORS fixed sets of points, explicit
+    // or a lattice origin + i * spacing (x fastest); every `every`-th substep from now on adds, on the device and inside the substep, the
+    // SphSample of each point to the point's running fp64 sums (SphMonitorRow), and with history > 0 keeps the raw samples of the first
+    // ringPoints points in a ring.  MonitorConfig() gives the defaults.  A set call restarts its slot; ResetMonitor zeroes rows, counters and
+    // ring and keeps the buffers (averaging after a spin-up).  SetMonitor* and ResetMonitor do not synchronise; MonitorInfo, DownloadMonitor,
+    // MonitorHistory (rows oldest first, row k, point p at samples[k * ringPoints + p]) and MonitorField do.  MonitorField derives the field
+    // on the host from the downloaded rows with sph_monitor_field_host (the device's bytes); MonitorFieldDevice writes M floats into device
+    // memory on the engine's stream.  Return false on error (LastError()).
+    static SphMonitorConfig MonitorConfig() {
+        SphMonitorConfig c;
+        sph_monitor_config_default(&c);
+        return c;
+    }
+    bool SetMonitor(int slot, const std::vector<MATH::Vec4>& points, const SphMonitorConfig& config) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_monitor_set(engine, slot, points.empty() ? nullptr : &points[0].x, points.size(), &config), "sph_monitor_set");
+    }
+    bool SetMonitorLattice(int slot, const MATH::Vec3& origin, const MATH::Vec3& spacing, const int dims[3], const SphMonitorConfig& config) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {spacing.x, spacing.y, spacing.z};
+        return !Check(sph_monitor_set_lattice(engine, slot, o, s, dims, &config), "sph_monitor_set_lattice");
+    }
+    bool MonitorInfo(int slot, SphMonitorInfo& out) { return !Check(sph_monitor_info(engine, slot, &out), "sph_monitor_info"); }
+    bool DownloadMonitor(int slot, std::vector<SphMonitorRow>& rows) {
+        SphMonitorInfo info;
+        if (!MonitorInfo(slot, info)) return false;
+        rows.assign(size_t(info.points), SphMonitorRow());
+        return !Check(sph_monitor_download(engine, slot, rows.empty() ? nullptr : rows.data(), rows.size()), "sph_monitor_download");
+    }
+    bool MonitorHistory(int slot, std::vector<SphSample>& samples, std::vector<double>& times, uint32_t& stored, uint64_t& firstRow) {
+        SphMonitorInfo info;
+        if (!MonitorInfo(slot, info)) return false;
+        samples.assign(size_t(info.config.history) * size_t(info.config.ringPoints), SphSample());
+        times.assign(info.config.history, 0.0);
+        if (Check(sph_monitor_history(engine, slot, &firstRow, &stored, samples.empty() ? nullptr : samples.data(), times.empty() ? nullptr : times.data(),
+                                      info.config.history), "sph_monitor_history")) return false;
+        samples.resize(size_t(stored) * size_t(info.config.ringPoints));
+        times.resize(stored);
+        return true;
+    }
+    bool MonitorField(int slot, int field, std::vector<float>& out) {
+        std::vector<SphMonitorRow> rows;
+        if (!DownloadMonitor(slot, rows)) return false;
+        out.assign(rows.size(), 0.0f);
+        return !Check(sph_monitor_field_host(rows.empty() ? nullptr : rows.data(), rows.size(), field, out.empty() ? nullptr : out.data()), "sph_monitor_field_host");
+    }
+    bool MonitorFieldDevice(int slot, int field, float* devOut) { return !Check(sph_monitor_field(engine, slot, field, devOut), "sph_monitor_field"); }
+    bool ResetMonitor(int slot) { return !Check(sph_monitor_reset(engine, slot), "sph_monitor_reset"); }
+    bool ClearMonitor(int slot = -1) { return !Check(sph_monitor_clear(engine, slot), "sph_monitor_clear"); }
     // Kinematic solid obstacles (engine extension, sph_abi.h "obstacles"): up to SPH_MAX_OBSTACLES bodies whose
     // motion the caller prescribes; every substep keeps the fluid out of them, advances their poses on the device and sums, per body,
     // the impulse (Jx, Jy, Jz, Lx, Ly, Lz) the fluid gave it.  An empty vector drops the set.  SetObstacleMotion keeps the device's pose

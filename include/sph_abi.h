@@ -46,6 +46,9 @@ extern "C" {
 /* (still 4, additions only: SphScalarSource, SPH_MAX_SCALAR_SOURCES, SPH_SOURCE_*, sph_scalar_source_default, sph_scalars_set_buoyancy / _get_buoyancy /
     _set_sources / _get_sources / _injected / _couple_host -- active scalars: buoyancy and continuous sources) */
 /* (still 4, additions only: SphGate, SphGateBooks, SPH_MAX_GATES, SPH_MAX_GATE_HISTORY, SPH_GATE_*, sph_gates_set / _get / _books / _history / _step_host -- flow gates) */
+/* (still 4, additions only: SphMonitorConfig, SphMonitorRow, SphMonitorInfo, SPH_MAX_MONITORS, SPH_MAX_MONITOR_POINTS, SPH_MAX_MONITOR_HISTORY, SPH_MONITOR_*,
+    sph_monitor_config_default / _set / _set_device / _set_lattice / _info / _download / _device / _history / _field / _reset / _clear / _accumulate_host /
+    _field_host / _schedule_host -- field monitors: probes and lattices averaged inside the substep) */
 /* (still 4, additions only: SphDiffuse, SphDiffuseConfig, SphDiffuseInfo, SPH_DIFFUSE_*, sph_diffuse_default / _set / _get / _info / _download / _device /
     _seed / _step_host, SPH_OPT_DIFFUSE_TIMED -- spray, foam and bubbles: secondary particles spawned by the fluid) */
 /* (still 4, additions only: SphDiffuseCrest, SphDiffuseCrestInfo, sph_diffuse_crest_default / _crest_info, sph_diffuse_set_crest / _get_crest,
@@ -797,6 +800,99 @@ int  sph_gates_history(SphEngine* e, uint64_t* firstOut, uint32_t* countOut, Sph
  * floats (record i owns values[i * channels ..]) or NULL with channels 0. */
 int  sph_gates_step_host(const SphParticle* entry, const SphParticle* exitRecords, size_t n, const SphGate* gates, int count,
                          const float* values, int channels, SphGateBooks* books);
+
+/* ---- field monitors: probes and lattices averaged inside the substep (no reference counterpart) -------------
+ * A monitor is a fixed set of M points (1 <= M <= SPH_MAX_MONITOR_POINTS): m explicit (x, y, z, unused) rows, or the lattice
+ * origin + (float)i * spacing, x fastest, the point formula of sph_sample_lattice.  Up to SPH_MAX_MONITORS independent monitors per
+ * engine, addressed by `slot`.  Off by default; with no monitor set a dispatch launches exactly what it launched before.
+ *   which substeps act   c = the non-paused substeps this monitor has seen since it was set or reset (a counter in device memory).  The
+ *            substep acts iff c % every == 0: the first substep after a set acts and sees the state at set time.  With a = the acting
+ *            substeps before this one, it also writes ring row (a / stride) % history iff history > 0 && a % stride == 0.
+ *   what it samples      for each point the SphSample sph_sample_points would return on the state the substep STARTS from, evaluated on
+ *            the sorted copy the substep has just built (where the tracers are advected): the sampler's own candidate function in the
+ *            sampler's order, so a monitor sample is, bit for bit, sph_sample_points called just before the dispatch.
+ *   accumulation         each point owns one SphMonitorRow; no atomics.  wet: fraction >= wetFraction.  Every update is
+ *            sum = sum + (double)x or sum = sum + (double)a * (double)b (the product of two fp32 values is exact in fp64: fused or not,
+ *            the same bits).  A sample with a non-finite field is skipped whole (the row's `samples` then stays below the monitor's
+ *            `acting`); a non-finite POINT gives the sampler's all-zero record and counts as a dry sample.
+ *   ring                 a ring row holds the raw SphSample of the points 0 .. ringPoints-1 and the fp64 time of the entry state (the
+ *            sum of dt of the substeps before this one since set or reset).  history * ringPoints * 32 bytes <= 256 MiB.
+ * every, stride, the ring geometry, the counters, wetFraction and a lattice's origin and spacing live in device memory: a replayed
+ * graph sees a later set or reset.  A graph's key holds, only while a monitor is set, each slot's kind, M, a lattice's dims, the
+ * buffers and the ring layout: sph_monitor_reset, and a set call that keeps these, need no new capture.  A set call on a slot always
+ * restarts that slot (rows, counters, ring); sph_reset drops every monitor, param_pause leaves everything untouched.
+ * SPH_ERR_STATE, before any allocation: z-slab engines and SPH_OPT_GRID_BUILD 1 (no sorted copy); setting that option while a monitor
+ * exists makes the next dispatch fail and change nothing.  SPH_ERR_ARG (the previous state stays): slot out of range, null data with
+ * m > 0, m above the cap, a lattice dim < 1 or a point count above the cap, a spacing not finite and > 0, an origin not finite,
+ * every or stride of 0, history above SPH_MAX_MONITOR_HISTORY, ringPoints > M, a ring above 256 MiB, a wetFraction that is not finite.
+ * SPH_ERR_CAPACITY from the download calls when the capacity is too small. */
+#define SPH_MAX_MONITORS 4
+#define SPH_MAX_MONITOR_POINTS 4194304
+#define SPH_MAX_MONITOR_HISTORY 4096
+enum { SPH_MONITOR_NONE = 0, SPH_MONITOR_POINTS = 1, SPH_MONITOR_LATTICE = 2 };   /* SphMonitorInfo.kind */
+enum { SPH_MONITOR_WET_SHARE = 0, SPH_MONITOR_MEAN_FRACTION = 1, SPH_MONITOR_VAR_FRACTION = 2, SPH_MONITOR_MEAN_DENSITY = 3,
+       SPH_MONITOR_MEAN_PRESSURE = 4, SPH_MONITOR_VAR_PRESSURE = 5, SPH_MONITOR_MEAN_VEL_X = 6, SPH_MONITOR_MEAN_VEL_Y = 7,
+       SPH_MONITOR_MEAN_VEL_Z = 8, SPH_MONITOR_TKE = 9 };
+typedef struct SphMonitorConfig {   /* 24 bytes */
+    uint32_t every;        /* >= 1: every `every`-th non-paused substep acts */
+    float    wetFraction;  /* a sample is wet iff fraction >= wetFraction (0.5) */
+    uint32_t history;      /* ring rows, 0 .. SPH_MAX_MONITOR_HISTORY (0: no ring) */
+    uint32_t stride;       /* >= 1: every `stride`-th acting substep writes a ring row */
+    uint32_t ringPoints;   /* the ring keeps the points 0 .. ringPoints-1 (0 .. M; 0 with a history: min(M, 64)) */
+    uint32_t pad;
+} SphMonitorConfig;
+typedef struct SphMonitorRow {        /* 128 bytes */
+    uint64_t samples, wet;
+    double sumFraction, sumFraction2, sumDensity;          /* over all samples            */
+    double sumPressure, sumPressure2;                      /* over wet samples            */
+    double sumVel[3];                                      /* over wet samples            */
+    double sumVelVel[6];                                   /* xx, yy, zz, xy, xz, yz; wet */
+} SphMonitorRow;
+typedef struct SphMonitorInfo {   /* 112 bytes */
+    int32_t  kind;         /* SPH_MONITOR_NONE (an empty slot: everything else 0) | _POINTS | _LATTICE */
+    int32_t  dims[3];      /* lattice: nx, ny, nz; points: M, 1, 1 */
+    uint64_t points;       /* M */
+    SphMonitorConfig config;   /* as set, ringPoints as in force */
+    uint64_t substeps;     /* c: non-paused substeps seen since set / reset */
+    uint64_t acting;       /* a: those of them that acted */
+    double   time;         /* sum of dt over the c substeps */
+    uint64_t firstRow;     /* index of the oldest ring row held (ring row r was written by acting substep r * stride) */
+    uint32_t ringRows;     /* ring rows held, <= history */
+    uint32_t pad;
+    float    origin[3], spacing[3];   /* lattice */
+} SphMonitorInfo;
+void sph_monitor_config_default(SphMonitorConfig* out);   /* every 1, wetFraction 0.5, history 0, stride 1, ringPoints 0 */
+/* Sets slot `slot` to m explicit points (4 floats each, host / device memory); config NULL: the defaults; m 0 clears the slot.  The
+ * points are copied. */
+int  sph_monitor_set(SphEngine* e, int slot, const float* points4, size_t m, const SphMonitorConfig* config);
+int  sph_monitor_set_device(SphEngine* e, int slot, const float* devPoints4, size_t m, const SphMonitorConfig* config);
+/* Sets slot `slot` to the lattice of dims[0] x dims[1] x dims[2] points; row index (l * ny + j) * nx + i. */
+int  sph_monitor_set_lattice(SphEngine* e, int slot, const float origin[3], const float spacing[3], const int dims[3], const SphMonitorConfig* config);
+/* What slot `slot` holds, with the device's counters.  Synchronises. */
+int  sph_monitor_info(SphEngine* e, int slot, SphMonitorInfo* out);
+/* The M rows in the caller's order (cap >= M rows, else SPH_ERR_CAPACITY).  Synchronises. */
+int  sph_monitor_download(SphEngine* e, int slot, SphMonitorRow* out, size_t cap);
+/* Borrowed device address of the rows (NULL for an empty slot); valid until the slot is set, cleared or the engine reset.  No synchronisation. */
+int  sph_monitor_device(SphEngine* e, int slot, const SphMonitorRow** devPtr);
+/* The ring rows held, oldest first: *countOut rows of ringPoints samples each (row k, point p at samples[k * ringPoints + p]) with
+ * their times and the index of the first (rowCap >= rows held, else SPH_ERR_CAPACITY).  Any output pointer may be null.  Synchronises. */
+int  sph_monitor_history(SphEngine* e, int slot, uint64_t* firstOut, uint32_t* countOut, SphSample* samples, double* times, size_t rowCap);
+/* A derived volume: M floats into device memory.  Every operation in fp64 and rounded on its own, then one rounding to fp32; 0 where
+ * the dividing count is 0:  WET_SHARE wet / samples; MEAN_FRACTION sumFraction / samples; VAR_FRACTION sumFraction2 / samples - mean^2;
+ * MEAN_DENSITY sumDensity / samples; MEAN_PRESSURE sumPressure / wet; VAR_PRESSURE sumPressure2 / wet - mean^2; MEAN_VEL_a sumVel[a] / wet;
+ * TKE 0.5 * (((xx / wet - mx^2) + (yy / wet - my^2)) + (zz / wet - mz^2)).  SPH_ERR_STATE on an empty slot.  Stream-ordered. */
+int  sph_monitor_field(SphEngine* e, int slot, int field, float* devOut);
+/* Zeroes rows, counters and ring on the stream and keeps the buffers (averaging can begin after a spin-up; a captured graph stays valid). */
+int  sph_monitor_reset(SphEngine* e, int slot);
+/* Drops slot `slot` and frees its buffers; slot < 0: every slot. */
+int  sph_monitor_clear(SphEngine* e, int slot);
+/* Host-only, no device, plain loops over the same __host__ __device__ functions the kernels run: one acting substep of m samples INTO
+ * rows[0 .. m), and a derived field of m rows. */
+int  sph_monitor_accumulate_host(SphMonitorRow* rows, const SphSample* samples, size_t m, float wetFraction);
+int  sph_monitor_field_host(const SphMonitorRow* rows, size_t m, int field, float* out);
+/* Host-only: the counters' rule over `substeps` substeps after a set: actsOut[s] = 1 iff substep s acts, rowsOut[s] = the ring row it
+ * writes or 0xFFFFFFFF (what k_monitor_tick runs). */
+int  sph_monitor_schedule_host(uint32_t every, uint32_t stride, uint32_t history, size_t substeps, uint32_t* actsOut, uint32_t* rowsOut);
 
 /* ---- spray, foam and bubbles: secondary particles spawned by the fluid (no reference counterpart) -----------
  * Secondary ("diffuse") particles in the sense of Ihmsen et al. 2012, reduced to what the engine's state supports: points that do not
