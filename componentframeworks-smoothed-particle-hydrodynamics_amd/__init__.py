@@ -41,5 +41,7 @@ from .engine import (  # noqa: F401
     shell_config,
     SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID, SPH_ANISO_SPARSE, SPH_ANISO_CLAMPED, SphAniso, SphAnisoConfig, SphAnisoInfo, ANISO_DTYPE, aniso_config,
     aniso_host, aniso_lattice_host,
+    SPH_STATE_FORMAT, SPH_STATE_CHECKSUM_MIX64, SPH_STATE_MAGIC, STATE_SECTIONS, SphStateInfo, SphStateDigest, SphStateHeader, SphStateEntry, SphStateCore,
+    STATE_HEADER_DTYPE, STATE_ENTRY_DTYPE, state_info, state_checksum_host, state_sections,
 )
 from . import build, synthetic  # noqa: F401

@@ -40,6 +40,7 @@
 #include "sph_couple.h"
 #include "sph_gate.h"
 #include "sph_monitor.h"
+#include "sph_state.h"
 
 static_assert(sizeof(SphParticle) == 80, "SPHParticle must be 80 bytes (SPHFluid3D.h:12-24)");
 static_assert(sizeof(SphSample) == 32, "SphSample must be 32 bytes");
@@ -473,6 +474,9 @@ struct SphEngine {
     DevBuf<double> d_meshW;
 
     std::vector<SphParticle> hostInit;   // SPHFluidGPU::particles: initial state only
+
+    // sph_state_digest (sph_state.h): two 64-bit sums per section
+    DevBuf<unsigned long long> d_stateAcc;
 
     // timing
     struct Ev { int cls; hipEvent_t a, b; };
@@ -1615,6 +1619,7 @@ int sph_destroy(SphEngine* e) {
     monitors_free(e);
     obstacles_free(e);
     volumes_free(e);
+    e->d_stateAcc.release();
     for (auto& ev : e->evLive) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->evPool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (e->xstream) { (void)hipStreamSynchronize(e->xstream); (void)hipStreamDestroy(e->xstream); }
@@ -6601,6 +6606,610 @@ int sph_kernel_times(SphEngine* e, double msOut[SPH_K_COUNT], int64_t launchesOu
         if (launchesOut) launchesOut[i] = e->klaunch[i];
         if (reset) { e->kms[i] = 0.0; e->klaunch[i] = 0; }
     }
+    return SPH_OK;
+}
+
+// ---- checkpoints (sph_state.h) ------------------------------------------------
+static_assert(offsetof(sph::MonitorTab, c) == 0 && offsetof(sph::MonitorTab, a) == 8 && offsetof(sph::MonitorTab, time) == 16, "the counters lead the monitor table");
+static_assert(sizeof(sph::GateAcc) % 8 == 0 && sizeof(SphTracer) == 32 && sizeof(SphSample) == 32, "checkpoint pieces are 64-bit words");
+
+// One section as the pieces it is made of, in order: bytes the host holds, or an array in device memory (a multiple of 8 bytes each).
+// sph_state_size sums them, sph_state_save copies them, sph_state_digest hashes them where they lie.
+namespace {
+struct StatePiece {
+    std::vector<unsigned char> host;
+    const void* dev = nullptr;
+    size_t bytes = 0;
+};
+struct StateSection {
+    uint32_t tag = 0;
+    std::vector<StatePiece> pieces;
+    size_t bytes() const { size_t b = 0; for (const StatePiece& p : pieces) b += p.bytes; return b; }
+    void add_host(const void* p, size_t n) {
+        if (pieces.empty() || pieces.back().dev) pieces.emplace_back();
+        const unsigned char* c = static_cast<const unsigned char*>(p);
+        pieces.back().host.insert(pieces.back().host.end(), c, c + n);
+        pieces.back().bytes = pieces.back().host.size();
+    }
+    void add_dev(const void* p, size_t n) {
+        if (!n) return;
+        pieces.emplace_back();
+        pieces.back().dev = p; pieces.back().bytes = n;
+    }
+    // A device array of 32-bit words: the whole 64-bit words where they lie, an odd last word as a host piece (with four zero bytes, the
+    // blob's padding), read from the device only if `read` (sizes do not need it).
+    int add_dev32(SphEngine* e, const void* p, size_t words, bool read) {
+        add_dev(p, (words & ~(size_t)1) * 4u);
+        if (words & 1u) {
+            uint32_t last[2] = {0u, 0u};
+            if (read) {
+                HIP_TRY(hipMemcpyAsync(last, static_cast<const uint32_t*>(p) + (words - 1), 4, hipMemcpyDeviceToHost, e->stream));
+                HIP_TRY(hipStreamSynchronize(e->stream));
+            }
+            add_host(last, 8);
+        }
+        return SPH_OK;
+    }
+};
+}  // namespace
+
+static void state_tracer_words(uint64_t steps, uint32_t K, uint32_t S, uint32_t out[3]) {
+    out[0] = (uint32_t)steps; out[1] = (uint32_t)(steps >> 32);
+    out[2] = (K != 0u && (steps + 1ull) % S == 0ull) ? (uint32_t)(((steps + 1ull) / S) % K) : sph::kTracerNoSlot;   // tracer_slot_of(steps + 1)
+}
+
+// The sections of the engine as it stands.  current: also bring the 80-byte records up to date (a launch; sizes do not need it).
+static int state_collect(SphEngine* e, bool current, std::vector<StateSection>& out) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "checkpoints of a z-slab engine are not supported: its state is one share of a decomposed run");
+    if (e->n == 0) return fail(SPH_ERR_STATE, "an engine without particles has no checkpoint");
+    int rc;
+    if (current && (rc = writeback(e))) return rc;
+    out.clear();
+    {
+        StateSection s;
+        s.tag = SPH_STATE_CORE;
+        sph::StateCore c;
+        std::memset(&c, 0, sizeof(c));
+        c.params = e->params; c.lastDt = e->lastDt; c.fountain = e->fountain; c.river = e->river;
+        c.terrainCount = e->terrainHeights.size(); c.stencilCount = e->d_stencil ? e->stencilCount : 0;
+        s.add_host(&c, sizeof(c));
+        if (c.terrainCount) {
+            s.add_host(e->terrainHeights.data(), c.terrainCount * sizeof(float));
+            const uint32_t zero = 0u;
+            if (c.terrainCount & 1u) s.add_host(&zero, 4);
+        }
+        s.add_dev(e->d_stencil, (size_t)c.stencilCount * sizeof(float4));
+        out.push_back(std::move(s));
+    }
+    {
+        StateSection s;
+        s.tag = SPH_STATE_PARTICLES;
+        s.add_dev(e->d_aos, e->n * sizeof(SphParticle));
+        out.push_back(std::move(s));
+    }
+    if (e->trM) {
+        StateSection s;
+        s.tag = SPH_STATE_TRACERS;
+        sph::StateTracers t;
+        std::memset(&t, 0, sizeof(t));
+        t.m = e->trM; t.integrator = (uint32_t)e->trIntegrator; t.history = e->trK; t.stride = e->trS;
+        state_tracer_words(e->trSteps, e->trK, e->trS, t.state);       // (the device words: sph_state_save holds them against the device's)
+        t.hostSteps = e->trSteps;
+        s.add_host(&t, sizeof(t));
+        s.add_dev(e->d_trRec, e->trM * sizeof(SphTracer));
+        s.add_dev(e->d_trRing, (size_t)sph::state_tracer_slots(e->trSteps, e->trK, e->trS) * e->trM * sizeof(float4));
+        out.push_back(std::move(s));
+    }
+    if (e->dfC) {
+        // (the pool's size lies on the device: its state words, and the crest books, are read first -- a few hundred bytes, no array)
+        StateSection s;
+        s.tag = SPH_STATE_DIFFUSE;
+        uint32_t w[sph::DF_WORDS + 2] = {0}, cw[sph::DFC_WORDS + 2] = {0};
+        if (current) {
+            HIP_TRY(hipMemcpyAsync(w, e->d_dfState, sph::DF_WORDS * 4u, hipMemcpyDeviceToHost, e->stream));
+            if (e->d_dfCrState) HIP_TRY(hipMemcpyAsync(cw, e->d_dfCrState, sph::DFC_WORDS * 4u, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        } else {                                                      // (sizes: the count alone)
+            HIP_TRY(hipMemcpyAsync(&w[sph::DF_ALIVE], e->d_dfState + sph::DF_ALIVE, 4, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+        sph::StateDiffuse d;
+        std::memset(&d, 0, sizeof(d));
+        d.cfg = e->dfCfg; d.crest = e->dfCrCfg;
+        d.crestOn = e->dfCrOn ? 1u : 0u; d.hasCrestBooks = e->d_dfCrState ? 1u : 0u;
+        d.stateWords = (uint32_t)sph::DF_WORDS; d.crestWords = (uint32_t)sph::DFC_WORDS;
+        d.alive = std::min(w[sph::DF_ALIVE], e->dfC);
+        s.add_host(&d, sizeof(d));
+        s.add_host(w, (size_t)sph::state_pad8(sph::DF_WORDS * 4u));
+        if (d.hasCrestBooks) s.add_host(cw, (size_t)sph::state_pad8(sph::DFC_WORDS * 4u));
+        s.add_dev(e->d_dfPool, (size_t)d.alive * sizeof(SphDiffuse));
+        out.push_back(std::move(s));
+    }
+    if (e->scK) {
+        StateSection s;
+        s.tag = SPH_STATE_SCALARS;
+        sph::StateScalars c;
+        std::memset(&c, 0, sizeof(c));
+        c.channels = e->scK; c.hasCouple = e->d_cpTab ? 1u : 0u; c.accBytes = (uint32_t)sizeof(sph::CoupleAcc); c.steps = e->scSteps;
+        if (current) {
+            HIP_TRY(hipMemcpyAsync(&c.stateWord, e->d_scState, 4, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+        std::memcpy(c.coeffs, e->scCoeffs, sizeof(float) * 2 * (size_t)e->scK);
+        std::memcpy(c.beta, e->cpTab.beta, sizeof(c.beta)); std::memcpy(c.ref, e->cpTab.ref, sizeof(c.ref));
+        c.nSrc = e->cpTab.nSrc;
+        std::memcpy(c.src, e->cpTab.src, sizeof(c.src));
+        s.add_host(&c, sizeof(c));
+        if ((rc = s.add_dev32(e, e->d_scVal, e->scN * (size_t)e->scK, current))) return rc;
+        if (c.hasCouple) s.add_dev(e->d_cpAcc, sizeof(sph::CoupleAcc));
+        out.push_back(std::move(s));
+    }
+    bool anyVolume = false;
+    for (const auto& v : e->vols) anyVolume = anyVolume || v.d != nullptr;
+    if (e->obsK || anyVolume) {
+        StateSection s;
+        s.tag = SPH_STATE_OBSTACLES;
+        sph::StateObstacles o;
+        std::memset(&o, 0, sizeof(o));
+        o.count = e->obsK; o.recBytes = (uint32_t)sizeof(sph::ObsRec); o.dynBytes = (uint32_t)sizeof(sph::ObsDyn); o.accBytes = (uint32_t)sizeof(sph::ObsAcc);
+        for (int i = 0; i < sph::kObsMax; ++i) {
+            o.bind[i] = i < e->obsK ? e->volTab.bind[i] : -1;
+            if (i >= e->obsK) continue;
+            o.shape[i] = e->obsShape[i];
+            o.dynOn[i] = e->dynOn[i] ? 1 : 0;
+            if (e->dynOn[i]) o.dynSet[i] = e->dynSet[i];
+        }
+        for (int i = 0; i < sph::kVolMax; ++i)
+            if (e->vols[i].d) for (int a = 0; a < 3; ++a) { o.vol[i].dims[a] = e->vols[i].dims[a]; o.vol[i].spacing[a] = e->vols[i].spacing[a]; }
+        s.add_host(&o, sizeof(o));
+        if (e->obsK) {
+            s.add_dev(e->d_obs, sizeof(sph::ObsRec) * (size_t)e->obsK);
+            s.add_dev(e->d_obsAcc, sizeof(sph::ObsAcc));
+            s.add_dev(e->d_dyn, sizeof(sph::ObsDyn) * (size_t)e->obsK);
+        }
+        for (int i = 0; i < sph::kVolMax; ++i)
+            if (e->vols[i].d && (rc = s.add_dev32(e, e->vols[i].d, (size_t)e->vols[i].dims[0] * e->vols[i].dims[1] * e->vols[i].dims[2], current))) return rc;
+        out.push_back(std::move(s));
+    }
+    if (e->gtTab.count && e->d_gtTab) {
+        StateSection s;
+        s.tag = SPH_STATE_GATES;
+        sph::StateGates g;
+        std::memset(&g, 0, sizeof(g));
+        g.count = e->gtTab.count; g.history = e->gtTab.history; g.stride = e->gtTab.stride;
+        g.accWords = (uint32_t)(sizeof(sph::GateAcc) / 8); g.ringRowWords = (uint32_t)sph::kGateRingRow;
+        std::memcpy(g.set, e->gtSet, sizeof(g.set));
+        s.add_host(&g, sizeof(g));
+        s.add_dev(e->d_gtAcc, sizeof(sph::GateAcc));
+        s.add_dev(e->d_gtRing.p, (size_t)g.history * sph::kGateRingRow * 8u);
+        out.push_back(std::move(s));
+    }
+    if (e->monCount) {
+        StateSection s;
+        s.tag = SPH_STATE_MONITORS;
+        for (int i = 0; i < sph::kMonitorMax; ++i) {
+            const MonitorSlot& m = e->mon[i];
+            sph::StateMonitorSlot r;
+            std::memset(&r, 0, sizeof(r));
+            r.kind = m.kind;
+            if (m.kind != SPH_MONITOR_NONE) {
+                r.m = m.m; r.cfg = m.cfg;
+                for (int a = 0; a < 3; ++a) { r.dims[a] = m.dims[a]; r.origin[a] = m.origin[a]; r.spacing[a] = m.spacing[a]; }
+            }
+            s.add_host(&r, sizeof(r));
+        }
+        for (int i = 0; i < sph::kMonitorMax; ++i) {
+            const MonitorSlot& m = e->mon[i];
+            if (m.kind == SPH_MONITOR_NONE) continue;
+            s.add_dev(m.d_tab, sph::kStateMonitorCounters);
+            if (m.kind == SPH_MONITOR_POINTS) s.add_dev(m.d_points.p, m.m * sizeof(float4));
+            s.add_dev(m.d_rows.p, m.m * sizeof(sph::MonitorRow));
+            s.add_dev(m.d_ring.p, (size_t)m.cfg.history * m.cfg.ringPoints * sizeof(SphSample));
+            s.add_dev(m.d_times.p, (size_t)m.cfg.history * sizeof(double));
+        }
+        out.push_back(std::move(s));
+    }
+    return SPH_OK;
+}
+
+static size_t state_total_bytes(const std::vector<StateSection>& secs) {
+    size_t at = sizeof(sph::StateHeader) + sizeof(sph::StateEntry) * secs.size();
+    for (const StateSection& s : secs) at = sph::state_align16(at) + s.bytes();
+    return sph::state_align16(at);
+}
+
+int sph_state_size(SphEngine* e, size_t* bytes) {
+    if (!e || !bytes) return fail(SPH_ERR_ARG, "null argument");
+    std::vector<StateSection> secs;
+    int rc;
+    if ((rc = state_collect(e, false, secs))) return rc;
+    *bytes = state_total_bytes(secs);
+    return SPH_OK;
+}
+
+int sph_state_save(SphEngine* e, void* blob, size_t cap, size_t* written) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    std::vector<StateSection> secs;
+    int rc;
+    if ((rc = state_collect(e, true, secs))) return rc;
+    const size_t total = state_total_bytes(secs);
+    if (written) *written = total;
+    if (cap < total) return fail(SPH_ERR_CAPACITY, "a checkpoint of %zu bytes (capacity %zu)", total, cap);
+    if (!blob) return fail(SPH_ERR_ARG, "null argument");
+    unsigned char* b = static_cast<unsigned char*>(blob);
+    std::memset(b, 0, total);
+    std::vector<sph::StateEntry> table(secs.size());
+    size_t at = sizeof(sph::StateHeader) + sizeof(sph::StateEntry) * secs.size();
+    uint32_t mask = 0;
+    for (size_t i = 0; i < secs.size(); ++i) {
+        at = sph::state_align16(at);
+        table[i] = sph::StateEntry{secs[i].tag, 1u, at, secs[i].bytes(), {0, 0}};
+        for (const StatePiece& p : secs[i].pieces) {
+            if (p.dev) HIP_TRY(hipMemcpyAsync(b + at, p.dev, p.bytes, hipMemcpyDeviceToHost, e->stream));
+            else std::memcpy(b + at, p.host.data(), p.bytes);
+            at += p.bytes;
+        }
+        mask |= secs[i].tag;
+    }
+    uint32_t trWords[3] = {0, 0, 0};
+    if (e->trM) HIP_TRY(hipMemcpyAsync(trWords, e->d_trState, sizeof(trWords), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->trM) {
+        uint32_t want[3];
+        state_tracer_words(e->trSteps, e->trK, e->trS, want);
+        if (std::memcmp(want, trWords, sizeof(want)) != 0)
+            return fail(SPH_ERR_STATE, "the tracers' device step counter (%u, %u, slot %u) is not the host mirror's (%llu substeps)", trWords[0], trWords[1], trWords[2],
+                        (unsigned long long)e->trSteps);
+    }
+    for (sph::StateEntry& s : table) sph::state_checksum(b + s.offset, (size_t)s.bytes, 0, s.sum);
+    std::memcpy(b + sizeof(sph::StateHeader), table.data(), sizeof(sph::StateEntry) * table.size());
+    sph::StateHeader h;
+    std::memset(&h, 0, sizeof(h));
+    h.magic = sph::kStateMagic; h.format = sph::kStateFormat; h.abi = (uint32_t)SPH_ABI_VERSION; h.checksumKind = SPH_STATE_CHECKSUM_MIX64;
+    h.sectionCount = (uint32_t)secs.size(); h.n = e->n; h.totalBytes = total; h.sectionMask = mask; h.headerBytes = (uint32_t)sizeof(h);
+    h.params = e->params;
+    sph::state_checksum(&h, sph::kStateHeaderSummed, 0, h.sum);
+    sph::state_checksum(table.data(), sizeof(sph::StateEntry) * table.size(), sph::kStateHeaderSummed / 8, h.sum);
+    std::memcpy(b, &h, sizeof(h));
+    return SPH_OK;
+}
+
+int sph_state_peek(const void* blob, size_t bytes, SphStateInfo* out) {
+    if (!out) return fail(SPH_ERR_ARG, "null argument");
+    char why[400];
+    if (sph::state_parse(blob, bytes, out, why, sizeof(why)) != SPH_OK) return fail(SPH_ERR_ARG, "checkpoint blob: %s", why);
+    return SPH_OK;
+}
+
+int sph_state_checksum_host(const void* bytes, size_t n, uint64_t out[2]) {
+    if ((!bytes && n) || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (n % 8u) return fail(SPH_ERR_ARG, "%zu bytes are not a multiple of 8", n);
+    out[0] = out[1] = 0;
+    sph::state_checksum(bytes, n, 0, out);
+    return SPH_OK;
+}
+
+int sph_state_digest(SphEngine* e, uint32_t sections, SphStateDigest* out) {
+    if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (sections & ~sph::kStateKnownMask) return fail(SPH_ERR_ARG, "unknown section bits %u", sections & ~sph::kStateKnownMask);
+    std::vector<StateSection> secs;
+    int rc;
+    if ((rc = state_collect(e, true, secs))) return rc;
+    if ((rc = e->d_stateAcc.grow(e, 2 * sph::kStateSections))) return rc;
+    // the sums start at what the host's pieces add; the kernels add the device's pieces, each at its word index inside the section
+    uint64_t init[sph::kStateSections][2];
+    std::memset(init, 0, sizeof(init));
+    uint32_t done = 0;
+    for (const StateSection& s : secs) {
+        if (sections && !(sections & s.tag)) continue;
+        const int idx = sph::state_section_index(s.tag);
+        size_t at = 0;
+        for (const StatePiece& p : s.pieces) {
+            if (!p.dev) sph::state_checksum(p.host.data(), p.bytes, at / 8, init[idx]);
+            else if (((uintptr_t)p.dev & 15u) || (p.bytes & 7u)) return fail(SPH_ERR_STATE, "a piece of section %s is not 16-byte aligned", sph::state_section_name(s.tag));
+            at += p.bytes;
+        }
+        done |= s.tag;
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_stateAcc.p, init, sizeof(init), hipMemcpyHostToDevice, e->stream));
+    for (const StateSection& s : secs) {
+        if (!(done & s.tag)) continue;
+        const int idx = sph::state_section_index(s.tag);
+        size_t at = 0;
+        for (const StatePiece& p : s.pieces) {
+            if (p.dev) {
+                const unsigned long long words = p.bytes / 8;
+                Timed t(e, SPH_K_OTHER);
+                hipLaunchKernelGGL(sph::k_state_checksum, dim3(sph::state_checksum_blocks(words)), dim3(sph::kStateBlock), 0, e->stream,
+                                   static_cast<const unsigned long long*>(p.dev), words, (unsigned long long)(at / 8), e->d_stateAcc.p + 2 * idx);
+            }
+            at += p.bytes;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    std::memset(out, 0, sizeof(*out));
+    HIP_TRY(hipMemcpyAsync(out->sum, e->d_stateAcc.p, sizeof(out->sum), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < sph::kStateSections; ++i) if (!(done & (1u << i))) out->sum[i][0] = out->sum[i][1] = 0;
+    out->sections = done;
+    return SPH_OK;
+}
+
+// What a load checks of the sections' configs beyond state_parse, by the checks of the set calls, before the engine is touched.
+static int state_load_check(SphEngine* e, const unsigned char* b, const SphStateInfo& info) {
+    int rc;
+    if ((rc = validate_params(info.params))) return rc;
+    sph::StateCore c;
+    std::memcpy(&c, b + info.offset[0], sizeof(c));
+    if (c.terrainCount) {
+        if ((rc = validate_river(c.river))) return rc;
+        for (uint64_t i = 0; i < c.terrainCount; ++i) {
+            float v;
+            std::memcpy(&v, b + info.offset[0] + sizeof(c) + 4 * i, 4);
+            if (!std::isfinite(v)) return fail(SPH_ERR_ARG, "checkpoint blob: terrain height %llu is not finite", (unsigned long long)i);
+        }
+    }
+    if (info.sections & SPH_STATE_TRACERS) {
+        sph::StateTracers t;
+        std::memcpy(&t, b + info.offset[2], sizeof(t));
+        if ((rc = tracers_check(e, reinterpret_cast<const float*>(b), (size_t)t.m, (int)t.integrator, t.history, t.stride))) return rc;
+        uint32_t want[3];
+        state_tracer_words(t.hostSteps, t.history, t.stride, want);
+        if (std::memcmp(want, t.state, sizeof(want)) != 0) return fail(SPH_ERR_ARG, "checkpoint blob: the tracers' device words do not belong to %llu substeps", (unsigned long long)t.hostSteps);
+    }
+    if (info.sections & SPH_STATE_DIFFUSE) {
+        if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+        sph::StateDiffuse d;
+        std::memcpy(&d, b + info.offset[3], sizeof(d));
+        if ((rc = diffuse_check_config(d.cfg))) return rc;
+        if (d.stateWords != (uint32_t)sph::DF_WORDS || d.crestWords != (uint32_t)sph::DFC_WORDS)
+            return fail(SPH_ERR_ARG, "checkpoint blob: a diffuse pool of %u + %u state words (this build: %d + %d)", d.stateWords, d.crestWords, sph::DF_WORDS, sph::DFC_WORDS);
+        uint32_t alive;
+        std::memcpy(&alive, b + info.offset[3] + sizeof(d) + 4 * sph::DF_ALIVE, 4);
+        if (std::min(alive, d.cfg.capacity) != d.alive) return fail(SPH_ERR_ARG, "checkpoint blob: the diffuse pool's state words count %u living records, the section holds %u", alive, d.alive);
+        if (d.crestOn) {
+            SphGridInfo g;
+            sph::compute_grid_extents(info.params, g);
+            if ((rc = diffuse_check_crest(d.crest, info.params.param_h, g.cellSize))) return rc;
+        }
+    }
+    if (info.sections & SPH_STATE_SCALARS) {
+        if ((rc = scalars_refused(e))) return rc;
+        sph::StateScalars c;
+        std::memcpy(&c, b + info.offset[4], sizeof(c));
+        if ((rc = scalars_check_coeffs(c.coeffs, c.channels)) || (rc = couple_check_buoyancy(c.beta, c.ref, c.channels)) ||
+            (rc = couple_check_sources(c.src, c.nSrc, c.channels))) return rc;
+        if (c.hasCouple && c.accBytes != sizeof(sph::CoupleAcc)) return fail(SPH_ERR_ARG, "checkpoint blob: injected books of %u bytes (this build: %zu)", c.accBytes, sizeof(sph::CoupleAcc));
+    }
+    if (info.sections & SPH_STATE_OBSTACLES) {
+        std::unique_ptr<sph::StateObstacles> o(new sph::StateObstacles());
+        std::memcpy(o.get(), b + info.offset[5], sizeof(*o));
+        if (o->recBytes != sizeof(sph::ObsRec) || o->dynBytes != sizeof(sph::ObsDyn) || o->accBytes != sizeof(sph::ObsAcc))
+            return fail(SPH_ERR_ARG, "checkpoint blob: body records of %u / %u bytes and sums of %u (this build: %zu / %zu and %zu)", o->recBytes, o->dynBytes, o->accBytes,
+                        sizeof(sph::ObsRec), sizeof(sph::ObsDyn), sizeof(sph::ObsAcc));
+        SphObstacle obs[sph::kObsMax];
+        for (int i = 0; i < o->count; ++i) {
+            sph::ObsRec r;
+            std::memcpy(&r, b + info.offset[5] + sizeof(*o) + sizeof(r) * i, sizeof(r));
+            rec_to_obstacle(r, obs[i]);
+            if (r.shape != o->shape[i]) return fail(SPH_ERR_ARG, "checkpoint blob: body %d has shape %d in its record and %d in the table", i, r.shape, o->shape[i]);
+            if (o->bind[i] >= 0 && r.shape != SPH_OBSTACLE_BOX) return fail(SPH_ERR_ARG, "checkpoint blob: body %d is bound to a volume and is not a box", i);
+            sph::ObsDyn dr;
+            if (o->dynOn[i] && (rc = dynamics_to_rec(o->dynSet[i], i, dr))) return rc;
+        }
+        if ((rc = obstacles_check(obs, o->count))) return rc;
+        for (int i = 0; i < sph::kVolMax; ++i)
+            if (sph::state_volume_points(o->vol[i]) > 0 && (rc = check_lattice(o->vol[i].dims, o->vol[i].spacing, 2, nullptr))) return rc;
+    }
+    if (info.sections & SPH_STATE_GATES) {
+        if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+        sph::StateGates g;
+        std::memcpy(&g, b + info.offset[6], sizeof(g));
+        if ((rc = gates_check(g.set, g.count))) return rc;
+        if (g.stride == 0) return fail(SPH_ERR_ARG, "checkpoint blob: gate stride must be >= 1");
+        if (g.accWords != sizeof(sph::GateAcc) / 8 || g.ringRowWords != (uint32_t)sph::kGateRingRow)
+            return fail(SPH_ERR_ARG, "checkpoint blob: gate books of %u words and ring rows of %u (this build: %zu and %d)", g.accWords, g.ringRowWords,
+                        sizeof(sph::GateAcc) / 8, sph::kGateRingRow);
+    }
+    if (info.sections & SPH_STATE_MONITORS) {
+        if ((rc = monitor_refused(e))) return rc;
+        for (int i = 0; i < sph::kMonitorMax; ++i) {
+            sph::StateMonitorSlot s;
+            std::memcpy(&s, b + info.offset[7] + sizeof(s) * i, sizeof(s));
+            if (s.kind == SPH_MONITOR_NONE) continue;
+            SphMonitorConfig cfg;
+            if ((rc = monitor_config_check(&s.cfg, (size_t)s.m, &cfg))) return rc;
+            if (std::memcmp(&cfg, &s.cfg, sizeof(cfg)) != 0) return fail(SPH_ERR_ARG, "checkpoint blob: monitor %d does not carry the config in force", i);
+            if (s.kind == SPH_MONITOR_LATTICE) {
+                long long total = 0;
+                if ((rc = check_lattice(s.dims, s.spacing, 1, &total))) return rc;
+                if ((uint64_t)total != s.m || !obs_all_finite(s.origin, 3)) return fail(SPH_ERR_ARG, "checkpoint blob: monitor %d's lattice does not have its %llu points", i, (unsigned long long)s.m);
+            }
+        }
+    }
+    return SPH_OK;
+}
+
+int sph_state_load(SphEngine* e, const void* blob, size_t bytes) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (e->slab) return fail(SPH_ERR_STATE, "checkpoints of a z-slab engine are not supported: its state is one share of a decomposed run");
+    SphStateInfo info;
+    int rc;
+    if ((rc = sph_state_peek(blob, bytes, &info))) return rc;
+    const unsigned char* b = static_cast<const unsigned char*>(blob);
+    if ((rc = state_load_check(e, b, info))) return rc;
+
+    // ---- from here on the engine changes ----
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->surfValid = false;                                             // query results: "no result", as after sph_reset
+    neighbors_free(e); components_free(e); knn_free(e); rays_free(e); shell_free(e); aniso_free(e);
+    tracers_free(e); diffuse_free(e); scalars_free(e); gates_free(e); monitors_free(e);
+    obstacles_free(e); volumes_free(e);
+    for (auto& s : e->obsShape) s = 0;
+    for (auto& d : e->dynSet) d = SphObstacleDynamics{};
+
+    sph::StateCore c;
+    std::memcpy(&c, b + info.offset[0], sizeof(c));
+    const unsigned char* tail = b + info.offset[0] + sizeof(c);
+    e->params = c.params;
+    e->lastDt = c.lastDt;
+    e->fountain = c.fountain;
+    if (c.terrainCount) {
+        std::vector<float> heights(c.terrainCount);
+        std::memcpy(heights.data(), tail, 4 * c.terrainCount);
+        e->terrainHeights.clear();                                    // (another heightfield size than the engine's is no error here)
+        if ((rc = sph_set_river(e, &c.river, heights.data()))) return rc;
+    } else {
+        e->terrainHeights.clear();
+        e->river = c.river;
+    }
+    tail += (4 * c.terrainCount + 7u) & ~(uint64_t)7u;
+    {
+        std::vector<float> pts(4 * c.stencilCount);
+        if (c.stencilCount) std::memcpy(pts.data(), tail, 16 * c.stencilCount);
+        if ((rc = sph_set_stencil_targets(e, pts.data(), (size_t)c.stencilCount))) return rc;
+    }
+    sph::compute_grid_extents(e->params, e->grid);
+    free_particle_buffers(e);                                         // (the graph cache goes with them)
+    {
+        std::vector<SphParticle> rec(info.n);
+        std::memcpy(rec.data(), b + info.offset[1], info.n * sizeof(SphParticle));
+        if ((rc = set_particles(e, rec.data(), rec.size())) || (rc = ensure_grid_buffers(e))) return rc;
+    }
+
+    if (info.sections & SPH_STATE_OBSTACLES) {                        // (in front of the scalars: a source may ride on a body)
+        const unsigned char* p = b + info.offset[5];
+        std::unique_ptr<sph::StateObstacles> o(new sph::StateObstacles());
+        std::memcpy(o.get(), p, sizeof(*o));
+        const unsigned char* recs = p + sizeof(*o);
+        const unsigned char* acc = recs + sizeof(sph::ObsRec) * (size_t)o->count;
+        const unsigned char* dyn = acc + (o->count ? sizeof(sph::ObsAcc) : 0);
+        const unsigned char* vals = dyn + sizeof(sph::ObsDyn) * (size_t)o->count;
+        if (o->count) {
+            SphObstacle obs[sph::kObsMax];
+            for (int i = 0; i < o->count; ++i) {
+                sph::ObsRec r;
+                std::memcpy(&r, recs + sizeof(r) * i, sizeof(r));
+                rec_to_obstacle(r, obs[i]);
+            }
+            if ((rc = sph_obstacles_set(e, obs, o->count))) return rc;
+            for (int i = 0; i < o->count; ++i)
+                if (o->dynOn[i] && (rc = sph_obstacles_set_dynamics(e, i, &o->dynSet[i]))) return rc;
+        }
+        for (int i = 0; i < sph::kVolMax; ++i) {                      // (every volume in the slot it had: the bindings name slots)
+            const long long pts = sph::state_volume_points(o->vol[i]);
+            if (pts <= 0) continue;
+            int unused = -1;
+            float* d = nullptr;
+            if ((rc = volume_free_slot(e, &unused)) || (rc = dev_alloc(&d, (size_t)pts))) return rc;
+            const hipError_t er = hipMemcpyAsync(d, vals, (size_t)pts * sizeof(float), hipMemcpyHostToDevice, e->stream);
+            if (er != hipSuccess) { dev_free(d); return fail(SPH_ERR_HIP, "volume upload: %s", hipGetErrorString(er)); }
+            if ((rc = volume_adopt(e, i, d, o->vol[i].dims, o->vol[i].spacing))) return rc;
+            vals += sph::state_pad8(4ull * (uint64_t)pts);
+        }
+        for (int i = 0; i < o->count; ++i)
+            if (o->bind[i] >= 0 && (rc = sph_obstacles_bind_volume(e, i, o->bind[i]))) return rc;
+        if (o->count) {                                               // the advanced poses, the sums and the device's dynamics records over what the set calls made
+            HIP_TRY(hipMemcpyAsync(e->d_obs, recs, sizeof(sph::ObsRec) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->d_obsAcc, acc, sizeof(sph::ObsAcc), hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->d_dyn, dyn, sizeof(sph::ObsDyn) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
+        }
+    }
+    if (info.sections & SPH_STATE_SCALARS) {
+        const unsigned char* p = b + info.offset[4];
+        sph::StateScalars c;
+        std::memcpy(&c, p, sizeof(c));
+        const size_t words = (size_t)info.n * (size_t)c.channels;
+        std::vector<float> values(words);
+        std::memcpy(values.data(), p + sizeof(c), 4 * words);
+        if ((rc = sph_scalars_set(e, values.data(), (size_t)info.n, c.channels, c.coeffs))) return rc;
+        if (c.hasCouple) {
+            SphScalarSource src[SPH_MAX_SCALAR_SOURCES];
+            std::memcpy(src, c.src, sizeof(src));
+            if ((rc = couple_ensure(e)) || (rc = sph_scalars_set_buoyancy(e, c.beta, c.ref)) || (rc = sph_scalars_set_sources(e, src, c.nSrc))) return rc;
+            HIP_TRY(hipMemcpyAsync(e->d_cpAcc, p + sizeof(c) + sph::state_pad8(4ull * words), sizeof(sph::CoupleAcc), hipMemcpyHostToDevice, e->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_scState, p + offsetof(sph::StateScalars, stateWord), 4, hipMemcpyHostToDevice, e->stream));
+        e->scSteps = c.steps;
+    }
+    if (info.sections & SPH_STATE_DIFFUSE) {
+        const unsigned char* p = b + info.offset[3];
+        sph::StateDiffuse d;
+        std::memcpy(&d, p, sizeof(d));
+        const unsigned char* words = p + sizeof(d);
+        const unsigned char* crestWords = words + sph::state_pad8(4ull * sph::DF_WORDS);
+        const unsigned char* pool = crestWords + (d.hasCrestBooks ? sph::state_pad8(4ull * sph::DFC_WORDS) : 0u);
+        if ((rc = sph_diffuse_set(e, &d.cfg))) return rc;
+        if (d.hasCrestBooks) {                                        // (the books exist once the term was on; off again: the books stay)
+            SphDiffuseCrest on;
+            sph_diffuse_crest_default(&on);
+            if ((rc = sph_diffuse_set_crest(e, d.crestOn ? &d.crest : &on)) || (!d.crestOn && (rc = sph_diffuse_set_crest(e, nullptr)))) return rc;
+            HIP_TRY(hipMemcpyAsync(e->d_dfCrState, crestWords, 4u * sph::DFC_WORDS, hipMemcpyHostToDevice, e->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_dfState, words, 4u * sph::DF_WORDS, hipMemcpyHostToDevice, e->stream));
+        if (d.alive) HIP_TRY(hipMemcpyAsync(e->d_dfPool, pool, (size_t)d.alive * sizeof(SphDiffuse), hipMemcpyHostToDevice, e->stream));
+    }
+    if (info.sections & SPH_STATE_TRACERS) {
+        const unsigned char* p = b + info.offset[2];
+        sph::StateTracers t;
+        std::memcpy(&t, p, sizeof(t));
+        const unsigned char* recs = p + sizeof(t);
+        std::vector<float> pts(4 * t.m);
+        for (uint64_t i = 0; i < t.m; ++i) std::memcpy(&pts[4 * i], recs + 32 * i, 16);
+        if ((rc = sph_tracers_set(e, pts.data(), (size_t)t.m, (int)t.integrator, t.history, t.stride))) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_trRec, recs, 32 * t.m, hipMemcpyHostToDevice, e->stream));
+        const uint64_t slots = sph::state_tracer_slots(t.hostSteps, t.history, t.stride);
+        if (slots) HIP_TRY(hipMemcpyAsync(e->d_trRing, recs + 32 * t.m, 16ull * slots * t.m, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->d_trState, p + offsetof(sph::StateTracers, state), 12, hipMemcpyHostToDevice, e->stream));
+        e->trSteps = t.hostSteps;
+        e->trSorted = t.hostSteps;                                    // (not ordered yet: the next dispatch sorts)
+    }
+    if (info.sections & SPH_STATE_GATES) {
+        const unsigned char* p = b + info.offset[6];
+        sph::StateGates g;
+        std::memcpy(&g, p, sizeof(g));
+        if ((rc = sph_gates_set(e, g.set, g.count, g.history, g.stride))) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_gtAcc, p + sizeof(g), sizeof(sph::GateAcc), hipMemcpyHostToDevice, e->stream));
+        if (g.history) HIP_TRY(hipMemcpyAsync(e->d_gtRing.p, p + sizeof(g) + sizeof(sph::GateAcc), 8ull * g.history * sph::kGateRingRow, hipMemcpyHostToDevice, e->stream));
+    }
+    if (info.sections & SPH_STATE_MONITORS) {
+        const unsigned char* dir = b + info.offset[7];
+        const unsigned char* p = dir + sizeof(sph::StateMonitorSlot) * sph::kMonitorMax;
+        for (int i = 0; i < sph::kMonitorMax; ++i) {
+            sph::StateMonitorSlot s;
+            std::memcpy(&s, dir + sizeof(s) * i, sizeof(s));
+            if (s.kind == SPH_MONITOR_NONE) continue;
+            unsigned long long ca[2];
+            double time;
+            std::memcpy(ca, p, 16); std::memcpy(&time, p + 16, 8);
+            p += sph::kStateMonitorCounters;
+            if (s.kind == SPH_MONITOR_POINTS) {
+                std::vector<float> pts(4 * s.m);
+                std::memcpy(pts.data(), p, 16 * s.m);
+                p += 16 * s.m;
+                if ((rc = sph_monitor_set(e, i, pts.data(), (size_t)s.m, &s.cfg))) return rc;
+            } else if ((rc = sph_monitor_set_lattice(e, i, s.origin, s.spacing, s.dims, &s.cfg))) return rc;
+            MonitorSlot& m = e->mon[i];
+            HIP_TRY(hipMemcpyAsync(m.d_rows.p, p, sizeof(sph::MonitorRow) * s.m, hipMemcpyHostToDevice, e->stream));
+            p += sizeof(sph::MonitorRow) * s.m;
+            const size_t ring = (size_t)s.cfg.history * s.cfg.ringPoints * sizeof(SphSample);
+            if (ring) HIP_TRY(hipMemcpyAsync(m.d_ring.p, p, ring, hipMemcpyHostToDevice, e->stream));
+            p += ring;
+            if (s.cfg.history) HIP_TRY(hipMemcpyAsync(m.d_times.p, p, 8ull * s.cfg.history, hipMemcpyHostToDevice, e->stream));
+            p += 8ull * s.cfg.history;
+            sph::MonitorTab tab = m.tab;                              // the table of the set, with the saved counters and what follows from them
+            tab.c = ca[0]; tab.a = ca[1]; tab.time = time;
+            tab.act = sph::monitor_acts(tab.c, tab.every) ? 1u : 0u;
+            tab.row = sph::monitor_row_of(tab.a, tab.history, tab.stride);
+            sph::MonitorTab* slot = nullptr;
+            if ((rc = m.stage.next(&slot))) return rc;
+            *slot = tab;
+            HIP_TRY(hipMemcpyAsync(m.d_tab, slot, sizeof(sph::MonitorTab), hipMemcpyHostToDevice, e->stream));
+            if ((rc = m.stage.commit(e->stream))) return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
 

@@ -453,6 +453,49 @@ assert C.sizeof(SphSlabIntent) == 64
 KERNEL_CLASSES = ("bin", "scan", "scatter", "sph", "writeback", "impulse", "other")     # SPH_K_* of "measurement"
 
 
+# ---- checkpoints (include/sph_abi.h "checkpoints"): the records the library fills, and the blob's header and table entry -----
+SPH_STATE_FORMAT = 1
+SPH_STATE_CHECKSUM_MIX64 = 1
+SPH_STATE_MAGIC = 0x4554415453485053                                       # "SPHSTATE"
+STATE_SECTIONS = ("core", "particles", "tracers", "diffuse", "scalars", "obstacles", "gates", "monitors")   # the section with tag 1 << i
+
+
+class SphStateInfo(C.Structure):
+    _fields_ = [("formatVersion", C.c_uint32), ("abiVersion", C.c_uint32), ("checksumKind", C.c_uint32), ("sections", C.c_uint32),
+                ("n", C.c_uint64), ("totalBytes", C.c_uint64), ("params", SphParams), ("pad", C.c_uint32),
+                ("version", C.c_uint32 * len(STATE_SECTIONS)), ("offset", C.c_uint64 * len(STATE_SECTIONS)),
+                ("bytes", C.c_uint64 * len(STATE_SECTIONS)), ("sum", (C.c_uint64 * 2) * len(STATE_SECTIONS)),
+                ("terrainCount", C.c_uint64), ("terrainOffset", C.c_uint64), ("stencilCount", C.c_uint64)]
+
+
+class SphStateDigest(C.Structure):
+    _fields_ = [("sections", C.c_uint32), ("pad", C.c_uint32), ("sum", (C.c_uint64 * 2) * len(STATE_SECTIONS))]
+
+
+class SphStateHeader(C.Structure):
+    """The first 256 bytes of a blob."""
+    _fields_ = [("magic", C.c_uint64), ("format", C.c_uint32), ("abi", C.c_uint32), ("checksumKind", C.c_uint32), ("sectionCount", C.c_uint32),
+                ("n", C.c_uint64), ("totalBytes", C.c_uint64), ("sectionMask", C.c_uint32), ("headerBytes", C.c_uint32),
+                ("params", SphParams), ("zero", C.c_ubyte * (240 - 48 - C.sizeof(SphParams))), ("sum", C.c_uint64 * 2)]
+
+
+class SphStateEntry(C.Structure):
+    """One entry of a blob's section table."""
+    _fields_ = [("tag", C.c_uint32), ("version", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("sum", C.c_uint64 * 2)]
+
+
+class SphStateCore(C.Structure):
+    """The record the core section opens with; the heightfield and the stencil targets follow it."""
+    _fields_ = [("params", SphParams), ("lastDt", C.c_float), ("fountain", SphFountain), ("river", SphRiver),
+                ("terrainCount", C.c_uint64), ("stencilCount", C.c_uint64)]
+
+
+assert C.sizeof(SphStateCore) == 280
+STATE_HEADER_DTYPE = np.dtype(SphStateHeader)
+STATE_ENTRY_DTYPE = np.dtype(SphStateEntry)
+assert STATE_HEADER_DTYPE.itemsize == 256 and STATE_ENTRY_DTYPE.itemsize == 40 and STATE_HEADER_DTYPE.fields["sum"][1] == 240
+
+
 # ---- the C-ABI: every function include/sph_abi.h declares, in its order, as name -> (restype, argtypes) -------------------
 # The one statement of the binding: ABI_SYMBOLS and load_library() derive from it, tests/test_abi.py holds it against the header's
 # prototypes.  A record that only passes through (particles, samples, tracers, obstacles ...) crosses as c_void_p.
@@ -698,6 +741,13 @@ _ABI = {
     "sph_slab_step_times": (_int, [_vp, _pf]),
     # measurement
     "sph_kernel_times": (_int, [_vp, _P(_d), _P(C.c_int64), _int]),
+    # checkpoints
+    "sph_state_size": (_int, [_vp, _P(_sz)]),
+    "sph_state_save": (_int, [_vp, _vp, _sz, _P(_sz)]),
+    "sph_state_load": (_int, [_vp, _vp, _sz]),
+    "sph_state_peek": (_int, [_vp, _sz, _P(SphStateInfo)]),
+    "sph_state_digest": (_int, [_vp, _u32, _P(SphStateDigest)]),
+    "sph_state_checksum_host": (_int, [_vp, _sz, _P(_u64)]),
 }
 ABI_SYMBOLS = tuple(_ABI)
 
@@ -2265,6 +2315,56 @@ class SPHFluidGPU:
         _check(self._L.sph_kernel_times(self._h, ms, cnt, 1 if reset else 0))
         return {k: (ms[i], cnt[i]) for i, k in enumerate(KERNEL_CLASSES)}
 
+    # -- checkpoints (include/sph_abi.h "checkpoints") ---------------------------------------
+    def save_state(self, path=None) -> np.ndarray:
+        """The engine's state as a blob (a uint8 array), written to `path` too if one is given.  Synchronises; the members are pushed
+        first, as before a dispatch, so the blob carries the values the next substep would have read."""
+        self._push_members()
+        need = C.c_size_t(0)
+        _check(self._L.sph_state_size(self._h, C.byref(need)))
+        blob = np.zeros(need.value, np.uint8)
+        _check(self._L.sph_state_save(self._h, _ptr(blob), blob.size, C.byref(need)))
+        if path is not None:
+            blob.tofile(path)
+        return blob
+
+    def load_state(self, blob_or_path):
+        """Make this engine what the saved one was (whatever it held before), and refresh every host-side mirror of the class: the
+        param_*, fountain* and river members with the heightfield, numParticles, stencilCount.  SphError on a bad blob: the engine is
+        then unchanged."""
+        blob = _state_blob(blob_or_path)
+        info = SphStateInfo()
+        _check(self._L.sph_state_peek(_ptr(blob), blob.size, C.byref(info)))         # (where the heightfield lies, from the library: no offsets by hand)
+        _check(self._L.sph_state_load(self._h, _ptr(blob), blob.size))
+        _check(self._L.sph_get_params(self._h, C.byref(self._p)))
+        _check(self._L.sph_get_fountain(self._h, C.byref(self._f)))
+        _check(self._L.sph_get_river(self._h, C.byref(self._r)))
+        at = int(info.terrainOffset)
+        self.terrainHeights = blob[at:at + 4 * int(info.terrainCount)].view(np.float32).copy()
+        self._terrain_sent = self.terrainHeights                     # (the library holds exactly these)
+        self.stencilCount = int(info.stencilCount)
+        self.numParticles = self.GetNumFluids()
+
+    @classmethod
+    def from_state(cls, blob_or_path, stream: int | None = None) -> "SPHFluidGPU":
+        """A new engine that continues the saved run: created from the blob's particle count and params, then loaded."""
+        blob = _state_blob(blob_or_path)
+        info = state_info(blob)
+        f = cls(1, params=info["params"], stream=stream, _particles=np.zeros(1, PARTICLE_DTYPE))     # (the load re-sizes it)
+        f.load_state(blob)
+        return f
+
+    def state_digest(self, sections=None) -> dict:
+        """name -> (lo, hi) of the sections the engine holds (sections: names, or None for all): their checksums computed on the device,
+        by definition what a blob saved now stores for them.  Synchronises."""
+        self._push_members()
+        mask = 0
+        for name in (sections or ()):
+            mask |= 1 << STATE_SECTIONS.index(name)
+        d = SphStateDigest()
+        _check(self._L.sph_state_digest(self._h, mask, C.byref(d)))
+        return {name: (int(d.sum[i][0]), int(d.sum[i][1])) for i, name in enumerate(STATE_SECTIONS) if d.sections & (1 << i)}
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._L.sph_destroy(self._h)
@@ -2842,6 +2942,63 @@ def monitor_schedule_host(every: int, stride: int, history: int, substeps: int):
     acts, rows = np.zeros(substeps, np.uint32), np.zeros(substeps, np.uint32)
     _check(load_library().sph_monitor_schedule_host(int(every), int(stride), int(history), int(substeps), _ptr(acts), _ptr(rows)))
     return acts, rows
+
+
+# ---- checkpoints: the host-only calls and the pure-Python twin of the parser ---------------------------------------------
+def _state_blob(blob_or_path) -> np.ndarray:
+    """A blob as a contiguous uint8 array: an array or bytes as they are, anything else is a path to read."""
+    if isinstance(blob_or_path, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(blob_or_path), np.uint8)
+    if isinstance(blob_or_path, np.ndarray):
+        return np.ascontiguousarray(blob_or_path).view(np.uint8).reshape(-1)
+    return np.fromfile(blob_or_path, np.uint8)
+
+
+def _state_dict(formatVersion, abiVersion, checksumKind, n, totalBytes, params, sections) -> dict:
+    return dict(formatVersion=int(formatVersion), abiVersion=int(abiVersion), checksumKind=int(checksumKind), n=int(n), totalBytes=int(totalBytes),
+                params=params, sections=sections)
+
+
+def state_info(blob) -> dict:
+    """sph_state_peek: the blob validated whole (SphError names what is wrong) and its header and section table: formatVersion,
+    abiVersion, checksumKind, n, totalBytes, params, and sections: name -> dict(version, offset, bytes, sum=(lo, hi))."""
+    blob = _state_blob(blob)
+    info = SphStateInfo()
+    _check(load_library().sph_state_peek(_ptr(blob), blob.size, C.byref(info)))
+    secs = {name: dict(version=int(info.version[i]), offset=int(info.offset[i]), bytes=int(info.bytes[i]), sum=(int(info.sum[i][0]), int(info.sum[i][1])))
+            for i, name in enumerate(STATE_SECTIONS) if info.sections & (1 << i)}
+    params = SphParams()
+    C.memmove(C.byref(params), C.byref(info.params), C.sizeof(SphParams))
+    return _state_dict(info.formatVersion, info.abiVersion, info.checksumKind, info.n, info.totalBytes, params, secs)
+
+
+def state_checksum_host(buf):
+    """sph_state_checksum_host: (lo, hi) of a buffer of a multiple of 8 bytes (an array of any dtype, or bytes)."""
+    arr = _state_blob(buf)
+    out = (C.c_uint64 * 2)()
+    _check(load_library().sph_state_checksum_host(_ptr(arr) if arr.size else None, arr.size, out))
+    return int(out[0]), int(out[1])
+
+
+def state_sections(blob) -> dict:
+    """The header and section table of a blob read in Python from the documented format (include/sph_abi.h): what state_info returns,
+    without the library and WITHOUT its validation (no checksum is verified, no size is checked beyond what the reading needs)."""
+    blob = _state_blob(blob)
+    if blob.size < STATE_HEADER_DTYPE.itemsize:
+        raise SphError(f"state_sections: {blob.size} bytes are less than a header")
+    h = blob[:STATE_HEADER_DTYPE.itemsize].view(STATE_HEADER_DTYPE)[0]
+    if int(h["magic"]) != SPH_STATE_MAGIC:
+        raise SphError("state_sections: wrong magic")
+    end = STATE_HEADER_DTYPE.itemsize + STATE_ENTRY_DTYPE.itemsize * int(h["sectionCount"])
+    if blob.size < end:
+        raise SphError("state_sections: the section table is truncated")
+    secs = {}
+    for s in blob[STATE_HEADER_DTYPE.itemsize:end].view(STATE_ENTRY_DTYPE):
+        tag = int(s["tag"])
+        name = STATE_SECTIONS[tag.bit_length() - 1] if tag and tag & (tag - 1) == 0 and tag.bit_length() <= len(STATE_SECTIONS) else f"tag{tag}"
+        secs[name] = dict(version=int(s["version"]), offset=int(s["offset"]), bytes=int(s["bytes"]), sum=(int(s["sum"][0]), int(s["sum"][1])))
+    params = SphParams.from_buffer_copy(h["params"].tobytes())
+    return _state_dict(h["format"], h["abi"], h["checksumKind"], h["n"], h["totalBytes"], params, secs)
 
 
 def monitor_means(rows) -> dict:

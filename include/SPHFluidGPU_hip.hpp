@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -721,6 +722,49 @@ public:
         out.resize(sph_num_particles(engine));
         return !Check(sph_download_particles(engine, reinterpret_cast<SphParticle*>(out.data()), out.size()), "sph_download_particles");
     }
+    // ---- checkpoints (sph_abi.h "checkpoints"): SaveState pushes the members first, as a dispatch would; LoadState makes the engine what
+    // the saved one was and refreshes every member this class mirrors (param_*, fountain*, river*, terrainHeights, particles, numParticles,
+    // stencilCount, the grid).  A refused blob leaves engine and members as they were.  All three synchronise.  Return false on error.
+    bool SaveState(std::vector<unsigned char>& blob) {
+        if (PushMembers()) return false;
+        size_t need = 0;
+        if (Check(sph_state_size(engine, &need), "sph_state_size")) return false;
+        blob.assign(need, 0);
+        return !Check(sph_state_save(engine, blob.data(), blob.size(), &need), "sph_state_save");
+    }
+    bool LoadState(const void* blob, size_t bytes) {
+        SphStateInfo info;
+        if (Check(sph_state_peek(blob, bytes, &info), "sph_state_peek") || Check(sph_state_load(engine, blob, bytes), "sph_state_load")) return false;
+        SphParams p;
+        SphFountain f;
+        SphRiver r;
+        if (Check(sph_get_params(engine, &p), "sph_get_params") || Check(sph_get_fountain(engine, &f), "sph_get_fountain") ||
+            Check(sph_get_river(engine, &r), "sph_get_river")) return false;
+        FromParams(p);
+        fountainMode = f.fountainMode != 0; fountainOffset = MATH::Vec3(f.fountainOffset[0], f.fountainOffset[1], f.fountainOffset[2]);
+        fountainRadius = f.fountainRadius; fountainSpread = f.fountainSpread; fountainJetSpeedLive = f.fountainJetSpeedLive;
+        fountainDrainLevel = f.fountainDrainLevel; fountainDrainPerSec = f.fountainDrainPerSec; fountainSeed = f.fountainSeed;
+        riverMode = r.riverMode != 0; terrainW = r.terrainW; terrainH = r.terrainH;
+        terrainWorldMinX = r.terrainWorldMinX; terrainWorldMinZ = r.terrainWorldMinZ; terrainWorldSizeX = r.terrainWorldSizeX; terrainWorldSizeZ = r.terrainWorldSizeZ;
+        riverEmitterPos = MATH::Vec3(r.riverEmitterPos[0], r.riverEmitterPos[1], r.riverEmitterPos[2]);
+        riverEmitterVel = MATH::Vec3(r.riverEmitterVel[0], r.riverEmitterVel[1], r.riverEmitterVel[2]);
+        riverEmitterRadius = r.riverEmitterRadius; riverSinkY = r.riverSinkY; riverSinkZMax = r.riverSinkZMax;
+        riverAmp = r.riverAmp; riverFreq = r.riverFreq; riverPhase = r.riverPhase;
+        riverChannelWidth = r.riverChannelWidth; riverChannelDepth = r.riverChannelDepth; riverSlopeDrop = r.riverSlopeDrop;
+        terrainHeights.resize(size_t(info.terrainCount));
+        if (info.terrainCount) std::memcpy(terrainHeights.data(), static_cast<const unsigned char*>(blob) + info.terrainOffset, 4 * size_t(info.terrainCount));
+        terrainDirty = false;
+        stencilCount = int(info.stencilCount);
+        numParticles = size_t(info.n);
+        surface = SphSurface{};
+        AfterSpawn();
+        return true;
+    }
+    bool StateDigest(SphStateDigest& out, uint32_t sections = 0) {
+        if (PushMembers()) return false;
+        return !Check(sph_state_digest(engine, sections, &out), "sph_state_digest");
+    }
+    static bool PeekState(const void* blob, size_t bytes, SphStateInfo& out) { return sph_state_peek(blob, bytes, &out) == SPH_OK; }
     void Sync() { Check(sph_sync(engine), "sph_sync"); }
     const std::string& LastError() const { return lastError; }
     SphEngine* Handle() { return engine; }
@@ -803,6 +847,14 @@ private:
         if (Check(sph_set_river(engine, &r, send ? terrainHeights.data() : nullptr), "sph_set_river")) return true;
         if (send) terrainDirty = false;
         return false;
+    }
+    bool PushMembers() {                       // what DispatchCompute sends ahead of a substep; true on error
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return true;
+        SphFountain f{fountainMode ? 1 : 0, {fountainOffset.x, fountainOffset.y, fountainOffset.z}, fountainRadius, fountainSpread,
+                      fountainJetSpeedLive, fountainDrainLevel, fountainDrainPerSec, fountainSeed};
+        if (Check(sph_set_fountain(engine, &f), "sph_set_fountain")) return true;
+        return PushRiver();
     }
     SphParams ToParams() const {
         SphParams p;

@@ -60,6 +60,7 @@ extern "C" {
 /* (still 4, additions only: SphRaySpan, SphRaySpansInfo, sph_rays_span / _span_device / _span_info / _span_rows / _span_download / _span_host / _span_walk_host, SPH_OPT_RAY_SPANS_VARIANT -- ray spans: what each ray crosses in all) */
 /* (still 4, additions only: SphAniso, SphAnisoConfig, SphAnisoInfo, SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID / _SPARSE / _CLAMPED, sph_aniso_default / _build / _info / _device / _download / _lattice / _surface / _host / _lattice_host -- anisotropic kernels) */
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
+/* (still 4, additions only: SphStateInfo, SphStateDigest, SPH_STATE_*, sph_state_size / _save / _load / _peek / _digest / _checksum_host -- checkpoints) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -1532,6 +1533,115 @@ enum {
 /* Accumulated hipEvent milliseconds and launch counts per kernel class since the
  * last reset (SPH_OPT_TIMING must be 1). Synchronises. */
 int sph_kernel_times(SphEngine* e, double msOut[SPH_K_COUNT], int64_t launchesOut[SPH_K_COUNT], int reset);
+
+/* ---- checkpoints: save, restore and digest the engine's state ------------------------------
+ * A checkpoint is a blob of bytes from which another engine continues the run bit for bit: the records and the outputs of every
+ * feature the blob carries are those of the uninterrupted run.  The digest is the checksum of a section computed on the device: two
+ * engines whose digests agree hold the same state, and a blob proves on load that it is intact.
+ *
+ * The blob is little-endian.  All offsets are from the blob's first byte.
+ *   header, 256 bytes
+ *       0  uint64   magic "SPHSTATE" (0x4554415453485053)
+ *       8  uint32   format version (SPH_STATE_FORMAT)          12  uint32  sph_abi_version() of the saving library
+ *      16  uint32   checksum kind (SPH_STATE_CHECKSUM_MIX64)   20  uint32  number of sections
+ *      24  uint64   n, the particle count                      32  uint64  total bytes of the blob
+ *      40  uint32   mask of the sections present (SPH_STATE_*) 44  uint32  256, the header's size
+ *      48  SphParams of the saved engine (132 bytes), then zeros up to byte 240
+ *     240  2 x uint64  checksum of bytes [0, 240) and of the section table (word indices run on from the header into the table)
+ *   section table at 256: per section 40 bytes
+ *       0  uint32 tag (one SPH_STATE_* bit)   4  uint32 section version (1)   8  uint64 offset   16  uint64 bytes (a multiple of 8)
+ *      24  2 x uint64 checksum of the payload (word index 0 at its first byte)
+ *   payloads, in the table's order (ascending tags), each at the next multiple of 16 behind what lies before it, the gaps and the
+ *   end of the blob (a multiple of 16) filled with zeros.  The layout is canonical: a blob with one byte changed anywhere is refused.
+ *
+ * The checksum of a byte range read as little-endian 64-bit words w_i (i from a base word index, 0 unless stated):
+ *       lane L = sum over i of mix64(w_i + C_L + (base + i) * G) mod 2^64,  L = 0, 1
+ *       mix64(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31   (splitmix64's finaliser)
+ *       G = 0x9e3779b97f4a7c15, C_0 = 0x243f6a8885a308d3, C_1 = 0x13198a2e03707344
+ * The terms are keyed by the word index (swapping two different records changes the sums) and the sums commute, so the checksum of a
+ * concatenation is the sum of the pieces' checksums at their base indices.  It is an integrity check, not a cryptographic hash.
+ *
+ * Sections (the records are StateCore, StateTracers, StateDiffuse, StateScalars, StateObstacles, StateGates, StateMonitorSlot of csrc/sph_state.h):
+ *   CORE       SphParams, lastDt, SphFountain (with the current seed), SphRiver, uint64 terrain count T, uint64 stencil count S; T floats of the
+ *              heightfield (padded with zeros to 8 bytes); S float4 stencil targets
+ *   PARTICLES  the n 80-byte records by particle id, exactly what sph_download_particles returns
+ *   TRACERS    uint64 M, uint32 integrator, history K, stride, the three device words (substeps low / high, next ring slot), uint64 host
+ *              mirror of the step counter c; M 32-byte records in the caller's order; the written slots of the pathline ring, min(c / stride + 1, K)
+ *              x M float4 in slot order (a slot no snapshot has reached yet holds nothing a call returns, and is not saved)
+ *   GATES      int32 count, uint32 history H, stride, words per books table A, words per ring row R, 0; SPH_MAX_GATES SphGate as set; A 8-byte
+ *              words of the books (all gates' SphGateBooks, time, substeps, ring substeps); H x R words of the ring
+ *   MONITORS   SPH_MAX_MONITORS slot records of 80 bytes (kind, 0, uint64 points M, dims, origin, spacing, the config in force, 0); then per slot
+ *              that holds a monitor: substeps, acting substeps (uint64), time (double); M float4 points (explicit points only); M 128-byte
+ *              rows; history x ringPoints 32-byte samples; history doubles
+ *   DIFFUSE    SphDiffuseConfig, SphDiffuseCrest in force, uint32 crest on, crest books exist, state words W, crest words V, alive A, 0; W
+ *              32-bit state words of the pool (alive, substep counter, class counts, totals; padded to 8 bytes); V crest words if the books
+ *              exist (padded); the A living 48-byte records in pool order
+ *   SCALARS    int32 K, uint32 table exists, bytes of the injected books B, the device word of the last diffusion number, uint64 substeps,
+ *              8 floats D_k and lambda_k, 4 beta, 4 ref, int32 sources, 3 x 0, SPH_MAX_SCALAR_SOURCES SphScalarSource; n x K floats by
+ *              particle id (padded to 8 bytes); B bytes of the books (sums, hits, time, substeps) if the table exists
+ *   OBSTACLES  int32 bodies C, uint32 bytes of a device body record R, of a device dynamics record D, of the impulse sums S; 16 x int32 shape,
+ *              dynamic, bound volume (-1: none); 16 SphObstacleDynamics as set; 16 x (dims[3], spacing[3]) per volume slot (dims 0: empty);
+ *              C x R bytes of the bodies as they stand on the device (advanced poses); S bytes of the sums (C > 0); C x D bytes; per volume
+ *              slot in use its dims[0] x dims[1] x dims[2] floats (padded to 8 bytes).  R, D and S must be this build's.
+ * A section is present iff the saved engine held the feature (gates: at least one gate).  CORE and PARTICLES always are.
+ *
+ * NOT saved: query results (neighbour lists, components, kNN rows, ray hits and spans, shell, aniso, surface, statistics: derived; after a
+ * load they are "no result", as after sph_reset); timing sums, debug counters and the graph cache (a load empties it); engine options
+ * (they do not change bits; the loading engine keeps its own, so a blob saved under one pass variant, record mode or graph setting is
+ * continued under another); the initial particles (after a load sph_initial_particles returns the loaded records, as after
+ * sph_create_from_particles).  The processing orders (slot order, the tracers' and monitors' perm) are rebuilt: no output depends on them. */
+#define SPH_STATE_FORMAT 1
+#define SPH_STATE_CHECKSUM_MIX64 1
+#define SPH_STATE_SECTION_COUNT 8
+enum {
+    SPH_STATE_CORE = 1, SPH_STATE_PARTICLES = 2, SPH_STATE_TRACERS = 4, SPH_STATE_DIFFUSE = 8, SPH_STATE_SCALARS = 16, SPH_STATE_OBSTACLES = 32,
+    SPH_STATE_GATES = 64, SPH_STATE_MONITORS = 128
+};
+/* What sph_state_peek reads from a blob; section with tag 1 << i is at index i (bytes 0: absent). */
+typedef struct SphStateInfo {
+    uint32_t formatVersion, abiVersion, checksumKind, sections;
+    uint64_t n, totalBytes;
+    SphParams params;
+    uint32_t pad;
+    uint32_t version[SPH_STATE_SECTION_COUNT];
+    uint64_t offset[SPH_STATE_SECTION_COUNT], bytes[SPH_STATE_SECTION_COUNT];
+    uint64_t sum[SPH_STATE_SECTION_COUNT][2];
+    uint64_t terrainCount, terrainOffset;   /* of the core section: the heightfield's floats and where they lie in the blob (count 0: none) */
+    uint64_t stencilCount;                  /* the stencil targets it carries */
+} SphStateInfo;
+/* The digests of a live engine: sum[i] is the checksum a blob saved now would store for the section with tag 1 << i. */
+typedef struct SphStateDigest {
+    uint32_t sections;                 /* the sections digested (those asked for that the engine holds) */
+    uint32_t pad;
+    uint64_t sum[SPH_STATE_SECTION_COUNT][2];
+} SphStateDigest;
+
+/* The bytes sph_state_save would write now. */
+int sph_state_size(SphEngine* e, size_t* bytes);
+/* Writes the blob.  Synchronises; brings the 80-byte records up to date as sph_download_particles does and changes nothing else a later
+ * dispatch reads: a run with saves gives the bytes of the run without.  cap too small: SPH_ERR_CAPACITY, *written holds the need.
+ * SPH_ERR_STATE on a z-slab engine. */
+int sph_state_save(SphEngine* e, void* blob, size_t cap, size_t* written);
+/* Makes the engine what the saved one was, whatever it held before (another n, other features, junk books): the sph_reset path for the
+ * particles, every feature's own set path for its buffers, then the saved buffers and counters over what the set calls zeroed.  Features
+ * the blob does not carry are cleared (obstacles and volumes too).  A volume comes back in the slot it had.  Synchronises.
+ * Everything is validated BEFORE the engine is touched -- the blob as by sph_state_peek, then the params and every feature's config by
+ * the checks of the set calls: a bad blob is SPH_ERR_ARG with a message that names what is wrong, and the engine is bit for bit what it
+ * was (sph_state_digest proves it).  SPH_ERR_STATE on a z-slab engine, and under SPH_OPT_GRID_BUILD 1 for a blob with feature sections,
+ * before anything is touched.  Only a failing HIP call (an allocation, say) can stop a load halfway: the engine is then valid and
+ * destroyable, it holds the blob's core state and particles if those were reached, the features restored before the failure, and none
+ * of the others; load again or sph_reset. */
+int sph_state_load(SphEngine* e, const void* blob, size_t bytes);
+/* Host only, no device: validates the whole blob (magic, versions, layout, every size against its own config, every checksum) and
+ * reports its header and section table. */
+int sph_state_peek(const void* blob, size_t bytes, SphStateInfo* out);
+/* The checksums of the engine's sections computed on the device (sections: a mask of SPH_STATE_*, 0 = all the engine holds): no array
+ * moves to the host, one read of 16 bytes per section.  What is read first, because a size or a count lies there: the pool's state and
+ * crest words (112 bytes), the scalars' diffusion word, and the last 32-bit word of an array with an odd number of them.  By definition
+ * what a blob saved at this moment stores (sph_state_peek's sum).  Brings the records up to date like sph_state_save.  Synchronises. */
+int sph_state_digest(SphEngine* e, uint32_t sections, SphStateDigest* out);
+/* Host only: the checksum above of n bytes (n % 8 == 0) at base word index 0. */
+int sph_state_checksum_host(const void* bytes, size_t n, uint64_t out[2]);
 
 #ifdef __cplusplus
 }
