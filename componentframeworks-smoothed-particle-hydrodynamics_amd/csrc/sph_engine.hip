@@ -143,6 +143,27 @@ struct StageRing {
     }
 };
 
+// Records the kernels read from device memory (a replayed graph sees a later upload), with the pinned staging of their stream-ordered
+// uploads.  No destructor, like DevBuf.
+template <class T>
+struct DevTable {
+    T* p = nullptr;
+    StageRing<T> stage;                              // `count` records per slot
+    // The first call makes `count` records and the staging; a failure leaves nothing behind (`what` names the staging in its message).
+    int ensure(SphEngine* e, size_t count, const char* what);
+    int slot(T** out) { return stage.next(out); }    // the next pinned slot, to be filled in place and sent
+    int send(SphEngine* e, size_t n = 1, size_t at = 0) { return send_part(e, 0, n * sizeof(T), at); }   // the slot's first n records to records at ..
+    int send_part(SphEngine* e, size_t off, size_t bytes, size_t at);   // `bytes` at byte `off` of the slot's first record to the same bytes of record `at`
+    int put(SphEngine* e, const T* src, size_t n = 1, size_t at = 0) {  // n finished records through the next slot
+        T* s = nullptr;
+        const int rc = slot(&s);
+        if (rc) return rc;
+        std::memcpy(s, src, n * sizeof(T));
+        return send(e, n, at);
+    }
+    void release() { dev_free(p); stage.destroy(); }
+};
+
 inline int blocks_for(size_t n, int per = sph::kBlock) { return (int)((n + per - 1) / per); }
 
 // The scratch of one 64-bit scan (scan_counts64_launch) of `rows` counts: blocks_for(rows, kScanTile) + 2 words of tile sums (the totals,
@@ -158,18 +179,17 @@ struct ScanScratch {
     void release() { tileSums.release(); tileMax.release(); }
 };
 
-// One field monitor (sph_monitor.h): the table the kernels read (device memory: a replayed graph sees a later set or
-// reset) with the table as uploaded last and its pinned staging, the points and their processing order (explicit points only), the rows,
-// the ring of history x ringPoints samples (two float4 each) and its history times.  Buffers only grow while the slot lives.
+// One field monitor (sph_monitor.h): the table the kernels read with the table as uploaded last, the points and
+// their processing order (explicit points only), the rows, the ring of history x ringPoints samples (two float4 each) and its history
+// times.  Buffers only grow while the slot lives.
 struct MonitorSlot {
     int kind = SPH_MONITOR_NONE;
     size_t m = 0;
     int dims[3] = {0, 0, 0};
     float origin[3] = {0.0f, 0.0f, 0.0f}, spacing[3] = {0.0f, 0.0f, 0.0f};
     SphMonitorConfig cfg{};
-    sph::MonitorTab* d_tab = nullptr;
+    DevTable<sph::MonitorTab> d_tab;
     sph::MonitorTab tab{};
-    StageRing<sph::MonitorTab> stage;
     DevBuf<float4> d_points, d_ring;
     DevBuf<uint32_t> d_perm;
     DevBuf<sph::MonitorRow> d_rows;
@@ -372,14 +392,12 @@ struct SphEngine {
     bool capturing = false;              // sph_dispatch_n is capturing its launches into a graph
 
     // sph_diffuse_* (sph_diffuse.h): the pool of C records (three float4 each) and the scratch pool a substep advances
-    // into, the device state words (alive count, substep counter, totals), the coefficients as the kernels read them (device memory: a
-    // replayed graph sees a later change) with their pinned staging, the survivor flags with their scan, the per-block counts, and the
-    // child counts in id order with their scan
+    // into, the device state words (alive count, substep counter, totals), the coefficients as the kernels read them, the survivor flags
+    // with their scan, the per-block counts, and the child counts in id order with their scan
     float4* d_dfPool = nullptr;
     float4* d_dfScratch = nullptr;
     uint32_t* d_dfState = nullptr;
-    sph::DiffuseCoef* d_dfCoef = nullptr;
-    StageRing<sph::DiffuseCoef> dfStage;
+    DevTable<sph::DiffuseCoef> d_dfCoef;
     uint32_t *d_dfFlag = nullptr, *d_dfFlagStart = nullptr, *d_dfFlagSums = nullptr, *d_dfPart = nullptr;
     DevBuf<uint32_t> d_dfCnt, d_dfCntStart, d_dfCntSums;
     uint32_t dfC = 0;                    // capacity of the pool (0: none)
@@ -387,12 +405,11 @@ struct SphEngine {
     int optDiffuseTimed = 0;             // SPH_OPT_DIFFUSE_TIMED: which launches of the substep the timing bracket covers (0 all, 1 advance, 2 the rest)
     SphDiffuseConfig dfCfg{};            // the config in force
     // crest births of the pool (sph_diffuse_set_crest): the coefficients and the books in device memory (made by the first set, kept as
-    // long as the pool) with their pinned staging, and the scratch of the shell pass by slot, all its own (a captured graph bakes the
+    // long as the pool), and the scratch of the shell pass by slot, all its own (a captured graph bakes the
     // addresses in, and the scratch of sph_shell_* may be re-made by any query): normal and member word, 0 / 1 flag, its scan with the
     // tile scratch, the compacted shell slots, the crest per slot, the per-block rows of crest children
-    sph::DiffuseCrestCoef* d_dfCrCoef = nullptr;
+    DevTable<sph::DiffuseCrestCoef> d_dfCrCoef;
     uint32_t* d_dfCrState = nullptr;
-    StageRing<sph::DiffuseCrestCoef> dfCrStage;
     DevBuf<float4> d_dfCrNrm;
     DevBuf<uint32_t> d_dfCrFlag, d_dfCrPart;
     DevBuf<long long> d_dfCrOffsets;
@@ -403,13 +420,12 @@ struct SphEngine {
     SphDiffuseCrest dfCrCfg{};           // the crest config in force (all zero while off)
 
     // sph_scalars_* (sph_scalar.h): K channels per particle in the caller's order, their gathered copy in slot order
-    // (K values + the ghost weight per slot), the coefficients as the kernels read them (device memory: a replayed graph sees a later
-    // change) with their pinned staging, and the device word of the last substep's diffusion number
+    // (K values + the ghost weight per slot), the coefficients as the kernels read them, and the device word of the last substep's
+    // diffusion number
     float* d_scVal = nullptr;
     float* d_scSorted = nullptr;
-    sph::ScalarCoef* d_scCoef = nullptr;
+    DevTable<sph::ScalarCoef> d_scCoef;
     uint32_t* d_scState = nullptr;
-    StageRing<sph::ScalarCoef> scStage;
     int scK = 0;
     size_t scN = 0;                      // particles the buffers were allocated for
     float scCoeffs[2 * sph::kScalarMax] = {0};   // D_0 .. D_{K-1}, lambda_0 .. lambda_{K-1} as set
@@ -418,23 +434,21 @@ struct SphEngine {
     DevBuf<float4> d_scView;             // sph_scalars_moments: a channel laid out as the statistics kernels' input (3 float4 per slot)
     DevBuf<float2> d_scViewRp;
     DevBuf<float> d_scSampleOut;         // sph_scalars_sample_points (host arrays): device copy of the results
-    // sph_scalars_set_buoyancy / _set_sources (sph_couple.h): the table the kernel reads (device memory: a replayed
-    // graph sees a later change) with its host mirror and pinned staging, the books, and the per-block partial rows.  They belong to the
-    // scalar set: allocated by the first call that switches something on, freed with the channels.
-    sph::CoupleTab* d_cpTab = nullptr;
+    // sph_scalars_set_buoyancy / _set_sources (sph_couple.h): the table the kernel reads with its host mirror, the
+    // books, and the per-block partial rows.  They belong to the scalar set: allocated by the first call that switches something on,
+    // freed with the channels.
+    DevTable<sph::CoupleTab> d_cpTab;
     sph::CoupleAcc* d_cpAcc = nullptr;
     double* d_cpPart = nullptr;
-    StageRing<sph::CoupleTab> cpStage;   // one table per slot
-    sph::CoupleTab cpTab{};              // host mirror of *d_cpTab
+    sph::CoupleTab cpTab{};              // host mirror of *d_cpTab.p
     bool cpBuoy = false;                 // a beta is non-zero: the kick runs, and the pass does not keep the 80-byte array current
 
-    // sph_gates_* (sph_gate.h): the table the kernels read (device memory: a replayed graph sees a later set) with
-    // its host mirror and pinned staging, the gates as set, the books, the per-block partial rows and the history ring (gtRingCap rows)
-    sph::GateTab* d_gtTab = nullptr;
+    // sph_gates_* (sph_gate.h): the table the kernels read with its host mirror, the gates as set, the books, the
+    // per-block partial rows and the history ring (gtRingCap rows)
+    DevTable<sph::GateTab> d_gtTab;
     sph::GateAcc* d_gtAcc = nullptr;
     DevBuf<unsigned long long> d_gtPart, d_gtRing;
-    StageRing<sph::GateTab> gtStage;     // one table per slot
-    sph::GateTab gtTab{};                // host mirror of *d_gtTab (count 0: no gates, nothing is launched)
+    sph::GateTab gtTab{};                // host mirror of *d_gtTab.p (count 0: no gates, nothing is launched)
     SphGate gtSet[sph::kGateMax] = {};
     uint32_t gtRingCap = 0;
 
@@ -442,27 +456,23 @@ struct SphEngine {
     MonitorSlot mon[sph::kMonitorMax];
     int monCount = 0;
 
-    // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators, the per-block partial rows of k_obstacles,
-    // and the pinned staging of their stream-ordered uploads (kObsMax records per slot)
-    sph::ObsRec* d_obs = nullptr;
+    // sph_obstacles_*: K bodies (sph_obstacle.h ObsRec, room for kObsMax), their accumulators and the per-block partial rows of k_obstacles
+    DevTable<sph::ObsRec> d_obs;
     sph::ObsAcc* d_obsAcc = nullptr;
     double* d_obsPart = nullptr;
-    StageRing<sph::ObsRec> obsStage;
     int obsK = 0;
 
-    // sph_volume_* (sph_volume.h): the signed distance lattices, the device table (slots and per-body bindings) with its host mirror, pinned
-    // staging slots for stream-ordered uploads of the table, and the scratch of sph_mesh_distance (mesh copy and per-split partial results)
+    // sph_volume_* (sph_volume.h): the signed distance lattices, the device table (slots and per-body bindings) with its host mirror, and
+    // the scratch of sph_mesh_distance (mesh copy and per-split partial results)
     struct VolSlot { float* d = nullptr; int dims[3] = {0, 0, 0}; float spacing[3] = {0.0f, 0.0f, 0.0f}; };
     VolSlot vols[sph::kVolMax];
-    sph::VolTable* d_volTab = nullptr;
-    sph::VolTable volTab{};              // host mirror of *d_volTab
-    StageRing<sph::VolTable> volStage;   // one table per slot
+    DevTable<sph::VolTable> d_volTab;
+    sph::VolTable volTab{};              // host mirror of *d_volTab.p
     int volBound = 0;                    // bodies bound to a volume: k_obstacles_vol is launched instead of k_obstacles while > 0
     int obsShape[sph::kObsMax] = {0};    // shapes of the current set (a volume binds to a box only)
-    // dynamic bodies (sph_obstacle.h ObsDyn): one record per body beside d_obs, the records as set (host mirror),
-    // pinned staging like the bodies'; k_obstacles_finish_dyn is launched instead of k_obstacles_finish while dynCount > 0
-    sph::ObsDyn* d_dyn = nullptr;
-    StageRing<sph::ObsDyn> dynStage;     // one record per slot
+    // dynamic bodies (sph_obstacle.h ObsDyn): one record per body beside d_obs and the records as set (host
+    // mirror); k_obstacles_finish_dyn is launched instead of k_obstacles_finish while dynCount > 0
+    DevTable<sph::ObsDyn> d_dyn;
     int dynCount = 0;
     bool dynOn[sph::kObsMax] = {false};
     SphObstacleDynamics dynSet[sph::kObsMax] = {};
@@ -499,6 +509,41 @@ int DevBuf<T>::grow(SphEngine* e, size_t need) {
     if ((rc = dev_alloc(&p, need))) return rc;
     cap = need;
     return SPH_OK;
+}
+
+template <class T>
+int DevTable<T>::ensure(SphEngine* e, size_t count, const char* what) {
+    if (p) return SPH_OK;
+    int rc;
+    if ((rc = dev_alloc(&p, count))) return rc;
+    const hipError_t er = stage.create(e->stream, count);
+    if (er == hipSuccess) return SPH_OK;
+    release();
+    return fail(SPH_ERR_HIP, "%s: %s", what, hipGetErrorString(er));
+}
+template <class T>
+int DevTable<T>::send_part(SphEngine* e, size_t off, size_t bytes, size_t at) {
+    const char* from = reinterpret_cast<const char*>(stage.h + (size_t)stage.cur * stage.per) + off;
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(p + at) + off, from, bytes, hipMemcpyHostToDevice, e->stream));
+    return stage.commit(e->stream);
+}
+
+// The rows `span` (sph_state.h ring_span) still held by a ring of `history` rows of rowBytes each, row q in slot q mod history, to `out`,
+// oldest first: at most two contiguous copies, queued on the engine's stream.  The caller synchronises.
+int ring_read(SphEngine* e, const void* d_ring, size_t rowBytes, uint32_t history, RingSpan span, void* out) {
+    if (!span.have) return SPH_OK;
+    const uint32_t s0 = (uint32_t)(span.first % history), n0 = std::min(span.have, history - s0);
+    const char* ring = static_cast<const char*>(d_ring);
+    char* to = static_cast<char*>(out);
+    HIP_TRY(hipMemcpyAsync(to, ring + (size_t)s0 * rowBytes, (size_t)n0 * rowBytes, hipMemcpyDeviceToHost, e->stream));
+    if (span.have > n0) HIP_TRY(hipMemcpyAsync(to + (size_t)n0 * rowBytes, ring, (size_t)(span.have - n0) * rowBytes, hipMemcpyDeviceToHost, e->stream));
+    return SPH_OK;
+}
+
+// What every feature that reads the sorted copy answers under the linked-list grid build; `who` is subject and verb ("gates need").
+int needs_sorted_copy(const SphEngine* e, const char* who) {
+    if (e->optGridBuild != 1) return SPH_OK;
+    return fail(SPH_ERR_STATE, "%s the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy", who);
 }
 
 // Members that decide where the container walls and the grid are (for the slab exchange's reduced scan).
@@ -629,28 +674,28 @@ void tracers_free(SphEngine* e) {
     e->trOrdered = false;
 }
 
+// The crest term's coefficients and books (behind a drained stream).
+void diffuse_crest_free(SphEngine* e) { e->d_dfCrCoef.release(); dev_free(e->d_dfCrState); }
 void diffuse_free(SphEngine* e) {
     if (e->d_dfPool && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(e->d_dfPool); dev_free(e->d_dfScratch); dev_free(e->d_dfState); dev_free(e->d_dfCoef);
-    e->dfStage.destroy();
+    dev_free(e->d_dfPool); dev_free(e->d_dfScratch); dev_free(e->d_dfState); e->d_dfCoef.release();
     dev_free(e->d_dfFlag); dev_free(e->d_dfFlagStart); dev_free(e->d_dfFlagSums); dev_free(e->d_dfPart);
     e->d_dfCnt.release(); e->d_dfCntStart.release(); e->d_dfCntSums.release();
     e->dfC = 0;
     e->dfCfg = SphDiffuseConfig{};
-    dev_free(e->d_dfCrCoef); dev_free(e->d_dfCrState);               // (the crest term goes with the pool)
-    e->dfCrStage.destroy();
+    diffuse_crest_free(e);                                           // (the crest term goes with the pool)
     e->d_dfCrNrm.release(); e->d_dfCrFlag.release(); e->dfCrScan.release(); e->d_dfCrPart.release(); e->d_dfCrOffsets.release();
     e->d_dfCrSlots.release(); e->d_dfCrCrest.release();
     e->dfCrOn = false;
     e->dfCrCfg = SphDiffuseCrest{};
 }
 
+// The coupling's table, books and partial rows (behind a drained stream, or before anything was queued on them).
+void couple_free(SphEngine* e) { e->d_cpTab.release(); dev_free(e->d_cpAcc); dev_free(e->d_cpPart); }
 void scalars_free(SphEngine* e) {
     if (e->d_scVal && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(e->d_scVal); dev_free(e->d_scSorted); dev_free(e->d_scCoef); dev_free(e->d_scState);
-    e->scStage.destroy();
-    dev_free(e->d_cpTab); dev_free(e->d_cpAcc); dev_free(e->d_cpPart);
-    e->cpStage.destroy();
+    dev_free(e->d_scVal); dev_free(e->d_scSorted); e->d_scCoef.release(); dev_free(e->d_scState);
+    couple_free(e);
     e->cpTab = sph::CoupleTab{};
     e->cpBuoy = false;
     e->d_scView.release(); e->d_scViewRp.release(); e->d_scSampleOut.release();
@@ -658,19 +703,17 @@ void scalars_free(SphEngine* e) {
 }
 
 void gates_free(SphEngine* e) {
-    if (e->d_gtTab && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(e->d_gtTab); dev_free(e->d_gtAcc);
+    if (e->d_gtTab.p && e->stream) (void)hipStreamSynchronize(e->stream);
+    e->d_gtTab.release(); dev_free(e->d_gtAcc);
     e->d_gtPart.release(); e->d_gtRing.release();
-    e->gtStage.destroy();
     e->gtTab = sph::GateTab{};
     e->gtRingCap = 0;
 }
 
 void monitor_free(SphEngine* e, int slot) {
     MonitorSlot& s = e->mon[slot];
-    if (s.d_tab && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(s.d_tab);
-    s.stage.destroy();
+    if (s.d_tab.p && e->stream) (void)hipStreamSynchronize(e->stream);
+    s.d_tab.release();
     s.d_points.release(); s.d_ring.release(); s.d_perm.release(); s.d_rows.release(); s.d_times.release();
     if (s.kind != SPH_MONITOR_NONE) e->monCount -= 1;
     s.kind = SPH_MONITOR_NONE; s.m = 0;
@@ -683,10 +726,8 @@ void monitors_free(SphEngine* e) {
 }
 
 void obstacles_free(SphEngine* e) {
-    if (e->d_obs && e->stream) (void)hipStreamSynchronize(e->stream);
-    dev_free(e->d_obs); dev_free(e->d_obsAcc); dev_free(e->d_obsPart); dev_free(e->d_dyn);
-    e->obsStage.destroy();
-    e->dynStage.destroy();
+    if (e->d_obs.p && e->stream) (void)hipStreamSynchronize(e->stream);
+    e->d_obs.release(); dev_free(e->d_obsAcc); dev_free(e->d_obsPart); e->d_dyn.release();
     e->dynCount = 0;
     for (auto& on : e->dynOn) on = false;
     e->obsK = 0;
@@ -700,8 +741,7 @@ void volumes_unbind_all(SphEngine* e) {
 void volumes_free(SphEngine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto& v : e->vols) { dev_free(v.d); v = SphEngine::VolSlot{}; }
-    dev_free(e->d_volTab);
-    e->volStage.destroy();
+    e->d_volTab.release();
     std::memset(&e->volTab, 0, sizeof(e->volTab));
     volumes_unbind_all(e);
     e->d_meshVerts.release(); e->d_meshTris.release(); e->d_meshD2.release(); e->d_meshW.release();
@@ -947,7 +987,7 @@ int diffuse_crest_shell(SphEngine* e, const SimK& k, uint32_t n) {
     const float4* pv = (const float4*)e->d_sPV;
     const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
     const uint32_t* counter = (const uint32_t*)e->d_dfState + DF_STEP_LO;
-    const uint32_t* period = &e->d_dfCrCoef->every;          // (an address, not a load: device memory)
+    const uint32_t* period = &e->d_dfCrCoef.p->every;         // (an address, not a load: device memory)
     hipLaunchKernelGGL(k_shell_slot_gather, grid, block, 0, e->stream, k, nb, sk, pv, cellStart, (const float4*)e->d_sOwn, counter, period, e->d_dfCrNrm.p,
                        e->d_dfCrFlag.p);
     (void)scan_counts64_launch(e, e->dfCrScan, (const uint32_t*)e->d_dfCrFlag.p, (size_t)n, e->d_dfCrOffsets.p);
@@ -975,17 +1015,17 @@ int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
     if (e->optDiffuseTimed != 2) t.reset(new Timed(e, SPH_K_OTHER));
     const int cb = blocks_for(C), nb = blocks_for(n);
     hipLaunchKernelGGL(k_diffuse_advance, dim3(cb), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, dt,
-                       (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const float4*)e->d_dfPool, e->d_dfScratch, e->d_dfFlag, e->d_dfPart, C);
+                       (const DiffuseCoef*)e->d_dfCoef.p, (const uint32_t*)e->d_dfState, (const float4*)e->d_dfPool, e->d_dfScratch, e->d_dfFlag, e->d_dfPart, C);
     if (e->optDiffuseTimed == 1) t.reset();
     if (e->optDiffuseTimed == 2) t.reset(new Timed(e, SPH_K_OTHER));
     if (crest && (rc = diffuse_crest_shell(e, k, n))) return rc;
     if (n && crest)
         hipLaunchKernelGGL(k_diffuse_count_crest, dim3(nb), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn, dt,
-                           (const DiffuseCoef*)e->d_dfCoef, (const DiffuseCrestCoef*)e->d_dfCrCoef, (const uint32_t*)e->d_dfState,
+                           (const DiffuseCoef*)e->d_dfCoef.p, (const DiffuseCrestCoef*)e->d_dfCrCoef.p, (const uint32_t*)e->d_dfState,
                            (const float4*)e->d_dfCrNrm.p, (const float*)e->d_dfCrCrest.p, e->d_dfCnt.p, e->d_dfCrPart.p, e->idBase, n);
     else if (n)
         hipLaunchKernelGGL(k_diffuse_count, dim3(nb), dim3(kBlock), 0, e->stream, (const float4*)e->d_sPV, (const float4*)e->d_sOwn, dt,
-                           (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, e->d_dfCnt.p, e->idBase, n);
+                           (const DiffuseCoef*)e->d_dfCoef.p, (const uint32_t*)e->d_dfState, e->d_dfCnt.p, e->idBase, n);
     launch_cell_scan(e, e->d_dfFlag, e->d_dfFlagSums, e->d_dfFlagStart, (int)C, C);
     if (n) launch_cell_scan(e, e->d_dfCnt.p, e->d_dfCntSums.p, e->d_dfCntStart.p, (int)n, n);
     else HIP_TRY(hipMemsetAsync(e->d_dfCntStart.p, 0, sizeof(uint32_t), e->stream));
@@ -993,10 +1033,10 @@ int diffuse_step(SphEngine* e, const SimK& k, float dt, uint32_t n) {
                        (const uint32_t*)e->d_dfState, e->d_dfPool, C);
     if (n)
         hipLaunchKernelGGL(k_diffuse_emit, dim3(nb), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
-                           (const DiffuseCoef*)e->d_dfCoef, (const uint32_t*)e->d_dfState, (const uint32_t*)e->d_dfCntStart.p,
+                           (const DiffuseCoef*)e->d_dfCoef.p, (const uint32_t*)e->d_dfState, (const uint32_t*)e->d_dfCntStart.p,
                            (const uint32_t*)e->d_dfFlagStart, e->d_dfPool, e->idBase, n, C);
     if (crest)                                                          // (in front of the tick: it reads the counter the tick advances)
-        hipLaunchKernelGGL(k_diffuse_crest_tick, dim3(1), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_dfState, (const DiffuseCrestCoef*)e->d_dfCrCoef,
+        hipLaunchKernelGGL(k_diffuse_crest_tick, dim3(1), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_dfState, (const DiffuseCrestCoef*)e->d_dfCrCoef.p,
                            (const uint32_t*)e->d_dfCrPart.p, (uint32_t)(n ? nb : 0), (const long long*)e->d_dfCrOffsets.p + n, n, e->d_dfCrState);
     hipLaunchKernelGGL(k_diffuse_tick, dim3(1), dim3(kBlock), 0, e->stream, e->d_dfState, (const uint32_t*)e->d_dfPart, (uint32_t)cb,
                        (const uint32_t*)e->d_dfFlagStart, (const uint32_t*)e->d_dfCntStart.p, n, C);
@@ -1014,11 +1054,11 @@ void scalars_launch(SphEngine* e, const SimK& k, float dt, uint32_t n) {
     const float kLap = scalar_klap(e->params.param_mass, e->params.param_h);
     if (e->optScalarSweep == 1)
         hipLaunchKernelGGL((k_scalar_sweep_staged<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
-                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef, kLap, dt, e->d_scVal, e->d_scState,
+                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef.p, kLap, dt, e->d_scVal, e->d_scState,
                            e->idBase, n);
     else
         hipLaunchKernelGGL((k_scalar_sweep<K>), dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const float4*)e->d_sOwn,
-                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef, kLap, dt, e->d_scVal, e->d_scState,
+                           (const uint32_t*)e->d_cellStart, (const float*)e->d_scSorted, (const ScalarCoef*)e->d_scCoef.p, kLap, dt, e->d_scVal, e->d_scState,
                            e->idBase, n);
 }
 // The gather alone, outside a substep (sampling, on the grid of the current state): the diffusion number is left alone.
@@ -1134,17 +1174,17 @@ int obstacles_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
     {
         Timed t(e, SPH_K_OTHER);
         if (rows && e->volBound > 0)
-            hipLaunchKernelGGL(k_obstacles_vol, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, (const VolTable*)e->d_volTab, e->obsK,
+            hipLaunchKernelGGL(k_obstacles_vol, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs.p, (const VolTable*)e->d_volTab.p, e->obsK,
                                e->params.param_mass, pos, vel, n, e->d_obsPart);
-        else if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs, e->obsK, e->params.param_mass, pos, vel, n,
+        else if (rows) hipLaunchKernelGGL(k_obstacles, dim3(rows), dim3(kObsBlock), 0, e->stream, (const ObsRec*)e->d_obs.p, e->obsK, e->params.param_mass, pos, vel, n,
                                      e->d_obsPart);
         if (e->dynCount > 0) {                                       // (the finish that also steps the dynamic bodies)
             ObsWorld W;
             obstacle_world(e->params, W);
-            hipLaunchKernelGGL(k_obstacles_finish_dyn, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, (const ObsDyn*)e->d_dyn, W, e->obsK, dt,
+            hipLaunchKernelGGL(k_obstacles_finish_dyn, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs.p, (const ObsDyn*)e->d_dyn.p, W, e->obsK, dt,
                                (const double*)e->d_obsPart, rows, e->d_obsAcc);
         } else
-        hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
+        hipLaunchKernelGGL(k_obstacles_finish, dim3(1), dim3(kObsFinishBlock), 0, e->stream, e->d_obs.p, e->obsK, dt, (const double*)e->d_obsPart, rows, e->d_obsAcc);
     }
     HIP_TRY(hipGetLastError());
     return SPH_OK;
@@ -1162,8 +1202,8 @@ template <int K>
 void couple_launch(SphEngine* e, int rows, bool src, float4* pos, float4* vel, int n, float dt) {
     const SphParams& p = e->params;
     const dim3 grid(rows), block(kObsBlock);
-    const CoupleTab* tab = e->d_cpTab;
-    const ObsRec* bodies = e->d_obs;
+    const CoupleTab* tab = e->d_cpTab.p;
+    const ObsRec* bodies = e->d_obs.p;
     if (src && e->cpBuoy)
         hipLaunchKernelGGL((k_scalar_couple<K, true, true>), grid, block, 0, e->stream, tab, bodies, e->obsK, dt, p.param_gravityX, p.param_gravityY, p.param_gravityZ,
                            (const float4*)pos, vel, e->d_scVal, e->idBase, n, e->d_cpPart);
@@ -1197,7 +1237,7 @@ int couple_step(SphEngine* e, float4* pos, float4* vel, int n, float dt) {
 // ---- flow gates (sph_gate.h) -------------------------------------------------------------------------
 template <int K>
 void gates_launch(SphEngine* e, int rows, const float4* pos, const float4* vel, int n) {
-    hipLaunchKernelGGL((k_gates<K>), dim3(rows), dim3(kGateBlock), 0, e->stream, (const GateTab*)e->d_gtTab, pos, vel, (const float4*)e->d_sPV,
+    hipLaunchKernelGGL((k_gates<K>), dim3(rows), dim3(kGateBlock), 0, e->stream, (const GateTab*)e->d_gtTab.p, pos, vel, (const float4*)e->d_sPV,
                        (const float*)e->d_scVal, e->idBase, n, e->d_gtPart.p);
 }
 // One substep's gate step on the pass's output state and the sorted copy of its entry state: k_gates, then the one-block finish of the
@@ -1216,7 +1256,7 @@ int gates_step(SphEngine* e, const float4* pos, const float4* vel, int n, float 
             }
         }
         hipLaunchKernelGGL(k_gates_finish, dim3(1), dim3(kGateFinishBlock), 0, e->stream, dt, (const unsigned long long*)e->d_gtPart.p, rows,
-                           (const GateTab*)e->d_gtTab, e->d_gtAcc, e->d_gtRing.p, e->gtRingCap);
+                           (const GateTab*)e->d_gtTab.p, e->d_gtAcc, e->d_gtRing.p, e->gtRingCap);
     }
     HIP_TRY(hipGetLastError());
     return SPH_OK;
@@ -1232,11 +1272,11 @@ int monitors_step(SphEngine* e, const SimK& k, float dt) {
         Timed t(e, SPH_K_OTHER);
         if (s.kind == SPH_MONITOR_POINTS)
             hipLaunchKernelGGL(k_monitor_points, dim3(blocks_for(s.m)), dim3(kBlock), 0, e->stream, k, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
-                               (const MonitorTab*)s.d_tab, (const float4*)s.d_points.p, (const uint32_t*)s.d_perm.p, s.d_rows.p, s.d_ring.p, (uint32_t)s.m);
+                               (const MonitorTab*)s.d_tab.p, (const float4*)s.d_points.p, (const uint32_t*)s.d_perm.p, s.d_rows.p, s.d_ring.p, (uint32_t)s.m);
         else
             hipLaunchKernelGGL(k_monitor_lattice, dim3((unsigned)std::min<long long>(s.tab.L.nBricks, 1ll << 20)), dim3(kBlock), 0, e->stream, k,
-                               (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const MonitorTab*)s.d_tab, s.d_rows.p, s.d_ring.p);
-        hipLaunchKernelGGL(k_monitor_tick, dim3(1), dim3(64), 0, e->stream, s.d_tab, s.d_times.p, dt);
+                               (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart, (const MonitorTab*)s.d_tab.p, s.d_rows.p, s.d_ring.p);
+        hipLaunchKernelGGL(k_monitor_tick, dim3(1), dim3(64), 0, e->stream, s.d_tab.p, s.d_times.p, dt);
     }
     HIP_TRY(hipGetLastError());
     return SPH_OK;
@@ -1284,16 +1324,11 @@ int ensure_shape_table(SphEngine* e) {
 int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     if (e->params.param_pause) { if (boundaryFirst) HIP_TRY(hipEventRecord(e->evBoundary, e->stream)); return SPH_OK; }                               // SPHFluid3D.cpp:432
     int rc;
-    if (e->trM && e->optGridBuild == 1)
-        return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if (e->scK && e->optGridBuild == 1)
-        return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if (e->dfC && e->optGridBuild == 1)
-        return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if (e->gtTab.count && e->optGridBuild == 1)
-        return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if (e->monCount && e->optGridBuild == 1)
-        return fail(SPH_ERR_STATE, "monitors need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (e->trM && (rc = needs_sorted_copy(e, "tracers need"))) return rc;
+    if (e->scK && (rc = needs_sorted_copy(e, "scalars need"))) return rc;
+    if (e->dfC && (rc = needs_sorted_copy(e, "diffuse particles need"))) return rc;
+    if (e->gtTab.count && (rc = needs_sorted_copy(e, "gates need"))) return rc;
+    if (e->monCount && (rc = needs_sorted_copy(e, "monitors need"))) return rc;
     if ((rc = validate_params(e->params)) || (rc = couple_refused(e))) return rc;
     float cont[15];
     container_key(e->params, cont);
@@ -1768,38 +1803,38 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     const uint64_t trv[4] = {(uint64_t)e->trM, (uint64_t)e->trIntegrator, e->trK, e->trS};
     add(trv, sizeof(trv));
     // diffuse particles: pool set, its capacity and every buffer the substep's kernels get; the coefficients and all counts are read from memory
-    const void* df[11] = {e->d_dfPool, e->d_dfScratch, e->d_dfState, e->d_dfCoef, e->d_dfFlag, e->d_dfFlagStart, e->d_dfFlagSums, e->d_dfPart,
+    const void* df[11] = {e->d_dfPool, e->d_dfScratch, e->d_dfState, e->d_dfCoef.p, e->d_dfFlag, e->d_dfFlagStart, e->d_dfFlagSums, e->d_dfPart,
                           e->d_dfCnt.p, e->d_dfCntStart.p, e->d_dfCntSums.p};
     add(df, sizeof(df));
     add(&e->dfC, sizeof(e->dfC));
     // scalars: a call with scalars is never served by a graph captured without them or with another channel count; the coefficients are read from memory
-    const void* sc[4] = {e->d_scVal, e->d_scSorted, e->d_scCoef, e->d_scState};
+    const void* sc[4] = {e->d_scVal, e->d_scSorted, e->d_scCoef.p, e->d_scState};
     add(sc, sizeof(sc));
     add(&e->scK, sizeof(e->scK));
     add(&e->optScalarSweep, sizeof(e->optScalarSweep));
     // active scalars: the buffers and which of the coupling kernels run; coefficients, sources and their count are read from memory
-    const void* cp[3] = {e->d_cpTab, e->d_cpAcc, e->d_cpPart};
+    const void* cp[3] = {e->d_cpTab.p, e->d_cpAcc, e->d_cpPart};
     add(cp, sizeof(cp));
     const int cpWhat = (e->cpBuoy ? 1 : 0) | (e->cpTab.nSrc > 0 ? 2 : 0);
     add(&cpWhat, sizeof(cpWhat));
     // obstacles: the buffers and the count (the kernels read the bodies from memory, so a later set / set_motion needs no new graph)
-    const void* ob[3] = {e->d_obs, e->d_obsAcc, e->d_obsPart};
+    const void* ob[3] = {e->d_obs.p, e->d_obsAcc, e->d_obsPart};
     add(ob, sizeof(ob));
     add(&e->obsK, sizeof(e->obsK));
     // volumes: the table's address and whether any body is bound (which of the two obstacle kernels runs); the bindings and the lattices are read from memory
-    const void* vt = e->d_volTab;
+    const void* vt = e->d_volTab.p;
     const int anyBound = e->volBound > 0 ? 1 : 0;
     add(&vt, sizeof(vt));
     add(&anyBound, sizeof(anyBound));
     // dynamic bodies: the records' address and which finish kernel runs; the records are read from memory
-    const void* dy = e->d_dyn;
+    const void* dy = e->d_dyn.p;
     const int anyDyn = e->dynCount > 0 ? 1 : 0;
     add(&dy, sizeof(dy));
     add(&anyDyn, sizeof(anyDyn));
     // crest births of the pool, only while the term is on (off: the material of before): every buffer its launches get and the shell pass's
     // launch arguments (radius, hence the stencil, offset, minCount, flags); rate, windows, align and every are read from memory
     if (e->dfC && e->dfCrOn) {
-        const void* cr[10] = {e->d_dfCrCoef, e->d_dfCrState, e->d_dfCrNrm.p, e->d_dfCrFlag.p, e->dfCrScan.tileMax.p, e->d_dfCrPart.p, e->d_dfCrOffsets.p,
+        const void* cr[10] = {e->d_dfCrCoef.p, e->d_dfCrState, e->d_dfCrNrm.p, e->d_dfCrFlag.p, e->dfCrScan.tileMax.p, e->d_dfCrPart.p, e->d_dfCrOffsets.p,
                               e->dfCrScan.tileSums.p, e->d_dfCrSlots.p, e->d_dfCrCrest.p};
         add(cr, sizeof(cr));
         add(&e->dfCrCfg.radius, sizeof(float));                       // (with the params above it fixes the radius in force and the stencil)
@@ -1807,7 +1842,7 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     }
     // flow gates, only while gates are set (off: the material of before): the buffers of the two launches; table, count, history and stride are read from memory
     if (e->gtTab.count) {
-        const void* gt[4] = {e->d_gtTab, e->d_gtAcc, e->d_gtPart.p, e->d_gtRing.p};
+        const void* gt[4] = {e->d_gtTab.p, e->d_gtAcc, e->d_gtPart.p, e->d_gtRing.p};
         add(gt, sizeof(gt));
         add(&e->gtRingCap, sizeof(e->gtRingCap));
     }
@@ -1815,7 +1850,7 @@ static std::vector<unsigned char> graph_material(const SphEngine* e, float dt, i
     // buffers and the ring layout; every, stride, the counters, wetFraction, a lattice's origin and spacing are read from memory
     if (e->monCount) {
         for (const MonitorSlot& s : e->mon) {
-            const void* mo[6] = {s.d_tab, s.d_points.p, s.d_perm.p, s.d_rows.p, s.d_ring.p, s.d_times.p};
+            const void* mo[6] = {s.d_tab.p, s.d_points.p, s.d_perm.p, s.d_rows.p, s.d_ring.p, s.d_times.p};
             add(mo, sizeof(mo));
             const uint64_t mv[7] = {(uint64_t)s.kind, (uint64_t)s.m, (uint64_t)s.dims[0], (uint64_t)s.dims[1], (uint64_t)s.dims[2], s.tab.history, s.tab.ringPoints};
             add(mv, sizeof(mv));
@@ -3090,8 +3125,7 @@ int sph_sync_deadline(SphEngine* e, double seconds) {
 // What no query of the current state supports: a z-slab engine, the linked-list grid.  Entry points that allocate state this first.
 static int query_refused(const SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "sampling a z-slab engine is not supported: its halo records after a step are the step's entry state");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "sampling needs the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    return SPH_OK;
+    return needs_sorted_copy(e, "sampling needs");
 }
 // The grid of the CURRENT state, built outside a substep exactly as sph_download_grid builds it.  The next dispatch builds its
 // own (dispatch_one always does), so nothing of this build reaches the simulation.
@@ -4636,8 +4670,7 @@ int sph_aniso_lattice_host(const SphParticle* particles, size_t n, const SphPara
 // ---- state statistics (sph_stats.h) ------------------------------------------------------------------
 static int stats_refused(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "statistics of a z-slab engine are not supported: the order of the fp64 sums is defined over one engine's grid");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "statistics need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    return SPH_OK;
+    return needs_sorted_copy(e, "statistics need");
 }
 
 static int stats_check_specs(const SphHistogramSpec* specs, int nSpecs, const uint64_t* histOut, sph::StatK& s) {
@@ -4745,7 +4778,7 @@ int sph_statistics(SphEngine* e, SphStatistics* out, const SphHistogramSpec* spe
 static int tracers_check(SphEngine* e, const float* points4, size_t m, int integrator, uint32_t historyCap, uint32_t historyStride) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) return fail(SPH_ERR_STATE, "tracers on a z-slab engine are not supported: its halo records after a step are the step's entry state");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "tracers need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+    if (int rc = needs_sorted_copy(e, "tracers need")) return rc;
     if (m && !points4) return fail(SPH_ERR_ARG, "null argument");
     if (integrator != SPH_TRACER_EULER && integrator != SPH_TRACER_MIDPOINT) return fail(SPH_ERR_ARG, "unknown integrator %d", integrator);
     if (historyStride == 0) return fail(SPH_ERR_ARG, "historyStride must be >= 1");
@@ -4793,13 +4826,16 @@ int sph_tracers_set(SphEngine* e, const float* points4, size_t m, int integrator
 
 size_t sph_tracers_count(const SphEngine* e) { return e ? e->trM : 0; }
 
+// The snapshots the pathline ring holds: one per trS substeps, the seed being snapshot 0.
+static sph::RingSpan tracers_span(const SphEngine* e) {
+    return sph::ring_span((e->trM && e->trK) ? e->trSteps / e->trS + 1 : 0, e->trK);
+}
 int sph_tracers_info(const SphEngine* e, uint64_t* substeps, uint32_t* snapshots, uint64_t* firstSnapshot) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    const uint64_t last = e->trSteps / e->trS;                            // number of the newest snapshot
-    const uint64_t count = (e->trM && e->trK) ? std::min<uint64_t>(last + 1, e->trK) : 0;
+    const sph::RingSpan span = tracers_span(e);
     if (substeps) *substeps = e->trSteps;
-    if (snapshots) *snapshots = (uint32_t)count;
-    if (firstSnapshot) *firstSnapshot = count ? last + 1 - count : 0;
+    if (snapshots) *snapshots = span.have;
+    if (firstSnapshot) *firstSnapshot = span.first;
     return SPH_OK;
 }
 
@@ -4821,21 +4857,14 @@ int sph_tracers_device(SphEngine* e, const SphTracer** devPtr) {
 int sph_tracers_history(SphEngine* e, float* out4, size_t snapshotCap, uint32_t* snapshotsOut, uint64_t* firstSnapshotOut) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (!e->trM || !e->trK) return fail(SPH_ERR_STATE, "no pathline history: call sph_tracers_set with historyCap >= 1 first");
-    uint32_t count = 0;
-    uint64_t first = 0;
-    (void)sph_tracers_info(e, nullptr, &count, &first);
-    if (snapshotCap < count) return fail(SPH_ERR_CAPACITY, "%u snapshots (capacity %zu)", count, snapshotCap);
+    const sph::RingSpan span = tracers_span(e);
+    if (snapshotCap < span.have) return fail(SPH_ERR_CAPACITY, "%u snapshots (capacity %zu)", span.have, snapshotCap);
     if (!out4) return fail(SPH_ERR_ARG, "null argument");
-    // snapshot q lives in slot q mod K: the stored ones are at most two contiguous pieces of the ring
-    const size_t snap = e->trM * 4;                                        // floats per snapshot
-    const uint32_t s0 = (uint32_t)(first % e->trK);
-    const uint32_t n0 = std::min<uint32_t>(count, e->trK - s0);
-    HIP_TRY(hipMemcpyAsync(out4, reinterpret_cast<const float*>(e->d_trRing) + (size_t)s0 * snap, (size_t)n0 * snap * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    if (count > n0)
-        HIP_TRY(hipMemcpyAsync(out4 + (size_t)n0 * snap, e->d_trRing, (size_t)(count - n0) * snap * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    int rc;
+    if ((rc = ring_read(e, e->d_trRing, e->trM * sizeof(float4), e->trK, span, out4))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (snapshotsOut) *snapshotsOut = count;
-    if (firstSnapshotOut) *firstSnapshotOut = first;
+    if (snapshotsOut) *snapshotsOut = span.have;
+    if (firstSnapshotOut) *firstSnapshotOut = span.first;
     return SPH_OK;
 }
 
@@ -4871,32 +4900,28 @@ void sph_diffuse_default(SphDiffuseConfig* out) {
 int sph_diffuse_set(SphEngine* e, const SphDiffuseConfig* cfg) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) return fail(SPH_ERR_STATE, "diffuse particles on a z-slab engine are not supported: a record would have to migrate with the fluid around it");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    if (!cfg || cfg->capacity == 0u) { diffuse_free(e); return SPH_OK; }
     int rc;
+    if ((rc = needs_sorted_copy(e, "diffuse particles need"))) return rc;
+    if (!cfg || cfg->capacity == 0u) { diffuse_free(e); return SPH_OK; }
     if ((rc = diffuse_check_config(*cfg))) return rc;
     const uint32_t C = cfg->capacity;
     if (C != e->dfC || !e->d_dfPool) {
         diffuse_free(e);
-        hipError_t er = hipSuccess;
         const size_t cb = (size_t)blocks_for((size_t)C);
         if ((rc = dev_alloc(&e->d_dfPool, (size_t)3 * C)) || (rc = dev_alloc(&e->d_dfScratch, (size_t)3 * C)) || (rc = dev_alloc(&e->d_dfState, (size_t)DF_WORDS)) ||
-            (rc = dev_alloc(&e->d_dfCoef, 1)) || (rc = dev_alloc(&e->d_dfFlag, (size_t)C + 8)) || (rc = dev_alloc(&e->d_dfFlagStart, (size_t)C + 1)) ||
-            (rc = dev_alloc(&e->d_dfFlagSums, (size_t)blocks_for((size_t)C, kScanTile) + 1)) || (rc = dev_alloc(&e->d_dfPart, cb * DF_PART_WORDS)) ||
-            (er = e->dfStage.create(e->stream, 1)) != hipSuccess) {
+            (rc = e->d_dfCoef.ensure(e, 1, "pinned staging of the diffuse coefficients")) || (rc = dev_alloc(&e->d_dfFlag, (size_t)C + 8)) ||
+            (rc = dev_alloc(&e->d_dfFlagStart, (size_t)C + 1)) || (rc = dev_alloc(&e->d_dfFlagSums, (size_t)blocks_for((size_t)C, kScanTile) + 1)) ||
+            (rc = dev_alloc(&e->d_dfPart, cb * DF_PART_WORDS))) {
             diffuse_free(e);
-            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the diffuse coefficients: %s", hipGetErrorString(er));
+            return rc;
         }
         hipError_t m1 = hipMemsetAsync(e->d_dfState, 0, DF_WORDS * sizeof(uint32_t), e->stream);
         hipError_t m2 = hipMemsetAsync(e->d_dfFlag, 0, ((size_t)C + 8) * sizeof(uint32_t), e->stream);    // (k_scan_apply leaves it zero again)
         if (m1 != hipSuccess || m2 != hipSuccess) { diffuse_free(e); return fail(SPH_ERR_HIP, "hipMemsetAsync of the diffuse pool failed"); }
         e->dfC = C;
     }
-    sph::DiffuseCoef* slot = nullptr;
-    if ((rc = e->dfStage.next(&slot))) return rc;
-    *slot = diffuse_coef_of(*cfg);
-    HIP_TRY(hipMemcpyAsync(e->d_dfCoef, slot, sizeof(sph::DiffuseCoef), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->dfStage.commit(e->stream))) return rc;
+    const sph::DiffuseCoef coef = diffuse_coef_of(*cfg);
+    if ((rc = e->d_dfCoef.put(e, &coef))) return rc;
     e->dfCfg = *cfg;
     return SPH_OK;
 }
@@ -5003,22 +5028,17 @@ int sph_diffuse_set_crest(SphEngine* e, const SphDiffuseCrest* crest) {
     SphGridInfo g;
     sph::compute_grid_extents(e->params, g);
     if ((rc = diffuse_check_crest(*crest, e->params.param_h, g.cellSize))) return rc;
-    if (!e->d_dfCrCoef) {
+    if (!e->d_dfCrCoef.p) {
         hipError_t er = hipSuccess;
-        if ((rc = dev_alloc(&e->d_dfCrCoef, 1)) || (rc = dev_alloc(&e->d_dfCrState, (size_t)DFC_WORDS)) ||
-            (er = e->dfCrStage.create(e->stream, 1)) != hipSuccess ||
+        if ((rc = e->d_dfCrCoef.ensure(e, 1, "staging of the diffuse crest coefficients")) || (rc = dev_alloc(&e->d_dfCrState, (size_t)DFC_WORDS)) ||
             (er = hipMemsetAsync(e->d_dfCrState, 0, DFC_WORDS * sizeof(uint32_t), e->stream)) != hipSuccess) {
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            dev_free(e->d_dfCrCoef); dev_free(e->d_dfCrState);
-            e->dfCrStage.destroy();
+            HIP_TRY(hipStreamSynchronize(e->stream));                  // (a memset may have been queued)
+            diffuse_crest_free(e);
             return rc ? rc : fail(SPH_ERR_HIP, "staging of the diffuse crest coefficients: %s", hipGetErrorString(er));
         }
     }
-    sph::DiffuseCrestCoef* slot = nullptr;
-    if ((rc = e->dfCrStage.next(&slot))) return rc;
-    *slot = diffuse_crest_coef_of(*crest);
-    HIP_TRY(hipMemcpyAsync(e->d_dfCrCoef, slot, sizeof(sph::DiffuseCrestCoef), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->dfCrStage.commit(e->stream))) return rc;
+    const sph::DiffuseCrestCoef coef = diffuse_crest_coef_of(*crest);
+    if ((rc = e->d_dfCrCoef.put(e, &coef))) return rc;
     e->dfCrCfg = *crest;
     e->dfCrCfg.pad = 0u;
     e->dfCrOn = true;
@@ -5159,8 +5179,7 @@ int sph_diffuse_step_host_crest(const SphDiffuseConfig* cfg, const SphDiffuseCre
 static int scalars_refused(SphEngine* e) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) return fail(SPH_ERR_STATE, "scalars on a z-slab engine are not supported: halo records would have to carry them");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "scalars need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    return SPH_OK;
+    return needs_sorted_copy(e, "scalars need");
 }
 static int scalars_check_coeffs(const float* coeffs, int K) {
     if (!coeffs) return fail(SPH_ERR_ARG, "null argument");
@@ -5173,10 +5192,9 @@ static int scalars_check_coeffs(const float* coeffs, int K) {
 static int scalars_upload_coef(SphEngine* e) {
     sph::ScalarCoef* slot = nullptr;
     int rc;
-    if ((rc = e->scStage.next(&slot))) return rc;
+    if ((rc = e->d_scCoef.slot(&slot))) return rc;
     sph::scalar_make_coef(e->scK, e->scCoeffs, *slot);
-    HIP_TRY(hipMemcpyAsync(e->d_scCoef, slot, sizeof(sph::ScalarCoef), hipMemcpyHostToDevice, e->stream));
-    return e->scStage.commit(e->stream);
+    return e->d_scCoef.send(e);
 }
 static int scalars_check_set(SphEngine* e, size_t n, int channels, const float* coeffs) {
     int rc;
@@ -5195,12 +5213,10 @@ int sph_scalars_set_device(SphEngine* e, const float* devValues, size_t n, int c
     if (channels == 0) { scalars_free(e); return SPH_OK; }
     if (channels != e->scK || n != e->scN || !e->d_scVal) {              // (a set of the same shape reuses the buffers, and the graphs captured over them)
         scalars_free(e);
-        hipError_t er = hipSuccess;
         if ((rc = dev_alloc(&e->d_scVal, n * (size_t)channels)) || (rc = dev_alloc(&e->d_scSorted, n * (size_t)(channels + 1))) ||
-            (rc = dev_alloc(&e->d_scCoef, 1)) || (rc = dev_alloc(&e->d_scState, 4)) ||
-            (er = e->scStage.create(e->stream, 1)) != hipSuccess) {
+            (rc = e->d_scCoef.ensure(e, 1, "pinned staging of the scalar coefficients")) || (rc = dev_alloc(&e->d_scState, 4))) {
             scalars_free(e);
-            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the scalar coefficients: %s", hipGetErrorString(er));
+            return rc;
         }
         e->scN = n;
     }
@@ -5489,13 +5505,7 @@ static int obstacle_index_check(const SphEngine* e, int index) {
 
 // The host mirror of the table to the device, stream-ordered, through the next pinned staging slot.
 static int volumes_upload_table(SphEngine* e) {
-    if (!e->d_volTab) return SPH_OK;
-    int rc;
-    sph::VolTable* slot = nullptr;
-    if ((rc = e->volStage.next(&slot))) return rc;
-    *slot = e->volTab;
-    HIP_TRY(hipMemcpyAsync(e->d_volTab, slot, sizeof(sph::VolTable), hipMemcpyHostToDevice, e->stream));
-    return e->volStage.commit(e->stream);
+    return e->d_volTab.p ? e->d_volTab.put(e, &e->volTab) : SPH_OK;
 }
 
 void sph_obstacle_default(SphObstacle* out) {
@@ -5517,27 +5527,23 @@ int sph_obstacles_set(SphEngine* e, const SphObstacle* obs, int count) {
         if ((rc = volumes_upload_table(e))) return rc;
     }
     if (count == 0) { obstacles_free(e); return SPH_OK; }
-    if (!e->d_obs) {
-        if ((rc = dev_alloc(&e->d_obs, (size_t)kObsMax)) || (rc = dev_alloc(&e->d_obsAcc, 1)) || (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow)) ||
-            (rc = dev_alloc(&e->d_dyn, (size_t)kObsMax))) {
+    if (!e->d_obs.p) {
+        if ((rc = e->d_obs.ensure(e, (size_t)kObsMax, "obstacle staging")) || (rc = dev_alloc(&e->d_obsAcc, 1)) ||
+            (rc = dev_alloc(&e->d_obsPart, (size_t)kObsGrid * kObsRow)) || (rc = e->d_dyn.ensure(e, (size_t)kObsMax, "obstacle staging"))) {
             obstacles_free(e); return rc;
         }
-        hipError_t er = e->obsStage.create(e->stream, (size_t)kObsMax);
-        if (er == hipSuccess) er = e->dynStage.create(e->stream, 1);
-        if (er != hipSuccess) { obstacles_free(e); return fail(SPH_ERR_HIP, "obstacle staging: %s", hipGetErrorString(er)); }
-        HIP_TRY(hipMemsetAsync(e->d_dyn, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dyn.p, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
         e->obsK = 0;
     }
     if (e->dynCount > 0) {                                           // (a set replaces the set: every dynamics record goes with it)
-        HIP_TRY(hipMemsetAsync(e->d_dyn, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
+        HIP_TRY(hipMemsetAsync(e->d_dyn.p, 0, sizeof(sph::ObsDyn) * kObsMax, e->stream));
         e->dynCount = 0;
         for (auto& on : e->dynOn) on = false;
     }
     sph::ObsRec* slot = nullptr;
-    if ((rc = e->obsStage.next(&slot))) return rc;
+    if ((rc = e->d_obs.slot(&slot))) return rc;
     for (int i = 0; i < count; ++i) obstacle_to_rec(obs[i], true, slot[i]);
-    HIP_TRY(hipMemcpyAsync(e->d_obs, slot, sizeof(sph::ObsRec) * (size_t)count, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->obsStage.commit(e->stream))) return rc;
+    if ((rc = e->d_obs.send(e, (size_t)count))) return rc;
     if (count != e->obsK) HIP_TRY(hipMemsetAsync(e->d_obsAcc, 0, sizeof(sph::ObsAcc), e->stream));   // (another count: the sums restart)
     e->obsK = count;
     for (int i = 0; i < count; ++i) e->obsShape[i] = obs[i].shape;
@@ -5550,11 +5556,10 @@ int sph_obstacles_set_motion(SphEngine* e, int index, const float vel[3], const 
     if ((rc = obstacles_refuse_slab(e)) || (rc = obstacle_index_check(e, index))) return rc;
     if (!obs_all_finite(vel, 3) || !obs_all_finite(omega, 3)) return fail(SPH_ERR_ARG, "obstacle %d: velocity not finite", index);
     sph::ObsRec* slot = nullptr;
-    if ((rc = e->obsStage.next(&slot))) return rc;
+    if ((rc = e->d_obs.slot(&slot))) return rc;
     for (int a = 0; a < 3; ++a) { slot[0].v[a] = vel[a]; slot[0].w[a] = omega[a]; }
     static_assert(offsetof(sph::ObsRec, w) == offsetof(sph::ObsRec, v) + 3 * sizeof(float), "v and w are adjacent");
-    HIP_TRY(hipMemcpyAsync(&e->d_obs[index].v[0], &slot[0].v[0], 6 * sizeof(float), hipMemcpyHostToDevice, e->stream));   // (the pose stays the device's)
-    return e->obsStage.commit(e->stream);
+    return e->d_obs.send_part(e, offsetof(sph::ObsRec, v), 6 * sizeof(float), (size_t)index);   // (the pose stays the device's)
 }
 
 int sph_obstacles_get(SphEngine* e, SphObstacle* out, int cap, int* countOut) {
@@ -5563,7 +5568,7 @@ int sph_obstacles_get(SphEngine* e, SphObstacle* out, int cap, int* countOut) {
     if (e->obsK && !out) return fail(SPH_ERR_ARG, "null argument");
     if (e->obsK) {
         sph::ObsRec host[kObsMax];
-        HIP_TRY(hipMemcpyAsync(host, e->d_obs, sizeof(sph::ObsRec) * (size_t)e->obsK, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(host, e->d_obs.p, sizeof(sph::ObsRec) * (size_t)e->obsK, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         for (int i = 0; i < e->obsK; ++i) rec_to_obstacle(host[i], out[i]);
     }
@@ -5642,27 +5647,19 @@ static int couple_precheck(SphEngine* e) {
 }
 // The buffers, at the first call that switches something on.
 static int couple_ensure(SphEngine* e) {
-    if (e->d_cpTab) return SPH_OK;
+    if (e->d_cpTab.p) return SPH_OK;
     int rc;
-    hipError_t er = hipSuccess;
-    if ((rc = dev_alloc(&e->d_cpTab, 1)) || (rc = dev_alloc(&e->d_cpAcc, 1)) || (rc = dev_alloc(&e->d_cpPart, (size_t)kObsGrid * kCoupleTerms)) ||
-        (er = e->cpStage.create(e->stream, 1)) != hipSuccess) {
-        dev_free(e->d_cpTab); dev_free(e->d_cpAcc); dev_free(e->d_cpPart);
-        e->cpStage.destroy();
-        return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the coupling table: %s", hipGetErrorString(er));
+    if ((rc = e->d_cpTab.ensure(e, 1, "pinned staging of the coupling table")) || (rc = dev_alloc(&e->d_cpAcc, 1)) ||
+        (rc = dev_alloc(&e->d_cpPart, (size_t)kObsGrid * kCoupleTerms))) {
+        couple_free(e);
+        return rc;
     }
     HIP_TRY(hipMemsetAsync(e->d_cpAcc, 0, sizeof(sph::CoupleAcc), e->stream));
     return SPH_OK;
 }
-// The host mirror to the device, stream-ordered, through the next pinned staging slot.
+// The host mirror to the device, stream-ordered.
 static int couple_upload(SphEngine* e) {
-    if (!e->d_cpTab) return SPH_OK;
-    int rc;
-    sph::CoupleTab* slot = nullptr;
-    if ((rc = e->cpStage.next(&slot))) return rc;
-    *slot = e->cpTab;
-    HIP_TRY(hipMemcpyAsync(e->d_cpTab, slot, sizeof(sph::CoupleTab), hipMemcpyHostToDevice, e->stream));
-    return e->cpStage.commit(e->stream);
+    return e->d_cpTab.p ? e->d_cpTab.put(e, &e->cpTab) : SPH_OK;
 }
 static int couple_clear(SphEngine* e) {
     e->cpTab = sph::CoupleTab{};
@@ -5836,25 +5833,14 @@ static void gate_to_rec(const SphGate& g, sph::GateRec& r) {
     for (int a = 0; a < 3; ++a) { r.c[a] = g.center[a]; r.u[a] = g.u[a]; r.v[a] = g.v[a]; }
     sph::gate_derive(r);
 }
-// The host mirror to the device, stream-ordered, through the next pinned staging slot.
-static int gates_upload(SphEngine* e) {
-    int rc;
-    sph::GateTab* slot = nullptr;
-    if ((rc = e->gtStage.next(&slot))) return rc;
-    *slot = e->gtTab;
-    HIP_TRY(hipMemcpyAsync(e->d_gtTab, slot, sizeof(sph::GateTab), hipMemcpyHostToDevice, e->stream));
-    return e->gtStage.commit(e->stream);
-}
 // The buffers, at the first call that sets a gate; the ring grows with the history asked for.
 static int gates_ensure(SphEngine* e, uint32_t history) {
     int rc;
-    if (!e->d_gtTab) {
-        hipError_t er = hipSuccess;
-        if ((rc = dev_alloc(&e->d_gtTab, 1)) || (rc = dev_alloc(&e->d_gtAcc, 1)) || (er = e->gtStage.create(e->stream, 1)) != hipSuccess ||
+    if (!e->d_gtTab.p) {
+        if ((rc = e->d_gtTab.ensure(e, 1, "pinned staging of the gate table")) || (rc = dev_alloc(&e->d_gtAcc, 1)) ||
             (rc = e->d_gtPart.grow(e, (size_t)kGateGrid * kGateTerms))) {
-            dev_free(e->d_gtTab); dev_free(e->d_gtAcc);
-            e->gtStage.destroy();
-            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the gate table: %s", hipGetErrorString(er));
+            gates_free(e);
+            return rc;
         }
         HIP_TRY(hipMemsetAsync(e->d_gtAcc, 0, sizeof(sph::GateAcc), e->stream));
     }
@@ -5868,12 +5854,11 @@ static int gates_ensure(SphEngine* e, uint32_t history) {
 int sph_gates_set(SphEngine* e, const SphGate* gates, int count, uint32_t history, uint32_t stride) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) return fail(SPH_ERR_STATE, "gates on a z-slab engine are not supported: a crossing needs the entry and the exit state at one slot");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
     int rc;
-    if ((rc = gates_check(gates, count))) return rc;
+    if ((rc = needs_sorted_copy(e, "gates need")) || (rc = gates_check(gates, count))) return rc;
     if (history > SPH_MAX_GATE_HISTORY) return fail(SPH_ERR_ARG, "history %u above %d", history, SPH_MAX_GATE_HISTORY);
     if (stride == 0) return fail(SPH_ERR_ARG, "stride must be >= 1");
-    if (!count && !e->d_gtTab) return SPH_OK;                         // (never set: nothing to clear)
+    if (!count && !e->d_gtTab.p) return SPH_OK;                        // (never set: nothing to clear)
     if ((rc = gates_ensure(e, history))) return rc;
     if (count != e->gtTab.count || history != e->gtTab.history || stride != e->gtTab.stride) {   // (another count, history or stride: books and ring restart)
         HIP_TRY(hipMemsetAsync(e->d_gtAcc, 0, sizeof(sph::GateAcc), e->stream));
@@ -5884,7 +5869,7 @@ int sph_gates_set(SphEngine* e, const SphGate* gates, int count, uint32_t histor
         else { std::memset(&e->gtTab.g[i], 0, sizeof(sph::GateRec)); std::memset(&e->gtSet[i], 0, sizeof(SphGate)); }
     }
     e->gtTab.count = count; e->gtTab.history = history; e->gtTab.stride = stride;
-    return gates_upload(e);
+    return e->d_gtTab.put(e, &e->gtTab);
 }
 
 int sph_gates_get(SphEngine* e, SphGate* out, int cap, int* countOut, uint32_t* historyOut, uint32_t* strideOut) {
@@ -5916,25 +5901,25 @@ int sph_gates_books(SphEngine* e, SphGateBooks* books, double* timeOut, uint64_t
 int sph_gates_history(SphEngine* e, uint64_t* firstOut, uint32_t* countOut, SphGateBooks* rows, double* times) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     const uint32_t H = e->gtTab.count ? e->gtTab.history : 0u, S = std::max(e->gtTab.stride, 1u);
-    uint64_t taken = 0;
-    std::vector<unsigned long long> ring;
+    sph::RingSpan span{0, 0};
+    std::vector<unsigned long long> held;                              // the rows the ring holds, oldest first
     if (H && e->d_gtAcc) {
         unsigned long long steps = 0;
-        ring.resize((size_t)H * kGateRingRow);
         HIP_TRY(hipMemcpyAsync(&steps, &e->d_gtAcc->ringSteps, sizeof(steps), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(ring.data(), e->d_gtRing.p, sizeof(unsigned long long) * ring.size(), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        taken = steps / S;
+        span = sph::ring_span(steps / S, H);                           // one row per S counted substeps
+        held.resize((size_t)span.have * kGateRingRow);
+        int rc;
+        if ((rc = ring_read(e, e->d_gtRing.p, sizeof(unsigned long long) * kGateRingRow, H, span, held.data()))) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
     }
-    const uint32_t have = (uint32_t)std::min<uint64_t>(taken, H);
-    const uint64_t first = taken - have;
-    for (uint32_t i = 0; i < have; ++i) {
-        const unsigned long long* row = ring.data() + (size_t)((first + i) % H) * kGateRingRow;
+    for (uint32_t i = 0; i < span.have; ++i) {
+        const unsigned long long* row = held.data() + (size_t)i * kGateRingRow;
         if (rows) std::memcpy(rows + (size_t)i * e->gtTab.count, row, sizeof(SphGateBooks) * (size_t)e->gtTab.count);
         if (times) std::memcpy(times + i, row + kGateTerms, sizeof(double));
     }
-    if (firstOut) *firstOut = first;
-    if (countOut) *countOut = have;
+    if (firstOut) *firstOut = span.first;
+    if (countOut) *countOut = span.have;
     return SPH_OK;
 }
 
@@ -5980,8 +5965,7 @@ static constexpr size_t kMonitorRingBytes = (size_t)256 << 20;
 static int monitor_refused(const SphEngine* e) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) return fail(SPH_ERR_STATE, "monitors on a z-slab engine are not supported: its halo records after a step are the step's entry state");
-    if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "monitors need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
-    return SPH_OK;
+    return needs_sorted_copy(e, "monitors need");
 }
 static int monitor_slot_check(int slot) {
     if (slot < 0 || slot >= SPH_MAX_MONITORS) return fail(SPH_ERR_ARG, "monitor slot %d outside 0..%d", slot, SPH_MAX_MONITORS - 1);
@@ -6011,34 +5995,22 @@ static sph::MonitorTab monitor_fresh_tab(const SphMonitorConfig& cfg, const sph:
     t.L = L;
     return t;
 }
-// Rows, ring and times to zero and the fresh table to the device, stream-ordered (the table through the next pinned staging slot).
+// Rows, ring and times to zero and the fresh table to the device, stream-ordered.
 static int monitor_restart(SphEngine* e, MonitorSlot& s) {
-    int rc;
     HIP_TRY(hipMemsetAsync(s.d_rows.p, 0, s.m * sizeof(sph::MonitorRow), e->stream));
     if (s.tab.history) {
         HIP_TRY(hipMemsetAsync(s.d_ring.p, 0, (size_t)s.tab.history * s.tab.ringPoints * 2 * sizeof(float4), e->stream));
         HIP_TRY(hipMemsetAsync(s.d_times.p, 0, (size_t)s.tab.history * sizeof(double), e->stream));
     }
-    sph::MonitorTab* slot = nullptr;
-    if ((rc = s.stage.next(&slot))) return rc;
-    *slot = s.tab;
-    HIP_TRY(hipMemcpyAsync(s.d_tab, slot, sizeof(sph::MonitorTab), hipMemcpyHostToDevice, e->stream));
-    return s.stage.commit(e->stream);
+    return s.d_tab.put(e, &s.tab);
 }
 // The buffers of a slot about to hold `m` points of `kind` under cfg (arguments already checked).  A slot that keeps kind, M and ring
 // layout keeps every buffer, and the graphs captured over them.
 static int monitor_ensure(SphEngine* e, int slot, int kind, size_t m, const SphMonitorConfig& cfg) {
     MonitorSlot& s = e->mon[slot];
     int rc;
-    if (!s.d_tab) {
-        hipError_t er = hipSuccess;
-        if ((rc = dev_alloc(&s.d_tab, 1)) || (er = s.stage.create(e->stream, 1)) != hipSuccess) {
-            monitor_free(e, slot);
-            return rc ? rc : fail(SPH_ERR_HIP, "pinned staging of the monitor table: %s", hipGetErrorString(er));
-        }
-    }
     const size_t ring = std::max<size_t>((size_t)cfg.history * cfg.ringPoints * 2, 1);
-    if ((rc = s.d_rows.grow(e, m)) || (rc = s.d_ring.grow(e, ring)) || (rc = s.d_times.grow(e, std::max<size_t>(cfg.history, 1))) ||
+    if ((rc = s.d_tab.ensure(e, 1, "pinned staging of the monitor table")) || (rc = s.d_rows.grow(e, m)) || (rc = s.d_ring.grow(e, ring)) || (rc = s.d_times.grow(e, std::max<size_t>(cfg.history, 1))) ||
         (kind == SPH_MONITOR_POINTS && ((rc = s.d_points.grow(e, m)) || (rc = s.d_perm.grow(e, m))))) {
         monitor_free(e, slot);
         return rc;
@@ -6122,15 +6094,13 @@ int sph_monitor_set_lattice(SphEngine* e, int slot, const float origin[3], const
 }
 // The device's counters of a slot that holds a monitor.  Synchronises.
 static int monitor_counters(SphEngine* e, const MonitorSlot& s, sph::MonitorTab* out) {
-    HIP_TRY(hipMemcpyAsync(out, s.d_tab, sizeof(sph::MonitorTab), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(out, s.d_tab.p, sizeof(sph::MonitorTab), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SPH_OK;
 }
-// Ring rows written by `a` acting substeps, and how many of them the ring still holds.
-static void monitor_ring_span(const sph::MonitorTab& t, uint64_t* first, uint32_t* have) {
-    const uint64_t taken = t.history ? (t.a + t.stride - 1) / t.stride : 0;
-    *have = (uint32_t)std::min<uint64_t>(taken, t.history);
-    *first = taken - *have;
+// The ring rows a slot still holds: one per `stride` acting substeps, the first acting substep writing row 0.
+static sph::RingSpan monitor_ring_span(const sph::MonitorTab& t) {
+    return sph::ring_span(t.history ? (t.a + t.stride - 1) / t.stride : 0, t.history);
 }
 int sph_monitor_info(SphEngine* e, int slot, SphMonitorInfo* out) {
     if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
@@ -6144,9 +6114,8 @@ int sph_monitor_info(SphEngine* e, int slot, SphMonitorInfo* out) {
     out->kind = s.kind; out->points = s.m; out->config = s.cfg;
     for (int a = 0; a < 3; ++a) { out->dims[a] = s.dims[a]; out->origin[a] = s.origin[a]; out->spacing[a] = s.spacing[a]; }
     out->substeps = t.c; out->acting = t.a; out->time = t.time;
-    uint64_t first; uint32_t have;
-    monitor_ring_span(t, &first, &have);
-    out->firstRow = first; out->ringRows = have;
+    const sph::RingSpan span = monitor_ring_span(t);
+    out->firstRow = span.first; out->ringRows = span.have;
     return SPH_OK;
 }
 int sph_monitor_download(SphEngine* e, int slot, SphMonitorRow* out, size_t cap) {
@@ -6172,22 +6141,18 @@ int sph_monitor_history(SphEngine* e, int slot, uint64_t* firstOut, uint32_t* co
     int rc;
     if ((rc = monitor_slot_check(slot))) return rc;
     const MonitorSlot& s = e->mon[slot];
-    uint64_t first = 0; uint32_t have = 0;
+    sph::RingSpan span{0, 0};
     if (s.kind != SPH_MONITOR_NONE && s.tab.history) {
         sph::MonitorTab t;
         if ((rc = monitor_counters(e, s, &t))) return rc;
-        monitor_ring_span(t, &first, &have);
-        if ((samples || times) && rowCap < have) return fail(SPH_ERR_CAPACITY, "%u ring rows (capacity %zu)", have, rowCap);
-        const size_t rowBytes = (size_t)t.ringPoints * sizeof(SphSample);
-        for (uint32_t i = 0; i < have; ++i) {                          // (oldest first: the ring's rows in chronological order)
-            const size_t r = (size_t)((first + i) % t.history);
-            if (samples) HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(samples) + i * rowBytes, reinterpret_cast<const char*>(s.d_ring.p) + r * rowBytes, rowBytes, hipMemcpyDeviceToHost, e->stream));
-            if (times) HIP_TRY(hipMemcpyAsync(times + i, s.d_times.p + r, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        }
+        span = monitor_ring_span(t);
+        if ((samples || times) && rowCap < span.have) return fail(SPH_ERR_CAPACITY, "%u ring rows (capacity %zu)", span.have, rowCap);
+        if (samples && (rc = ring_read(e, s.d_ring.p, (size_t)t.ringPoints * sizeof(SphSample), t.history, span, samples))) return rc;
+        if (times && (rc = ring_read(e, s.d_times.p, sizeof(double), t.history, span, times))) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
-    if (firstOut) *firstOut = first;
-    if (countOut) *countOut = have;
+    if (firstOut) *firstOut = span.first;
+    if (countOut) *countOut = span.have;
     return SPH_OK;
 }
 int sph_monitor_field(SphEngine* e, int slot, int field, float* devOut) {
@@ -6288,13 +6253,10 @@ int sph_obstacles_set_dynamics(SphEngine* e, int index, const SphObstacleDynamic
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     int rc;
     if ((rc = obstacles_refuse_slab(e)) || (rc = obstacle_index_check(e, index))) return rc;
-    sph::ObsDyn rec, *slot = nullptr;
+    sph::ObsDyn rec;
     std::memset(&rec, 0, sizeof(rec));
     if (dyn && (rc = dynamics_to_rec(*dyn, index, rec))) return rc;
-    if ((rc = e->dynStage.next(&slot))) return rc;
-    *slot = rec;
-    HIP_TRY(hipMemcpyAsync(&e->d_dyn[index], slot, sizeof(sph::ObsDyn), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->dynStage.commit(e->stream))) return rc;
+    if ((rc = e->d_dyn.put(e, &rec, 1, (size_t)index))) return rc;
     const bool on = dyn != nullptr;
     e->dynCount += (on ? 1 : 0) - (e->dynOn[index] ? 1 : 0);
     e->dynOn[index] = on;
@@ -6343,11 +6305,7 @@ static int volume_free_slot(SphEngine* e, int* idOut) {
     int rc, id = -1;
     for (int i = 0; i < kVolMax; ++i) if (!e->vols[i].d) { id = i; break; }
     if (id < 0) return fail(SPH_ERR_CAPACITY, "all %d volume slots are in use", kVolMax);
-    if (!e->d_volTab) {
-        if ((rc = dev_alloc(&e->d_volTab, 1))) return rc;
-        const hipError_t er = e->volStage.create(e->stream, 1);
-        if (er != hipSuccess) { volumes_free(e); return fail(SPH_ERR_HIP, "volume staging: %s", hipGetErrorString(er)); }
-    }
+    if ((rc = e->d_volTab.ensure(e, 1, "volume staging"))) return rc;
     *idOut = id;
     return SPH_OK;
 }
@@ -6655,7 +6613,7 @@ struct StateSection {
 
 static void state_tracer_words(uint64_t steps, uint32_t K, uint32_t S, uint32_t out[3]) {
     out[0] = (uint32_t)steps; out[1] = (uint32_t)(steps >> 32);
-    out[2] = (K != 0u && (steps + 1ull) % S == 0ull) ? (uint32_t)(((steps + 1ull) / S) % K) : sph::kTracerNoSlot;   // tracer_slot_of(steps + 1)
+    out[2] = sph::tracer_slot_of(steps + 1ull, K, S);
 }
 
 // The sections of the engine as it stands.  current: also bring the 80-byte records up to date (a launch; sizes do not need it).
@@ -6731,7 +6689,7 @@ static int state_collect(SphEngine* e, bool current, std::vector<StateSection>& 
         s.tag = SPH_STATE_SCALARS;
         sph::StateScalars c;
         std::memset(&c, 0, sizeof(c));
-        c.channels = e->scK; c.hasCouple = e->d_cpTab ? 1u : 0u; c.accBytes = (uint32_t)sizeof(sph::CoupleAcc); c.steps = e->scSteps;
+        c.channels = e->scK; c.hasCouple = e->d_cpTab.p ? 1u : 0u; c.accBytes = (uint32_t)sizeof(sph::CoupleAcc); c.steps = e->scSteps;
         if (current) {
             HIP_TRY(hipMemcpyAsync(&c.stateWord, e->d_scState, 4, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
@@ -6764,15 +6722,15 @@ static int state_collect(SphEngine* e, bool current, std::vector<StateSection>& 
             if (e->vols[i].d) for (int a = 0; a < 3; ++a) { o.vol[i].dims[a] = e->vols[i].dims[a]; o.vol[i].spacing[a] = e->vols[i].spacing[a]; }
         s.add_host(&o, sizeof(o));
         if (e->obsK) {
-            s.add_dev(e->d_obs, sizeof(sph::ObsRec) * (size_t)e->obsK);
+            s.add_dev(e->d_obs.p, sizeof(sph::ObsRec) * (size_t)e->obsK);
             s.add_dev(e->d_obsAcc, sizeof(sph::ObsAcc));
-            s.add_dev(e->d_dyn, sizeof(sph::ObsDyn) * (size_t)e->obsK);
+            s.add_dev(e->d_dyn.p, sizeof(sph::ObsDyn) * (size_t)e->obsK);
         }
         for (int i = 0; i < sph::kVolMax; ++i)
             if (e->vols[i].d && (rc = s.add_dev32(e, e->vols[i].d, (size_t)e->vols[i].dims[0] * e->vols[i].dims[1] * e->vols[i].dims[2], current))) return rc;
         out.push_back(std::move(s));
     }
-    if (e->gtTab.count && e->d_gtTab) {
+    if (e->gtTab.count && e->d_gtTab.p) {
         StateSection s;
         s.tag = SPH_STATE_GATES;
         sph::StateGates g;
@@ -6802,7 +6760,7 @@ static int state_collect(SphEngine* e, bool current, std::vector<StateSection>& 
         for (int i = 0; i < sph::kMonitorMax; ++i) {
             const MonitorSlot& m = e->mon[i];
             if (m.kind == SPH_MONITOR_NONE) continue;
-            s.add_dev(m.d_tab, sph::kStateMonitorCounters);
+            s.add_dev(m.d_tab.p, sph::kStateMonitorCounters);
             if (m.kind == SPH_MONITOR_POINTS) s.add_dev(m.d_points.p, m.m * sizeof(float4));
             s.add_dev(m.d_rows.p, m.m * sizeof(sph::MonitorRow));
             s.add_dev(m.d_ring.p, (size_t)m.cfg.history * m.cfg.ringPoints * sizeof(SphSample));
@@ -6959,7 +6917,7 @@ static int state_load_check(SphEngine* e, const unsigned char* b, const SphState
         if (std::memcmp(want, t.state, sizeof(want)) != 0) return fail(SPH_ERR_ARG, "checkpoint blob: the tracers' device words do not belong to %llu substeps", (unsigned long long)t.hostSteps);
     }
     if (info.sections & SPH_STATE_DIFFUSE) {
-        if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "diffuse particles need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+        if ((rc = needs_sorted_copy(e, "diffuse particles need"))) return rc;
         sph::StateDiffuse d;
         std::memcpy(&d, b + info.offset[3], sizeof(d));
         if ((rc = diffuse_check_config(d.cfg))) return rc;
@@ -7003,7 +6961,7 @@ static int state_load_check(SphEngine* e, const unsigned char* b, const SphState
             if (sph::state_volume_points(o->vol[i]) > 0 && (rc = check_lattice(o->vol[i].dims, o->vol[i].spacing, 2, nullptr))) return rc;
     }
     if (info.sections & SPH_STATE_GATES) {
-        if (e->optGridBuild == 1) return fail(SPH_ERR_STATE, "gates need the counting-sort grid build (SPH_OPT_GRID_BUILD 0): the linked-list variant keeps no sorted copy");
+        if ((rc = needs_sorted_copy(e, "gates need"))) return rc;
         sph::StateGates g;
         std::memcpy(&g, b + info.offset[6], sizeof(g));
         if ((rc = gates_check(g.set, g.count))) return rc;
@@ -7111,9 +7069,9 @@ int sph_state_load(SphEngine* e, const void* blob, size_t bytes) {
         for (int i = 0; i < o->count; ++i)
             if (o->bind[i] >= 0 && (rc = sph_obstacles_bind_volume(e, i, o->bind[i]))) return rc;
         if (o->count) {                                               // the advanced poses, the sums and the device's dynamics records over what the set calls made
-            HIP_TRY(hipMemcpyAsync(e->d_obs, recs, sizeof(sph::ObsRec) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->d_obs.p, recs, sizeof(sph::ObsRec) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
             HIP_TRY(hipMemcpyAsync(e->d_obsAcc, acc, sizeof(sph::ObsAcc), hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(e->d_dyn, dyn, sizeof(sph::ObsDyn) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->d_dyn.p, dyn, sizeof(sph::ObsDyn) * (size_t)o->count, hipMemcpyHostToDevice, e->stream));
         }
     }
     if (info.sections & SPH_STATE_SCALARS) {
@@ -7202,11 +7160,7 @@ int sph_state_load(SphEngine* e, const void* blob, size_t bytes) {
             tab.c = ca[0]; tab.a = ca[1]; tab.time = time;
             tab.act = sph::monitor_acts(tab.c, tab.every) ? 1u : 0u;
             tab.row = sph::monitor_row_of(tab.a, tab.history, tab.stride);
-            sph::MonitorTab* slot = nullptr;
-            if ((rc = m.stage.next(&slot))) return rc;
-            *slot = tab;
-            HIP_TRY(hipMemcpyAsync(m.d_tab, slot, sizeof(sph::MonitorTab), hipMemcpyHostToDevice, e->stream));
-            if ((rc = m.stage.commit(e->stream))) return rc;
+            if ((rc = m.d_tab.put(e, &tab))) return rc;
         }
     }
     HIP_TRY(hipStreamSynchronize(e->stream));

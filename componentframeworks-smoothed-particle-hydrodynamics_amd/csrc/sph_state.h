@@ -175,12 +175,19 @@ inline long long state_volume_points(const StateVolume& v) {
     return total;
 }
 
+// A history ring of `history` rows that has taken `taken` rows so far, row q into slot q mod history: the oldest row it still holds and
+// how many it holds.  The one statement of the rule for the engine's three rings (pathlines, gate history, monitor history); it lives
+// here because this is the host code that must also compile without HIP.
+struct RingSpan { uint64_t first; uint32_t have; };
+inline RingSpan ring_span(uint64_t taken, uint32_t history) {
+    const uint32_t have = (uint32_t)(taken < history ? taken : history);
+    return RingSpan{taken - have, have};
+}
+
 // The ring slots of the tracers' pathlines written so far: snapshot q (taken after q * stride substeps, 0 the seed) lies in slot q mod
-// history, so after `steps` substeps the slots [0, min(steps / stride + 1, history)) hold snapshots and the others were never written.
+// history, so after `steps` substeps the first `have` slots hold snapshots and the others were never written.
 inline uint64_t state_tracer_slots(uint64_t steps, uint32_t history, uint32_t stride) {
-    if (!history || !stride) return 0;
-    const uint64_t taken = steps / stride + 1u;
-    return taken < history ? taken : history;
+    return (history && stride) ? ring_span(steps / stride + 1u, history).have : 0;
 }
 
 inline const char* state_section_name(uint32_t tag) {

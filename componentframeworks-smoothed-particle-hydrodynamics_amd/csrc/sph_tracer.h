@@ -28,7 +28,7 @@ constexpr int kTracerRefresh = SPH_TRACER_REFRESH;
 constexpr int kTracerAhead = 4;             // candidates whose records are in flight before the first of them is accumulated
 
 // state[0], state[1]: low / high word of the substeps c that advected this tracer set; state[2]: ring slot substep c + 1 writes, or none
-__device__ __forceinline__ uint32_t tracer_slot_of(unsigned long long c, uint32_t K, uint32_t S) {
+__host__ __device__ __forceinline__ uint32_t tracer_slot_of(unsigned long long c, uint32_t K, uint32_t S) {
     return (K != 0u && c % S == 0ull) ? (uint32_t)((c / S) % K) : kTracerNoSlot;
 }
 

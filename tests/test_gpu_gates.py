@@ -239,6 +239,30 @@ def test_lifetimes(pkg):
         g.close()
 
 
+def test_a_wrapped_ring_is_read_in_two_unequal_pieces(pkg):
+    """H = 5, S = 3, 20 substeps: six rows taken, the ring holds rows 1 .. 5 and the oldest of them lies in slot 1, so the read-out is
+    slots 1 .. 4 and then slot 0.  Rows and times equal, bit for bit, the books of single dispatches after 6, 9, 12, 15 and 18 substeps."""
+    rec, sp, c, E, _ = _scene(pkg)
+    gates = _gates(pkg, c, E)
+    f, g = engine(pkg, rec, sp), engine(pkg, rec, sp)
+    try:
+        f.set_gates(gates, history=5, stride=3)
+        g.set_gates(gates)
+        f.DispatchN(20)
+        want = []
+        for i in range(1, 19):
+            g.DispatchCompute()
+            if i % 3 == 0 and i >= 6:
+                want.append(g.gate_books())
+        first, rows, times = f.gate_history()
+        assert first == 1 and rows.shape == (5, 8) and int(rows[-1]["forward"].sum()) > 0
+        for k, (books, t, n) in enumerate(want):
+            assert rows[k].tobytes() == books.tobytes() and times[k] == t, f"ring row {first + k} (after {n} substeps)"
+    finally:
+        f.close()
+        g.close()
+
+
 def test_a_recycled_particle_is_not_booked(pkg):
     """The fountain recycles behind the gate step: with every particle recycled across a plane in every substep the books equal those
     of the same substep without the fountain, and the jump itself is no crossing of the next substep either."""
