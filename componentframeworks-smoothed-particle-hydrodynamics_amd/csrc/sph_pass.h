@@ -23,17 +23,31 @@ struct SortedIn {
     __device__ __forceinline__ float4 V(uint32_t q) const { return pv[2u * q + 1u]; }     // (vx, vy, vz, P)
 };   // written by k_rank<true>
 
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// STREAM: the five SoA stores are non-temporal.  k_sph_walk's gathers live on the lines its CU's L1 holds (69 % of its line accesses
+// hit there); the pass never reads its own output, and with plain stores those 29 lines per wave cost the walks L1 hits
+// (profiles/r29_walk_cache_policy_counters.json).  The next kernel finds the lines in L2 either way.
+template <bool STREAM = false>
 __device__ __forceinline__ void store_fields(const SimK& k, const StateOut& out, int s, uint32_t flags, uint32_t id, float px, float py,
                                              float pz, float vx, float vy, float vz, float ax, float ay, float az, float rho, float prs,
                                              float foamOut, int czEntry) {
     if (!(flags & F_GHOSTNZ)) obb_apply(k, px, py, pz, vx, vy, vz);   // OBBConstraints.comp:46
     slab_check_layer_move(k, czEntry, pz);
-    out.pos[s] = make_float4(px, py, pz, bitsf(flags));
-    out.vel[s] = make_float4(vx, vy, vz, bitsf(id));
-    out.rp[s] = make_float2(rho, prs);
-    out.foam[s] = foamOut;
+    if constexpr (!STREAM) {
+        out.pos[s] = make_float4(px, py, pz, bitsf(flags));
+        out.vel[s] = make_float4(vx, vy, vz, bitsf(id));
+        out.rp[s] = make_float2(rho, prs);
+        out.foam[s] = foamOut;
+    } else {
+        __builtin_nontemporal_store(v4f{px, py, pz, bitsf(flags)}, reinterpret_cast<v4f*>(&out.pos[s]));
+        __builtin_nontemporal_store(v4f{vx, vy, vz, bitsf(id)}, reinterpret_cast<v4f*>(&out.vel[s]));
+        __builtin_nontemporal_store(v2f{rho, prs}, reinterpret_cast<v2f*>(&out.rp[s]));
+        __builtin_nontemporal_store(foamOut, &out.foam[s]);
+    }
     if (out.aos) aos_write_fluid(out.aos, id - out.idBase, px, py, pz, vx, vy, vz, ax, ay, az, rho, prs, foamOut);
-    else out.acc[s] = make_float4(ax, ay, az, 0.0f);
+    else if constexpr (!STREAM) out.acc[s] = make_float4(ax, ay, az, 0.0f);
+    else __builtin_nontemporal_store(v4f{ax, ay, az, 0.0f}, reinterpret_cast<v4f*>(&out.acc[s]));
 }
 
 // Halo copy / ghost branch of SPHFluid.comp:72-83 for sorted slot s.  Returns true when the slot is done.
