@@ -27,6 +27,7 @@
 #include "sph_neighbors.h"
 #include "sph_components.h"
 #include "sph_knn.h"
+#include "sph_aggregate.h"
 #include "sph_shell.h"
 #include "sph_aniso.h"
 #include "sph_rays.h"
@@ -346,6 +347,10 @@ struct SphEngine {
     SphRaySpansInfo spansInfo{};
     bool spansValid = false;
     int optKnnVariant = 0;                  // SPH_OPT_KNN_VARIANT: 0 = k_knn (LDS), 1 = k_knn_select (same bits)
+    // sph_aggregate_*: the caller's values in slot order (the stage of the default variant); no result is kept
+    DevBuf<float> d_aggStage, d_aggIn, d_aggOut;   // (d_aggIn / d_aggOut / d_aggCnt: the device side of sph_aggregate_staged's host arrays)
+    DevBuf<uint32_t> d_aggCnt;
+    int optAggVariant = 0;                  // SPH_OPT_AGGREGATE_VARIANT: bit 0 gather by id (no stage), bits 1-2 channels per pass, bit 3 4-byte loads (same bits)
     // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
     // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets); the two words of the reduction
     DevBuf<sph::ShellRow> d_shRows;
@@ -646,6 +651,7 @@ void shell_free(SphEngine* e) {
     e->d_shStats.release(); e->d_shOffsets.release();
     e->shellInfo = SphShellInfo{};
 }
+void aggregate_free(SphEngine* e) { e->d_aggStage.release(); e->d_aggIn.release(); e->d_aggOut.release(); e->d_aggCnt.release(); }
 void aniso_free(SphEngine* e) {
     e->d_anRows.release(); e->d_anSlots.release(); e->d_anStats.release();
     e->anisoInfo = SphAnisoInfo{};
@@ -1645,6 +1651,7 @@ int sph_destroy(SphEngine* e) {
     rays_free(e);
     shell_free(e);
     aniso_free(e);
+    aggregate_free(e);
     surface_free(e);
     stats_free(e);
     tracers_free(e);
@@ -1690,6 +1697,7 @@ int sph_reset(SphEngine* e, size_t nRequested, uint32_t seed) {       // SPHFlui
     rays_free(e);                                                     // (and the ray hits and spans)
     shell_free(e);                                                    // (and the free-surface rows)
     aniso_free(e);                                                    // (and the anisotropy rows)
+    aggregate_free(e);                                                // (and the stage of the neighbourhood reductions)
     tracers_free(e);                                                  // (and the tracer set)
     diffuse_free(e);                                                  // (and the pool of diffuse particles)
     scalars_free(e);                                                  // (and the scalar channels)
@@ -1737,6 +1745,7 @@ int sph_set_option(SphEngine* e, int option, int value) {
     case SPH_OPT_KNN_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optKnnVariant = value; break;
     case SPH_OPT_RAYS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaysVariant = value; break;
     case SPH_OPT_RAY_SPANS_VARIANT: if (value < 0 || value > 1) return fail(SPH_ERR_ARG, "bad value"); e->optRaySpansVariant = value; break;
+    case SPH_OPT_AGGREGATE_VARIANT: if (value < 0 || value > 15) return fail(SPH_ERR_ARG, "bad value"); e->optAggVariant = value; break;
     case SPH_OPT_SHELL_TIMED: if (value < 0 || value > 3) return fail(SPH_ERR_ARG, "bad value"); e->optShellTimed = value; break;
     case SPH_OPT_DEBUG:
         e->debugFlags = value;
@@ -1766,6 +1775,7 @@ int sph_get_option(const SphEngine* e, int option, int* value) {
     case SPH_OPT_KNN_VARIANT: *value = e->optKnnVariant; break;
     case SPH_OPT_RAYS_VARIANT: *value = e->optRaysVariant; break;
     case SPH_OPT_RAY_SPANS_VARIANT: *value = e->optRaySpansVariant; break;
+    case SPH_OPT_AGGREGATE_VARIANT: *value = e->optAggVariant; break;
     case SPH_OPT_SHELL_TIMED: *value = e->optShellTimed; break;
     case SPH_OPT_GRAPH_LAUNCHES: *value = (int)e->graphLaunches; break;
     case SPH_OPT_DEBUG: *value = e->debugFlags; break;
@@ -4667,6 +4677,206 @@ int sph_aniso_lattice_host(const SphParticle* particles, size_t n, const SphPara
     return SPH_OK;
 }
 
+// ---- fused neighbourhood reductions of caller tensors (sph_aggregate.h) ---------------------------------
+static_assert(sizeof(SphAggregateConfig) == 32 && sizeof(SphAggregateInfo) == 32, "SphAggregateConfig is 32 bytes, SphAggregateInfo 32");
+static_assert(SPH_AGGREGATE_SELF == sph::kAggSelf && SPH_AGGREGATE_FLUID_ONLY == sph::kAggFluidOnly && SPH_AGGREGATE_DELTA == sph::kAggDelta &&
+              SPH_AGGREGATE_MOMENTS == sph::kAggMoments && SPH_AGGREGATE_SUM == sph::kAggSum && SPH_AGGREGATE_MEAN == sph::kAggMean &&
+              SPH_AGGREGATE_MAX == sph::kAggMax && SPH_AGGREGATE_MIN == sph::kAggMin && SPH_AGGREGATE_WEIGHT_ONE == sph::kAggWeightOne &&
+              SPH_AGGREGATE_WEIGHT_POLY6 == sph::kAggWeightPoly6 && SPH_AGGREGATE_MAX_CHANNELS == sph::kAggMaxChannels, "sph_aggregate.h mirrors SPH_AGGREGATE_*");
+
+void sph_aggregate_default(SphAggregateConfig* cfg) {
+    if (!cfg) return;
+    *cfg = SphAggregateConfig{};
+    cfg->op = SPH_AGGREGATE_SUM;
+    cfg->weight = SPH_AGGREGATE_WEIGHT_ONE;
+    cfg->channels = 1;
+}
+
+// The config as an argument: the stencil half-width through *stencil.
+static int aggregate_check(const SphAggregateConfig& c, float cellSize, bool query, int* stencil) {
+    if (c.op < SPH_AGGREGATE_SUM || c.op > SPH_AGGREGATE_MIN) return fail(SPH_ERR_ARG, "unknown aggregate op %d", c.op);
+    if (c.weight < SPH_AGGREGATE_WEIGHT_ONE || c.weight > SPH_AGGREGATE_WEIGHT_POLY6) return fail(SPH_ERR_ARG, "unknown aggregate weight %d", c.weight);
+    if (c.flags & ~(SPH_AGGREGATE_SELF | SPH_AGGREGATE_FLUID_ONLY | SPH_AGGREGATE_DELTA | SPH_AGGREGATE_MOMENTS)) return fail(SPH_ERR_ARG, "unknown aggregate flags %d", c.flags);
+    if (c.pad[0] || c.pad[1] || c.pad[2]) return fail(SPH_ERR_ARG, "the padding of SphAggregateConfig must be zero");
+    if (c.channels < 1 || c.channels > SPH_AGGREGATE_MAX_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (1 .. %d)", c.channels, (int)SPH_AGGREGATE_MAX_CHANNELS);
+    if ((c.flags & SPH_AGGREGATE_MOMENTS) && c.op != SPH_AGGREGATE_SUM) return fail(SPH_ERR_ARG, "SPH_AGGREGATE_MOMENTS goes with SPH_AGGREGATE_SUM only");
+    if ((c.op == SPH_AGGREGATE_MAX || c.op == SPH_AGGREGATE_MIN) && c.weight != SPH_AGGREGATE_WEIGHT_ONE) return fail(SPH_ERR_ARG, "SPH_AGGREGATE_MAX / _MIN take the weight ONE");
+    if (query && (c.flags & (SPH_AGGREGATE_SELF | SPH_AGGREGATE_DELTA))) return fail(SPH_ERR_ARG, "SPH_AGGREGATE_SELF / _DELTA apply to particle targets only");
+    return radius_stencil(c.radius, cellSize, stencil);
+}
+
+static int aggregate_planes(const SphAggregateConfig& c) { return (c.flags & SPH_AGGREGATE_MOMENTS) ? 4 : 1; }
+
+// Do [a, a + aBytes) and [b, b + bBytes) share an address?
+static bool ranges_overlap(const void* a, size_t aBytes, const void* b, size_t bBytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return aBytes && bBytes && a0 < b0 + bBytes && b0 < a0 + aBytes;
+}
+
+// One launch of the instance the config and SPH_OPT_AGGREGATE_VARIANT select (arguments already checked).
+static void aggregate_launch(SphEngine* e, bool query, const sph::SimK& k, const sph::NbK& nb, const sph::AggK& ag, int chunk, bool moments, const float4* devPoints,
+                             size_t rows, const float* vals, float* devOut, uint32_t* devCount) {
+    using namespace sph;
+    using Kernel = void (*)(SimK, NbK, AggK, const float4*, const uint32_t*, const int32_t*, const float4*, const float4*, size_t, const float*, float*, uint32_t*);
+    const bool extremum = ag.op == kAggMax || ag.op == kAggMin;
+    auto pick = [&](auto ch) -> Kernel {
+        constexpr int CH = decltype(ch)::value;
+        if (extremum) return query ? (Kernel)k_aggregate<false, true, false, CH> : (Kernel)k_aggregate<true, true, false, CH>;
+        if (moments) return query ? (Kernel)k_aggregate<false, false, true, CH> : (Kernel)k_aggregate<true, false, true, CH>;
+        return query ? (Kernel)k_aggregate<false, false, false, CH> : (Kernel)k_aggregate<true, false, false, CH>;
+    };
+    const Kernel kernel = chunk == 4 ? pick(std::integral_constant<int, 4>{}) : chunk == 8 ? pick(std::integral_constant<int, 8>{}) : pick(std::integral_constant<int, 16>{});
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(rows)), dim3(kBlock), 0, e->stream, k, nb, ag, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                       (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn, devPoints, rows, vals, devOut, devCount);
+}
+
+// Grid of the current state, ids, the stage (default variant), the walk.  No synchronisation: nothing is read back.
+static int aggregate_run(SphEngine* e, bool query, const SphAggregateConfig* cfg, const float4* devPoints, size_t m, const float* devValues, float* devOut,
+                         uint32_t* devCount, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = aggregate_check(*cfg, g.cellSize, query, &stencil))) return rc;
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (rows > ((size_t)-1) / (planes * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, planes, C);
+    const size_t outBytes = rows * planes * C * sizeof(float), valBytes = n * C * sizeof(float);
+    if (ranges_overlap(devOut, outBytes, devValues, valBytes) || ranges_overlap(devCount, devCount ? rows * sizeof(uint32_t) : 0, devValues, valBytes))
+        return fail(SPH_ERR_ARG, "the output overlaps the values");
+    SphAggregateInfo info{};
+    info.rows = rows; info.channels = cfg->channels; info.planes = (int32_t)planes; info.stencil = stencil; info.flags = cfg->flags; info.radius = cfg->radius;
+    *out = info;
+    if (!rows || !n) return SPH_OK;
+    const int variant = e->optAggVariant;
+    const bool byId = (variant & 1) != 0;
+    const int chunkSel = (variant >> 1) & 3, chunk = chunkSel ? 2 << chunkSel : aggregate_chunk(cfg->channels);
+    if ((rc = e->d_slotIds.grow(e, n)) || (!byId && (rc = e->d_aggStage.grow(e, n * C)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const float* vals = byId ? devValues : e->d_aggStage.p;
+    const AggK ag{cfg->op, cfg->weight, cfg->channels, byId ? 1 : 0, (!(variant & 8) && C % 4 == 0 && (uintptr_t)vals % 16 == 0) ? 1 : 0};
+    slot_ids_fill(e);
+    if (!byId) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * C)), dim3(kBlock), 0, e->stream, (const int32_t*)e->d_slotIds.p, devValues, e->d_aggStage.p, (uint32_t)n, cfg->channels);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        aggregate_launch(e, query, k, nb, ag, chunk, planes == 4, devPoints, rows, vals, devOut, devCount);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info || (e->n && (!devValues || !devOut))) return fail(SPH_ERR_ARG, "null argument");
+    return aggregate_run(e, false, cfg, nullptr, 0, devValues, devOut, devCount, info);
+}
+
+int sph_aggregate_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                        uint32_t* devCount, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info || (m && e->n && (!devPoints4 || !devValues || !devOut))) return fail(SPH_ERR_ARG, "null argument");
+    if (m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    return aggregate_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devValues, devOut, devCount, info);
+}
+
+// Host memory in and out through engine scratch: the upload, the device call, the download, one synchronisation.
+int sph_aggregate_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* values, float* out, uint32_t* count,
+                         SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = aggregate_check(*cfg, g.cellSize, query, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, cells = rows * (size_t)aggregate_planes(*cfg) * C;
+    const bool work = rows && n;
+    if (work && (!values || !out)) return fail(SPH_ERR_ARG, "null argument");
+    if (work && ((rc = e->d_aggIn.grow(e, n * C)) || (rc = e->d_aggOut.grow(e, cells)) || (rc = e->d_aggCnt.grow(e, rows)) ||
+                 (query && (rc = e->d_sampleIn.grow(e, m))))) return rc;
+    if (work) HIP_TRY(hipMemcpyAsync(e->d_aggIn.p, values, n * C * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (work && query) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = aggregate_run(e, query, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, e->d_aggIn.p, e->d_aggOut.p,
+                            count ? e->d_aggCnt.p : nullptr, info))) return rc;
+    if (work) HIP_TRY(hipMemcpyAsync(out, e->d_aggOut.p, cells * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (work && count) HIP_TRY(hipMemcpyAsync(count, e->d_aggCnt.p, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_aggregate_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                       const float* values, float* out, uint32_t* count) {
+    if (!params || !cfg || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    int rc, stencil = 0;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    SimK k;
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    if ((rc = aggregate_check(*cfg, g.cellSize, query, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (!rows || !n) return SPH_OK;
+    if (!values || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (ranges_overlap(out, rows * planes * C * sizeof(float), values, n * C * sizeof(float)) ||
+        ranges_overlap(count, count ? rows * sizeof(uint32_t) : 0, values, n * C * sizeof(float))) return fail(SPH_ERR_ARG, "the output overlaps the values");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const bool delta = !query && (cfg->flags & SPH_AGGREGATE_DELTA) != 0, moments = planes == 4;
+    const bool extremum = cfg->op == SPH_AGGREGATE_MAX || cfg->op == SPH_AGGREGATE_MIN, isMax = cfg->op == SPH_AGGREGATE_MAX;
+    const sph::HostGrid grid(k, particles, n);
+    std::vector<float> acc(planes * C);
+    std::vector<uint32_t> best(C);
+    for (size_t r = 0; r < rows; ++r) {
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+        std::fill(acc.begin(), acc.end(), 0.0f);
+        std::fill(best.begin(), best.end(), isMax ? sph::kAggLowest : sph::kAggHighest);
+        float W = 0.0f;
+        uint32_t cnt = 0u;
+        const float* mine = values + (query ? 0 : r) * C;
+        if (walk) {
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
+                    const SphParticle& cand = particles[grid.order[j]];
+                    float dx, dy, dz, r2;
+                    if (!sph::aggregate_accept(!query && j == grid.slotOf[r], self, x[0], x[1], x[2], cand.pos[0], cand.pos[1], cand.pos[2], R2, dx, dy, dz, r2)) continue;
+                    if (fluidOnly && cand.isGhost != 0) continue;
+                    const float* v = values + (size_t)grid.order[j] * C;
+                    const float w = sph::aggregate_weight(cfg->weight, R2, r2);
+                    cnt += 1u;
+                    W = W + w;
+                    for (size_t c = 0; c < C; ++c) {
+                        const float val = sph::aggregate_value(delta, v[c], mine[c]);
+                        if (extremum) {
+                            best[c] = sph::aggregate_extremum(isMax, best[c], val);
+                            continue;
+                        }
+                        acc[c] = sph::aggregate_add(acc[c], w, val);
+                        if (!moments) continue;
+                        acc[C + c] = sph::aggregate_add_moment(acc[C + c], w, dx, val);
+                        acc[2 * C + c] = sph::aggregate_add_moment(acc[2 * C + c], w, dy, val);
+                        acc[3 * C + c] = sph::aggregate_add_moment(acc[3 * C + c], w, dz, val);
+                    }
+                }
+            });
+        }
+        float* orow = out + r * planes * C;
+        for (size_t c = 0; c < C; ++c) {
+            if (extremum) { orow[c] = sph::agg_unordered(best[c]); continue; }
+            orow[c] = cfg->op == SPH_AGGREGATE_MEAN ? sph::aggregate_mean(acc[c], W) : acc[c];
+            for (size_t p = 1; p < planes; ++p) orow[p * C + c] = acc[p * C + c];
+        }
+        if (count) count[r] = cnt;
+    }
+    return SPH_OK;
+}
+
 // ---- state statistics (sph_stats.h) ------------------------------------------------------------------
 static int stats_refused(SphEngine* e) {
     if (e->slab) return fail(SPH_ERR_STATE, "statistics of a z-slab engine are not supported: the order of the fp64 sums is defined over one engine's grid");
@@ -7001,7 +7211,7 @@ int sph_state_load(SphEngine* e, const void* blob, size_t bytes) {
     // ---- from here on the engine changes ----
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->surfValid = false;                                             // query results: "no result", as after sph_reset
-    neighbors_free(e); components_free(e); knn_free(e); rays_free(e); shell_free(e); aniso_free(e);
+    neighbors_free(e); components_free(e); knn_free(e); rays_free(e); shell_free(e); aniso_free(e); aggregate_free(e);
     tracers_free(e); diffuse_free(e); scalars_free(e); gates_free(e); monitors_free(e);
     obstacles_free(e); volumes_free(e);
     for (auto& s : e->obsShape) s = 0;

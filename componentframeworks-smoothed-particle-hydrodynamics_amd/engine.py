@@ -88,6 +88,7 @@ SPH_OPT_KNN_VARIANT = 12
 SPH_OPT_RAYS_VARIANT = 13
 SPH_OPT_RAY_SPANS_VARIANT = 15
 SPH_OPT_SHELL_TIMED = 14
+SPH_OPT_AGGREGATE_VARIANT = 16
 # sph_debug_counters (SPH_OPT_DEBUG bit 3): diagnostics of k_sph_walk / k_sph_list, summed over launches:
 # [0] candidate rows walked from global memory (window too large; k_sph_walk), [1] targets on an exact fallback sweep,
 # [2] neighbour-list entries, [3] candidate rows (k_sph_walk), [4] lanes, [5] targets whose list overflowed, [6] targets that
@@ -442,6 +443,26 @@ SPH_ANISO_FLUID_ONLY = 1
 SPH_ANISO_VALID, SPH_ANISO_SPARSE, SPH_ANISO_CLAMPED = 1, 2, 4
 
 
+class SphAggregateConfig(C.Structure):
+    """struct SphAggregateConfig of include/sph_abi.h: radius, op, weight, flags, channels, zero padding (see aggregate_config())."""
+    _fields_ = [("radius", C.c_float), ("op", C.c_int32), ("weight", C.c_int32), ("flags", C.c_int32), ("channels", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+class SphAggregateInfo(C.Structure):
+    """struct SphAggregateInfo of include/sph_abi.h: what one neighbourhood reduction wrote."""
+    _fields_ = [("rows", C.c_uint64), ("channels", C.c_int32), ("planes", C.c_int32), ("stencil", C.c_int32), ("flags", C.c_int32),
+                ("radius", C.c_float), ("pad", C.c_int32)]
+
+
+assert C.sizeof(SphAggregateConfig) == 32 and C.sizeof(SphAggregateInfo) == 32
+SPH_AGGREGATE_SUM, SPH_AGGREGATE_MEAN, SPH_AGGREGATE_MAX, SPH_AGGREGATE_MIN = 0, 1, 2, 3
+SPH_AGGREGATE_WEIGHT_ONE, SPH_AGGREGATE_WEIGHT_POLY6 = 0, 1
+SPH_AGGREGATE_SELF, SPH_AGGREGATE_FLUID_ONLY, SPH_AGGREGATE_DELTA, SPH_AGGREGATE_MOMENTS = 1, 2, 4, 8
+SPH_AGGREGATE_MAX_CHANNELS = 128
+AGGREGATE_OPS = {"sum": SPH_AGGREGATE_SUM, "mean": SPH_AGGREGATE_MEAN, "max": SPH_AGGREGATE_MAX, "min": SPH_AGGREGATE_MIN}
+AGGREGATE_WEIGHTS = {"one": SPH_AGGREGATE_WEIGHT_ONE, "poly6": SPH_AGGREGATE_WEIGHT_POLY6}
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -705,6 +726,12 @@ _ABI = {
     "sph_aniso_surface": (_int, [_vp, _P(SphAnisoConfig), _pf, _pf, _pi, _f, _P(SphSurface), _P(SphAnisoInfo)]),
     "sph_aniso_host": (_int, [_vp, _sz, _pp, _P(SphAnisoConfig), _vp, _P(SphAnisoInfo)]),
     "sph_aniso_lattice_host": (_int, [_vp, _sz, _pp, _P(SphAnisoConfig), _pf, _pf, _pi, _vp, _P(SphAnisoInfo)]),
+    # fused neighbourhood reductions of caller tensors
+    "sph_aggregate_default": (None, [_P(SphAggregateConfig)]),
+    "sph_aggregate_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_staged": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -871,6 +898,20 @@ def _device_points4(points, who):
     if isinstance(points, torch.Tensor) and _is_cuda_f32(points) and points.dim() == 2 and points.shape[1] == 4:
         return points
     return torch.from_numpy(_points4(points, who, keep_w=False)).cuda()
+
+
+def _device_values(values, who):
+    """Per-particle values as an (n, C) float32 torch device tensor: a contiguous float32 device tensor of (n, C) is used in place,
+    anything else ((n,) or (n, C)) is uploaded."""
+    import torch
+    if isinstance(values, torch.Tensor) and _is_cuda_f32(values) and values.dim() == 2:
+        return values
+    return torch.from_numpy(_scalar_values(values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else values)).cuda()
+
+
+def _tensor_ptr(t):
+    """The address of a torch tensor's data, None for an empty one."""
+    return C.c_void_p(t.data_ptr()) if t.numel() else None
 
 
 def _fetch(call, device, specs, null_empty=True):
@@ -1770,6 +1811,52 @@ class SPHFluidGPU:
                                          _f3(_spacing3(ds if spacing is None else spacing)), _dims3(dd if dims is None else dims), float(iso),
                                          C.byref(surf), C.byref(info)))
         return self._download_surface(surf)
+
+    # -- fused neighbourhood reductions (include/sph_abi.h "fused neighbourhood reductions") -----------
+    def aggregate(self, values, radius=None, op="sum", weight="one", self_=False, fluid_only=False, delta=False, moments=False, counts=False,
+                  device: bool = False):
+        """Sum, mean, max or min of the caller's per-particle tensor over every particle's neighbours within `radius` (None: param_h;
+        at most three cells), fused into the grid walk: no edge list, no gather, and the same bytes on every run (DESIGN.md section
+        3u).  values: an (n, C) or (n,) numpy array, which is uploaded, or a contiguous float32 torch device tensor of (n, C), which
+        is used in place; 1 <= C <= 128.  op "sum" | "mean" | "max" | "min"; weight "one" | "poly6" ((R^2 - r^2)^3, not with max /
+        min); self_ keeps the particle itself (d = 0); fluid_only leaves the records with isGhost != 0 out and gives them empty rows;
+        delta reduces values[j] - values[i]; moments (sum only) adds the three planes sum (w d_a) v, d = x_j - x_i.  Returns float32
+        of shape (n, C), or (n, 4, C) with moments; with counts=True (out, counts uint32[n], the candidates reduced).  An empty row is
+        0 for sum and mean, -inf for max, +inf for min.  numpy arrays, or with device=True fresh torch device tensors.
+        Streams: the engine works on its own stream.  Torch's current stream is synchronised before the call, so that values written
+        there are complete, and the engine's stream is synchronised (sync()) before the results are returned, also with device=True."""
+        return self._aggregate(None, values, self._radius(radius), op, weight, self_, fluid_only, delta, moments, counts, device)
+
+    def query_aggregate(self, points, values, radius, op="sum", weight="one", fluid_only=False, moments=False, counts=False, device: bool = False):
+        """The same around (m, 3) or (m, 4) query points: row i reduces the particles within `radius` of points[i] (a torch device tensor
+        of (m, 4) float32 is used in place).  A point with a non-finite coordinate has an empty row.  Streams as aggregate()."""
+        return self._aggregate(_device_points4(points, "query_aggregate"), values, radius, op, weight, False, fluid_only, False, moments, counts, device)
+
+    def _aggregate(self, dev_points, values, radius, op, weight, self_, fluid_only, delta, moments, counts, device):
+        import torch
+        vals = _device_values(values, "aggregate")
+        n, c = int(vals.shape[0]), int(vals.shape[1])
+        if n != self.GetNumFluids():
+            raise SphError(f"aggregate: {n} rows of values for {self.GetNumFluids()} particles")
+        cfg = _aggregate_cfg(radius, op, weight, c, self_, fluid_only, delta, moments)
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        shape = (rows, 4, c) if moments else (rows, c)
+        written = rows and n                                                          # (nothing is written otherwise: sph_abi.h)
+        out = (torch.empty if written else torch.zeros)(shape, dtype=torch.float32, device="cuda")
+        cnt = (torch.empty if written else torch.zeros)(rows, dtype=torch.int32, device="cuda") if counts else None
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        p_out, p_cnt = _tensor_ptr(out), None if cnt is None else _tensor_ptr(cnt)
+        if dev_points is None:
+            _check(self._L.sph_aggregate_particles(self._h, C.byref(cfg), _tensor_ptr(vals), p_out, p_cnt, C.byref(info)))
+        else:
+            _check(self._L.sph_aggregate_query(self._h, C.byref(cfg), _tensor_ptr(dev_points), rows, _tensor_ptr(vals), p_out, p_cnt, C.byref(info)))
+        self.sync()
+        if not device:
+            out = out.cpu().numpy()
+            cnt = None if cnt is None else cnt.cpu().numpy().view(np.uint32)
+        return (out, cnt) if counts else out
 
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
@@ -2691,6 +2778,41 @@ def aniso_host(records, params, **cfg):
     info = SphAnisoInfo()
     _check(load_library().sph_aniso_host(_ptr_or_none(rec), len(rec), C.byref(params), C.byref(_aniso_cfg(**cfg)), _ptr_or_none(out), C.byref(info)))
     return out, info
+
+
+def aggregate_config(**overrides) -> SphAggregateConfig:
+    """sph_aggregate_default with the named fields replaced.  No device is needed."""
+    cfg = SphAggregateConfig()
+    load_library().sph_aggregate_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def _aggregate_cfg(radius, op, weight, channels, self_=False, fluid_only=False, delta=False, moments=False) -> SphAggregateConfig:
+    """The config of aggregate(), query_aggregate() and aggregate_host(); op and weight by name or by number."""
+    flags = (SPH_AGGREGATE_SELF if self_ else 0) | (SPH_AGGREGATE_FLUID_ONLY if fluid_only else 0) | (SPH_AGGREGATE_DELTA if delta else 0) | \
+        (SPH_AGGREGATE_MOMENTS if moments else 0)
+    try:
+        op, weight = AGGREGATE_OPS.get(op, op), AGGREGATE_WEIGHTS.get(weight, weight)
+        return aggregate_config(radius=float(radius), op=int(op), weight=int(weight), flags=flags, channels=int(channels))
+    except (TypeError, ValueError):
+        raise SphError(f"aggregate: op {op!r} (one of {sorted(AGGREGATE_OPS)}), weight {weight!r} (one of {sorted(AGGREGATE_WEIGHTS)})") from None
+
+
+def aggregate_host(records, params, values, radius, points=None, op="sum", weight="one", self_=False, fluid_only=False, delta=False, moments=False,
+                   counts=False):
+    """sph_aggregate_host: the result of SPHFluidGPU.aggregate (points None) or query_aggregate on host records and (n, C) host values,
+    computed on the CPU by the same per-candidate functions over the counting sort of neighbors_host: the same bytes.  No device is
+    needed."""
+    p4 = None if points is None else _points4(points, "aggregate_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)                    # (non-null: query rows, also for m = 0)
+    vals = _scalar_values(values, head[1])
+    c = int(vals.shape[1])
+    cfg = _aggregate_cfg(radius, op, weight, c, self_, fluid_only, delta, moments)
+    out = np.zeros((rows, 4, c) if moments else (rows, c), np.float32)
+    cnt = np.zeros(rows, np.uint32)
+    _check(load_library().sph_aggregate_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(out),
+                                             _ptr_or_none(cnt) if counts else None))
+    return (out, cnt) if counts else out
 
 
 def aniso_lattice_host(records, params, origin, spacing, dims, **cfg):

@@ -324,6 +324,40 @@ public:
         surface = out;
         return true;
     }
+    // Fused neighbourhood reductions (engine extension, sph_abi.h "fused neighbourhood reductions"): sum, mean, max
+    // or min of the caller's devValues[n][channels] over the neighbours of every particle (rows numbered by particle id) or of m query
+    // points, written to devOut[rows][planes][channels] and, where not null, devCount[rows]; all three are DEVICE memory.  cfg:
+    // sph_aggregate_default's fields with radius set (AggregateConfig: param_h).  The engine keeps nothing and does not synchronise: the
+    // results are complete after Sync().  Members are pushed first, as DispatchCompute does.  Return false on error (LastError()).
+    SphAggregateConfig AggregateConfig() const {
+        SphAggregateConfig cfg;
+        sph_aggregate_default(&cfg);
+        cfg.radius = param_h;
+        return cfg;
+    }
+    bool Aggregate(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devValues, float* devOut, uint32_t* devCount = nullptr) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_particles(engine, &cfg, devValues, devOut, devCount, &out), "sph_aggregate_particles");
+    }
+    bool QueryAggregate(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                        uint32_t* devCount = nullptr) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_query(engine, &cfg, devPoints4, m, devValues, devOut, devCount, &out), "sph_aggregate_query");
+    }
+    // The same for HOST arrays (values n * channels floats; points4 m * 4 floats or null for particle targets): out is sized to rows *
+    // planes * channels, counts (may be null) to rows.  Synchronises.
+    bool Aggregate(SphAggregateInfo& info, const SphAggregateConfig& cfg, const std::vector<float>& values, std::vector<float>& out,
+                   std::vector<uint32_t>* counts = nullptr, const float* points4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t rows = points4 ? m : sph_num_particles(engine), planes = (cfg.flags & SPH_AGGREGATE_MOMENTS) ? 4 : 1;
+        if (cfg.channels < 1 || values.size() != sph_num_particles(engine) * size_t(cfg.channels)) return !Check(SPH_ERR_ARG, "Aggregate: values.size() is not n * channels");
+        out.assign(rows * planes * size_t(cfg.channels), 0.0f);
+        if (counts) counts->assign(rows, 0u);
+        return !Check(sph_aggregate_staged(engine, &cfg, points4, m, values.data(), out.data(), counts ? counts->data() : nullptr, &info), "sph_aggregate_staged");
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

@@ -61,6 +61,7 @@ extern "C" {
 /* (still 4, additions only: SphAniso, SphAnisoConfig, SphAnisoInfo, SPH_ANISO_FLUID_ONLY, SPH_ANISO_VALID / _SPARSE / _CLAMPED, sph_aniso_default / _build / _info / _device / _download / _lattice / _surface / _host / _lattice_host -- anisotropic kernels) */
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (still 4, additions only: SphStateInfo, SphStateDigest, SPH_STATE_*, sph_state_size / _save / _load / _peek / _digest / _checksum_host -- checkpoints) */
+/* (still 4, additions only: SphAggregateConfig, SphAggregateInfo, SPH_AGGREGATE_*, sph_aggregate_default / _particles / _query / _staged / _host, SPH_OPT_AGGREGATE_VARIANT -- fused neighbourhood reductions of caller tensors) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -171,6 +172,7 @@ enum {
     SPH_OPT_RAYS_VARIANT = 13,   /* ray casts (sph_rays_*), an A/B for measurements: 0 = the rays are cast in the caller's order (default), 1 = in the order of the grid cell they enter first (a counting sort of the rays in front of the walk: faster for incoherent rays, slower for sheets and fans); the same bits */
     SPH_OPT_SHELL_TIMED = 14,    /* free-surface particles (sph_shell_*), measurements only: which launches of a build the SPH_OPT_TIMING bracket covers -- 0 = all of them (default), 1 = pass 1 (ids and the gather), 2 = pass 2 (the crest kernel), 3 = the two scans and compactions; the launches themselves are the same */
     SPH_OPT_RAY_SPANS_VARIANT = 15, /* ray spans (sph_rays_span*), an A/B for measurements: 0 = the layer walk (default: after the first cell only the new 3 x 3 layer of the block is tested), 1 = the block walk (every step tests the whole block and drops what the previous cell's block held); the same bits.  SPH_OPT_RAYS_VARIANT orders the rays of spans as it does those of casts */
+    SPH_OPT_AGGREGATE_VARIANT = 16, /* neighbourhood reductions (sph_aggregate_*), A/Bs for measurements: bit 0 = the payload is gathered by particle id straight from the caller's array (no staging into slot order); bits 1-2 = the channels per pass of the walk: 0 the default (the smallest of 4, 8, 16 that holds the channels), 1 = 4, 2 = 8, 3 = 16; bit 3 = 4-byte payload loads also where 16-byte loads apply; default 0; the same bits */
     SPH_OPT_GRAPH_LAUNCHES = 6,  /* read-only: number of graph replays so far */
     SPH_OPT_TIMING = 4,          /* hipEvents around kernels for sph_kernel_times(): 1 = every kernel, 2 = only the SPH pass */
     /* test / tuning hooks */
@@ -1366,6 +1368,57 @@ int sph_aniso_host(const SphParticle* particles, size_t n, const SphParams* para
 /* The twin of sph_aniso_lattice: values (dims[0] * dims[1] * dims[2] floats, x fastest) in host memory. */
 int sph_aniso_lattice_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAnisoConfig* cfg, const float origin[3],
                            const float spacing[3], const int dims[3], float* values, SphAnisoInfo* out);
+
+/* ---- fused neighbourhood reductions of caller tensors (no reference counterpart) -------------------------------
+ * Sum, mean, maximum or minimum of a caller's per-particle tensor values[n][C] (float32, row-major by particle id, device memory, never
+ * written) over the neighbours of every particle (rows numbered by particle id) or of m query points (x, y, z, .).  A query: it keeps
+ * no result and no engine state.  Grid, radius rules (0 < R <= 3 cells), stencil and candidate order (ascending sorted slot = ascending
+ * (cell index, particle id)) are those of the neighbour lists above; candidate j is accepted when r2 < R2 with d = x_j - x_i,
+ * r2 = dot3(d, d) (the bits of the lists' r2).  1 <= channels <= SPH_AGGREGATE_MAX_CHANNELS.
+ * Flags.  SELF (particle targets): the own slot is kept by slot identity and enters with d = 0, r2 = 0 exactly; without it the own slot
+ * is skipped.  FLUID_ONLY: records with isGhost != 0 are never candidates and a ghost target has an empty row.  DELTA (particle targets):
+ * the reduced value is values[j][c] - values[i][c], one rounded subtraction.  MOMENTS (SUM only): see below.  A query point with a
+ * non-finite coordinate has an empty row; a particle with a non-finite position accepts nobody and is accepted by nobody, so its row
+ * is empty apart from its own slot under SELF.
+ * Weights.  ONE: w = 1.  POLY6: t = R2 - r2, w = (t * t) * t, unnormalised.
+ * Operations, per channel one fp32 accumulator over the accepted candidates in the order above, every product and sum rounded on its
+ * own (no fused multiply-add anywhere): SUM acc = acc + w * v.  MEAN the same and W = W + w; the result is acc / W (IEEE division), +0
+ * where W == 0.  MAX / MIN (weight ONE): compared through the ordered-bits key of the fp32 value (the key of the rays' t), so -0 < +0
+ * and the result does not depend on the order; a NaN never wins; an empty row is -inf for MAX and +inf for MIN.  MOMENTS: the output row
+ * is [4][C]; plane 0 is the SUM, planes 1 .. 3 are acc_a = acc_a + (w * d_a) * v for a = x, y, z (with DELTA the raw sums an SPH
+ * gradient, divergence or curl of the caller's field is assembled from).  NaN and inf values propagate through SUM and MEAN in the rows
+ * that accept them, and in no other row.
+ * Outputs, device memory: out float32[rows][planes][C] (planes 1, or 4 with MOMENTS); count (may be null) uint32[rows], the candidates
+ * reduced: for particle targets the degree sph_neighbors_build(SPH_NEIGHBORS_COUNT_ONLY) gives at the same radius and SELF setting,
+ * under FLUID_ONLY the non-ghost ones of them.  The same bytes on every run, and the bytes of sph_aggregate_host.
+ * The device calls work on the engine's stream and do NOT synchronise: out and count are complete once the stream has drained
+ * (sph_sync), and values must stay unchanged until then; a caller that fills values on another stream synchronises that stream first.
+ * A later dispatch is unaffected, a call never changes the simulation.  Timed as SPH_K_OTHER.
+ * SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1 (as sampling), before any allocation.  SPH_ERR_ARG: a null argument, a radius
+ * that is not finite, <= 0 or above three cells, an unknown op, weight or flag bit, non-zero padding, channels outside 1 .. 128, MOMENTS
+ * without SUM, MAX / MIN with POLY6, SELF or DELTA on query targets, more than 2^31 - 1 query points, out or count overlapping values
+ * as address ranges, rows * planes * channels beyond size_t.  m = 0 or n = 0: success, nothing is written. */
+enum { SPH_AGGREGATE_SUM = 0, SPH_AGGREGATE_MEAN = 1, SPH_AGGREGATE_MAX = 2, SPH_AGGREGATE_MIN = 3 };                  /* SphAggregateConfig.op */
+enum { SPH_AGGREGATE_WEIGHT_ONE = 0, SPH_AGGREGATE_WEIGHT_POLY6 = 1 };                                                 /* SphAggregateConfig.weight */
+enum { SPH_AGGREGATE_SELF = 1, SPH_AGGREGATE_FLUID_ONLY = 2, SPH_AGGREGATE_DELTA = 4, SPH_AGGREGATE_MOMENTS = 8 };     /* SphAggregateConfig.flags */
+enum { SPH_AGGREGATE_MAX_CHANNELS = 128 };
+typedef struct SphAggregateConfig { float radius; int32_t op, weight, flags, channels; int32_t pad[3]; } SphAggregateConfig;   /* 32 bytes */
+typedef struct SphAggregateInfo { uint64_t rows; int32_t channels, planes, stencil, flags; float radius; int32_t pad; } SphAggregateInfo;   /* 32 bytes */
+/* radius 0 (to be set: there is no default radius), op SUM, weight ONE, flags 0, channels 1, padding 0. */
+void sph_aggregate_default(SphAggregateConfig* cfg);
+/* Rows of every particle: devValues float32[n][channels], devOut float32[n][planes][channels], devCount uint32[n] or null. */
+int sph_aggregate_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, SphAggregateInfo* info);
+/* Rows of m query points (x, y, z, .) in device memory: devOut float32[m][planes][channels], devCount uint32[m] or null. */
+int sph_aggregate_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                        uint32_t* devCount, SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets; count may be null): values, and the points, are uploaded
+ * into engine scratch, out and count are copied back; synchronises. */
+int sph_aggregate_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* values, float* out, uint32_t* count,
+                         SphAggregateInfo* info);
+/* Host-only, no device: the counting sort of sph_neighbors_host and the same per-candidate functions in the same order; the same bytes.
+ * points4 null: particle targets.  count may be null. */
+int sph_aggregate_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                       const float* values, float* out, uint32_t* count);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
