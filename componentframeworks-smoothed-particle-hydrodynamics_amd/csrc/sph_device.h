@@ -79,18 +79,28 @@ __device__ __forceinline__ int cell_z_local(const SimK& k, float pz) {
 __host__ __device__ __forceinline__ int3 cell_of(const SimK& k, float x, float y, float z) {
     return make_int3(cell_axis(x, k.gminx, k.cellSize, k.gx), cell_axis(y, k.gminy, k.cellSize, k.gy), cell_axis(z, k.gminz, k.cellSize, k.gz));
 }
-// z-slab engines.  Round 4: the exchange FOLLOWS a particle across up to kSlabJump cell layers in z per substep (halo copies are one layer
+// z-slab engines.  The exchange FOLLOWS a particle across up to kSlabJump cell layers in z per substep (halo copies are one layer
 // deep and migrants go to the adjacent rank -- which a jump of up to kSlabJump layers still reaches while every slab is thicker than
 // that -- and while the container stays put the pack looks only at the slots of the kSlabDepth = kSlabJump + 2 lowest / highest local layers:
 // whatever ends in a face layer or beyond it began the substep there).  SPHFluid.comp integrates the position with the UNCAPPED velocity (v + a dt) and
 // OBBConstraints.comp projects, so a violent substep can do more.  Where that makes the decomposed run differ from the single-domain
-// run it is REPORTED (error bit 16 of the exchange's flags), not followed:
+// run it is REPORTED (kSlabFlagLayerJump in the exchange's flags), not followed:
 //   * here, for the pack's reduced scan: a particle that began the substep OUTSIDE the slot ranges the next pack reads and ends in a
 //     layer that pack would have acted on (a face layer: halo copy; beyond it: migrant);
 //   * in k_slab_unpack*, for migrants that land on a rank that cannot place them (slab_record_misplaced).
 // k.slabFlags is set only for substeps whose following pack may use the reduced scan.
 constexpr int kSlabJump = 3;                  // cell layers in z a substep may carry a particle across and still be followed exactly
 constexpr int kSlabDepth = kSlabJump + 2;     // local layers (ghost layer included) at each end of a slab that the pack and the face launches cover
+// The exchange's sticky flags (counter word kSlabCntFlags of sph_slab.h), SPH_SLAB_FLAG_* of sph_abi.h.  They live in this base layer because the
+// SPH pass sets one of them (below); every other one is set by the k_slab_* kernels.  All but LayerJump mean that records were lost.
+enum : uint32_t {
+    kSlabFlagSendOverflow = 1u,    // k_slab_headers2: a send face held more records than its capacity
+    kSlabFlagSlotOverflow = 2u,    // k_slab_unpack2: the slab's slot capacity overflowed while appending received records
+    kSlabFlagBadHeader = 4u,       // k_slab_commit2: a received face did not start with a valid header
+    kSlabFlagTruncated = 8u,       // k_slab_commit2: the sender had more records than its message carried
+    kSlabFlagLayerJump = 16u,      // a notice: a particle crossed more cell layers within one substep than the exchange follows (here, slab_record_misplaced)
+    kSlabFlagSizeMismatch = 32u    // k_slab_commit2: the header names other message sizes than this end received (the receiver's come out of its own plan)
+};
 __device__ __forceinline__ void slab_check_layer_move(const SimK& k, int czEntryLocal, float pzNew) {
     if (!k.slabFlags) return;                                      // (kernel-uniform)
     if (czEntryLocal < kSlabDepth || czEntryLocal > k.gz - kSlabDepth - 1) return;       // the pack reads this slot anyway
@@ -98,7 +108,7 @@ __device__ __forceinline__ void slab_check_layer_move(const SimK& k, int czEntry
     const float zLo = fmaf((float)(k.zoff + 2) + 0.5f, k.cellSize, k.gminz), zHi = fmaf((float)(k.zoff + k.gz - 2) - 0.5f, k.cellSize, k.gminz);
     if (pzNew > zLo && pzNew < zHi) return;
     const int czNew = cell_z_global(k, pzNew) - k.zoff;
-    if (czNew <= 1 || czNew >= k.gz - 2) atomicOr(k.slabFlags, 16u);
+    if (czNew <= 1 || czNew >= k.gz - 2) atomicOr(k.slabFlags, kSlabFlagLayerJump);
 }
 
 // ======================= SPHFluid.comp main(), per-particle / per-pair arithmetic =======================

@@ -202,6 +202,16 @@ struct MonitorSlot {
 static std::set<SphEngine*> g_engines;      // live engines of this process (sph_destroy clears what neighbours hold of a destroyed one)
 static std::mutex g_enginesMutex;           // (a host may drive its engines from one thread each)
 
+// One exchange's true record counts as both ends of its links know them: what this engine packed (its Last* counter words) and what the
+// headers it received named (nHaloTrue / nMigTrue of the face from direction d).  slab_note_counts writes, slab_plan reads.
+struct SlabSeen { sph::SlabMsg sent, received; };
+// The plans of one handshake: this engine's, and the ones received from the lower / upper neighbour.
+struct SlabPlans { SphSlabIntent mine, from[2]; };
+static_assert(sizeof(SphSlabIntent) == 64 && sizeof(SlabPlans) == 192, "a plan is a fixed 64-byte message");
+static_assert(SPH_SLAB_FLAG_SEND_OVERFLOW == sph::kSlabFlagSendOverflow && SPH_SLAB_FLAG_SLOT_OVERFLOW == sph::kSlabFlagSlotOverflow && SPH_SLAB_FLAG_BAD_HEADER == sph::kSlabFlagBadHeader &&
+              SPH_SLAB_FLAG_TRUNCATED == sph::kSlabFlagTruncated && SPH_SLAB_FLAG_LAYER_JUMP == sph::kSlabFlagLayerJump && SPH_SLAB_FLAG_SIZE_MISMATCH == sph::kSlabFlagSizeMismatch, "sph_device.h mirrors SPH_SLAB_FLAG_*");
+static_assert(sizeof(sph::SlabRec) == SPH_SLAB_REC_BYTES && sizeof(sph::HaloRec) == SPH_SLAB_HALO_BYTES && sizeof(sph::SlabOut) == SPH_SLAB_OUT_BYTES, "the wire records of sph_slab.h have the sizes sph_abi.h names");
+
 struct SphEngine {
     hipStream_t stream = nullptr;
     bool ownStream = false;
@@ -251,18 +261,18 @@ struct SphEngine {
     int z0 = 0, z1 = 0, hasLo = 0, hasHi = 0;
     size_t nSlots = 0;                      // state slots in use (live + dead), upper bound of the live count (= cap once the async exchange is used)
     char* d_face[4] = {nullptr, nullptr, nullptr, nullptr};   // engine-owned halo buffers: send lo / hi, recv lo / hi (sph::slab_face_bytes(faceCap): header, migrants, halo copies)
-    // message sizing (round 4): the two messages per direction carry the records in use, sized from the counts of TWO exchanges ago
+    // message sizing: the two messages per direction carry the records in use, sized from the counts of TWO exchanges ago
     // (read back asynchronously into pinned memory; both ends of a link see the same numbers: the sender its own count, the receiver the
     // header it got), the face capacity until those exist
-    uint32_t* h_cnt = nullptr;              // pinned, 4 slots x 8 words: own halo lo / hi, own migrants lo / hi, received (halo, migrants) from lo, from hi
+    SlabSeen* h_seen = nullptr;             // pinned ring of 4 exchanges: the true counts this engine packed and the ones its neighbours' headers named
     hipEvent_t evCnt[4] = {nullptr, nullptr, nullptr, nullptr};
     bool cntValid[4] = {false, false, false, false};
     uint32_t exchangeNo = 0;                // sized exchanges enqueued so far
-    uint32_t msgSend[4] = {0, 0, 0, 0}, msgRecv[4] = {0, 0, 0, 0};   // records of the exchange being enqueued: halo lo / hi, migrants lo / hi
+    sph::SlabMsg msgSend{}, msgRecv{};      // records the messages of the exchange being enqueued carry
     uint64_t sentBytes[2] = {0, 0};         // bytes of the last exchange's messages to lo / hi
     int calmHold = 0;                       // exchanges that still send whole faces because something just changed under the fluid (impulse, container, re-prime)
     uint32_t stepNo = 0;                    // boundary-first steps begun
-    // round 5: the PLAN of an exchange and its agreement with the neighbours' plans (slab_plan, slab_intent_mismatch, slab_handshake_rccl)
+    // the PLAN of an exchange and its agreement with the neighbours' plans (slab_plan, slab_intent_mismatch, slab_handshake_rccl)
     SphSlabIntent intent{};                 // what this engine is about to do in exchange intent.exchangeNo: compared with the neighbours' plans before a sized message is posted
     bool intentValid = false;
     uint32_t holdEvents = 0;                // things that set calmHold so far (impulses, container / grid edits, priming exchanges): every rank must have seen the same ones
@@ -272,7 +282,7 @@ struct SphEngine {
     int tightMessages = 0;                  // test hook (sph_slab_debug_tight_messages): the count of two exchanges ago, no margin, no calm rule
     hipStream_t hstream = nullptr;          // the handshake's stream
     hipEvent_t evIntent = nullptr;
-    uint32_t *d_intent = nullptr, *h_intent = nullptr;   // device / pinned host, 48 words: [0..15] this engine's plan, [16..31] the lower neighbour's, [32..47] the upper neighbour's
+    SlabPlans *d_intent = nullptr, *h_intent = nullptr;   // device / pinned host: the plans of one handshake
     float handshakeMs = 0.0f;               // host time the last handshake waited for its neighbours
     uint64_t handshakes = 0;
     bool stepPaused = false;                // the pending step is a paused one (nothing was enqueued)
@@ -300,7 +310,7 @@ struct SphEngine {
     bool stepPending = false;               // sph_slab_step_begin ran, its finish has not yet
     bool slabOrderValid = false;            // slots are in the order of the last counting sort and no particle can have moved by more than a layer since
     float lastContainer[15] = {0};          // container / grid members of the last dispatch (a change may move particles by many cells, or the grid under them)
-    uint32_t* d_slabCnt = nullptr;          // [0] lo records, [1] hi records, [2] live count, [3] download count, [4] flags, [5] / [6] counts of the last async pack
+    uint32_t* d_slabCnt = nullptr;          // sph::kSlabCounters words, named by sph::SlabCounter (sph_slab.h)
     int debugFlags = 0;
     unsigned long long* d_stats = nullptr;   // k_sph_walk / k_sph_list diagnostics (SPH_OPT_DEBUG bit 3), see sph_debug_counters
     // sph_sample_points (host arrays): device copies of the probes and of the results
@@ -768,8 +778,8 @@ int alloc_particle_buffers(SphEngine* e, size_t n) {
     if ((rc = dev_alloc(&e->d_binKey, n))) return rc;
     if ((rc = dev_alloc(&e->d_order, n))) return rc;
     if ((rc = dev_alloc(&e->d_tmp, n))) return rc;
-    if ((rc = dev_alloc(&e->d_slabCnt, 16))) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_slabCnt, 0, 16 * sizeof(uint32_t), e->stream));
+    if ((rc = dev_alloc(&e->d_slabCnt, kSlabCounters))) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_slabCnt, 0, kSlabCounters * sizeof(uint32_t), e->stream));
     e->cap = n;
     return SPH_OK;
 }
@@ -860,7 +870,7 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
     if (n) {
         Timed t(e, SPH_K_BIN);
         hipLaunchKernelGGL(k_bin, dim3(nb), dim3(kBlock), 0, e->stream, k, e->d_pos[e->cur], e->d_binKey, e->d_cellCount, n,
-                           e->slab ? e->d_slabCnt + 2 : (const uint32_t*)nullptr);
+                           e->slab ? e->d_slabCnt + kSlabCntLive : (const uint32_t*)nullptr);
     }
     {
         Timed t(e, SPH_K_SCAN);
@@ -869,7 +879,7 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
     if (n) {
         Timed t(e, SPH_K_SCATTER);
         hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(kBlock), 0, e->stream, e->d_binKey, e->d_cellStart, e->d_tmp, n,
-                           e->slab ? e->d_slabCnt + 2 : (const uint32_t*)nullptr);
+                           e->slab ? e->d_slabCnt + kSlabCntLive : (const uint32_t*)nullptr);
         if (sortedCopy && orderAll) {
             hipLaunchKernelGGL((k_rank<true, true>), dim3(nb), dim3(kBlock), 0, e->stream, e->d_tmp, e->d_cellStart, e->d_order, n, C,
                                e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur], e->d_foam[e->cur], e->d_sPV, e->d_sOwn, k.gx, k.gy,
@@ -877,11 +887,11 @@ int build_grid(SphEngine* e, const SimK& k, bool commitLive = false, bool orderA
         } else if (sortedCopy) {
             hipLaunchKernelGGL((k_rank<true>), dim3(nb), dim3(kBlock), 0, e->stream, e->d_tmp, e->d_cellStart, e->d_order, n, C,
                                e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur], e->d_foam[e->cur], e->d_sPV, e->d_sOwn, k.gx, k.gy,
-                               (commitLive && e->slab) ? e->d_slabCnt + 2 : (uint32_t*)nullptr);
+                               (commitLive && e->slab) ? e->d_slabCnt + kSlabCntLive : (uint32_t*)nullptr);
         } else {
             hipLaunchKernelGGL((k_rank<false>), dim3(nb), dim3(kBlock), 0, e->stream, e->d_tmp, e->d_cellStart, e->d_order, n, C,
                                nullptr, e->d_vel[e->cur], nullptr, nullptr, nullptr, nullptr, k.gx, k.gy,
-                               (commitLive && e->slab) ? e->d_slabCnt + 2 : (uint32_t*)nullptr);
+                               (commitLive && e->slab) ? e->d_slabCnt + kSlabCntLive : (uint32_t*)nullptr);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1356,7 +1366,7 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
         k.gz = e->z1 - e->z0 + 2; k.numCells = k.gx * k.gy * k.gz; k.zoff = e->z0 - 1;
         // the pack that follows this substep may restrict itself to the ends of the slot range (same container as the substep
         // before, sorted slots): a particle that this substep carries from the middle into a face layer is then reported
-        if (e->optGridBuild != 1 && sameContainer) k.slabFlags = e->d_slabCnt + 4;
+        if (e->optGridBuild != 1 && sameContainer) k.slabFlags = e->d_slabCnt + kSlabCntFlags;
     }
     if ((rc = import_state(e))) return rc;
     const int n = (int)(e->slab ? e->nSlots : e->n);
@@ -1489,9 +1499,9 @@ int dispatch_one(SphEngine* e, float overrideDt, bool boundaryFirst = false) {
     e->cur = nx;
     e->accValid = !fuseAos;
     e->aosValid = fuseAos;
-    if (e->slab) {   // the sorted output holds exactly the live particles: their count is on the device (slabCnt[2])
+    if (e->slab) {   // the sorted output holds exactly the live particles: their count is on the device (kSlabCntLive)
         const bool sorted = e->optGridBuild != 1 && n > 0;
-        if (!sorted) HIP_TRY(hipMemcpyAsync(e->d_slabCnt + 2, e->d_cellStart + k.numCells, sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));   // (k_rank stored it otherwise)
+        if (!sorted) HIP_TRY(hipMemcpyAsync(e->d_slabCnt + kSlabCntLive, e->d_cellStart + k.numCells, sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));   // (k_rank stored it otherwise)
         // the next k_slab_pack may restrict itself to the ends of the slot range if this substep cannot have moved a
         // particle by more than one layer: a container that did not change under the fluid (and the SPH pass reports the particle that
         // jumps from the middle into a face layer all the same, slab_check_layer_move)
@@ -1518,15 +1528,22 @@ SlabGeom slab_geom(SphEngine* e) {
     return g;
 }
 
-// Device-side error flags of the exchange (slabCnt[4]) as a status: every entry point that synchronises anyway reports them.
+// The preamble of the sph_slab_* entry points: an engine, a slab engine, and where the call moves faces one that has them.
+int slab_engine(const SphEngine* e, bool needFaces = false) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (needFaces) return e->slab && e->d_face[0] ? SPH_OK : fail(SPH_ERR_STATE, "slab engine with face buffers required");
+    return e->slab ? SPH_OK : fail(SPH_ERR_STATE, "not a slab engine");
+}
+
+// Device-side error flags of the exchange (kSlabCntFlags) as a status: every entry point that synchronises anyway reports them.
 int slab_flags_error(const SphEngine* e, uint32_t flags, uint32_t nLo, uint32_t nHi) {
-    if (flags & 1u) return fail(SPH_ERR_CAPACITY, "halo send buffer overflowed (%u / %u records for a capacity of %u)", nLo, nHi, e->faceCap);
-    if (flags & 2u) return fail(SPH_ERR_CAPACITY, "slab capacity %zu exceeded while appending halo records", e->cap);
-    if (flags & 4u) return fail(SPH_ERR_HIP, "a received halo message did not start with a valid header (magic / count): failed or garbled receive");
-    if (flags & 8u) return fail(SPH_ERR_CAPACITY, "a neighbour rank had more halo records than its message could carry (face capacity %u)", e->faceCap);
-    if (flags & 32u) return fail(SPH_ERR_STATE, "the two ends of a link sized an exchange's messages differently (a received header names other message sizes than this engine received): "
+    if (flags & SPH_SLAB_FLAG_SEND_OVERFLOW) return fail(SPH_ERR_CAPACITY, "halo send buffer overflowed (%u / %u records for a capacity of %u)", nLo, nHi, e->faceCap);
+    if (flags & SPH_SLAB_FLAG_SLOT_OVERFLOW) return fail(SPH_ERR_CAPACITY, "slab capacity %zu exceeded while appending halo records", e->cap);
+    if (flags & SPH_SLAB_FLAG_BAD_HEADER) return fail(SPH_ERR_HIP, "a received halo message did not start with a valid header (magic / count): failed or garbled receive");
+    if (flags & SPH_SLAB_FLAG_TRUNCATED) return fail(SPH_ERR_CAPACITY, "a neighbour rank had more halo records than its message could carry (face capacity %u)", e->faceCap);
+    if (flags & SPH_SLAB_FLAG_SIZE_MISMATCH) return fail(SPH_ERR_STATE, "the two ends of a link sized an exchange's messages differently (a received header names other message sizes than this engine received): "
                                                 "the ranks' call sequences differ");
-    // (flag 16 -- a particle crossed more cell layers in z within one substep than the exchange follows -- loses nothing: it is a notice
+    // (SPH_SLAB_FLAG_LAYER_JUMP -- a particle crossed more cell layers in z within one substep than the exchange follows -- loses nothing: it is a notice
     //  that the decomposed run no longer equals the single-domain run, carried by sph_slab_status's out[4], cleared by sph_slab_clear_flags)
     return SPH_OK;
 }
@@ -1675,7 +1692,7 @@ int sph_destroy(SphEngine* e) {
     for (hipEvent_t ev : {e->evBoundary, e->evPacked, e->evDone, e->evSorted, e->evInterior, e->evPassEnd}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evX) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evCnt) if (ev) (void)hipEventDestroy(ev);
-    if (e->h_cnt) (void)hipHostFree(e->h_cnt);
+    if (e->h_seen) (void)hipHostFree(e->h_seen);
     if (e->hstream) { (void)hipStreamSynchronize(e->hstream); (void)hipStreamDestroy(e->hstream); }
     if (e->evIntent) (void)hipEventDestroy(e->evIntent);
     if (e->h_intent) (void)hipHostFree(e->h_intent);
@@ -2228,7 +2245,8 @@ int sph_create_slab(SphEngine** out, const SphParticle* particles, const uint32_
         if (er != hipSuccess) return cleanup(fail(SPH_ERR_HIP, "upload failed: %s", hipGetErrorString(er)));
         hipLaunchKernelGGL(k_slab_import, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, e->d_aos, d_ids, e->d_pos[0], e->d_vel[0], e->d_rp[0], e->d_foam[0], (int)n);
     }
-    const uint32_t init[16] = {0u, 0u, (uint32_t)n, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t init[kSlabCounters] = {0u};
+    init[kSlabCntLive] = (uint32_t)n;
     hipError_t er = hipMemcpyAsync(e->d_slabCnt, init, sizeof(init), hipMemcpyHostToDevice, e->stream);
     if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
     if (er != hipSuccess) return cleanup(fail(SPH_ERR_HIP, "slab init failed: %s", hipGetErrorString(er)));
@@ -2240,15 +2258,15 @@ int sph_create_slab(SphEngine** out, const SphParticle* particles, const uint32_
 
 int sph_slab_pack(SphEngine* e, void* sendLo, void* sendHi, uint32_t capLo, uint32_t capHi, uint32_t countsOut[2]) {
     if (!e || !countsOut) return fail(SPH_ERR_ARG, "null argument");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+    if (int rc = slab_engine(e)) return rc;
     if ((e->hasLo && !sendLo) || (e->hasHi && !sendHi)) return fail(SPH_ERR_ARG, "missing send buffer");
     sph::compute_grid_extents(e->params, e->grid);
     SimK k;
     make_simk(e->params, e->grid, e->params.param_timeStep, k);
-    HIP_TRY(hipMemsetAsync(e->d_slabCnt, 0, 2 * sizeof(uint32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_slabCnt + 5, 0, 2 * sizeof(uint32_t), e->stream));      // counts of an earlier async pack
-    uint32_t host[3] = {0, 0, 0};
-    // e->nSlots bounds the slots in use; the device-side live count (slabCnt[2]) trims it to the
+    HIP_TRY(hipMemsetAsync(e->d_slabCnt + kSlabCntRecLo, 0, 2 * sizeof(uint32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_slabCnt + kSlabCntPackedLo, 0, 2 * sizeof(uint32_t), e->stream));      // counts of an earlier async pack
+    uint32_t host[kSlabCntLive + 1] = {0, 0, 0};              // RecLo, RecHi, Live
+    // e->nSlots bounds the slots in use; the device-side live count (kSlabCntLive) trims it to the
     // slots that hold data, so no host round trip is needed before the launch
     if (e->nSlots) {
         Timed t(e, SPH_K_OTHER);
@@ -2258,22 +2276,22 @@ int sph_slab_pack(SphEngine* e, void* sendLo, void* sendHi, uint32_t capLo, uint
                            slab_ranges_usable(e) ? e->d_cellStart : (const uint32_t*)nullptr, k.gx * k.gy);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, e->d_slabCnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(host, e->d_slabCnt, sizeof(host), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->nSlots = std::min<size_t>(e->nSlots, host[2]);
-    // sph_slab_pack_async / sph_slab_exchange expect zeros in [0..1]; the counts of this pack stay visible to sph_slab_status in [5..6]
-    HIP_TRY(hipMemsetAsync(e->d_slabCnt, 0, 2 * sizeof(uint32_t), e->stream));
-    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + 5, host[0]);
-    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + 6, host[1]);
+    e->nSlots = std::min<size_t>(e->nSlots, host[kSlabCntLive]);
+    const uint32_t nLo = host[kSlabCntRecLo], nHi = host[kSlabCntRecHi];
+    // sph_slab_status adds Rec* and Packed*: the counts of this pack stay visible to it in Packed*, Rec* go back to zero
+    HIP_TRY(hipMemsetAsync(e->d_slabCnt + kSlabCntRecLo, 0, 2 * sizeof(uint32_t), e->stream));
+    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + kSlabCntPackedLo, nLo);
+    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + kSlabCntPackedHi, nHi);
     HIP_TRY(hipGetLastError());
-    if (host[0] > capLo || host[1] > capHi) return fail(SPH_ERR_CAPACITY, "halo send buffer too small (%u/%u lo, %u/%u hi)", host[0], capLo, host[1], capHi);
-    countsOut[0] = host[0]; countsOut[1] = host[1];
+    if (nLo > capLo || nHi > capHi) return fail(SPH_ERR_CAPACITY, "halo send buffer too small (%u/%u lo, %u/%u hi)", nLo, capLo, nHi, capHi);
+    countsOut[0] = nLo; countsOut[1] = nHi;
     return SPH_OK;
 }
 
 int sph_slab_unpack(SphEngine* e, const void* recvLo, uint32_t nLo, const void* recvHi, uint32_t nHi) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+    if (int rc = slab_engine(e)) return rc;
     if ((nLo && !recvLo) || (nHi && !recvHi)) return fail(SPH_ERR_ARG, "missing receive buffer");
     if (e->nSlots + nLo + nHi > e->cap) return fail(SPH_ERR_CAPACITY, "slab capacity %zu < %zu slots", e->cap, e->nSlots + nLo + nHi);
     const int c = e->cur;
@@ -2286,32 +2304,31 @@ int sph_slab_unpack(SphEngine* e, const void* recvLo, uint32_t nLo, const void* 
     e->nSlots += nHi;
     HIP_TRY(hipGetLastError());
     // until the next dispatch sorts again, every slot may hold data
-    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + 2, (uint32_t)e->nSlots);
+    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_slabCnt + kSlabCntLive, (uint32_t)e->nSlots);
     HIP_TRY(hipGetLastError());
     return SPH_OK;
 }
 
 int sph_slab_download(SphEngine* e, void* hostOut, size_t capRecords, size_t* nOut) {
     if (!e || !nOut || (!hostOut && capRecords)) return fail(SPH_ERR_ARG, "null argument");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
-    uint32_t cnts[8] = {0};
+    int rc;
+    if ((rc = slab_engine(e))) return rc;
+    uint32_t cnts[kSlabCntPackedHi + 1] = {0};
     HIP_TRY(hipMemcpyAsync(cnts, e->d_slabCnt, sizeof(cnts), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->xstream) HIP_TRY(hipStreamSynchronize(e->xstream));
-    // a face or slot overflow dropped records: the owned set would come back short without a word.  (Flag 16 -- a particle crossed
+    // a face or slot overflow dropped records: the owned set would come back short without a word.  (SPH_SLAB_FLAG_LAYER_JUMP -- a particle crossed
     // more layers than the exchange follows -- drops nothing: the records are delivered, sph_slab_status carries the notice.)
-    int frc = slab_flags_error(e, cnts[4], cnts[5], cnts[6]);
-    if (frc) return frc;
-    const size_t n = cnts[2];
+    if ((rc = slab_flags_error(e, cnts[kSlabCntFlags], cnts[kSlabCntPackedLo], cnts[kSlabCntPackedHi]))) return rc;
+    const size_t n = cnts[kSlabCntLive];
     SlabOut* d_out = nullptr;
-    int rc;
     if ((rc = dev_alloc(&d_out, n ? n : 1))) return rc;
-    hipError_t er = hipMemsetAsync(e->d_slabCnt + 3, 0, sizeof(uint32_t), e->stream);
+    hipError_t er = hipMemsetAsync(e->d_slabCnt + kSlabCntDownload, 0, sizeof(uint32_t), e->stream);
     if (er == hipSuccess && n)
         hipLaunchKernelGGL(k_slab_download, dim3(blocks_for(n)), dim3(kBlock), 0, e->stream, e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur],
-                           e->d_foam[e->cur], e->d_acc, (int)n, e->accValid ? 1 : 0, d_out, (uint32_t)n, e->d_slabCnt + 3);
+                           e->d_foam[e->cur], e->d_acc, (int)n, e->accValid ? 1 : 0, d_out, (uint32_t)n, e->d_slabCnt + kSlabCntDownload);
     uint32_t cnt = 0;
-    if (er == hipSuccess) er = hipMemcpyAsync(&cnt, e->d_slabCnt + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(&cnt, e->d_slabCnt + kSlabCntDownload, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
     if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
     if (er == hipSuccess && cnt > capRecords) { (void)hipFree(d_out); return fail(SPH_ERR_CAPACITY, "%u owned records > capacity %zu", cnt, capRecords); }
     if (er == hipSuccess && cnt) er = hipMemcpy(hostOut, d_out, (size_t)cnt * sizeof(SlabOut), hipMemcpyDeviceToHost);
@@ -2323,19 +2340,18 @@ int sph_slab_download(SphEngine* e, void* hostOut, size_t capRecords, size_t* nO
 
 // ---- exchange without host round trips (device-side counts) + RCCL transport -------------------------------------
 int sph_slab_alloc_faces(SphEngine* e, uint32_t faceCap) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+    int rc;
+    if ((rc = slab_engine(e))) return rc;
     if (faceCap == 0) return fail(SPH_ERR_ARG, "face capacity must be > 0");
     if (e->faceCap == faceCap && e->d_face[0]) return SPH_OK;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    int rc;
     for (int i = 0; i < 4; ++i) {
         dev_free(e->d_face[i]);
         if ((rc = dev_alloc(&e->d_face[i], slab_face_bytes(faceCap)))) return rc;
         HIP_TRY(hipMemsetAsync(e->d_face[i], 0, sizeof(SlabHdr), e->stream));      // no header yet
     }
-    if (!e->h_cnt) {
-        HIP_TRY(hipHostMalloc((void**)&e->h_cnt, 4 * 8 * sizeof(uint32_t), hipHostMallocDefault));
+    if (!e->h_seen) {
+        HIP_TRY(hipHostMalloc((void**)&e->h_seen, 4 * sizeof(SlabSeen), hipHostMallocDefault));
         for (auto& ev : e->evCnt) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     for (auto& v : e->cntValid) v = false;
@@ -2355,67 +2371,63 @@ int sph_slab_face_bytes(SphEngine* e, uint64_t* bytes) {
     *bytes = (uint64_t)slab_face_bytes(e->faceCap);
     return SPH_OK;
 }
+static SlabMsg slab_msg_whole(uint32_t faceCap) { return SlabMsg{{faceCap, faceCap}, {faceCap, faceCap}}; }   // whole faces
 static void grid_key(const SphGridInfo& g, float out[8]) {
     const float v[8] = {g.gridMin[0], g.gridMin[1], g.gridMin[2], g.cellSize, (float)g.dims[0], (float)g.dims[1], (float)g.dims[2], 0.0f};
     std::memcpy(out, v, sizeof(v));
 }
 static int slab_pack_on(SphEngine* e, hipStream_t st) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab || !e->d_face[0]) return fail(SPH_ERR_STATE, "slab engine with face buffers required");
+    if (int rc = slab_engine(e, true)) return rc;
     sph::compute_grid_extents(e->params, e->grid);
     SimK k;
     make_simk(e->params, e->grid, e->params.param_timeStep, k);
     grid_key(e->grid, e->packGrid);                         // the records this pack cuts are classified for THIS grid (sph_slab_step_begin checks it)
     e->packGridValid = true;
-    e->nSlots = e->cap;                                     // from now on only a launch bound: slabCnt[2] counts the slots in use
-    {                                                       // (slabCnt[8..11] are zero: set at creation, reset by k_slab_headers2)
+    e->nSlots = e->cap;                                     // from now on only a launch bound: kSlabCntLive counts the slots in use
+    {                                                       // (the running counts HaloLo .. MigHi are zero: set at creation, reset by k_slab_headers2)
         Timed t(e, SPH_K_OTHER, st);
         hipLaunchKernelGGL((k_slab_pack<true>), dim3(blocks_for(e->cap)), dim3(kBlock), 0, st, k, e->z0, e->z1, e->hasLo, e->hasHi,
                            e->d_pos[e->cur], e->d_vel[e->cur], e->d_rp[e->cur], e->d_foam[e->cur], e->accValid ? e->d_acc : (const float4*)nullptr, (int)e->cap,
                            (SlabRec*)e->d_face[0], (SlabRec*)e->d_face[1], e->faceCap, e->faceCap, e->d_slabCnt,
                            slab_ranges_usable(e) ? e->d_cellStart : (const uint32_t*)nullptr, k.gx * k.gy);
         hipLaunchKernelGGL(k_slab_headers2, dim3(1), dim3(1), 0, st, e->d_slabCnt, e->hasLo ? e->d_face[0] : (char*)nullptr,
-                           e->hasHi ? e->d_face[1] : (char*)nullptr, e->faceCap, e->msgSend[0], e->msgSend[2], e->msgSend[1], e->msgSend[3]);
+                           e->hasHi ? e->d_face[1] : (char*)nullptr, e->faceCap, e->msgSend);
     }
     HIP_TRY(hipGetLastError());
     return SPH_OK;
 }
-// msg[4]: records the messages carried (halo lo / hi, migrants lo / hi); the face capacity when whole faces were moved
-static int slab_unpack_on(SphEngine* e, hipStream_t st, const void* recvLo, const void* recvHi, uint32_t recvCap, const uint32_t msg[4]) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+// msg: records the messages carried; the face capacity when whole faces were moved
+static int slab_unpack_on(SphEngine* e, hipStream_t st, const void* recvLo, const void* recvHi, uint32_t recvCap, const SlabMsg& msg) {
+    if (int rc = slab_engine(e)) return rc;
     if (recvCap != e->faceCap || !e->faceCap) return fail(SPH_ERR_ARG, "received faces must have this engine's face capacity (%u, got %u)", e->faceCap, recvCap);
-    const char* lo = e->hasLo ? (const char*)recvLo : nullptr;
-    const char* hi = e->hasHi ? (const char*)recvHi : nullptr;
-    if ((e->hasLo && !lo) || (e->hasHi && !hi)) return fail(SPH_ERR_ARG, "missing receive buffer");
+    const char* const face[2] = {e->hasLo ? (const char*)recvLo : nullptr, e->hasHi ? (const char*)recvHi : nullptr};
+    if ((e->hasLo && !face[0]) || (e->hasHi && !face[1])) return fail(SPH_ERR_ARG, "missing receive buffer");
     const int c = e->cur;
     e->nSlots = e->cap;
     const SlabGeom geom = slab_geom(e);
     Timed t(e, SPH_K_OTHER, st);
-    if (lo) hipLaunchKernelGGL(k_slab_unpack2, dim3(blocks_for((size_t)msg[0] + msg[2])), dim3(kBlock), 0, st, lo, (const char*)nullptr, recvCap, msg[0], msg[2], 0u, 0u,
-                               e->d_pos[c], e->d_vel[c], e->d_rp[c], e->d_foam[c], e->d_acc, e->d_slabCnt, (uint32_t)e->cap, geom, 1);
-    if (hi) hipLaunchKernelGGL(k_slab_unpack2, dim3(blocks_for((size_t)msg[1] + msg[3])), dim3(kBlock), 0, st, hi, lo, recvCap, msg[1], msg[3], msg[0], msg[2],
-                               e->d_pos[c], e->d_vel[c], e->d_rp[c], e->d_foam[c], e->d_acc, e->d_slabCnt, (uint32_t)e->cap, geom, 0);
-    hipLaunchKernelGGL(k_slab_commit2, dim3(1), dim3(1), 0, st, e->d_slabCnt, lo, hi, recvCap, (uint32_t)e->cap, msg[0], msg[2], msg[1], msg[3]);
+    for (int d = 0; d < 2; ++d)                              // the face from below first: the upper one's records go behind its
+        if (face[d]) hipLaunchKernelGGL(k_slab_unpack2, dim3(blocks_for((size_t)msg.halo[d] + msg.mig[d])), dim3(kBlock), 0, st, face[d], d ? face[0] : (const char*)nullptr, recvCap, msg,
+                                        e->d_pos[c], e->d_vel[c], e->d_rp[c], e->d_foam[c], e->d_acc, e->d_slabCnt, (uint32_t)e->cap, geom, d);
+    hipLaunchKernelGGL(k_slab_commit2, dim3(1), dim3(1), 0, st, e->d_slabCnt, face[0], face[1], recvCap, (uint32_t)e->cap, msg);
     HIP_TRY(hipGetLastError());
     return SPH_OK;
 }
 int sph_slab_pack_async(SphEngine* e) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
     if (e->slab) slab_hold(e);                              // an exchange outside the sized protocol (priming, re-priming after a grid change): no counts are noted for it
-    for (int i = 0; i < 4; ++i) e->msgSend[i] = e->msgRecv[i] = e->faceCap;   // whole faces (the headers say so)
+    e->msgSend = e->msgRecv = slab_msg_whole(e->faceCap);   // (the headers say so)
     e->intentValid = false;
     return slab_pack_on(e, e->stream);
 }
 int sph_slab_unpack_async(SphEngine* e, const void* recvLo, const void* recvHi, uint32_t recvCap) {
     if (!e) return fail(SPH_ERR_ARG, "null engine");
-    const uint32_t whole[4] = {e->faceCap, e->faceCap, e->faceCap, e->faceCap};
-    return slab_unpack_on(e, e->stream, recvLo, recvHi, recvCap, whole);
+    return slab_unpack_on(e, e->stream, recvLo, recvHi, recvCap, slab_msg_whole(e->faceCap));
 }
 
 // ---- message sizes.  A message carries whole capacity unless the face has been CALM: the counts of the last two known exchanges (e - 3, e - 2)
 // within 3 % + 64 records of each other; then it carries the count of e - 2 + a quarter + 1024.  (A face whose count grows faster than that while it
-// was calm two exchanges ago gets cut off: error flag 8 on the receiver, loud.  Random violent scenes showed that a margin alone is not enough:
+// was calm two exchanges ago gets cut off: SPH_SLAB_FLAG_TRUNCATED on the receiver, loud.  Random violent scenes showed that a margin alone is not enough:
 // tools/fuzz_sweep.py, 2 of 240 slab runs with the plain "count + 25 % + 1024" rule of the first version.)
 static uint32_t msg_records(uint32_t seen, uint32_t before, uint32_t cap, bool tight = false) {
     if (tight) return std::min(cap, seen);                                   // test hook (sph_slab_debug_tight_messages): no margin, no calm test
@@ -2450,30 +2462,31 @@ static int slab_plan(SphEngine* e) {
         const bool wallsMoved = e->lastDt > 0.0f && std::memcmp(cont, e->lastContainer, sizeof(cont)) != 0;   // (before the first dispatch lastContainer is not a container yet)
         if (gridMoved || wallsMoved) slab_hold(e);
     }
-    for (int i = 0; i < 4; ++i) e->msgSend[i] = e->msgRecv[i] = e->faceCap;
+    e->msgSend = e->msgRecv = slab_msg_whole(e->faceCap);
     const bool hold = e->calmHold > 0;                      // (host-side knowledge that every rank shares IF every rank makes the same calls: the plans' holdEvents say whether they did)
     if (hold) e->calmHold -= 1;
     if (e->exchangeNo >= 3 && !hold) {
         const int s2 = (int)((e->exchangeNo - 2u) & 3u), s3 = (int)((e->exchangeNo - 3u) & 3u);
         if (e->cntValid[s2] && e->cntValid[s3]) {
             HIP_TRY(hipEventSynchronize(e->evCnt[s2]));     // two exchanges back: long done unless the host is that far ahead of the device (the host's look-ahead is bounded by this wait)
-            const uint32_t* c = e->h_cnt + 8 * s2;
-            const uint32_t* b = e->h_cnt + 8 * s3;
+            const SlabSeen &seen = e->h_seen[s2], &before = e->h_seen[s3];
             const bool tight = e->tightMessages != 0;
-            for (int i = 0; i < 4; ++i) e->msgSend[i] = msg_records(c[i], b[i], e->faceCap, tight);
-            e->msgRecv[0] = msg_records(c[4], b[4], e->faceCap, tight); e->msgRecv[2] = msg_records(c[5], b[5], e->faceCap, tight);   // from lo: its halo copies, its migrants
-            e->msgRecv[1] = msg_records(c[6], b[6], e->faceCap, tight); e->msgRecv[3] = msg_records(c[7], b[7], e->faceCap, tight);   // from hi
+            for (int d = 0; d < 2; ++d) {
+                e->msgSend.halo[d] = msg_records(seen.sent.halo[d], before.sent.halo[d], e->faceCap, tight);
+                e->msgSend.mig[d] = msg_records(seen.sent.mig[d], before.sent.mig[d], e->faceCap, tight);
+                e->msgRecv.halo[d] = msg_records(seen.received.halo[d], before.received.halo[d], e->faceCap, tight);
+                e->msgRecv.mig[d] = msg_records(seen.received.mig[d], before.received.mig[d], e->faceCap, tight);
+            }
         }
     }
-    e->sentBytes[0] = e->hasLo ? sizeof(SlabHdr) + (uint64_t)e->msgSend[2] * 64u + (uint64_t)e->msgSend[0] * 40u : 0u;
-    e->sentBytes[1] = e->hasHi ? sizeof(SlabHdr) + (uint64_t)e->msgSend[3] * 64u + (uint64_t)e->msgSend[1] * 40u : 0u;
     SphSlabIntent& I = e->intent;
     std::memset(&I, 0, sizeof(I));
     I.magic = kIntentMagic; I.exchangeNo = e->exchangeNo; I.stepNo = e->stepNo; I.faceCap = e->faceCap;
     for (int d = 0; d < 2; ++d) {
         const bool has = d ? e->hasHi : e->hasLo;
-        I.sendHalo[d] = has ? e->msgSend[d] : 0u; I.sendMig[d] = has ? e->msgSend[2 + d] : 0u;
-        I.recvHalo[d] = has ? e->msgRecv[d] : 0u; I.recvMig[d] = has ? e->msgRecv[2 + d] : 0u;
+        e->sentBytes[d] = has ? slab_mig_msg_bytes(e->msgSend.mig[d]) + slab_halo_msg_bytes(e->msgSend.halo[d]) : 0u;
+        I.sendHalo[d] = has ? e->msgSend.halo[d] : 0u; I.sendMig[d] = has ? e->msgSend.mig[d] : 0u;   // (SphSlabIntent keeps its own, public order)
+        I.recvHalo[d] = has ? e->msgRecv.halo[d] : 0u; I.recvMig[d] = has ? e->msgRecv.mig[d] : 0u;
     }
     I.holdEvents = e->holdEvents;
     I.paramsHash = fnv32(&e->params, sizeof(e->params));
@@ -2508,16 +2521,16 @@ static bool slab_intent_mismatch(const SphSlabIntent& me, const SphSlabIntent& n
     }
     return false;
 }
-// behind the transfer on `st`: this exchange's true counts (own: slabCnt[12..15]; the neighbours': their headers) on their way to the host
+// behind the transfer on `st`: this exchange's true counts (own: the Last* counter words; the neighbours': their headers) on their way to the host
 static int slab_note_counts(SphEngine* e, hipStream_t st) {
     const int slot = (int)(e->exchangeNo & 3u);
-    uint32_t* c = e->h_cnt + 8 * slot;
-    HIP_TRY(hipMemcpyAsync(c, e->d_slabCnt + 12, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SlabSeen& c = e->h_seen[slot];
+    HIP_TRY(hipMemcpyAsync(&c.sent, e->d_slabCnt + kSlabCntLastHaloLo, sizeof(SlabMsg), hipMemcpyDeviceToHost, st));
     for (int d = 0; d < 2; ++d) {
-        c[4 + 2 * d] = c[5 + 2 * d] = 0u;
-        if (d ? e->hasHi : e->hasLo) {                      // SlabHdr words: [2] nHaloTrue, [4] nMigTrue
-            HIP_TRY(hipMemcpyAsync(c + 4 + 2 * d, e->d_face[2 + d] + 2 * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(c + 5 + 2 * d, e->d_face[2 + d] + 4 * sizeof(uint32_t), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        c.received.halo[d] = c.received.mig[d] = 0u;
+        if (d ? e->hasHi : e->hasLo) {
+            HIP_TRY(hipMemcpyAsync(&c.received.halo[d], e->d_face[2 + d] + offsetof(SlabHdr, nHaloTrue), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&c.received.mig[d], e->d_face[2 + d] + offsetof(SlabHdr, nMigTrue), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         }
     }
     HIP_TRY(hipEventRecord(e->evCnt[slot], st));
@@ -2545,10 +2558,9 @@ static int ensure_xstream(SphEngine* e) {
     return SPH_OK;
 }
 int sph_slab_step_begin(SphEngine* e, float overrideDt) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab || !e->d_face[0]) return fail(SPH_ERR_STATE, "slab engine with face buffers required");
-    if (e->stepPending) return fail(SPH_ERR_STATE, "sph_slab_step_begin twice without sph_slab_step_finish / sph_slab_step_finish_local");
     int rc;
+    if ((rc = slab_engine(e, true))) return rc;
+    if (e->stepPending) return fail(SPH_ERR_STATE, "sph_slab_step_begin twice without sph_slab_step_finish / sph_slab_step_finish_local");
     if ((rc = ensure_xstream(e))) return rc;
     if (e->params.param_pause) {                             // SPHFluid3D.cpp:432: a paused DispatchCompute is a no-op, and so is its exchange --
         e->stepPending = true; e->stepPaused = true;         // the halo records in place stay valid (impulses act on the copies as on their owners)
@@ -2623,8 +2635,8 @@ int sph_slab_step_finish_local(SphEngine* e, SphEngine* lo, SphEngine* hi) {
         const char* src = nb->d_face[d ? 0 : 1];                             // its "send lo" is my "receive hi" and the other way round
         char* dst = e->d_face[2 + d];
         HIP_TRY(hipStreamWaitEvent(e->xstream, nb->evPacked, 0));
-        HIP_TRY(hipMemcpyAsync(dst, src, sizeof(SlabHdr) + (size_t)e->msgRecv[2 + d] * 64u, hipMemcpyDeviceToDevice, e->xstream));
-        HIP_TRY(hipMemcpyAsync(dst + slab_face_halo_off(e->faceCap), src + slab_face_halo_off(e->faceCap), (size_t)e->msgRecv[d] * 40u, hipMemcpyDeviceToDevice, e->xstream));
+        HIP_TRY(hipMemcpyAsync(dst, src, slab_mig_msg_bytes(e->msgRecv.mig[d]), hipMemcpyDeviceToDevice, e->xstream));
+        HIP_TRY(hipMemcpyAsync(dst + slab_face_halo_off(e->faceCap), src + slab_face_halo_off(e->faceCap), slab_halo_msg_bytes(e->msgRecv.halo[d]), hipMemcpyDeviceToDevice, e->xstream));
     }
     if (e->optTiming) HIP_TRY(hipEventRecord(e->evX[3], e->xstream));
     if ((rc = slab_unpack_on(e, e->xstream, e->d_face[2], e->d_face[3], e->faceCap, e->msgRecv))) return rc;
@@ -2636,25 +2648,24 @@ int sph_slab_step_finish_local(SphEngine* e, SphEngine* lo, SphEngine* hi) {
 }
 int sph_slab_status(SphEngine* e, uint32_t out[5]) {
     if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
-    uint32_t host[8];
+    if (int rc = slab_engine(e)) return rc;
+    uint32_t host[kSlabCntPackedHi + 1];
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->xstream) HIP_TRY(hipStreamSynchronize(e->xstream));
     HIP_TRY(hipMemcpyAsync(host, e->d_slabCnt, sizeof(host), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 5; ++i) out[i] = host[i];
-    out[0] += host[5]; out[1] += host[6];                   // the async pack keeps its counts there (the header kernels reset the running ones)
-    return slab_flags_error(e, host[4], out[0], out[1]);    // (flag 16 alone is a notice, not an error: out[4] carries it)
+    for (int i = 0; i <= kSlabCntFlags; ++i) out[i] = host[i];   // out[5] is the first five counter words ...
+    out[0] += host[kSlabCntPackedLo]; out[1] += host[kSlabCntPackedHi];   // ... plus the async pack's counts (the header kernel resets the running ones)
+    return slab_flags_error(e, host[kSlabCntFlags], out[0], out[1]);    // (SPH_SLAB_FLAG_LAYER_JUMP alone is a notice, not an error: out[4] carries it)
 }
 int sph_slab_clear_flags(SphEngine* e, uint32_t mask) {
-    if (!e) return fail(SPH_ERR_ARG, "null engine");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+    if (int rc = slab_engine(e)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->xstream) HIP_TRY(hipStreamSynchronize(e->xstream));
     uint32_t f = 0;
-    HIP_TRY(hipMemcpy(&f, e->d_slabCnt + 4, sizeof(f), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&f, e->d_slabCnt + kSlabCntFlags, sizeof(f), hipMemcpyDeviceToHost));
     f &= ~mask;
-    HIP_TRY(hipMemcpy(e->d_slabCnt + 4, &f, sizeof(f), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_slabCnt + kSlabCntFlags, &f, sizeof(f), hipMemcpyHostToDevice));
     return SPH_OK;
 }
 int sph_slab_message_bytes(SphEngine* e, uint64_t out[4]) {
@@ -2823,16 +2834,14 @@ int sph_comm_selftest_timed(SphComm* c, uint64_t bytes, float* msOut) {
         if (back[i] != host[i]) return fail(SPH_ERR_HIP, "self send / recv delivered wrong data at word %zu of %zu", i, words);
     return SPH_OK;
 }
-// One halo exchange of a substep: pack -> one grouped ncclSend / ncclRecv per z-neighbour (fixed-size messages: header
-// record + faceCap payload records) -> unpack, all enqueued on the engine's stream: no host synchronisation, and the
-// stream order makes the unpack wait for the receives and the next pack wait for the sends.
+// What every call that takes a communicator checks first: the engine's neighbours are the communicator's, and all ranks allocated the same faces.
 static int slab_check_comm(SphEngine* e, SphComm* c) {
     if (!e || !c) return fail(SPH_ERR_ARG, "null argument");
-    if (!e->slab || !e->d_face[0]) return fail(SPH_ERR_STATE, "slab engine with face buffers required");
+    int rc;
+    if ((rc = slab_engine(e, true))) return rc;
     // both directions: a rank that waits for a neighbour the neighbour does not know about would hang in ncclRecv
     if ((e->hasLo != 0) != (c->rank > 0) || (e->hasHi != 0) != (c->rank < c->world - 1))
         return fail(SPH_ERR_ARG, "slab neighbours (lo %d, hi %d) do not match rank %d of %d", e->hasLo, e->hasHi, c->rank, c->world);
-    int rc;
     if (e->faceAgreedWith != c) {
         // Once per (engine, communicator): the face capacity is the size of every message, so all ranks must have
         // allocated the same one -- a mismatch would otherwise show up as a hang inside ncclSend / ncclRecv.
@@ -2859,17 +2868,17 @@ static int slab_check_comm(SphEngine* e, SphComm* c) {
 // halo copies in use -- of unequal sizes.  One routine for the engine's exchange (slab_transfer_rccl) and for the self-test that runs exactly this
 // pattern on a one-GPU box with the rank itself as both neighbours (sph_comm_selftest_faces): ncclSend / ncclRecv to one peer match in issue order.
 static int rccl_post_faces(SphComm* c, hipStream_t st, const int peer[2], const bool has[2], char* const sendFace[2], char* const recvFace[2],
-                           const uint32_t msgSend[4], const uint32_t msgRecv[4], uint32_t faceCap) {
+                           const SlabMsg& msgSend, const SlabMsg& msgRecv, uint32_t faceCap) {
     if (!has[0] && !has[1]) return SPH_OK;
     const size_t hoff = slab_face_halo_off(faceCap);
     NCCL_TRY(g_rccl.GroupStart());
     ncclResult_t r = ncclSuccess;
     for (int d = 0; d < 2 && r == ncclSuccess; ++d) {
         if (!has[d]) continue;
-        r = g_rccl.Send(sendFace[d], sizeof(SlabHdr) + (size_t)msgSend[2 + d] * 64u, ncclUint8, peer[d], c->comm, st);
-        if (r == ncclSuccess) r = g_rccl.Send(sendFace[d] + hoff, (size_t)msgSend[d] * 40u, ncclUint8, peer[d], c->comm, st);
-        if (r == ncclSuccess) r = g_rccl.Recv(recvFace[d], sizeof(SlabHdr) + (size_t)msgRecv[2 + d] * 64u, ncclUint8, peer[d], c->comm, st);
-        if (r == ncclSuccess) r = g_rccl.Recv(recvFace[d] + hoff, (size_t)msgRecv[d] * 40u, ncclUint8, peer[d], c->comm, st);
+        r = g_rccl.Send(sendFace[d], slab_mig_msg_bytes(msgSend.mig[d]), ncclUint8, peer[d], c->comm, st);
+        if (r == ncclSuccess) r = g_rccl.Send(sendFace[d] + hoff, slab_halo_msg_bytes(msgSend.halo[d]), ncclUint8, peer[d], c->comm, st);
+        if (r == ncclSuccess) r = g_rccl.Recv(recvFace[d], slab_mig_msg_bytes(msgRecv.mig[d]), ncclUint8, peer[d], c->comm, st);
+        if (r == ncclSuccess) r = g_rccl.Recv(recvFace[d] + hoff, slab_halo_msg_bytes(msgRecv.halo[d]), ncclUint8, peer[d], c->comm, st);
     }
     ncclResult_t g = g_rccl.GroupEnd();
     if (r != ncclSuccess) return fail(SPH_ERR_HIP, "ncclSend / ncclRecv failed: %s", g_rccl.GetErrorString(r));
@@ -2879,9 +2888,7 @@ static int rccl_post_faces(SphComm* c, hipStream_t st, const int peer[2], const 
 static int slab_transfer_rccl(SphEngine* e, SphComm* c, hipStream_t st) {
     const int peer[2] = {c->rank - 1, c->rank + 1};
     const bool has[2] = {e->hasLo != 0, e->hasHi != 0};
-    char* const sendFace[2] = {e->d_face[0], e->d_face[1]};
-    char* const recvFace[2] = {e->d_face[2], e->d_face[3]};
-    return rccl_post_faces(c, st, peer, has, sendFace, recvFace, e->msgSend, e->msgRecv, e->faceCap);
+    return rccl_post_faces(c, st, peer, has, e->d_face, e->d_face + 2, e->msgSend, e->msgRecv, e->faceCap);   // send lo / hi, receive lo / hi
 }
 // A wait for a neighbour that cannot hang the host: the event is polled, and after `seconds` the call fails (SPH_ERR_TIMEOUT).  The work behind the
 // event is then still queued on the device (a receive whose sender never came): the process has to end; nothing can be re-posted on this communicator.
@@ -2899,14 +2906,14 @@ static int wait_event_deadline(hipEvent_t ev, double seconds, float* waitedMs) {
 }
 // The fixed-size message that precedes the sized ones: every rank sends its PLAN (64 bytes, slab_plan) to its neighbours and receives theirs.  Its size
 // depends on nothing, so it cannot be mismatched.
-static int rccl_post_plans(SphComm* c, hipStream_t st, const int peer[2], const bool has[2], uint32_t* d_plans /* 48 words: mine, from lo, from hi */) {
+static int rccl_post_plans(SphComm* c, hipStream_t st, const int peer[2], const bool has[2], SlabPlans* d_plans) {
     if (!has[0] && !has[1]) return SPH_OK;
     NCCL_TRY(g_rccl.GroupStart());
     ncclResult_t r = ncclSuccess;
     for (int d = 0; d < 2 && r == ncclSuccess; ++d) {
         if (!has[d]) continue;
-        r = g_rccl.Send(d_plans, sizeof(SphSlabIntent), ncclUint8, peer[d], c->comm, st);
-        if (r == ncclSuccess) r = g_rccl.Recv(d_plans + 16 * (1 + d), sizeof(SphSlabIntent), ncclUint8, peer[d], c->comm, st);
+        r = g_rccl.Send(&d_plans->mine, sizeof(SphSlabIntent), ncclUint8, peer[d], c->comm, st);
+        if (r == ncclSuccess) r = g_rccl.Recv(&d_plans->from[d], sizeof(SphSlabIntent), ncclUint8, peer[d], c->comm, st);
     }
     ncclResult_t g = g_rccl.GroupEnd();
     if (r != ncclSuccess) return fail(SPH_ERR_HIP, "ncclSend / ncclRecv of the plans failed: %s", g_rccl.GetErrorString(r));
@@ -2916,8 +2923,8 @@ static int rccl_post_plans(SphComm* c, hipStream_t st, const int peer[2], const 
 static int ensure_handshake(SphEngine* e) {
     if (e->hstream) return SPH_OK;
     int rc;
-    if ((rc = dev_alloc(&e->d_intent, 48))) return rc;
-    HIP_TRY(hipHostMalloc((void**)&e->h_intent, 48 * sizeof(uint32_t), hipHostMallocDefault));
+    if ((rc = dev_alloc(&e->d_intent, 1))) return rc;
+    HIP_TRY(hipHostMalloc((void**)&e->h_intent, sizeof(SlabPlans), hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&e->evIntent, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&e->hstream, hipStreamNonBlocking));
     return SPH_OK;
@@ -2933,13 +2940,13 @@ static int slab_handshake_rccl(SphEngine* e, SphComm* c) {
     if (!e->intentValid) return fail(SPH_ERR_STATE, "no plan for this exchange");
     int rc;
     if ((rc = ensure_handshake(e))) return rc;
-    std::memcpy(e->h_intent, &e->intent, sizeof(SphSlabIntent));
-    std::memset(e->h_intent + 16, 0, 2 * sizeof(SphSlabIntent));
-    HIP_TRY(hipMemcpyAsync(e->d_intent, e->h_intent, 48 * sizeof(uint32_t), hipMemcpyHostToDevice, e->hstream));
+    e->h_intent->mine = e->intent;
+    std::memset(e->h_intent->from, 0, sizeof(e->h_intent->from));
+    HIP_TRY(hipMemcpyAsync(e->d_intent, e->h_intent, sizeof(SlabPlans), hipMemcpyHostToDevice, e->hstream));
     const int peer[2] = {c->rank - 1, c->rank + 1};
     const bool has[2] = {e->hasLo != 0, e->hasHi != 0};
     if ((rc = rccl_post_plans(c, e->hstream, peer, has, e->d_intent))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->h_intent + 16, e->d_intent + 16, 2 * sizeof(SphSlabIntent), hipMemcpyDeviceToHost, e->hstream));
+    HIP_TRY(hipMemcpyAsync(e->h_intent->from, e->d_intent->from, sizeof(e->h_intent->from), hipMemcpyDeviceToHost, e->hstream));
     HIP_TRY(hipEventRecord(e->evIntent, e->hstream));
     rc = wait_event_deadline(e->evIntent, e->deadlineSec, &e->handshakeMs);
     e->handshakes += 1u;
@@ -2950,10 +2957,8 @@ static int slab_handshake_rccl(SphEngine* e, SphComm* c) {
     if (rc) return rc;
     for (int d = 0; d < 2; ++d) {
         if (!has[d]) continue;
-        SphSlabIntent nb;
-        std::memcpy(&nb, e->h_intent + 16 * (1 + d), sizeof(nb));
         char why[320];
-        if (slab_intent_mismatch(e->intent, nb, d, why, sizeof(why)))
+        if (slab_intent_mismatch(e->intent, e->h_intent->from[d], d, why, sizeof(why)))
             return fail(SPH_ERR_STATE, "rank %d of %d: slab exchange %u refused before any record moved: %s", c->rank, c->world, e->intent.exchangeNo, why);
     }
     return SPH_OK;
@@ -3003,7 +3008,7 @@ int sph_slab_set_deadline(SphEngine* e, double seconds) {
 }
 int sph_slab_plan(const SphEngine* e, SphSlabIntent* out, float* handshakeMsOut) {
     if (!e || !out) return fail(SPH_ERR_ARG, "null argument");
-    if (!e->slab) return fail(SPH_ERR_STATE, "not a slab engine");
+    if (int rc = slab_engine(e)) return rc;
     if (!e->intentValid) return fail(SPH_ERR_STATE, "no sized exchange has been planned yet");
     *out = e->intent;
     if (handshakeMsOut) *handshakeMsOut = e->handshakeMs;
@@ -3031,7 +3036,7 @@ int sph_comm_selftest_faces(SphComm* c, uint32_t faceCap, const uint32_t counts[
     for (int i = 0; i < 4; ++i) if (counts[i] > faceCap) return fail(SPH_ERR_ARG, "count %u > face capacity %u", counts[i], faceCap);
     const size_t fb = slab_face_bytes(faceCap), hoff = slab_face_halo_off(faceCap);
     char* face[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t* d_plans = nullptr;
+    SlabPlans* d_plans = nullptr;
     hipStream_t st = nullptr, hs = nullptr;
     hipEvent_t ev = nullptr, t0 = nullptr, t1 = nullptr;
     auto cleanup = [&]() {
@@ -3043,7 +3048,7 @@ int sph_comm_selftest_faces(SphComm* c, uint32_t faceCap, const uint32_t counts[
     };
     int rc = SPH_OK;
     for (int i = 0; i < 4 && !rc; ++i) rc = dev_alloc(&face[i], fb);
-    if (!rc) rc = dev_alloc(&d_plans, 48);
+    if (!rc) rc = dev_alloc(&d_plans, 1);
     if (rc) { cleanup(); return rc; }
     hipError_t er = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
     if (er == hipSuccess) er = hipStreamCreateWithFlags(&hs, hipStreamNonBlocking);
@@ -3062,9 +3067,12 @@ int sph_comm_selftest_faces(SphComm* c, uint32_t faceCap, const uint32_t counts[
     const int peer[2] = {c->rank, c->rank};
     const bool has[2] = {true, true};
     // the plans
-    uint32_t plans[48];
-    for (int i = 0; i < 48; ++i) plans[i] = i < 16 ? 0x504c0000u + (uint32_t)i : 0u;
-    er = hipMemcpyAsync(d_plans, plans, sizeof(plans), hipMemcpyHostToDevice, hs);
+    constexpr int planWords = (int)(sizeof(SphSlabIntent) / sizeof(uint32_t));
+    uint32_t pattern[planWords];
+    for (int i = 0; i < planWords; ++i) pattern[i] = 0x504c0000u + (uint32_t)i;
+    SlabPlans plans{}, back;
+    std::memcpy(&plans.mine, pattern, sizeof(pattern));
+    er = hipMemcpyAsync(d_plans, &plans, sizeof(plans), hipMemcpyHostToDevice, hs);
     if (er == hipSuccess) er = hipStreamSynchronize(hs);
     if (er != hipSuccess) { cleanup(); return fail(SPH_ERR_HIP, "self-test setup failed: %s", hipGetErrorString(er)); }
     if ((rc = rccl_post_plans(c, hs, peer, has, d_plans))) { cleanup(); return rc; }
@@ -3072,14 +3080,16 @@ int sph_comm_selftest_faces(SphComm* c, uint32_t faceCap, const uint32_t counts[
     float waited = 0.0f;
     rc = wait_event_deadline(ev, 20.0, &waited);
     if (rc) { cleanup(); return rc == SPH_ERR_TIMEOUT ? fail(SPH_ERR_TIMEOUT, "the plans' send / receive to self did not complete within 20 s") : rc; }
-    uint32_t back[48];
-    er = hipMemcpy(back, d_plans, sizeof(back), hipMemcpyDeviceToHost);
+    er = hipMemcpy(&back, d_plans, sizeof(back), hipMemcpyDeviceToHost);
     if (er != hipSuccess) { cleanup(); return fail(SPH_ERR_HIP, "self-test copy back failed: %s", hipGetErrorString(er)); }
-    for (int i = 0; i < 32; ++i)
-        if (back[16 + i] != plans[i & 15]) { cleanup(); return fail(SPH_ERR_HIP, "a 64-byte plan sent to self arrived wrong at word %d", i); }
+    uint32_t words[2 * planWords];
+    std::memcpy(words, back.from, sizeof(words));
+    for (int i = 0; i < 2 * planWords; ++i)
+        if (words[i] != pattern[i % planWords]) { cleanup(); return fail(SPH_ERR_HIP, "a 64-byte plan sent to self arrived wrong at word %d", i); }
     // the faces: the sizes a receiver posts are the sizes the matching sender uses (what the plans' comparison guarantees between two ranks)
     (void)hipEventRecord(t0, st);
-    if ((rc = rccl_post_faces(c, st, peer, has, face, face + 2, counts, counts, faceCap))) { cleanup(); return rc; }
+    const SlabMsg msg{{counts[0], counts[1]}, {counts[2], counts[3]}};   // (the public order: halo lo, halo hi, migrants lo, migrants hi)
+    if ((rc = rccl_post_faces(c, st, peer, has, face, face + 2, msg, msg, faceCap))) { cleanup(); return rc; }
     (void)hipEventRecord(t1, st);
     rc = wait_event_deadline(t1, 60.0, nullptr);
     if (rc) { cleanup(); return rc == SPH_ERR_TIMEOUT ? fail(SPH_ERR_TIMEOUT, "the face messages to self did not complete within 60 s") : rc; }
@@ -3088,7 +3098,7 @@ int sph_comm_selftest_faces(SphComm* c, uint32_t faceCap, const uint32_t counts[
     for (int d = 0; d < 2; ++d) {
         er = hipMemcpy(got.data(), face[2 + d], fb, hipMemcpyDeviceToHost);
         if (er != hipSuccess) { cleanup(); return fail(SPH_ERR_HIP, "self-test copy back failed: %s", hipGetErrorString(er)); }
-        const size_t migEnd = sizeof(SlabHdr) + (size_t)counts[2 + d] * 64u, haloEnd = hoff + (size_t)counts[d] * 40u;
+        const size_t migEnd = slab_mig_msg_bytes(msg.mig[d]), haloEnd = hoff + slab_halo_msg_bytes(msg.halo[d]);
         for (size_t i = 0; i < fb; ++i) {
             const bool sent = i < migEnd || (i >= hoff && i < haloEnd);
             const unsigned char want = sent ? host[d][i] : (unsigned char)0;

@@ -4,6 +4,7 @@
 //   wave_sum / wave_min / wave_max        the value of the whole wave in every lane; the butterfly runs 32, 16, ..., 1 for every type, so a
 //                                         float or double sum has one fixed order (and its bits) wherever it is taken
 //   block_max                             the largest value of the block in every thread; sm: 4 words of LDS
+//   wave_append                           compaction: one record per lane with a predicate, appended behind a device counter with one atomic per wave
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,6 +74,21 @@ __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t* sm) {
     const uint32_t m = max(max(sm[0], sm[1]), max(sm[2], sm[3]));
     __syncthreads();
     return m;
+}
+
+// Wave-aggregated append: the lanes with pred take consecutive slots of buf behind *counter (one atomicAdd per wave, by its first such lane) and
+// store rec there if the slot is below cap; *counter counts every lane with pred, stored or not.  Lanes without pred only take part in the ballot.
+template <class R>
+__device__ __forceinline__ void wave_append(R* buf, uint32_t* counter, uint32_t cap, bool pred, const R& rec) {
+    const unsigned long long m = __ballot(pred);
+    if (!pred) return;
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, leader, 64);
+    const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (slot < cap) buf[slot] = rec;
 }
 
 }  // namespace sph

@@ -471,6 +471,9 @@ class SphSlabIntent(C.Structure):
 
 
 assert C.sizeof(SphSlabIntent) == 64
+# bits of the z-slab exchange's flag word (sph_slab_status out[4]); all but LAYER_JUMP, a notice, mean that records were lost
+SPH_SLAB_FLAG_SEND_OVERFLOW, SPH_SLAB_FLAG_SLOT_OVERFLOW, SPH_SLAB_FLAG_BAD_HEADER, SPH_SLAB_FLAG_TRUNCATED = 1, 2, 4, 8
+SPH_SLAB_FLAG_LAYER_JUMP, SPH_SLAB_FLAG_SIZE_MISMATCH = 16, 32
 KERNEL_CLASSES = ("bin", "scan", "scatter", "sph", "writeback", "impulse", "other")     # SPH_K_* of "measurement"
 
 

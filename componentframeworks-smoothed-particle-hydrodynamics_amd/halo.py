@@ -30,6 +30,7 @@ from . import engine as _eng
 from . import synthetic as _syn
 
 REC_WORDS = 16          # 64-byte exchange record: pos3 vel3 rho prs foam id flags pad acc3 pad
+REC_BYTES, HALO_REC_BYTES, FACE_HDR_BYTES = 4 * REC_WORDS, 40, 64   # SPH_SLAB_REC_BYTES, SPH_SLAB_HALO_BYTES, the header in front of a face's migrants
 OUT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("vel", "<f4", (3,)), ("acc", "<f4", (3,)), ("density", "<f4"),
                       ("pressure", "<f4"), ("padA", "<f4"), ("id", "<u4"), ("flags", "<u4"), ("pad", "<u4", (2,))])
 assert OUT_DTYPE.itemsize == 64
@@ -146,13 +147,13 @@ class HipSlabEngine:
         _eng._check(self._L.sph_slab_debug_tight_messages(self._h, 1 if on else 0))
 
     def status(self):
-        """[records packed for lo, for hi, slots in use, -, flags]; raises for the flags that lost records (1, 2, 4, 8).  Flag 16 (a particle
-        crossed more cell layers in one substep than the exchange follows) is a notice: it comes back in [4]."""
+        """[records packed for lo, for hi, slots in use, -, flags]; raises for the SPH_SLAB_FLAG_* that lost records.  SPH_SLAB_FLAG_LAYER_JUMP (a
+        particle crossed more cell layers in one substep than the exchange follows) is a notice: it comes back in [4]."""
         out = (C.c_uint32 * 5)()
         _eng._check(self._L.sph_slab_status(self._h, out))
         return [int(x) for x in out]
 
-    def clear_flags(self, mask: int = 16):
+    def clear_flags(self, mask: int = _eng.SPH_SLAB_FLAG_LAYER_JUMP):
         _eng._check(self._L.sph_slab_clear_flags(self._h, int(mask)))
 
     def message_bytes(self):

@@ -94,9 +94,9 @@ int main(int argc, char** argv) {
         got += m;
         uint64_t bytes[4];
         CHECK(sph_slab_message_bytes(slab[r], bytes));       // what the last exchange sent to the lower / upper neighbour, against a whole face
-        if (st[4] & 16u) {                                    // notice: a particle crossed more cell layers in one substep than the exchange follows
+        if (st[4] & SPH_SLAB_FLAG_LAYER_JUMP) {                                    // notice: a particle crossed more cell layers in one substep than the exchange follows
             std::printf("slab %d: notice 16 (a particle crossed more than 3 cell layers in one substep)\n", r);
-            CHECK(sph_slab_clear_flags(slab[r], 16u));
+            CHECK(sph_slab_clear_flags(slab[r], SPH_SLAB_FLAG_LAYER_JUMP));
         }
         std::printf("slab %d: %zu owned particles, last pack %u / %u records, last messages %llu / %llu bytes (a face: %llu)\n", r, m, st[0], st[1],
                     (unsigned long long)bytes[0], (unsigned long long)bytes[1], (unsigned long long)(bytes[2] ? bytes[2] : bytes[3]));
@@ -120,7 +120,7 @@ int main(int argc, char** argv) {
         CHECK(sph_slab_plan(slab[1], &b, nullptr));
         std::printf("plans of exchange %u: slab 0 has seen %u hold events and would send %u + %u records up, slab 1 has seen %u and expects %u + %u\n",
                     a.exchangeNo, a.holdEvents, a.sendHalo[1], a.sendMig[1], b.holdEvents, b.recvHalo[0], b.recvMig[0]);
-        for (auto* e : slab) { uint32_t st[5]; CHECK(sph_slab_status(e, st)); if (st[4] & ~16u) refused = false; }   // nothing was cut off: nothing moved
+        for (auto* e : slab) { uint32_t st[5]; CHECK(sph_slab_status(e, st)); if (st[4] & ~(uint32_t)SPH_SLAB_FLAG_LAYER_JUMP) refused = false; }   // nothing was cut off: nothing moved
     }
     for (auto* e : slab) sph_destroy(e);
     sph_destroy(one);

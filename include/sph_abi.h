@@ -62,6 +62,7 @@ extern "C" {
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (still 4, additions only: SphStateInfo, SphStateDigest, SPH_STATE_*, sph_state_size / _save / _load / _peek / _digest / _checksum_host -- checkpoints) */
 /* (still 4, additions only: SphAggregateConfig, SphAggregateInfo, SPH_AGGREGATE_*, sph_aggregate_default / _particles / _query / _staged / _host, SPH_OPT_AGGREGATE_VARIANT -- fused neighbourhood reductions of caller tensors) */
+/* (still 4, additions only: SPH_SLAB_FLAG_* -- names of the six bits of the z-slab exchange's flag word, values as before) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -1450,7 +1451,7 @@ int sph_slab_download(SphEngine* e, void* hostOut, size_t capRecords, size_t* nO
  * record counts of the last two known exchanges within 3 % of each other, no impulse / container edit / re-priming in the last
  * three exchanges): then the records in use two exchanges ago + a quarter + 1024 (read back asynchronously into pinned memory,
  * so the path never waits for the device; both ends of a link derive the size from the same numbers: the sender from its own
- * counts, the receiver from the headers it received then).  A message that turns out too small sets error flag 8 on the
+ * counts, the receiver from the headers it received then).  A message that turns out too small sets SPH_SLAB_FLAG_TRUNCATED on the
  * receiver (records were cut off).
  * sph_slab_pack_async / sph_slab_unpack_async are the two halves for hosts that move the faces themselves (several slab
  * engines in one process, another transport): move sph_slab_face_bytes() bytes, or the three parts in use.  Overflows (send
@@ -1467,11 +1468,17 @@ int sph_slab_face_buffer(SphEngine* e, int which /* 0 send lo, 1 send hi, 2 recv
 int sph_slab_face_bytes(SphEngine* e, uint64_t* bytes);
 int sph_slab_pack_async(SphEngine* e);
 int sph_slab_unpack_async(SphEngine* e, const void* recvLo, const void* recvHi, uint32_t recvCap);
-/* Synchronises; out = {records packed for lo, for hi, slots in use, -, flags}.  Flags (device side, sticky until
- * sph_slab_clear_flags).  ERRORS -- records were lost; this call and sph_slab_download then return an error: 1 a send face
- * overflowed, 2 the slot capacity overflowed while appending received records, 4 a received message did not start with a valid
- * header, 8 the neighbour had more records than its message carried.  NOTICE -- nothing lost, the call succeeds and out[4]
- * carries the bit: 16 a particle crossed MORE cell layers in z within one substep than the exchange follows.  The exchange
+/* The exchange's flags: device side, sticky until sph_slab_clear_flags, out[4] of sph_slab_status.  ERRORS -- records were lost;
+ * sph_slab_status and sph_slab_download then return an error.  One NOTICE -- nothing lost, the calls succeed and out[4] carries the bit. */
+enum {
+    SPH_SLAB_FLAG_SEND_OVERFLOW = 1,    /* error: a send face overflowed */
+    SPH_SLAB_FLAG_SLOT_OVERFLOW = 2,    /* error: the slot capacity overflowed while appending received records */
+    SPH_SLAB_FLAG_BAD_HEADER = 4,       /* error: a received message did not start with a valid header */
+    SPH_SLAB_FLAG_TRUNCATED = 8,        /* error: the neighbour had more records than its message carried */
+    SPH_SLAB_FLAG_LAYER_JUMP = 16,      /* notice: a particle crossed MORE cell layers in z within one substep than the exchange follows */
+    SPH_SLAB_FLAG_SIZE_MISMATCH = 32    /* error: the two ends of a link sized an exchange's messages differently (see the plans below) */
+};
+/* Synchronises; out = {records packed for lo, for hi, slots in use, -, flags (SPH_SLAB_FLAG_*)}.  SPH_SLAB_FLAG_LAYER_JUMP: the exchange
  * follows up to 3 layers per substep (the pack and the face launches of a boundary-first step cover the 5 lowest / highest
  * local layers; migrants go to the adjacent rank, which such a jump still reaches while every slab is at least 4 layers
  * thick); beyond that -- a particle placed far outside the container, a container that moved by cells under the fluid, a
@@ -1480,7 +1487,7 @@ int sph_slab_unpack_async(SphEngine* e, const void* recvLo, const void* recvHi, 
  * the BASELINE workloads stay far inside it through their whole collapse; the pack after a container change scans
  * every slot, so a change of shape alone is followed exactly as long as no particle has to cross a whole slab.) */
 int sph_slab_status(SphEngine* e, uint32_t out[5]);
-/* Clears the given flag bits (synchronises): a host acknowledges notice 16 and goes on. */
+/* Clears the given flag bits (synchronises): a host acknowledges SPH_SLAB_FLAG_LAYER_JUMP and goes on. */
 int sph_slab_clear_flags(SphEngine* e, uint32_t mask);
 /* Bytes of the last exchange's messages to the lower / upper neighbour, and the bytes a whole face would be: {sent lo, sent hi,
  * face lo, face hi} (host-side bookkeeping, no synchronisation). */
@@ -1531,7 +1538,7 @@ typedef struct SphSlabIntent {
  *     off: then there is no host wait on the path beyond the pinned-memory read of counts that are two exchanges old, and agreement rests
  *     on the ranks' call sequences being the same.
  * Behind both there is a device-side check: a header names the sizes its sender's messages carry, the receiver's unpack compares them with the
- * sizes it received: flag 32 (an error of sph_slab_status / sph_slab_download). */
+ * sizes it received: SPH_SLAB_FLAG_SIZE_MISMATCH (an error of sph_slab_status / sph_slab_download). */
 int sph_slab_set_verify(SphEngine* e, int mode /* 1 (default) | 0 */);
 /* Limit of every host-side wait for a neighbour (default 30 s). */
 int sph_slab_set_deadline(SphEngine* e, double seconds);
@@ -1551,7 +1558,7 @@ int sph_comm_selftest_faces(SphComm* comm, uint32_t faceCap, const uint32_t coun
 /* ---- boundary-first substep: the exchange hidden behind the interior of the SPH pass -----------------------------
  * sph_slab_step_begin = sph_dispatch, except that the SPH pass runs the slot ranges next to the slab's faces first (the
  * five lowest / five highest local cell layers: everything the next pack can touch as long as a substep moves a particle
- * across at most three layers; a substep that does not is reported, flag 16 above), and then, on a second stream of the engine, the pack of the exchange that prepares the
+ * across at most three layers; a substep that does not is reported, SPH_SLAB_FLAG_LAYER_JUMP above), and then, on a second stream of the engine, the pack of the exchange that prepares the
  * NEXT substep -- while the interior slots are still being computed on the engine's stream.  The second half moves the
  * faces and unpacks, still on the second stream; the engine's stream waits for it only at its end:
  *   sph_slab_step_finish(engine, comm)            one process per GPU: grouped ncclSend / ncclRecv (RCCL over xGMI)

@@ -1,6 +1,7 @@
 """The C-ABI library loads, exports every symbol include/sph_abi.h declares, fails loudly
 without a device, and its host-only entry points agree with the oracle (no GPU needed)."""
 import ctypes as C
+import importlib
 import os
 import re
 
@@ -135,6 +136,22 @@ def test_slab_message_sizing_rule(pkg):
     assert f(10, 200, cap) == cap
     for seen, before in ((5000, 5100), (5100, 5000), (123456, 120000)):
         assert 0 < f(seen, before, cap) <= cap
+
+
+def test_slab_flag_names(pkg):
+    """SPH_SLAB_FLAG_*: the header's six names are six distinct bits with the values the flag word has always had, the package exports
+    them under the same names, and the library's source ties the device-side mirror to them when it is built."""
+    names = dict((n, int(v)) for n, v in re.findall(r"\b(SPH_SLAB_FLAG_[A-Z_]+)\s*=\s*(\d+)", _header()))
+    assert names == {"SPH_SLAB_FLAG_SEND_OVERFLOW": 1, "SPH_SLAB_FLAG_SLOT_OVERFLOW": 2, "SPH_SLAB_FLAG_BAD_HEADER": 4,
+                     "SPH_SLAB_FLAG_TRUNCATED": 8, "SPH_SLAB_FLAG_LAYER_JUMP": 16, "SPH_SLAB_FLAG_SIZE_MISMATCH": 32}
+    for name, value in names.items():
+        assert getattr(pkg, name) == value, name
+    eng = open(os.path.join(ROOT, pkg.__name__, "csrc", "sph_engine.hip")).read()
+    for name in names:
+        assert re.search(r"static_assert\([^;]*\b%s == sph::kSlabFlag" % name, eng), name
+    halo = importlib.import_module(pkg.__name__ + ".halo")
+    sizes = dict((n, int(v)) for n, v in re.findall(r"#define (SPH_SLAB_[A-Z]+_BYTES) (\d+)", _header()))
+    assert (halo.REC_BYTES, halo.HALO_REC_BYTES) == (sizes["SPH_SLAB_REC_BYTES"], sizes["SPH_SLAB_HALO_BYTES"]) == (64, 40)
 
 
 def _plan(pkg, **kw):

@@ -90,8 +90,8 @@ def test_random_scene_as_z_slabs_with_boundary_first_steps(pkg, oracle, seed):
     reported = []
     for s in grp.sims:
         st = s.engine.status()                     # (raises for the flags that lose records)
-        assert st[4] & ~16 == 0, st
-        if st[4] & 16:
+        assert st[4] & ~pkg.SPH_SLAB_FLAG_LAYER_JUMP == 0, st
+        if st[4] & pkg.SPH_SLAB_FLAG_LAYER_JUMP:
             reported.append(st)
     if reported:                                   # allowed only where a particle crossed more layers than the exchange follows (3, or the slab's thickness)
         thin = min(s.z1 - s.z0 for s in grp.sims)
@@ -295,8 +295,8 @@ def test_random_call_sequences_on_z_slabs(pkg, oracle, seed):
     reported = []
     for s in grp.sims:
         st = s.engine.status()
-        assert st[4] & ~16 == 0, st
-        if st[4] & 16:
+        assert st[4] & ~pkg.SPH_SLAB_FLAG_LAYER_JUMP == 0, st
+        if st[4] & pkg.SPH_SLAB_FLAG_LAYER_JUMP:
             reported.append(st)
     if reported:
         thin = min(s.z1 - s.z0 for s in grp.sims)

@@ -449,7 +449,7 @@ def test_grid_change_between_two_steps_is_refused_by_the_abi_and_followed_by_the
     for _ in range(3):
         grp.DispatchCompute(); want = oracle.substep(want, op)
     st = [s.engine.status() for s in grp.sims]
-    assert all(x[4] & ~16 == 0 for x in st), st
+    assert all(x[4] & ~pkg.SPH_SLAB_FLAG_LAYER_JUMP == 0 for x in st), st
     if all(x[4] == 0 for x in st):                               # (the move itself may carry particles across more layers than the exchange follows)
         assert_records_equal(halo.merge_into_records(P, grp.download()), want, "2 slabs across a grid that moved by a cell")
 
@@ -476,7 +476,7 @@ def test_messages_shrink_to_the_records_in_use_and_halo_copies_are_40_bytes(pkg,
 
 
 def test_a_jump_across_a_whole_slab_is_a_notice_not_an_error(pkg, oracle):
-    """Flag 16 (a particle crossed more layers than the exchange follows) loses no record: sph_slab_download delivers, the status call
+    """SPH_SLAB_FLAG_LAYER_JUMP (a particle crossed more layers than the exchange follows) loses no record: sph_slab_download delivers, the status call
     succeeds and carries the bit, sph_slab_clear_flags acknowledges it."""
     halo = importlib.import_module(PKG_NAME + ".halo")
     P, sp, op = _scene(pkg, oracle)
@@ -490,11 +490,11 @@ def test_a_jump_across_a_whole_slab_is_a_notice_not_an_error(pkg, oracle):
     for _ in range(3):
         grp.DispatchCompute()
     st = [s.engine.status() for s in grp.sims]                   # does not raise
-    assert any(x[4] & 16 for x in st) and all(x[4] & ~16 == 0 for x in st), st
+    assert any(x[4] & pkg.SPH_SLAB_FLAG_LAYER_JUMP for x in st) and all(x[4] & ~pkg.SPH_SLAB_FLAG_LAYER_JUMP == 0 for x in st), st
     owned = grp.download()                                       # does not raise, nobody is lost
     assert sorted(owned["id"].tolist()) == list(range(len(P)))
     for s in grp.sims:
-        s.engine.clear_flags(16)
+        s.engine.clear_flags(pkg.SPH_SLAB_FLAG_LAYER_JUMP)
     assert all(s.engine.status()[4] == 0 for s in grp.sims)
 
 
@@ -515,7 +515,7 @@ def test_step_times_say_whether_the_exchange_was_hidden(pkg, oracle):
 def test_a_message_that_turns_out_too_small_is_reported(pkg, oracle):
     """Messages are sized from the counts of two exchanges ago + 25 % + 1024 records.  With the margin and the calm / hold rules taken away
     (sph_slab_debug_tight_messages on EVERY engine: the hook is part of the plan, so both ends of a link still agree) any growth of a face's
-    record count cuts records off -- which must be LOUD (error flag 8: sph_slab_status / sph_slab_download fail), never silent."""
+    record count cuts records off -- which must be LOUD (SPH_SLAB_FLAG_TRUNCATED: sph_slab_status / sph_slab_download fail), never silent."""
     halo = importlib.import_module(PKG_NAME + ".halo")
     rec, sp = small_scene(pkg, n=6000, grid=20, seed=51)
     grp = _group(pkg, halo, rec, sp, 2)
@@ -562,6 +562,48 @@ def test_the_plans_of_neighbouring_engines_agree_on_every_step(pkg, oracle):
             assert plans[r].sendHalo[1] == plans[r + 1].recvHalo[0] and plans[r].recvMig[1] == plans[r + 1].sendMig[0]
             assert 0 < plans[r].sendHalo[1] < 20000                                  # sized, not whole faces
     assert_records_equal(halo.merge_into_records(P, grp.download()), want, "3 slabs, sized exchanges, plans compared on every step")
+
+
+def test_sized_messages_of_a_slab_whose_two_faces_differ(pkg, oracle):
+    """Every other scene here is symmetric in z, so a lower / upper or halo / migrant mix-up in the message sizes would pass.  Here the
+    middle slab of three sends clearly different numbers of halo copies down and up: the resting lattice of _primed_calm_group with every
+    second particle of the upper half (cell layer 12 and above) taken out.  The layer populations come from the oracle: over the steps of
+    this test the two face layers of the middle slab (8 and 15) differ by more than the calm slack of the sizing rule, max / 32 + 64, and
+    each moves by less than that from step to step -- so the exchanges are sized, and sized differently per direction."""
+    halo = importlib.import_module(PKG_NAME + ".halo")
+    P, sp = small_scene(pkg, n=15000, grid=24, seed=51)
+    cz, dims = _cell_z(pkg, sp, P)
+    P = P[~((cz >= 12) & (np.arange(len(P)) % 2 == 1))].copy()
+    op = to_oracle_params(oracle, sp)
+    z0, z1, cap, primed, steps = dims[2] // 3, 2 * (dims[2] // 3), 20000, 6, 12
+    traj = [P]
+    for _ in range(steps):
+        traj.append(oracle.substep(traj[-1], op))
+    faces = np.array([np.bincount(_cell_z(pkg, sp, Q)[0], minlength=dims[2])[[z0, z1 - 1]] for Q in traj])   # [step, lower / upper face layer]
+    def apart(a, b):                                              # the sizing rule's "not calm" (msg_records of sph_engine.hip)
+        return np.abs(a - b) > np.maximum(a, b) // 32 + 64
+    assert apart(faces[:, 0], faces[:, 1]).all() and not apart(faces[1:], faces[:-1]).any(), faces.tolist()
+
+    grp = _group(pkg, halo, P, sp, 3)
+    grp.enable_overlap(cap)
+    assert [(s.z0, s.z1) for s in grp.sims][1] == (z0, z1)
+    for _ in range(primed):
+        grp.DispatchCompute()
+    plans = [s.engine.plan()[0] for s in grp.sims]
+    mid = plans[1]
+    assert mid.flags == 0 and all(0 < mid.sendHalo[d] < cap for d in (0, 1)) and mid.sendHalo[0] != mid.sendHalo[1], (list(mid.sendHalo), mid.flags)
+    sent_lo, sent_hi, _, _ = grp.sims[1].engine.message_bytes()
+    assert sent_lo == halo.FACE_HDR_BYTES + mid.sendMig[0] * halo.REC_BYTES + mid.sendHalo[0] * halo.HALO_REC_BYTES
+    assert sent_hi == halo.FACE_HDR_BYTES + mid.sendMig[1] * halo.REC_BYTES + mid.sendHalo[1] * halo.HALO_REC_BYTES
+    for lo, hi in zip(plans[:-1], plans[1:]):                     # every link, both ways
+        assert lo.sendHalo[1] == hi.recvHalo[0] and lo.sendMig[1] == hi.recvMig[0]
+        assert hi.sendHalo[0] == lo.recvHalo[1] and hi.sendMig[0] == lo.recvMig[1]
+    assert all(s.engine.status()[4] == 0 for s in grp.sims)
+    for _ in range(steps - primed):
+        grp.DispatchCompute()
+    assert all(s.engine.plan()[0].flags == 0 for s in grp.sims)   # sized to the end
+    assert all(s.engine.status()[4] == 0 for s in grp.sims)
+    assert_records_equal(halo.merge_into_records(P, grp.download()), traj[-1], "3 slabs whose faces differ, sized exchanges")
 
 
 @pytest.mark.parametrize("what", ["kick", "member", "hook"])
