@@ -360,6 +360,12 @@ struct SphEngine {
     // sph_aggregate_*: the caller's values in slot order (the stage of the default variant); no result is kept
     DevBuf<float> d_aggStage, d_aggIn, d_aggOut;   // (d_aggIn / d_aggOut / d_aggCnt: the device side of sph_aggregate_staged's host arrays)
     DevBuf<uint32_t> d_aggCnt;
+    // sph_aggregate_adjoint_* / _route_*: the counting sort of the query points (key, count, tile sums, start, arrival order, perm, sorted
+    // points), arg in row order, and the device side of the staged call's g
+    DevBuf<uint2> d_adjKey;
+    DevBuf<uint32_t> d_adjCount, d_adjSums, d_adjStart, d_adjTmp, d_adjPerm, d_adjArg;
+    DevBuf<float4> d_adjPts;
+    DevBuf<float> d_adjIn;
     int optAggVariant = 0;                  // SPH_OPT_AGGREGATE_VARIANT: bit 0 gather by id (no stage), bits 1-2 channels per pass, bit 3 4-byte loads (same bits)
     // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
     // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets); the two words of the reduction
@@ -661,7 +667,11 @@ void shell_free(SphEngine* e) {
     e->d_shStats.release(); e->d_shOffsets.release();
     e->shellInfo = SphShellInfo{};
 }
-void aggregate_free(SphEngine* e) { e->d_aggStage.release(); e->d_aggIn.release(); e->d_aggOut.release(); e->d_aggCnt.release(); }
+void aggregate_free(SphEngine* e) {
+    e->d_aggStage.release(); e->d_aggIn.release(); e->d_aggOut.release(); e->d_aggCnt.release();
+    e->d_adjKey.release(); e->d_adjCount.release(); e->d_adjSums.release(); e->d_adjStart.release(); e->d_adjTmp.release(); e->d_adjPerm.release();
+    e->d_adjArg.release(); e->d_adjPts.release(); e->d_adjIn.release();
+}
 void aniso_free(SphEngine* e) {
     e->d_anRows.release(); e->d_anSlots.release(); e->d_anStats.release();
     e->anisoInfo = SphAnisoInfo{};
@@ -4881,6 +4891,342 @@ int sph_aggregate_host(const SphParticle* particles, size_t n, const SphParams* 
             if (extremum) { orow[c] = sph::agg_unordered(best[c]); continue; }
             orow[c] = cfg->op == SPH_AGGREGATE_MEAN ? sph::aggregate_mean(acc[c], W) : acc[c];
             for (size_t p = 1; p < planes; ++p) orow[p * C + c] = acc[p * C + c];
+        }
+        if (count) count[r] = cnt;
+    }
+    return SPH_OK;
+}
+
+// ---- the adjoint of the neighbourhood sums, extrema with their winners, routing through them (sph_aggregate.h) ----
+// The forward's config plus the op the family takes: SUM for the adjoint, MAX / MIN for the winners and the routing.
+static int adjoint_check(const SphAggregateConfig& c, float cellSize, bool query, bool extremum, int* stencil) {
+    int rc;
+    if ((rc = aggregate_check(c, cellSize, query, stencil))) return rc;
+    if (!extremum && c.op != SPH_AGGREGATE_SUM) return fail(SPH_ERR_ARG, "the adjoint is that of SPH_AGGREGATE_SUM (op %d)", c.op);
+    if (extremum && c.op != SPH_AGGREGATE_MAX && c.op != SPH_AGGREGATE_MIN) return fail(SPH_ERR_ARG, "winners are those of SPH_AGGREGATE_MAX / _MIN (op %d)", c.op);
+    return SPH_OK;
+}
+
+// The counting sort of m query points by clamped cell into (cell, point index) order, without the non-finite ones: d_adjStart (the cell
+// table; its last word is the number of binned points), d_adjPerm, d_adjPts.  Scratch grown by the caller before sample_grid.
+static int adjoint_bin_grow(SphEngine* e, size_t m, size_t cells) {
+    int rc;
+    if ((rc = e->d_adjKey.grow(e, m)) || (rc = e->d_adjTmp.grow(e, m)) || (rc = e->d_adjPerm.grow(e, m)) || (rc = e->d_adjPts.grow(e, m)) ||
+        (rc = e->d_adjCount.grow(e, cells + 8)) || (rc = e->d_adjSums.grow(e, (size_t)blocks_for(cells, kScanTile) + 1)) ||
+        (rc = e->d_adjStart.grow(e, cells + 1))) return rc;
+    return SPH_OK;
+}
+static int adjoint_bin(SphEngine* e, const SimK& k, const float4* devPoints, size_t m) {
+    const uint32_t cells = (uint32_t)k.numCells, mm = (uint32_t)m;
+    HIP_TRY(hipMemsetAsync(e->d_adjCount.p, 0, (size_t)cells * sizeof(uint32_t), e->stream));
+    Timed t(e, SPH_K_OTHER);
+    hipLaunchKernelGGL(k_adjoint_bin, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, k, devPoints, e->d_adjKey.p, e->d_adjCount.p, mm);
+    launch_cell_scan(e, e->d_adjCount.p, e->d_adjSums.p, e->d_adjStart.p, (int)cells, mm);
+    hipLaunchKernelGGL(k_adjoint_scatter, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_adjKey.p, (const uint32_t*)e->d_adjStart.p, e->d_adjTmp.p, mm, cells);
+    hipLaunchKernelGGL(k_adjoint_rank, dim3(blocks_for(m)), dim3(kBlock), 0, e->stream, (const uint2*)e->d_adjKey.p, (const uint32_t*)e->d_adjStart.p,
+                       (const uint32_t*)e->d_adjTmp.p, devPoints, e->d_adjPerm.p, e->d_adjPts.p, mm, cells);
+    return SPH_OK;
+}
+
+// The adjoint (route false: devArg null) or the routing of g.  Grid of the current state, ids, the rows (sorted slots, or the binned
+// points), g (and arg) staged into row order, the walk.  No synchronisation: nothing is read back.
+static int adjoint_run(SphEngine* e, bool query, bool route, const SphAggregateConfig* cfg, const float4* devPoints, size_t m, const int32_t* devArg,
+                       const float* devG, float* devOut, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = adjoint_check(*cfg, g.cellSize, query, route, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, planes = route ? 1 : (size_t)aggregate_planes(*cfg);
+    if (n && !devOut) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!devG || (route && !devArg) || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (planes * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, planes, C);
+    const size_t gBytes = rows * planes * C * sizeof(float), outBytes = n * C * sizeof(float);
+    if (ranges_overlap(devOut, outBytes, devG, gBytes) || ranges_overlap(devOut, outBytes, devArg, route ? rows * C * sizeof(int32_t) : 0) ||
+        ranges_overlap(devOut, outBytes, devPoints, query ? m * sizeof(float4) : 0)) return fail(SPH_ERR_ARG, "the output overlaps g, arg or the points");
+    SphAggregateInfo info{};
+    info.rows = n; info.channels = cfg->channels; info.planes = (int32_t)planes; info.stencil = stencil; info.flags = cfg->flags; info.radius = cfg->radius;
+    *out = info;
+    if (!n) return SPH_OK;
+    if (!rows) {                                                        // no query point: every row is +0
+        HIP_TRY(hipMemsetAsync(devOut, 0, outBytes, e->stream));
+        return SPH_OK;
+    }
+    if (!query && !route && planes == 1) {                             // the relation and the weights are symmetric: the forward of g
+        SphAggregateInfo fwd;
+        return aggregate_run(e, false, cfg, nullptr, 0, devG, devOut, nullptr, &fwd);
+    }
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_aggStage.grow(e, rows * planes * C)) || (route && (rc = e->d_adjArg.grow(e, rows * C))) ||
+        (query && (rc = adjoint_bin_grow(e, m, (size_t)g.numCells)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const AggK ag{cfg->op, cfg->weight, cfg->channels, 0, 0};
+    slot_ids_fill(e);
+    if (query && (rc = adjoint_bin(e, k, devPoints, m))) return rc;
+    const uint32_t* perm = query ? (const uint32_t*)e->d_adjPerm.p : reinterpret_cast<const uint32_t*>(e->d_slotIds.p);
+    const uint32_t* binned = query ? (const uint32_t*)e->d_adjStart.p + k.numCells : nullptr;
+    const AdjRows R{query ? (const float4*)e->d_adjPts.p : (const float4*)e->d_sPV, query ? (const uint32_t*)e->d_adjStart.p : (const uint32_t*)e->d_cellStart, (uint32_t)rows};
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_adjoint_stage, dim3(blocks_for(rows * planes * C)), dim3(kBlock), 0, e->stream, perm, binned, reinterpret_cast<const uint32_t*>(devG),
+                           reinterpret_cast<uint32_t*>(e->d_aggStage.p), (uint32_t)rows, (int)(planes * C));
+        if (route)
+            hipLaunchKernelGGL(k_adjoint_stage, dim3(blocks_for(rows * C)), dim3(kBlock), 0, e->stream, perm, binned, reinterpret_cast<const uint32_t*>(devArg),
+                               e->d_adjArg.p, (uint32_t)rows, (int)C);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        const bool moments = planes == 4, delta = !query && (cfg->flags & SPH_AGGREGATE_DELTA) != 0;
+        // (DELTA with MOMENTS keeps the particle's own four planes beside the accumulators: 16 channels per pass need 130 VGPRs, 8 need 90)
+        const int chunk = (delta && moments) ? std::min(aggregate_chunk(cfg->channels), 8) : aggregate_chunk(cfg->channels);
+        const dim3 grid(blocks_for(n)), block(kBlock);
+        const float4 *pv = (const float4*)e->d_sPV, *own = (const float4*)e->d_sOwn;
+        const int32_t* ids = (const int32_t*)e->d_slotIds.p;
+        if (route) {
+            using Kernel = void (*)(SimK, NbK, AggK, const float4*, const int32_t*, const float4*, AdjRows, const int32_t*, const float*, float*);
+            auto pick = [&](auto ch) -> Kernel {
+                constexpr int CH = decltype(ch)::value;
+                return query ? (Kernel)k_aggregate_route<true, CH> : (Kernel)k_aggregate_route<false, CH>;
+            };
+            const Kernel kernel = chunk == 4 ? pick(std::integral_constant<int, 4>{}) : chunk == 8 ? pick(std::integral_constant<int, 8>{}) : pick(std::integral_constant<int, 16>{});
+            hipLaunchKernelGGL(kernel, grid, block, 0, e->stream, k, nb, ag, pv, ids, own, R, reinterpret_cast<const int32_t*>(e->d_adjArg.p), (const float*)e->d_aggStage.p, devOut);
+        } else {
+            using Kernel = void (*)(SimK, NbK, AggK, const float4*, const int32_t*, const float4*, AdjRows, const float*, float*);
+            auto pick = [&](auto ch) -> Kernel {
+                constexpr int CH = decltype(ch)::value;
+                if (query) return moments ? (Kernel)k_aggregate_adjoint<true, true, false, CH> : (Kernel)k_aggregate_adjoint<true, false, false, CH>;
+                return delta ? (Kernel)k_aggregate_adjoint<false, true, true, (CH > 8 ? 8 : CH)> : (Kernel)k_aggregate_adjoint<false, true, false, CH>;
+            };
+            const Kernel kernel = chunk == 4 ? pick(std::integral_constant<int, 4>{}) : chunk == 8 ? pick(std::integral_constant<int, 8>{}) : pick(std::integral_constant<int, 16>{});
+            hipLaunchKernelGGL(kernel, grid, block, 0, e->stream, k, nb, ag, pv, ids, own, R, (const float*)e->d_aggStage.p, devOut);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_adjoint_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devG, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return adjoint_run(e, false, false, cfg, nullptr, 0, nullptr, devG, devOut, info);
+}
+
+int sph_aggregate_adjoint_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devG, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return adjoint_run(e, true, false, cfg, reinterpret_cast<const float4*>(devPoints4), m, nullptr, devG, devOut, info);
+}
+
+int sph_aggregate_route_particles(SphEngine* e, const SphAggregateConfig* cfg, const int32_t* devArg, const float* devG, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return adjoint_run(e, false, true, cfg, nullptr, 0, devArg, devG, devOut, info);
+}
+
+int sph_aggregate_route_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const int32_t* devArg, const float* devG, float* devOut,
+                              SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return adjoint_run(e, true, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devArg, devG, devOut, info);
+}
+
+// Host memory in and out through engine scratch, as sph_aggregate_staged: the upload, the device call, the download, one synchronisation.
+int sph_aggregate_adjoint_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* g, float* out, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo grid;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, grid)) || (rc = adjoint_check(*cfg, grid.cellSize, query, false, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, gWords = rows * (size_t)aggregate_planes(*cfg) * C;
+    if (n && (!out || (rows && !g))) return fail(SPH_ERR_ARG, "null argument");
+    if (n && ((rc = e->d_adjIn.grow(e, gWords + 1)) || (rc = e->d_aggOut.grow(e, n * C)) || (query && (rc = e->d_sampleIn.grow(e, m + 1))))) return rc;
+    if (n && gWords) HIP_TRY(hipMemcpyAsync(e->d_adjIn.p, g, gWords * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && query && m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = adjoint_run(e, query, false, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, nullptr, e->d_adjIn.p, e->d_aggOut.p, info))) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(out, e->d_aggOut.p, n * C * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// MAX / MIN with the winners: aggregate_run's order of work; the values are always staged into slot order.
+static int arg_run(SphEngine* e, bool query, const SphAggregateConfig* cfg, const float4* devPoints, size_t m, const float* devValues, float* devOut,
+                   uint32_t* devCount, int32_t* devArg, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = adjoint_check(*cfg, g.cellSize, query, true, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels;
+    if (rows && n && (!devValues || !devOut || !devArg || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu floats exceed size_t", rows, C);
+    const size_t outBytes = rows * C * sizeof(float), valBytes = n * C * sizeof(float), cntBytes = devCount ? rows * sizeof(uint32_t) : 0;
+    if (ranges_overlap(devOut, outBytes, devValues, valBytes) || ranges_overlap(devCount, cntBytes, devValues, valBytes) || ranges_overlap(devArg, outBytes, devValues, valBytes) ||
+        ranges_overlap(devArg, outBytes, devOut, outBytes) || ranges_overlap(devArg, outBytes, devCount, cntBytes) || ranges_overlap(devOut, outBytes, devCount, cntBytes))
+        return fail(SPH_ERR_ARG, "the outputs overlap the values or each other");
+    SphAggregateInfo info{};
+    info.rows = rows; info.channels = cfg->channels; info.planes = 1; info.stencil = stencil; info.flags = cfg->flags; info.radius = cfg->radius;
+    *out = info;
+    if (!rows || !n) return SPH_OK;
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_aggStage.grow(e, n * C))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const AggK ag{cfg->op, cfg->weight, cfg->channels, 0, 0};
+    slot_ids_fill(e);
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * C)), dim3(kBlock), 0, e->stream, (const int32_t*)e->d_slotIds.p, devValues, e->d_aggStage.p, (uint32_t)n, cfg->channels);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        using Kernel = void (*)(SimK, NbK, AggK, const float4*, const uint32_t*, const int32_t*, const float4*, const float4*, size_t, const float*, float*, uint32_t*, int32_t*);
+        auto pick = [&](auto ch) -> Kernel {
+            constexpr int CH = decltype(ch)::value;
+            return query ? (Kernel)k_aggregate_arg<false, CH> : (Kernel)k_aggregate_arg<true, CH>;
+        };
+        const int chunk = aggregate_chunk(cfg->channels);
+        const Kernel kernel = chunk == 4 ? pick(std::integral_constant<int, 4>{}) : chunk == 8 ? pick(std::integral_constant<int, 8>{}) : pick(std::integral_constant<int, 16>{});
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(rows)), dim3(kBlock), 0, e->stream, k, nb, ag, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                           (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn, devPoints, rows, (const float*)e->d_aggStage.p, devOut, devCount, devArg);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_arg_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, int32_t* devArg,
+                                SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return arg_run(e, false, cfg, nullptr, 0, devValues, devOut, devCount, devArg, info);
+}
+
+int sph_aggregate_arg_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut, uint32_t* devCount,
+                            int32_t* devArg, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return arg_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devValues, devOut, devCount, devArg, info);
+}
+
+// What the three host twins open with: the params, the grid they give, the config.
+static int adjoint_host_open(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, bool query, size_t m, bool extremum,
+                             SimK& k, int* stencil) {
+    if (!params || !cfg || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    return adjoint_check(*cfg, g.cellSize, query, extremum, stencil);
+}
+
+int sph_aggregate_adjoint_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                               const float* g, float* out) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = adjoint_host_open(particles, n, params, cfg, query, m, false, k, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (!n) return SPH_OK;
+    if (!out || (rows && !g)) return fail(SPH_ERR_ARG, "null argument");
+    if (ranges_overlap(out, n * C * sizeof(float), g, rows * planes * C * sizeof(float)) || ranges_overlap(out, n * C * sizeof(float), points4, query ? m * 4 * sizeof(float) : 0))
+        return fail(SPH_ERR_ARG, "the output overlaps g or the points");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const bool delta = !query && (cfg->flags & SPH_AGGREGATE_DELTA) != 0, moments = planes == 4;
+    const sph::AdjHostRows table = query ? sph::AdjHostRows(k, points4, m) : sph::AdjHostRows(sph::HostGrid(k, particles, n));
+    std::vector<float> acc(C);
+    for (size_t r = 0; r < n; ++r) {
+        std::fill(acc.begin(), acc.end(), 0.0f);
+        const float* mine = delta ? g + r * planes * C : nullptr;
+        sph::adjoint_walk_host(k, stencil, table, particles, points4, r, R2, self, fluidOnly, [&](size_t row, float dx, float dy, float dz, float r2) {
+            const float* grow = g + row * planes * C;
+            const float w = sph::aggregate_weight(cfg->weight, R2, r2);
+            for (size_t c = 0; c < C; ++c) {
+                acc[c] = sph::aggregate_add(acc[c], w, sph::aggregate_adjoint_plane0(delta, grow[c], delta ? mine[c] : 0.0f));
+                if (!moments) continue;
+                acc[c] = sph::aggregate_add_moment(acc[c], w, dx, sph::aggregate_adjoint_moment(delta, grow[C + c], delta ? mine[C + c] : 0.0f));
+                acc[c] = sph::aggregate_add_moment(acc[c], w, dy, sph::aggregate_adjoint_moment(delta, grow[2 * C + c], delta ? mine[2 * C + c] : 0.0f));
+                acc[c] = sph::aggregate_add_moment(acc[c], w, dz, sph::aggregate_adjoint_moment(delta, grow[3 * C + c], delta ? mine[3 * C + c] : 0.0f));
+            }
+        });
+        memcpy(out + r * C, acc.data(), C * sizeof(float));
+    }
+    return SPH_OK;
+}
+
+int sph_aggregate_route_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                             const int32_t* arg, const float* g, float* out) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = adjoint_host_open(particles, n, params, cfg, query, m, true, k, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels;
+    if (!n) return SPH_OK;
+    if (!out || (rows && (!g || !arg))) return fail(SPH_ERR_ARG, "null argument");
+    if (ranges_overlap(out, n * C * sizeof(float), g, rows * C * sizeof(float)) || ranges_overlap(out, n * C * sizeof(float), arg, rows * C * sizeof(int32_t)) ||
+        ranges_overlap(out, n * C * sizeof(float), points4, query ? m * 4 * sizeof(float) : 0)) return fail(SPH_ERR_ARG, "the output overlaps g, arg or the points");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const sph::AdjHostRows table = query ? sph::AdjHostRows(k, points4, m) : sph::AdjHostRows(sph::HostGrid(k, particles, n));
+    std::vector<float> acc(C);
+    for (size_t r = 0; r < n; ++r) {
+        std::fill(acc.begin(), acc.end(), 0.0f);
+        sph::adjoint_walk_host(k, stencil, table, particles, points4, r, R2, self, fluidOnly, [&](size_t row, float, float, float, float) {
+            for (size_t c = 0; c < C; ++c)
+                if (arg[row * C + c] == (int32_t)r) acc[c] = acc[c] + g[row * C + c];
+        });
+        memcpy(out + r * C, acc.data(), C * sizeof(float));
+    }
+    return SPH_OK;
+}
+
+int sph_aggregate_arg_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                           const float* values, float* out, uint32_t* count, int32_t* arg) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = adjoint_host_open(particles, n, params, cfg, query, m, true, k, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels;
+    if (!rows || !n) return SPH_OK;
+    if (!values || !out || !arg) return fail(SPH_ERR_ARG, "null argument");
+    const size_t outBytes = rows * C * sizeof(float), valBytes = n * C * sizeof(float), cntBytes = count ? rows * sizeof(uint32_t) : 0;
+    if (ranges_overlap(out, outBytes, values, valBytes) || ranges_overlap(count, cntBytes, values, valBytes) || ranges_overlap(arg, outBytes, values, valBytes) ||
+        ranges_overlap(arg, outBytes, out, outBytes) || ranges_overlap(arg, outBytes, count, cntBytes) || ranges_overlap(out, outBytes, count, cntBytes))
+        return fail(SPH_ERR_ARG, "the outputs overlap the values or each other");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const bool delta = !query && (cfg->flags & SPH_AGGREGATE_DELTA) != 0, isMax = cfg->op == SPH_AGGREGATE_MAX;
+    const sph::HostGrid grid(k, particles, n);
+    std::vector<uint32_t> best(C), who(C);
+    for (size_t r = 0; r < rows; ++r) {
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+        std::fill(best.begin(), best.end(), isMax ? sph::kAggLowest : sph::kAggHighest);
+        std::fill(who.begin(), who.end(), sph::kAggNoArg);
+        uint32_t cnt = 0u;
+        const float* mine = values + (query ? 0 : r) * C;
+        if (walk) {
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
+                    const uint32_t id = grid.order[j];
+                    const SphParticle& cand = particles[id];
+                    float dx, dy, dz, r2;
+                    if (!sph::aggregate_accept(!query && j == grid.slotOf[r], self, x[0], x[1], x[2], cand.pos[0], cand.pos[1], cand.pos[2], R2, dx, dy, dz, r2)) continue;
+                    if (fluidOnly && cand.isGhost != 0) continue;
+                    const float* v = values + (size_t)id * C;
+                    cnt += 1u;
+                    for (size_t c = 0; c < C; ++c) sph::aggregate_arg_step(isMax, best[c], who[c], sph::aggregate_value(delta, v[c], mine[c]), id);
+                }
+            });
+        }
+        for (size_t c = 0; c < C; ++c) {
+            out[r * C + c] = sph::agg_unordered(best[c]);
+            arg[r * C + c] = who[c] == sph::kAggNoArg ? -1 : (int32_t)who[c];
         }
         if (count) count[r] = cnt;
     }

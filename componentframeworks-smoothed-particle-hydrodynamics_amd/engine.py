@@ -735,6 +735,16 @@ _ABI = {
     "sph_aggregate_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_staged": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp]),
+    "sph_aggregate_adjoint_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_adjoint_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_adjoint_staged": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_adjoint_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp]),
+    "sph_aggregate_arg_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_arg_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_arg_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp]),
+    "sph_aggregate_route_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_route_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_route_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -910,6 +920,26 @@ def _device_values(values, who):
     if isinstance(values, torch.Tensor) and _is_cuda_f32(values) and values.dim() == 2:
         return values
     return torch.from_numpy(_scalar_values(values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else values)).cuda()
+
+
+def _planes(grad, rows, moments, who):
+    """What a SUM's output looks like, as float32 numpy of (rows, C) or with moments (rows, 4, C); (rows,) counts as (rows, 1)."""
+    g = np.ascontiguousarray(grad, np.float32)
+    if g.ndim == 1 and not moments:
+        g = g.reshape(-1, 1)
+    if g.ndim != (3 if moments else 2) or len(g) != rows or (moments and g.shape[1] != 4):
+        raise SphError(f"{who}: grad of shape {g.shape} for {rows} rows{' of 4 planes' if moments else ''}")
+    return g
+
+
+def _device_planes(grad, rows, moments, who):
+    """The same as a torch device tensor: a contiguous float32 device tensor of the right shape is used in place, anything else uploaded."""
+    import torch
+    if isinstance(grad, torch.Tensor) and _is_cuda_f32(grad) and grad.dim() == (3 if moments else 2):
+        if int(grad.shape[0]) != rows or (moments and int(grad.shape[1]) != 4):
+            raise SphError(f"{who}: grad of shape {tuple(grad.shape)} for {rows} rows{' of 4 planes' if moments else ''}")
+        return grad
+    return torch.from_numpy(_planes(grad.detach().cpu().numpy() if isinstance(grad, torch.Tensor) else grad, rows, moments, who)).cuda()
 
 
 def _tensor_ptr(t):
@@ -1860,6 +1890,120 @@ class SPHFluidGPU:
             out = out.cpu().numpy()
             cnt = None if cnt is None else cnt.cpu().numpy().view(np.uint32)
         return (out, cnt) if counts else out
+
+    # -- the adjoint of the neighbourhood sums, extrema with winners, routing (include/sph_abi.h "the adjoint of the neighbourhood sums") --
+    def aggregate_adjoint(self, grad, radius=None, weight="one", self_=False, fluid_only=False, delta=False, moments=False, device: bool = False):
+        """The exact transpose of aggregate(op="sum") with the same arguments, applied to grad: (n, C), or (n, 4, C) with moments, what
+        aggregate() would return (numpy, or a contiguous float32 torch device tensor, which is used in place).  Returns (n, C) float32:
+        row k sums what the rows that accept particle k carry, in ascending sorted slot with the forward's own weights and offsets
+        (DESIGN.md section 3v); without moments these are the bytes of aggregate(grad, ...).  Streams as aggregate()."""
+        return self._adjoint(None, grad, self._radius(radius), "sum", weight, self_, fluid_only, delta, moments, None, device)
+
+    def query_aggregate_adjoint(self, points, point_values, radius, weight="one", fluid_only=False, moments=False, device: bool = False):
+        """The point -> particle transfer, the transpose of query_aggregate(op="sum"): point_values (m, C), or (m, 4, C) with moments, sit
+        on the (m, 3) or (m, 4) query points, and row k of the (n, C) result sums what the points within `radius` of particle k carry,
+        in ascending (clamped cell of the point, point index).  The points are binned into the engine's grid on the device, the particles
+        gather: no float atomics, the same bytes on every run.  A point with a non-finite coordinate contributes nothing.  Streams as
+        aggregate()."""
+        return self._adjoint(_device_points4(points, "query_aggregate_adjoint"), point_values, radius, "sum", weight, False, fluid_only, False, moments, None, device)
+
+    def aggregate_route(self, arg, grad, radius=None, op="max", self_=False, fluid_only=False, delta=False, device: bool = False):
+        """The routing of a gradient through aggregate(op="max" | "min"): arg (n, C) int32 from aggregate_arg() with the same arguments,
+        grad (n, C); row k of the (n, C) result sums grad[i][c] over the rows i with arg[i][c] == k, in the adjoint's row order."""
+        return self._adjoint(None, grad, self._radius(radius), op, "one", self_, fluid_only, delta, False, arg, device)
+
+    def query_aggregate_route(self, points, arg, grad, radius, op="max", fluid_only=False, device: bool = False):
+        """The same through query_aggregate(op="max" | "min"): arg and grad are (m, C), one row per query point."""
+        return self._adjoint(_device_points4(points, "query_aggregate_route"), grad, radius, op, "one", False, fluid_only, False, False, arg, device)
+
+    def _adjoint(self, dev_points, grad, radius, op, weight, self_, fluid_only, delta, moments, arg, device):
+        import torch
+        n = self.GetNumFluids()
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        g = _device_planes(grad, rows, moments, "aggregate_adjoint")
+        c = int(g.shape[-1])
+        cfg = _aggregate_cfg(radius, op, weight, c, self_, fluid_only, delta, moments)
+        a = None
+        if arg is not None:
+            a = arg if isinstance(arg, torch.Tensor) and arg.is_cuda and arg.dtype == torch.int32 and arg.is_contiguous() else \
+                torch.from_numpy(np.ascontiguousarray(arg.detach().cpu().numpy() if isinstance(arg, torch.Tensor) else arg, np.int32)).cuda()
+            if tuple(a.shape) != (rows, c):
+                raise SphError(f"aggregate_route: arg of shape {tuple(a.shape)} for grad of shape {(rows, c)}")
+        out = torch.empty((n, c), dtype=torch.float32, device="cuda")
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        L, h, p = self._L, self._h, C.byref(cfg)
+        if a is None and dev_points is None:
+            _check(L.sph_aggregate_adjoint_particles(h, p, _tensor_ptr(g), _tensor_ptr(out), C.byref(info)))
+        elif a is None:
+            _check(L.sph_aggregate_adjoint_query(h, p, _tensor_ptr(dev_points), rows, _tensor_ptr(g), _tensor_ptr(out), C.byref(info)))
+        elif dev_points is None:
+            _check(L.sph_aggregate_route_particles(h, p, _tensor_ptr(a), _tensor_ptr(g), _tensor_ptr(out), C.byref(info)))
+        else:
+            _check(L.sph_aggregate_route_query(h, p, _tensor_ptr(dev_points), rows, _tensor_ptr(a), _tensor_ptr(g), _tensor_ptr(out), C.byref(info)))
+        self.sync()
+        return out if device else out.cpu().numpy()
+
+    def aggregate_autograd(self, values, radius=None, op="sum", weight="one", self_=False, fluid_only=False, delta=False, moments=False,
+                           check_state: bool = True):
+        """aggregate() as a torch.autograd.Function: values is a float32 torch device tensor of (n, C) that may require grad, the result
+        has the bytes of aggregate(..., device=True) and carries a graph whose backward is the engine's adjoint (sum: aggregate_adjoint;
+        mean: the adjoint of grad / W; max / min: aggregate_route through the winners of aggregate_arg), so no edge list is built.
+        Differentiable in values only (the positions are the engine's state, not a tensor) and once differentiable: a backward of the
+        backward raises.  check_state: the forward stores state_digest(["particles"]) and the backward raises SphError if it has
+        changed, because a dispatch in between would silently give the adjoint of another neighbour relation; each of the two reads
+        checksums the particle section on the device and synchronises (about the cost of one download-free pass over the records).
+        False skips both.  See autograd.py for the formulas."""
+        from .autograd import EngineAggregateBackend, aggregate_autograd
+        return aggregate_autograd(EngineAggregateBackend(self), None, values, self._radius(radius), op, weight, self_, fluid_only, delta, moments, check_state)
+
+    def query_aggregate_autograd(self, points, values, radius, op="sum", weight="one", fluid_only=False, moments=False, check_state: bool = True):
+        """query_aggregate() as a torch.autograd.Function of values ((n, C) on the device); the result is (m, C) or (m, 4, C).  The backward
+        is query_aggregate_adjoint / query_aggregate_route.  Everything else as aggregate_autograd()."""
+        from .autograd import EngineAggregateBackend, aggregate_autograd
+        return aggregate_autograd(EngineAggregateBackend(self), _device_points4(points, "query_aggregate_autograd"), values, radius, op, weight, False,
+                                  fluid_only, False, moments, check_state)
+
+    def aggregate_arg(self, values, radius=None, op="max", self_=False, fluid_only=False, delta=False, counts=False, device: bool = False):
+        """aggregate(op="max" | "min") and who won: (out, arg) or with counts=True (out, counts, arg).  out and counts are the bytes of
+        aggregate(); arg (n, C) int32 is the smallest particle id among the accepted candidates whose value is not NaN and equals the
+        extremum as an ordered key (-0 below +0), -1 for an empty row or a row of NaNs.  Streams as aggregate()."""
+        return self._aggregate_arg(None, values, self._radius(radius), op, self_, fluid_only, delta, counts, device)
+
+    def query_aggregate_arg(self, points, values, radius, op="max", fluid_only=False, counts=False, device: bool = False):
+        """The same around query points: arg is (m, C)."""
+        return self._aggregate_arg(_device_points4(points, "query_aggregate_arg"), values, radius, op, False, fluid_only, False, counts, device)
+
+    def _aggregate_arg(self, dev_points, values, radius, op, self_, fluid_only, delta, counts, device):
+        import torch
+        vals = _device_values(values, "aggregate_arg")
+        n, c = int(vals.shape[0]), int(vals.shape[1])
+        if n != self.GetNumFluids():
+            raise SphError(f"aggregate_arg: {n} rows of values for {self.GetNumFluids()} particles")
+        cfg = _aggregate_cfg(radius, op, "one", c, self_, fluid_only, delta, False)
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        written = rows and n                                                          # (nothing is written otherwise: sph_abi.h)
+        make = torch.empty if written else torch.zeros
+        out = make((rows, c), dtype=torch.float32, device="cuda")
+        arg = make((rows, c), dtype=torch.int32, device="cuda")
+        cnt = make(rows, dtype=torch.int32, device="cuda") if counts else None
+        if not written:
+            arg.fill_(-1)
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        p_cnt = None if cnt is None else _tensor_ptr(cnt)
+        if dev_points is None:
+            _check(self._L.sph_aggregate_arg_particles(self._h, C.byref(cfg), _tensor_ptr(vals), _tensor_ptr(out), p_cnt, _tensor_ptr(arg), C.byref(info)))
+        else:
+            _check(self._L.sph_aggregate_arg_query(self._h, C.byref(cfg), _tensor_ptr(dev_points), rows, _tensor_ptr(vals), _tensor_ptr(out), p_cnt,
+                                                   _tensor_ptr(arg), C.byref(info)))
+        self.sync()
+        if not device:
+            out, arg = out.cpu().numpy(), arg.cpu().numpy()
+            cnt = None if cnt is None else cnt.cpu().numpy().view(np.uint32)
+        return (out, cnt, arg) if counts else (out, arg)
 
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
@@ -2816,6 +2960,51 @@ def aggregate_host(records, params, values, radius, points=None, op="sum", weigh
     _check(load_library().sph_aggregate_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(out),
                                              _ptr_or_none(cnt) if counts else None))
     return (out, cnt) if counts else out
+
+
+def aggregate_adjoint_host(records, params, grad, radius, points=None, weight="one", self_=False, fluid_only=False, delta=False, moments=False):
+    """sph_aggregate_adjoint_host: the (n, C) result of SPHFluidGPU.aggregate_adjoint (points None) or query_aggregate_adjoint on host
+    records and host grad, computed on the CPU by the same per-term functions in the same order: the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_adjoint_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    g = _planes(grad, rows, moments, "aggregate_adjoint_host")
+    c = int(g.shape[-1])
+    cfg = _aggregate_cfg(radius, "sum", weight, c, self_, fluid_only, delta, moments)
+    out = np.zeros((head[1], c), np.float32)
+    _check(load_library().sph_aggregate_adjoint_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(g), _ptr_or_none(out)))
+    return out
+
+
+def aggregate_arg_host(records, params, values, radius, points=None, op="max", self_=False, fluid_only=False, delta=False, counts=False):
+    """sph_aggregate_arg_host: (out, arg), or with counts=True (out, counts, arg), of SPHFluidGPU.aggregate_arg (points None) or
+    query_aggregate_arg on host records: the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_arg_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    vals = _scalar_values(values, head[1])
+    c = int(vals.shape[1])
+    cfg = _aggregate_cfg(radius, op, "one", c, self_, fluid_only, delta, False)
+    out = np.zeros((rows, c), np.float32)
+    arg = np.full((rows, c), -1, np.int32)
+    cnt = np.zeros(rows, np.uint32)
+    _check(load_library().sph_aggregate_arg_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(out),
+                                                 _ptr_or_none(cnt) if counts else None, _ptr_or_none(arg)))
+    return (out, cnt, arg) if counts else (out, arg)
+
+
+def aggregate_route_host(records, params, arg, grad, radius, points=None, op="max", self_=False, fluid_only=False, delta=False):
+    """sph_aggregate_route_host: the (n, C) result of SPHFluidGPU.aggregate_route (points None) or query_aggregate_route on host records:
+    the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_route_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    g = _planes(grad, rows, False, "aggregate_route_host")
+    c = int(g.shape[1])
+    a = np.ascontiguousarray(arg, np.int32)
+    if a.shape != (rows, c):
+        raise SphError(f"aggregate_route_host: arg of shape {a.shape} for grad of shape {(rows, c)}")
+    cfg = _aggregate_cfg(radius, op, "one", c, self_, fluid_only, delta, False)
+    out = np.zeros((head[1], c), np.float32)
+    _check(load_library().sph_aggregate_route_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(a), _ptr_or_none(g), _ptr_or_none(out)))
+    return out
 
 
 def aniso_lattice_host(records, params, origin, spacing, dims, **cfg):

@@ -358,6 +358,46 @@ public:
         if (counts) counts->assign(rows, 0u);
         return !Check(sph_aggregate_staged(engine, &cfg, points4, m, values.data(), out.data(), counts ? counts->data() : nullptr, &info), "sph_aggregate_staged");
     }
+    // The adjoint of those sums (sph_abi.h "the adjoint of the neighbourhood sums"), cfg.op SUM: devG[rows][planes]
+    // [channels] is what Aggregate / QueryAggregate would write, devOut[n][channels] by particle id what each particle sums over the rows
+    // that accept it.  QueryAggregateAdjoint is the point -> particle transfer.  DEVICE memory, no synchronisation, as Aggregate.
+    bool AggregateAdjoint(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devG, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_adjoint_particles(engine, &cfg, devG, devOut, &out), "sph_aggregate_adjoint_particles");
+    }
+    bool QueryAggregateAdjoint(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devPoints4, size_t m, const float* devG, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_adjoint_query(engine, &cfg, devPoints4, m, devG, devOut, &out), "sph_aggregate_adjoint_query");
+    }
+    // The same for HOST arrays (g rows * planes * channels floats; points4 m * 4 floats or null for particle targets): out is sized to
+    // n * channels.  Synchronises.
+    bool AggregateAdjoint(SphAggregateInfo& info, const SphAggregateConfig& cfg, const std::vector<float>& g, std::vector<float>& out,
+                          const float* points4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine), rows = points4 ? m : n, planes = (cfg.flags & SPH_AGGREGATE_MOMENTS) ? 4 : 1;
+        if (cfg.channels < 1 || g.size() != rows * planes * size_t(cfg.channels)) return !Check(SPH_ERR_ARG, "AggregateAdjoint: g.size() is not rows * planes * channels");
+        out.assign(n * size_t(cfg.channels), 0.0f);
+        return !Check(sph_aggregate_adjoint_staged(engine, &cfg, points4, m, g.data(), out.data(), &info), "sph_aggregate_adjoint_staged");
+    }
+    // MAX / MIN with the winners (devArg int32[rows][channels]: the smallest id that holds the extremum, -1 for none; devPoints4 null:
+    // particle targets) and the routing of devG[rows][channels] through them into devOut[n][channels].  DEVICE memory, no synchronisation.
+    bool AggregateArg(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devValues, float* devOut, uint32_t* devCount, int32_t* devArg,
+                      const float* devPoints4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        if (devPoints4) return !Check(sph_aggregate_arg_query(engine, &cfg, devPoints4, m, devValues, devOut, devCount, devArg, &out), "sph_aggregate_arg_query");
+        return !Check(sph_aggregate_arg_particles(engine, &cfg, devValues, devOut, devCount, devArg, &out), "sph_aggregate_arg_particles");
+    }
+    bool AggregateRoute(SphAggregateInfo& out, const SphAggregateConfig& cfg, const int32_t* devArg, const float* devG, float* devOut,
+                        const float* devPoints4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        if (devPoints4) return !Check(sph_aggregate_route_query(engine, &cfg, devPoints4, m, devArg, devG, devOut, &out), "sph_aggregate_route_query");
+        return !Check(sph_aggregate_route_particles(engine, &cfg, devArg, devG, devOut, &out), "sph_aggregate_route_particles");
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

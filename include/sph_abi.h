@@ -62,6 +62,7 @@ extern "C" {
 /* (still 4, additions only: SphShell, SphShellConfig, SphShellInfo, SPH_SHELL_FLUID_ONLY, SPH_SHELL_MEMBER, SPH_SHELL_ISOLATED, sph_shell_default / _build / _query / _info / _device / _download / _host, SPH_OPT_SHELL_TIMED -- free-surface particles) */
 /* (still 4, additions only: SphStateInfo, SphStateDigest, SPH_STATE_*, sph_state_size / _save / _load / _peek / _digest / _checksum_host -- checkpoints) */
 /* (still 4, additions only: SphAggregateConfig, SphAggregateInfo, SPH_AGGREGATE_*, sph_aggregate_default / _particles / _query / _staged / _host, SPH_OPT_AGGREGATE_VARIANT -- fused neighbourhood reductions of caller tensors) */
+/* (still 4, additions only: sph_aggregate_adjoint_particles / _query / _staged / _host, sph_aggregate_arg_particles / _query / _host, sph_aggregate_route_particles / _query / _host -- the adjoint of the neighbourhood sums, extrema with their winners, routing through them) */
 /* (still 4, additions only: SPH_SLAB_FLAG_* -- names of the six bits of the z-slab exchange's flag word, values as before) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
@@ -1420,6 +1421,66 @@ int sph_aggregate_staged(SphEngine* e, const SphAggregateConfig* cfg, const floa
  * points4 null: particle targets.  count may be null. */
 int sph_aggregate_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
                        const float* values, float* out, uint32_t* count);
+
+/* ---- the adjoint of the neighbourhood sums, and extrema that say who won (no reference counterpart) -------------
+ * Every SUM above is a linear map A of values whose weights depend on the engine's positions alone; these calls apply its exact
+ * transpose.  Config: SphAggregateConfig under the rules above, op SUM.  Input g float32[rows][planes][C], what the forward's out would
+ * be (rows = n, or m for query targets; planes 4 with MOMENTS); output out float32[n][C] by particle id.  Every row of out is written,
+ * +0 where nothing contributes.  Queries like the forward: no result is kept, no engine state, nothing in a checkpoint.
+ * Definition.  Particle k sums over the rows i that accept k in the forward, with the forward's own bits of d = x_k - x_i (row i's
+ * offset to candidate k, the same operand order), r2 and w.  Order of the rows: particle targets ascending sorted slot (the forward's
+ * candidate order); query targets ascending (clamped cell index of the point, point index).  One fp32 accumulator per channel; per row
+ * and channel, in this order, every product and sum rounded on its own:
+ *   without DELTA   acc = acc + w * g[i][0][c];                          with MOMENTS then, a = x, y, z: acc = acc + (w * d_a) * g[i][1+a][c]
+ *   with DELTA      acc = acc + w * (g[i][0][c] - g[k][0][c]);           with MOMENTS then: acc = acc + (w * d_a) * (g[i][1+a][c] + g[k][1+a][c])
+ * (the moment planes under DELTA: the derivative of sum_j (w d_a)(x_j - x_i) with respect to x_k; the two occurrences of x_k combine
+ * because d is antisymmetric and w * d negates exactly).  The forward's rules hold transposed: under SELF the own slot enters by slot
+ * identity with d = 0; under FLUID_ONLY a ghost particle's row of out is zero and a ghost target's row of g contributes nothing; a
+ * particle with a non-finite position has a zero row apart from its own slot under SELF; a query point with a non-finite coordinate
+ * contributes nothing.
+ * Why the rows found are the transpose: the stencil is a box of cells, symmetric per axis, and both sides use clamped cells, so "the
+ * row's cell lies in my stencil" is exactly "my cell lies in the row's stencil"; acceptance itself (r2 < R2, slot identity, the ghost
+ * rules) reads the same bits from either side.
+ * Identity: for particle targets without MOMENTS the call gives, byte for byte, sph_aggregate_particles(cfg, g), with and without
+ * DELTA, SELF and FLUID_ONLY (the relation and the weights are symmetric); the library runs that kernel.  SPH_OPT_AGGREGATE_VARIANT
+ * steers it there and nothing else here; the bytes do not move.
+ * Query targets bin the m points into the engine's grid by their clamped cell, in (cell, point index) order without the non-finite
+ * ones (a counting sort whose arrival order a ranking pass removes), stage g into that order, and one particle per lane walks the
+ * forward's stencil around its own clamped cell over the points' cell table.  No float atomics; stores are lane-owned.  The same
+ * bytes on every run, and the bytes of sph_aggregate_adjoint_host, which runs the same per-term functions in the same order.
+ * Streams, timing class and SPH_ERR_STATE as the forward.  SPH_ERR_ARG: the forward's cases, and op != SUM, a null g or out, out
+ * overlapping g or the points as address ranges.  m = 0: out is zeroed.  n = 0: success, nothing is written.
+ * SphAggregateInfo: rows = n (the rows of out), planes those of g. */
+int sph_aggregate_adjoint_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devG, float* devOut, SphAggregateInfo* info);
+/* devPoints4: m query points (x, y, z, .) in device memory, never written; devG float32[m][planes][channels]. */
+int sph_aggregate_adjoint_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devG, float* devOut,
+                                SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets): g, and the points, are uploaded into engine scratch,
+ * out is copied back; synchronises. */
+int sph_aggregate_adjoint_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* g, float* out,
+                                 SphAggregateInfo* info);
+/* Host-only, no device: the same bytes.  points4 null: particle targets. */
+int sph_aggregate_adjoint_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                               const float* g, float* out);
+/* MAX / MIN (any other op: SPH_ERR_ARG) with one more output, arg int32[rows][C]: out and count are byte for byte those of
+ * sph_aggregate_particles / _query; arg[i][c] is the smallest particle id among the accepted candidates whose reduced value is not NaN
+ * and whose ordered key equals the winning key, -1 for an empty row or a row of NaNs.  Coincident particles and lattices therefore have
+ * one answer, whatever the order of the walk.  Further SPH_ERR_ARG: a null arg, outputs that overlap the values or each other. */
+int sph_aggregate_arg_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, int32_t* devArg,
+                                SphAggregateInfo* info);
+int sph_aggregate_arg_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                            uint32_t* devCount, int32_t* devArg, SphAggregateInfo* info);
+int sph_aggregate_arg_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                           const float* values, float* out, uint32_t* count, int32_t* arg);
+/* The routing of a gradient through MAX / MIN (config as for arg): out[k][c] is the sum, in the adjoint's row order, of g[i][c] over the
+ * rows i that accept k with arg[i][c] == k; the step is acc = acc + g.  arg int32[rows][C] and g float32[rows][C] are never written; out
+ * float32[n][C], every row written.  A winner is always an accepted candidate, so the adjoint's walk finds every such row: a gather,
+ * no scatter.  Refusals as the adjoint's (op MAX or MIN), and a null arg or out overlapping arg. */
+int sph_aggregate_route_particles(SphEngine* e, const SphAggregateConfig* cfg, const int32_t* devArg, const float* devG, float* devOut, SphAggregateInfo* info);
+int sph_aggregate_route_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const int32_t* devArg, const float* devG,
+                              float* devOut, SphAggregateInfo* info);
+int sph_aggregate_route_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                             const int32_t* arg, const float* g, float* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
