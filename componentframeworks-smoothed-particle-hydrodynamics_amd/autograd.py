@@ -9,6 +9,14 @@ the host twins implement on the CPU (HostAggregateBackend), so that they can be 
   mean       grad = adjoint(g / W), 0 where W == 0; W is the counts output for weight "one" and a one-channel SUM of ones otherwise
              (acc = acc + w * 1 in the forward's order: MEAN's own W bits)
   max / min  grad = route(arg, g); with delta additionally -g[i][c] goes to row i wherever arg[i][c] >= 0
+
+continuous_conv stands on two more backend calls, basis and basis_adjoint.  With A the basis sums of a block of
+input channels, (rows, B, cw), and F the block's filters as a (B * cw, Cout) matrix:
+
+  forward    out = sum over the blocks of A.reshape(rows, B * cw) @ F;  with normalize out / W, 0 where W == 0 (MEAN's own W, as above)
+  backward   g' = g (g / W with normalize);  grad_filters = A^T @ g' per block, A recomputed rather than saved;
+             grad_x = basis_adjoint((g' @ F^T).reshape(rows, B, cw)) per block
+The basis tensors and the adjoint have fixed bytes; the two matrix products are torch's, and no byte claim is made for them.
 """
 from __future__ import annotations
 
@@ -16,9 +24,10 @@ import zlib
 
 import numpy as np
 
-from .engine import (SphError, aggregate_adjoint_host, aggregate_arg_host, aggregate_host, aggregate_route_host)
+from .engine import (SPH_AGGREGATE_MAX_CHANNELS, SphError, aggregate_adjoint_host, aggregate_arg_host, aggregate_basis_adjoint_host, aggregate_basis_host,
+                     aggregate_host, aggregate_route_host)
 
-__all__ = ["EngineAggregateBackend", "HostAggregateBackend", "aggregate_autograd"]
+__all__ = ["EngineAggregateBackend", "HostAggregateBackend", "aggregate_autograd", "continuous_conv"]
 
 
 class EngineAggregateBackend:
@@ -50,6 +59,16 @@ class EngineAggregateBackend:
         if points is None:
             return self.f.aggregate_route(arg, grad, radius, op=op, self_=self_, fluid_only=fluid_only, delta=delta, device=True)
         return self.f.query_aggregate_route(points, arg, grad, radius, op=op, fluid_only=fluid_only, device=True)
+
+    def basis(self, points, x, radius, size, weight, self_, fluid_only):
+        if points is None:
+            return self.f.aggregate_basis(x, radius, size=size, weight=weight, self_=self_, fluid_only=fluid_only, device=True)
+        return self.f.query_aggregate_basis(points, x, radius, size=size, weight=weight, fluid_only=fluid_only, device=True)
+
+    def basis_adjoint(self, points, h, radius, size, weight, self_, fluid_only):
+        if points is None:
+            return self.f.aggregate_basis_adjoint(h, radius, size=size, weight=weight, self_=self_, fluid_only=fluid_only, device=True)
+        return self.f.query_aggregate_basis_adjoint(points, h, radius, size=size, weight=weight, fluid_only=fluid_only, device=True)
 
 
 class HostAggregateBackend:
@@ -86,6 +105,14 @@ class HostAggregateBackend:
     def route(self, points, arg, grad, radius, op, self_, fluid_only, delta):
         return self._t(aggregate_route_host(self.records, self.params, self._np(arg), self._np(grad), radius, points=points, op=op, self_=self_,
                                             fluid_only=fluid_only, delta=delta))
+
+    def basis(self, points, x, radius, size, weight, self_, fluid_only):
+        return self._t(aggregate_basis_host(self.records, self.params, self._np(x), radius, points=points, size=size, weight=weight, self_=self_,
+                                            fluid_only=fluid_only))
+
+    def basis_adjoint(self, points, h, radius, size, weight, self_, fluid_only):
+        return self._t(aggregate_basis_adjoint_host(self.records, self.params, self._np(h), radius, points=points, size=size, weight=weight, self_=self_,
+                                                    fluid_only=fluid_only))
 
 
 def _function():
@@ -166,3 +193,98 @@ def aggregate_autograd(backend, points, values, radius, op="sum", weight="one", 
     if points is not None and (self_ or delta):
         raise SphError("aggregate_autograd: self_ and delta apply to particle targets only")
     return _function().apply(values, backend, points, float(radius), op, weight, bool(self_), bool(fluid_only), bool(delta), bool(moments), bool(check_state))
+
+
+def _conv_blocks(rows, planes, cin, max_basis_bytes):
+    """The blocks [c0, c1) of input channels: the widest of at most SPH_AGGREGATE_MAX_CHANNELS channels whose basis tensor of
+    rows * planes * width floats stays under max_basis_bytes (one channel where even that does not)."""
+    width = max(1, min(cin, SPH_AGGREGATE_MAX_CHANNELS, int(max_basis_bytes) // max(1, rows * planes * 4)))
+    return [(c0, min(cin, c0 + width)) for c0 in range(0, cin, width)]
+
+
+def _conv_function():
+    """continuous_conv's torch.autograd.Function, made on first use as _function()."""
+    global _CONV
+    if _CONV is not None:
+        return _CONV
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def weight_sum(backend, points, n, like, radius, weight, self_, fluid_only):
+        ones = torch.ones((n, 1), dtype=torch.float32, device=like.device)
+        return backend.forward(points, ones, radius, "sum", weight, self_, fluid_only, False, False, False).reshape(-1)
+
+    def divide(t, W):
+        ok = (W != 0)[:, None]
+        return torch.where(ok, t / torch.where(ok, W[:, None], torch.ones_like(W[:, None])), torch.zeros_like(t))
+
+    class ContinuousConvFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, filters, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks):
+            ctx.backend, ctx.points, ctx.radius, ctx.blocks = backend, points, radius, blocks
+            ctx.cfg = (weight, self_, fluid_only, normalize)
+            ctx.digest = backend.state() if check_state else None
+            ctx.check_state = check_state
+            xd, fd = x.detach(), filters.detach()
+            K, cout = int(fd.shape[0]), int(fd.shape[4])
+            out = None
+            for c0, c1 in blocks:
+                A = backend.basis(points, xd[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
+                part = A.reshape(A.shape[0], -1) @ fd[:, :, :, c0:c1, :].reshape(-1, cout)
+                out = part if out is None else out + part
+            W = weight_sum(backend, points, xd.shape[0], xd, radius, weight, self_, fluid_only) if normalize else xd.new_zeros(0)
+            ctx.save_for_backward(xd, fd, W)
+            return divide(out, W) if normalize else out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            weight, self_, fluid_only, normalize = ctx.cfg
+            backend, points, radius = ctx.backend, ctx.points, ctx.radius
+            if ctx.check_state and backend.state() != ctx.digest:
+                raise SphError("continuous_conv: the particle state changed between forward and backward (a dispatch, an upload or an impulse): "
+                               "the adjoint would be that of another neighbour relation")
+            x, filters, W = ctx.saved_tensors
+            K, cout = int(filters.shape[0]), int(filters.shape[4])
+            g = divide(g, W) if normalize else g
+            g = g.contiguous()
+            need_x, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            grad_x = torch.zeros_like(x) if need_x else None
+            grad_f = torch.zeros_like(filters) if need_f else None
+            for c0, c1 in ctx.blocks:
+                fblock = filters[:, :, :, c0:c1, :].reshape(-1, cout)
+                if need_f:
+                    A = backend.basis(points, x[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
+                    grad_f[:, :, :, c0:c1, :] = (A.reshape(A.shape[0], -1).t() @ g).reshape(K, K, K, c1 - c0, cout)
+                if need_x:
+                    h = (g @ fblock.t()).reshape(g.shape[0], K ** 3, c1 - c0).contiguous()
+                    grad_x[:, c0:c1] = backend.basis_adjoint(points, h, radius, K, weight, self_, fluid_only)
+            return (grad_x, grad_f) + (None,) * 9
+
+    _CONV = ContinuousConvFunction
+    return _CONV
+
+
+_CONV = None
+
+
+def continuous_conv(backend, points, x, filters, radius, weight="poly6", self_=True, fluid_only=False, normalize=False, check_state=True,
+                    max_basis_bytes=2 ** 31):
+    """The continuous convolution of `backend` (points None: particle targets) as a differentiable function of x, float32 (n, Cin), and
+    filters, float32 (K, K, K, Cin, Cout) with axes (z, y, x) and K in 2 .. 4, both on the backend's device: (rows, Cout).  Once
+    differentiable in both.  The module docstring has the formulas; SPHFluidGPU.continuous_conv the arguments."""
+    import torch
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise SphError("continuous_conv: x must be a float32 torch tensor of shape (n, Cin)")
+    if not isinstance(filters, torch.Tensor) or filters.dtype != torch.float32 or filters.dim() != 5 or filters.device != x.device:
+        raise SphError("continuous_conv: filters must be a float32 torch tensor of shape (K, K, K, Cin, Cout) on the device of x")
+    K, cin, cout = int(filters.shape[0]), int(filters.shape[3]), int(filters.shape[4])
+    if tuple(filters.shape[:3]) != (K, K, K) or K < 2 or K > 4 or cin != int(x.shape[1]) or cin < 1 or cout < 1:
+        raise SphError(f"continuous_conv: filters of shape {tuple(filters.shape)} for x of shape {tuple(x.shape)} (K, K, K, Cin, Cout with K in 2 .. 4)")
+    if weight not in ("one", "poly6"):
+        raise SphError(f"continuous_conv: weight {weight!r}")
+    if points is not None and self_:
+        raise SphError("continuous_conv: self_ applies to particle targets only")
+    rows = int(x.shape[0]) if points is None else int(points.shape[0])
+    blocks = _conv_blocks(rows, K ** 3, cin, max_basis_bytes)
+    return _conv_function().apply(x, filters, backend, points, float(radius), weight, bool(self_), bool(fluid_only), bool(normalize), bool(check_state), blocks)

@@ -19,6 +19,7 @@
 // channel index stays below C, so the range guards (row < rows, j < n, c < C) never fire; they stay so that no load or store can
 // leave its array.
 #pragma once
+#define SPH_AGGREGATE_H 1     // (sph_conv.h, which is built on this header, checks that it came first)
 #include <math.h>
 #include <string.h>
 

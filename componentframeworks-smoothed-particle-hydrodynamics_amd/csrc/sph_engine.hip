@@ -28,6 +28,7 @@
 #include "sph_components.h"
 #include "sph_knn.h"
 #include "sph_aggregate.h"
+#include "sph_conv.h"
 #include "sph_shell.h"
 #include "sph_aniso.h"
 #include "sph_rays.h"
@@ -5229,6 +5230,289 @@ int sph_aggregate_arg_host(const SphParticle* particles, size_t n, const SphPara
             arg[r * C + c] = who[c] == sph::kAggNoArg ? -1 : (int32_t)who[c];
         }
         if (count) count[r] = cnt;
+    }
+    return SPH_OK;
+}
+
+// ---- filter-grid basis sums and their adjoint (sph_conv.h) ----------------------
+static_assert(sizeof(SphBasisConfig) == 32, "SphBasisConfig is 32 bytes");
+static_assert(SPH_BASIS_GRID == sph::kBasisGrid, "sph_conv.h mirrors SPH_BASIS_*");
+
+void sph_aggregate_basis_default(SphBasisConfig* cfg) {
+    if (!cfg) return;
+    *cfg = SphBasisConfig{};
+    cfg->weight = SPH_AGGREGATE_WEIGHT_POLY6;
+    cfg->channels = 1;
+    cfg->kind = SPH_BASIS_GRID;
+    cfg->size = 4;
+}
+
+// The config as an argument: the stencil half-width through *stencil.
+static int basis_check(const SphBasisConfig& c, float cellSize, bool query, int* stencil) {
+    if (c.weight < SPH_AGGREGATE_WEIGHT_ONE || c.weight > SPH_AGGREGATE_WEIGHT_POLY6) return fail(SPH_ERR_ARG, "unknown basis weight %d", c.weight);
+    if (c.flags & (SPH_AGGREGATE_DELTA | SPH_AGGREGATE_MOMENTS)) return fail(SPH_ERR_ARG, "SPH_AGGREGATE_DELTA / _MOMENTS do not apply to basis sums (flags %d)", c.flags);
+    if (c.flags & ~(SPH_AGGREGATE_SELF | SPH_AGGREGATE_FLUID_ONLY)) return fail(SPH_ERR_ARG, "unknown basis flags %d", c.flags);
+    if (c.pad[0] || c.pad[1]) return fail(SPH_ERR_ARG, "the padding of SphBasisConfig must be zero");
+    if (c.channels < 1 || c.channels > SPH_AGGREGATE_MAX_CHANNELS) return fail(SPH_ERR_ARG, "%d channels (1 .. %d)", c.channels, (int)SPH_AGGREGATE_MAX_CHANNELS);
+    if (c.kind != SPH_BASIS_GRID) return fail(SPH_ERR_ARG, "unknown basis kind %d", c.kind);
+    if (c.size < sph::kBasisMinSize || c.size > sph::kBasisMaxSize) return fail(SPH_ERR_ARG, "filter grid size %d (%d .. %d)", c.size, sph::kBasisMinSize, sph::kBasisMaxSize);
+    if (query && (c.flags & SPH_AGGREGATE_SELF)) return fail(SPH_ERR_ARG, "SPH_AGGREGATE_SELF applies to particle targets only");
+    return radius_stencil(c.radius, cellSize, stencil);
+}
+
+static size_t basis_planes(const SphBasisConfig& c) { return (size_t)(c.size * c.size * c.size); }
+static sph::BasisK make_basisk(const SphBasisConfig& c) {
+    return sph::BasisK{c.radius, 0.5f * (float)(c.size - 1), c.weight, c.channels, c.size, sph::basis_group_shift(c.channels)};
+}
+static void basis_info(const SphBasisConfig& c, size_t rows, int stencil, SphAggregateInfo* out) {
+    SphAggregateInfo info{};
+    info.rows = rows; info.channels = c.channels; info.planes = (int32_t)basis_planes(c); info.stencil = stencil; info.flags = c.flags; info.radius = c.radius;
+    *out = info;
+}
+
+// Grid of the current state, ids, the stage, the walk.  No synchronisation: nothing is read back.
+static int basis_run(SphEngine* e, bool query, const SphBasisConfig* cfg, const float4* devPoints, size_t m, const float* devValues, float* devOut,
+                     uint32_t* devCount, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = basis_check(*cfg, g.cellSize, query, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (rows && n && (!devValues || !devOut || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t outBytes = rows * B * C * sizeof(float), valBytes = n * C * sizeof(float);
+    if (ranges_overlap(devOut, outBytes, devValues, valBytes) || ranges_overlap(devCount, devCount ? rows * sizeof(uint32_t) : 0, devValues, valBytes))
+        return fail(SPH_ERR_ARG, "the output overlaps the values");
+    basis_info(*cfg, rows, stencil, out);
+    if (!rows || !n) return SPH_OK;
+    if ((rc = e->d_slotIds.grow(e, n)) || (rc = e->d_aggStage.grow(e, n * C))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const BasisK bk = make_basisk(*cfg);
+    slot_ids_fill(e);
+    {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * C)), dim3(kBlock), 0, e->stream, (const int32_t*)e->d_slotIds.p, devValues, e->d_aggStage.p, (uint32_t)n, cfg->channels);
+    }
+    {
+        Timed t(e, SPH_K_OTHER);
+        const int block = basis_block(cfg->size);
+        const size_t lds = B * (size_t)block * sizeof(float);
+        auto kernel = query ? k_aggregate_basis<false> : k_aggregate_basis<true>;
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(rows << bk.gshift, block)), dim3(block), lds, e->stream, k, nb, bk, (const float4*)e->d_sPV, (const uint32_t*)e->d_cellStart,
+                           (const int32_t*)e->d_slotIds.p, (const float4*)e->d_sOwn, devPoints, rows, (const float*)e->d_aggStage.p, devOut, devCount);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_basis_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return basis_run(e, false, cfg, nullptr, 0, devValues, devOut, devCount, info);
+}
+
+int sph_aggregate_basis_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                              uint32_t* devCount, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return basis_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devValues, devOut, devCount, info);
+}
+
+// Host memory in and out through engine scratch, as sph_aggregate_staged: the upload, the device call, the download, one synchronisation.
+int sph_aggregate_basis_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* values, float* out, uint32_t* count,
+                               SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = basis_check(*cfg, g.cellSize, query, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t cells = rows * B * C;
+    const bool work = rows && n;
+    if (work && (!values || !out)) return fail(SPH_ERR_ARG, "null argument");
+    if (work && ((rc = e->d_aggIn.grow(e, n * C)) || (rc = e->d_aggOut.grow(e, cells)) || (rc = e->d_aggCnt.grow(e, rows)) ||
+                 (query && (rc = e->d_sampleIn.grow(e, m))))) return rc;
+    if (work) HIP_TRY(hipMemcpyAsync(e->d_aggIn.p, values, n * C * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (work && query) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = basis_run(e, query, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, e->d_aggIn.p, e->d_aggOut.p,
+                        count ? e->d_aggCnt.p : nullptr, info))) return rc;
+    if (work) HIP_TRY(hipMemcpyAsync(out, e->d_aggOut.p, cells * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (work && count) HIP_TRY(hipMemcpyAsync(count, e->d_aggCnt.p, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+// What the two host twins open with: the params, the grid they give, the config.
+static int basis_host_open(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, bool query, size_t m, SimK& k, int* stencil) {
+    if (!params || !cfg || (n && !particles)) return fail(SPH_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = validate_params(*params))) return rc;
+    if (n > kMaxParticles) return fail(SPH_ERR_CAPACITY, "%zu particles exceed the engine limit of %zu", n, kMaxParticles);
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    SphGridInfo g;
+    sph::compute_grid_extents(*params, g);
+    sph::make_simk(*params, g, params->param_timeStep, k);
+    return basis_check(*cfg, g.cellSize, query, stencil);
+}
+
+int sph_aggregate_basis_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                             const float* values, float* out, uint32_t* count) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = basis_host_open(particles, n, params, cfg, query, m, k, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (!rows || !n) return SPH_OK;
+    if (!values || !out) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    if (ranges_overlap(out, rows * B * C * sizeof(float), values, n * C * sizeof(float)) ||
+        ranges_overlap(count, count ? rows * sizeof(uint32_t) : 0, values, n * C * sizeof(float))) return fail(SPH_ERR_ARG, "the output overlaps the values");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const sph::BasisK bk = make_basisk(*cfg);
+    const sph::HostGrid grid(k, particles, n);
+    std::vector<float> acc(B * C);
+    for (size_t r = 0; r < rows; ++r) {
+        const float* x = query ? points4 + 4 * r : particles[r].pos;
+        const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+        std::fill(acc.begin(), acc.end(), 0.0f);
+        uint32_t cnt = 0u;
+        if (walk) {
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
+                    const SphParticle& cand = particles[grid.order[j]];
+                    float dx, dy, dz, r2;
+                    if (!sph::aggregate_accept(!query && j == grid.slotOf[r], self, x[0], x[1], x[2], cand.pos[0], cand.pos[1], cand.pos[2], R2, dx, dy, dz, r2)) continue;
+                    if (fluidOnly && cand.isGhost != 0) continue;
+                    const float* v = values + (size_t)grid.order[j] * C;
+                    const float w = sph::aggregate_weight(cfg->weight, R2, r2);
+                    int b[8];
+                    float coef[8];
+                    sph::basis_corners(bk.R, bk.half, bk.K, w, dx, dy, dz, b, coef);
+                    cnt += 1u;
+                    for (int t = 0; t < 8; ++t) {
+                        float* plane = acc.data() + (size_t)b[t] * C;
+                        for (size_t c = 0; c < C; ++c) plane[c] = sph::basis_add(plane[c], coef[t], v[c]);
+                    }
+                }
+            });
+        }
+        memcpy(out + r * B * C, acc.data(), B * C * sizeof(float));
+        if (count) count[r] = cnt;
+    }
+    return SPH_OK;
+}
+
+// The adjoint.  Grid of the current state, ids, the rows (sorted slots, or the binned points), the walk; h is read in place through
+// ids[] / perm[].  No synchronisation: nothing is read back.
+static int basis_adjoint_run(SphEngine* e, bool query, const SphBasisConfig* cfg, const float4* devPoints, size_t m, const float* devH, float* devOut,
+                             SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = basis_check(*cfg, g.cellSize, query, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (n && !devOut) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!devH || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t hBytes = rows * B * C * sizeof(float), outBytes = n * C * sizeof(float);
+    if (ranges_overlap(devOut, outBytes, devH, hBytes) || ranges_overlap(devOut, outBytes, devPoints, query ? m * sizeof(float4) : 0))
+        return fail(SPH_ERR_ARG, "the output overlaps h or the points");
+    basis_info(*cfg, n, stencil, out);
+    if (!n) return SPH_OK;
+    if (!rows) {                                                        // no query point: every row is +0
+        HIP_TRY(hipMemsetAsync(devOut, 0, outBytes, e->stream));
+        return SPH_OK;
+    }
+    if ((rc = e->d_slotIds.grow(e, n)) || (query && (rc = adjoint_bin_grow(e, m, (size_t)g.numCells)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const BasisK bk = make_basisk(*cfg);
+    slot_ids_fill(e);
+    if (query && (rc = adjoint_bin(e, k, devPoints, m))) return rc;
+    const uint32_t* rowOf = query ? (const uint32_t*)e->d_adjPerm.p : reinterpret_cast<const uint32_t*>(e->d_slotIds.p);
+    const AdjRows R{query ? (const float4*)e->d_adjPts.p : (const float4*)e->d_sPV, query ? (const uint32_t*)e->d_adjStart.p : (const uint32_t*)e->d_cellStart, (uint32_t)rows};
+    {
+        Timed t(e, SPH_K_OTHER);
+        auto kernel = query ? k_aggregate_basis_adjoint<true> : k_aggregate_basis_adjoint<false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(n << bk.gshift)), dim3(kBlock), 0, e->stream, k, nb, bk, (const float4*)e->d_sPV, (const int32_t*)e->d_slotIds.p,
+                           (const float4*)e->d_sOwn, R, rowOf, devH, devOut);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_basis_adjoint_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devH, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return basis_adjoint_run(e, false, cfg, nullptr, 0, devH, devOut, info);
+}
+
+int sph_aggregate_basis_adjoint_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devH, float* devOut,
+                                      SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return basis_adjoint_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devH, devOut, info);
+}
+
+int sph_aggregate_basis_adjoint_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* h, float* out, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo grid;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, grid)) || (rc = basis_check(*cfg, grid.cellSize, query, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t hWords = rows * B * C;
+    if (n && (!out || (rows && !h))) return fail(SPH_ERR_ARG, "null argument");
+    if (n && ((rc = e->d_adjIn.grow(e, hWords + 1)) || (rc = e->d_aggOut.grow(e, n * C)) || (query && (rc = e->d_sampleIn.grow(e, m + 1))))) return rc;
+    if (n && hWords) HIP_TRY(hipMemcpyAsync(e->d_adjIn.p, h, hWords * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && query && m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    if ((rc = basis_adjoint_run(e, query, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, e->d_adjIn.p, e->d_aggOut.p, info))) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(out, e->d_aggOut.p, n * C * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_aggregate_basis_adjoint_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                                     const float* h, float* out) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = basis_host_open(particles, n, params, cfg, query, m, k, &stencil))) return rc;
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (!n) return SPH_OK;
+    if (!out || (rows && !h)) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    if (ranges_overlap(out, n * C * sizeof(float), h, rows * B * C * sizeof(float)) || ranges_overlap(out, n * C * sizeof(float), points4, query ? m * 4 * sizeof(float) : 0))
+        return fail(SPH_ERR_ARG, "the output overlaps h or the points");
+    const float R2 = cfg->radius * cfg->radius;
+    const bool self = (cfg->flags & SPH_AGGREGATE_SELF) != 0, fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const sph::BasisK bk = make_basisk(*cfg);
+    const sph::AdjHostRows table = query ? sph::AdjHostRows(k, points4, m) : sph::AdjHostRows(sph::HostGrid(k, particles, n));
+    std::vector<float> acc(C);
+    for (size_t r = 0; r < n; ++r) {
+        std::fill(acc.begin(), acc.end(), 0.0f);
+        sph::adjoint_walk_host(k, stencil, table, particles, points4, r, R2, self, fluidOnly, [&](size_t row, float dx, float dy, float dz, float r2) {
+            const float* hrow = h + row * B * C;
+            const float w = sph::aggregate_weight(cfg->weight, R2, r2);
+            int b[8];
+            float coef[8];
+            sph::basis_corners(bk.R, bk.half, bk.K, w, dx, dy, dz, b, coef);
+            for (size_t c = 0; c < C; ++c)
+                for (int t = 0; t < 8; ++t) acc[c] = sph::basis_add(acc[c], coef[t], hrow[(size_t)b[t] * C + c]);
+        });
+        memcpy(out + r * C, acc.data(), C * sizeof(float));
     }
     return SPH_OK;
 }

@@ -463,6 +463,16 @@ AGGREGATE_OPS = {"sum": SPH_AGGREGATE_SUM, "mean": SPH_AGGREGATE_MEAN, "max": SP
 AGGREGATE_WEIGHTS = {"one": SPH_AGGREGATE_WEIGHT_ONE, "poly6": SPH_AGGREGATE_WEIGHT_POLY6}
 
 
+class SphBasisConfig(C.Structure):
+    """struct SphBasisConfig of include/sph_abi.h: radius, weight, flags, channels, kind, size, zero padding (see basis_config())."""
+    _fields_ = [("radius", C.c_float), ("weight", C.c_int32), ("flags", C.c_int32), ("channels", C.c_int32), ("kind", C.c_int32), ("size", C.c_int32),
+                ("pad", C.c_int32 * 2)]
+
+
+assert C.sizeof(SphBasisConfig) == 32
+SPH_BASIS_GRID = 0
+
+
 class SphSlabIntent(C.Structure):
     """The plan of one sized halo exchange (include/sph_abi.h SphSlabIntent): what both ends of a link must agree on before a record moves."""
     _fields_ = [("magic", C.c_uint32), ("exchangeNo", C.c_uint32), ("stepNo", C.c_uint32), ("faceCap", C.c_uint32),
@@ -745,6 +755,15 @@ _ABI = {
     "sph_aggregate_route_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_route_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_route_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp]),
+    "sph_aggregate_basis_default": (None, [_P(SphBasisConfig)]),
+    "sph_aggregate_basis_particles": (_int, [_vp, _P(SphBasisConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_query": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_staged": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_host": (_int, [_vp, _sz, _pp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp]),
+    "sph_aggregate_basis_adjoint_particles": (_int, [_vp, _P(SphBasisConfig), _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_adjoint_query": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_adjoint_staged": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_adjoint_host": (_int, [_vp, _sz, _pp, _P(SphBasisConfig), _vp, _sz, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -2005,6 +2024,101 @@ class SPHFluidGPU:
             cnt = None if cnt is None else cnt.cpu().numpy().view(np.uint32)
         return (out, cnt, arg) if counts else (out, arg)
 
+    # -- filter-grid basis sums and continuous convolutions (include/sph_abi.h "filter-grid basis sums") ----
+    def aggregate_basis(self, x, radius=None, size=4, weight="poly6", self_=False, fluid_only=False, counts=False, device: bool = False):
+        """The basis sums of a continuous convolution, A[i][b][c] = sum_j w(r_ij) phi_b(x_j - x_i) x[j][c] over every particle's neighbours
+        within `radius` (None: param_h; at most three cells), fused into the grid walk: no edge list.  phi_b are
+        the size^3 trilinear hat functions of a size x size x size filter grid over [-radius, radius]^3, b = (z * size + y) * size + x;
+        size 2, 3 or 4.  x: (n, C) or (n,) numpy, or a contiguous float32 torch device tensor of (n, C), used in place; 1 <= C <= 128.
+        weight "one" | "poly6"; self_ keeps the particle itself (d = 0: the centre of the grid); fluid_only as aggregate().  Returns
+        float32 (n, size^3, C), with counts=True (out, counts uint32[n]); numpy, or with device=True fresh torch device tensors.  The
+        same bytes on every run.  Streams as aggregate()."""
+        return self._basis(None, x, self._radius(radius), size, weight, self_, fluid_only, counts, device)
+
+    def query_aggregate_basis(self, points, x, radius, size=4, weight="poly6", fluid_only=False, counts=False, device: bool = False):
+        """The same around (m, 3) or (m, 4) query points: (m, size^3, C).  A point with a non-finite coordinate has an empty row."""
+        return self._basis(_device_points4(points, "query_aggregate_basis"), x, radius, size, weight, False, fluid_only, counts, device)
+
+    def _basis(self, dev_points, x, radius, size, weight, self_, fluid_only, counts, device):
+        import torch
+        vals = _device_values(x, "aggregate_basis")
+        n, c = int(vals.shape[0]), int(vals.shape[1])
+        if n != self.GetNumFluids():
+            raise SphError(f"aggregate_basis: {n} rows of values for {self.GetNumFluids()} particles")
+        cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        written = rows and n                                                          # (nothing is written otherwise: sph_abi.h)
+        out = (torch.empty if written else torch.zeros)((rows, _basis_planes(size), c), dtype=torch.float32, device="cuda")
+        cnt = (torch.empty if written else torch.zeros)(rows, dtype=torch.int32, device="cuda") if counts else None
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        p_out, p_cnt = _tensor_ptr(out), None if cnt is None else _tensor_ptr(cnt)
+        if dev_points is None:
+            _check(self._L.sph_aggregate_basis_particles(self._h, C.byref(cfg), _tensor_ptr(vals), p_out, p_cnt, C.byref(info)))
+        else:
+            _check(self._L.sph_aggregate_basis_query(self._h, C.byref(cfg), _tensor_ptr(dev_points), rows, _tensor_ptr(vals), p_out, p_cnt, C.byref(info)))
+        self.sync()
+        if not device:
+            out = out.cpu().numpy()
+            cnt = None if cnt is None else cnt.cpu().numpy().view(np.uint32)
+        return (out, cnt) if counts else out
+
+    def aggregate_basis_adjoint(self, h, radius=None, size=4, weight="poly6", self_=False, fluid_only=False, device: bool = False):
+        """The exact transpose of aggregate_basis() with the same arguments, applied to h of (n, size^3, C): (n, C) float32, row k sums
+        coef_b * h[i][b][c] over the rows i that accept particle k, in ascending sorted slot, with the forward's own coefficients.  No
+        float atomics, the same bytes on every run.  Streams as aggregate()."""
+        return self._basis_adjoint(None, h, self._radius(radius), size, weight, self_, fluid_only, device)
+
+    def query_aggregate_basis_adjoint(self, points, h, radius, size=4, weight="poly6", fluid_only=False, device: bool = False):
+        """The transpose of query_aggregate_basis(): h (m, size^3, C) sits on the query points, the result is (n, C); the rows are
+        taken in ascending (clamped cell of the point, point index), as query_aggregate_adjoint()."""
+        return self._basis_adjoint(_device_points4(points, "query_aggregate_basis_adjoint"), h, radius, size, weight, False, fluid_only, device)
+
+    def _basis_adjoint(self, dev_points, h, radius, size, weight, self_, fluid_only, device):
+        import torch
+        n = self.GetNumFluids()
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        if isinstance(h, torch.Tensor) and _is_cuda_f32(h) and h.dim() == 3:
+            ht = h
+        else:
+            ht = torch.from_numpy(_basis_planes_array(h.detach().cpu().numpy() if isinstance(h, torch.Tensor) else h, rows, size, "aggregate_basis_adjoint")).cuda()
+        if tuple(ht.shape[:2]) != (rows, _basis_planes(size)):
+            raise SphError(f"aggregate_basis_adjoint: h of shape {tuple(ht.shape)} for {rows} rows of {_basis_planes(size)} planes")
+        c = int(ht.shape[2])
+        cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+        out = torch.empty((n, c), dtype=torch.float32, device="cuda")
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        if dev_points is None:
+            _check(self._L.sph_aggregate_basis_adjoint_particles(self._h, C.byref(cfg), _tensor_ptr(ht), _tensor_ptr(out), C.byref(info)))
+        else:
+            _check(self._L.sph_aggregate_basis_adjoint_query(self._h, C.byref(cfg), _tensor_ptr(dev_points), rows, _tensor_ptr(ht), _tensor_ptr(out), C.byref(info)))
+        self.sync()
+        return out if device else out.cpu().numpy()
+
+    def continuous_conv(self, x, filters, radius=None, weight="poly6", self_=True, fluid_only=False, normalize=False, check_state: bool = True,
+                        max_basis_bytes: int = 2 ** 31):
+        """A continuous convolution (Ummenhofer et al. 2020) of the particles' features over the engine's own neighbourhoods, as a
+        torch.autograd.Function: out[i] = sum_j w(r_ij) x[j] @ F(x_j - x_i), F the trilinear interpolation of filters (K, K, K, Cin, Cout)
+        (axes z, y, x; K 2, 3 or 4) laid over [-radius, radius]^3.  x: a float32 torch device tensor of (n, Cin); the result is
+        (n, Cout).  Once differentiable in x and filters; the positions are the engine's state, not a tensor.  The basis sums are
+        aggregate_basis()'s, in blocks of input channels so that one basis tensor stays under max_basis_bytes (channels are
+        independent: the blocking changes no basis byte), and recomputed in the backward rather than saved; their bytes are fixed.  The
+        product with the filters is torch's matmul, for which no byte claim is made.  normalize divides by the sum of the weights
+        (0 where it is 0).  check_state as aggregate_autograd().  See autograd.py for the formulas."""
+        from .autograd import EngineAggregateBackend, continuous_conv
+        return continuous_conv(EngineAggregateBackend(self), None, x, filters, self._radius(radius), weight, self_, fluid_only, normalize, check_state,
+                               max_basis_bytes)
+
+    def query_continuous_conv(self, points, x, filters, radius, weight="poly6", fluid_only=False, normalize=False, check_state: bool = True,
+                              max_basis_bytes: int = 2 ** 31):
+        """continuous_conv() around (m, 3) or (m, 4) query points: the result is (m, Cout)."""
+        from .autograd import EngineAggregateBackend, continuous_conv
+        return continuous_conv(EngineAggregateBackend(self), _device_points4(points, "query_continuous_conv"), x, filters, radius, weight, False, fluid_only,
+                               normalize, check_state, max_basis_bytes)
+
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
         """(origin, spacing, dims) of surface()'s default lattice: spacing h/2 over the ComputeGridExtents box widened by 2h on every side."""
@@ -3004,6 +3118,68 @@ def aggregate_route_host(records, params, arg, grad, radius, points=None, op="ma
     cfg = _aggregate_cfg(radius, op, "one", c, self_, fluid_only, delta, False)
     out = np.zeros((head[1], c), np.float32)
     _check(load_library().sph_aggregate_route_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(a), _ptr_or_none(g), _ptr_or_none(out)))
+    return out
+
+
+def basis_config(**overrides) -> SphBasisConfig:
+    """sph_aggregate_basis_default with the named fields replaced.  No device is needed."""
+    cfg = SphBasisConfig()
+    load_library().sph_aggregate_basis_default(C.byref(cfg))
+    return _copy_config(cfg, overrides)
+
+
+def _basis_planes(size) -> int:
+    """B = K^3 of a filter grid of size K; the library refuses a K outside 2 .. 4, so anything else counts as no plane."""
+    try:
+        k = int(size)
+    except (TypeError, ValueError):
+        raise SphError(f"aggregate_basis: size {size!r} (2, 3 or 4)") from None
+    return k ** 3 if 2 <= k <= 4 else 0
+
+
+def _basis_cfg(radius, size, weight, channels, self_=False, fluid_only=False) -> SphBasisConfig:
+    """The config of aggregate_basis(), its adjoint and the host twins; weight by name or by number."""
+    flags = (SPH_AGGREGATE_SELF if self_ else 0) | (SPH_AGGREGATE_FLUID_ONLY if fluid_only else 0)
+    try:
+        return basis_config(radius=float(radius), weight=int(AGGREGATE_WEIGHTS.get(weight, weight)), flags=flags, channels=int(channels), size=int(size))
+    except (TypeError, ValueError):
+        raise SphError(f"aggregate_basis: weight {weight!r} (one of {sorted(AGGREGATE_WEIGHTS)}), size {size!r} (2, 3 or 4)") from None
+
+
+def _basis_planes_array(h, rows, size, who):
+    """h as float32 numpy of (rows, K^3, C)."""
+    a = np.ascontiguousarray(h, np.float32)
+    if a.ndim != 3 or a.shape[0] != rows or a.shape[1] != _basis_planes(size):
+        raise SphError(f"{who}: h of shape {a.shape} for {rows} rows of {_basis_planes(size)} planes")
+    return a
+
+
+def aggregate_basis_host(records, params, x, radius, points=None, size=4, weight="poly6", self_=False, fluid_only=False, counts=False):
+    """sph_aggregate_basis_host: the (rows, size^3, C) result of SPHFluidGPU.aggregate_basis (points None) or query_aggregate_basis on
+    host records and (n, C) host values, computed on the CPU by the same per-candidate functions in the same order: the same bytes.  No
+    device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_basis_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)                    # (non-null: query rows, also for m = 0)
+    vals = _scalar_values(x, head[1])
+    c = int(vals.shape[1])
+    cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+    out = np.zeros((rows, _basis_planes(size), c), np.float32)
+    cnt = np.zeros(rows, np.uint32)
+    _check(load_library().sph_aggregate_basis_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(out),
+                                                   _ptr_or_none(cnt) if counts else None))
+    return (out, cnt) if counts else out
+
+
+def aggregate_basis_adjoint_host(records, params, h, radius, points=None, size=4, weight="poly6", self_=False, fluid_only=False):
+    """sph_aggregate_basis_adjoint_host: the (n, C) result of SPHFluidGPU.aggregate_basis_adjoint (points None) or
+    query_aggregate_basis_adjoint on host records and host h of (rows, size^3, C): the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_basis_adjoint_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    a = _basis_planes_array(h, rows, size, "aggregate_basis_adjoint_host")
+    c = int(a.shape[2])
+    cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+    out = np.zeros((head[1], c), np.float32)
+    _check(load_library().sph_aggregate_basis_adjoint_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(a), _ptr_or_none(out)))
     return out
 
 

@@ -398,6 +398,59 @@ public:
         if (devPoints4) return !Check(sph_aggregate_route_query(engine, &cfg, devPoints4, m, devArg, devG, devOut, &out), "sph_aggregate_route_query");
         return !Check(sph_aggregate_route_particles(engine, &cfg, devArg, devG, devOut, &out), "sph_aggregate_route_particles");
     }
+    // Filter-grid basis sums (sph_abi.h "filter-grid basis sums"): devOut[rows][K^3][channels] = the sums of
+    // w * phi_b(x_j - x_i) * devValues[j][c] over the neighbours, the linear part of a continuous convolution (the caller multiplies by
+    // the filters), and the exact transpose devH[rows][K^3][channels] -> devOut[n][channels].  cfg: sph_aggregate_basis_default's fields
+    // with radius set (BasisConfig: param_h).  DEVICE memory, no synchronisation, as Aggregate.
+    SphBasisConfig BasisConfig() const {
+        SphBasisConfig cfg;
+        sph_aggregate_basis_default(&cfg);
+        cfg.radius = param_h;
+        return cfg;
+    }
+    bool AggregateBasis(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devValues, float* devOut, uint32_t* devCount = nullptr) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_particles(engine, &cfg, devValues, devOut, devCount, &out), "sph_aggregate_basis_particles");
+    }
+    bool QueryAggregateBasis(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                             uint32_t* devCount = nullptr) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_query(engine, &cfg, devPoints4, m, devValues, devOut, devCount, &out), "sph_aggregate_basis_query");
+    }
+    bool AggregateBasisAdjoint(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devH, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_adjoint_particles(engine, &cfg, devH, devOut, &out), "sph_aggregate_basis_adjoint_particles");
+    }
+    bool QueryAggregateBasisAdjoint(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devPoints4, size_t m, const float* devH, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_adjoint_query(engine, &cfg, devPoints4, m, devH, devOut, &out), "sph_aggregate_basis_adjoint_query");
+    }
+    // The same for HOST arrays (points4 m * 4 floats, or null for particle targets): out is sized by the call.  Synchronises.
+    bool AggregateBasis(SphAggregateInfo& info, const SphBasisConfig& cfg, const std::vector<float>& values, std::vector<float>& out,
+                        std::vector<uint32_t>* counts = nullptr, const float* points4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t rows = points4 ? m : sph_num_particles(engine);
+        if (cfg.channels < 1 || cfg.size < 2 || cfg.size > 4 || values.size() != sph_num_particles(engine) * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "AggregateBasis: values.size() is not n * channels, or a bad size");
+        out.assign(rows * size_t(cfg.size * cfg.size * cfg.size) * size_t(cfg.channels), 0.0f);
+        if (counts) counts->assign(rows, 0u);
+        return !Check(sph_aggregate_basis_staged(engine, &cfg, points4, m, values.data(), out.data(), counts ? counts->data() : nullptr, &info), "sph_aggregate_basis_staged");
+    }
+    bool AggregateBasisAdjoint(SphAggregateInfo& info, const SphBasisConfig& cfg, const std::vector<float>& h, std::vector<float>& out,
+                               const float* points4 = nullptr, size_t m = 0) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine), rows = points4 ? m : n;
+        if (cfg.channels < 1 || cfg.size < 2 || cfg.size > 4 || h.size() != rows * size_t(cfg.size * cfg.size * cfg.size) * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "AggregateBasisAdjoint: h.size() is not rows * K^3 * channels");
+        out.assign(n * size_t(cfg.channels), 0.0f);
+        return !Check(sph_aggregate_basis_adjoint_staged(engine, &cfg, points4, m, h.data(), out.data(), &info), "sph_aggregate_basis_adjoint_staged");
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

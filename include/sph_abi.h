@@ -64,6 +64,7 @@ extern "C" {
 /* (still 4, additions only: SphAggregateConfig, SphAggregateInfo, SPH_AGGREGATE_*, sph_aggregate_default / _particles / _query / _staged / _host, SPH_OPT_AGGREGATE_VARIANT -- fused neighbourhood reductions of caller tensors) */
 /* (still 4, additions only: sph_aggregate_adjoint_particles / _query / _staged / _host, sph_aggregate_arg_particles / _query / _host, sph_aggregate_route_particles / _query / _host -- the adjoint of the neighbourhood sums, extrema with their winners, routing through them) */
 /* (still 4, additions only: SPH_SLAB_FLAG_* -- names of the six bits of the z-slab exchange's flag word, values as before) */
+/* (still 4, additions only: SphBasisConfig, SPH_BASIS_GRID, sph_aggregate_basis_default / _particles / _query / _staged / _host, sph_aggregate_basis_adjoint_particles / _query / _staged / _host -- filter-grid basis sums: continuous convolutions without an edge list) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -1481,6 +1482,66 @@ int sph_aggregate_route_query(SphEngine* e, const SphAggregateConfig* cfg, const
                               float* devOut, SphAggregateInfo* info);
 int sph_aggregate_route_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
                              const int32_t* arg, const float* g, float* out);
+
+/* ---- filter-grid basis sums: continuous convolutions without an edge list (no reference counterpart) -----------
+ * A continuous convolution (Ummenhofer et al. 2020) interpolates a K x K x K grid of Cin x Cout filter matrices trilinearly at the
+ * neighbour's offset, so it is linear in B = K^3 fixed geometric functions.  These calls give the basis sums
+ *   A[i][b][c] = sum_j w(r_ij) * phi_b(x_j - x_i) * values[j][c]
+ * of a caller's values[n][C] (float32, row-major by particle id, device memory, never written) over the neighbours of every particle or
+ * of m query points; the learned part is one dense product A.reshape(rows, B * C) @ filters.reshape(B * C, Cout) that the caller runs.
+ * A query: it keeps no result, puts nothing in a checkpoint and touches no engine state.
+ * Grid, radius rules (0 < R <= 3 cells), stencil, candidate order (ascending sorted slot), acceptance (d = x_j - x_i, r2 < R2), SELF by
+ * slot identity with d = 0, FLUID_ONLY, and the empty rows of non-finite targets and points are those of the fused neighbourhood
+ * reductions above.  Not supported, SPH_ERR_ARG: DELTA, MOMENTS (any flag bit but SELF and FLUID_ONLY); the operation is SUM.  Weights:
+ * SPH_AGGREGATE_WEIGHT_ONE, or _POLY6 (t = R2 - r2, w = (t * t) * t).
+ * Config.  kind SPH_BASIS_GRID (the only one), size = K in {2, 3, 4}, 1 <= channels <= SPH_AGGREGATE_MAX_CHANNELS, zero padding.
+ * Coordinates, per axis a, every operation fp32 and rounded on its own (no fused multiply-add):
+ *   u_a = d_a / R (IEEE division by the config's radius);  g_a = (u_a + 1.0f) * half, half = 0.5f * (float)(K - 1);
+ *   i_a = (int)g_a clamped to [0, K - 2];  f_a = g_a - (float)i_a;  lo_a = 1.0f - f_a;  hi_a = f_a
+ * the linear map of [-R, R] onto the grid's [0, K - 1] with aligned corners and no ball-to-cube map (|d_a| < R for an accepted
+ * candidate, so the clamp is a guard).  Per candidate the 8 corners (cz, cy, cx) in {lo, hi}^3 have the plane index
+ * b = ((i_z + cz) K + (i_y + cy)) K + (i_x + cx), x fastest, the coefficient coef = w * ((wx * wy) * wz) and the step
+ * acc[b][c] = acc[b][c] + coef * v[c], zero coefficients included.  The 8 planes are distinct, so the order of the corners does not
+ * enter the bytes.  NaN and inf values propagate in the rows that accept them.
+ * Outputs, device memory: out float32[rows][B][C], c fastest, every row written (+0 where empty); count (may be null) uint32[rows],
+ * the numbers sph_aggregate_* gives.  The same bytes on every run, and the bytes of sph_aggregate_basis_host.
+ * Adjoint.  Input h float32[rows][B][C], output out float32[n][C] by particle id, every row written.  Particle k sums over the rows i
+ * that accept it in the order of sph_aggregate_adjoint_* (particle targets: ascending sorted slot; query targets: ascending (clamped
+ * cell of the point, point index)), with the forward's own bits of d = x_k - x_i, r2, w and the corner coefficients; per row the 8
+ * corners in ascending b: acc = acc + coef_b * h[i][b][c].  Query targets are binned as there.  No float atomics; the same bytes on
+ * every run, and the bytes of sph_aggregate_basis_adjoint_host.
+ * Streams: the device calls work on the engine's stream and do NOT synchronise; timed as SPH_K_OTHER.  SphAggregateInfo: rows (those
+ * of out), channels, planes = B, stencil, flags, radius.
+ * SPH_ERR_STATE: z-slab engines and SPH_OPT_GRID_BUILD 1, before any allocation.  SPH_ERR_ARG: a null argument, a bad radius, an
+ * unknown weight, kind or flag bit (DELTA and MOMENTS among them), a size outside 2 .. 4, channels outside 1 .. 128, non-zero padding,
+ * SELF on query targets, more than 2^31 - 1 query points, overlapping address ranges (out or count with values; the adjoint's out with
+ * h or the points), rows * B * channels beyond size_t.  Forward, m = 0 or n = 0: success, nothing is written.  Adjoint, m = 0: out is
+ * zeroed; n = 0: success, nothing is written. */
+enum { SPH_BASIS_GRID = 0 };                                                                                            /* SphBasisConfig.kind */
+typedef struct SphBasisConfig { float radius; int32_t weight, flags, channels, kind, size; int32_t pad[2]; } SphBasisConfig;     /* 32 bytes */
+/* radius 0 (to be set), weight POLY6, flags 0, channels 1, kind GRID, size 4, padding 0. */
+void sph_aggregate_basis_default(SphBasisConfig* cfg);
+/* Rows of every particle: devValues float32[n][channels], devOut float32[n][B][channels], devCount uint32[n] or null. */
+int sph_aggregate_basis_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devValues, float* devOut, uint32_t* devCount, SphAggregateInfo* info);
+/* Rows of m query points (x, y, z, .) in device memory: devOut float32[m][B][channels], devCount uint32[m] or null. */
+int sph_aggregate_basis_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devValues, float* devOut,
+                              uint32_t* devCount, SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets; count may be null); synchronises. */
+int sph_aggregate_basis_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* values, float* out, uint32_t* count,
+                               SphAggregateInfo* info);
+/* Host-only, no device: the same per-candidate functions in the same order; the same bytes.  points4 null: particle targets. */
+int sph_aggregate_basis_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                             const float* values, float* out, uint32_t* count);
+/* The adjoint: devH float32[rows][B][channels], devOut float32[n][channels]. */
+int sph_aggregate_basis_adjoint_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devH, float* devOut, SphAggregateInfo* info);
+int sph_aggregate_basis_adjoint_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devH, float* devOut,
+                                      SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets); synchronises. */
+int sph_aggregate_basis_adjoint_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* h, float* out,
+                                       SphAggregateInfo* info);
+/* Host-only, no device: the same bytes.  points4 null: particle targets. */
+int sph_aggregate_basis_adjoint_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                                     const float* h, float* out);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
