@@ -1,14 +1,22 @@
 """Autograd through the fused neighbourhood reductions: torch.autograd.Functions whose backward is the engine's
 own adjoint, so that a loss over aggregate() needs no edge list.
 
-Differentiable in `values` only: the positions are the engine's state, not a tensor.  Once differentiable.  The backward formulas are
-written against a small backend (forward, adjoint, arg, route) that the engine implements on the device (EngineAggregateBackend) and
+Differentiable in `values`, and with the keyword `positions` (and `points_grad` for query points) in the positions too (DESIGN.md
+section 3x); continuous_conv stays differentiable in x and the filters only.  Once differentiable.  The backward formulas are written
+against a small backend (forward, adjoint, arg, route, posgrad) that the engine implements on the device (EngineAggregateBackend) and
 the host twins implement on the CPU (HostAggregateBackend), so that they can be checked without a GPU:
 
   sum        grad = adjoint(g)
   mean       grad = adjoint(g / W), 0 where W == 0; W is the counts output for weight "one" and a one-channel SUM of ones otherwise
              (acc = acc + w * 1 in the forward's order: MEAN's own W bits)
   max / min  grad = route(arg, g); with delta additionally -g[i][c] goes to row i wherever arg[i][c] >= 0
+
+and the gradient of the positions (posgrad returns the pair (points' rows or None, particles' rows); the cutoff is not differentiated):
+
+  sum        posgrad(values, g)
+  mean       with g' = g / W (0 where W == 0): posgrad(values, g'), and for weight "poly6" plus the gradient through W, a one-channel
+             posgrad of ones with the upstream -sum_c g'[i][c] * out[i][c] (for weight "one" W is a count: that term is zero)
+  max / min  zeros (weight "one": piecewise constant); no engine call
 
 continuous_conv stands on two more backend calls, basis and basis_adjoint.  With A the basis sums of a block of
 input channels, (rows, B, cw), and F the block's filters as a (B * cw, Cout) matrix:
@@ -25,13 +33,13 @@ import zlib
 import numpy as np
 
 from .engine import (SPH_AGGREGATE_MAX_CHANNELS, SphError, aggregate_adjoint_host, aggregate_arg_host, aggregate_basis_adjoint_host, aggregate_basis_host,
-                     aggregate_host, aggregate_route_host)
+                     aggregate_host, aggregate_position_grad_host, aggregate_route_host)
 
 __all__ = ["EngineAggregateBackend", "HostAggregateBackend", "aggregate_autograd", "continuous_conv"]
 
 
 class EngineAggregateBackend:
-    """The four calls on an SPHFluidGPU: torch device tensors in and out.  points: None, or (m, 3) / (m, 4) query points."""
+    """The backend calls on an SPHFluidGPU: torch device tensors in and out.  points: None, or (m, 3) / (m, 4) query points."""
 
     def __init__(self, engine):
         self.f = engine
@@ -60,6 +68,16 @@ class EngineAggregateBackend:
             return self.f.aggregate_route(arg, grad, radius, op=op, self_=self_, fluid_only=fluid_only, delta=delta, device=True)
         return self.f.query_aggregate_route(points, arg, grad, radius, op=op, fluid_only=fluid_only, device=True)
 
+    def positions(self):
+        return self.f.positions(device=True)
+
+    def posgrad(self, points, values, grad, radius, weight, self_, fluid_only, delta, moments, want_points=True, want_particles=True):
+        if points is None:
+            return None, self.f.aggregate_position_grad(values, grad, radius, weight=weight, self_=self_, fluid_only=fluid_only, delta=delta, moments=moments,
+                                                        device=True)
+        return self.f.query_aggregate_position_grad(points, values, grad, radius, weight=weight, fluid_only=fluid_only, moments=moments, device=True,
+                                                    want_points=want_points, want_particles=want_particles)
+
     def basis(self, points, x, radius, size, weight, self_, fluid_only):
         if points is None:
             return self.f.aggregate_basis(x, radius, size=size, weight=weight, self_=self_, fluid_only=fluid_only, device=True)
@@ -72,7 +90,7 @@ class EngineAggregateBackend:
 
 
 class HostAggregateBackend:
-    """The same four calls over the host twins on (records, params): CPU torch tensors in and out, the bytes the device gives.  No GPU."""
+    """The same calls over the host twins on (records, params): CPU torch tensors in and out, the bytes the device gives.  No GPU."""
 
     def __init__(self, records, params):
         self.records, self.params = records, params
@@ -106,6 +124,16 @@ class HostAggregateBackend:
         return self._t(aggregate_route_host(self.records, self.params, self._np(arg), self._np(grad), radius, points=points, op=op, self_=self_,
                                             fluid_only=fluid_only, delta=delta))
 
+    def positions(self):
+        return self._t(np.ascontiguousarray(self.records["pos"][:, :3], np.float32))
+
+    def posgrad(self, points, values, grad, radius, weight, self_, fluid_only, delta, moments, want_points=True, want_particles=True):
+        res = aggregate_position_grad_host(self.records, self.params, self._np(values), self._np(grad), radius, points=None if points is None else self._np(points),
+                                           weight=weight, self_=self_, fluid_only=fluid_only, delta=delta, moments=moments)
+        if points is None:
+            return None, self._t(res)
+        return (self._t(res[0]) if want_points else None), (self._t(res[1]) if want_particles else None)
+
     def basis(self, points, x, radius, size, weight, self_, fluid_only):
         return self._t(aggregate_basis_host(self.records, self.params, self._np(x), radius, points=points, size=size, weight=weight, self_=self_,
                                             fluid_only=fluid_only))
@@ -116,61 +144,133 @@ class HostAggregateBackend:
 
 
 def _function():
-    """The torch.autograd.Function, made on first use so that importing the package does not import torch."""
+    """The two torch.autograd.Functions (values only; values and positions), made on first use so that importing the package does not
+    import torch."""
     global _FN
     if _FN is not None:
         return _FN
     import torch
     from torch.autograd.function import once_differentiable
 
+    def values_forward(ctx, values, backend, points, radius, op, weight, self_, fluid_only, delta, moments, check_state):
+        """The forward of both Functions: (out, the tensors the values' backward needs)."""
+        ctx.backend, ctx.points, ctx.radius = backend, points, radius
+        ctx.cfg = (op, weight, self_, fluid_only, delta, moments)
+        ctx.digest = backend.state() if check_state else None
+        ctx.check_state = check_state
+        v = values.detach()
+        saved = ()
+        if op in ("max", "min"):
+            out, arg = backend.arg(points, v, radius, op, self_, fluid_only, delta)
+            saved = (arg,)
+        elif op == "mean":
+            if weight == "one":
+                out, cnt = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, False, True)
+                W = cnt.to(torch.float32)
+            else:
+                out = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, False, False)
+                ones = torch.ones((v.shape[0], 1), dtype=torch.float32, device=v.device)
+                W = backend.forward(points, ones, radius, "sum", weight, self_, fluid_only, False, False, False).reshape(-1)
+            saved = (W,)
+        else:
+            out = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, moments, False)
+        return out, saved
+
+    def check(ctx):
+        if ctx.check_state and ctx.backend.state() != ctx.digest:
+            raise SphError("aggregate_autograd: the particle state changed between forward and backward (a dispatch, an upload or an impulse): "
+                           "the adjoint would be that of another neighbour relation")
+
+    def mean_upstream(g, W):
+        ok = (W != 0)[:, None]
+        return torch.where(ok, g / torch.where(ok, W[:, None], torch.ones_like(W[:, None])), torch.zeros_like(g))
+
+    def values_backward(ctx, g, saved):
+        op, weight, self_, fluid_only, delta, moments = ctx.cfg
+        backend, points, radius = ctx.backend, ctx.points, ctx.radius
+        if op in ("max", "min"):
+            (arg,) = saved
+            grad = backend.route(points, arg, g, radius, op, self_, fluid_only, delta)
+            if delta:
+                grad = grad - torch.where(arg >= 0, g, torch.zeros_like(g))
+        elif op == "mean":
+            (W,) = saved
+            grad = backend.adjoint(points, mean_upstream(g, W).contiguous(), radius, weight, self_, fluid_only, delta, False)
+        else:
+            grad = backend.adjoint(points, g, radius, weight, self_, fluid_only, delta, moments)
+        return grad
+
+    def positions_backward(ctx, g, saved, v, out, want_points, want_particles):
+        """(the points' rows or None, the particles' rows or None) of the position gradient (module docstring)."""
+        op, weight, self_, fluid_only, delta, moments = ctx.cfg
+        backend, points, radius = ctx.backend, ctx.points, ctx.radius
+        rows = int(out.shape[0])
+        if op in ("max", "min"):
+            return (torch.zeros((rows, 3), dtype=torch.float32, device=v.device) if want_points else None,
+                    torch.zeros((int(v.shape[0]), 3), dtype=torch.float32, device=v.device) if want_particles else None)
+        if op == "sum":
+            return backend.posgrad(points, v, g, radius, weight, self_, fluid_only, delta, moments, want_points, want_particles)
+        (W,) = saved
+        gW = mean_upstream(g, W).contiguous()
+        pts, par = backend.posgrad(points, v, gW, radius, weight, self_, fluid_only, delta, False, want_points, want_particles)
+        if weight != "one":                                                         # the gradient through W = sum w * 1
+            up = (-(gW * out).sum(dim=1, keepdim=True)).contiguous()
+            ones = torch.ones((int(v.shape[0]), 1), dtype=torch.float32, device=v.device)
+            pts2, par2 = backend.posgrad(points, ones, up, radius, weight, self_, fluid_only, False, False, want_points, want_particles)
+            pts = None if pts is None else pts + pts2
+            par = None if par is None else par + par2
+        return pts, par
+
     class AggregateFunction(torch.autograd.Function):
         @staticmethod
         def forward(ctx, values, backend, points, radius, op, weight, self_, fluid_only, delta, moments, check_state):
-            ctx.backend, ctx.points, ctx.radius = backend, points, radius
-            ctx.cfg = (op, weight, self_, fluid_only, delta, moments)
-            ctx.digest = backend.state() if check_state else None
-            ctx.check_state = check_state
-            v = values.detach()
-            if op in ("max", "min"):
-                out, arg = backend.arg(points, v, radius, op, self_, fluid_only, delta)
-                ctx.save_for_backward(arg)
-            elif op == "mean":
-                if weight == "one":
-                    out, cnt = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, False, True)
-                    W = cnt.to(torch.float32)
-                else:
-                    out = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, False, False)
-                    ones = torch.ones((v.shape[0], 1), dtype=torch.float32, device=v.device)
-                    W = backend.forward(points, ones, radius, "sum", weight, self_, fluid_only, False, False, False).reshape(-1)
-                ctx.save_for_backward(W)
-            else:
-                out = backend.forward(points, v, radius, op, weight, self_, fluid_only, delta, moments, False)
+            out, saved = values_forward(ctx, values, backend, points, radius, op, weight, self_, fluid_only, delta, moments, check_state)
+            if saved:
+                ctx.save_for_backward(*saved)
             return out
 
         @staticmethod
         @once_differentiable
         def backward(ctx, g):
-            op, weight, self_, fluid_only, delta, moments = ctx.cfg
-            backend, points, radius = ctx.backend, ctx.points, ctx.radius
-            if ctx.check_state and backend.state() != ctx.digest:
-                raise SphError("aggregate_autograd: the particle state changed between forward and backward (a dispatch, an upload or an impulse): "
-                               "the adjoint would be that of another neighbour relation")
-            g = g.contiguous()
-            if op in ("max", "min"):
-                (arg,) = ctx.saved_tensors
-                grad = backend.route(points, arg, g, radius, op, self_, fluid_only, delta)
-                if delta:
-                    grad = grad - torch.where(arg >= 0, g, torch.zeros_like(g))
-            elif op == "mean":
-                (W,) = ctx.saved_tensors
-                ok = (W != 0)[:, None]
-                gW = torch.where(ok, g / torch.where(ok, W[:, None], torch.ones_like(W[:, None])), torch.zeros_like(g))
-                grad = backend.adjoint(points, gW.contiguous(), radius, weight, self_, fluid_only, delta, False)
-            else:
-                grad = backend.adjoint(points, g, radius, weight, self_, fluid_only, delta, moments)
-            return (grad,) + (None,) * 10
+            check(ctx)
+            return (values_backward(ctx, g.contiguous(), ctx.saved_tensors),) + (None,) * 10
 
-    _FN = AggregateFunction
+    class AggregatePositionFunction(torch.autograd.Function):
+        """The same forward with two more tensor inputs: positions (n, 3), which must hold the backend's positions, and the query points
+        as a tensor (or None).  The backward adds the position gradient."""
+
+        @staticmethod
+        def forward(ctx, values, positions, points_leaf, backend, points, radius, op, weight, self_, fluid_only, delta, moments, check_state):
+            if positions is not None and check_state:
+                mine = backend.positions()
+                theirs = positions.detach().contiguous()
+                if tuple(theirs.shape) != tuple(mine.shape) or not torch.equal(theirs.view(torch.int32), mine.view(torch.int32)):
+                    raise SphError("aggregate_autograd: positions does not hold the engine's positions byte for byte: the gradient would be that of "
+                                   "another configuration")
+            out, saved = values_forward(ctx, values, backend, points, radius, op, weight, self_, fluid_only, delta, moments, check_state)
+            ctx.nsaved = len(saved)
+            ctx.leaf_width = 0 if points_leaf is None else int(points_leaf.shape[1])
+            ctx.save_for_backward(*saved, values.detach(), out)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            check(ctx)
+            g = g.contiguous()
+            saved, (v, out) = ctx.saved_tensors[:ctx.nsaved], ctx.saved_tensors[ctx.nsaved:]
+            need_v, need_x, need_p = ctx.needs_input_grad[:3]
+            grad_v = values_backward(ctx, g, saved) if need_v else None
+            grad_x = grad_p = None
+            if need_x or need_p:
+                grad_p, grad_x = positions_backward(ctx, g, saved, v, out, need_p, need_x or ctx.points is None)
+                if not need_x:
+                    grad_x = None
+                if need_p and ctx.leaf_width == 4:
+                    grad_p = torch.cat([grad_p, torch.zeros_like(grad_p[:, :1])], dim=1)
+            return (grad_v, grad_x, grad_p) + (None,) * 10
+
+    _FN = (AggregateFunction, AggregatePositionFunction)
     return _FN
 
 
@@ -178,11 +278,17 @@ _FN = None
 
 
 def aggregate_autograd(backend, points, values, radius, op="sum", weight="one", self_=False, fluid_only=False, delta=False, moments=False,
-                       check_state=True):
+                       check_state=True, positions=None, points_grad=False, points_leaf=None):
     """aggregate() (points None) or query_aggregate() of `backend` as a differentiable function of `values`, a float32 torch tensor of
-    (n, C) on the backend's device.  The forward output has the bytes of aggregate(..., device=True).  Differentiable in values only, and
-    once differentiable: a double backward raises.  check_state: the forward stores the backend's digest of the particle state and the
-    backward raises SphError if it has changed; False skips both reads."""
+    (n, C) on the backend's device.  The forward output has the bytes of aggregate(..., device=True).  Once differentiable: a double
+    backward raises.  check_state: the forward stores the backend's digest of the particle state and the backward raises SphError if it
+    has changed; False skips both reads.
+    positions: None (differentiable in values only: the same Function, calls and bytes as without the keyword), or an (n, 3) float32
+    tensor on the backend's device that holds the backend's positions (backend.positions()); it takes part in the graph and receives
+    dL/dx (module docstring).  With check_state the forward verifies that it holds the backend's positions byte for byte and raises
+    SphError otherwise.  points_grad (query targets): `points` must be a float32 torch tensor of (m, 3) or (m, 4) and receives the points'
+    gradient (a fourth column gets zeros); without it a points tensor that requires grad still gets None.  points_leaf: the tensor
+    that receives it where `points` is a copy in the backend's layout (SPHFluidGPU.query_aggregate_autograd passes both)."""
     import torch
     if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2:
         raise SphError("aggregate_autograd: values must be a float32 torch tensor of shape (n, C)")
@@ -192,7 +298,20 @@ def aggregate_autograd(backend, points, values, radius, op="sum", weight="one", 
         raise SphError("aggregate_autograd: moments go with op 'sum' only")
     if points is not None and (self_ or delta):
         raise SphError("aggregate_autograd: self_ and delta apply to particle targets only")
-    return _function().apply(values, backend, points, float(radius), op, weight, bool(self_), bool(fluid_only), bool(delta), bool(moments), bool(check_state))
+    args = (float(radius), op, weight, bool(self_), bool(fluid_only), bool(delta), bool(moments), bool(check_state))
+    if positions is None and not points_grad:
+        return _function()[0].apply(values, backend, points, *args)
+    if positions is not None and (not isinstance(positions, torch.Tensor) or positions.dtype != torch.float32 or tuple(positions.shape) != (int(values.shape[0]), 3)
+                                  or positions.device != values.device):
+        raise SphError("aggregate_autograd: positions must be a float32 torch tensor of shape (n, 3) on the device of values")
+    leaf = None
+    if points_grad:
+        points_leaf = points if points_leaf is None else points_leaf
+        if points is None or not isinstance(points_leaf, torch.Tensor) or points_leaf.dtype != torch.float32 or points_leaf.dim() != 2 or int(points_leaf.shape[1]) not in (3, 4):
+            raise SphError("aggregate_autograd: points_grad takes the query points as a float32 torch tensor of shape (m, 3) or (m, 4)")
+        leaf = points_leaf
+    plain = points.detach() if isinstance(points, torch.Tensor) else points
+    return _function()[1].apply(values, positions, leaf, backend, plain, *args)
 
 
 def _conv_blocks(rows, planes, cin, max_basis_bytes):

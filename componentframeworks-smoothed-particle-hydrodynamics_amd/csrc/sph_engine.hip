@@ -29,6 +29,7 @@
 #include "sph_knn.h"
 #include "sph_aggregate.h"
 #include "sph_conv.h"
+#include "sph_posgrad.h"
 #include "sph_shell.h"
 #include "sph_aniso.h"
 #include "sph_rays.h"
@@ -367,6 +368,7 @@ struct SphEngine {
     DevBuf<uint32_t> d_adjCount, d_adjSums, d_adjStart, d_adjTmp, d_adjPerm, d_adjArg;
     DevBuf<float4> d_adjPts;
     DevBuf<float> d_adjIn;
+    DevBuf<float> d_posStage;               // sph_aggregate_posgrad_*: g in slot order (particle targets) or in binned order (query targets)
     int optAggVariant = 0;                  // SPH_OPT_AGGREGATE_VARIANT: bit 0 gather by id (no stage), bits 1-2 channels per pass, bit 3 4-byte loads (same bits)
     // sph_shell_*: the rows by particle id (or by query point) and the ids of the shell; per sorted slot the normal with the shell flag and the
     // compacted shell slots of pass 2; the flag words by row and by slot with their scan (offsets); the two words of the reduction
@@ -671,7 +673,7 @@ void shell_free(SphEngine* e) {
 void aggregate_free(SphEngine* e) {
     e->d_aggStage.release(); e->d_aggIn.release(); e->d_aggOut.release(); e->d_aggCnt.release();
     e->d_adjKey.release(); e->d_adjCount.release(); e->d_adjSums.release(); e->d_adjStart.release(); e->d_adjTmp.release(); e->d_adjPerm.release();
-    e->d_adjArg.release(); e->d_adjPts.release(); e->d_adjIn.release();
+    e->d_adjArg.release(); e->d_adjPts.release(); e->d_adjIn.release(); e->d_posStage.release();
 }
 void aniso_free(SphEngine* e) {
     e->d_anRows.release(); e->d_anSlots.release(); e->d_anStats.release();
@@ -5513,6 +5515,207 @@ int sph_aggregate_basis_adjoint_host(const SphParticle* particles, size_t n, con
                 for (int t = 0; t < 8; ++t) acc[c] = sph::basis_add(acc[c], coef[t], hrow[(size_t)b[t] * C + c]);
         });
         memcpy(out + r * C, acc.data(), C * sizeof(float));
+    }
+    return SPH_OK;
+}
+
+// ---- position gradients of the neighbourhood sums (sph_posgrad.h) ----------------
+// Do the outputs (either may be null) share an address with an input or with each other?
+static bool posgrad_overlap(const float* outPoints, size_t ptBytes, const float* outParticles, size_t paBytes, const void* values, size_t valBytes, const void* g,
+                            size_t gBytes, const void* points, size_t pointBytes) {
+    const float* outs[2] = {outPoints, outParticles};
+    const size_t bytes[2] = {outPoints ? ptBytes : 0, outParticles ? paBytes : 0};
+    for (int o = 0; o < 2; ++o)
+        if (ranges_overlap(outs[o], bytes[o], values, valBytes) || ranges_overlap(outs[o], bytes[o], g, gBytes) || ranges_overlap(outs[o], bytes[o], points, pointBytes))
+            return true;
+    return ranges_overlap(outs[0], bytes[0], outs[1], bytes[1]);
+}
+// Has the config no dependence on the positions?  (ONE without MOMENTS: out is a plain sum of values; its cutoff is not differentiated.)
+static bool posgrad_constant(const SphAggregateConfig& c) { return c.weight == SPH_AGGREGATE_WEIGHT_ONE && !(c.flags & SPH_AGGREGATE_MOMENTS); }
+
+// Grid of the current state, ids, the stages (values and g into slot order; for the particles' side of query targets the points binned
+// and g into binned order), the walks.  Query targets: a null output's walk is not launched.  No synchronisation.
+static int posgrad_run(SphEngine* e, bool query, const SphAggregateConfig* cfg, const float4* devPoints, size_t m, const float* devValues, const float* devG,
+                       float* devOutPoints, float* devOutParticles, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = adjoint_check(*cfg, g.cellSize, query, false, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    if (query && !devOutPoints && !devOutParticles) return fail(SPH_ERR_ARG, "both outputs are null");
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (!query && n && !devOutParticles) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!devValues || !devG || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (planes * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, planes, C);
+    const size_t gBytes = rows * planes * C * sizeof(float), valBytes = n * C * sizeof(float), ptBytes = query ? m * 3 * sizeof(float) : 0, paBytes = n * 3 * sizeof(float);
+    if (posgrad_overlap(query ? devOutPoints : nullptr, ptBytes, devOutParticles, paBytes, devValues, valBytes, devG, gBytes, devPoints, query ? m * sizeof(float4) : 0))
+        return fail(SPH_ERR_ARG, "an output overlaps the values, g, the points or the other output");
+    SphAggregateInfo info{};
+    info.rows = rows; info.channels = cfg->channels; info.planes = (int32_t)planes; info.stencil = stencil; info.flags = cfg->flags; info.radius = cfg->radius;
+    *out = info;
+    if (!n) return SPH_OK;
+    if (!rows || posgrad_constant(*cfg)) {                               // no query point, or nothing depends on the positions: every row is +0
+        if (devOutParticles) HIP_TRY(hipMemsetAsync(devOutParticles, 0, paBytes, e->stream));
+        if (query && devOutPoints && rows) HIP_TRY(hipMemsetAsync(devOutPoints, 0, ptBytes, e->stream));
+        return SPH_OK;
+    }
+    const bool targets = !query || devOutPoints, candidates = query && devOutParticles;
+    if ((rc = e->d_slotIds.grow(e, n)) || (targets && (rc = e->d_aggStage.grow(e, n * C))) || ((!query || candidates) && (rc = e->d_posStage.grow(e, rows * planes * C))) ||
+        (candidates && (rc = adjoint_bin_grow(e, m, (size_t)g.numCells)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const PosK pk{cfg->weight, cfg->channels, (!query && (cfg->flags & SPH_AGGREGATE_DELTA)) ? 1 : 0, posgrad_group_shift(cfg->channels)};
+    const bool moments = planes == 4, two = cfg->channels > kPosMaxGroup;
+    slot_ids_fill(e);
+    if (candidates && (rc = adjoint_bin(e, k, devPoints, m))) return rc;
+    const int32_t* ids = (const int32_t*)e->d_slotIds.p;
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (targets) hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * C)), dim3(kBlock), 0, e->stream, ids, devValues, e->d_aggStage.p, (uint32_t)n, cfg->channels);
+        if (!query)
+            hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * planes * C)), dim3(kBlock), 0, e->stream, ids, devG, e->d_posStage.p, (uint32_t)n, (int)(planes * C));
+        if (candidates)
+            hipLaunchKernelGGL(k_adjoint_stage, dim3(blocks_for(m * planes * C)), dim3(kBlock), 0, e->stream, (const uint32_t*)e->d_adjPerm.p,
+                               (const uint32_t*)e->d_adjStart.p + k.numCells, reinterpret_cast<const uint32_t*>(devG), reinterpret_cast<uint32_t*>(e->d_posStage.p),
+                               (uint32_t)m, (int)(planes * C));
+    }
+    using Kernel = void (*)(SimK, NbK, PosK, const float4*, const uint32_t*, const int32_t*, const float4*, const float4*, size_t, AdjRows, const float*, const float*, float*);
+    auto pick = [&](auto mode) -> Kernel {
+        constexpr int MODE = decltype(mode)::value;
+        if (moments) return two ? (Kernel)k_aggregate_posgrad<MODE, true, 2> : (Kernel)k_aggregate_posgrad<MODE, true, 1>;
+        return two ? (Kernel)k_aggregate_posgrad<MODE, false, 2> : (Kernel)k_aggregate_posgrad<MODE, false, 1>;
+    };
+    const float4 *pv = (const float4*)e->d_sPV, *own = (const float4*)e->d_sOwn;
+    const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
+    const AdjRows none{nullptr, nullptr, 0u};
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (!query)
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosParticles>{}), dim3(blocks_for(n << pk.gshift)), dim3(kBlock), 0, e->stream, k, nb, pk, pv, cellStart, ids,
+                               own, (const float4*)nullptr, n, none, (const float*)e->d_aggStage.p, (const float*)e->d_posStage.p, devOutParticles);
+        if (query && targets)
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosPoints>{}), dim3(blocks_for(m << pk.gshift)), dim3(kBlock), 0, e->stream, k, nb, pk, pv, cellStart, ids,
+                               own, devPoints, m, none, (const float*)e->d_aggStage.p, devG, devOutPoints);
+        if (candidates) {
+            const AdjRows R{(const float4*)e->d_adjPts.p, (const uint32_t*)e->d_adjStart.p, (uint32_t)m};
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosCandidates>{}), dim3(blocks_for(n << pk.gshift)), dim3(kBlock), 0, e->stream, k, nb, pk, pv, cellStart,
+                               ids, own, (const float4*)nullptr, n, R, devValues, (const float*)e->d_posStage.p, devOutParticles);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_posgrad_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, const float* devG, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return posgrad_run(e, false, cfg, nullptr, 0, devValues, devG, nullptr, devOut, info);
+}
+
+int sph_aggregate_posgrad_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                float* devOutPoints, float* devOutParticles, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return posgrad_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devValues, devG, devOutPoints, devOutParticles, info);
+}
+
+// Host memory in and out through engine scratch, as sph_aggregate_adjoint_staged: the uploads, the device call, the downloads, one
+// synchronisation.  d_aggOut holds the points' rows, then the particles'.
+int sph_aggregate_posgrad_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* values, const float* g, float* outPoints,
+                                 float* outParticles, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo grid;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, grid)) || (rc = adjoint_check(*cfg, grid.cellSize, query, false, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    if (query ? (!outPoints && !outParticles) : (e->n && !outParticles)) return fail(SPH_ERR_ARG, query ? "both outputs are null" : "null argument");
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (rows > ((size_t)-1) / (planes * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, planes, C);
+    const size_t gWords = rows * planes * C, ptWords = query ? m * 3 : 0;
+    if (n && rows && (!values || !g)) return fail(SPH_ERR_ARG, "null argument");
+    if (n && ((rc = e->d_aggIn.grow(e, n * C)) || (rc = e->d_adjIn.grow(e, gWords + 1)) || (rc = e->d_aggOut.grow(e, ptWords + n * 3)) ||
+              (query && (rc = e->d_sampleIn.grow(e, m + 1))))) return rc;
+    if (n && rows) HIP_TRY(hipMemcpyAsync(e->d_aggIn.p, values, n * C * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && gWords) HIP_TRY(hipMemcpyAsync(e->d_adjIn.p, g, gWords * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && query && m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    float *dPoints = (n && query && outPoints) ? e->d_aggOut.p : nullptr, *dParticles = (n && outParticles) ? e->d_aggOut.p + ptWords : nullptr;
+    if (!n) { dPoints = outPoints; dParticles = outParticles; }         // (nothing is written: only the null checks read them)
+    if ((rc = posgrad_run(e, query, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, e->d_aggIn.p, e->d_adjIn.p, dPoints, dParticles, info))) return rc;
+    if (n && dPoints && ptWords) HIP_TRY(hipMemcpyAsync(outPoints, dPoints, ptWords * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (n && dParticles) HIP_TRY(hipMemcpyAsync(outParticles, dParticles, n * 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_aggregate_posgrad_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                               const float* values, const float* g, float* outPoints, float* outParticles) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = adjoint_host_open(particles, n, params, cfg, query, m, false, k, &stencil))) return rc;
+    if (query && !outPoints && !outParticles) return fail(SPH_ERR_ARG, "both outputs are null");
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, planes = (size_t)aggregate_planes(*cfg);
+    if (!query && n && !outParticles) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!values || !g)) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (planes * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, planes, C);
+    if (posgrad_overlap(query ? outPoints : nullptr, query ? m * 3 * sizeof(float) : 0, outParticles, n * 3 * sizeof(float), values, n * C * sizeof(float), g,
+                        rows * planes * C * sizeof(float), points4, query ? m * 4 * sizeof(float) : 0))
+        return fail(SPH_ERR_ARG, "an output overlaps the values, g, the points or the other output");
+    if (!n) return SPH_OK;
+    if (outParticles) memset(outParticles, 0, n * 3 * sizeof(float));
+    if (query && outPoints && m) memset(outPoints, 0, m * 3 * sizeof(float));
+    if (!rows || posgrad_constant(*cfg)) return SPH_OK;
+    const float R2 = cfg->radius * cfg->radius;
+    const bool fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0, delta = !query && (cfg->flags & SPH_AGGREGATE_DELTA) != 0, moments = planes == 4;
+    const int Ci = cfg->channels, P = (int)planes;
+    const sph::HostGrid grid(k, particles, n);
+    if (!query || outPoints) {
+        for (size_t r = 0; r < rows; ++r) {
+            const float* x = query ? points4 + 4 * r : particles[r].pos;
+            const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+            if (!walk) continue;
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+            const float* gr = g + r * planes * C;
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
+                    if (!query && j == grid.slotOf[r]) continue;          // the own slot's two terms are equal
+                    const size_t ci = grid.order[j];
+                    const SphParticle& cand = particles[ci];
+                    float dx, dy, dz, r2;
+                    if (!sph::aggregate_accept(false, false, x[0], x[1], x[2], cand.pos[0], cand.pos[1], cand.pos[2], R2, dx, dy, dz, r2)) continue;
+                    if (fluidOnly && cand.isGhost != 0) continue;
+                    const float* vj = values + ci * C;
+                    float s[4], e[3];
+                    sph::posgrad_dots_host(Ci, P, delta, gr, vj, query ? nullptr : values + r * C, s);
+                    sph::posgrad_pair(moments, cfg->weight, R2, r2, dx, dy, dz, s, e);
+                    if (query) {
+                        for (int a = 0; a < 3; ++a) acc[a] = acc[a] - e[a];
+                    } else {
+                        float b[3];
+                        sph::posgrad_dots_host(Ci, P, delta, g + ci * planes * C, values + r * C, vj, s);
+                        sph::posgrad_pair(moments, cfg->weight, R2, r2, -dx, -dy, -dz, s, b);
+                        for (int a = 0; a < 3; ++a) acc[a] = acc[a] + (b[a] - e[a]);
+                    }
+                }
+            });
+            memcpy((query ? outPoints : outParticles) + r * 3, acc, sizeof(acc));
+        }
+    }
+    if (query && outParticles) {
+        const sph::AdjHostRows table(k, points4, m);
+        for (size_t r = 0; r < n; ++r) {
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+            sph::adjoint_walk_host(k, stencil, table, particles, points4, r, R2, false, fluidOnly, [&](size_t row, float dx, float dy, float dz, float r2) {
+                float s[4], e[3];
+                sph::posgrad_dots_host(Ci, P, false, g + row * planes * C, values + r * C, nullptr, s);
+                sph::posgrad_pair(moments, cfg->weight, R2, r2, dx, dy, dz, s, e);
+                for (int a = 0; a < 3; ++a) acc[a] = acc[a] + e[a];
+            });
+            memcpy(outParticles + r * 3, acc, sizeof(acc));
+        }
     }
     return SPH_OK;
 }

@@ -764,6 +764,10 @@ _ABI = {
     "sph_aggregate_basis_adjoint_query": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_basis_adjoint_staged": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_basis_adjoint_host": (_int, [_vp, _sz, _pp, _P(SphBasisConfig), _vp, _sz, _vp, _vp]),
+    "sph_aggregate_posgrad_particles": (_int, [_vp, _P(SphAggregateConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_posgrad_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_posgrad_staged": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_posgrad_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -1964,25 +1968,99 @@ class SPHFluidGPU:
         self.sync()
         return out if device else out.cpu().numpy()
 
+    # -- position gradients of the neighbourhood sums (include/sph_abi.h "position gradients of the neighbourhood sums") --
+    def positions(self, device: bool = False):
+        """The current positions by particle id as (n, 3) float32: a numpy array, or with device=True a fresh torch device tensor (what
+        aggregate_autograd(positions=...) hangs the position gradient on)."""
+        if not device:
+            return np.ascontiguousarray(self.download()["pos"][:, :3])
+        import torch
+        buf = torch.empty((self.GetNumFluids(), 4), dtype=torch.float32, device="cuda")
+        torch.cuda.current_stream().synchronize()
+        if buf.numel():
+            self.pack_render_buffer(buf.data_ptr())
+        self.sync()
+        return buf[:, :3].contiguous()
+
+    def aggregate_position_grad(self, values, grad, radius=None, weight="one", self_=False, fluid_only=False, delta=False, moments=False,
+                                device: bool = False):
+        """d/dx of L = sum(grad * aggregate(values, op="sum", ...)) with the same arguments: (n, 3) float32 by particle id.  values (n, C)
+        as aggregate(); grad (n, C), or (n, 4, C) with moments, as aggregate_adjoint().  Row k sums, over k's neighbours in ascending
+        sorted slot, the pair terms of both directions with the forward's own offsets and weights: no edge list,
+        no float atomics, the same bytes on every run.  The cutoff is not differentiated; weight "one" without moments gives zeros.
+        Streams as aggregate()."""
+        return self._posgrad(None, values, grad, self._radius(radius), weight, self_, fluid_only, delta, moments, True, True, device)[1]
+
+    def query_aggregate_position_grad(self, points, values, grad, radius, weight="one", fluid_only=False, moments=False, device: bool = False,
+                                      want_points: bool = True, want_particles: bool = True):
+        """The same for query_aggregate(points, values, op="sum", ...): (grad_points (m, 3), grad_particles (n, 3)); grad is (m, C) or
+        (m, 4, C).  grad_points row i sums over the row's candidates in the forward's order, grad_particles row k over the points that
+        accept particle k in ascending (clamped cell of the point, point index).  want_points / want_particles False: that walk is not
+        launched and None stands in its place (not both)."""
+        return self._posgrad(_device_points4(points, "query_aggregate_position_grad"), values, grad, radius, weight, False, fluid_only, False, moments,
+                             want_points, want_particles, device)
+
+    def _posgrad(self, dev_points, values, grad, radius, weight, self_, fluid_only, delta, moments, want_points, want_particles, device):
+        import torch
+        vals = _device_values(values, "aggregate_position_grad")
+        n, c = int(vals.shape[0]), int(vals.shape[1])
+        if n != self.GetNumFluids():
+            raise SphError(f"aggregate_position_grad: {n} rows of values for {self.GetNumFluids()} particles")
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        g = _device_planes(grad, rows, moments, "aggregate_position_grad")
+        if int(g.shape[-1]) != c:
+            raise SphError(f"aggregate_position_grad: grad of shape {tuple(g.shape)} for values of shape {(n, c)}")
+        cfg = _aggregate_cfg(radius, "sum", weight, c, self_, fluid_only, delta, moments)
+        out_pts = torch.empty((rows, 3), dtype=torch.float32, device="cuda") if dev_points is not None and want_points else None
+        out_par = torch.empty((n, 3), dtype=torch.float32, device="cuda") if want_particles else None
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        L, h, p = self._L, self._h, C.byref(cfg)
+        if dev_points is None:
+            _check(L.sph_aggregate_posgrad_particles(h, p, _tensor_ptr(vals), _tensor_ptr(g), _tensor_ptr(out_par), C.byref(info)))
+        else:
+            # (an output of no rows still goes as a non-null pointer: null means "not wanted")
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if t.numel() else _NO_POINT.ctypes.data)
+            _check(L.sph_aggregate_posgrad_query(h, p, _tensor_ptr(dev_points), rows, _tensor_ptr(vals), _tensor_ptr(g), ptr(out_pts), ptr(out_par), C.byref(info)))
+        self.sync()
+        if not device:
+            out_pts, out_par = (None if t is None else t.cpu().numpy() for t in (out_pts, out_par))
+        return out_pts, out_par
+
     def aggregate_autograd(self, values, radius=None, op="sum", weight="one", self_=False, fluid_only=False, delta=False, moments=False,
-                           check_state: bool = True):
+                           check_state: bool = True, positions=None):
         """aggregate() as a torch.autograd.Function: values is a float32 torch device tensor of (n, C) that may require grad, the result
         has the bytes of aggregate(..., device=True) and carries a graph whose backward is the engine's adjoint (sum: aggregate_adjoint;
         mean: the adjoint of grad / W; max / min: aggregate_route through the winners of aggregate_arg), so no edge list is built.
-        Differentiable in values only (the positions are the engine's state, not a tensor) and once differentiable: a backward of the
-        backward raises.  check_state: the forward stores state_digest(["particles"]) and the backward raises SphError if it has
-        changed, because a dispatch in between would silently give the adjoint of another neighbour relation; each of the two reads
-        checksums the particle section on the device and synchronises (about the cost of one download-free pass over the records).
-        False skips both.  See autograd.py for the formulas."""
+        Once differentiable: a backward of the backward raises.  positions: None (differentiable in values only), or the (n, 3)
+        tensor of positions(device=True), which then takes part in the graph and receives dL/dx through aggregate_position_grad
+        (zeros for max / min; the cutoff is not differentiated).  check_state: the forward stores
+        state_digest(["particles"]) and the backward raises SphError if it has changed, because a dispatch in between would silently give
+        the adjoint of another neighbour relation; each of the two reads checksums the particle section on the device and synchronises
+        (about the cost of one download-free pass over the records); with positions the forward also verifies that the tensor holds
+        the engine's positions byte for byte.  False skips all of it.  See autograd.py for the formulas."""
         from .autograd import EngineAggregateBackend, aggregate_autograd
-        return aggregate_autograd(EngineAggregateBackend(self), None, values, self._radius(radius), op, weight, self_, fluid_only, delta, moments, check_state)
+        return aggregate_autograd(EngineAggregateBackend(self), None, values, self._radius(radius), op, weight, self_, fluid_only, delta, moments, check_state,
+                                  positions=positions)
 
-    def query_aggregate_autograd(self, points, values, radius, op="sum", weight="one", fluid_only=False, moments=False, check_state: bool = True):
+    def query_aggregate_autograd(self, points, values, radius, op="sum", weight="one", fluid_only=False, moments=False, check_state: bool = True,
+                                 positions=None, points_grad: bool = False):
         """query_aggregate() as a torch.autograd.Function of values ((n, C) on the device); the result is (m, C) or (m, 4, C).  The backward
-        is query_aggregate_adjoint / query_aggregate_route.  Everything else as aggregate_autograd()."""
+        is query_aggregate_adjoint / query_aggregate_route.  positions as aggregate_autograd(); points_grad=True: points must be a float32
+        torch device tensor of (m, 3) or (m, 4) and receives the points' gradient of query_aggregate_position_grad (without it a points
+        tensor that requires grad still gets None).  Everything else as aggregate_autograd()."""
+        import torch
         from .autograd import EngineAggregateBackend, aggregate_autograd
+        leaf = None
+        if points_grad:
+            if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or int(points.shape[1]) not in (3, 4):
+                raise SphError("query_aggregate_autograd: points_grad takes the query points as a float32 torch device tensor of shape (m, 3) or (m, 4)")
+            leaf = points
+            flat = points.detach()
+            points = flat.contiguous() if int(flat.shape[1]) == 4 else torch.cat([flat, torch.zeros_like(flat[:, :1])], dim=1).contiguous()
         return aggregate_autograd(EngineAggregateBackend(self), _device_points4(points, "query_aggregate_autograd"), values, radius, op, weight, False,
-                                  fluid_only, False, moments, check_state)
+                                  fluid_only, False, moments, check_state, positions=positions, points_grad=points_grad, points_leaf=leaf)
 
     def aggregate_arg(self, values, radius=None, op="max", self_=False, fluid_only=False, delta=False, counts=False, device: bool = False):
         """aggregate(op="max" | "min") and who won: (out, arg) or with counts=True (out, counts, arg).  out and counts are the bytes of
@@ -3087,6 +3165,25 @@ def aggregate_adjoint_host(records, params, grad, radius, points=None, weight="o
     out = np.zeros((head[1], c), np.float32)
     _check(load_library().sph_aggregate_adjoint_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(g), _ptr_or_none(out)))
     return out
+
+
+def aggregate_position_grad_host(records, params, values, grad, radius, points=None, weight="one", self_=False, fluid_only=False, delta=False,
+                                 moments=False):
+    """sph_aggregate_posgrad_host: the (n, 3) result of SPHFluidGPU.aggregate_position_grad (points None), or the pair (grad_points (m, 3),
+    grad_particles (n, 3)) of query_aggregate_position_grad, on host records, values and grad, computed on the CPU by the same per-term
+    functions in the same order: the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_position_grad_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    vals = _scalar_values(values, head[1])
+    c = int(vals.shape[1])
+    g = _planes(grad, rows, moments, "aggregate_position_grad_host")
+    if int(g.shape[-1]) != c:
+        raise SphError(f"aggregate_position_grad_host: grad of shape {g.shape} for values of shape {vals.shape}")
+    cfg = _aggregate_cfg(radius, "sum", weight, c, self_, fluid_only, delta, moments)
+    out_pts, out_par = np.zeros((rows if p4 is not None else 0, 3), np.float32), np.zeros((head[1], 3), np.float32)
+    _check(load_library().sph_aggregate_posgrad_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(g),
+                                                     None if p4 is None else _ptr(out_pts if len(out_pts) else _NO_POINT), _ptr(out_par if len(out_par) else _NO_POINT)))
+    return out_par if p4 is None else (out_pts, out_par)
 
 
 def aggregate_arg_host(records, params, values, radius, points=None, op="max", self_=False, fluid_only=False, delta=False, counts=False):

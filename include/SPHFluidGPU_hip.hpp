@@ -398,6 +398,47 @@ public:
         if (devPoints4) return !Check(sph_aggregate_route_query(engine, &cfg, devPoints4, m, devArg, devG, devOut, &out), "sph_aggregate_route_query");
         return !Check(sph_aggregate_route_particles(engine, &cfg, devArg, devG, devOut, &out), "sph_aggregate_route_particles");
     }
+    // Position gradients of the neighbourhood sums (sph_abi.h "position gradients of the neighbourhood sums"): with
+    // L = sum devG . Aggregate(devValues) under cfg (op SUM), devOut[n][3] = dL/dx of the particles; for query targets devOutPoints[m][3]
+    // and devOutParticles[n][3], either of which may be null (its walk is not launched).  DEVICE memory, no synchronisation, as Aggregate.
+    bool AggregatePositionGrad(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devValues, const float* devG, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_posgrad_particles(engine, &cfg, devValues, devG, devOut, &out), "sph_aggregate_posgrad_particles");
+    }
+    bool QueryAggregatePositionGrad(SphAggregateInfo& out, const SphAggregateConfig& cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                    float* devOutPoints, float* devOutParticles) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_posgrad_query(engine, &cfg, devPoints4, m, devValues, devG, devOutPoints, devOutParticles, &out), "sph_aggregate_posgrad_query");
+    }
+    // The same for HOST arrays (values n * channels floats, g rows * planes * channels): grad is sized to n * 3.  Synchronises.
+    bool AggregatePositionGrad(SphAggregateInfo& info, const SphAggregateConfig& cfg, const std::vector<float>& values, const std::vector<float>& g,
+                               std::vector<float>& grad) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine), planes = (cfg.flags & SPH_AGGREGATE_MOMENTS) ? 4 : 1;
+        if (cfg.channels < 1 || values.size() != n * size_t(cfg.channels) || g.size() != n * planes * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "AggregatePositionGrad: values.size() is not n * channels or g.size() is not n * planes * channels");
+        grad.assign(n * 3, 0.0f);
+        return !Check(sph_aggregate_posgrad_staged(engine, &cfg, nullptr, 0, values.data(), g.data(), nullptr, grad.data(), &info), "sph_aggregate_posgrad_staged");
+    }
+    // points4: m * 4 floats; gradPoints is sized to m * 3 and gradParticles to n * 3.
+    bool QueryAggregatePositionGrad(SphAggregateInfo& info, const SphAggregateConfig& cfg, const float* points4, size_t m, const std::vector<float>& values,
+                                    const std::vector<float>& g, std::vector<float>& gradPoints, std::vector<float>& gradParticles) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine), planes = (cfg.flags & SPH_AGGREGATE_MOMENTS) ? 4 : 1;
+        if (!points4 || cfg.channels < 1 || values.size() != n * size_t(cfg.channels) || g.size() != m * planes * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "QueryAggregatePositionGrad: null points, values.size() is not n * channels or g.size() is not m * planes * channels");
+        gradPoints.assign(m * 3 + 1, 0.0f);                            // (one spare float: the pointer of an empty result must not be null)
+        gradParticles.assign(n * 3 + 1, 0.0f);
+        const bool ok = !Check(sph_aggregate_posgrad_staged(engine, &cfg, points4, m, values.data(), g.data(), gradPoints.data(), gradParticles.data(), &info),
+                               "sph_aggregate_posgrad_staged");
+        gradPoints.resize(m * 3);
+        gradParticles.resize(n * 3);
+        return ok;
+    }
     // Filter-grid basis sums (sph_abi.h "filter-grid basis sums"): devOut[rows][K^3][channels] = the sums of
     // w * phi_b(x_j - x_i) * devValues[j][c] over the neighbours, the linear part of a continuous convolution (the caller multiplies by
     // the filters), and the exact transpose devH[rows][K^3][channels] -> devOut[n][channels].  cfg: sph_aggregate_basis_default's fields

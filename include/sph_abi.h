@@ -65,6 +65,7 @@ extern "C" {
 /* (still 4, additions only: sph_aggregate_adjoint_particles / _query / _staged / _host, sph_aggregate_arg_particles / _query / _host, sph_aggregate_route_particles / _query / _host -- the adjoint of the neighbourhood sums, extrema with their winners, routing through them) */
 /* (still 4, additions only: SPH_SLAB_FLAG_* -- names of the six bits of the z-slab exchange's flag word, values as before) */
 /* (still 4, additions only: SphBasisConfig, SPH_BASIS_GRID, sph_aggregate_basis_default / _particles / _query / _staged / _host, sph_aggregate_basis_adjoint_particles / _query / _staged / _host -- filter-grid basis sums: continuous convolutions without an edge list) */
+/* (still 4, additions only: sph_aggregate_posgrad_particles / _query / _staged / _host -- position gradients of the neighbourhood sums) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -1542,6 +1543,55 @@ int sph_aggregate_basis_adjoint_staged(SphEngine* e, const SphBasisConfig* cfg, 
 /* Host-only, no device: the same bytes.  points4 null: particle targets. */
 int sph_aggregate_basis_adjoint_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
                                      const float* h, float* out);
+
+/* ---- position gradients of the neighbourhood sums (no reference counterpart) -----------------------------------
+ * The SUM of sph_aggregate_* as a function of the POSITIONS: with values float32[n][C] (the forward's input) and g float32[rows][planes][C]
+ * (the upstream gradient: what the forward's out would be, as the adjoint takes it), the scalar is L = sum g . out, and these calls give
+ * dL/dx of the particles and, for query targets, of the query points.  Config: SphAggregateConfig under the forward's rules, op SUM
+ * (MEAN is composed above this layer), weight ONE or POLY6, any of SELF, FLUID_ONLY, DELTA, MOMENTS.  A query: no result is kept, no
+ * engine state is written, nothing enters a checkpoint.
+ * The pair term.  For a target i (a particle or a query point) and a candidate j that the forward accepts, with the forward's own bits
+ * of d = x_j - x_i, r2 and w, every product and sum fp32 and rounded on its own (no fused multiply-add):
+ *   val_c = v[j][c], with DELTA v[j][c] - v[i][c]                          (the forward's reduced value)
+ *   s_p   = sum_c g[i][p][c] * val_c, p = 0 .. planes - 1                  (the channel dot, order below)
+ *   w1    = 0 for ONE;  POLY6: t = R2 - r2, w1 = -6.0f * (t * t)
+ *   q     = s_0;  with MOMENTS q = ((s_0 + d_x * s_1) + d_y * s_2) + d_z * s_3
+ *   f     = w1 * q;  e_a = f * d_a;  with MOMENTS e_a = (f * d_a) + w * s_{1+a},  a = x, y, z
+ * e(i -> j) is dL/dd of that pair: it goes to x_j with + and to x_i with -.
+ * Order of the channel dot, a function of C alone: G = the smallest of 4, 8, 16, 32, 64 that holds C (64 for C > 64).  Lane l of G
+ * sums the channels c = l, l + G, .. ascending, part = part + g * val from +0 (+0 where it has no channel); then for off = 1, 2, 4, ..
+ * G / 2 every lane takes part[l] = part[l] + part[l xor off] (all lanes at once).  Every lane ends with the same bits; they are s_p.
+ * Particle targets, one output grad float32[n][3] by particle id: grad[k] = sum over k's accepted candidates j != k in ascending sorted
+ * slot of (e(j -> k) - e(k -> j)), acc_a = acc_a + (eIn_a - eOut_a) from +0.  e(k -> j) uses g[k] and val = v[j] (- v[k]) with d; e(j -> k)
+ * uses g[j] and val = v[k] (- v[j]) with -d (exact), the same r2 and w.  The relation is symmetric, so this one walk meets every pair
+ * that involves k.  Under SELF the own slot contributes nothing (its two terms are equal) and is skipped: SELF does not move a byte.
+ * Query targets, two outputs: gradPoints float32[m][3], row i = the sum over the row's accepted candidates in the forward's order,
+ * acc_a = acc_a - e_a(i -> j) from +0; gradParticles float32[n][3], row k = the sum over the rows i that accept k in the adjoint's row
+ * order (ascending (clamped cell of the point, point index)), acc_a = acc_a + e_a(i -> k), the points binned as there.  Either may be
+ * null: its walk is not launched.
+ * The forward's rules carry over: under FLUID_ONLY a ghost is neither a target nor a candidate, its rows are +0; a particle or a query
+ * point with a non-finite coordinate has +0 rows and contributes to nobody.  Every row of every output is written.  Weight ONE
+ * without MOMENTS does not depend on the positions: the outputs are zeroed without a walk, after the argument and state checks.
+ * The cutoff itself is not differentiated: the jump of ONE and of the moment planes at r = R is ignored, as every fixed-radius
+ * operator does; POLY6 and its derivative vanish there, so for POLY6 without MOMENTS the gradient is the true one.
+ * No float atomics; stores are lane-owned.  The same bytes on every run, and the bytes of sph_aggregate_posgrad_host, which runs the
+ * same per-term functions in the same order.  SPH_OPT_AGGREGATE_VARIANT does not reach these calls.
+ * Streams, the timing class (SPH_K_OTHER) and SPH_ERR_STATE (z-slab engines, SPH_OPT_GRID_BUILD 1; before any allocation) as the
+ * adjoint.  SPH_ERR_ARG: the adjoint's cases, a null values, an output that overlaps values, g, the points or the other output as
+ * address ranges, both query outputs null.  m = 0: gradParticles is zeroed.  n = 0: success, nothing is written.
+ * SphAggregateInfo: rows = those of g (n, or m), planes those of g. */
+/* Particle targets: devValues float32[n][channels], devG float32[n][planes][channels], devOut float32[n][3]. */
+int sph_aggregate_posgrad_particles(SphEngine* e, const SphAggregateConfig* cfg, const float* devValues, const float* devG, float* devOut, SphAggregateInfo* info);
+/* devPoints4: m query points (x, y, z, .) in device memory, never written; devG float32[m][planes][channels]; devOutPoints float32[m][3]
+ * or null; devOutParticles float32[n][3] or null. */
+int sph_aggregate_posgrad_query(SphEngine* e, const SphAggregateConfig* cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                float* devOutPoints, float* devOutParticles, SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets, outPoints is not read); synchronises. */
+int sph_aggregate_posgrad_staged(SphEngine* e, const SphAggregateConfig* cfg, const float* points4, size_t m, const float* values, const float* g, float* outPoints,
+                                 float* outParticles, SphAggregateInfo* info);
+/* Host-only, no device: the same bytes.  points4 null: particle targets (outPoints is not read). */
+int sph_aggregate_posgrad_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
+                               const float* values, const float* g, float* outPoints, float* outParticles);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
