@@ -46,7 +46,7 @@ from .engine import (  # noqa: F401
     SPH_AGGREGATE_WEIGHT_POLY6, SPH_AGGREGATE_SELF, SPH_AGGREGATE_FLUID_ONLY, SPH_AGGREGATE_DELTA, SPH_AGGREGATE_MOMENTS,
     SPH_AGGREGATE_MAX_CHANNELS, SphAggregateConfig, SphAggregateInfo, aggregate_config, aggregate_host,
     aggregate_adjoint_host, aggregate_arg_host, aggregate_route_host, aggregate_position_grad_host,
-    SPH_BASIS_GRID, SphBasisConfig, basis_config, aggregate_basis_host, aggregate_basis_adjoint_host,
+    SPH_BASIS_GRID, SphBasisConfig, basis_config, aggregate_basis_host, aggregate_basis_adjoint_host, aggregate_basis_position_grad_host,
     SPH_STATE_FORMAT, SPH_STATE_CHECKSUM_MIX64, SPH_STATE_MAGIC, STATE_SECTIONS, SphStateInfo, SphStateDigest, SphStateHeader, SphStateEntry, SphStateCore,
     STATE_HEADER_DTYPE, STATE_ENTRY_DTYPE, state_info, state_checksum_host, state_sections,
 )

@@ -2,7 +2,7 @@
 own adjoint, so that a loss over aggregate() needs no edge list.
 
 Differentiable in `values`, and with the keyword `positions` (and `points_grad` for query points) in the positions too (DESIGN.md
-section 3x); continuous_conv stays differentiable in x and the filters only.  Once differentiable.  The backward formulas are written
+section 3x), continuous_conv included.  Once differentiable.  The backward formulas are written
 against a small backend (forward, adjoint, arg, route, posgrad) that the engine implements on the device (EngineAggregateBackend) and
 the host twins implement on the CPU (HostAggregateBackend), so that they can be checked without a GPU:
 
@@ -25,6 +25,14 @@ input channels, (rows, B, cw), and F the block's filters as a (B * cw, Cout) mat
   backward   g' = g (g / W with normalize);  grad_filters = A^T @ g' per block, A recomputed rather than saved;
              grad_x = basis_adjoint((g' @ F^T).reshape(rows, B, cw)) per block
 The basis tensors and the adjoint have fixed bytes; the two matrix products are torch's, and no byte claim is made for them.
+
+With positions= (and points_grad= for query points) a second Function with the same forward calls adds, through the backend call
+basis_posgrad (the pair (points' rows or None, particles' rows), as posgrad):
+
+  positions  sum over the blocks of basis_posgrad(x[:, c0:c1], h_block), h_block the (g' @ F_block^T) tensor of grad_x;
+             with normalize and weight "poly6" plus the gradient through W: the one-channel posgrad of ones with the upstream
+             -sum_o g'[i][o] * out[i][o] (for weight "one" W is a count: that term is zero)
+With one block and no normalize the gradient is basis_posgrad's bytes; otherwise the parts are added by torch in block order.
 """
 from __future__ import annotations
 
@@ -33,7 +41,7 @@ import zlib
 import numpy as np
 
 from .engine import (SPH_AGGREGATE_MAX_CHANNELS, SphError, aggregate_adjoint_host, aggregate_arg_host, aggregate_basis_adjoint_host, aggregate_basis_host,
-                     aggregate_host, aggregate_position_grad_host, aggregate_route_host)
+                     aggregate_basis_position_grad_host, aggregate_host, aggregate_position_grad_host, aggregate_route_host)
 
 __all__ = ["EngineAggregateBackend", "HostAggregateBackend", "aggregate_autograd", "continuous_conv"]
 
@@ -88,6 +96,12 @@ class EngineAggregateBackend:
             return self.f.aggregate_basis_adjoint(h, radius, size=size, weight=weight, self_=self_, fluid_only=fluid_only, device=True)
         return self.f.query_aggregate_basis_adjoint(points, h, radius, size=size, weight=weight, fluid_only=fluid_only, device=True)
 
+    def basis_posgrad(self, points, x, grad, radius, size, weight, self_, fluid_only, want_points=True, want_particles=True):
+        if points is None:
+            return None, self.f.aggregate_basis_position_grad(x, grad, radius, size=size, weight=weight, self_=self_, fluid_only=fluid_only, device=True)
+        return self.f.query_aggregate_basis_position_grad(points, x, grad, radius, size=size, weight=weight, fluid_only=fluid_only, device=True,
+                                                          want_points=want_points, want_particles=want_particles)
+
 
 class HostAggregateBackend:
     """The same calls over the host twins on (records, params): CPU torch tensors in and out, the bytes the device gives.  No GPU."""
@@ -141,6 +155,14 @@ class HostAggregateBackend:
     def basis_adjoint(self, points, h, radius, size, weight, self_, fluid_only):
         return self._t(aggregate_basis_adjoint_host(self.records, self.params, self._np(h), radius, points=points, size=size, weight=weight, self_=self_,
                                                     fluid_only=fluid_only))
+
+    def basis_posgrad(self, points, x, grad, radius, size, weight, self_, fluid_only, want_points=True, want_particles=True):
+        res = aggregate_basis_position_grad_host(self.records, self.params, self._np(x), self._np(grad), radius, points=None if points is None else self._np(points),
+                                                 size=size, weight=weight, self_=self_, fluid_only=fluid_only, want_points=want_points,
+                                                 want_particles=want_particles)
+        if points is None:
+            return None, self._t(res)
+        return (None if res[0] is None else self._t(res[0])), (None if res[1] is None else self._t(res[1]))
 
 
 def _function():
@@ -337,50 +359,100 @@ def _conv_function():
         ok = (W != 0)[:, None]
         return torch.where(ok, t / torch.where(ok, W[:, None], torch.ones_like(W[:, None])), torch.zeros_like(t))
 
+    def conv_forward(ctx, x, filters, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks):
+        """The forward of both Functions: (out, the tensors the backward of x and the filters needs)."""
+        ctx.backend, ctx.points, ctx.radius, ctx.blocks = backend, points, radius, blocks
+        ctx.cfg = (weight, self_, fluid_only, normalize)
+        ctx.digest = backend.state() if check_state else None
+        ctx.check_state = check_state
+        xd, fd = x.detach(), filters.detach()
+        K, cout = int(fd.shape[0]), int(fd.shape[4])
+        out = None
+        for c0, c1 in blocks:
+            A = backend.basis(points, xd[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
+            part = A.reshape(A.shape[0], -1) @ fd[:, :, :, c0:c1, :].reshape(-1, cout)
+            out = part if out is None else out + part
+        W = weight_sum(backend, points, xd.shape[0], xd, radius, weight, self_, fluid_only) if normalize else xd.new_zeros(0)
+        return (divide(out, W) if normalize else out), (xd, fd, W)
+
     class ContinuousConvFunction(torch.autograd.Function):
         @staticmethod
         def forward(ctx, x, filters, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks):
-            ctx.backend, ctx.points, ctx.radius, ctx.blocks = backend, points, radius, blocks
-            ctx.cfg = (weight, self_, fluid_only, normalize)
-            ctx.digest = backend.state() if check_state else None
-            ctx.check_state = check_state
-            xd, fd = x.detach(), filters.detach()
-            K, cout = int(fd.shape[0]), int(fd.shape[4])
-            out = None
-            for c0, c1 in blocks:
-                A = backend.basis(points, xd[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
-                part = A.reshape(A.shape[0], -1) @ fd[:, :, :, c0:c1, :].reshape(-1, cout)
-                out = part if out is None else out + part
-            W = weight_sum(backend, points, xd.shape[0], xd, radius, weight, self_, fluid_only) if normalize else xd.new_zeros(0)
-            ctx.save_for_backward(xd, fd, W)
-            return divide(out, W) if normalize else out
+            out, saved = conv_forward(ctx, x, filters, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks)
+            ctx.save_for_backward(*saved)
+            return out
 
         @staticmethod
         @once_differentiable
         def backward(ctx, g):
-            weight, self_, fluid_only, normalize = ctx.cfg
-            backend, points, radius = ctx.backend, ctx.points, ctx.radius
-            if ctx.check_state and backend.state() != ctx.digest:
-                raise SphError("continuous_conv: the particle state changed between forward and backward (a dispatch, an upload or an impulse): "
-                               "the adjoint would be that of another neighbour relation")
-            x, filters, W = ctx.saved_tensors
-            K, cout = int(filters.shape[0]), int(filters.shape[4])
-            g = divide(g, W) if normalize else g
-            g = g.contiguous()
-            need_x, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            grad_x = torch.zeros_like(x) if need_x else None
-            grad_f = torch.zeros_like(filters) if need_f else None
-            for c0, c1 in ctx.blocks:
-                fblock = filters[:, :, :, c0:c1, :].reshape(-1, cout)
-                if need_f:
-                    A = backend.basis(points, x[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
-                    grad_f[:, :, :, c0:c1, :] = (A.reshape(A.shape[0], -1).t() @ g).reshape(K, K, K, c1 - c0, cout)
-                if need_x:
-                    h = (g @ fblock.t()).reshape(g.shape[0], K ** 3, c1 - c0).contiguous()
-                    grad_x[:, c0:c1] = backend.basis_adjoint(points, h, radius, K, weight, self_, fluid_only)
-            return (grad_x, grad_f) + (None,) * 9
+            return conv_backward(ctx, g, ctx.saved_tensors, False, False)[:2] + (None,) * 9
 
-    _CONV = ContinuousConvFunction
+    def conv_backward(ctx, g, saved, need_pos, need_pts):
+        """(grad_x, grad_filters, the points' rows or None, the particles' rows or None); the last two are asked for by need_pts / need_pos."""
+        weight, self_, fluid_only, normalize = ctx.cfg
+        backend, points, radius = ctx.backend, ctx.points, ctx.radius
+        if ctx.check_state and backend.state() != ctx.digest:
+            raise SphError("continuous_conv: the particle state changed between forward and backward (a dispatch, an upload or an impulse): "
+                           "the adjoint would be that of another neighbour relation")
+        x, filters, W = saved[:3]
+        K, cout = int(filters.shape[0]), int(filters.shape[4])
+        g = divide(g, W) if normalize else g
+        g = g.contiguous()
+        need_x, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        grad_x = torch.zeros_like(x) if need_x else None
+        grad_f = torch.zeros_like(filters) if need_f else None
+        grad_pts = grad_par = None
+        geometry = need_pos or need_pts
+        for c0, c1 in ctx.blocks:
+            fblock = filters[:, :, :, c0:c1, :].reshape(-1, cout)
+            if need_f:
+                A = backend.basis(points, x[:, c0:c1].contiguous(), radius, K, weight, self_, fluid_only)
+                grad_f[:, :, :, c0:c1, :] = (A.reshape(A.shape[0], -1).t() @ g).reshape(K, K, K, c1 - c0, cout)
+            if need_x or geometry:
+                h = (g @ fblock.t()).reshape(g.shape[0], K ** 3, c1 - c0).contiguous()
+            if need_x:
+                grad_x[:, c0:c1] = backend.basis_adjoint(points, h, radius, K, weight, self_, fluid_only)
+            if geometry:
+                pts, par = backend.basis_posgrad(points, x[:, c0:c1].contiguous(), h, radius, K, weight, self_, fluid_only, need_pts,
+                                                 need_pos or points is None)
+                grad_pts = pts if grad_pts is None or pts is None else grad_pts + pts
+                grad_par = par if grad_par is None or par is None else grad_par + par
+        if geometry and normalize and weight != "one":                              # the gradient through W = sum w * 1
+            out = saved[3]
+            up = (-(g * out).sum(dim=1, keepdim=True)).contiguous()
+            ones = torch.ones((int(x.shape[0]), 1), dtype=torch.float32, device=x.device)
+            pts, par = backend.posgrad(points, ones, up, radius, weight, self_, fluid_only, False, False, need_pts, need_pos or points is None)
+            grad_pts = None if grad_pts is None else grad_pts + pts
+            grad_par = None if grad_par is None else grad_par + par
+        return grad_x, grad_f, grad_pts, (grad_par if need_pos else None)
+
+    class ContinuousConvPositionFunction(torch.autograd.Function):
+        """The same forward with two more tensor inputs: positions (n, 3), which must hold the backend's positions, and the query points
+        as a tensor (or None).  The backward adds the position gradient."""
+
+        @staticmethod
+        def forward(ctx, x, filters, positions, points_leaf, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks):
+            if positions is not None and check_state:
+                mine = backend.positions()
+                theirs = positions.detach().contiguous()
+                if tuple(theirs.shape) != tuple(mine.shape) or not torch.equal(theirs.view(torch.int32), mine.view(torch.int32)):
+                    raise SphError("continuous_conv: positions does not hold the engine's positions byte for byte: the gradient would be that of another "
+                                   "configuration")
+            out, saved = conv_forward(ctx, x, filters, backend, points, radius, weight, self_, fluid_only, normalize, check_state, blocks)
+            ctx.leaf_width = 0 if points_leaf is None else int(points_leaf.shape[1])
+            ctx.save_for_backward(*saved, *((out,) if normalize else ()))           # (out enters the gradient through W)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            need_pos, need_pts = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+            grad_x, grad_f, grad_pts, grad_par = conv_backward(ctx, g, ctx.saved_tensors, need_pos, need_pts)
+            if need_pts and ctx.leaf_width == 4:
+                grad_pts = torch.cat([grad_pts, torch.zeros_like(grad_pts[:, :1])], dim=1)
+            return (grad_x, grad_f, grad_par, grad_pts) + (None,) * 9
+
+    _CONV = (ContinuousConvFunction, ContinuousConvPositionFunction)
     return _CONV
 
 
@@ -388,10 +460,12 @@ _CONV = None
 
 
 def continuous_conv(backend, points, x, filters, radius, weight="poly6", self_=True, fluid_only=False, normalize=False, check_state=True,
-                    max_basis_bytes=2 ** 31):
+                    max_basis_bytes=2 ** 31, positions=None, points_grad=False, points_leaf=None):
     """The continuous convolution of `backend` (points None: particle targets) as a differentiable function of x, float32 (n, Cin), and
     filters, float32 (K, K, K, Cin, Cout) with axes (z, y, x) and K in 2 .. 4, both on the backend's device: (rows, Cout).  Once
-    differentiable in both.  The module docstring has the formulas; SPHFluidGPU.continuous_conv the arguments."""
+    differentiable in both.  positions, points_grad, points_leaf as aggregate_autograd(): with them the positions (and the query points)
+    take part in the graph; with both at their defaults the Function, the backend calls and the bytes are those of a call without
+    them.  The module docstring has the formulas; SPHFluidGPU.continuous_conv the arguments."""
     import torch
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2:
         raise SphError("continuous_conv: x must be a float32 torch tensor of shape (n, Cin)")
@@ -406,4 +480,17 @@ def continuous_conv(backend, points, x, filters, radius, weight="poly6", self_=T
         raise SphError("continuous_conv: self_ applies to particle targets only")
     rows = int(x.shape[0]) if points is None else int(points.shape[0])
     blocks = _conv_blocks(rows, K ** 3, cin, max_basis_bytes)
-    return _conv_function().apply(x, filters, backend, points, float(radius), weight, bool(self_), bool(fluid_only), bool(normalize), bool(check_state), blocks)
+    args = (float(radius), weight, bool(self_), bool(fluid_only), bool(normalize), bool(check_state), blocks)
+    if positions is None and not points_grad:
+        return _conv_function()[0].apply(x, filters, backend, points, *args)
+    if positions is not None and (not isinstance(positions, torch.Tensor) or positions.dtype != torch.float32 or tuple(positions.shape) != (int(x.shape[0]), 3)
+                                  or positions.device != x.device):
+        raise SphError("continuous_conv: positions must be a float32 torch tensor of shape (n, 3) on the device of x")
+    leaf = None
+    if points_grad:
+        points_leaf = points if points_leaf is None else points_leaf
+        if points is None or not isinstance(points_leaf, torch.Tensor) or points_leaf.dtype != torch.float32 or points_leaf.dim() != 2 or int(points_leaf.shape[1]) not in (3, 4):
+            raise SphError("continuous_conv: points_grad takes the query points as a float32 torch tensor of shape (m, 3) or (m, 4)")
+        leaf = points_leaf
+    plain = points.detach() if isinstance(points, torch.Tensor) else points
+    return _conv_function()[1].apply(x, filters, positions, leaf, backend, plain, *args)

@@ -34,6 +34,7 @@
 #ifndef SPH_AGGREGATE_H
 #error "sph_conv.h is built on sph_aggregate.h: include sph_aggregate.h before it"
 #endif
+#define SPH_CONV_H 1          // (sph_convgrad.h, which is built on this header, checks that it came first)
 
 namespace sph {
 

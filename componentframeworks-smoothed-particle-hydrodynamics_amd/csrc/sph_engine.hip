@@ -30,6 +30,7 @@
 #include "sph_aggregate.h"
 #include "sph_conv.h"
 #include "sph_posgrad.h"
+#include "sph_convgrad.h"
 #include "sph_shell.h"
 #include "sph_aniso.h"
 #include "sph_rays.h"
@@ -5712,6 +5713,178 @@ int sph_aggregate_posgrad_host(const SphParticle* particles, size_t n, const Sph
                 float s[4], e[3];
                 sph::posgrad_dots_host(Ci, P, false, g + row * planes * C, values + r * C, nullptr, s);
                 sph::posgrad_pair(moments, cfg->weight, R2, r2, dx, dy, dz, s, e);
+                for (int a = 0; a < 3; ++a) acc[a] = acc[a] + e[a];
+            });
+            memcpy(outParticles + r * 3, acc, sizeof(acc));
+        }
+    }
+    return SPH_OK;
+}
+
+// ---- position gradients of the basis sums (sph_convgrad.h) ----------------------
+// Grid of the current state, ids, the stage (values into slot order; for the particles' side of query targets the points binned), the
+// walks; g is read in place.  Query targets: a null output's walk is not launched.  No synchronisation.
+static int convgrad_run(SphEngine* e, bool query, const SphBasisConfig* cfg, const float4* devPoints, size_t m, const float* devValues, const float* devG,
+                        float* devOutPoints, float* devOutParticles, SphAggregateInfo* out) {
+    using namespace sph;
+    SimK k;
+    SphGridInfo g;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, g)) || (rc = basis_check(*cfg, g.cellSize, query, &stencil))) return rc;
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    if (query && !devOutPoints && !devOutParticles) return fail(SPH_ERR_ARG, "both outputs are null");
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (!query && n && !devOutParticles) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!devValues || !devG || (query && !devPoints))) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t gBytes = rows * B * C * sizeof(float), valBytes = n * C * sizeof(float), ptBytes = query ? m * 3 * sizeof(float) : 0, paBytes = n * 3 * sizeof(float);
+    if (posgrad_overlap(query ? devOutPoints : nullptr, ptBytes, devOutParticles, paBytes, devValues, valBytes, devG, gBytes, devPoints, query ? m * sizeof(float4) : 0))
+        return fail(SPH_ERR_ARG, "an output overlaps the values, g, the points or the other output");
+    basis_info(*cfg, rows, stencil, out);
+    if (!n) return SPH_OK;
+    if (!rows) {                                                        // no query point: every row is +0
+        if (devOutParticles) HIP_TRY(hipMemsetAsync(devOutParticles, 0, paBytes, e->stream));
+        return SPH_OK;
+    }
+    const bool targets = !query || devOutPoints, candidates = query && devOutParticles;
+    if ((rc = e->d_slotIds.grow(e, n)) || (targets && (rc = e->d_aggStage.grow(e, n * C))) || (candidates && (rc = adjoint_bin_grow(e, m, (size_t)g.numCells)))) return rc;
+    if ((rc = sample_grid(e, k))) return rc;
+    const NbK nb = make_nbk(e, cfg->radius, stencil, cfg->flags, e->n);
+    const BasisK bk = make_basisk(*cfg);
+    const bool two = cfg->channels > kPosMaxGroup;
+    slot_ids_fill(e);
+    if (candidates && (rc = adjoint_bin(e, k, devPoints, m))) return rc;
+    const int32_t* ids = (const int32_t*)e->d_slotIds.p;
+    if (targets) {
+        Timed t(e, SPH_K_OTHER);
+        hipLaunchKernelGGL(k_aggregate_stage, dim3(blocks_for(n * C)), dim3(kBlock), 0, e->stream, ids, devValues, e->d_aggStage.p, (uint32_t)n, cfg->channels);
+    }
+    const float4 *pv = (const float4*)e->d_sPV, *own = (const float4*)e->d_sOwn;
+    const uint32_t* cellStart = (const uint32_t*)e->d_cellStart;
+    const AdjRows none{nullptr, nullptr, 0u};
+    auto pick = [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        return two ? k_aggregate_basis_posgrad<MODE, 2> : k_aggregate_basis_posgrad<MODE, 1>;
+    };
+    {
+        Timed t(e, SPH_K_OTHER);
+        if (!query)
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosParticles>{}), dim3(blocks_for(n << bk.gshift)), dim3(kBlock), 0,
+                               e->stream, k, nb, bk, pv, cellStart, ids, own, (const float4*)nullptr, n, none, reinterpret_cast<const uint32_t*>(ids),
+                               (const float*)e->d_aggStage.p, devG, devOutParticles);
+        if (query && targets)
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosPoints>{}), dim3(blocks_for(m << bk.gshift)), dim3(kBlock), 0,
+                               e->stream, k, nb, bk, pv, cellStart, ids, own, devPoints, m, none, (const uint32_t*)nullptr, (const float*)e->d_aggStage.p, devG, devOutPoints);
+        if (candidates) {
+            const AdjRows R{(const float4*)e->d_adjPts.p, (const uint32_t*)e->d_adjStart.p, (uint32_t)m};
+            hipLaunchKernelGGL(pick(std::integral_constant<int, kPosCandidates>{}), dim3(blocks_for(n << bk.gshift)), dim3(kBlock),
+                               0, e->stream, k, nb, bk, pv, cellStart, ids, own, (const float4*)nullptr, n, R, (const uint32_t*)e->d_adjPerm.p, devValues, devG, devOutParticles);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+int sph_aggregate_basis_posgrad_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devValues, const float* devG, float* devOut, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return convgrad_run(e, false, cfg, nullptr, 0, devValues, devG, nullptr, devOut, info);
+}
+
+int sph_aggregate_basis_posgrad_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                      float* devOutPoints, float* devOutParticles, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    return convgrad_run(e, true, cfg, reinterpret_cast<const float4*>(devPoints4), m, devValues, devG, devOutPoints, devOutParticles, info);
+}
+
+// Host memory in and out through engine scratch, as sph_aggregate_posgrad_staged: the uploads, the device call, the downloads, one
+// synchronisation.  d_aggOut holds the points' rows, then the particles'.
+int sph_aggregate_basis_posgrad_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* values, const float* g, float* outPoints,
+                                       float* outParticles, SphAggregateInfo* info) {
+    if (!e) return fail(SPH_ERR_ARG, "null engine");
+    if (!cfg || !info) return fail(SPH_ERR_ARG, "null argument");
+    const bool query = points4 != nullptr;
+    SphGridInfo grid;
+    int rc, stencil = 0;
+    if ((rc = query_grid(e, grid)) || (rc = basis_check(*cfg, grid.cellSize, query, &stencil))) return rc;     // (the refusal, before any allocation)
+    if (query && m > 2147483647ull) return fail(SPH_ERR_ARG, "%zu query points (at most 2^31 - 1)", m);
+    if (query ? (!outPoints && !outParticles) : (e->n && !outParticles)) return fail(SPH_ERR_ARG, query ? "both outputs are null" : "null argument");
+    const size_t n = e->n, rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    const size_t gWords = rows * B * C, ptWords = query ? m * 3 : 0;
+    if (n && rows && (!values || !g)) return fail(SPH_ERR_ARG, "null argument");
+    if (n && ((rc = e->d_aggIn.grow(e, n * C)) || (rc = e->d_adjIn.grow(e, gWords + 1)) || (rc = e->d_aggOut.grow(e, ptWords + n * 3)) ||
+              (query && (rc = e->d_sampleIn.grow(e, m + 1))))) return rc;
+    if (n && rows) HIP_TRY(hipMemcpyAsync(e->d_aggIn.p, values, n * C * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && gWords) HIP_TRY(hipMemcpyAsync(e->d_adjIn.p, g, gWords * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (n && query && m) HIP_TRY(hipMemcpyAsync(e->d_sampleIn.p, points4, m * sizeof(float4), hipMemcpyHostToDevice, e->stream));
+    float *dPoints = (n && query && outPoints) ? e->d_aggOut.p : nullptr, *dParticles = (n && outParticles) ? e->d_aggOut.p + ptWords : nullptr;
+    if (!n) { dPoints = outPoints; dParticles = outParticles; }         // (nothing is written: only the null checks read them)
+    if ((rc = convgrad_run(e, query, cfg, query ? (const float4*)e->d_sampleIn.p : nullptr, query ? m : 0, e->d_aggIn.p, e->d_adjIn.p, dPoints, dParticles, info))) return rc;
+    if (n && dPoints && ptWords) HIP_TRY(hipMemcpyAsync(outPoints, dPoints, ptWords * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (n && dParticles) HIP_TRY(hipMemcpyAsync(outParticles, dParticles, n * 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SPH_OK;
+}
+
+int sph_aggregate_basis_posgrad_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                                     const float* values, const float* g, float* outPoints, float* outParticles) {
+    const bool query = points4 != nullptr;
+    SimK k;
+    int rc, stencil = 0;
+    if ((rc = basis_host_open(particles, n, params, cfg, query, m, k, &stencil))) return rc;
+    if (query && !outPoints && !outParticles) return fail(SPH_ERR_ARG, "both outputs are null");
+    const size_t rows = query ? m : n, C = (size_t)cfg->channels, B = basis_planes(*cfg);
+    if (!query && n && !outParticles) return fail(SPH_ERR_ARG, "null argument");
+    if (n && rows && (!values || !g)) return fail(SPH_ERR_ARG, "null argument");
+    if (rows > ((size_t)-1) / (B * C * sizeof(float))) return fail(SPH_ERR_ARG, "%zu rows of %zu x %zu floats exceed size_t", rows, B, C);
+    if (posgrad_overlap(query ? outPoints : nullptr, query ? m * 3 * sizeof(float) : 0, outParticles, n * 3 * sizeof(float), values, n * C * sizeof(float), g,
+                        rows * B * C * sizeof(float), points4, query ? m * 4 * sizeof(float) : 0))
+        return fail(SPH_ERR_ARG, "an output overlaps the values, g, the points or the other output");
+    if (!n) return SPH_OK;
+    if (outParticles) memset(outParticles, 0, n * 3 * sizeof(float));
+    if (query && outPoints && m) memset(outPoints, 0, m * 3 * sizeof(float));
+    if (!rows) return SPH_OK;
+    const float R2 = cfg->radius * cfg->radius;
+    const bool fluidOnly = (cfg->flags & SPH_AGGREGATE_FLUID_ONLY) != 0;
+    const sph::BasisK bk = make_basisk(*cfg);
+    const sph::HostGrid grid(k, particles, n);
+    if (!query || outPoints) {
+        for (size_t r = 0; r < rows; ++r) {
+            const float* x = query ? points4 + 4 * r : particles[r].pos;
+            const bool walk = query ? (sph::float_finite(x[0]) && sph::float_finite(x[1]) && sph::float_finite(x[2])) : !(fluidOnly && particles[r].isGhost != 0);
+            if (!walk) continue;
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+            const float* gr = g + r * B * C;
+            grid.rows(stencil, x, [&](uint32_t qs, uint32_t qe) {
+                for (uint32_t j = qs; j < qe; ++j) {
+                    if (!query && j == grid.slotOf[r]) continue;          // the own slot: d = x_i - x_i, which no position moves
+                    const size_t ci = grid.order[j];
+                    const SphParticle& cand = particles[ci];
+                    float dx, dy, dz, r2, e[3];
+                    if (!sph::aggregate_accept(false, false, x[0], x[1], x[2], cand.pos[0], cand.pos[1], cand.pos[2], R2, dx, dy, dz, r2)) continue;
+                    if (fluidOnly && cand.isGhost != 0) continue;
+                    sph::convgrad_pair_host(bk, R2, dx, dy, dz, r2, gr, values + ci * C, e);
+                    if (query) {
+                        for (int a = 0; a < 3; ++a) acc[a] = acc[a] - e[a];
+                    } else {
+                        float b[3];
+                        sph::convgrad_pair_host(bk, R2, -dx, -dy, -dz, r2, g + ci * B * C, values + r * C, b);
+                        for (int a = 0; a < 3; ++a) acc[a] = acc[a] + (b[a] - e[a]);
+                    }
+                }
+            });
+            memcpy((query ? outPoints : outParticles) + r * 3, acc, sizeof(acc));
+        }
+    }
+    if (query && outParticles) {
+        const sph::AdjHostRows table(k, points4, m);
+        for (size_t r = 0; r < n; ++r) {
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+            sph::adjoint_walk_host(k, stencil, table, particles, points4, r, R2, false, fluidOnly, [&](size_t row, float dx, float dy, float dz, float r2) {
+                float e[3];
+                sph::convgrad_pair_host(bk, R2, dx, dy, dz, r2, g + row * B * C, values + r * C, e);
                 for (int a = 0; a < 3; ++a) acc[a] = acc[a] + e[a];
             });
             memcpy(outParticles + r * 3, acc, sizeof(acc));

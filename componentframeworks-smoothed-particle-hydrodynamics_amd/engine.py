@@ -768,6 +768,10 @@ _ABI = {
     "sph_aggregate_posgrad_query": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_posgrad_staged": (_int, [_vp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
     "sph_aggregate_posgrad_host": (_int, [_vp, _sz, _pp, _P(SphAggregateConfig), _vp, _sz, _vp, _vp, _vp, _vp]),
+    "sph_aggregate_basis_posgrad_particles": (_int, [_vp, _P(SphBasisConfig), _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_posgrad_query": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_posgrad_staged": (_int, [_vp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp, _vp, _P(SphAggregateInfo)]),
+    "sph_aggregate_basis_posgrad_host": (_int, [_vp, _sz, _pp, _P(SphBasisConfig), _vp, _sz, _vp, _vp, _vp, _vp]),
     # multi-GPU: z-slab decomposition
     "sph_create_slab": (_int, [_P(_vp), _vp, _vp, _sz, _pp, _int, _int, _int, _int, _sz, _vp]),
     "sph_slab_pack": (_int, [_vp, _vp, _vp, _u32, _u32, _P(_u32)]),
@@ -2176,26 +2180,88 @@ class SPHFluidGPU:
         self.sync()
         return out if device else out.cpu().numpy()
 
+    def aggregate_basis_position_grad(self, x, grad, radius=None, size=4, weight="poly6", self_=False, fluid_only=False, device: bool = False):
+        """d/dx of L = sum(grad * aggregate_basis(x, ...)) with the same arguments: (n, 3) float32 by particle id.  x (n, C) as
+        aggregate_basis(); grad (n, size^3, C) as aggregate_basis_adjoint() takes its h; numpy, or contiguous float32 torch device tensors
+        used in place and never written.  Row k sums, over k's neighbours in ascending sorted slot, the pair terms of both directions
+        with the forward's own offsets, weights and cells: no edge list, no float atomics, the same bytes on every
+        run.  The hats are differentiated piece by piece: neither their kinks nor the cutoff contribute; self_ changes no byte.
+        Streams as aggregate()."""
+        return self._basis_posgrad(None, x, grad, self._radius(radius), size, weight, self_, fluid_only, True, True, device)[1]
+
+    def query_aggregate_basis_position_grad(self, points, x, grad, radius, size=4, weight="poly6", fluid_only=False, device: bool = False,
+                                            want_points: bool = True, want_particles: bool = True):
+        """The same for query_aggregate_basis(points, x, ...): (grad_points (m, 3), grad_particles (n, 3)); grad is (m, size^3, C).
+        grad_points row i sums over the row's candidates in the forward's order, grad_particles row k over the points that accept
+        particle k in ascending (clamped cell of the point, point index).  want_points / want_particles False: that walk is not launched
+        and None stands in its place (not both)."""
+        return self._basis_posgrad(_device_points4(points, "query_aggregate_basis_position_grad"), x, grad, radius, size, weight, False, fluid_only,
+                                   want_points, want_particles, device)
+
+    def _basis_posgrad(self, dev_points, x, grad, radius, size, weight, self_, fluid_only, want_points, want_particles, device):
+        import torch
+        vals = _device_values(x, "aggregate_basis_position_grad")
+        n, c = int(vals.shape[0]), int(vals.shape[1])
+        if n != self.GetNumFluids():
+            raise SphError(f"aggregate_basis_position_grad: {n} rows of values for {self.GetNumFluids()} particles")
+        rows = n if dev_points is None else int(dev_points.shape[0])
+        if isinstance(grad, torch.Tensor) and _is_cuda_f32(grad) and grad.dim() == 3:
+            g = grad
+        else:
+            g = torch.from_numpy(_basis_planes_array(grad.detach().cpu().numpy() if isinstance(grad, torch.Tensor) else grad, rows, size,
+                                                     "aggregate_basis_position_grad")).cuda()
+        if tuple(g.shape) != (rows, _basis_planes(size), c):
+            raise SphError(f"aggregate_basis_position_grad: grad of shape {tuple(g.shape)} for {rows} rows of {_basis_planes(size)} planes and {c} channels")
+        cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+        out_pts = torch.empty((rows, 3), dtype=torch.float32, device="cuda") if dev_points is not None and want_points else None
+        out_par = torch.empty((n, 3), dtype=torch.float32, device="cuda") if want_particles else None
+        torch.cuda.current_stream().synchronize()
+        self._push_params()
+        info = SphAggregateInfo()
+        L, h, p = self._L, self._h, C.byref(cfg)
+        if dev_points is None:
+            _check(L.sph_aggregate_basis_posgrad_particles(h, p, _tensor_ptr(vals), _tensor_ptr(g), _tensor_ptr(out_par), C.byref(info)))
+        else:
+            # (an output of no rows still goes as a non-null pointer: null means "not wanted")
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if t.numel() else _NO_POINT.ctypes.data)
+            _check(L.sph_aggregate_basis_posgrad_query(h, p, _tensor_ptr(dev_points), rows, _tensor_ptr(vals), _tensor_ptr(g), ptr(out_pts), ptr(out_par),
+                                                       C.byref(info)))
+        self.sync()
+        if not device:
+            out_pts, out_par = (None if t is None else t.cpu().numpy() for t in (out_pts, out_par))
+        return out_pts, out_par
+
     def continuous_conv(self, x, filters, radius=None, weight="poly6", self_=True, fluid_only=False, normalize=False, check_state: bool = True,
-                        max_basis_bytes: int = 2 ** 31):
+                        max_basis_bytes: int = 2 ** 31, positions=None):
         """A continuous convolution (Ummenhofer et al. 2020) of the particles' features over the engine's own neighbourhoods, as a
         torch.autograd.Function: out[i] = sum_j w(r_ij) x[j] @ F(x_j - x_i), F the trilinear interpolation of filters (K, K, K, Cin, Cout)
         (axes z, y, x; K 2, 3 or 4) laid over [-radius, radius]^3.  x: a float32 torch device tensor of (n, Cin); the result is
-        (n, Cout).  Once differentiable in x and filters; the positions are the engine's state, not a tensor.  The basis sums are
+        (n, Cout).  Once differentiable in x and filters, and with positions= (the (n, 3) tensor of positions(device=True), as
+        aggregate_autograd()) in the positions too, through aggregate_basis_position_grad; without the keyword the
+        Function, the engine calls and the bytes are those of a call that does not know it.  The basis sums are
         aggregate_basis()'s, in blocks of input channels so that one basis tensor stays under max_basis_bytes (channels are
         independent: the blocking changes no basis byte), and recomputed in the backward rather than saved; their bytes are fixed.  The
         product with the filters is torch's matmul, for which no byte claim is made.  normalize divides by the sum of the weights
         (0 where it is 0).  check_state as aggregate_autograd().  See autograd.py for the formulas."""
         from .autograd import EngineAggregateBackend, continuous_conv
         return continuous_conv(EngineAggregateBackend(self), None, x, filters, self._radius(radius), weight, self_, fluid_only, normalize, check_state,
-                               max_basis_bytes)
+                               max_basis_bytes, positions=positions)
 
     def query_continuous_conv(self, points, x, filters, radius, weight="poly6", fluid_only=False, normalize=False, check_state: bool = True,
-                              max_basis_bytes: int = 2 ** 31):
-        """continuous_conv() around (m, 3) or (m, 4) query points: the result is (m, Cout)."""
+                              max_basis_bytes: int = 2 ** 31, positions=None, points_grad: bool = False):
+        """continuous_conv() around (m, 3) or (m, 4) query points: the result is (m, Cout).  points_grad=True: points must be a float32
+        torch device tensor of (m, 3) or (m, 4) and receives the points' gradient (a fourth column gets zeros)."""
+        import torch
         from .autograd import EngineAggregateBackend, continuous_conv
+        leaf = None
+        if points_grad:
+            if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or int(points.shape[1]) not in (3, 4):
+                raise SphError("query_continuous_conv: points_grad takes the query points as a float32 torch device tensor of shape (m, 3) or (m, 4)")
+            leaf = points
+            flat = points.detach()
+            points = flat.contiguous() if int(flat.shape[1]) == 4 else torch.cat([flat, torch.zeros_like(flat[:, :1])], dim=1).contiguous()
         return continuous_conv(EngineAggregateBackend(self), _device_points4(points, "query_continuous_conv"), x, filters, radius, weight, False, fluid_only,
-                               normalize, check_state, max_basis_bytes)
+                               normalize, check_state, max_basis_bytes, positions=positions, points_grad=points_grad, points_leaf=leaf)
 
     # -- iso-surface meshes (include/sph_abi.h "iso-surface") ------------------------------------
     def default_surface_lattice(self):
@@ -3278,6 +3344,27 @@ def aggregate_basis_adjoint_host(records, params, h, radius, points=None, size=4
     out = np.zeros((head[1], c), np.float32)
     _check(load_library().sph_aggregate_basis_adjoint_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(a), _ptr_or_none(out)))
     return out
+
+
+def aggregate_basis_position_grad_host(records, params, x, grad, radius, points=None, size=4, weight="poly6", self_=False, fluid_only=False,
+                                       want_points=True, want_particles=True):
+    """sph_aggregate_basis_posgrad_host: the (n, 3) result of SPHFluidGPU.aggregate_basis_position_grad (points None), or the pair
+    (grad_points (m, 3), grad_particles (n, 3)) of query_aggregate_basis_position_grad (None for an output that is not wanted), on host
+    records, x and grad, computed on the CPU by the same per-term functions in the same order: the same bytes.  No device is needed."""
+    p4 = None if points is None else _points4(points, "aggregate_basis_position_grad_host", keep_w=False)
+    rows, head = _host_args(records, params, p4, if_empty=_NO_POINT)
+    vals = _scalar_values(x, head[1])
+    c = int(vals.shape[1])
+    g = _basis_planes_array(grad, rows, size, "aggregate_basis_position_grad_host")
+    if int(g.shape[2]) != c:
+        raise SphError(f"aggregate_basis_position_grad_host: grad of shape {g.shape} for values of shape {vals.shape}")
+    cfg = _basis_cfg(radius, size, weight, c, self_, fluid_only)
+    out_pts = np.zeros((rows, 3), np.float32) if p4 is not None and want_points else None
+    out_par = np.zeros((head[1], 3), np.float32) if p4 is None or want_particles else None
+    ptr = lambda a: None if a is None else _ptr(a if len(a) else _NO_POINT)
+    _check(load_library().sph_aggregate_basis_posgrad_host(head[0], head[1], head[2], C.byref(cfg), head[3], head[4], _ptr_or_none(vals), _ptr_or_none(g),
+                                                           ptr(out_pts), ptr(out_par)))
+    return out_par if p4 is None else (out_pts, out_par)
 
 
 def aniso_lattice_host(records, params, origin, spacing, dims, **cfg):

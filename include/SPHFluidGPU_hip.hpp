@@ -492,6 +492,52 @@ public:
         out.assign(n * size_t(cfg.channels), 0.0f);
         return !Check(sph_aggregate_basis_adjoint_staged(engine, &cfg, points4, m, h.data(), out.data(), &info), "sph_aggregate_basis_adjoint_staged");
     }
+    // Position gradients of the basis sums (sph_abi.h "position gradients of the basis sums"): with
+    // L = sum devG . AggregateBasis(devValues) under cfg, devG[rows][K^3][channels], devOut[n][3] = dL/dx of the particles; for query targets
+    // devOutPoints[m][3] and devOutParticles[n][3], either of which may be null (its walk is not launched).  DEVICE memory, no
+    // synchronisation, as Aggregate.
+    bool AggregateBasisPositionGrad(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devValues, const float* devG, float* devOut) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_posgrad_particles(engine, &cfg, devValues, devG, devOut, &out), "sph_aggregate_basis_posgrad_particles");
+    }
+    bool QueryAggregateBasisPositionGrad(SphAggregateInfo& out, const SphBasisConfig& cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                         float* devOutPoints, float* devOutParticles) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        return !Check(sph_aggregate_basis_posgrad_query(engine, &cfg, devPoints4, m, devValues, devG, devOutPoints, devOutParticles, &out),
+                      "sph_aggregate_basis_posgrad_query");
+    }
+    // The same for HOST arrays (values n * channels floats, g rows * K^3 * channels): grad is sized to n * 3.  Synchronises.
+    bool AggregateBasisPositionGrad(SphAggregateInfo& info, const SphBasisConfig& cfg, const std::vector<float>& values, const std::vector<float>& g,
+                                    std::vector<float>& grad) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine);
+        if (cfg.channels < 1 || cfg.size < 2 || cfg.size > 4 || values.size() != n * size_t(cfg.channels) ||
+            g.size() != n * size_t(cfg.size * cfg.size * cfg.size) * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "AggregateBasisPositionGrad: values.size() is not n * channels or g.size() is not n * K^3 * channels");
+        grad.assign(n * 3, 0.0f);
+        return !Check(sph_aggregate_basis_posgrad_staged(engine, &cfg, nullptr, 0, values.data(), g.data(), nullptr, grad.data(), &info),
+                      "sph_aggregate_basis_posgrad_staged");
+    }
+    // points4: m * 4 floats; gradPoints is sized to m * 3 and gradParticles to n * 3.
+    bool QueryAggregateBasisPositionGrad(SphAggregateInfo& info, const SphBasisConfig& cfg, const float* points4, size_t m, const std::vector<float>& values,
+                                         const std::vector<float>& g, std::vector<float>& gradPoints, std::vector<float>& gradParticles) {
+        SphParams p = ToParams();
+        if (Check(sph_set_params(engine, &p), "sph_set_params")) return false;
+        const size_t n = sph_num_particles(engine);
+        if (!points4 || cfg.channels < 1 || cfg.size < 2 || cfg.size > 4 || values.size() != n * size_t(cfg.channels) ||
+            g.size() != m * size_t(cfg.size * cfg.size * cfg.size) * size_t(cfg.channels))
+            return !Check(SPH_ERR_ARG, "QueryAggregateBasisPositionGrad: null points, values.size() is not n * channels or g.size() is not m * K^3 * channels");
+        gradPoints.assign(m * 3 + 1, 0.0f);                            // (one spare float: the pointer of an empty result must not be null)
+        gradParticles.assign(n * 3 + 1, 0.0f);
+        const bool ok = !Check(sph_aggregate_basis_posgrad_staged(engine, &cfg, points4, m, values.data(), g.data(), gradPoints.data(), gradParticles.data(), &info),
+                               "sph_aggregate_basis_posgrad_staged");
+        gradPoints.resize(m * 3);
+        gradParticles.resize(n * 3);
+        return ok;
+    }
     // Ray casts (engine extension, sph_abi.h "ray casts"): for each of m rays of 8 floats (ox, oy, oz, tmin, dx, dy,
     // dz, tmax; t in units of the given direction) the first particle the ray enters, every particle a solid sphere of `radius` (<= 0:
     // param_h / 4; at most half a cell).  flags: SPH_RAYS_FLUID_ONLY / _ANY_HIT.  CastRays takes host rays, CastRaysDevice rays in DEVICE

@@ -66,6 +66,7 @@ extern "C" {
 /* (still 4, additions only: SPH_SLAB_FLAG_* -- names of the six bits of the z-slab exchange's flag word, values as before) */
 /* (still 4, additions only: SphBasisConfig, SPH_BASIS_GRID, sph_aggregate_basis_default / _particles / _query / _staged / _host, sph_aggregate_basis_adjoint_particles / _query / _staged / _host -- filter-grid basis sums: continuous convolutions without an edge list) */
 /* (still 4, additions only: sph_aggregate_posgrad_particles / _query / _staged / _host -- position gradients of the neighbourhood sums) */
+/* (still 4, additions only: sph_aggregate_basis_posgrad_particles / _query / _staged / _host -- position gradients of the basis sums) */
 /* (3: compact halo faces (40-byte halo copies, count-sized messages), jumps of up to 3 cell layers followed, sph_slab_clear_flags / _message_bytes / _step_times / _face_bytes, flag 16 no longer an error, SPH_OPT_NEIGHBOR_KERNEL 4) */
 /* (2: sph_slab_step_*, header validation of received halo messages, SPH_OPT_NEIGHBOR_KERNEL 3 (default), records on demand by default) */
 
@@ -1592,6 +1593,58 @@ int sph_aggregate_posgrad_staged(SphEngine* e, const SphAggregateConfig* cfg, co
 /* Host-only, no device: the same bytes.  points4 null: particle targets (outPoints is not read). */
 int sph_aggregate_posgrad_host(const SphParticle* particles, size_t n, const SphParams* params, const SphAggregateConfig* cfg, const float* points4, size_t m,
                                const float* values, const float* g, float* outPoints, float* outParticles);
+
+/* ---- position gradients of the basis sums (no reference counterpart) --------------------------------------------
+ * The basis sums of sph_aggregate_basis_* as a function of the POSITIONS: with values float32[n][C] (the forward's input) and
+ * g float32[rows][B][C] (the upstream gradient: what the forward's out would be, as the basis adjoint takes its h), the scalar is
+ * L = sum g . out, and these calls give dL/dx of the particles and, for query targets, of the query points.  Config: SphBasisConfig
+ * under the forward's rules.  A query: no result is kept, no engine state is written, nothing enters a checkpoint.
+ * The pair term.  For a target i (a particle or a query point) and a candidate j != i that the forward accepts, with the forward's own
+ * bits of d = x_j - x_i, r2 and w, every product and sum fp32 and rounded on its own (no fused multiply-add):
+ *   per axis a: the forward's u = d_a / R, g_a = (u + 1) * half, cell i_a, f = g_a - i_a, hat weights lo_a = 1 - f, hi_a = f; their slopes
+ *               are -s and +s, s = half / R (one division): the derivative of the linear piece the forward selects
+ *   corner n = 0 .. 7 (cx = n & 1, cy = (n >> 1) & 1, cz = n >> 2; plane b_n as the forward), w_a / s_a the hat weight / slope of the
+ *               corner's side of axis a:
+ *               hat_n = (w_x * w_y) * w_z   (without w)
+ *               dx_n  = (s_x * w_y) * w_z,  dy_n = (w_x * s_y) * w_z,  dz_n = (w_x * w_y) * s_z
+ *   a lane's partial sums, G = the smallest of 4, 8, 16, 32, 64 that holds C (64 for C > 64): lane l of G starts pq, px, py, pz at +0
+ *               and takes its channels c = l, l + G, .. ascending, inside a channel the corners n = 0 .. 7 ascending:
+ *               u = g[i][b_n][c] * v[j][c];  pq = pq + hat_n * u;  pa = pa + da_n * u  (a = x, y, z)
+ *               (one running sum over all the lane's channels and corners; a lane without a channel keeps +0)
+ *   then for off = 1, 2, 4, .. G / 2 every lane takes part[l] = part[l] + part[l xor off] (all lanes at once), each of the four sums on
+ *               its own.  Every lane ends with the same bits: q, p_x, p_y, p_z.
+ *   w1 = 0 for ONE;  POLY6: t = R2 - r2, w1 = -6.0f * (t * t);  f = w1 * q;  e_a = (f * d_a) + w * p_a
+ * e(i -> j) is dL/dd of that pair: it goes to x_j with + and to x_i with -.  The kink of a hat at an integer g_a and the cutoff at r = R
+ * are not differentiated (POLY6 vanishes at the cutoff; ONE jumps there, as for every fixed-radius operator).  Weight ONE still
+ * depends on the positions through the hats: there is no zeroed shortcut.
+ * Particle targets, one output grad float32[n][3] by particle id: grad[k] = sum over k's accepted candidates j != k in ascending sorted
+ * slot of (e(j -> k) - e(k -> j)), acc_a = acc_a + (eIn_a - eOut_a) from +0.  e(k -> j) uses g[k], v[j] and d; e(j -> k) uses g[j], v[k]
+ * and -d (exact), the same r2 and w, its cells and hat weights from the per-axis rule applied to -d (not mirrored from d).  Under SELF
+ * the own slot's d = x_k - x_k moves with no position and is skipped: SELF does not move a byte.
+ * Query targets, two outputs: gradPoints float32[m][3], row i = the sum over the row's accepted candidates in the forward's order,
+ * acc_a = acc_a - e_a(i -> j) from +0; gradParticles float32[n][3], row k = the sum over the rows i that accept k in the adjoint's row
+ * order (ascending (clamped cell of the point, point index)), acc_a = acc_a + e_a(i -> k), the points binned as there.  Either may be
+ * null: its walk is not launched.
+ * The forward's rules carry over: under FLUID_ONLY a ghost is neither a target nor a candidate, its rows are +0; a particle or a query
+ * point with a non-finite coordinate has +0 rows and contributes to nobody.  Every row of every output is written.
+ * No float atomics; stores are lane-owned.  The same bytes on every run, and the bytes of sph_aggregate_basis_posgrad_host, which runs
+ * the same per-term functions in the same order.
+ * Streams, the timing class (SPH_K_OTHER) and SPH_ERR_STATE (z-slab engines, SPH_OPT_GRID_BUILD 1; before any allocation) as the basis
+ * sums.  SPH_ERR_ARG: the basis sums' cases (a bad weight, flags, channels, kind, size or radius, SELF on query targets, m >= 2^31, a
+ * null argument), an output that overlaps values, g, the points or the other output as address ranges, both query outputs null.
+ * m = 0: gradParticles is zeroed.  n = 0: success, nothing is written.  SphAggregateInfo: rows = those of g (n, or m), planes = B. */
+/* Particle targets: devValues float32[n][channels], devG float32[n][B][channels], devOut float32[n][3]. */
+int sph_aggregate_basis_posgrad_particles(SphEngine* e, const SphBasisConfig* cfg, const float* devValues, const float* devG, float* devOut, SphAggregateInfo* info);
+/* devPoints4: m query points (x, y, z, .) in device memory, never written; devG float32[m][B][channels]; devOutPoints float32[m][3] or
+ * null; devOutParticles float32[n][3] or null. */
+int sph_aggregate_basis_posgrad_query(SphEngine* e, const SphBasisConfig* cfg, const float* devPoints4, size_t m, const float* devValues, const float* devG,
+                                      float* devOutPoints, float* devOutParticles, SphAggregateInfo* info);
+/* The same two calls for arrays in HOST memory (points4 null: particle targets, outPoints is not read); synchronises. */
+int sph_aggregate_basis_posgrad_staged(SphEngine* e, const SphBasisConfig* cfg, const float* points4, size_t m, const float* values, const float* g,
+                                       float* outPoints, float* outParticles, SphAggregateInfo* info);
+/* Host-only, no device: the same bytes.  points4 null: particle targets (outPoints is not read). */
+int sph_aggregate_basis_posgrad_host(const SphParticle* particles, size_t n, const SphParams* params, const SphBasisConfig* cfg, const float* points4, size_t m,
+                                     const float* values, const float* g, float* outPoints, float* outParticles);
 
 /* ---- multi-GPU: z-slab decomposition (no reference counterpart) ------------
  * One engine per rank owns the global cell layers [z0, z1) of ComputeGridExtents' grid plus one
